@@ -219,6 +219,34 @@ def median(xs):
     return ys[n // 2] if n % 2 else 0.5 * (ys[n // 2 - 1] + ys[n // 2])
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, engs, prms, n, rank=0, world=1):
+    """--dump-outputs: what the timed path computed in its last step, one .npy per array (float64), for comparing two
+    builds output for output.  Per attack in flight (axis 0): adver_audio (K, n) the adversarial audio after the step,
+    scores (K, B, S) and loss (K, B) of the step's NES batch (row 0 = the unperturbed adversarial audio), final_loss /
+    adver_loss / distance (K,).  Above DUMP_MAX_BYTES the audio is a fixed, seeded sample of its columns (adver_index).
+    With several ranks each writes under out_dir/rank<r>/."""
+    import numpy as np
+    d = out_dir if world == 1 else os.path.join(out_dir, "rank%d" % rank)
+    os.makedirs(d, exist_ok=True)
+    st = [e.bench_nes_state(p, n) for e, p in zip(engs, prms)]
+    arrs = {"adver_audio": np.stack([x["adver"] for x in st]), "scores": np.stack([x["scores"] for x in st]),
+            "loss": np.stack([x["loss"] for x in st])}
+    for k in ("final_loss", "adver_loss", "distance"):
+        arrs[k] = np.array([x[k] for x in st], np.float64)
+    rest = sum(a.nbytes for k, a in arrs.items() if k != "adver_audio") + 4096   # (+ the .npy headers)
+    if arrs["adver_audio"].nbytes + rest > DUMP_MAX_BYTES:
+        keep = max(1, (DUMP_MAX_BYTES - rest) // (8 * (len(st) + 1)))     # the audio columns and their indices
+        idx = np.sort(np.random.RandomState(0).choice(n, size=min(n, keep), replace=False))
+        arrs["adver_audio"] = np.ascontiguousarray(arrs["adver_audio"][:, idx])
+        arrs["adver_index"] = idx.astype(np.float64)
+    for k, a in arrs.items():
+        np.save(os.path.join(d, k + ".npy"), a)
+    return d
+
+
 def iv_rooflines(B, n_active, con_ms, solve_ms, R=400):
     """(contraction, solve) roofline objects of an i-vector NES batch of B utterances: the T-matrix contraction against
     HBM (and its float64-MFMA utilisation), the posterior solve against the float64 MFMA peak."""
@@ -306,6 +334,8 @@ def bench_ivector(args, torch):
     con_acc = []
     dts = timed_region(args, torch, dist, workers, K, after_window=lambda: con_acc.append(sum(r[1] for r in res) / K))
     dt = median(dts)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, engs, prms, N_SAMPLES, rank, world)
     ms_con = sum(con_acc) / len(con_acc)
     rows = res[0][2]
     total_steps = args.steps * K
@@ -579,7 +609,14 @@ def main():
                          "the exact integer energy), f64 = float64 between Kaldi's float32 storage points (k_mfcc_r16)")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise the process group even with one rank (exercises RCCL on a 1-GPU box)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step (adversarial audio, "
+                         "scores, losses of every attack in flight) as DIR/<name>.npy (float64, at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if args.dump_outputs and args.e2e_only:
+        raise SystemExit("--dump-outputs writes the outputs of the timed steps; --e2e-only has none")
     self_launch(args)
 
     import torch  # device sync + torch.distributed (RCCL); imported before the HIP library
@@ -658,6 +695,8 @@ def main():
     acc = []
     dts = timed_region(args, torch, dist, aset.workers, K, after_window=lambda: acc.append((list(aset.results), list(aset.windows))))
     dt = median(dts)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, engs, prms, N_SAMPLES, rank, world)
     results, windows = acc[dts.index(sorted(dts)[len(dts) // 2])]   # the per-attack view of a median window
     ms_dev = sum(sum(r[0] for r in rs) for rs, _ in acc) / K / len(acc)
     ms_gmm = sum(sum(r[1] for r in rs) for rs, _ in acc) / K / len(acc)   # per attack and window: sum over its timed launches

@@ -2784,3 +2784,26 @@ extern "C" int fb_bench_nes(fb_engine *e, const fb_nes_params *p, const double *
   if (voiced_rows) *voiced_rows = vrows;
   return FB_OK;
 }
+
+extern "C" int fb_bench_nes_state(fb_engine *e, double *adver, double *scores, double *loss, double *summary) {
+  if (!e) return fb_fail(FB_E_ARG, "null engine");
+  if (e->bench_it < 0) return fb_fail(FB_E_STATE, "fb_bench_nes_state: no attack is resident on the engine");
+  HIPCHK(hipSetDevice(e->device));
+  const int64_t N = e->bench_N;
+  const int B = e->bench_B, S = fb_num_speakers(e);
+  const size_t n_adv = sizeof(double) * (size_t)N, n_sc = sizeof(double) * (size_t)B * (S > 0 ? S : 1),
+               n_loss = sizeof(double) * (size_t)B;
+  if (n_adv > e->adver.cap || n_sc > e->scores.cap || n_loss > e->loss.cap || !e->nes_out.p)
+    return fb_fail(FB_E_STATE, "fb_bench_nes_state: the resident attack's buffers no longer match the loaded system");
+  if (adver) FBCHK(d2h(e, adver, e->adver.p, n_adv));
+  if (scores) FBCHK(d2h(e, scores, e->scores.p, n_sc));
+  if (loss) FBCHK(d2h(e, loss, e->loss.p, n_loss));
+  HIPCHK(hipMemcpyAsync(e->h_out, e->nes_out.p, sizeof(FbNesDev), hipMemcpyDeviceToHost, e->stream));
+  FBCHK(sync_stream(e));
+  if (summary) {
+    summary[0] = e->h_out->final_loss;
+    summary[1] = e->h_out->adver_loss;
+    summary[2] = e->h_out->distance;
+  }
+  return FB_OK;
+}

@@ -405,3 +405,15 @@ class Engine(object):
                                      C.c_int(warmup), C.c_int(iters), C.c_int(int(time_gmm)),
                                      C.byref(ms), C.byref(msg), C.byref(rows)))
         return ms.value, msg.value, rows.value
+
+    def bench_nes_state(self, params, n):
+        """What the attack bench_nes left on the device holds after its last iteration (fb_bench_nes_state): a dict of
+        adver (n,) the adversarial audio, scores (B, S) and loss (B,) of the last NES batch (row 0 = the unperturbed
+        adversarial audio), final_loss, adver_loss, distance.  `params` / `n`: those of the bench_nes calls."""
+        B = 2 * (params.samples_per_draw // 2) + 1
+        adver = np.empty(int(n), np.float64)
+        scores = np.empty((B, max(self.n_speakers, 1)), np.float64)
+        loss = np.empty(B, np.float64)
+        summary = np.empty(3, np.float64)
+        N.check(self._L.fb_bench_nes_state(self._h, N.ptr(adver), N.ptr(scores), N.ptr(loss), N.ptr(summary)))
+        return dict(adver=adver, scores=scores, loss=loss, final_loss=summary[0], adver_loss=summary[1], distance=summary[2])

@@ -72,6 +72,11 @@ int fb_bench_gmm_kernel(fb_engine *e, int reps, double *ms_avg, int64_t *rows);
 int fb_bench_nes(fb_engine *e, const fb_nes_params *p, const double *audio,
                  int64_t N, int warmup, int iters, int time_gmm,
                  double *ms_total, double *ms_gmm, int64_t *voiced_rows);
+/* read back the attack fb_bench_nes left on the device (read only; it can be continued afterwards):
+ * adver[N] the adversarial audio after the last update, scores[B*S] and loss[B] of the last NES batch
+ * (row 0 = the unperturbed adversarial audio), summary[3] = {final_loss, adver_loss, distance} of that
+ * iteration.  Any output may be NULL. */
+int fb_bench_nes_state(fb_engine *e, double *adver, double *scores, double *loss, double *summary);
 
 #ifdef __cplusplus
 }
