@@ -1874,6 +1874,7 @@ extern "C" int fb_debug_iv_gselect(fb_engine *e, int *sel, int64_t sel_cap, int6
   info[0] = e->gs_last_path;   // 0: dump + k_iv_select, 1: k_gmm_fx2_sel (lists of survivors), 2: k_gsel_w (records of groups)
   info[1] = info[2] = info[3] = 0;
   info[4] = rows;
+  info[5] = n_chunks;
   if (info[0]) {
     int flag = 0;
     HIPCHK(hipMemcpy(&flag, e->gs_flag.p, sizeof(int), hipMemcpyDeviceToHost));

@@ -516,11 +516,23 @@ int fb_gsel_cap(int n_chunks) {
 // component chunks of the selection kernels: the dump's count brought down to a power of two <= 8 (the lists of a row
 // are n_chunks x cap <= FB_GSEL_MAXC entries)
 int fb_gsel_chunks(int n_chunks) { return n_chunks >= 8 ? 8 : (n_chunks >= 4 ? 4 : (n_chunks >= 2 ? 2 : 1)); }
+// dynamic LDS of k_gmm_fx2_sel: the two item images it double-buffers, then pass A's group maxima of every tile of its chunk
+// ([tiles_per_chunk][256] floats) or pass B's survivor lists (128 counts, [128][cap] keys).  One component chunk (a batch of
+// more than 32 768 frames) at C = 2048 asks 16 KB + 64 KB at NK = 4: above the 64 KB default, so the launch opts in.
+#define FB_GSEL_LDS_MAX (160 * 1024)   // the opt-in (the LDS of an MI355X compute unit)
+static size_t fb_gsel_lds_a(int NK, int tpc) { return (size_t)2 * 2 * NK * 64 * 16 + sizeof(float) * 256 * (size_t)tpc; }
+static size_t fb_gsel_lds_b(int NK, int cap) {
+  return (size_t)2 * 2 * NK * 64 * 16 + sizeof(int) * 128 + sizeof(unsigned long long) * 128 * (size_t)cap;
+}
 bool fb_gsel_applies(const FbGmmDev &g, int nsel, int n_chunks) {
   // (few groups: tau would be -inf and every component a survivor -- the dump is the right tool for small models)
   const bool off = getenv("FB_IV_GSEL_DUMP") != nullptr;   // A/B and tests: the dump + k_iv_select path (read per batch)
-  return !off && g.mode == FB_GMM_MODE_FX2 && g.M == 1 && g.n_items == 2 && 2 * g.n_tiles >= 4 * nsel && 2 * g.n_tiles <= 256 &&
-         fb_gsel_cap(n_chunks) > 0 && nsel <= 32;
+  if (off || !(g.mode == FB_GMM_MODE_FX2 && g.M == 1 && g.n_items == 2 && 2 * g.n_tiles >= 4 * nsel && 2 * g.n_tiles <= 256 &&
+               fb_gsel_cap(n_chunks) > 0 && nsel <= 32))
+    return false;
+  // a shape whose passes would not fit the opted-in LDS takes the dump path (n_tiles <= 128, NK <= 6: at most 152 KB)
+  const int tpc = (g.n_tiles + n_chunks - 1) / n_chunks;
+  return fb_gsel_lds_a(g.NKF, tpc) <= FB_GSEL_LDS_MAX && fb_gsel_lds_b(g.NKF, fb_gsel_cap(n_chunks)) <= FB_GSEL_LDS_MAX;
 }
 __device__ __forceinline__ unsigned fb_f32_ordered(float v) {  // monotone map float -> unsigned (total order of the values)
   const unsigned u = __float_as_uint(v);
@@ -719,14 +731,21 @@ static void launch_gsel_t(hipStream_t s, const FbGmmDev &g, const float *feats, 
     grid = dim3((unsigned)(8 * ((strips + per - 1) / per)), 1);
     xcd_map = n_chunks;
   }
-  const size_t img = (size_t)2 * 2 * NK * 64 * 16;
-  hipLaunchKernelGGL((k_gmm_fx2_sel<NK, false>), grid, dim3(256), img + sizeof(float) * 256 * (size_t)tpc, s, g, feats, n_rows_ptr, tpc,
+  const size_t lds_a = fb_gsel_lds_a(NK, tpc), lds_b = fb_gsel_lds_b(NK, cap);
+  static std::atomic<unsigned long long> optin{0};   // per instantiation, one bit per device
+  unsigned long long bit = 0;
+  if ((lds_a > 64 * 1024 || lds_b > 64 * 1024) && fb_device_needs_optin(optin, &bit)) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_gmm_fx2_sel<NK, false>), hipFuncAttributeMaxDynamicSharedMemorySize, FB_GSEL_LDS_MAX) == hipSuccess &&
+        hipFuncSetAttribute(reinterpret_cast<const void *>(k_gmm_fx2_sel<NK, true>), hipFuncAttributeMaxDynamicSharedMemorySize, FB_GSEL_LDS_MAX) == hipSuccess)
+      optin.fetch_or(bit, std::memory_order_release);
+  }
+  hipLaunchKernelGGL((k_gmm_fx2_sel<NK, false>), grid, dim3(256), lds_a, s, g, feats, n_rows_ptr, tpc,
                      n_chunks, gmax, nullptr, cap, nullptr, nullptr, xcd_map);
   const int NG = 2 * g.n_tiles, tb = (rows_cap + 15) / 16;
   if (NG <= 64) hipLaunchKernelGGL(k_gsel_tau<4>, dim3(tb), dim3(256), 0, s, gmax, NG, n_rows_ptr, nsel, tau, flag);
   else if (NG <= 128) hipLaunchKernelGGL(k_gsel_tau<8>, dim3(tb), dim3(256), 0, s, gmax, NG, n_rows_ptr, nsel, tau, flag);
   else hipLaunchKernelGGL(k_gsel_tau<16>, dim3(tb), dim3(256), 0, s, gmax, NG, n_rows_ptr, nsel, tau, flag);
-  hipLaunchKernelGGL((k_gmm_fx2_sel<NK, true>), grid, dim3(256), img + sizeof(int) * 128 + sizeof(unsigned long long) * 128 * (size_t)cap, s, g,
+  hipLaunchKernelGGL((k_gmm_fx2_sel<NK, true>), grid, dim3(256), lds_b, s, g,
                      feats, n_rows_ptr, tpc, n_chunks, nullptr, tau, cap, glist, gcnt, xcd_map);
   hipLaunchKernelGGL(k_gsel_final, dim3(tb), dim3(256), 0, s, glist, gcnt, n_chunks, cap, n_rows_ptr, nsel, g.C, sel, flag);
 }

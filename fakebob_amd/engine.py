@@ -175,13 +175,13 @@ class Engine(object):
 
     def debug_iv_gselect(self, rows_cap=None):
         """(sel[rows][num_gselect], info dict) of the last i-vector batch -- fb_debug_iv_gselect."""
-        info = (C.c_int64 * 5)()
+        info = (C.c_int64 * 6)()
         N.check(self._L.fb_debug_iv_gselect(self._h, None, C.c_int64(0), info))
         rows, nsel = int(info[4]), int(self._iv_nsel)
         sel = np.empty((rows, nsel), np.int32)
         N.check(self._L.fb_debug_iv_gselect(self._h, N.ptr(sel), C.c_int64(sel.size), info))
         return sel, dict(threshold_path=bool(info[0]), path=int(info[0]), overflow=int(info[1]), max_list=int(info[2]),
-                         survivors=int(info[3]), rows=rows)
+                         survivors=int(info[3]), rows=rows, chunks=int(info[5]))
 
     def set_system(self, task, z_mean=None, z_std=None):
         zm = None if z_mean is None else np.ascontiguousarray(z_mean, np.float64)
