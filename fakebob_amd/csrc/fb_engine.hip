@@ -138,6 +138,8 @@ struct fb_engine {
   std::vector<int64_t> h_wav_off;
   std::vector<int> h_frame_off, h_chunk_off;
   bool any_long = false;  // some utterance has T > cmn_window
+  int route[5] = {};      // fb_debug_frontend_route: what the last batch's front end ran
+  bool have_route = false;  // ... once a batch has reached the MFCC launch
   int cached_B = -1;
   int64_t cached_N = -1;
   int last_total_frames = 0, last_B = 0, last_chunks = 1;
@@ -287,6 +289,10 @@ extern "C" int fb_set_frontend(fb_engine *e, const fb_frontend_cfg *c) {
     return fb_fail(FB_E_ARG, "bad mel/ceps/shift configuration");
   if (c->delta_order < 0 || c->delta_order > 4 || c->delta_window <= 0 || c->delta_window > 8)
     return fb_fail(FB_E_ARG, "bad delta options");
+  // a CMVN window of no frames divides by zero in k_cmvn_sliding (NaN features, scored as they were); a negative VAD
+  // context is no window at all
+  if (c->cmn_window < 1) return fb_fail(FB_E_ARG, "cmn_window %d < 1", c->cmn_window);
+  if (c->vad_frames_context < 0) return fb_fail(FB_E_ARG, "vad_frames_context %d < 0", c->vad_frames_context);
   const int dim = nc * (c->delta_order + 1);
   if (dim > 256) return fb_fail(FB_E_ARG, "feature dim %d > 256 unsupported", dim);
   HIPCHK(hipSetDevice(e->device));
@@ -318,8 +324,11 @@ extern "C" int fb_set_frontend(fb_engine *e, const fb_frontend_cfg *c) {
           wts.push_back((double)(float)wv);
         }
       }
-      mel_first[b] = first < 0 ? 0 : first;
-      mel_len[b] = first < 0 ? 0 : last - first + 1;
+      // [EXT] Kaldi's MelBanks refuses a bin that takes no FFT bin ("You may have set --num-mel-bins too large"): its
+      // log-energy would be the constant log(FLT_EPSILON)
+      if (first < 0) return fb_fail(FB_E_ARG, "mel bin %d covers no FFT bin (num_mel_bins %d too large)", b, nb);
+      mel_first[b] = first;
+      mel_len[b] = last - first + 1;
       mel_off[b] = (int)mel_w.size();
       mel_w.insert(mel_w.end(), wts.begin(), wts.end());
     }
@@ -1190,10 +1199,27 @@ static bool fb_iv_use_rw(const fb_engine *e) {
   if (ev && strcmp(ev, "ll") == 0) return false;
   return e->fuse_opt == 1;
 }
+// MFCC of every frame of the batch prepared in e->wav: k_mfcc_f32 when the configuration asks for it, else k_mfcc_r16 / k_mfcc
+static void launch_mfcc(fb_engine *e, int B, int total_frames) {
+  const FbFrontendDev &fe = e->fe;
+  hipStream_t s = e->stream;
+  e->have_route = true;
+  e->route[3] = e->t_max;
+  e->route[4] = B;
+  if (fe.mfcc_f32 && fb_launch_mfcc_f32(s, fe, e->melw_n, e->wav.as<int16_t>(), e->frame_rec.as<int32_t>(), total_frames,
+                                        e->mfcc.as<float>(), e->uni_T, e->uni_n, e->h_wav_off[0]))
+    e->route[0] = fe.L / 32 >= 12 ? FB_ROUTE_MFCC_F32_12 : FB_ROUTE_MFCC_F32_0;  // (fb_launch_mfcc_f32's instantiation rule)
+  else
+    e->route[0] = fb_launch_mfcc(s, fe, e->melw_n, e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), e->frame_off.as<int>(),
+                                 e->frame_rec.as<int32_t>(), B, total_frames, e->mfcc.as<float>());
+}
+
 // mfcc -> VAD (+ row offsets) -> deltas -> CMVN -> voiced-row compaction
 static int run_post_mfcc(fb_engine *e, int B) {
   const FbFrontendDev &fe = e->fe;
   hipStream_t s = e->stream;
+  e->route[1] = FB_ROUTE_NONE;  // (until a chain is enqueued: a call that fails on the way reports none)
+  e->route[2] = FB_ROUTE_NONE;
   if (!e->vad_counter.p) {
     FBCHK(e->vad_counter.ensure(sizeof(int)));
     HIPCHK(hipMemsetAsync(e->vad_counter.p, 0, sizeof(int), s));
@@ -1206,7 +1232,7 @@ static int run_post_mfcc(fb_engine *e, int B) {
   //  buffers swap roles: e->mfcc is the matrix the later stages and fb_debug_mfcc read)
   auto compress = [&]() -> int {
     FBCHK(e->mfcc_cm.ensure(sizeof(float) * (size_t)e->h_frame_off[B] * fe.nc));
-    fb_launch_feat_compress(s, fe, e->mfcc.as<float>(), e->mfcc_cm.as<float>(), e->frame_off.as<int>(), B, e->t_max);
+    e->route[2] = fb_launch_feat_compress(s, fe, e->mfcc.as<float>(), e->mfcc_cm.as<float>(), e->frame_off.as<int>(), B, e->t_max);
     std::swap(e->mfcc, e->mfcc_cm);
     return FB_OK;
   };
@@ -1233,12 +1259,15 @@ static int run_post_mfcc(fb_engine *e, int B) {
                                    e->fuse_opt != 0)) {
       e->vad_epoch += 1;
       e->vad_p_launches += 1;
+      e->route[1] = FB_ROUTE_CHAIN_SPLIT;
       return FB_OK;
     }
     if (fb_fuse_part(e, 0) && fb_launch_vad_delta_cmvn(s, fe, e->mfcc.as<float>(), e->frame_off.as<int>(), B, e->t_max, e->vad_epoch + 1,
                                              e->vad_counter.as<int>(), e->vad_pub.as<unsigned long long>(), e->tv.as<int>(),
                                              e->row_off.as<int>(), e->feats.as<float>(), cm_fused ? e->mfcc.as<float>() : nullptr)) {
       e->vad_epoch += 1;
+      e->route[1] = FB_ROUTE_CHAIN_WHOLE;
+      if (cm_fused) e->route[2] = FB_ROUTE_CM_FUSED;
       return FB_OK;
     }
     if (cm_fused) FBCHK(compress());  // (the batch did not qualify)
@@ -1246,8 +1275,10 @@ static int run_post_mfcc(fb_engine *e, int B) {
   fb_launch_vad(s, fe, e->mfcc.as<float>(), e->frame_off.as<int>(), B, e->vrank.as<int>(), e->tv.as<int>(),
                 e->vad_counter.as<int>(), e->row_off.as<int>());
   if (fb_launch_delta_cmvn(s, fe, e->mfcc.as<float>(), e->frame_off.as<int>(), e->vrank.as<int>(),
-                           e->row_off.as<int>(), B, e->t_max, e->feats.as<float>()))
+                           e->row_off.as<int>(), B, e->t_max, e->feats.as<float>())) {
+    e->route[1] = FB_ROUTE_CHAIN_VAD_DC;
     return FB_OK;
+  }
   const int total_frames = e->h_frame_off[B], total_chunks = e->h_chunk_off[B];
   FBCHK(e->dfeat.ensure(sizeof(float) * (size_t)total_frames * fe.dim));
   FBCHK(e->chunk_sum.ensure(sizeof(double) * (size_t)total_chunks * fe.dim));
@@ -1256,6 +1287,7 @@ static int run_post_mfcc(fb_engine *e, int B) {
   fb_launch_cmvn(s, fe, e->dfeat.as<float>(), e->frame_off.as<int>(), e->chunk_off.as<int>(),
                  e->chunk_sum.as<double>(), e->vrank.as<int>(), e->row_off.as<int>(), B, total_chunks, e->any_long,
                  e->feats.as<float>());
+  e->route[1] = e->any_long ? FB_ROUTE_CHAIN_SLIDING : FB_ROUTE_CHAIN_SEPARATE;
   return FB_OK;
 }
 
@@ -1279,9 +1311,7 @@ static int run_scoring(fb_engine *e, int B, int total_frames) {
     const char *cv = getenv("FB_MFCC_CUS");
     e->fe.mfcc_cus = cv ? atoi(cv) : (e->fuse_opt == 0 ? 128 : 0);
   }
-  if (!(fe.mfcc_f32 && fb_launch_mfcc_f32(s, fe, e->melw_n, e->wav.as<int16_t>(), e->frame_rec.as<int32_t>(), total_frames, e->mfcc.as<float>(), e->uni_T, e->uni_n, e->h_wav_off[0])))
-    fb_launch_mfcc(s, fe, e->melw_n, e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), e->frame_off.as<int>(),
-                   e->frame_rec.as<int32_t>(), B, total_frames, e->mfcc.as<float>());
+  launch_mfcc(e, B, total_frames);
   FBCHK(run_post_mfcc(e, B));
   if (e->kind == 0) {
     // A GPU shared by three or more attacks (fb_set_fused_chain(e, 0)): k_gmm_fx2w takes a whole compute unit per workgroup (one
@@ -1850,6 +1880,14 @@ extern "C" int fb_debug_iv_active(fb_engine *e, int *n_active) {
   HIPCHK(hipSetDevice(e->device));
   FBCHK(sync_stream(e));
   HIPCHK(hipMemcpy(n_active, e->iv_active.as<int>() + e->iv.C, sizeof(int), hipMemcpyDeviceToHost));
+  return FB_OK;
+}
+
+// the kernels the front end of the last batch ran (launch_mfcc / run_post_mfcc record them as they enqueue)
+extern "C" int fb_debug_frontend_route(fb_engine *e, int *info) {
+  if (!e || !info) return fb_fail(FB_E_ARG, "null argument");
+  if (!e->have_route) return fb_fail(FB_E_STATE, "no batch has run the front end yet");
+  for (int i = 0; i < 5; ++i) info[i] = e->route[i];
   return FB_OK;
 }
 
@@ -2560,10 +2598,7 @@ static int debug_frontend(fb_engine *e, const int16_t *wav, int64_t n) {
   FBCHK(e->tv.ensure(sizeof(int)));
   FBCHK(e->row_off.ensure(sizeof(int) * 2));
   FBCHK(e->feats.ensure(sizeof(float) * (size_t)T * fe.dim));
-  hipStream_t s = e->stream;
-  if (!(fe.mfcc_f32 && fb_launch_mfcc_f32(s, fe, e->melw_n, e->wav.as<int16_t>(), e->frame_rec.as<int32_t>(), T, e->mfcc.as<float>(), e->uni_T, e->uni_n, e->h_wav_off[0])))
-    fb_launch_mfcc(s, fe, e->melw_n, e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), e->frame_off.as<int>(),
-                   e->frame_rec.as<int32_t>(), 1, T, e->mfcc.as<float>());
+  launch_mfcc(e, 1, T);
   FBCHK(run_post_mfcc(e, 1));
   HIPCHK(hipGetLastError());
   return FB_OK;

@@ -116,8 +116,9 @@ void fb_launch_grad_update(hipStream_t s, const double *loss, int64_t N, int hal
 // ---- front-end ------------------------------------------------------------
 // MFCC of every frame of a (ragged) batch.  wav_off[B+1], frame_off[B+1] device arrays.
 // frame_rec: [total_frames][4] int32 = {absolute start sample (int64 in two words), start within the
-// utterance, utterance length} (used by the P = 512 kernel instead of a search in frame_off)
-void fb_launch_mfcc(hipStream_t s, const FbFrontendDev &fe, int melw_n, const int16_t *wav,
+// utterance, utterance length} (used by the P = 512 kernel instead of a search in frame_off).  Returns the kernel it
+// launched: FB_ROUTE_MFCC_R16_* or FB_ROUTE_MFCC_GENERIC (fb_debug_frontend_route)
+int fb_launch_mfcc(hipStream_t s, const FbFrontendDev &fe, int melw_n, const int16_t *wav,
                     const int64_t *wav_off, const int *frame_off, const int32_t *frame_rec, int B,
                     int total_frames, float *mfcc);
 // fb_frontend_cfg.mfcc_f32: the float32 kernel (frontend_f32_kernels.hip); false = this configuration is not one it takes
@@ -136,8 +137,9 @@ bool fb_launch_mfcc_f32(hipStream_t s, const FbFrontendDev &fe, int melw_n, cons
 // counter: one device int, zero before the first launch (the kernel leaves it at zero); row_off[B+1]
 // = exclusive scan of max(tv, 0), written by the workgroup that finishes last
 // Kaldi CompressedMatrix round trip of every utterance's MFCC matrix, in place (t_max: longest utterance, frames)
-void fb_launch_feat_compress(hipStream_t s, const FbFrontendDev &fe, const float *mfcc, float *out, const int *frame_off, int B,
-                             int t_max);  // out != mfcc: every workgroup reads the whole input matrix
+// returns FB_ROUTE_CM_REGS, _LDS or _GLOBAL: where the longest column's sort keys are kept
+int fb_launch_feat_compress(hipStream_t s, const FbFrontendDev &fe, const float *mfcc, float *out, const int *frame_off, int B,
+                            int t_max);  // out != mfcc: every workgroup reads the whole input matrix
 void fb_launch_vad(hipStream_t s, const FbFrontendDev &fe, const float *mfcc, const int *frame_off, int B,
                    int *vrank, int *tv, int *counter, int *row_off);
 // row_off[b] = sum_{b'<b} tv[b'] ; row_off[B] = total

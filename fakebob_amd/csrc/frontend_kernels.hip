@@ -530,10 +530,10 @@ int fb_mfcc_layout_doubles(int P, int L, int nb, int nc, int melw_n) {
   return lo.wave0 + 4 * lo.per_wave;
 }
 
-void fb_launch_mfcc(hipStream_t s, const FbFrontendDev &fe, int melw_n, const int16_t *wav,
-                    const int64_t *wav_off, const int *frame_off, const int32_t *frame_rec, int B,
-                    int total_frames, float *mfcc) {
-  if (total_frames <= 0) return;
+int fb_launch_mfcc(hipStream_t s, const FbFrontendDev &fe, int melw_n, const int16_t *wav,
+                   const int64_t *wav_off, const int *frame_off, const int32_t *frame_rec, int B,
+                   int total_frames, float *mfcc) {
+  if (total_frames <= 0) return FB_ROUTE_NONE;
   if (fe.P == 512 && fe.nb <= 31 && fe.nc <= 32 && (fe.L & 1) == 0 && fe.L >= 2) {
     const MfccR4Lds l16 = fb_mfcc_r4_layout(fe.L, fe.nb, fe.nc, melw_n);
     const size_t shm16 = sizeof(double) * (size_t)l16.wave0 + sizeof(double2) * (size_t)FB_R16_WAVES * 4 * FB_R16_SLOTS;
@@ -558,7 +558,8 @@ void fb_launch_mfcc(hipStream_t s, const FbFrontendDev &fe, int melw_n, const in
       else if (full12) hipLaunchKernelGGL((k_mfcc_r16<12, false>), grid, blk, shm16, s, fe, melw_n, wav, rec, total_frames, mfcc);
       else if (fe.raw_energy) hipLaunchKernelGGL((k_mfcc_r16<0, true>), grid, blk, shm16, s, fe, melw_n, wav, rec, total_frames, mfcc);
       else hipLaunchKernelGGL((k_mfcc_r16<0, false>), grid, blk, shm16, s, fe, melw_n, wav, rec, total_frames, mfcc);
-      return;
+      return full12 ? (fe.raw_energy ? FB_ROUTE_MFCC_R16_12_RAW : FB_ROUTE_MFCC_R16_12)
+                    : (fe.raw_energy ? FB_ROUTE_MFCC_R16_0_RAW : FB_ROUTE_MFCC_R16_0);
     }
   }
   const MfccLds lo = fb_mfcc_layout(fe.P, fe.L, fe.nb, fe.nc, melw_n);
@@ -567,6 +568,7 @@ void fb_launch_mfcc(hipStream_t s, const FbFrontendDev &fe, int melw_n, const in
   if (blocks > 768) blocks = 768;
   hipLaunchKernelGGL(k_mfcc, dim3(blocks), dim3(256), shm, s, fe, melw_n, wav, wav_off, frame_off, B,
                      total_frames, mfcc);
+  return FB_ROUTE_MFCC_GENERIC;
 }
 
 // -------------------------------------------------------------------- VAD
@@ -854,11 +856,12 @@ __global__ __launch_bounds__(256) void k_feat_compress(const float *__restrict__
     }
   }
 }
-void fb_launch_feat_compress(hipStream_t s, const FbFrontendDev &fe, const float *mfcc, float *out, const int *frame_off, int B,
-                             int t_max) {
+int fb_launch_feat_compress(hipStream_t s, const FbFrontendDev &fe, const float *mfcc, float *out, const int *frame_off, int B,
+                            int t_max) {
   const int cap = t_max <= 64 * FB_CM_REG ? 1 : std::min(t_max, 3840);  // keys per wave in LDS (4 x 15 KB: no opt-in needed)
   hipLaunchKernelGGL(k_feat_compress, dim3(B, (fe.nc + 3) / 4), dim3(256), sizeof(unsigned) * 4 * (size_t)cap, s, mfcc,
                      out, frame_off, fe.nc, cap);
+  return t_max <= 64 * FB_CM_REG ? FB_ROUTE_CM_REGS : (t_max <= 3840 ? FB_ROUTE_CM_LDS : FB_ROUTE_CM_GLOBAL);
 }
 
 // ------------------------------------------------------------------ deltas

@@ -183,6 +183,21 @@ class Engine(object):
         return sel, dict(threshold_path=bool(info[0]), path=int(info[0]), overflow=int(info[1]), max_list=int(info[2]),
                          survivors=int(info[3]), rows=rows, chunks=int(info[5]))
 
+    # fb_debug_frontend_route's codes (include/fakebob_hip_test.h: FB_ROUTE_*)
+    _ROUTE_MFCC = {0: None, 1: "k_mfcc_f32<12>", 2: "k_mfcc_f32<0>", 3: "k_mfcc_r16<12,true>", 4: "k_mfcc_r16<12,false>",
+                   5: "k_mfcc_r16<0,true>", 6: "k_mfcc_r16<0,false>", 7: "k_mfcc"}
+    _ROUTE_CHAIN = {0: None, 1: "split", 2: "whole", 3: "vad+delta_cmvn", 4: "separate", 5: "separate+sliding"}
+    _ROUTE_CM = {0: None, 1: "fused", 2: "registers", 3: "lds", 4: "global"}
+
+    def debug_frontend_route(self):
+        """What the front end of the last batch ran (fb_debug_frontend_route): a dict of mfcc (the kernel), chain (the
+        VAD / deltas / CMVN launches), compress (where the CompressedMatrix round trip ran, None when it is off), t_max
+        (the longest utterance, frames) and B."""
+        info = (C.c_int * 5)()
+        N.check(self._L.fb_debug_frontend_route(self._h, info))
+        return dict(mfcc=self._ROUTE_MFCC[info[0]], chain=self._ROUTE_CHAIN[info[1]], compress=self._ROUTE_CM[info[2]],
+                    t_max=int(info[3]), B=int(info[4]))
+
     def set_system(self, task, z_mean=None, z_std=None):
         zm = None if z_mean is None else np.ascontiguousarray(z_mean, np.float64)
         zs = None if z_std is None else np.ascontiguousarray(z_std, np.float64)

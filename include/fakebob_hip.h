@@ -128,6 +128,8 @@ int fb_engine_create(int device, fb_engine **out);
 int fb_engine_destroy(fb_engine *e);
 
 void fb_default_frontend(fb_frontend_cfg *cfg);
+/* FB_E_ARG, the previous configuration kept, for options that describe no front end: besides the shapes the kernels do
+ * not take, cmn_window < 1, vad_frames_context < 0 and a mel bin that covers no FFT bin. */
 int fb_set_frontend(fb_engine *e, const fb_frontend_cfg *cfg);
 
 /* Diagonal GMMs in Kaldi DiagGmm internal form (float32): gconsts[M*C],

@@ -25,6 +25,33 @@ int fb_debug_mfcc(fb_engine *e, const int16_t *wav, int64_t n, float *mfcc, int 
 int fb_debug_feats(fb_engine *e, const int16_t *wav, int64_t n, float *feats,
                    int *Tv, int *T);
 
+/* What the front end of the last batch ran (fb_score_*, fb_get_grad, an NES iteration, fb_debug_mfcc / _feats, enrolment
+ * statistics): info[5] = {the MFCC kernel, the chain after it, where the CompressedMatrix round trip ran, the longest
+ * utterance of the batch in frames, the batch size}.  Recorded on the host when the kernels are enqueued; read only.
+ * An entry is FB_ROUTE_NONE when that stage launched nothing (a call that failed before its chain was enqueued reports
+ * no chain).  FB_E_STATE before the first batch. */
+int fb_debug_frontend_route(fb_engine *e, int *info);
+/* info[0] */
+#define FB_ROUTE_NONE 0
+#define FB_ROUTE_MFCC_F32_12 1       /* k_mfcc_f32<12> */
+#define FB_ROUTE_MFCC_F32_0 2        /* k_mfcc_f32<0> */
+#define FB_ROUTE_MFCC_R16_12_RAW 3   /* k_mfcc_r16<12, true> */
+#define FB_ROUTE_MFCC_R16_12 4       /* k_mfcc_r16<12, false> */
+#define FB_ROUTE_MFCC_R16_0_RAW 5    /* k_mfcc_r16<0, true> */
+#define FB_ROUTE_MFCC_R16_0 6        /* k_mfcc_r16<0, false> */
+#define FB_ROUTE_MFCC_GENERIC 7      /* k_mfcc */
+/* info[1] */
+#define FB_ROUTE_CHAIN_SPLIT 1       /* k_vad_delta_cmvn_p: an utterance over four workgroups */
+#define FB_ROUTE_CHAIN_WHOLE 2       /* k_vad_delta_cmvn: one workgroup per utterance */
+#define FB_ROUTE_CHAIN_VAD_DC 3      /* k_vad, then k_delta_cmvn */
+#define FB_ROUTE_CHAIN_SEPARATE 4    /* k_vad, k_deltas, k_cmvn (whole-utterance mean) */
+#define FB_ROUTE_CHAIN_SLIDING 5     /* k_vad, k_deltas, k_cmvn, k_cmvn_sliding (some utterance longer than cmn_window) */
+/* info[2] (FB_ROUTE_NONE: compress_feats off) */
+#define FB_ROUTE_CM_FUSED 1          /* inside k_vad_delta_cmvn */
+#define FB_ROUTE_CM_REGS 2           /* k_feat_compress, sort keys in registers */
+#define FB_ROUTE_CM_LDS 3            /* k_feat_compress, sort keys in LDS */
+#define FB_ROUTE_CM_GLOBAL 4         /* k_feat_compress, columns read from global memory (longer than LDS holds) */
+
 /* Which diagonal-GMM arithmetic the loaded model runs on: 2 = two-term f16 split (k_gmm_fx2w / k_gmm_fx2, default),
  * 1 = exact three-term bf16 split (k_gmm_bx3: chosen automatically when a parameter does not fit f16's exponent
  * range; FB_GMM_MODE=bx3 forces it).  Negative FB_E_* without a model.

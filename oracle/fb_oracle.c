@@ -193,6 +193,25 @@ int fbo_num_frames(const fbo_frontend_cfg *c, int64_t n) {
 }
 int fbo_feat_dim(const fbo_frontend_cfg *c) { return c->num_ceps * (c->delta_order + 1); }
 
+static double mel_scale(double f);
+int fbo_check_cfg(const fbo_frontend_cfg *c) {
+  if (c->cmn_window < 1) return -1;
+  if (c->vad_frames_context < 0) return -2;
+  const int P = c->padded_length, nb = c->num_mel_bins;
+  const double nyq = 0.5 * c->sample_freq, hi = c->high_freq > 0.0 ? c->high_freq : nyq + c->high_freq;
+  const double mlo = mel_scale(c->low_freq), md = (mel_scale(hi) - mlo) / (nb + 1), bw = c->sample_freq / P;
+  for (int b = 0; b < nb; ++b) {
+    const double left = mlo + b * md, right = mlo + (b + 2) * md;
+    int any = 0;
+    for (int i = 0; i < P / 2 && !any; ++i) {
+      const double mel = mel_scale(bw * i);
+      any = mel > left && mel < right;
+    }
+    if (!any) return -3;
+  }
+  return 0;
+}
+
 typedef struct {
   int L, P, nb, nc;
   float *window;        /* [L] povey, stored float like Kaldi */
@@ -441,6 +460,7 @@ static int fbo_mfcc_f32(const fbo_frontend_cfg *c, const int16_t *wav, int64_t n
 }
 
 int fbo_mfcc(const fbo_frontend_cfg *c, const int16_t *wav, int64_t n, float *out) {
+  if (fbo_check_cfg(c) != 0) return 0;
   if (c->mfcc_f32) return fbo_mfcc_f32(c, wav, n, out);
   int T = fbo_num_frames(c, n);
   if (T <= 0) return 0;
@@ -666,7 +686,7 @@ void fbo_cmvn_sliding(const fbo_frontend_cfg *c, float *feats, int T, int dim) {
 int fbo_frontend(const fbo_frontend_cfg *c, const int16_t *wav, int64_t n, float *feats, int *T_out) {
   int T = fbo_num_frames(c, n);
   if (T_out) *T_out = T;
-  if (T <= 0) return 0;
+  if (T <= 0 || fbo_check_cfg(c) != 0) return 0;
   int nc = c->num_ceps, dim = fbo_feat_dim(c);
   float *mf = (float *)malloc(sizeof(float) * (size_t)T * nc);
   float *df = (float *)malloc(sizeof(float) * (size_t)T * dim);

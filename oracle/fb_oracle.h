@@ -82,6 +82,10 @@ void fbo_quantize(const double *x, int64_t n, int bits_per_sample, int16_t *q);
 /* ---- K2..K6 front-end ---- */
 int fbo_num_frames(const fbo_frontend_cfg *cfg, int64_t n_samples);
 int fbo_feat_dim(const fbo_frontend_cfg *cfg); /* num_ceps*(delta_order+1) */
+/* 0 when the options describe a front end, else a negative code: -1 cmn_window < 1 (the sliding mean would divide by an
+ * empty window), -2 vad_frames_context < 0, -3 a mel bin that covers no FFT bin (Kaldi: "num-mel-bins too large" [EXT]).
+ * fbo_mfcc / fbo_frontend compute nothing (return 0) for such options. */
+int fbo_check_cfg(const fbo_frontend_cfg *cfg);
 /* MFCC: out[T*num_ceps] float32.  returns T. */
 int fbo_mfcc(const fbo_frontend_cfg *cfg, const int16_t *wav, int64_t n, float *out);
 /* Kaldi CompressedMatrix round trip of a T x ncols float matrix, in place (compressed-matrix.{h,cc} [EXT]:

@@ -84,12 +84,23 @@ def _p(a, t=C.c_void_p):
     return a.ctypes.data_as(t)
 
 
+_CFG_ERRORS = {-1: "cmn_window < 1", -2: "vad_frames_context < 0", -3: "a mel bin covers no FFT bin (num_mel_bins too large)"}
+
+
+def check_cfg(cfg):
+    """Raises ValueError for options that describe no front end (fbo_check_cfg); returns cfg."""
+    rc = lib().fbo_check_cfg(C.byref(cfg))
+    if rc != 0:
+        raise ValueError("oracle: bad front-end options: " + _CFG_ERRORS.get(rc, str(rc)))
+    return cfg
+
+
 def default_cfg(**over):
     cfg = FrontendCfg()
     lib().fbo_default_cfg(C.byref(cfg))
     for k, v in over.items():
         setattr(cfg, k, v)
-    return cfg
+    return check_cfg(cfg)
 
 
 def philox(ctr, key):
@@ -119,6 +130,7 @@ def num_frames(cfg, n):
 
 
 def mfcc(cfg, wav):
+    check_cfg(cfg)
     wav = np.ascontiguousarray(wav, np.int16)
     T = num_frames(cfg, wav.size)
     out = np.empty((T, cfg.num_ceps), np.float32)
@@ -136,6 +148,7 @@ def compress_roundtrip(mat):
 
 
 def vad(cfg, mf):
+    check_cfg(cfg)
     mf = np.ascontiguousarray(mf, np.float32)
     v = np.empty(mf.shape[0], np.uint8)
     lib().fbo_vad(C.byref(cfg), _p(mf), C.c_int(mf.shape[0]), _p(v))
@@ -143,6 +156,7 @@ def vad(cfg, mf):
 
 
 def deltas(cfg, mf):
+    check_cfg(cfg)
     mf = np.ascontiguousarray(mf, np.float32)
     out = np.empty((mf.shape[0], mf.shape[1] * (cfg.delta_order + 1)), np.float32)
     lib().fbo_deltas(C.byref(cfg), _p(mf), C.c_int(mf.shape[0]), _p(out))
@@ -150,12 +164,14 @@ def deltas(cfg, mf):
 
 
 def cmvn_sliding(cfg, feats):
+    check_cfg(cfg)
     f = np.array(feats, np.float32, order="C", copy=True)
     lib().fbo_cmvn_sliding(C.byref(cfg), _p(f), C.c_int(f.shape[0]), C.c_int(f.shape[1]))
     return f
 
 
 def frontend(cfg, wav):
+    check_cfg(cfg)
     wav = np.ascontiguousarray(wav, np.int16)
     T = num_frames(cfg, wav.size)
     dim = lib().fbo_feat_dim(C.byref(cfg))
@@ -188,6 +204,7 @@ def diag_gmm_loglikes(gconsts, miv, iv, feats):
 def gmm_score_batch(cfg, wavs, gconsts, miv, iv, nthreads=1):
     """wavs: list of int16 arrays.  models: gconsts[M,C], miv/iv [M,C,D] float32.
     returns raw[B,M] average log-likelihoods, tv[B]."""
+    check_cfg(cfg)
     gconsts = np.ascontiguousarray(gconsts, np.float32)
     miv = np.ascontiguousarray(miv, np.float32)
     iv = np.ascontiguousarray(iv, np.float32)
@@ -293,7 +310,7 @@ class GmmSystemCtx(object):
         self.zm = np.ascontiguousarray(z_mean if z_mean is not None else np.zeros(M), np.float64)
         self.zs = np.ascontiguousarray(z_std if z_std is not None else np.ones(M), np.float64)
         s = GmmSystem()
-        s.cfg = cfg; s.task = TASK[task]; s.M = M; s.C = Cn; s.D = D
+        s.cfg = check_cfg(cfg); s.task = TASK[task]; s.M = M; s.C = Cn; s.D = D
         s.gconsts = self.gc.ctypes.data; s.means_invvars = self.miv.ctypes.data
         s.inv_vars = self.iv.ctypes.data; s.z_mean = self.zm.ctypes.data
         s.z_std = self.zs.ctypes.data; s.nthreads = nthreads; s.scored_utts = 0
@@ -388,6 +405,7 @@ class IvSystemCtx(object):
     def __init__(self, cfg, sysm, nthreads=1, share=None):
         """share: another IvSystemCtx over the same UBM / extractor / back-end whose derived variables are reused
         (only the enrolled speakers and z-norm statistics differ)."""
+        check_cfg(cfg)
         f32, f64 = np.float32, np.float64
         Cn, D, R, L, S = sysm.C, sysm.D, sysm.R, sysm.L, sysm.S
         if share is not None:

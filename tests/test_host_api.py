@@ -331,6 +331,19 @@ def test_kaldi_conf_parsing(tmp_path):
         frontend_overrides("--window-type=hamming")
     for k in o:                                            # every override is a real struct field
         assert k in [f[0] for f in _native.FrontendCfg._fields_]
+    # the options the recipe leaves at Kaldi's defaults
+    o2 = frontend_overrides("--dither=0 --frame-length=25.0625 --frame-shift=12.5 --snip-edges=true --remove-dc-offset=false\n"
+                            "--preemphasis-coefficient=0.5 --use-energy=false --raw-energy=false --energy-floor=1.5e3\n"
+                            "--cepstral-lifter=0 --low-freq=300 --high-freq=-400 --num-mel-bins=23 --num-ceps=13\n",
+                            "--vad-energy-threshold=4 --vad-energy-mean-scale=0 --vad-proportion-threshold=1.0 "
+                            "--vad-frames-context=0\n", "--delta-order=4 --delta-window=8\n")
+    assert o2 == dict(frame_length=401, padded_length=512, frame_shift=200, snip_edges=1, remove_dc=0, preemph=0.5,
+                      use_energy=0, raw_energy=0, energy_floor=1500.0, cepstral_lifter=0.0, low_freq=300.0,
+                      high_freq=-400.0, num_mel_bins=23, num_ceps=13, vad_energy_threshold=4.0,
+                      vad_energy_mean_scale=0.0, vad_proportion_threshold=1.0, vad_frames_context=0, delta_order=4,
+                      delta_window=8)
+    assert frontend_overrides("--dither=0 --frame-length=50")["padded_length"] == 1024
+    assert frontend_overrides("--dither=0 --use-energy=true --snip-edges=1")["use_energy"] == 1
 
 
 def test_fakebob_accepts_any_model_with_score_and_rejects_objects_without():

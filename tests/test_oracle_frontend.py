@@ -48,23 +48,35 @@ def test_quantize_matches_numpy_astype(oracle):
 
 
 # ------------------------------------------------------- independent numpy front-end
-def np_mfcc(wav, L=400, shift=160, P=512, nb=30, nc=24, lo=20.0, hi=7600.0, fs=16000.0, pre=0.97, lift=22.0):
+def np_mfcc(wav, L=400, shift=160, P=512, nb=30, nc=24, lo=20.0, hi=7600.0, fs=16000.0, pre=0.97, lift=22.0,
+            snip_edges=False, remove_dc=True, use_energy=True, raw_energy=True, energy_floor=0.0):
+    """compute-mfcc-feats with the povey window, restated in float64 numpy.  hi <= 0 is an offset from Nyquist; lift = 0
+    means no liftering; use_energy = False keeps C0 from the DCT; energy_floor > 0 clamps the log-energy from below."""
     wav = wav.astype(np.float64)
     n = wav.size
-    T = (n + shift // 2) // shift
-    idx = (np.arange(T)[:, None] * shift + shift // 2 - L // 2) + np.arange(L)[None, :]
+    if snip_edges:
+        T = 0 if n < L else 1 + (n - L) // shift
+        idx = (np.arange(T)[:, None] * shift) + np.arange(L)[None, :]
+    else:
+        T = (n + shift // 2) // shift
+        idx = (np.arange(T)[:, None] * shift + shift // 2 - L // 2) + np.arange(L)[None, :]
     while ((idx < 0) | (idx >= n)).any():          # Kaldi reflects repeatedly for very short waves
         idx = np.where(idx < 0, -idx - 1, idx)
         idx = np.where(idx >= n, 2 * n - 1 - idx, idx)
     fr = wav[idx]
-    fr = fr - fr.mean(axis=1, keepdims=True)
+    if remove_dc:
+        fr = fr - fr.mean(axis=1, keepdims=True)
     log_e = np.log(np.maximum((fr ** 2).sum(axis=1), FLT_EPS))
     fr = np.concatenate([fr[:, :1] * (1 - pre), fr[:, 1:] - pre * fr[:, :-1]], axis=1)
     win = (0.5 - 0.5 * np.cos(2 * np.pi * np.arange(L) / (L - 1))) ** 0.85
     fr = fr * win.astype(np.float32).astype(np.float64)
+    if not raw_energy:
+        log_e = np.log(np.maximum((fr ** 2).sum(axis=1), FLT_EPS))
+    if energy_floor > 0.0:
+        log_e = np.maximum(log_e, np.log(energy_floor))
     spec = np.abs(np.fft.rfft(fr, n=P, axis=1)) ** 2
     mel = lambda f: 1127.0 * np.log(1.0 + f / 700.0)
-    edges = np.linspace(mel(lo), mel(hi), nb + 2)
+    edges = np.linspace(mel(lo), mel(hi if hi > 0 else fs / 2 + hi), nb + 2)
     fmel = mel(np.arange(P // 2) * fs / P)
     W = np.zeros((nb, P // 2 + 1))
     for b in range(nb):
@@ -79,8 +91,10 @@ def np_mfcc(wav, L=400, shift=160, P=512, nb=30, nc=24, lo=20.0, hi=7600.0, fs=1
     dct = np.sqrt(2.0 / nb) * np.cos(np.pi / nb * (nn + 0.5) * k)
     dct[0] = np.sqrt(1.0 / nb)
     cep = lm @ dct.astype(np.float32).astype(np.float64).T
-    cep = cep * (1.0 + 0.5 * lift * np.sin(np.pi * np.arange(nc) / lift)).astype(np.float32)
-    cep[:, 0] = log_e
+    if lift != 0.0:
+        cep = cep * (1.0 + 0.5 * lift * np.sin(np.pi * np.arange(nc) / lift)).astype(np.float32)
+    if use_energy:
+        cep[:, 0] = log_e
     return cep
 
 
