@@ -140,6 +140,9 @@ struct fb_engine {
   bool any_long = false;  // some utterance has T > cmn_window
   int route[5] = {};      // fb_debug_frontend_route: what the last batch's front end ran
   bool have_route = false;  // ... once a batch has reached the MFCC launch
+  FbGmmShape shape_gmm = {};    // fb_debug_launch_shape: the geometry of the last batch's GMM launch (the launchers fill it in)
+  FbMfccShape shape_mfcc = {};  // ... and of its k_mfcc_f32 launch
+  bool have_shape = false;      // ... once a batch has chosen its launch shape
   int cached_B = -1;
   int64_t cached_N = -1;
   int last_total_frames = 0, last_B = 0, last_chunks = 1;
@@ -1199,6 +1202,18 @@ static bool fb_iv_use_rw(const fb_engine *e) {
   if (ev && strcmp(ev, "ll") == 0) return false;
   return e->fuse_opt == 1;
 }
+// The launch shape of a batch on a GPU shared by three or more attacks (fb_set_fused_chain(e, 0)): k_gmm_fx2w with two
+// component chunks per workgroup and k_mfcc_f32 on half of the compute units (run_scoring says why); FB_GMM_SUB=1 | 2 and
+// FB_MFCC_CUS=n force either.  Every path that launches those kernels decides it here, at the start of its batch, so that
+// none inherits the shape of the batch before it; the record fb_debug_launch_shape reads starts empty with it.
+static void choose_launch_shape(fb_engine *e) {
+  const char *sv = getenv("FB_GMM_SUB"), *cv = getenv("FB_MFCC_CUS");
+  e->gmm.fxw_sub = sv ? atoi(sv) : (e->fuse_opt == 0 ? 2 : 1);
+  e->fe.mfcc_cus = cv ? atoi(cv) : (e->fuse_opt == 0 ? 128 : 0);
+  e->shape_gmm = FbGmmShape{};
+  e->shape_mfcc = FbMfccShape{};
+  e->have_shape = true;
+}
 // MFCC of every frame of the batch prepared in e->wav: k_mfcc_f32 when the configuration asks for it, else k_mfcc_r16 / k_mfcc
 static void launch_mfcc(fb_engine *e, int B, int total_frames) {
   const FbFrontendDev &fe = e->fe;
@@ -1207,7 +1222,7 @@ static void launch_mfcc(fb_engine *e, int B, int total_frames) {
   e->route[3] = e->t_max;
   e->route[4] = B;
   if (fe.mfcc_f32 && fb_launch_mfcc_f32(s, fe, e->melw_n, e->wav.as<int16_t>(), e->frame_rec.as<int32_t>(), total_frames,
-                                        e->mfcc.as<float>(), e->uni_T, e->uni_n, e->h_wav_off[0]))
+                                        e->mfcc.as<float>(), e->uni_T, e->uni_n, e->h_wav_off[0], &e->shape_mfcc))
     e->route[0] = fe.L / 32 >= 12 ? FB_ROUTE_MFCC_F32_12 : FB_ROUTE_MFCC_F32_0;  // (fb_launch_mfcc_f32's instantiation rule)
   else
     e->route[0] = fb_launch_mfcc(s, fe, e->melw_n, e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), e->frame_off.as<int>(),
@@ -1307,10 +1322,7 @@ static int run_scoring(fb_engine *e, int B, int total_frames) {
   }
   FBCHK(e->raw.ensure(sizeof(double) * (size_t)B * e->n_out));
   hipStream_t s = e->stream;
-  {  // (a GPU shared by three or more attacks: k_mfcc_f32 on half of the compute units, like k_gmm_fx2w above; FB_MFCC_CUS=n forces)
-    const char *cv = getenv("FB_MFCC_CUS");
-    e->fe.mfcc_cus = cv ? atoi(cv) : (e->fuse_opt == 0 ? 128 : 0);
-  }
+  choose_launch_shape(e);
   launch_mfcc(e, B, total_frames);
   FBCHK(run_post_mfcc(e, B));
   if (e->kind == 0) {
@@ -1320,14 +1332,10 @@ static int run_scoring(fb_engine *e, int B, int total_frames) {
     // between one attack's k_gmm_fx2w and the others' k_mfcc_f32 / VAD (kernel trace, round 6: 62 + 19 us per iteration).
     // With HALF as many workgroups, each scoring two component chunks one after the other (the same partial sums, bit for
     // bit), the kernel alone is slower -- 92 us against 60 -- but the other half of the chip carries the other attacks'
-    // front-ends meanwhile: 12 319 -> 12 800 - 13 000 it/s (tools/profile/r06_fewer_wg.sh).  FB_GMM_SUB=1 | 2 forces either.
-    {
-      const char *sv = getenv("FB_GMM_SUB");
-      e->gmm.fxw_sub = sv ? atoi(sv) : (e->fuse_opt == 0 ? 2 : 1);
-    }
+    // front-ends meanwhile: 12 319 -> 12 800 - 13 000 it/s (tools/profile/r06_fewer_wg.sh).  choose_launch_shape decides it.
     FBCHK(time_begin(e));
     fb_launch_gmm(s, g, e->feats.as<float>(), e->row_off.as<int>() + B, total_frames, n_chunks,
-                  e->part_m.as<float>(), e->part_s.as<float>());
+                  e->part_m.as<float>(), e->part_s.as<float>(), &e->shape_gmm);
     FBCHK(time_end(e));
     if (!e->defer_finalize)
       fb_launch_gmm_finalize(s, g, e->part_m.as<float>(), e->part_s.as<float>(), total_frames, n_chunks,
@@ -1434,7 +1442,7 @@ static int run_scoring(fb_engine *e, int B, int total_frames) {
         e->gs_last_chunks = sel_chunks;
       }
       fb_launch_gmm_dump(s, gd, e->feats.as<float>(), e->row_off.as<int>() + B, total_frames, n_chunks,
-                         e->iv_ll.as<float>());
+                         e->iv_ll.as<float>(), &e->shape_gmm);
       FB_DBG_SYNC(e, "gmm_dump");
     }
     fb_launch_iv_select_post(s, iv, e->iv_ll.as<float>(), e->feats.as<float>(), e->row_off.as<int>() + B,
@@ -1888,6 +1896,18 @@ extern "C" int fb_debug_frontend_route(fb_engine *e, int *info) {
   if (!e || !info) return fb_fail(FB_E_ARG, "null argument");
   if (!e->have_route) return fb_fail(FB_E_STATE, "no batch has run the front end yet");
   for (int i = 0; i < 5; ++i) info[i] = e->route[i];
+  return FB_OK;
+}
+
+// the launch geometry of the last batch (choose_launch_shape starts the record, the launchers fill it in)
+extern "C" int fb_debug_launch_shape(fb_engine *e, int *info) {
+  if (!e || !info) return fb_fail(FB_E_ARG, "null argument");
+  if (!e->have_shape) return fb_fail(FB_E_STATE, "no batch has launched yet");
+  const FbGmmShape &g = e->shape_gmm;
+  const FbMfccShape &m = e->shape_mfcc;
+  const int v[12] = {g.kernel, g.n_chunks, g.sub, g.grid_chunks, g.xcd_map, g.passes, g.strips, g.tiles_min, g.tiles_max,
+                     m.cus, m.rounds, m.blocks};
+  for (int i = 0; i < 12; ++i) info[i] = v[i];
   return FB_OK;
 }
 
@@ -2598,6 +2618,7 @@ static int debug_frontend(fb_engine *e, const int16_t *wav, int64_t n) {
   FBCHK(e->tv.ensure(sizeof(int)));
   FBCHK(e->row_off.ensure(sizeof(int) * 2));
   FBCHK(e->feats.ensure(sizeof(float) * (size_t)T * fe.dim));
+  choose_launch_shape(e);
   launch_mfcc(e, 1, T);
   FBCHK(run_post_mfcc(e, 1));
   HIPCHK(hipGetLastError());
@@ -2619,7 +2640,7 @@ extern "C" int fb_gmm_acc_stats(fb_engine *e, const int16_t *wav, int64_t n, dou
   FBCHK(e->enr_stats.ensure(sizeof(double) * (size_t)g.C * (g.D + 1)));
   hipStream_t s = e->stream;
   const int *n_rows_ptr = e->row_off.as<int>() + 1;
-  fb_launch_gmm_dump(s, g, e->feats.as<float>(), n_rows_ptr, T, choose_chunks(g, T, false), e->enr_ll.as<float>());
+  fb_launch_gmm_dump(s, g, e->feats.as<float>(), n_rows_ptr, T, choose_chunks(g, T, false), e->enr_ll.as<float>(), &e->shape_gmm);
   double *d_occ = e->enr_stats.as<double>(), *d_F = d_occ + g.C;
   fb_launch_gmm_post_stats(s, g.C, ld, g.D, e->enr_ll.as<float>(), e->feats.as<float>(), n_rows_ptr, T,
                            e->enr_aux.as<float>(), e->enr_aux.as<float>() + T, d_occ, d_F);
@@ -2714,6 +2735,7 @@ extern "C" int fb_debug_gmm_frames(fb_engine *e, const float *feats, int T, doub
   HIPCHK(hipSetDevice(e->device));
   const FbGmmDev &g = e->gmm;
   FBCHK(sync_stream(e));
+  choose_launch_shape(e);
   const int n_chunks = choose_chunks(g, T, true);
   FBCHK(e->feats.ensure(sizeof(float) * (size_t)T * g.D));
   FBCHK(e->row_off.ensure(sizeof(int) * 2));
@@ -2723,7 +2745,7 @@ extern "C" int fb_debug_gmm_frames(fb_engine *e, const float *feats, int T, doub
   HIPCHK(hipMemcpy(e->feats.p, feats, sizeof(float) * (size_t)T * g.D, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(e->row_off.p, rows_host, sizeof(rows_host), hipMemcpyHostToDevice));
   fb_launch_gmm(e->stream, g, e->feats.as<float>(), e->row_off.as<int>() + 1, T, n_chunks, e->part_m.as<float>(),
-                e->part_s.as<float>());
+                e->part_s.as<float>(), &e->shape_gmm);
   HIPCHK(hipGetLastError());
   FBCHK(sync_stream(e));
   std::vector<float> pm((size_t)n_chunks * g.M * T), ps(pm.size());

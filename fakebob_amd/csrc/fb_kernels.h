@@ -129,10 +129,14 @@ int fb_mfcc_f32_mel_pieces(const int *mel_len, int nb);  // chunks of 12 weights
 std::vector<float> fb_mfcc_f32_table(int L, int nb, int nc, const double *window, const double *tw_half, const double *tw_full,
                                      const int *mel_first, const int *mel_len, const int *mel_off, const double *mel_w, int melw_n,
                                      const double *dct, const double *lifter);
+// the launch k_mfcc_f32's launcher chose (fb_debug_launch_shape): compute units it may take, rounds of 16-wave groups, workgroups
+struct FbMfccShape { int cus, rounds, blocks; };
 // uni_T > 0: every utterance has uni_n samples / uni_T frames and the first one starts at sample uni_base -- a frame's
-// record is computed, not loaded (one dependent global round trip less at the head of every wave)
+// record is computed, not loaded (one dependent global round trip less at the head of every wave).  shape (nullable): filled
+// in with the launch's geometry when the kernel is launched
 bool fb_launch_mfcc_f32(hipStream_t s, const FbFrontendDev &fe, int melw_n, const int16_t *wav, const int32_t *frame_rec,
-                        int total_frames, float *mfcc, int uni_T = 0, int64_t uni_n = 0, int64_t uni_base = 0);
+                        int total_frames, float *mfcc, int uni_T = 0, int64_t uni_n = 0, int64_t uni_base = 0,
+                        FbMfccShape *shape = nullptr);
 // VAD + per-utt voiced ranks.  vrank[f] = rank among voiced frames of its utt or -1; tv[b].
 // counter: one device int, zero before the first launch (the kernel leaves it at zero); row_off[B+1]
 // = exclusive scan of max(tv, 0), written by the workgroup that finishes last
@@ -233,19 +237,24 @@ static inline bool fb_device_needs_optin(std::atomic<unsigned long long> &mask, 
 }
 
 
+// The geometry of a GMM scoring / dump launch as its launcher chose it (fb_debug_launch_shape; nullable `shape` arguments
+// below): the kernel (FB_SHAPE_GMM_*), the component chunks, the chunks one k_gmm_fx2w workgroup scores one after the other
+// (after the n_chunks % fxw_sub rule), the grid's chunk dimension, the XCD mapping (0: the plain 2-D grid), the launches
+// (k_gmm_fx2w's passes), the frame strips and the fewest / most component tiles of any chunk
+struct FbGmmShape { int kernel, n_chunks, sub, grid_chunks, xcd_map, passes, strips, tiles_min, tiles_max; };
 // true when fb_launch_gmm runs the one-wave-per-SIMD scoring kernel k_gmm_fx2w (256-frame strips, one round of <= 256
 // workgroups): the engine sizes the component chunks for it
 bool fb_gmm_use_wide(const FbGmmDev &g);
 // gmm_wide_kernel.hip: the launch of k_gmm_fx2w (chunk c scores the component tiles c, c + n_chunks, ...); called by
 // fb_launch_gmm
 void fb_launch_gmm_wide(hipStream_t s, const FbGmmDev &g, const float *feats, const int *n_rows_ptr, int rows_cap,
-                        int n_chunks, float *part_m, float *part_s);
+                        int n_chunks, float *part_m, float *part_s, FbGmmShape *shape = nullptr);
 // part_m/part_s: [n_chunks][M][rows_pad]
 void fb_launch_gmm(hipStream_t s, const FbGmmDev &g, const float *feats, const int *row_off_total,
-                   int rows_cap, int n_chunks, float *part_m, float *part_s);
+                   int rows_cap, int n_chunks, float *part_m, float *part_s, FbGmmShape *shape = nullptr);
 // single model (g.M == 1): ll[row][n_tiles*32] = every component log-likelihood (gmm-gselect input)
 void fb_launch_gmm_dump(hipStream_t s, const FbGmmDev &g, const float *feats, const int *row_off_total,
-                        int rows_cap, int n_chunks, float *ll);
+                        int rows_cap, int n_chunks, float *ll, FbGmmShape *shape = nullptr);
 // gmm-gselect WITHOUT the dump (round 6; k_gmm_fx2_sel / k_gsel_tau / k_gsel_final, gmm_kernels.hip): single model in
 // the FX2 mode.  Workspace: gmax rows_cap x 2 n_tiles floats, tau rows_cap floats, glist rows_cap x n_chunks x cap 64-bit
 // keys, gcnt rows_cap x n_chunks ints, flag 1 int (set when any row overflowed its lists: the caller then runs the dump +

@@ -492,7 +492,7 @@ bool fb_mfcc_f32_supported(const FbFrontendDev &fe) {
   return fe.P == 512 && fe.nb <= 31 && fe.nc <= 32 && (fe.L & 1) == 0 && fe.L >= 2 && fe.L <= 512 && fe.raw_energy != 0 && fe.f32_tab != nullptr;
 }
 bool fb_launch_mfcc_f32(hipStream_t s, const FbFrontendDev &fe, int melw_n, const int16_t *wav, const int32_t *frame_rec,
-                        int total_frames, float *mfcc, int uni_T, int64_t uni_n, int64_t uni_base) {
+                        int total_frames, float *mfcc, int uni_T, int64_t uni_n, int64_t uni_base, FbMfccShape *shape) {
   if (total_frames <= 0) return true;
   if (!fb_mfcc_f32_supported(fe)) return false;
   const MfccF32Lds l = fb_mfcc_f32_layout(fe.L, fe.nb, fe.nc, melw_n);
@@ -517,6 +517,7 @@ bool fb_launch_mfcc_f32(hipStream_t s, const FbFrontendDev &fe, int melw_n, cons
   if (uni_n > 0x7fffffffLL || getenv("FB_MFCC_RECORDS") != nullptr) uni_T = 0;  // (A/B: always load the records)
   const int un = (int)uni_n;
   const long long ub = (long long)uni_base;
+  if (shape) *shape = FbMfccShape{cus, rounds, blocks};
   if (fe.L / 32 >= 12) hipLaunchKernelGGL((k_mfcc_f32<12>), dim3(blocks), dim3(64 * FB_F32_WAVES), shm, s, fe, melw_n, wav, rec, total_frames, mfcc, words, uni_T, un, ub);
   else hipLaunchKernelGGL((k_mfcc_f32<0>), dim3(blocks), dim3(64 * FB_F32_WAVES), shm, s, fe, melw_n, wav, rec, total_frames, mfcc, words, uni_T, un, ub);
   return true;

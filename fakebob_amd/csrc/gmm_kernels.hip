@@ -249,7 +249,7 @@ __global__ __launch_bounds__(256, FB_BX_OCC) void k_gmm_bx3(FbGmmDev g, const fl
 
 template <int NK, bool DUMP>
 static void launch_gmm_bx_t(hipStream_t s, const FbGmmDev &g, const float *feats, const int *n_rows_ptr,
-                            int rows_cap, int n_chunks, int tpc, float *part_m, float *part_s) {
+                            int rows_cap, int n_chunks, int tpc, float *part_m, float *part_s, FbGmmShape *shape) {
   const int strips = (rows_cap + 127) / 128;
   dim3 grid((unsigned)strips, (unsigned)n_chunks);
   int xcd_map = 0;
@@ -259,18 +259,20 @@ static void launch_gmm_bx_t(hipStream_t s, const FbGmmDev &g, const float *feats
     grid = dim3((unsigned)(8 * ((strips + per - 1) / per)), 1);
     xcd_map = n_chunks;
   }
+  if (shape)  // (chunk c scores the tiles [c tpc, (c + 1) tpc): the last one what is left)
+    *shape = FbGmmShape{FB_SHAPE_GMM_BX3, n_chunks, 1, n_chunks, xcd_map, 1, strips, g.n_tiles - (n_chunks - 1) * tpc, tpc};
   const size_t ldsb = (size_t)2 * 3 * NK * 64 * 16 + (size_t)2 * g.M * 256 * sizeof(float);
   hipLaunchKernelGGL((k_gmm_bx3<NK, DUMP>), grid, dim3(256), ldsb, s, g, feats, n_rows_ptr, tpc, rows_cap,
                      part_m, part_s, xcd_map);
 }
 template <bool DUMP>
 static void launch_gmm_bx(hipStream_t s, const FbGmmDev &g, const float *feats, const int *n_rows_ptr,
-                          int rows_cap, int n_chunks, int tpc, float *part_m, float *part_s) {
+                          int rows_cap, int n_chunks, int tpc, float *part_m, float *part_s, FbGmmShape *shape) {
   switch (g.NK) {
-    case 3: launch_gmm_bx_t<3, DUMP>(s, g, feats, n_rows_ptr, rows_cap, n_chunks, tpc, part_m, part_s); break;
-    case 4: launch_gmm_bx_t<4, DUMP>(s, g, feats, n_rows_ptr, rows_cap, n_chunks, tpc, part_m, part_s); break;
-    case 5: launch_gmm_bx_t<5, DUMP>(s, g, feats, n_rows_ptr, rows_cap, n_chunks, tpc, part_m, part_s); break;
-    case 6: launch_gmm_bx_t<6, DUMP>(s, g, feats, n_rows_ptr, rows_cap, n_chunks, tpc, part_m, part_s); break;
+    case 3: launch_gmm_bx_t<3, DUMP>(s, g, feats, n_rows_ptr, rows_cap, n_chunks, tpc, part_m, part_s, shape); break;
+    case 4: launch_gmm_bx_t<4, DUMP>(s, g, feats, n_rows_ptr, rows_cap, n_chunks, tpc, part_m, part_s, shape); break;
+    case 5: launch_gmm_bx_t<5, DUMP>(s, g, feats, n_rows_ptr, rows_cap, n_chunks, tpc, part_m, part_s, shape); break;
+    case 6: launch_gmm_bx_t<6, DUMP>(s, g, feats, n_rows_ptr, rows_cap, n_chunks, tpc, part_m, part_s, shape); break;
     default: break;  // fb_load_gmm only produces the NK values above
   }
 }
@@ -463,7 +465,7 @@ __global__ __launch_bounds__(256, FB_FX_OCC) void k_gmm_fx2(FbGmmDev g, const fl
 
 template <int NK, bool DUMP>
 static void launch_gmm_fx_t(hipStream_t s, const FbGmmDev &g, const float *feats, const int *n_rows_ptr,
-                            int rows_cap, int n_chunks, int tpc, float *part_m, float *part_s) {
+                            int rows_cap, int n_chunks, int tpc, float *part_m, float *part_s, FbGmmShape *shape) {
   const int strips = (rows_cap + 127) / 128;
   dim3 grid((unsigned)strips, (unsigned)n_chunks);
   int xcd_map = 0;
@@ -473,6 +475,8 @@ static void launch_gmm_fx_t(hipStream_t s, const FbGmmDev &g, const float *feats
     grid = dim3((unsigned)(8 * ((strips + per - 1) / per)), 1);
     xcd_map = n_chunks;
   }
+  if (shape)  // (chunk c scores the tiles [c tpc, (c + 1) tpc): the last one what is left)
+    *shape = FbGmmShape{FB_SHAPE_GMM_FX2, n_chunks, 1, n_chunks, xcd_map, 1, strips, g.n_tiles - (n_chunks - 1) * tpc, tpc};
   const size_t ldsb = (size_t)2 * 2 * NK * 64 * 16 + (size_t)2 * g.M * 256 * sizeof(float) +
                       (DUMP ? (size_t)4 * 32 * 36 * sizeof(float) : 0);   // + the dump's per-wave transposition tiles
   hipLaunchKernelGGL((k_gmm_fx2<NK, DUMP>), grid, dim3(256), ldsb, s, g, feats, n_rows_ptr, tpc, rows_cap,
@@ -480,13 +484,13 @@ static void launch_gmm_fx_t(hipStream_t s, const FbGmmDev &g, const float *feats
 }
 template <bool DUMP>
 static void launch_gmm_fx(hipStream_t s, const FbGmmDev &g, const float *feats, const int *n_rows_ptr,
-                          int rows_cap, int n_chunks, int tpc, float *part_m, float *part_s) {
+                          int rows_cap, int n_chunks, int tpc, float *part_m, float *part_s, FbGmmShape *shape) {
   switch (g.NKF) {
-    case 2: launch_gmm_fx_t<2, DUMP>(s, g, feats, n_rows_ptr, rows_cap, n_chunks, tpc, part_m, part_s); break;
-    case 3: launch_gmm_fx_t<3, DUMP>(s, g, feats, n_rows_ptr, rows_cap, n_chunks, tpc, part_m, part_s); break;
-    case 4: launch_gmm_fx_t<4, DUMP>(s, g, feats, n_rows_ptr, rows_cap, n_chunks, tpc, part_m, part_s); break;
-    case 5: launch_gmm_fx_t<5, DUMP>(s, g, feats, n_rows_ptr, rows_cap, n_chunks, tpc, part_m, part_s); break;
-    case 6: launch_gmm_fx_t<6, DUMP>(s, g, feats, n_rows_ptr, rows_cap, n_chunks, tpc, part_m, part_s); break;
+    case 2: launch_gmm_fx_t<2, DUMP>(s, g, feats, n_rows_ptr, rows_cap, n_chunks, tpc, part_m, part_s, shape); break;
+    case 3: launch_gmm_fx_t<3, DUMP>(s, g, feats, n_rows_ptr, rows_cap, n_chunks, tpc, part_m, part_s, shape); break;
+    case 4: launch_gmm_fx_t<4, DUMP>(s, g, feats, n_rows_ptr, rows_cap, n_chunks, tpc, part_m, part_s, shape); break;
+    case 5: launch_gmm_fx_t<5, DUMP>(s, g, feats, n_rows_ptr, rows_cap, n_chunks, tpc, part_m, part_s, shape); break;
+    case 6: launch_gmm_fx_t<6, DUMP>(s, g, feats, n_rows_ptr, rows_cap, n_chunks, tpc, part_m, part_s, shape); break;
     default: break;  // fb_load_gmm only produces the NKF values above
   }
 }
@@ -926,20 +930,20 @@ void fb_launch_gsel_wide(hipStream_t s, const FbGmmDev &g, const float *feats, c
 }
 
 void fb_launch_gmm_dump(hipStream_t s, const FbGmmDev &g, const float *feats, const int *n_rows_ptr,
-                        int rows_cap, int n_chunks, float *ll) {
+                        int rows_cap, int n_chunks, float *ll, FbGmmShape *shape) {
   if (rows_cap <= 0) return;
   const int tpc = (g.n_tiles + n_chunks - 1) / n_chunks;
-  if (g.mode == FB_GMM_MODE_FX2) launch_gmm_fx<true>(s, g, feats, n_rows_ptr, rows_cap, n_chunks, tpc, ll, nullptr);
-  else launch_gmm_bx<true>(s, g, feats, n_rows_ptr, rows_cap, n_chunks, tpc, ll, nullptr);
+  if (g.mode == FB_GMM_MODE_FX2) launch_gmm_fx<true>(s, g, feats, n_rows_ptr, rows_cap, n_chunks, tpc, ll, nullptr, shape);
+  else launch_gmm_bx<true>(s, g, feats, n_rows_ptr, rows_cap, n_chunks, tpc, ll, nullptr, shape);
 }
 
 void fb_launch_gmm(hipStream_t s, const FbGmmDev &g, const float *feats, const int *n_rows_ptr,
-                   int rows_cap, int n_chunks, float *part_m, float *part_s) {
+                   int rows_cap, int n_chunks, float *part_m, float *part_s, FbGmmShape *shape) {
   if (rows_cap <= 0) return;
   const int tpc = (g.n_tiles + n_chunks - 1) / n_chunks;
-  if (fb_gmm_use_wide(g)) fb_launch_gmm_wide(s, g, feats, n_rows_ptr, rows_cap, n_chunks, part_m, part_s);
-  else if (g.mode == FB_GMM_MODE_FX2) launch_gmm_fx<false>(s, g, feats, n_rows_ptr, rows_cap, n_chunks, tpc, part_m, part_s);
-  else launch_gmm_bx<false>(s, g, feats, n_rows_ptr, rows_cap, n_chunks, tpc, part_m, part_s);
+  if (fb_gmm_use_wide(g)) fb_launch_gmm_wide(s, g, feats, n_rows_ptr, rows_cap, n_chunks, part_m, part_s, shape);
+  else if (g.mode == FB_GMM_MODE_FX2) launch_gmm_fx<false>(s, g, feats, n_rows_ptr, rows_cap, n_chunks, tpc, part_m, part_s, shape);
+  else launch_gmm_bx<false>(s, g, feats, n_rows_ptr, rows_cap, n_chunks, tpc, part_m, part_s, shape);
 }
 
 // raw[b][m] = (1/Tv) * sum_{voiced rows of b} logsumexp_k ll_k   (float64 sum of

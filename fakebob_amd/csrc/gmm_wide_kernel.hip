@@ -905,9 +905,13 @@ __global__ __launch_bounds__(256, 1) void k_gmm_fx2w(FbGmmDev g, const float *__
   // the updates the last tile deferred: the fast form (one exponential and one addition per value, the guard, the cold
   // rescue) without MFMAs to thread it through -- the classical form here (a maximum, a re-reference, fma + exp + add
   // per value) was 2.3 us of every workgroup's 58
+  // The fast form adds values relative to rc, so it needs the model's state at rc.  Inside the loop the tile boundary moves
+  // every state there after a rescue; here no boundary follows the last tile, whose first two steps carried this model's
+  // deferred update from the tile before -- a rescue in that update left the state at a reference of its own (mref > rc),
+  // and those lanes take the classical update (wave-uniform: rare and cold).
   auto tail_update = [&](const f32x16 &v0, const f32x16 &v1, int model) {
-    if (slow) { update(v0, v1, model); return; }
     float *pm = st_m + (2 * model) * 256 + tid, *ps = st_s + (2 * model) * 256 + tid;
+    if (slow || __builtin_amdgcn_ballot_w64(pm[0] != rc[0] || pm[256] != rc[1]) != 0ull) { update(v0, v1, model); return; }
     FbFxwUpd u;
     u.so0 = ps[0]; u.so1 = ps[256];
     float e0 = __builtin_amdgcn_exp2f(v0[0]), d0 = __builtin_amdgcn_exp2f(v0[1]);
@@ -1197,7 +1201,7 @@ void fb_launch_gsel_w(hipStream_t s, const FbGmmDev &g, const float *feats, cons
 
 template <int NK, int M>
 static void launch_gmm_fxw_t(hipStream_t s, const FbGmmDev &g, const float *feats, const int *n_rows_ptr,
-                             int rows_cap, int n_chunks, float *part_m, float *part_s) {
+                             int rows_cap, int n_chunks, float *part_m, float *part_s, FbGmmShape *shape) {
   const int strips = (rows_cap + 255) / 256;
   // (component chunks a workgroup scores one after the other: FbGmmDev::fxw_sub when it divides the chunk count)
   FbGmmDev gl = g;
@@ -1210,6 +1214,11 @@ static void launch_gmm_fxw_t(hipStream_t s, const FbGmmDev &g, const float *feat
     const int per = 8 / gchunks;
     grid = dim3((unsigned)(8 * ((strips + per - 1) / per)), 1);
     xcd_map = gchunks;
+  }
+  if (shape) {  // (chunk c scores the tiles c, c + n_chunks, ...: floor or ceil of n_tiles / n_chunks of them)
+    const int passes = shape->kernel == FB_SHAPE_GMM_FX2W ? shape->passes + 1 : 1;
+    *shape = FbGmmShape{FB_SHAPE_GMM_FX2W, n_chunks, gl.fxw_sub, gchunks, xcd_map, passes, strips, g.n_tiles / n_chunks,
+                        (g.n_tiles + n_chunks - 1) / n_chunks};
   }
   const size_t ldsb = ((size_t)(M + 1) * 2 * NK * 64 + 2 * 192) * 16 + (size_t)2 * M * 512 * sizeof(float);  // one tile (two padded slots) + the state
   static std::atomic<unsigned long long> optin{0};
@@ -1231,7 +1240,8 @@ bool fb_gmm_use_wide(const FbGmmDev &g) {
          g.n_pass >= 1 && g.item_model_host_q_first && g.delta_p >= 1 && g.images_fd != nullptr && g.anchor != nullptr;
 }
 void fb_launch_gmm_wide(hipStream_t s, const FbGmmDev &g, const float *feats, const int *n_rows_ptr, int rows_cap,
-                        int n_chunks, float *part_m, float *part_s) {
+                        int n_chunks, float *part_m, float *part_s, FbGmmShape *shape) {
+  if (shape) *shape = FbGmmShape{};  // (each pass's launch counts itself)
   // one launch per pass (fb_load_gmm: more than FB_FXW_MAX_M models are dealt over up to FB_FXW_MAX_PASS launches, each
   // with the base model and its own delta images; the base model's partials are written by every pass with the same
   // values)
@@ -1240,15 +1250,15 @@ void fb_launch_gmm_wide(hipStream_t s, const FbGmmDev &g, const float *feats, co
     gp.images_fd = g.pass_images[p];
     gp.pass_first = g.pass_lo[p];
     switch (1 + g.pass_lo[p + 1] - g.pass_lo[p]) {
-      case 2: launch_gmm_fxw_t<5, 2>(s, gp, feats, n_rows_ptr, rows_cap, n_chunks, part_m, part_s); break;
-      case 3: launch_gmm_fxw_t<5, 3>(s, gp, feats, n_rows_ptr, rows_cap, n_chunks, part_m, part_s); break;
-      case 4: launch_gmm_fxw_t<5, 4>(s, gp, feats, n_rows_ptr, rows_cap, n_chunks, part_m, part_s); break;
-      case 5: launch_gmm_fxw_t<5, 5>(s, gp, feats, n_rows_ptr, rows_cap, n_chunks, part_m, part_s); break;
-      case 6: launch_gmm_fxw_t<5, 6>(s, gp, feats, n_rows_ptr, rows_cap, n_chunks, part_m, part_s); break;
-      case 7: launch_gmm_fxw_t<5, 7>(s, gp, feats, n_rows_ptr, rows_cap, n_chunks, part_m, part_s); break;
-      case 8: launch_gmm_fxw_t<5, 8>(s, gp, feats, n_rows_ptr, rows_cap, n_chunks, part_m, part_s); break;
-      case 9: launch_gmm_fxw_t<5, 9>(s, gp, feats, n_rows_ptr, rows_cap, n_chunks, part_m, part_s); break;
-      case 10: launch_gmm_fxw_t<5, 10>(s, gp, feats, n_rows_ptr, rows_cap, n_chunks, part_m, part_s); break;
+      case 2: launch_gmm_fxw_t<5, 2>(s, gp, feats, n_rows_ptr, rows_cap, n_chunks, part_m, part_s, shape); break;
+      case 3: launch_gmm_fxw_t<5, 3>(s, gp, feats, n_rows_ptr, rows_cap, n_chunks, part_m, part_s, shape); break;
+      case 4: launch_gmm_fxw_t<5, 4>(s, gp, feats, n_rows_ptr, rows_cap, n_chunks, part_m, part_s, shape); break;
+      case 5: launch_gmm_fxw_t<5, 5>(s, gp, feats, n_rows_ptr, rows_cap, n_chunks, part_m, part_s, shape); break;
+      case 6: launch_gmm_fxw_t<5, 6>(s, gp, feats, n_rows_ptr, rows_cap, n_chunks, part_m, part_s, shape); break;
+      case 7: launch_gmm_fxw_t<5, 7>(s, gp, feats, n_rows_ptr, rows_cap, n_chunks, part_m, part_s, shape); break;
+      case 8: launch_gmm_fxw_t<5, 8>(s, gp, feats, n_rows_ptr, rows_cap, n_chunks, part_m, part_s, shape); break;
+      case 9: launch_gmm_fxw_t<5, 9>(s, gp, feats, n_rows_ptr, rows_cap, n_chunks, part_m, part_s, shape); break;
+      case 10: launch_gmm_fxw_t<5, 10>(s, gp, feats, n_rows_ptr, rows_cap, n_chunks, part_m, part_s, shape); break;
       default: break;  // fb_load_gmm deals at most FB_FXW_MAX_M - 1 delta models to a pass
     }
   }

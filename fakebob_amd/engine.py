@@ -198,6 +198,21 @@ class Engine(object):
         return dict(mfcc=self._ROUTE_MFCC[info[0]], chain=self._ROUTE_CHAIN[info[1]], compress=self._ROUTE_CM[info[2]],
                     t_max=int(info[3]), B=int(info[4]))
 
+    # fb_debug_launch_shape's GMM kernel codes (include/fakebob_hip_test.h: FB_SHAPE_GMM_*)
+    _SHAPE_GMM = {0: None, 1: "fx2w", 2: "fx2", 3: "bx3"}
+
+    def debug_launch_shape(self):
+        """The launch geometry of the last batch as the launchers chose it (fb_debug_launch_shape): a dict of gmm (the
+        kernel, None when none ran), n_chunks, sub (chunks per k_gmm_fx2w workgroup), grid_chunks, xcd_map (0: the plain
+        2-D grid), passes, strips, tiles_min / tiles_max (component tiles of a chunk), and k_mfcc_f32's cus, rounds and
+        blocks (0 when another MFCC kernel ran)."""
+        info = (C.c_int * 12)()
+        N.check(self._L.fb_debug_launch_shape(self._h, info))
+        keys = ("n_chunks", "sub", "grid_chunks", "xcd_map", "passes", "strips", "tiles_min", "tiles_max", "cus", "rounds", "blocks")
+        d = dict(gmm=self._SHAPE_GMM[info[0]])
+        d.update((k, int(v)) for k, v in zip(keys, info[1:]))
+        return d
+
     def set_system(self, task, z_mean=None, z_std=None):
         zm = None if z_mean is None else np.ascontiguousarray(z_mean, np.float64)
         zs = None if z_std is None else np.ascontiguousarray(z_std, np.float64)

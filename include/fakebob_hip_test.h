@@ -52,6 +52,20 @@ int fb_debug_frontend_route(fb_engine *e, int *info);
 #define FB_ROUTE_CM_LDS 3            /* k_feat_compress, sort keys in LDS */
 #define FB_ROUTE_CM_GLOBAL 4         /* k_feat_compress, columns read from global memory (longer than LDS holds) */
 
+/* The launch geometry of the last batch (fb_score_*, fb_get_grad, an NES iteration, fb_debug_gmm_frames, fb_debug_mfcc /
+ * _feats, enrolment statistics), as the launchers chose it: info[12] = {the GMM kernel (FB_SHAPE_GMM_*: the scoring kernel,
+ * or the per-component dump of an i-vector batch or of enrolment statistics), component chunks, chunks one k_gmm_fx2w
+ * workgroup scores one after the other (1 when fxw_sub does not divide the chunk count), the grid's chunk dimension, the XCD
+ * mapping (the chunk count it serves, 0: the plain 2-D grid), launches (k_gmm_fx2w's passes), frame strips, fewest and most
+ * component tiles of any chunk, then k_mfcc_f32's compute units, rounds and workgroups}.  A stage that launched nothing in
+ * that batch reports zeros.  Recorded on the host when the kernels are enqueued; read only.  FB_E_STATE before the first
+ * batch. */
+int fb_debug_launch_shape(fb_engine *e, int *info);
+#define FB_SHAPE_GMM_NONE 0
+#define FB_SHAPE_GMM_FX2W 1          /* k_gmm_fx2w */
+#define FB_SHAPE_GMM_FX2 2           /* k_gmm_fx2 */
+#define FB_SHAPE_GMM_BX3 3           /* k_gmm_bx3 */
+
 /* Which diagonal-GMM arithmetic the loaded model runs on: 2 = two-term f16 split (k_gmm_fx2w / k_gmm_fx2, default),
  * 1 = exact three-term bf16 split (k_gmm_bx3: chosen automatically when a parameter does not fit f16's exponent
  * range; FB_GMM_MODE=bx3 forces it).  Negative FB_E_* without a model.

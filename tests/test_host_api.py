@@ -31,6 +31,14 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert L.fb_version() >= 100
 
 
+def test_debug_hooks_refuse_a_null_engine():
+    import ctypes as C
+    L = _native.lib()
+    info = (C.c_int * 12)()
+    assert L.fb_debug_launch_shape(None, info) == _native.FB_E_ARG
+    assert L.fb_debug_frontend_route(None, info) == _native.FB_E_ARG
+
+
 def test_no_gpu_means_a_loud_error_not_a_fallback():
     import ctypes as C
     L = _native.lib()
