@@ -60,10 +60,28 @@ class IvectorSystem(C.Structure):
 # fb_score_cb: int (*)(void *ctx, const double *audios, int64_t N, int B, double *scores)
 SCORE_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int64, C.c_int, C.POINTER(C.c_double))
 
+# fb_score_dev_cb: int (*)(void *ctx, void *stream, int64_t N, int B, int S) -- a device-resident foreign model
+SCORE_DEV_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int)
+FB_DT_F32, FB_DT_F64 = 0, 1
+
+
+class DevModel(C.Structure):
+    """fb_dev_model"""
+    _fields_ = [("x_dtype", C.c_int), ("x", C.c_void_p), ("score_dtype", C.c_int), ("scores", C.c_void_p),
+                ("look_every", C.c_int)]
+
+
+class ForeignPathInfo(C.Structure):
+    """fb_foreign_path_info (include/fakebob_hip_test.h)"""
+    _fields_ = [("path", C.c_int), ("x_dtype", C.c_int), ("score_dtype", C.c_int), ("launches_per_iter", C.c_int),
+                ("model_calls", C.c_int64), ("batch_bytes_d2h", C.c_int64), ("score_bytes_h2d", C.c_int64)]
+
+
 EXPORTS = [
     "fb_last_error", "fb_version", "fb_device_count", "fb_engine_create", "fb_engine_destroy",
     "fb_default_frontend", "fb_set_frontend", "fb_load_gmm", "fb_load_ivector", "fb_set_system", "fb_num_speakers",
     "fb_score_i16", "fb_score_f64", "fb_system_scores", "fb_get_grad", "fb_attack", "fb_attack_iter_seconds", "fb_get_grad_ext", "fb_attack_ext",
+    "fb_get_grad_dev", "fb_attack_dev", "fb_debug_foreign_path",
     "fb_estimate_threshold", "fb_debug_noise", "fb_debug_quantize", "fb_debug_mfcc", "fb_debug_feats", "fb_debug_gmm_frames", "fb_debug_iv_active", "fb_debug_iv_gselect", "fb_debug_frontend_route", "fb_debug_launch_shape", "fb_stats", "fb_gmm_acc_stats", "fb_last_ivectors", "fb_gmm_kernel_mode", "fb_gmm_kernel_variant", "fb_gmm_delta_tiles", "fb_gmm_delta_tiles_f6", "fb_set_fused_chain",
     "fb_bench_gmm_kernel", "fb_bench_nes", "fb_bench_nes_state",
 ]
@@ -92,6 +110,37 @@ def lib():
         getattr(L, name)  # AttributeError if the ABI is incomplete
     _lib = L
     return L
+
+
+def hip_runtimes():
+    """The distinct libamdhip64 files this process has mapped (/proc/self/maps)."""
+    paths = set()
+    try:
+        with open("/proc/self/maps") as r:
+            for line in r:
+                f = line.split(None, 5)
+                if len(f) == 6 and os.path.basename(f[5].strip()).startswith("libamdhip64"):
+                    paths.add(f[5].strip())
+    except OSError:
+        pass
+    return sorted(paths)
+
+
+def torch_first():
+    """Import torch ahead of this library: the device path hands torch's device pointers and streams to the library, so
+    both must run on ONE HIP runtime.  torch's wheel ships its own libamdhip64 under the soname the library links
+    against, and whichever of the two loads first serves both.  Imported here, lazily: nothing else needs torch."""
+    import torch
+    return torch
+
+
+def check_one_hip_runtime():
+    """Raise when the process maps more than one libamdhip64: pointers and streams must not cross runtimes."""
+    rt = hip_runtimes()
+    if len(rt) > 1:
+        raise RuntimeError("this process maps %d HIP runtimes (%s): torch and libfakebob_hip.so must share one.  Import "
+                           "torch before the library is first loaded (fakebob_amd._native.torch_first())" %
+                           (len(rt), ", ".join(rt)))
 
 
 def check(rc):

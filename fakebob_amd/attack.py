@@ -9,6 +9,11 @@ A `model` that is not one of this package's systems -- the reference's plugin AP
 your system by providing score and make_decisions") -- is driven through `fb_attack_ext` / `fb_get_grad_ext`: its
 `score` is called once per NES iteration on the (N, samples_per_draw + 1) float64 batch, exactly as FAKEBOB.py:250
 does, while noise, perturbation, loss, gradient estimate, momentum sign step and clipping stay on the GPU.
+A foreign model that also has a callable `score_device(x)` runs on the same GPU instead (`fb_attack_dev` /
+`fb_get_grad_dev`): x is a torch tensor [samples_per_draw + 1, N] in device memory, one utterance per row, of the
+model's `device_dtype` (torch.float32 by default, or torch.float64), and the result is [B, S] scores ([B] for SV).  The
+batch and the scores never leave the device.  The optional `look_every` attribute sets how many iterations the host
+queues between looks at the loop control (default 4; 1: exactly one model call per iteration).
 
 The reference never seeds its RNG (FAKEBOB.py:234).  Here the noise is a Philox4x32-10 stream
 keyed by `seed` (constructor keyword, default drawn from numpy's global RNG so that
@@ -74,7 +79,10 @@ class FakeBob(object):
         # estimate_threshold); only the NES arithmetic around it runs on the GPU.
         self._native = hasattr(model, "engine")
         self._own_engine = None
-        if not self._native and not callable(getattr(model, "score", None)):
+        # a foreign model on the GPU: batch and scores stay in device memory (fb_attack_dev / fb_get_grad_dev)
+        self._device = not self._native and callable(getattr(model, "score_device", None))
+        self._dev_bufs = None
+        if not self._native and not self._device and not callable(getattr(model, "score", None)):
             raise TypeError("model must provide score(audios, fs=, bits_per_sample=, n_jobs=, debug=) "
                             "(and make_decisions for estimate_threshold), README.md:136 of the reference")
         if self._native and getattr(model, "task", task) != task:
@@ -101,6 +109,9 @@ class FakeBob(object):
         if self._native:
             return self.model.engine
         if self._own_engine is None:
+            if self._device:
+                from . import _native
+                _native.torch_first()   # torch before the library: one HIP runtime for both
             from .engine import Engine
             from .systems import default_device
             self._own_engine = Engine(default_device())
@@ -115,6 +126,10 @@ class FakeBob(object):
                 self._n_spk = 1
             elif hasattr(self.model, "spk_ids"):
                 self._n_spk = len(self.model.spk_ids)
+            elif probe_audio is not None and self._device:
+                torch = self._torch()
+                x = torch.as_tensor(np.ascontiguousarray(probe_audio[:, 0]), device=self._cuda()).to(self._x_dtype())
+                self._n_spk = int(self.model.score_device(x.reshape(1, -1)).numel())
             elif probe_audio is not None:
                 self._n_spk = int(np.asarray(self.model.score(probe_audio, **score_kw)).size)
             else:
@@ -126,9 +141,45 @@ class FakeBob(object):
             return self.model.score(audios, fs=fs, bits_per_sample=bits_per_sample, n_jobs=n_jobs, debug=debug)
         return fn
 
+    # ----------------------------------------- foreign models on the GPU (score_device)
+    @staticmethod
+    def _torch():
+        from . import _native
+        return _native.torch_first()
+
+    def _cuda(self):
+        return self._torch().device("cuda", self._engine().device)
+
+    def _x_dtype(self):
+        torch = self._torch()
+        dt = getattr(self.model, "device_dtype", torch.float32)
+        if dt not in (torch.float32, torch.float64):
+            raise ValueError("model.device_dtype %s: torch.float32 or torch.float64" % (dt,))
+        return dt
+
+    def _device_buffers(self, n, S):
+        """x [B, N] of the model's device_dtype and float64 scores [B, S] on the engine's GPU, kept across calls of the
+        same shape.  (float64 scores: a float32 result is widened exactly, a float64 one kept as it is.)"""
+        torch = self._torch()
+        B = 2 * (self.samples_per_draw // 2) + 1
+        dt = self._x_dtype()
+        b = self._dev_bufs
+        if b is None or b[0].shape != (B, n) or b[0].dtype != dt or b[1].shape != (B, S):
+            b = (torch.empty((B, n), dtype=dt, device=self._cuda()), torch.empty((B, S), dtype=torch.float64, device=self._cuda()))
+            self._dev_bufs = b
+        return b
+
+    def _grad_foreign(self, eng, p, S, audio, fs, bits_per_sample, n_jobs, debug, it, noise_pos):
+        """get_grad around a foreign model: on the device when it has score_device, else through its score."""
+        if self._device:
+            x, sc = self._device_buffers(audio.size, S)
+            return eng.get_grad_dev(p, S, self.model.score_device, x, sc, audio, it=it, noise_pos=noise_pos)
+        return eng.get_grad_ext(p, S, self._score_fn(fs, bits_per_sample, n_jobs, debug), audio, it=it, noise_pos=noise_pos)
+
     def _estimate_threshold_foreign(self, audio, fs, bits_per_sample, n_jobs, debug, max_total_iters, noise_all):
         """FAKEBOB.py:39-137 around a black-box model: its make_decisions decides, its score feeds the device NES
-        gradient (fb_get_grad_ext); the momentum / plateau / sign-step bookkeeping is a few length-N numpy lines."""
+        gradient (fb_get_grad_ext, or fb_get_grad_dev for a model with score_device); the momentum / plateau /
+        sign-step bookkeeping is a few length-N numpy lines."""
         kw = dict(fs=fs, bits_per_sample=bits_per_sample, n_jobs=n_jobs, debug=debug)
         eng = self._engine()
         init = np.asarray(self.model.score(audio, **kw), np.float64)   # FAKEBOB.py:53
@@ -145,7 +196,6 @@ class FakeBob(object):
         velocity = 0.
         n_iters = n_outer = 0
         spent = 0.
-        fn = self._score_fn(fs, bits_per_sample, n_jobs, debug)
         while True:
             lr = self.max_lr
             history = []
@@ -164,7 +214,7 @@ class FakeBob(object):
                     raise RuntimeError("estimate_threshold: max_total_iters %d reached" % max_total_iters)
                 p = self._params(attack_type=UNTARGETED, bits_per_sample=bits_per_sample)
                 noise = None if noise_all is None else noise_all[n_iters]
-                loss, g, _, _ = eng.get_grad_ext(p, S, fn, adver[:, 0], it=n_iters, noise_pos=noise)
+                loss, g, _, _ = self._grad_foreign(eng, p, S, adver[:, 0], fs, bits_per_sample, n_jobs, debug, n_iters, noise)
                 velocity = self.momentum * velocity + (1.0 - self.momentum) * g[:, np.newaxis]
                 history = (history + [loss])[-self.plateau_length:]
                 if len(history) == self.plateau_length and history[-1] > history[0]:
@@ -225,6 +275,12 @@ class FakeBob(object):
         if self._native:
             eng = self.model.engine
             adv, flag, _advf, trace = eng.attack(p, audio[:, 0], noise_all=noise_all)
+        elif self._device:
+            eng = self._engine()
+            S = self._speakers(audio, **kw)
+            x, sc = self._device_buffers(audio.shape[0], S)
+            adv, flag, _advf, trace = eng.attack_dev(p, S, self.model.score_device, x, sc, audio[:, 0], noise_all=noise_all,
+                                                     look_every=int(getattr(self.model, "look_every", 0)))
         else:
             eng = self._engine()
             adv, flag, _advf, trace = eng.attack_ext(
@@ -255,9 +311,8 @@ class FakeBob(object):
             fl, grad, al, sc = self.model.engine.get_grad(p, audio[:, 0], it=iteration, noise_pos=noise_pos)
         else:
             kw = dict(fs=fs, bits_per_sample=bits_per_sample, n_jobs=n_jobs, debug=debug)
-            fl, grad, al, sc = self._engine().get_grad_ext(
-                p, self._speakers(audio, **kw), self._score_fn(fs, bits_per_sample, n_jobs, debug), audio[:, 0],
-                it=iteration, noise_pos=noise_pos)
+            fl, grad, al, sc = self._grad_foreign(self._engine(), p, self._speakers(audio, **kw), audio[:, 0], fs,
+                                                  bits_per_sample, n_jobs, debug, iteration, noise_pos)
         return fl, grad[:, np.newaxis], np.array([al]), self._score_shape(sc)
 
     # ------------------------------------------------------------------- loss_fn

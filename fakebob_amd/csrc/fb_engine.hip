@@ -115,7 +115,8 @@ struct fb_engine {
   std::vector<double> h_zmean, h_zstd;
   // batch scratch
   DevBuf frame_rec, vad_counter, vad_pub, vad_part, fin_counter, fin_xch, ctl, ctl_ls, trace_dev, ticks, enr_ll, enr_aux, enr_stats;
-  std::vector<double> iter_seconds;  // per-iteration device times of the last fb_attack / fb_attack_ext
+  std::vector<double> iter_seconds;  // per-iteration device times of the last fb_attack / fb_attack_ext / fb_attack_dev
+  fb_foreign_path_info foreign = {};  // fb_debug_foreign_path: the last foreign-model call (path 0: none yet)
   long long bench_it = -1;  // fb_bench_nes: next iteration index of the attack left resident (-1: none)
   int64_t bench_N = 0;
   int bench_B = 0;
@@ -2266,8 +2267,8 @@ static int collect_iter_seconds(fb_engine *e, int rows) {
 // For a model that is not one of this library's systems the scores come from a host callback; everything else of
 // the NES iteration stays on the device: Philox noise + perturbation (k_perturb_f64), loss + loop control (k_loss),
 // gradient estimate + momentum sign step (k_grad_update).  One host round trip per iteration is inherent.
-static int check_params_ext(fb_engine *e, const fb_nes_params *p, int64_t N, int S, fb_score_cb cb) {
-  if (!e || !p || !cb) return fb_fail(FB_E_ARG, "null argument");
+static int check_params_ext(fb_engine *e, const fb_nes_params *p, int64_t N, int S, bool have_cb) {
+  if (!e || !p || !have_cb) return fb_fail(FB_E_ARG, "null argument");
   if (N <= 0) return fb_fail(FB_E_ARG, "empty audio");
   if (p->task != FB_TASK_OSI && p->task != FB_TASK_CSI && p->task != FB_TASK_SV) return fb_fail(FB_E_ARG, "bad task");
   if (S <= 0 || S > 62) return fb_fail(FB_E_ARG, "number of speakers must be in [1, 62] (got %d)", S);
@@ -2297,6 +2298,15 @@ static int ensure_ext_buffers(fb_engine *e, int64_t N, int B, int S) {
   return FB_OK;
 }
 
+// fb_debug_foreign_path's record of the foreign-model call that starts now
+static void foreign_begin(fb_engine *e, int path, int x_dtype, int score_dtype, int launches_per_iter) {
+  e->foreign = fb_foreign_path_info{};
+  e->foreign.path = path;
+  e->foreign.x_dtype = x_dtype;
+  e->foreign.score_dtype = score_dtype;
+  e->foreign.launches_per_iter = launches_per_iter;
+}
+
 // perturb -> float64 batch to the host -> callback -> scores to the device -> loss (+ loop control)
 static int enqueue_get_grad_ext(fb_engine *e, const fb_nes_params *p, int S, fb_score_cb cb, void *cb_ctx, int64_t N,
                                 uint32_t iter, const double *noise_dev, bool with_dist, FbCtlDev *ctl = nullptr,
@@ -2323,6 +2333,9 @@ static int enqueue_get_grad_ext(fb_engine *e, const fb_nes_params *p, int S, fb_
     if (rc != 0) return fb_fail(FB_E_CALLBACK, "score callback failed (rc %d)", rc);
   }
   FBCHK(h2d(e, e->raw.p, sc.data(), sizeof(double) * sc.size()));
+  e->foreign.model_calls += 1;
+  e->foreign.batch_bytes_d2h += (int64_t)xb;
+  e->foreign.score_bytes_h2d += (int64_t)(sizeof(double) * sc.size());
   fb_launch_loss(e->stream, e->raw.as<double>(), nullptr, B, S, p->task, 1, p->attack_type, e->ext_z.as<double>(),
                  e->ext_z.as<double>() + 64, p->threshold, p->adver_thresh, p->target, p->true_label,
                  e->dist_part.as<double>(), with_dist ? ndp : 0, e->scores.as<double>(), e->loss.as<double>(),
@@ -2335,11 +2348,12 @@ extern "C" int fb_get_grad_ext(fb_engine *e, const fb_nes_params *p, int S, fb_s
                                double *final_loss, double *grad, double *adver_loss, double *score0) {
   if (e) e->bench_it = -1;
   if (!audio) return fb_fail(FB_E_ARG, "audio is NULL");
-  FBCHK(check_params_ext(e, p, N, S, cb));
+  FBCHK(check_params_ext(e, p, N, S, cb != nullptr));
   HIPCHK(hipSetDevice(e->device));
   FBCHK(sync_stream(e));
   const int half = p->samples_per_draw / 2, B = 2 * half + 1;
   FBCHK(ensure_ext_buffers(e, N, B, S));
+  foreign_begin(e, FB_FOREIGN_HOST, FB_DT_F64, FB_DT_F64, 3);  // k_perturb_f64, k_loss, k_grad_update
   FBCHK(h2d(e, e->adver.p, audio, sizeof(double) * (size_t)N));
   const double *noise_dev = nullptr;
   if (noise_pos && half > 0) {
@@ -2365,12 +2379,13 @@ extern "C" int fb_attack_ext(fb_engine *e, const fb_nes_params *p, int S, fb_sco
                              double *adver_f64, double *trace, int *n_trace, int *success_flag) {
   if (e) e->bench_it = -1;
   if (!audio || !adv_i16 || !success_flag) return fb_fail(FB_E_ARG, "null argument");
-  FBCHK(check_params_ext(e, p, N, S, cb));
+  FBCHK(check_params_ext(e, p, N, S, cb != nullptr));
   if (p->max_iter <= 0) return fb_fail(FB_E_ARG, "max_iter must be > 0");
   HIPCHK(hipSetDevice(e->device));
   FBCHK(sync_stream(e));
   const int half = p->samples_per_draw / 2, B = 2 * half + 1;
   FBCHK(ensure_ext_buffers(e, N, B, S));
+  foreign_begin(e, FB_FOREIGN_HOST, FB_DT_F64, FB_DT_F64, 3);  // k_perturb_f64, k_loss, k_grad_update
   FBCHK(h2d(e, e->audio.p, audio, sizeof(double) * (size_t)N));
   HIPCHK(hipMemcpyAsync(e->adver.p, e->audio.p, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, e->stream));
   HIPCHK(hipMemsetAsync(e->grad_m.p, 0, sizeof(double) * (size_t)N, e->stream));  // grad = 0 (FAKEBOB.py:157)
@@ -2426,6 +2441,220 @@ extern "C" int fb_attack_ext(fb_engine *e, const fb_nes_params *p, int S, fb_sco
   FBCHK(d2h(e, adv_i16, e->wav.p, sizeof(int16_t) * (size_t)N));
   if (adver_f64) FBCHK(d2h(e, adver_f64, e->adver.p, sizeof(double) * (size_t)N));
   FBCHK(sync_stream(e));
+  return FB_OK;
+}
+
+// ------------------------------------------- foreign models on the same GPU (fb_get_grad_dev / fb_attack_dev)
+// The batch goes into the caller's device buffer (k_perturb_x, k_update_perturb_x), the callback enqueues the model on
+// the engine's stream, and the loss reads the model's scores where it wrote them: no copy through the host, and the host
+// looks at the control block every look_every iterations as fb_attack does.
+static int check_dev_buffer(fb_engine *e, const char *what, const void *ptr, size_t bytes) {
+  if (!ptr) return fb_fail(FB_E_ARG, "%s is NULL", what);
+  hipPointerAttribute_t a;
+  memset(&a, 0, sizeof(a));
+  const hipError_t rc = hipPointerGetAttributes(&a, ptr);
+  if (rc != hipSuccess) {
+    (void)hipGetLastError();  // (an unknown host pointer: not a sticky error)
+    return fb_fail(FB_E_ARG, "%s is not device memory (hipPointerGetAttributes: %s)", what, hipGetErrorString(rc));
+  }
+  if (a.type != hipMemoryTypeDevice) return fb_fail(FB_E_ARG, "%s is not device memory (memory type %d)", what, (int)a.type);
+  if (a.device != e->device)
+    return fb_fail(FB_E_ARG, "%s is memory of device %d, the engine runs on device %d", what, a.device, e->device);
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, const_cast<void *>(ptr)) == hipSuccess) {
+    const size_t room = (size_t)(static_cast<const char *>(base) + size - static_cast<const char *>(ptr));
+    if (room < bytes) return fb_fail(FB_E_ARG, "%s: %zu bytes needed, its allocation holds %zu from there", what, bytes, room);
+  } else {
+    (void)hipGetLastError();
+  }
+  return FB_OK;
+}
+
+static int check_dev_model(fb_engine *e, const fb_dev_model *m, int64_t N, int B, int S) {
+  if (!m) return fb_fail(FB_E_ARG, "null argument");
+  if (m->x_dtype != FB_DT_F32 && m->x_dtype != FB_DT_F64)
+    return fb_fail(FB_E_ARG, "x_dtype %d: FB_DT_F32 (%d) or FB_DT_F64 (%d)", m->x_dtype, FB_DT_F32, FB_DT_F64);
+  if (m->score_dtype != FB_DT_F32 && m->score_dtype != FB_DT_F64)
+    return fb_fail(FB_E_ARG, "score_dtype %d: FB_DT_F32 (%d) or FB_DT_F64 (%d)", m->score_dtype, FB_DT_F32, FB_DT_F64);
+  if (m->look_every < 0) return fb_fail(FB_E_ARG, "look_every %d < 0", m->look_every);
+  const size_t xe = m->x_dtype == FB_DT_F32 ? sizeof(float) : sizeof(double);
+  const size_t se = m->score_dtype == FB_DT_F32 ? sizeof(float) : sizeof(double);
+  FBCHK(check_dev_buffer(e, "x", m->x, xe * (size_t)N * (size_t)B));
+  FBCHK(check_dev_buffer(e, "scores", m->scores, se * (size_t)B * (size_t)S));
+  return FB_OK;
+}
+
+static int ensure_dev_buffers(fb_engine *e, int64_t N, int B, int S) {
+  FBCHK(ensure_nes_buffers(e, N, B, S));
+  const size_t had = e->ext_z.cap;
+  FBCHK(e->ext_z.ensure(sizeof(double) * 2 * 64));
+  if (e->ext_z.cap != had) {  // z-norm of the identity, as ensure_ext_buffers
+    double z[128];
+    for (int i = 0; i < 64; ++i) { z[i] = 0.0; z[64 + i] = 1.0; }
+    FBCHK(h2d(e, e->ext_z.p, z, sizeof(z)));
+  }
+  return FB_OK;
+}
+
+// the model's work on the engine's stream, then the loss (+ loop control) on its scores
+static int enqueue_score_loss_dev(fb_engine *e, const fb_nes_params *p, int S, const fb_dev_model *m, fb_score_dev_cb cb,
+                                  void *ctx, int64_t N, int ndp, FbCtlDev *ctl, double *trace_dev, int trace_row) {
+  const int B = 2 * (p->samples_per_draw / 2) + 1;
+  const int rc = cb(ctx, (void *)e->stream, N, B, S);
+  e->foreign.model_calls += 1;
+  if (rc != 0) {
+    (void)sync_stream(e);  // (whatever the model did enqueue has finished when the caller sees the error)
+    return fb_fail(FB_E_CALLBACK, "score callback failed (rc %d)", rc);
+  }
+  if (m->score_dtype == FB_DT_F32)
+    fb_launch_loss(e->stream, static_cast<const float *>(m->scores), nullptr, B, S, p->task, 1, p->attack_type,
+                   e->ext_z.as<double>(), e->ext_z.as<double>() + 64, p->threshold, p->adver_thresh, p->target,
+                   p->true_label, e->dist_part.as<double>(), ndp, e->scores.as<double>(), e->loss.as<double>(),
+                   e->nes_out.as<FbNesDev>(), ctl, trace_dev, trace_row);
+  else
+    fb_launch_loss(e->stream, static_cast<const double *>(m->scores), nullptr, B, S, p->task, 1, p->attack_type,
+                   e->ext_z.as<double>(), e->ext_z.as<double>() + 64, p->threshold, p->adver_thresh, p->target,
+                   p->true_label, e->dist_part.as<double>(), ndp, e->scores.as<double>(), e->loss.as<double>(),
+                   e->nes_out.as<FbNesDev>(), ctl, trace_dev, trace_row);
+  return FB_OK;
+}
+
+static bool x_aligned(const fb_dev_model *m) { return (reinterpret_cast<uintptr_t>(m->x) & 15) == 0; }
+
+extern "C" int fb_get_grad_dev(fb_engine *e, const fb_nes_params *p, int S, const fb_dev_model *m, fb_score_dev_cb cb,
+                               void *ctx, const double *audio, int64_t N, uint32_t iter, const double *noise_pos,
+                               double *final_loss, double *grad, double *adver_loss, double *score0) {
+  if (e) e->bench_it = -1;
+  if (!audio) return fb_fail(FB_E_ARG, "audio is NULL");
+  FBCHK(check_params_ext(e, p, N, S, cb != nullptr));
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  const int half = p->samples_per_draw / 2, B = 2 * half + 1;
+  FBCHK(check_dev_model(e, m, N, B, S));
+  FBCHK(ensure_dev_buffers(e, N, B, S));
+  foreign_begin(e, FB_FOREIGN_DEV, m->x_dtype, m->score_dtype, 3);  // k_perturb_x, k_loss, k_grad_update
+  FBCHK(h2d(e, e->adver.p, audio, sizeof(double) * (size_t)N));
+  const double *noise_dev = nullptr;
+  if (noise_pos && half > 0) {
+    FBCHK(e->noise.ensure(sizeof(double) * (size_t)N * half));
+    FBCHK(h2d(e, e->noise.p, noise_pos, sizeof(double) * (size_t)N * half));
+    noise_dev = e->noise.as<double>();
+  }
+  fb_launch_perturb_x(e->stream, m->x_dtype, e->adver.as<double>(), nullptr, N, half, p->sigma, p->seed, iter, p->stream,
+                      noise_dev, m->x, x_aligned(m), e->dist_part.as<double>(), nullptr,
+                      noise_dev ? nullptr : e->zbuf.as<float>(), nullptr);
+  FBCHK(enqueue_score_loss_dev(e, p, S, m, cb, ctx, N, 0, nullptr, nullptr, 0));
+  fb_launch_grad_update(e->stream, e->loss.as<double>(), N, half, p->sigma, e->zbuf.as<float>(), noise_dev,
+                        e->grad.as<double>(), 0, 0.0, 0.0, 0.0, 0.0, nullptr, nullptr, nullptr);
+  if (grad) FBCHK(d2h(e, grad, e->grad.p, sizeof(double) * (size_t)N));
+  HIPCHK(hipMemcpyAsync(e->h_out, e->nes_out.p, sizeof(FbNesDev), hipMemcpyDeviceToHost, e->stream));
+  FBCHK(sync_stream(e));
+  e->nes_iters += 1;
+  if (final_loss) *final_loss = e->h_out->final_loss;
+  if (adver_loss) *adver_loss = e->h_out->adver_loss;
+  if (score0) for (int s = 0; s < S; ++s) score0[s] = e->h_out->score0[s];
+  return FB_OK;
+}
+
+extern "C" int fb_attack_dev(fb_engine *e, const fb_nes_params *p, int S, const fb_dev_model *m, fb_score_dev_cb cb,
+                             void *ctx, const double *audio, int64_t N, const double *noise_all, int16_t *adv_i16,
+                             double *adver_f64, double *trace, int *n_trace, int *success_flag) {
+  if (e) e->bench_it = -1;
+  if (!audio || !adv_i16 || !success_flag) return fb_fail(FB_E_ARG, "null argument");
+  FBCHK(check_params_ext(e, p, N, S, cb != nullptr));
+  if (p->max_iter <= 0) return fb_fail(FB_E_ARG, "max_iter must be > 0");
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  const int half = p->samples_per_draw / 2, B = 2 * half + 1;
+  FBCHK(check_dev_model(e, m, N, B, S));
+  FBCHK(ensure_dev_buffers(e, N, B, S));
+  // Philox noise and a small enough batch: the momentum sign step of iteration i and the batch of i + 1 in one launch
+  // (k_update_perturb_x, as fb_attack's k_update_perturb); otherwise k_grad_update + k_perturb_x
+  const bool fuse = !noise_all && half > 0 && half <= FB_FUSE_MAX_HALF;
+  foreign_begin(e, FB_FOREIGN_DEV, m->x_dtype, m->score_dtype, fuse ? 2 : 3);
+  FBCHK(h2d(e, e->audio.p, audio, sizeof(double) * (size_t)N));
+  HIPCHK(hipMemcpyAsync(e->adver.p, e->audio.p, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, e->stream));
+  HIPCHK(hipMemsetAsync(e->grad_m.p, 0, sizeof(double) * (size_t)N, e->stream));  // grad = 0 (FAKEBOB.py:157)
+  if (noise_all && half > 0) FBCHK(e->noise.ensure(sizeof(double) * (size_t)N * half));
+  double *trace_dev = nullptr;
+  if (trace) {
+    FBCHK(e->trace_dev.ensure(sizeof(double) * (size_t)p->max_iter * (3 + S)));
+    trace_dev = e->trace_dev.as<double>();
+  }
+  FBCHK(e->ctl.ensure(sizeof(FbCtlDev)));
+  FBCHK(e->ctl_ls.ensure(sizeof(double) * (size_t)(p->plateau_length > 0 ? p->plateau_length : 1)));
+  FbCtlDev *ctl = e->ctl.as<FbCtlDev>();
+  {
+    FbCtlDev h;
+    memset(&h, 0, sizeof(h));
+    h.lr = p->max_lr; h.min_lr = p->min_lr; h.plateau_drop = p->plateau_drop;
+    h.ls = e->ctl_ls.as<double>();
+    h.plateau_length = p->plateau_length;
+    FBCHK(e->ticks.ensure(sizeof(unsigned long long) * ((size_t)p->max_iter + 1)));
+    h.ticks = e->ticks.as<unsigned long long>();
+    *e->h_ctl = h;
+    HIPCHK(hipMemcpyAsync(ctl, e->h_ctl, sizeof(FbCtlDev), hipMemcpyHostToDevice, e->stream));
+    FBCHK(sync_stream(e));
+    fb_launch_stamp(e->stream, h.ticks);
+  }
+  const double one_minus_m = 1.0 - p->momentum;
+  const int look = m->look_every > 0 ? m->look_every : 4;
+  const int xv = x_aligned(m) ? 1 : 0;
+  int ndp = 0;
+  bool have_batch = false;  // the fused launch of the previous iteration wrote this iteration's batch
+  for (int it = 0; it < p->max_iter;) {
+    const int nb = p->max_iter - it < look ? p->max_iter - it : look;
+    for (int k = 0; k < nb; ++k) {
+      const int i = it + k;
+      const double *noise_dev = nullptr;
+      if (noise_all && half > 0) {
+        FBCHK(h2d(e, e->noise.p, noise_all + (size_t)i * N * half, sizeof(double) * (size_t)N * half));
+        noise_dev = e->noise.as<double>();
+      }
+      if (!have_batch)
+        fb_launch_perturb_x(e->stream, m->x_dtype, e->adver.as<double>(), e->audio.as<double>(), N, half, p->sigma, p->seed,
+                            (uint32_t)i, p->stream, noise_dev, m->x, xv, e->dist_part.as<double>(), &ndp,
+                            noise_dev ? nullptr : e->zbuf.as<float>(), &ctl->stop);
+      FBCHK(enqueue_score_loss_dev(e, p, S, m, cb, ctx, N, ndp, ctl, trace_dev, i));
+      if (fuse) {
+        ndp = fb_launch_update_perturb_x(e->stream, m->x_dtype, e->loss.as<double>(), N, half, p->sigma,
+                                         e->zbuf.as<float>(), p->momentum, one_minus_m, p->epsilon, e->audio.as<double>(),
+                                         e->grad_m.as<double>(), e->adver.as<double>(), ctl, p->seed, (uint32_t)(i + 1),
+                                         p->stream, m->x, xv, e->dist_part.as<double>());
+        have_batch = true;
+      } else {
+        fb_launch_grad_update(e->stream, e->loss.as<double>(), N, half, p->sigma, e->zbuf.as<float>(), noise_dev, nullptr,
+                              1, p->momentum, one_minus_m, 0.0, p->epsilon, e->audio.as<double>(), e->grad_m.as<double>(),
+                              e->adver.as<double>(), ctl);
+      }
+    }
+    HIPCHK(hipMemcpyAsync(e->h_ctl, ctl, sizeof(FbCtlDev), hipMemcpyDeviceToHost, e->stream));
+    FBCHK(sync_stream(e));
+    it += nb;
+    if (e->h_ctl->stop) break;
+  }
+  const int rows = e->h_ctl->iters_done;
+  const bool broke = e->h_ctl->broke != 0;
+  e->nes_iters += rows;
+  FBCHK(collect_iter_seconds(e, rows));
+  if (trace && rows > 0) FBCHK(d2h(e, trace, trace_dev, sizeof(double) * (size_t)rows * (3 + S)));
+  const int last_iter = broke ? e->h_ctl->stop_iter : p->max_iter - 1;
+  *success_flag = (last_iter < p->max_iter - 1) ? 1 : -1;  // FAKEBOB.py:219
+  if (n_trace) *n_trace = rows;
+  FBCHK(e->wav.ensure(sizeof(int16_t) * (size_t)N));
+  e->cached_B = -1;  // the scoring batch layout no longer describes e->wav
+  fb_launch_quantize(e->stream, e->adver.as<double>(), N, p->bits_per_sample ? p->bits_per_sample : 16, e->wav.as<int16_t>());
+  FBCHK(d2h(e, adv_i16, e->wav.p, sizeof(int16_t) * (size_t)N));
+  if (adver_f64) FBCHK(d2h(e, adver_f64, e->adver.p, sizeof(double) * (size_t)N));
+  FBCHK(sync_stream(e));
+  return FB_OK;
+}
+
+extern "C" int fb_debug_foreign_path(fb_engine *e, fb_foreign_path_info *info) {
+  if (!e || !info) return fb_fail(FB_E_ARG, "null argument");
+  if (e->foreign.path == 0) return fb_fail(FB_E_STATE, "no foreign-model call has run yet");
+  *info = e->foreign;
   return FB_OK;
 }
 

@@ -43,6 +43,11 @@ void fb_launch_perturb(hipStream_t s, const double *adver, const double *audio, 
 void fb_launch_perturb_f64(hipStream_t s, const double *adver, const double *audio, int64_t N, int half,
                            double sigma, uint64_t seed, uint32_t iter, uint32_t stream, const double *noise_pos,
                            double *x, double *dist_part, int *n_dist_part, float *zbuf);
+// the same batch into a device-resident foreign model's x[B][N] as FB_DT_F32 / FB_DT_F64 (x_vec: x is 16-byte aligned);
+// honours `stop` (nullable) like fb_launch_perturb
+void fb_launch_perturb_x(hipStream_t s, int x_dtype, const double *adver, const double *audio, int64_t N, int half,
+                         double sigma, uint64_t seed, uint32_t iter, uint32_t stream, const double *noise_pos, void *x,
+                         int x_vec, double *dist_part, int *n_dist_part, float *zbuf, const int *stop);
 // *t = the device's constant-rate clock (wall_clock64) when the stream gets there
 void fb_launch_stamp(hipStream_t s, unsigned long long *t);
 // plain quantisation of float64 audio (model.score on float input)
@@ -80,6 +85,12 @@ void fb_launch_loss(hipStream_t s, const double *raw, const int *tv, int B, int 
                     double adver_thresh, int target, int true_label, const double *dist_part,
                     int n_dist_part, double *scores, double *loss, FbNesDev *out, FbCtlDev *ctl = nullptr,
                     double *trace = nullptr, int it = 0);
+// ... a foreign model's float32 scores, read from its own buffer and widened exactly
+void fb_launch_loss(hipStream_t s, const float *raw, const int *tv, int B, int M, int task, int znorm_all,
+                    int attack_type, const double *z_mean, const double *z_std, double threshold,
+                    double adver_thresh, int target, int true_label, const double *dist_part,
+                    int n_dist_part, double *scores, double *loss, FbNesDev *out, FbCtlDev *ctl = nullptr,
+                    double *trace = nullptr, int it = 0);
 // k_grad_update (iteration `next_iter - 1`) + k_perturb (iteration next_iter) in one launch; device-controlled attacks
 // with Philox noise and half <= FB_FUSE_MAX_HALF only.  Returns the number of distance partials written.
 #define FB_FUSE_MAX_HALF 40
@@ -106,6 +117,12 @@ int fb_launch_update_perturb(hipStream_t s, const double *loss, int64_t N, int h
                              double momentum, double one_minus_m, double epsilon, const double *audio, double *grad_m,
                              double *adver, const FbCtlDev *ctl, uint64_t seed, uint32_t next_iter, uint32_t stream,
                              int16_t *q, double *dist_part, int bits = 16);
+// ... and with the batch of iteration next_iter written into a device-resident foreign model's x[B][N] (x_dtype FB_DT_*,
+// x_vec: x is 16-byte aligned) instead of the int16 batch
+int fb_launch_update_perturb_x(hipStream_t s, int x_dtype, const double *loss, int64_t N, int half, double sigma,
+                               float *zbuf, double momentum, double one_minus_m, double epsilon, const double *audio,
+                               double *grad_m, double *adver, const FbCtlDev *ctl, uint64_t seed, uint32_t next_iter,
+                               uint32_t stream, void *x, int x_vec, double *dist_part);
 // grad estimate (numpy-pairwise order) + optional momentum/sign/clip update.
 // do_update: 0 = only grad_out; 1 = momentum+update with lr.
 void fb_launch_grad_update(hipStream_t s, const double *loss, int64_t N, int half, double sigma,

@@ -89,8 +89,21 @@ static __device__ unsigned long long g_fin_stamps[1024 * 12];
 #else
 #define FN_STAMP(k) do { } while (0)
 #endif
-template <bool SMALL, bool FUSED>
-__device__ __forceinline__ void fb_loss_body(const double *__restrict__ raw, const int *__restrict__ tv,
+// raw scores as the loss body reads them: FUSED, written by other workgroups of the same launch (agent-scope loads);
+// a foreign model's float32 scores are widened exactly
+template <bool FUSED, typename TR>
+__device__ __forceinline__ double fb_ld_raw(const TR *p) {
+  if constexpr (FUSED) {
+    static_assert(sizeof(TR) == sizeof(double), "agent-scope loads of float64 scores only");
+    return fb_ld_agent_f64(p);
+  } else {
+    return (double)*p;
+  }
+}
+// TR: the element type of raw[] -- double for this library's systems, float or double for a foreign model's scores
+// read straight from its device buffer (fb_attack_dev)
+template <bool SMALL, bool FUSED, typename TR = double>
+__device__ __forceinline__ void fb_loss_body(const TR *__restrict__ raw, const int *__restrict__ tv,
                                               int B, int M, int task, int znorm_all, int attack_type,
                                               const double *__restrict__ z_mean,
                                               const double *__restrict__ z_std, double threshold,
@@ -128,8 +141,7 @@ __device__ __forceinline__ void fb_loss_body(const double *__restrict__ raw, con
     if (M <= FB_RAW_LOCAL) {
 #pragma unroll
       for (int m = 0; m < FB_RAW_LOCAL; ++m) {
-        const double *rp = raw + (size_t)b * M + (m < M ? m : M - 1);
-        rv[m] = FUSED ? fb_ld_agent_f64(rp) : *rp;
+        rv[m] = fb_ld_raw<FUSED>(raw + (size_t)b * M + (m < M ? m : M - 1));
       }
     }
     auto r = [&](int m) -> double {
@@ -139,7 +151,7 @@ __device__ __forceinline__ void fb_loss_body(const double *__restrict__ raw, con
         for (int q = 1; q < FB_RAW_LOCAL; ++q) v = m == q ? rv[q] : v;
         return v;
       }
-      return FUSED ? fb_ld_agent_f64(raw + (size_t)b * M + m) : raw[(size_t)b * M + m];
+      return fb_ld_raw<FUSED>(raw + (size_t)b * M + m);
     };
     double *sc = sc_lds ? s_sc + (size_t)b * S : scores + (size_t)b * S;
 #ifdef FB_FIN_STAMP
@@ -379,14 +391,49 @@ __device__ __forceinline__ void fb_loss_body(const double *__restrict__ raw, con
 // (Philox + Box-Muller: most of the kernel's time) -- is done first, then one thread polls the control block until loss body
 // number wait_seq has published (or the attack has stopped), and the losses and the step size are read with agent-scope
 // loads.  Same arithmetic in the same order either way: trajectories are bit-identical.
-template <bool SMALL, bool WAIT>
+// Where fb_update_perturb_body puts the next iteration's batch: element type V, cvt(a) = the element of float64 value a,
+// at(off) = the element at offset `off` of the [B][N] batch, st4(p, v): four consecutive elements in one go (p a
+// multiple of four elements into a suitably aligned buffer).
+// FbOutI16: the int16 batch this library's systems score (gmm_ubm_OSI.py:85's cast, 2^(bits_per_sample - 1)).
+struct FbOutI16 {
+  using V = int16_t;
+  int16_t *q;
+  double qscale;
+  __device__ __forceinline__ V cvt(double a) const { return fb_quantize(a, qscale); }
+  __device__ __forceinline__ V *at(int64_t off) const { return q + off; }
+  __device__ __forceinline__ static void st4(V *p, const V (&v)[4]) {
+    *reinterpret_cast<short4 *>(p) = make_short4(v[0], v[1], v[2], v[3]);
+  }
+};
+// FbOutX<T>: a foreign model's float32 / float64 batch in the caller's device buffer x[B][N] (fb_attack_dev): float64
+// as it is, float32 rounded to nearest (= torch's .float() of the float64 batch)
+template <typename T> __device__ __forceinline__ T fb_to_x(double v);
+template <> __device__ __forceinline__ double fb_to_x<double>(double v) { return v; }
+template <> __device__ __forceinline__ float fb_to_x<float>(double v) { return __double2float_rn(v); }
+template <typename T>
+struct FbOutX {
+  using V = T;
+  T *x;
+  __device__ __forceinline__ V cvt(double a) const { return fb_to_x<T>(a); }
+  __device__ __forceinline__ V *at(int64_t off) const { return x + off; }
+  __device__ __forceinline__ static void st4(V *p, const V (&v)[4]) {
+    if constexpr (sizeof(T) == 4) {
+      *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+      *reinterpret_cast<double2 *>(p) = make_double2(v[0], v[1]);
+      *reinterpret_cast<double2 *>(p + 2) = make_double2(v[2], v[3]);
+    }
+  }
+};
+
+template <bool SMALL, bool WAIT, typename W>
 __device__ __forceinline__ void fb_update_perturb_body(const double *__restrict__ loss, int64_t N, int half, double sigma,
                                                        float *__restrict__ zbuf, double momentum, double one_minus_m,
                                                        double epsilon, const double *__restrict__ audio,
                                                        double *__restrict__ grad_m, double *__restrict__ adver,
                                                        const FbCtlDev *__restrict__ ctl, uint64_t seed, uint32_t next_iter,
-                                                       uint32_t stream, int16_t *__restrict__ q, double *__restrict__ dist_part,
-                                                       double qscale, const int bidx, const int wait_seq, double *s_loss) {
+                                                       uint32_t stream, const W out, double *__restrict__ dist_part,
+                                                       const int bidx, const int wait_seq, double *s_loss, bool x_vec = true) {
   FN_STAMP(0);
   const int spd = 2 * half;
   double *s_a = s_loss + spd;
@@ -503,7 +550,7 @@ __device__ __forceinline__ void fb_update_perturb_body(const double *__restrict_
     a = a > hi ? hi : a;
     adver[n] = a;
     s_a[threadIdx.x] = a;
-    q[n] = fb_quantize(a, qscale);  // column 0 of the next batch: the clean adver
+    *out.at(n) = out.cvt(a);  // column 0 of the next batch: the clean adver
     const double d = fabs(__dsub_rn(au, a));
     dmax = d;
   } else {
@@ -542,19 +589,19 @@ __device__ __forceinline__ void fb_update_perturb_body(const double *__restrict_
       fb_noise4(seed, next_iter, stream, (uint32_t)(n4_0 + n4l), (uint32_t)j, zf);
     }
     float *zp = zbuf + (int64_t)j * N + n0;
-    int16_t *qp = q + (int64_t)(1 + j) * N + n0;
-    int16_t *qm = q + (int64_t)(1 + half + j) * N + n0;
-    int16_t vp[4], vm[4];
+    typename W::V *qp = out.at((int64_t)(1 + j) * N + n0);
+    typename W::V *qm = out.at((int64_t)(1 + half + j) * N + n0);
+    typename W::V vp[4], vm[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const double a = s_a[4 * n4l + k], z = (double)zf[k];
-      vp[k] = fb_quantize(__dadd_rn(__dmul_rn(sigma, z), a), qscale);   // noise_audios = sigma * noise + audio (:237)
-      vm[k] = fb_quantize(__dadd_rn(__dmul_rn(sigma, -z), a), qscale);
+      vp[k] = out.cvt(__dadd_rn(__dmul_rn(sigma, z), a));   // noise_audios = sigma * noise + audio (:237)
+      vm[k] = out.cvt(__dadd_rn(__dmul_rn(sigma, -z), a));
     }
-    if (cnt == 4 && ((N & 3) == 0)) {
+    if (cnt == 4 && ((N & 3) == 0) && x_vec) {
       *reinterpret_cast<float4 *>(zp) = make_float4(zf[0], zf[1], zf[2], zf[3]);
-      *reinterpret_cast<short4 *>(qp) = make_short4(vp[0], vp[1], vp[2], vp[3]);
-      *reinterpret_cast<short4 *>(qm) = make_short4(vm[0], vm[1], vm[2], vm[3]);
+      W::st4(qp, vp);
+      W::st4(qm, vm);
     } else {
       for (int k = 0; k < cnt; ++k) { zp[k] = zf[k]; qp[k] = vp[k]; qm[k] = vm[k]; }
     }

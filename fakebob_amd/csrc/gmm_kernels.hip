@@ -1215,7 +1215,7 @@ __global__ __launch_bounds__(512) void k_gmm_finalize_loss_update(FbGmmDev g, co
                                      ctl, trace, it, lin % B, lin / B, n_fin, pub_seq, n_fin <= (SMALL ? 512 : 1024) ? u.xch : nullptr, lin == n_fin - 1);
   } else {
     fb_update_perturb_body<SMALL, true>(u.loss, u.N, u.half, u.sigma, u.zbuf, u.momentum, u.one_minus_m, u.epsilon, u.audio, u.grad_m,
-                                        u.adver, ctl, u.seed, u.next_iter, u.stream, u.q, u.dist_part, u.qscale, lin - n_fin, pub_seq,
+                                        u.adver, ctl, u.seed, u.next_iter, u.stream, FbOutI16{u.q, u.qscale}, u.dist_part, lin - n_fin, pub_seq,
                                         s_dyn_upd);
   }
 }

@@ -154,6 +154,92 @@ void fb_launch_perturb_f64(hipStream_t s, const double *adver, const double *aud
                      noise_pos, x, dist_part, zbuf);
 }
 
+// Device-resident foreign model (fb_attack_dev / fb_get_grad_dev): k_perturb_f64's batch written straight into the
+// caller's device buffer x[B][N] as T -- float64 as it is, float32 rounded to nearest -- with the same distance partials
+// and zbuf normals.  Unlike k_perturb_f64 it honours the loop control: the host queues several iterations ahead, and
+// one queued behind the stopping iteration leaves x alone.
+template <typename T>
+__global__ __launch_bounds__(256) void k_perturb_x(const double *__restrict__ adver, const double *__restrict__ audio,
+                                                   int64_t N, int half, double sigma, uint64_t seed, uint32_t iter,
+                                                   uint32_t stream, const double *__restrict__ noise_pos, T *__restrict__ x,
+                                                   double *__restrict__ dist_part, float *__restrict__ zbuf,
+                                                   const int *__restrict__ stop, int x_vec) {
+  if (stop && *stop) return;
+  const int64_t n4 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int j = blockIdx.y;
+  const int64_t n0 = n4 * 4;
+  double dmax = 0.0;
+  if (n0 < N) {
+    const int cnt = (N - n0) >= 4 ? 4 : (int)(N - n0);
+    const bool vec = cnt == 4 && (N & 3) == 0;
+    double a[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) a[k] = (k < cnt) ? adver[n0 + k] : 0.0;
+    if (half > 0) {
+      double z[4];
+      if (noise_pos) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) z[k] = (k < cnt) ? noise_pos[(n0 + k) * half + j] : 0.0;
+      } else {
+        float zf[4];
+        fb_noise4(seed, iter, stream, (uint32_t)n4, (uint32_t)j, zf);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) z[k] = (double)zf[k];
+        if (zbuf) {
+          float *zp = zbuf + (int64_t)j * N + n0;
+          if (vec) *reinterpret_cast<float4 *>(zp) = make_float4(zf[0], zf[1], zf[2], zf[3]);
+          else for (int k = 0; k < cnt; ++k) zp[k] = zf[k];
+        }
+      }
+      const FbOutX<T> out{x};
+      T *xq = out.at((int64_t)(1 + j) * N + n0), *xr = out.at((int64_t)(1 + half + j) * N + n0);
+      T vp[4], vm[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        vp[k] = out.cvt(__dadd_rn(__dmul_rn(sigma, z[k]), a[k]));   // noise_audios = sigma * noise + audio (FAKEBOB.py:237)
+        vm[k] = out.cvt(__dadd_rn(__dmul_rn(sigma, -z[k]), a[k]));
+      }
+      if (vec && x_vec) {
+        FbOutX<T>::st4(xq, vp);
+        FbOutX<T>::st4(xr, vm);
+      } else {
+        for (int k = 0; k < cnt; ++k) { xq[k] = vp[k]; xr[k] = vm[k]; }
+      }
+    }
+    if (j == 0) {
+      for (int k = 0; k < cnt; ++k) {
+        x[n0 + k] = fb_to_x<T>(a[k]);
+        if (audio) { double d = fabs(__dsub_rn(audio[n0 + k], a[k])); dmax = d > dmax ? d : dmax; }
+      }
+    }
+  }
+  if (blockIdx.y == 0 && dist_part) {
+    __shared__ double red[4];
+    double m = fb_wave_max(dmax);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      double r = red[0];
+      for (int w = 1; w < (int)(blockDim.x >> 6); ++w) r = red[w] > r ? red[w] : r;
+      dist_part[blockIdx.x] = r;
+    }
+  }
+}
+// x_dtype: FB_DT_F32 / FB_DT_F64; x_vec: x is 16-byte aligned (vector stores where N allows them)
+void fb_launch_perturb_x(hipStream_t s, int x_dtype, const double *adver, const double *audio, int64_t N, int half,
+                         double sigma, uint64_t seed, uint32_t iter, uint32_t stream, const double *noise_pos, void *x,
+                         int x_vec, double *dist_part, int *n_dist_part, float *zbuf, const int *stop) {
+  int64_t n4 = (N + 3) / 4;
+  dim3 grid((unsigned)((n4 + 255) / 256), (unsigned)(half > 0 ? half : 1));
+  if (n_dist_part) *n_dist_part = (int)grid.x;
+  if (x_dtype == FB_DT_F32)
+    hipLaunchKernelGGL(k_perturb_x<float>, grid, dim3(256), 0, s, adver, audio, N, half, sigma, seed, iter, stream,
+                       noise_pos, static_cast<float *>(x), dist_part, zbuf, stop, x_vec);
+  else
+    hipLaunchKernelGGL(k_perturb_x<double>, grid, dim3(256), 0, s, adver, audio, N, half, sigma, seed, iter, stream,
+                       noise_pos, static_cast<double *>(x), dist_part, zbuf, stop, x_vec);
+}
+
 __global__ __launch_bounds__(256) void k_quantize(const double *__restrict__ x, int64_t n, double scale,
                                                   int16_t *__restrict__ q) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -190,8 +276,9 @@ void fb_launch_noise(hipStream_t s, uint64_t seed, uint32_t iter, uint32_t strea
 // (numpy-order sums and the loss body: fb_nes_device.h, shared with k_gmm_finalize_loss)
 // SMALL: samples_per_draw <= 128 -- numpy's sum is a single block then and the kernel needs no
 // recursion stack (the stack lives in scratch memory, which also slows the dispatch down)
-template <bool SMALL>
-__global__ __launch_bounds__(256) void k_loss(const double *__restrict__ raw, const int *__restrict__ tv,
+// TS: the element type of raw[] (float64, or a foreign model's float32 scores read from its own buffer)
+template <bool SMALL, typename TS>
+__global__ __launch_bounds__(256) void k_loss(const TS *__restrict__ raw, const int *__restrict__ tv,
                                               int B, int M, int task, int znorm_all, int attack_type,
                                               const double *__restrict__ z_mean,
                                               const double *__restrict__ z_std, double threshold,
@@ -206,19 +293,36 @@ __global__ __launch_bounds__(256) void k_loss(const double *__restrict__ raw, co
                              true_label, dist_part, n_dist_part, scores, loss, out, ctl, trace, it, s_lv, s_sc);
 }
 
+template <typename TS>
+static void launch_loss(hipStream_t s, const TS *raw, const int *tv, int B, int M, int task, int znorm_all,
+                        int attack_type, const double *z_mean, const double *z_std, double threshold,
+                        double adver_thresh, int target, int true_label, const double *dist_part,
+                        int n_dist_part, double *scores, double *loss, FbNesDev *out, FbCtlDev *ctl, double *trace,
+                        int it) {
+  if (B - 1 <= 128)
+    hipLaunchKernelGGL((k_loss<true, TS>), dim3(1), dim3(256), 0, s, raw, tv, B, M, task, znorm_all, attack_type, z_mean,
+                       z_std, threshold, adver_thresh, target, true_label, dist_part, n_dist_part, scores, loss, out,
+                       ctl, trace, it);
+  else
+    hipLaunchKernelGGL((k_loss<false, TS>), dim3(1), dim3(256), 0, s, raw, tv, B, M, task, znorm_all, attack_type, z_mean,
+                       z_std, threshold, adver_thresh, target, true_label, dist_part, n_dist_part, scores, loss, out,
+                       ctl, trace, it);
+}
 void fb_launch_loss(hipStream_t s, const double *raw, const int *tv, int B, int M, int task, int znorm_all,
                     int attack_type, const double *z_mean, const double *z_std, double threshold,
                     double adver_thresh, int target, int true_label, const double *dist_part,
                     int n_dist_part, double *scores, double *loss, FbNesDev *out, FbCtlDev *ctl, double *trace,
                     int it) {
-  if (B - 1 <= 128)
-    hipLaunchKernelGGL(k_loss<true>, dim3(1), dim3(256), 0, s, raw, tv, B, M, task, znorm_all, attack_type, z_mean,
-                       z_std, threshold, adver_thresh, target, true_label, dist_part, n_dist_part, scores, loss, out,
-                       ctl, trace, it);
-  else
-    hipLaunchKernelGGL(k_loss<false>, dim3(1), dim3(256), 0, s, raw, tv, B, M, task, znorm_all, attack_type, z_mean,
-                       z_std, threshold, adver_thresh, target, true_label, dist_part, n_dist_part, scores, loss, out,
-                       ctl, trace, it);
+  launch_loss(s, raw, tv, B, M, task, znorm_all, attack_type, z_mean, z_std, threshold, adver_thresh, target, true_label,
+              dist_part, n_dist_part, scores, loss, out, ctl, trace, it);
+}
+void fb_launch_loss(hipStream_t s, const float *raw, const int *tv, int B, int M, int task, int znorm_all,
+                    int attack_type, const double *z_mean, const double *z_std, double threshold,
+                    double adver_thresh, int target, int true_label, const double *dist_part,
+                    int n_dist_part, double *scores, double *loss, FbNesDev *out, FbCtlDev *ctl, double *trace,
+                    int it) {
+  launch_loss(s, raw, tv, B, M, task, znorm_all, attack_type, z_mean, z_std, threshold, adver_thresh, target, true_label,
+              dist_part, n_dist_part, scores, loss, out, ctl, trace, it);
 }
 
 // ------------------------------------------------------------- grad + update
@@ -314,7 +418,7 @@ __global__ __launch_bounds__(FB_UP_THREADS) void k_update_perturb(const double *
                                                         double qscale) {
   extern __shared__ double s_loss[];  // loss[1..spd], the block's updated samples [256], the block's normals [half][256]
   fb_update_perturb_body<SMALL, false>(loss, N, half, sigma, zbuf, momentum, one_minus_m, epsilon, audio, grad_m, adver, ctl, seed,
-                                       next_iter, stream, q, dist_part, qscale, (int)blockIdx.x, 0, s_loss);
+                                       next_iter, stream, FbOutI16{q, qscale}, dist_part, (int)blockIdx.x, 0, s_loss);
 }
 // returns the number of distance partials the launch writes (one per workgroup)
 int fb_launch_update_perturb(hipStream_t s, const double *loss, int64_t N, int half, double sigma, float *zbuf,
@@ -332,6 +436,47 @@ int fb_launch_update_perturb(hipStream_t s, const double *loss, int64_t N, int h
     hipLaunchKernelGGL(k_update_perturb<false>, dim3(blocks), dim3(FB_UP_THREADS), shm, s, loss, N, half, sigma, zbuf, momentum,
                        one_minus_m, epsilon, audio, grad_m, adver, ctl, seed, next_iter, stream, q, dist_part, qscale);
   return blocks;
+}
+
+// ... the same launch for a device-resident foreign model (fb_attack_dev): the batch of iteration next_iter goes into the
+// caller's x[B][N] as T instead of the int16 batch (FbOutX<T>)
+template <bool SMALL, typename T>
+__global__ __launch_bounds__(FB_UP_THREADS) void k_update_perturb_x(const double *__restrict__ loss, int64_t N, int half,
+                                                          double sigma, float *__restrict__ zbuf, double momentum,
+                                                          double one_minus_m, double epsilon,
+                                                          const double *__restrict__ audio, double *__restrict__ grad_m,
+                                                          double *__restrict__ adver, const FbCtlDev *__restrict__ ctl,
+                                                          uint64_t seed, uint32_t next_iter, uint32_t stream,
+                                                          T *__restrict__ x, int x_vec, double *__restrict__ dist_part) {
+  extern __shared__ double s_loss[];
+  fb_update_perturb_body<SMALL, false>(loss, N, half, sigma, zbuf, momentum, one_minus_m, epsilon, audio, grad_m, adver, ctl, seed,
+                                       next_iter, stream, FbOutX<T>{x}, dist_part, (int)blockIdx.x, 0, s_loss, x_vec != 0);
+}
+template <typename T>
+static void launch_update_perturb_x(hipStream_t s, const double *loss, int64_t N, int half, double sigma, float *zbuf,
+                                    double momentum, double one_minus_m, double epsilon, const double *audio,
+                                    double *grad_m, double *adver, const FbCtlDev *ctl, uint64_t seed, uint32_t next_iter,
+                                    uint32_t stream, T *x, int x_vec, double *dist_part) {
+  const int blocks = (int)((N + 255) / 256);
+  const size_t shm = sizeof(double) * (size_t)(2 * half + 256) + sizeof(float) * 256 * (size_t)(half > 0 ? half : 1);
+  if (2 * half <= 128)
+    hipLaunchKernelGGL((k_update_perturb_x<true, T>), dim3(blocks), dim3(FB_UP_THREADS), shm, s, loss, N, half, sigma, zbuf,
+                       momentum, one_minus_m, epsilon, audio, grad_m, adver, ctl, seed, next_iter, stream, x, x_vec, dist_part);
+  else
+    hipLaunchKernelGGL((k_update_perturb_x<false, T>), dim3(blocks), dim3(FB_UP_THREADS), shm, s, loss, N, half, sigma, zbuf,
+                       momentum, one_minus_m, epsilon, audio, grad_m, adver, ctl, seed, next_iter, stream, x, x_vec, dist_part);
+}
+int fb_launch_update_perturb_x(hipStream_t s, int x_dtype, const double *loss, int64_t N, int half, double sigma,
+                               float *zbuf, double momentum, double one_minus_m, double epsilon, const double *audio,
+                               double *grad_m, double *adver, const FbCtlDev *ctl, uint64_t seed, uint32_t next_iter,
+                               uint32_t stream, void *x, int x_vec, double *dist_part) {
+  if (x_dtype == FB_DT_F32)
+    launch_update_perturb_x(s, loss, N, half, sigma, zbuf, momentum, one_minus_m, epsilon, audio, grad_m, adver, ctl, seed,
+                            next_iter, stream, static_cast<float *>(x), x_vec, dist_part);
+  else
+    launch_update_perturb_x(s, loss, N, half, sigma, zbuf, momentum, one_minus_m, epsilon, audio, grad_m, adver, ctl, seed,
+                            next_iter, stream, static_cast<double *>(x), x_vec, dist_part);
+  return (int)((N + 255) / 256);
 }
 
 void fb_launch_grad_update(hipStream_t s, const double *loss, int64_t N, int half, double sigma,

@@ -353,6 +353,106 @@ class Engine(object):
             self._raise_cb(err, ex)
         return adv, flag.value, adv_f, trace[:nt.value]
 
+    # ---- NES with a foreign model on the same GPU: the batch and the scores stay in device memory
+    def _dev_model(self, params, S, n, x, scores, look_every):
+        """fb_dev_model over the torch tensors x [B, N] and scores [B, S] (float32 / float64, on this engine's device)."""
+        torch = N.torch_first()
+        B = 2 * (params.samples_per_draw // 2) + 1
+        dts = {torch.float32: N.FB_DT_F32, torch.float64: N.FB_DT_F64}
+        for name, t, want in (("x", x, B * n), ("scores", scores, B * S)):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError("%s must be a torch tensor (got %s)" % (name, type(t).__name__))
+            if t.device.type != "cuda" or t.device.index != self.device:
+                raise ValueError("%s is on %s: the device path needs a tensor on cuda:%d" % (name, t.device, self.device))
+            if t.dtype not in dts:
+                raise ValueError("%s has dtype %s: float32 or float64" % (name, t.dtype))
+            if not t.is_contiguous() or t.numel() != want:
+                raise ValueError("%s must be contiguous with %d elements (got %s)" % (name, want, tuple(t.shape)))
+        m = N.DevModel()
+        m.x_dtype, m.x = dts[x.dtype], x.data_ptr()
+        m.score_dtype, m.scores = dts[scores.dtype], scores.data_ptr()
+        m.look_every = int(look_every)
+        N.check_one_hip_runtime()
+        return m
+
+    def _score_dev_cb(self, score_fn, x, scores, S, err):
+        """score_fn(x) -> [B, S] scores on the device, run on the engine's stream and copied into `scores`, wrapped as an
+        fb_score_dev_cb.  x is the engine's batch buffer itself, rewritten by the next iteration.  An exception raised by
+        the model is kept in err[0] and re-raised by the caller, as _score_cb does."""
+        torch = N.torch_first()
+        ext = []
+
+        def _cb(_ctx, stream, n, b, s):
+            try:
+                if not ext:
+                    ext.append(torch.cuda.ExternalStream(stream, device=torch.device("cuda", self.device)))
+                with torch.cuda.stream(ext[0]):
+                    out = score_fn(x.view(b, n))
+                    if not isinstance(out, torch.Tensor):
+                        out = torch.as_tensor(out, device=scores.device)
+                    scores.view(b, s).copy_(out.reshape(b, s))
+                return 0
+            except BaseException as ex:  # noqa: BLE001
+                err[0] = ex
+                return 1
+        return N.SCORE_DEV_CB(_cb)
+
+    def get_grad_dev(self, params, S, score_fn, x, scores, audio, it=0, noise_pos=None):
+        """fb_get_grad_dev: one NES gradient estimate at `audio`, the batch written into the torch tensor x [B, N] and
+        scored by score_fn on the GPU into scores [B, S]."""
+        audio = np.ascontiguousarray(audio, np.float64).reshape(-1)
+        n = audio.size
+        npz = None if noise_pos is None else np.ascontiguousarray(noise_pos, np.float64)
+        if npz is not None and npz.shape != (n, params.samples_per_draw // 2):
+            raise ValueError("noise_pos must be (N, samples_per_draw//2)")
+        m = self._dev_model(params, S, n, x, scores, 0)
+        grad = np.empty(n, np.float64)
+        fl, al = C.c_double(), C.c_double()
+        sc = np.empty(S, np.float64)
+        err = [None]
+        cb = self._score_dev_cb(score_fn, x, scores, S, err)
+        try:
+            N.check(self._L.fb_get_grad_dev(self._h, C.byref(params), C.c_int(S), C.byref(m), cb, None, N.ptr(audio),
+                                            C.c_int64(n), C.c_uint32(it), None if npz is None else N.ptr(npz),
+                                            C.byref(fl), N.ptr(grad), C.byref(al), N.ptr(sc)))
+        except N.NativeError as ex:
+            self._raise_cb(err, ex)
+        return fl.value, grad, al.value, sc
+
+    def attack_dev(self, params, S, score_fn, x, scores, audio, noise_all=None, look_every=0):
+        """fb_attack_dev: the whole attack loop around a model on the GPU -> (int16 adv, flag, float64 adv, trace).
+        look_every: iterations between the host's looks at the loop control (0: 4)."""
+        audio = np.ascontiguousarray(audio, np.float64).reshape(-1)
+        n = audio.size
+        na = None if noise_all is None else np.ascontiguousarray(noise_all, np.float64)
+        m = self._dev_model(params, S, n, x, scores, look_every)
+        adv = np.empty(n, np.int16)
+        adv_f = np.empty(n, np.float64)
+        trace = np.zeros((max(params.max_iter, 1), 3 + S), np.float64)
+        nt, flag = C.c_int(), C.c_int()
+        err = [None]
+        cb = self._score_dev_cb(score_fn, x, scores, S, err)
+        try:
+            N.check(self._L.fb_attack_dev(self._h, C.byref(params), C.c_int(S), C.byref(m), cb, None, N.ptr(audio),
+                                          C.c_int64(n), None if na is None else N.ptr(na), N.ptr(adv), N.ptr(adv_f),
+                                          N.ptr(trace), C.byref(nt), C.byref(flag)))
+        except N.NativeError as ex:
+            self._raise_cb(err, ex)
+        return adv, flag.value, adv_f, trace[:nt.value]
+
+    _FOREIGN_PATH = {1: "host", 2: "device"}
+    _DT = {0: "float32", 1: "float64"}
+
+    def debug_foreign_path(self):
+        """The last foreign-model call (fb_debug_foreign_path): a dict of path ("host" / "device"), x_dtype and
+        score_dtype, launches_per_iter, model_calls, batch_bytes_d2h and score_bytes_h2d (during the loop)."""
+        info = N.ForeignPathInfo()
+        N.check(self._L.fb_debug_foreign_path(self._h, C.byref(info)))
+        return dict(path=self._FOREIGN_PATH[info.path], x_dtype=self._DT[info.x_dtype],
+                    score_dtype=self._DT[info.score_dtype], launches_per_iter=int(info.launches_per_iter),
+                    model_calls=int(info.model_calls), batch_bytes_d2h=int(info.batch_bytes_d2h),
+                    score_bytes_h2d=int(info.score_bytes_h2d))
+
     def estimate_threshold(self, params, model_threshold, audio, noise_all=None, max_total_iters=100000):
         audio = np.ascontiguousarray(audio, np.float64).reshape(-1)
         n = audio.size

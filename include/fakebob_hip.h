@@ -21,6 +21,8 @@
  *   fb_attack                 FakeBob.attack (FAKEBOB.py:139-221)
  *   fb_estimate_threshold     FakeBob.estimate_threshold (FAKEBOB.py:39-137)
  *   fb_get_grad_ext / fb_attack_ext   the same around a foreign `model` (README.md:136)
+ *   fb_get_grad_dev / fb_attack_dev   ... around a foreign model that runs on the
+ *                             same GPU: the batch and the scores stay on the device
  *
  * Test / profiling hooks (no reference counterpart) live in fakebob_hip_test.h.
  *
@@ -233,6 +235,46 @@ int fb_get_grad_ext(fb_engine *e, const fb_nes_params *p, int S, fb_score_cb cb,
                     const double *audio, int64_t N, uint32_t iter, const double *noise_pos,
                     double *final_loss, double *grad, double *adver_loss, double *score0);
 int fb_attack_ext(fb_engine *e, const fb_nes_params *p, int S, fb_score_cb cb, void *cb_ctx,
+                  const double *audio, int64_t N, const double *noise_all, int16_t *adv_i16,
+                  double *adver_f64, double *trace, int *n_trace, int *success_flag);
+
+/* ---- foreign models on the same GPU --------------------------------------------------------------------------
+ * The plugin API above for a model that runs on the engine's GPU (a PyTorch model, say): the engine writes each NES
+ * batch into the caller's device buffer x, the model reads it and writes its scores into the caller's device buffer
+ * `scores`, in the order of the engine's stream, and the loss reads them there.  No copy of the batch or of the scores
+ * passes through the host; on the Philox path with samples_per_draw / 2 <= 40 an iteration is 2 engine launches
+ * (the loss; the momentum sign step fused with the next batch) around the model's own work.
+ *
+ * - Arguments, outputs, trace rows, the success flag and fb_attack_iter_seconds behave as in fb_get_grad_ext /
+ *   fb_attack_ext; S, task, target and the other parameters are checked the same way.
+ * - x[B][N] is utterance-major, rows exactly as fb_attack_ext's `audios`.  A float64 batch holds the same bits the
+ *   host path hands its callback; each float32 element is the round-to-nearest of that float64 value (it equals
+ *   torch.from_numpy(x64).float()).
+ * - scores[B][S]: float32 scores are widened exactly to float64 before the loss.
+ * - x and scores must be device memory on the engine's device (checked with hipPointerGetAttributes, and against the
+ *   allocation's extent where the runtime reports it): a host or foreign-device pointer or a bad dtype is FB_E_ARG.
+ * - The callback enqueues the model on `stream` (the engine's hipStream_t): it reads x and writes scores in stream
+ *   order and returns 0; it may return before its work has run.  A non-zero return gives FB_E_CALLBACK.
+ * - Both calls return only after the engine stream is idle: the caller may free or reuse its buffers afterwards.
+ * - fb_attack_dev reads the loop control block every m->look_every iterations.  Iterations queued after the stopping
+ *   one are no-ops on the device; the model may be called up to look_every - 1 more times and those scores are
+ *   ignored.  With look_every = 1 the model is called exactly once per executed iteration, as in the host path. */
+#define FB_DT_F32 0
+#define FB_DT_F64 1
+typedef struct {
+  int x_dtype;        /* FB_DT_*: element type of the batch the engine writes */
+  void *x;            /* caller-owned device buffer [B][N], utterance-major, rows exactly as fb_attack_ext's `audios` */
+  int score_dtype;    /* FB_DT_*: element type the model writes */
+  void *scores;       /* caller-owned device buffer [B][S] */
+  int look_every;     /* fb_attack_dev: the host reads the loop control block every this many iterations; 0 = 4 */
+} fb_dev_model;
+/* Enqueue the model on `stream` (the engine's hipStream_t): read x and write scores in stream order; return 0.
+ * The callback may return before its work has run. */
+typedef int (*fb_score_dev_cb)(void *ctx, void *stream, int64_t N, int B, int S);
+int fb_get_grad_dev(fb_engine *e, const fb_nes_params *p, int S, const fb_dev_model *m, fb_score_dev_cb cb, void *ctx,
+                    const double *audio, int64_t N, uint32_t iter, const double *noise_pos,
+                    double *final_loss, double *grad, double *adver_loss, double *score0);
+int fb_attack_dev(fb_engine *e, const fb_nes_params *p, int S, const fb_dev_model *m, fb_score_dev_cb cb, void *ctx,
                   const double *audio, int64_t N, const double *noise_all, int16_t *adv_i16,
                   double *adver_f64, double *trace, int *n_trace, int *success_flag);
 

@@ -66,6 +66,24 @@ int fb_debug_launch_shape(fb_engine *e, int *info);
 #define FB_SHAPE_GMM_FX2 2           /* k_gmm_fx2 */
 #define FB_SHAPE_GMM_BX3 3           /* k_gmm_bx3 */
 
+/* The last foreign-model call (fb_get_grad_ext / fb_attack_ext or fb_get_grad_dev / fb_attack_dev): path (FB_FOREIGN_*),
+ * the batch and score dtypes (FB_DT_*; the host path hands its callback float64 and reads float64 back), the engine
+ * launches of one NES iteration, the model calls, and the bytes of the batch copied device -> host and of the scores
+ * copied host -> device during the loop (final outputs and control-block reads not counted).  Recorded on the host as
+ * the work is enqueued.  FB_E_STATE before the first foreign call. */
+#define FB_FOREIGN_HOST 1   /* fb_get_grad_ext / fb_attack_ext */
+#define FB_FOREIGN_DEV 2    /* fb_get_grad_dev / fb_attack_dev */
+typedef struct {
+  int path;
+  int x_dtype;
+  int score_dtype;
+  int launches_per_iter;
+  int64_t model_calls;
+  int64_t batch_bytes_d2h;
+  int64_t score_bytes_h2d;
+} fb_foreign_path_info;
+int fb_debug_foreign_path(fb_engine *e, fb_foreign_path_info *info);
+
 /* Which diagonal-GMM arithmetic the loaded model runs on: 2 = two-term f16 split (k_gmm_fx2w / k_gmm_fx2, default),
  * 1 = exact three-term bf16 split (k_gmm_bx3: chosen automatically when a parameter does not fit f16's exponent
  * range; FB_GMM_MODE=bx3 forces it).  Negative FB_E_* without a model.
