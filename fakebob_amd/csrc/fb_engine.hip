@@ -1079,7 +1079,7 @@ extern "C" int fb_num_speakers(fb_engine *e) {
 // Prepares offsets for a batch whose int16 samples are already in e->wav.
 static int prepare_batch(fb_engine *e, const int64_t *off, int B) {
   e->bench_it = -1;  // whatever attack fb_bench_nes left resident is gone with the batch layout
-  if (e->vad_counter.p) HIPCHK(hipMemsetAsync(e->vad_counter.p, 0, sizeof(int), e->stream));  // see run_attack_core
+  if (e->vad_counter.p) HIPCHK(hipMemsetAsync(e->vad_counter.p, 0, sizeof(int), e->stream));  // see ctl_reset
   e->h_wav_off.assign(off, off + B + 1);
   e->h_frame_off.resize(B + 1);
   e->h_chunk_off.resize(B + 1);
@@ -1957,13 +1957,8 @@ extern "C" int fb_last_ivectors(fb_engine *e, int B, double *ivecs) {
 }
 
 // --------------------------------------------------------------------- NES
-static int check_params(fb_engine *e, const fb_nes_params *p, int64_t N) {
-  if (!e || !p) return fb_fail(FB_E_ARG, "null argument");
-  if (!e->have_gmm) return fb_fail(FB_E_STATE, "no model loaded");
-  if (N <= 0) return fb_fail(FB_E_ARG, "empty audio");
-  if (p->task != e->task) return fb_fail(FB_E_ARG, "params.task %d != engine system task %d", p->task, e->task);
-  const int S = fb_num_speakers(e);
-  if (S > 62) return fb_fail(FB_E_ARG, "more than 62 speakers unsupported in the NES result block");
+// the checks of fb_nes_params every NES call makes, for a system of S speakers
+static int check_nes_params(const fb_nes_params *p, int S) {
   if (p->samples_per_draw < 0 || p->samples_per_draw > 4094) return fb_fail(FB_E_ARG, "bad samples_per_draw");
   if (p->task != FB_TASK_SV && p->attack_type == FB_TARGETED && (p->target < 0 || p->target >= S))
     return fb_fail(FB_E_ARG, "target %d out of range", p->target);
@@ -1972,6 +1967,16 @@ static int check_params(fb_engine *e, const fb_nes_params *p, int64_t N) {
   if (!(p->sigma > 0.0) && p->samples_per_draw >= 2) return fb_fail(FB_E_ARG, "sigma must be > 0");
   if (p->bits_per_sample != 0 && (p->bits_per_sample < 2 || p->bits_per_sample > 16))
     return fb_fail(FB_E_ARG, "bits_per_sample %d unsupported (2 .. 16)", p->bits_per_sample);
+  return FB_OK;
+}
+static int check_params(fb_engine *e, const fb_nes_params *p, int64_t N) {
+  if (!e || !p) return fb_fail(FB_E_ARG, "null argument");
+  if (!e->have_gmm) return fb_fail(FB_E_STATE, "no model loaded");
+  if (N <= 0) return fb_fail(FB_E_ARG, "empty audio");
+  if (p->task != e->task) return fb_fail(FB_E_ARG, "params.task %d != engine system task %d", p->task, e->task);
+  const int S = fb_num_speakers(e);
+  if (S > 62) return fb_fail(FB_E_ARG, "more than 62 speakers unsupported in the NES result block");
+  FBCHK(check_nes_params(p, S));
   if (num_frames(e->cfg, N) <= 0) return fb_fail(FB_E_ARG, "audio shorter than one frame");
   return FB_OK;
 }
@@ -2026,10 +2031,60 @@ static bool fb_fuse_on(const fb_engine *e) {
   if (e->fuse_opt >= 0) return e->fuse_opt != 0;  // fb_set_fused_chain
   return getenv("FB_NO_FUSE") == nullptr;  // FB_NO_FUSE=1: the 8-launch chain (A/B, debugging; read per call)
 }
+
+// Who scores the NES batch: this library's own system, a host callback (fb_score_cb) or a model on the same GPU
+// (fb_score_dev_cb writing into fb_dev_model's buffers)
+enum FbScorerKind { FB_SCORER_NATIVE, FB_SCORER_HOST, FB_SCORER_DEV };
+struct FbScorer {
+  FbScorerKind kind;
+  int S = 0;                            // speakers scored (the native systems': filled in by nes_setup)
+  fb_score_cb cb = nullptr;             // FB_SCORER_HOST
+  const fb_dev_model *m = nullptr;      // FB_SCORER_DEV
+  fb_score_dev_cb dcb = nullptr;
+  void *ctx = nullptr;                  // the callback's
+};
+
+// How an attack's NES loop runs, fixed at the start of the public call: the A/B knobs are read from the environment
+// there and nowhere in the loop (attack threads run it while the process may change its environment, and getenv
+// racing setenv is undefined).  The default -- the host-callback path -- looks after every iteration and fuses nothing.
+struct FbLoopKnobs {
+  int look = 1;             // iterations queued per look at the control block
+  bool fuse_fin = false;    // the GMM finalisation and the loss in one launch (fb_fuse_part(e, 1))
+  bool fuse_upd = false;    // the momentum step and the next batch in one launch (fb_fuse_part(e, 2); the device path)
+  bool upd_in_fin = false;  // ... riding in the finalising launch (FB_FUSE_UPD=0: two launches)
+  bool fin_ticket = false;  // FB_FIN_TICKET=1: the finalising launch's roles by an arrival ticket
+  bool fin_xch = false;     // its exchange slots (FB_FIN_COUNTER=1: the arrival counter instead)
+};
+static FbLoopKnobs loop_knobs(const fb_engine *e, const FbScorer &sc) {
+  FbLoopKnobs k;
+  if (sc.kind == FB_SCORER_DEV) {
+    k.look = sc.m->look_every > 0 ? sc.m->look_every : 4;
+    k.fuse_upd = true;
+  } else if (sc.kind == FB_SCORER_NATIVE) {
+    // Iterations queued per host round trip.  Beyond ~4 the host is off the critical path anyway, and
+    // every iteration queued behind the stopping one is (cheap, but not free) wasted work.
+    const char *ev = getenv("FB_ATTACK_BATCH");
+    const int b = ev ? atoi(ev) : 4;
+    k.look = b < 1 ? 1 : (b > 16 ? 16 : b);
+    k.fuse_fin = fb_fuse_part(e, 1);
+    k.fuse_upd = fb_fuse_part(e, 2);
+    const char *fu = getenv("FB_FUSE_UPD");
+    k.upd_in_fin = !(fu && fu[0] == '0');
+    const char *tk = getenv("FB_FIN_TICKET");
+    k.fin_ticket = tk && tk[0] == '1';
+    k.fin_xch = getenv("FB_FIN_COUNTER") == nullptr;
+  }
+  return k;
+}
+// the momentum sign step of iteration i and the batch of i + 1 in one launch: Philox noise and a small enough batch
+static bool fuses_update(const FbLoopKnobs &kn, const double *noise, int half) {
+  return kn.fuse_upd && !noise && half > 0 && half <= FB_FUSE_MAX_HALF;
+}
+
 static int enqueue_get_grad(fb_engine *e, const fb_nes_params *p, int64_t N, uint32_t iter,
-                            const double *noise_dev, bool with_dist, FbCtlDev *ctl = nullptr,
-                            double *trace_dev = nullptr, int trace_row = 0, const FbUpdArgs *upd = nullptr,
-                            bool *upd_done = nullptr) {
+                            const double *noise_dev, bool with_dist, const FbLoopKnobs &kn = FbLoopKnobs(),
+                            FbCtlDev *ctl = nullptr, double *trace_dev = nullptr, int trace_row = 0,
+                            const FbUpdArgs *upd = nullptr, bool *upd_done = nullptr) {
   const int half = p->samples_per_draw / 2, B = 2 * half + 1;
   int ndp = 0;
   const int *stop = ctl ? &ctl->stop : nullptr;
@@ -2044,7 +2099,7 @@ static int enqueue_get_grad(fb_engine *e, const fb_nes_params *p, int64_t N, uin
   }
   e->pre_iter = -1;
   // GMM systems inside the device-controlled loop: finalisation and loss share one launch
-  const bool fuse_fin = ctl && e->kind == 0 && fb_fuse_part(e, 1);
+  const bool fuse_fin = ctl && e->kind == 0 && kn.fuse_fin;
   e->defer_finalize = fuse_fin;
   if (e->kind == 1) {  // i-vector systems: the loss body rides in the tail of the solve kernel when the batch allows it
     FbIvTail &t = e->tail_req;
@@ -2077,13 +2132,12 @@ static int enqueue_get_grad(fb_engine *e, const fb_nes_params *p, int64_t N, uin
       // roles by blockIdx (the default again, round 6); FB_FIN_TICKET=1: by an arrival ticket (round 6's first answer to the
       // advisor's finding -- 494 returning atomics on one word in front of every workgroup's work: 6.8 us per iteration of
       // a lone attack, tools/profile/r06_fin.sh).  See the note at k_gmm_finalize_loss_update for why the launch cannot
-      // deadlock either way (read per launch: A/B inside one process)
-      const char *tk_env = getenv("FB_FIN_TICKET");
+      // deadlock either way (A/B between calls: FbLoopKnobs)
       ux = *upd;
-      ux.role_ticket = (tk_env && tk_env[0] == '1') ? e->fin_counter.as<int>() + 1 : nullptr;
+      ux.role_ticket = kn.fin_ticket ? e->fin_counter.as<int>() + 1 : nullptr;
       upd = &ux;
     }
-    if (upd && getenv("FB_FIN_COUNTER") == nullptr) {  // (FB_FIN_COUNTER=1: the arrival counter instead of the exchange slots, A/B)
+    if (upd && kn.fin_xch) {  // (FB_FIN_COUNTER=1: the arrival counter instead of the exchange slots, A/B)
       const size_t had = e->fin_xch.cap;
       FBCHK(e->fin_xch.ensure(sizeof(unsigned long long) * (size_t)B * e->gmm.M));
       if (e->fin_xch.cap != had || !e->fin_xch_clean) {
@@ -2108,146 +2162,15 @@ static int enqueue_get_grad(fb_engine *e, const fb_nes_params *p, int64_t N, uin
   return FB_OK;
 }
 
-// The NES loop of FakeBob.attack (FAKEBOB.py:171-216) with the loop control on the device
-// (FbCtlDev): `count` iterations starting at Philox iteration index `it_base` are queued `batch` at
-// a time; the host reads the control block once per batch.  reset: start a new attack (lr = max_lr,
-// empty loss history); otherwise continue the previous state (bench warm-up -> timed region).
-// trace_dev rows are indexed from it_base.
-static int attack_batch_size(const fb_engine *e) {
-  // Iterations queued per host round trip.  Beyond ~4 the host is off the critical path anyway, and
-  // every iteration queued behind the stopping one is (cheap, but not free) wasted work.
-  (void)e;
-  const char *ev = getenv("FB_ATTACK_BATCH");
-  int k = ev ? atoi(ev) : 4;
-  return k < 1 ? 1 : (k > 16 ? 16 : k);
-}
-static int run_attack_core(fb_engine *e, const fb_nes_params *p, int64_t N, const double *noise_all, int it_base,
-                           int count, bool reset, bool disable_stop, double *trace_dev,
-                           unsigned long long *ticks = nullptr) {
-  const int half = p->samples_per_draw / 2;
-  FBCHK(e->ctl.ensure(sizeof(FbCtlDev)));
-  FBCHK(e->ctl_ls.ensure(sizeof(double) * (size_t)(p->plateau_length > 0 ? p->plateau_length : 1)));
-  FbCtlDev *ctl = e->ctl.as<FbCtlDev>();
-  if (reset) {
-    e->pre_iter = -1;
-    // The ticket of k_vad_delta_cmvn and the arrival counter of k_gmm_finalize_loss are left at zero by every launch
-    // that completes; one that was aborted or failed would leave them elsewhere and every later launch would then
-    // mis-assign utterances / skip its loss body.  A new attack starts them clean.
-    if (e->vad_counter.p) HIPCHK(hipMemsetAsync(e->vad_counter.p, 0, sizeof(int), e->stream));
-    if (e->fin_counter.p) HIPCHK(hipMemsetAsync(e->fin_counter.p, 0, 2 * sizeof(int), e->stream));
-    e->fin_xch_clean = false;  // (refilled with sentinels before its next use)
-    if (e->iv_tail_counter.p) HIPCHK(hipMemsetAsync(e->iv_tail_counter.p, 0, sizeof(int), e->stream));
-    e->vad_part_B = -1;  // ... and k_vad_delta_cmvn_p's exchange slots are refilled with sentinels (run_post_mfcc)
-    FbCtlDev h;
-    memset(&h, 0, sizeof(h));
-    h.lr = p->max_lr; h.min_lr = p->min_lr; h.plateau_drop = p->plateau_drop;
-    h.ls = e->ctl_ls.as<double>();
-    h.plateau_length = p->plateau_length;
-    h.disable_stop = disable_stop ? 1 : 0;
-    h.ticks = ticks;
-    e->ctl_seq = 0;   // (h.pub_seq = 0: the loss bodies of this attack count from 1)
-    *e->h_ctl = h;
-    HIPCHK(hipMemcpyAsync(ctl, e->h_ctl, sizeof(FbCtlDev), hipMemcpyHostToDevice, e->stream));
-    FBCHK(sync_stream(e));  // h_ctl is reused for the read-back below
-    if (ticks) fb_launch_stamp(e->stream, ticks);
-  }
-  const double one_minus_m = 1.0 - p->momentum;
-  const int K = attack_batch_size(e);
-  int done = 0;
-  while (done < count) {
-    const int nb = count - done < K ? count - done : K;
-    for (int k = 0; k < nb; ++k) {
-      const int it = it_base + done + k;
-      const double *noise_dev = nullptr;
-      if (noise_all && half > 0) {
-        FBCHK(h2d(e, e->noise.p, noise_all + (size_t)it * N * half, sizeof(double) * (size_t)N * half));
-        noise_dev = e->noise.as<double>();
-      }
-      if (fb_debug_sync_on()) fprintf(stderr, "[fb] iteration %d\n", it);
-      // GMM systems on the fused chain: the update of this iteration and the batch of the next one ride in the launch
-      // that finalises the scores and runs the loss body (k_gmm_finalize_loss_update; FB_FUSE_UPD=0: two launches)
-      // (at most FB_FUSE_MAX_UPD_WG update workgroups in the finalising launch: the bound its no-deadlock argument needs)
-      const bool upd_ok = !noise_dev && half > 0 && half <= FB_FUSE_MAX_HALF && fb_fuse_part(e, 1) && fb_fuse_part(e, 2) &&
-                          (N + 255) / 256 <= FB_FUSE_MAX_UPD_WG;
-      const char *fu_env = getenv("FB_FUSE_UPD");   // (read per iteration: A/B inside one process)
-      const bool no_fuse_upd = fu_env && fu_env[0] == '0';
-      FbUpdArgs ua = {};
-      bool upd_done = false;
-      if (upd_ok && e->kind == 0 && !no_fuse_upd) {
-        ua.loss = e->loss.as<double>(); ua.N = N; ua.half = half; ua.sigma = p->sigma; ua.zbuf = e->zbuf.as<float>();
-        ua.momentum = p->momentum; ua.one_minus_m = one_minus_m; ua.epsilon = p->epsilon; ua.audio = e->audio.as<double>();
-        ua.grad_m = e->grad_m.as<double>(); ua.adver = e->adver.as<double>(); ua.seed = p->seed; ua.next_iter = (uint32_t)(it + 1);
-        ua.stream = p->stream; ua.q = e->wav.as<int16_t>(); ua.dist_part = e->dist_part.as<double>();
-        ua.qscale = ldexp(1.0, nes_bits(p) - 1);
-      }
-      FBCHK(enqueue_get_grad(e, p, N, (uint32_t)it, noise_dev, true, ctl, trace_dev, it - it_base, ua.loss ? &ua : nullptr, &upd_done));
-      FB_DBG_SYNC(e, "loss");
-      if (upd_done) {
-        e->pre_ndp = (int)((N + 255) / 256);
-        e->pre_iter = (long long)it + 1;
-      } else if (!noise_dev && half > 0 && half <= FB_FUSE_MAX_HALF && fb_fuse_part(e, 2)) {
-        // momentum sign step of this iteration + the perturbed batch of the next one in a single launch
-        e->pre_ndp = fb_launch_update_perturb(e->stream, e->loss.as<double>(), N, half, p->sigma, e->zbuf.as<float>(),
-                                              p->momentum, one_minus_m, p->epsilon, e->audio.as<double>(),
-                                              e->grad_m.as<double>(), e->adver.as<double>(), ctl, p->seed,
-                                              (uint32_t)(it + 1), p->stream, e->wav.as<int16_t>(),
-                                              e->dist_part.as<double>(), nes_bits(p));
-        e->pre_iter = (long long)it + 1;
-      } else {
-        fb_launch_grad_update(e->stream, e->loss.as<double>(), N, half, p->sigma, e->zbuf.as<float>(), noise_dev,
-                              nullptr, 1, p->momentum, one_minus_m, 0.0, p->epsilon, e->audio.as<double>(),
-                              e->grad_m.as<double>(), e->adver.as<double>(), ctl);
-      }
-    }
-    HIPCHK(hipMemcpyAsync(e->h_ctl, ctl, sizeof(FbCtlDev), hipMemcpyDeviceToHost, e->stream));
-    FBCHK(sync_stream(e));
-    if (e->gmm_pending) FBCHK(time_collect(e));
-    if (e->h_ctl->err != 0)
-      return fb_fail(FB_E_NO_VOICED, "NES sample %d has no voiced frames", e->h_ctl->err - 1);
-    done += nb;
-    if (e->h_ctl->stop) break;
-  }
-  return FB_OK;
-}
-
-static int fetch_out(fb_engine *e) {
+// the NES result block of the last iteration to the host (native: with the GMM timing of fb_bench_nes)
+static int fetch_out(fb_engine *e, bool native) {
   HIPCHK(hipMemcpyAsync(e->h_out, e->nes_out.p, sizeof(FbNesDev), hipMemcpyDeviceToHost, e->stream));
   FBCHK(sync_stream(e));
-  if (e->gmm_pending) FBCHK(time_collect(e));
-  if (e->h_out->err != 0)
+  if (native && e->gmm_pending) FBCHK(time_collect(e));
+  if (e->h_out->err != 0)  // (never set for a foreign model: see attack_loop)
     return fb_fail(FB_E_NO_VOICED, "NES sample %d has no voiced frames", e->h_out->err - 1);
   return FB_OK;
 }
-
-extern "C" int fb_get_grad(fb_engine *e, const fb_nes_params *p, const double *audio, int64_t N, uint32_t iter,
-                           const double *noise_pos, double *final_loss, double *grad, double *adver_loss,
-                           double *score0) {
-  if (e) e->bench_it = -1;
-  if (!audio) return fb_fail(FB_E_ARG, "audio is NULL");
-  FBCHK(check_params(e, p, N));
-  HIPCHK(hipSetDevice(e->device));
-  const int half = p->samples_per_draw / 2, B = 2 * half + 1, S = fb_num_speakers(e);
-  FBCHK(prepare_nes_batch(e, N, B));
-  FBCHK(ensure_nes_buffers(e, N, B));
-  FBCHK(h2d(e, e->adver.p, audio, sizeof(double) * (size_t)N));
-  const double *noise_dev = nullptr;
-  if (noise_pos && half > 0) {
-    FBCHK(e->noise.ensure(sizeof(double) * (size_t)N * half));
-    FBCHK(h2d(e, e->noise.p, noise_pos, sizeof(double) * (size_t)N * half));
-    noise_dev = e->noise.as<double>();
-  }
-  FBCHK(enqueue_get_grad(e, p, N, iter, noise_dev, false));
-  fb_launch_grad_update(e->stream, e->loss.as<double>(), N, half, p->sigma, e->zbuf.as<float>(), noise_dev,
-                        e->grad.as<double>(), 0, 0.0, 0.0, 0.0, 0.0, nullptr, nullptr, nullptr);
-  if (grad) FBCHK(d2h(e, grad, e->grad.p, sizeof(double) * (size_t)N));
-  FBCHK(fetch_out(e));
-  e->nes_iters += 1;
-  if (final_loss) *final_loss = e->h_out->final_loss;
-  if (adver_loss) *adver_loss = e->h_out->adver_loss;
-  if (score0) for (int s = 0; s < S; ++s) score0[s] = e->h_out->score0[s];
-  return FB_OK;
-}
-
 
 // device clock stamps of the attack that just ran -> seconds per iteration (e->iter_seconds)
 static int collect_iter_seconds(fb_engine *e, int rows) {
@@ -2273,174 +2196,52 @@ static int check_params_ext(fb_engine *e, const fb_nes_params *p, int64_t N, int
   if (p->task != FB_TASK_OSI && p->task != FB_TASK_CSI && p->task != FB_TASK_SV) return fb_fail(FB_E_ARG, "bad task");
   if (S <= 0 || S > 62) return fb_fail(FB_E_ARG, "number of speakers must be in [1, 62] (got %d)", S);
   if (p->task == FB_TASK_SV && S != 1) return fb_fail(FB_E_ARG, "SV scores one speaker (got S = %d)", S);
-  if (p->samples_per_draw < 0 || p->samples_per_draw > 4094) return fb_fail(FB_E_ARG, "bad samples_per_draw");
-  if (p->task != FB_TASK_SV && p->attack_type == FB_TARGETED && (p->target < 0 || p->target >= S))
-    return fb_fail(FB_E_ARG, "target %d out of range", p->target);
-  if (p->task == FB_TASK_CSI && p->attack_type == FB_UNTARGETED && (p->true_label < 0 || p->true_label >= S))
-    return fb_fail(FB_E_ARG, "true label %d out of range", p->true_label);
-  if (!(p->sigma > 0.0) && p->samples_per_draw >= 2) return fb_fail(FB_E_ARG, "sigma must be > 0");
-  if (p->bits_per_sample != 0 && (p->bits_per_sample < 2 || p->bits_per_sample > 16))
-    return fb_fail(FB_E_ARG, "bits_per_sample %d unsupported (2 .. 16)", p->bits_per_sample);
-  return FB_OK;
-}
-
-static int ensure_ext_buffers(fb_engine *e, int64_t N, int B, int S) {
-  FBCHK(ensure_nes_buffers(e, N, B, S));
-  FBCHK(e->ext_x.ensure(sizeof(double) * (size_t)N * B));
-  FBCHK(e->raw.ensure(sizeof(double) * (size_t)B * S));
-  const size_t had = e->ext_z.cap;
-  FBCHK(e->ext_z.ensure(sizeof(double) * 2 * 64));
-  if (e->ext_z.cap != had) {  // z-norm of the identity: (s - 0) / 1 == s bit for bit
-    double z[128];
-    for (int i = 0; i < 64; ++i) { z[i] = 0.0; z[64 + i] = 1.0; }
-    FBCHK(h2d(e, e->ext_z.p, z, sizeof(z)));
-  }
-  return FB_OK;
+  return check_nes_params(p, S);
 }
 
 // fb_debug_foreign_path's record of the foreign-model call that starts now
-static void foreign_begin(fb_engine *e, int path, int x_dtype, int score_dtype, int launches_per_iter) {
+static void foreign_begin(fb_engine *e, const FbScorer &sc, int launches_per_iter) {
+  const bool dev = sc.kind == FB_SCORER_DEV;
   e->foreign = fb_foreign_path_info{};
-  e->foreign.path = path;
-  e->foreign.x_dtype = x_dtype;
-  e->foreign.score_dtype = score_dtype;
+  e->foreign.path = dev ? FB_FOREIGN_DEV : FB_FOREIGN_HOST;
+  e->foreign.x_dtype = dev ? sc.m->x_dtype : FB_DT_F64;
+  e->foreign.score_dtype = dev ? sc.m->score_dtype : FB_DT_F64;
   e->foreign.launches_per_iter = launches_per_iter;
 }
 
 // perturb -> float64 batch to the host -> callback -> scores to the device -> loss (+ loop control)
-static int enqueue_get_grad_ext(fb_engine *e, const fb_nes_params *p, int S, fb_score_cb cb, void *cb_ctx, int64_t N,
-                                uint32_t iter, const double *noise_dev, bool with_dist, FbCtlDev *ctl = nullptr,
+static int enqueue_get_grad_ext(fb_engine *e, const fb_nes_params *p, const FbScorer &sc, int64_t N, uint32_t iter,
+                                const double *noise_dev, bool with_dist, FbCtlDev *ctl = nullptr,
                                 double *trace_dev = nullptr, int trace_row = 0) {
-  const int half = p->samples_per_draw / 2, B = 2 * half + 1;
+  const int half = p->samples_per_draw / 2, B = 2 * half + 1, S = sc.S;
   int ndp = 0;
   fb_launch_perturb_f64(e->stream, e->adver.as<double>(), with_dist ? e->audio.as<double>() : nullptr, N, half,
                         p->sigma, p->seed, iter, p->stream, noise_dev, e->ext_x.as<double>(),
                         e->dist_part.as<double>(), &ndp, noise_dev ? nullptr : e->zbuf.as<float>());
   const size_t xb = sizeof(double) * (size_t)N * B;
-  std::vector<double> sc((size_t)B * S);
+  std::vector<double> sc_h((size_t)B * S);
   if (xb <= FB_PIN_MAX) {  // the callback reads the pinned staging area directly
     char *xh = nullptr;
     FBCHK(pin_reserve(e, xb, &xh));
     HIPCHK(hipMemcpyAsync(xh, e->ext_x.p, xb, hipMemcpyDeviceToHost, e->stream));
     FBCHK(sync_stream(e));
-    const int rc = cb(cb_ctx, reinterpret_cast<const double *>(xh), N, B, sc.data());
+    const int rc = sc.cb(sc.ctx, reinterpret_cast<const double *>(xh), N, B, sc_h.data());
     if (rc != 0) return fb_fail(FB_E_CALLBACK, "score callback failed (rc %d)", rc);
   } else {
     std::vector<double> xh((size_t)N * B);
     FBCHK(sync_stream(e));
     HIPCHK(hipMemcpy(xh.data(), e->ext_x.p, xb, hipMemcpyDeviceToHost));
-    const int rc = cb(cb_ctx, xh.data(), N, B, sc.data());
+    const int rc = sc.cb(sc.ctx, xh.data(), N, B, sc_h.data());
     if (rc != 0) return fb_fail(FB_E_CALLBACK, "score callback failed (rc %d)", rc);
   }
-  FBCHK(h2d(e, e->raw.p, sc.data(), sizeof(double) * sc.size()));
+  FBCHK(h2d(e, e->raw.p, sc_h.data(), sizeof(double) * sc_h.size()));
   e->foreign.model_calls += 1;
   e->foreign.batch_bytes_d2h += (int64_t)xb;
-  e->foreign.score_bytes_h2d += (int64_t)(sizeof(double) * sc.size());
+  e->foreign.score_bytes_h2d += (int64_t)(sizeof(double) * sc_h.size());
   fb_launch_loss(e->stream, e->raw.as<double>(), nullptr, B, S, p->task, 1, p->attack_type, e->ext_z.as<double>(),
                  e->ext_z.as<double>() + 64, p->threshold, p->adver_thresh, p->target, p->true_label,
                  e->dist_part.as<double>(), with_dist ? ndp : 0, e->scores.as<double>(), e->loss.as<double>(),
                  e->nes_out.as<FbNesDev>(), ctl, trace_dev, trace_row);
-  return FB_OK;
-}
-
-extern "C" int fb_get_grad_ext(fb_engine *e, const fb_nes_params *p, int S, fb_score_cb cb, void *cb_ctx,
-                               const double *audio, int64_t N, uint32_t iter, const double *noise_pos,
-                               double *final_loss, double *grad, double *adver_loss, double *score0) {
-  if (e) e->bench_it = -1;
-  if (!audio) return fb_fail(FB_E_ARG, "audio is NULL");
-  FBCHK(check_params_ext(e, p, N, S, cb != nullptr));
-  HIPCHK(hipSetDevice(e->device));
-  FBCHK(sync_stream(e));
-  const int half = p->samples_per_draw / 2, B = 2 * half + 1;
-  FBCHK(ensure_ext_buffers(e, N, B, S));
-  foreign_begin(e, FB_FOREIGN_HOST, FB_DT_F64, FB_DT_F64, 3);  // k_perturb_f64, k_loss, k_grad_update
-  FBCHK(h2d(e, e->adver.p, audio, sizeof(double) * (size_t)N));
-  const double *noise_dev = nullptr;
-  if (noise_pos && half > 0) {
-    FBCHK(e->noise.ensure(sizeof(double) * (size_t)N * half));
-    FBCHK(h2d(e, e->noise.p, noise_pos, sizeof(double) * (size_t)N * half));
-    noise_dev = e->noise.as<double>();
-  }
-  FBCHK(enqueue_get_grad_ext(e, p, S, cb, cb_ctx, N, iter, noise_dev, false));
-  fb_launch_grad_update(e->stream, e->loss.as<double>(), N, half, p->sigma, e->zbuf.as<float>(), noise_dev,
-                        e->grad.as<double>(), 0, 0.0, 0.0, 0.0, 0.0, nullptr, nullptr, nullptr);
-  if (grad) FBCHK(d2h(e, grad, e->grad.p, sizeof(double) * (size_t)N));
-  HIPCHK(hipMemcpyAsync(e->h_out, e->nes_out.p, sizeof(FbNesDev), hipMemcpyDeviceToHost, e->stream));
-  FBCHK(sync_stream(e));
-  e->nes_iters += 1;
-  if (final_loss) *final_loss = e->h_out->final_loss;
-  if (adver_loss) *adver_loss = e->h_out->adver_loss;
-  if (score0) for (int s = 0; s < S; ++s) score0[s] = e->h_out->score0[s];
-  return FB_OK;
-}
-
-extern "C" int fb_attack_ext(fb_engine *e, const fb_nes_params *p, int S, fb_score_cb cb, void *cb_ctx,
-                             const double *audio, int64_t N, const double *noise_all, int16_t *adv_i16,
-                             double *adver_f64, double *trace, int *n_trace, int *success_flag) {
-  if (e) e->bench_it = -1;
-  if (!audio || !adv_i16 || !success_flag) return fb_fail(FB_E_ARG, "null argument");
-  FBCHK(check_params_ext(e, p, N, S, cb != nullptr));
-  if (p->max_iter <= 0) return fb_fail(FB_E_ARG, "max_iter must be > 0");
-  HIPCHK(hipSetDevice(e->device));
-  FBCHK(sync_stream(e));
-  const int half = p->samples_per_draw / 2, B = 2 * half + 1;
-  FBCHK(ensure_ext_buffers(e, N, B, S));
-  foreign_begin(e, FB_FOREIGN_HOST, FB_DT_F64, FB_DT_F64, 3);  // k_perturb_f64, k_loss, k_grad_update
-  FBCHK(h2d(e, e->audio.p, audio, sizeof(double) * (size_t)N));
-  HIPCHK(hipMemcpyAsync(e->adver.p, e->audio.p, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, e->stream));
-  HIPCHK(hipMemsetAsync(e->grad_m.p, 0, sizeof(double) * (size_t)N, e->stream));  // grad = 0 (FAKEBOB.py:157)
-  if (noise_all && half > 0) FBCHK(e->noise.ensure(sizeof(double) * (size_t)N * half));
-  double *trace_dev = nullptr;
-  if (trace) {
-    FBCHK(e->trace_dev.ensure(sizeof(double) * (size_t)p->max_iter * (3 + S)));
-    trace_dev = e->trace_dev.as<double>();
-  }
-  // device loop control exactly as in fb_attack; the host looks at it after every iteration
-  FBCHK(e->ctl.ensure(sizeof(FbCtlDev)));
-  FBCHK(e->ctl_ls.ensure(sizeof(double) * (size_t)(p->plateau_length > 0 ? p->plateau_length : 1)));
-  FbCtlDev *ctl = e->ctl.as<FbCtlDev>();
-  {
-    FbCtlDev h;
-    memset(&h, 0, sizeof(h));
-    h.lr = p->max_lr; h.min_lr = p->min_lr; h.plateau_drop = p->plateau_drop;
-    h.ls = e->ctl_ls.as<double>();
-    h.plateau_length = p->plateau_length;
-    FBCHK(e->ticks.ensure(sizeof(unsigned long long) * ((size_t)p->max_iter + 1)));
-    h.ticks = e->ticks.as<unsigned long long>();
-    *e->h_ctl = h;
-    HIPCHK(hipMemcpyAsync(ctl, e->h_ctl, sizeof(FbCtlDev), hipMemcpyHostToDevice, e->stream));
-    FBCHK(sync_stream(e));
-    fb_launch_stamp(e->stream, h.ticks);
-  }
-  const double one_minus_m = 1.0 - p->momentum;
-  for (int it = 0; it < p->max_iter; ++it) {
-    const double *noise_dev = nullptr;
-    if (noise_all && half > 0) {
-      FBCHK(h2d(e, e->noise.p, noise_all + (size_t)it * N * half, sizeof(double) * (size_t)N * half));
-      noise_dev = e->noise.as<double>();
-    }
-    FBCHK(enqueue_get_grad_ext(e, p, S, cb, cb_ctx, N, (uint32_t)it, noise_dev, true, ctl, trace_dev, it));
-    fb_launch_grad_update(e->stream, e->loss.as<double>(), N, half, p->sigma, e->zbuf.as<float>(), noise_dev, nullptr,
-                          1, p->momentum, one_minus_m, 0.0, p->epsilon, e->audio.as<double>(), e->grad_m.as<double>(),
-                          e->adver.as<double>(), ctl);
-    HIPCHK(hipMemcpyAsync(e->h_ctl, ctl, sizeof(FbCtlDev), hipMemcpyDeviceToHost, e->stream));
-    FBCHK(sync_stream(e));
-    if (e->h_ctl->stop) break;
-  }
-  const int rows = e->h_ctl->iters_done;
-  const bool broke = e->h_ctl->broke != 0;
-  e->nes_iters += rows;
-  FBCHK(collect_iter_seconds(e, rows));
-  if (trace && rows > 0) FBCHK(d2h(e, trace, trace_dev, sizeof(double) * (size_t)rows * (3 + S)));
-  const int last_iter = broke ? e->h_ctl->stop_iter : p->max_iter - 1;
-  *success_flag = (last_iter < p->max_iter - 1) ? 1 : -1;  // FAKEBOB.py:219
-  if (n_trace) *n_trace = rows;
-  FBCHK(e->wav.ensure(sizeof(int16_t) * (size_t)N));
-  e->cached_B = -1;  // the scoring batch layout no longer describes e->wav
-  fb_launch_quantize(e->stream, e->adver.as<double>(), N, p->bits_per_sample ? p->bits_per_sample : 16, e->wav.as<int16_t>());
-  FBCHK(d2h(e, adv_i16, e->wav.p, sizeof(int16_t) * (size_t)N));
-  if (adver_f64) FBCHK(d2h(e, adver_f64, e->adver.p, sizeof(double) * (size_t)N));
-  FBCHK(sync_stream(e));
   return FB_OK;
 }
 
@@ -2485,35 +2286,23 @@ static int check_dev_model(fb_engine *e, const fb_dev_model *m, int64_t N, int B
   return FB_OK;
 }
 
-static int ensure_dev_buffers(fb_engine *e, int64_t N, int B, int S) {
-  FBCHK(ensure_nes_buffers(e, N, B, S));
-  const size_t had = e->ext_z.cap;
-  FBCHK(e->ext_z.ensure(sizeof(double) * 2 * 64));
-  if (e->ext_z.cap != had) {  // z-norm of the identity, as ensure_ext_buffers
-    double z[128];
-    for (int i = 0; i < 64; ++i) { z[i] = 0.0; z[64 + i] = 1.0; }
-    FBCHK(h2d(e, e->ext_z.p, z, sizeof(z)));
-  }
-  return FB_OK;
-}
-
 // the model's work on the engine's stream, then the loss (+ loop control) on its scores
-static int enqueue_score_loss_dev(fb_engine *e, const fb_nes_params *p, int S, const fb_dev_model *m, fb_score_dev_cb cb,
-                                  void *ctx, int64_t N, int ndp, FbCtlDev *ctl, double *trace_dev, int trace_row) {
-  const int B = 2 * (p->samples_per_draw / 2) + 1;
-  const int rc = cb(ctx, (void *)e->stream, N, B, S);
+static int enqueue_score_loss_dev(fb_engine *e, const fb_nes_params *p, const FbScorer &sc, int64_t N, int ndp,
+                                  FbCtlDev *ctl, double *trace_dev, int trace_row) {
+  const int B = 2 * (p->samples_per_draw / 2) + 1, S = sc.S;
+  const int rc = sc.dcb(sc.ctx, (void *)e->stream, N, B, S);
   e->foreign.model_calls += 1;
   if (rc != 0) {
     (void)sync_stream(e);  // (whatever the model did enqueue has finished when the caller sees the error)
     return fb_fail(FB_E_CALLBACK, "score callback failed (rc %d)", rc);
   }
-  if (m->score_dtype == FB_DT_F32)
-    fb_launch_loss(e->stream, static_cast<const float *>(m->scores), nullptr, B, S, p->task, 1, p->attack_type,
+  if (sc.m->score_dtype == FB_DT_F32)
+    fb_launch_loss(e->stream, static_cast<const float *>(sc.m->scores), nullptr, B, S, p->task, 1, p->attack_type,
                    e->ext_z.as<double>(), e->ext_z.as<double>() + 64, p->threshold, p->adver_thresh, p->target,
                    p->true_label, e->dist_part.as<double>(), ndp, e->scores.as<double>(), e->loss.as<double>(),
                    e->nes_out.as<FbNesDev>(), ctl, trace_dev, trace_row);
   else
-    fb_launch_loss(e->stream, static_cast<const double *>(m->scores), nullptr, B, S, p->task, 1, p->attack_type,
+    fb_launch_loss(e->stream, static_cast<const double *>(sc.m->scores), nullptr, B, S, p->task, 1, p->attack_type,
                    e->ext_z.as<double>(), e->ext_z.as<double>() + 64, p->threshold, p->adver_thresh, p->target,
                    p->true_label, e->dist_part.as<double>(), ndp, e->scores.as<double>(), e->loss.as<double>(),
                    e->nes_out.as<FbNesDev>(), ctl, trace_dev, trace_row);
@@ -2522,18 +2311,46 @@ static int enqueue_score_loss_dev(fb_engine *e, const fb_nes_params *p, int S, c
 
 static bool x_aligned(const fb_dev_model *m) { return (reinterpret_cast<uintptr_t>(m->x) & 15) == 0; }
 
-extern "C" int fb_get_grad_dev(fb_engine *e, const fb_nes_params *p, int S, const fb_dev_model *m, fb_score_dev_cb cb,
-                               void *ctx, const double *audio, int64_t N, uint32_t iter, const double *noise_pos,
-                               double *final_loss, double *grad, double *adver_loss, double *score0) {
+// ------------------------------------------------- the NES driver of every scorer
+// Checks and buffers of a NES call.  attack: fb_attack*, which also need max_iter > 0.
+static int nes_setup(fb_engine *e, const fb_nes_params *p, int64_t N, FbScorer &sc, bool attack) {
+  const bool native = sc.kind == FB_SCORER_NATIVE;
+  FBCHK(native ? check_params(e, p, N) : check_params_ext(e, p, N, sc.S, sc.cb || sc.dcb));
+  if (attack && p->max_iter <= 0) return fb_fail(FB_E_ARG, "max_iter must be > 0");
+  HIPCHK(hipSetDevice(e->device));
+  const int B = 2 * (p->samples_per_draw / 2) + 1;
+  if (native) {
+    sc.S = fb_num_speakers(e);
+    FBCHK(prepare_nes_batch(e, N, B));
+    return ensure_nes_buffers(e, N, B);
+  }
+  FBCHK(sync_stream(e));
+  if (sc.kind == FB_SCORER_DEV) FBCHK(check_dev_model(e, sc.m, N, B, sc.S));
+  FBCHK(ensure_nes_buffers(e, N, B, sc.S));
+  if (sc.kind == FB_SCORER_HOST) {
+    FBCHK(e->ext_x.ensure(sizeof(double) * (size_t)N * B));
+    FBCHK(e->raw.ensure(sizeof(double) * (size_t)B * sc.S));
+  }
+  const size_t had = e->ext_z.cap;
+  FBCHK(e->ext_z.ensure(sizeof(double) * 2 * 64));
+  if (e->ext_z.cap != had) {  // z-norm of the identity: (s - 0) / 1 == s bit for bit
+    double z[128];
+    for (int i = 0; i < 64; ++i) { z[i] = 0.0; z[64 + i] = 1.0; }
+    FBCHK(h2d(e, e->ext_z.p, z, sizeof(z)));
+  }
+  return FB_OK;
+}
+
+// fb_get_grad*: one NES gradient estimate at `audio`
+static int nes_gradient(fb_engine *e, const fb_nes_params *p, FbScorer sc, const double *audio, int64_t N,
+                        uint32_t iter, const double *noise_pos, double *final_loss, double *grad, double *adver_loss,
+                        double *score0) {
   if (e) e->bench_it = -1;
   if (!audio) return fb_fail(FB_E_ARG, "audio is NULL");
-  FBCHK(check_params_ext(e, p, N, S, cb != nullptr));
-  HIPCHK(hipSetDevice(e->device));
-  FBCHK(sync_stream(e));
-  const int half = p->samples_per_draw / 2, B = 2 * half + 1;
-  FBCHK(check_dev_model(e, m, N, B, S));
-  FBCHK(ensure_dev_buffers(e, N, B, S));
-  foreign_begin(e, FB_FOREIGN_DEV, m->x_dtype, m->score_dtype, 3);  // k_perturb_x, k_loss, k_grad_update
+  FBCHK(nes_setup(e, p, N, sc, false));
+  const bool native = sc.kind == FB_SCORER_NATIVE;
+  if (!native) foreign_begin(e, sc, 3);  // k_perturb_f64 / k_perturb_x, k_loss, k_grad_update
+  const int half = p->samples_per_draw / 2;
   FBCHK(h2d(e, e->adver.p, audio, sizeof(double) * (size_t)N));
   const double *noise_dev = nullptr;
   if (noise_pos && half > 0) {
@@ -2541,120 +2358,254 @@ extern "C" int fb_get_grad_dev(fb_engine *e, const fb_nes_params *p, int S, cons
     FBCHK(h2d(e, e->noise.p, noise_pos, sizeof(double) * (size_t)N * half));
     noise_dev = e->noise.as<double>();
   }
-  fb_launch_perturb_x(e->stream, m->x_dtype, e->adver.as<double>(), nullptr, N, half, p->sigma, p->seed, iter, p->stream,
-                      noise_dev, m->x, x_aligned(m), e->dist_part.as<double>(), nullptr,
-                      noise_dev ? nullptr : e->zbuf.as<float>(), nullptr);
-  FBCHK(enqueue_score_loss_dev(e, p, S, m, cb, ctx, N, 0, nullptr, nullptr, 0));
+  switch (sc.kind) {
+    case FB_SCORER_NATIVE:
+      FBCHK(enqueue_get_grad(e, p, N, iter, noise_dev, false));
+      break;
+    case FB_SCORER_HOST:
+      FBCHK(enqueue_get_grad_ext(e, p, sc, N, iter, noise_dev, false));
+      break;
+    case FB_SCORER_DEV:  // (no loop control: no stop flag)
+      fb_launch_perturb_x(e->stream, sc.m->x_dtype, e->adver.as<double>(), nullptr, N, half, p->sigma, p->seed, iter,
+                          p->stream, noise_dev, sc.m->x, x_aligned(sc.m), e->dist_part.as<double>(), nullptr,
+                          noise_dev ? nullptr : e->zbuf.as<float>(), nullptr);
+      FBCHK(enqueue_score_loss_dev(e, p, sc, N, 0, nullptr, nullptr, 0));
+      break;
+  }
   fb_launch_grad_update(e->stream, e->loss.as<double>(), N, half, p->sigma, e->zbuf.as<float>(), noise_dev,
                         e->grad.as<double>(), 0, 0.0, 0.0, 0.0, 0.0, nullptr, nullptr, nullptr);
   if (grad) FBCHK(d2h(e, grad, e->grad.p, sizeof(double) * (size_t)N));
-  HIPCHK(hipMemcpyAsync(e->h_out, e->nes_out.p, sizeof(FbNesDev), hipMemcpyDeviceToHost, e->stream));
-  FBCHK(sync_stream(e));
+  FBCHK(fetch_out(e, native));
   e->nes_iters += 1;
   if (final_loss) *final_loss = e->h_out->final_loss;
   if (adver_loss) *adver_loss = e->h_out->adver_loss;
-  if (score0) for (int s = 0; s < S; ++s) score0[s] = e->h_out->score0[s];
+  if (score0) for (int s = 0; s < sc.S; ++s) score0[s] = e->h_out->score0[s];
   return FB_OK;
 }
 
-extern "C" int fb_attack_dev(fb_engine *e, const fb_nes_params *p, int S, const fb_dev_model *m, fb_score_dev_cb cb,
-                             void *ctx, const double *audio, int64_t N, const double *noise_all, int16_t *adv_i16,
-                             double *adver_f64, double *trace, int *n_trace, int *success_flag) {
-  if (e) e->bench_it = -1;
-  if (!audio || !adv_i16 || !success_flag) return fb_fail(FB_E_ARG, "null argument");
-  FBCHK(check_params_ext(e, p, N, S, cb != nullptr));
-  if (p->max_iter <= 0) return fb_fail(FB_E_ARG, "max_iter must be > 0");
-  HIPCHK(hipSetDevice(e->device));
-  FBCHK(sync_stream(e));
-  const int half = p->samples_per_draw / 2, B = 2 * half + 1;
-  FBCHK(check_dev_model(e, m, N, B, S));
-  FBCHK(ensure_dev_buffers(e, N, B, S));
-  // Philox noise and a small enough batch: the momentum sign step of iteration i and the batch of i + 1 in one launch
-  // (k_update_perturb_x, as fb_attack's k_update_perturb); otherwise k_grad_update + k_perturb_x
-  const bool fuse = !noise_all && half > 0 && half <= FB_FUSE_MAX_HALF;
-  foreign_begin(e, FB_FOREIGN_DEV, m->x_dtype, m->score_dtype, fuse ? 2 : 3);
+// the start of an attack: adver = audio, grad = 0 (FAKEBOB.py:157), room for replayed normals
+static int attack_start(fb_engine *e, const double *audio, int64_t N, int half, const double *noise_all) {
   FBCHK(h2d(e, e->audio.p, audio, sizeof(double) * (size_t)N));
   HIPCHK(hipMemcpyAsync(e->adver.p, e->audio.p, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, e->stream));
-  HIPCHK(hipMemsetAsync(e->grad_m.p, 0, sizeof(double) * (size_t)N, e->stream));  // grad = 0 (FAKEBOB.py:157)
+  HIPCHK(hipMemsetAsync(e->grad_m.p, 0, sizeof(double) * (size_t)N, e->stream));
   if (noise_all && half > 0) FBCHK(e->noise.ensure(sizeof(double) * (size_t)N * half));
+  return FB_OK;
+}
+
+// A new attack's loop control (lr = max_lr, empty loss history) on the device; ticks (nullable) get the start stamp.
+// native: the engine's own launch state starts clean as well -- the foreign paths use none of it.
+static int ctl_reset(fb_engine *e, const fb_nes_params *p, bool native, bool disable_stop, unsigned long long *ticks) {
+  if (native) {
+    e->pre_iter = -1;
+    // The ticket of k_vad_delta_cmvn and the arrival counter of k_gmm_finalize_loss are left at zero by every launch
+    // that completes; one that was aborted or failed would leave them elsewhere and every later launch would then
+    // mis-assign utterances / skip its loss body.  A new attack starts them clean.
+    if (e->vad_counter.p) HIPCHK(hipMemsetAsync(e->vad_counter.p, 0, sizeof(int), e->stream));
+    if (e->fin_counter.p) HIPCHK(hipMemsetAsync(e->fin_counter.p, 0, 2 * sizeof(int), e->stream));
+    e->fin_xch_clean = false;  // (refilled with sentinels before its next use)
+    if (e->iv_tail_counter.p) HIPCHK(hipMemsetAsync(e->iv_tail_counter.p, 0, sizeof(int), e->stream));
+    e->vad_part_B = -1;  // ... and k_vad_delta_cmvn_p's exchange slots are refilled with sentinels (run_post_mfcc)
+    e->ctl_seq = 0;   // (h.pub_seq = 0: the loss bodies of this attack count from 1)
+  }
+  FBCHK(e->ctl.ensure(sizeof(FbCtlDev)));
+  FBCHK(e->ctl_ls.ensure(sizeof(double) * (size_t)(p->plateau_length > 0 ? p->plateau_length : 1)));
+  FbCtlDev h;
+  memset(&h, 0, sizeof(h));
+  h.lr = p->max_lr; h.min_lr = p->min_lr; h.plateau_drop = p->plateau_drop;
+  h.ls = e->ctl_ls.as<double>();
+  h.plateau_length = p->plateau_length;
+  h.disable_stop = disable_stop ? 1 : 0;
+  h.ticks = ticks;
+  *e->h_ctl = h;
+  HIPCHK(hipMemcpyAsync(e->ctl.p, e->h_ctl, sizeof(FbCtlDev), hipMemcpyHostToDevice, e->stream));
+  FBCHK(sync_stream(e));  // h_ctl is reused for the read-back in attack_loop
+  if (ticks) fb_launch_stamp(e->stream, ticks);
+  return FB_OK;
+}
+
+// The NES loop of FakeBob.attack (FAKEBOB.py:171-216) with the loop control on the device (FbCtlDev): `count`
+// iterations starting at Philox iteration index `it_base` are queued kn.look at a time; the host reads the control block
+// once per look and stops when it is told to.  trace_dev rows are indexed from it_base.
+static int attack_loop(fb_engine *e, const fb_nes_params *p, int64_t N, const FbScorer &sc, const FbLoopKnobs &kn,
+                       const double *noise_all, int it_base, int count, double *trace_dev) {
+  const int half = p->samples_per_draw / 2;
+  const double one_minus_m = 1.0 - p->momentum;
+  const bool upd_next = fuses_update(kn, noise_all, half);
+  FbCtlDev *ctl = e->ctl.as<FbCtlDev>();
+  int ndp = 0;              // FB_SCORER_DEV: the distance partials of the batch the previous iteration's update wrote
+  bool have_batch = false;  // ... if it wrote one
+  for (int done = 0; done < count;) {
+    const int nb = count - done < kn.look ? count - done : kn.look;
+    for (int k = 0; k < nb; ++k) {
+      const int it = it_base + done + k;
+      const double *noise_dev = nullptr;
+      if (noise_all && half > 0) {
+        FBCHK(h2d(e, e->noise.p, noise_all + (size_t)it * N * half, sizeof(double) * (size_t)N * half));
+        noise_dev = e->noise.as<double>();
+      }
+      bool updated = false;  // the momentum sign step of this iteration is queued
+      switch (sc.kind) {
+        case FB_SCORER_NATIVE: {
+          if (fb_debug_sync_on()) fprintf(stderr, "[fb] iteration %d\n", it);
+          // GMM systems on the fused chain: the update of this iteration and the batch of the next one ride in the
+          // launch that finalises the scores and runs the loss body (k_gmm_finalize_loss_update; FB_FUSE_UPD=0: two
+          // launches) (at most FB_FUSE_MAX_UPD_WG update workgroups in the finalising launch: the bound its no-deadlock
+          // argument needs)
+          FbUpdArgs ua = {};
+          if (upd_next && kn.fuse_fin && kn.upd_in_fin && e->kind == 0 && (N + 255) / 256 <= FB_FUSE_MAX_UPD_WG) {
+            ua.loss = e->loss.as<double>(); ua.N = N; ua.half = half; ua.sigma = p->sigma; ua.zbuf = e->zbuf.as<float>();
+            ua.momentum = p->momentum; ua.one_minus_m = one_minus_m; ua.epsilon = p->epsilon; ua.audio = e->audio.as<double>();
+            ua.grad_m = e->grad_m.as<double>(); ua.adver = e->adver.as<double>(); ua.seed = p->seed; ua.next_iter = (uint32_t)(it + 1);
+            ua.stream = p->stream; ua.q = e->wav.as<int16_t>(); ua.dist_part = e->dist_part.as<double>();
+            ua.qscale = ldexp(1.0, nes_bits(p) - 1);
+          }
+          FBCHK(enqueue_get_grad(e, p, N, (uint32_t)it, noise_dev, true, kn, ctl, trace_dev, it - it_base,
+                                 ua.loss ? &ua : nullptr, &updated));
+          FB_DBG_SYNC(e, "loss");
+          if (updated) {
+            e->pre_ndp = (int)((N + 255) / 256);
+            e->pre_iter = (long long)it + 1;
+          } else if (upd_next) {
+            e->pre_ndp = fb_launch_update_perturb(e->stream, e->loss.as<double>(), N, half, p->sigma, e->zbuf.as<float>(),
+                                                  p->momentum, one_minus_m, p->epsilon, e->audio.as<double>(),
+                                                  e->grad_m.as<double>(), e->adver.as<double>(), ctl, p->seed,
+                                                  (uint32_t)(it + 1), p->stream, e->wav.as<int16_t>(),
+                                                  e->dist_part.as<double>(), nes_bits(p));
+            e->pre_iter = (long long)it + 1;
+            updated = true;
+          }
+          break;
+        }
+        case FB_SCORER_HOST:
+          FBCHK(enqueue_get_grad_ext(e, p, sc, N, (uint32_t)it, noise_dev, true, ctl, trace_dev, it - it_base));
+          break;
+        case FB_SCORER_DEV: {
+          const int xv = x_aligned(sc.m) ? 1 : 0;
+          if (!have_batch)
+            fb_launch_perturb_x(e->stream, sc.m->x_dtype, e->adver.as<double>(), e->audio.as<double>(), N, half, p->sigma,
+                                p->seed, (uint32_t)it, p->stream, noise_dev, sc.m->x, xv, e->dist_part.as<double>(), &ndp,
+                                noise_dev ? nullptr : e->zbuf.as<float>(), &ctl->stop);
+          FBCHK(enqueue_score_loss_dev(e, p, sc, N, ndp, ctl, trace_dev, it - it_base));
+          if (upd_next) {
+            ndp = fb_launch_update_perturb_x(e->stream, sc.m->x_dtype, e->loss.as<double>(), N, half, p->sigma,
+                                             e->zbuf.as<float>(), p->momentum, one_minus_m, p->epsilon,
+                                             e->audio.as<double>(), e->grad_m.as<double>(), e->adver.as<double>(), ctl,
+                                             p->seed, (uint32_t)(it + 1), p->stream, sc.m->x, xv,
+                                             e->dist_part.as<double>());
+            have_batch = updated = true;
+          }
+          break;
+        }
+      }
+      if (!updated)
+        fb_launch_grad_update(e->stream, e->loss.as<double>(), N, half, p->sigma, e->zbuf.as<float>(), noise_dev,
+                              nullptr, 1, p->momentum, one_minus_m, 0.0, p->epsilon, e->audio.as<double>(),
+                              e->grad_m.as<double>(), e->adver.as<double>(), ctl);
+    }
+    HIPCHK(hipMemcpyAsync(e->h_ctl, ctl, sizeof(FbCtlDev), hipMemcpyDeviceToHost, e->stream));
+    FBCHK(sync_stream(e));
+    if (sc.kind == FB_SCORER_NATIVE && e->gmm_pending) FBCHK(time_collect(e));
+    // err on a foreign path is never set: k_loss sets it only when it has the voiced-frame counts (tv), and only the
+    // native systems pass them (fb_nes_device.h)
+    if (e->h_ctl->err != 0)
+      return fb_fail(FB_E_NO_VOICED, "NES sample %d has no voiced frames", e->h_ctl->err - 1);
+    done += nb;
+    if (e->h_ctl->stop) break;
+  }
+  return FB_OK;
+}
+
+// fb_attack*: FakeBob.attack (FAKEBOB.py:157-220) -> int16 adver, success flag, float64 adver, trace
+static int run_attack(fb_engine *e, const fb_nes_params *p, FbScorer sc, const double *audio, int64_t N,
+                      const double *noise_all, int16_t *adv_i16, double *adver_f64, double *trace, int *n_trace,
+                      int *success_flag) {
+  if (e) e->bench_it = -1;
+  if (!audio || !adv_i16 || !success_flag) return fb_fail(FB_E_ARG, "null argument");
+  FBCHK(nes_setup(e, p, N, sc, true));
+  const bool native = sc.kind == FB_SCORER_NATIVE;
+  const int half = p->samples_per_draw / 2, B = 2 * half + 1, S = sc.S;
+  const FbLoopKnobs kn = loop_knobs(e, sc);
+  // the device path's update and next batch in one launch: k_update_perturb_x instead of k_grad_update + k_perturb_x
+  if (!native) foreign_begin(e, sc, fuses_update(kn, noise_all, half) ? 2 : 3);
+  FBCHK(attack_start(e, audio, N, half, noise_all));
   double *trace_dev = nullptr;
   if (trace) {
     FBCHK(e->trace_dev.ensure(sizeof(double) * (size_t)p->max_iter * (3 + S)));
     trace_dev = e->trace_dev.as<double>();
   }
-  FBCHK(e->ctl.ensure(sizeof(FbCtlDev)));
-  FBCHK(e->ctl_ls.ensure(sizeof(double) * (size_t)(p->plateau_length > 0 ? p->plateau_length : 1)));
-  FbCtlDev *ctl = e->ctl.as<FbCtlDev>();
-  {
-    FbCtlDev h;
-    memset(&h, 0, sizeof(h));
-    h.lr = p->max_lr; h.min_lr = p->min_lr; h.plateau_drop = p->plateau_drop;
-    h.ls = e->ctl_ls.as<double>();
-    h.plateau_length = p->plateau_length;
-    FBCHK(e->ticks.ensure(sizeof(unsigned long long) * ((size_t)p->max_iter + 1)));
-    h.ticks = e->ticks.as<unsigned long long>();
-    *e->h_ctl = h;
-    HIPCHK(hipMemcpyAsync(ctl, e->h_ctl, sizeof(FbCtlDev), hipMemcpyHostToDevice, e->stream));
-    FBCHK(sync_stream(e));
-    fb_launch_stamp(e->stream, h.ticks);
-  }
-  const double one_minus_m = 1.0 - p->momentum;
-  const int look = m->look_every > 0 ? m->look_every : 4;
-  const int xv = x_aligned(m) ? 1 : 0;
-  int ndp = 0;
-  bool have_batch = false;  // the fused launch of the previous iteration wrote this iteration's batch
-  for (int it = 0; it < p->max_iter;) {
-    const int nb = p->max_iter - it < look ? p->max_iter - it : look;
-    for (int k = 0; k < nb; ++k) {
-      const int i = it + k;
-      const double *noise_dev = nullptr;
-      if (noise_all && half > 0) {
-        FBCHK(h2d(e, e->noise.p, noise_all + (size_t)i * N * half, sizeof(double) * (size_t)N * half));
-        noise_dev = e->noise.as<double>();
-      }
-      if (!have_batch)
-        fb_launch_perturb_x(e->stream, m->x_dtype, e->adver.as<double>(), e->audio.as<double>(), N, half, p->sigma, p->seed,
-                            (uint32_t)i, p->stream, noise_dev, m->x, xv, e->dist_part.as<double>(), &ndp,
-                            noise_dev ? nullptr : e->zbuf.as<float>(), &ctl->stop);
-      FBCHK(enqueue_score_loss_dev(e, p, S, m, cb, ctx, N, ndp, ctl, trace_dev, i));
-      if (fuse) {
-        ndp = fb_launch_update_perturb_x(e->stream, m->x_dtype, e->loss.as<double>(), N, half, p->sigma,
-                                         e->zbuf.as<float>(), p->momentum, one_minus_m, p->epsilon, e->audio.as<double>(),
-                                         e->grad_m.as<double>(), e->adver.as<double>(), ctl, p->seed, (uint32_t)(i + 1),
-                                         p->stream, m->x, xv, e->dist_part.as<double>());
-        have_batch = true;
-      } else {
-        fb_launch_grad_update(e->stream, e->loss.as<double>(), N, half, p->sigma, e->zbuf.as<float>(), noise_dev, nullptr,
-                              1, p->momentum, one_minus_m, 0.0, p->epsilon, e->audio.as<double>(), e->grad_m.as<double>(),
-                              e->adver.as<double>(), ctl);
-      }
-    }
-    HIPCHK(hipMemcpyAsync(e->h_ctl, ctl, sizeof(FbCtlDev), hipMemcpyDeviceToHost, e->stream));
-    FBCHK(sync_stream(e));
-    it += nb;
-    if (e->h_ctl->stop) break;
-  }
-  const int rows = e->h_ctl->iters_done;
-  const bool broke = e->h_ctl->broke != 0;
+  FBCHK(e->ticks.ensure(sizeof(unsigned long long) * ((size_t)p->max_iter + 1)));
+  FBCHK(ctl_reset(e, p, native, false, e->ticks.as<unsigned long long>()));
+  FBCHK(attack_loop(e, p, N, sc, kn, noise_all, 0, p->max_iter, trace_dev));
+  const int rows = e->h_ctl->iters_done;  // one trace row per executed iteration, the stopping one included
   e->nes_iters += rows;
   FBCHK(collect_iter_seconds(e, rows));
   if (trace && rows > 0) FBCHK(d2h(e, trace, trace_dev, sizeof(double) * (size_t)rows * (3 + S)));
-  const int last_iter = broke ? e->h_ctl->stop_iter : p->max_iter - 1;
-  *success_flag = (last_iter < p->max_iter - 1) ? 1 : -1;  // FAKEBOB.py:219
+  const int last_iter = e->h_ctl->broke ? e->h_ctl->stop_iter : p->max_iter - 1;
+  *success_flag = (last_iter < p->max_iter - 1) ? 1 : -1;  // :219
   if (n_trace) *n_trace = rows;
-  FBCHK(e->wav.ensure(sizeof(int16_t) * (size_t)N));
-  e->cached_B = -1;  // the scoring batch layout no longer describes e->wav
-  fb_launch_quantize(e->stream, e->adver.as<double>(), N, p->bits_per_sample ? p->bits_per_sample : 16, e->wav.as<int16_t>());
+  // adver -> int16 (:220)
+  FBCHK(e->wav.ensure(sizeof(int16_t) * (size_t)N * (native ? B : 1)));
+  if (!native) e->cached_B = -1;  // the scoring batch layout no longer describes e->wav
+  fb_launch_quantize(e->stream, e->adver.as<double>(), N, nes_bits(p), e->wav.as<int16_t>());
   FBCHK(d2h(e, adv_i16, e->wav.p, sizeof(int16_t) * (size_t)N));
   if (adver_f64) FBCHK(d2h(e, adver_f64, e->adver.p, sizeof(double) * (size_t)N));
   FBCHK(sync_stream(e));
   return FB_OK;
 }
 
+// ------------------------------------------------- the public NES calls
+extern "C" int fb_get_grad(fb_engine *e, const fb_nes_params *p, const double *audio, int64_t N, uint32_t iter,
+                           const double *noise_pos, double *final_loss, double *grad, double *adver_loss,
+                           double *score0) {
+  return nes_gradient(e, p, FbScorer{FB_SCORER_NATIVE}, audio, N, iter, noise_pos, final_loss, grad, adver_loss, score0);
+}
+
+extern "C" int fb_get_grad_ext(fb_engine *e, const fb_nes_params *p, int S, fb_score_cb cb, void *cb_ctx,
+                               const double *audio, int64_t N, uint32_t iter, const double *noise_pos,
+                               double *final_loss, double *grad, double *adver_loss, double *score0) {
+  return nes_gradient(e, p, FbScorer{FB_SCORER_HOST, S, cb, nullptr, nullptr, cb_ctx}, audio, N, iter, noise_pos,
+                      final_loss, grad, adver_loss, score0);
+}
+
+extern "C" int fb_get_grad_dev(fb_engine *e, const fb_nes_params *p, int S, const fb_dev_model *m, fb_score_dev_cb cb,
+                               void *ctx, const double *audio, int64_t N, uint32_t iter, const double *noise_pos,
+                               double *final_loss, double *grad, double *adver_loss, double *score0) {
+  return nes_gradient(e, p, FbScorer{FB_SCORER_DEV, S, nullptr, m, cb, ctx}, audio, N, iter, noise_pos, final_loss,
+                      grad, adver_loss, score0);
+}
+
+extern "C" int fb_attack(fb_engine *e, const fb_nes_params *p, const double *audio, int64_t N,
+                         const double *noise_all, int16_t *adv_i16, double *adver_f64, double *trace,
+                         int *n_trace, int *success_flag) {
+  return run_attack(e, p, FbScorer{FB_SCORER_NATIVE}, audio, N, noise_all, adv_i16, adver_f64, trace, n_trace,
+                    success_flag);
+}
+
+extern "C" int fb_attack_ext(fb_engine *e, const fb_nes_params *p, int S, fb_score_cb cb, void *cb_ctx,
+                             const double *audio, int64_t N, const double *noise_all, int16_t *adv_i16,
+                             double *adver_f64, double *trace, int *n_trace, int *success_flag) {
+  return run_attack(e, p, FbScorer{FB_SCORER_HOST, S, cb, nullptr, nullptr, cb_ctx}, audio, N, noise_all, adv_i16,
+                    adver_f64, trace, n_trace, success_flag);
+}
+
+extern "C" int fb_attack_dev(fb_engine *e, const fb_nes_params *p, int S, const fb_dev_model *m, fb_score_dev_cb cb,
+                             void *ctx, const double *audio, int64_t N, const double *noise_all, int16_t *adv_i16,
+                             double *adver_f64, double *trace, int *n_trace, int *success_flag) {
+  return run_attack(e, p, FbScorer{FB_SCORER_DEV, S, nullptr, m, cb, ctx}, audio, N, noise_all, adv_i16, adver_f64,
+                    trace, n_trace, success_flag);
+}
+
 extern "C" int fb_debug_foreign_path(fb_engine *e, fb_foreign_path_info *info) {
   if (!e || !info) return fb_fail(FB_E_ARG, "null argument");
   if (e->foreign.path == 0) return fb_fail(FB_E_STATE, "no foreign-model call has run yet");
   *info = e->foreign;
+  return FB_OK;
+}
+
+extern "C" int fb_attack_iter_seconds(fb_engine *e, double *seconds, int n) {
+  if (!e || !seconds || n < 0) return fb_fail(FB_E_ARG, "bad argument");
+  if ((size_t)n > e->iter_seconds.size()) return fb_fail(FB_E_STATE, "the last attack ran %zu iterations (asked for %d)", e->iter_seconds.size(), n);
+  for (int i = 0; i < n; ++i) seconds[i] = e->iter_seconds[i];
   return FB_OK;
 }
 
@@ -2671,54 +2622,6 @@ struct Plateau {  // FAKEBOB.py:195-200
   }
 };
 
-extern "C" int fb_attack(fb_engine *e, const fb_nes_params *p, const double *audio, int64_t N,
-                         const double *noise_all, int16_t *adv_i16, double *adver_f64, double *trace,
-                         int *n_trace, int *success_flag) {
-  if (e) e->bench_it = -1;
-  if (!audio || !adv_i16 || !success_flag) return fb_fail(FB_E_ARG, "null argument");
-  FBCHK(check_params(e, p, N));
-  if (p->max_iter <= 0) return fb_fail(FB_E_ARG, "max_iter must be > 0");
-  HIPCHK(hipSetDevice(e->device));
-  const int half = p->samples_per_draw / 2, B = 2 * half + 1, S = fb_num_speakers(e);
-  FBCHK(prepare_nes_batch(e, N, B));
-  FBCHK(ensure_nes_buffers(e, N, B));
-  FBCHK(h2d(e, e->audio.p, audio, sizeof(double) * (size_t)N));
-  HIPCHK(hipMemcpyAsync(e->adver.p, e->audio.p, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, e->stream));
-  HIPCHK(hipMemsetAsync(e->grad_m.p, 0, sizeof(double) * (size_t)N, e->stream));  // grad = 0 (:157)
-  if (noise_all && half > 0) FBCHK(e->noise.ensure(sizeof(double) * (size_t)N * half));
-  double *trace_dev = nullptr;
-  if (trace) {
-    FBCHK(e->trace_dev.ensure(sizeof(double) * (size_t)p->max_iter * (3 + S)));
-    trace_dev = e->trace_dev.as<double>();
-  }
-  FBCHK(e->ticks.ensure(sizeof(unsigned long long) * ((size_t)p->max_iter + 1)));
-  FBCHK(run_attack_core(e, p, N, noise_all, 0, p->max_iter, true, false, trace_dev, e->ticks.as<unsigned long long>()));
-  const int rows = e->h_ctl->iters_done;  // one trace row per executed iteration, the stopping one included
-  FBCHK(collect_iter_seconds(e, rows));
-  const bool broke = e->h_ctl->broke != 0;
-  const int it = e->h_ctl->stop_iter;
-  e->nes_iters += rows;
-  if (trace && rows > 0)
-    FBCHK(d2h(e, trace, trace_dev, sizeof(double) * (size_t)rows * (3 + S)));
-  const int last_iter = broke ? it : p->max_iter - 1;
-  *success_flag = (last_iter < p->max_iter - 1) ? 1 : -1;  // :219
-  if (n_trace) *n_trace = rows;
-  // adver -> int16 (:220)
-  FBCHK(e->wav.ensure(sizeof(int16_t) * (size_t)N * B));
-  fb_launch_quantize(e->stream, e->adver.as<double>(), N, nes_bits(p), e->wav.as<int16_t>());
-  FBCHK(d2h(e, adv_i16, e->wav.p, sizeof(int16_t) * (size_t)N));
-  if (adver_f64) FBCHK(d2h(e, adver_f64, e->adver.p, sizeof(double) * (size_t)N));
-  FBCHK(sync_stream(e));
-  return FB_OK;
-}
-
-extern "C" int fb_attack_iter_seconds(fb_engine *e, double *seconds, int n) {
-  if (!e || !seconds || n < 0) return fb_fail(FB_E_ARG, "bad argument");
-  if ((size_t)n > e->iter_seconds.size()) return fb_fail(FB_E_STATE, "the last attack ran %zu iterations (asked for %d)", e->iter_seconds.size(), n);
-  for (int i = 0; i < n; ++i) seconds[i] = e->iter_seconds[i];
-  return FB_OK;
-}
-
 extern "C" int fb_estimate_threshold(fb_engine *e, const fb_nes_params *p_in, double model_threshold,
                                      const double *audio, int64_t N, const double *noise_all, int max_total_iters,
                                      double *score_out, int *n_iters_out, int *n_outer_out, double *thr_final,
@@ -2729,15 +2632,10 @@ extern "C" int fb_estimate_threshold(fb_engine *e, const fb_nes_params *p_in, do
   if (p_in->task == FB_TASK_CSI) return fb_fail(FB_E_ARG, "no threshold to estimate for CSI (FAKEBOB.py:41-43)");
   fb_nes_params q = *p_in;
   q.attack_type = FB_UNTARGETED;  // :73-74
-  FBCHK(check_params(e, &q, N));
-  HIPCHK(hipSetDevice(e->device));
-  const int half = q.samples_per_draw / 2, B = 2 * half + 1, S = fb_num_speakers(e);
-  FBCHK(prepare_nes_batch(e, N, B));
-  FBCHK(ensure_nes_buffers(e, N, B));
-  FBCHK(h2d(e, e->audio.p, audio, sizeof(double) * (size_t)N));
-  HIPCHK(hipMemcpyAsync(e->adver.p, e->audio.p, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, e->stream));
-  HIPCHK(hipMemsetAsync(e->grad_m.p, 0, sizeof(double) * (size_t)N, e->stream));
-  if (noise_all && half > 0) FBCHK(e->noise.ensure(sizeof(double) * (size_t)N * half));
+  FbScorer sc{FB_SCORER_NATIVE};
+  FBCHK(nes_setup(e, &q, N, sc, false));
+  const int half = q.samples_per_draw / 2, B = 2 * half + 1, S = sc.S;
+  FBCHK(attack_start(e, audio, N, half, noise_all));
   // Column 0 of every NES batch is the clean adver (noise 0), i.e. exactly what
   // model.score(audio) (:53) / model.make_decisions(adver) (:89) would score, so one batch
   // per inner iteration serves both the decision and the gradient.
@@ -2759,7 +2657,7 @@ extern "C" int fb_estimate_threshold(fb_engine *e, const fb_nes_params *p_in, do
     // the loss depends on q.threshold, which may change below; scores do not.  Score first
     // with the current threshold, then (rarely) recompute the loss after a sweep step.
     FBCHK(enqueue_get_grad(e, &q, N, (uint32_t)n_iters, noise_dev, false));
-    FBCHK(fetch_out(e));
+    FBCHK(fetch_out(e, true));
     double s0 = e->h_out->score0[0];
     for (int s = 1; s < S; ++s) if (e->h_out->score0[s] > s0) s0 = e->h_out->score0[s];
     bool thr_changed = false;
@@ -2784,7 +2682,7 @@ extern "C" int fb_estimate_threshold(fb_engine *e, const fb_nes_params *p_in, do
                      e->zmean.as<double>(), e->zstd.as<double>(), q.threshold, q.adver_thresh, q.target,
                      q.true_label, e->dist_part.as<double>(), 0, e->scores.as<double>(), e->loss.as<double>(),
                      e->nes_out.as<FbNesDev>());
-      FBCHK(fetch_out(e));
+      FBCHK(fetch_out(e, true));
     }
     e->nes_iters += 1;
     pl.step(e->h_out->final_loss, &q);
@@ -3027,6 +2925,8 @@ extern "C" int fb_bench_nes(fb_engine *e, const fb_nes_params *p, const double *
   FBCHK(check_params(e, p, N));
   HIPCHK(hipSetDevice(e->device));
   const int half = p->samples_per_draw / 2, B = 2 * half + 1;
+  const FbScorer sc{FB_SCORER_NATIVE};
+  const FbLoopKnobs kn = loop_knobs(e, sc);
   const bool resume = warmup < 0;  // continue the attack a previous call left on the device: nothing is uploaded or reset
   if (resume) {
     if (e->bench_N != N || e->bench_B != B || e->bench_it < 0)
@@ -3035,22 +2935,21 @@ extern "C" int fb_bench_nes(fb_engine *e, const fb_nes_params *p, const double *
   } else {
     FBCHK(prepare_nes_batch(e, N, B));
     FBCHK(ensure_nes_buffers(e, N, B));
-    FBCHK(h2d(e, e->audio.p, audio, sizeof(double) * (size_t)N));
-    HIPCHK(hipMemcpyAsync(e->adver.p, e->audio.p, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, e->stream));
-    HIPCHK(hipMemsetAsync(e->grad_m.p, 0, sizeof(double) * (size_t)N, e->stream));
+    FBCHK(attack_start(e, audio, N, half, nullptr));
     e->bench_it = 0;
+    // identical work to fb_attack's loop (early stop disabled for timing)
+    FBCHK(ctl_reset(e, p, true, true, nullptr));
+    FBCHK(attack_loop(e, p, N, sc, kn, nullptr, 0, warmup, nullptr));
   }
   double gmm_ms = 0.0;
   int64_t vrows = 0;
-  // identical work to fb_attack's loop (early stop disabled for timing)
-  if (!resume) FBCHK(run_attack_core(e, p, N, nullptr, 0, warmup, true, true, nullptr));
   const int it0 = (int)e->bench_it + warmup;
   FBCHK(sync_stream(e));
   HIPCHK(hipEventRecord(e->ev0, e->stream));
   e->time_gmm = time_gmm;
   e->gmm_ms_acc = 0.0;
   e->gmm_launches = 0;
-  FBCHK(run_attack_core(e, p, N, nullptr, it0, iters, false, true, nullptr));
+  FBCHK(attack_loop(e, p, N, sc, kn, nullptr, it0, iters, nullptr));
   e->bench_it = it0 + iters;
   e->bench_N = N;
   e->bench_B = B;

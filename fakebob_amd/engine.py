@@ -255,31 +255,47 @@ class Engine(object):
 
     # ---- NES
     def get_grad(self, params, audio, it=0, noise_pos=None, want_grad=True):
+        return self._get_grad("fb_get_grad", params, max(self.n_speakers, 1), audio, it, noise_pos, want_grad)
+
+    def attack(self, params, audio, noise_all=None):
+        return self._attack("fb_attack", params, self.n_speakers, audio, noise_all)
+
+    def _nes_call(self, fn, err, *args):
+        try:
+            N.check(getattr(self._L, fn)(*args))
+        except N.NativeError as ex:
+            self._raise_cb(err, ex)
+
+    def _get_grad(self, fn, params, n_scores, audio, it, noise_pos, want_grad=True, model=None):
+        """The get_grad* wrappers: model(n) -> (the arguments between params and audio, the callback's error cell) for
+        a foreign model, None for this engine's system."""
         audio = np.ascontiguousarray(audio, np.float64).reshape(-1)
         n = audio.size
         npz = None if noise_pos is None else np.ascontiguousarray(noise_pos, np.float64)
         if npz is not None and npz.shape != (n, params.samples_per_draw // 2):
             raise ValueError("noise_pos must be (N, samples_per_draw//2)")
+        mid, err = model(n) if model else ((), [None])
         grad = np.empty(n, np.float64) if want_grad else None
         fl, al = C.c_double(), C.c_double()
-        sc = np.empty(max(self.n_speakers, 1), np.float64)
-        N.check(self._L.fb_get_grad(self._h, C.byref(params), N.ptr(audio), C.c_int64(n), C.c_uint32(it),
-                                    None if npz is None else N.ptr(npz), C.byref(fl),
-                                    None if grad is None else N.ptr(grad), C.byref(al), N.ptr(sc)))
+        sc = np.empty(n_scores, np.float64)
+        self._nes_call(fn, err, self._h, C.byref(params), *mid, N.ptr(audio), C.c_int64(n), C.c_uint32(it),
+                       None if npz is None else N.ptr(npz), C.byref(fl), None if grad is None else N.ptr(grad),
+                       C.byref(al), N.ptr(sc))
         return fl.value, grad, al.value, sc
 
-    def attack(self, params, audio, noise_all=None):
+    def _attack(self, fn, params, S, audio, noise_all, model=None):
+        """The attack* wrappers -> (int16 adv, flag, float64 adv, trace); model as in _get_grad."""
         audio = np.ascontiguousarray(audio, np.float64).reshape(-1)
         n = audio.size
         na = None if noise_all is None else np.ascontiguousarray(noise_all, np.float64)
-        S = self.n_speakers
+        mid, err = model(n) if model else ((), [None])
         adv = np.empty(n, np.int16)
         adv_f = np.empty(n, np.float64)
         trace = np.zeros((max(params.max_iter, 1), 3 + S), np.float64)
         nt, flag = C.c_int(), C.c_int()
-        N.check(self._L.fb_attack(self._h, C.byref(params), N.ptr(audio), C.c_int64(n),
-                                  None if na is None else N.ptr(na), N.ptr(adv), N.ptr(adv_f),
-                                  N.ptr(trace), C.byref(nt), C.byref(flag)))
+        self._nes_call(fn, err, self._h, C.byref(params), *mid, N.ptr(audio), C.c_int64(n),
+                       None if na is None else N.ptr(na), N.ptr(adv), N.ptr(adv_f), N.ptr(trace), C.byref(nt),
+                       C.byref(flag))
         return adv, flag.value, adv_f, trace[:nt.value]
 
     def attack_iter_seconds(self, n):
@@ -314,44 +330,19 @@ class Engine(object):
             raise err[0]
         raise ex
 
+    def _host_model(self, S, score_fn):
+        def model(_n):
+            err = [None]
+            return (C.c_int(S), self._score_cb(score_fn, S, err), None), err
+        return model
+
     def get_grad_ext(self, params, S, score_fn, audio, it=0, noise_pos=None):
         """fb_get_grad_ext: one NES gradient estimate at `audio` scored by score_fn."""
-        audio = np.ascontiguousarray(audio, np.float64).reshape(-1)
-        n = audio.size
-        npz = None if noise_pos is None else np.ascontiguousarray(noise_pos, np.float64)
-        if npz is not None and npz.shape != (n, params.samples_per_draw // 2):
-            raise ValueError("noise_pos must be (N, samples_per_draw//2)")
-        grad = np.empty(n, np.float64)
-        fl, al = C.c_double(), C.c_double()
-        sc = np.empty(S, np.float64)
-        err = [None]
-        cb = self._score_cb(score_fn, S, err)
-        try:
-            N.check(self._L.fb_get_grad_ext(self._h, C.byref(params), C.c_int(S), cb, None, N.ptr(audio),
-                                            C.c_int64(n), C.c_uint32(it), None if npz is None else N.ptr(npz),
-                                            C.byref(fl), N.ptr(grad), C.byref(al), N.ptr(sc)))
-        except N.NativeError as ex:
-            self._raise_cb(err, ex)
-        return fl.value, grad, al.value, sc
+        return self._get_grad("fb_get_grad_ext", params, S, audio, it, noise_pos, model=self._host_model(S, score_fn))
 
     def attack_ext(self, params, S, score_fn, audio, noise_all=None):
         """fb_attack_ext: the whole attack loop with a foreign scorer -> (int16 adv, flag, float64 adv, trace)."""
-        audio = np.ascontiguousarray(audio, np.float64).reshape(-1)
-        n = audio.size
-        na = None if noise_all is None else np.ascontiguousarray(noise_all, np.float64)
-        adv = np.empty(n, np.int16)
-        adv_f = np.empty(n, np.float64)
-        trace = np.zeros((max(params.max_iter, 1), 3 + S), np.float64)
-        nt, flag = C.c_int(), C.c_int()
-        err = [None]
-        cb = self._score_cb(score_fn, S, err)
-        try:
-            N.check(self._L.fb_attack_ext(self._h, C.byref(params), C.c_int(S), cb, None, N.ptr(audio), C.c_int64(n),
-                                          None if na is None else N.ptr(na), N.ptr(adv), N.ptr(adv_f), N.ptr(trace),
-                                          C.byref(nt), C.byref(flag)))
-        except N.NativeError as ex:
-            self._raise_cb(err, ex)
-        return adv, flag.value, adv_f, trace[:nt.value]
+        return self._attack("fb_attack_ext", params, S, audio, noise_all, model=self._host_model(S, score_fn))
 
     # ---- NES with a foreign model on the same GPU: the batch and the scores stay in device memory
     def _dev_model(self, params, S, n, x, scores, look_every):
@@ -397,48 +388,24 @@ class Engine(object):
                 return 1
         return N.SCORE_DEV_CB(_cb)
 
+    def _device_model(self, params, S, score_fn, x, scores, look_every):
+        def model(n):
+            m = self._dev_model(params, S, n, x, scores, look_every)
+            err = [None]
+            return (C.c_int(S), C.byref(m), self._score_dev_cb(score_fn, x, scores, S, err), None), err
+        return model
+
     def get_grad_dev(self, params, S, score_fn, x, scores, audio, it=0, noise_pos=None):
         """fb_get_grad_dev: one NES gradient estimate at `audio`, the batch written into the torch tensor x [B, N] and
         scored by score_fn on the GPU into scores [B, S]."""
-        audio = np.ascontiguousarray(audio, np.float64).reshape(-1)
-        n = audio.size
-        npz = None if noise_pos is None else np.ascontiguousarray(noise_pos, np.float64)
-        if npz is not None and npz.shape != (n, params.samples_per_draw // 2):
-            raise ValueError("noise_pos must be (N, samples_per_draw//2)")
-        m = self._dev_model(params, S, n, x, scores, 0)
-        grad = np.empty(n, np.float64)
-        fl, al = C.c_double(), C.c_double()
-        sc = np.empty(S, np.float64)
-        err = [None]
-        cb = self._score_dev_cb(score_fn, x, scores, S, err)
-        try:
-            N.check(self._L.fb_get_grad_dev(self._h, C.byref(params), C.c_int(S), C.byref(m), cb, None, N.ptr(audio),
-                                            C.c_int64(n), C.c_uint32(it), None if npz is None else N.ptr(npz),
-                                            C.byref(fl), N.ptr(grad), C.byref(al), N.ptr(sc)))
-        except N.NativeError as ex:
-            self._raise_cb(err, ex)
-        return fl.value, grad, al.value, sc
+        return self._get_grad("fb_get_grad_dev", params, S, audio, it, noise_pos,
+                              model=self._device_model(params, S, score_fn, x, scores, 0))
 
     def attack_dev(self, params, S, score_fn, x, scores, audio, noise_all=None, look_every=0):
         """fb_attack_dev: the whole attack loop around a model on the GPU -> (int16 adv, flag, float64 adv, trace).
         look_every: iterations between the host's looks at the loop control (0: 4)."""
-        audio = np.ascontiguousarray(audio, np.float64).reshape(-1)
-        n = audio.size
-        na = None if noise_all is None else np.ascontiguousarray(noise_all, np.float64)
-        m = self._dev_model(params, S, n, x, scores, look_every)
-        adv = np.empty(n, np.int16)
-        adv_f = np.empty(n, np.float64)
-        trace = np.zeros((max(params.max_iter, 1), 3 + S), np.float64)
-        nt, flag = C.c_int(), C.c_int()
-        err = [None]
-        cb = self._score_dev_cb(score_fn, x, scores, S, err)
-        try:
-            N.check(self._L.fb_attack_dev(self._h, C.byref(params), C.c_int(S), C.byref(m), cb, None, N.ptr(audio),
-                                          C.c_int64(n), None if na is None else N.ptr(na), N.ptr(adv), N.ptr(adv_f),
-                                          N.ptr(trace), C.byref(nt), C.byref(flag)))
-        except N.NativeError as ex:
-            self._raise_cb(err, ex)
-        return adv, flag.value, adv_f, trace[:nt.value]
+        return self._attack("fb_attack_dev", params, S, audio, noise_all,
+                            model=self._device_model(params, S, score_fn, x, scores, look_every))
 
     _FOREIGN_PATH = {1: "host", 2: "device"}
     _DT = {0: "float32", 1: "float64"}
