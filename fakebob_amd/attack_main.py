@@ -15,6 +15,7 @@ computed on rank 0 and broadcast, the success counters are all-reduced (fakebob_
 (The reference's own attackMain.py also runs unmodified on the engine: see fakebob_amd/dropin/.)
 """
 import argparse
+import functools
 import os
 import pickle
 import threading
@@ -38,21 +39,21 @@ def load_spk_models(model_dir, spk_id_list, architecture):
     return out
 
 
-def make_model(architecture, task, model_list, pre_model_dir, threshold, group_id):
-    """attackMain.load_model (:38-85)."""
+def make_model(architecture, task, model_list, pre_model_dir, threshold, group_id, dither=None):
+    """attackMain.load_model (:38-85).  dither: the systems' keyword (Kaldi's --dither: a number, or "conf")."""
     from .systems import gmm_CSI, gmm_OSI, gmm_SV, iv_CSI, iv_OSI, iv_SV
     ubm = os.path.join(pre_model_dir, "final.dubm")
     if architecture == "iv":
         if task == "OSI":
-            return iv_OSI(group_id, model_list, pre_model_dir=pre_model_dir, threshold=threshold)
+            return iv_OSI(group_id, model_list, pre_model_dir=pre_model_dir, threshold=threshold, dither=dither)
         if task == "CSI":
-            return iv_CSI(group_id, model_list, pre_model_dir=pre_model_dir)
-        return iv_SV(group_id, model_list[0], pre_model_dir=pre_model_dir, threshold=threshold)
+            return iv_CSI(group_id, model_list, pre_model_dir=pre_model_dir, dither=dither)
+        return iv_SV(group_id, model_list[0], pre_model_dir=pre_model_dir, threshold=threshold, dither=dither)
     if task == "OSI":
-        return gmm_OSI(group_id, model_list, ubm, pre_model_dir=pre_model_dir, threshold=threshold)
+        return gmm_OSI(group_id, model_list, ubm, pre_model_dir=pre_model_dir, threshold=threshold, dither=dither)
     if task == "CSI":
-        return gmm_CSI(group_id, model_list, pre_model_dir=pre_model_dir)
-    return gmm_SV(group_id, model_list[0], ubm, pre_model_dir=pre_model_dir, threshold=threshold)
+        return gmm_CSI(group_id, model_list, pre_model_dir=pre_model_dir, dither=dither)
+    return gmm_SV(group_id, model_list[0], ubm, pre_model_dir=pre_model_dir, threshold=threshold, dither=dither)
 
 
 def collect_voices(data_dir):
@@ -128,6 +129,11 @@ def main(argv=None, model_factory=None, bob_factory=None):
     ap.add_argument("--schedule", default="dynamic", choices=["dynamic", "static"],
                     help="dynamic: free attack streams draw the next attack (ticket counter); static: round-robin deal")
     ap.add_argument("--seed", default=None, type=int, help="Philox key (default: from numpy's global RNG)")
+    ap.add_argument("--dither", default=None,
+                    help="Kaldi's --dither for the victim's front end: a number, or 'conf' for what pre-models/conf/mfcc.conf "
+                         "configures (Kaldi's 1.0 when it is silent); default: off, or FB_DITHER")
+    ap.add_argument("--dither-seed", dest="dither_seed", default=0, type=int,
+                    help="dither key of the scoring calls outside an attack (inside one, --seed and the attack's stream key it)")
     ap.add_argument("--model_dir", default="./model")
     ap.add_argument("--pre_model_dir", default="pre-models")
     ap.add_argument("--test_dir", default="./data/test-set")
@@ -150,11 +156,14 @@ def main(argv=None, model_factory=None, bob_factory=None):
     K = max(1, args.streams)
     if model_factory is None:
         model_list = load_spk_models(args.model_dir, spk_id_list, args.architecture)
-        model_factory = make_model
+        model_factory = make_model if args.dither is None else functools.partial(make_model, dither=args.dither)
     else:
         model_list = spk_id_list
     models = [model_factory(args.architecture, task, model_list, args.pre_model_dir, args.threshold,
                             os.path.join(args.out_dir, ident + ("-%d" % k))) for k in range(K)]
+    for m in models:  # (a stub model of the driver-rule tests has no engine)
+        if hasattr(m, "engine") and hasattr(m.engine, "set_dither_seed"):
+            m.engine.set_dither_seed(args.dither_seed)
     if K >= 3:  # several engines share the GPU: the separate launches interleave better (fb_set_fused_chain)
         for m in models:
             if hasattr(m, "engine"):

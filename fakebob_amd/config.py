@@ -22,8 +22,12 @@ def _b(v):
     return 1 if str(v).lower() in ("true", "t", "1", "yes") else 0
 
 
-def frontend_overrides(mfcc_conf="", vad_conf="", delta_opts=""):
-    """Option text -> dict of fb_frontend_cfg field overrides."""
+def frontend_overrides(mfcc_conf="", vad_conf="", delta_opts="", dither=None):
+    """Option text -> dict of fb_frontend_cfg field overrides.
+
+    dither: None (default) leaves Kaldi's dither out of the result -- the engine keeps its dither = 0 -- and warns when
+    Kaldi would have dithered; "conf" puts the configured value in (--dither of mfcc.conf, Kaldi's default 1.0 when the
+    file is silent); a number puts that number in.  Neither warns."""
     o = {}
     m = _parse_opts(mfcc_conf)
     fs = float(m.get("sample-frequency", 16000))
@@ -54,8 +58,13 @@ def frontend_overrides(mfcc_conf="", vad_conf="", delta_opts=""):
         raise ValueError("window-type=%s unsupported (povey only)" % m["window-type"])
     # Kaldi's default is --dither=1.0 and the stock voxceleb mfcc.conf does not override it: a real Kaldi run adds
     # random noise of one LSB to every sample before the MFCC, which no re-implementation can reproduce
-    dither = float(m.get("dither", 1.0))
-    if dither != 0.0:
+    conf_dither = float(m.get("dither", 1.0))
+    if dither is not None:
+        o["dither"] = conf_dither if isinstance(dither, str) and dither == "conf" else float(dither)
+        if not o["dither"] >= 0.0 or o["dither"] == float("inf"):
+            raise ValueError("dither=%r: a finite value >= 0 is needed" % (o["dither"],))
+    elif conf_dither != 0.0:
+        dither = conf_dither
         warnings.warn("Kaldi would run with dither=%g (%s): its features are random at the 1-LSB level; the engine "
                       "always uses dither=0, so scores differ from a Kaldi run by that noise"
                       % (dither, "set in mfcc.conf" if "dither" in m else "Kaldi's default, mfcc.conf does not set it"))
@@ -74,11 +83,11 @@ def frontend_overrides(mfcc_conf="", vad_conf="", delta_opts=""):
     return o
 
 
-def frontend_from_kaldi_conf(pre_model_dir):
+def frontend_from_kaldi_conf(pre_model_dir, dither=None):
     def rd(p):
         p = os.path.join(pre_model_dir, p)
         if os.path.isfile(p):
             with open(p) as r:
                 return r.read()
         return ""
-    return frontend_overrides(rd("conf/mfcc.conf"), rd("conf/vad.conf"), rd("delta_opts"))
+    return frontend_overrides(rd("conf/mfcc.conf"), rd("conf/vad.conf"), rd("delta_opts"), dither=dither)

@@ -121,6 +121,49 @@ __device__ __forceinline__ void fb_noise4(uint64_t seed, uint32_t iter, uint32_t
   fb_box_muller(r[2], r[3], z[2], z[3]);
 }
 
+// fb_box_muller with the quadrant applied without branches: the same values bit for bit (a negation is a flip of the sign
+// bit).  The dither functions below call this form: inside the float64 MFCC kernels hipcc turned fb_box_muller's if-chain
+// into divergent branches whose q == 3 arm left the sine factor unset (seen in the ISA and as garbage samples on the
+// MI355X); selects leave nothing to structure.
+__device__ __forceinline__ void fb_box_muller_sel(uint32_t r0, uint32_t r1, float &z0, float &z1) {
+  float u1 = __fmul_rn((float)((r0 >> 8) + 1u), 5.9604644775390625e-08f);
+  uint32_t q = r1 >> 30;
+  uint32_t fr = (r1 & 0x3FFFFFFFu) >> 6;
+  float a = __fmul_rn((float)fr, 9.36227702e-08f);
+  float s, c;
+  fb_sincos_q(a, s, c);
+  float rr = sqrtf(__fmul_rn(-2.0f, fb_ln_u(u1)));
+  // q:  0 (c, s)   1 (-s, c)   2 (-c, -s)   3 (s, -c)
+  const uint32_t sb = __float_as_uint(s), cb = __float_as_uint(c);
+  const uint32_t odd = 0u - (q & 1u);                      // all ones for q = 1, 3
+  const uint32_t cs_b = ((sb & odd) | (cb & ~odd)) ^ (((q + 1u) & 2u) << 30);   // sign: q = 1, 2
+  const uint32_t sn_b = ((cb & odd) | (sb & ~odd)) ^ ((q & 2u) << 30);          // sign: q = 2, 3
+  z0 = __fmul_rn(rr, __uint_as_float(cs_b));
+  z1 = __fmul_rn(rr, __uint_as_float(sn_b));
+}
+
+// Kaldi's dither (include/fakebob_hip.h, "Dither RNG contract"): the standard normals of samples 4 q .. 4 q + 3 of frame
+// `frame` of utterance `utt` (index within the call) at `epoch`, key (k0, k1) = (seed_lo ^ "DITH", seed_hi ^ stream): the key
+// differs from the NES stream's, so the two never meet (FbDitherKey, fb_kernels.h, carries the words of a launch).
+__device__ __forceinline__ void fb_dither_words(uint32_t k0, uint32_t k1, uint32_t epoch, uint32_t utt, uint32_t frame,
+                                                uint32_t q, uint32_t r[4]) {
+  fb_philox4x32_10(q, frame, utt, epoch, k0, k1, r);
+}
+// the normals of samples 4 q + 2 h and 4 q + 2 h + 1 (h = 0, 1): one Box-Muller transform of two of the four words
+__device__ __forceinline__ void fb_dither2(uint32_t k0, uint32_t k1, uint32_t epoch, uint32_t utt, uint32_t frame,
+                                           uint32_t q, int h, float &z0, float &z1) {
+  uint32_t r[4];
+  fb_dither_words(k0, k1, epoch, utt, frame, q, r);
+  fb_box_muller_sel(h ? r[2] : r[0], h ? r[3] : r[1], z0, z1);
+}
+__device__ __forceinline__ void fb_dither4(uint32_t k0, uint32_t k1, uint32_t epoch, uint32_t utt, uint32_t frame,
+                                           uint32_t q, float z[4]) {
+  uint32_t r[4];
+  fb_dither_words(k0, k1, epoch, utt, frame, q, r);
+  fb_box_muller_sel(r[0], r[1], z[0], z[1]);
+  fb_box_muller_sel(r[2], r[3], z[2], z[3]);
+}
+
 // (x * 2^(bits-1)).astype(int16): trunc toward zero, keep the low 16 bits
 // (gmm_ubm_OSI.py:83-85; golden G5: 1.0 -> -32768)
 __device__ __forceinline__ int16_t fb_quantize(double x, double scale) {

@@ -84,6 +84,12 @@ struct fb_engine {
   FbFrontendDev fe;
   int melw_n = 0;  // packed mel weight count
   DevBuf fe_tables, fe_tables32;
+  // Kaldi's dither (cfg.dither > 0; the "Dither RNG contract" of fakebob_hip.h)
+  uint64_t dither_seed = 0;     // fb_set_dither_seed: the key of scoring calls outside an attack
+  uint32_t dither_serial = 0;   // ... and their epoch: scoring calls since it was set
+  FbDitherKey dkey = {};        // what the next front-end launch carries: set by every path in front of launch_mfcc
+  DevBuf frame_ut;              // [total_frames][2] {utterance, frame within it} of the batch (prepare_batch, dither > 0)
+  std::vector<int32_t> h_frame_ut;
   // gmm
   bool have_gmm = false;
   FbGmmDev gmm;
@@ -248,7 +254,7 @@ extern "C" int fb_engine_destroy(fb_engine *e) {
   if (!e) return FB_OK;
   (void)hipSetDevice(e->device);
   if (e->stream) (void)hipStreamSynchronize(e->stream);
-  DevBuf *bufs[] = {&e->fe_tables, &e->fe_tables32, &e->gmm_items, &e->gmm_images_bx, &e->gmm_images_fx, &e->gmm_images_fd, &e->gmm_images_fd2, &e->gmm_images_fd3, &e->gmm_anchor, &e->zmean, &e->zstd, &e->wav, &e->wav_off,
+  DevBuf *bufs[] = {&e->fe_tables, &e->fe_tables32, &e->frame_ut, &e->gmm_items, &e->gmm_images_bx, &e->gmm_images_fx, &e->gmm_images_fd, &e->gmm_images_fd2, &e->gmm_images_fd3, &e->gmm_anchor, &e->zmean, &e->zstd, &e->wav, &e->wav_off,
                     &e->frame_rec, &e->vad_counter, &e->vad_pub, &e->vad_part, &e->fin_counter, &e->fin_xch, &e->ctl, &e->ctl_ls, &e->trace_dev, &e->ticks, &e->enr_ll, &e->enr_aux, &e->enr_stats, &e->frame_off, &e->chunk_off, &e->chunk_sum, &e->mfcc, &e->mfcc_cm, &e->vrank, &e->tv, &e->row_off, &e->dfeat, &e->feats,
                     &e->part_m, &e->part_s, &e->raw, &e->audio, &e->adver, &e->grad_m, &e->grad, &e->noise, &e->zbuf,
                     &e->scores, &e->loss, &e->dist_part, &e->nes_out, &e->stage_f64, &e->ext_x, &e->ext_z, &e->iv_fg, &e->iv_fg64, &e->iv_fgL, &e->iv_tri,
@@ -279,6 +285,7 @@ extern "C" void fb_default_frontend(fb_frontend_cfg *c) {
   c->text_scores = 0;
   c->compress_feats = 0;
   c->mfcc_f32 = 0;
+  c->dither = 0.0;
 }
 
 static double mel_scale(double f) { return 1127.0 * log(1.0 + f / 700.0); }
@@ -297,6 +304,7 @@ extern "C" int fb_set_frontend(fb_engine *e, const fb_frontend_cfg *c) {
   // context is no window at all
   if (c->cmn_window < 1) return fb_fail(FB_E_ARG, "cmn_window %d < 1", c->cmn_window);
   if (c->vad_frames_context < 0) return fb_fail(FB_E_ARG, "vad_frames_context %d < 0", c->vad_frames_context);
+  if (!(c->dither >= 0.0) || !std::isfinite(c->dither)) return fb_fail(FB_E_ARG, "dither %g is not a finite value >= 0", c->dither);
   const int dim = nc * (c->delta_order + 1);
   if (dim > 256) return fb_fail(FB_E_ARG, "feature dim %d > 256 unsupported", dim);
   HIPCHK(hipSetDevice(e->device));
@@ -1121,6 +1129,16 @@ static int prepare_batch(fb_engine *e, const int64_t *off, int B) {
     }
     FBCHK(e->frame_rec.ensure(sizeof(int32_t) * 4 * (size_t)(total > 0 ? total : 1)));
     FBCHK(h2d(e, e->frame_rec.p, e->h_frame_rec.data(), sizeof(int32_t) * 4 * (size_t)total));
+    if (e->cfg.dither > 0.0) {  // the dithered kernels' counter words of a frame: {utterance, frame within it}
+      e->h_frame_ut.resize((size_t)2 * total);
+      for (int b = 0; b < B; ++b)
+        for (int f = e->h_frame_off[b]; f < e->h_frame_off[b + 1]; ++f) {
+          e->h_frame_ut[(size_t)2 * f] = b;
+          e->h_frame_ut[(size_t)2 * f + 1] = f - e->h_frame_off[b];
+        }
+      FBCHK(e->frame_ut.ensure(sizeof(int32_t) * 2 * (size_t)(total > 0 ? total : 1)));
+      FBCHK(h2d(e, e->frame_ut.p, e->h_frame_ut.data(), sizeof(int32_t) * 2 * (size_t)total));
+    }
   }
   FBCHK(e->chunk_off.ensure(sizeof(int) * (B + 1)));
   FBCHK(h2d(e, e->chunk_off.p, e->h_chunk_off.data(), sizeof(int) * (B + 1)));
@@ -1222,12 +1240,25 @@ static void launch_mfcc(fb_engine *e, int B, int total_frames) {
   e->have_route = true;
   e->route[3] = e->t_max;
   e->route[4] = B;
+  // Kaldi's dither: the dithered form of the same kernel, with the key its caller left in e->dkey (the amplitude is the
+  // configuration's whatever the caller wrote)
+  const bool dither = e->cfg.dither > 0.0;
+  e->dkey.amp = e->cfg.dither;
+  const FbDitherKey *dk = dither ? &e->dkey : nullptr;
+  const int32_t *ut = dither ? e->frame_ut.as<int32_t>() : nullptr;
   if (fe.mfcc_f32 && fb_launch_mfcc_f32(s, fe, e->melw_n, e->wav.as<int16_t>(), e->frame_rec.as<int32_t>(), total_frames,
-                                        e->mfcc.as<float>(), e->uni_T, e->uni_n, e->h_wav_off[0], &e->shape_mfcc))
-    e->route[0] = fe.L / 32 >= 12 ? FB_ROUTE_MFCC_F32_12 : FB_ROUTE_MFCC_F32_0;  // (fb_launch_mfcc_f32's instantiation rule)
+                                        e->mfcc.as<float>(), e->uni_T, e->uni_n, e->h_wav_off[0], &e->shape_mfcc, dk, ut))
+    e->route[0] = fe.L / 32 >= 12 ? (dither ? FB_ROUTE_MFCC_F32_12_DITHER : FB_ROUTE_MFCC_F32_12)
+                                  : (dither ? FB_ROUTE_MFCC_F32_0_DITHER : FB_ROUTE_MFCC_F32_0);  // (fb_launch_mfcc_f32's instantiation rule)
   else
     e->route[0] = fb_launch_mfcc(s, fe, e->melw_n, e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), e->frame_off.as<int>(),
-                                 e->frame_rec.as<int32_t>(), B, total_frames, e->mfcc.as<float>());
+                                 e->frame_rec.as<int32_t>(), B, total_frames, e->mfcc.as<float>(), dk, ut);
+}
+// the dither key of a scoring call outside an attack (fb_score_*, fb_gmm_acc_stats, fb_debug_mfcc / _feats): the engine's
+// seed, stream 0xFFFFFFFF, epoch = the scoring-call serial, which the call consumes
+static void dither_key_scoring_call(fb_engine *e) {
+  e->dkey = fb_dither_key(e->cfg.dither, e->dither_seed, 0xFFFFFFFFu, e->dither_serial, 0);
+  e->dither_serial += 1;
 }
 
 // mfcc -> VAD (+ row offsets) -> deltas -> CMVN -> voiced-row compaction
@@ -1549,6 +1580,7 @@ extern "C" int fb_score_i16(fb_engine *e, const int16_t *wav, const int64_t *off
   FBCHK(h2d(e, e->wav.p, wav, sizeof(int16_t) * (size_t)total));
   FBCHK(prepare_batch(e, off, B));
   e->cached_B = -1;
+  dither_key_scoring_call(e);
   FBCHK(run_scoring(e, B, e->h_frame_off[B]));
   return finish_score(e, B, raw, tv);
 }
@@ -1568,6 +1600,7 @@ extern "C" int fb_score_f64(fb_engine *e, const double *audio, const int64_t *of
   fb_launch_quantize(e->stream, e->stage_f64.as<double>(), total, bits, e->wav.as<int16_t>());
   FBCHK(prepare_batch(e, off, B));
   e->cached_B = -1;
+  dither_key_scoring_call(e);
   FBCHK(run_scoring(e, B, e->h_frame_off[B]));
   return finish_score(e, B, raw, tv);
 }
@@ -2115,6 +2148,9 @@ static int enqueue_get_grad(fb_engine *e, const fb_nes_params *p, int64_t N, uin
     e->tail_loss_req = true;
   }
   e->tail_loss_done = false;
+  // Kaldi's dither inside an attack: keyed by the attack's own (seed, stream), epoch = the NES iteration (in
+  // fb_estimate_threshold `iter` counts the call's front-end launches: one per pass of its loop)
+  e->dkey = fb_dither_key(e->cfg.dither, p->seed, p->stream, iter, 0);
   const int rc = run_scoring(e, B, e->h_frame_off[B]);
   e->tail_loss_req = false;
   e->defer_finalize = false;
@@ -2729,7 +2765,8 @@ extern "C" int fb_debug_quantize(fb_engine *e, const double *x, int64_t n, int b
   return FB_OK;
 }
 
-static int debug_frontend(fb_engine *e, const int16_t *wav, int64_t n) {
+// key (nullable): the point of the dither contract the utterance stands at; null = a scoring call of the engine's own
+static int debug_frontend(fb_engine *e, const int16_t *wav, int64_t n, const FbDitherKey *key = nullptr) {
   if (!e || !wav || n <= 0) return fb_fail(FB_E_ARG, "bad argument");
   HIPCHK(hipSetDevice(e->device));
   FBCHK(sync_stream(e));
@@ -2746,6 +2783,8 @@ static int debug_frontend(fb_engine *e, const int16_t *wav, int64_t n) {
   FBCHK(e->row_off.ensure(sizeof(int) * 2));
   FBCHK(e->feats.ensure(sizeof(float) * (size_t)T * fe.dim));
   choose_launch_shape(e);
+  if (key) e->dkey = *key;
+  else dither_key_scoring_call(e);
   launch_mfcc(e, 1, T);
   FBCHK(run_post_mfcc(e, 1));
   HIPCHK(hipGetLastError());
@@ -2820,19 +2859,60 @@ extern "C" int fb_gmm_delta_tiles_f6(fb_engine *e) {
   return wide ? e->gmm.delta_t6 - e->gmm.delta_t3 : 0;
 }
 
-extern "C" int fb_debug_mfcc(fb_engine *e, const int16_t *wav, int64_t n, float *mfcc, int *T_out) {
+static int debug_mfcc(fb_engine *e, const int16_t *wav, int64_t n, const FbDitherKey *key, float *mfcc, int *T_out) {
   if (!mfcc) return fb_fail(FB_E_ARG, "mfcc is NULL");
-  FBCHK(debug_frontend(e, wav, n));
+  FBCHK(debug_frontend(e, wav, n, key));
   const int T = e->h_frame_off[1];
   FBCHK(d2h(e, mfcc, e->mfcc.p, sizeof(float) * (size_t)T * e->fe.nc));
   FBCHK(sync_stream(e));
   if (T_out) *T_out = T;
   return FB_OK;
 }
+extern "C" int fb_debug_mfcc(fb_engine *e, const int16_t *wav, int64_t n, float *mfcc, int *T_out) {
+  return debug_mfcc(e, wav, n, nullptr, mfcc, T_out);
+}
+extern "C" int fb_debug_mfcc_dither(fb_engine *e, const int16_t *wav, int64_t n, uint64_t seed, uint32_t stream,
+                                    uint32_t epoch, uint32_t utt, float *mfcc, int *T_out) {
+  const FbDitherKey key = fb_dither_key(0.0, seed, stream, epoch, utt);
+  return debug_mfcc(e, wav, n, &key, mfcc, T_out);
+}
 
+// the normals of the dither contract, from the device function the MFCC kernels call
+extern "C" int fb_debug_dither_noise(fb_engine *e, uint64_t seed, uint32_t stream, uint32_t epoch, uint32_t utt, int t0,
+                                     int n_frames, int L, float *z) {
+  if (!e || !z || t0 < 0 || n_frames <= 0 || L <= 0) return fb_fail(FB_E_ARG, "bad argument");
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  const size_t bytes = sizeof(float) * (size_t)n_frames * L;
+  DevBuf tmp;
+  FBCHK(tmp.ensure(bytes));
+  fb_launch_dither_noise(e->stream, fb_dither_key(1.0, seed, stream, epoch, utt), t0, n_frames, L, tmp.as<float>());
+  hipError_t er = hipMemcpyAsync(z, tmp.p, bytes, hipMemcpyDeviceToHost, e->stream);
+  if (er == hipSuccess) er = hipStreamSynchronize(e->stream);
+  tmp.release();
+  if (er != hipSuccess) return fb_fail(FB_E_HIP, "dither noise dump failed: %s", hipGetErrorString(er));
+  return FB_OK;
+}
+
+extern "C" int fb_set_dither_seed(fb_engine *e, uint64_t seed) {
+  if (!e) return fb_fail(FB_E_ARG, "null engine");
+  e->dither_seed = seed;
+  e->dither_serial = 0;
+  return FB_OK;
+}
+
+static int debug_feats(fb_engine *e, const int16_t *wav, int64_t n, const FbDitherKey *key, float *feats, int *Tv, int *T_out);
 extern "C" int fb_debug_feats(fb_engine *e, const int16_t *wav, int64_t n, float *feats, int *Tv, int *T_out) {
+  return debug_feats(e, wav, n, nullptr, feats, Tv, T_out);
+}
+extern "C" int fb_debug_feats_dither(fb_engine *e, const int16_t *wav, int64_t n, uint64_t seed, uint32_t stream,
+                                     uint32_t epoch, uint32_t utt, float *feats, int *Tv, int *T_out) {
+  const FbDitherKey key = fb_dither_key(0.0, seed, stream, epoch, utt);
+  return debug_feats(e, wav, n, &key, feats, Tv, T_out);
+}
+static int debug_feats(fb_engine *e, const int16_t *wav, int64_t n, const FbDitherKey *key, float *feats, int *Tv, int *T_out) {
   if (!feats || !Tv) return fb_fail(FB_E_ARG, "null output");
-  FBCHK(debug_frontend(e, wav, n));
+  FBCHK(debug_frontend(e, wav, n, key));
   const int T = e->h_frame_off[1];
   int tv = 0;
   FBCHK(d2h(e, &tv, e->tv.p, sizeof(int)));

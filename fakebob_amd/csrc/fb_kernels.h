@@ -30,6 +30,18 @@ struct FbFrontendDev {
   int mfcc_cus;           // k_mfcc_f32: compute units the launch may take (0 = all); set per batch by the engine
 };
 
+// What a front-end launch carries of the dither RNG contract (include/fakebob_hip.h): Kaldi's --dither, the Philox key
+// (seed_lo ^ "DITH", seed_hi ^ stream), counter word 3 and the index of the batch's first utterance within the call
+struct FbDitherKey {
+  double amp;
+  uint32_t k0, k1, epoch, utt0;
+};
+static inline FbDitherKey fb_dither_key(double amp, uint64_t seed, uint32_t stream, uint32_t epoch, uint32_t utt0) {
+  return FbDitherKey{amp, (uint32_t)seed ^ 0x44495448u, (uint32_t)(seed >> 32) ^ stream, epoch, utt0};
+}
+// the normals the dithered MFCC kernels add to frames t0 .. t0 + n_frames - 1 of utterance dk.utt0: z[n_frames][L]
+void fb_launch_dither_noise(hipStream_t s, const FbDitherKey &dk, int t0, int n_frames, int L, float *z);
+
 // ---- NES ----------------------------------------------------------------
 // q[b][n] = int16((adver[n] + sigma*noise_b[n]) * 2^15), b in [0, 2*half]; column 0 is the
 // un-noised adver.  noise: Philox(seed, iter, stream) or explicit float64 [N][half].
@@ -135,9 +147,11 @@ void fb_launch_grad_update(hipStream_t s, const double *loss, int64_t N, int hal
 // frame_rec: [total_frames][4] int32 = {absolute start sample (int64 in two words), start within the
 // utterance, utterance length} (used by the P = 512 kernel instead of a search in frame_off).  Returns the kernel it
 // launched: FB_ROUTE_MFCC_R16_* or FB_ROUTE_MFCC_GENERIC (fb_debug_frontend_route)
+// dk != nullptr (dk->amp > 0): the dithered form of the same kernel (FB_ROUTE_MFCC_*_DITHER); frame_ut[total_frames][2] =
+// {utterance, frame within it} then serves the kernels that read frame records
 int fb_launch_mfcc(hipStream_t s, const FbFrontendDev &fe, int melw_n, const int16_t *wav,
                     const int64_t *wav_off, const int *frame_off, const int32_t *frame_rec, int B,
-                    int total_frames, float *mfcc);
+                    int total_frames, float *mfcc, const FbDitherKey *dk = nullptr, const int32_t *frame_ut = nullptr);
 // fb_frontend_cfg.mfcc_f32: the float32 kernel (frontend_f32_kernels.hip); false = this configuration is not one it takes
 bool fb_mfcc_f32_supported(const FbFrontendDev &fe);
 // the float32 table blob of k_mfcc_f32 (its LDS image up to the per-wave buffers) from the float64 host tables
@@ -151,9 +165,10 @@ struct FbMfccShape { int cus, rounds, blocks; };
 // uni_T > 0: every utterance has uni_n samples / uni_T frames and the first one starts at sample uni_base -- a frame's
 // record is computed, not loaded (one dependent global round trip less at the head of every wave).  shape (nullable): filled
 // in with the launch's geometry when the kernel is launched
+// dk / frame_ut: as fb_launch_mfcc
 bool fb_launch_mfcc_f32(hipStream_t s, const FbFrontendDev &fe, int melw_n, const int16_t *wav, const int32_t *frame_rec,
                         int total_frames, float *mfcc, int uni_T = 0, int64_t uni_n = 0, int64_t uni_base = 0,
-                        FbMfccShape *shape = nullptr);
+                        FbMfccShape *shape = nullptr, const FbDitherKey *dk = nullptr, const int32_t *frame_ut = nullptr);
 // VAD + per-utt voiced ranks.  vrank[f] = rank among voiced frames of its utt or -1; tv[b].
 // counter: one device int, zero before the first launch (the kernel leaves it at zero); row_off[B+1]
 // = exclusive scan of max(tv, 0), written by the workgroup that finishes last

@@ -163,12 +163,19 @@ extern "C" int fb_debug_mfcc_stamps(unsigned long long *out) {
 
 // NFULL: the points a < NFULL lie inside the frame for every lane (32 a + 31 < L), their validity selects are dropped
 // at compile time (12 of 16 for the recipe's L = 400); 0 = no assumption.
-template <int NFULL>
+// DITHER: Kaldi's --dither (fb_frontend_cfg.dither > 0).  Every extracted sample becomes fmaf(dither, z, (float)x) with z the
+// normal of (utterance, frame, sample-in-frame) under the dither RNG contract (include/fakebob_hip.h), drawn here: a lane's
+// point is half of a Philox quad, so it runs the ten rounds and ONE Box-Muller transform per point.  The frame is no longer
+// integers: sum x and sum x^2 are float64 accumulations of the float32 samples (an error of 1e-16 of the raw moments: nothing
+// next to the float32 arithmetic behind them), everything after that is the undithered kernel's.  dk and frame_ut (the
+// {utterance, frame} of a frame, for batches that read frame records) are not read when DITHER is false.
+template <int NFULL, bool DITHER>
 __global__ __launch_bounds__(64 * FB_F32_WAVES, 1) void k_mfcc_f32(FbFrontendDev fe, int melw_n,
                                                                    const int16_t *__restrict__ wav,
                                                                    const int4 *__restrict__ frame_rec,
                                                                    int total_frames, float *__restrict__ mfcc, int words,
-                                                                   int uni_T, int uni_n, long long uni_base) {
+                                                                   int uni_T, int uni_n, long long uni_base,
+                                                                   FbDitherKey dk, const int2 *__restrict__ frame_ut) {
   if (fe.stop && *fe.stop) return;
   extern __shared__ __attribute__((aligned(16))) float smem32[];
   constexpr int NT = 64 * FB_F32_WAVES, Nc = 256;
@@ -189,7 +196,7 @@ __global__ __launch_bounds__(64 * FB_F32_WAVES, 1) void k_mfcc_f32(FbFrontendDev
   const int n_groups = (total_frames + 3) >> 2;
   const int w_glob = blockIdx.x * FB_F32_WAVES + w, w_step = gridDim.x * FB_F32_WAVES;
   // samples of points p = 16 a + t of frame 4 g + fq: s0 = 32 a + 2 t and s0 + 1, packed into one register per point
-  auto load_group = [&](int g, int tl, int (&xq)[16]) {
+  auto load_group = [&](int g, int tl, int (&xq)[16], int2 &ut) {  // ut (DITHER): {utterance, frame within it}
     const int fl = 4 * g + fq;
     const int fc = fl < total_frames ? fl : total_frames - 1;
     int64_t abs_start;
@@ -199,11 +206,13 @@ __global__ __launch_bounds__(64 * FB_F32_WAVES, 1) void k_mfcc_f32(FbFrontendDev
       start = fe.snip_edges ? tt * fe.shift : tt * fe.shift + fe.shift / 2 - L / 2;
       n = uni_n;
       abs_start = uni_base + (int64_t)b * uni_n + start;
+      if constexpr (DITHER) ut = int2{b, tt};
     } else {
       const int4 rec = frame_rec[fc];
       abs_start = ((int64_t)(unsigned)rec.x) | ((int64_t)rec.y << 32);
       start = rec.z;
       n = rec.w;
+      if constexpr (DITHER) ut = frame_ut[fc];
     }
     const bool interior = start >= 0 && start + L <= n;
     if (words && __all(interior && !(abs_start & 1))) {  // the pair of a point is one aligned 32-bit word, already in register format
@@ -240,7 +249,8 @@ __global__ __launch_bounds__(64 * FB_F32_WAVES, 1) void k_mfcc_f32(FbFrontendDev
     }
   };
   int xn[16];
-  if (w_glob < n_groups) load_group(w_glob, t_lane, xn);
+  int2 utn = {0, 0};
+  if (w_glob < n_groups) load_group(w_glob, t_lane, xn, utn);
   // tables: one float32 blob in this kernel's LDS layout, built by fb_set_frontend from the float64 host tables (the
   // window, mel weights, DCT and lifter are float32 values already: Kaldi stores them as BaseFloat) -- a straight copy,
   // one 16-byte load per thread
@@ -269,36 +279,62 @@ __global__ __launch_bounds__(64 * FB_F32_WAVES, 1) void k_mfcc_f32(FbFrontendDev
     int xp[16];
 #pragma unroll
     for (int a = 0; a < 16; ++a) xp[a] = xn[a];
-    if (g + w_step < n_groups) load_group(g + w_step, t, xn);
+    const int2 utp = utn;
+    if (g + w_step < n_groups) load_group(g + w_step, t, xn, utn);
     // ---- exact integer moments of the frame: sum x (|.| < 2^24) and sum x^2 (< 2^39).  A register holds the sample
     //      pair of a point, so one v_dot2 gives x0 + x1 and one gives x0^2 + x1^2 (<= 2^31: read as unsigned); the squares
     //      are summed in float64, where every partial sum is an integer below 2^53, i.e. exact.  L is even, so the two
     //      samples of a pair lie inside the frame or outside it together.
     int isum = 0;
     double sqd = 0.0;
-    const s16x2 ones = {1, 1};
+    f32x2 fs[DITHER ? 16 : 1];  // DITHER: the dithered samples of point a
+    double smd = 0.0;           // ... and their sum
+    if constexpr (DITHER) {
+      const float amp = (float)dk.amp;
+      const unsigned utt = dk.utt0 + (unsigned)utp.x;
 #pragma unroll
-    for (int a = 0; a < 16; ++a) {
-      if (a >= NFULL) xp[a] = 32 * a + 2 * t < L ? xp[a] : 0;
-      const s16x2 q = __builtin_bit_cast(s16x2, xp[a]);
-      isum = __builtin_amdgcn_sdot2(q, ones, isum, false);
-      sqd += (double)(unsigned)__builtin_amdgcn_sdot2(q, q, 0, false);
+      for (int a = 0; a < 16; ++a) {
+        float z0, z1;  // samples 32 a + 2 t, + 1: half h = t & 1 of quad 8 a + t / 2
+        fb_dither2(dk.k0, dk.k1, dk.epoch, utt, (unsigned)utp.y, (unsigned)(8 * a + (t >> 1)), t & 1, z0, z1);
+        f32x2 x = {__builtin_fmaf(amp, z0, (float)(int)(short)xp[a]), __builtin_fmaf(amp, z1, (float)(xp[a] >> 16))};
+        if (a >= NFULL) x = 32 * a + 2 * t < L ? x : f32x2{0.0f, 0.0f};
+        fs[a] = x;
+        const double x0 = (double)x.x, x1 = (double)x.y;
+        smd += x0;
+        smd += x1;
+        sqd = __builtin_fma(x0, x0, sqd);
+        sqd = __builtin_fma(x1, x1, sqd);
+        if (a & 1) __builtin_amdgcn_sched_barrier(0);  // two points' transforms in flight: bounds the live registers
+      }
+      smd += fb_dpp_f64<0xb1, 0xf>(smd);
+      smd += fb_dpp_f64<0x4e, 0xf>(smd);
+      smd += fb_dpp_f64<0x141, 0xf>(smd);
+      smd += fb_dpp_f64<0x140, 0xf>(smd);
+    } else {
+      const s16x2 ones = {1, 1};
+#pragma unroll
+      for (int a = 0; a < 16; ++a) {
+        if (a >= NFULL) xp[a] = 32 * a + 2 * t < L ? xp[a] : 0;
+        const s16x2 q = __builtin_bit_cast(s16x2, xp[a]);
+        isum = __builtin_amdgcn_sdot2(q, ones, isum, false);
+        sqd += (double)(unsigned)__builtin_amdgcn_sdot2(q, q, 0, false);
+      }
+      isum = fb_row_sum_i32f(isum);
     }
-    isum = fb_row_sum_i32f(isum);
     sqd += fb_dpp_f64<0xb1, 0xf>(sqd);
     sqd += fb_dpp_f64<0x4e, 0xf>(sqd);
     sqd += fb_dpp_f64<0x141, 0xf>(sqd);
     sqd += fb_dpp_f64<0x140, 0xf>(sqd);
-    const double dcd = fe.remove_dc ? (double)isum : 0.0;
-    const double energy = ((double)L * sqd - dcd * dcd) / (double)L;  // exact numerator (< 2^53), one rounding
-    const float mean = fe.remove_dc ? (float)isum / (float)L : 0.0f;
+    const double dcd = fe.remove_dc ? (DITHER ? smd : (double)isum) : 0.0;
+    const double energy = ((double)L * sqd - dcd * dcd) / (double)L;  // undithered: exact numerator (< 2^53), one rounding
+    const float mean = fe.remove_dc ? (DITHER ? (float)(smd / (double)L) : (float)isum / (float)L) : 0.0f;
 
     f32x2 v[16];
     float prev_rot = 0.0f;  // row-rotated second samples (mean removed) of point a - 1
 #pragma unroll
     for (int a = 0; a < 16; ++a) {
       const int s0 = 32 * a + 2 * t;
-      const f32x2 d = f32x2{(float)(int)(short)xp[a], (float)(xp[a] >> 16)} - mean;
+      const f32x2 d = (DITHER ? fs[DITHER ? a : 0] : f32x2{(float)(int)(short)xp[a], (float)(xp[a] >> 16)}) - mean;
       // row_ror:1: lane t gets lane (t - 1) & 15 -- the sample before this lane's first one, already converted
       const float rot = __int_as_float(fb_dpp_i32<0x121, 0xf>(__float_as_int(d.y)));
       const f32x2 pv = {t == 0 ? (a == 0 ? d.x : prev_rot) : rot, d.x};  // Kaldi: sample 0 is pre-emphasised with itself
@@ -492,7 +528,8 @@ bool fb_mfcc_f32_supported(const FbFrontendDev &fe) {
   return fe.P == 512 && fe.nb <= 31 && fe.nc <= 32 && (fe.L & 1) == 0 && fe.L >= 2 && fe.L <= 512 && fe.raw_energy != 0 && fe.f32_tab != nullptr;
 }
 bool fb_launch_mfcc_f32(hipStream_t s, const FbFrontendDev &fe, int melw_n, const int16_t *wav, const int32_t *frame_rec,
-                        int total_frames, float *mfcc, int uni_T, int64_t uni_n, int64_t uni_base, FbMfccShape *shape) {
+                        int total_frames, float *mfcc, int uni_T, int64_t uni_n, int64_t uni_base, FbMfccShape *shape,
+                        const FbDitherKey *dk, const int32_t *frame_ut) {
   if (total_frames <= 0) return true;
   if (!fb_mfcc_f32_supported(fe)) return false;
   const MfccF32Lds l = fb_mfcc_f32_layout(fe.L, fe.nb, fe.nc, melw_n);
@@ -501,7 +538,8 @@ bool fb_launch_mfcc_f32(hipStream_t s, const FbFrontendDev &fe, int melw_n, cons
   static std::atomic<unsigned long long> optin{0};
   unsigned long long bit = 0;
   if (fb_device_needs_optin(optin, &bit)) {
-    const void *fns[] = {reinterpret_cast<const void *>(k_mfcc_f32<12>), reinterpret_cast<const void *>(k_mfcc_f32<0>)};
+    const void *fns[] = {reinterpret_cast<const void *>(k_mfcc_f32<12, false>), reinterpret_cast<const void *>(k_mfcc_f32<0, false>),
+                         reinterpret_cast<const void *>(k_mfcc_f32<12, true>), reinterpret_cast<const void *>(k_mfcc_f32<0, true>)};
     for (const void *fn : fns)
       if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return false;
     optin.fetch_or(bit, std::memory_order_release);
@@ -518,7 +556,15 @@ bool fb_launch_mfcc_f32(hipStream_t s, const FbFrontendDev &fe, int melw_n, cons
   const int un = (int)uni_n;
   const long long ub = (long long)uni_base;
   if (shape) *shape = FbMfccShape{cus, rounds, blocks};
-  if (fe.L / 32 >= 12) hipLaunchKernelGGL((k_mfcc_f32<12>), dim3(blocks), dim3(64 * FB_F32_WAVES), shm, s, fe, melw_n, wav, rec, total_frames, mfcc, words, uni_T, un, ub);
-  else hipLaunchKernelGGL((k_mfcc_f32<0>), dim3(blocks), dim3(64 * FB_F32_WAVES), shm, s, fe, melw_n, wav, rec, total_frames, mfcc, words, uni_T, un, ub);
+  const bool dither = dk != nullptr && dk->amp > 0.0;
+  if (dither && uni_T <= 0 && frame_ut == nullptr) return false;
+  const FbDitherKey dkv = dither ? *dk : FbDitherKey{};
+  const int2 *ut = reinterpret_cast<const int2 *>(frame_ut);
+  const dim3 grid(blocks), blk(64 * FB_F32_WAVES);
+  const bool full12 = fe.L / 32 >= 12;
+  if (full12 && !dither) hipLaunchKernelGGL((k_mfcc_f32<12, false>), grid, blk, shm, s, fe, melw_n, wav, rec, total_frames, mfcc, words, uni_T, un, ub, dkv, ut);
+  else if (!dither) hipLaunchKernelGGL((k_mfcc_f32<0, false>), grid, blk, shm, s, fe, melw_n, wav, rec, total_frames, mfcc, words, uni_T, un, ub, dkv, ut);
+  else if (full12) hipLaunchKernelGGL((k_mfcc_f32<12, true>), grid, blk, shm, s, fe, melw_n, wav, rec, total_frames, mfcc, words, uni_T, un, ub, dkv, ut);
+  else hipLaunchKernelGGL((k_mfcc_f32<0, true>), grid, blk, shm, s, fe, melw_n, wav, rec, total_frames, mfcc, words, uni_T, un, ub, dkv, ut);
   return true;
 }

@@ -56,10 +56,13 @@ __host__ __device__ inline MfccLds fb_mfcc_layout(int P, int L, int nb, int nc, 
   return o;
 }
 
+// DITHER: Kaldi's --dither -- every extracted sample (reflection included) becomes x + dither z before DC removal, z the
+// normal of (utterance, frame, sample-in-frame) under the dither RNG contract (include/fakebob_hip.h), drawn here
+template <bool DITHER>
 __global__ __launch_bounds__(256) void k_mfcc(FbFrontendDev fe, int melw_n, const int16_t *__restrict__ wav,
                                               const int64_t *__restrict__ wav_off,
                                               const int *__restrict__ frame_off, int B, int total_frames,
-                                              float *__restrict__ mfcc) {
+                                              float *__restrict__ mfcc, FbDitherKey dk) {
   if (fe.stop && *fe.stop) return;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -105,9 +108,14 @@ __global__ __launch_bounds__(256) void k_mfcc(FbFrontendDev fe, int melw_n, cons
         int64_t k = start + s;
         while (k < 0 || k >= n) { if (k < 0) k = -k - 1; else k = 2 * n - 1 - k; }
         v = (double)wv[k];
+        if constexpr (DITHER) {
+          float z0, z1;
+          fb_dither2(dk.k0, dk.k1, dk.epoch, dk.utt0 + (unsigned)b, (unsigned)t, (unsigned)(s >> 2), (s >> 1) & 1, z0, z1);
+          v += dk.amp * (double)((s & 1) ? z1 : z0);
+        }
       }
       xs[i] = v;
-      sum += v;  // integers: exact in any order
+      sum += v;  // undithered: integers, exact in any order
     }
     sum = fb_wave_sum(sum);
     const double mean = fe.remove_dc ? sum / (double)L : 0.0;
@@ -316,11 +324,15 @@ __device__ __forceinline__ void fb_dft16(double2 (&v)[16]) {
 // validity selects and mask multiplications are dropped at compile time (12 of 16 points for the recipe's L = 400:
 // ~ 12 % of a group's instructions; the kernel is bound by its float64 instruction count); 0 = no assumption.
 // RAW: which of the two frame energies is wanted (--raw-energy): the other one's 32 fmas are not issued.
-template <int NFULL, bool RAW>
+// DITHER: Kaldi's --dither, as in k_mfcc: the samples of a point become doubles x + dither z (a lane's point is half of a
+// Philox quad: the ten rounds and one Box-Muller transform per point), the DC sum a float64 row sum; dk and frame_ut (a
+// frame's {utterance, frame within it}) are not read otherwise.
+template <int NFULL, bool RAW, bool DITHER>
 __global__ __launch_bounds__(64 * FB_R16_WAVES, 1) void k_mfcc_r16(FbFrontendDev fe, int melw_n,
                                                                    const int16_t *__restrict__ wav,
                                                                    const int4 *__restrict__ frame_rec,
-                                                                   int total_frames, float *__restrict__ mfcc) {
+                                                                   int total_frames, float *__restrict__ mfcc,
+                                                                   FbDitherKey dk, const int2 *__restrict__ frame_ut) {
   if (fe.stop && *fe.stop) return;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   constexpr int NT = 64 * FB_R16_WAVES, Nc = 256;
@@ -342,9 +354,10 @@ __global__ __launch_bounds__(64 * FB_R16_WAVES, 1) void k_mfcc_r16(FbFrontendDev
   // samples of points p = 16 a + t of frame 4 g + fq: s0 = 32 a + 2 t and s0 + 1, packed into one register per point
   // (the pre-emphasis neighbour s0 - 1 is the previous lane's second sample).  The next group's samples are requested
   // before the current group is processed, so their L2 latency is off the critical path.
-  auto load_group = [&](int g, int tl, int (&xq)[16]) {
+  auto load_group = [&](int g, int tl, int (&xq)[16], int2 &ut) {
     const int fl = 4 * g + fq;
     const int4 rec = frame_rec[fl < total_frames ? fl : total_frames - 1];
+    if constexpr (DITHER) ut = frame_ut[fl < total_frames ? fl : total_frames - 1];
     const int64_t abs_start = ((int64_t)(unsigned)rec.x) | ((int64_t)rec.y << 32);
     const int start = rec.z, n = rec.w;
     const bool interior = start >= 0 && start + L <= n;
@@ -384,7 +397,8 @@ __global__ __launch_bounds__(64 * FB_R16_WAVES, 1) void k_mfcc_r16(FbFrontendDev
   // the first group's samples are requested BEFORE the tables are staged: their two dependent global round trips
   // (frame record, then samples) run in the shadow of the staging loads and the barrier
   int xn[16];
-  if (w_glob < n_groups) load_group(w_glob, t_lane, xn);
+  int2 utn = {0, 0};
+  if (w_glob < n_groups) load_group(w_glob, t_lane, xn, utn);
   for (int i = tid; i < Nc; i += NT) s_tw[i] = reinterpret_cast<const double2 *>(fe.tw_half)[i];
   for (int i = tid; i <= Nc; i += NT) s_twf[i] = reinterpret_cast<const double2 *>(fe.tw_full)[i];
   for (int i = tid; i < L; i += NT) s_win[i] = (float)fe.window[i];
@@ -404,32 +418,64 @@ __global__ __launch_bounds__(64 * FB_R16_WAVES, 1) void k_mfcc_r16(FbFrontendDev
     int xp[16];
 #pragma unroll
     for (int a = 0; a < 16; ++a) xp[a] = xn[a];
-    if (g + w_step < n_groups) load_group(g + w_step, t, xn);
-    int isum = 0;
+    const int2 utp = utn;
+    if (g + w_step < n_groups) load_group(g + w_step, t, xn, utn);
+    double2 xs[DITHER ? 16 : 1];  // DITHER: the dithered samples of point a (zero outside the frame)
+    double mean;
+    if constexpr (DITHER) {
+      const unsigned utt = dk.utt0 + (unsigned)utp.x;
+      double dsum = 0.0;
 #pragma unroll
-    for (int a = 0; a < 16; ++a) {
-      const int s0 = 32 * a + 2 * t;
-      isum += (a < NFULL || s0 < L ? (int)(short)xp[a] : 0) + (a < NFULL || s0 + 1 < L ? (xp[a] >> 16) : 0);
+      for (int a = 0; a < 16; ++a) {
+        const int s0 = 32 * a + 2 * t;
+        float z0, z1;  // samples s0, s0 + 1: half h = t & 1 of quad 8 a + t / 2
+        fb_dither2(dk.k0, dk.k1, dk.epoch, utt, (unsigned)utp.y, (unsigned)(8 * a + (t >> 1)), t & 1, z0, z1);
+        const double x0 = (double)(int)(short)xp[a] + dk.amp * (double)z0, x1 = (double)(xp[a] >> 16) + dk.amp * (double)z1;
+        xs[a] = make_double2(a < NFULL || s0 < L ? x0 : 0.0, a < NFULL || s0 + 1 < L ? x1 : 0.0);
+        dsum += xs[a].x;
+        dsum += xs[a].y;
+        if (a & 1) __builtin_amdgcn_sched_barrier(0);  // two points' transforms in flight: bounds the live registers
+      }
+      mean = fe.remove_dc ? fb_row_sum_f64(dsum) / (double)L : 0.0;
+    } else {
+      int isum = 0;
+#pragma unroll
+      for (int a = 0; a < 16; ++a) {
+        const int s0 = 32 * a + 2 * t;
+        isum += (a < NFULL || s0 < L ? (int)(short)xp[a] : 0) + (a < NFULL || s0 + 1 < L ? (xp[a] >> 16) : 0);
+      }
+      // DC: the samples are integers, |sum| < 2^24: exact in int32 in any order
+      mean = fe.remove_dc ? (double)fb_row_sum_i32(isum) / (double)L : 0.0;
     }
-    // DC: the samples are integers, |sum| < 2^24: exact in int32 in any order
-    const double mean = fe.remove_dc ? (double)fb_row_sum_i32(isum) / (double)L : 0.0;
     double en = 0.0, en2 = 0.0;
     double2 v[16];
-    int prev_rot = 0;  // row-rotated second samples of point a - 1
+    int prev_rot = 0;         // row-rotated second samples of point a - 1
+    double prev_rot_d = 0.0;  // (DITHER)
 #pragma unroll
     for (int a = 0; a < 16; ++a) {
       const int s0 = 32 * a + 2 * t;
-      const int xa0 = (int)(short)xp[a], xa1 = xp[a] >> 16;
-      const int rot = fb_dpp_i32<0x121, 0xf>(xa1);  // row_ror:1: lane t gets lane (t - 1) & 15
-      const int xprev = t == 0 ? (a == 0 ? xa0 : prev_rot) : rot;  // Kaldi: sample 0 is pre-emphasised with itself
-      prev_rot = rot;
       const bool inside = a < NFULL;  // compile time
       const float2 wq = *reinterpret_cast<const float2 *>(&s_win[inside ? s0 : min(s0, (L - 1) & ~1)]);  // L even: the pair exists
       const double w0 = inside || s0 < L ? (double)wq.x : 0.0, w1 = inside || s0 + 1 < L ? (double)wq.y : 0.0;
       const double m0 = inside || s0 < L ? 1.0 : 0.0, m1 = inside || s0 + 1 < L ? 1.0 : 0.0;
-      const double av = inside ? (double)xa0 - mean : ((double)xa0 - mean) * m0;
-      const double cv = inside ? (double)xa1 - mean : ((double)xa1 - mean) * m1;
-      const double pm = (double)xprev - mean;
+      double av, cv, pm;
+      if constexpr (DITHER) {
+        const double xa0 = xs[DITHER ? a : 0].x, xa1 = xs[DITHER ? a : 0].y;
+        const double rot = fb_dpp_f64<0x121, 0xf>(xa1);
+        const double xprev = t == 0 ? (a == 0 ? xa0 : prev_rot_d) : rot;
+        prev_rot_d = rot;
+        av = inside ? xa0 - mean : (xa0 - mean) * m0;
+        cv = inside ? xa1 - mean : (xa1 - mean) * m1;
+        pm = xprev - mean;
+      } else {
+        const int xa0 = (int)(short)xp[a], xa1 = xp[a] >> 16;
+        const int rot = fb_dpp_i32<0x121, 0xf>(xa1);  // row_ror:1: lane t gets lane (t - 1) & 15
+        const int xprev = t == 0 ? (a == 0 ? xa0 : prev_rot) : rot;  // Kaldi: sample 0 is pre-emphasised with itself
+        prev_rot = rot;
+        av = inside ? (double)xa0 - mean : ((double)xa0 - mean) * m0;
+        cv = inside ? (double)xa1 - mean : ((double)xa1 - mean) * m1;
+        pm = (double)xprev - mean;
+      }
       if constexpr (RAW) {
         en = fma(av, av, en);
         en = fma(cv, cv, en);
@@ -532,17 +578,22 @@ int fb_mfcc_layout_doubles(int P, int L, int nb, int nc, int melw_n) {
 
 int fb_launch_mfcc(hipStream_t s, const FbFrontendDev &fe, int melw_n, const int16_t *wav,
                    const int64_t *wav_off, const int *frame_off, const int32_t *frame_rec, int B,
-                   int total_frames, float *mfcc) {
+                   int total_frames, float *mfcc, const FbDitherKey *dk, const int32_t *frame_ut) {
   if (total_frames <= 0) return FB_ROUTE_NONE;
-  if (fe.P == 512 && fe.nb <= 31 && fe.nc <= 32 && (fe.L & 1) == 0 && fe.L >= 2) {
+  const bool dither = dk != nullptr && dk->amp > 0.0;
+  const FbDitherKey dkv = dither ? *dk : FbDitherKey{};
+  const int2 *ut = reinterpret_cast<const int2 *>(frame_ut);
+  if (fe.P == 512 && fe.nb <= 31 && fe.nc <= 32 && (fe.L & 1) == 0 && fe.L >= 2 && (!dither || ut != nullptr)) {
     const MfccR4Lds l16 = fb_mfcc_r4_layout(fe.L, fe.nb, fe.nc, melw_n);
     const size_t shm16 = sizeof(double) * (size_t)l16.wave0 + sizeof(double2) * (size_t)FB_R16_WAVES * 4 * FB_R16_SLOTS;
     static std::atomic<unsigned long long> optin16{0};
     unsigned long long bit16 = 0;
     bool ok16 = true;
     if (fb_device_needs_optin(optin16, &bit16)) {
-      const void *fns[] = {reinterpret_cast<const void *>(k_mfcc_r16<12, true>), reinterpret_cast<const void *>(k_mfcc_r16<12, false>),
-                           reinterpret_cast<const void *>(k_mfcc_r16<0, true>), reinterpret_cast<const void *>(k_mfcc_r16<0, false>)};
+      const void *fns[] = {reinterpret_cast<const void *>(k_mfcc_r16<12, true, false>), reinterpret_cast<const void *>(k_mfcc_r16<12, false, false>),
+                           reinterpret_cast<const void *>(k_mfcc_r16<0, true, false>), reinterpret_cast<const void *>(k_mfcc_r16<0, false, false>),
+                           reinterpret_cast<const void *>(k_mfcc_r16<12, true, true>), reinterpret_cast<const void *>(k_mfcc_r16<12, false, true>),
+                           reinterpret_cast<const void *>(k_mfcc_r16<0, true, true>), reinterpret_cast<const void *>(k_mfcc_r16<0, false, true>)};
       for (const void *fn : fns)
         ok16 = ok16 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
       if (ok16) optin16.fetch_or(bit16, std::memory_order_release);
@@ -554,21 +605,54 @@ int fb_launch_mfcc(hipStream_t s, const FbFrontendDev &fe, int melw_n, const int
       const dim3 grid(blocks), blk(64 * FB_R16_WAVES);
       const int4 *rec = reinterpret_cast<const int4 *>(frame_rec);
       const bool full12 = fe.L / 32 >= 12;
-      if (full12 && fe.raw_energy) hipLaunchKernelGGL((k_mfcc_r16<12, true>), grid, blk, shm16, s, fe, melw_n, wav, rec, total_frames, mfcc);
-      else if (full12) hipLaunchKernelGGL((k_mfcc_r16<12, false>), grid, blk, shm16, s, fe, melw_n, wav, rec, total_frames, mfcc);
-      else if (fe.raw_energy) hipLaunchKernelGGL((k_mfcc_r16<0, true>), grid, blk, shm16, s, fe, melw_n, wav, rec, total_frames, mfcc);
-      else hipLaunchKernelGGL((k_mfcc_r16<0, false>), grid, blk, shm16, s, fe, melw_n, wav, rec, total_frames, mfcc);
-      return full12 ? (fe.raw_energy ? FB_ROUTE_MFCC_R16_12_RAW : FB_ROUTE_MFCC_R16_12)
-                    : (fe.raw_energy ? FB_ROUTE_MFCC_R16_0_RAW : FB_ROUTE_MFCC_R16_0);
+#define FB_R16_LAUNCH(NF, RAW_, DI) hipLaunchKernelGGL((k_mfcc_r16<NF, RAW_, DI>), grid, blk, shm16, s, fe, melw_n, wav, rec, total_frames, mfcc, dkv, ut)
+      if (!dither) {
+        if (full12 && fe.raw_energy) FB_R16_LAUNCH(12, true, false);
+        else if (full12) FB_R16_LAUNCH(12, false, false);
+        else if (fe.raw_energy) FB_R16_LAUNCH(0, true, false);
+        else FB_R16_LAUNCH(0, false, false);
+        return full12 ? (fe.raw_energy ? FB_ROUTE_MFCC_R16_12_RAW : FB_ROUTE_MFCC_R16_12)
+                      : (fe.raw_energy ? FB_ROUTE_MFCC_R16_0_RAW : FB_ROUTE_MFCC_R16_0);
+      }
+      if (full12 && fe.raw_energy) FB_R16_LAUNCH(12, true, true);
+      else if (full12) FB_R16_LAUNCH(12, false, true);
+      else if (fe.raw_energy) FB_R16_LAUNCH(0, true, true);
+      else FB_R16_LAUNCH(0, false, true);
+#undef FB_R16_LAUNCH
+      return full12 ? (fe.raw_energy ? FB_ROUTE_MFCC_R16_12_RAW_DITHER : FB_ROUTE_MFCC_R16_12_DITHER)
+                    : (fe.raw_energy ? FB_ROUTE_MFCC_R16_0_RAW_DITHER : FB_ROUTE_MFCC_R16_0_DITHER);
     }
   }
   const MfccLds lo = fb_mfcc_layout(fe.P, fe.L, fe.nb, fe.nc, melw_n);
   size_t shm = sizeof(double) * (size_t)(lo.wave0 + 4 * lo.per_wave);
   int blocks = (total_frames + 3) / 4;
   if (blocks > 768) blocks = 768;
-  hipLaunchKernelGGL(k_mfcc, dim3(blocks), dim3(256), shm, s, fe, melw_n, wav, wav_off, frame_off, B,
-                     total_frames, mfcc);
+  if (dither) {
+    hipLaunchKernelGGL(k_mfcc<true>, dim3(blocks), dim3(256), shm, s, fe, melw_n, wav, wav_off, frame_off, B,
+                       total_frames, mfcc, dkv);
+    return FB_ROUTE_MFCC_GENERIC_DITHER;
+  }
+  hipLaunchKernelGGL(k_mfcc<false>, dim3(blocks), dim3(256), shm, s, fe, melw_n, wav, wav_off, frame_off, B,
+                     total_frames, mfcc, dkv);
   return FB_ROUTE_MFCC_GENERIC;
+}
+
+// the normals the dithered kernels add (fb_debug_dither_noise): one thread per Philox quad of a frame
+__global__ __launch_bounds__(256) void k_dither_noise(FbDitherKey dk, int t0, int n_frames, int L, float *__restrict__ z) {
+  const int nq = (L + 3) >> 2;
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long long)n_frames * nq) return;
+  const int f = (int)(i / nq), q = (int)(i - (long long)f * nq);
+  float z4[4];
+  fb_dither4(dk.k0, dk.k1, dk.epoch, dk.utt0, (unsigned)(t0 + f), (unsigned)q, z4);
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    if (4 * q + j < L) z[(size_t)f * L + 4 * q + j] = z4[j];
+}
+void fb_launch_dither_noise(hipStream_t s, const FbDitherKey &dk, int t0, int n_frames, int L, float *z) {
+  const long long n = (long long)n_frames * ((L + 3) >> 2);
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_dither_noise, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dk, t0, n_frames, L, z);
 }
 
 // -------------------------------------------------------------------- VAD

@@ -65,6 +65,11 @@ class Engine(object):
                 setattr(self.cfg, k, v)
             raise
 
+    def set_dither_seed(self, seed):
+        """The dither key of scoring calls outside an attack (fb_set_dither_seed); restarts their serial at 0, so the same
+        sequence of scoring calls after it draws the same noise."""
+        N.check(self._L.fb_set_dither_seed(self._h, C.c_uint64(int(seed))))
+
     @property
     def feat_dim(self):
         return self.cfg.num_ceps * (self.cfg.delta_order + 1)
@@ -185,7 +190,11 @@ class Engine(object):
 
     # fb_debug_frontend_route's codes (include/fakebob_hip_test.h: FB_ROUTE_*)
     _ROUTE_MFCC = {0: None, 1: "k_mfcc_f32<12>", 2: "k_mfcc_f32<0>", 3: "k_mfcc_r16<12,true>", 4: "k_mfcc_r16<12,false>",
-                   5: "k_mfcc_r16<0,true>", 6: "k_mfcc_r16<0,false>", 7: "k_mfcc"}
+                   5: "k_mfcc_r16<0,true>", 6: "k_mfcc_r16<0,false>", 7: "k_mfcc",
+                   # the dithered forms (cfg.dither > 0)
+                   8: "k_mfcc_f32<12,dither>", 9: "k_mfcc_f32<0,dither>", 10: "k_mfcc_r16<12,true,dither>",
+                   11: "k_mfcc_r16<12,false,dither>", 12: "k_mfcc_r16<0,true,dither>", 13: "k_mfcc_r16<0,false,dither>",
+                   14: "k_mfcc<dither>"}
     _ROUTE_CHAIN = {0: None, 1: "split", 2: "whole", 3: "vad+delta_cmvn", 4: "separate", 5: "separate+sliding"}
     _ROUTE_CM = {0: None, 1: "fused", 2: "registers", 3: "lds", 4: "global"}
 
@@ -467,6 +476,38 @@ class Engine(object):
         tv, To = C.c_int(), C.c_int()
         N.check(self._L.fb_debug_feats(self._h, N.ptr(wav), C.c_int64(wav.size), N.ptr(out), C.byref(tv),
                                        C.byref(To)))
+        return out[:tv.value].copy(), To.value
+
+    def debug_dither_noise(self, seed, stream, epoch, utt, t0, n_frames, L=None):
+        """The normals (n_frames, L) the dithered MFCC kernels add to frames t0 .. of utterance `utt` at (seed, stream,
+        epoch) -- fb_debug_dither_noise."""
+        L = self.cfg.frame_length if L is None else int(L)
+        z = np.empty((int(n_frames), L), np.float32)
+        N.check(self._L.fb_debug_dither_noise(self._h, C.c_uint64(int(seed)), C.c_uint32(int(stream)), C.c_uint32(int(epoch)),
+                                              C.c_uint32(int(utt)), C.c_int(int(t0)), C.c_int(int(n_frames)), C.c_int(L),
+                                              N.ptr(z)))
+        return z
+
+    def debug_mfcc_dither(self, wav, seed, stream, epoch, utt):
+        """debug_mfcc of one utterance at that point of the dither contract (fb_debug_mfcc_dither)."""
+        wav = np.ascontiguousarray(wav, np.int16)
+        T = self._num_frames(wav.size)
+        out = np.empty((T, self.cfg.num_ceps), np.float32)
+        To = C.c_int()
+        N.check(self._L.fb_debug_mfcc_dither(self._h, N.ptr(wav), C.c_int64(wav.size), C.c_uint64(int(seed)),
+                                             C.c_uint32(int(stream)), C.c_uint32(int(epoch)), C.c_uint32(int(utt)),
+                                             N.ptr(out), C.byref(To)))
+        return out[:To.value]
+
+    def debug_feats_dither(self, wav, seed, stream, epoch, utt):
+        """debug_feats of one utterance at that point of the dither contract (fb_debug_feats_dither)."""
+        wav = np.ascontiguousarray(wav, np.int16)
+        T = self._num_frames(wav.size)
+        out = np.empty((max(T, 1), self.feat_dim), np.float32)
+        tv, To = C.c_int(), C.c_int()
+        N.check(self._L.fb_debug_feats_dither(self._h, N.ptr(wav), C.c_int64(wav.size), C.c_uint64(int(seed)),
+                                              C.c_uint32(int(stream)), C.c_uint32(int(epoch)), C.c_uint32(int(utt)),
+                                              N.ptr(out), C.byref(tv), C.byref(To)))
         return out[:tv.value].copy(), To.value
 
     def debug_gmm_frames(self, feats):

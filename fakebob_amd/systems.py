@@ -20,6 +20,8 @@ from .kaldi_io import load_gmm_any
 #   text_scores     the 6-significant-digit score text the helpers parse (gmm_ubm_kaldiHelper.py:236-248)
 #   mfcc_f32        compute-mfcc-feats in Kaldi's own BaseFloat = float32 arithmetic (k_mfcc_f32)
 #                   instead of float64 between Kaldi's float32 storage points
+# Kaldi's dither (fb_frontend_cfg.dither) is no pipeline flag: it is a number, off (0) in every class default, and asked
+# for with the constructors' `dither` keyword or FB_DITHER (_dither_option).
 # Every system class carries its own default in `PIPELINE` -- None for the library classes below (full precision: the
 # engine's flags are left as the caller set them), REFERENCE_PIPELINE for the subclasses the drop-in modules export
 # under the reference's names (fakebob_amd/dropin/).  Nothing process-global is switched by an import.
@@ -78,6 +80,27 @@ def _apply_frontend(engine, conf_over, text_scores, compress_feats, mfcc_f32, de
             warnings.warn("pipeline flags %s stay on from an earlier system on this engine" % inherited)
 
 
+def _dither_option(dither):
+    """Kaldi's dither for a system under construction: the constructor keyword, then FB_DITHER -- a number, or "conf" for
+    what pre_model_dir/conf/mfcc.conf configures (Kaldi's 1.0 when the file is silent).  None: not asked for -- the engine
+    keeps its setting (0 unless the caller changed it) and the conf reader warns as before."""
+    if dither is None:
+        dither = os.environ.get("FB_DITHER")
+        if dither is None or dither == "":
+            return None
+    return "conf" if dither == "conf" else float(dither)
+
+
+def _conf_overrides(pre_model_dir, dither=None):
+    """Front-end overrides of pre_model_dir/conf (none without that directory, or for pre_model_dir None) plus the dither
+    option (_dither_option)."""
+    from .config import frontend_from_kaldi_conf, frontend_overrides
+    d = _dither_option(dither)
+    if pre_model_dir is not None and os.path.isdir(os.path.join(pre_model_dir, "conf")):
+        return frontend_from_kaldi_conf(pre_model_dir, dither=d)
+    return {} if d is None else frontend_overrides(dither=d)
+
+
 def reference_pipeline(cls, module=None):
     """The subclass of a system class that behaves like the reference's pipeline by default (both round trips on):
     what fakebob_amd/dropin/<reference module name>.py exports under the reference's class name.  `module`: the
@@ -108,7 +131,7 @@ class _GmmSystem(object):
     PIPELINE = None  # class default of the two round trips (see REFERENCE_PIPELINE)
 
     def _setup(self, group_id, models, spk_ids, utt_ids, locations, z_means, z_stds, pre_model_dir, engine,
-               text_scores=None, compress_feats=None, mfcc_f32=None):
+               text_scores=None, compress_feats=None, mfcc_f32=None, dither=None):
         self.pre_model_dir = os.path.abspath(pre_model_dir)
         self.group_id = os.path.abspath(group_id)
         self.spk_ids = spk_ids
@@ -116,11 +139,7 @@ class _GmmSystem(object):
         self.identity_locations = locations
         self.n_speakers = len(spk_ids)
         self._engine = engine if engine is not None else Engine(default_device())
-        conf = os.path.join(self.pre_model_dir, "conf")
-        over = {}
-        if os.path.isdir(conf):
-            from .config import frontend_from_kaldi_conf
-            over = frontend_from_kaldi_conf(self.pre_model_dir)
+        over = _conf_overrides(self.pre_model_dir, dither)
         _apply_frontend(self._engine, over, text_scores, compress_feats, mfcc_f32, self.PIPELINE)
         self._engine.load_gmm(models)
         self._engine.set_system(self.task, z_means, z_stds)
@@ -146,13 +165,13 @@ class gmm_OSI(_GmmSystem):
     task = "OSI"
 
     def __init__(self, group_id, model_list, ubm, pre_model_dir="pre-models", threshold=0.0, engine=None,
-                 text_scores=None, compress_feats=None, mfcc_f32=None):
+                 text_scores=None, compress_feats=None, mfcc_f32=None, dither=None):
         self.threshold = threshold
         locs = [m[2] for m in model_list]
         self.model_list = [ubm] + locs  # UBM first (gmm_ubm_OSI.py:45)
         models = [load_gmm_any(x) for x in self.model_list]
         self._setup(group_id, models, [m[0] for m in model_list], [m[1] for m in model_list], locs, None, None,
-                    pre_model_dir, engine, text_scores, compress_feats, mfcc_f32)
+                    pre_model_dir, engine, text_scores, compress_feats, mfcc_f32, dither)
 
     def score(self, audios, fs=16000, bits_per_sample=16, debug=False, n_jobs=5):
         raw = self._raw(audios, bits_per_sample)
@@ -178,14 +197,14 @@ class gmm_CSI(_GmmSystem):
     task = "CSI"
 
     def __init__(self, group_id, model_list, pre_model_dir="pre-models", engine=None, text_scores=None,
-                 compress_feats=None, mfcc_f32=None):
+                 compress_feats=None, mfcc_f32=None, dither=None):
         locs = [m[2] for m in model_list]
         self.model_list = locs
         self.z_norm_means = np.array([m[3] for m in model_list], np.float64)
         self.z_norm_stds = np.array([m[4] for m in model_list], np.float64)
         models = [load_gmm_any(x) for x in locs]
         self._setup(group_id, models, [m[0] for m in model_list], [m[1] for m in model_list], locs,
-                    self.z_norm_means, self.z_norm_stds, pre_model_dir, engine, text_scores, compress_feats, mfcc_f32)
+                    self.z_norm_means, self.z_norm_stds, pre_model_dir, engine, text_scores, compress_feats, mfcc_f32, dither)
 
     def score(self, audios, fs=16000, bits_per_sample=16, debug=False, n_jobs=5):
         raw = self._raw(audios, bits_per_sample)
@@ -207,14 +226,14 @@ class gmm_SV(_GmmSystem):
     task = "SV"
 
     def __init__(self, spk_id, model, ubm, pre_model_dir="pre-models", threshold=0.0, engine=None,
-                 text_scores=None, compress_feats=None, mfcc_f32=None):
+                 text_scores=None, compress_feats=None, mfcc_f32=None, dither=None):
         self.threshold = threshold
         self.utt_id = model[1]
         self.identity_location = model[2]
         self.model_list = [ubm, self.identity_location]
         models = [load_gmm_any(x) for x in self.model_list]
         self._setup(spk_id, models, [model[0]], [model[1]], [model[2]], None, None, pre_model_dir, engine,
-                    text_scores, compress_feats, mfcc_f32)
+                    text_scores, compress_feats, mfcc_f32, dither)
         self.spk_id = self.group_id
 
     def score(self, audios, fs=16000, bits_per_sample=16, debug=False, n_jobs=5):
@@ -236,7 +255,7 @@ class _IvSystem(object):
     task = None
     PIPELINE = None
 
-    def _setup(self, group_id, model_list, pre_model_dir, engine, system, text_scores=None, compress_feats=None, mfcc_f32=None):
+    def _setup(self, group_id, model_list, pre_model_dir, engine, system, text_scores=None, compress_feats=None, mfcc_f32=None, dither=None):
         from .models import IvectorSystem
         self.pre_model_dir = os.path.abspath(pre_model_dir)
         self.group_id = os.path.abspath(group_id)
@@ -262,16 +281,12 @@ class _IvSystem(object):
         from .kaldi_io import load_ivector_pre_models, read_ivector_location
         enrolled = np.stack([read_ivector_location(x) for x in locs])
         if system is None:
-            conf = os.path.join(self.pre_model_dir, "conf")
-            over = {}
-            if os.path.isdir(conf):
-                from .config import frontend_from_kaldi_conf
-                over = frontend_from_kaldi_conf(self.pre_model_dir)
+            over = _conf_overrides(self.pre_model_dir, dither)
             _apply_frontend(self._engine, over, text_scores, compress_feats, mfcc_f32, self.PIPELINE)
             d = load_ivector_pre_models(self.pre_model_dir)
             system = IvectorSystem(enrolled=enrolled, z_mean=zm, z_std=zs, **d)
         else:
-            _apply_frontend(self._engine, {}, text_scores, compress_feats, mfcc_f32, self.PIPELINE)
+            _apply_frontend(self._engine, _conf_overrides(None, dither), text_scores, compress_feats, mfcc_f32, self.PIPELINE)
             system = system.with_enrolled(enrolled, zm, zs)
         self._engine.load_ivector(system, self.task)
 
@@ -295,9 +310,9 @@ class iv_OSI(_IvSystem):
     task = "OSI"
 
     def __init__(self, group_id, model_list, pre_model_dir="pre-models", threshold=0.0, engine=None, system=None,
-                 text_scores=None, compress_feats=None, mfcc_f32=None):
+                 text_scores=None, compress_feats=None, mfcc_f32=None, dither=None):
         self.threshold = threshold
-        self._setup(group_id, model_list, pre_model_dir, engine, system, text_scores, compress_feats, mfcc_f32)
+        self._setup(group_id, model_list, pre_model_dir, engine, system, text_scores, compress_feats, mfcc_f32, dither)
 
     def score(self, audio_list, fs=16000, bits_per_sample=16, n_jobs=10, debug=False):
         s = (self._llr(audio_list, bits_per_sample) - self.z_norm_means) / self.z_norm_stds   # :119
@@ -325,8 +340,8 @@ class iv_CSI(_IvSystem):
     task = "CSI"
 
     def __init__(self, group_id, model_list, pre_model_dir="pre-models", engine=None, system=None, text_scores=None,
-                 compress_feats=None, mfcc_f32=None):
-        self._setup(group_id, model_list, pre_model_dir, engine, system, text_scores, compress_feats, mfcc_f32)
+                 compress_feats=None, mfcc_f32=None, dither=None):
+        self._setup(group_id, model_list, pre_model_dir, engine, system, text_scores, compress_feats, mfcc_f32, dither)
 
     def score(self, audio_list, fs=16000, bits_per_sample=16, n_jobs=10, debug=False):
         s = (self._llr(audio_list, bits_per_sample) - self.z_norm_means) / self.z_norm_stds
@@ -349,9 +364,9 @@ class iv_SV(_IvSystem):
     task = "SV"
 
     def __init__(self, spk_id, model, pre_model_dir="pre-models", threshold=0.0, engine=None, system=None,
-                 text_scores=None, compress_feats=None, mfcc_f32=None):
+                 text_scores=None, compress_feats=None, mfcc_f32=None, dither=None):
         self.threshold = threshold
-        self._setup(spk_id, [model], pre_model_dir, engine, system, text_scores, compress_feats, mfcc_f32)
+        self._setup(spk_id, [model], pre_model_dir, engine, system, text_scores, compress_feats, mfcc_f32, dither)
         self.spk_id = self.group_id
         self.utt_id = model[1]
         self.identity_location = model[2]

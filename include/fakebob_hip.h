@@ -57,7 +57,7 @@ enum { FB_UNTARGETED = 0, FB_TARGETED = 1 };
 typedef struct fb_engine fb_engine;
 
 /* Kaldi front-end options ([EXT] conf/mfcc.conf, conf/vad.conf, delta_opts;
- * cmn flags fixed by gmm_ubm_kaldiHelper.py:196).  dither is always 0. */
+ * cmn flags fixed by gmm_ubm_kaldiHelper.py:196).  dither (the last field) defaults to 0. */
 typedef struct {
   double sample_freq;
   int frame_length;   /* samples */
@@ -96,6 +96,13 @@ typedef struct {
    * log-energy C0 -- what compute-vad-decision votes on -- from the exact integer energy.  Needs the recipe's shape
    * (padded_length 512, raw_energy, <= 31 mel bins); fb_set_frontend refuses it otherwise. */
   int mfcc_f32;
+  /* Kaldi's --dither (compute-mfcc-feats; Kaldi's own default is 1.0 and the stock conf/mfcc.conf does not set it).
+   * 0 (default): no noise, the front end is a pure function of the samples.  > 0: after a frame of frame_length samples
+   * is extracted (reflection at the utterance edges included) and before DC removal, raw energy, pre-emphasis and the
+   * window, sample i of frame t of utterance u becomes x[i] + dither * z(u, t, i), z standard normal, drawn per (utterance,
+   * frame, sample-in-frame) -- a waveform sample gets independent noise in each of its overlapping frames, as in Kaldi -- by
+   * the "Dither RNG contract" below.  Negative or non-finite: FB_E_ARG. */
+  double dither;
 } fb_frontend_cfg;
 
 /* FakeBob hyper-parameters (FAKEBOB.py:21-37) + attack() arguments (:139) +
@@ -122,6 +129,22 @@ typedef struct {
                           2 .. 16; 0 means 16 */
 } fb_nes_params;
 
+/* ---- Dither RNG contract (fb_frontend_cfg.dither > 0) ------------------------------------------------------------------
+ * The normals come from the generator of the NES contract -- Philox4x32-10 and the float32 Box-Muller built from exactly
+ * rounded primitives -- on a key of their own, so the two streams never meet:
+ *   key     = (seed_lo ^ 0x44495448 ("DITH"), seed_hi ^ stream)
+ *   counter = (i >> 2, frame index within the utterance, utterance index within the call, epoch)
+ * and the four output words give z(u, t, 4 (i >> 2) .. + 3): words 0, 1 the first Box-Muller pair, words 2, 3 the second.
+ *  - fb_get_grad / fb_attack / fb_estimate_threshold: seed and stream are fb_nes_params'; the utterance index is the row of
+ *    the NES batch (0 = the unperturbed audio); epoch is the NES iteration (fb_get_grad's `iter`, fb_attack's loop index)
+ *    or, in fb_estimate_threshold, the call's running count of front-end launches.
+ *  - fb_score_*, fb_gmm_acc_stats and the fb_debug_mfcc / fb_debug_feats hooks: seed is the engine's dither seed
+ *    (fb_set_dither_seed; 0 at creation), stream is 0xFFFFFFFF, epoch is the engine's scoring-call serial: 0 for the first
+ *    such call after fb_set_dither_seed, one more for every later one.
+ * So an attack's result depends on (seed, stream) only -- not on the engine that ran it, on the launch chain or on how
+ * many iterations the host queues ahead --, and an utterance's noise does not depend on what else is in its batch. */
+int fb_set_dither_seed(fb_engine *e, uint64_t seed);
+
 const char *fb_last_error(void);
 int fb_version(void);
 int fb_device_count(void);
@@ -131,7 +154,7 @@ int fb_engine_destroy(fb_engine *e);
 
 void fb_default_frontend(fb_frontend_cfg *cfg);
 /* FB_E_ARG, the previous configuration kept, for options that describe no front end: besides the shapes the kernels do
- * not take, cmn_window < 1, vad_frames_context < 0 and a mel bin that covers no FFT bin. */
+ * not take, cmn_window < 1, vad_frames_context < 0, a mel bin that covers no FFT bin and a negative or non-finite dither. */
 int fb_set_frontend(fb_engine *e, const fb_frontend_cfg *cfg);
 
 /* Diagonal GMMs in Kaldi DiagGmm internal form (float32): gconsts[M*C],

@@ -25,6 +25,20 @@ int fb_debug_mfcc(fb_engine *e, const int16_t *wav, int64_t n, float *mfcc, int 
 int fb_debug_feats(fb_engine *e, const int16_t *wav, int64_t n, float *feats,
                    int *Tv, int *T);
 
+/* Kaldi's dither (fakebob_hip.h, "Dither RNG contract").
+ * fb_debug_dither_noise: the normals z[n_frames * L] the dithered MFCC kernels add to samples 0 .. L - 1 of frames t0 .. t0 + n_frames
+ * - 1 of utterance `utt` at (seed, stream, epoch), produced by the device function the kernels call.
+ * fb_debug_mfcc_dither / fb_debug_feats_dither: fb_debug_mfcc / fb_debug_feats of one utterance at that point of the contract
+ * (it is utterance `utt` of a call with that seed, stream and epoch), on whatever route the current front-end selects; the
+ * engine's own dither seed and scoring-call serial are neither used nor advanced.  With dither 0 they equal fb_debug_mfcc /
+ * fb_debug_feats bit for bit. */
+int fb_debug_dither_noise(fb_engine *e, uint64_t seed, uint32_t stream, uint32_t epoch, uint32_t utt, int t0, int n_frames,
+                          int L, float *z);
+int fb_debug_mfcc_dither(fb_engine *e, const int16_t *wav, int64_t n, uint64_t seed, uint32_t stream, uint32_t epoch,
+                         uint32_t utt, float *mfcc, int *T);
+int fb_debug_feats_dither(fb_engine *e, const int16_t *wav, int64_t n, uint64_t seed, uint32_t stream, uint32_t epoch,
+                          uint32_t utt, float *feats, int *Tv, int *T);
+
 /* What the front end of the last batch ran (fb_score_*, fb_get_grad, an NES iteration, fb_debug_mfcc / _feats, enrolment
  * statistics): info[5] = {the MFCC kernel, the chain after it, where the CompressedMatrix round trip ran, the longest
  * utterance of the batch in frames, the batch size}.  Recorded on the host when the kernels are enqueued; read only.
@@ -39,7 +53,15 @@ int fb_debug_frontend_route(fb_engine *e, int *info);
 #define FB_ROUTE_MFCC_R16_12 4       /* k_mfcc_r16<12, false> */
 #define FB_ROUTE_MFCC_R16_0_RAW 5    /* k_mfcc_r16<0, true> */
 #define FB_ROUTE_MFCC_R16_0 6        /* k_mfcc_r16<0, false> */
-#define FB_ROUTE_MFCC_GENERIC 7      /* k_mfcc */
+#define FB_ROUTE_MFCC_GENERIC 7      /* k_mfcc<false> */
+/* ... the dithered forms (fb_frontend_cfg.dither > 0) */
+#define FB_ROUTE_MFCC_F32_12_DITHER 8      /* k_mfcc_f32<12, true> */
+#define FB_ROUTE_MFCC_F32_0_DITHER 9       /* k_mfcc_f32<0, true> */
+#define FB_ROUTE_MFCC_R16_12_RAW_DITHER 10 /* k_mfcc_r16<12, true, true> */
+#define FB_ROUTE_MFCC_R16_12_DITHER 11     /* k_mfcc_r16<12, false, true> */
+#define FB_ROUTE_MFCC_R16_0_RAW_DITHER 12  /* k_mfcc_r16<0, true, true> */
+#define FB_ROUTE_MFCC_R16_0_DITHER 13      /* k_mfcc_r16<0, false, true> */
+#define FB_ROUTE_MFCC_GENERIC_DITHER 14    /* k_mfcc<true> */
 /* info[1] */
 #define FB_ROUTE_CHAIN_SPLIT 1       /* k_vad_delta_cmvn_p: an utterance over four workgroups */
 #define FB_ROUTE_CHAIN_WHOLE 2       /* k_vad_delta_cmvn: one workgroup per utterance */
