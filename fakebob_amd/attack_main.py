@@ -39,21 +39,28 @@ def load_spk_models(model_dir, spk_id_list, architecture):
     return out
 
 
-def make_model(architecture, task, model_list, pre_model_dir, threshold, group_id, dither=None):
-    """attackMain.load_model (:38-85).  dither: the systems' keyword (Kaldi's --dither: a number, or "conf")."""
+def make_model(architecture, task, model_list, pre_model_dir, threshold, group_id, dither=None, input_transform=None):
+    """attackMain.load_model (:38-85).  dither: the systems' keyword (Kaldi's --dither: a number, or "conf");
+    input_transform: theirs too (the defended victim's input-transform chain, a spec such as "ms:7")."""
     from .systems import gmm_CSI, gmm_OSI, gmm_SV, iv_CSI, iv_OSI, iv_SV
     ubm = os.path.join(pre_model_dir, "final.dubm")
     if architecture == "iv":
         if task == "OSI":
-            return iv_OSI(group_id, model_list, pre_model_dir=pre_model_dir, threshold=threshold, dither=dither)
+            return iv_OSI(group_id, model_list, pre_model_dir=pre_model_dir, threshold=threshold, dither=dither,
+                          input_transform=input_transform)
         if task == "CSI":
-            return iv_CSI(group_id, model_list, pre_model_dir=pre_model_dir, dither=dither)
-        return iv_SV(group_id, model_list[0], pre_model_dir=pre_model_dir, threshold=threshold, dither=dither)
+            return iv_CSI(group_id, model_list, pre_model_dir=pre_model_dir, dither=dither,
+                          input_transform=input_transform)
+        return iv_SV(group_id, model_list[0], pre_model_dir=pre_model_dir, threshold=threshold, dither=dither,
+                          input_transform=input_transform)
     if task == "OSI":
-        return gmm_OSI(group_id, model_list, ubm, pre_model_dir=pre_model_dir, threshold=threshold, dither=dither)
+        return gmm_OSI(group_id, model_list, ubm, pre_model_dir=pre_model_dir, threshold=threshold, dither=dither,
+                          input_transform=input_transform)
     if task == "CSI":
-        return gmm_CSI(group_id, model_list, pre_model_dir=pre_model_dir, dither=dither)
-    return gmm_SV(group_id, model_list[0], ubm, pre_model_dir=pre_model_dir, threshold=threshold, dither=dither)
+        return gmm_CSI(group_id, model_list, pre_model_dir=pre_model_dir, dither=dither,
+                          input_transform=input_transform)
+    return gmm_SV(group_id, model_list[0], ubm, pre_model_dir=pre_model_dir, threshold=threshold, dither=dither,
+                          input_transform=input_transform)
 
 
 def collect_voices(data_dir):
@@ -134,6 +141,10 @@ def main(argv=None, model_factory=None, bob_factory=None):
                          "configures (Kaldi's 1.0 when it is silent); default: off, or FB_DITHER")
     ap.add_argument("--dither-seed", dest="dither_seed", default=0, type=int,
                     help="dither key of the scoring calls outside an attack (inside one, --seed and the attack's stream key it)")
+    ap.add_argument("--input-transform", dest="input_transform", default=None,
+                    help="attack a defended victim: the input-transform chain in front of its recogniser, e.g. 'ms:7', "
+                         "'qt:512', 'ds:2', 'lpf:4000' or several joined by commas (fakebob_amd/input_transform.py); "
+                         "default: none, or FB_INPUT_TRANSFORM")
     ap.add_argument("--model_dir", default="./model")
     ap.add_argument("--pre_model_dir", default="pre-models")
     ap.add_argument("--test_dir", default="./data/test-set")
@@ -156,7 +167,8 @@ def main(argv=None, model_factory=None, bob_factory=None):
     K = max(1, args.streams)
     if model_factory is None:
         model_list = load_spk_models(args.model_dir, spk_id_list, args.architecture)
-        model_factory = make_model if args.dither is None else functools.partial(make_model, dither=args.dither)
+        kw = {k: v for k, v in (("dither", args.dither), ("input_transform", args.input_transform)) if v is not None}
+        model_factory = functools.partial(make_model, **kw) if kw else make_model
     else:
         model_list = spk_id_list
     models = [model_factory(args.architecture, task, model_list, args.pre_model_dir, args.threshold,

@@ -90,6 +90,10 @@ struct fb_engine {
   FbDitherKey dkey = {};        // what the next front-end launch carries: set by every path in front of launch_mfcc
   DevBuf frame_ut;              // [total_frames][2] {utterance, frame within it} of the batch (prepare_batch, dither > 0)
   std::vector<int32_t> h_frame_ut;
+  // input-transform chain (fb_set_input_transform): tf.n == 0 -- none, launch_mfcc reads `wav` itself
+  FbTfChain tf = {};
+  DevBuf tf_taps;               // the FIR stages' taps, one after the other
+  DevBuf wav_tf;                // the transformed batch, in wav's layout: what the MFCC reads when a chain is set
   // gmm
   bool have_gmm = false;
   FbGmmDev gmm;
@@ -254,7 +258,7 @@ extern "C" int fb_engine_destroy(fb_engine *e) {
   if (!e) return FB_OK;
   (void)hipSetDevice(e->device);
   if (e->stream) (void)hipStreamSynchronize(e->stream);
-  DevBuf *bufs[] = {&e->fe_tables, &e->fe_tables32, &e->frame_ut, &e->gmm_items, &e->gmm_images_bx, &e->gmm_images_fx, &e->gmm_images_fd, &e->gmm_images_fd2, &e->gmm_images_fd3, &e->gmm_anchor, &e->zmean, &e->zstd, &e->wav, &e->wav_off,
+  DevBuf *bufs[] = {&e->fe_tables, &e->fe_tables32, &e->frame_ut, &e->tf_taps, &e->wav_tf, &e->gmm_items, &e->gmm_images_bx, &e->gmm_images_fx, &e->gmm_images_fd, &e->gmm_images_fd2, &e->gmm_images_fd3, &e->gmm_anchor, &e->zmean, &e->zstd, &e->wav, &e->wav_off,
                     &e->frame_rec, &e->vad_counter, &e->vad_pub, &e->vad_part, &e->fin_counter, &e->fin_xch, &e->ctl, &e->ctl_ls, &e->trace_dev, &e->ticks, &e->enr_ll, &e->enr_aux, &e->enr_stats, &e->frame_off, &e->chunk_off, &e->chunk_sum, &e->mfcc, &e->mfcc_cm, &e->vrank, &e->tv, &e->row_off, &e->dfeat, &e->feats,
                     &e->part_m, &e->part_s, &e->raw, &e->audio, &e->adver, &e->grad_m, &e->grad, &e->noise, &e->zbuf,
                     &e->scores, &e->loss, &e->dist_part, &e->nes_out, &e->stage_f64, &e->ext_x, &e->ext_z, &e->iv_fg, &e->iv_fg64, &e->iv_fgL, &e->iv_tri,
@@ -1233,10 +1237,27 @@ static void choose_launch_shape(fb_engine *e) {
   e->shape_mfcc = FbMfccShape{};
   e->have_shape = true;
 }
+// The batch the MFCC reads: e->wav, or -- with an input-transform chain set -- its transform in e->wav_tf, one more launch.
+// off: the batch's offsets on the host (off[0] = 0), already in e->wav_off on the device.
+static int transformed_wav(fb_engine *e, const int64_t *off, int B, const int16_t **wav) {
+  *wav = e->wav.as<int16_t>();
+  if (e->tf.n == 0) return FB_OK;
+  if (B > 65535) return fb_fail(FB_E_LIMIT, "an input-transform chain takes batches of up to 65535 utterances");
+  int64_t n_max = 0;
+  for (int b = 0; b < B; ++b) n_max = std::max(n_max, off[b + 1] - off[b]);
+  if (n_max > 0x7fffffffLL) return fb_fail(FB_E_LIMIT, "utterance longer than 2^31 samples");
+  FBCHK(e->wav_tf.ensure(sizeof(int16_t) * (size_t)off[B]));
+  fb_launch_input_transform(e->stream, e->tf, e->tf_taps.as<double>(), e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), B, n_max,
+                            e->wav_tf.as<int16_t>(), e->fe.stop);
+  *wav = e->wav_tf.as<int16_t>();
+  return FB_OK;
+}
 // MFCC of every frame of the batch prepared in e->wav: k_mfcc_f32 when the configuration asks for it, else k_mfcc_r16 / k_mfcc
-static void launch_mfcc(fb_engine *e, int B, int total_frames) {
+static int launch_mfcc(fb_engine *e, int B, int total_frames) {
   const FbFrontendDev &fe = e->fe;
   hipStream_t s = e->stream;
+  const int16_t *wav = nullptr;
+  FBCHK(transformed_wav(e, e->h_wav_off.data(), B, &wav));
   e->have_route = true;
   e->route[3] = e->t_max;
   e->route[4] = B;
@@ -1246,13 +1267,14 @@ static void launch_mfcc(fb_engine *e, int B, int total_frames) {
   e->dkey.amp = e->cfg.dither;
   const FbDitherKey *dk = dither ? &e->dkey : nullptr;
   const int32_t *ut = dither ? e->frame_ut.as<int32_t>() : nullptr;
-  if (fe.mfcc_f32 && fb_launch_mfcc_f32(s, fe, e->melw_n, e->wav.as<int16_t>(), e->frame_rec.as<int32_t>(), total_frames,
+  if (fe.mfcc_f32 && fb_launch_mfcc_f32(s, fe, e->melw_n, wav, e->frame_rec.as<int32_t>(), total_frames,
                                         e->mfcc.as<float>(), e->uni_T, e->uni_n, e->h_wav_off[0], &e->shape_mfcc, dk, ut))
     e->route[0] = fe.L / 32 >= 12 ? (dither ? FB_ROUTE_MFCC_F32_12_DITHER : FB_ROUTE_MFCC_F32_12)
                                   : (dither ? FB_ROUTE_MFCC_F32_0_DITHER : FB_ROUTE_MFCC_F32_0);  // (fb_launch_mfcc_f32's instantiation rule)
   else
-    e->route[0] = fb_launch_mfcc(s, fe, e->melw_n, e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), e->frame_off.as<int>(),
+    e->route[0] = fb_launch_mfcc(s, fe, e->melw_n, wav, e->wav_off.as<int64_t>(), e->frame_off.as<int>(),
                                  e->frame_rec.as<int32_t>(), B, total_frames, e->mfcc.as<float>(), dk, ut);
+  return FB_OK;
 }
 // the dither key of a scoring call outside an attack (fb_score_*, fb_gmm_acc_stats, fb_debug_mfcc / _feats): the engine's
 // seed, stream 0xFFFFFFFF, epoch = the scoring-call serial, which the call consumes
@@ -1355,7 +1377,7 @@ static int run_scoring(fb_engine *e, int B, int total_frames) {
   FBCHK(e->raw.ensure(sizeof(double) * (size_t)B * e->n_out));
   hipStream_t s = e->stream;
   choose_launch_shape(e);
-  launch_mfcc(e, B, total_frames);
+  FBCHK(launch_mfcc(e, B, total_frames));
   FBCHK(run_post_mfcc(e, B));
   if (e->kind == 0) {
     // A GPU shared by three or more attacks (fb_set_fused_chain(e, 0)): k_gmm_fx2w takes a whole compute unit per workgroup (one
@@ -2785,7 +2807,7 @@ static int debug_frontend(fb_engine *e, const int16_t *wav, int64_t n, const FbD
   choose_launch_shape(e);
   if (key) e->dkey = *key;
   else dither_key_scoring_call(e);
-  launch_mfcc(e, 1, T);
+  FBCHK(launch_mfcc(e, 1, T));
   FBCHK(run_post_mfcc(e, 1));
   HIPCHK(hipGetLastError());
   return FB_OK;
@@ -2891,6 +2913,86 @@ extern "C" int fb_debug_dither_noise(fb_engine *e, uint64_t seed, uint32_t strea
   if (er == hipSuccess) er = hipStreamSynchronize(e->stream);
   tmp.release();
   if (er != hipSuccess) return fb_fail(FB_E_HIP, "dither noise dump failed: %s", hipGetErrorString(er));
+  return FB_OK;
+}
+
+// ---- input-transform chain (the stage contract: include/fakebob_hip.h)
+extern "C" int fb_set_input_transform(fb_engine *e, const fb_tf_stage *stages, int n) {
+  if (!e) return fb_fail(FB_E_ARG, "null engine");
+  if (n < 0 || n > FB_TF_MAX_STAGES) return fb_fail(FB_E_ARG, "%d stages: an input-transform chain has 0 .. %d", n, FB_TF_MAX_STAGES);
+  if (n > 0 && !stages) return fb_fail(FB_E_ARG, "stages is NULL");
+  // everything is checked before anything is changed: a refusal keeps the previous chain
+  FbTfChain ch = {};
+  std::vector<double> taps;
+  for (int s = 0; s < n; ++s) {
+    const int kind = stages[s].kind, k = stages[s].k;
+    int radius = 0;
+    if (kind == FB_TF_QUANT) {
+      if (k < 1 || k > 16384) return fb_fail(FB_E_ARG, "stage %d: quantisation step %d outside 1 .. 16384", s, k);
+    } else if (kind == FB_TF_DECIMATE) {
+      if (k < 2 || k > 64) return fb_fail(FB_E_ARG, "stage %d: decimation factor %d outside 2 .. 64", s, k);
+    } else if (kind == FB_TF_MEDIAN) {
+      if (k < 3 || k > 31 || !(k & 1)) return fb_fail(FB_E_ARG, "stage %d: median width %d is not odd in 3 .. 31", s, k);
+      radius = (k - 1) / 2;
+    } else if (kind == FB_TF_FIR) {
+      if (k < 1 || k > 511 || !(k & 1)) return fb_fail(FB_E_ARG, "stage %d: FIR length %d is not odd in 1 .. 511", s, k);
+      if (!stages[s].taps) return fb_fail(FB_E_ARG, "stage %d: FIR taps are NULL", s);
+      for (int j = 0; j < k; ++j)
+        if (!(fabs(stages[s].taps[j]) <= 1048576.0))  // (NaN fails the comparison too)
+          return fb_fail(FB_E_ARG, "stage %d: tap %d is not finite or exceeds 2^20 in magnitude", s, j);
+      radius = (k - 1) / 2;
+      ch.tap_off[s] = (int)taps.size();
+      taps.insert(taps.end(), stages[s].taps, stages[s].taps + k);
+    } else {
+      return fb_fail(FB_E_ARG, "stage %d: unknown kind %d", s, kind);
+    }
+    ch.kind[s] = kind;
+    ch.k[s] = k;
+    ch.H += radius;
+  }
+  if (ch.H > FB_TF_MAX_HALO) return fb_fail(FB_E_ARG, "the stages' radii sum to %d: at most %d", ch.H, FB_TF_MAX_HALO);
+  ch.n = n;
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));  // nothing in flight reads the taps any more
+  DevBuf fresh;
+  if (!taps.empty()) {
+    FBCHK(fresh.ensure(sizeof(double) * taps.size()));
+    int rc = h2d(e, fresh.p, taps.data(), sizeof(double) * taps.size());
+    if (rc == FB_OK) rc = sync_stream(e);
+    if (rc != FB_OK) { fresh.release(); return rc; }
+  }
+  e->tf_taps.release();
+  e->tf_taps = fresh;
+  e->tf = ch;
+  e->bench_it = -1;  // an attack fb_bench_nes left resident was scored through the previous chain
+  return FB_OK;
+}
+
+extern "C" int fb_debug_input_transform(fb_engine *e, const int16_t *wav, const int64_t *off, int B, int16_t *out) {
+  if (!e || !wav || !off || !out || B <= 0 || B > 65535) return fb_fail(FB_E_ARG, "bad argument");
+  if (off[0] != 0) return fb_fail(FB_E_ARG, "off[0] must be 0");
+  int64_t n_max = 0;
+  for (int b = 0; b < B; ++b) {
+    const int64_t n = off[b + 1] - off[b];
+    if (n <= 0) return fb_fail(FB_E_ARG, "utterance %d is empty", b);
+    if (n > 0x7fffffffLL) return fb_fail(FB_E_LIMIT, "utterance %d longer than 2^31 samples", b);
+    n_max = std::max(n_max, n);
+  }
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  e->cached_B = -1;  // the scoring batch layout no longer describes e->wav / e->wav_off
+  e->bench_it = -1;
+  const size_t bytes = sizeof(int16_t) * (size_t)off[B];
+  FBCHK(e->wav.ensure(bytes));
+  FBCHK(e->wav_tf.ensure(bytes));
+  FBCHK(e->wav_off.ensure(sizeof(int64_t) * (B + 1)));
+  FBCHK(h2d(e, e->wav.p, wav, bytes));
+  FBCHK(h2d(e, e->wav_off.p, off, sizeof(int64_t) * (B + 1)));
+  fb_launch_input_transform(e->stream, e->tf, e->tf_taps.as<double>(), e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), B, n_max,
+                            e->wav_tf.as<int16_t>(), nullptr);
+  HIPCHK(hipGetLastError());
+  FBCHK(d2h(e, out, e->wav_tf.p, bytes));
+  FBCHK(sync_stream(e));
   return FB_OK;
 }
 

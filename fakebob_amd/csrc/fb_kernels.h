@@ -42,6 +42,22 @@ static inline FbDitherKey fb_dither_key(double amp, uint64_t seed, uint32_t stre
 // the normals the dithered MFCC kernels add to frames t0 .. t0 + n_frames - 1 of utterance dk.utt0: z[n_frames][L]
 void fb_launch_dither_noise(hipStream_t s, const FbDitherKey &dk, int t0, int n_frames, int L, float *z);
 
+// ---- input-transform chain (fb_set_input_transform; input_transform_kernel.hip) ----------------------------------
+#define FB_TF_MAX_STAGES 8
+#define FB_TF_MAX_HALO 1024   // largest sum of the stages' radii
+#define FB_TF_TILE 4096       // output samples of one workgroup
+// the chain as the kernel takes it (by value): H = the sum of the radii, k[s] = the stage's parameter (q, k or L),
+// tap_off[s] = where a FIR stage's taps start in the taps buffer
+struct FbTfChain {
+  int n, H;
+  int kind[FB_TF_MAX_STAGES], k[FB_TF_MAX_STAGES], tap_off[FB_TF_MAX_STAGES];
+};
+// out (the layout of wav: wav_off[B + 1]) = the chain applied to every utterance of wav; n_max = the longest utterance;
+// honours `stop` (nullable) like the MFCC kernels.  ch.n == 0 copies.
+void fb_launch_input_transform(hipStream_t s, const FbTfChain &ch, const double *taps, const int16_t *wav,
+                               const int64_t *wav_off, int B, int64_t n_max, int16_t *out, const int *stop);
+size_t fb_input_transform_lds_bytes(const FbTfChain &ch);
+
 // ---- NES ----------------------------------------------------------------
 // q[b][n] = int16((adver[n] + sigma*noise_b[n]) * 2^15), b in [0, 2*half]; column 0 is the
 // un-noised adver.  noise: Philox(seed, iter, stream) or explicit float64 [N][half].

@@ -38,6 +38,7 @@ class Engine(object):
         self.n_models = 0
         self.cfg = N.FrontendCfg()
         self._L.fb_default_frontend(C.byref(self.cfg))
+        self.input_transform = []
 
     def close(self):
         if self._h:
@@ -69,6 +70,29 @@ class Engine(object):
         """The dither key of scoring calls outside an attack (fb_set_dither_seed); restarts their serial at 0, so the same
         sequence of scoring calls after it draws the same noise."""
         N.check(self._L.fb_set_dither_seed(self._h, C.c_uint64(int(seed))))
+
+    def set_input_transform(self, stages, validate=True):
+        """The input-transform chain of a defended system (fb_set_input_transform): a spec string ("ms:7,qt:512"), a list of
+        fakebob_amd.input_transform stages, or None / [] / "none" to clear it.  The engine applies it to every utterance its
+        own front end reads -- scoring, enrolment statistics, the NES loops --, not to the batch of a foreign model and not
+        to the returned audio.  The limits are checked here before the call (ValueError); validate=False hands the stages
+        to the library as they are (it refuses what is outside the contract and keeps the previous chain)."""
+        from . import input_transform as T
+        stages = T.parse(stages) if validate else list(stages or [])
+        arr, keep = T.c_stages(stages)
+        N.check(self._L.fb_set_input_transform(self._h, arr, C.c_int(len(stages))))
+        self.input_transform = stages
+        del keep
+
+    def debug_input_transform(self, audio_list):
+        """The int16 batch the MFCC would read for these int16 utterances (fb_debug_input_transform): a list of arrays."""
+        lst = [np.ascontiguousarray(a, np.int16).reshape(-1) for a in audio_list]
+        off = np.zeros(len(lst) + 1, np.int64)
+        off[1:] = np.cumsum([a.size for a in lst])
+        cat = np.ascontiguousarray(np.concatenate(lst))
+        out = np.empty_like(cat)
+        N.check(self._L.fb_debug_input_transform(self._h, N.ptr(cat), N.ptr(off), C.c_int(len(lst)), N.ptr(out)))
+        return [out[off[i]:off[i + 1]].copy() for i in range(len(lst))]
 
     @property
     def feat_dim(self):

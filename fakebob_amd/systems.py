@@ -91,6 +91,17 @@ def _dither_option(dither):
     return "conf" if dither == "conf" else float(dither)
 
 
+def _apply_input_transform(engine, input_transform):
+    """The input-transform chain of a (defended) system under construction: the constructor keyword -- a spec string such
+    as "ms:7,qt:512" or a list of fakebob_amd.input_transform stages; "none" or [] for no chain --, then
+    FB_INPUT_TRANSFORM.  None of the two: the engine keeps its chain (none unless the caller set one)."""
+    if input_transform is None:
+        input_transform = os.environ.get("FB_INPUT_TRANSFORM")
+        if input_transform is None or input_transform == "":
+            return
+    engine.set_input_transform(input_transform)
+
+
 def _conf_overrides(pre_model_dir, dither=None):
     """Front-end overrides of pre_model_dir/conf (none without that directory, or for pre_model_dir None) plus the dither
     option (_dither_option)."""
@@ -131,7 +142,7 @@ class _GmmSystem(object):
     PIPELINE = None  # class default of the two round trips (see REFERENCE_PIPELINE)
 
     def _setup(self, group_id, models, spk_ids, utt_ids, locations, z_means, z_stds, pre_model_dir, engine,
-               text_scores=None, compress_feats=None, mfcc_f32=None, dither=None):
+               text_scores=None, compress_feats=None, mfcc_f32=None, dither=None, input_transform=None):
         self.pre_model_dir = os.path.abspath(pre_model_dir)
         self.group_id = os.path.abspath(group_id)
         self.spk_ids = spk_ids
@@ -141,6 +152,7 @@ class _GmmSystem(object):
         self._engine = engine if engine is not None else Engine(default_device())
         over = _conf_overrides(self.pre_model_dir, dither)
         _apply_frontend(self._engine, over, text_scores, compress_feats, mfcc_f32, self.PIPELINE)
+        _apply_input_transform(self._engine, input_transform)
         self._engine.load_gmm(models)
         self._engine.set_system(self.task, z_means, z_stds)
 
@@ -165,13 +177,15 @@ class gmm_OSI(_GmmSystem):
     task = "OSI"
 
     def __init__(self, group_id, model_list, ubm, pre_model_dir="pre-models", threshold=0.0, engine=None,
-                 text_scores=None, compress_feats=None, mfcc_f32=None, dither=None):
+                 text_scores=None, compress_feats=None, mfcc_f32=None, dither=None,
+                 input_transform=None):
         self.threshold = threshold
         locs = [m[2] for m in model_list]
         self.model_list = [ubm] + locs  # UBM first (gmm_ubm_OSI.py:45)
         models = [load_gmm_any(x) for x in self.model_list]
         self._setup(group_id, models, [m[0] for m in model_list], [m[1] for m in model_list], locs, None, None,
-                    pre_model_dir, engine, text_scores, compress_feats, mfcc_f32, dither)
+                    pre_model_dir, engine, text_scores, compress_feats, mfcc_f32, dither,
+                    input_transform)
 
     def score(self, audios, fs=16000, bits_per_sample=16, debug=False, n_jobs=5):
         raw = self._raw(audios, bits_per_sample)
@@ -197,14 +211,16 @@ class gmm_CSI(_GmmSystem):
     task = "CSI"
 
     def __init__(self, group_id, model_list, pre_model_dir="pre-models", engine=None, text_scores=None,
-                 compress_feats=None, mfcc_f32=None, dither=None):
+                 compress_feats=None, mfcc_f32=None, dither=None,
+                 input_transform=None):
         locs = [m[2] for m in model_list]
         self.model_list = locs
         self.z_norm_means = np.array([m[3] for m in model_list], np.float64)
         self.z_norm_stds = np.array([m[4] for m in model_list], np.float64)
         models = [load_gmm_any(x) for x in locs]
         self._setup(group_id, models, [m[0] for m in model_list], [m[1] for m in model_list], locs,
-                    self.z_norm_means, self.z_norm_stds, pre_model_dir, engine, text_scores, compress_feats, mfcc_f32, dither)
+                    self.z_norm_means, self.z_norm_stds, pre_model_dir, engine, text_scores, compress_feats, mfcc_f32, dither,
+                    input_transform)
 
     def score(self, audios, fs=16000, bits_per_sample=16, debug=False, n_jobs=5):
         raw = self._raw(audios, bits_per_sample)
@@ -226,14 +242,16 @@ class gmm_SV(_GmmSystem):
     task = "SV"
 
     def __init__(self, spk_id, model, ubm, pre_model_dir="pre-models", threshold=0.0, engine=None,
-                 text_scores=None, compress_feats=None, mfcc_f32=None, dither=None):
+                 text_scores=None, compress_feats=None, mfcc_f32=None, dither=None,
+                 input_transform=None):
         self.threshold = threshold
         self.utt_id = model[1]
         self.identity_location = model[2]
         self.model_list = [ubm, self.identity_location]
         models = [load_gmm_any(x) for x in self.model_list]
         self._setup(spk_id, models, [model[0]], [model[1]], [model[2]], None, None, pre_model_dir, engine,
-                    text_scores, compress_feats, mfcc_f32, dither)
+                    text_scores, compress_feats, mfcc_f32, dither,
+                    input_transform)
         self.spk_id = self.group_id
 
     def score(self, audios, fs=16000, bits_per_sample=16, debug=False, n_jobs=5):
@@ -255,7 +273,8 @@ class _IvSystem(object):
     task = None
     PIPELINE = None
 
-    def _setup(self, group_id, model_list, pre_model_dir, engine, system, text_scores=None, compress_feats=None, mfcc_f32=None, dither=None):
+    def _setup(self, group_id, model_list, pre_model_dir, engine, system, text_scores=None, compress_feats=None, mfcc_f32=None, dither=None,
+               input_transform=None):
         from .models import IvectorSystem
         self.pre_model_dir = os.path.abspath(pre_model_dir)
         self.group_id = os.path.abspath(group_id)
@@ -288,6 +307,7 @@ class _IvSystem(object):
         else:
             _apply_frontend(self._engine, _conf_overrides(None, dither), text_scores, compress_feats, mfcc_f32, self.PIPELINE)
             system = system.with_enrolled(enrolled, zm, zs)
+        _apply_input_transform(self._engine, input_transform)
         self._engine.load_ivector(system, self.task)
 
     @property
@@ -310,9 +330,11 @@ class iv_OSI(_IvSystem):
     task = "OSI"
 
     def __init__(self, group_id, model_list, pre_model_dir="pre-models", threshold=0.0, engine=None, system=None,
-                 text_scores=None, compress_feats=None, mfcc_f32=None, dither=None):
+                 text_scores=None, compress_feats=None, mfcc_f32=None, dither=None,
+                 input_transform=None):
         self.threshold = threshold
-        self._setup(group_id, model_list, pre_model_dir, engine, system, text_scores, compress_feats, mfcc_f32, dither)
+        self._setup(group_id, model_list, pre_model_dir, engine, system, text_scores, compress_feats, mfcc_f32, dither,
+                    input_transform)
 
     def score(self, audio_list, fs=16000, bits_per_sample=16, n_jobs=10, debug=False):
         s = (self._llr(audio_list, bits_per_sample) - self.z_norm_means) / self.z_norm_stds   # :119
@@ -340,8 +362,10 @@ class iv_CSI(_IvSystem):
     task = "CSI"
 
     def __init__(self, group_id, model_list, pre_model_dir="pre-models", engine=None, system=None, text_scores=None,
-                 compress_feats=None, mfcc_f32=None, dither=None):
-        self._setup(group_id, model_list, pre_model_dir, engine, system, text_scores, compress_feats, mfcc_f32, dither)
+                 compress_feats=None, mfcc_f32=None, dither=None,
+                 input_transform=None):
+        self._setup(group_id, model_list, pre_model_dir, engine, system, text_scores, compress_feats, mfcc_f32, dither,
+                    input_transform)
 
     def score(self, audio_list, fs=16000, bits_per_sample=16, n_jobs=10, debug=False):
         s = (self._llr(audio_list, bits_per_sample) - self.z_norm_means) / self.z_norm_stds
@@ -364,9 +388,11 @@ class iv_SV(_IvSystem):
     task = "SV"
 
     def __init__(self, spk_id, model, pre_model_dir="pre-models", threshold=0.0, engine=None, system=None,
-                 text_scores=None, compress_feats=None, mfcc_f32=None, dither=None):
+                 text_scores=None, compress_feats=None, mfcc_f32=None, dither=None,
+                 input_transform=None):
         self.threshold = threshold
-        self._setup(spk_id, [model], pre_model_dir, engine, system, text_scores, compress_feats, mfcc_f32, dither)
+        self._setup(spk_id, [model], pre_model_dir, engine, system, text_scores, compress_feats, mfcc_f32, dither,
+                    input_transform)
         self.spk_id = self.group_id
         self.utt_id = model[1]
         self.identity_location = model[2]

@@ -13,6 +13,8 @@
  *                             (gmm_ubm_OSI.py:15,45; attackMain.py:55,73-83)
  *   fb_set_frontend           pre-models/conf/{mfcc,vad}.conf + delta_opts read
  *                             by gmm_ubm_kaldiHelper.py:133,153,191
+ *   fb_set_input_transform    (none: the input-transformation defences of the paper's evaluation,
+ *                             placed in front of the recogniser)
  *   fb_score_i16 / _f64       gmm_ubm_kaldiHelper.score (:270-291) and the
  *                             int16 cast of gmm_ubm_OSI.py:83-85
  *   fb_system_scores          wrapper post-processing gmm_ubm_OSI.py:89,
@@ -144,6 +146,34 @@ typedef struct {
  * So an attack's result depends on (seed, stream) only -- not on the engine that ran it, on the launch chain or on how
  * many iterations the host queues ahead --, and an utterance's noise does not depend on what else is in its batch. */
 int fb_set_dither_seed(fb_engine *e, uint64_t seed);
+
+/* ---- input-transform chain: a defended system ---------------------------------------------------------------
+ * A short list of int16 -> int16 stages (the input transformations of the FAKEBOB paper's defence study: quantisation,
+ * median smoothing, down-sampling; average smoothing, low-pass / band-pass filters and room impulse responses as FIR)
+ * applied on the device, in one launch, to every utterance the engine's own front end reads, between the int16 cast and
+ * the MFCC.  The filter sits inside the victim:
+ *  - applied in fb_score_i16 / _f64, fb_gmm_acc_stats (a defended system enrols through its filter), fb_get_grad,
+ *    fb_attack, fb_estimate_threshold and the fb_debug_mfcc / fb_debug_feats hooks, for GMM and i-vector systems on
+ *    every MFCC route, with or without dither (dither acts on the frames extracted from the transformed samples);
+ *  - NOT applied to the batch handed to foreign models (_ext, _dev: their defence is their own), to the returned
+ *    adversarial audio or to the trace's distance column.
+ * Stage contract.  A stage maps the samples x[0 .. n) of ONE utterance to y[0 .. n); indices outside [0, n) read as 0 at
+ * every stage; every result is exactly reproducible in numpy:
+ *   FB_TF_QUANT     k = q, 1 .. 16384    y = clip(q * floor_div(x + q / 2, q)): int32 arithmetic, q / 2 integer division,
+ *                                        floor_div rounds toward -inf, clip to [-32768, 32767]
+ *   FB_TF_MEDIAN    k odd, 3 .. 31       y[i] = median of x[i - r .. i + r], r = (k - 1) / 2 (scipy.signal.medfilt's
+ *                                        zero-padded semantics)
+ *   FB_TF_FIR       k = L odd, 1 .. 511  acc = 0.0; for j = 0 .. L - 1 ascending: acc = acc + taps[j] * x[i + c - j],
+ *                   taps[L] float64,     c = (L - 1) / 2; every product is rounded to float64, then the sum is, with no
+ *                   finite, |h| <= 2^20  fused multiply-add; y = clip(rint(acc)), ties to even
+ *   FB_TF_DECIMATE  k = q, 2 .. 64       y[i] = x[i] if i mod q == 0, else 0, i counted from the utterance's first sample
+ * (average smoothing = FIR with taps 1 / k; audio squeezing by q = FIR, DECIMATE(q), FIR with the gain q folded into the
+ * second filter's taps.)  Limits: at most 8 stages; the stages' radii (r or c; 0 for QUANT and DECIMATE) sum to at most
+ * 1024.  Anything outside the contract returns FB_E_ARG and keeps the previous chain, as fb_set_frontend does.
+ * n = 0 clears the chain: no launch is added and nothing else changes.  `taps` is read for FB_TF_FIR only and copied. */
+enum { FB_TF_QUANT = 0, FB_TF_MEDIAN = 1, FB_TF_FIR = 2, FB_TF_DECIMATE = 3 };
+typedef struct { int kind; int k; const double *taps; } fb_tf_stage;
+int fb_set_input_transform(fb_engine *e, const fb_tf_stage *stages, int n);
 
 const char *fb_last_error(void);
 int fb_version(void);

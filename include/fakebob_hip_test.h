@@ -39,6 +39,11 @@ int fb_debug_mfcc_dither(fb_engine *e, const int16_t *wav, int64_t n, uint64_t s
 int fb_debug_feats_dither(fb_engine *e, const int16_t *wav, int64_t n, uint64_t seed, uint32_t stream, uint32_t epoch,
                           uint32_t utt, float *feats, int *Tv, int *T);
 
+/* The int16 batch the MFCC reads with the engine's input-transform chain (fb_set_input_transform): out, in wav's layout
+ * (off[B + 1], off[0] = 0), from the kernel the scoring paths launch.  Utterances may be of any length >= 1 (shorter than a
+ * frame included: nothing but the transform runs).  Without a chain out equals wav. */
+int fb_debug_input_transform(fb_engine *e, const int16_t *wav, const int64_t *off, int B, int16_t *out);
+
 /* What the front end of the last batch ran (fb_score_*, fb_get_grad, an NES iteration, fb_debug_mfcc / _feats, enrolment
  * statistics): info[5] = {the MFCC kernel, the chain after it, where the CompressedMatrix round trip ran, the longest
  * utterance of the batch in frames, the batch size}.  Recorded on the host when the kernels are enqueued; read only.
