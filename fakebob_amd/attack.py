@@ -52,7 +52,7 @@ class FakeBob(object):
 
     def __init__(self, task, attack_type, model, adver_thresh=0., epsilon=0.002, max_iter=1000,
                  max_lr=0.001, min_lr=1e-6, samples_per_draw=50, sigma=0.001, momentum=0.9,
-                 plateau_length=5, plateau_drop=2., seed=None, verbose=True):
+                 plateau_length=5, plateau_drop=2., seed=None, verbose=True, eot_size=None):
         self.task = task
         self.attack_type = attack_type
         self.model = model
@@ -88,6 +88,17 @@ class FakeBob(object):
         if self._native and getattr(model, "task", task) != task:
             raise ValueError("model implements task %s, attack asked for %s" % (model.task, task))
         self._n_spk = None
+        # expectation over transformation (SpeakerGuard's EOT_size): every NES sample scored under eot_size draws of a
+        # randomised victim.  The engine's own systems only; a foreign model's randomness is its own.
+        from .systems import eot_option
+        if self._native:
+            self.eot_size = eot_option(eot_size)          # the keyword, then FB_EOT_SIZE
+            if self.eot_size is not None:
+                model.engine.set_eot(self.eot_size)
+        else:                                             # (FB_EOT_SIZE is not meant for a foreign model: the library ignores EOT there)
+            self.eot_size = None
+            if eot_size is not None and eot_option(eot_size) != 1:
+                raise ValueError("eot_size applies to the engine's own systems, not to a foreign model")
 
     # ------------------------------------------------------------------ helpers
     def _params(self, attack_type=None, max_iter=None, stream=None, bits_per_sample=16):

@@ -145,6 +145,10 @@ def main(argv=None, model_factory=None, bob_factory=None):
                     help="attack a defended victim: the input-transform chain in front of its recogniser, e.g. 'ms:7', "
                          "'qt:512', 'ds:2', 'lpf:4000' or several joined by commas (fakebob_amd/input_transform.py); "
                          "default: none, or FB_INPUT_TRANSFORM")
+    ap.add_argument("--eot-size", dest="eot_size", default=None, type=int,
+                    help="expectation over transformation against a randomised victim (a 'noise:' / 'at:' stage, --dither): "
+                         "every NES sample is scored under this many independent draws and the losses are averaged "
+                         "(1 .. 32); default: 1, or FB_EOT_SIZE")
     ap.add_argument("--model_dir", default="./model")
     ap.add_argument("--pre_model_dir", default="pre-models")
     ap.add_argument("--test_dir", default="./data/test-set")
@@ -176,6 +180,8 @@ def main(argv=None, model_factory=None, bob_factory=None):
     for m in models:  # (a stub model of the driver-rule tests has no engine)
         if hasattr(m, "engine") and hasattr(m.engine, "set_dither_seed"):
             m.engine.set_dither_seed(args.dither_seed)
+        if args.eot_size is not None and hasattr(m, "engine") and hasattr(m.engine, "set_eot"):
+            m.engine.set_eot(args.eot_size)
     if K >= 3:  # several engines share the GPU: the separate launches interleave better (fb_set_fused_chain)
         for m in models:
             if hasattr(m, "engine"):

@@ -94,6 +94,12 @@ struct fb_engine {
   FbTfChain tf = {};
   DevBuf tf_taps;               // the FIR stages' taps, one after the other
   DevBuf wav_tf;                // the transformed batch, in wav's layout: what the MFCC reads when a chain is set
+  // randomised stages and expectation over transformation (FB_TF_NOISE, fb_set_eot; the "Noise RNG contract" of fakebob_hip.h)
+  FbTfRnd nkey = {};            // the point of the noise contract the next transform launch stands at: set beside dkey
+  DevBuf tf_power;              // k_tf_power's per-utterance sums of squares (chains with an SNR stage)
+  int eot = 1;                  // fb_set_eot: replicas of every NES row (1: none)
+  int eot_run = 1;              // ... of the batch run_scoring is working on (enqueue_get_grad sets it around its call; else 1)
+  DevBuf eot_sc, eot_l;         // k_loss_eot's per-replica scores [B * r][S] and losses [B * r]
   // gmm
   bool have_gmm = false;
   FbGmmDev gmm;
@@ -258,7 +264,7 @@ extern "C" int fb_engine_destroy(fb_engine *e) {
   if (!e) return FB_OK;
   (void)hipSetDevice(e->device);
   if (e->stream) (void)hipStreamSynchronize(e->stream);
-  DevBuf *bufs[] = {&e->fe_tables, &e->fe_tables32, &e->frame_ut, &e->tf_taps, &e->wav_tf, &e->gmm_items, &e->gmm_images_bx, &e->gmm_images_fx, &e->gmm_images_fd, &e->gmm_images_fd2, &e->gmm_images_fd3, &e->gmm_anchor, &e->zmean, &e->zstd, &e->wav, &e->wav_off,
+  DevBuf *bufs[] = {&e->fe_tables, &e->fe_tables32, &e->frame_ut, &e->tf_taps, &e->wav_tf, &e->tf_power, &e->eot_sc, &e->eot_l, &e->gmm_items, &e->gmm_images_bx, &e->gmm_images_fx, &e->gmm_images_fd, &e->gmm_images_fd2, &e->gmm_images_fd3, &e->gmm_anchor, &e->zmean, &e->zstd, &e->wav, &e->wav_off,
                     &e->frame_rec, &e->vad_counter, &e->vad_pub, &e->vad_part, &e->fin_counter, &e->fin_xch, &e->ctl, &e->ctl_ls, &e->trace_dev, &e->ticks, &e->enr_ll, &e->enr_aux, &e->enr_stats, &e->frame_off, &e->chunk_off, &e->chunk_sum, &e->mfcc, &e->mfcc_cm, &e->vrank, &e->tv, &e->row_off, &e->dfeat, &e->feats,
                     &e->part_m, &e->part_s, &e->raw, &e->audio, &e->adver, &e->grad_m, &e->grad, &e->noise, &e->zbuf,
                     &e->scores, &e->loss, &e->dist_part, &e->nes_out, &e->stage_f64, &e->ext_x, &e->ext_z, &e->iv_fg, &e->iv_fg64, &e->iv_fgL, &e->iv_tri,
@@ -1239,16 +1245,41 @@ static void choose_launch_shape(fb_engine *e) {
 }
 // The batch the MFCC reads: e->wav, or -- with an input-transform chain set -- its transform in e->wav_tf, one more launch.
 // off: the batch's offsets on the host (off[0] = 0), already in e->wav_off on the device.
+// stages of kind FB_TF_NOISE in the chain (snr_only: in SNR mode, the ones that need k_tf_power in front)
+static int tf_noise_stages(const FbTfChain &ch, bool snr_only) {
+  int c = 0;
+  for (int s = 0; s < ch.n; ++s) c += ch.kind[s] == FB_TF_NOISE && (!snr_only || ch.k[s] == 1);
+  return c;
+}
+// With e->eot_run = r > 1 (an NES batch under fb_set_eot) B counts the REPLICATED rows: e->wav holds B / r utterances of
+// equal length -- the first B / r + 1 entries of e->wav_off describe them -- and replica j of utterance u goes to row
+// u * r + j of e->wav_tf, every time and with an empty chain too.
 static int transformed_wav(fb_engine *e, const int64_t *off, int B, const int16_t **wav) {
   *wav = e->wav.as<int16_t>();
-  if (e->tf.n == 0) return FB_OK;
+  const int r = e->eot_run;
+  if (e->tf.n == 0 && r == 1) return FB_OK;
   if (B > 65535) return fb_fail(FB_E_LIMIT, "an input-transform chain takes batches of up to 65535 utterances");
   int64_t n_max = 0;
   for (int b = 0; b < B; ++b) n_max = std::max(n_max, off[b + 1] - off[b]);
   if (n_max > 0x7fffffffLL) return fb_fail(FB_E_LIMIT, "utterance longer than 2^31 samples");
   FBCHK(e->wav_tf.ensure(sizeof(int16_t) * (size_t)off[B]));
-  fb_launch_input_transform(e->stream, e->tf, e->tf_taps.as<double>(), e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), B, n_max,
-                            e->wav_tf.as<int16_t>(), e->fe.stop);
+  if (r == 1 && tf_noise_stages(e->tf, false) == 0) {
+    fb_launch_input_transform(e->stream, e->tf, e->tf_taps.as<double>(), e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), B, n_max,
+                              e->wav_tf.as<int16_t>(), e->fe.stop);
+  } else {
+    const int B_in = B / r;
+    FbTfRnd rn = e->nkey;
+    rn.r = r;
+    rn.power = nullptr;
+    if (tf_noise_stages(e->tf, true) > 0) {  // the SNR stages' E_u: a launch of its own, read by the next one only
+      FBCHK(e->tf_power.ensure(sizeof(unsigned long long) * (size_t)B_in));
+      HIPCHK(fb_launch_tf_power(e->stream, e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), B_in, n_max,
+                                e->tf_power.as<unsigned long long>(), e->fe.stop));
+      rn.power = e->tf_power.as<unsigned long long>();
+    }
+    fb_launch_input_transform_rnd(e->stream, e->tf, e->tf_taps.as<double>(), e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), B_in,
+                                  n_max, e->wav_tf.as<int16_t>(), e->wav_off.as<int64_t>(), rn, e->fe.stop);
+  }
   *wav = e->wav_tf.as<int16_t>();
   return FB_OK;
 }
@@ -1280,6 +1311,7 @@ static int launch_mfcc(fb_engine *e, int B, int total_frames) {
 // seed, stream 0xFFFFFFFF, epoch = the scoring-call serial, which the call consumes
 static void dither_key_scoring_call(fb_engine *e) {
   e->dkey = fb_dither_key(e->cfg.dither, e->dither_seed, 0xFFFFFFFFu, e->dither_serial, 0);
+  e->nkey = fb_tf_rnd(e->dither_seed, 0xFFFFFFFFu, e->dither_serial, 0);  // (the noise stages' key: the same rules)
   e->dither_serial += 1;
 }
 
@@ -1519,7 +1551,7 @@ static int run_scoring(fb_engine *e, int B, int total_frames) {
     FbIvTail tail = {};
     {
       const char *tv_env = getenv("FB_IV_TAIL");
-      const bool split = tv_env && strcmp(tv_env, "split") == 0;
+      const bool split = (tv_env && strcmp(tv_env, "split") == 0) || e->eot_run > 1;  // (fb_set_eot: k_loss_eot follows k_iv_backend)
       if (!e->iv_tail_counter.p) {
         FBCHK(e->iv_tail_counter.ensure(sizeof(int)));
         HIPCHK(hipMemsetAsync(e->iv_tail_counter.p, 0, sizeof(int), s));
@@ -2121,7 +2153,7 @@ static FbLoopKnobs loop_knobs(const fb_engine *e, const FbScorer &sc) {
     const char *ev = getenv("FB_ATTACK_BATCH");
     const int b = ev ? atoi(ev) : 4;
     k.look = b < 1 ? 1 : (b > 16 ? 16 : b);
-    k.fuse_fin = fb_fuse_part(e, 1);
+    k.fuse_fin = fb_fuse_part(e, 1) && e->eot == 1;  // (fb_set_eot: the finalisation, then k_loss_eot)
     k.fuse_upd = fb_fuse_part(e, 2);
     const char *fu = getenv("FB_FUSE_UPD");
     k.upd_in_fin = !(fu && fu[0] == '0');
@@ -2141,6 +2173,7 @@ static int enqueue_get_grad(fb_engine *e, const fb_nes_params *p, int64_t N, uin
                             FbCtlDev *ctl = nullptr, double *trace_dev = nullptr, int trace_row = 0,
                             const FbUpdArgs *upd = nullptr, bool *upd_done = nullptr) {
   const int half = p->samples_per_draw / 2, B = 2 * half + 1;
+  const int r = e->eot, BR = B * r;  // fb_set_eot: the front end scores r replicas of every row
   int ndp = 0;
   const int *stop = ctl ? &ctl->stop : nullptr;
   e->fe.stop = stop;
@@ -2154,9 +2187,9 @@ static int enqueue_get_grad(fb_engine *e, const fb_nes_params *p, int64_t N, uin
   }
   e->pre_iter = -1;
   // GMM systems inside the device-controlled loop: finalisation and loss share one launch
-  const bool fuse_fin = ctl && e->kind == 0 && kn.fuse_fin;
+  const bool fuse_fin = ctl && e->kind == 0 && kn.fuse_fin;  // (never with fb_set_eot r > 1: loop_knobs)
   e->defer_finalize = fuse_fin;
-  if (e->kind == 1) {  // i-vector systems: the loss body rides in the tail of the solve kernel when the batch allows it
+  if (e->kind == 1 && r == 1) {  // i-vector systems: the loss body rides in the tail of the solve kernel when the batch allows it
     FbIvTail &t = e->tail_req;
     t = FbIvTail{};
     t.tv = e->tv.as<int>();
@@ -2173,12 +2206,22 @@ static int enqueue_get_grad(fb_engine *e, const fb_nes_params *p, int64_t N, uin
   // Kaldi's dither inside an attack: keyed by the attack's own (seed, stream), epoch = the NES iteration (in
   // fb_estimate_threshold `iter` counts the call's front-end launches: one per pass of its loop)
   e->dkey = fb_dither_key(e->cfg.dither, p->seed, p->stream, iter, 0);
-  const int rc = run_scoring(e, B, e->h_frame_off[B]);
+  e->nkey = fb_tf_rnd(p->seed, p->stream, iter, 0);
+  e->eot_run = r;
+  const int rc = run_scoring(e, BR, e->h_frame_off[BR]);
+  e->eot_run = 1;
   e->tail_loss_req = false;
   e->defer_finalize = false;
   e->fe.stop = nullptr;
   e->gmm.stop = nullptr;
   FBCHK(rc);
+  if (r > 1) {
+    fb_launch_loss_eot(e->stream, e->raw.as<double>(), e->tv.as<int>(), B, r, e->n_out, p->task, e->kind, p->attack_type,
+                       e->zmean.as<double>(), e->zstd.as<double>(), p->threshold, p->adver_thresh, p->target, p->true_label,
+                       e->dist_part.as<double>(), with_dist ? ndp : 0, e->eot_sc.as<double>(), e->eot_l.as<double>(),
+                       e->scores.as<double>(), e->loss.as<double>(), e->nes_out.as<FbNesDev>(), ctl, trace_dev, trace_row);
+    return FB_OK;
+  }
   if (e->tail_loss_done) return FB_OK;
   if (fuse_fin) {
     if (!e->fin_counter.p) {
@@ -2379,7 +2422,14 @@ static int nes_setup(fb_engine *e, const fb_nes_params *p, int64_t N, FbScorer &
   const int B = 2 * (p->samples_per_draw / 2) + 1;
   if (native) {
     sc.S = fb_num_speakers(e);
-    FBCHK(prepare_nes_batch(e, N, B));
+    const int r = e->eot;
+    if ((int64_t)B * r > 65535)
+      return fb_fail(FB_E_LIMIT, "(samples_per_draw + 1) * eot = %lld rows: a scoring batch takes up to 65535", (long long)B * r);
+    FBCHK(prepare_nes_batch(e, N, B * r));
+    if (r > 1) {
+      FBCHK(e->eot_sc.ensure(sizeof(double) * (size_t)B * r * (sc.S > 0 ? sc.S : 1)));
+      FBCHK(e->eot_l.ensure(sizeof(double) * (size_t)B * r));
+    }
     return ensure_nes_buffers(e, N, B);
   }
   FBCHK(sync_stream(e));
@@ -2688,6 +2738,8 @@ extern "C" int fb_estimate_threshold(fb_engine *e, const fb_nes_params *p_in, do
   if (!audio || !score_out) return fb_fail(FB_E_ARG, "null argument");
   if (!p_in) return fb_fail(FB_E_ARG, "null params");
   if (p_in->task == FB_TASK_CSI) return fb_fail(FB_E_ARG, "no threshold to estimate for CSI (FAKEBOB.py:41-43)");
+  if (e && e->eot > 1)
+    return fb_fail(FB_E_STATE, "fb_estimate_threshold does not run under expectation over transformation (fb_set_eot(%d)): set 1", e->eot);
   fb_nes_params q = *p_in;
   q.attack_type = FB_UNTARGETED;  // :73-74
   FbScorer sc{FB_SCORER_NATIVE};
@@ -2805,8 +2857,12 @@ static int debug_frontend(fb_engine *e, const int16_t *wav, int64_t n, const FbD
   FBCHK(e->row_off.ensure(sizeof(int) * 2));
   FBCHK(e->feats.ensure(sizeof(float) * (size_t)T * fe.dim));
   choose_launch_shape(e);
-  if (key) e->dkey = *key;
-  else dither_key_scoring_call(e);
+  if (key) {  // (the noise stages stand at the same point: the key's first word carries the seed's low half)
+    e->dkey = *key;
+    e->nkey = FbTfRnd{key->k0 ^ 0x44495448u ^ 0x4E4F4953u, key->k1, key->epoch, key->utt0, 1, nullptr};
+  } else {
+    dither_key_scoring_call(e);
+  }
   FBCHK(launch_mfcc(e, 1, T));
   FBCHK(run_post_mfcc(e, 1));
   HIPCHK(hipGetLastError());
@@ -2943,6 +2999,16 @@ extern "C" int fb_set_input_transform(fb_engine *e, const fb_tf_stage *stages, i
       radius = (k - 1) / 2;
       ch.tap_off[s] = (int)taps.size();
       taps.insert(taps.end(), stages[s].taps, stages[s].taps + k);
+    } else if (kind == FB_TF_NOISE) {
+      if (k != 0 && k != 1) return fb_fail(FB_E_ARG, "stage %d: noise mode %d is neither 0 (absolute) nor 1 (SNR)", s, k);
+      if (!stages[s].taps) return fb_fail(FB_E_ARG, "stage %d: the noise stage's parameter (taps[0]) is NULL", s);
+      const double v = stages[s].taps[0];
+      if (k == 0 && !(v >= 0.0 && v <= 32768.0))  // (NaN fails the comparisons too)
+        return fb_fail(FB_E_ARG, "stage %d: noise amplitude %g is not in 0 .. 32768", s, v);
+      if (k == 1 && !(v > 0.0 && std::isfinite(v)))
+        return fb_fail(FB_E_ARG, "stage %d: rho = %g (10^(snr_db / 10)) is not finite and positive", s, v);
+      ch.tap_off[s] = (int)taps.size();
+      taps.push_back(v);
     } else {
       return fb_fail(FB_E_ARG, "stage %d: unknown kind %d", s, kind);
     }
@@ -2994,6 +3060,77 @@ extern "C" int fb_debug_input_transform(fb_engine *e, const int16_t *wav, const 
   FBCHK(d2h(e, out, e->wav_tf.p, bytes));
   FBCHK(sync_stream(e));
   return FB_OK;
+}
+
+// ---- expectation over transformation
+extern "C" int fb_set_eot(fb_engine *e, int r) {
+  if (!e) return fb_fail(FB_E_ARG, "null engine");
+  if (r < 1 || r > 32) return fb_fail(FB_E_ARG, "EOT size %d outside 1 .. 32", r);
+  e->eot = r;
+  e->bench_it = -1;  // an attack fb_bench_nes left resident was laid out for the previous size
+  return FB_OK;
+}
+
+extern "C" int fb_debug_tf_noise(fb_engine *e, uint64_t seed, uint32_t stream, uint32_t epoch, uint32_t utt, int replica,
+                                 int stage, int64_t i0, int64_t n, float *z) {
+  if (!e || !z || i0 < 0 || n <= 0 || i0 + n > 0x7fffffffLL || replica < 0 || replica > 31 || stage < 0 || stage >= FB_TF_MAX_STAGES)
+    return fb_fail(FB_E_ARG, "bad argument");
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  DevBuf tmp;
+  FBCHK(tmp.ensure(sizeof(float) * (size_t)n));
+  fb_launch_tf_noise(e->stream, fb_tf_rnd(seed, stream, epoch, utt), replica, stage, i0, n, tmp.as<float>());
+  hipError_t er = hipMemcpyAsync(z, tmp.p, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, e->stream);
+  if (er == hipSuccess) er = hipStreamSynchronize(e->stream);
+  tmp.release();
+  if (er != hipSuccess) return fb_fail(FB_E_HIP, "noise dump failed: %s", hipGetErrorString(er));
+  return FB_OK;
+}
+
+extern "C" int fb_debug_input_transform_eot(fb_engine *e, const int16_t *wav, const int64_t *off, int B, int r, uint64_t seed,
+                                            uint32_t stream, uint32_t epoch, int16_t *out) {
+  if (!e || !wav || !off || !out || B <= 0 || r < 1 || r > 32 || (int64_t)B * r > 65535) return fb_fail(FB_E_ARG, "bad argument");
+  if (off[0] != 0) return fb_fail(FB_E_ARG, "off[0] must be 0");
+  int64_t n_max = 0;
+  std::vector<int64_t> out_off((size_t)B * r + 1, 0);
+  for (int b = 0; b < B; ++b) {
+    const int64_t n = off[b + 1] - off[b];
+    if (n <= 0) return fb_fail(FB_E_ARG, "utterance %d is empty", b);
+    if (n > 0x7fffffffLL) return fb_fail(FB_E_LIMIT, "utterance %d longer than 2^31 samples", b);
+    n_max = std::max(n_max, n);
+    for (int j = 0; j < r; ++j) out_off[(size_t)b * r + j + 1] = out_off[(size_t)b * r + j] + n;
+  }
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  e->cached_B = -1;  // the scoring batch layout no longer describes e->wav / e->wav_off
+  e->bench_it = -1;
+  const size_t bytes = sizeof(int16_t) * (size_t)off[B];
+  DevBuf d_out_off;
+  FBCHK(e->wav.ensure(bytes));
+  FBCHK(e->wav_tf.ensure(bytes * r));
+  FBCHK(e->wav_off.ensure(sizeof(int64_t) * (B + 1)));
+  FBCHK(d_out_off.ensure(sizeof(int64_t) * out_off.size()));
+  int rc = h2d(e, e->wav.p, wav, bytes);
+  if (rc == FB_OK) rc = h2d(e, e->wav_off.p, off, sizeof(int64_t) * (B + 1));
+  if (rc == FB_OK) rc = h2d(e, d_out_off.p, out_off.data(), sizeof(int64_t) * out_off.size());
+  if (rc == FB_OK && tf_noise_stages(e->tf, true) > 0) rc = e->tf_power.ensure(sizeof(unsigned long long) * (size_t)B);
+  if (rc == FB_OK) {
+    FbTfRnd rn = fb_tf_rnd(seed, stream, epoch, 0);
+    rn.r = r;
+    if (tf_noise_stages(e->tf, true) > 0) {
+      if (fb_launch_tf_power(e->stream, e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), B, n_max,
+                             e->tf_power.as<unsigned long long>(), nullptr) != hipSuccess)
+        rc = fb_fail(FB_E_HIP, "zeroing the power words failed");
+      rn.power = e->tf_power.as<unsigned long long>();
+    }
+    fb_launch_input_transform_rnd(e->stream, e->tf, e->tf_taps.as<double>(), e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), B, n_max,
+                                  e->wav_tf.as<int16_t>(), d_out_off.as<int64_t>(), rn, nullptr);
+    if (hipGetLastError() != hipSuccess) rc = fb_fail(FB_E_HIP, "the transform launch failed");
+  }
+  if (rc == FB_OK) rc = d2h(e, out, e->wav_tf.p, bytes * r);
+  const int rs = sync_stream(e);
+  d_out_off.release();
+  return rc != FB_OK ? rc : rs;
 }
 
 extern "C" int fb_set_dither_seed(fb_engine *e, uint64_t seed) {
@@ -3115,7 +3252,12 @@ extern "C" int fb_bench_nes(fb_engine *e, const fb_nes_params *p, const double *
       return fb_fail(FB_E_STATE, "fb_bench_nes(warmup < 0): no attack of this shape is resident on the engine");
     warmup = 0;
   } else {
-    FBCHK(prepare_nes_batch(e, N, B));
+    if ((int64_t)B * e->eot > 65535) return fb_fail(FB_E_LIMIT, "(samples_per_draw + 1) * eot rows: a scoring batch takes up to 65535");
+    FBCHK(prepare_nes_batch(e, N, B * e->eot));
+    if (e->eot > 1) {
+      FBCHK(e->eot_sc.ensure(sizeof(double) * (size_t)B * e->eot * (size_t)std::max(fb_num_speakers(e), 1)));
+      FBCHK(e->eot_l.ensure(sizeof(double) * (size_t)B * e->eot));
+    }
     FBCHK(ensure_nes_buffers(e, N, B));
     FBCHK(attack_start(e, audio, N, half, nullptr));
     e->bench_it = 0;
@@ -3145,7 +3287,7 @@ extern "C" int fb_bench_nes(fb_engine *e, const fb_nes_params *p, const double *
   *ms_total = (double)ms;
   {
     int r = 0;
-    HIPCHK(hipMemcpy(&r, e->row_off.as<int>() + B, sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&r, e->row_off.as<int>() + B * e->eot, sizeof(int), hipMemcpyDeviceToHost));
     vrows = r;
   }
   if (ms_gmm) *ms_gmm = gmm_ms;

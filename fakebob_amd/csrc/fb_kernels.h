@@ -46,8 +46,8 @@ void fb_launch_dither_noise(hipStream_t s, const FbDitherKey &dk, int t0, int n_
 #define FB_TF_MAX_STAGES 8
 #define FB_TF_MAX_HALO 1024   // largest sum of the stages' radii
 #define FB_TF_TILE 4096       // output samples of one workgroup
-// the chain as the kernel takes it (by value): H = the sum of the radii, k[s] = the stage's parameter (q, k or L),
-// tap_off[s] = where a FIR stage's taps start in the taps buffer
+// the chain as the kernel takes it (by value): H = the sum of the radii, k[s] = the stage's parameter (q, k, L or the
+// noise mode), tap_off[s] = where a FIR stage's taps (a noise stage's s or rho) start in the taps buffer
 struct FbTfChain {
   int n, H;
   int kind[FB_TF_MAX_STAGES], k[FB_TF_MAX_STAGES], tap_off[FB_TF_MAX_STAGES];
@@ -56,7 +56,29 @@ struct FbTfChain {
 // honours `stop` (nullable) like the MFCC kernels.  ch.n == 0 copies.
 void fb_launch_input_transform(hipStream_t s, const FbTfChain &ch, const double *taps, const int16_t *wav,
                                const int64_t *wav_off, int B, int64_t n_max, int16_t *out, const int *stop);
-size_t fb_input_transform_lds_bytes(const FbTfChain &ch);
+size_t fb_input_transform_lds_bytes(const FbTfChain &ch, bool rnd = false);
+// What a randomised / replicating transform launch carries of the noise RNG contract (include/fakebob_hip.h): the Philox
+// key (seed_lo ^ "NOIS", seed_hi ^ stream), counter word 3, the row of the batch's first utterance within the call, the
+// replicas written per utterance (fb_set_eot) and the per-utterance sums of squares k_tf_power left (SNR stages; else null)
+struct FbTfRnd {
+  uint32_t k0, k1, epoch, utt0;
+  int r;
+  const unsigned long long *power;
+};
+static inline FbTfRnd fb_tf_rnd(uint64_t seed, uint32_t stream, uint32_t epoch, uint32_t utt0) {
+  return FbTfRnd{(uint32_t)seed ^ 0x4E4F4953u, (uint32_t)(seed >> 32) ^ stream, epoch, utt0, 1, nullptr};
+}
+// power[u] = the exact sum of squares of utterance u of wav (zeroed here, then one integer atomic per tile); honours `stop`
+// returns the memset's status
+hipError_t fb_launch_tf_power(hipStream_t s, const int16_t *wav, const int64_t *wav_off, int B, int64_t n_max,
+                              unsigned long long *power, const int *stop);
+// the chain with FB_TF_NOISE stages and / or rn.r replicas per utterance: utterance u of wav (wav_off[B + 1]) is read once
+// per tile and replica j written at out_off[u * rn.r + j] of out; an empty chain is a replicating copy
+void fb_launch_input_transform_rnd(hipStream_t s, const FbTfChain &ch, const double *taps, const int16_t *wav,
+                                   const int64_t *wav_off, int B, int64_t n_max, int16_t *out, const int64_t *out_off,
+                                   const FbTfRnd &rn, const int *stop);
+// z[n] = the normals a noise stage adds to samples i0 .. i0 + n - 1 of utterance rn.utt0 (fb_debug_tf_noise)
+void fb_launch_tf_noise(hipStream_t s, const FbTfRnd &rn, int replica, int stage, int64_t i0, int64_t n, float *z);
 
 // ---- NES ----------------------------------------------------------------
 // q[b][n] = int16((adver[n] + sigma*noise_b[n]) * 2^15), b in [0, 2*half]; column 0 is the
@@ -119,6 +141,14 @@ void fb_launch_loss(hipStream_t s, const float *raw, const int *tv, int B, int M
                     double adver_thresh, int target, int true_label, const double *dist_part,
                     int n_dist_part, double *scores, double *loss, FbNesDev *out, FbCtlDev *ctl = nullptr,
                     double *trace = nullptr, int it = 0);
+// the expectation-over-transformation loss (fb_set_eot, r > 1; k_loss_eot): raw[B * r][M] and tv[B * r] of the replicated
+// batch (replica j of NES row b = row b * r + j) -> per-replica scores rep_sc[B * r][S] and losses rep_l[B * r] by the
+// operations of k_loss, their float64 means over j ascending in scores[B][S] / loss[B], then k_loss's tail on those B rows
+void fb_launch_loss_eot(hipStream_t s, const double *raw, const int *tv, int B, int r, int M, int task, int znorm_all,
+                        int attack_type, const double *z_mean, const double *z_std, double threshold,
+                        double adver_thresh, int target, int true_label, const double *dist_part, int n_dist_part,
+                        double *rep_sc, double *rep_l, double *scores, double *loss, FbNesDev *out, FbCtlDev *ctl,
+                        double *trace, int it);
 // k_grad_update (iteration `next_iter - 1`) + k_perturb (iteration next_iter) in one launch; device-controlled attacks
 // with Philox noise and half <= FB_FUSE_MAX_HALF only.  Returns the number of distance partials written.
 #define FB_FUSE_MAX_HALF 40

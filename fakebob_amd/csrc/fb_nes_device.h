@@ -100,146 +100,131 @@ __device__ __forceinline__ double fb_ld_raw(const TR *p) {
     return (double)*p;
   }
 }
+// The per-row part of the loss: the system scores of row b of raw[][M] -- written to sc[S] and, when gsc is not null, to
+// gsc[S] as well -- and FakeBob.loss_fn of them.  Shared by fb_loss_body (one row per NES sample) and k_loss_eot (one row per
+// replica of a NES sample): the same operations on the same values in the same order.
 // TR: the element type of raw[] -- double for this library's systems, float or double for a foreign model's scores
 // read straight from its device buffer (fb_attack_dev)
-template <bool SMALL, bool FUSED, typename TR = double>
-__device__ __forceinline__ void fb_loss_body(const TR *__restrict__ raw, const int *__restrict__ tv,
-                                              int B, int M, int task, int znorm_all, int attack_type,
-                                              const double *__restrict__ z_mean,
-                                              const double *__restrict__ z_std, double threshold,
-                                              double adver_thresh, int target, int true_label,
-                                              const double *__restrict__ dist_part, int n_dist_part,
-                                              double *__restrict__ scores, double *__restrict__ loss,
-                                              FbNesDev *__restrict__ out, FbCtlDev *__restrict__ ctl,
-                                              double *__restrict__ trace, int it, double *__restrict__ s_lv,
-                                              double *__restrict__ s_sc, const int pub_seq = 0,
-                                              const int lv_cap = FB_LOSS_LDS, const int sc_cap = FB_SC_LDS) {
-  // pub_seq != 0: workgroups of the SAME launch wait for this body's results (k_gmm_finalize_loss_update's update part):
-  // the losses, the step size and the stop flag go out as agent-scope (write-through) stores, and when they are complete
-  // ctl->pub_seq = pub_seq tells the pollers -- no device-wide fence
-  const int S = (task == FB_TASK_CSI || znorm_all) ? M : M - 1;
-  __shared__ int s_errw[16];
-  // The decisions at the end are one thread's work: everything it needs from global memory is requested HERE and
-  // arrives while the block computes the losses; nothing below waits for it before it is used (no barrier up here: the
-  // "no voiced frames" flag is reduced over the waves at the end instead of being initialised in LDS first).  Read
-  // where they were used, the control block, the window of recent losses, the raw scores (a run-time loop: one L2
-  // round trip per model) and the losses were ~20 dependent round trips, 9 of the fused kernel's 18 us.
-  // s_lv[FB_LOSS_LDS]: the losses of this iteration (B <= FB_LOSS_LDS; otherwise read back from `loss`); s_sc[FB_SC_LDS]: the
-  // scores while the loss is formed from them (B S <= FB_SC_LDS; otherwise in `scores`) -- LDS of the caller (static
-  // arrays in the small kernels, a piece of the dynamic allocation in the solve kernels' tail)
-  constexpr int FB_LS_LOCAL = 8;
-  const bool sc_lds = (size_t)B * S <= (size_t)sc_cap;
-  const double dist_first = (int)threadIdx.x < n_dist_part ? dist_part[threadIdx.x] : 0.0;  // in flight with the rest
-  FbCtlDev c = {};
-  double lsv[FB_LS_LOCAL] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  if (threadIdx.x == 0 && ctl) c = *ctl;
-  int my_err = 0;
-  for (int b = threadIdx.x; b < B; b += blockDim.x) {
-    if (tv && tv[b] <= 0) my_err = b + 1 > my_err ? b + 1 : my_err;
-    constexpr int FB_RAW_LOCAL = 8;  // all raw scores of the utterance in one batch of loads
-    double rv[FB_RAW_LOCAL];
-    if (M <= FB_RAW_LOCAL) {
+template <bool FUSED, typename TR>
+__device__ __forceinline__ double fb_loss_row(const TR *__restrict__ raw, const int b, const int M, const int S, const int task,
+                                              const int znorm_all, const int attack_type, const double *__restrict__ z_mean,
+                                              const double *__restrict__ z_std, const double threshold,
+                                              const double adver_thresh, const int target, const int true_label,
+                                              double *__restrict__ sc, double *__restrict__ gsc) {
+  constexpr int FB_RAW_LOCAL = 8;  // all raw scores of the utterance in one batch of loads
+  double rv[FB_RAW_LOCAL];
+  if (M <= FB_RAW_LOCAL) {
 #pragma unroll
-      for (int m = 0; m < FB_RAW_LOCAL; ++m) {
-        rv[m] = fb_ld_raw<FUSED>(raw + (size_t)b * M + (m < M ? m : M - 1));
-      }
+    for (int m = 0; m < FB_RAW_LOCAL; ++m) {
+      rv[m] = fb_ld_raw<FUSED>(raw + (size_t)b * M + (m < M ? m : M - 1));
     }
-    auto r = [&](int m) -> double {
-      if (M <= FB_RAW_LOCAL) {
-        double v = rv[0];
-#pragma unroll
-        for (int q = 1; q < FB_RAW_LOCAL; ++q) v = m == q ? rv[q] : v;
-        return v;
-      }
-      return fb_ld_raw<FUSED>(raw + (size_t)b * M + m);
-    };
-    double *sc = sc_lds ? s_sc + (size_t)b * S : scores + (size_t)b * S;
-#ifdef FB_FIN_STAMP
-    if (rv[0] == 12345.678) FN_STAMP(11); else FN_STAMP(11);  // (raw scores arrived)
-#endif
-    double l;
+  }
+  auto r = [&](int m) -> double {
     if (M <= FB_RAW_LOCAL) {
-      // at most eight scores: they stay in registers (the general path below writes them to LDS and reads every one back
-      // through run-time loops -- a dozen dependent LDS round trips in the one workgroup everybody waits for); the same
-      // operations on the same values in the same order
-      double scr[FB_RAW_LOCAL];
-      if (task == FB_TASK_CSI || znorm_all) {
-        double zm[FB_RAW_LOCAL], zs[FB_RAW_LOCAL];
+      double v = rv[0];
 #pragma unroll
-        for (int m = 0; m < FB_RAW_LOCAL; ++m) { zm[m] = z_mean[m < M ? m : M - 1]; zs[m] = z_std[m < M ? m : M - 1]; }
+      for (int q = 1; q < FB_RAW_LOCAL; ++q) v = m == q ? rv[q] : v;
+      return v;
+    }
+    return fb_ld_raw<FUSED>(raw + (size_t)b * M + m);
+  };
+#ifdef FB_FIN_STAMP
+  if (rv[0] == 12345.678) FN_STAMP(11); else FN_STAMP(11);  // (raw scores arrived)
+#endif
+  double l;
+  if (M <= FB_RAW_LOCAL) {
+    // at most eight scores: they stay in registers (the general path below writes them to LDS and reads every one back
+    // through run-time loops -- a dozen dependent LDS round trips in the one workgroup everybody waits for); the same
+    // operations on the same values in the same order
+    double scr[FB_RAW_LOCAL];
+    if (task == FB_TASK_CSI || znorm_all) {
+      double zm[FB_RAW_LOCAL], zs[FB_RAW_LOCAL];
 #pragma unroll
-        for (int m = 0; m < FB_RAW_LOCAL; ++m) scr[m] = __ddiv_rn(__dsub_rn(rv[m], zm[m]), zs[m]);
-      } else {
+      for (int m = 0; m < FB_RAW_LOCAL; ++m) { zm[m] = z_mean[m < M ? m : M - 1]; zs[m] = z_std[m < M ? m : M - 1]; }
 #pragma unroll
-        for (int m = 0; m < FB_RAW_LOCAL; ++m) scr[m] = __dsub_rn(rv[m + 1 < FB_RAW_LOCAL ? m + 1 : FB_RAW_LOCAL - 1], rv[0]);
+      for (int m = 0; m < FB_RAW_LOCAL; ++m) scr[m] = __ddiv_rn(__dsub_rn(rv[m], zm[m]), zs[m]);
+    } else {
+#pragma unroll
+      for (int m = 0; m < FB_RAW_LOCAL; ++m) scr[m] = __dsub_rn(rv[m + 1 < FB_RAW_LOCAL ? m + 1 : FB_RAW_LOCAL - 1], rv[0]);
+    }
+#pragma unroll
+    for (int m = 0; m < FB_RAW_LOCAL; ++m)
+      if (m < S) {
+        sc[m] = scr[m];
+        if (gsc) gsc[m] = scr[m];
       }
+    auto pick = [&](int i) -> double {
+      double v = scr[0];
+#pragma unroll
+      for (int q = 1; q < FB_RAW_LOCAL; ++q) v = i == q ? scr[q] : v;
+      return v;
+    };
+    auto max_but = [&](int skip) -> double {   // max over m < S, m != skip, in index order
+      double om = -INFINITY;
 #pragma unroll
       for (int m = 0; m < FB_RAW_LOCAL; ++m)
-        if (m < S) {
-          sc[m] = scr[m];
-          if (sc_lds) scores[(size_t)b * S + m] = scr[m];
-        }
-      auto pick = [&](int i) -> double {
-        double v = scr[0];
-#pragma unroll
-        for (int q = 1; q < FB_RAW_LOCAL; ++q) v = i == q ? scr[q] : v;
-        return v;
-      };
-      auto max_but = [&](int skip) -> double {   // max over m < S, m != skip, in index order
-        double om = -INFINITY;
-#pragma unroll
-        for (int m = 0; m < FB_RAW_LOCAL; ++m)
-          if (m < S && m != skip) om = scr[m] > om ? scr[m] : om;
-        return om;
-      };
-      if (task == FB_TASK_SV) {
-        l = __dsub_rn(__dadd_rn(threshold, adver_thresh), scr[0]);  // FAKEBOB.py:297
-      } else if (task == FB_TASK_OSI && attack_type == FB_UNTARGETED) {
-        l = __dsub_rn(__dadd_rn(threshold, adver_thresh), max_but(-1));  // :269
-      } else if (task == FB_TASK_OSI) {
-        const double om = max_but(target);
-        const double mx = om > threshold ? om : threshold;
-        l = __dsub_rn(__dadd_rn(mx, adver_thresh), pick(target));  // :262
-      } else if (attack_type == FB_TARGETED) {
-        l = __dsub_rn(__dadd_rn(max_but(target), adver_thresh), pick(target));  // :281
-      } else {
-        l = __dsub_rn(__dadd_rn(pick(true_label), adver_thresh), max_but(true_label));  // :291
-      }
+        if (m < S && m != skip) om = scr[m] > om ? scr[m] : om;
+      return om;
+    };
+    if (task == FB_TASK_SV) {
+      l = __dsub_rn(__dadd_rn(threshold, adver_thresh), scr[0]);  // FAKEBOB.py:297
+    } else if (task == FB_TASK_OSI && attack_type == FB_UNTARGETED) {
+      l = __dsub_rn(__dadd_rn(threshold, adver_thresh), max_but(-1));  // :269
+    } else if (task == FB_TASK_OSI) {
+      const double om = max_but(target);
+      const double mx = om > threshold ? om : threshold;
+      l = __dsub_rn(__dadd_rn(mx, adver_thresh), pick(target));  // :262
+    } else if (attack_type == FB_TARGETED) {
+      l = __dsub_rn(__dadd_rn(max_but(target), adver_thresh), pick(target));  // :281
     } else {
-      if (task == FB_TASK_CSI || znorm_all) {
-        // gmm_ubm_CSI.py:93; ivector_PLDA_OSI.py:119 / _CSI.py:118 / _SV.py:85
-        for (int m = 0; m < M; ++m) sc[m] = __ddiv_rn(__dsub_rn(r(m), z_mean[m]), z_std[m]);
-      } else {
-        const double r_ubm = r(0);
-        for (int m = 0; m < S; ++m) sc[m] = __dsub_rn(r(1 + m), r_ubm);  // gmm_ubm_OSI.py:89, gmm_ubm_SV.py:77
-      }
-      if (sc_lds) for (int m = 0; m < S; ++m) scores[(size_t)b * S + m] = sc[m];
-      if (task == FB_TASK_SV) {
-        l = __dsub_rn(__dadd_rn(threshold, adver_thresh), sc[0]);  // FAKEBOB.py:297
-      } else if (task == FB_TASK_OSI && attack_type == FB_UNTARGETED) {
-        double mx = -INFINITY;
-        for (int m = 0; m < S; ++m) mx = sc[m] > mx ? sc[m] : mx;
-        l = __dsub_rn(__dadd_rn(threshold, adver_thresh), mx);  // :269
-      } else if (task == FB_TASK_OSI) {
-        double om = -INFINITY;
-        for (int m = 0; m < S; ++m) if (m != target) om = sc[m] > om ? sc[m] : om;
-        double mx = om > threshold ? om : threshold;
-        l = __dsub_rn(__dadd_rn(mx, adver_thresh), sc[target]);  // :262
-      } else if (attack_type == FB_TARGETED) {
-        double om = -INFINITY;
-        for (int m = 0; m < S; ++m) if (m != target) om = sc[m] > om ? sc[m] : om;
-        l = __dsub_rn(__dadd_rn(om, adver_thresh), sc[target]);  // :281
-      } else {
-        double om = -INFINITY;
-        for (int m = 0; m < S; ++m) if (m != true_label) om = sc[m] > om ? sc[m] : om;
-        l = __dsub_rn(__dadd_rn(sc[true_label], adver_thresh), om);  // :291
-      }
+      l = __dsub_rn(__dadd_rn(pick(true_label), adver_thresh), max_but(true_label));  // :291
     }
-    if (pub_seq) __hip_atomic_store(reinterpret_cast<unsigned long long *>(loss + b), (unsigned long long)__double_as_longlong(l),
-                                    FB_XCH_ST, __HIP_MEMORY_SCOPE_AGENT);
-    else loss[b] = l;
-    if (b < lv_cap) s_lv[b] = l;
+  } else {
+    if (task == FB_TASK_CSI || znorm_all) {
+      // gmm_ubm_CSI.py:93; ivector_PLDA_OSI.py:119 / _CSI.py:118 / _SV.py:85
+      for (int m = 0; m < M; ++m) sc[m] = __ddiv_rn(__dsub_rn(r(m), z_mean[m]), z_std[m]);
+    } else {
+      const double r_ubm = r(0);
+      for (int m = 0; m < S; ++m) sc[m] = __dsub_rn(r(1 + m), r_ubm);  // gmm_ubm_OSI.py:89, gmm_ubm_SV.py:77
+    }
+    if (gsc) for (int m = 0; m < S; ++m) gsc[m] = sc[m];
+    if (task == FB_TASK_SV) {
+      l = __dsub_rn(__dadd_rn(threshold, adver_thresh), sc[0]);  // FAKEBOB.py:297
+    } else if (task == FB_TASK_OSI && attack_type == FB_UNTARGETED) {
+      double mx = -INFINITY;
+      for (int m = 0; m < S; ++m) mx = sc[m] > mx ? sc[m] : mx;
+      l = __dsub_rn(__dadd_rn(threshold, adver_thresh), mx);  // :269
+    } else if (task == FB_TASK_OSI) {
+      double om = -INFINITY;
+      for (int m = 0; m < S; ++m) if (m != target) om = sc[m] > om ? sc[m] : om;
+      double mx = om > threshold ? om : threshold;
+      l = __dsub_rn(__dadd_rn(mx, adver_thresh), sc[target]);  // :262
+    } else if (attack_type == FB_TARGETED) {
+      double om = -INFINITY;
+      for (int m = 0; m < S; ++m) if (m != target) om = sc[m] > om ? sc[m] : om;
+      l = __dsub_rn(__dadd_rn(om, adver_thresh), sc[target]);  // :281
+    } else {
+      double om = -INFINITY;
+      for (int m = 0; m < S; ++m) if (m != true_label) om = sc[m] > om ? sc[m] : om;
+      l = __dsub_rn(__dadd_rn(sc[true_label], adver_thresh), om);  // :291
+    }
   }
+  return l;
+}
+
+constexpr int FB_LS_LOCAL = 8;  // plateau windows of up to this many losses are kept in registers
+// What follows the per-row losses, on the B rows whose losses stand in s_lv / loss and whose scores in s_sc / scores:
+// numpy's pairwise mean of loss[1:], the stop rule on loss[0], the plateau rule, the outputs and the trace row.  c: thread
+// 0's copy of the control block, requested before the rows were computed; my_err: the thread's "no voiced frames" row + 1.
+template <bool SMALL>
+__device__ __forceinline__ void fb_loss_tail(const int B, const int S, const double *__restrict__ dist_part, const int n_dist_part,
+                                             const double dist_first, const FbCtlDev &c, int my_err,
+                                             double *__restrict__ scores, double *__restrict__ loss, FbNesDev *__restrict__ out,
+                                             FbCtlDev *__restrict__ ctl, double *__restrict__ trace, const int it,
+                                             double *__restrict__ s_lv, double *__restrict__ s_sc, const int pub_seq,
+                                             const int lv_cap, const bool sc_lds) {
+  __shared__ int s_errw[16];
+  double lsv[FB_LS_LOCAL] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   // (the window of recent losses hangs off a pointer IN the control block: requested here, behind the raw scores, it
   //  arrives during the barrier and the mean below; requested at the top it put a second round trip in front of them)
   if (threadIdx.x == 0 && ctl && c.plateau_length > 0 && c.plateau_length <= FB_LS_LOCAL) {
@@ -382,6 +367,51 @@ __device__ __forceinline__ void fb_loss_body(const TR *__restrict__ raw, const i
       }
     }
   }
+}
+
+// TR: the element type of raw[] -- double for this library's systems, float or double for a foreign model's scores
+// read straight from its device buffer (fb_attack_dev)
+template <bool SMALL, bool FUSED, typename TR = double>
+__device__ __forceinline__ void fb_loss_body(const TR *__restrict__ raw, const int *__restrict__ tv,
+                                              int B, int M, int task, int znorm_all, int attack_type,
+                                              const double *__restrict__ z_mean,
+                                              const double *__restrict__ z_std, double threshold,
+                                              double adver_thresh, int target, int true_label,
+                                              const double *__restrict__ dist_part, int n_dist_part,
+                                              double *__restrict__ scores, double *__restrict__ loss,
+                                              FbNesDev *__restrict__ out, FbCtlDev *__restrict__ ctl,
+                                              double *__restrict__ trace, int it, double *__restrict__ s_lv,
+                                              double *__restrict__ s_sc, const int pub_seq = 0,
+                                              const int lv_cap = FB_LOSS_LDS, const int sc_cap = FB_SC_LDS) {
+  // pub_seq != 0: workgroups of the SAME launch wait for this body's results (k_gmm_finalize_loss_update's update part):
+  // the losses, the step size and the stop flag go out as agent-scope (write-through) stores, and when they are complete
+  // ctl->pub_seq = pub_seq tells the pollers -- no device-wide fence
+  const int S = (task == FB_TASK_CSI || znorm_all) ? M : M - 1;
+  // The decisions at the end are one thread's work: everything it needs from global memory is requested HERE and
+  // arrives while the block computes the losses; nothing below waits for it before it is used (no barrier up here: the
+  // "no voiced frames" flag is reduced over the waves at the end instead of being initialised in LDS first).  Read
+  // where they were used, the control block, the window of recent losses, the raw scores (a run-time loop: one L2
+  // round trip per model) and the losses were ~20 dependent round trips, 9 of the fused kernel's 18 us.
+  // s_lv[FB_LOSS_LDS]: the losses of this iteration (B <= FB_LOSS_LDS; otherwise read back from `loss`); s_sc[FB_SC_LDS]: the
+  // scores while the loss is formed from them (B S <= FB_SC_LDS; otherwise in `scores`) -- LDS of the caller (static
+  // arrays in the small kernels, a piece of the dynamic allocation in the solve kernels' tail)
+  const bool sc_lds = (size_t)B * S <= (size_t)sc_cap;
+  const double dist_first = (int)threadIdx.x < n_dist_part ? dist_part[threadIdx.x] : 0.0;  // in flight with the rest
+  FbCtlDev c = {};
+  if (threadIdx.x == 0 && ctl) c = *ctl;
+  int my_err = 0;
+  for (int b = threadIdx.x; b < B; b += blockDim.x) {
+    if (tv && tv[b] <= 0) my_err = b + 1 > my_err ? b + 1 : my_err;
+    double *sc = sc_lds ? s_sc + (size_t)b * S : scores + (size_t)b * S;
+    const double l = fb_loss_row<FUSED>(raw, b, M, S, task, znorm_all, attack_type, z_mean, z_std, threshold, adver_thresh, target,
+                                        true_label, sc, sc_lds ? scores + (size_t)b * S : nullptr);
+    if (pub_seq) __hip_atomic_store(reinterpret_cast<unsigned long long *>(loss + b), (unsigned long long)__double_as_longlong(l),
+                                    FB_XCH_ST, __HIP_MEMORY_SCOPE_AGENT);
+    else loss[b] = l;
+    if (b < lv_cap) s_lv[b] = l;
+  }
+  fb_loss_tail<SMALL>(B, S, dist_part, n_dist_part, dist_first, c, my_err, scores, loss, out, ctl, trace, it, s_lv, s_sc, pub_seq,
+                      lv_cap, sc_lds);
 }
 
 // k_grad_update (momentum sign step of iteration `iter`) + k_perturb (the batch of iteration iter + 1) for the 256

@@ -15,6 +15,15 @@
 //
 // LDS: 2 * (FB_TF_TILE + 2 H + 4) int16 = 16 KB for a radius-0 chain, 24 KB at the largest halo (H = 1024) -- requested per
 // launch, so that a workgroup fits beside another attack's k_gmm_fx2w workgroup (101 KB) on a compute unit.
+//
+// RND (the second instantiation): the chain holds an FB_TF_NOISE stage, or the batch is replicated for an
+// expectation-over-transformation attack (fb_set_eot, r > 1).  The tile is loaded ONCE into a third LDS buffer and the
+// chain runs r times from it, replica j into row u * r + j of the output, its noise stages drawing from replica j's
+// stream (the "Noise RNG contract" of fakebob_hip.h).  A sample's normal depends on its absolute index only, so the halo
+// positions two neighbouring workgroups both compute get the same value.  An SNR stage scales by the utterance's power,
+// which k_tf_power -- the launch in front -- summed: nothing is exchanged inside a kernel here either.  The instantiation
+// without RND is the kernel as it was: a chain without noise and without replication runs the same code as before.
+#include "fb_device.h"
 #include "fb_kernels.h"
 
 #define TF_THREADS 256
@@ -51,10 +60,26 @@ static __device__ __forceinline__ int tf_median(const int16_t *w0, int k) {
   return med;
 }
 
+// FB_TF_NOISE: the standard normals of samples 4 q .. 4 q + 3 of utterance `utt` for (stage, replica) at the launch's point
+// of the noise RNG contract
+static __device__ __forceinline__ void tf_noise4(const FbTfRnd &rn, uint32_t utt, int stage, int replica, uint32_t q, float z[4]) {
+  uint32_t r[4];
+  fb_philox4x32_10(q, (uint32_t)(stage + 8 * replica), rn.utt0 + utt, rn.epoch, rn.k0, rn.k1, r);
+  fb_box_muller_sel(r[0], r[1], z[0], z[1]);
+  fb_box_muller_sel(r[2], r[3], z[2], z[3]);
+}
+// ... and the stage's scale: taps[0] itself (absolute mode) or sqrt(E / n / rho), E the utterance's exact sum of squares
+static __device__ __forceinline__ double tf_noise_scale(int mode, double t0, unsigned long long E, int64_t n) {
+  if (mode == 0) return t0;
+  return __dsqrt_rn(__ddiv_rn(__ddiv_rn((double)E, (double)n), t0));
+}
+
+template <bool RND>
 __global__ __launch_bounds__(TF_THREADS) void k_input_transform(FbTfChain ch, const double *__restrict__ taps,
                                                                 const int16_t *__restrict__ wav,
                                                                 const int64_t *__restrict__ wav_off,
-                                                                int16_t *__restrict__ out, const int *__restrict__ stop) {
+                                                                int16_t *__restrict__ out, const int *__restrict__ stop,
+                                                                const int64_t *__restrict__ out_off, FbTfRnd rn) {
   extern __shared__ int16_t tf_lds[];
   if (stop && *stop) return;
   const int u = blockIdx.y;
@@ -64,19 +89,50 @@ __global__ __launch_bounds__(TF_THREADS) void k_input_transform(FbTfChain ch, co
   if (t0 >= n) return;  // (the grid is sized for the longest utterance of the batch)
   const int H = ch.H, W = FB_TF_TILE + 2 * H;
   int16_t *a = tf_lds, *b = tf_lds + W + TF_PAD;
+  int16_t *const src = RND ? tf_lds + 2 * (W + TF_PAD) : a;  // RND: the tile as loaded, kept for every replica
   const int tid = threadIdx.x;
   // LDS position p of either buffer <-> sample g0 + p of the utterance
   const int64_t g0 = t0 - H;
   for (int p = tid; p < W + TF_PAD; p += TF_THREADS) {
     const int64_t i = g0 + p;
-    a[p] = (p < W && i >= 0 && i < n) ? wav[base + i] : (int16_t)0;
-    if (p >= W) b[p] = 0;
+    src[p] = (p < W && i >= 0 && i < n) ? wav[base + i] : (int16_t)0;
+    if (p >= W) {
+      b[p] = 0;
+      if (RND) a[p] = 0;
+    }
   }
   __syncthreads();
+  const int reps = RND ? rn.r : 1;
+  for (int rep = 0; rep < reps; ++rep) {
+  if (RND) {
+    a = src;
+    b = tf_lds;  // the first stage reads src and writes the first working buffer
+  }
   int lo = 0, hi = W;  // positions [lo, hi) of `a` hold the signal after the stages run so far
   for (int s = 0; s < ch.n; ++s) {
     const int kind = ch.kind[s], k = ch.k[s];
-    if (kind == FB_TF_FIR) {
+    if (RND && kind == FB_TF_NOISE) {
+      const double sc = tf_noise_scale(k, taps[ch.tap_off[s]], k ? rn.power[u] : 0ull, n);
+      // a lane owns the four samples of one Philox call: groups of four by ABSOLUTE index (i >> 2), whatever the tile
+      const int64_t i_first = ((g0 + lo) >> 2) << 2;  // (arithmetic shift: rounds toward -inf for the halo in front of sample 0)
+      for (int64_t i4 = i_first + 4 * tid; i4 < g0 + hi; i4 += 4 * TF_THREADS) {
+        float z[4] = {0.f, 0.f, 0.f, 0.f};
+        if (i4 + 3 >= 0 && i4 < n) tf_noise4(rn, (uint32_t)u, s, rep, (uint32_t)(i4 >> 2), z);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int64_t i = i4 + q;
+          const int p = (int)(i - g0);
+          if (p >= lo && p < hi) {
+            int y = 0;
+            if (i >= 0 && i < n) {
+              const double v = __dadd_rn((double)a[p], __dmul_rn(sc, (double)z[q]));
+              y = (int)fmin(fmax(rint(v), -32768.0), 32767.0);
+            }
+            b[p] = (int16_t)y;
+          }
+        }
+      }
+    } else if (kind == FB_TF_FIR) {
       const int c = (k - 1) >> 1;
       const double *__restrict__ h = taps + ch.tap_off[s];
       lo += c;
@@ -131,22 +187,96 @@ __global__ __launch_bounds__(TF_THREADS) void k_input_transform(FbTfChain ch, co
       }
     }
     __syncthreads();
-    int16_t *t = a;
-    a = b;
-    b = t;
+    if (RND && s == 0) {  // src stays as loaded: from here on the two working buffers alternate
+      a = b;
+      b = tf_lds + ((a == tf_lds) ? W + TF_PAD : 0);
+    } else {
+      int16_t *t = a;
+      a = b;
+      b = t;
+    }
   }
   // lo == H, hi == H + FB_TF_TILE: the tile
+  const int64_t obase = RND ? out_off[(int64_t)u * reps + rep] : base;
   for (int p = H + tid; p < H + FB_TF_TILE; p += TF_THREADS) {
     const int64_t i = g0 + p;
-    if (i < n) out[base + i] = a[p];
+    if (i < n) out[obase + i] = a[p];
+  }
+  if (RND && rep + 1 < reps) __syncthreads();  // the next replica overwrites the buffers this one's result is read from
   }
 }
 
-size_t fb_input_transform_lds_bytes(const FbTfChain &ch) { return sizeof(int16_t) * 2 * (size_t)(FB_TF_TILE + 2 * ch.H + TF_PAD); }
+// E_u of the noise stage's SNR mode: the exact integer sum of squares of every utterance as it is handed to the chain.
+// One workgroup per (utterance, tile); 64-bit partial sums, one integer atomic per workgroup into the utterance's word
+// (zeroed by the launcher): integer addition is associative, so the result does not depend on the order.  Its only
+// reader is the next launch.
+__global__ __launch_bounds__(TF_THREADS) void k_tf_power(const int16_t *__restrict__ wav, const int64_t *__restrict__ wav_off,
+                                                         unsigned long long *__restrict__ power, const int *__restrict__ stop) {
+  if (stop && *stop) return;
+  const int u = blockIdx.y;
+  const int64_t base = wav_off[u];
+  const int64_t n = wav_off[u + 1] - base;
+  const int64_t t0 = (int64_t)blockIdx.x * FB_TF_TILE;
+  if (t0 >= n) return;
+  const int64_t t1 = t0 + FB_TF_TILE < n ? t0 + FB_TF_TILE : n;
+  unsigned long long acc = 0;
+  for (int64_t i = t0 + threadIdx.x; i < t1; i += TF_THREADS) {
+    const int v = wav[base + i];
+    acc += (unsigned long long)(v * v);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  __shared__ unsigned long long s_part[TF_THREADS / 64];
+  if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long t = 0;
+    for (int w = 0; w < TF_THREADS / 64; ++w) t += s_part[w];
+    atomicAdd(power + u, t);
+  }
+}
+
+// the normals of one (utterance, replica, stage) of the noise contract: z[n] for samples i0 .. i0 + n - 1 (fb_debug_tf_noise)
+__global__ __launch_bounds__(256) void k_tf_noise(FbTfRnd rn, int replica, int stage, int64_t i0, int64_t n, float *__restrict__ z) {
+  const int64_t q0 = i0 >> 2;
+  const int64_t q = q0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (4 * q >= i0 + n) return;
+  float v[4];
+  tf_noise4(rn, 0u, stage, replica, (uint32_t)q, v);
+  for (int k = 0; k < 4; ++k) {
+    const int64_t i = 4 * q + k;
+    if (i >= i0 && i < i0 + n) z[i - i0] = v[k];
+  }
+}
+void fb_launch_tf_noise(hipStream_t s, const FbTfRnd &rn, int replica, int stage, int64_t i0, int64_t n, float *z) {
+  const int64_t quads = ((i0 + n + 3) >> 2) - (i0 >> 2);
+  hipLaunchKernelGGL(k_tf_noise, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, s, rn, replica, stage, i0, n, z);
+}
+
+size_t fb_input_transform_lds_bytes(const FbTfChain &ch, bool rnd) {
+  return sizeof(int16_t) * (rnd ? 3 : 2) * (size_t)(FB_TF_TILE + 2 * ch.H + TF_PAD);
+}
 
 void fb_launch_input_transform(hipStream_t s, const FbTfChain &ch, const double *taps, const int16_t *wav,
                                const int64_t *wav_off, int B, int64_t n_max, int16_t *out, const int *stop) {
   const unsigned tiles = (unsigned)((n_max + FB_TF_TILE - 1) / FB_TF_TILE);
-  hipLaunchKernelGGL(k_input_transform, dim3(tiles > 0 ? tiles : 1, B), dim3(TF_THREADS), fb_input_transform_lds_bytes(ch), s,
-                     ch, taps, wav, wav_off, out, stop);
+  hipLaunchKernelGGL(k_input_transform<false>, dim3(tiles > 0 ? tiles : 1, B), dim3(TF_THREADS), fb_input_transform_lds_bytes(ch, false), s,
+                     ch, taps, wav, wav_off, out, stop, nullptr, FbTfRnd{});
+}
+
+hipError_t fb_launch_tf_power(hipStream_t s, const int16_t *wav, const int64_t *wav_off, int B, int64_t n_max,
+                              unsigned long long *power, const int *stop) {
+  const unsigned tiles = (unsigned)((n_max + FB_TF_TILE - 1) / FB_TF_TILE);
+  const hipError_t er = hipMemsetAsync(power, 0, sizeof(unsigned long long) * (size_t)B, s);
+  if (er != hipSuccess) return er;
+  hipLaunchKernelGGL(k_tf_power, dim3(tiles > 0 ? tiles : 1, B), dim3(TF_THREADS), 0, s, wav, wav_off, power, stop);
+  return hipSuccess;
+}
+
+void fb_launch_input_transform_rnd(hipStream_t s, const FbTfChain &ch, const double *taps, const int16_t *wav,
+                                   const int64_t *wav_off, int B, int64_t n_max, int16_t *out, const int64_t *out_off,
+                                   const FbTfRnd &rn, const int *stop) {
+  const unsigned tiles = (unsigned)((n_max + FB_TF_TILE - 1) / FB_TF_TILE);
+  hipLaunchKernelGGL(k_input_transform<true>, dim3(tiles > 0 ? tiles : 1, B), dim3(TF_THREADS), fb_input_transform_lds_bytes(ch, true), s,
+                     ch, taps, wav, wav_off, out, stop, out_off, rn);
 }

@@ -325,6 +325,70 @@ void fb_launch_loss(hipStream_t s, const float *raw, const int *tv, int B, int M
               dist_part, n_dist_part, scores, loss, out, ctl, trace, it);
 }
 
+// The expectation-over-transformation loss (fb_set_eot, r > 1): the batch the front end scored holds r replicas of every NES
+// row -- replica j of row b is row b * r + j, scored under its own draw of the victim's randomness (noise stages, dither).
+// System scores and loss_fn per replica row by fb_loss_row, the operations of k_loss; then per NES row
+//   loss[b] = (l[b][0] + l[b][1] + ... + l[b][r - 1]) / r,   scores[b][s] likewise,
+// float64, j ascending, one rounding per addition and one for the division; then k_loss's tail (fb_loss_tail) on the B
+// averaged rows.  "No voiced frames" is raised for NES row b if any of its replicas has none.  One workgroup, as k_loss.
+template <bool SMALL>
+__global__ __launch_bounds__(256) void k_loss_eot(const double *__restrict__ raw, const int *__restrict__ tv, int B, int r, int M,
+                                                  int task, int znorm_all, int attack_type, const double *__restrict__ z_mean,
+                                                  const double *__restrict__ z_std, double threshold, double adver_thresh,
+                                                  int target, int true_label, const double *__restrict__ dist_part,
+                                                  int n_dist_part, double *__restrict__ rep_sc, double *__restrict__ rep_l,
+                                                  double *__restrict__ scores, double *__restrict__ loss,
+                                                  FbNesDev *__restrict__ out, FbCtlDev *__restrict__ ctl,
+                                                  double *__restrict__ trace, int it) {
+  if (ctl && ctl->stop) return;  // queued behind the stopping iteration
+  __shared__ double s_lv[FB_LOSS_LDS], s_sc[FB_SC_LDS];
+  const int S = (task == FB_TASK_CSI || znorm_all) ? M : M - 1;
+  const bool sc_lds = (size_t)B * S <= (size_t)FB_SC_LDS;
+  const double dist_first = (int)threadIdx.x < n_dist_part ? dist_part[threadIdx.x] : 0.0;
+  FbCtlDev c = {};
+  if (threadIdx.x == 0 && ctl) c = *ctl;
+  int my_err = 0;
+  const int rows = B * r;
+  for (int row = threadIdx.x; row < rows; row += blockDim.x) {
+    if (tv && tv[row] <= 0) my_err = row / r + 1 > my_err ? row / r + 1 : my_err;
+    rep_l[row] = fb_loss_row<false>(raw, row, M, S, task, znorm_all, attack_type, z_mean, z_std, threshold, adver_thresh, target,
+                                    true_label, rep_sc + (size_t)row * S, nullptr);
+  }
+  __syncthreads();  // the replicas' rows were written by other threads of this workgroup
+  for (int b = threadIdx.x; b < B; b += blockDim.x) {
+    const double *lr = rep_l + (size_t)b * r;
+    double acc = lr[0];
+    for (int j = 1; j < r; ++j) acc = __dadd_rn(acc, lr[j]);
+    const double l = __ddiv_rn(acc, (double)r);
+    loss[b] = l;
+    if (b < FB_LOSS_LDS) s_lv[b] = l;
+    for (int m = 0; m < S; ++m) {
+      const double *sr = rep_sc + (size_t)b * r * S + m;
+      double a = sr[0];
+      for (int j = 1; j < r; ++j) a = __dadd_rn(a, sr[(size_t)j * S]);
+      const double v = __ddiv_rn(a, (double)r);
+      scores[(size_t)b * S + m] = v;
+      if (sc_lds) s_sc[(size_t)b * S + m] = v;
+    }
+  }
+  fb_loss_tail<SMALL>(B, S, dist_part, n_dist_part, dist_first, c, my_err, scores, loss, out, ctl, trace, it, s_lv, s_sc, 0,
+                      FB_LOSS_LDS, sc_lds);
+}
+void fb_launch_loss_eot(hipStream_t s, const double *raw, const int *tv, int B, int r, int M, int task, int znorm_all,
+                        int attack_type, const double *z_mean, const double *z_std, double threshold,
+                        double adver_thresh, int target, int true_label, const double *dist_part, int n_dist_part,
+                        double *rep_sc, double *rep_l, double *scores, double *loss, FbNesDev *out, FbCtlDev *ctl,
+                        double *trace, int it) {
+  if (B - 1 <= 128)
+    hipLaunchKernelGGL(k_loss_eot<true>, dim3(1), dim3(256), 0, s, raw, tv, B, r, M, task, znorm_all, attack_type, z_mean, z_std,
+                       threshold, adver_thresh, target, true_label, dist_part, n_dist_part, rep_sc, rep_l, scores, loss, out,
+                       ctl, trace, it);
+  else
+    hipLaunchKernelGGL(k_loss_eot<false>, dim3(1), dim3(256), 0, s, raw, tv, B, r, M, task, znorm_all, attack_type, z_mean, z_std,
+                       threshold, adver_thresh, target, true_label, dist_part, n_dist_part, rep_sc, rep_l, scores, loss, out,
+                       ctl, trace, it);
+}
+
 // ------------------------------------------------------------- grad + update
 // estimate_grad = np.mean(loss.flatten() * noise, axis=1) / sigma   (FAKEBOB.py:244)
 // then grad = m*pre + (1-m)*grad (:193), adver -= lr*sign(grad), clip (:202-203).

@@ -39,6 +39,7 @@ class Engine(object):
         self.cfg = N.FrontendCfg()
         self._L.fb_default_frontend(C.byref(self.cfg))
         self.input_transform = []
+        self.eot = 1
 
     def close(self):
         if self._h:
@@ -93,6 +94,41 @@ class Engine(object):
         out = np.empty_like(cat)
         N.check(self._L.fb_debug_input_transform(self._h, N.ptr(cat), N.ptr(off), C.c_int(len(lst)), N.ptr(out)))
         return [out[off[i]:off[i + 1]].copy() for i in range(len(lst))]
+
+    def set_eot(self, r):
+        """Expectation over transformation (fb_set_eot): get_grad and attack score every NES sample under r independent draws
+        of a randomised victim (a noise stage in the chain, dither > 0) and average the losses and scores before the
+        gradient estimate and the stop test.  1 (the default) changes nothing; 2 .. 32."""
+        r = int(r)
+        if not 1 <= r <= 32:
+            raise ValueError("EOT size %d outside 1 .. 32" % r)
+        N.check(self._L.fb_set_eot(self._h, C.c_int(r)))
+        self.eot = r
+
+    def debug_tf_noise(self, seed, stream, epoch, utt, replica, stage, i0, n):
+        """The float32 normals a noise stage at position `stage` adds to samples i0 .. i0 + n - 1 (fb_debug_tf_noise)."""
+        z = np.empty(int(n), np.float32)
+        N.check(self._L.fb_debug_tf_noise(self._h, C.c_uint64(int(seed)), C.c_uint32(int(stream)), C.c_uint32(int(epoch)),
+                                          C.c_uint32(int(utt)), C.c_int(int(replica)), C.c_int(int(stage)),
+                                          C.c_int64(int(i0)), C.c_int64(int(n)), N.ptr(z)))
+        return z
+
+    def debug_input_transform_eot(self, audio_list, r, seed, stream, epoch):
+        """The replicated int16 batch the MFCC would read at (seed, stream, epoch) of the noise contract
+        (fb_debug_input_transform_eot): a list of len(audio_list) lists of r arrays."""
+        lst = [np.ascontiguousarray(a, np.int16).reshape(-1) for a in audio_list]
+        off = np.zeros(len(lst) + 1, np.int64)
+        off[1:] = np.cumsum([a.size for a in lst])
+        cat = np.ascontiguousarray(np.concatenate(lst))
+        out = np.empty(cat.size * int(r), np.int16)
+        N.check(self._L.fb_debug_input_transform_eot(self._h, N.ptr(cat), N.ptr(off), C.c_int(len(lst)), C.c_int(int(r)),
+                                                     C.c_uint64(int(seed)), C.c_uint32(int(stream)), C.c_uint32(int(epoch)),
+                                                     N.ptr(out)))
+        res, o = [], 0
+        for a in lst:
+            res.append([out[o + j * a.size:o + (j + 1) * a.size].copy() for j in range(int(r))])
+            o += a.size * int(r)
+        return res
 
     @property
     def feat_dim(self):

@@ -3,7 +3,9 @@ reads, between the int16 cast and the MFCC (fb_set_input_transform; the stage co
 
 The input transformations FAKEBOB's evaluation places in front of the recogniser -- quantisation, local median
 smoothing, down-sampling ("audio squeezing") -- and the filters of the same family (average smoothing, low-pass
-filters, a room impulse response) are all chains of four int16 -> int16 stage kinds.  This module builds the stages
+filters, a room impulse response) are all chains of four int16 -> int16 stage kinds; the fifth kind, additive white
+Gaussian noise (SpeakerGuard's AT), makes the victim randomised: it draws afresh at every query, and the attack answers
+with expectation over transformation (Engine.set_eot, eot_size=).  This module builds the stages
 (the filter taps with numpy: the engine takes them as data), parses the short spec strings the system classes and the
 driver accept, and checks the engine's limits before the call.
 
@@ -14,12 +16,15 @@ driver accept, and checks the engine's limits before the call.
     lpf:f    windowed-sinc low-pass at f Hz (lpf:f:L for L taps)  lowpass(f, L)
     ds:q     audio squeezing: down-sample by q and back           squeeze(q)   (three stages)
     dec:q    keep every q-th sample, zero the others              decimate(q)
+    noise:s  white Gaussian noise of standard deviation s LSBs    noise(s)
+    at:snr   white Gaussian noise at snr dB below the utterance   at(snr_db)
 """
 import collections
 
 import numpy as np
 
-QUANT, MEDIAN, FIR, DECIMATE = 0, 1, 2, 3
+QUANT, MEDIAN, FIR, DECIMATE, NOISE = 0, 1, 2, 3, 4
+NOISE_ABS, NOISE_SNR = 0, 1   # a noise stage's k: taps[0] is the amplitude s / rho = 10^(snr_db / 10)
 MAX_STAGES = 8
 MAX_HALO = 1024       # largest sum of the stages' radii
 MAX_TAP = 2.0 ** 20   # largest tap magnitude
@@ -59,6 +64,33 @@ def decimate(q):
     if not 2 <= q <= 64:
         raise ValueError("decimation factor %d outside 2 .. 64" % q)
     return Stage(DECIMATE, q, None)
+
+
+def _noise_stage(mode, value):
+    """A noise stage from its mode and parameter, inside the library's limits (the C refusals, mirrored)."""
+    mode = int(mode)
+    if mode not in (NOISE_ABS, NOISE_SNR):
+        raise ValueError("noise mode %d is neither 0 (absolute) nor 1 (SNR)" % mode)
+    v = float(value)
+    if mode == NOISE_ABS and not 0.0 <= v <= 32768.0:       # (NaN fails the comparisons too)
+        raise ValueError("noise amplitude %g is not in 0 .. 32768" % v)
+    if mode == NOISE_SNR and not (v > 0.0 and np.isfinite(v)):
+        raise ValueError("rho = %g (10^(snr_db / 10)) is not finite and positive" % v)
+    return Stage(NOISE, mode, np.array([v], np.float64))
+
+
+def noise(s):
+    """White Gaussian noise of standard deviation s (int16 LSBs, 0 .. 32768), drawn afresh at every query."""
+    return _noise_stage(NOISE_ABS, s)
+
+
+def at(snr_db):
+    """SpeakerGuard's AT: white Gaussian noise snr_db decibels below the utterance's own power, drawn afresh at every query.
+    The stage carries rho = 10 ** (snr_db / 10)."""
+    snr_db = float(snr_db)
+    if not np.isfinite(snr_db):
+        raise ValueError("SNR %g dB is not finite" % snr_db)
+    return _noise_stage(NOISE_SNR, 10.0 ** (snr_db / 10))
 
 
 def average(k):
@@ -129,6 +161,10 @@ def parse(spec):
                 out.append(decimate(int(args[0])))
             elif name == "ds" and len(args) in (1, 2):
                 out.extend(squeeze(int(args[0]), *[int(a) for a in args[1:]]))
+            elif name == "noise" and len(args) == 1:
+                out.append(noise(float(args[0])))
+            elif name == "at" and len(args) == 1:
+                out.append(at(float(args[0])))
             elif name == "lpf" and len(args) in (1, 2):
                 out.append(lowpass(float(args[0]), *[int(a) for a in args[1:]]))
             else:
@@ -151,6 +187,10 @@ def validate(stages):
             if t.k != int(s.k):
                 raise ValueError("FIR stage says %d taps and carries %d" % (s.k, t.k))
             out.append(t)
+        elif s.kind == NOISE:
+            if s.taps is None or np.size(s.taps) != 1:
+                raise ValueError("a noise stage carries one parameter")
+            out.append(_noise_stage(s.k, np.ravel(s.taps)[0]))
         elif s.kind in build:
             out.append(build[s.kind](s))
         else:

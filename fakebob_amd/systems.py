@@ -102,6 +102,26 @@ def _apply_input_transform(engine, input_transform):
     engine.set_input_transform(input_transform)
 
 
+def eot_option(eot_size):
+    """The expectation-over-transformation size asked for: the `eot_size` keyword (the system classes', FakeBob's), then
+    FB_EOT_SIZE.  None: nobody asked, the engine keeps its value (1 unless the caller set one)."""
+    if eot_size is None:
+        eot_size = os.environ.get("FB_EOT_SIZE")
+        if eot_size is None or eot_size == "":
+            return None
+    r = int(eot_size)
+    if not 1 <= r <= 32:
+        raise ValueError("eot_size %d outside 1 .. 32" % r)
+    return r
+
+
+def apply_eot(engine, eot_size):
+    """Engine.set_eot with eot_option's answer, when there is one."""
+    r = eot_option(eot_size)
+    if r is not None:
+        engine.set_eot(r)
+
+
 def _conf_overrides(pre_model_dir, dither=None):
     """Front-end overrides of pre_model_dir/conf (none without that directory, or for pre_model_dir None) plus the dither
     option (_dither_option)."""
@@ -142,7 +162,7 @@ class _GmmSystem(object):
     PIPELINE = None  # class default of the two round trips (see REFERENCE_PIPELINE)
 
     def _setup(self, group_id, models, spk_ids, utt_ids, locations, z_means, z_stds, pre_model_dir, engine,
-               text_scores=None, compress_feats=None, mfcc_f32=None, dither=None, input_transform=None):
+               text_scores=None, compress_feats=None, mfcc_f32=None, dither=None, input_transform=None, eot_size=None):
         self.pre_model_dir = os.path.abspath(pre_model_dir)
         self.group_id = os.path.abspath(group_id)
         self.spk_ids = spk_ids
@@ -153,6 +173,7 @@ class _GmmSystem(object):
         over = _conf_overrides(self.pre_model_dir, dither)
         _apply_frontend(self._engine, over, text_scores, compress_feats, mfcc_f32, self.PIPELINE)
         _apply_input_transform(self._engine, input_transform)
+        apply_eot(self._engine, eot_size)
         self._engine.load_gmm(models)
         self._engine.set_system(self.task, z_means, z_stds)
 
@@ -178,14 +199,14 @@ class gmm_OSI(_GmmSystem):
 
     def __init__(self, group_id, model_list, ubm, pre_model_dir="pre-models", threshold=0.0, engine=None,
                  text_scores=None, compress_feats=None, mfcc_f32=None, dither=None,
-                 input_transform=None):
+                 input_transform=None, eot_size=None):
         self.threshold = threshold
         locs = [m[2] for m in model_list]
         self.model_list = [ubm] + locs  # UBM first (gmm_ubm_OSI.py:45)
         models = [load_gmm_any(x) for x in self.model_list]
         self._setup(group_id, models, [m[0] for m in model_list], [m[1] for m in model_list], locs, None, None,
                     pre_model_dir, engine, text_scores, compress_feats, mfcc_f32, dither,
-                    input_transform)
+                    input_transform, eot_size)
 
     def score(self, audios, fs=16000, bits_per_sample=16, debug=False, n_jobs=5):
         raw = self._raw(audios, bits_per_sample)
@@ -212,7 +233,7 @@ class gmm_CSI(_GmmSystem):
 
     def __init__(self, group_id, model_list, pre_model_dir="pre-models", engine=None, text_scores=None,
                  compress_feats=None, mfcc_f32=None, dither=None,
-                 input_transform=None):
+                 input_transform=None, eot_size=None):
         locs = [m[2] for m in model_list]
         self.model_list = locs
         self.z_norm_means = np.array([m[3] for m in model_list], np.float64)
@@ -220,7 +241,7 @@ class gmm_CSI(_GmmSystem):
         models = [load_gmm_any(x) for x in locs]
         self._setup(group_id, models, [m[0] for m in model_list], [m[1] for m in model_list], locs,
                     self.z_norm_means, self.z_norm_stds, pre_model_dir, engine, text_scores, compress_feats, mfcc_f32, dither,
-                    input_transform)
+                    input_transform, eot_size)
 
     def score(self, audios, fs=16000, bits_per_sample=16, debug=False, n_jobs=5):
         raw = self._raw(audios, bits_per_sample)
@@ -243,7 +264,7 @@ class gmm_SV(_GmmSystem):
 
     def __init__(self, spk_id, model, ubm, pre_model_dir="pre-models", threshold=0.0, engine=None,
                  text_scores=None, compress_feats=None, mfcc_f32=None, dither=None,
-                 input_transform=None):
+                 input_transform=None, eot_size=None):
         self.threshold = threshold
         self.utt_id = model[1]
         self.identity_location = model[2]
@@ -251,7 +272,7 @@ class gmm_SV(_GmmSystem):
         models = [load_gmm_any(x) for x in self.model_list]
         self._setup(spk_id, models, [model[0]], [model[1]], [model[2]], None, None, pre_model_dir, engine,
                     text_scores, compress_feats, mfcc_f32, dither,
-                    input_transform)
+                    input_transform, eot_size)
         self.spk_id = self.group_id
 
     def score(self, audios, fs=16000, bits_per_sample=16, debug=False, n_jobs=5):
@@ -274,7 +295,7 @@ class _IvSystem(object):
     PIPELINE = None
 
     def _setup(self, group_id, model_list, pre_model_dir, engine, system, text_scores=None, compress_feats=None, mfcc_f32=None, dither=None,
-               input_transform=None):
+               input_transform=None, eot_size=None):
         from .models import IvectorSystem
         self.pre_model_dir = os.path.abspath(pre_model_dir)
         self.group_id = os.path.abspath(group_id)
@@ -308,6 +329,7 @@ class _IvSystem(object):
             _apply_frontend(self._engine, _conf_overrides(None, dither), text_scores, compress_feats, mfcc_f32, self.PIPELINE)
             system = system.with_enrolled(enrolled, zm, zs)
         _apply_input_transform(self._engine, input_transform)
+        apply_eot(self._engine, eot_size)
         self._engine.load_ivector(system, self.task)
 
     @property
@@ -331,10 +353,10 @@ class iv_OSI(_IvSystem):
 
     def __init__(self, group_id, model_list, pre_model_dir="pre-models", threshold=0.0, engine=None, system=None,
                  text_scores=None, compress_feats=None, mfcc_f32=None, dither=None,
-                 input_transform=None):
+                 input_transform=None, eot_size=None):
         self.threshold = threshold
         self._setup(group_id, model_list, pre_model_dir, engine, system, text_scores, compress_feats, mfcc_f32, dither,
-                    input_transform)
+                    input_transform, eot_size)
 
     def score(self, audio_list, fs=16000, bits_per_sample=16, n_jobs=10, debug=False):
         s = (self._llr(audio_list, bits_per_sample) - self.z_norm_means) / self.z_norm_stds   # :119
@@ -363,9 +385,9 @@ class iv_CSI(_IvSystem):
 
     def __init__(self, group_id, model_list, pre_model_dir="pre-models", engine=None, system=None, text_scores=None,
                  compress_feats=None, mfcc_f32=None, dither=None,
-                 input_transform=None):
+                 input_transform=None, eot_size=None):
         self._setup(group_id, model_list, pre_model_dir, engine, system, text_scores, compress_feats, mfcc_f32, dither,
-                    input_transform)
+                    input_transform, eot_size)
 
     def score(self, audio_list, fs=16000, bits_per_sample=16, n_jobs=10, debug=False):
         s = (self._llr(audio_list, bits_per_sample) - self.z_norm_means) / self.z_norm_stds
@@ -389,10 +411,10 @@ class iv_SV(_IvSystem):
 
     def __init__(self, spk_id, model, pre_model_dir="pre-models", threshold=0.0, engine=None, system=None,
                  text_scores=None, compress_feats=None, mfcc_f32=None, dither=None,
-                 input_transform=None):
+                 input_transform=None, eot_size=None):
         self.threshold = threshold
         self._setup(spk_id, [model], pre_model_dir, engine, system, text_scores, compress_feats, mfcc_f32, dither,
-                    input_transform)
+                    input_transform, eot_size)
         self.spk_id = self.group_id
         self.utt_id = model[1]
         self.identity_location = model[2]

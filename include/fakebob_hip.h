@@ -19,6 +19,8 @@
  *                             int16 cast of gmm_ubm_OSI.py:83-85
  *   fb_system_scores          wrapper post-processing gmm_ubm_OSI.py:89,
  *                             gmm_ubm_SV.py:77, gmm_ubm_CSI.py:93
+ *   fb_set_eot                (none: SpeakerGuard's EOT_size -- every NES sample scored under several draws of a
+ *                             randomised victim, the losses averaged)
  *   fb_get_grad               FakeBob.get_grad + loss_fn (FAKEBOB.py:223-299)
  *   fb_attack                 FakeBob.attack (FAKEBOB.py:139-221)
  *   fb_estimate_threshold     FakeBob.estimate_threshold (FAKEBOB.py:39-137)
@@ -147,6 +149,19 @@ typedef struct {
  * many iterations the host queues ahead --, and an utterance's noise does not depend on what else is in its batch. */
 int fb_set_dither_seed(fb_engine *e, uint64_t seed);
 
+/* ---- Noise RNG contract (FB_TF_NOISE stages of the input-transform chain below) -----------------------------------------
+ * The normals z of a noise stage come from the same generator -- Philox4x32-10 and the float32 Box-Muller -- on a third key:
+ *   key     = (seed_lo ^ 0x4E4F4953 ("NOIS"), seed_hi ^ stream)
+ *   counter = (i >> 2, stage index + 8 * replica, utterance row of the un-replicated batch, epoch)
+ * and the four output words give z for samples 4 (i >> 2) .. + 3 of the utterance, as in the dither contract.  `stage index`
+ * is the stage's position in the chain (0 .. 7), `replica` is 0 unless fb_set_eot replicates the batch.
+ * Seed, stream and epoch follow exactly the rules of the dither contract: in fb_get_grad / fb_attack / fb_estimate_threshold
+ * the call's seed and stream and the NES iteration; in scoring calls (fb_score_*, fb_gmm_acc_stats, fb_debug_mfcc / _feats)
+ * the engine's fb_set_dither_seed seed, stream 0xFFFFFFFF and the scoring-call serial.
+ * A sample's noise depends on its absolute index i within the utterance, on nothing else of the launch.  So a defended
+ * victim answers two scoring calls differently (the serial advances), an attack's result depends on (seed, stream) only,
+ * and the two other streams (NES, dither) are never met. */
+
 /* ---- input-transform chain: a defended system ---------------------------------------------------------------
  * A short list of int16 -> int16 stages (the input transformations of the FAKEBOB paper's defence study: quantisation,
  * median smoothing, down-sampling; average smoothing, low-pass / band-pass filters and room impulse responses as FIR)
@@ -167,13 +182,45 @@ int fb_set_dither_seed(fb_engine *e, uint64_t seed);
  *                   taps[L] float64,     c = (L - 1) / 2; every product is rounded to float64, then the sum is, with no
  *                   finite, |h| <= 2^20  fused multiply-add; y = clip(rint(acc)), ties to even
  *   FB_TF_DECIMATE  k = q, 2 .. 64       y[i] = x[i] if i mod q == 0, else 0, i counted from the utterance's first sample
+ *   FB_TF_NOISE     k = mode, 0 or 1     y[i] = clip(rint(x[i] + s * z[i])): float64, z the float32 normal of the "Noise RNG
+ *                   taps[1] float64      contract" widened exactly, the product rounded, then the sum (no fused multiply-add),
+ *                                        rint ties to even, clip to [-32768, 32767]; indices outside [0, n) stay 0; radius 0
+ *                     k = 0 (absolute)   s = taps[0], in int16 LSBs, finite, 0 <= s <= 32768
+ *                     k = 1 (SNR)        taps[0] = rho = 10^(snr_db / 10), formed by the caller, finite and > 0;
+ *                                        s = sqrt((double)E / (double)n / rho), division and square root correctly rounded,
+ *                                        E the exact integer sum of squares of the utterance AS IT IS HANDED TO THE CHAIN
+ *                                        (a silent utterance: s = 0, y = x)
+ * (FB_TF_NOISE is SpeakerGuard's additive-noise transformation AT: white Gaussian noise at a set SNR, drawn afresh at every
+ *  query.  Deviation: SpeakerGuard takes the power of the signal its AT layer receives; here E is taken at the chain's
+ *  INPUT wherever the stage stands, by a launch of its own in front of the chain (k_tf_power) -- the same thing when the
+ *  stage comes first, which is where SpeakerGuard puts it.  A noise stage may stand anywhere and more than once.)
  * (average smoothing = FIR with taps 1 / k; audio squeezing by q = FIR, DECIMATE(q), FIR with the gain q folded into the
  * second filter's taps.)  Limits: at most 8 stages; the stages' radii (r or c; 0 for QUANT and DECIMATE) sum to at most
  * 1024.  Anything outside the contract returns FB_E_ARG and keeps the previous chain, as fb_set_frontend does.
- * n = 0 clears the chain: no launch is added and nothing else changes.  `taps` is read for FB_TF_FIR only and copied. */
+ * n = 0 clears the chain: no launch is added and nothing else changes.  `taps` is read for FB_TF_FIR (k values) and
+ * FB_TF_NOISE (one value) only and copied. */
 enum { FB_TF_QUANT = 0, FB_TF_MEDIAN = 1, FB_TF_FIR = 2, FB_TF_DECIMATE = 3 };
+enum { FB_TF_NOISE = 4 };  /* the randomised kind */
 typedef struct { int kind; int k; const double *taps; } fb_tf_stage;
 int fb_set_input_transform(fb_engine *e, const fb_tf_stage *stages, int n);
+
+/* ---- expectation over transformation: attacking a randomised victim ---------------------------------------------------
+ * With a noise stage in the chain or dither > 0 the victim answers every query with a fresh draw.  r > 1 makes fb_get_grad
+ * and fb_attack score every row of the NES batch under r independent draws and average BEFORE the gradient estimate and the
+ * stop test (SpeakerGuard's FAKEBOB: EOT_size):
+ *  - the transform launch (a replicating copy when the chain is empty) writes replica j of NES row b to row b * r + j; its
+ *    noise stages draw with `replica` = j; the front end sees a batch of B * r utterances, so the dither counter's utterance
+ *    index is the replicated row and the replicas' dither differs too;
+ *  - system scores and loss_fn are formed per replica row exactly as without EOT, then
+ *      loss[b] = (l[b][0] + ... + l[b][r - 1]) / r,   scores[b][s] = (sc[b][0][s] + ... + sc[b][r - 1][s]) / r
+ *    in float64, j ascending, one rounding per addition and one for the division;
+ *  - everything behind that -- the mean of loss[1:], the stop rule on loss[0], the plateau rule, the trace row (averaged
+ *    scores), the gradient estimate -- is unchanged and sees the B averaged rows.  FB_E_NO_VOICED if ANY replica has no
+ *    voiced frames.
+ * r = 1 (the default) changes nothing: no launch is added.  r = 2 .. 32; anything else is FB_E_ARG and keeps the previous
+ * value.  Not applied to foreign models (_ext, _dev), as the chain is not.  fb_estimate_threshold returns FB_E_STATE while
+ * r > 1.  An attack whose (samples_per_draw + 1) * r exceeds 65535 rows returns FB_E_LIMIT. */
+int fb_set_eot(fb_engine *e, int r);
 
 const char *fb_last_error(void);
 int fb_version(void);

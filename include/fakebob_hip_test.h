@@ -44,6 +44,17 @@ int fb_debug_feats_dither(fb_engine *e, const int16_t *wav, int64_t n, uint64_t 
  * frame included: nothing but the transform runs).  Without a chain out equals wav. */
 int fb_debug_input_transform(fb_engine *e, const int16_t *wav, const int64_t *off, int B, int16_t *out);
 
+/* Randomised stages and replication (fakebob_hip.h: FB_TF_NOISE, "Noise RNG contract", fb_set_eot).
+ * fb_debug_tf_noise: the normals z[n] the noise stage at position `stage` of a chain adds to samples i0 .. i0 + n - 1 of
+ * utterance `utt`, replica `replica`, at (seed, stream, epoch), from the device function the transform kernel calls.
+ * fb_debug_input_transform_eot: fb_debug_input_transform at that point of the contract with every utterance written r
+ * times: out holds B * r utterances, replica j of utterance b at row b * r + j (rows one after the other, each as long as
+ * its utterance).  The engine's fb_set_eot value, dither seed and scoring-call serial are neither used nor advanced. */
+int fb_debug_tf_noise(fb_engine *e, uint64_t seed, uint32_t stream, uint32_t epoch, uint32_t utt, int replica, int stage,
+                      int64_t i0, int64_t n, float *z);
+int fb_debug_input_transform_eot(fb_engine *e, const int16_t *wav, const int64_t *off, int B, int r, uint64_t seed,
+                                 uint32_t stream, uint32_t epoch, int16_t *out);
+
 /* What the front end of the last batch ran (fb_score_*, fb_get_grad, an NES iteration, fb_debug_mfcc / _feats, enrolment
  * statistics): info[5] = {the MFCC kernel, the chain after it, where the CompressedMatrix round trip ran, the longest
  * utterance of the batch in frames, the batch size}.  Recorded on the host when the kernels are enqueued; read only.
