@@ -100,6 +100,13 @@ struct fb_engine {
   int eot = 1;                  // fb_set_eot: replicas of every NES row (1: none)
   int eot_run = 1;              // ... of the batch run_scoring is working on (enqueue_get_grad sets it around its call; else 1)
   DevBuf eot_sc, eot_l;         // k_loss_eot's per-replica scores [B * r][S] and losses [B * r]
+  // feature compression (fb_set_feature_compression; the stage contract of fakebob_hip.h): feco_iters == 0 -- off, the back
+  // end reads `feats` / `row_off` as the front end wrote them
+  double feco_ratio = 0.0;
+  int feco_iters = 0;
+  FbFeco fkey = {};             // the point of the contract the next k_feature_compress launch stands at: set beside nkey
+  DevBuf feats_fc, row_off_fc;  // the compressed rows and their offsets: they swap roles with feats / row_off behind the launch
+  DevBuf feco_ws;               // FB_FECO_WS_INTS ints per input row: the arrays of rows that do not fit the LDS
   // gmm
   bool have_gmm = false;
   FbGmmDev gmm;
@@ -264,7 +271,7 @@ extern "C" int fb_engine_destroy(fb_engine *e) {
   if (!e) return FB_OK;
   (void)hipSetDevice(e->device);
   if (e->stream) (void)hipStreamSynchronize(e->stream);
-  DevBuf *bufs[] = {&e->fe_tables, &e->fe_tables32, &e->frame_ut, &e->tf_taps, &e->wav_tf, &e->tf_power, &e->eot_sc, &e->eot_l, &e->gmm_items, &e->gmm_images_bx, &e->gmm_images_fx, &e->gmm_images_fd, &e->gmm_images_fd2, &e->gmm_images_fd3, &e->gmm_anchor, &e->zmean, &e->zstd, &e->wav, &e->wav_off,
+  DevBuf *bufs[] = {&e->fe_tables, &e->fe_tables32, &e->frame_ut, &e->tf_taps, &e->wav_tf, &e->tf_power, &e->eot_sc, &e->eot_l, &e->feats_fc, &e->row_off_fc, &e->feco_ws, &e->gmm_items, &e->gmm_images_bx, &e->gmm_images_fx, &e->gmm_images_fd, &e->gmm_images_fd2, &e->gmm_images_fd3, &e->gmm_anchor, &e->zmean, &e->zstd, &e->wav, &e->wav_off,
                     &e->frame_rec, &e->vad_counter, &e->vad_pub, &e->vad_part, &e->fin_counter, &e->fin_xch, &e->ctl, &e->ctl_ls, &e->trace_dev, &e->ticks, &e->enr_ll, &e->enr_aux, &e->enr_stats, &e->frame_off, &e->chunk_off, &e->chunk_sum, &e->mfcc, &e->mfcc_cm, &e->vrank, &e->tv, &e->row_off, &e->dfeat, &e->feats,
                     &e->part_m, &e->part_s, &e->raw, &e->audio, &e->adver, &e->grad_m, &e->grad, &e->noise, &e->zbuf,
                     &e->scores, &e->loss, &e->dist_part, &e->nes_out, &e->stage_f64, &e->ext_x, &e->ext_z, &e->iv_fg, &e->iv_fg64, &e->iv_fgL, &e->iv_tri,
@@ -1312,6 +1319,7 @@ static int launch_mfcc(fb_engine *e, int B, int total_frames) {
 static void dither_key_scoring_call(fb_engine *e) {
   e->dkey = fb_dither_key(e->cfg.dither, e->dither_seed, 0xFFFFFFFFu, e->dither_serial, 0);
   e->nkey = fb_tf_rnd(e->dither_seed, 0xFFFFFFFFu, e->dither_serial, 0);  // (the noise stages' key: the same rules)
+  e->fkey = fb_feco_key(0.0, 0, e->dither_seed, 0xFFFFFFFFu, e->dither_serial, 0);  // (... and feature compression's)
   e->dither_serial += 1;
 }
 
@@ -1392,6 +1400,28 @@ static int run_post_mfcc(fb_engine *e, int B) {
   return FB_OK;
 }
 
+// Feature compression (fb_set_feature_compression): k-means over the voiced rows of every utterance row of the batch, one
+// launch between the front end and the back end.  It reads e->feats / e->row_off and writes e->feats_fc / e->row_off_fc; the
+// two pairs then swap roles (the mfcc / mfcc_cm idiom of run_post_mfcc), so every launch behind it -- the GMM and gselect
+// kernels, the finalising launches, the i-vector chain -- takes the compressed rows and their counts from where it always did.
+// With e->eot_run = r > 1 B counts the replicated rows and row b * r + j draws replica j's initialisation.
+static int feature_compress(fb_engine *e, int B, int total_frames) {
+  const int D = e->fe.dim;
+  FBCHK(e->feats_fc.ensure(sizeof(float) * (size_t)total_frames * D));
+  FBCHK(e->row_off_fc.ensure(sizeof(int) * (size_t)(B + 1)));
+  FBCHK(e->feco_ws.ensure(sizeof(int) * (size_t)FB_FECO_WS_INTS * (size_t)(total_frames > 0 ? total_frames : 1)));
+  FbFeco fc = e->fkey;
+  fc.ratio = e->feco_ratio;
+  fc.iters = e->feco_iters;
+  fc.r = e->eot_run;
+  if (!fb_launch_feature_compress(e->stream, fc, D, e->feats.as<float>(), e->row_off.as<int>(), B, e->t_max,
+                                  e->feats_fc.as<float>(), e->row_off_fc.as<int>(), e->feco_ws.as<int>(), e->fe.stop))
+    return fb_fail(FB_E_HIP, "k_feature_compress: the dynamic-LDS opt-in failed");
+  std::swap(e->feats, e->feats_fc);
+  std::swap(e->row_off, e->row_off_fc);
+  return FB_OK;
+}
+
 // wav (device) + offsets (device) -> raw[B][M] (device).  Purely asynchronous.
 static int run_scoring(fb_engine *e, int B, int total_frames) {
   const FbFrontendDev &fe = e->fe;
@@ -1411,6 +1441,7 @@ static int run_scoring(fb_engine *e, int B, int total_frames) {
   choose_launch_shape(e);
   FBCHK(launch_mfcc(e, B, total_frames));
   FBCHK(run_post_mfcc(e, B));
+  if (e->feco_iters > 0) FBCHK(feature_compress(e, B, total_frames));
   if (e->kind == 0) {
     // A GPU shared by three or more attacks (fb_set_fused_chain(e, 0)): k_gmm_fx2w takes a whole compute unit per workgroup (one
     // wave per SIMD with the full register file), and so does k_mfcc_f32 (four waves per SIMD at 122 registers) -- with a
@@ -2207,6 +2238,7 @@ static int enqueue_get_grad(fb_engine *e, const fb_nes_params *p, int64_t N, uin
   // fb_estimate_threshold `iter` counts the call's front-end launches: one per pass of its loop)
   e->dkey = fb_dither_key(e->cfg.dither, p->seed, p->stream, iter, 0);
   e->nkey = fb_tf_rnd(p->seed, p->stream, iter, 0);
+  e->fkey = fb_feco_key(0.0, 0, p->seed, p->stream, iter, 0);
   e->eot_run = r;
   const int rc = run_scoring(e, BR, e->h_frame_off[BR]);
   e->eot_run = 1;
@@ -3068,6 +3100,76 @@ extern "C" int fb_set_eot(fb_engine *e, int r) {
   if (r < 1 || r > 32) return fb_fail(FB_E_ARG, "EOT size %d outside 1 .. 32", r);
   e->eot = r;
   e->bench_it = -1;  // an attack fb_bench_nes left resident was laid out for the previous size
+  return FB_OK;
+}
+
+extern "C" int fb_set_feature_compression(fb_engine *e, double ratio, int iters) {
+  if (!e) return fb_fail(FB_E_ARG, "null engine");
+  const bool off = ratio == 0.0 && iters == 0;
+  if (!off && (!(ratio > 0.0 && ratio <= 1.0) || iters < 1 || iters > 64))
+    return fb_fail(FB_E_ARG, "feature compression takes 0 < ratio <= 1 and 1 .. 64 iterations, or 0 and 0 for none (got %g, %d)", ratio, iters);
+  e->feco_ratio = off ? 0.0 : ratio;
+  e->feco_iters = iters;
+  e->bench_it = -1;  // an attack fb_bench_nes left resident ran under the previous setting
+  return FB_OK;
+}
+
+extern "C" int fb_debug_feature_compress(fb_engine *e, const float *feats, const int *row_off, int B, int r, uint64_t seed,
+                                         uint32_t stream, uint32_t epoch, float *out, int *out_off) {
+  if (!e || !feats || !row_off || !out || !out_off || B <= 0 || r < 1 || r > 32 || (int64_t)B * r > 65535)
+    return fb_fail(FB_E_ARG, "bad argument");
+  if (e->feco_iters <= 0) return fb_fail(FB_E_STATE, "feature compression is off: fb_set_feature_compression first");
+  const int rows = B * r, D = e->fe.dim;
+  if (row_off[0] != 0) return fb_fail(FB_E_ARG, "row_off[0] must be 0");
+  int t_max = 0;
+  for (int u = 0; u < rows; ++u) {
+    if (row_off[u + 1] < row_off[u]) return fb_fail(FB_E_ARG, "row_off decreases at row %d", u);
+    t_max = std::max(t_max, row_off[u + 1] - row_off[u]);
+  }
+  const size_t total = (size_t)row_off[rows];
+  if (total == 0 || total * (size_t)D > 0x7fffffffull) return fb_fail(FB_E_ARG, "the batch holds no row, or more than the hook takes");
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  DevBuf d_in, d_off, d_out, d_ooff, d_ws;
+  int rc = d_in.ensure(sizeof(float) * total * D);
+  if (rc == FB_OK) rc = d_off.ensure(sizeof(int) * (size_t)(rows + 1));
+  if (rc == FB_OK) rc = d_out.ensure(sizeof(float) * total * D);
+  if (rc == FB_OK) rc = d_ooff.ensure(sizeof(int) * (size_t)(rows + 1));
+  if (rc == FB_OK) rc = d_ws.ensure(sizeof(int) * FB_FECO_WS_INTS * total);
+  if (rc == FB_OK) rc = h2d(e, d_in.p, feats, sizeof(float) * total * D);
+  if (rc == FB_OK) rc = h2d(e, d_off.p, row_off, sizeof(int) * (size_t)(rows + 1));
+  if (rc == FB_OK) {
+    FbFeco fc = fb_feco_key(e->feco_ratio, e->feco_iters, seed, stream, epoch, 0);
+    fc.r = r;
+    if (!fb_launch_feature_compress(e->stream, fc, D, d_in.as<float>(), d_off.as<int>(), rows, t_max, d_out.as<float>(),
+                                    d_ooff.as<int>(), d_ws.as<int>(), nullptr))
+      rc = fb_fail(FB_E_HIP, "k_feature_compress: the dynamic-LDS opt-in failed");
+    else if (hipGetLastError() != hipSuccess)
+      rc = fb_fail(FB_E_HIP, "the feature-compression launch failed");
+  }
+  // (k <= T per row: the compressed rows fit a buffer of the input's size; what lies behind them is left as it was)
+  if (rc == FB_OK) rc = d2h(e, out_off, d_ooff.p, sizeof(int) * (size_t)(rows + 1));
+  int rs = sync_stream(e);
+  if (rc == FB_OK && rs == FB_OK && out_off[rows] > 0) {
+    rc = d2h(e, out, d_out.p, sizeof(float) * (size_t)out_off[rows] * D);
+    rs = sync_stream(e);
+  }
+  for (DevBuf *b : {&d_in, &d_off, &d_out, &d_ooff, &d_ws}) b->release();
+  return rc != FB_OK ? rc : rs;
+}
+
+extern "C" int fb_debug_feco_keys(fb_engine *e, uint64_t seed, uint32_t stream, uint32_t epoch, uint32_t utt, int replica, int T,
+                                  uint32_t *keys) {
+  if (!e || !keys || T <= 0 || replica < 0 || replica > 31) return fb_fail(FB_E_ARG, "bad argument");
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  DevBuf tmp;
+  FBCHK(tmp.ensure(sizeof(uint32_t) * (size_t)T));
+  fb_launch_feco_keys(e->stream, fb_feco_key(0.0, 0, seed, stream, epoch, utt), replica, T, tmp.as<uint32_t>());
+  hipError_t er = hipMemcpyAsync(keys, tmp.p, sizeof(uint32_t) * (size_t)T, hipMemcpyDeviceToHost, e->stream);
+  if (er == hipSuccess) er = hipStreamSynchronize(e->stream);
+  tmp.release();
+  if (er != hipSuccess) return fb_fail(FB_E_HIP, "key dump failed: %s", hipGetErrorString(er));
   return FB_OK;
 }
 

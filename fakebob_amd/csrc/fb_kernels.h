@@ -80,6 +80,27 @@ void fb_launch_input_transform_rnd(hipStream_t s, const FbTfChain &ch, const dou
 // z[n] = the normals a noise stage adds to samples i0 .. i0 + n - 1 of utterance rn.utt0 (fb_debug_tf_noise)
 void fb_launch_tf_noise(hipStream_t s, const FbTfRnd &rn, int replica, int stage, int64_t i0, int64_t n, float *z);
 
+// ---- feature compression (fb_set_feature_compression; feature_compress_kernel.hip) -------------------------------
+// What a launch carries of the stage contract (include/fakebob_hip.h): the setting, the Philox key (seed_lo ^ "FECO",
+// seed_hi ^ stream), counter word 3, the row of the batch's first utterance within the call and the replicas per utterance
+struct FbFeco {
+  double ratio;
+  int iters;
+  uint32_t k0, k1, epoch, utt0;
+  int r;
+};
+static inline FbFeco fb_feco_key(double ratio, int iters, uint64_t seed, uint32_t stream, uint32_t epoch, uint32_t utt0) {
+  return FbFeco{ratio, iters, (uint32_t)seed ^ 0x4645434Fu, (uint32_t)(seed >> 32) ^ stream, epoch, utt0, 1};
+}
+#define FB_FECO_WS_INTS 5  // ints of workspace per input row (rows that do not fit the LDS: keys, labels, sorted order, counts, starts)
+// k-means over the rows of every utterance row (row_off[rows + 1]; row b * fc.r + j = replica j of utterance b): the centres
+// to out, their offsets to out_off[rows + 1]; ws: FB_FECO_WS_INTS ints per input row; t_max: an upper bound of the longest
+// row (it sizes the LDS request); honours `stop` (nullable) like the MFCC kernels.  false: the LDS opt-in failed
+bool fb_launch_feature_compress(hipStream_t s, const FbFeco &fc, int D, const float *feats, const int *row_off, int rows,
+                                int t_max, float *out, int *out_off, int *ws, const int *stop);
+// keys[T] of one (utterance fc.utt0, replica) of the contract (fb_debug_feco_keys)
+void fb_launch_feco_keys(hipStream_t s, const FbFeco &fc, int replica, int T, uint32_t *keys);
+
 // ---- NES ----------------------------------------------------------------
 // q[b][n] = int16((adver[n] + sigma*noise_b[n]) * 2^15), b in [0, 2*half]; column 0 is the
 // un-noised adver.  noise: Philox(seed, iter, stream) or explicit float64 [N][half].

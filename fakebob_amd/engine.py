@@ -40,6 +40,7 @@ class Engine(object):
         self._L.fb_default_frontend(C.byref(self.cfg))
         self.input_transform = []
         self.eot = 1
+        self.feature_compression = None
 
     def close(self):
         if self._h:
@@ -104,6 +105,42 @@ class Engine(object):
             raise ValueError("EOT size %d outside 1 .. 32" % r)
         N.check(self._L.fb_set_eot(self._h, C.c_int(r)))
         self.eot = r
+
+    def set_feature_compression(self, ratio, iters=10):
+        """Feature compression (fb_set_feature_compression; SpeakerGuard's FeCo): the engine clusters the voiced feature rows
+        of every utterance it scores with k-means -- keyed initialisation, `iters` Lloyd iterations -- and scores the
+        max(1, floor(T * ratio)) centres in the frames' place.  0 < ratio <= 1, iters 1 .. 64; ratio None switches it off.
+        Not applied to foreign models, to enrolment statistics or to debug_mfcc / debug_feats."""
+        if ratio is None:
+            N.check(self._L.fb_set_feature_compression(self._h, C.c_double(0.0), C.c_int(0)))
+            self.feature_compression = None
+            return
+        N.check(self._L.fb_set_feature_compression(self._h, C.c_double(float(ratio)), C.c_int(int(iters))))
+        self.feature_compression = (float(ratio), int(iters))
+
+    def debug_feature_compress(self, mats, r, seed, stream, epoch):
+        """k_feature_compress on feature matrices handed in as they are (fb_debug_feature_compress): `mats`, a list of B
+        float32 arrays (T_b, feat_dim), T_b = 0 allowed, each scored under r replicas at (seed, stream, epoch) of the contract
+        -> a list of B lists of r arrays (k_b, feat_dim)."""
+        D, r = self.feat_dim, int(r)
+        lst = [np.ascontiguousarray(m, np.float32).reshape(-1, D) for m in mats]
+        rep = [m for m in lst for _ in range(r)]
+        off = np.zeros(len(rep) + 1, np.int32)
+        off[1:] = np.cumsum([m.shape[0] for m in rep])
+        cat = np.ascontiguousarray(np.concatenate(rep, axis=0))
+        out = np.empty_like(cat)
+        out_off = np.empty_like(off)
+        N.check(self._L.fb_debug_feature_compress(self._h, N.ptr(cat), N.ptr(off), C.c_int(len(lst)), C.c_int(r),
+                                                  C.c_uint64(int(seed)), C.c_uint32(int(stream)), C.c_uint32(int(epoch)),
+                                                  N.ptr(out), N.ptr(out_off)))
+        return [[out[out_off[b * r + j]:out_off[b * r + j + 1]].copy() for j in range(r)] for b in range(len(lst))]
+
+    def debug_feco_keys(self, seed, stream, epoch, utt, replica, T):
+        """The uint32 initialisation keys of frames 0 .. T - 1 of (utterance row `utt`, replica) (fb_debug_feco_keys)."""
+        keys = np.empty(int(T), np.uint32)
+        N.check(self._L.fb_debug_feco_keys(self._h, C.c_uint64(int(seed)), C.c_uint32(int(stream)), C.c_uint32(int(epoch)),
+                                           C.c_uint32(int(utt)), C.c_int(int(replica)), C.c_int(int(T)), N.ptr(keys)))
+        return keys
 
     def debug_tf_noise(self, seed, stream, epoch, utt, replica, stage, i0, n):
         """The float32 normals a noise stage at position `stage` adds to samples i0 .. i0 + n - 1 (fb_debug_tf_noise)."""

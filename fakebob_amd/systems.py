@@ -122,6 +122,50 @@ def apply_eot(engine, eot_size):
         engine.set_eot(r)
 
 
+def parse_feco(spec):
+    """A feature-compression spec -> (ratio, iters), or None for "none" / "off": "0.5" (10 iterations) or "0.5:10"; a number
+    or a (ratio, iters) pair is taken as it is.  ValueError for anything else or outside 0 < ratio <= 1, iters 1 .. 64."""
+    iters = 10
+    if isinstance(spec, str):
+        txt = spec.strip()
+        if txt.lower() in ("none", "off"):
+            return None
+        parts = txt.split(":")
+        if len(parts) > 2:
+            raise ValueError("feature compression spec %r: RATIO or RATIO:ITERS" % (spec,))
+        try:
+            ratio = float(parts[0])
+            if len(parts) == 2:
+                iters = int(parts[1])
+        except ValueError:
+            raise ValueError("feature compression spec %r: RATIO or RATIO:ITERS" % (spec,))
+    elif isinstance(spec, (tuple, list)):
+        if len(spec) != 2:
+            raise ValueError("feature compression takes (ratio, iters), got %r" % (spec,))
+        ratio, iters = float(spec[0]), int(spec[1])
+    else:
+        ratio = float(spec)
+    if not (0.0 < ratio <= 1.0):        # (NaN fails too)
+        raise ValueError("feature compression ratio %r outside (0, 1]" % (ratio,))
+    if not 1 <= iters <= 64:
+        raise ValueError("feature compression iterations %d outside 1 .. 64" % iters)
+    return ratio, iters
+
+
+def apply_feature_compression(engine, feature_compression):
+    """The feature-compression defence of a system under construction: the `feature_compression` keyword (parse_feco's
+    forms), then FB_FECO.  None of the two: the engine keeps its setting (off unless the caller set one)."""
+    if feature_compression is None:
+        feature_compression = os.environ.get("FB_FECO")
+        if feature_compression is None or feature_compression == "":
+            return
+    fc = parse_feco(feature_compression)
+    if fc is None:
+        engine.set_feature_compression(None)
+    else:
+        engine.set_feature_compression(fc[0], fc[1])
+
+
 def _conf_overrides(pre_model_dir, dither=None):
     """Front-end overrides of pre_model_dir/conf (none without that directory, or for pre_model_dir None) plus the dither
     option (_dither_option)."""
@@ -162,7 +206,7 @@ class _GmmSystem(object):
     PIPELINE = None  # class default of the two round trips (see REFERENCE_PIPELINE)
 
     def _setup(self, group_id, models, spk_ids, utt_ids, locations, z_means, z_stds, pre_model_dir, engine,
-               text_scores=None, compress_feats=None, mfcc_f32=None, dither=None, input_transform=None, eot_size=None):
+               text_scores=None, compress_feats=None, mfcc_f32=None, dither=None, input_transform=None, eot_size=None, feature_compression=None):
         self.pre_model_dir = os.path.abspath(pre_model_dir)
         self.group_id = os.path.abspath(group_id)
         self.spk_ids = spk_ids
@@ -174,6 +218,7 @@ class _GmmSystem(object):
         _apply_frontend(self._engine, over, text_scores, compress_feats, mfcc_f32, self.PIPELINE)
         _apply_input_transform(self._engine, input_transform)
         apply_eot(self._engine, eot_size)
+        apply_feature_compression(self._engine, feature_compression)
         self._engine.load_gmm(models)
         self._engine.set_system(self.task, z_means, z_stds)
 
@@ -199,14 +244,14 @@ class gmm_OSI(_GmmSystem):
 
     def __init__(self, group_id, model_list, ubm, pre_model_dir="pre-models", threshold=0.0, engine=None,
                  text_scores=None, compress_feats=None, mfcc_f32=None, dither=None,
-                 input_transform=None, eot_size=None):
+                 input_transform=None, eot_size=None, feature_compression=None):
         self.threshold = threshold
         locs = [m[2] for m in model_list]
         self.model_list = [ubm] + locs  # UBM first (gmm_ubm_OSI.py:45)
         models = [load_gmm_any(x) for x in self.model_list]
         self._setup(group_id, models, [m[0] for m in model_list], [m[1] for m in model_list], locs, None, None,
                     pre_model_dir, engine, text_scores, compress_feats, mfcc_f32, dither,
-                    input_transform, eot_size)
+                    input_transform, eot_size, feature_compression)
 
     def score(self, audios, fs=16000, bits_per_sample=16, debug=False, n_jobs=5):
         raw = self._raw(audios, bits_per_sample)
@@ -233,7 +278,7 @@ class gmm_CSI(_GmmSystem):
 
     def __init__(self, group_id, model_list, pre_model_dir="pre-models", engine=None, text_scores=None,
                  compress_feats=None, mfcc_f32=None, dither=None,
-                 input_transform=None, eot_size=None):
+                 input_transform=None, eot_size=None, feature_compression=None):
         locs = [m[2] for m in model_list]
         self.model_list = locs
         self.z_norm_means = np.array([m[3] for m in model_list], np.float64)
@@ -241,7 +286,7 @@ class gmm_CSI(_GmmSystem):
         models = [load_gmm_any(x) for x in locs]
         self._setup(group_id, models, [m[0] for m in model_list], [m[1] for m in model_list], locs,
                     self.z_norm_means, self.z_norm_stds, pre_model_dir, engine, text_scores, compress_feats, mfcc_f32, dither,
-                    input_transform, eot_size)
+                    input_transform, eot_size, feature_compression)
 
     def score(self, audios, fs=16000, bits_per_sample=16, debug=False, n_jobs=5):
         raw = self._raw(audios, bits_per_sample)
@@ -264,7 +309,7 @@ class gmm_SV(_GmmSystem):
 
     def __init__(self, spk_id, model, ubm, pre_model_dir="pre-models", threshold=0.0, engine=None,
                  text_scores=None, compress_feats=None, mfcc_f32=None, dither=None,
-                 input_transform=None, eot_size=None):
+                 input_transform=None, eot_size=None, feature_compression=None):
         self.threshold = threshold
         self.utt_id = model[1]
         self.identity_location = model[2]
@@ -272,7 +317,7 @@ class gmm_SV(_GmmSystem):
         models = [load_gmm_any(x) for x in self.model_list]
         self._setup(spk_id, models, [model[0]], [model[1]], [model[2]], None, None, pre_model_dir, engine,
                     text_scores, compress_feats, mfcc_f32, dither,
-                    input_transform, eot_size)
+                    input_transform, eot_size, feature_compression)
         self.spk_id = self.group_id
 
     def score(self, audios, fs=16000, bits_per_sample=16, debug=False, n_jobs=5):
@@ -295,7 +340,7 @@ class _IvSystem(object):
     PIPELINE = None
 
     def _setup(self, group_id, model_list, pre_model_dir, engine, system, text_scores=None, compress_feats=None, mfcc_f32=None, dither=None,
-               input_transform=None, eot_size=None):
+               input_transform=None, eot_size=None, feature_compression=None):
         from .models import IvectorSystem
         self.pre_model_dir = os.path.abspath(pre_model_dir)
         self.group_id = os.path.abspath(group_id)
@@ -330,6 +375,7 @@ class _IvSystem(object):
             system = system.with_enrolled(enrolled, zm, zs)
         _apply_input_transform(self._engine, input_transform)
         apply_eot(self._engine, eot_size)
+        apply_feature_compression(self._engine, feature_compression)
         self._engine.load_ivector(system, self.task)
 
     @property
@@ -353,10 +399,10 @@ class iv_OSI(_IvSystem):
 
     def __init__(self, group_id, model_list, pre_model_dir="pre-models", threshold=0.0, engine=None, system=None,
                  text_scores=None, compress_feats=None, mfcc_f32=None, dither=None,
-                 input_transform=None, eot_size=None):
+                 input_transform=None, eot_size=None, feature_compression=None):
         self.threshold = threshold
         self._setup(group_id, model_list, pre_model_dir, engine, system, text_scores, compress_feats, mfcc_f32, dither,
-                    input_transform, eot_size)
+                    input_transform, eot_size, feature_compression)
 
     def score(self, audio_list, fs=16000, bits_per_sample=16, n_jobs=10, debug=False):
         s = (self._llr(audio_list, bits_per_sample) - self.z_norm_means) / self.z_norm_stds   # :119
@@ -385,9 +431,9 @@ class iv_CSI(_IvSystem):
 
     def __init__(self, group_id, model_list, pre_model_dir="pre-models", engine=None, system=None, text_scores=None,
                  compress_feats=None, mfcc_f32=None, dither=None,
-                 input_transform=None, eot_size=None):
+                 input_transform=None, eot_size=None, feature_compression=None):
         self._setup(group_id, model_list, pre_model_dir, engine, system, text_scores, compress_feats, mfcc_f32, dither,
-                    input_transform, eot_size)
+                    input_transform, eot_size, feature_compression)
 
     def score(self, audio_list, fs=16000, bits_per_sample=16, n_jobs=10, debug=False):
         s = (self._llr(audio_list, bits_per_sample) - self.z_norm_means) / self.z_norm_stds
@@ -411,10 +457,10 @@ class iv_SV(_IvSystem):
 
     def __init__(self, spk_id, model, pre_model_dir="pre-models", threshold=0.0, engine=None, system=None,
                  text_scores=None, compress_feats=None, mfcc_f32=None, dither=None,
-                 input_transform=None, eot_size=None):
+                 input_transform=None, eot_size=None, feature_compression=None):
         self.threshold = threshold
         self._setup(spk_id, [model], pre_model_dir, engine, system, text_scores, compress_feats, mfcc_f32, dither,
-                    input_transform, eot_size)
+                    input_transform, eot_size, feature_compression)
         self.spk_id = self.group_id
         self.utt_id = model[1]
         self.identity_location = model[2]

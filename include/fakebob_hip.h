@@ -15,6 +15,8 @@
  *                             by gmm_ubm_kaldiHelper.py:133,153,191
  *   fb_set_input_transform    (none: the input-transformation defences of the paper's evaluation,
  *                             placed in front of the recogniser)
+ *   fb_set_feature_compression (none: SpeakerGuard's feature-level defence FeCo -- k-means over an utterance's
+ *                             frames, the cluster centres scored in their place)
  *   fb_score_i16 / _f64       gmm_ubm_kaldiHelper.score (:270-291) and the
  *                             int16 cast of gmm_ubm_OSI.py:83-85
  *   fb_system_scores          wrapper post-processing gmm_ubm_OSI.py:89,
@@ -221,6 +223,45 @@ int fb_set_input_transform(fb_engine *e, const fb_tf_stage *stages, int n);
  * value.  Not applied to foreign models (_ext, _dev), as the chain is not.  fb_estimate_threshold returns FB_E_STATE while
  * r > 1.  An attack whose (samples_per_draw + 1) * r exceeds 65535 rows returns FB_E_LIMIT. */
 int fb_set_eot(fb_engine *e, int r);
+
+/* ---- feature compression: a feature-level defence (SpeakerGuard's FeCo) -------------------------------------------------
+ * The victim clusters the T voiced feature vectors of an utterance with k-means and scores the k = ratio * T cluster centres
+ * instead of the frames.  The stage is SpeakerGuard's "final" one: behind VAD, deltas, CMVN and voiced-frame selection, in
+ * front of the GMM / gselect launches, one launch more per batch (k_feature_compress).  Randomised through the k-means
+ * initialisation: the case fb_set_eot was built for.
+ *  - applied to the features of every utterance whose scores the engine forms: fb_score_i16 / _f64, fb_get_grad, fb_attack,
+ *    fb_estimate_threshold, for GMM and i-vector systems, on every launch chain and MFCC route, with or without an
+ *    input-transform chain, dither and EOT (under fb_set_eot(r) the kernel sees the B * r replicated rows and draws an
+ *    initialisation per replica);
+ *  - NOT applied to foreign models (_ext, _dev), to fb_gmm_acc_stats (a decision: FeCo is a test-time defence, models are
+ *    enrolled on uncompressed features), to the fb_debug_mfcc / fb_debug_feats hooks (they stay the front end's) or to the
+ *    returned audio.  `tv` stays the VAD's count T (k > 0 exactly when T > 0); fb_stats' counters are unchanged (its
+ *    scored_frames counts the frames the front end produced, voiced or not, as before).
+ * fb_set_feature_compression(e, ratio, iters): 0 < ratio <= 1 and iters in 1 .. 64 switch it on; ratio = 0 with iters = 0
+ * switches it off (the default: no launch is added, no code path differs).  Anything else, NaN included, is FB_E_ARG and
+ * keeps the previous setting.
+ * Stage contract.  Exactly reproducible in numpy (the assignment is an arg-min: a tolerance cannot be tested, bits can):
+ *   input      X[T][D] float32, the voiced rows of ONE utterance row as the front end wrote them
+ *   size       k = max(1, (int)floor((double)T * ratio)): one float64 product, one floor.  T = 0 gives k = 0.
+ *   keys       frame t gets the 32-bit key = word (t & 3) of Philox4x32-10 with
+ *                key     = (seed_lo ^ 0x4645434F ("FECO"), seed_hi ^ stream)
+ *                counter = (t >> 2, 0x100 + replica, utterance row of the un-replicated batch, epoch)
+ *              seed, stream, epoch, replica and utterance row exactly by the rules of the "Noise RNG contract": in
+ *              fb_get_grad / fb_attack / fb_estimate_threshold the call's seed and stream and the NES iteration; in scoring
+ *              calls fb_set_dither_seed's seed, stream 0xFFFFFFFF and the scoring-call serial, which the call consumes
+ *   init       the k frames with the smallest (key, t) pairs are chosen; taken in ascending t they are the initial centres
+ *              0 .. k - 1 (float32 copies)
+ *   Lloyd      exactly `iters` iterations of {assign, update} (an implementation may stop once an iteration leaves every
+ *              assignment unchanged: the result cannot change any more)
+ *     assign   d(t, j): acc = 0; for dimension 0 .. D - 1 ascending: diff = x - c, sq = diff * diff, acc = acc + sq, each
+ *              rounded to float32, no fused multiply-add.  Frame t goes to the centre of smallest d; the lowest j wins a
+ *              tie (start at j = 0, replace on strict <)
+ *     update   a centre with n > 0 members becomes (float)(S / (double)n), S the float64 sum of its members' rows added
+ *              one by one in ascending t from 0.0, the division correctly rounded; a centre without members keeps its value
+ *   output     the k centres in cluster order are the utterance's rows; the row offsets are the prefix sums of the k's
+ * Deviations from SpeakerGuard: its k-means (kmeans_pytorch) runs to a tolerance on an unseeded generator and returns the
+ * centres in its own order; here the iteration count is fixed, the generator is keyed and the order is defined. */
+int fb_set_feature_compression(fb_engine *e, double ratio, int iters);
 
 const char *fb_last_error(void);
 int fb_version(void);

@@ -55,6 +55,19 @@ int fb_debug_tf_noise(fb_engine *e, uint64_t seed, uint32_t stream, uint32_t epo
 int fb_debug_input_transform_eot(fb_engine *e, const int16_t *wav, const int64_t *off, int B, int r, uint64_t seed,
                                  uint32_t stream, uint32_t epoch, int16_t *out);
 
+/* Feature compression (fakebob_hip.h: fb_set_feature_compression and its stage contract).
+ * fb_debug_feature_compress: the kernel the scoring paths launch, on feature rows handed in as they are (no front end, no
+ * model; D = the front end's feature dimension): feats holds the rows of B * r utterance rows one after the other,
+ * row_off[B * r + 1] their offsets (row_off[0] = 0; an empty row is allowed), row b * r + j being replica j of utterance b
+ * at (seed, stream, epoch) of the contract.  out (as many floats as feats) receives the compressed rows, out_off[B * r + 1]
+ * their offsets.  It uses the engine's ratio and iters (FB_E_STATE when the setting is off); the dither seed and the
+ * scoring-call serial are neither used nor advanced.
+ * fb_debug_feco_keys: keys[T] of the frames 0 .. T - 1 of (utterance `utt`, replica) at that point of the contract. */
+int fb_debug_feature_compress(fb_engine *e, const float *feats, const int *row_off, int B, int r, uint64_t seed,
+                              uint32_t stream, uint32_t epoch, float *out, int *out_off);
+int fb_debug_feco_keys(fb_engine *e, uint64_t seed, uint32_t stream, uint32_t epoch, uint32_t utt, int replica, int T,
+                       uint32_t *keys);
+
 /* What the front end of the last batch ran (fb_score_*, fb_get_grad, an NES iteration, fb_debug_mfcc / _feats, enrolment
  * statistics): info[5] = {the MFCC kernel, the chain after it, where the CompressedMatrix round trip ran, the longest
  * utterance of the batch in frames, the batch size}.  Recorded on the host when the kernels are enqueued; read only.
