@@ -267,15 +267,27 @@ class FakeBob(object):
 
     # -------------------------------------------------------------------- attack
     def attack(self, audio, checkpoint_path, threshold=0., true=None, target=None, fs=16000,
-               bits_per_sample=16, n_jobs=10, debug=False, noise_all=None):
+               bits_per_sample=16, n_jobs=10, debug=False, noise_all=None, companions=None):
         """FAKEBOB.py:139-221.  Returns (int16 adversarial audio (N,1), success_flag +-1) and
         writes the per-iteration trace [distance, adver_loss, score, used_time] to
         checkpoint_path (pickle protocol -1), like the reference.  used_time is each iteration's own time, read from
         the device clock where its loss is evaluated (fb_attack_iter_seconds; the loop runs inside the library), 0. on
         the early-stop row (:187).
-        noise_all (extension): (max_iter, N, samples_per_draw//2) normals to replay a NumPy run."""
+        noise_all (extension): (max_iter, N, samples_per_draw//2) normals to replay a NumPy run.
+        companions (extension; the engine's own systems): a list of float / int16 utterances, each exactly as long as
+        `audio` (ValueError otherwise: nothing is cropped silently), that ride along -- the attack searches for ONE
+        perturbation over all of them (fb_set_companions; the loop's losses are means over the utterances), for this
+        call only.  The returned pair is a companions.AttackResult: it also carries perturbation_i16,
+        apply_perturbation(wavs) and, with companions, per_utterance -- every composed utterance re-scored through
+        model.make_decisions, with its success."""
         audio = _col(audio)
         bits = _check_bits(bits_per_sample)
+        from . import companions as CP
+        comp = None
+        if companions is not None:
+            if not self._native:
+                raise ValueError("companions apply to the engine's own systems, not to a foreign model")
+            comp = CP.as_companions(companions, audio.shape[0], bits)
         self.threshold = threshold
         self.true = true
         self.target = target
@@ -285,7 +297,15 @@ class FakeBob(object):
         kw = dict(fs=fs, bits_per_sample=bits_per_sample, n_jobs=n_jobs, debug=debug)
         if self._native:
             eng = self.model.engine
-            adv, flag, _advf, trace = eng.attack(p, audio[:, 0], noise_all=noise_all)
+            if companions is None:
+                adv, flag, _advf, trace = eng.attack(p, audio[:, 0], noise_all=noise_all)
+            else:
+                before = eng.companions
+                eng.set_companions(comp)
+                try:
+                    adv, flag, _advf, trace = eng.attack(p, audio[:, 0], noise_all=noise_all)
+                finally:
+                    eng.set_companions(before)
         elif self._device:
             eng = self._engine()
             S = self._speakers(audio, **kw)
@@ -311,7 +331,17 @@ class FakeBob(object):
         if self.verbose:
             print("--- %d iters, distance:%f, loss:%f, %.1f iters/s ---" %
                   (n, trace[-1, 0], trace[-1, 1], n / dt if dt > 0 else 0.0))
-        return adv[:, np.newaxis], flag
+        a0 = CP.cast_i16(audio[:, 0], bits)
+        delta = adv.astype(np.int32) - a0.astype(np.int32)
+        per = None
+        if comp is not None:
+            per = []
+            rows = [adv] + CP.apply_perturbation(delta, list(comp))
+            for u, w in enumerate(rows):
+                dec, sc = self.model.make_decisions(w, **kw)
+                per.append(dict(utterance=u, audio_i16=w, decision=dec, score=sc,
+                                success=CP.succeeded(self.task, self.attack_type, dec, target=target, true=true)))
+        return CP.AttackResult(adv[:, np.newaxis], flag, delta, bits, per)
 
     # ------------------------------------------------------------------ get_grad
     def get_grad(self, audio, fs=16000, bits_per_sample=16, n_jobs=10, debug=False, iteration=0, noise_pos=None):

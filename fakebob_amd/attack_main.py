@@ -112,6 +112,20 @@ def build_attack_list(task, attack_type, model, test_dir, illegal_dir, out_audio
     return items
 
 
+def with_companions(items, idx, count):
+    """--companions: items[idx]'s audio and the next `count` utterances of its speaker (companions.pick_companions), all
+    cropped to the shortest of them -- printed, never silent -> (audio, list of companions; [] when the speaker has no
+    other utterance)."""
+    from .companions import crop_to_shortest, pick_companions
+    picks = pick_companions(items, idx, count)
+    wavs, n = crop_to_shortest([items[idx]["audio"]] + [items[i]["audio"] for i in picks])
+    cut = [(items[i]["name"], items[i]["audio"].shape[0]) for i in [idx] + picks if items[i]["audio"].shape[0] != n]
+    print("--- %s/%s: %d companions (%s), %d samples each%s ---" % (
+        items[idx]["spk"], items[idx]["name"], len(picks), ", ".join(items[i]["name"] for i in picks) or "none", n,
+        "".join("; %s cropped from %d" % c for c in cut)))
+    return wavs[0], wavs[1:]
+
+
 def main(argv=None, model_factory=None, bob_factory=None):
     """model_factory(architecture, task, model_list, pre_model_dir, threshold, group_id) / bob_factory(task,
     attack_type, model, **hyper_parameters): injection points for the driver-rule tests (a stub model / stub FakeBob
@@ -155,6 +169,10 @@ def main(argv=None, model_factory=None, bob_factory=None):
                     help="expectation over transformation against a randomised victim (a 'noise:' / 'at:' stage, --dither): "
                          "every NES sample is scored under this many independent draws and the losses are averaged "
                          "(1 .. 32); default: 1, or FB_EOT_SIZE")
+    ap.add_argument("--companions", dest="companions", default=0, type=int, metavar="N",
+                    help="universal perturbation: the next N utterances of the same speaker in the data directory ride along "
+                         "with every attacked one (1 .. 31, times --eot-size at most 32); all are cropped to the shortest, "
+                         "which is printed; default: 0")
     ap.add_argument("--model_dir", default="./model")
     ap.add_argument("--pre_model_dir", default="pre-models")
     ap.add_argument("--test_dir", default="./data/test-set")
@@ -244,6 +262,14 @@ def main(argv=None, model_factory=None, bob_factory=None):
             bob._stream = idx + 1         # Philox stream = global attack index: results do not depend on the sharding
             # the reference passes true= only for CSI untargeted (:346) and target= only for targeted attacks (:332,:367)
             true = it["true"] if (task == "CSI" and attack_type == "untargeted") else None
+            if args.companions > 0:
+                audio, comp = with_companions(items, idx, args.companions)
+                adv, flag = bob.attack(audio, it["cp_path"], threshold=threshold, true=true, target=it["target"], fs=fs,
+                                       bits_per_sample=bits_per_sample, companions=comp)
+                write(it["wav_path"], fs, adv)
+                with lock:
+                    results[idx] = flag
+                continue
             adv, flag = bob.attack(it["audio"], it["cp_path"], threshold=threshold, true=true,
                                    target=it["target"], fs=fs, bits_per_sample=bits_per_sample)
             write(it["wav_path"], fs, adv)

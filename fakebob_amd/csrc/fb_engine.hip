@@ -100,6 +100,11 @@ struct fb_engine {
   int eot = 1;                  // fb_set_eot: replicas of every NES row (1: none)
   int eot_run = 1;              // ... of the batch run_scoring is working on (enqueue_get_grad sets it around its call; else 1)
   DevBuf eot_sc, eot_l;         // k_loss_eot's per-replica scores [B * r][S] and losses [B * r]
+  // companion utterances (fb_set_companions; the "Composition" paragraph of fakebob_hip.h): comp_K1 == 0 -- none
+  int comp_K1 = 0;              // companions set; with the call's own utterance K = comp_K1 + 1
+  int64_t comp_N = 0;           // ... their length
+  DevBuf comp_wav, comp_a0;     // the companions [K1][N] and the int16 cast of the call's original audio [N] (cast once per call)
+  int comp_run = 1;             // K of the batch run_scoring is working on (set beside eot_run, which then counts K * eot; else 1)
   // feature compression (fb_set_feature_compression; the stage contract of fakebob_hip.h): feco_iters == 0 -- off, the back
   // end reads `feats` / `row_off` as the front end wrote them
   double feco_ratio = 0.0;
@@ -271,7 +276,7 @@ extern "C" int fb_engine_destroy(fb_engine *e) {
   if (!e) return FB_OK;
   (void)hipSetDevice(e->device);
   if (e->stream) (void)hipStreamSynchronize(e->stream);
-  DevBuf *bufs[] = {&e->fe_tables, &e->fe_tables32, &e->frame_ut, &e->tf_taps, &e->wav_tf, &e->tf_power, &e->eot_sc, &e->eot_l, &e->feats_fc, &e->row_off_fc, &e->feco_ws, &e->gmm_items, &e->gmm_images_bx, &e->gmm_images_fx, &e->gmm_images_fd, &e->gmm_images_fd2, &e->gmm_images_fd3, &e->gmm_anchor, &e->zmean, &e->zstd, &e->wav, &e->wav_off,
+  DevBuf *bufs[] = {&e->fe_tables, &e->fe_tables32, &e->frame_ut, &e->tf_taps, &e->wav_tf, &e->tf_power, &e->eot_sc, &e->eot_l, &e->comp_wav, &e->comp_a0, &e->feats_fc, &e->row_off_fc, &e->feco_ws, &e->gmm_items, &e->gmm_images_bx, &e->gmm_images_fx, &e->gmm_images_fd, &e->gmm_images_fd2, &e->gmm_images_fd3, &e->gmm_anchor, &e->zmean, &e->zstd, &e->wav, &e->wav_off,
                     &e->frame_rec, &e->vad_counter, &e->vad_pub, &e->vad_part, &e->fin_counter, &e->fin_xch, &e->ctl, &e->ctl_ls, &e->trace_dev, &e->ticks, &e->enr_ll, &e->enr_aux, &e->enr_stats, &e->frame_off, &e->chunk_off, &e->chunk_sum, &e->mfcc, &e->mfcc_cm, &e->vrank, &e->tv, &e->row_off, &e->dfeat, &e->feats,
                     &e->part_m, &e->part_s, &e->raw, &e->audio, &e->adver, &e->grad_m, &e->grad, &e->noise, &e->zbuf,
                     &e->scores, &e->loss, &e->dist_part, &e->nes_out, &e->stage_f64, &e->ext_x, &e->ext_z, &e->iv_fg, &e->iv_fg64, &e->iv_fgL, &e->iv_tri,
@@ -1260,7 +1265,8 @@ static int tf_noise_stages(const FbTfChain &ch, bool snr_only) {
 }
 // With e->eot_run = r > 1 (an NES batch under fb_set_eot) B counts the REPLICATED rows: e->wav holds B / r utterances of
 // equal length -- the first B / r + 1 entries of e->wav_off describe them -- and replica j of utterance u goes to row
-// u * r + j of e->wav_tf, every time and with an empty chain too.
+// u * r + j of e->wav_tf, every time and with an empty chain too.  With e->comp_run = K > 1 (fb_set_companions) r = K * eot
+// and the same launch composes: replica c * eot + j is draw j over utterance c of the row (k_input_transform_cmp).
 static int transformed_wav(fb_engine *e, const int64_t *off, int B, const int16_t **wav) {
   *wav = e->wav.as<int16_t>();
   const int r = e->eot_run;
@@ -1278,6 +1284,20 @@ static int transformed_wav(fb_engine *e, const int64_t *off, int B, const int16_
     FbTfRnd rn = e->nkey;
     rn.r = r;
     rn.power = nullptr;
+    if (e->comp_run > 1) {
+      const FbTfComp cn{e->comp_run, e->comp_N, e->comp_a0.as<int16_t>(), e->comp_wav.as<int16_t>()};
+      rn.r = r / cn.K;
+      if (tf_noise_stages(e->tf, true) > 0) {  // one E per (row, utterance), of the row as composed
+        FBCHK(e->tf_power.ensure(sizeof(unsigned long long) * (size_t)B_in * cn.K));
+        HIPCHK(fb_launch_tf_power_cmp(e->stream, e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), B_in, n_max,
+                                      e->tf_power.as<unsigned long long>(), cn, e->fe.stop));
+        rn.power = e->tf_power.as<unsigned long long>();
+      }
+      fb_launch_input_transform_cmp(e->stream, e->tf, e->tf_taps.as<double>(), e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), B_in,
+                                    n_max, e->wav_tf.as<int16_t>(), e->wav_off.as<int64_t>(), rn, cn, e->fe.stop);
+      *wav = e->wav_tf.as<int16_t>();
+      return FB_OK;
+    }
     if (tf_noise_stages(e->tf, true) > 0) {  // the SNR stages' E_u: a launch of its own, read by the next one only
       FBCHK(e->tf_power.ensure(sizeof(unsigned long long) * (size_t)B_in));
       HIPCHK(fb_launch_tf_power(e->stream, e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), B_in, n_max,
@@ -2099,6 +2119,29 @@ static int check_params(fb_engine *e, const fb_nes_params *p, int64_t N) {
   return FB_OK;
 }
 static inline int nes_bits(const fb_nes_params *p) { return p->bits_per_sample ? p->bits_per_sample : 16; }
+// replicas of every NES row the front end scores in the native NES calls: K * eot (fb_set_companions, fb_set_eot)
+static inline int nes_replicas(const fb_engine *e) { return (e->comp_K1 + 1) * e->eot; }
+// The checks and buffers of a native NES call that scale with the replicas.  B: the rows of the NES batch.
+static int prepare_nes_batch(fb_engine *e, int64_t N, int B);
+static int prepare_nes_replicas(fb_engine *e, int64_t N, int B) {
+  const int r = nes_replicas(e);
+  if (e->comp_K1 > 0 && N != e->comp_N)
+    return fb_fail(FB_E_ARG, "the audio has %lld samples, the companions (fb_set_companions) %lld", (long long)N, (long long)e->comp_N);
+  if (r > 32) return fb_fail(FB_E_ARG, "utterances * eot = %d replicas per NES row: at most 32", r);
+  if ((int64_t)B * r > 65535)
+    return fb_fail(FB_E_LIMIT, "(samples_per_draw + 1) * utterances * eot = %lld rows: a scoring batch takes up to 65535", (long long)B * r);
+  FBCHK(prepare_nes_batch(e, N, B * r));
+  if (r > 1) {
+    FBCHK(e->eot_sc.ensure(sizeof(double) * (size_t)B * r * (size_t)std::max(fb_num_speakers(e), 1)));
+    FBCHK(e->eot_l.ensure(sizeof(double) * (size_t)B * r));
+  }
+  if (e->comp_K1 > 0) FBCHK(e->comp_a0.ensure(sizeof(int16_t) * (size_t)N));
+  return FB_OK;
+}
+// a_0 of the composition: the int16 cast of the call's original audio (x: device float64 [N]), once per call
+static void cast_a0(fb_engine *e, const fb_nes_params *p, const double *x, int64_t N) {
+  if (e->comp_K1 > 0) fb_launch_quantize(e->stream, x, N, nes_bits(p), e->comp_a0.as<int16_t>());
+}
 
 // (re)builds the equal-length batch layout of B utterances of N samples
 static int prepare_nes_batch(fb_engine *e, int64_t N, int B) {
@@ -2184,7 +2227,7 @@ static FbLoopKnobs loop_knobs(const fb_engine *e, const FbScorer &sc) {
     const char *ev = getenv("FB_ATTACK_BATCH");
     const int b = ev ? atoi(ev) : 4;
     k.look = b < 1 ? 1 : (b > 16 ? 16 : b);
-    k.fuse_fin = fb_fuse_part(e, 1) && e->eot == 1;  // (fb_set_eot: the finalisation, then k_loss_eot)
+    k.fuse_fin = fb_fuse_part(e, 1) && nes_replicas(e) == 1;  // (fb_set_eot, fb_set_companions: the finalisation, then k_loss_eot)
     k.fuse_upd = fb_fuse_part(e, 2);
     const char *fu = getenv("FB_FUSE_UPD");
     k.upd_in_fin = !(fu && fu[0] == '0');
@@ -2204,7 +2247,7 @@ static int enqueue_get_grad(fb_engine *e, const fb_nes_params *p, int64_t N, uin
                             FbCtlDev *ctl = nullptr, double *trace_dev = nullptr, int trace_row = 0,
                             const FbUpdArgs *upd = nullptr, bool *upd_done = nullptr) {
   const int half = p->samples_per_draw / 2, B = 2 * half + 1;
-  const int r = e->eot, BR = B * r;  // fb_set_eot: the front end scores r replicas of every row
+  const int r = nes_replicas(e), BR = B * r;  // fb_set_eot, fb_set_companions: the front end scores r replicas of every row
   int ndp = 0;
   const int *stop = ctl ? &ctl->stop : nullptr;
   e->fe.stop = stop;
@@ -2240,8 +2283,10 @@ static int enqueue_get_grad(fb_engine *e, const fb_nes_params *p, int64_t N, uin
   e->nkey = fb_tf_rnd(p->seed, p->stream, iter, 0);
   e->fkey = fb_feco_key(0.0, 0, p->seed, p->stream, iter, 0);
   e->eot_run = r;
+  e->comp_run = e->comp_K1 + 1;
   const int rc = run_scoring(e, BR, e->h_frame_off[BR]);
   e->eot_run = 1;
+  e->comp_run = 1;
   e->tail_loss_req = false;
   e->defer_finalize = false;
   e->fe.stop = nullptr;
@@ -2454,14 +2499,7 @@ static int nes_setup(fb_engine *e, const fb_nes_params *p, int64_t N, FbScorer &
   const int B = 2 * (p->samples_per_draw / 2) + 1;
   if (native) {
     sc.S = fb_num_speakers(e);
-    const int r = e->eot;
-    if ((int64_t)B * r > 65535)
-      return fb_fail(FB_E_LIMIT, "(samples_per_draw + 1) * eot = %lld rows: a scoring batch takes up to 65535", (long long)B * r);
-    FBCHK(prepare_nes_batch(e, N, B * r));
-    if (r > 1) {
-      FBCHK(e->eot_sc.ensure(sizeof(double) * (size_t)B * r * (sc.S > 0 ? sc.S : 1)));
-      FBCHK(e->eot_l.ensure(sizeof(double) * (size_t)B * r));
-    }
+    FBCHK(prepare_nes_replicas(e, N, B));
     return ensure_nes_buffers(e, N, B);
   }
   FBCHK(sync_stream(e));
@@ -2492,6 +2530,7 @@ static int nes_gradient(fb_engine *e, const fb_nes_params *p, FbScorer sc, const
   if (!native) foreign_begin(e, sc, 3);  // k_perturb_f64 / k_perturb_x, k_loss, k_grad_update
   const int half = p->samples_per_draw / 2;
   FBCHK(h2d(e, e->adver.p, audio, sizeof(double) * (size_t)N));
+  if (native) cast_a0(e, p, e->adver.as<double>(), N);
   const double *noise_dev = nullptr;
   if (noise_pos && half > 0) {
     FBCHK(e->noise.ensure(sizeof(double) * (size_t)N * half));
@@ -2668,6 +2707,7 @@ static int run_attack(fb_engine *e, const fb_nes_params *p, FbScorer sc, const d
   // the device path's update and next batch in one launch: k_update_perturb_x instead of k_grad_update + k_perturb_x
   if (!native) foreign_begin(e, sc, fuses_update(kn, noise_all, half) ? 2 : 3);
   FBCHK(attack_start(e, audio, N, half, noise_all));
+  if (native) cast_a0(e, p, e->audio.as<double>(), N);
   double *trace_dev = nullptr;
   if (trace) {
     FBCHK(e->trace_dev.ensure(sizeof(double) * (size_t)p->max_iter * (3 + S)));
@@ -2772,6 +2812,8 @@ extern "C" int fb_estimate_threshold(fb_engine *e, const fb_nes_params *p_in, do
   if (p_in->task == FB_TASK_CSI) return fb_fail(FB_E_ARG, "no threshold to estimate for CSI (FAKEBOB.py:41-43)");
   if (e && e->eot > 1)
     return fb_fail(FB_E_STATE, "fb_estimate_threshold does not run under expectation over transformation (fb_set_eot(%d)): set 1", e->eot);
+  if (e && e->comp_K1 > 0)
+    return fb_fail(FB_E_STATE, "fb_estimate_threshold does not run with companion utterances (fb_set_companions: %d set): clear them", e->comp_K1);
   fb_nes_params q = *p_in;
   q.attack_type = FB_UNTARGETED;  // :73-74
   FbScorer sc{FB_SCORER_NATIVE};
@@ -3098,9 +3140,85 @@ extern "C" int fb_debug_input_transform(fb_engine *e, const int16_t *wav, const 
 extern "C" int fb_set_eot(fb_engine *e, int r) {
   if (!e) return fb_fail(FB_E_ARG, "null engine");
   if (r < 1 || r > 32) return fb_fail(FB_E_ARG, "EOT size %d outside 1 .. 32", r);
+  if ((e->comp_K1 + 1) * r > 32)
+    return fb_fail(FB_E_ARG, "EOT size %d with %d utterances (fb_set_companions): utterances * eot is at most 32", r, e->comp_K1 + 1);
   e->eot = r;
   e->bench_it = -1;  // an attack fb_bench_nes left resident was laid out for the previous size
   return FB_OK;
+}
+
+// ---- companion utterances: a universal perturbation
+extern "C" int fb_set_companions(fb_engine *e, const int16_t *wav, int K1, int64_t N) {
+  if (!e) return fb_fail(FB_E_ARG, "null engine");
+  if (K1 != 0) {
+    if (K1 < 1 || K1 > 31) return fb_fail(FB_E_ARG, "%d companions: 1 .. 31, or 0 for none", K1);
+    if (!wav) return fb_fail(FB_E_ARG, "wav is NULL");
+    if (N < 1 || N > 0x7fffffffLL) return fb_fail(FB_E_ARG, "companions of %lld samples: 1 .. 2^31 - 1", (long long)N);
+    if ((K1 + 1) * e->eot > 32)
+      return fb_fail(FB_E_ARG, "%d utterances under fb_set_eot(%d): utterances * eot is at most 32", K1 + 1, e->eot);
+    HIPCHK(hipSetDevice(e->device));
+    FBCHK(sync_stream(e));  // (nothing in flight reads the previous companions)
+    DevBuf nb;              // the previous setting stays whole until the new one is on the device
+    FBCHK(nb.ensure(sizeof(int16_t) * (size_t)K1 * (size_t)N));
+    int rc = h2d(e, nb.p, wav, sizeof(int16_t) * (size_t)K1 * (size_t)N);
+    if (rc == FB_OK) rc = sync_stream(e);
+    if (rc != FB_OK) {
+      nb.release();
+      return rc;
+    }
+    std::swap(e->comp_wav, nb);
+    nb.release();
+  }
+  e->comp_K1 = K1;
+  e->comp_N = K1 ? N : 0;
+  e->bench_it = -1;  // an attack fb_bench_nes left resident was laid out for the previous setting
+  return FB_OK;
+}
+
+extern "C" int fb_debug_compose(fb_engine *e, const int16_t *q, int B, int64_t N, const int16_t *a0, int r, uint64_t seed,
+                                uint32_t stream, uint32_t epoch, int16_t *out) {
+  if (!e || !q || !a0 || !out || B <= 0 || N <= 0 || N > 0x7fffffffLL || r < 1) return fb_fail(FB_E_ARG, "bad argument");
+  const int K = e->comp_K1 + 1, R = K * r;
+  if (R > 32 || (int64_t)B * R > 65535) return fb_fail(FB_E_ARG, "utterances * r = %d replicas per row (at most 32), %d rows", R, B);
+  if (e->comp_K1 > 0 && N != e->comp_N)
+    return fb_fail(FB_E_ARG, "rows of %lld samples, the companions (fb_set_companions) have %lld", (long long)N, (long long)e->comp_N);
+  std::vector<int64_t> off((size_t)B * R + 1);
+  for (size_t b = 0; b < off.size(); ++b) off[b] = (int64_t)b * N;
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  e->cached_B = -1;  // the scoring batch layout no longer describes e->wav / e->wav_off
+  e->bench_it = -1;
+  const size_t bytes = sizeof(int16_t) * (size_t)B * (size_t)N;
+  const bool snr = tf_noise_stages(e->tf, true) > 0;
+  DevBuf d_a0;
+  FBCHK(e->wav.ensure(bytes));
+  FBCHK(e->wav_tf.ensure(bytes * R));
+  FBCHK(e->wav_off.ensure(sizeof(int64_t) * off.size()));
+  if (snr) FBCHK(e->tf_power.ensure(sizeof(unsigned long long) * (size_t)B * K));
+  FBCHK(d_a0.ensure(sizeof(int16_t) * (size_t)N));
+  int rc = h2d(e, e->wav.p, q, bytes);
+  if (rc == FB_OK) rc = h2d(e, e->wav_off.p, off.data(), sizeof(int64_t) * off.size());
+  if (rc == FB_OK) rc = h2d(e, d_a0.p, a0, sizeof(int16_t) * (size_t)N);
+  if (rc == FB_OK) {
+    const FbTfComp cn{K, N, d_a0.as<int16_t>(), e->comp_wav.as<int16_t>()};
+    FbTfRnd rn = fb_tf_rnd(seed, stream, epoch, 0);
+    rn.r = r;
+    if (snr) {
+      if (fb_launch_tf_power_cmp(e->stream, e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), B, N,
+                                 e->tf_power.as<unsigned long long>(), cn, nullptr) != hipSuccess)
+        rc = fb_fail(FB_E_HIP, "zeroing the power words failed");
+      rn.power = e->tf_power.as<unsigned long long>();
+    }
+    if (rc == FB_OK) {
+      fb_launch_input_transform_cmp(e->stream, e->tf, e->tf_taps.as<double>(), e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), B, N,
+                                    e->wav_tf.as<int16_t>(), e->wav_off.as<int64_t>(), rn, cn, nullptr);
+      if (hipGetLastError() != hipSuccess) rc = fb_fail(FB_E_HIP, "the composing launch failed");
+    }
+  }
+  if (rc == FB_OK) rc = d2h(e, out, e->wav_tf.p, bytes * R);
+  const int rs = sync_stream(e);
+  d_a0.release();
+  return rc != FB_OK ? rc : rs;
 }
 
 extern "C" int fb_set_feature_compression(fb_engine *e, double ratio, int iters) {
@@ -3354,14 +3472,10 @@ extern "C" int fb_bench_nes(fb_engine *e, const fb_nes_params *p, const double *
       return fb_fail(FB_E_STATE, "fb_bench_nes(warmup < 0): no attack of this shape is resident on the engine");
     warmup = 0;
   } else {
-    if ((int64_t)B * e->eot > 65535) return fb_fail(FB_E_LIMIT, "(samples_per_draw + 1) * eot rows: a scoring batch takes up to 65535");
-    FBCHK(prepare_nes_batch(e, N, B * e->eot));
-    if (e->eot > 1) {
-      FBCHK(e->eot_sc.ensure(sizeof(double) * (size_t)B * e->eot * (size_t)std::max(fb_num_speakers(e), 1)));
-      FBCHK(e->eot_l.ensure(sizeof(double) * (size_t)B * e->eot));
-    }
+    FBCHK(prepare_nes_replicas(e, N, B));
     FBCHK(ensure_nes_buffers(e, N, B));
     FBCHK(attack_start(e, audio, N, half, nullptr));
+    cast_a0(e, p, e->audio.as<double>(), N);
     e->bench_it = 0;
     // identical work to fb_attack's loop (early stop disabled for timing)
     FBCHK(ctl_reset(e, p, true, true, nullptr));
@@ -3389,7 +3503,7 @@ extern "C" int fb_bench_nes(fb_engine *e, const fb_nes_params *p, const double *
   *ms_total = (double)ms;
   {
     int r = 0;
-    HIPCHK(hipMemcpy(&r, e->row_off.as<int>() + B * e->eot, sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&r, e->row_off.as<int>() + B * nes_replicas(e), sizeof(int), hipMemcpyDeviceToHost));
     vrows = r;
   }
   if (ms_gmm) *ms_gmm = gmm_ms;

@@ -77,6 +77,21 @@ hipError_t fb_launch_tf_power(hipStream_t s, const int16_t *wav, const int64_t *
 void fb_launch_input_transform_rnd(hipStream_t s, const FbTfChain &ch, const double *taps, const int16_t *wav,
                                    const int64_t *wav_off, int B, int64_t n_max, int16_t *out, const int64_t *out_off,
                                    const FbTfRnd &rn, const int *stop);
+// Companion utterances (fb_set_companions; the "Composition" paragraph of include/fakebob_hip.h): K utterances per NES row
+// -- the row itself and comp[K - 1][N] --, a0[N] the int16 cast of the call's original audio.  Every row of the batch is N long.
+struct FbTfComp {
+  int K;
+  int64_t N;
+  const int16_t *a0, *comp;
+};
+// the replicating launch over the composed utterances: NES row b of wav (B rows) is read once per tile and utterance, replica
+// rho = c * rn.r + j (utterance c, draw j) written at out_off[b * cn.K * rn.r + rho], its noise stages drawing with replica rho
+// and scaling by power[b * cn.K + c] (fb_launch_tf_power_cmp's layout)
+void fb_launch_input_transform_cmp(hipStream_t s, const FbTfChain &ch, const double *taps, const int16_t *wav,
+                                   const int64_t *wav_off, int B, int64_t n_max, int16_t *out, const int64_t *out_off,
+                                   const FbTfRnd &rn, const FbTfComp &cn, const int *stop);
+hipError_t fb_launch_tf_power_cmp(hipStream_t s, const int16_t *wav, const int64_t *wav_off, int B, int64_t n_max,
+                                  unsigned long long *power, const FbTfComp &cn, const int *stop);
 // z[n] = the normals a noise stage adds to samples i0 .. i0 + n - 1 of utterance rn.utt0 (fb_debug_tf_noise)
 void fb_launch_tf_noise(hipStream_t s, const FbTfRnd &rn, int replica, int stage, int64_t i0, int64_t n, float *z);
 

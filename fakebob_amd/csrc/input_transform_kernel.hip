@@ -74,13 +74,24 @@ static __device__ __forceinline__ double tf_noise_scale(int mode, double t0, uns
   return __dsqrt_rn(__ddiv_rn(__ddiv_rn((double)E, (double)n), t0));
 }
 
-template <bool RND>
-__global__ __launch_bounds__(TF_THREADS) void k_input_transform(FbTfChain ch, const double *__restrict__ taps,
-                                                                const int16_t *__restrict__ wav,
-                                                                const int64_t *__restrict__ wav_off,
-                                                                int16_t *__restrict__ out, const int *__restrict__ stop,
-                                                                const int64_t *__restrict__ out_off, FbTfRnd rn) {
-  extern __shared__ int16_t tf_lds[];
+// The composed read of fb_set_companions (CMP; the "Composition" paragraph of fakebob_hip.h): sample i of utterance c of NES
+// row b, whose int16 samples q start at `q`.  Utterance 0 is q itself; a companion takes the attacker's int16 difference
+// q - a0 on top of its own samples, int32 arithmetic, clipped before the chain sees it.
+static __device__ __forceinline__ int16_t tf_composed(const FbTfComp &cn, const int16_t *__restrict__ q, int c, int64_t i) {
+  const int v = q[i];
+  if (c == 0) return (int16_t)v;
+  return (int16_t)tf_clip16((int)cn.comp[(int64_t)(c - 1) * cn.N + i] + v - (int)cn.a0[i]);
+}
+
+// The body of k_input_transform (RND as described above) and of k_input_transform_cmp (CMP, which implies RND): with
+// companions the workgroup of (NES row u, tile) writes cn.K * rn.r replicas -- replica rho = c * rn.r + j is the chain's
+// draw j over utterance c as composed for this row.  The composed tile and its halo are formed once per utterance c, into
+// the buffer the replicas are run from: three int16 streams per sample, not per tap.
+template <bool RND, bool CMP>
+static __device__ __forceinline__ void tf_tile(int16_t *tf_lds, const FbTfChain &ch, const double *__restrict__ taps,
+                                               const int16_t *__restrict__ wav, const int64_t *__restrict__ wav_off,
+                                               int16_t *__restrict__ out, const int *__restrict__ stop,
+                                               const int64_t *__restrict__ out_off, const FbTfRnd &rn, const FbTfComp &cn) {
   if (stop && *stop) return;
   const int u = blockIdx.y;
   const int64_t base = wav_off[u];
@@ -95,15 +106,24 @@ __global__ __launch_bounds__(TF_THREADS) void k_input_transform(FbTfChain ch, co
   const int64_t g0 = t0 - H;
   for (int p = tid; p < W + TF_PAD; p += TF_THREADS) {
     const int64_t i = g0 + p;
-    src[p] = (p < W && i >= 0 && i < n) ? wav[base + i] : (int16_t)0;
+    if (!CMP) src[p] = (p < W && i >= 0 && i < n) ? wav[base + i] : (int16_t)0;
     if (p >= W) {
+      if (CMP) src[p] = 0;
       b[p] = 0;
       if (RND) a[p] = 0;
     }
   }
   __syncthreads();
-  const int reps = RND ? rn.r : 1;
+  const int reps = CMP ? cn.K * rn.r : (RND ? rn.r : 1);
   for (int rep = 0; rep < reps; ++rep) {
+  if (CMP && rep % rn.r == 0) {  // the next utterance (the replica before it has left the buffers: the barrier at the loop's end)
+    const int c = rep / rn.r;
+    for (int p = tid; p < W; p += TF_THREADS) {
+      const int64_t i = g0 + p;
+      src[p] = (i >= 0 && i < n) ? tf_composed(cn, wav + base, c, i) : (int16_t)0;
+    }
+    __syncthreads();
+  }
   if (RND) {
     a = src;
     b = tf_lds;  // the first stage reads src and writes the first working buffer
@@ -112,7 +132,7 @@ __global__ __launch_bounds__(TF_THREADS) void k_input_transform(FbTfChain ch, co
   for (int s = 0; s < ch.n; ++s) {
     const int kind = ch.kind[s], k = ch.k[s];
     if (RND && kind == FB_TF_NOISE) {
-      const double sc = tf_noise_scale(k, taps[ch.tap_off[s]], k ? rn.power[u] : 0ull, n);
+      const double sc = tf_noise_scale(k, taps[ch.tap_off[s]], k ? rn.power[CMP ? u * cn.K + rep / rn.r : u] : 0ull, n);
       // a lane owns the four samples of one Philox call: groups of four by ABSOLUTE index (i >> 2), whatever the tile
       const int64_t i_first = ((g0 + lo) >> 2) << 2;  // (arithmetic shift: rounds toward -inf for the halo in front of sample 0)
       for (int64_t i4 = i_first + 4 * tid; i4 < g0 + hi; i4 += 4 * TF_THREADS) {
@@ -206,6 +226,26 @@ __global__ __launch_bounds__(TF_THREADS) void k_input_transform(FbTfChain ch, co
   }
 }
 
+template <bool RND>
+__global__ __launch_bounds__(TF_THREADS) void k_input_transform(FbTfChain ch, const double *__restrict__ taps,
+                                                                const int16_t *__restrict__ wav,
+                                                                const int64_t *__restrict__ wav_off,
+                                                                int16_t *__restrict__ out, const int *__restrict__ stop,
+                                                                const int64_t *__restrict__ out_off, FbTfRnd rn) {
+  extern __shared__ int16_t tf_lds[];
+  tf_tile<RND, false>(tf_lds, ch, taps, wav, wav_off, out, stop, out_off, rn, FbTfComp{});
+}
+
+// fb_set_companions: the replicating launch over the composed utterances (rows of cn.N samples each, checked on the host)
+__global__ __launch_bounds__(TF_THREADS) void k_input_transform_cmp(FbTfChain ch, const double *__restrict__ taps,
+                                                                    const int16_t *__restrict__ wav,
+                                                                    const int64_t *__restrict__ wav_off,
+                                                                    int16_t *__restrict__ out, const int *__restrict__ stop,
+                                                                    const int64_t *__restrict__ out_off, FbTfRnd rn, FbTfComp cn) {
+  extern __shared__ int16_t tf_lds[];
+  tf_tile<true, true>(tf_lds, ch, taps, wav, wav_off, out, stop, out_off, rn, cn);
+}
+
 // E_u of the noise stage's SNR mode: the exact integer sum of squares of every utterance as it is handed to the chain.
 // One workgroup per (utterance, tile); 64-bit partial sums, one integer atomic per workgroup into the utterance's word
 // (zeroed by the launcher): integer addition is associative, so the result does not depend on the order.  Its only
@@ -233,6 +273,34 @@ __global__ __launch_bounds__(TF_THREADS) void k_tf_power(const int16_t *__restri
     unsigned long long t = 0;
     for (int w = 0; w < TF_THREADS / 64; ++w) t += s_part[w];
     atomicAdd(power + u, t);
+  }
+}
+
+// ... with companions: one E per (NES row b, utterance c), word b * K + c, of the row as composed -- what the chain is handed
+__global__ __launch_bounds__(TF_THREADS) void k_tf_power_cmp(const int16_t *__restrict__ wav, const int64_t *__restrict__ wav_off,
+                                                             unsigned long long *__restrict__ power, const int *__restrict__ stop,
+                                                             FbTfComp cn) {
+  if (stop && *stop) return;
+  const int b = blockIdx.y / cn.K, c = blockIdx.y % cn.K;
+  const int64_t base = wav_off[b];
+  const int64_t n = wav_off[b + 1] - base;
+  const int64_t t0 = (int64_t)blockIdx.x * FB_TF_TILE;
+  if (t0 >= n) return;
+  const int64_t t1 = t0 + FB_TF_TILE < n ? t0 + FB_TF_TILE : n;
+  unsigned long long acc = 0;
+  for (int64_t i = t0 + threadIdx.x; i < t1; i += TF_THREADS) {
+    const int v = tf_composed(cn, wav + base, c, i);
+    acc += (unsigned long long)(v * v);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  __shared__ unsigned long long s_part[TF_THREADS / 64];
+  if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long t = 0;
+    for (int w = 0; w < TF_THREADS / 64; ++w) t += s_part[w];
+    atomicAdd(power + blockIdx.y, t);
   }
 }
 
@@ -279,4 +347,21 @@ void fb_launch_input_transform_rnd(hipStream_t s, const FbTfChain &ch, const dou
   const unsigned tiles = (unsigned)((n_max + FB_TF_TILE - 1) / FB_TF_TILE);
   hipLaunchKernelGGL(k_input_transform<true>, dim3(tiles > 0 ? tiles : 1, B), dim3(TF_THREADS), fb_input_transform_lds_bytes(ch, true), s,
                      ch, taps, wav, wav_off, out, stop, out_off, rn);
+}
+
+hipError_t fb_launch_tf_power_cmp(hipStream_t s, const int16_t *wav, const int64_t *wav_off, int B, int64_t n_max,
+                                  unsigned long long *power, const FbTfComp &cn, const int *stop) {
+  const unsigned tiles = (unsigned)((n_max + FB_TF_TILE - 1) / FB_TF_TILE);
+  const hipError_t er = hipMemsetAsync(power, 0, sizeof(unsigned long long) * (size_t)B * cn.K, s);
+  if (er != hipSuccess) return er;
+  hipLaunchKernelGGL(k_tf_power_cmp, dim3(tiles > 0 ? tiles : 1, B * cn.K), dim3(TF_THREADS), 0, s, wav, wav_off, power, stop, cn);
+  return hipSuccess;
+}
+
+void fb_launch_input_transform_cmp(hipStream_t s, const FbTfChain &ch, const double *taps, const int16_t *wav,
+                                   const int64_t *wav_off, int B, int64_t n_max, int16_t *out, const int64_t *out_off,
+                                   const FbTfRnd &rn, const FbTfComp &cn, const int *stop) {
+  const unsigned tiles = (unsigned)((n_max + FB_TF_TILE - 1) / FB_TF_TILE);
+  hipLaunchKernelGGL(k_input_transform_cmp, dim3(tiles > 0 ? tiles : 1, B), dim3(TF_THREADS), fb_input_transform_lds_bytes(ch, true), s,
+                     ch, taps, wav, wav_off, out, stop, out_off, rn, cn);
 }

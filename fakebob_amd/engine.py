@@ -40,6 +40,7 @@ class Engine(object):
         self._L.fb_default_frontend(C.byref(self.cfg))
         self.input_transform = []
         self.eot = 1
+        self.companions = None
         self.feature_compression = None
 
     def close(self):
@@ -105,6 +106,39 @@ class Engine(object):
             raise ValueError("EOT size %d outside 1 .. 32" % r)
         N.check(self._L.fb_set_eot(self._h, C.c_int(r)))
         self.eot = r
+
+    def set_companions(self, wavs, bits_per_sample=16):
+        """Companion utterances (fb_set_companions): get_grad and attack then search for ONE perturbation over K = K1 + 1
+        utterances -- the audio of the call and these --, the losses and scores averaged over them (and over the EOT draws)
+        before the gradient estimate and the stop test.  wavs: an int16 array (K1, N) or a list of float / int16 utterances
+        of equal length N, the length of the audio the calls will attack; None (or an empty list) clears them.  ValueError for
+        unequal lengths, more than 31 companions or K * eot > 32.  The stop test reads the MEAN loss: see
+        FakeBob.attack(companions=...) for per-utterance results."""
+        from .companions import MAX_REPLICAS, as_companions
+        arr = as_companions(wavs, None, bits_per_sample)
+        if arr is None:
+            N.check(self._L.fb_set_companions(self._h, None, C.c_int(0), C.c_int64(0)))
+            self.companions = None
+            return
+        if (arr.shape[0] + 1) * self.eot > MAX_REPLICAS:
+            raise ValueError("%d utterances under eot %d: utterances * eot is at most %d" % (arr.shape[0] + 1, self.eot, MAX_REPLICAS))
+        N.check(self._L.fb_set_companions(self._h, N.ptr(arr), C.c_int(arr.shape[0]), C.c_int64(arr.shape[1])))
+        self.companions = arr
+
+    def debug_compose(self, q, a0, r, seed, stream, epoch):
+        """The int16 rows the composing launch writes (fb_debug_compose) for the hand-made NES rows q (B, N) and the cast
+        original a0 (N,), r draws per utterance at (seed, stream, epoch): an array (B, K, r, N), K - 1 the companions set."""
+        q = np.ascontiguousarray(q, np.int16)
+        q = q.reshape(1, -1) if q.ndim == 1 else q
+        a0 = np.ascontiguousarray(a0, np.int16).reshape(-1)
+        B, n = q.shape
+        if a0.size != n:
+            raise ValueError("a0 of %d samples, rows of %d" % (a0.size, n))
+        K = 1 if self.companions is None else self.companions.shape[0] + 1
+        out = np.empty((B, K, int(r), n), np.int16)
+        N.check(self._L.fb_debug_compose(self._h, N.ptr(q), C.c_int(B), C.c_int64(n), N.ptr(a0), C.c_int(int(r)),
+                                         C.c_uint64(int(seed)), C.c_uint32(int(stream)), C.c_uint32(int(epoch)), N.ptr(out)))
+        return out
 
     def set_feature_compression(self, ratio, iters=10):
         """Feature compression (fb_set_feature_compression; SpeakerGuard's FeCo): the engine clusters the voiced feature rows

@@ -122,6 +122,13 @@ def apply_eot(engine, eot_size):
         engine.set_eot(r)
 
 
+def apply_companions(engine, companions):
+    """Engine.set_companions for a system under construction: the `companions` keyword (a list of float / int16 utterances
+    of equal length, or an int16 array (K1, N)); None: the engine keeps its setting (none unless the caller set some)."""
+    if companions is not None:
+        engine.set_companions(companions)
+
+
 def parse_feco(spec):
     """A feature-compression spec -> (ratio, iters), or None for "none" / "off": "0.5" (10 iterations) or "0.5:10"; a number
     or a (ratio, iters) pair is taken as it is.  ValueError for anything else or outside 0 < ratio <= 1, iters 1 .. 64."""
@@ -206,7 +213,7 @@ class _GmmSystem(object):
     PIPELINE = None  # class default of the two round trips (see REFERENCE_PIPELINE)
 
     def _setup(self, group_id, models, spk_ids, utt_ids, locations, z_means, z_stds, pre_model_dir, engine,
-               text_scores=None, compress_feats=None, mfcc_f32=None, dither=None, input_transform=None, eot_size=None, feature_compression=None):
+               text_scores=None, compress_feats=None, mfcc_f32=None, dither=None, input_transform=None, eot_size=None, feature_compression=None, companions=None):
         self.pre_model_dir = os.path.abspath(pre_model_dir)
         self.group_id = os.path.abspath(group_id)
         self.spk_ids = spk_ids
@@ -219,6 +226,7 @@ class _GmmSystem(object):
         _apply_input_transform(self._engine, input_transform)
         apply_eot(self._engine, eot_size)
         apply_feature_compression(self._engine, feature_compression)
+        apply_companions(self._engine, companions)
         self._engine.load_gmm(models)
         self._engine.set_system(self.task, z_means, z_stds)
 
@@ -244,14 +252,14 @@ class gmm_OSI(_GmmSystem):
 
     def __init__(self, group_id, model_list, ubm, pre_model_dir="pre-models", threshold=0.0, engine=None,
                  text_scores=None, compress_feats=None, mfcc_f32=None, dither=None,
-                 input_transform=None, eot_size=None, feature_compression=None):
+                 input_transform=None, eot_size=None, feature_compression=None, companions=None):
         self.threshold = threshold
         locs = [m[2] for m in model_list]
         self.model_list = [ubm] + locs  # UBM first (gmm_ubm_OSI.py:45)
         models = [load_gmm_any(x) for x in self.model_list]
         self._setup(group_id, models, [m[0] for m in model_list], [m[1] for m in model_list], locs, None, None,
                     pre_model_dir, engine, text_scores, compress_feats, mfcc_f32, dither,
-                    input_transform, eot_size, feature_compression)
+                    input_transform, eot_size, feature_compression, companions)
 
     def score(self, audios, fs=16000, bits_per_sample=16, debug=False, n_jobs=5):
         raw = self._raw(audios, bits_per_sample)
@@ -278,7 +286,7 @@ class gmm_CSI(_GmmSystem):
 
     def __init__(self, group_id, model_list, pre_model_dir="pre-models", engine=None, text_scores=None,
                  compress_feats=None, mfcc_f32=None, dither=None,
-                 input_transform=None, eot_size=None, feature_compression=None):
+                 input_transform=None, eot_size=None, feature_compression=None, companions=None):
         locs = [m[2] for m in model_list]
         self.model_list = locs
         self.z_norm_means = np.array([m[3] for m in model_list], np.float64)
@@ -286,7 +294,7 @@ class gmm_CSI(_GmmSystem):
         models = [load_gmm_any(x) for x in locs]
         self._setup(group_id, models, [m[0] for m in model_list], [m[1] for m in model_list], locs,
                     self.z_norm_means, self.z_norm_stds, pre_model_dir, engine, text_scores, compress_feats, mfcc_f32, dither,
-                    input_transform, eot_size, feature_compression)
+                    input_transform, eot_size, feature_compression, companions)
 
     def score(self, audios, fs=16000, bits_per_sample=16, debug=False, n_jobs=5):
         raw = self._raw(audios, bits_per_sample)
@@ -309,7 +317,7 @@ class gmm_SV(_GmmSystem):
 
     def __init__(self, spk_id, model, ubm, pre_model_dir="pre-models", threshold=0.0, engine=None,
                  text_scores=None, compress_feats=None, mfcc_f32=None, dither=None,
-                 input_transform=None, eot_size=None, feature_compression=None):
+                 input_transform=None, eot_size=None, feature_compression=None, companions=None):
         self.threshold = threshold
         self.utt_id = model[1]
         self.identity_location = model[2]
@@ -317,7 +325,7 @@ class gmm_SV(_GmmSystem):
         models = [load_gmm_any(x) for x in self.model_list]
         self._setup(spk_id, models, [model[0]], [model[1]], [model[2]], None, None, pre_model_dir, engine,
                     text_scores, compress_feats, mfcc_f32, dither,
-                    input_transform, eot_size, feature_compression)
+                    input_transform, eot_size, feature_compression, companions)
         self.spk_id = self.group_id
 
     def score(self, audios, fs=16000, bits_per_sample=16, debug=False, n_jobs=5):
@@ -340,7 +348,7 @@ class _IvSystem(object):
     PIPELINE = None
 
     def _setup(self, group_id, model_list, pre_model_dir, engine, system, text_scores=None, compress_feats=None, mfcc_f32=None, dither=None,
-               input_transform=None, eot_size=None, feature_compression=None):
+               input_transform=None, eot_size=None, feature_compression=None, companions=None):
         from .models import IvectorSystem
         self.pre_model_dir = os.path.abspath(pre_model_dir)
         self.group_id = os.path.abspath(group_id)
@@ -376,6 +384,7 @@ class _IvSystem(object):
         _apply_input_transform(self._engine, input_transform)
         apply_eot(self._engine, eot_size)
         apply_feature_compression(self._engine, feature_compression)
+        apply_companions(self._engine, companions)
         self._engine.load_ivector(system, self.task)
 
     @property
@@ -399,10 +408,10 @@ class iv_OSI(_IvSystem):
 
     def __init__(self, group_id, model_list, pre_model_dir="pre-models", threshold=0.0, engine=None, system=None,
                  text_scores=None, compress_feats=None, mfcc_f32=None, dither=None,
-                 input_transform=None, eot_size=None, feature_compression=None):
+                 input_transform=None, eot_size=None, feature_compression=None, companions=None):
         self.threshold = threshold
         self._setup(group_id, model_list, pre_model_dir, engine, system, text_scores, compress_feats, mfcc_f32, dither,
-                    input_transform, eot_size, feature_compression)
+                    input_transform, eot_size, feature_compression, companions)
 
     def score(self, audio_list, fs=16000, bits_per_sample=16, n_jobs=10, debug=False):
         s = (self._llr(audio_list, bits_per_sample) - self.z_norm_means) / self.z_norm_stds   # :119
@@ -431,9 +440,9 @@ class iv_CSI(_IvSystem):
 
     def __init__(self, group_id, model_list, pre_model_dir="pre-models", engine=None, system=None, text_scores=None,
                  compress_feats=None, mfcc_f32=None, dither=None,
-                 input_transform=None, eot_size=None, feature_compression=None):
+                 input_transform=None, eot_size=None, feature_compression=None, companions=None):
         self._setup(group_id, model_list, pre_model_dir, engine, system, text_scores, compress_feats, mfcc_f32, dither,
-                    input_transform, eot_size, feature_compression)
+                    input_transform, eot_size, feature_compression, companions)
 
     def score(self, audio_list, fs=16000, bits_per_sample=16, n_jobs=10, debug=False):
         s = (self._llr(audio_list, bits_per_sample) - self.z_norm_means) / self.z_norm_stds
@@ -457,10 +466,10 @@ class iv_SV(_IvSystem):
 
     def __init__(self, spk_id, model, pre_model_dir="pre-models", threshold=0.0, engine=None, system=None,
                  text_scores=None, compress_feats=None, mfcc_f32=None, dither=None,
-                 input_transform=None, eot_size=None, feature_compression=None):
+                 input_transform=None, eot_size=None, feature_compression=None, companions=None):
         self.threshold = threshold
         self._setup(spk_id, [model], pre_model_dir, engine, system, text_scores, compress_feats, mfcc_f32, dither,
-                    input_transform, eot_size, feature_compression)
+                    input_transform, eot_size, feature_compression, companions)
         self.spk_id = self.group_id
         self.utt_id = model[1]
         self.identity_location = model[2]

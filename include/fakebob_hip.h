@@ -23,6 +23,8 @@
  *                             gmm_ubm_SV.py:77, gmm_ubm_CSI.py:93
  *   fb_set_eot                (none: SpeakerGuard's EOT_size -- every NES sample scored under several draws of a
  *                             randomised victim, the losses averaged)
+ *   fb_set_companions         (none: the universal perturbation of the speaker-recognition literature -- one delta for
+ *                             several utterances of a speaker, the losses averaged over them)
  *   fb_get_grad               FakeBob.get_grad + loss_fn (FAKEBOB.py:223-299)
  *   fb_attack                 FakeBob.attack (FAKEBOB.py:139-221)
  *   fb_estimate_threshold     FakeBob.estimate_threshold (FAKEBOB.py:39-137)
@@ -223,6 +225,41 @@ int fb_set_input_transform(fb_engine *e, const fb_tf_stage *stages, int n);
  * value.  Not applied to foreign models (_ext, _dev), as the chain is not.  fb_estimate_threshold returns FB_E_STATE while
  * r > 1.  An attack whose (samples_per_draw + 1) * r exceeds 65535 rows returns FB_E_LIMIT. */
 int fb_set_eot(fb_engine *e, int r);
+
+/* ---- companion utterances: one perturbation for several utterances (a "universal" attack) -----------------------------------
+ * fb_get_grad and fb_attack search for an adversarial version of ONE recording.  With companions set they search for one
+ * perturbation that works on K = K1 + 1 recordings at once: the utterance handed to the call stays utterance 0, `wav`
+ * [K1][N] int16 holds K1 more of exactly N samples each (copied).  It is the expectation fb_set_eot takes over the victim's
+ * coin flips, taken over utterances as well.
+ * Composition.  q_b[i]: the int16 sample the NES batch holds for row b (what k_perturb and the fused update write); a_0: the
+ * int16 cast of the ORIGINAL audio of the call (fb_get_grad's / fb_attack's `audio`), by the cast rule and bits_per_sample of
+ * the batch, made once per call; a_u: companion u = 1 .. K1.  Utterance u of NES row b is
+ *     w[b][0][i] = q_b[i]                                            (q_b itself: no a_0 - a_0 detour)
+ *     w[b][u][i] = clip(a_u[i] + q_b[i] - a_0[i], -32768, 32767)     int32 arithmetic
+ * -- the perturbation is exactly what the attacker would submit: the int16 difference, added to another recording.
+ * Row order.  Everything downstream sees r' = K * eot replicas of every NES row: replica rho = u * eot + j (utterance u, draw
+ * j of fb_set_eot) is row b * r' + rho of the batch the front end scores, and rho is the `replica` of the Noise, dither and
+ * FeCo contracts (K * eot <= 32 keeps stage index + 8 * rho below the 0x100 of FeCo's counter word).  The composition runs
+ * in the launch that already writes the replicas; the input-transform chain acts on the composed, clipped samples, indices
+ * outside [0, N) reading 0 as before; an SNR-mode noise stage takes its power E from the composed row (b, u), "as it is
+ * handed to the chain".
+ * Averaging.  fb_set_eot's rule with r' in place of r: system scores and loss_fn per replica row as always, then
+ *     loss[b] = (l[b][0] + ... + l[b][r' - 1]) / r',   scores[b][s] likewise
+ * in float64, rho ascending, one rounding per addition and one for the division.
+ * Everything behind the averaging is unchanged: the stop test on loss[0], the plateau rule, the trace row (averaged scores),
+ * the gradient estimate, the momentum sign step, the epsilon ball and the [-1, 1] clip around utterance 0's audio, the
+ * returned adv_i16 -- all utterance 0's, as is the trace's distance column.  The perturbation to carry over is adv_i16 - a_0.
+ * THE STOP TEST READS A MEAN, NOT A MAXIMUM: a mean loss below zero does not say that every utterance succeeded.
+ * adver_thresh is the margin a caller raises; the Python layer re-scores every composed utterance and reports each.
+ * fb_set_companions(e, wav, K1, N): 1 <= K1 <= 31, N >= 1 and K * eot <= 32 (checked here, in fb_set_eot -- a setting that
+ * would break the product is FB_E_ARG there and keeps the previous value -- and at the NES calls); K1 = 0 clears the companions
+ * (the default: no launch is added, no code path differs; wav and N are not read).  FB_E_ARG, the previous setting kept: K1
+ * out of range, wav NULL with K1 > 0, N out of range, or -- at fb_get_grad / fb_attack -- a call whose N differs from the
+ * companions'.  FB_E_NO_VOICED if ANY composed row has no voiced frames, as with EOT.  The fused finalisation and the
+ * i-vector tail-loss shortcut are off while K > 1, as they are for eot > 1; fb_stats counts what the front end scored (K * eot
+ * rows per NES row).  fb_estimate_threshold returns FB_E_STATE while companions are set.  Foreign models (_ext, _dev),
+ * fb_score_*, fb_gmm_acc_stats and the fb_debug_* hooks of the sections above ignore companions. */
+int fb_set_companions(fb_engine *e, const int16_t *wav, int K1, int64_t N);
 
 /* ---- feature compression: a feature-level defence (SpeakerGuard's FeCo) -------------------------------------------------
  * The victim clusters the T voiced feature vectors of an utterance with k-means and scores the k = ratio * T cluster centres

@@ -55,6 +55,16 @@ int fb_debug_tf_noise(fb_engine *e, uint64_t seed, uint32_t stream, uint32_t epo
 int fb_debug_input_transform_eot(fb_engine *e, const int16_t *wav, const int64_t *off, int B, int r, uint64_t seed,
                                  uint32_t stream, uint32_t epoch, int16_t *out);
 
+/* Companion utterances (fakebob_hip.h: fb_set_companions, "Composition" and "Row order").
+ * fb_debug_compose: the int16 rows the composing launch (the engine's input-transform chain included) writes for a hand-made
+ * batch: q[B][N] the NES rows, a0[N] the cast original, r the draws per utterance at (seed, stream, epoch) of the noise
+ * contract; out[B * K * r][N], replica u * r + j of row b at row b * K * r + u * r + j, K - 1 the engine's companions (none
+ * set: K = 1, the rows are the chain's over q).  N must be the companions'.  The engine's fb_set_eot value, dither seed and
+ * scoring-call serial are neither used nor advanced.
+ * (fb_bench_nes below times the attack loop as it is configured, companions included, as it does for fb_set_eot.) */
+int fb_debug_compose(fb_engine *e, const int16_t *q, int B, int64_t N, const int16_t *a0, int r, uint64_t seed,
+                     uint32_t stream, uint32_t epoch, int16_t *out);
+
 /* Feature compression (fakebob_hip.h: fb_set_feature_compression and its stage contract).
  * fb_debug_feature_compress: the kernel the scoring paths launch, on feature rows handed in as they are (no front end, no
  * model; D = the front end's feature dimension): feats holds the rows of B * r utterance rows one after the other,
