@@ -47,9 +47,26 @@ extern "C" int fb_device_count(void) {
   return n;
 }
 
+// A device allocation and its owner: freed when the buffer goes out of scope (with its engine, or at the end of the call
+// that made a temporary one); moving hands the allocation over and leaves the source empty
 struct DevBuf {
   void *p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+  DevBuf &operator=(DevBuf &&o) noexcept {
+    if (this != &o) {
+      release();
+      p = o.p;
+      cap = o.cap;
+      o.p = nullptr;
+      o.cap = 0;
+    }
+    return *this;
+  }
+  ~DevBuf() { release(); }
   int ensure(size_t bytes) {
     if (bytes <= cap) return FB_OK;
     if (p) (void)hipFree(p);
@@ -85,9 +102,8 @@ struct fb_engine {
   int melw_n = 0;  // packed mel weight count
   DevBuf fe_tables, fe_tables32;
   // Kaldi's dither (cfg.dither > 0; the "Dither RNG contract" of fakebob_hip.h)
-  uint64_t dither_seed = 0;     // fb_set_dither_seed: the key of scoring calls outside an attack
+  uint64_t dither_seed = 0;     // fb_set_dither_seed: the seed of scoring calls outside an attack (scoring_call_point)
   uint32_t dither_serial = 0;   // ... and their epoch: scoring calls since it was set
-  FbDitherKey dkey = {};        // what the next front-end launch carries: set by every path in front of launch_mfcc
   DevBuf frame_ut;              // [total_frames][2] {utterance, frame within it} of the batch (prepare_batch, dither > 0)
   std::vector<int32_t> h_frame_ut;
   // input-transform chain (fb_set_input_transform): tf.n == 0 -- none, launch_mfcc reads `wav` itself
@@ -95,21 +111,17 @@ struct fb_engine {
   DevBuf tf_taps;               // the FIR stages' taps, one after the other
   DevBuf wav_tf;                // the transformed batch, in wav's layout: what the MFCC reads when a chain is set
   // randomised stages and expectation over transformation (FB_TF_NOISE, fb_set_eot; the "Noise RNG contract" of fakebob_hip.h)
-  FbTfRnd nkey = {};            // the point of the noise contract the next transform launch stands at: set beside dkey
   DevBuf tf_power;              // k_tf_power's per-utterance sums of squares (chains with an SNR stage)
   int eot = 1;                  // fb_set_eot: replicas of every NES row (1: none)
-  int eot_run = 1;              // ... of the batch run_scoring is working on (enqueue_get_grad sets it around its call; else 1)
   DevBuf eot_sc, eot_l;         // k_loss_eot's per-replica scores [B * r][S] and losses [B * r]
   // companion utterances (fb_set_companions; the "Composition" paragraph of fakebob_hip.h): comp_K1 == 0 -- none
   int comp_K1 = 0;              // companions set; with the call's own utterance K = comp_K1 + 1
   int64_t comp_N = 0;           // ... their length
   DevBuf comp_wav, comp_a0;     // the companions [K1][N] and the int16 cast of the call's original audio [N] (cast once per call)
-  int comp_run = 1;             // K of the batch run_scoring is working on (set beside eot_run, which then counts K * eot; else 1)
   // feature compression (fb_set_feature_compression; the stage contract of fakebob_hip.h): feco_iters == 0 -- off, the back
   // end reads `feats` / `row_off` as the front end wrote them
   double feco_ratio = 0.0;
   int feco_iters = 0;
-  FbFeco fkey = {};             // the point of the contract the next k_feature_compress launch stands at: set beside nkey
   DevBuf feats_fc, row_off_fc;  // the compressed rows and their offsets: they swap roles with feats / row_off behind the launch
   DevBuf feco_ws;               // FB_FECO_WS_INTS ints per input row: the arrays of rows that do not fit the LDS
   // gmm
@@ -132,8 +144,6 @@ struct fb_engine {
   DevBuf iv_tail_counter;     // arrivals of the solve kernels' fused tail (fb_iv_tail.h)
   DevBuf gs_max, gs_tau, gs_list, gs_cnt, gs_flag, gs_gid;  // fb_launch_gsel's workspace (group maxima, thresholds, survivor lists, overflow flag; wide form: group ids)
   int gs_last_chunks = 0, gs_last_path = 0;  // the last i-vector batch: chunk count of the selection kernels, 0 dump / 1 k_gmm_fx2_sel / 2 k_gsel_w
-  bool tail_loss_req = false, tail_loss_done = false;  // enqueue_get_grad asks run_scoring to take the loss body along / it did
-  FbIvTail tail_req = {};
   unsigned iv_rw_epoch = 0;
   int iv_rw_B = -1, iv_rw_R = -1;
   bool iv_linv_dirty = false;  // k_iv_solve_ll used the slot buffer as plain scratch: refill before k_iv_solve_rw polls it
@@ -150,7 +160,6 @@ struct fb_engine {
   int bench_B = 0;
   long long pre_iter = -1;  // >= 0: wav / zbuf / dist_part already hold the NES batch of this iteration (k_update_perturb)
   int pre_ndp = 0;
-  bool defer_finalize = false;  // run_scoring leaves the GMM finalisation to the fused finalize + loss launch
   int vad_part_B = -1, vad_part_dim = -1;  // slot layout the sentinel-filled exchange buffer of k_vad_delta_cmvn_p was prepared for
   int ctl_seq = 0;         // loss bodies queued on the control block since its reset (FbCtlDev::pub_seq)
   unsigned vad_epoch = 0;  // launches of the fused VAD/CMVN kernels on vad_pub (its published counts carry the epoch)
@@ -276,13 +285,6 @@ extern "C" int fb_engine_destroy(fb_engine *e) {
   if (!e) return FB_OK;
   (void)hipSetDevice(e->device);
   if (e->stream) (void)hipStreamSynchronize(e->stream);
-  DevBuf *bufs[] = {&e->fe_tables, &e->fe_tables32, &e->frame_ut, &e->tf_taps, &e->wav_tf, &e->tf_power, &e->eot_sc, &e->eot_l, &e->comp_wav, &e->comp_a0, &e->feats_fc, &e->row_off_fc, &e->feco_ws, &e->gmm_items, &e->gmm_images_bx, &e->gmm_images_fx, &e->gmm_images_fd, &e->gmm_images_fd2, &e->gmm_images_fd3, &e->gmm_anchor, &e->zmean, &e->zstd, &e->wav, &e->wav_off,
-                    &e->frame_rec, &e->vad_counter, &e->vad_pub, &e->vad_part, &e->fin_counter, &e->fin_xch, &e->ctl, &e->ctl_ls, &e->trace_dev, &e->ticks, &e->enr_ll, &e->enr_aux, &e->enr_stats, &e->frame_off, &e->chunk_off, &e->chunk_sum, &e->mfcc, &e->mfcc_cm, &e->vrank, &e->tv, &e->row_off, &e->dfeat, &e->feats,
-                    &e->part_m, &e->part_s, &e->raw, &e->audio, &e->adver, &e->grad_m, &e->grad, &e->noise, &e->zbuf,
-                    &e->scores, &e->loss, &e->dist_part, &e->nes_out, &e->stage_f64, &e->ext_x, &e->ext_z, &e->iv_fg, &e->iv_fg64, &e->iv_fgL, &e->iv_tri,
-                    &e->iv_sim, &e->iv_u, &e->iv_backend, &e->iv_ll, &e->iv_sel, &e->iv_post, &e->iv_gamma,
-                    &e->iv_X, &e->iv_linp, &e->iv_quad, &e->iv_A, &e->iv_linv, &e->iv_prog, &e->iv_ticket, &e->iv_tail_counter, &e->gs_max, &e->gs_tau, &e->gs_list, &e->gs_cnt, &e->gs_flag, &e->gs_gid, &e->iv_bws, &e->iv_pairs, &e->iv_llf, &e->iv_ivec, &e->iv_fail, &e->iv_active};
-  for (DevBuf *b : bufs) b->release();
   if (e->h_out) (void)hipHostFree(e->h_out);
   if (e->h_tv) (void)hipHostFree(e->h_tv);
   if (e->ev0) (void)hipEventDestroy(e->ev0);
@@ -291,7 +293,7 @@ extern "C" int fb_engine_destroy(fb_engine *e) {
   if (e->h_ctl) (void)hipHostFree(e->h_ctl);
   if (e->pin) (void)hipHostFree(e->pin);
   if (e->stream) (void)hipStreamDestroy(e->stream);
-  delete e;
+  delete e;  // (the device buffers go with it: e->device is still the current one)
   return FB_OK;
 }
 
@@ -1263,13 +1265,43 @@ static int tf_noise_stages(const FbTfChain &ch, bool snr_only) {
   for (int s = 0; s < ch.n; ++s) c += ch.kind[s] == FB_TF_NOISE && (!snr_only || ch.k[s] == 1);
   return c;
 }
-// With e->eot_run = r > 1 (an NES batch under fb_set_eot) B counts the REPLICATED rows: e->wav holds B / r utterances of
+// What one scoring call tells run_scoring and the helpers under it about its batch.  It lives on the caller's stack for the
+// length of the call -- nothing of it is engine state --, and a default-constructed one plus a point is a scoring call
+// outside an attack: one replica per utterance, no stop flag, no loss tail.
+struct FbScoreCall {
+  FbRngPoint pt = {};            // where the call stands in the dither, noise and feature-compression contracts
+  int eot = 1;                   // draws of every utterance (fb_set_eot) ...
+  int K = 1;                     // ... and utterances of every NES row (fb_set_companions): the batch holds K * eot rows per NES row
+  const int *stop = nullptr;     // nullable device flag: != 0 -> the call's launches do nothing (attack already stopped)
+  bool defer_finalize = false;   // the GMM finalisation is left to the caller's fused finalize + loss launch
+  const FbIvTail *tail_loss = nullptr;  // i-vector systems: the loss body the solve kernels' tail should take along (null: none)
+  bool tail_loss_done = false;   // out: it did
+  int replicas() const { return K * eot; }
+};
+// The replicating / composing transform launch: rn.r replicas of every utterance of `in` (in_off[B_in + 1]; longest: n_max) --
+// with cn of every utterance of its composition -- written at out_off of `out`, behind the launch that leaves the chain's
+// SNR stages their sums of squares: one E per (row, utterance), of the row as composed
+static int launch_transform_replicas(fb_engine *e, const int16_t *in, const int64_t *in_off, int B_in, int64_t n_max, int16_t *out,
+                                     const int64_t *out_off, FbTfRnd rn, const FbTfComp *cn, const int *stop) {
+  rn.power = nullptr;
+  if (tf_noise_stages(e->tf, true) > 0) {  // a launch of its own, read by the next one only
+    FBCHK(e->tf_power.ensure(sizeof(unsigned long long) * (size_t)B_in * (cn ? cn->K : 1)));
+    unsigned long long *power = e->tf_power.as<unsigned long long>();
+    if (cn) HIPCHK(fb_launch_tf_power_cmp(e->stream, in, in_off, B_in, n_max, power, *cn, stop));
+    else HIPCHK(fb_launch_tf_power(e->stream, in, in_off, B_in, n_max, power, stop));
+    rn.power = power;
+  }
+  if (cn) fb_launch_input_transform_cmp(e->stream, e->tf, e->tf_taps.as<double>(), in, in_off, B_in, n_max, out, out_off, rn, *cn, stop);
+  else fb_launch_input_transform_rnd(e->stream, e->tf, e->tf_taps.as<double>(), in, in_off, B_in, n_max, out, out_off, rn, stop);
+  return FB_OK;
+}
+// With r = call.replicas() > 1 (an NES batch under fb_set_eot) B counts the REPLICATED rows: e->wav holds B / r utterances of
 // equal length -- the first B / r + 1 entries of e->wav_off describe them -- and replica j of utterance u goes to row
-// u * r + j of e->wav_tf, every time and with an empty chain too.  With e->comp_run = K > 1 (fb_set_companions) r = K * eot
-// and the same launch composes: replica c * eot + j is draw j over utterance c of the row (k_input_transform_cmp).
-static int transformed_wav(fb_engine *e, const int64_t *off, int B, const int16_t **wav) {
+// u * r + j of e->wav_tf, every time and with an empty chain too.  With call.K > 1 (fb_set_companions) the same launch
+// composes: replica c * eot + j is draw j over utterance c of the row (k_input_transform_cmp).
+static int transformed_wav(fb_engine *e, const FbScoreCall &call, const int64_t *off, int B, const int16_t **wav) {
   *wav = e->wav.as<int16_t>();
-  const int r = e->eot_run;
+  const int r = call.replicas();
   if (e->tf.n == 0 && r == 1) return FB_OK;
   if (B > 65535) return fb_fail(FB_E_LIMIT, "an input-transform chain takes batches of up to 65535 utterances");
   int64_t n_max = 0;
@@ -1278,52 +1310,28 @@ static int transformed_wav(fb_engine *e, const int64_t *off, int B, const int16_
   FBCHK(e->wav_tf.ensure(sizeof(int16_t) * (size_t)off[B]));
   if (r == 1 && tf_noise_stages(e->tf, false) == 0) {
     fb_launch_input_transform(e->stream, e->tf, e->tf_taps.as<double>(), e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), B, n_max,
-                              e->wav_tf.as<int16_t>(), e->fe.stop);
+                              e->wav_tf.as<int16_t>(), call.stop);
   } else {
-    const int B_in = B / r;
-    FbTfRnd rn = e->nkey;
-    rn.r = r;
-    rn.power = nullptr;
-    if (e->comp_run > 1) {
-      const FbTfComp cn{e->comp_run, e->comp_N, e->comp_a0.as<int16_t>(), e->comp_wav.as<int16_t>()};
-      rn.r = r / cn.K;
-      if (tf_noise_stages(e->tf, true) > 0) {  // one E per (row, utterance), of the row as composed
-        FBCHK(e->tf_power.ensure(sizeof(unsigned long long) * (size_t)B_in * cn.K));
-        HIPCHK(fb_launch_tf_power_cmp(e->stream, e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), B_in, n_max,
-                                      e->tf_power.as<unsigned long long>(), cn, e->fe.stop));
-        rn.power = e->tf_power.as<unsigned long long>();
-      }
-      fb_launch_input_transform_cmp(e->stream, e->tf, e->tf_taps.as<double>(), e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), B_in,
-                                    n_max, e->wav_tf.as<int16_t>(), e->wav_off.as<int64_t>(), rn, cn, e->fe.stop);
-      *wav = e->wav_tf.as<int16_t>();
-      return FB_OK;
-    }
-    if (tf_noise_stages(e->tf, true) > 0) {  // the SNR stages' E_u: a launch of its own, read by the next one only
-      FBCHK(e->tf_power.ensure(sizeof(unsigned long long) * (size_t)B_in));
-      HIPCHK(fb_launch_tf_power(e->stream, e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), B_in, n_max,
-                                e->tf_power.as<unsigned long long>(), e->fe.stop));
-      rn.power = e->tf_power.as<unsigned long long>();
-    }
-    fb_launch_input_transform_rnd(e->stream, e->tf, e->tf_taps.as<double>(), e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), B_in,
-                                  n_max, e->wav_tf.as<int16_t>(), e->wav_off.as<int64_t>(), rn, e->fe.stop);
+    const FbTfComp cn{call.K, e->comp_N, e->comp_a0.as<int16_t>(), e->comp_wav.as<int16_t>()};
+    FBCHK(launch_transform_replicas(e, e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), B / r, n_max, e->wav_tf.as<int16_t>(),
+                                    e->wav_off.as<int64_t>(), fb_tf_rnd(call.pt, call.eot), call.K > 1 ? &cn : nullptr, call.stop));
   }
   *wav = e->wav_tf.as<int16_t>();
   return FB_OK;
 }
 // MFCC of every frame of the batch prepared in e->wav: k_mfcc_f32 when the configuration asks for it, else k_mfcc_r16 / k_mfcc
-static int launch_mfcc(fb_engine *e, int B, int total_frames) {
-  const FbFrontendDev &fe = e->fe;
+// fe: the engine's front end as the call's launches take it (run_scoring: with the call's stop flag)
+static int launch_mfcc(fb_engine *e, const FbScoreCall &call, const FbFrontendDev &fe, int B, int total_frames) {
   hipStream_t s = e->stream;
   const int16_t *wav = nullptr;
-  FBCHK(transformed_wav(e, e->h_wav_off.data(), B, &wav));
+  FBCHK(transformed_wav(e, call, e->h_wav_off.data(), B, &wav));
   e->have_route = true;
   e->route[3] = e->t_max;
   e->route[4] = B;
-  // Kaldi's dither: the dithered form of the same kernel, with the key its caller left in e->dkey (the amplitude is the
-  // configuration's whatever the caller wrote)
+  // Kaldi's dither: the dithered form of the same kernel, keyed by the call's point
   const bool dither = e->cfg.dither > 0.0;
-  e->dkey.amp = e->cfg.dither;
-  const FbDitherKey *dk = dither ? &e->dkey : nullptr;
+  const FbDitherKey dith = fb_dither_key(call.pt, e->cfg.dither);
+  const FbDitherKey *dk = dither ? &dith : nullptr;
   const int32_t *ut = dither ? e->frame_ut.as<int32_t>() : nullptr;
   if (fe.mfcc_f32 && fb_launch_mfcc_f32(s, fe, e->melw_n, wav, e->frame_rec.as<int32_t>(), total_frames,
                                         e->mfcc.as<float>(), e->uni_T, e->uni_n, e->h_wav_off[0], &e->shape_mfcc, dk, ut))
@@ -1334,18 +1342,12 @@ static int launch_mfcc(fb_engine *e, int B, int total_frames) {
                                  e->frame_rec.as<int32_t>(), B, total_frames, e->mfcc.as<float>(), dk, ut);
   return FB_OK;
 }
-// the dither key of a scoring call outside an attack (fb_score_*, fb_gmm_acc_stats, fb_debug_mfcc / _feats): the engine's
-// seed, stream 0xFFFFFFFF, epoch = the scoring-call serial, which the call consumes
-static void dither_key_scoring_call(fb_engine *e) {
-  e->dkey = fb_dither_key(e->cfg.dither, e->dither_seed, 0xFFFFFFFFu, e->dither_serial, 0);
-  e->nkey = fb_tf_rnd(e->dither_seed, 0xFFFFFFFFu, e->dither_serial, 0);  // (the noise stages' key: the same rules)
-  e->fkey = fb_feco_key(0.0, 0, e->dither_seed, 0xFFFFFFFFu, e->dither_serial, 0);  // (... and feature compression's)
-  e->dither_serial += 1;
-}
+// the point of a scoring call outside an attack (fb_score_*, fb_gmm_acc_stats, fb_debug_mfcc / _feats): the engine's seed,
+// stream 0xFFFFFFFF, epoch = the scoring-call serial, which the call consumes
+static FbRngPoint scoring_call_point(fb_engine *e) { return FbRngPoint{e->dither_seed, 0xFFFFFFFFu, e->dither_serial++, 0}; }
 
 // mfcc -> VAD (+ row offsets) -> deltas -> CMVN -> voiced-row compaction
-static int run_post_mfcc(fb_engine *e, int B) {
-  const FbFrontendDev &fe = e->fe;
+static int run_post_mfcc(fb_engine *e, const FbFrontendDev &fe, int B) {
   hipStream_t s = e->stream;
   e->route[1] = FB_ROUTE_NONE;  // (until a chain is enqueued: a call that fails on the way reports none)
   e->route[2] = FB_ROUTE_NONE;
@@ -1424,18 +1426,15 @@ static int run_post_mfcc(fb_engine *e, int B) {
 // launch between the front end and the back end.  It reads e->feats / e->row_off and writes e->feats_fc / e->row_off_fc; the
 // two pairs then swap roles (the mfcc / mfcc_cm idiom of run_post_mfcc), so every launch behind it -- the GMM and gselect
 // kernels, the finalising launches, the i-vector chain -- takes the compressed rows and their counts from where it always did.
-// With e->eot_run = r > 1 B counts the replicated rows and row b * r + j draws replica j's initialisation.
-static int feature_compress(fb_engine *e, int B, int total_frames) {
+// With r = call.replicas() > 1 B counts the replicated rows and row b * r + j draws replica j's initialisation.
+static int feature_compress(fb_engine *e, const FbScoreCall &call, int B, int total_frames) {
   const int D = e->fe.dim;
   FBCHK(e->feats_fc.ensure(sizeof(float) * (size_t)total_frames * D));
   FBCHK(e->row_off_fc.ensure(sizeof(int) * (size_t)(B + 1)));
   FBCHK(e->feco_ws.ensure(sizeof(int) * (size_t)FB_FECO_WS_INTS * (size_t)(total_frames > 0 ? total_frames : 1)));
-  FbFeco fc = e->fkey;
-  fc.ratio = e->feco_ratio;
-  fc.iters = e->feco_iters;
-  fc.r = e->eot_run;
+  const FbFeco fc = fb_feco_key(call.pt, e->feco_ratio, e->feco_iters, call.replicas());
   if (!fb_launch_feature_compress(e->stream, fc, D, e->feats.as<float>(), e->row_off.as<int>(), B, e->t_max,
-                                  e->feats_fc.as<float>(), e->row_off_fc.as<int>(), e->feco_ws.as<int>(), e->fe.stop))
+                                  e->feats_fc.as<float>(), e->row_off_fc.as<int>(), e->feco_ws.as<int>(), call.stop))
     return fb_fail(FB_E_HIP, "k_feature_compress: the dynamic-LDS opt-in failed");
   std::swap(e->feats, e->feats_fc);
   std::swap(e->row_off, e->row_off_fc);
@@ -1443,25 +1442,27 @@ static int feature_compress(fb_engine *e, int B, int total_frames) {
 }
 
 // wav (device) + offsets (device) -> raw[B][M] (device).  Purely asynchronous.
-static int run_scoring(fb_engine *e, int B, int total_frames) {
-  const FbFrontendDev &fe = e->fe;
-  const FbGmmDev &g = e->gmm;
-  FBCHK(e->mfcc.ensure(sizeof(float) * (size_t)total_frames * fe.nc));
+static int run_scoring(fb_engine *e, FbScoreCall &call, int B, int total_frames) {
+  FBCHK(e->mfcc.ensure(sizeof(float) * (size_t)total_frames * e->fe.nc));
   FBCHK(e->vrank.ensure(sizeof(int) * (size_t)total_frames));
   FBCHK(e->tv.ensure(sizeof(int) * (size_t)B));
   FBCHK(e->row_off.ensure(sizeof(int) * (size_t)(B + 1)));
-  FBCHK(e->feats.ensure(sizeof(float) * (size_t)total_frames * fe.dim));
-  const int n_chunks = choose_chunks(g, total_frames, e->kind == 0);
+  FBCHK(e->feats.ensure(sizeof(float) * (size_t)total_frames * e->fe.dim));
+  const int n_chunks = choose_chunks(e->gmm, total_frames, e->kind == 0);
   if (e->kind == 0) {
-    FBCHK(e->part_m.ensure(sizeof(float) * (size_t)n_chunks * g.M * total_frames));
-    FBCHK(e->part_s.ensure(sizeof(float) * (size_t)n_chunks * g.M * total_frames));
+    FBCHK(e->part_m.ensure(sizeof(float) * (size_t)n_chunks * e->gmm.M * total_frames));
+    FBCHK(e->part_s.ensure(sizeof(float) * (size_t)n_chunks * e->gmm.M * total_frames));
   }
   FBCHK(e->raw.ensure(sizeof(double) * (size_t)B * e->n_out));
   hipStream_t s = e->stream;
   choose_launch_shape(e);
-  FBCHK(launch_mfcc(e, B, total_frames));
-  FBCHK(run_post_mfcc(e, B));
-  if (e->feco_iters > 0) FBCHK(feature_compress(e, B, total_frames));
+  // the kernel-argument structs as this call's launches take them (by value): the engine's, with the call's stop flag
+  FbFrontendDev fe = e->fe;
+  FbGmmDev g = e->gmm;
+  fe.stop = g.stop = call.stop;
+  FBCHK(launch_mfcc(e, call, fe, B, total_frames));
+  FBCHK(run_post_mfcc(e, fe, B));
+  if (e->feco_iters > 0) FBCHK(feature_compress(e, call, B, total_frames));
   if (e->kind == 0) {
     // A GPU shared by three or more attacks (fb_set_fused_chain(e, 0)): k_gmm_fx2w takes a whole compute unit per workgroup (one
     // wave per SIMD with the full register file), and so does k_mfcc_f32 (four waves per SIMD at 122 registers) -- with a
@@ -1474,7 +1475,7 @@ static int run_scoring(fb_engine *e, int B, int total_frames) {
     fb_launch_gmm(s, g, e->feats.as<float>(), e->row_off.as<int>() + B, total_frames, n_chunks,
                   e->part_m.as<float>(), e->part_s.as<float>(), &e->shape_gmm);
     FBCHK(time_end(e));
-    if (!e->defer_finalize)
+    if (!call.defer_finalize)
       fb_launch_gmm_finalize(s, g, e->part_m.as<float>(), e->part_s.as<float>(), total_frames, n_chunks,
                              e->row_off.as<int>(), B, e->raw.as<double>());
   } else {
@@ -1602,7 +1603,7 @@ static int run_scoring(fb_engine *e, int B, int total_frames) {
     FbIvTail tail = {};
     {
       const char *tv_env = getenv("FB_IV_TAIL");
-      const bool split = (tv_env && strcmp(tv_env, "split") == 0) || e->eot_run > 1;  // (fb_set_eot: k_loss_eot follows k_iv_backend)
+      const bool split = (tv_env && strcmp(tv_env, "split") == 0) || call.replicas() > 1;  // (fb_set_eot: k_loss_eot follows k_iv_backend)
       if (!e->iv_tail_counter.p) {
         FBCHK(e->iv_tail_counter.ensure(sizeof(int)));
         HIPCHK(hipMemsetAsync(e->iv_tail_counter.p, 0, sizeof(int), s));
@@ -1610,13 +1611,13 @@ static int run_scoring(fb_engine *e, int B, int total_frames) {
       // (LDA dimension > 512: the tail's 512 threads would take two l each in the PLDA partial sums where k_iv_backend's
       //  1024 take one -- a different summation grouping; such a system keeps the separate launch and its rounding)
       if (!split && iv.L <= 512) {
-        if (e->tail_loss_req && fb_iv_tail_takes_loss(B)) { tail = e->tail_req; tail.loss = 1; }
+        if (call.tail_loss && fb_iv_tail_takes_loss(B)) { tail = *call.tail_loss; tail.loss = 1; }
         tail.backend = 1;
         tail.llr = e->raw.as<double>();
         tail.counter = e->iv_tail_counter.as<int>();
       }
     }
-    e->tail_loss_done = tail.loss != 0;
+    call.tail_loss_done = tail.loss != 0;
     FBCHK(time_begin(e, 2));
     // FB_IV_SOLVE=ll keeps the one-workgroup-per-matrix kernel (A/B); otherwise the row-wise kernel whenever its grid of
     // 5 workgroups per matrix is resident at once, which is when the chip has idle units to give it
@@ -1685,8 +1686,8 @@ extern "C" int fb_score_i16(fb_engine *e, const int16_t *wav, const int64_t *off
   FBCHK(h2d(e, e->wav.p, wav, sizeof(int16_t) * (size_t)total));
   FBCHK(prepare_batch(e, off, B));
   e->cached_B = -1;
-  dither_key_scoring_call(e);
-  FBCHK(run_scoring(e, B, e->h_frame_off[B]));
+  FbScoreCall call{scoring_call_point(e)};
+  FBCHK(run_scoring(e, call, B, e->h_frame_off[B]));
   return finish_score(e, B, raw, tv);
 }
 
@@ -1705,8 +1706,8 @@ extern "C" int fb_score_f64(fb_engine *e, const double *audio, const int64_t *of
   fb_launch_quantize(e->stream, e->stage_f64.as<double>(), total, bits, e->wav.as<int16_t>());
   FBCHK(prepare_batch(e, off, B));
   e->cached_B = -1;
-  dither_key_scoring_call(e);
-  FBCHK(run_scoring(e, B, e->h_frame_off[B]));
+  FbScoreCall call{scoring_call_point(e)};
+  FBCHK(run_scoring(e, call, B, e->h_frame_off[B]));
   return finish_score(e, B, raw, tv);
 }
 
@@ -1971,8 +1972,6 @@ extern "C" int fb_load_ivector(fb_engine *e, const fb_ivector_system *sy, int ta
     HIPCHK(hipMemcpy(dS.p, sy->ie_sigma_inv, sizeof(double) * (size_t)C * triD, hipMemcpyHostToDevice));
     fb_launch_iv_derive(e->stream, C, D, R, dM.as<double>(), dS.as<double>(), e->iv_sim.as<double>(), e->iv_u.as<double>());
     FBCHK(sync_stream(e));
-    dM.release();
-    dS.release();
     e->iv.sim = e->iv_sim.as<double>();
     e->iv.u = e->iv_u.as<double>();
   }
@@ -2250,8 +2249,6 @@ static int enqueue_get_grad(fb_engine *e, const fb_nes_params *p, int64_t N, uin
   const int r = nes_replicas(e), BR = B * r;  // fb_set_eot, fb_set_companions: the front end scores r replicas of every row
   int ndp = 0;
   const int *stop = ctl ? &ctl->stop : nullptr;
-  e->fe.stop = stop;
-  e->gmm.stop = stop;
   if (ctl && e->pre_iter == (long long)iter && !noise_dev) {
     ndp = e->pre_ndp;  // the fused update of the previous iteration already wrote this batch
   } else {
@@ -2262,10 +2259,15 @@ static int enqueue_get_grad(fb_engine *e, const fb_nes_params *p, int64_t N, uin
   e->pre_iter = -1;
   // GMM systems inside the device-controlled loop: finalisation and loss share one launch
   const bool fuse_fin = ctl && e->kind == 0 && kn.fuse_fin;  // (never with fb_set_eot r > 1: loop_knobs)
-  e->defer_finalize = fuse_fin;
+  // Kaldi's dither, the noise stages and feature compression inside an attack: keyed by the attack's own (seed, stream),
+  // epoch = the NES iteration (in fb_estimate_threshold `iter` counts the call's front-end launches: one per pass of its loop)
+  FbScoreCall call{FbRngPoint{p->seed, p->stream, iter, 0}};
+  call.eot = e->eot;
+  call.K = e->comp_K1 + 1;
+  call.stop = stop;
+  call.defer_finalize = fuse_fin;
+  FbIvTail t = {};
   if (e->kind == 1 && r == 1) {  // i-vector systems: the loss body rides in the tail of the solve kernel when the batch allows it
-    FbIvTail &t = e->tail_req;
-    t = FbIvTail{};
     t.tv = e->tv.as<int>();
     t.task = p->task; t.attack_type = p->attack_type;
     t.z_mean = e->zmean.as<double>(); t.z_std = e->zstd.as<double>();
@@ -2274,24 +2276,9 @@ static int enqueue_get_grad(fb_engine *e, const fb_nes_params *p, int64_t N, uin
     t.dist_part = e->dist_part.as<double>(); t.n_dist_part = with_dist ? ndp : 0;
     t.scores = e->scores.as<double>(); t.loss_out = e->loss.as<double>();
     t.out = e->nes_out.as<FbNesDev>(); t.ctl = ctl; t.trace = trace_dev; t.it = trace_row;
-    e->tail_loss_req = true;
+    call.tail_loss = &t;
   }
-  e->tail_loss_done = false;
-  // Kaldi's dither inside an attack: keyed by the attack's own (seed, stream), epoch = the NES iteration (in
-  // fb_estimate_threshold `iter` counts the call's front-end launches: one per pass of its loop)
-  e->dkey = fb_dither_key(e->cfg.dither, p->seed, p->stream, iter, 0);
-  e->nkey = fb_tf_rnd(p->seed, p->stream, iter, 0);
-  e->fkey = fb_feco_key(0.0, 0, p->seed, p->stream, iter, 0);
-  e->eot_run = r;
-  e->comp_run = e->comp_K1 + 1;
-  const int rc = run_scoring(e, BR, e->h_frame_off[BR]);
-  e->eot_run = 1;
-  e->comp_run = 1;
-  e->tail_loss_req = false;
-  e->defer_finalize = false;
-  e->fe.stop = nullptr;
-  e->gmm.stop = nullptr;
-  FBCHK(rc);
+  FBCHK(run_scoring(e, call, BR, e->h_frame_off[BR]));
   if (r > 1) {
     fb_launch_loss_eot(e->stream, e->raw.as<double>(), e->tv.as<int>(), B, r, e->n_out, p->task, e->kind, p->attack_type,
                        e->zmean.as<double>(), e->zstd.as<double>(), p->threshold, p->adver_thresh, p->target, p->true_label,
@@ -2299,7 +2286,7 @@ static int enqueue_get_grad(fb_engine *e, const fb_nes_params *p, int64_t N, uin
                        e->scores.as<double>(), e->loss.as<double>(), e->nes_out.as<FbNesDev>(), ctl, trace_dev, trace_row);
     return FB_OK;
   }
-  if (e->tail_loss_done) return FB_OK;
+  if (call.tail_loss_done) return FB_OK;
   if (fuse_fin) {
     if (!e->fin_counter.p) {
       FBCHK(e->fin_counter.ensure(2 * sizeof(int)));   // [0] the arrival counter, [1] the fused launch's role ticket
@@ -2891,10 +2878,8 @@ extern "C" int fb_debug_noise(fb_engine *e, uint64_t seed, uint32_t iter, uint32
   DevBuf tmp;
   FBCHK(tmp.ensure(sizeof(float) * (size_t)N * half));
   fb_launch_noise(e->stream, seed, iter, stream, N, half, tmp.as<float>());
-  hipError_t er = hipMemcpyAsync(z, tmp.p, sizeof(float) * (size_t)N * half, hipMemcpyDeviceToHost, e->stream);
-  if (er == hipSuccess) er = hipStreamSynchronize(e->stream);
-  tmp.release();
-  if (er != hipSuccess) return fb_fail(FB_E_HIP, "noise dump failed: %s", hipGetErrorString(er));
+  HIPCHK(hipMemcpyAsync(z, tmp.p, sizeof(float) * (size_t)N * half, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
   return FB_OK;
 }
 
@@ -2913,8 +2898,8 @@ extern "C" int fb_debug_quantize(fb_engine *e, const double *x, int64_t n, int b
   return FB_OK;
 }
 
-// key (nullable): the point of the dither contract the utterance stands at; null = a scoring call of the engine's own
-static int debug_frontend(fb_engine *e, const int16_t *wav, int64_t n, const FbDitherKey *key = nullptr) {
+// pt (nullable): the point of the RNG contracts the utterance stands at; null = a scoring call of the engine's own
+static int debug_frontend(fb_engine *e, const int16_t *wav, int64_t n, const FbRngPoint *pt = nullptr) {
   if (!e || !wav || n <= 0) return fb_fail(FB_E_ARG, "bad argument");
   HIPCHK(hipSetDevice(e->device));
   FBCHK(sync_stream(e));
@@ -2931,14 +2916,9 @@ static int debug_frontend(fb_engine *e, const int16_t *wav, int64_t n, const FbD
   FBCHK(e->row_off.ensure(sizeof(int) * 2));
   FBCHK(e->feats.ensure(sizeof(float) * (size_t)T * fe.dim));
   choose_launch_shape(e);
-  if (key) {  // (the noise stages stand at the same point: the key's first word carries the seed's low half)
-    e->dkey = *key;
-    e->nkey = FbTfRnd{key->k0 ^ 0x44495448u ^ 0x4E4F4953u, key->k1, key->epoch, key->utt0, 1, nullptr};
-  } else {
-    dither_key_scoring_call(e);
-  }
-  FBCHK(launch_mfcc(e, 1, T));
-  FBCHK(run_post_mfcc(e, 1));
+  const FbScoreCall call{pt ? *pt : scoring_call_point(e)};
+  FBCHK(launch_mfcc(e, call, fe, 1, T));
+  FBCHK(run_post_mfcc(e, fe, 1));
   HIPCHK(hipGetLastError());
   return FB_OK;
 }
@@ -3011,9 +2991,9 @@ extern "C" int fb_gmm_delta_tiles_f6(fb_engine *e) {
   return wide ? e->gmm.delta_t6 - e->gmm.delta_t3 : 0;
 }
 
-static int debug_mfcc(fb_engine *e, const int16_t *wav, int64_t n, const FbDitherKey *key, float *mfcc, int *T_out) {
+static int debug_mfcc(fb_engine *e, const int16_t *wav, int64_t n, const FbRngPoint *pt, float *mfcc, int *T_out) {
   if (!mfcc) return fb_fail(FB_E_ARG, "mfcc is NULL");
-  FBCHK(debug_frontend(e, wav, n, key));
+  FBCHK(debug_frontend(e, wav, n, pt));
   const int T = e->h_frame_off[1];
   FBCHK(d2h(e, mfcc, e->mfcc.p, sizeof(float) * (size_t)T * e->fe.nc));
   FBCHK(sync_stream(e));
@@ -3025,8 +3005,8 @@ extern "C" int fb_debug_mfcc(fb_engine *e, const int16_t *wav, int64_t n, float 
 }
 extern "C" int fb_debug_mfcc_dither(fb_engine *e, const int16_t *wav, int64_t n, uint64_t seed, uint32_t stream,
                                     uint32_t epoch, uint32_t utt, float *mfcc, int *T_out) {
-  const FbDitherKey key = fb_dither_key(0.0, seed, stream, epoch, utt);
-  return debug_mfcc(e, wav, n, &key, mfcc, T_out);
+  const FbRngPoint pt{seed, stream, epoch, utt};
+  return debug_mfcc(e, wav, n, &pt, mfcc, T_out);
 }
 
 // the normals of the dither contract, from the device function the MFCC kernels call
@@ -3038,11 +3018,9 @@ extern "C" int fb_debug_dither_noise(fb_engine *e, uint64_t seed, uint32_t strea
   const size_t bytes = sizeof(float) * (size_t)n_frames * L;
   DevBuf tmp;
   FBCHK(tmp.ensure(bytes));
-  fb_launch_dither_noise(e->stream, fb_dither_key(1.0, seed, stream, epoch, utt), t0, n_frames, L, tmp.as<float>());
-  hipError_t er = hipMemcpyAsync(z, tmp.p, bytes, hipMemcpyDeviceToHost, e->stream);
-  if (er == hipSuccess) er = hipStreamSynchronize(e->stream);
-  tmp.release();
-  if (er != hipSuccess) return fb_fail(FB_E_HIP, "dither noise dump failed: %s", hipGetErrorString(er));
+  fb_launch_dither_noise(e->stream, fb_dither_key(FbRngPoint{seed, stream, epoch, utt}, 1.0), t0, n_frames, L, tmp.as<float>());
+  HIPCHK(hipMemcpyAsync(z, tmp.p, bytes, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
   return FB_OK;
 }
 
@@ -3097,12 +3075,10 @@ extern "C" int fb_set_input_transform(fb_engine *e, const fb_tf_stage *stages, i
   DevBuf fresh;
   if (!taps.empty()) {
     FBCHK(fresh.ensure(sizeof(double) * taps.size()));
-    int rc = h2d(e, fresh.p, taps.data(), sizeof(double) * taps.size());
-    if (rc == FB_OK) rc = sync_stream(e);
-    if (rc != FB_OK) { fresh.release(); return rc; }
+    FBCHK(h2d(e, fresh.p, taps.data(), sizeof(double) * taps.size()));
+    FBCHK(sync_stream(e));
   }
-  e->tf_taps.release();
-  e->tf_taps = fresh;
+  e->tf_taps = std::move(fresh);
   e->tf = ch;
   e->bench_it = -1;  // an attack fb_bench_nes left resident was scored through the previous chain
   return FB_OK;
@@ -3160,14 +3136,9 @@ extern "C" int fb_set_companions(fb_engine *e, const int16_t *wav, int K1, int64
     FBCHK(sync_stream(e));  // (nothing in flight reads the previous companions)
     DevBuf nb;              // the previous setting stays whole until the new one is on the device
     FBCHK(nb.ensure(sizeof(int16_t) * (size_t)K1 * (size_t)N));
-    int rc = h2d(e, nb.p, wav, sizeof(int16_t) * (size_t)K1 * (size_t)N);
-    if (rc == FB_OK) rc = sync_stream(e);
-    if (rc != FB_OK) {
-      nb.release();
-      return rc;
-    }
-    std::swap(e->comp_wav, nb);
-    nb.release();
+    FBCHK(h2d(e, nb.p, wav, sizeof(int16_t) * (size_t)K1 * (size_t)N));
+    FBCHK(sync_stream(e));
+    e->comp_wav = std::move(nb);
   }
   e->comp_K1 = K1;
   e->comp_N = K1 ? N : 0;
@@ -3189,36 +3160,21 @@ extern "C" int fb_debug_compose(fb_engine *e, const int16_t *q, int B, int64_t N
   e->cached_B = -1;  // the scoring batch layout no longer describes e->wav / e->wav_off
   e->bench_it = -1;
   const size_t bytes = sizeof(int16_t) * (size_t)B * (size_t)N;
-  const bool snr = tf_noise_stages(e->tf, true) > 0;
   DevBuf d_a0;
   FBCHK(e->wav.ensure(bytes));
   FBCHK(e->wav_tf.ensure(bytes * R));
   FBCHK(e->wav_off.ensure(sizeof(int64_t) * off.size()));
-  if (snr) FBCHK(e->tf_power.ensure(sizeof(unsigned long long) * (size_t)B * K));
   FBCHK(d_a0.ensure(sizeof(int16_t) * (size_t)N));
-  int rc = h2d(e, e->wav.p, q, bytes);
-  if (rc == FB_OK) rc = h2d(e, e->wav_off.p, off.data(), sizeof(int64_t) * off.size());
-  if (rc == FB_OK) rc = h2d(e, d_a0.p, a0, sizeof(int16_t) * (size_t)N);
-  if (rc == FB_OK) {
-    const FbTfComp cn{K, N, d_a0.as<int16_t>(), e->comp_wav.as<int16_t>()};
-    FbTfRnd rn = fb_tf_rnd(seed, stream, epoch, 0);
-    rn.r = r;
-    if (snr) {
-      if (fb_launch_tf_power_cmp(e->stream, e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), B, N,
-                                 e->tf_power.as<unsigned long long>(), cn, nullptr) != hipSuccess)
-        rc = fb_fail(FB_E_HIP, "zeroing the power words failed");
-      rn.power = e->tf_power.as<unsigned long long>();
-    }
-    if (rc == FB_OK) {
-      fb_launch_input_transform_cmp(e->stream, e->tf, e->tf_taps.as<double>(), e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), B, N,
-                                    e->wav_tf.as<int16_t>(), e->wav_off.as<int64_t>(), rn, cn, nullptr);
-      if (hipGetLastError() != hipSuccess) rc = fb_fail(FB_E_HIP, "the composing launch failed");
-    }
-  }
-  if (rc == FB_OK) rc = d2h(e, out, e->wav_tf.p, bytes * R);
-  const int rs = sync_stream(e);
-  d_a0.release();
-  return rc != FB_OK ? rc : rs;
+  FBCHK(h2d(e, e->wav.p, q, bytes));
+  FBCHK(h2d(e, e->wav_off.p, off.data(), sizeof(int64_t) * off.size()));
+  FBCHK(h2d(e, d_a0.p, a0, sizeof(int16_t) * (size_t)N));
+  const FbTfComp cn{K, N, d_a0.as<int16_t>(), e->comp_wav.as<int16_t>()};
+  FBCHK(launch_transform_replicas(e, e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), B, N, e->wav_tf.as<int16_t>(),
+                                  e->wav_off.as<int64_t>(), fb_tf_rnd(FbRngPoint{seed, stream, epoch, 0}, r), &cn, nullptr));
+  HIPCHK(hipGetLastError());
+  FBCHK(d2h(e, out, e->wav_tf.p, bytes * R));
+  FBCHK(sync_stream(e));
+  return FB_OK;
 }
 
 extern "C" int fb_set_feature_compression(fb_engine *e, double ratio, int iters) {
@@ -3249,31 +3205,26 @@ extern "C" int fb_debug_feature_compress(fb_engine *e, const float *feats, const
   HIPCHK(hipSetDevice(e->device));
   FBCHK(sync_stream(e));
   DevBuf d_in, d_off, d_out, d_ooff, d_ws;
-  int rc = d_in.ensure(sizeof(float) * total * D);
-  if (rc == FB_OK) rc = d_off.ensure(sizeof(int) * (size_t)(rows + 1));
-  if (rc == FB_OK) rc = d_out.ensure(sizeof(float) * total * D);
-  if (rc == FB_OK) rc = d_ooff.ensure(sizeof(int) * (size_t)(rows + 1));
-  if (rc == FB_OK) rc = d_ws.ensure(sizeof(int) * FB_FECO_WS_INTS * total);
-  if (rc == FB_OK) rc = h2d(e, d_in.p, feats, sizeof(float) * total * D);
-  if (rc == FB_OK) rc = h2d(e, d_off.p, row_off, sizeof(int) * (size_t)(rows + 1));
-  if (rc == FB_OK) {
-    FbFeco fc = fb_feco_key(e->feco_ratio, e->feco_iters, seed, stream, epoch, 0);
-    fc.r = r;
-    if (!fb_launch_feature_compress(e->stream, fc, D, d_in.as<float>(), d_off.as<int>(), rows, t_max, d_out.as<float>(),
-                                    d_ooff.as<int>(), d_ws.as<int>(), nullptr))
-      rc = fb_fail(FB_E_HIP, "k_feature_compress: the dynamic-LDS opt-in failed");
-    else if (hipGetLastError() != hipSuccess)
-      rc = fb_fail(FB_E_HIP, "the feature-compression launch failed");
-  }
+  FBCHK(d_in.ensure(sizeof(float) * total * D));
+  FBCHK(d_off.ensure(sizeof(int) * (size_t)(rows + 1)));
+  FBCHK(d_out.ensure(sizeof(float) * total * D));
+  FBCHK(d_ooff.ensure(sizeof(int) * (size_t)(rows + 1)));
+  FBCHK(d_ws.ensure(sizeof(int) * FB_FECO_WS_INTS * total));
+  FBCHK(h2d(e, d_in.p, feats, sizeof(float) * total * D));
+  FBCHK(h2d(e, d_off.p, row_off, sizeof(int) * (size_t)(rows + 1)));
+  const FbFeco fc = fb_feco_key(FbRngPoint{seed, stream, epoch, 0}, e->feco_ratio, e->feco_iters, r);
+  if (!fb_launch_feature_compress(e->stream, fc, D, d_in.as<float>(), d_off.as<int>(), rows, t_max, d_out.as<float>(),
+                                  d_ooff.as<int>(), d_ws.as<int>(), nullptr))
+    return fb_fail(FB_E_HIP, "k_feature_compress: the dynamic-LDS opt-in failed");
+  HIPCHK(hipGetLastError());
   // (k <= T per row: the compressed rows fit a buffer of the input's size; what lies behind them is left as it was)
-  if (rc == FB_OK) rc = d2h(e, out_off, d_ooff.p, sizeof(int) * (size_t)(rows + 1));
-  int rs = sync_stream(e);
-  if (rc == FB_OK && rs == FB_OK && out_off[rows] > 0) {
-    rc = d2h(e, out, d_out.p, sizeof(float) * (size_t)out_off[rows] * D);
-    rs = sync_stream(e);
+  FBCHK(d2h(e, out_off, d_ooff.p, sizeof(int) * (size_t)(rows + 1)));
+  FBCHK(sync_stream(e));
+  if (out_off[rows] > 0) {
+    FBCHK(d2h(e, out, d_out.p, sizeof(float) * (size_t)out_off[rows] * D));
+    FBCHK(sync_stream(e));
   }
-  for (DevBuf *b : {&d_in, &d_off, &d_out, &d_ooff, &d_ws}) b->release();
-  return rc != FB_OK ? rc : rs;
+  return FB_OK;
 }
 
 extern "C" int fb_debug_feco_keys(fb_engine *e, uint64_t seed, uint32_t stream, uint32_t epoch, uint32_t utt, int replica, int T,
@@ -3283,11 +3234,10 @@ extern "C" int fb_debug_feco_keys(fb_engine *e, uint64_t seed, uint32_t stream, 
   FBCHK(sync_stream(e));
   DevBuf tmp;
   FBCHK(tmp.ensure(sizeof(uint32_t) * (size_t)T));
-  fb_launch_feco_keys(e->stream, fb_feco_key(0.0, 0, seed, stream, epoch, utt), replica, T, tmp.as<uint32_t>());
-  hipError_t er = hipMemcpyAsync(keys, tmp.p, sizeof(uint32_t) * (size_t)T, hipMemcpyDeviceToHost, e->stream);
-  if (er == hipSuccess) er = hipStreamSynchronize(e->stream);
-  tmp.release();
-  if (er != hipSuccess) return fb_fail(FB_E_HIP, "key dump failed: %s", hipGetErrorString(er));
+  // (the keys depend on the point alone, not on the setting)
+  fb_launch_feco_keys(e->stream, fb_feco_key(FbRngPoint{seed, stream, epoch, utt}, e->feco_ratio, e->feco_iters), replica, T, tmp.as<uint32_t>());
+  HIPCHK(hipMemcpyAsync(keys, tmp.p, sizeof(uint32_t) * (size_t)T, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
   return FB_OK;
 }
 
@@ -3299,11 +3249,9 @@ extern "C" int fb_debug_tf_noise(fb_engine *e, uint64_t seed, uint32_t stream, u
   FBCHK(sync_stream(e));
   DevBuf tmp;
   FBCHK(tmp.ensure(sizeof(float) * (size_t)n));
-  fb_launch_tf_noise(e->stream, fb_tf_rnd(seed, stream, epoch, utt), replica, stage, i0, n, tmp.as<float>());
-  hipError_t er = hipMemcpyAsync(z, tmp.p, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, e->stream);
-  if (er == hipSuccess) er = hipStreamSynchronize(e->stream);
-  tmp.release();
-  if (er != hipSuccess) return fb_fail(FB_E_HIP, "noise dump failed: %s", hipGetErrorString(er));
+  fb_launch_tf_noise(e->stream, fb_tf_rnd(FbRngPoint{seed, stream, epoch, utt}), replica, stage, i0, n, tmp.as<float>());
+  HIPCHK(hipMemcpyAsync(z, tmp.p, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
   return FB_OK;
 }
 
@@ -3330,27 +3278,15 @@ extern "C" int fb_debug_input_transform_eot(fb_engine *e, const int16_t *wav, co
   FBCHK(e->wav_tf.ensure(bytes * r));
   FBCHK(e->wav_off.ensure(sizeof(int64_t) * (B + 1)));
   FBCHK(d_out_off.ensure(sizeof(int64_t) * out_off.size()));
-  int rc = h2d(e, e->wav.p, wav, bytes);
-  if (rc == FB_OK) rc = h2d(e, e->wav_off.p, off, sizeof(int64_t) * (B + 1));
-  if (rc == FB_OK) rc = h2d(e, d_out_off.p, out_off.data(), sizeof(int64_t) * out_off.size());
-  if (rc == FB_OK && tf_noise_stages(e->tf, true) > 0) rc = e->tf_power.ensure(sizeof(unsigned long long) * (size_t)B);
-  if (rc == FB_OK) {
-    FbTfRnd rn = fb_tf_rnd(seed, stream, epoch, 0);
-    rn.r = r;
-    if (tf_noise_stages(e->tf, true) > 0) {
-      if (fb_launch_tf_power(e->stream, e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), B, n_max,
-                             e->tf_power.as<unsigned long long>(), nullptr) != hipSuccess)
-        rc = fb_fail(FB_E_HIP, "zeroing the power words failed");
-      rn.power = e->tf_power.as<unsigned long long>();
-    }
-    fb_launch_input_transform_rnd(e->stream, e->tf, e->tf_taps.as<double>(), e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), B, n_max,
-                                  e->wav_tf.as<int16_t>(), d_out_off.as<int64_t>(), rn, nullptr);
-    if (hipGetLastError() != hipSuccess) rc = fb_fail(FB_E_HIP, "the transform launch failed");
-  }
-  if (rc == FB_OK) rc = d2h(e, out, e->wav_tf.p, bytes * r);
-  const int rs = sync_stream(e);
-  d_out_off.release();
-  return rc != FB_OK ? rc : rs;
+  FBCHK(h2d(e, e->wav.p, wav, bytes));
+  FBCHK(h2d(e, e->wav_off.p, off, sizeof(int64_t) * (B + 1)));
+  FBCHK(h2d(e, d_out_off.p, out_off.data(), sizeof(int64_t) * out_off.size()));
+  FBCHK(launch_transform_replicas(e, e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), B, n_max, e->wav_tf.as<int16_t>(),
+                                  d_out_off.as<int64_t>(), fb_tf_rnd(FbRngPoint{seed, stream, epoch, 0}, r), nullptr, nullptr));
+  HIPCHK(hipGetLastError());
+  FBCHK(d2h(e, out, e->wav_tf.p, bytes * r));
+  FBCHK(sync_stream(e));
+  return FB_OK;
 }
 
 extern "C" int fb_set_dither_seed(fb_engine *e, uint64_t seed) {
@@ -3360,18 +3296,18 @@ extern "C" int fb_set_dither_seed(fb_engine *e, uint64_t seed) {
   return FB_OK;
 }
 
-static int debug_feats(fb_engine *e, const int16_t *wav, int64_t n, const FbDitherKey *key, float *feats, int *Tv, int *T_out);
+static int debug_feats(fb_engine *e, const int16_t *wav, int64_t n, const FbRngPoint *pt, float *feats, int *Tv, int *T_out);
 extern "C" int fb_debug_feats(fb_engine *e, const int16_t *wav, int64_t n, float *feats, int *Tv, int *T_out) {
   return debug_feats(e, wav, n, nullptr, feats, Tv, T_out);
 }
 extern "C" int fb_debug_feats_dither(fb_engine *e, const int16_t *wav, int64_t n, uint64_t seed, uint32_t stream,
                                      uint32_t epoch, uint32_t utt, float *feats, int *Tv, int *T_out) {
-  const FbDitherKey key = fb_dither_key(0.0, seed, stream, epoch, utt);
-  return debug_feats(e, wav, n, &key, feats, Tv, T_out);
+  const FbRngPoint pt{seed, stream, epoch, utt};
+  return debug_feats(e, wav, n, &pt, feats, Tv, T_out);
 }
-static int debug_feats(fb_engine *e, const int16_t *wav, int64_t n, const FbDitherKey *key, float *feats, int *Tv, int *T_out) {
+static int debug_feats(fb_engine *e, const int16_t *wav, int64_t n, const FbRngPoint *pt, float *feats, int *Tv, int *T_out) {
   if (!feats || !Tv) return fb_fail(FB_E_ARG, "null output");
-  FBCHK(debug_frontend(e, wav, n, key));
+  FBCHK(debug_frontend(e, wav, n, pt));
   const int T = e->h_frame_off[1];
   int tv = 0;
   FBCHK(d2h(e, &tv, e->tv.p, sizeof(int)));

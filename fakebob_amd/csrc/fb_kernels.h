@@ -36,8 +36,14 @@ struct FbDitherKey {
   double amp;
   uint32_t k0, k1, epoch, utt0;
 };
-static inline FbDitherKey fb_dither_key(double amp, uint64_t seed, uint32_t stream, uint32_t epoch, uint32_t utt0) {
-  return FbDitherKey{amp, (uint32_t)seed ^ 0x44495448u, (uint32_t)(seed >> 32) ^ stream, epoch, utt0};
+// The point of the RNG contracts a launch stands at (host side): the dither, noise and feature-compression keys below are
+// derived from it at the launch that needs them, each with its own domain constant
+struct FbRngPoint {
+  uint64_t seed;
+  uint32_t stream, epoch, utt0;
+};
+static inline FbDitherKey fb_dither_key(const FbRngPoint &pt, double amp) {
+  return FbDitherKey{amp, (uint32_t)pt.seed ^ 0x44495448u, (uint32_t)(pt.seed >> 32) ^ pt.stream, pt.epoch, pt.utt0};
 }
 // the normals the dithered MFCC kernels add to frames t0 .. t0 + n_frames - 1 of utterance dk.utt0: z[n_frames][L]
 void fb_launch_dither_noise(hipStream_t s, const FbDitherKey &dk, int t0, int n_frames, int L, float *z);
@@ -65,8 +71,8 @@ struct FbTfRnd {
   int r;
   const unsigned long long *power;
 };
-static inline FbTfRnd fb_tf_rnd(uint64_t seed, uint32_t stream, uint32_t epoch, uint32_t utt0) {
-  return FbTfRnd{(uint32_t)seed ^ 0x4E4F4953u, (uint32_t)(seed >> 32) ^ stream, epoch, utt0, 1, nullptr};
+static inline FbTfRnd fb_tf_rnd(const FbRngPoint &pt, int r = 1) {
+  return FbTfRnd{(uint32_t)pt.seed ^ 0x4E4F4953u, (uint32_t)(pt.seed >> 32) ^ pt.stream, pt.epoch, pt.utt0, r, nullptr};
 }
 // power[u] = the exact sum of squares of utterance u of wav (zeroed here, then one integer atomic per tile); honours `stop`
 // returns the memset's status
@@ -104,8 +110,8 @@ struct FbFeco {
   uint32_t k0, k1, epoch, utt0;
   int r;
 };
-static inline FbFeco fb_feco_key(double ratio, int iters, uint64_t seed, uint32_t stream, uint32_t epoch, uint32_t utt0) {
-  return FbFeco{ratio, iters, (uint32_t)seed ^ 0x4645434Fu, (uint32_t)(seed >> 32) ^ stream, epoch, utt0, 1};
+static inline FbFeco fb_feco_key(const FbRngPoint &pt, double ratio, int iters, int r = 1) {
+  return FbFeco{ratio, iters, (uint32_t)pt.seed ^ 0x4645434Fu, (uint32_t)(pt.seed >> 32) ^ pt.stream, pt.epoch, pt.utt0, r};
 }
 #define FB_FECO_WS_INTS 5  // ints of workspace per input row (rows that do not fit the LDS: keys, labels, sorted order, counts, starts)
 // k-means over the rows of every utterance row (row_off[rows + 1]; row b * fc.r + j = replica j of utterance b): the centres
