@@ -126,6 +126,17 @@ def with_companions(items, idx, count):
     return wavs[0], wavs[1:]
 
 
+def _pair(text):
+    """'A:B' -> (float A, float B): --pso-w, --pso-c"""
+    parts = text.split(":")
+    if len(parts) != 2:
+        raise argparse.ArgumentTypeError("%r: two numbers joined by a colon" % (text,))
+    try:
+        return float(parts[0]), float(parts[1])
+    except ValueError:
+        raise argparse.ArgumentTypeError("%r: two numbers joined by a colon" % (text,))
+
+
 def main(argv=None, model_factory=None, bob_factory=None):
     """model_factory(architecture, task, model_list, pre_model_dir, threshold, group_id) / bob_factory(task,
     attack_type, model, **hyper_parameters): injection points for the driver-rule tests (a stub model / stub FakeBob
@@ -173,6 +184,16 @@ def main(argv=None, model_factory=None, bob_factory=None):
                     help="universal perturbation: the next N utterances of the same speaker in the data directory ride along "
                          "with every attacked one (1 .. 31, times --eot-size at most 32); all are cropped to the shortest, "
                          "which is printed; default: 0")
+    ap.add_argument("--attack", default="nes", choices=["nes", "pso"],
+                    help="the search: FAKEBOB's NES gradient estimate (default) or SirenAttack's particle swarm "
+                         "(fakebob_amd/pso.py; -epsilon, -max_iter, -adver and --seed apply, the other NES options do not)")
+    ap.add_argument("--particles", default=25, type=int, help="--attack pso: particles of the swarm (2 .. 64)")
+    ap.add_argument("--pso-w", dest="pso_w", default=(0.9, 0.1), type=_pair, metavar="WI:WE",
+                    help="--attack pso: inertia weight, falling linearly from WI to WE over max_iter iterations")
+    ap.add_argument("--pso-c", dest="pso_c", default=(1.4961, 1.4961), type=_pair, metavar="C1:C2",
+                    help="--attack pso: the pulls towards a particle's own best and the swarm's best")
+    ap.add_argument("--pso-vmax", dest="pso_vmax", default=None, type=float,
+                    help="--attack pso: largest step of a sample per iteration (default: epsilon)")
     ap.add_argument("--model_dir", default="./model")
     ap.add_argument("--pre_model_dir", default="pre-models")
     ap.add_argument("--test_dir", default="./data/test-set")
@@ -180,6 +201,11 @@ def main(argv=None, model_factory=None, bob_factory=None):
     ap.add_argument("--out_dir", default=".")
     ap.add_argument("--dist-backend", default=None)
     args = ap.parse_args(argv)
+    if args.attack == "pso":      # refused here, before any model is built
+        if args.eot_size is not None and args.eot_size > 1:
+            ap.error("--attack pso does not run under expectation over transformation (--eot-size %d)" % args.eot_size)
+        if args.companions > 0:
+            ap.error("--attack pso does not take companion utterances (--companions %d)" % args.companions)
 
     task, attack_type, spk_id_list = args.task, args.attack_type, args.speaker_id
     if task == "SV":                      # SV only supports one enrolled speaker (:449-451)
@@ -218,7 +244,13 @@ def main(argv=None, model_factory=None, bob_factory=None):
     hp = dict(adver_thresh=args.adver_thresh, epsilon=args.epsilon, max_iter=args.max_iter, max_lr=args.max_lr,
               min_lr=args.min_lr, samples_per_draw=args.samples_per_draw, sigma=args.sigma,
               momentum=args.momentum, plateau_length=args.plateau_length, plateau_drop=args.plateau_drop)
-    if bob_factory is None:
+    if args.attack == "pso":
+        hp = dict(adver_thresh=args.adver_thresh, epsilon=args.epsilon, max_iter=args.max_iter, n_particles=args.particles,
+                  w_init=args.pso_w[0], w_end=args.pso_w[1], c1=args.pso_c[0], c2=args.pso_c[1], v_max=args.pso_vmax)
+    if bob_factory is None and args.attack == "pso":
+        from .pso import ParticleSwarm
+        bobs = [ParticleSwarm(task, attack_type, m, seed=seed, verbose=False, **hp) for m in models]
+    elif bob_factory is None:
         bobs = [FakeBob(task, attack_type, m, seed=seed, verbose=False, **hp) for m in models]
     else:
         bobs = [bob_factory(task, attack_type, m, **hp) for m in models]

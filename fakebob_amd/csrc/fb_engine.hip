@@ -12,6 +12,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <chrono>
 #include <string>
 #include <vector>
 
@@ -153,7 +154,7 @@ struct fb_engine {
   std::vector<double> h_zmean, h_zstd;
   // batch scratch
   DevBuf frame_rec, vad_counter, vad_pub, vad_part, fin_counter, fin_xch, ctl, ctl_ls, trace_dev, ticks, enr_ll, enr_aux, enr_stats;
-  std::vector<double> iter_seconds;  // per-iteration device times of the last fb_attack / fb_attack_ext / fb_attack_dev
+  std::vector<double> iter_seconds;  // per-iteration device times of the last fb_attack / fb_attack_ext / fb_attack_dev (fb_attack_pso: host times)
   fb_foreign_path_info foreign = {};  // fb_debug_foreign_path: the last foreign-model call (path 0: none yet)
   long long bench_it = -1;  // fb_bench_nes: next iteration index of the attack left resident (-1: none)
   int64_t bench_N = 0;
@@ -186,6 +187,8 @@ struct fb_engine {
   int last_total_frames = 0, last_B = 0, last_chunks = 1;
   // NES state
   DevBuf audio, adver, grad_m, grad, noise, zbuf, scores, loss, dist_part, nes_out, stage_f64, ext_x, ext_z;
+  DevBuf pso_x, pso_v, pso_pb, pso_gb;  // fb_attack_pso's swarm: positions, velocities, personal bests [P][N], global best [N]
+  DevBuf pso_look;                      // ... and what its host reads per iteration: {FbNesDev, loss[P], scores[P][S]}
   FbNesDev *h_out = nullptr;  // pinned
   int *h_tv = nullptr;        // pinned, grows
   size_t h_tv_cap = 0;
@@ -2095,16 +2098,20 @@ extern "C" int fb_last_ivectors(fb_engine *e, int B, double *ivecs) {
 
 // --------------------------------------------------------------------- NES
 // the checks of fb_nes_params every NES call makes, for a system of S speakers
-static int check_nes_params(const fb_nes_params *p, int S) {
-  if (p->samples_per_draw < 0 || p->samples_per_draw > 4094) return fb_fail(FB_E_ARG, "bad samples_per_draw");
+// ... the part every attack shares, whatever its search (fb_attack_pso reads none of the NES-only fields)
+static int check_goal_params(const fb_nes_params *p, int S) {
   if (p->task != FB_TASK_SV && p->attack_type == FB_TARGETED && (p->target < 0 || p->target >= S))
     return fb_fail(FB_E_ARG, "target %d out of range", p->target);
   if (p->task == FB_TASK_CSI && p->attack_type == FB_UNTARGETED && (p->true_label < 0 || p->true_label >= S))
     return fb_fail(FB_E_ARG, "true label %d out of range", p->true_label);
-  if (!(p->sigma > 0.0) && p->samples_per_draw >= 2) return fb_fail(FB_E_ARG, "sigma must be > 0");
   if (p->bits_per_sample != 0 && (p->bits_per_sample < 2 || p->bits_per_sample > 16))
     return fb_fail(FB_E_ARG, "bits_per_sample %d unsupported (2 .. 16)", p->bits_per_sample);
   return FB_OK;
+}
+static int check_nes_params(const fb_nes_params *p, int S) {
+  if (p->samples_per_draw < 0 || p->samples_per_draw > 4094) return fb_fail(FB_E_ARG, "bad samples_per_draw");
+  if (!(p->sigma > 0.0) && p->samples_per_draw >= 2) return fb_fail(FB_E_ARG, "sigma must be > 0");
+  return check_goal_params(p, S);
 }
 static int check_params(fb_engine *e, const fb_nes_params *p, int64_t N) {
   if (!e || !p) return fb_fail(FB_E_ARG, "null argument");
@@ -2558,21 +2565,24 @@ static int attack_start(fb_engine *e, const double *audio, int64_t N, int half, 
   return FB_OK;
 }
 
+// The engine's own launch state at the start of an attack on its own system
+static int launch_state_reset(fb_engine *e) {
+  e->pre_iter = -1;
+  // The ticket of k_vad_delta_cmvn and the arrival counter of k_gmm_finalize_loss are left at zero by every launch
+  // that completes; one that was aborted or failed would leave them elsewhere and every later launch would then
+  // mis-assign utterances / skip its loss body.  A new attack starts them clean.
+  if (e->vad_counter.p) HIPCHK(hipMemsetAsync(e->vad_counter.p, 0, sizeof(int), e->stream));
+  if (e->fin_counter.p) HIPCHK(hipMemsetAsync(e->fin_counter.p, 0, 2 * sizeof(int), e->stream));
+  e->fin_xch_clean = false;  // (refilled with sentinels before its next use)
+  if (e->iv_tail_counter.p) HIPCHK(hipMemsetAsync(e->iv_tail_counter.p, 0, sizeof(int), e->stream));
+  e->vad_part_B = -1;  // ... and k_vad_delta_cmvn_p's exchange slots are refilled with sentinels (run_post_mfcc)
+  e->ctl_seq = 0;   // (h.pub_seq = 0: the loss bodies of this attack count from 1)
+  return FB_OK;
+}
 // A new attack's loop control (lr = max_lr, empty loss history) on the device; ticks (nullable) get the start stamp.
 // native: the engine's own launch state starts clean as well -- the foreign paths use none of it.
 static int ctl_reset(fb_engine *e, const fb_nes_params *p, bool native, bool disable_stop, unsigned long long *ticks) {
-  if (native) {
-    e->pre_iter = -1;
-    // The ticket of k_vad_delta_cmvn and the arrival counter of k_gmm_finalize_loss are left at zero by every launch
-    // that completes; one that was aborted or failed would leave them elsewhere and every later launch would then
-    // mis-assign utterances / skip its loss body.  A new attack starts them clean.
-    if (e->vad_counter.p) HIPCHK(hipMemsetAsync(e->vad_counter.p, 0, sizeof(int), e->stream));
-    if (e->fin_counter.p) HIPCHK(hipMemsetAsync(e->fin_counter.p, 0, 2 * sizeof(int), e->stream));
-    e->fin_xch_clean = false;  // (refilled with sentinels before its next use)
-    if (e->iv_tail_counter.p) HIPCHK(hipMemsetAsync(e->iv_tail_counter.p, 0, sizeof(int), e->stream));
-    e->vad_part_B = -1;  // ... and k_vad_delta_cmvn_p's exchange slots are refilled with sentinels (run_post_mfcc)
-    e->ctl_seq = 0;   // (h.pub_seq = 0: the loss bodies of this attack count from 1)
-  }
+  if (native) FBCHK(launch_state_reset(e));
   FBCHK(e->ctl.ensure(sizeof(FbCtlDev)));
   FBCHK(e->ctl_ls.ensure(sizeof(double) * (size_t)(p->plateau_length > 0 ? p->plateau_length : 1)));
   FbCtlDev h;
@@ -2773,6 +2783,184 @@ extern "C" int fb_attack_iter_seconds(fb_engine *e, double *seconds, int n) {
   if (!e || !seconds || n < 0) return fb_fail(FB_E_ARG, "bad argument");
   if ((size_t)n > e->iter_seconds.size()) return fb_fail(FB_E_STATE, "the last attack ran %zu iterations (asked for %d)", e->iter_seconds.size(), n);
   for (int i = 0; i < n; ++i) seconds[i] = e->iter_seconds[i];
+  return FB_OK;
+}
+
+// ------------------------------------------------- particle-swarm attack
+// fb_attack_pso (the "particle-swarm attack" section of fakebob_hip.h).  The swarm is a batch of P rows: the ordinary path
+// scores it, k_loss forms loss[P] and scores[P][S], the host reads them once per iteration, decides the personal and global
+// bests and the stop, and k_pso_step moves the swarm -- taking the best-copies and the next batch's int16 cast along.
+// The fused finalisation, the i-vector tail-loss shortcut and the device control block are not used.
+static int check_pso_swarm(int P, double eps, double v_max, int bits) {
+  if (P < 2 || P > FB_PSO_MAX_PARTICLES) return fb_fail(FB_E_ARG, "particles %d outside 2 .. %d", P, FB_PSO_MAX_PARTICLES);
+  if (!isfinite(eps) || !(eps > 0.0)) return fb_fail(FB_E_ARG, "epsilon must be finite and > 0");
+  if (!isfinite(v_max) || !(v_max > 0.0)) return fb_fail(FB_E_ARG, "v_max must be finite and > 0");
+  if (bits < 2 || bits > 16) return fb_fail(FB_E_ARG, "bits_per_sample %d unsupported (2 .. 16)", bits);
+  return FB_OK;
+}
+static int ensure_pso_buffers(fb_engine *e, int64_t N, int P) {
+  FBCHK(e->audio.ensure(sizeof(double) * (size_t)N));
+  FBCHK(e->pso_x.ensure(sizeof(double) * (size_t)N * P));
+  FBCHK(e->pso_v.ensure(sizeof(double) * (size_t)N * P));
+  FBCHK(e->pso_pb.ensure(sizeof(double) * (size_t)N * P));
+  FBCHK(e->pso_gb.ensure(sizeof(double) * (size_t)N));
+  return FB_OK;
+}
+
+extern "C" int fb_attack_pso(fb_engine *e, const fb_nes_params *p, const fb_pso_params *q, const double *audio, int64_t N,
+                             int16_t *adv_i16, double *adv_f64, int *success, int *n_iters, double *trace, double *losses) {
+  if (e) e->bench_it = -1;
+  if (!e || !p || !q || !audio || !adv_i16 || !success || !n_iters || !trace || !losses) return fb_fail(FB_E_ARG, "null argument");
+  if (!e->have_gmm) return fb_fail(FB_E_STATE, "no model loaded");
+  if (e->eot > 1)
+    return fb_fail(FB_E_STATE, "fb_attack_pso does not run under expectation over transformation (fb_set_eot(%d)): set 1", e->eot);
+  if (e->comp_K1 > 0)
+    return fb_fail(FB_E_STATE, "fb_attack_pso does not run with companion utterances (fb_set_companions: %d set): clear them", e->comp_K1);
+  const int P = q->particles, bits = nes_bits(p);
+  FBCHK(check_pso_swarm(P, p->epsilon, q->v_max, bits));
+  for (double c : {q->w_init, q->w_end, q->c1, q->c2})
+    if (!isfinite(c) || c < 0.0) return fb_fail(FB_E_ARG, "w_init, w_end, c1 and c2 must be finite and >= 0");
+  if (p->max_iter < 1) return fb_fail(FB_E_ARG, "max_iter must be > 0");
+  if (N <= 0) return fb_fail(FB_E_ARG, "empty audio");
+  if (p->task != e->task) return fb_fail(FB_E_ARG, "params.task %d != engine system task %d", p->task, e->task);
+  const int S = fb_num_speakers(e);
+  FBCHK(check_goal_params(p, S));
+  if (num_frames(e->cfg, N) <= 0) return fb_fail(FB_E_ARG, "audio shorter than one frame");
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(prepare_nes_batch(e, N, P));
+  FBCHK(ensure_pso_buffers(e, N, P));
+  // what the host reads once per iteration, in one block: k_loss's result block (for its "no voiced frames" word), loss[P],
+  // scores[P][S]
+  static_assert(sizeof(FbNesDev) % sizeof(double) == 0, "the result block is followed by doubles");
+  const size_t out_d = sizeof(FbNesDev) / sizeof(double), look_d = out_d + (size_t)P + (size_t)P * S;
+  FBCHK(e->pso_look.ensure(sizeof(double) * look_d));
+  FbNesDev *out_dev = e->pso_look.as<FbNesDev>();
+  double *loss_dev = e->pso_look.as<double>() + out_d, *scores_dev = loss_dev + P;
+  FBCHK(launch_state_reset(e));
+  e->iter_seconds.clear();
+
+  double *x = e->pso_x.as<double>(), *gb = e->pso_gb.as<double>();
+  FBCHK(h2d(e, e->audio.p, audio, sizeof(double) * (size_t)N));
+  fb_launch_pso_init(e->stream, e->audio.as<double>(), N, P, p->epsilon, q->v_max, p->seed, p->stream, bits, x,
+                     e->pso_v.as<double>(), e->wav.as<int16_t>());
+  std::vector<double> look(look_d), pl((size_t)P, 0.0);
+  const double *l = look.data() + out_d, *sc = l + P;
+  double gl = 0.0;
+  int g = 0, k = 0, g_new = -1;
+  auto t_prev = std::chrono::steady_clock::now();
+  for (;; ++k) {
+    FbScoreCall call{FbRngPoint{p->seed, p->stream, (uint32_t)k, 0}};
+    FBCHK(run_scoring(e, call, P, e->h_frame_off[P]));
+    fb_launch_loss(e->stream, e->raw.as<double>(), e->tv.as<int>(), P, e->n_out, p->task, e->kind, p->attack_type,
+                   e->zmean.as<double>(), e->zstd.as<double>(), p->threshold, p->adver_thresh, p->target, p->true_label,
+                   nullptr, 0, scores_dev, loss_dev, out_dev);
+    // the one look of the iteration: one copy through pinned memory, one synchronisation
+    FBCHK(d2h(e, look.data(), e->pso_look.p, sizeof(double) * look_d));
+    FBCHK(sync_stream(e));
+    {
+      FbNesDev out;
+      memcpy(&out, look.data(), sizeof(out));
+      if (out.err != 0) return fb_fail(FB_E_NO_VOICED, "particle %d of iteration %d has no voiced frames", out.err - 1, k);
+    }
+    // step 2: personal bests (strict <), then the global best -- the lowest particle among the minimal ones
+    unsigned long long improved = 0;
+    int n_improved = 0;
+    for (int b = 0; b < P; ++b) {
+      losses[(size_t)k * P + b] = l[b];
+      if (k == 0 || l[b] < pl[b]) {
+        pl[b] = l[b];
+        improved |= 1ull << b;
+        ++n_improved;
+      }
+    }
+    int gs = 0;
+    for (int b = 1; b < P; ++b) if (pl[b] < pl[gs]) gs = b;
+    double *row = trace + (size_t)k * (3 + S);
+    g_new = -1;
+    if (k == 0 || pl[gs] < gl) {
+      gl = pl[gs];
+      g = g_new = gs;
+      for (int s = 0; s < S; ++s) row[3 + s] = sc[(size_t)gs * S + s];
+    } else {
+      for (int s = 0; s < S; ++s) row[3 + s] = row[3 + s - (3 + S)];  // gs unchanged: the previous row's
+    }
+    row[0] = gl; row[1] = (double)g; row[2] = (double)n_improved;
+    const auto t_now = std::chrono::steady_clock::now();
+    e->iter_seconds.push_back(std::chrono::duration<double>(t_now - t_prev).count());
+    t_prev = t_now;
+    if (gl < 0.0) { *success = 1; break; }
+    if (k == p->max_iter - 1) { *success = -1; break; }
+    const double w_k = q->w_init - ((q->w_init - q->w_end) * (double)k) / (double)p->max_iter;
+    fb_launch_pso_step(e->stream, e->audio.as<double>(), N, P, p->epsilon, x, e->pso_v.as<double>(), e->pso_pb.as<double>(), gb,
+                       improved, g_new, w_k, q->c1, q->c2, q->v_max, p->seed, p->stream, (uint32_t)(k + 1), bits,
+                       e->wav.as<int16_t>());
+  }
+  *n_iters = k + 1;
+  // the last iteration's new global best has not been copied yet: that rides in the step that was not launched
+  if (g_new >= 0)
+    HIPCHK(hipMemcpyAsync(gb, x + (size_t)g_new * N, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, e->stream));
+  fb_launch_quantize(e->stream, gb, N, bits, e->wav.as<int16_t>());
+  FBCHK(d2h(e, adv_i16, e->wav.p, sizeof(int16_t) * (size_t)N));
+  if (adv_f64) FBCHK(d2h(e, adv_f64, gb, sizeof(double) * (size_t)N));
+  FBCHK(sync_stream(e));
+  HIPCHK(hipGetLastError());
+  return FB_OK;
+}
+
+extern "C" int fb_debug_pso_init(fb_engine *e, const double *audio, int64_t N, double epsilon, int P, double v_max, uint64_t seed,
+                                 uint32_t stream, int bits, double *x, double *v, int16_t *q) {
+  if (!e || !audio || !x || !v || !q || N <= 0) return fb_fail(FB_E_ARG, "bad argument");
+  FBCHK(check_pso_swarm(P, epsilon, v_max, bits));
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  e->cached_B = -1;  // (e->wav takes the batch, without a batch layout)
+  const size_t n = (size_t)N * P;
+  FBCHK(ensure_pso_buffers(e, N, P));
+  FBCHK(e->wav.ensure(sizeof(int16_t) * n));
+  FBCHK(h2d(e, e->audio.p, audio, sizeof(double) * (size_t)N));
+  fb_launch_pso_init(e->stream, e->audio.as<double>(), N, P, epsilon, v_max, seed, stream, bits, e->pso_x.as<double>(),
+                     e->pso_v.as<double>(), e->wav.as<int16_t>());
+  FBCHK(d2h(e, x, e->pso_x.p, sizeof(double) * n));
+  FBCHK(d2h(e, v, e->pso_v.p, sizeof(double) * n));
+  FBCHK(d2h(e, q, e->wav.p, sizeof(int16_t) * n));
+  FBCHK(sync_stream(e));
+  HIPCHK(hipGetLastError());
+  return FB_OK;
+}
+
+extern "C" int fb_debug_pso_step(fb_engine *e, const double *audio, int64_t N, double epsilon, int P, const double *x,
+                                 const double *v, const double *pb, const double *gb, const int *improved, int g_new, double w,
+                                 double c1, double c2, double v_max, uint64_t seed, uint32_t stream, uint32_t t, int bits,
+                                 double *x_out, double *v_out, double *pb_out, double *gb_out, int16_t *q_out) {
+  if (!e || !audio || !x || !v || !pb || !gb || !improved || !x_out || !v_out || !pb_out || !gb_out || !q_out || N <= 0)
+    return fb_fail(FB_E_ARG, "bad argument");
+  FBCHK(check_pso_swarm(P, epsilon, v_max, bits));
+  if (g_new < -1 || g_new >= P) return fb_fail(FB_E_ARG, "g_new %d outside -1 .. %d", g_new, P - 1);
+  for (double c : {w, c1, c2})
+    if (!isfinite(c) || c < 0.0) return fb_fail(FB_E_ARG, "w, c1 and c2 must be finite and >= 0");
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  e->cached_B = -1;
+  const size_t n = (size_t)N * P;
+  FBCHK(ensure_pso_buffers(e, N, P));
+  FBCHK(e->wav.ensure(sizeof(int16_t) * n));
+  FBCHK(h2d(e, e->audio.p, audio, sizeof(double) * (size_t)N));
+  FBCHK(h2d(e, e->pso_x.p, x, sizeof(double) * n));
+  FBCHK(h2d(e, e->pso_v.p, v, sizeof(double) * n));
+  FBCHK(h2d(e, e->pso_pb.p, pb, sizeof(double) * n));
+  FBCHK(h2d(e, e->pso_gb.p, gb, sizeof(double) * (size_t)N));
+  unsigned long long mask = 0;
+  for (int b = 0; b < P; ++b) if (improved[b]) mask |= 1ull << b;
+  fb_launch_pso_step(e->stream, e->audio.as<double>(), N, P, epsilon, e->pso_x.as<double>(), e->pso_v.as<double>(),
+                     e->pso_pb.as<double>(), e->pso_gb.as<double>(), mask, g_new, w, c1, c2, v_max, seed, stream, t, bits,
+                     e->wav.as<int16_t>());
+  FBCHK(d2h(e, x_out, e->pso_x.p, sizeof(double) * n));
+  FBCHK(d2h(e, v_out, e->pso_v.p, sizeof(double) * n));
+  FBCHK(d2h(e, pb_out, e->pso_pb.p, sizeof(double) * n));
+  FBCHK(d2h(e, gb_out, e->pso_gb.p, sizeof(double) * (size_t)N));
+  FBCHK(d2h(e, q_out, e->wav.p, sizeof(int16_t) * n));
+  FBCHK(sync_stream(e));
+  HIPCHK(hipGetLastError());
   return FB_OK;
 }
 

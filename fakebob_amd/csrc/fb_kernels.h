@@ -148,6 +148,19 @@ void fb_launch_quantize(hipStream_t s, const double *x, int64_t n, int bits, int
 void fb_launch_noise(hipStream_t s, uint64_t seed, uint32_t iter, uint32_t stream, int64_t N, int half,
                      float *z);
 
+// ---- particle-swarm attack (fb_attack_pso; pso_kernels.hip) --------------------------------------------------------
+#define FB_PSO_KEY 0x5053574Du   // "PSWM": the swarm's uniforms have a Philox key of their own
+#define FB_PSO_MAX_PARTICLES 64  // (the per-particle "improved" flags travel as one 64-bit kernel argument)
+// the swarm at t = 0: x, v [P][N] and their int16 cast q [P][N] (the first batch)
+void fb_launch_pso_init(hipStream_t s, const double *audio, int64_t N, int P, double eps, double vmax, uint64_t seed,
+                        uint32_t stream, int bits, double *x, double *v, int16_t *q);
+// the update `t` (= iteration + 1) of every particle, with what the host decided from the iteration's losses riding along:
+// pb_p <- x_p where bit p of `improved` is set, gb <- x of particle g_new (-1: gb stays) -- both before the velocities read
+// them --, and the int16 cast of the new positions in q [P][N] (the next batch)
+void fb_launch_pso_step(hipStream_t s, const double *audio, int64_t N, int P, double eps, double *x, double *v, double *pb,
+                        double *gb, unsigned long long improved, int g_new, double w, double c1, double c2, double vmax,
+                        uint64_t seed, uint32_t stream, uint32_t t, int bits, int16_t *q);
+
 // Device-side control block of an attack (FAKEBOB.py:171-203): early stop on loss[0] < 0 (:181), the
 // plateau learning-rate schedule (:195-200) and the per-iteration trace rows are handled by the loss
 // kernel itself, so the host can queue several NES iterations ahead and only looks at the block once

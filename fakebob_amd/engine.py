@@ -28,6 +28,14 @@ def nes_params(task, attack_type, adver_thresh=0., epsilon=0.002, max_iter=1000,
     return p
 
 
+def pso_params(particles=25, w_init=0.9, w_end=0.1, c1=1.4961, c2=1.4961, v_max=0.002):
+    """fb_pso_params: the swarm of Engine.attack_pso (fakebob_hip.h, "particle-swarm attack")."""
+    q = N.PsoParams()
+    q.particles = int(particles)
+    q.w_init = float(w_init); q.w_end = float(w_end); q.c1 = float(c1); q.c2 = float(c2); q.v_max = float(v_max)
+    return q
+
+
 class Engine(object):
     def __init__(self, device=0):
         self._L = N.lib()
@@ -438,8 +446,58 @@ class Engine(object):
                        C.byref(flag))
         return adv, flag.value, adv_f, trace[:nt.value]
 
+    # ---- particle swarm
+    def attack_pso(self, params, pso, audio):
+        """fb_attack_pso: the particle-swarm attack on this engine's system -> (int16 adv, flag, float64 adv, trace
+        (n_iters, 3 + S): gbest loss, gbest particle, particles improved, gbest scores; losses (n_iters, P))."""
+        audio = np.ascontiguousarray(audio, np.float64).reshape(-1)
+        n, S, P = audio.size, self.n_speakers, max(int(pso.particles), 1)
+        adv = np.empty(n, np.int16)
+        adv_f = np.empty(n, np.float64)
+        rows = max(params.max_iter, 1)
+        trace = np.zeros((rows, 3 + S), np.float64)
+        losses = np.zeros((rows, P), np.float64)
+        flag, ni = C.c_int(), C.c_int()
+        N.check(self._L.fb_attack_pso(self._h, C.byref(params), C.byref(pso), N.ptr(audio), C.c_int64(n), N.ptr(adv),
+                                      N.ptr(adv_f), C.byref(flag), C.byref(ni), N.ptr(trace), N.ptr(losses)))
+        return adv, flag.value, adv_f, trace[:ni.value], losses[:ni.value]
+
+    def debug_pso_init(self, audio, epsilon, particles, v_max, seed, stream, bits_per_sample=16):
+        """The swarm at t = 0 (fb_debug_pso_init) -> x, v (P, N) float64 and q (P, N) int16, the first batch."""
+        audio = np.ascontiguousarray(audio, np.float64).reshape(-1)
+        P = int(particles)
+        shape = (max(P, 1), audio.size)
+        x, v, q = np.empty(shape, np.float64), np.empty(shape, np.float64), np.empty(shape, np.int16)
+        N.check(self._L.fb_debug_pso_init(self._h, N.ptr(audio), C.c_int64(audio.size), C.c_double(float(epsilon)), C.c_int(P),
+                                          C.c_double(float(v_max)), C.c_uint64(int(seed)), C.c_uint32(int(stream)),
+                                          C.c_int(int(bits_per_sample)), N.ptr(x), N.ptr(v), N.ptr(q)))
+        return x, v, q
+
+    def debug_pso_step(self, audio, epsilon, x, v, pb, gb, improved, g_new, w, c1, c2, v_max, seed, stream, t,
+                       bits_per_sample=16):
+        """One update of a swarm handed in as it is (fb_debug_pso_step): x, v, pb (P, N), gb (N,), improved (P,) flags,
+        g_new the particle whose position becomes gb (-1: none) -> the new x, v, pb, gb and q, the int16 cast of the new x."""
+        audio = np.ascontiguousarray(audio, np.float64).reshape(-1)
+        x, v, pb = (np.ascontiguousarray(a, np.float64) for a in (x, v, pb))
+        gb = np.ascontiguousarray(gb, np.float64).reshape(-1)
+        P, n = x.shape
+        if v.shape != (P, n) or pb.shape != (P, n) or gb.size != n or audio.size != n:
+            raise ValueError("x, v, pb must be (P, N), gb and audio (N,)")
+        imp = np.ascontiguousarray(improved, np.int32).reshape(-1)
+        if imp.size != P:
+            raise ValueError("improved must hold one flag per particle")
+        xo, vo, po, go = np.empty_like(x), np.empty_like(v), np.empty_like(pb), np.empty_like(gb)
+        q = np.empty((P, n), np.int16)
+        N.check(self._L.fb_debug_pso_step(self._h, N.ptr(audio), C.c_int64(n), C.c_double(float(epsilon)), C.c_int(P), N.ptr(x),
+                                          N.ptr(v), N.ptr(pb), N.ptr(gb), N.ptr(imp), C.c_int(int(g_new)), C.c_double(float(w)),
+                                          C.c_double(float(c1)), C.c_double(float(c2)), C.c_double(float(v_max)),
+                                          C.c_uint64(int(seed)), C.c_uint32(int(stream)), C.c_uint32(int(t)),
+                                          C.c_int(int(bits_per_sample)), N.ptr(xo), N.ptr(vo), N.ptr(po), N.ptr(go), N.ptr(q)))
+        return xo, vo, po, go, q
+
     def attack_iter_seconds(self, n):
-        """Seconds per iteration of the last attack / attack_ext (device clock, fb_attack_iter_seconds)."""
+        """Seconds per iteration of the last attack / attack_ext (device clock, fb_attack_iter_seconds); of the last
+        attack_pso, as the host measured them."""
         out = np.zeros(max(int(n), 0), np.float64)
         if n > 0:
             N.check(self._L.fb_attack_iter_seconds(self._h, N.ptr(out), C.c_int(int(n))))

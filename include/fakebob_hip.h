@@ -28,6 +28,8 @@
  *   fb_get_grad               FakeBob.get_grad + loss_fn (FAKEBOB.py:223-299)
  *   fb_attack                 FakeBob.attack (FAKEBOB.py:139-221)
  *   fb_estimate_threshold     FakeBob.estimate_threshold (FAKEBOB.py:39-137)
+ *   fb_attack_pso             (none in FAKEBOB: SirenAttack's particle-swarm optimisation, the other score-based black-box
+ *                             attack of SpeakerGuard's evaluation, on this library's own systems)
  *   fb_get_grad_ext / fb_attack_ext   the same around a foreign `model` (README.md:136)
  *   fb_get_grad_dev / fb_attack_dev   ... around a foreign model that runs on the
  *                             same GPU: the batch and the scores stay on the device
@@ -299,6 +301,57 @@ int fb_set_companions(fb_engine *e, const int16_t *wav, int K1, int64_t N);
  * Deviations from SpeakerGuard: its k-means (kmeans_pytorch) runs to a tolerance on an unseeded generator and returns the
  * centres in its own order; here the iteration count is fixed, the generator is keyed and the order is defined. */
 int fb_set_feature_compression(fb_engine *e, double ratio, int iters);
+
+/* ---- particle-swarm attack: the other score-based black-box attack (SirenAttack's PSO, as SpeakerGuard runs it) ---------
+ * fb_attack searches by estimating a gradient (NES); fb_attack_pso searches without one: a swarm of P particles -- P candidate
+ * audios inside the epsilon ball -- is scored as ONE batch of P rows per iteration by the path that scores every NES batch,
+ * and one element-wise launch (k_pso_step) moves the swarm.  The host looks at the P losses once per iteration, as
+ * fb_estimate_threshold looks at its batch, and decides the bests and the stop.
+ * Read from fb_nes_params: task, attack_type, adver_thresh, epsilon, max_iter, threshold, target, true_label, seed, stream and
+ * bits_per_sample.  The NES-only fields (max_lr, min_lr, samples_per_draw, sigma, momentum, plateau_*) are neither read nor
+ * validated.
+ * Refusals.  FB_E_ARG: particles outside 2 .. 64; w_init, w_end, c1 or c2 not finite or < 0; v_max not finite or <= 0;
+ * max_iter < 1; epsilon not finite or <= 0; the task, target, true-label and bits_per_sample rules of fb_attack.  FB_E_STATE:
+ * no system loaded, or fb_set_eot(r > 1) or companions (fb_set_companions) in force -- BOTH STAY OUT OF THIS VERSION: set 1 /
+ * clear them.  FB_E_NO_VOICED: some particle of some iteration has no voiced frames.  The engine's own systems only (GMM and
+ * i-vector): there are no _ext / _dev twins.  The input-transform chain, dither and feature compression act as in fb_attack,
+ * keyed by the call's (seed, stream) with epoch = the PSO iteration k and utterance row = the particle index.
+ * Arithmetic.  Everything below is float64, round to nearest, one rounding per written operation, no fused multiply-add;
+ * clip(s, l, h) = min(max(s, l), h); a = `audio` as given, i the sample index, p the particle.
+ *   ball       lo[i] = clip(a[i] - eps, -1, 1), hi[i] = clip(a[i] + eps, -1, 1)                        (FAKEBOB.py:163-164)
+ *   uniforms   U(w) = ((double)w + 0.5) * 2^-32 for a 32-bit word w: exact, inside (0, 1).  The words are Philox4x32-10's with
+ *                key     = (seed_lo ^ 0x5053574D ("PSWM"), seed_hi ^ stream)
+ *                counter = (i >> 1, p, t, 0)
+ *              words 0, 1 serve element 2 (i >> 1), words 2, 3 element 2 (i >> 1) + 1; of a pair the first word is u_x (t = 0)
+ *              or r1 (t > 0), the second u_v or r2.  t = 0 is the initialisation, t = k + 1 the update behind iteration k.
+ *   init       particle 0: x = a, v = 0.  p >= 1: x = clip(lo + u_x * (hi - lo), lo, hi) -- the difference, the product, the
+ *              sum, in that order --, v = (2 u_v - 1) * v_max (2 u_v - 1 is exact).
+ *   iteration k = 0 .. max_iter - 1
+ *     1 score  row p of the batch is the int16 cast of x_p (the cast of every NES row: trunc(x * 2^(bits_per_sample - 1)), low
+ *              16 bits); l_p = loss_fn of row p's system scores, as fb_attack forms it.  losses[k][p] = l_p.
+ *     2 bests  for every p: if k == 0 or l_p < pl_p (strict) then pl_p = l_p, pb_p = x_p ("p improved").
+ *              g* = the lowest p with pl_p minimal.  If k == 0 or pl_g* < gl: gl = pl_g*, gb = pb_g*, g = g*, gs = row g*'s
+ *              scores of this iteration (such a g* improved in this iteration, so pb_g* = x_g*).
+ *     3 trace  trace[k] = {gl, (double)g, number of particles that improved in this iteration, gs[0 .. S)}
+ *     4 stop   gl < 0: *success = 1, stop.  Otherwise k == max_iter - 1: *success = -1, stop.
+ *     5 move   w_k = w_init - ((w_init - w_end) * (double)k) / (double)max_iter, formed on the host.  For every p (0 included)
+ *              and i, with pb and gb as they stand after step 2 and r1, r2 of t = k + 1:
+ *                v' = clip((w_k * v + (c1 * r1) * (pb - x)) + (c2 * r2) * (gb - x), -v_max, v_max);  x' = clip(x + v', lo, hi)
+ *   result     adv_f64 = gb, adv_i16 = its int16 cast, *n_iters = k + 1.  gb is always a position that WAS scored, so the
+ *              success decision is about exactly the samples returned, as in the reference (FAKEBOB.py:220).  Rows of trace
+ *              [max_iter][3 + S] and losses [max_iter][P] beyond n_iters are not written; adv_f64 may be NULL.
+ * fb_attack_iter_seconds reports the seconds per iteration of the last PSO call as the host measured them (an iteration ends
+ * with the host's look at its losses).  fb_stats counts the P rows per iteration in scored_utts / scored_frames as for any
+ * batch; nes_iters is not advanced.
+ * Deviations from SirenAttack / SpeakerGuard's PSO: their swarm draws from an unseeded generator, here the uniforms are keyed;
+ * the search runs inside the epsilon ball of fb_attack (theirs clips to a ball too, SirenAttack's own to [-1, 1] only);
+ * particle 0 starts at the audio itself, so gl of iteration 0 is never worse than the clean audio's loss; one swarm per
+ * call -- no restarts ("epochs") and no hand-over to a gradient stage; the inertia weight falls linearly from w_init to w_end
+ * over max_iter iterations. */
+typedef struct { int particles; double w_init, w_end, c1, c2, v_max; } fb_pso_params;
+int fb_attack_pso(fb_engine *e, const fb_nes_params *p, const fb_pso_params *q, const double *audio, int64_t N,
+                  int16_t *adv_i16, double *adv_f64 /*nullable*/, int *success, int *n_iters,
+                  double *trace /*[max_iter][3 + S]*/, double *losses /*[max_iter][P]*/);
 
 const char *fb_last_error(void);
 int fb_version(void);

@@ -78,6 +78,20 @@ int fb_debug_feature_compress(fb_engine *e, const float *feats, const int *row_o
 int fb_debug_feco_keys(fb_engine *e, uint64_t seed, uint32_t stream, uint32_t epoch, uint32_t utt, int replica, int T,
                        uint32_t *keys);
 
+/* Particle-swarm attack (fakebob_hip.h: fb_attack_pso and its arithmetic).  Both hooks run exactly the launches the attack
+ * runs, on swarms handed in as they are; no system has to be loaded.  P = 2 .. 64, N >= 1, bits = 2 .. 16.
+ * fb_debug_pso_init: the swarm at t = 0 -- x, v [P][N] float64 and q [P][N], the int16 cast of x (the first batch).
+ * fb_debug_pso_step: update t >= 1 of the swarm x, v, pb [P][N], gb [N] with what the host would have decided riding along:
+ * pb_p = x_p for every p with improved[p] != 0, gb = x_{g_new} unless g_new = -1 (in an attack g_new improved in that
+ * iteration, so this is pb_{g_new}; the hook takes any combination) -- both BEFORE the velocities read them.  Outputs: the new
+ * x, v, pb, gb and q, the int16 cast of the new x (the next batch). */
+int fb_debug_pso_init(fb_engine *e, const double *audio, int64_t N, double epsilon, int P, double v_max, uint64_t seed,
+                      uint32_t stream, int bits, double *x, double *v, int16_t *q);
+int fb_debug_pso_step(fb_engine *e, const double *audio, int64_t N, double epsilon, int P, const double *x, const double *v,
+                      const double *pb, const double *gb, const int *improved, int g_new, double w, double c1, double c2,
+                      double v_max, uint64_t seed, uint32_t stream, uint32_t t, int bits, double *x_out, double *v_out,
+                      double *pb_out, double *gb_out, int16_t *q_out);
+
 /* What the front end of the last batch ran (fb_score_*, fb_get_grad, an NES iteration, fb_debug_mfcc / _feats, enrolment
  * statistics): info[5] = {the MFCC kernel, the chain after it, where the CompressedMatrix round trip ran, the longest
  * utterance of the batch in frames, the batch size}.  Recorded on the host when the kernels are enqueued; read only.
