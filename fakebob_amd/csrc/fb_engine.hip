@@ -155,6 +155,7 @@ struct fb_engine {
   // batch scratch
   DevBuf frame_rec, vad_counter, vad_pub, vad_part, fin_counter, fin_xch, ctl, ctl_ls, trace_dev, ticks, enr_ll, enr_aux, enr_stats;
   std::vector<double> iter_seconds;  // per-iteration device times of the last fb_attack / fb_attack_ext / fb_attack_dev (fb_attack_pso: host times)
+  int nes_route[FB_NES_ROUTE_N] = {};  // fb_debug_nes_route: launches the last fb_get_grad* / fb_attack* call enqueued
   fb_foreign_path_info foreign = {};  // fb_debug_foreign_path: the last foreign-model call (path 0: none yet)
   long long bench_it = -1;  // fb_bench_nes: next iteration index of the attack left resident (-1: none)
   int64_t bench_N = 0;
@@ -1614,7 +1615,13 @@ static int run_scoring(fb_engine *e, FbScoreCall &call, int B, int total_frames)
       // (LDA dimension > 512: the tail's 512 threads would take two l each in the PLDA partial sums where k_iv_backend's
       //  1024 take one -- a different summation grouping; such a system keeps the separate launch and its rounding)
       if (!split && iv.L <= 512) {
-        if (call.tail_loss && fb_iv_tail_takes_loss(B)) { tail = *call.tail_loss; tail.loss = 1; }
+        if (call.tail_loss && fb_iv_tail_takes_loss(B)) {
+          tail = *call.tail_loss;
+          tail.loss = 1;
+          // (the voiced-frame counts as THIS batch's front end wrote them: e->tv grows with the batch up there, so a pointer
+          //  the caller took before the call may be to the buffer that was freed)
+          tail.tv = e->tv.as<int>();
+        }
         tail.backend = 1;
         tail.llr = e->raw.as<double>();
         tail.counter = e->iv_tail_counter.as<int>();
@@ -2275,7 +2282,6 @@ static int enqueue_get_grad(fb_engine *e, const fb_nes_params *p, int64_t N, uin
   call.defer_finalize = fuse_fin;
   FbIvTail t = {};
   if (e->kind == 1 && r == 1) {  // i-vector systems: the loss body rides in the tail of the solve kernel when the batch allows it
-    t.tv = e->tv.as<int>();
     t.task = p->task; t.attack_type = p->attack_type;
     t.z_mean = e->zmean.as<double>(); t.z_std = e->zstd.as<double>();
     t.threshold = p->threshold; t.adver_thresh = p->adver_thresh;
@@ -2291,9 +2297,13 @@ static int enqueue_get_grad(fb_engine *e, const fb_nes_params *p, int64_t N, uin
                        e->zmean.as<double>(), e->zstd.as<double>(), p->threshold, p->adver_thresh, p->target, p->true_label,
                        e->dist_part.as<double>(), with_dist ? ndp : 0, e->eot_sc.as<double>(), e->eot_l.as<double>(),
                        e->scores.as<double>(), e->loss.as<double>(), e->nes_out.as<FbNesDev>(), ctl, trace_dev, trace_row);
+    e->nes_route[FB_NES_ROUTE_K_LOSS] += 1;
     return FB_OK;
   }
-  if (call.tail_loss_done) return FB_OK;
+  if (call.tail_loss_done) {
+    e->nes_route[FB_NES_ROUTE_IV_TAIL] += 1;
+    return FB_OK;
+  }
   if (fuse_fin) {
     if (!e->fin_counter.p) {
       FBCHK(e->fin_counter.ensure(2 * sizeof(int)));   // [0] the arrival counter, [1] the fused launch's role ticket
@@ -2325,12 +2335,14 @@ static int enqueue_get_grad(fb_engine *e, const fb_nes_params *p, int64_t N, uin
                                 with_dist ? ndp : 0, e->scores.as<double>(), e->loss.as<double>(),
                                 e->nes_out.as<FbNesDev>(), ctl, trace_dev, trace_row, upd ? ++e->ctl_seq : 0, upd);
     if (upd && upd_done) *upd_done = true;
+    e->nes_route[upd ? FB_NES_ROUTE_FIN_LOSS_UPDATE : FB_NES_ROUTE_FIN_LOSS] += 1;
     return FB_OK;
   }
   fb_launch_loss(e->stream, e->raw.as<double>(), e->tv.as<int>(), B, e->n_out, p->task, e->kind, p->attack_type,
                  e->zmean.as<double>(), e->zstd.as<double>(), p->threshold, p->adver_thresh, p->target,
                  p->true_label, e->dist_part.as<double>(), with_dist ? ndp : 0, e->scores.as<double>(),
                  e->loss.as<double>(), e->nes_out.as<FbNesDev>(), ctl, trace_dev, trace_row);
+  e->nes_route[FB_NES_ROUTE_K_LOSS] += 1;
   return FB_OK;
 }
 
@@ -2414,6 +2426,7 @@ static int enqueue_get_grad_ext(fb_engine *e, const fb_nes_params *p, const FbSc
                  e->ext_z.as<double>() + 64, p->threshold, p->adver_thresh, p->target, p->true_label,
                  e->dist_part.as<double>(), with_dist ? ndp : 0, e->scores.as<double>(), e->loss.as<double>(),
                  e->nes_out.as<FbNesDev>(), ctl, trace_dev, trace_row);
+  e->nes_route[FB_NES_ROUTE_K_LOSS] += 1;
   return FB_OK;
 }
 
@@ -2478,6 +2491,7 @@ static int enqueue_score_loss_dev(fb_engine *e, const fb_nes_params *p, const Fb
                    e->ext_z.as<double>(), e->ext_z.as<double>() + 64, p->threshold, p->adver_thresh, p->target,
                    p->true_label, e->dist_part.as<double>(), ndp, e->scores.as<double>(), e->loss.as<double>(),
                    e->nes_out.as<FbNesDev>(), ctl, trace_dev, trace_row);
+  e->nes_route[FB_NES_ROUTE_K_LOSS] += 1;
   return FB_OK;
 }
 
@@ -2518,6 +2532,7 @@ static int nes_gradient(fb_engine *e, const fb_nes_params *p, FbScorer sc, const
                         uint32_t iter, const double *noise_pos, double *final_loss, double *grad, double *adver_loss,
                         double *score0) {
   if (e) e->bench_it = -1;
+  if (e) memset(e->nes_route, 0, sizeof(e->nes_route));
   if (!audio) return fb_fail(FB_E_ARG, "audio is NULL");
   FBCHK(nes_setup(e, p, N, sc, false));
   const bool native = sc.kind == FB_SCORER_NATIVE;
@@ -2547,6 +2562,7 @@ static int nes_gradient(fb_engine *e, const fb_nes_params *p, FbScorer sc, const
   }
   fb_launch_grad_update(e->stream, e->loss.as<double>(), N, half, p->sigma, e->zbuf.as<float>(), noise_dev,
                         e->grad.as<double>(), 0, 0.0, 0.0, 0.0, 0.0, nullptr, nullptr, nullptr);
+  e->nes_route[FB_NES_ROUTE_K_GRAD_UPDATE] += 1;
   if (grad) FBCHK(d2h(e, grad, e->grad.p, sizeof(double) * (size_t)N));
   FBCHK(fetch_out(e, native));
   e->nes_iters += 1;
@@ -2647,6 +2663,7 @@ static int attack_loop(fb_engine *e, const fb_nes_params *p, int64_t N, const Fb
                                                   e->grad_m.as<double>(), e->adver.as<double>(), ctl, p->seed,
                                                   (uint32_t)(it + 1), p->stream, e->wav.as<int16_t>(),
                                                   e->dist_part.as<double>(), nes_bits(p));
+            e->nes_route[FB_NES_ROUTE_K_UPDATE_PERTURB] += 1;
             e->pre_iter = (long long)it + 1;
             updated = true;
           }
@@ -2668,15 +2685,18 @@ static int attack_loop(fb_engine *e, const fb_nes_params *p, int64_t N, const Fb
                                              e->audio.as<double>(), e->grad_m.as<double>(), e->adver.as<double>(), ctl,
                                              p->seed, (uint32_t)(it + 1), p->stream, sc.m->x, xv,
                                              e->dist_part.as<double>());
+            e->nes_route[FB_NES_ROUTE_K_UPDATE_PERTURB] += 1;
             have_batch = updated = true;
           }
           break;
         }
       }
-      if (!updated)
+      if (!updated) {
         fb_launch_grad_update(e->stream, e->loss.as<double>(), N, half, p->sigma, e->zbuf.as<float>(), noise_dev,
                               nullptr, 1, p->momentum, one_minus_m, 0.0, p->epsilon, e->audio.as<double>(),
                               e->grad_m.as<double>(), e->adver.as<double>(), ctl);
+        e->nes_route[FB_NES_ROUTE_K_GRAD_UPDATE] += 1;
+      }
     }
     HIPCHK(hipMemcpyAsync(e->h_ctl, ctl, sizeof(FbCtlDev), hipMemcpyDeviceToHost, e->stream));
     FBCHK(sync_stream(e));
@@ -2696,6 +2716,7 @@ static int run_attack(fb_engine *e, const fb_nes_params *p, FbScorer sc, const d
                       const double *noise_all, int16_t *adv_i16, double *adver_f64, double *trace, int *n_trace,
                       int *success_flag) {
   if (e) e->bench_it = -1;
+  if (e) memset(e->nes_route, 0, sizeof(e->nes_route));
   if (!audio || !adv_i16 || !success_flag) return fb_fail(FB_E_ARG, "null argument");
   FBCHK(nes_setup(e, p, N, sc, true));
   const bool native = sc.kind == FB_SCORER_NATIVE;
@@ -2770,6 +2791,12 @@ extern "C" int fb_attack_dev(fb_engine *e, const fb_nes_params *p, int S, const 
                              double *adver_f64, double *trace, int *n_trace, int *success_flag) {
   return run_attack(e, p, FbScorer{FB_SCORER_DEV, S, nullptr, m, cb, ctx}, audio, N, noise_all, adv_i16, adver_f64,
                     trace, n_trace, success_flag);
+}
+
+extern "C" int fb_debug_nes_route(fb_engine *e, int *info) {
+  if (!e || !info) return fb_fail(FB_E_ARG, "null argument");
+  for (int i = 0; i < FB_NES_ROUTE_N; ++i) info[i] = e->nes_route[i];
+  return FB_OK;
 }
 
 extern "C" int fb_debug_foreign_path(fb_engine *e, fb_foreign_path_info *info) {

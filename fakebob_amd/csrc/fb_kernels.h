@@ -451,7 +451,7 @@ struct FbIvTail {
   int loss;             // 1 (needs backend): the last arriver runs fb_loss_body<true, true>
   double *llr;          // [B][S]
   int *counter;         // arrivals (one int, zero before the first launch)
-  const int *tv;
+  const int *tv;        // voiced frames per row: filled in by run_scoring, behind the front end that may regrow the buffer
   int task, attack_type;
   const double *z_mean, *z_std;
   double threshold, adver_thresh;

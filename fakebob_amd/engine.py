@@ -618,6 +618,16 @@ class Engine(object):
                     model_calls=int(info.model_calls), batch_bytes_d2h=int(info.batch_bytes_d2h),
                     score_bytes_h2d=int(info.score_bytes_h2d))
 
+    _NES_ROUTE = ("iv_tail", "fin_loss", "fin_loss_update", "k_loss", "k_update_perturb", "k_grad_update")
+
+    def debug_nes_route(self):
+        """Where the loss and the momentum step of the last get_grad* / attack* call ran (fb_debug_nes_route): a dict of
+        launch counts -- iv_tail, fin_loss, fin_loss_update, k_loss, k_update_perturb, k_grad_update -- one per NES
+        iteration the call queued."""
+        info = (C.c_int * len(self._NES_ROUTE))()
+        N.check(self._L.fb_debug_nes_route(self._h, info))
+        return dict(zip(self._NES_ROUTE, (int(v) for v in info)))
+
     def estimate_threshold(self, params, model_threshold, audio, noise_all=None, max_total_iters=100000):
         audio = np.ascontiguousarray(audio, np.float64).reshape(-1)
         n = audio.size

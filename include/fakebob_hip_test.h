@@ -159,6 +159,18 @@ typedef struct {
 } fb_foreign_path_info;
 int fb_debug_foreign_path(fb_engine *e, fb_foreign_path_info *info);
 
+/* Where the loss and the momentum step of the last fb_get_grad* / fb_attack* call ran: info[FB_NES_ROUTE_N] counts the
+ * launches of each kind the call enqueued, one per NES iteration queued (those queued behind the stopping iteration
+ * included).  Recorded on the host as the work is enqueued. */
+#define FB_NES_ROUTE_IV_TAIL 0            /* the loss body in the tail of the i-vector solve kernel */
+#define FB_NES_ROUTE_FIN_LOSS 1           /* k_gmm_finalize_loss: GMM finalisation + loss body */
+#define FB_NES_ROUTE_FIN_LOSS_UPDATE 2    /* k_gmm_finalize_loss_update: ... + momentum step + the next batch */
+#define FB_NES_ROUTE_K_LOSS 3             /* k_loss / k_loss_eot on their own */
+#define FB_NES_ROUTE_K_UPDATE_PERTURB 4   /* k_update_perturb / k_update_perturb_x: momentum step + the next batch */
+#define FB_NES_ROUTE_K_GRAD_UPDATE 5      /* k_grad_update on its own */
+#define FB_NES_ROUTE_N 6
+int fb_debug_nes_route(fb_engine *e, int *info);
+
 /* Which diagonal-GMM arithmetic the loaded model runs on: 2 = two-term f16 split (k_gmm_fx2w / k_gmm_fx2, default),
  * 1 = exact three-term bf16 split (k_gmm_bx3: chosen automatically when a parameter does not fit f16's exponent
  * range; FB_GMM_MODE=bx3 forces it).  Negative FB_E_* without a model.
