@@ -40,29 +40,30 @@ def load_spk_models(model_dir, spk_id_list, architecture):
 
 
 def make_model(architecture, task, model_list, pre_model_dir, threshold, group_id, dither=None, input_transform=None,
-               feature_compression=None):
+               feature_compression=None, air_channel=None):
     """attackMain.load_model (:38-85).  dither: the systems' keyword (Kaldi's --dither: a number, or "conf");
     input_transform: theirs too (the defended victim's input-transform chain, a spec such as "ms:7"); feature_compression:
-    theirs as well (the feature-level defence, a spec such as "0.5" or "0.5:10")."""
+    theirs as well (the feature-level defence, a spec such as "0.5" or "0.5:10"); air_channel: theirs too (the random room
+    in front of the victim, a spec such as "t60:200-600,drr:6")."""
     from .systems import gmm_CSI, gmm_OSI, gmm_SV, iv_CSI, iv_OSI, iv_SV
     ubm = os.path.join(pre_model_dir, "final.dubm")
     if architecture == "iv":
         if task == "OSI":
             return iv_OSI(group_id, model_list, pre_model_dir=pre_model_dir, threshold=threshold, dither=dither,
-                          input_transform=input_transform, feature_compression=feature_compression)
+                          input_transform=input_transform, feature_compression=feature_compression, air_channel=air_channel)
         if task == "CSI":
             return iv_CSI(group_id, model_list, pre_model_dir=pre_model_dir, dither=dither,
-                          input_transform=input_transform, feature_compression=feature_compression)
+                          input_transform=input_transform, feature_compression=feature_compression, air_channel=air_channel)
         return iv_SV(group_id, model_list[0], pre_model_dir=pre_model_dir, threshold=threshold, dither=dither,
-                          input_transform=input_transform, feature_compression=feature_compression)
+                          input_transform=input_transform, feature_compression=feature_compression, air_channel=air_channel)
     if task == "OSI":
         return gmm_OSI(group_id, model_list, ubm, pre_model_dir=pre_model_dir, threshold=threshold, dither=dither,
-                          input_transform=input_transform, feature_compression=feature_compression)
+                          input_transform=input_transform, feature_compression=feature_compression, air_channel=air_channel)
     if task == "CSI":
         return gmm_CSI(group_id, model_list, pre_model_dir=pre_model_dir, dither=dither,
-                          input_transform=input_transform, feature_compression=feature_compression)
+                          input_transform=input_transform, feature_compression=feature_compression, air_channel=air_channel)
     return gmm_SV(group_id, model_list[0], ubm, pre_model_dir=pre_model_dir, threshold=threshold, dither=dither,
-                          input_transform=input_transform, feature_compression=feature_compression)
+                          input_transform=input_transform, feature_compression=feature_compression, air_channel=air_channel)
 
 
 def collect_voices(data_dir):
@@ -172,6 +173,10 @@ def main(argv=None, model_factory=None, bob_factory=None):
                     help="attack a defended victim: the input-transform chain in front of its recogniser, e.g. 'ms:7', "
                          "'qt:512', 'ds:2', 'lpf:4000' or several joined by commas (fakebob_amd/input_transform.py); "
                          "default: none, or FB_INPUT_TRANSFORM")
+    ap.add_argument("--air-channel", dest="air_channel", default=None, metavar="SPEC",
+                    help="attack over the air: a random room impulse response in front of the victim, drawn afresh for "
+                         "every query, e.g. 't60:200-600,drr:6,taps:2048,delay:32' (t60 in ms, required; "
+                         "fakebob_amd/air_channel.py); randomised, so combine with --eot-size; default: none, or FB_AIR_CHANNEL")
     ap.add_argument("--feco", dest="feco", default=None, metavar="RATIO[:ITERS]",
                     help="attack a victim defended by feature compression: k-means over every utterance's voiced frames, "
                          "RATIO * T cluster centres scored in their place after ITERS (default 10) Lloyd iterations, e.g. "
@@ -222,7 +227,7 @@ def main(argv=None, model_factory=None, bob_factory=None):
     if model_factory is None:
         model_list = load_spk_models(args.model_dir, spk_id_list, args.architecture)
         kw = {k: v for k, v in (("dither", args.dither), ("input_transform", args.input_transform),
-                                       ("feature_compression", args.feco)) if v is not None}
+                                       ("feature_compression", args.feco), ("air_channel", args.air_channel)) if v is not None}
         model_factory = functools.partial(make_model, **kw) if kw else make_model
     else:
         model_list = spk_id_list

@@ -115,6 +115,10 @@ struct fb_engine {
   DevBuf tf_power;              // k_tf_power's per-utterance sums of squares (chains with an SNR stage)
   int eot = 1;                  // fb_set_eot: replicas of every NES row (1: none)
   DevBuf eot_sc, eot_l;         // k_loss_eot's per-replica scores [B * r][S] and losses [B * r]
+  // over-the-air channel (fb_set_air_channel; its contract is in fakebob_hip.h): air.L == 0 -- none
+  FbAir air = {};               // the setting (the key fields are filled per launch: fb_air_key)
+  DevBuf wav_air;               // the channel's output, in the replicated layout: what the chain -- or, without one, the MFCC -- reads
+  DevBuf air_taps;              // k_air_taps' responses [rows][L] int16
   // companion utterances (fb_set_companions; the "Composition" paragraph of fakebob_hip.h): comp_K1 == 0 -- none
   int comp_K1 = 0;              // companions set; with the call's own utterance K = comp_K1 + 1
   int64_t comp_N = 0;           // ... their length
@@ -1299,6 +1303,32 @@ static int launch_transform_replicas(fb_engine *e, const int16_t *in, const int6
   else fb_launch_input_transform_rnd(e->stream, e->tf, e->tf_taps.as<double>(), in, in_off, B_in, n_max, out, out_off, rn, stop);
   return FB_OK;
 }
+// The over-the-air channel and the chain behind it: rows = B_in * r output rows (row R = replica R % r of utterance row R / r
+// of `in`; with cn utterance (R % r) / eot of that row as composed) go through k_air_taps + k_air_conv into e->wav_air at
+// out_off, then -- if a chain is set -- through the chain's launch in its "input already replicated" mode into e->wav_tf
+// (both buffers sized by the caller: out_samples).  *res: the buffer that holds the result.
+static int launch_air_path(fb_engine *e, const int16_t *in, const int64_t *in_off, int B_in, int r, int eot, int64_t n_max,
+                           size_t out_samples, const int64_t *out_off, const FbRngPoint &pt, const FbTfComp *cn, const int *stop,
+                           const int16_t **res) {
+  const int rows = B_in * r, L = e->air.L;
+  FBCHK(e->wav_air.ensure(sizeof(int16_t) * out_samples));
+  FBCHK(e->air_taps.ensure(sizeof(int16_t) * (size_t)rows * (size_t)L));
+  fb_launch_air_taps(e->stream, fb_air_key(pt, e->air, r), 0, rows, e->air_taps.as<int16_t>(), nullptr, nullptr, stop);
+  fb_launch_air_conv(e->stream, in, in_off, rows, r, eot, n_max, e->air_taps.as<int16_t>(), L, e->wav_air.as<int16_t>(), out_off, cn, stop);
+  *res = e->wav_air.as<int16_t>();
+  if (e->tf.n == 0) return FB_OK;
+  FBCHK(e->wav_tf.ensure(sizeof(int16_t) * out_samples));
+  if (tf_noise_stages(e->tf, false) == 0) {
+    fb_launch_input_transform(e->stream, e->tf, e->tf_taps.as<double>(), e->wav_air.as<int16_t>(), out_off, rows, n_max,
+                              e->wav_tf.as<int16_t>(), stop);
+  } else {  // the noise stages draw with (utterance row R / r, replica R % r); k_tf_power, the plain form, sums the channel's output rows
+    FbTfRnd rn = fb_tf_rnd(pt, 1);
+    rn.pre = r;
+    FBCHK(launch_transform_replicas(e, e->wav_air.as<int16_t>(), out_off, rows, n_max, e->wav_tf.as<int16_t>(), out_off, rn, nullptr, stop));
+  }
+  *res = e->wav_tf.as<int16_t>();
+  return FB_OK;
+}
 // With r = call.replicas() > 1 (an NES batch under fb_set_eot) B counts the REPLICATED rows: e->wav holds B / r utterances of
 // equal length -- the first B / r + 1 entries of e->wav_off describe them -- and replica j of utterance u goes to row
 // u * r + j of e->wav_tf, every time and with an empty chain too.  With call.K > 1 (fb_set_companions) the same launch
@@ -1306,11 +1336,16 @@ static int launch_transform_replicas(fb_engine *e, const int16_t *in, const int6
 static int transformed_wav(fb_engine *e, const FbScoreCall &call, const int64_t *off, int B, const int16_t **wav) {
   *wav = e->wav.as<int16_t>();
   const int r = call.replicas();
-  if (e->tf.n == 0 && r == 1) return FB_OK;
+  if (e->tf.n == 0 && r == 1 && e->air.L == 0) return FB_OK;
   if (B > 65535) return fb_fail(FB_E_LIMIT, "an input-transform chain takes batches of up to 65535 utterances");
   int64_t n_max = 0;
   for (int b = 0; b < B; ++b) n_max = std::max(n_max, off[b + 1] - off[b]);
   if (n_max > 0x7fffffffLL) return fb_fail(FB_E_LIMIT, "utterance longer than 2^31 samples");
+  if (e->air.L > 0) {  // (fb_set_air_channel) the channel writes the replicas, the chain follows row by row
+    const FbTfComp cn{call.K, e->comp_N, e->comp_a0.as<int16_t>(), e->comp_wav.as<int16_t>()};
+    return launch_air_path(e, e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), B / r, r, call.eot, n_max, (size_t)off[B],
+                           e->wav_off.as<int64_t>(), call.pt, call.K > 1 ? &cn : nullptr, call.stop, wav);
+  }
   FBCHK(e->wav_tf.ensure(sizeof(int16_t) * (size_t)off[B]));
   if (r == 1 && tf_noise_stages(e->tf, false) == 0) {
     fb_launch_input_transform(e->stream, e->tf, e->tf_taps.as<double>(), e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), B, n_max,
@@ -3327,6 +3362,78 @@ extern "C" int fb_debug_input_transform(fb_engine *e, const int16_t *wav, const 
   return FB_OK;
 }
 
+// ---- over-the-air channel (the contract: include/fakebob_hip.h)
+extern "C" int fb_set_air_channel(fb_engine *e, const fb_air_params *p) {
+  if (!e) return fb_fail(FB_E_ARG, "null engine");
+  FbAir set = {};
+  if (p && p->taps != 0) {  // everything is checked before anything is changed: a refusal keeps the previous setting
+    if (p->taps < 2 || p->taps > 4096) return fb_fail(FB_E_ARG, "a room response of %d taps: 2 .. 4096, or 0 for none", p->taps);
+    if (p->predelay < 1 || p->predelay > p->taps - 1) return fb_fail(FB_E_ARG, "predelay %d outside 1 .. taps - 1 = %d", p->predelay, p->taps - 1);
+    if (!(p->amp >= 0.0 && p->amp <= 16384.0))  // (NaN fails the comparisons too)
+      return fb_fail(FB_E_ARG, "amp = %g is not in 0 .. 16384", p->amp);
+    if (!(p->rho_lo > 0.0 && p->rho_lo <= p->rho_hi && p->rho_hi <= 1.0))
+      return fb_fail(FB_E_ARG, "decay range %g .. %g: 0 < rho_lo <= rho_hi <= 1", p->rho_lo, p->rho_hi);
+    set.L = p->taps;
+    set.d = p->predelay;
+    set.amp = p->amp;
+    set.rho_lo = p->rho_lo;
+    set.rho_hi = p->rho_hi;
+  }
+  e->air = set;
+  e->bench_it = -1;  // an attack fb_bench_nes left resident was scored through the previous setting
+  return FB_OK;
+}
+
+extern "C" int fb_debug_air_taps(fb_engine *e, uint64_t seed, uint32_t stream, uint32_t epoch, uint32_t utt, int replica, int16_t *taps,
+                                 float *z, uint32_t *w) {
+  if (!e || !taps || replica < 0 || replica > 31) return fb_fail(FB_E_ARG, "bad argument");
+  if (e->air.L == 0) return fb_fail(FB_E_STATE, "no over-the-air channel is set: fb_set_air_channel first");
+  const int L = e->air.L, L4 = 4 * ((L + 3) / 4);
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  DevBuf d_t, d_z, d_w;
+  FBCHK(d_t.ensure(sizeof(int16_t) * (size_t)L));
+  FBCHK(d_z.ensure(sizeof(float) * (size_t)L4));
+  FBCHK(d_w.ensure(sizeof(uint32_t)));
+  fb_launch_air_taps(e->stream, fb_air_key(FbRngPoint{seed, stream, epoch, utt}, e->air, 1), replica, 1, d_t.as<int16_t>(), d_z.as<float>(),
+                     d_w.as<uint32_t>(), nullptr);
+  HIPCHK(hipGetLastError());
+  FBCHK(d2h(e, taps, d_t.p, sizeof(int16_t) * (size_t)L));
+  if (z) FBCHK(d2h(e, z, d_z.p, sizeof(float) * (size_t)L));
+  if (w) FBCHK(d2h(e, w, d_w.p, sizeof(uint32_t)));
+  FBCHK(sync_stream(e));
+  return FB_OK;
+}
+
+extern "C" int fb_debug_air_convolve(fb_engine *e, const int16_t *wav, const int64_t *off, int B, const int16_t *taps, int L, int16_t *out) {
+  if (!e || !wav || !off || !taps || !out || B <= 0 || B > 65535 || L < 2 || L > 4096) return fb_fail(FB_E_ARG, "bad argument");
+  if (off[0] != 0) return fb_fail(FB_E_ARG, "off[0] must be 0");
+  int64_t n_max = 0;
+  for (int b = 0; b < B; ++b) {
+    const int64_t n = off[b + 1] - off[b];
+    if (n <= 0) return fb_fail(FB_E_ARG, "utterance %d is empty", b);
+    if (n > 0x7fffffffLL) return fb_fail(FB_E_LIMIT, "utterance %d longer than 2^31 samples", b);
+    n_max = std::max(n_max, n);
+  }
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  const size_t bytes = sizeof(int16_t) * (size_t)off[B];
+  DevBuf d_in, d_off, d_t, d_out;
+  FBCHK(d_in.ensure(bytes));
+  FBCHK(d_out.ensure(bytes));
+  FBCHK(d_off.ensure(sizeof(int64_t) * (size_t)(B + 1)));
+  FBCHK(d_t.ensure(sizeof(int16_t) * (size_t)B * (size_t)L));
+  FBCHK(h2d(e, d_in.p, wav, bytes));
+  FBCHK(h2d(e, d_off.p, off, sizeof(int64_t) * (size_t)(B + 1)));
+  FBCHK(h2d(e, d_t.p, taps, sizeof(int16_t) * (size_t)B * (size_t)L));
+  fb_launch_air_conv(e->stream, d_in.as<int16_t>(), d_off.as<int64_t>(), B, 1, 1, n_max, d_t.as<int16_t>(), L, d_out.as<int16_t>(),
+                     d_off.as<int64_t>(), nullptr, nullptr);
+  HIPCHK(hipGetLastError());
+  FBCHK(d2h(e, out, d_out.p, bytes));
+  FBCHK(sync_stream(e));
+  return FB_OK;
+}
+
 // ---- expectation over transformation
 extern "C" int fb_set_eot(fb_engine *e, int r) {
   if (!e) return fb_fail(FB_E_ARG, "null engine");
@@ -3384,10 +3491,15 @@ extern "C" int fb_debug_compose(fb_engine *e, const int16_t *q, int B, int64_t N
   FBCHK(h2d(e, e->wav_off.p, off.data(), sizeof(int64_t) * off.size()));
   FBCHK(h2d(e, d_a0.p, a0, sizeof(int16_t) * (size_t)N));
   const FbTfComp cn{K, N, d_a0.as<int16_t>(), e->comp_wav.as<int16_t>()};
-  FBCHK(launch_transform_replicas(e, e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), B, N, e->wav_tf.as<int16_t>(),
-                                  e->wav_off.as<int64_t>(), fb_tf_rnd(FbRngPoint{seed, stream, epoch, 0}, r), &cn, nullptr));
+  const int16_t *res = e->wav_tf.as<int16_t>();
+  if (e->air.L > 0)
+    FBCHK(launch_air_path(e, e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), B, R, r, N, (size_t)B * (size_t)N * R, e->wav_off.as<int64_t>(),
+                          FbRngPoint{seed, stream, epoch, 0}, K > 1 ? &cn : nullptr, nullptr, &res));
+  else
+    FBCHK(launch_transform_replicas(e, e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), B, N, e->wav_tf.as<int16_t>(),
+                                    e->wav_off.as<int64_t>(), fb_tf_rnd(FbRngPoint{seed, stream, epoch, 0}, r), &cn, nullptr));
   HIPCHK(hipGetLastError());
-  FBCHK(d2h(e, out, e->wav_tf.p, bytes * R));
+  FBCHK(d2h(e, out, res, bytes * R));
   FBCHK(sync_stream(e));
   return FB_OK;
 }
@@ -3496,10 +3608,15 @@ extern "C" int fb_debug_input_transform_eot(fb_engine *e, const int16_t *wav, co
   FBCHK(h2d(e, e->wav.p, wav, bytes));
   FBCHK(h2d(e, e->wav_off.p, off, sizeof(int64_t) * (B + 1)));
   FBCHK(h2d(e, d_out_off.p, out_off.data(), sizeof(int64_t) * out_off.size()));
-  FBCHK(launch_transform_replicas(e, e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), B, n_max, e->wav_tf.as<int16_t>(),
-                                  d_out_off.as<int64_t>(), fb_tf_rnd(FbRngPoint{seed, stream, epoch, 0}, r), nullptr, nullptr));
+  const int16_t *res = e->wav_tf.as<int16_t>();
+  if (e->air.L > 0)
+    FBCHK(launch_air_path(e, e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), B, r, r, n_max, (size_t)off[B] * r, d_out_off.as<int64_t>(),
+                          FbRngPoint{seed, stream, epoch, 0}, nullptr, nullptr, &res));
+  else
+    FBCHK(launch_transform_replicas(e, e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), B, n_max, e->wav_tf.as<int16_t>(),
+                                    d_out_off.as<int64_t>(), fb_tf_rnd(FbRngPoint{seed, stream, epoch, 0}, r), nullptr, nullptr));
   HIPCHK(hipGetLastError());
-  FBCHK(d2h(e, out, e->wav_tf.p, bytes * r));
+  FBCHK(d2h(e, out, res, bytes * r));
   FBCHK(sync_stream(e));
   return FB_OK;
 }

@@ -65,14 +65,17 @@ void fb_launch_input_transform(hipStream_t s, const FbTfChain &ch, const double 
 size_t fb_input_transform_lds_bytes(const FbTfChain &ch, bool rnd = false);
 // What a randomised / replicating transform launch carries of the noise RNG contract (include/fakebob_hip.h): the Philox
 // key (seed_lo ^ "NOIS", seed_hi ^ stream), counter word 3, the row of the batch's first utterance within the call, the
-// replicas written per utterance (fb_set_eot) and the per-utterance sums of squares k_tf_power left (SNR stages; else null)
+// replicas written per utterance (fb_set_eot) and the per-utterance sums of squares k_tf_power left (SNR stages; else null).
+// pre > 0: the input is already replicated (the over-the-air channel wrote it) -- input row R is replica R % pre of
+// utterance row R / pre, draws as such, and is written once, to row R (r is not read)
 struct FbTfRnd {
   uint32_t k0, k1, epoch, utt0;
   int r;
   const unsigned long long *power;
+  int pre;
 };
 static inline FbTfRnd fb_tf_rnd(const FbRngPoint &pt, int r = 1) {
-  return FbTfRnd{(uint32_t)pt.seed ^ 0x4E4F4953u, (uint32_t)(pt.seed >> 32) ^ pt.stream, pt.epoch, pt.utt0, r, nullptr};
+  return FbTfRnd{(uint32_t)pt.seed ^ 0x4E4F4953u, (uint32_t)(pt.seed >> 32) ^ pt.stream, pt.epoch, pt.utt0, r, nullptr, 0};
 }
 // power[u] = the exact sum of squares of utterance u of wav (zeroed here, then one integer atomic per tile); honours `stop`
 // returns the memset's status
@@ -100,6 +103,29 @@ hipError_t fb_launch_tf_power_cmp(hipStream_t s, const int16_t *wav, const int64
                                   unsigned long long *power, const FbTfComp &cn, const int *stop);
 // z[n] = the normals a noise stage adds to samples i0 .. i0 + n - 1 of utterance rn.utt0 (fb_debug_tf_noise)
 void fb_launch_tf_noise(hipStream_t s, const FbTfRnd &rn, int replica, int stage, int64_t i0, int64_t n, float *z);
+
+// ---- over-the-air channel (fb_set_air_channel; air_channel_kernel.hip) -------------------------------------------
+// What a launch carries of the channel's contract (include/fakebob_hip.h): the setting (L == 0: no channel), the Philox key
+// (seed_lo ^ "AIRC", seed_hi ^ stream), counter word 3, the row of the batch's first utterance within the call and the output
+// rows per utterance row (K * eot)
+struct FbAir {
+  int L, d;
+  double amp, rho_lo, rho_hi;
+  uint32_t k0, k1, epoch, utt0;
+  int r;
+};
+static inline FbAir fb_air_key(const FbRngPoint &pt, const FbAir &set, int r = 1) {
+  return FbAir{set.L, set.d, set.amp, set.rho_lo, set.rho_hi, (uint32_t)pt.seed ^ 0x41495243u, (uint32_t)(pt.seed >> 32) ^ pt.stream,
+               pt.epoch, pt.utt0, r};
+}
+// taps[rows][ac.L]: output row R is utterance row ac.utt0 + R / ac.r, replica rep0 + R % ac.r.  z (nullable): the normals
+// [rows][4 * ceil(L / 4)] as drawn; w (nullable): [rows] the decay's words.  Honours `stop`.
+void fb_launch_air_taps(hipStream_t s, const FbAir &ac, int rep0, int rows, int16_t *taps, float *z, uint32_t *w, const int *stop);
+// out row R (at out_off[R]; R = 0 .. rows - 1) = row R / r of wav (in_off) -- with cn (nullable) utterance (R % r) / eot of
+// that row as composed -- convolved with taps[R][L]; n_max = the longest row.  Honours `stop`.
+void fb_launch_air_conv(hipStream_t s, const int16_t *wav, const int64_t *in_off, int rows, int r, int eot, int64_t n_max,
+                        const int16_t *taps, int L, int16_t *out, const int64_t *out_off, const FbTfComp *cn, const int *stop);
+size_t fb_air_conv_lds_bytes(int L);
 
 // ---- feature compression (fb_set_feature_compression; feature_compress_kernel.hip) -------------------------------
 // What a launch carries of the stage contract (include/fakebob_hip.h): the setting, the Philox key (seed_lo ^ "FECO",

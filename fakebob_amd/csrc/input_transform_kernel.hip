@@ -23,6 +23,8 @@
 // positions two neighbouring workgroups both compute get the same value.  An SNR stage scales by the utterance's power,
 // which k_tf_power -- the launch in front -- summed: nothing is exchanged inside a kernel here either.  The instantiation
 // without RND is the kernel as it was: a chain without noise and without replication runs the same code as before.
+// With rn.pre set (the over-the-air channel, air_channel_kernel.hip, has written the replicas already) the RND form runs
+// the chain once per input row and only the two indices a noise stage draws with are taken from the row's number.
 #include "fb_device.h"
 #include "fb_kernels.h"
 
@@ -114,7 +116,7 @@ static __device__ __forceinline__ void tf_tile(int16_t *tf_lds, const FbTfChain 
     }
   }
   __syncthreads();
-  const int reps = CMP ? cn.K * rn.r : (RND ? rn.r : 1);
+  const int reps = CMP ? cn.K * rn.r : (RND ? (rn.pre ? 1 : rn.r) : 1);
   for (int rep = 0; rep < reps; ++rep) {
   if (CMP && rep % rn.r == 0) {  // the next utterance (the replica before it has left the buffers: the barrier at the loop's end)
     const int c = rep / rn.r;
@@ -137,7 +139,9 @@ static __device__ __forceinline__ void tf_tile(int16_t *tf_lds, const FbTfChain 
       const int64_t i_first = ((g0 + lo) >> 2) << 2;  // (arithmetic shift: rounds toward -inf for the halo in front of sample 0)
       for (int64_t i4 = i_first + 4 * tid; i4 < g0 + hi; i4 += 4 * TF_THREADS) {
         float z[4] = {0.f, 0.f, 0.f, 0.f};
-        if (i4 + 3 >= 0 && i4 < n) tf_noise4(rn, (uint32_t)u, s, rep, (uint32_t)(i4 >> 2), z);
+        // (rn.pre: the over-the-air channel wrote the replicas -- row u is replica u % pre of utterance row u / pre)
+        if (i4 + 3 >= 0 && i4 < n)
+          tf_noise4(rn, (uint32_t)(!CMP && rn.pre ? u / rn.pre : u), s, !CMP && rn.pre ? u % rn.pre : rep, (uint32_t)(i4 >> 2), z);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int64_t i = i4 + q;

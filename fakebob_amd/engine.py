@@ -47,6 +47,7 @@ class Engine(object):
         self.cfg = N.FrontendCfg()
         self._L.fb_default_frontend(C.byref(self.cfg))
         self.input_transform = []
+        self.air_channel = None
         self.eot = 1
         self.companions = None
         self.feature_compression = None
@@ -103,6 +104,54 @@ class Engine(object):
         cat = np.ascontiguousarray(np.concatenate(lst))
         out = np.empty_like(cat)
         N.check(self._L.fb_debug_input_transform(self._h, N.ptr(cat), N.ptr(off), C.c_int(len(lst)), N.ptr(out)))
+        return [out[off[i]:off[i + 1]].copy() for i in range(len(lst))]
+
+    def set_air_channel(self, channel, validate=True):
+        """The over-the-air channel (fb_set_air_channel): a spec string ("t60:200-600,drr:6,taps:2048,delay:32"), a
+        fakebob_amd.air_channel.AirChannel, or None / "none" to clear it.  The engine then convolves every utterance its own
+        front end reads -- scoring, enrolment statistics, every NES batch, the PSO swarm -- with a random room impulse response
+        drawn afresh per (query, row, utterance, draw), directly in front of the input-transform chain; not the batch of a
+        foreign model and not the returned audio.  The limits are checked here before the call (ValueError); validate=False
+        hands a (taps, predelay, amp, rho_lo, rho_hi) tuple to the library as it is (it refuses what is outside the contract
+        and keeps the previous setting)."""
+        from . import air_channel as A
+        if validate:
+            ch = A.parse(channel)
+            vals = None if ch is None else (ch.taps, ch.predelay, ch.amp, ch.rho_lo, ch.rho_hi)
+        else:
+            ch = vals = channel
+        if vals is None:
+            N.check(self._L.fb_set_air_channel(self._h, None))
+        else:
+            p = N.AirParams(int(vals[0]), int(vals[1]), float(vals[2]), float(vals[3]), float(vals[4]))
+            N.check(self._L.fb_set_air_channel(self._h, C.byref(p)))
+        self.air_channel = ch
+
+    def debug_air_taps(self, seed, stream, epoch, utt=0, replica=0):
+        """What k_air_taps writes for one row under the channel set (fb_debug_air_taps): (taps int16 (L,), the float32
+        normals z (L,), the decay's 32-bit word w)."""
+        if self.air_channel is None:
+            raise ValueError("no air channel is set")
+        L = int(self.air_channel[0] if isinstance(self.air_channel, tuple) else self.air_channel.taps)
+        taps, z, w = np.empty(L, np.int16), np.empty(L, np.float32), C.c_uint32(0)
+        N.check(self._L.fb_debug_air_taps(self._h, C.c_uint64(int(seed)), C.c_uint32(int(stream)), C.c_uint32(int(epoch)),
+                                          C.c_uint32(int(utt)), C.c_int(int(replica)), N.ptr(taps), N.ptr(z), C.byref(w)))
+        return taps, z, int(w.value)
+
+    def debug_air_convolve(self, audio_list, taps):
+        """k_air_conv on taps handed in as they are (fb_debug_air_convolve): int16 utterances of any length >= 1 and int16 taps
+        (B, L), one response per utterance; a list of int16 arrays."""
+        lst = [np.ascontiguousarray(a, np.int16).reshape(-1) for a in audio_list]
+        taps = np.ascontiguousarray(taps, np.int16)
+        taps = taps.reshape(1, -1) if taps.ndim == 1 else taps
+        if taps.shape[0] != len(lst):
+            raise ValueError("%d responses for %d utterances" % (taps.shape[0], len(lst)))
+        off = np.zeros(len(lst) + 1, np.int64)
+        off[1:] = np.cumsum([a.size for a in lst])
+        cat = np.ascontiguousarray(np.concatenate(lst))
+        out = np.empty_like(cat)
+        N.check(self._L.fb_debug_air_convolve(self._h, N.ptr(cat), N.ptr(off), C.c_int(len(lst)), N.ptr(taps),
+                                              C.c_int(taps.shape[1]), N.ptr(out)))
         return [out[off[i]:off[i + 1]].copy() for i in range(len(lst))]
 
     def set_eot(self, r):

@@ -102,6 +102,17 @@ def _apply_input_transform(engine, input_transform):
     engine.set_input_transform(input_transform)
 
 
+def _apply_air_channel(engine, air_channel):
+    """The over-the-air channel of a system under construction: the constructor keyword -- a spec string such as
+    "t60:200-600,drr:6" or a fakebob_amd.air_channel.AirChannel; "none" for no channel --, then FB_AIR_CHANNEL.  None of
+    the two: the engine keeps its setting (none unless the caller set one)."""
+    if air_channel is None:
+        air_channel = os.environ.get("FB_AIR_CHANNEL")
+        if air_channel is None or air_channel == "":
+            return
+    engine.set_air_channel(air_channel)
+
+
 def eot_option(eot_size):
     """The expectation-over-transformation size asked for: the `eot_size` keyword (the system classes', FakeBob's), then
     FB_EOT_SIZE.  None: nobody asked, the engine keeps its value (1 unless the caller set one)."""
@@ -213,7 +224,7 @@ class _GmmSystem(object):
     PIPELINE = None  # class default of the two round trips (see REFERENCE_PIPELINE)
 
     def _setup(self, group_id, models, spk_ids, utt_ids, locations, z_means, z_stds, pre_model_dir, engine,
-               text_scores=None, compress_feats=None, mfcc_f32=None, dither=None, input_transform=None, eot_size=None, feature_compression=None, companions=None):
+               text_scores=None, compress_feats=None, mfcc_f32=None, dither=None, input_transform=None, eot_size=None, feature_compression=None, companions=None, air_channel=None):
         self.pre_model_dir = os.path.abspath(pre_model_dir)
         self.group_id = os.path.abspath(group_id)
         self.spk_ids = spk_ids
@@ -224,6 +235,7 @@ class _GmmSystem(object):
         over = _conf_overrides(self.pre_model_dir, dither)
         _apply_frontend(self._engine, over, text_scores, compress_feats, mfcc_f32, self.PIPELINE)
         _apply_input_transform(self._engine, input_transform)
+        _apply_air_channel(self._engine, air_channel)
         apply_eot(self._engine, eot_size)
         apply_feature_compression(self._engine, feature_compression)
         apply_companions(self._engine, companions)
@@ -252,14 +264,14 @@ class gmm_OSI(_GmmSystem):
 
     def __init__(self, group_id, model_list, ubm, pre_model_dir="pre-models", threshold=0.0, engine=None,
                  text_scores=None, compress_feats=None, mfcc_f32=None, dither=None,
-                 input_transform=None, eot_size=None, feature_compression=None, companions=None):
+                 input_transform=None, eot_size=None, feature_compression=None, companions=None, air_channel=None):
         self.threshold = threshold
         locs = [m[2] for m in model_list]
         self.model_list = [ubm] + locs  # UBM first (gmm_ubm_OSI.py:45)
         models = [load_gmm_any(x) for x in self.model_list]
         self._setup(group_id, models, [m[0] for m in model_list], [m[1] for m in model_list], locs, None, None,
                     pre_model_dir, engine, text_scores, compress_feats, mfcc_f32, dither,
-                    input_transform, eot_size, feature_compression, companions)
+                    input_transform, eot_size, feature_compression, companions, air_channel)
 
     def score(self, audios, fs=16000, bits_per_sample=16, debug=False, n_jobs=5):
         raw = self._raw(audios, bits_per_sample)
@@ -286,7 +298,7 @@ class gmm_CSI(_GmmSystem):
 
     def __init__(self, group_id, model_list, pre_model_dir="pre-models", engine=None, text_scores=None,
                  compress_feats=None, mfcc_f32=None, dither=None,
-                 input_transform=None, eot_size=None, feature_compression=None, companions=None):
+                 input_transform=None, eot_size=None, feature_compression=None, companions=None, air_channel=None):
         locs = [m[2] for m in model_list]
         self.model_list = locs
         self.z_norm_means = np.array([m[3] for m in model_list], np.float64)
@@ -294,7 +306,7 @@ class gmm_CSI(_GmmSystem):
         models = [load_gmm_any(x) for x in locs]
         self._setup(group_id, models, [m[0] for m in model_list], [m[1] for m in model_list], locs,
                     self.z_norm_means, self.z_norm_stds, pre_model_dir, engine, text_scores, compress_feats, mfcc_f32, dither,
-                    input_transform, eot_size, feature_compression, companions)
+                    input_transform, eot_size, feature_compression, companions, air_channel)
 
     def score(self, audios, fs=16000, bits_per_sample=16, debug=False, n_jobs=5):
         raw = self._raw(audios, bits_per_sample)
@@ -317,7 +329,7 @@ class gmm_SV(_GmmSystem):
 
     def __init__(self, spk_id, model, ubm, pre_model_dir="pre-models", threshold=0.0, engine=None,
                  text_scores=None, compress_feats=None, mfcc_f32=None, dither=None,
-                 input_transform=None, eot_size=None, feature_compression=None, companions=None):
+                 input_transform=None, eot_size=None, feature_compression=None, companions=None, air_channel=None):
         self.threshold = threshold
         self.utt_id = model[1]
         self.identity_location = model[2]
@@ -325,7 +337,7 @@ class gmm_SV(_GmmSystem):
         models = [load_gmm_any(x) for x in self.model_list]
         self._setup(spk_id, models, [model[0]], [model[1]], [model[2]], None, None, pre_model_dir, engine,
                     text_scores, compress_feats, mfcc_f32, dither,
-                    input_transform, eot_size, feature_compression, companions)
+                    input_transform, eot_size, feature_compression, companions, air_channel)
         self.spk_id = self.group_id
 
     def score(self, audios, fs=16000, bits_per_sample=16, debug=False, n_jobs=5):
@@ -348,7 +360,7 @@ class _IvSystem(object):
     PIPELINE = None
 
     def _setup(self, group_id, model_list, pre_model_dir, engine, system, text_scores=None, compress_feats=None, mfcc_f32=None, dither=None,
-               input_transform=None, eot_size=None, feature_compression=None, companions=None):
+               input_transform=None, eot_size=None, feature_compression=None, companions=None, air_channel=None):
         from .models import IvectorSystem
         self.pre_model_dir = os.path.abspath(pre_model_dir)
         self.group_id = os.path.abspath(group_id)
@@ -382,6 +394,7 @@ class _IvSystem(object):
             _apply_frontend(self._engine, _conf_overrides(None, dither), text_scores, compress_feats, mfcc_f32, self.PIPELINE)
             system = system.with_enrolled(enrolled, zm, zs)
         _apply_input_transform(self._engine, input_transform)
+        _apply_air_channel(self._engine, air_channel)
         apply_eot(self._engine, eot_size)
         apply_feature_compression(self._engine, feature_compression)
         apply_companions(self._engine, companions)
@@ -408,10 +421,10 @@ class iv_OSI(_IvSystem):
 
     def __init__(self, group_id, model_list, pre_model_dir="pre-models", threshold=0.0, engine=None, system=None,
                  text_scores=None, compress_feats=None, mfcc_f32=None, dither=None,
-                 input_transform=None, eot_size=None, feature_compression=None, companions=None):
+                 input_transform=None, eot_size=None, feature_compression=None, companions=None, air_channel=None):
         self.threshold = threshold
         self._setup(group_id, model_list, pre_model_dir, engine, system, text_scores, compress_feats, mfcc_f32, dither,
-                    input_transform, eot_size, feature_compression, companions)
+                    input_transform, eot_size, feature_compression, companions, air_channel)
 
     def score(self, audio_list, fs=16000, bits_per_sample=16, n_jobs=10, debug=False):
         s = (self._llr(audio_list, bits_per_sample) - self.z_norm_means) / self.z_norm_stds   # :119
@@ -440,9 +453,9 @@ class iv_CSI(_IvSystem):
 
     def __init__(self, group_id, model_list, pre_model_dir="pre-models", engine=None, system=None, text_scores=None,
                  compress_feats=None, mfcc_f32=None, dither=None,
-                 input_transform=None, eot_size=None, feature_compression=None, companions=None):
+                 input_transform=None, eot_size=None, feature_compression=None, companions=None, air_channel=None):
         self._setup(group_id, model_list, pre_model_dir, engine, system, text_scores, compress_feats, mfcc_f32, dither,
-                    input_transform, eot_size, feature_compression, companions)
+                    input_transform, eot_size, feature_compression, companions, air_channel)
 
     def score(self, audio_list, fs=16000, bits_per_sample=16, n_jobs=10, debug=False):
         s = (self._llr(audio_list, bits_per_sample) - self.z_norm_means) / self.z_norm_stds
@@ -466,10 +479,10 @@ class iv_SV(_IvSystem):
 
     def __init__(self, spk_id, model, pre_model_dir="pre-models", threshold=0.0, engine=None, system=None,
                  text_scores=None, compress_feats=None, mfcc_f32=None, dither=None,
-                 input_transform=None, eot_size=None, feature_compression=None, companions=None):
+                 input_transform=None, eot_size=None, feature_compression=None, companions=None, air_channel=None):
         self.threshold = threshold
         self._setup(spk_id, [model], pre_model_dir, engine, system, text_scores, compress_feats, mfcc_f32, dither,
-                    input_transform, eot_size, feature_compression, companions)
+                    input_transform, eot_size, feature_compression, companions, air_channel)
         self.spk_id = self.group_id
         self.utt_id = model[1]
         self.identity_location = model[2]

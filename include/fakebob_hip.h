@@ -210,6 +210,43 @@ enum { FB_TF_NOISE = 4 };  /* the randomised kind */
 typedef struct { int kind; int k; const double *taps; } fb_tf_stage;
 int fb_set_input_transform(fb_engine *e, const fb_tf_stage *stages, int n);
 
+/* ---- over-the-air channel: a random room in front of the victim ---------------------------------------------------------
+ * An adversarial voice played over the air reaches the victim through a room.  With a channel set every utterance the
+ * chain above would see is first convolved with a room impulse response of L = taps samples drawn afresh for every
+ * (query, row, utterance, draw): a direct path, a predelay of silence, then Gaussian noise under an exponential decay --
+ * hundreds of milliseconds of tail where a FIR stage holds 32 (a FIXED, SHORT response is still a FIR stage).
+ * Where it acts.  Directly in front of the input-transform chain, wherever the chain acts: fb_score_*, fb_gmm_acc_stats,
+ * every NES batch of fb_get_grad / fb_attack / fb_estimate_threshold, fb_attack_pso's swarm, the fb_debug_mfcc / _feats
+ * hooks.  With companions it acts on the composed, clipped rows: composition, then air, then the chain, then the front end.
+ * NOT applied to foreign models (_ext, _dev), to the returned audio or to the distance column.  FB_E_NO_VOICED and
+ * FB_E_LIMIT rules are unchanged.
+ * Random numbers.  Philox4x32-10 on a key of its own:
+ *   key     = (seed_lo ^ 0x41495243 ("AIRC"), seed_hi ^ stream)
+ *   counter = (c0, replica rho, utterance row of the un-replicated batch, epoch)
+ * seed, stream, epoch, utterance row and replica exactly by the rules of the "Noise RNG contract" and of the "Row order"
+ * paragraph of fb_set_companions (rho = u * eot + j; 0 without replication): a scoring call draws afresh, an attack
+ * depends on (seed, stream) only.  c0 = k >> 2 yields the four float32 normals z[4 (k >> 2) .. + 3], the words paired
+ * through the float32 Box-Muller as the noise stage pairs them (words 0, 1 -> z[0], z[1]; words 2, 3 -> z[2], z[3]);
+ * c0 = 0xFFFFFFFF yields the decay's word w = output word 0.
+ * Arithmetic.  Float64, round to nearest, one rounding per written operation, no fused multiply-add; integers exact.
+ *   decay     U = ((double)w + 0.5) * 2^-32;  rho = clip(rho_lo + U * (rho_hi - rho_lo), rho_lo, rho_hi): the difference,
+ *             the product, the sum
+ *   envelope  Q[0] = 1, Q[i] = Q[i - 1] * rho (i = 1 .. 63);  S = Q[63] * rho;  P[0] = 1, P[j] = P[j - 1] * S (j = 1 .. 63);
+ *             e[m] = P[m >> 6] * Q[m & 63]
+ *   taps      int16, Q14, d = predelay:  t[0] = 16384 (the direct path);  t[k] = 0 for 0 < k < d;
+ *             t[k] = (int)min(max(rint((amp * (double)z[k]) * e[k - d]), -32767), 32767) for d <= k < L
+ *   output    y[i] = sum over k = 0 .. min(i, L - 1) of t[k] * x[i - k], exact integer (|y| < 2^42);
+ *             o[i] = clip16((y[i] + 8192) >> 14), arithmetic shift (floor).  The output has the input's length.
+ * So amp = 0 is the identity bit for bit, and a silent row stays silent.  The chain then runs on o with its own contract
+ * untouched: its noise stages draw with (replica rho, utterance row b) as always, and an SNR stage takes E from the row
+ * "as it is handed to the chain" -- the channel's output.  (T60 and the direct-to-reverberant ratio become rho_* and amp
+ * on the host: fakebob_amd/air_channel.py.)
+ * Limits.  taps in 2 .. 4096, predelay in 1 .. taps - 1, amp finite in [0, 16384], 0 < rho_lo <= rho_hi <= 1, both
+ * finite.  Anything else returns FB_E_ARG and keeps the previous setting.  p == NULL or taps == 0 clears the channel (the
+ * default: no launch is added, no code path differs). */
+typedef struct { int taps; int predelay; double amp; double rho_lo, rho_hi; } fb_air_params;
+int fb_set_air_channel(fb_engine *e, const fb_air_params *p);
+
 /* ---- expectation over transformation: attacking a randomised victim ---------------------------------------------------
  * With a noise stage in the chain or dither > 0 the victim answers every query with a fresh draw.  r > 1 makes fb_get_grad
  * and fb_attack score every row of the NES batch under r independent draws and average BEFORE the gradient estimate and the

@@ -65,6 +65,18 @@ int fb_debug_input_transform_eot(fb_engine *e, const int16_t *wav, const int64_t
 int fb_debug_compose(fb_engine *e, const int16_t *q, int B, int64_t N, const int16_t *a0, int r, uint64_t seed,
                      uint32_t stream, uint32_t epoch, int16_t *out);
 
+/* Over-the-air channel (fakebob_hip.h: fb_set_air_channel and its contract).  With a channel set,
+ * fb_debug_input_transform_eot and fb_debug_compose above -- they carry a point of the contract -- apply it in front of the
+ * chain, as the scoring path does; fb_debug_input_transform has no point and ignores the channel.
+ * fb_debug_air_taps: what k_air_taps writes for ONE row -- utterance row `utt`, replica `replica` at (seed, stream, epoch) --
+ * under the engine's channel setting (FB_E_STATE without one): taps[L] int16, and (both nullable) the normals z[L] and the
+ * decay's word w it used.
+ * fb_debug_air_convolve: k_air_conv on taps handed in as they are -- taps[B][L] int16, any values, L in 2 .. 4096 -- over B
+ * rows of any length >= 1 (off[B + 1], off[0] = 0); out has wav's layout.  The engine's setting is neither used nor changed. */
+int fb_debug_air_taps(fb_engine *e, uint64_t seed, uint32_t stream, uint32_t epoch, uint32_t utt, int replica, int16_t *taps,
+                      float *z, uint32_t *w);
+int fb_debug_air_convolve(fb_engine *e, const int16_t *wav, const int64_t *off, int B, const int16_t *taps, int L, int16_t *out);
+
 /* Feature compression (fakebob_hip.h: fb_set_feature_compression and its stage contract).
  * fb_debug_feature_compress: the kernel the scoring paths launch, on feature rows handed in as they are (no front end, no
  * model; D = the front end's feature dimension): feats holds the rows of B * r utterance rows one after the other,
