@@ -405,7 +405,10 @@ int fb_set_frontend(fb_engine *e, const fb_frontend_cfg *cfg);
 /* Diagonal GMMs in Kaldi DiagGmm internal form (float32): gconsts[M*C],
  * means_invvars[M*C*D], inv_vars[M*C*D].  Models whose inv_vars are bitwise
  * identical (mean-only MAP adaptation, build_spk_models.py:170) share the
- * quadratic term on device. */
+ * quadratic term on device.
+ * At most 60 models per engine, the UBM included (the scoring kernels keep 2 KB of logsumexp state per model in LDS: at
+ * 60 models and D = 78 .. 80 they ask for 159 744 of a compute unit's 163 840 bytes).  M > 60 is FB_E_ARG, "at most 60 models per engine
+ * (got M)", refused before anything is touched: the system loaded before stays loaded and scores as it did. */
 int fb_load_gmm(fb_engine *e, int M, int C, int D, const float *gconsts,
                 const float *means_invvars, const float *inv_vars);
 
@@ -435,7 +438,9 @@ typedef struct {
 } fb_ivector_system;
 
 /* Loads an i-vector/PLDA system; scores are PLDA LLRs [B*S]; fb_system_scores / the NES
- * kernels apply (llr - z_mean) / z_std for every task (ivector_PLDA_OSI.py:119). */
+ * kernels apply (llr - z_mean) / z_std for every task (ivector_PLDA_OSI.py:119).
+ * At most 60 enrolled speakers per engine (the NES result block holds 62 scores).  S > 60 is FB_E_ARG, "at most 60
+ * enrolled speakers per engine", refused before anything is touched: the system loaded before stays loaded. */
 int fb_load_ivector(fb_engine *e, const fb_ivector_system *sys, int task);
 
 /* How raw per-model log-likelihoods become system scores:
