@@ -3173,6 +3173,24 @@ static int debug_frontend(fb_engine *e, const int16_t *wav, int64_t n, const FbR
   return FB_OK;
 }
 
+// The launches of enrolment statistics on the n rows (*n_rows_ptr, at most T) of e->feats: the single-model dump, the
+// float32 soft-max and the float64 accumulation; the copies of occ[C] and F[C][D] are queued, the caller synchronises.
+static int gmm_stats_launch(fb_engine *e, const int *n_rows_ptr, int T, double *occ, double *F) {
+  const FbGmmDev &g = e->gmm;
+  const int ld = g.n_tiles * 32;
+  FBCHK(e->enr_ll.ensure(sizeof(float) * (size_t)T * ld));
+  FBCHK(e->enr_aux.ensure(sizeof(float) * 2 * (size_t)T));
+  FBCHK(e->enr_stats.ensure(sizeof(double) * (size_t)g.C * (g.D + 1)));
+  hipStream_t s = e->stream;
+  fb_launch_gmm_dump(s, g, e->feats.as<float>(), n_rows_ptr, T, choose_chunks(g, T, false), e->enr_ll.as<float>(), &e->shape_gmm);
+  double *d_occ = e->enr_stats.as<double>(), *d_F = d_occ + g.C;
+  fb_launch_gmm_post_stats(s, g.C, ld, g.D, e->enr_ll.as<float>(), e->feats.as<float>(), n_rows_ptr, T,
+                           e->enr_aux.as<float>(), e->enr_aux.as<float>() + T, d_occ, d_F);
+  FBCHK(d2h(e, occ, d_occ, sizeof(double) * (size_t)g.C));
+  FBCHK(d2h(e, F, d_F, sizeof(double) * (size_t)g.C * g.D));
+  return FB_OK;
+}
+
 // Enrolment statistics (build_spk_models.py:184-216, `gmm-global-acc-stats --update-flags=m`): posteriors
 // of the loaded GMM (the UBM, loaded alone) on the voiced frames of one utterance.
 extern "C" int fb_gmm_acc_stats(fb_engine *e, const int16_t *wav, int64_t n, double *occ, double *F, int *tv_out) {
@@ -3181,25 +3199,38 @@ extern "C" int fb_gmm_acc_stats(fb_engine *e, const int16_t *wav, int64_t n, dou
     return fb_fail(FB_E_STATE, "load exactly one diagonal GMM (the UBM) before accumulating statistics");
   FBCHK(debug_frontend(e, wav, n));  // MFCC, VAD, deltas, CMVN, voiced rows of this utterance
   const int T = e->h_frame_off[1];
-  const FbGmmDev &g = e->gmm;
-  const int ld = g.n_tiles * 32;
-  FBCHK(e->enr_ll.ensure(sizeof(float) * (size_t)T * ld));
-  FBCHK(e->enr_aux.ensure(sizeof(float) * 2 * (size_t)T));
-  FBCHK(e->enr_stats.ensure(sizeof(double) * (size_t)g.C * (g.D + 1)));
-  hipStream_t s = e->stream;
-  const int *n_rows_ptr = e->row_off.as<int>() + 1;
-  fb_launch_gmm_dump(s, g, e->feats.as<float>(), n_rows_ptr, T, choose_chunks(g, T, false), e->enr_ll.as<float>(), &e->shape_gmm);
-  double *d_occ = e->enr_stats.as<double>(), *d_F = d_occ + g.C;
-  fb_launch_gmm_post_stats(s, g.C, ld, g.D, e->enr_ll.as<float>(), e->feats.as<float>(), n_rows_ptr, T,
-                           e->enr_aux.as<float>(), e->enr_aux.as<float>() + T, d_occ, d_F);
   int tv = 0;
   FBCHK(d2h(e, &tv, e->tv.p, sizeof(int)));
-  FBCHK(d2h(e, occ, d_occ, sizeof(double) * (size_t)g.C));
-  FBCHK(d2h(e, F, d_F, sizeof(double) * (size_t)g.C * g.D));
+  FBCHK(gmm_stats_launch(e, e->row_off.as<int>() + 1, T, occ, F));
   FBCHK(sync_stream(e));
   HIPCHK(hipGetLastError());
   if (tv_out) *tv_out = tv;
   if (tv <= 0) return fb_fail(FB_E_NO_VOICED, "enrolment utterance has no voiced frames");
+  return FB_OK;
+}
+
+// Test hook: the launches of fb_gmm_acc_stats on T rows of features handed in as they are (no front-end); with `ll` the
+// dump matrix comes back as [T][C], without the padding columns of its last 32-component tile.
+extern "C" int fb_debug_gmm_acc_rows(fb_engine *e, const float *feats, int T, float *ll, double *occ, double *F) {
+  if (!e || !feats || !occ || !F || T <= 0) return fb_fail(FB_E_ARG, "bad argument");
+  if (!e->have_gmm || e->kind != 0 || e->gmm.M != 1)
+    return fb_fail(FB_E_STATE, "load exactly one diagonal GMM (the UBM) before accumulating statistics");
+  HIPCHK(hipSetDevice(e->device));
+  const FbGmmDev &g = e->gmm;
+  FBCHK(sync_stream(e));
+  choose_launch_shape(e);
+  FBCHK(e->feats.ensure(sizeof(float) * (size_t)T * g.D));
+  FBCHK(e->row_off.ensure(sizeof(int) * 2));
+  const int rows_host[2] = {0, T};
+  HIPCHK(hipMemcpy(e->feats.p, feats, sizeof(float) * (size_t)T * g.D, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(e->row_off.p, rows_host, sizeof(rows_host), hipMemcpyHostToDevice));
+  e->last_total_frames = 0;  // the feature buffer no longer belongs to a scored batch
+  FBCHK(gmm_stats_launch(e, e->row_off.as<int>() + 1, T, occ, F));
+  FBCHK(sync_stream(e));
+  HIPCHK(hipGetLastError());
+  if (ll)
+    HIPCHK(hipMemcpy2D(ll, sizeof(float) * (size_t)g.C, e->enr_ll.p, sizeof(float) * (size_t)g.n_tiles * 32,
+                       sizeof(float) * (size_t)g.C, (size_t)T, hipMemcpyDeviceToHost));
   return FB_OK;
 }
 

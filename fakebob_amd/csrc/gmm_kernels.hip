@@ -365,12 +365,14 @@ __global__ __launch_bounds__(256, FB_FX_OCC) void k_gmm_fx2(FbGmmDev g, const fl
   //      whose residual is 0), bq = fl(x*x), both moved by the load-time powers of two 2^kx / 2^kx2.
   // Range guard: the load-time scalings assume |x| 2^kx and x^2 2^kx2 below f16's 65504.  Features beyond
   // that (|x| >= 64 with kx2 = 4: liftered cepstra of tonal audio, unusual front-end configurations) would turn
-  // into inf and the scores into NaN.  Each wave therefore takes the largest scaled operand of its 32 frames
-  // and, when it reaches 2^15, moves ALL its frame operands (x, the 1.0 that multiplies gconst, x^2) down by one
-  // wave-uniform power of two 2^-sh: the accumulators then hold ll 2^(kacc - sh), the logsumexp multiplier and
-  // the final un-scaling take the factor back, and every step stays an exact power-of-two scaling.  Small
+  // into inf and the scores into NaN.  Each FRAME therefore takes its largest scaled operand and, when it reaches
+  // 2^15, moves all its operands (x, the 1.0 that multiplies gconst, x^2) down by one power of two 2^-sh of its
+  // own (a lane's accumulators all belong to one frame): they then hold ll 2^(kacc - sh), the logsumexp multiplier
+  // and the final un-scaling take the factor back, and every step stays an exact power-of-two scaling.  Small
   // operands of such a frame may become f16 subnormals (absolute precision 2^-25 of the scaled operand), which is
   // below the f32 rounding of the large terms that caused the shift.  sh = 0 for ordinary speech features.
+  // (The shift was one per wave of 32 frames until the enrolment tests compared the dump per component: an ordinary
+  //  frame next to rows of magnitude 1e4 -- sh = 19 -- lost its operands' second terms and came out 1.4e-4 S off.)
   u32x4 bx1[NK], bx2[NK], bq1[NK], bq2[NK];
   const int sh = fb_fx_frame_frags<NK>(g, feats, row, n_rows, h, bx1, bx2, bq1, bq2);
   for (int m = 0; m < g.M; ++m) { st_m[m * 256 + tid] = FB_GMM_NEG; st_s[m * 256 + tid] = 0.0f; }

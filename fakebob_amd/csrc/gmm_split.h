@@ -30,7 +30,8 @@ __device__ __forceinline__ void fb_split2_frag(const float (&v)[8], u32x4 &f1, u
 }
 
 // The frame operands of a lane of k_gmm_fx2 / k_gmm_fx2_sel / k_gsel_w (see the comment in k_gmm_fx2, gmm_kernels.hip): chunk c = dims 16c + 8h + i,
-// two-term f16 splits of x (1.0 at position D) and x^2 under the load-time powers of two; returns the wave's range shift.
+// two-term f16 splits of x (1.0 at position D) and x^2 under the load-time powers of two; returns the frame's range shift (the
+// same in the two lanes that hold the frame, and its own: an out-of-range frame does not cost its wave's other frames bits).
 // (two steps, so that a kernel with several frames per lane can have every row's loads in flight before the first is used:
 //  fb_fx_frame_load -- D a multiple of 4 -- and fb_fx_frame_make; fb_fx_frame_frags is both for one frame, any D)
 template <int NK>
@@ -76,9 +77,8 @@ __device__ __forceinline__ int fb_fx_frame_make(const FbGmmDev &g, const float *
 #pragma unroll
       for (int i = 0; i < 8; ++i) amax = fmaxf(amax, fmaxf(fabsf(v[i]), q[i]));
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
-    if (amax >= 32768.0f) {  // wave-uniform; finite features only (the front-end produces nothing else)
+    amax = fmaxf(amax, __shfl_xor(amax, 32, 64));  // the frame's other K half: lanes j and j + 32 hold ONE frame
+    if (amax >= 32768.0f) {  // the frame's own; finite features only (the front-end produces nothing else)
       const int ex = (int)((__float_as_uint(amax) >> 23) & 0xffu) - 127;  // amax in [2^ex, 2^(ex+1))
       sh = min(ex - 14, 100);
     }

@@ -766,6 +766,21 @@ class Engine(object):
         N.check(self._L.fb_debug_gmm_frames(self._h, N.ptr(feats), C.c_int(T), N.ptr(out)))
         return out
 
+    def debug_gmm_acc_rows(self, feats, want_ll=False):
+        """Enrolment statistics of `feats` [T, D] handed in as they are: the launches of gmm_acc_stats without its
+        front-end (test hook).  -> occ[C], F[C, D] (float64), and with want_ll the dump matrix ll[T, C] (float32)."""
+        feats = np.ascontiguousarray(feats, np.float32)
+        Cn, D = self._gmm_shape
+        if feats.ndim != 2 or feats.shape[1] != D:
+            raise ValueError("debug_gmm_acc_rows takes rows of %d features" % D)
+        T = feats.shape[0]
+        occ = np.empty(Cn, np.float64)
+        F = np.empty((Cn, D), np.float64)
+        ll = np.empty((T, Cn), np.float32) if want_ll else None
+        N.check(self._L.fb_debug_gmm_acc_rows(self._h, N.ptr(feats), C.c_int(T), N.ptr(ll) if want_ll else None,
+                                              N.ptr(occ), N.ptr(F)))
+        return (occ, F, ll) if want_ll else (occ, F)
+
     def stats(self):
         a, b, c, d = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
         N.check(self._L.fb_stats(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))

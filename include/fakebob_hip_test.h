@@ -209,6 +209,13 @@ int fb_gmm_delta_tiles_f6(fb_engine *e);
  * inputs the front-end never produces: outliers, huge magnitudes, frames far from every component. */
 int fb_debug_gmm_frames(fb_engine *e, const float *feats, int T, double *out);
 
+/* the launches of fb_gmm_acc_stats -- the single-model dump, k_gmm_lse, k_gmm_post_stats -- on T >= 1 rows of D features
+ * handed in as they are (no front-end); exactly one diagonal GMM loaded, FB_E_STATE otherwise.  occ[C], F[C][D] as
+ * fb_gmm_acc_stats returns them; with `ll` (nullable) the dump matrix, ll[t * C + k] = log-likelihood of row t under
+ * component k, without the padding columns of the dump's last 32-component tile.  Lets the tests reach model sizes, row
+ * counts and rows the front-end never produces, and compare the dump per component. */
+int fb_debug_gmm_acc_rows(fb_engine *e, const float *feats, int T, float *ll, double *occ, double *F);
+
 /* number of UBM components that received posterior mass in the last i-vector batch (only their
  * rows of Sigma^-1 M / U are streamed by the contraction kernels) */
 int fb_debug_iv_active(fb_engine *e, int *n_active);

@@ -1,7 +1,7 @@
 """k_gmm_fx2 range guard (gmm_ubm_kaldiHelper.py:202-221 evaluates the same log-likelihoods in float32 with no
 range limit): the two-term f16 split moves its operands by powers of two chosen from the MODEL at load time
 (x * 2^4, x^2 * 2^kx2 with kx2 up to 4), so features with |x| >= 64 would overflow f16 and turn the scores
-into NaN.  The kernel now rescales such frames per wave; these cases feed it features far outside the range
+into NaN.  The kernel rescales such frames, each by a power of two of its own; these cases feed it features far outside the range
 ordinary speech produces and compare with the oracle."""
 import numpy as np
 import pytest
@@ -69,7 +69,7 @@ def test_features_beyond_the_f16_range_score_like_the_oracle(oracle, C):
 
 def test_ordinary_features_are_unaffected_by_the_guard(engine, oracle, small_system):
     """sh = 0 for speech-like features: same scores as before, <= 1e-4 from the oracle (the guard only costs a
-    wave-wide maximum in the prologue)."""
+    maximum in the prologue)."""
     from fakebob_amd.models import synthetic_audio
     ubm, spk = small_system
     engine.load_gmm([ubm] + spk)
