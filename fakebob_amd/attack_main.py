@@ -25,6 +25,7 @@ from scipy.io.wavfile import read, write
 
 from . import parallel
 from .attack import FakeBob
+from .codec import NAMES as CODEC_NAMES
 
 bits_per_sample = 16
 fs = 16000
@@ -40,30 +41,31 @@ def load_spk_models(model_dir, spk_id_list, architecture):
 
 
 def make_model(architecture, task, model_list, pre_model_dir, threshold, group_id, dither=None, input_transform=None,
-               feature_compression=None, air_channel=None):
+               feature_compression=None, air_channel=None, codec=None):
     """attackMain.load_model (:38-85).  dither: the systems' keyword (Kaldi's --dither: a number, or "conf");
     input_transform: theirs too (the defended victim's input-transform chain, a spec such as "ms:7"); feature_compression:
     theirs as well (the feature-level defence, a spec such as "0.5" or "0.5:10"); air_channel: theirs too (the random room
-    in front of the victim, a spec such as "t60:200-600,drr:6")."""
+    in front of the victim, a spec such as "t60:200-600,drr:6"); codec: theirs as well (the telephone line in front of the
+    victim: "ulaw", "alaw" or "adpcm")."""
     from .systems import gmm_CSI, gmm_OSI, gmm_SV, iv_CSI, iv_OSI, iv_SV
     ubm = os.path.join(pre_model_dir, "final.dubm")
     if architecture == "iv":
         if task == "OSI":
             return iv_OSI(group_id, model_list, pre_model_dir=pre_model_dir, threshold=threshold, dither=dither,
-                          input_transform=input_transform, feature_compression=feature_compression, air_channel=air_channel)
+                          input_transform=input_transform, feature_compression=feature_compression, air_channel=air_channel, codec=codec)
         if task == "CSI":
             return iv_CSI(group_id, model_list, pre_model_dir=pre_model_dir, dither=dither,
-                          input_transform=input_transform, feature_compression=feature_compression, air_channel=air_channel)
+                          input_transform=input_transform, feature_compression=feature_compression, air_channel=air_channel, codec=codec)
         return iv_SV(group_id, model_list[0], pre_model_dir=pre_model_dir, threshold=threshold, dither=dither,
-                          input_transform=input_transform, feature_compression=feature_compression, air_channel=air_channel)
+                          input_transform=input_transform, feature_compression=feature_compression, air_channel=air_channel, codec=codec)
     if task == "OSI":
         return gmm_OSI(group_id, model_list, ubm, pre_model_dir=pre_model_dir, threshold=threshold, dither=dither,
-                          input_transform=input_transform, feature_compression=feature_compression, air_channel=air_channel)
+                          input_transform=input_transform, feature_compression=feature_compression, air_channel=air_channel, codec=codec)
     if task == "CSI":
         return gmm_CSI(group_id, model_list, pre_model_dir=pre_model_dir, dither=dither,
-                          input_transform=input_transform, feature_compression=feature_compression, air_channel=air_channel)
+                          input_transform=input_transform, feature_compression=feature_compression, air_channel=air_channel, codec=codec)
     return gmm_SV(group_id, model_list[0], ubm, pre_model_dir=pre_model_dir, threshold=threshold, dither=dither,
-                          input_transform=input_transform, feature_compression=feature_compression, air_channel=air_channel)
+                          input_transform=input_transform, feature_compression=feature_compression, air_channel=air_channel, codec=codec)
 
 
 def collect_voices(data_dir):
@@ -177,6 +179,10 @@ def main(argv=None, model_factory=None, bob_factory=None):
                     help="attack over the air: a random room impulse response in front of the victim, drawn afresh for "
                          "every query, e.g. 't60:200-600,drr:6,taps:2048,delay:32' (t60 in ms, required; "
                          "fakebob_amd/air_channel.py); randomised, so combine with --eot-size; default: none, or FB_AIR_CHANNEL")
+    ap.add_argument("--codec", dest="codec", default=None, choices=CODEC_NAMES + ("none",), metavar="NAME",
+                    help="attack through a telephone line: the encode / decode round trip of a line codec directly behind the "
+                         "input-transform chain, one of 'ulaw', 'alaw' (G.711), 'adpcm' (IMA ADPCM, 4 bit) "
+                         "(fakebob_amd/codec.py); default: none, or FB_CODEC")
     ap.add_argument("--feco", dest="feco", default=None, metavar="RATIO[:ITERS]",
                     help="attack a victim defended by feature compression: k-means over every utterance's voiced frames, "
                          "RATIO * T cluster centres scored in their place after ITERS (default 10) Lloyd iterations, e.g. "
@@ -227,7 +233,8 @@ def main(argv=None, model_factory=None, bob_factory=None):
     if model_factory is None:
         model_list = load_spk_models(args.model_dir, spk_id_list, args.architecture)
         kw = {k: v for k, v in (("dither", args.dither), ("input_transform", args.input_transform),
-                                       ("feature_compression", args.feco), ("air_channel", args.air_channel)) if v is not None}
+                                       ("feature_compression", args.feco), ("air_channel", args.air_channel),
+                                       ("codec", args.codec)) if v is not None}
         model_factory = functools.partial(make_model, **kw) if kw else make_model
     else:
         model_list = spk_id_list

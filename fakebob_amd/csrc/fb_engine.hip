@@ -119,6 +119,9 @@ struct fb_engine {
   FbAir air = {};               // the setting (the key fields are filled per launch: fb_air_key)
   DevBuf wav_air;               // the channel's output, in the replicated layout: what the chain -- or, without one, the MFCC -- reads
   DevBuf air_taps;              // k_air_taps' responses [rows][L] int16
+  // telephone-line codec (fb_set_codec; its contract is in fakebob_hip.h): FB_CODEC_NONE -- none
+  int codec = FB_CODEC_NONE;
+  DevBuf wav_codec;             // k_codec's output when nothing in front of it wrote a buffer of its own (the source is e->wav)
   // companion utterances (fb_set_companions; the "Composition" paragraph of fakebob_hip.h): comp_K1 == 0 -- none
   int comp_K1 = 0;              // companions set; with the call's own utterance K = comp_K1 + 1
   int64_t comp_N = 0;           // ... their length
@@ -1333,7 +1336,7 @@ static int launch_air_path(fb_engine *e, const int16_t *in, const int64_t *in_of
 // equal length -- the first B / r + 1 entries of e->wav_off describe them -- and replica j of utterance u goes to row
 // u * r + j of e->wav_tf, every time and with an empty chain too.  With call.K > 1 (fb_set_companions) the same launch
 // composes: replica c * eot + j is draw j over utterance c of the row (k_input_transform_cmp).
-static int transformed_wav(fb_engine *e, const FbScoreCall &call, const int64_t *off, int B, const int16_t **wav) {
+static int chained_wav(fb_engine *e, const FbScoreCall &call, const int64_t *off, int B, const int16_t **wav) {
   *wav = e->wav.as<int16_t>();
   const int r = call.replicas();
   if (e->tf.n == 0 && r == 1 && e->air.L == 0) return FB_OK;
@@ -1356,6 +1359,25 @@ static int transformed_wav(fb_engine *e, const FbScoreCall &call, const int64_t 
                                     e->wav_off.as<int64_t>(), fb_tf_rnd(call.pt, call.eot), call.K > 1 ? &cn : nullptr, call.stop));
   }
   *wav = e->wav_tf.as<int16_t>();
+  return FB_OK;
+}
+// The batch the front end reads: chained_wav's B rows, and -- with a codec set (fb_set_codec) -- their round trip through
+// it, one more launch: in place on wav_tf / wav_air; e->wav itself, the batch other code reads and returns, is coded into a
+// buffer of the codec's own.  The limits are the chain's.
+static int transformed_wav(fb_engine *e, const FbScoreCall &call, const int64_t *off, int B, const int16_t **wav) {
+  FBCHK(chained_wav(e, call, off, B, wav));
+  if (e->codec == FB_CODEC_NONE) return FB_OK;
+  if (B > 65535) return fb_fail(FB_E_LIMIT, "a codec takes batches of up to 65535 utterances");
+  int64_t n_max = 0;
+  for (int b = 0; b < B; ++b) n_max = std::max(n_max, off[b + 1] - off[b]);
+  if (n_max > 0x7fffffffLL) return fb_fail(FB_E_LIMIT, "utterance longer than 2^31 samples");
+  int16_t *out = const_cast<int16_t *>(*wav);
+  if (*wav == e->wav.as<int16_t>()) {
+    FBCHK(e->wav_codec.ensure(sizeof(int16_t) * (size_t)off[B]));
+    out = e->wav_codec.as<int16_t>();
+  }
+  fb_launch_codec(e->stream, e->codec, *wav, e->wav_off.as<int64_t>(), B, n_max, out, call.stop);
+  *wav = out;
   return FB_OK;
 }
 // MFCC of every frame of the batch prepared in e->wav: k_mfcc_f32 when the configuration asks for it, else k_mfcc_r16 / k_mfcc
@@ -3459,6 +3481,43 @@ extern "C" int fb_debug_air_convolve(fb_engine *e, const int16_t *wav, const int
   FBCHK(h2d(e, d_t.p, taps, sizeof(int16_t) * (size_t)B * (size_t)L));
   fb_launch_air_conv(e->stream, d_in.as<int16_t>(), d_off.as<int64_t>(), B, 1, 1, n_max, d_t.as<int16_t>(), L, d_out.as<int16_t>(),
                      d_off.as<int64_t>(), nullptr, nullptr);
+  HIPCHK(hipGetLastError());
+  FBCHK(d2h(e, out, d_out.p, bytes));
+  FBCHK(sync_stream(e));
+  return FB_OK;
+}
+
+// ---- telephone-line codec (the contract: include/fakebob_hip.h)
+extern "C" int fb_set_codec(fb_engine *e, int kind) {
+  if (!e) return fb_fail(FB_E_ARG, "null engine");
+  if (kind != FB_CODEC_NONE && kind != FB_CODEC_ULAW && kind != FB_CODEC_ALAW && kind != FB_CODEC_ADPCM)
+    return fb_fail(FB_E_ARG, "codec kind %d: 0 (none), 1 (mu-law), 2 (A-law) or 3 (IMA ADPCM)", kind);
+  e->codec = kind;
+  e->bench_it = -1;  // an attack fb_bench_nes left resident was scored through the previous setting
+  return FB_OK;
+}
+
+extern "C" int fb_debug_codec(fb_engine *e, int kind, const int16_t *wav, const int64_t *off, int B, int16_t *out) {
+  if (!e || !wav || !off || !out || B <= 0 || B > 65535) return fb_fail(FB_E_ARG, "bad argument");
+  if (kind != FB_CODEC_ULAW && kind != FB_CODEC_ALAW && kind != FB_CODEC_ADPCM) return fb_fail(FB_E_ARG, "codec kind %d: 1, 2 or 3", kind);
+  if (off[0] != 0) return fb_fail(FB_E_ARG, "off[0] must be 0");
+  int64_t n_max = 0;
+  for (int b = 0; b < B; ++b) {
+    const int64_t n = off[b + 1] - off[b];
+    if (n <= 0) return fb_fail(FB_E_ARG, "utterance %d is empty", b);
+    if (n > 0x7fffffffLL) return fb_fail(FB_E_LIMIT, "utterance %d longer than 2^31 samples", b);
+    n_max = std::max(n_max, n);
+  }
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  const size_t bytes = sizeof(int16_t) * (size_t)off[B];
+  DevBuf d_in, d_off, d_out;
+  FBCHK(d_in.ensure(bytes));
+  FBCHK(d_out.ensure(bytes));
+  FBCHK(d_off.ensure(sizeof(int64_t) * (size_t)(B + 1)));
+  FBCHK(h2d(e, d_in.p, wav, bytes));
+  FBCHK(h2d(e, d_off.p, off, sizeof(int64_t) * (size_t)(B + 1)));
+  fb_launch_codec(e->stream, kind, d_in.as<int16_t>(), d_off.as<int64_t>(), B, n_max, d_out.as<int16_t>(), nullptr);
   HIPCHK(hipGetLastError());
   FBCHK(d2h(e, out, d_out.p, bytes));
   FBCHK(sync_stream(e));

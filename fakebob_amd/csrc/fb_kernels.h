@@ -127,6 +127,12 @@ void fb_launch_air_conv(hipStream_t s, const int16_t *wav, const int64_t *in_off
                         const int16_t *taps, int L, int16_t *out, const int64_t *out_off, const FbTfComp *cn, const int *stop);
 size_t fb_air_conv_lds_bytes(int L);
 
+// ---- telephone-line codec (fb_set_codec; codec_kernel.hip) -------------------------------------------------------
+// out row R (at off[R], as in wav; R = 0 .. B - 1) = the round trip of row R of wav through codec `kind` (FB_CODEC_ULAW,
+// _ALAW or _ADPCM; the stage contract is in include/fakebob_hip.h); n_max = the longest row.  out == wav is allowed.
+// Honours `stop`.
+void fb_launch_codec(hipStream_t s, int kind, const int16_t *wav, const int64_t *off, int B, int64_t n_max, int16_t *out, const int *stop);
+
 // ---- feature compression (fb_set_feature_compression; feature_compress_kernel.hip) -------------------------------
 // What a launch carries of the stage contract (include/fakebob_hip.h): the setting, the Philox key (seed_lo ^ "FECO",
 // seed_hi ^ stream), counter word 3, the row of the batch's first utterance within the call and the replicas per utterance

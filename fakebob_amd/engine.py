@@ -48,6 +48,7 @@ class Engine(object):
         self._L.fb_default_frontend(C.byref(self.cfg))
         self.input_transform = []
         self.air_channel = None
+        self.codec = None
         self.eot = 1
         self.companions = None
         self.feature_compression = None
@@ -152,6 +153,29 @@ class Engine(object):
         out = np.empty_like(cat)
         N.check(self._L.fb_debug_air_convolve(self._h, N.ptr(cat), N.ptr(off), C.c_int(len(lst)), N.ptr(taps),
                                               C.c_int(taps.shape[1]), N.ptr(out)))
+        return [out[off[i]:off[i + 1]].copy() for i in range(len(lst))]
+
+    def set_codec(self, codec, validate=True):
+        """The telephone-line codec (fb_set_codec): "ulaw", "alaw", "adpcm", or None / "none" to clear it.  The engine then
+        sends every row its own front end reads -- scoring, enrolment statistics, every NES batch, the PSO swarm -- through
+        the codec's encode / decode round trip, directly behind the input-transform chain; not the batch of a foreign model
+        and not the returned audio.  An unknown name is refused here (ValueError); validate=False hands an integer to the
+        library as it is (it refuses what is outside the contract and keeps the previous setting)."""
+        from . import codec as K
+        kind = K.kind_of(codec) if validate else int(codec)
+        N.check(self._L.fb_set_codec(self._h, C.c_int(kind)))
+        self.codec = K.name_of(kind)
+
+    def debug_codec(self, kind, audio_list):
+        """k_codec on rows handed in as they are (fb_debug_codec): kind as set_codec names it (not None), int16 utterances of
+        any length >= 1; a list of int16 arrays.  The engine's own codec setting is neither read nor changed."""
+        from . import codec as K
+        lst = [np.ascontiguousarray(a, np.int16).reshape(-1) for a in audio_list]
+        off = np.zeros(len(lst) + 1, np.int64)
+        off[1:] = np.cumsum([a.size for a in lst])
+        cat = np.ascontiguousarray(np.concatenate(lst))
+        out = np.empty_like(cat)
+        N.check(self._L.fb_debug_codec(self._h, C.c_int(K.kind_of(kind)), N.ptr(cat), N.ptr(off), C.c_int(len(lst)), N.ptr(out)))
         return [out[off[i]:off[i + 1]].copy() for i in range(len(lst))]
 
     def set_eot(self, r):

@@ -113,6 +113,16 @@ def _apply_air_channel(engine, air_channel):
     engine.set_air_channel(air_channel)
 
 
+def _apply_codec(engine, codec):
+    """The telephone-line codec of a system under construction: the constructor keyword -- "ulaw", "alaw" or "adpcm";
+    "none" for no codec --, then FB_CODEC.  None of the two: the engine keeps its setting (none unless the caller set one)."""
+    if codec is None:
+        codec = os.environ.get("FB_CODEC")
+        if codec is None or codec == "":
+            return
+    engine.set_codec(codec)
+
+
 def eot_option(eot_size):
     """The expectation-over-transformation size asked for: the `eot_size` keyword (the system classes', FakeBob's), then
     FB_EOT_SIZE.  None: nobody asked, the engine keeps its value (1 unless the caller set one)."""
@@ -224,7 +234,7 @@ class _GmmSystem(object):
     PIPELINE = None  # class default of the two round trips (see REFERENCE_PIPELINE)
 
     def _setup(self, group_id, models, spk_ids, utt_ids, locations, z_means, z_stds, pre_model_dir, engine,
-               text_scores=None, compress_feats=None, mfcc_f32=None, dither=None, input_transform=None, eot_size=None, feature_compression=None, companions=None, air_channel=None):
+               text_scores=None, compress_feats=None, mfcc_f32=None, dither=None, input_transform=None, eot_size=None, feature_compression=None, companions=None, air_channel=None, codec=None):
         self.pre_model_dir = os.path.abspath(pre_model_dir)
         self.group_id = os.path.abspath(group_id)
         self.spk_ids = spk_ids
@@ -236,6 +246,7 @@ class _GmmSystem(object):
         _apply_frontend(self._engine, over, text_scores, compress_feats, mfcc_f32, self.PIPELINE)
         _apply_input_transform(self._engine, input_transform)
         _apply_air_channel(self._engine, air_channel)
+        _apply_codec(self._engine, codec)
         apply_eot(self._engine, eot_size)
         apply_feature_compression(self._engine, feature_compression)
         apply_companions(self._engine, companions)
@@ -264,14 +275,14 @@ class gmm_OSI(_GmmSystem):
 
     def __init__(self, group_id, model_list, ubm, pre_model_dir="pre-models", threshold=0.0, engine=None,
                  text_scores=None, compress_feats=None, mfcc_f32=None, dither=None,
-                 input_transform=None, eot_size=None, feature_compression=None, companions=None, air_channel=None):
+                 input_transform=None, eot_size=None, feature_compression=None, companions=None, air_channel=None, codec=None):
         self.threshold = threshold
         locs = [m[2] for m in model_list]
         self.model_list = [ubm] + locs  # UBM first (gmm_ubm_OSI.py:45)
         models = [load_gmm_any(x) for x in self.model_list]
         self._setup(group_id, models, [m[0] for m in model_list], [m[1] for m in model_list], locs, None, None,
                     pre_model_dir, engine, text_scores, compress_feats, mfcc_f32, dither,
-                    input_transform, eot_size, feature_compression, companions, air_channel)
+                    input_transform, eot_size, feature_compression, companions, air_channel, codec)
 
     def score(self, audios, fs=16000, bits_per_sample=16, debug=False, n_jobs=5):
         raw = self._raw(audios, bits_per_sample)
@@ -298,7 +309,7 @@ class gmm_CSI(_GmmSystem):
 
     def __init__(self, group_id, model_list, pre_model_dir="pre-models", engine=None, text_scores=None,
                  compress_feats=None, mfcc_f32=None, dither=None,
-                 input_transform=None, eot_size=None, feature_compression=None, companions=None, air_channel=None):
+                 input_transform=None, eot_size=None, feature_compression=None, companions=None, air_channel=None, codec=None):
         locs = [m[2] for m in model_list]
         self.model_list = locs
         self.z_norm_means = np.array([m[3] for m in model_list], np.float64)
@@ -306,7 +317,7 @@ class gmm_CSI(_GmmSystem):
         models = [load_gmm_any(x) for x in locs]
         self._setup(group_id, models, [m[0] for m in model_list], [m[1] for m in model_list], locs,
                     self.z_norm_means, self.z_norm_stds, pre_model_dir, engine, text_scores, compress_feats, mfcc_f32, dither,
-                    input_transform, eot_size, feature_compression, companions, air_channel)
+                    input_transform, eot_size, feature_compression, companions, air_channel, codec)
 
     def score(self, audios, fs=16000, bits_per_sample=16, debug=False, n_jobs=5):
         raw = self._raw(audios, bits_per_sample)
@@ -329,7 +340,7 @@ class gmm_SV(_GmmSystem):
 
     def __init__(self, spk_id, model, ubm, pre_model_dir="pre-models", threshold=0.0, engine=None,
                  text_scores=None, compress_feats=None, mfcc_f32=None, dither=None,
-                 input_transform=None, eot_size=None, feature_compression=None, companions=None, air_channel=None):
+                 input_transform=None, eot_size=None, feature_compression=None, companions=None, air_channel=None, codec=None):
         self.threshold = threshold
         self.utt_id = model[1]
         self.identity_location = model[2]
@@ -337,7 +348,7 @@ class gmm_SV(_GmmSystem):
         models = [load_gmm_any(x) for x in self.model_list]
         self._setup(spk_id, models, [model[0]], [model[1]], [model[2]], None, None, pre_model_dir, engine,
                     text_scores, compress_feats, mfcc_f32, dither,
-                    input_transform, eot_size, feature_compression, companions, air_channel)
+                    input_transform, eot_size, feature_compression, companions, air_channel, codec)
         self.spk_id = self.group_id
 
     def score(self, audios, fs=16000, bits_per_sample=16, debug=False, n_jobs=5):
@@ -360,7 +371,7 @@ class _IvSystem(object):
     PIPELINE = None
 
     def _setup(self, group_id, model_list, pre_model_dir, engine, system, text_scores=None, compress_feats=None, mfcc_f32=None, dither=None,
-               input_transform=None, eot_size=None, feature_compression=None, companions=None, air_channel=None):
+               input_transform=None, eot_size=None, feature_compression=None, companions=None, air_channel=None, codec=None):
         from .models import IvectorSystem
         self.pre_model_dir = os.path.abspath(pre_model_dir)
         self.group_id = os.path.abspath(group_id)
@@ -395,6 +406,7 @@ class _IvSystem(object):
             system = system.with_enrolled(enrolled, zm, zs)
         _apply_input_transform(self._engine, input_transform)
         _apply_air_channel(self._engine, air_channel)
+        _apply_codec(self._engine, codec)
         apply_eot(self._engine, eot_size)
         apply_feature_compression(self._engine, feature_compression)
         apply_companions(self._engine, companions)
@@ -421,10 +433,10 @@ class iv_OSI(_IvSystem):
 
     def __init__(self, group_id, model_list, pre_model_dir="pre-models", threshold=0.0, engine=None, system=None,
                  text_scores=None, compress_feats=None, mfcc_f32=None, dither=None,
-                 input_transform=None, eot_size=None, feature_compression=None, companions=None, air_channel=None):
+                 input_transform=None, eot_size=None, feature_compression=None, companions=None, air_channel=None, codec=None):
         self.threshold = threshold
         self._setup(group_id, model_list, pre_model_dir, engine, system, text_scores, compress_feats, mfcc_f32, dither,
-                    input_transform, eot_size, feature_compression, companions, air_channel)
+                    input_transform, eot_size, feature_compression, companions, air_channel, codec)
 
     def score(self, audio_list, fs=16000, bits_per_sample=16, n_jobs=10, debug=False):
         s = (self._llr(audio_list, bits_per_sample) - self.z_norm_means) / self.z_norm_stds   # :119
@@ -453,9 +465,9 @@ class iv_CSI(_IvSystem):
 
     def __init__(self, group_id, model_list, pre_model_dir="pre-models", engine=None, system=None, text_scores=None,
                  compress_feats=None, mfcc_f32=None, dither=None,
-                 input_transform=None, eot_size=None, feature_compression=None, companions=None, air_channel=None):
+                 input_transform=None, eot_size=None, feature_compression=None, companions=None, air_channel=None, codec=None):
         self._setup(group_id, model_list, pre_model_dir, engine, system, text_scores, compress_feats, mfcc_f32, dither,
-                    input_transform, eot_size, feature_compression, companions, air_channel)
+                    input_transform, eot_size, feature_compression, companions, air_channel, codec)
 
     def score(self, audio_list, fs=16000, bits_per_sample=16, n_jobs=10, debug=False):
         s = (self._llr(audio_list, bits_per_sample) - self.z_norm_means) / self.z_norm_stds
@@ -479,10 +491,10 @@ class iv_SV(_IvSystem):
 
     def __init__(self, spk_id, model, pre_model_dir="pre-models", threshold=0.0, engine=None, system=None,
                  text_scores=None, compress_feats=None, mfcc_f32=None, dither=None,
-                 input_transform=None, eot_size=None, feature_compression=None, companions=None, air_channel=None):
+                 input_transform=None, eot_size=None, feature_compression=None, companions=None, air_channel=None, codec=None):
         self.threshold = threshold
         self._setup(spk_id, [model], pre_model_dir, engine, system, text_scores, compress_feats, mfcc_f32, dither,
-                    input_transform, eot_size, feature_compression, companions, air_channel)
+                    input_transform, eot_size, feature_compression, companions, air_channel, codec)
         self.spk_id = self.group_id
         self.utt_id = model[1]
         self.identity_location = model[2]

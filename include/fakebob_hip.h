@@ -247,6 +247,48 @@ int fb_set_input_transform(fb_engine *e, const fb_tf_stage *stages, int n);
 typedef struct { int taps; int predelay; double amp; double rho_lo, rho_hi; } fb_air_params;
 int fb_set_air_channel(fb_engine *e, const fb_air_params *p);
 
+/* ---- telephone-line codec: G.711 and IMA ADPCM in front of the victim ---------------------------------------------------
+ * The commonest deployment of speaker verification hears the voice through a telephone line.  With a codec set every row
+ * the front end reads first goes through the encode / decode round trip of a line codec: G.711 mu-law or A-law (a
+ * memoryless companding) or IMA/DVI ADPCM, 4 bit (the 32 kbit/s family; its state runs along the whole row, so a
+ * perturbation's effect is not local in time).  All three are integer-exact: the contracts below agree bit for bit with
+ * Python's stdlib audioop (ulaw2lin(lin2ulaw), alaw2lin(lin2alaw), adpcm2lin(lin2adpcm) on 16-bit samples).
+ * Where it acts.  Directly behind the input-transform chain, wherever the chain acts: fb_score_*, fb_gmm_acc_stats (a
+ * defended system enrols through its line), every NES batch of fb_get_grad / fb_attack / fb_estimate_threshold,
+ * fb_attack_pso's swarm, the fb_debug_mfcc / _feats hooks.  The order is: composition, air channel, chain, codec, front end
+ * -- dither acts on frames cut from the coded samples -- for GMM and i-vector systems alike, on every row the front end
+ * reads: all K * eot replicas, each with a state of its own.  NOT applied to foreign models (_ext, _dev), to the returned
+ * audio or to the distance column.  An SNR noise stage still takes its power at the chain's input.  FB_E_NO_VOICED,
+ * FB_E_LIMIT (a batch of up to 65535 rows, as for a chain), the stop flag and fb_stats follow the chain's rules.
+ * Stage contract.  Each codec maps x[0 .. n) int16 of one row to y[0 .. n) int16: the output has the input's length.  All
+ * arithmetic is int32, >> is an arithmetic shift, every row is treated independently.
+ *   mu-law  v = x >> 2;  neg = v < 0;  m = min(neg ? -v : v, 8159) + 33;
+ *           seg = the number of entries of {0x3F, 0x7F, 0xFF, 0x1FF, 0x3FF, 0x7FF, 0xFFF, 0x1FFF} that m exceeds;
+ *           seg == 8 (m = 8192 only): seg = 7, q = 15;  otherwise q = (m >> (seg + 1)) & 15;
+ *           t = (((q << 3) + 0x84) << seg) - 0x84;  y = neg ? -t : t
+ *   A-law   v = x >> 3;  neg = v < 0;  m = neg ? -v - 1 : v;
+ *           seg = the number of entries of {0x1F, 0x3F, 0x7F, 0xFF, 0x1FF, 0x3FF, 0x7FF, 0xFFF} that m exceeds (0 .. 7);
+ *           q = seg < 2 ? (m >> 1) & 15 : (m >> seg) & 15;  t = q << 4;
+ *           u = seg == 0 ? t + 8 : seg == 1 ? t + 0x108 : (t + 0x108) << (seg - 1);  y = neg ? -u : u
+ *   ADPCM   the state (vp, ix) starts at (0, 0) for every row.  For i = 0 .. n - 1:
+ *           step = STEP[ix];  d = x[i] - vp;  s = d < 0;  d = |d|;  delta = 0;  vd = step >> 3;
+ *           if d >= step: delta = 4, d -= step, vd += step;
+ *           step >>= 1;  if d >= step: delta |= 2, d -= step, vd += step;
+ *           step >>= 1;  if d >= step: delta |= 1, vd += step;
+ *           vp = clip(s ? vp - vd : vp + vd, -32768, 32767);  ix = clip(ix + IDX[delta], 0, 88);  y[i] = vp
+ *           (the decoder's output is the encoder's predictor, so the round trip is this sequence).
+ *           IDX = {-1, -1, -1, -1, 2, 4, 6, 8};  STEP[89], the IMA table = 7 8 9 10 11 12 13 14 16 17 19 21 23 25 28 31 34
+ *           37 41 45 50 55 60 66 73 80 88 97 107 118 130 143 157 173 190 209 230 253 279 307 337 371 408 449 494 544 598 658
+ *           724 796 876 963 1060 1166 1282 1411 1552 1707 1878 2066 2272 2499 2749 3024 3327 3660 4026 4428 4871 5358 5894
+ *           6484 7132 7845 8630 9493 10442 11487 12635 13899 15289 16818 18500 20350 22385 24623 27086 29794 32767
+ * Deviation.  The codec runs at the utterance's own sampling rate, on every sample: there is no rate change here
+ * (FB_TF_DECIMATE keeps zeros in place, and the codec is last).  A narrow-band line is emulated by band-limiting with FIR
+ * stages in the chain first.
+ * kind: one of the values below; anything else returns FB_E_ARG and keeps the previous setting.  FB_CODEC_NONE clears the
+ * codec (the default: no launch is added, no code path differs). */
+enum { FB_CODEC_NONE = 0, FB_CODEC_ULAW = 1, FB_CODEC_ALAW = 2, FB_CODEC_ADPCM = 3 };
+int fb_set_codec(fb_engine *e, int kind);
+
 /* ---- expectation over transformation: attacking a randomised victim ---------------------------------------------------
  * With a noise stage in the chain or dither > 0 the victim answers every query with a fresh draw.  r > 1 makes fb_get_grad
  * and fb_attack score every row of the NES batch under r independent draws and average BEFORE the gradient estimate and the

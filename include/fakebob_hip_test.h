@@ -77,6 +77,16 @@ int fb_debug_air_taps(fb_engine *e, uint64_t seed, uint32_t stream, uint32_t epo
                       float *z, uint32_t *w);
 int fb_debug_air_convolve(fb_engine *e, const int16_t *wav, const int64_t *off, int B, const int16_t *taps, int L, int16_t *out);
 
+/* Telephone-line codec (fakebob_hip.h: fb_set_codec and its stage contract).  The hooks above that return int16 rows
+ * (fb_debug_input_transform*, fb_debug_compose, fb_debug_air_*) ignore the codec; fb_debug_mfcc / _feats apply it.
+ * fb_debug_codec: k_codec on rows handed in as they are -- B rows of any length >= 1 (off[B + 1], off[0] = 0), B up to
+ * 65535; out has wav's layout.  kind (FB_CODEC_ULAW, _ALAW or _ADPCM) comes from the argument: the engine's setting is
+ * neither read nor changed.
+ * FB_CODEC_TILE: the samples of a row the ADPCM kernel holds in LDS at a time (row lengths around its multiples are the
+ * kernel's edges). */
+#define FB_CODEC_TILE 512
+int fb_debug_codec(fb_engine *e, int kind, const int16_t *wav, const int64_t *off, int B, int16_t *out);
+
 /* Feature compression (fakebob_hip.h: fb_set_feature_compression and its stage contract).
  * fb_debug_feature_compress: the kernel the scoring paths launch, on feature rows handed in as they are (no front end, no
  * model; D = the front end's feature dimension): feats holds the rows of B * r utterance rows one after the other,
