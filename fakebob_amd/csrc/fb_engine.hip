@@ -189,6 +189,7 @@ struct fb_engine {
   bool have_route = false;  // ... once a batch has reached the MFCC launch
   FbGmmShape shape_gmm = {};    // fb_debug_launch_shape: the geometry of the last batch's GMM launch (the launchers fill it in)
   FbMfccShape shape_mfcc = {};  // ... and of its k_mfcc_f32 launch
+  int shape_upd_threads = 0;    // ... and the threads per workgroup of the update launch that followed it (0: none did)
   bool have_shape = false;      // ... once a batch has chosen its launch shape
   int cached_B = -1;
   int64_t cached_N = -1;
@@ -1266,6 +1267,26 @@ static void choose_launch_shape(fb_engine *e) {
   e->fe.mfcc_cus = cv ? atoi(cv) : (e->fuse_opt == 0 ? 128 : 0);
   e->shape_gmm = FbGmmShape{};
   e->shape_mfcc = FbMfccShape{};
+  e->shape_upd_threads = 0;
+  e->have_shape = true;
+}
+// ... and the third part of that shape: the threads of a k_update_perturb(_x) workgroup.  On the shared GPU 256, one wave
+// per SIMD: a k_gmm_fx2w workgroup leaves a SIMD 88 of its 512 registers, the kernel takes 56 per wave, so its workgroups run
+// beside the other attacks' GMM launches instead of queueing for the compute units those leave free (nes_kernels.hip).  A
+// lone attack keeps 512: nothing else is resident, and more waves draw the next batch sooner.  FB_UP_THREADS=256 | 512
+// forces either.  Unlike the two above this one is an attack's, not a batch's: loop_knobs calls it once, at the start of the
+// public call, and the loop carries the answer.
+static int choose_update_threads(const fb_engine *e) {
+  if (const char *uv = getenv("FB_UP_THREADS")) {
+    const int t = atoi(uv);
+    if (t == 256 || t == 512) return t;
+  }
+  return e->fuse_opt == 0 ? 256 : 512;
+}
+// the update launch of the batch as it went out (fb_debug_launch_shape); a foreign model's attack scores no batch of the
+// engine's own, so its record starts here
+static void record_update_threads(fb_engine *e, int threads) {
+  e->shape_upd_threads = threads;
   e->have_shape = true;
 }
 // The batch the MFCC reads: e->wav, or -- with an input-transform chain set -- its transform in e->wav_tf, one more launch.
@@ -2110,9 +2131,9 @@ extern "C" int fb_debug_launch_shape(fb_engine *e, int *info) {
   if (!e->have_shape) return fb_fail(FB_E_STATE, "no batch has launched yet");
   const FbGmmShape &g = e->shape_gmm;
   const FbMfccShape &m = e->shape_mfcc;
-  const int v[12] = {g.kernel, g.n_chunks, g.sub, g.grid_chunks, g.xcd_map, g.passes, g.strips, g.tiles_min, g.tiles_max,
-                     m.cus, m.rounds, m.blocks};
-  for (int i = 0; i < 12; ++i) info[i] = v[i];
+  const int v[13] = {g.kernel, g.n_chunks, g.sub, g.grid_chunks, g.xcd_map, g.passes, g.strips, g.tiles_min, g.tiles_max,
+                     m.cus, m.rounds, m.blocks, e->shape_upd_threads};
+  for (int i = 0; i < 13; ++i) info[i] = v[i];
   return FB_OK;
 }
 
@@ -2285,9 +2306,11 @@ struct FbLoopKnobs {
   bool upd_in_fin = false;  // ... riding in the finalising launch (FB_FUSE_UPD=0: two launches)
   bool fin_ticket = false;  // FB_FIN_TICKET=1: the finalising launch's roles by an arrival ticket
   bool fin_xch = false;     // its exchange slots (FB_FIN_COUNTER=1: the arrival counter instead)
+  int upd_threads = 512;    // threads of a k_update_perturb(_x) workgroup (choose_update_threads)
 };
 static FbLoopKnobs loop_knobs(const fb_engine *e, const FbScorer &sc) {
   FbLoopKnobs k;
+  k.upd_threads = choose_update_threads(e);
   if (sc.kind == FB_SCORER_DEV) {
     k.look = sc.m->look_every > 0 ? sc.m->look_every : 4;
     k.fuse_upd = true;
@@ -2714,12 +2737,14 @@ static int attack_loop(fb_engine *e, const fb_nes_params *p, int64_t N, const Fb
           if (updated) {
             e->pre_ndp = (int)((N + 255) / 256);
             e->pre_iter = (long long)it + 1;
+            record_update_threads(e, 512);  // (the update workgroups of k_gmm_finalize_loss_update)
           } else if (upd_next) {
             e->pre_ndp = fb_launch_update_perturb(e->stream, e->loss.as<double>(), N, half, p->sigma, e->zbuf.as<float>(),
                                                   p->momentum, one_minus_m, p->epsilon, e->audio.as<double>(),
                                                   e->grad_m.as<double>(), e->adver.as<double>(), ctl, p->seed,
                                                   (uint32_t)(it + 1), p->stream, e->wav.as<int16_t>(),
-                                                  e->dist_part.as<double>(), nes_bits(p));
+                                                  e->dist_part.as<double>(), nes_bits(p), kn.upd_threads);
+            record_update_threads(e, kn.upd_threads);
             e->nes_route[FB_NES_ROUTE_K_UPDATE_PERTURB] += 1;
             e->pre_iter = (long long)it + 1;
             updated = true;
@@ -2741,7 +2766,8 @@ static int attack_loop(fb_engine *e, const fb_nes_params *p, int64_t N, const Fb
                                              e->zbuf.as<float>(), p->momentum, one_minus_m, p->epsilon,
                                              e->audio.as<double>(), e->grad_m.as<double>(), e->adver.as<double>(), ctl,
                                              p->seed, (uint32_t)(it + 1), p->stream, sc.m->x, xv,
-                                             e->dist_part.as<double>());
+                                             e->dist_part.as<double>(), kn.upd_threads);
+            record_update_threads(e, kn.upd_threads);
             e->nes_route[FB_NES_ROUTE_K_UPDATE_PERTURB] += 1;
             have_batch = updated = true;
           }

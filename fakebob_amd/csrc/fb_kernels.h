@@ -238,6 +238,7 @@ void fb_launch_loss_eot(hipStream_t s, const double *raw, const int *tv, int B, 
                         double *trace, int it);
 // k_grad_update (iteration `next_iter - 1`) + k_perturb (iteration next_iter) in one launch; device-controlled attacks
 // with Philox noise and half <= FB_FUSE_MAX_HALF only.  Returns the number of distance partials written.
+// threads: 256 or 512 per workgroup of 256 samples (the same bits either way; nes_kernels.hip says which when)
 #define FB_FUSE_MAX_HALF 40
 #define FB_FUSE_MAX_UPD_WG 192  // update workgroups k_gmm_finalize_loss_update may carry (N <= 49 152 samples; longer audio: k_update_perturb)
 // the arguments of k_update_perturb, for the launch that carries it behind the GMM finalisation + loss (below)
@@ -261,13 +262,13 @@ struct FbUpdArgs {
 int fb_launch_update_perturb(hipStream_t s, const double *loss, int64_t N, int half, double sigma, float *zbuf,
                              double momentum, double one_minus_m, double epsilon, const double *audio, double *grad_m,
                              double *adver, const FbCtlDev *ctl, uint64_t seed, uint32_t next_iter, uint32_t stream,
-                             int16_t *q, double *dist_part, int bits = 16);
+                             int16_t *q, double *dist_part, int bits = 16, int threads = 512);
 // ... and with the batch of iteration next_iter written into a device-resident foreign model's x[B][N] (x_dtype FB_DT_*,
 // x_vec: x is 16-byte aligned) instead of the int16 batch
 int fb_launch_update_perturb_x(hipStream_t s, int x_dtype, const double *loss, int64_t N, int half, double sigma,
                                float *zbuf, double momentum, double one_minus_m, double epsilon, const double *audio,
                                double *grad_m, double *adver, const FbCtlDev *ctl, uint64_t seed, uint32_t next_iter,
-                               uint32_t stream, void *x, int x_vec, double *dist_part);
+                               uint32_t stream, void *x, int x_vec, double *dist_part, int threads = 512);
 // grad estimate (numpy-pairwise order) + optional momentum/sign/clip update.
 // do_update: 0 = only grad_out; 1 = momentum+update with lr.
 void fb_launch_grad_update(hipStream_t s, const double *loss, int64_t N, int half, double sigma,

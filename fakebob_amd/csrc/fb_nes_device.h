@@ -137,15 +137,24 @@ __device__ __forceinline__ double fb_loss_row(const TR *__restrict__ raw, const 
     // through run-time loops -- a dozen dependent LDS round trips in the one workgroup everybody waits for); the same
     // operations on the same values in the same order
     double scr[FB_RAW_LOCAL];
+    // scr[target] and scr[true_label] (scr[0] for an index outside 1 .. 7) are picked up as the values are formed: a chain
+    // of selects over scr[] read back afterwards came out of the compiler as ONE load at a selected address, which kept the
+    // array in scratch memory (80 bytes per lane, the only scratch of k_loss)
+    double s_tgt = 0.0, s_lbl = 0.0;
+    auto keep = [&](const int m, const double v) {
+      scr[m] = v;
+      s_tgt = (m == 0 || m == target) ? v : s_tgt;
+      s_lbl = (m == 0 || m == true_label) ? v : s_lbl;
+    };
     if (task == FB_TASK_CSI || znorm_all) {
       double zm[FB_RAW_LOCAL], zs[FB_RAW_LOCAL];
 #pragma unroll
       for (int m = 0; m < FB_RAW_LOCAL; ++m) { zm[m] = z_mean[m < M ? m : M - 1]; zs[m] = z_std[m < M ? m : M - 1]; }
 #pragma unroll
-      for (int m = 0; m < FB_RAW_LOCAL; ++m) scr[m] = __ddiv_rn(__dsub_rn(rv[m], zm[m]), zs[m]);
+      for (int m = 0; m < FB_RAW_LOCAL; ++m) keep(m, __ddiv_rn(__dsub_rn(rv[m], zm[m]), zs[m]));
     } else {
 #pragma unroll
-      for (int m = 0; m < FB_RAW_LOCAL; ++m) scr[m] = __dsub_rn(rv[m + 1 < FB_RAW_LOCAL ? m + 1 : FB_RAW_LOCAL - 1], rv[0]);
+      for (int m = 0; m < FB_RAW_LOCAL; ++m) keep(m, __dsub_rn(rv[m + 1 < FB_RAW_LOCAL ? m + 1 : FB_RAW_LOCAL - 1], rv[0]));
     }
 #pragma unroll
     for (int m = 0; m < FB_RAW_LOCAL; ++m)
@@ -153,12 +162,6 @@ __device__ __forceinline__ double fb_loss_row(const TR *__restrict__ raw, const 
         sc[m] = scr[m];
         if (gsc) gsc[m] = scr[m];
       }
-    auto pick = [&](int i) -> double {
-      double v = scr[0];
-#pragma unroll
-      for (int q = 1; q < FB_RAW_LOCAL; ++q) v = i == q ? scr[q] : v;
-      return v;
-    };
     auto max_but = [&](int skip) -> double {   // max over m < S, m != skip, in index order
       double om = -INFINITY;
 #pragma unroll
@@ -173,11 +176,11 @@ __device__ __forceinline__ double fb_loss_row(const TR *__restrict__ raw, const 
     } else if (task == FB_TASK_OSI) {
       const double om = max_but(target);
       const double mx = om > threshold ? om : threshold;
-      l = __dsub_rn(__dadd_rn(mx, adver_thresh), pick(target));  // :262
+      l = __dsub_rn(__dadd_rn(mx, adver_thresh), s_tgt);  // :262
     } else if (attack_type == FB_TARGETED) {
-      l = __dsub_rn(__dadd_rn(max_but(target), adver_thresh), pick(target));  // :281
+      l = __dsub_rn(__dadd_rn(max_but(target), adver_thresh), s_tgt);  // :281
     } else {
-      l = __dsub_rn(__dadd_rn(pick(true_label), adver_thresh), max_but(true_label));  // :291
+      l = __dsub_rn(__dadd_rn(s_lbl, adver_thresh), max_but(true_label));  // :291
     }
   } else {
     if (task == FB_TASK_CSI || znorm_all) {
@@ -468,7 +471,10 @@ __device__ __forceinline__ void fb_update_perturb_body(const double *__restrict_
   const int spd = 2 * half;
   double *s_a = s_loss + spd;
   float *s_z = reinterpret_cast<float *>(s_a + 256);
-  constexpr int MAXI = 5;   // (sample quad, pair) items per thread: 64 half / 512, half <= FB_FUSE_MAX_HALF
+  // (sample quad, pair) items per thread that a WAIT launch draws ahead of the wait: 64 half / 512, half <= FB_FUSE_MAX_HALF.
+  // Only k_gmm_finalize_loss_update waits, always with 512 threads; k_update_perturb(_x) with 256 or 512 threads draws in
+  // phase 2, one item per trip of its blockDim.x-strided loop, and neither uses zn nor takes the split sum below.
+  constexpr int MAXI = 5;
   float zn[WAIT ? MAXI : 1][4];
   double lr;
   if constexpr (!WAIT) {
@@ -476,7 +482,7 @@ __device__ __forceinline__ void fb_update_perturb_body(const double *__restrict_
     lr = ctl->lr;
     for (int i = threadIdx.x; i < spd; i += blockDim.x) s_loss[i] = loss[1 + i];
   }
-  const int64_t n = (int64_t)bidx * 256 + threadIdx.x;  // phase 1: threads 0 .. 255
+  const int64_t n = (int64_t)bidx * 256 + threadIdx.x;  // phase 1: threads 0 .. 255 (all of a 256-thread workgroup)
   {  // this iteration's normals of the block's 256 samples: sixteen loads in flight per trip (a plain copy loop waits for
      // every load before it issues the next: 12 dependent round trips at samples_per_draw = 50 -- half of k_update_perturb)
     const int total = half * 256;

@@ -464,15 +464,21 @@ __global__ __launch_bounds__(256) void k_grad_update(const double *__restrict__ 
 // Philox normals for iteration iter + 1, overwrites its zbuf entries (read in phase 1 by this block only) and writes
 // the two int16 columns; thread = sample writes the clean column and the distance partial.  Same arithmetic as the
 // two kernels, so trajectories are bit-identical.  Device-controlled attacks only (lr / stop from the control block).
-// Workgroup = 256 samples (the unit of the distance partials and of the LDS-staged normals) worked on by FB_UP_THREADS
-// threads: the update (phase 1) is one thread per sample, the next iteration's columns (phase 2: 64 sample quads x
-// spd/2 pairs of Philox + Box-Muller items) are dealt over all of them -- with 256 threads the 188 workgroups of a 3 s
-// utterance put fewer waves on the chip than it has SIMDs.  Measured (same box, 1 attack / 3 in flight): 256 threads
-// 19.1 us, 4 930 / 7 900 it/s; 512: 5 040 / 7 930; 1024: 13.1 us, 5 110 / 7 300 (the wide workgroups get in the way of
-// the other attacks' kernels).
-#define FB_UP_THREADS 512
-template <bool SMALL>
-__global__ __launch_bounds__(FB_UP_THREADS) void k_update_perturb(const double *__restrict__ loss, int64_t N, int half,
+// Workgroup = 256 samples (the unit of the distance partials and of the LDS-staged normals) worked on by THREADS = 256 or
+// 512 threads: the update (phase 1) is one thread per sample, the next iteration's columns (phase 2: 64 sample quads x
+// spd/2 pairs of Philox + Box-Muller items) are dealt over all of them, as the staging loads are -- the body takes the
+// count from blockDim.x, so both shapes do the same arithmetic in the same order on every sample and write the same bits.
+// 512: with 256 threads the 188 workgroups of a 3 s utterance put fewer waves on the chip than it has SIMDs; what a
+// lone attack launches.  Measured in round 5, when one k_gmm_fx2w launch covered every compute unit (same box, 1 attack /
+// 3 in flight): 256 threads 19.1 us, 4 930 / 7 900 it/s; 512: 5 040 / 7 930; 1024: 13.1 us, 5 110 / 7 300 (the wide
+// workgroups get in the way of the other attacks' kernels).
+// 256: the shape of a GPU shared by three or more attacks (fb_set_fused_chain(e, 0); fb_engine.hip, choose_update_threads).
+// Beside a resident k_gmm_fx2w workgroup (424 of a SIMD's 512 registers, 101 KB of LDS) a SIMD has 88 registers left: one
+// wave of this kernel (56) fits, the two that 512 threads put on every SIMD (112) do not, and with two half-chip GMM
+// launches of the other attacks running the 188 workgroups queued for the 16 compute units left over.  The 256-thread
+// instantiation must stay at or below 88 registers without scratch (tests/test_kernel_footprints.py).
+template <bool SMALL, int THREADS>
+__global__ __launch_bounds__(THREADS) void k_update_perturb(const double *__restrict__ loss, int64_t N, int half,
                                                         double sigma, float *__restrict__ zbuf, double momentum,
                                                         double one_minus_m, double epsilon,
                                                         const double *__restrict__ audio, double *__restrict__ grad_m,
@@ -480,6 +486,7 @@ __global__ __launch_bounds__(FB_UP_THREADS) void k_update_perturb(const double *
                                                         uint64_t seed, uint32_t next_iter, uint32_t stream,
                                                         int16_t *__restrict__ q, double *__restrict__ dist_part,
                                                         double qscale) {
+  static_assert(THREADS == 256 || THREADS == 512, "a workgroup's 256 samples, one or two threads each");
   extern __shared__ double s_loss[];  // loss[1..spd], the block's updated samples [256], the block's normals [half][256]
   fb_update_perturb_body<SMALL, false>(loss, N, half, sigma, zbuf, momentum, one_minus_m, epsilon, audio, grad_m, adver, ctl, seed,
                                        next_iter, stream, FbOutI16{q, qscale}, dist_part, (int)blockIdx.x, 0, s_loss);
@@ -488,30 +495,36 @@ __global__ __launch_bounds__(FB_UP_THREADS) void k_update_perturb(const double *
 int fb_launch_update_perturb(hipStream_t s, const double *loss, int64_t N, int half, double sigma, float *zbuf,
                              double momentum, double one_minus_m, double epsilon, const double *audio, double *grad_m,
                              double *adver, const FbCtlDev *ctl, uint64_t seed, uint32_t next_iter, uint32_t stream,
-                             int16_t *q, double *dist_part, int bits) {
+                             int16_t *q, double *dist_part, int bits, int threads) {
   const int blocks = (int)((N + 255) / 256);
   const double qscale = ldexp(1.0, bits - 1);
   const size_t shm = sizeof(double) * (size_t)(2 * half + 256) + sizeof(float) * 256 * (size_t)(half > 0 ? half : 1);
-  const int nthr = FB_UP_THREADS;
-  if (2 * half <= 128)
-    hipLaunchKernelGGL(k_update_perturb<true>, dim3(blocks), dim3(nthr), shm, s, loss, N, half, sigma, zbuf, momentum,
-                       one_minus_m, epsilon, audio, grad_m, adver, ctl, seed, next_iter, stream, q, dist_part, qscale);
-  else
-    hipLaunchKernelGGL(k_update_perturb<false>, dim3(blocks), dim3(FB_UP_THREADS), shm, s, loss, N, half, sigma, zbuf, momentum,
-                       one_minus_m, epsilon, audio, grad_m, adver, ctl, seed, next_iter, stream, q, dist_part, qscale);
+  const bool small = 2 * half <= 128;
+  auto go = [&](auto kernel, int nthr) {
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(nthr), shm, s, loss, N, half, sigma, zbuf, momentum, one_minus_m, epsilon,
+                       audio, grad_m, adver, ctl, seed, next_iter, stream, q, dist_part, qscale);
+  };
+  if (threads == 256) {
+    if (small) go(k_update_perturb<true, 256>, 256);
+    else go(k_update_perturb<false, 256>, 256);
+  } else {
+    if (small) go(k_update_perturb<true, 512>, 512);
+    else go(k_update_perturb<false, 512>, 512);
+  }
   return blocks;
 }
 
 // ... the same launch for a device-resident foreign model (fb_attack_dev): the batch of iteration next_iter goes into the
 // caller's x[B][N] as T instead of the int16 batch (FbOutX<T>)
-template <bool SMALL, typename T>
-__global__ __launch_bounds__(FB_UP_THREADS) void k_update_perturb_x(const double *__restrict__ loss, int64_t N, int half,
+template <bool SMALL, typename T, int THREADS>
+__global__ __launch_bounds__(THREADS) void k_update_perturb_x(const double *__restrict__ loss, int64_t N, int half,
                                                           double sigma, float *__restrict__ zbuf, double momentum,
                                                           double one_minus_m, double epsilon,
                                                           const double *__restrict__ audio, double *__restrict__ grad_m,
                                                           double *__restrict__ adver, const FbCtlDev *__restrict__ ctl,
                                                           uint64_t seed, uint32_t next_iter, uint32_t stream,
                                                           T *__restrict__ x, int x_vec, double *__restrict__ dist_part) {
+  static_assert(THREADS == 256 || THREADS == 512, "a workgroup's 256 samples, one or two threads each");
   extern __shared__ double s_loss[];
   fb_update_perturb_body<SMALL, false>(loss, N, half, sigma, zbuf, momentum, one_minus_m, epsilon, audio, grad_m, adver, ctl, seed,
                                        next_iter, stream, FbOutX<T>{x}, dist_part, (int)blockIdx.x, 0, s_loss, x_vec != 0);
@@ -520,26 +533,32 @@ template <typename T>
 static void launch_update_perturb_x(hipStream_t s, const double *loss, int64_t N, int half, double sigma, float *zbuf,
                                     double momentum, double one_minus_m, double epsilon, const double *audio,
                                     double *grad_m, double *adver, const FbCtlDev *ctl, uint64_t seed, uint32_t next_iter,
-                                    uint32_t stream, T *x, int x_vec, double *dist_part) {
+                                    uint32_t stream, T *x, int x_vec, double *dist_part, int threads) {
   const int blocks = (int)((N + 255) / 256);
   const size_t shm = sizeof(double) * (size_t)(2 * half + 256) + sizeof(float) * 256 * (size_t)(half > 0 ? half : 1);
-  if (2 * half <= 128)
-    hipLaunchKernelGGL((k_update_perturb_x<true, T>), dim3(blocks), dim3(FB_UP_THREADS), shm, s, loss, N, half, sigma, zbuf,
-                       momentum, one_minus_m, epsilon, audio, grad_m, adver, ctl, seed, next_iter, stream, x, x_vec, dist_part);
-  else
-    hipLaunchKernelGGL((k_update_perturb_x<false, T>), dim3(blocks), dim3(FB_UP_THREADS), shm, s, loss, N, half, sigma, zbuf,
-                       momentum, one_minus_m, epsilon, audio, grad_m, adver, ctl, seed, next_iter, stream, x, x_vec, dist_part);
+  const bool small = 2 * half <= 128;
+  auto go = [&](auto kernel, int nthr) {
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(nthr), shm, s, loss, N, half, sigma, zbuf, momentum, one_minus_m, epsilon,
+                       audio, grad_m, adver, ctl, seed, next_iter, stream, x, x_vec, dist_part);
+  };
+  if (threads == 256) {
+    if (small) go(k_update_perturb_x<true, T, 256>, 256);
+    else go(k_update_perturb_x<false, T, 256>, 256);
+  } else {
+    if (small) go(k_update_perturb_x<true, T, 512>, 512);
+    else go(k_update_perturb_x<false, T, 512>, 512);
+  }
 }
 int fb_launch_update_perturb_x(hipStream_t s, int x_dtype, const double *loss, int64_t N, int half, double sigma,
                                float *zbuf, double momentum, double one_minus_m, double epsilon, const double *audio,
                                double *grad_m, double *adver, const FbCtlDev *ctl, uint64_t seed, uint32_t next_iter,
-                               uint32_t stream, void *x, int x_vec, double *dist_part) {
+                               uint32_t stream, void *x, int x_vec, double *dist_part, int threads) {
   if (x_dtype == FB_DT_F32)
     launch_update_perturb_x(s, loss, N, half, sigma, zbuf, momentum, one_minus_m, epsilon, audio, grad_m, adver, ctl, seed,
-                            next_iter, stream, static_cast<float *>(x), x_vec, dist_part);
+                            next_iter, stream, static_cast<float *>(x), x_vec, dist_part, threads);
   else
     launch_update_perturb_x(s, loss, N, half, sigma, zbuf, momentum, one_minus_m, epsilon, audio, grad_m, adver, ctl, seed,
-                            next_iter, stream, static_cast<double *>(x), x_vec, dist_part);
+                            next_iter, stream, static_cast<double *>(x), x_vec, dist_part, threads);
   return (int)((N + 255) / 256);
 }
 

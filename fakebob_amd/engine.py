@@ -425,11 +425,13 @@ class Engine(object):
     def debug_launch_shape(self):
         """The launch geometry of the last batch as the launchers chose it (fb_debug_launch_shape): a dict of gmm (the
         kernel, None when none ran), n_chunks, sub (chunks per k_gmm_fx2w workgroup), grid_chunks, xcd_map (0: the plain
-        2-D grid), passes, strips, tiles_min / tiles_max (component tiles of a chunk), and k_mfcc_f32's cus, rounds and
-        blocks (0 when another MFCC kernel ran)."""
-        info = (C.c_int * 12)()
+        2-D grid), passes, strips, tiles_min / tiles_max (component tiles of a chunk), k_mfcc_f32's cus, rounds and
+        blocks (0 when another MFCC kernel ran), and up_threads: the threads per workgroup of the update launch that
+        followed the batch inside an attack (0: none did)."""
+        info = (C.c_int * 13)()
         N.check(self._L.fb_debug_launch_shape(self._h, info))
-        keys = ("n_chunks", "sub", "grid_chunks", "xcd_map", "passes", "strips", "tiles_min", "tiles_max", "cus", "rounds", "blocks")
+        keys = ("n_chunks", "sub", "grid_chunks", "xcd_map", "passes", "strips", "tiles_min", "tiles_max", "cus", "rounds", "blocks",
+                "up_threads")
         d = dict(gmm=self._SHAPE_GMM[info[0]])
         d.update((k, int(v)) for k, v in zip(keys, info[1:]))
         return d

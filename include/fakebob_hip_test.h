@@ -150,11 +150,13 @@ int fb_debug_frontend_route(fb_engine *e, int *info);
 #define FB_ROUTE_CM_GLOBAL 4         /* k_feat_compress, columns read from global memory (longer than LDS holds) */
 
 /* The launch geometry of the last batch (fb_score_*, fb_get_grad, an NES iteration, fb_debug_gmm_frames, fb_debug_mfcc /
- * _feats, enrolment statistics), as the launchers chose it: info[12] = {the GMM kernel (FB_SHAPE_GMM_*: the scoring kernel,
+ * _feats, enrolment statistics), as the launchers chose it: info[13] = {the GMM kernel (FB_SHAPE_GMM_*: the scoring kernel,
  * or the per-component dump of an i-vector batch or of enrolment statistics), component chunks, chunks one k_gmm_fx2w
  * workgroup scores one after the other (1 when fxw_sub does not divide the chunk count), the grid's chunk dimension, the XCD
  * mapping (the chunk count it serves, 0: the plain 2-D grid), launches (k_gmm_fx2w's passes), frame strips, fewest and most
- * component tiles of any chunk, then k_mfcc_f32's compute units, rounds and workgroups}.  A stage that launched nothing in
+ * component tiles of any chunk, then k_mfcc_f32's compute units, rounds and workgroups, then the threads per workgroup of
+ * the update launch that followed the batch inside an attack: 256 or 512 for k_update_perturb / k_update_perturb_x, 512
+ * for the update workgroups of k_gmm_finalize_loss_update}.  A stage that launched nothing in
  * that batch reports zeros.  Recorded on the host when the kernels are enqueued; read only.  FB_E_STATE before the first
  * batch. */
 int fb_debug_launch_shape(fb_engine *e, int *info);
