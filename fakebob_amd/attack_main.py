@@ -195,9 +195,14 @@ def main(argv=None, model_factory=None, bob_factory=None):
                     help="universal perturbation: the next N utterances of the same speaker in the data directory ride along "
                          "with every attacked one (1 .. 31, times --eot-size at most 32); all are cropped to the shortest, "
                          "which is printed; default: 0")
-    ap.add_argument("--attack", default="nes", choices=["nes", "pso"],
-                    help="the search: FAKEBOB's NES gradient estimate (default) or SirenAttack's particle swarm "
-                         "(fakebob_amd/pso.py; -epsilon, -max_iter, -adver and --seed apply, the other NES options do not)")
+    ap.add_argument("--attack", default="nes", choices=["nes", "pso", "kenansville"],
+                    help="the search: FAKEBOB's NES gradient estimate (default), SirenAttack's particle swarm "
+                         "(fakebob_amd/pso.py; -epsilon, -max_iter, -adver and --seed apply, the other NES options do not) or "
+                         "Kenansville's decision-only spectral removal (fakebob_amd/kenansville.py; --kv-* and --seed apply)")
+    ap.add_argument("--kv-window", dest="kv_window", default=100, type=int, help="--attack kenansville: samples per window (8 .. 128)")
+    ap.add_argument("--kv-grid", dest="kv_grid", default=15, type=int, help="--attack kenansville: candidates per round (1 .. 64)")
+    ap.add_argument("--kv-max-factor", dest="kv_max_factor", default=1.0, type=float,
+                    help="--attack kenansville: the largest share of a window's spectral energy to remove, in (0, 1]")
     ap.add_argument("--particles", default=25, type=int, help="--attack pso: particles of the swarm (2 .. 64)")
     ap.add_argument("--pso-w", dest="pso_w", default=(0.9, 0.1), type=_pair, metavar="WI:WE",
                     help="--attack pso: inertia weight, falling linearly from WI to WE over max_iter iterations")
@@ -217,6 +222,11 @@ def main(argv=None, model_factory=None, bob_factory=None):
             ap.error("--attack pso does not run under expectation over transformation (--eot-size %d)" % args.eot_size)
         if args.companions > 0:
             ap.error("--attack pso does not take companion utterances (--companions %d)" % args.companions)
+    if args.attack == "kenansville":      # likewise
+        if args.eot_size is not None and args.eot_size > 1:
+            ap.error("--attack kenansville does not run under expectation over transformation (--eot-size %d)" % args.eot_size)
+        if args.companions > 0:
+            ap.error("--attack kenansville does not take companion utterances (--companions %d)" % args.companions)
 
     task, attack_type, spk_id_list = args.task, args.attack_type, args.speaker_id
     if task == "SV":                      # SV only supports one enrolled speaker (:449-451)
@@ -259,7 +269,12 @@ def main(argv=None, model_factory=None, bob_factory=None):
     if args.attack == "pso":
         hp = dict(adver_thresh=args.adver_thresh, epsilon=args.epsilon, max_iter=args.max_iter, n_particles=args.particles,
                   w_init=args.pso_w[0], w_end=args.pso_w[1], c1=args.pso_c[0], c2=args.pso_c[1], v_max=args.pso_vmax)
-    if bob_factory is None and args.attack == "pso":
+    if args.attack == "kenansville":
+        hp = dict(window=args.kv_window, grid=args.kv_grid, max_factor=args.kv_max_factor)
+    if bob_factory is None and args.attack == "kenansville":
+        from .kenansville import Kenansville
+        bobs = [Kenansville(task, attack_type, m, seed=seed, verbose=False, **hp) for m in models]
+    elif bob_factory is None and args.attack == "pso":
         from .pso import ParticleSwarm
         bobs = [ParticleSwarm(task, attack_type, m, seed=seed, verbose=False, **hp) for m in models]
     elif bob_factory is None:

@@ -198,6 +198,9 @@ struct fb_engine {
   DevBuf audio, adver, grad_m, grad, noise, zbuf, scores, loss, dist_part, nes_out, stage_f64, ext_x, ext_z;
   DevBuf pso_x, pso_v, pso_pb, pso_gb;  // fb_attack_pso's swarm: positions, velocities, personal bests [P][N], global best [N]
   DevBuf pso_look;                      // ... and what its host reads per iteration: {FbNesDev, loss[P], scores[P][S]}
+  DevBuf kv_x, kv_best, kv_tab;         // fb_attack_kenansville: the int16 cast of the audio [N], the candidate of hi [N], the four tables [4][W]
+  DevBuf kv_ma, kv_mb, kv_cum, kv_E;    // ... the analysis: m a, m b [nw][K] int32, cum [nw][K] and E [nw] int64
+  DevBuf kv_look;                       // ... and what its host reads per round: {FbNesDev, loss[G], scores[G][S], tv[G]}
   FbNesDev *h_out = nullptr;  // pinned
   int *h_tv = nullptr;        // pinned, grows
   size_t h_tv_cap = 0;
@@ -3069,6 +3072,252 @@ extern "C" int fb_debug_pso_step(fb_engine *e, const double *audio, int64_t N, d
   FBCHK(d2h(e, pb_out, e->pso_pb.p, sizeof(double) * n));
   FBCHK(d2h(e, gb_out, e->pso_gb.p, sizeof(double) * (size_t)N));
   FBCHK(d2h(e, q_out, e->wav.p, sizeof(int16_t) * n));
+  FBCHK(sync_stream(e));
+  HIPCHK(hipGetLastError());
+  return FB_OK;
+}
+
+// ------------------------------------------------- decision-only attack
+// fb_attack_kenansville (the "decision-only attack" section of fakebob_hip.h).  k_kv_analyse runs once; every round
+// k_kv_candidates writes the round's rows into the NES batch, the ordinary path scores them, k_loss forms scores[rows][S],
+// and the host reads them with tv[rows] once, decides and narrows the bracket.  The fused finalisation, the i-vector
+// tail-loss shortcut and the device control block are not used.
+static int check_kv_tables(int W, const int32_t *tab) {
+  if (W < FB_KV_MIN_WINDOW || W > FB_KV_MAX_WINDOW)
+    return fb_fail(FB_E_ARG, "window %d outside %d .. %d", W, FB_KV_MIN_WINDOW, FB_KV_MAX_WINDOW);
+  if (!tab) return fb_fail(FB_E_ARG, "null tables");
+  if (tab[0] != (1 << 30) || tab[W] != 0 || tab[2 * W] != (1 << 22) || tab[3 * W] != 0)
+    return fb_fail(FB_E_ARG, "the tables do not start with CF[0] = 2^30, SF[0] = 0, CI[0] = 2^22, SI[0] = 0");
+  return FB_OK;
+}
+// the tables and the analysis buffers of N samples in windows of W, the tables uploaded
+static int prepare_kv(fb_engine *e, int64_t N, int W, const int32_t *tab) {
+  const size_t nw = (size_t)((N + W - 1) / W), K = (size_t)W / 2 + 1;
+  FBCHK(e->kv_x.ensure(sizeof(int16_t) * (size_t)N));
+  FBCHK(e->kv_best.ensure(sizeof(int16_t) * (size_t)N));
+  FBCHK(e->kv_tab.ensure(sizeof(int32_t) * 4 * (size_t)W));
+  FBCHK(e->kv_ma.ensure(sizeof(int32_t) * nw * K));
+  FBCHK(e->kv_mb.ensure(sizeof(int32_t) * nw * K));
+  FBCHK(e->kv_cum.ensure(sizeof(long long) * nw * K));
+  FBCHK(e->kv_E.ensure(sizeof(long long) * nw));
+  FBCHK(h2d(e, e->kv_tab.p, tab, sizeof(int32_t) * 4 * (size_t)W));
+  return FB_OK;
+}
+static void launch_kv_analyse(fb_engine *e, int64_t N, int W) {
+  fb_launch_kv_analyse(e->stream, e->kv_x.as<int16_t>(), N, W, e->kv_tab.as<int32_t>(), e->kv_ma.as<int32_t>(),
+                       e->kv_mb.as<int32_t>(), e->kv_cum.as<long long>(), e->kv_E.as<long long>());
+}
+static void launch_kv_candidates(fb_engine *e, int64_t N, int W, int rows, const int *q, int16_t *out) {
+  fb_launch_kv_candidates(e->stream, e->kv_x.as<int16_t>(), N, W, rows, q, e->kv_tab.as<int32_t>(), e->kv_ma.as<int32_t>(),
+                          e->kv_mb.as<int32_t>(), e->kv_cum.as<long long>(), e->kv_E.as<long long>(), out);
+}
+
+extern "C" int fb_attack_kenansville(fb_engine *e, const fb_nes_params *p, const fb_kv_params *k, const int32_t *tables,
+                                     const double *audio, int64_t N, int16_t *adv_i16, int *success, int *factor,
+                                     int *n_queries, int *n_rounds, int *qs, int *decisions, double *scores, int *trace) {
+  if (e) e->bench_it = -1;
+  if (!e || !p || !k || !audio || !adv_i16 || !success || !factor || !n_queries || !n_rounds || !qs || !decisions || !scores || !trace)
+    return fb_fail(FB_E_ARG, "null argument");
+  if (!e->have_gmm) return fb_fail(FB_E_STATE, "no model loaded");
+  if (e->eot > 1)
+    return fb_fail(FB_E_STATE, "fb_attack_kenansville does not run under expectation over transformation (fb_set_eot(%d)): set 1", e->eot);
+  if (e->comp_K1 > 0)
+    return fb_fail(FB_E_STATE, "fb_attack_kenansville does not run with companion utterances (fb_set_companions: %d set): clear them", e->comp_K1);
+  const int W = k->window, G = k->grid, bits = nes_bits(p);
+  FBCHK(check_kv_tables(W, tables));
+  if (G < 1 || G > FB_KV_MAX_ROWS) return fb_fail(FB_E_ARG, "grid %d outside 1 .. %d", G, FB_KV_MAX_ROWS);
+  if (k->q_max < 1 || k->q_max > 65536) return fb_fail(FB_E_ARG, "q_max %d outside 1 .. 65536", k->q_max);
+  if (k->max_rounds < 1 || k->max_rounds > FB_KV_MAX_ROUNDS) return fb_fail(FB_E_ARG, "max_rounds %d outside 1 .. %d", k->max_rounds, FB_KV_MAX_ROUNDS);
+  if (bits < 2 || bits > 16) return fb_fail(FB_E_ARG, "bits_per_sample %d unsupported (2 .. 16)", bits);
+  if (N <= 0) return fb_fail(FB_E_ARG, "empty audio");
+  if (p->task != e->task) return fb_fail(FB_E_ARG, "params.task %d != engine system task %d", p->task, e->task);
+  if (p->task != FB_TASK_SV && p->task != FB_TASK_OSI && p->task != FB_TASK_CSI) return fb_fail(FB_E_ARG, "bad task %d", p->task);
+  if (p->attack_type != FB_TARGETED && p->attack_type != FB_UNTARGETED) return fb_fail(FB_E_ARG, "bad attack_type %d", p->attack_type);
+  const int S = fb_num_speakers(e);
+  const bool targeted = p->attack_type == FB_TARGETED;
+  const int label = targeted ? p->target : p->true_label;   // a decision value
+  {
+    const bool ok = p->task == FB_TASK_SV ? (label == 1 || label == -1)
+                  : p->task == FB_TASK_OSI ? (label >= -1 && label < S) : (label >= 0 && label < S);
+    if (!ok) return fb_fail(FB_E_ARG, "%s %d is no decision of this system", targeted ? "target" : "true label", label);
+  }
+  if (num_frames(e->cfg, N) <= 0) return fb_fail(FB_E_ARG, "audio shorter than one frame");
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(e->audio.ensure(sizeof(double) * (size_t)N));
+  FBCHK(prepare_kv(e, N, W, tables));
+  // what the host reads once per round, in one block: k_loss's result block (not read), loss[G] (not read), scores[G][S], tv[G]
+  static_assert(sizeof(FbNesDev) % sizeof(double) == 0, "the result block is followed by doubles");
+  const size_t out_d = sizeof(FbNesDev) / sizeof(double), sc_d = out_d + (size_t)G, tv_d = sc_d + (size_t)G * S;
+  const size_t look_d = tv_d + ((size_t)G + 1) / 2;
+  FBCHK(e->kv_look.ensure(sizeof(double) * look_d));
+  FbNesDev *out_dev = e->kv_look.as<FbNesDev>();
+  double *loss_dev = e->kv_look.as<double>() + out_d, *scores_dev = e->kv_look.as<double>() + sc_d;
+  int *tv_dev = reinterpret_cast<int *>(e->kv_look.as<double>() + tv_d);
+  FBCHK(launch_state_reset(e));
+  e->iter_seconds.clear();
+
+  FBCHK(h2d(e, e->audio.p, audio, sizeof(double) * (size_t)N));
+  fb_launch_quantize(e->stream, e->audio.as<double>(), N, bits, e->kv_x.as<int16_t>());
+  launch_kv_analyse(e, N, W);
+  std::vector<double> look(look_d);
+  const double *sc = look.data() + sc_d;
+  std::vector<int> cand;
+  cand.reserve(G);
+  int lo = 0, hi = -1, r = 0, queries = 0;
+  *success = -1;
+  auto t_prev = std::chrono::steady_clock::now();
+  for (;; ++r) {
+    // the round's candidates, ascending
+    cand.clear();
+    bool last = false;
+    if (r == 0) {
+      for (int j = 0; j < G; ++j) {
+        const int qj = (int)(((long long)(j + 1) * k->q_max) / G);
+        if (qj > 0 && (cand.empty() || qj != cand.back())) cand.push_back(qj);
+      }
+    } else {
+      const int d = hi - lo;
+      if (d - 1 <= G) {
+        for (int qj = lo + 1; qj < hi; ++qj) cand.push_back(qj);
+        last = true;
+      } else {
+        for (int j = 0; j < G; ++j) cand.push_back(lo + (int)(((long long)(j + 1) * d) / (G + 1)));
+      }
+    }
+    const int rows = (int)cand.size();
+    FBCHK(prepare_nes_batch(e, N, rows));
+    launch_kv_candidates(e, N, W, rows, cand.data(), e->wav.as<int16_t>());
+    FbScoreCall call{FbRngPoint{p->seed, p->stream, (uint32_t)r, 0}};
+    FBCHK(run_scoring(e, call, rows, e->h_frame_off[rows]));
+    // (k_loss is here for the system scores of fb_loss_row alone: its loss and its labels are not this attack's)
+    fb_launch_loss(e->stream, e->raw.as<double>(), e->tv.as<int>(), rows, e->n_out, p->task, e->kind, FB_UNTARGETED,
+                   e->zmean.as<double>(), e->zstd.as<double>(), p->threshold, 0.0, 0, 0, nullptr, 0, scores_dev, loss_dev, out_dev);
+    HIPCHK(hipMemcpyAsync(tv_dev, e->tv.p, sizeof(int) * (size_t)rows, hipMemcpyDeviceToDevice, e->stream));
+    // the one look of the round: one copy through pinned memory, one synchronisation
+    FBCHK(d2h(e, look.data(), e->kv_look.p, sizeof(double) * look_d));
+    FBCHK(sync_stream(e));
+    const int *tv = reinterpret_cast<const int *>(look.data() + tv_d);
+    int first = -1;   // the smallest succeeding candidate's row
+    for (int j = 0; j < G; ++j) qs[(size_t)r * G + j] = j < rows ? cand[j] : -1;
+    for (int j = 0; j < rows; ++j) {
+      const double *s = sc + (size_t)j * S;
+      for (int m = 0; m < S; ++m) scores[((size_t)r * G + j) * S + m] = s[m];
+      int d;
+      if (tv[j] <= 0) {
+        d = -2;   // no voiced frames: no decision
+      } else if (p->task == FB_TASK_SV) {
+        d = s[0] >= p->threshold ? 1 : -1;
+      } else {
+        int am = 0;
+        for (int m = 1; m < S; ++m) if (s[m] > s[am]) am = m;   // the first maximum
+        d = (p->task == FB_TASK_OSI && s[am] < p->threshold) ? -1 : am;
+      }
+      decisions[(size_t)r * G + j] = d;
+      const bool ok = d != -2 && (targeted ? d == label : d != label);
+      if (ok && first < 0) first = j;
+    }
+    queries += rows;
+    if (first >= 0) {
+      hi = cand[first];
+      // the candidate of hi is a row that was scored: kept before the next round's batch takes its place
+      HIPCHK(hipMemcpyAsync(e->kv_best.p, e->wav.as<int16_t>() + (size_t)first * N, sizeof(int16_t) * (size_t)N,
+                            hipMemcpyDeviceToDevice, e->stream));
+      if (first > 0) lo = cand[first - 1];
+    } else if (hi >= 0 && rows > 0) {
+      lo = cand[rows - 1];
+    }
+    trace[3 * r] = lo; trace[3 * r + 1] = hi; trace[3 * r + 2] = rows;
+    const auto t_now = std::chrono::steady_clock::now();
+    e->iter_seconds.push_back(std::chrono::duration<double>(t_now - t_prev).count());
+    t_prev = t_now;
+    if (hi < 0) break;   // nothing succeeded in round 0
+    if (hi - lo == 1 || last || r == k->max_rounds - 1) break;
+  }
+  *n_rounds = r + 1;
+  *n_queries = queries;
+  *success = hi >= 0 ? 1 : -1;
+  *factor = hi;
+  FBCHK(d2h(e, adv_i16, hi >= 0 ? e->kv_best.p : e->kv_x.p, sizeof(int16_t) * (size_t)N));
+  FBCHK(sync_stream(e));
+  HIPCHK(hipGetLastError());
+  return FB_OK;
+}
+
+extern "C" int fb_debug_kv_analyse(fb_engine *e, const int16_t *x, int64_t N, int W, const int32_t *tables, int32_t *a,
+                                   int32_t *b, int64_t *cum, int64_t *E) {
+  if (!e || !x || !a || !b || !cum || !E || N <= 0) return fb_fail(FB_E_ARG, "bad argument");
+  FBCHK(check_kv_tables(W, tables));
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  FBCHK(prepare_kv(e, N, W, tables));
+  FBCHK(h2d(e, e->kv_x.p, x, sizeof(int16_t) * (size_t)N));
+  launch_kv_analyse(e, N, W);
+  const size_t nw = (size_t)((N + W - 1) / W), K = (size_t)W / 2 + 1;
+  FBCHK(d2h(e, a, e->kv_ma.p, sizeof(int32_t) * nw * K));
+  FBCHK(d2h(e, b, e->kv_mb.p, sizeof(int32_t) * nw * K));
+  FBCHK(d2h(e, cum, e->kv_cum.p, sizeof(int64_t) * nw * K));
+  FBCHK(d2h(e, E, e->kv_E.p, sizeof(int64_t) * nw));
+  FBCHK(sync_stream(e));
+  HIPCHK(hipGetLastError());
+  // the device keeps m a and m b; the hook hands out a and b
+  for (size_t w = 0; w < nw; ++w)
+    for (size_t kb = 0; kb < K; ++kb)
+      if (!(kb == 0 || (W % 2 == 0 && kb == (size_t)W / 2))) {
+        a[w * K + kb] /= 2;
+        b[w * K + kb] /= 2;
+      }
+  return FB_OK;
+}
+
+extern "C" int fb_debug_kv_candidates(fb_engine *e, const int16_t *x, int64_t N, int W, const int32_t *tables, const int *q,
+                                      int rows, int16_t *y) {
+  if (!e || !x || !q || !y || N <= 0) return fb_fail(FB_E_ARG, "bad argument");
+  FBCHK(check_kv_tables(W, tables));
+  if (rows < 1 || rows > FB_KV_MAX_ROWS) return fb_fail(FB_E_ARG, "rows %d outside 1 .. %d", rows, FB_KV_MAX_ROWS);
+  for (int j = 0; j < rows; ++j)
+    if (q[j] < 0 || q[j] > 65536) return fb_fail(FB_E_ARG, "factor %d outside 0 .. 65536", q[j]);
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  e->cached_B = -1;  // (e->wav takes the batch, without a batch layout)
+  FBCHK(prepare_kv(e, N, W, tables));
+  FBCHK(e->wav.ensure(sizeof(int16_t) * (size_t)N * rows));
+  FBCHK(h2d(e, e->kv_x.p, x, sizeof(int16_t) * (size_t)N));
+  launch_kv_analyse(e, N, W);
+  launch_kv_candidates(e, N, W, rows, q, e->wav.as<int16_t>());
+  FBCHK(d2h(e, y, e->wav.p, sizeof(int16_t) * (size_t)N * rows));
+  FBCHK(sync_stream(e));
+  HIPCHK(hipGetLastError());
+  return FB_OK;
+}
+
+// tools/kenansville_rate.py: `reps` launches of each kernel between two events, after one of each to warm up
+extern "C" int fb_bench_kv_kernels(fb_engine *e, const int16_t *x, int64_t N, int W, const int32_t *tables, const int *q, int rows,
+                                   int reps, double *ms /*[2]: analysis, candidates -- per launch*/) {
+  if (!e || !x || !q || !ms || N <= 0 || reps < 1) return fb_fail(FB_E_ARG, "bad argument");
+  FBCHK(check_kv_tables(W, tables));
+  if (rows < 1 || rows > FB_KV_MAX_ROWS) return fb_fail(FB_E_ARG, "rows %d outside 1 .. %d", rows, FB_KV_MAX_ROWS);
+  for (int j = 0; j < rows; ++j)
+    if (q[j] < 0 || q[j] > 65536) return fb_fail(FB_E_ARG, "factor %d outside 0 .. 65536", q[j]);
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  e->cached_B = -1;  // (e->wav takes the batch, without a batch layout)
+  FBCHK(prepare_kv(e, N, W, tables));
+  FBCHK(e->wav.ensure(sizeof(int16_t) * (size_t)N * rows));
+  FBCHK(h2d(e, e->kv_x.p, x, sizeof(int16_t) * (size_t)N));
+  launch_kv_analyse(e, N, W);
+  launch_kv_candidates(e, N, W, rows, q, e->wav.as<int16_t>());
+  for (int which = 0; which < 2; ++which) {
+    HIPCHK(hipEventRecord(e->ev0, e->stream));
+    for (int i = 0; i < reps; ++i) {
+      if (which == 0) launch_kv_analyse(e, N, W);
+      else launch_kv_candidates(e, N, W, rows, q, e->wav.as<int16_t>());
+    }
+    HIPCHK(hipEventRecord(e->ev1, e->stream));
+    HIPCHK(hipEventSynchronize(e->ev1));
+    float t = 0.f;
+    HIPCHK(hipEventElapsedTime(&t, e->ev0, e->ev1));
+    ms[which] = (double)t / reps;
+  }
   FBCHK(sync_stream(e));
   HIPCHK(hipGetLastError());
   return FB_OK;

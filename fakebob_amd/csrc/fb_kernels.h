@@ -193,6 +193,19 @@ void fb_launch_pso_step(hipStream_t s, const double *audio, int64_t N, int P, do
                         double *gb, unsigned long long improved, int g_new, double w, double c1, double c2, double vmax,
                         uint64_t seed, uint32_t stream, uint32_t t, int bits, int16_t *q);
 
+// ---- decision-only attack (fb_attack_kenansville; kenansville_kernels.hip) ---------------------------------------------
+#define FB_KV_MIN_WINDOW 8
+#define FB_KV_MAX_WINDOW 128
+#define FB_KV_MAX_ROWS 64        // rows of a round (the q list travels as one kernel argument)
+#define FB_KV_MAX_ROUNDS 32
+// the analysis of x[N] in windows of W (K = W / 2 + 1 bins, nw = ceil(N / W) windows): m a, m b [nw][K], cum [nw][K] in bin
+// order, E [nw].  tab: the four tables CF, SF, CI, SI, W entries each, one after the other.
+void fb_launch_kv_analyse(hipStream_t s, const int16_t *x, int64_t N, int W, const int32_t *tab, int32_t *ma, int32_t *mb,
+                          long long *cum, long long *E);
+// the candidates q[0 .. rows) (host array) of x, row j at out + j * N
+void fb_launch_kv_candidates(hipStream_t s, const int16_t *x, int64_t N, int W, int rows, const int *q, const int32_t *tab,
+                             const int32_t *ma, const int32_t *mb, const long long *cum, const long long *E, int16_t *out);
+
 // Device-side control block of an attack (FAKEBOB.py:171-203): early stop on loss[0] < 0 (:181), the
 // plateau learning-rate schedule (:195-200) and the per-iteration trace rows are handled by the loss
 // kernel itself, so the host can queue several NES iterations ahead and only looks at the block once

@@ -36,6 +36,13 @@ def pso_params(particles=25, w_init=0.9, w_end=0.1, c1=1.4961, c2=1.4961, v_max=
     return q
 
 
+def kv_params(window=100, grid=15, q_max=65536, max_rounds=32):
+    """fb_kv_params: the search of Engine.attack_kenansville (fakebob_hip.h, "decision-only attack")."""
+    k = N.KvParams()
+    k.window = int(window); k.grid = int(grid); k.q_max = int(q_max); k.max_rounds = int(max_rounds)
+    return k
+
+
 class Engine(object):
     def __init__(self, device=0):
         self._L = N.lib()
@@ -570,9 +577,78 @@ class Engine(object):
                                           C.c_int(int(bits_per_sample)), N.ptr(xo), N.ptr(vo), N.ptr(po), N.ptr(go), N.ptr(q)))
         return xo, vo, po, go, q
 
+    # ---- decision-only attack
+    def attack_kenansville(self, params, kv, audio, tables=None):
+        """fb_attack_kenansville: the decision-only attack on this engine's system -> a dict: adv (int16), success (+-1),
+        factor (-1: none), n_queries, and per round qs (n_rounds, G) (-1 in unused places), decisions (n_rounds, G) (-2: no
+        voiced frames; unused places -3), scores (n_rounds, G, S) (unused places NaN), trace (n_rounds, 3) = lo, hi, rows.
+        tables=None: fakebob_amd.kenansville.tables(kv.window)."""
+        from . import kenansville as KV
+        audio = np.ascontiguousarray(audio, np.float64).reshape(-1)
+        n, S = audio.size, max(self.n_speakers, 1)
+        G, R = min(max(int(kv.grid), 1), 64), min(max(int(kv.max_rounds), 1), 32)
+        tab = self._kv_tables(KV, kv.window, tables)
+        adv = np.empty(n, np.int16)
+        qs = np.full((R, G), -1, np.int32)
+        dec = np.full((R, G), -3, np.int32)
+        sc = np.full((R, G, S), np.nan, np.float64)
+        trace = np.zeros((R, 3), np.int32)
+        flag, factor, nq, nr = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        N.check(self._L.fb_attack_kenansville(self._h, C.byref(params), C.byref(kv), N.ptr(tab), N.ptr(audio), C.c_int64(n),
+                                              N.ptr(adv), C.byref(flag), C.byref(factor), C.byref(nq), C.byref(nr), N.ptr(qs),
+                                              N.ptr(dec), N.ptr(sc), N.ptr(trace)))
+        r = nr.value
+        return dict(adv=adv, success=flag.value, factor=factor.value, n_queries=nq.value, qs=qs[:r], decisions=dec[:r],
+                    scores=sc[:r], trace=trace[:r])
+
+    @staticmethod
+    def _kv_tables(KV, window, tables):
+        """the four tables as one contiguous (4, W') int32 array: handed in as they are, or built for a window in range
+        (a window out of range gets a dummy the library refuses by its own check)"""
+        if tables is not None:
+            return np.ascontiguousarray(tables, np.int32)
+        W = int(window)
+        return KV.tables(W) if KV.MIN_WINDOW <= W <= KV.MAX_WINDOW else np.zeros((4, 1), np.int32)
+
+    def debug_kv_analyse(self, x, window, tables=None):
+        """The analysis of int16 samples (fb_debug_kv_analyse) -> a, b (nw, K) int32, cum (nw, K) int64, E (nw,) int64."""
+        from . import kenansville as KV
+        x = np.ascontiguousarray(x, np.int16).reshape(-1)
+        W = int(window)
+        tab = self._kv_tables(KV, W, tables)
+        nw, K = (-(-x.size // W), W // 2 + 1) if W > 0 else (1, 1)
+        a, b = np.empty((nw, K), np.int32), np.empty((nw, K), np.int32)
+        cum, E = np.empty((nw, K), np.int64), np.empty(nw, np.int64)
+        N.check(self._L.fb_debug_kv_analyse(self._h, N.ptr(x), C.c_int64(x.size), C.c_int(W), N.ptr(tab), N.ptr(a), N.ptr(b),
+                                            N.ptr(cum), N.ptr(E)))
+        return a, b, cum, E
+
+    def debug_kv_candidates(self, x, window, qs, tables=None):
+        """The candidates of int16 samples for the factors qs (fb_debug_kv_candidates) -> y (rows, N) int16."""
+        from . import kenansville as KV
+        x = np.ascontiguousarray(x, np.int16).reshape(-1)
+        q = np.ascontiguousarray(qs, np.int32).reshape(-1)
+        tab = self._kv_tables(KV, window, tables)
+        y = np.empty((max(q.size, 1), x.size), np.int16)
+        N.check(self._L.fb_debug_kv_candidates(self._h, N.ptr(x), C.c_int64(x.size), C.c_int(int(window)), N.ptr(tab), N.ptr(q),
+                                               C.c_int(q.size), N.ptr(y)))
+        return y
+
+    def bench_kv_kernels(self, x, window, qs, reps=50, tables=None):
+        """Milliseconds per k_kv_analyse launch and per k_kv_candidates launch of len(qs) rows (fb_bench_kv_kernels: device
+        events around `reps` launches of each)."""
+        from . import kenansville as KV
+        x = np.ascontiguousarray(x, np.int16).reshape(-1)
+        q = np.ascontiguousarray(qs, np.int32).reshape(-1)
+        tab = self._kv_tables(KV, window, tables)
+        ms = np.zeros(2, np.float64)
+        N.check(self._L.fb_bench_kv_kernels(self._h, N.ptr(x), C.c_int64(x.size), C.c_int(int(window)), N.ptr(tab), N.ptr(q),
+                                            C.c_int(q.size), C.c_int(int(reps)), N.ptr(ms)))
+        return float(ms[0]), float(ms[1])
+
     def attack_iter_seconds(self, n):
         """Seconds per iteration of the last attack / attack_ext (device clock, fb_attack_iter_seconds); of the last
-        attack_pso, as the host measured them."""
+        attack_pso and per round of the last attack_kenansville, as the host measured them."""
         out = np.zeros(max(int(n), 0), np.float64)
         if n > 0:
             N.check(self._L.fb_attack_iter_seconds(self._h, N.ptr(out), C.c_int(int(n))))

@@ -30,6 +30,8 @@
  *   fb_estimate_threshold     FakeBob.estimate_threshold (FAKEBOB.py:39-137)
  *   fb_attack_pso             (none in FAKEBOB: SirenAttack's particle-swarm optimisation, the other score-based black-box
  *                             attack of SpeakerGuard's evaluation, on this library's own systems)
+ *   fb_attack_kenansville     (none in FAKEBOB: Kenansville, the decision-only black-box attack of that evaluation -- spectral
+ *                             content is removed until the decision changes)
  *   fb_get_grad_ext / fb_attack_ext   the same around a foreign `model` (README.md:136)
  *   fb_get_grad_dev / fb_attack_dev   ... around a foreign model that runs on the
  *                             same GPU: the batch and the scores stay on the device
@@ -431,6 +433,70 @@ typedef struct { int particles; double w_init, w_end, c1, c2, v_max; } fb_pso_pa
 int fb_attack_pso(fb_engine *e, const fb_nes_params *p, const fb_pso_params *q, const double *audio, int64_t N,
                   int16_t *adv_i16, double *adv_f64 /*nullable*/, int *success, int *n_iters,
                   double *trace /*[max_iter][3 + S]*/, double *losses /*[max_iter][P]*/);
+
+/* ---- decision-only attack: Kenansville, the third black-box attack SpeakerGuard runs -------------------------------------
+ * fb_attack and fb_attack_pso read scores; many deployed recognisers return a decision only.  fb_attack_kenansville reads
+ * nothing else: it removes the weakest spectral content of short windows of the utterance until the decision changes, and
+ * looks for the smallest removal that does so.  It is the evasion attack of the three: an enrolled speaker is no longer
+ * recognised.  Every candidate is a function of the audio and ONE integer, the factor q in 0 .. 65536 (the share q / 65536
+ * of a window's spectral energy that is removed, weakest bins first), so the search is a chain of batches: one launch
+ * analyses the utterance once (k_kv_analyse), one launch per round writes a round's candidates straight into the int16
+ * batch the front end scores (k_kv_candidates), and the host looks once per round, as it does for PSO.
+ * Read from fb_nes_params: task, attack_type, threshold, target, true_label, seed, stream and bits_per_sample.  adver_thresh
+ * and the NES-only fields are not read.
+ * Signal contract.  All integers; >> is an arithmetic shift; exactly reproducible in numpy (the mask is a sort and a
+ * threshold: a tolerance cannot be tested, bits can).  Every intermediate stays below 2^53.
+ *   input      x[0 .. N): the int16 cast of `audio` (the cast of every NES row, bits_per_sample).  W = window, 8 .. 128;
+ *              K = floor(W / 2) + 1 bins; nw = ceil(N / W) windows; the last window reads 0 beyond N and writes only its
+ *              first N mod W samples.  Below, n = 0 .. W - 1 counts inside ONE window.
+ *   tables     the caller passes four int32 tables of W entries each, one after the other (no libm in the contract):
+ *                CF[j] = rint(cos(2 pi j / W) 2^30), SF[j] = rint(sin(2 pi j / W) 2^30),
+ *                CI[j] = rint(cos(2 pi j / W) 2^22), SI[j] = rint(sin(2 pi j / W) 2^22).
+ *              Checked: CF[0] == 2^30, CI[0] == 2^22, SF[0] == SI[0] == 0 (FB_E_ARG otherwise).
+ *   analysis   once per attack, per window:
+ *                A[k] = sum_n x[n] CF[(n k) mod W],  B[k] = sum_n x[n] SF[(n k) mod W],  k = 0 .. K - 1   (|A|, |B| <= 2^52)
+ *                a[k] = (A[k] + 2^29) >> 30,  b[k] likewise                                             (|a|, |b| <= 2^22)
+ *                p[k] = a^2 + b^2;  m[k] = 1 for k = 0 and, W even, for k = W / 2, otherwise 2;  e[k] = m[k] p[k];  E = sum e[k]
+ *                the bins sorted ascending by the pair (p[k], k);  cum[k] = the sum of e over the bins up to and
+ *                including k in that order
+ *   candidate  for a factor q in 0 .. 65536:
+ *                thr = (E >> 16) q + (((E & 0xFFFF) q) >> 16)            (= floor(E q / 65536), no overflow)
+ *                bin k is removed iff cum[k] <= thr
+ *                R[n] = sum over removed k of m[k] (a[k] CI[(n k) mod W] + b[k] SI[(n k) mod W])   (sum of magnitudes <= 2^48)
+ *                D = W 2^22;  r[n] = floor((2 R[n] + D) / (2 D));  y[n] = clip16(x[n] - r[n])
+ *              Only what is removed is ever synthesised: q = 0 is the identity bit for bit, a silent window stays silent.
+ * Decisions.  Per scored row the system scores are formed exactly as fb_attack forms them (fb_system_scores' values), then
+ * the system classes' make_decisions rule: SV  s >= threshold ? 1 : -1;  OSI  the first maximum's index, -1 if the
+ * maximum < threshold;  CSI  the first maximum's index.  A row with no voiced frames is NO DECISION: it is written as -2,
+ * it is never a success, and it does not abort the call (high factors approach silence, so this happens in ordinary use:
+ * there is no FB_E_NO_VOICED here).  Success is d != true_label (untargeted) or d == target (targeted); the label is a
+ * decision value: SV +-1, OSI -1 .. S - 1, CSI 0 .. S - 1.
+ * Search.  grid = G rows per round, 1 .. 64; q_max 1 .. 65536; max_rounds 1 .. 32.  The bracket is (lo, hi]: lo fails, hi
+ * succeeds; it starts as lo = 0 (the audio itself: taken as failing, never scored) with no hi.
+ *   round 0      q_j = floor((j + 1) q_max / G), j = 0 .. G - 1, duplicates and zeros dropped
+ *   later        d = hi - lo.  d - 1 <= G: lo + 1 .. hi - 1, and this is the last round.  Otherwise
+ *                q_j = lo + floor((j + 1) d / (G + 1)), j = 0 .. G - 1.
+ *   after        hi becomes the smallest succeeding candidate, if any; lo the largest candidate below the new hi, if any.
+ *                (G = 1 is plain bisection.)
+ *   stops        no success in round 0 (*success = -1, adv_i16 = x, *factor = -1);  hi - lo == 1;  the last round as
+ *                defined above;  max_rounds.
+ *   result       *success = 1, *factor = hi, adv_i16 = the candidate of hi -- a row that WAS scored --, *n_queries = the rows
+ *                scored, *n_rounds.  Per round r < *n_rounds: qs[r][G] (the candidates ascending, -1 in unused places),
+ *                decisions[r][G], scores[r][G][S] (unused places not written), trace[r] = {lo, hi after the round, rows}.
+ * fb_attack_iter_seconds reports the host's seconds per round, as for PSO.  fb_stats counts the rows as for any batch.
+ * Victim.  The air channel, the input-transform chain, the codec, dither and feature compression act as in fb_attack_pso,
+ * keyed by the call's (seed, stream) with epoch = the round and utterance row = the candidate's index in the round.
+ * Refusals.  FB_E_ARG: anything outside the ranges above, a task other than the engine's, a label that is no decision of
+ * the system, wrong tables, bits_per_sample outside 2 .. 16, audio shorter than one frame.  FB_E_STATE: no system loaded, or
+ * fb_set_eot(r > 1) or companions in force -- BOTH STAY OUT OF THIS VERSION: set 1 / clear them.  The engine's own systems
+ * only: there are no _ext / _dev twins.
+ * Deviations from Kenansville / SpeakerGuard's version: theirs transforms with a floating-point FFT (or SSA) and bisects one
+ * candidate per query; here the arithmetic is the integer contract above and a round scores G candidates. */
+typedef struct { int window; int grid; int q_max; int max_rounds; } fb_kv_params;
+int fb_attack_kenansville(fb_engine *e, const fb_nes_params *p, const fb_kv_params *k, const int32_t *tables /*[4][W]*/,
+                          const double *audio, int64_t N, int16_t *adv_i16, int *success, int *factor, int *n_queries,
+                          int *n_rounds, int *qs /*[max_rounds][G]*/, int *decisions /*[max_rounds][G]*/,
+                          double *scores /*[max_rounds][G][S]*/, int *trace /*[max_rounds][3]*/);
 
 const char *fb_last_error(void);
 int fb_version(void);

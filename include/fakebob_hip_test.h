@@ -114,6 +114,21 @@ int fb_debug_pso_step(fb_engine *e, const double *audio, int64_t N, double epsil
                       double v_max, uint64_t seed, uint32_t stream, uint32_t t, int bits, double *x_out, double *v_out,
                       double *pb_out, double *gb_out, int16_t *q_out);
 
+/* Decision-only attack (fakebob_hip.h: fb_attack_kenansville and its signal contract).  Both hooks run exactly the launches
+ * the attack runs, on int16 samples handed in as they are; no system has to be loaded.  W = 8 .. 128, N >= 1, tables
+ * [4][W] as the attack takes them; K = W / 2 + 1, nw = ceil(N / W).
+ * fb_debug_kv_analyse: a, b [nw][K] (the device keeps m a and m b; the hook divides), cum [nw][K] in bin order, E [nw].
+ * fb_debug_kv_candidates: the analysis, then one candidate launch for the factors q[0 .. rows), rows = 1 .. 64, each
+ * 0 .. 65536 -> y [rows][N]. */
+int fb_debug_kv_analyse(fb_engine *e, const int16_t *x, int64_t N, int W, const int32_t *tables, int32_t *a, int32_t *b,
+                        int64_t *cum, int64_t *E);
+int fb_debug_kv_candidates(fb_engine *e, const int16_t *x, int64_t N, int W, const int32_t *tables, const int *q, int rows,
+                           int16_t *y);
+/* tools/kenansville_rate.py: the two launches alone, `reps` of each between two events after one of each to warm up ->
+ * ms[2] = milliseconds per analysis launch, per candidate launch of `rows` rows. */
+int fb_bench_kv_kernels(fb_engine *e, const int16_t *x, int64_t N, int W, const int32_t *tables, const int *q, int rows, int reps,
+                        double *ms);
+
 /* What the front end of the last batch ran (fb_score_*, fb_get_grad, an NES iteration, fb_debug_mfcc / _feats, enrolment
  * statistics): info[5] = {the MFCC kernel, the chain after it, where the CompressedMatrix round trip ran, the longest
  * utterance of the batch in frames, the batch size}.  Recorded on the host when the kernels are enqueued; read only.
