@@ -6,6 +6,7 @@
 // through pinned memory; nothing else crosses PCIe inside the attack loop.
 #include <float.h>
 #include <algorithm>
+#include <atomic>
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -175,8 +176,15 @@ struct fb_engine {
   bool fin_xch_clean = false;  // fin_xch holds sentinels everywhere (k_gmm_finalize_loss_update's exchange slots)
   unsigned vad_p_launches = 0;  // launches of k_vad_delta_cmvn_p on vad_part since its sentinel fill (its slot sets alternate with them)
   FbCtlDev *h_ctl = nullptr;  // pinned
-  hipEvent_t evg_ring[2 * 16] = {};
-  int evg_n = 0;
+  // attack_loop without the drain between looks: the control block of batch n lands in h_look[n & 1] and ev_look[n & 1] says
+  // when, while batch n + 1 is already queued; what the host has read is then copied into h_ctl
+  FbCtlDev *h_look[2] = {nullptr, nullptr};  // pinned
+  hipEvent_t ev_look[2] = {nullptr, nullptr};
+  // two banks of event pairs: the launches of the batch being queued record into bank evg_cur while the other bank's batch
+  // may still be running
+  hipEvent_t evg_ring[2][2 * 16] = {};
+  int evg_n[2] = {0, 0};
+  int evg_cur = 0;
   int t_max = 0;
   std::vector<int32_t> h_frame_rec;
   int uni_T = 0;        // frames per utterance when every utterance of the batch has the same length (NES batches), else 0
@@ -273,6 +281,18 @@ static int d2h(fb_engine *e, void *dst, const void *src_dev, size_t n) {
   return FB_OK;
 }
 
+// The engines of this process on one device whose chain is the shared-GPU one (fb_set_fused_chain(e, 0)): what the drivers
+// set on every engine when three or more attacks share a GPU.  From three on the attack loop does not drain its stream
+// between looks (loop_knobs, attack_loop): there a stopping attack's extra batch of empty launches is cheap beside what the
+// other attacks run meanwhile.  A lone engine on that chain keeps its drained looks, like every lone attack: it queues
+// exactly the looks it reads.
+static std::atomic<int> g_shared_chain[64];
+static int shared_chain_count(int device, int delta) {
+  std::atomic<int> &c = g_shared_chain[device & 63];
+  return delta ? c.fetch_add(delta) + delta : c.load();
+}
+static bool fb_shared_gpu(const fb_engine *e) { return e->fuse_opt == 0 && shared_chain_count(e->device, 0) >= 3; }
+
 // ------------------------------------------------------------------ create
 extern "C" int fb_engine_create(int device, fb_engine **out) {
   if (!out) return fb_fail(FB_E_ARG, "out is NULL");
@@ -285,8 +305,12 @@ extern "C" int fb_engine_create(int device, fb_engine **out) {
   HIPCHK(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
   HIPCHK(hipEventCreate(&e->ev0));
   HIPCHK(hipEventCreate(&e->ev1));
-  for (hipEvent_t &ev : e->evg_ring) HIPCHK(hipEventCreate(&ev));
+  for (auto &bank : e->evg_ring) for (hipEvent_t &ev : bank) HIPCHK(hipEventCreate(&ev));
   HIPCHK(hipHostMalloc((void **)&e->h_ctl, sizeof(FbCtlDev), hipHostMallocDefault));
+  for (int i = 0; i < 2; ++i) {
+    HIPCHK(hipHostMalloc((void **)&e->h_look[i], sizeof(FbCtlDev), hipHostMallocDefault));
+    HIPCHK(hipEventCreateWithFlags(&e->ev_look[i], hipEventDisableTiming));
+  }
   HIPCHK(hipHostMalloc((void **)&e->h_out, sizeof(FbNesDev), hipHostMallocDefault));
   fb_frontend_cfg cfg;
   fb_default_frontend(&cfg);
@@ -304,8 +328,13 @@ extern "C" int fb_engine_destroy(fb_engine *e) {
   if (e->h_tv) (void)hipHostFree(e->h_tv);
   if (e->ev0) (void)hipEventDestroy(e->ev0);
   if (e->ev1) (void)hipEventDestroy(e->ev1);
-  for (hipEvent_t ev : e->evg_ring) if (ev) (void)hipEventDestroy(ev);
+  for (auto &bank : e->evg_ring) for (hipEvent_t ev : bank) if (ev) (void)hipEventDestroy(ev);
   if (e->h_ctl) (void)hipHostFree(e->h_ctl);
+  for (int i = 0; i < 2; ++i) {
+    if (e->h_look[i]) (void)hipHostFree(e->h_look[i]);
+    if (e->ev_look[i]) (void)hipEventDestroy(e->ev_look[i]);
+  }
+  shared_chain_count(e->device, e->fuse_opt == 0 ? -1 : 0);
   if (e->pin) (void)hipHostFree(e->pin);
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;  // (the device buffers go with it: e->device is still the current one)
@@ -1220,30 +1249,36 @@ static bool fb_debug_sync_on() {
 
 // HIP-event timing of the dominant kernel (bench only): a ring of event pairs, because several
 // iterations may be queued before the host looks at the stream again
-static int time_collect(fb_engine *e) {
-  for (int i = 0; i < e->evg_n; ++i) {
+// (one bank: its launches have completed, the other bank's need not have)
+static int time_collect_bank(fb_engine *e, int bank) {
+  for (int i = 0; i < e->evg_n[bank]; ++i) {
     float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e->evg_ring[2 * i], e->evg_ring[2 * i + 1]));
+    HIPCHK(hipEventElapsedTime(&ms, e->evg_ring[bank][2 * i], e->evg_ring[bank][2 * i + 1]));
     e->gmm_ms_acc += (double)ms;
     e->gmm_launches += 1;
   }
-  e->evg_n = 0;
-  e->gmm_pending = false;
+  e->evg_n[bank] = 0;
+  e->gmm_pending = e->evg_n[0] + e->evg_n[1] > 0;
   return FB_OK;
+}
+// (the stream is idle: both banks)
+static int time_collect(fb_engine *e) {
+  FBCHK(time_collect_bank(e, 0));
+  return time_collect_bank(e, 1);
 }
 static int time_begin(fb_engine *e, int what = 1) {
   if (e->time_gmm != what) return FB_OK;
-  if (e->evg_n >= 16) {  // ring full: drain (never happens with the batch sizes used)
+  if (e->evg_n[e->evg_cur] >= 16) {  // ring full: drain (never happens with the batch sizes used)
     FBCHK(sync_stream(e));
     FBCHK(time_collect(e));
   }
-  HIPCHK(hipEventRecord(e->evg_ring[2 * e->evg_n], e->stream));
+  HIPCHK(hipEventRecord(e->evg_ring[e->evg_cur][2 * e->evg_n[e->evg_cur]], e->stream));
   return FB_OK;
 }
 static int time_end(fb_engine *e, int what = 1) {
   if (e->time_gmm != what) return FB_OK;
-  HIPCHK(hipEventRecord(e->evg_ring[2 * e->evg_n + 1], e->stream));
-  e->evg_n += 1;
+  HIPCHK(hipEventRecord(e->evg_ring[e->evg_cur][2 * e->evg_n[e->evg_cur] + 1], e->stream));
+  e->evg_n[e->evg_cur] += 1;
   e->gmm_pending = true;
   return FB_OK;
 }
@@ -2280,6 +2315,13 @@ static bool fb_fuse_part(const fb_engine *e, int part) {
   // (Not with the CompressedMatrix round trip on: its phase lives in the one-workgroup-per-utterance kernel, which a
   //  shared GPU does not take well -- the reference-pipeline secondary fell from 10.6 to 8.7 k it/s with it.)
   if ((part == 2 || (part == 0 && !e->cfg.compress_feats)) && e->fuse_opt == 0 && getenv("FB_NO_FUSE") == nullptr) return true;
+  // (The finalisation's once more, in an experiment that is not in this tree: k_gmm_finalize_loss<true> under an occupancy
+  //  bound of six waves per SIMD, which the compiler then reported at 75 registers per wave, so that it fits beside a resident
+  //  k_gmm_fx2w workgroup, the update a launch of its own: 12.85 - 12.93 k it/s against 13.07 - 13.13 k -- the one launch
+  //  took 23.3 us where k_gmm_finalize + k_loss take 9.7 + 9.1.  DESIGN.md section 6, the change itself as it was measured in
+  //  docs/experiments/fused_finalize_bound.diff (kept for the record like the others there; nothing builds it).
+  //  FB_FUSE_PARTS=7 FB_FUSE_UPD=0 runs
+  //  the same five launches with the kernel as it is here, unbounded at 119 registers.)
   return fb_fuse_on(e);
 }
 static bool fb_fuse_on(const fb_engine *e) {
@@ -2310,6 +2352,7 @@ struct FbLoopKnobs {
   bool fin_ticket = false;  // FB_FIN_TICKET=1: the finalising launch's roles by an arrival ticket
   bool fin_xch = false;     // its exchange slots (FB_FIN_COUNTER=1: the arrival counter instead)
   int upd_threads = 512;    // threads of a k_update_perturb(_x) workgroup (choose_update_threads)
+  bool look_ahead = false;  // batch n + 1 is queued before the host waits for batch n's control block (FB_LOOK_AHEAD=0 | 1)
 };
 static FbLoopKnobs loop_knobs(const fb_engine *e, const FbScorer &sc) {
   FbLoopKnobs k;
@@ -2327,6 +2370,10 @@ static FbLoopKnobs loop_knobs(const fb_engine *e, const FbScorer &sc) {
     k.fuse_upd = fb_fuse_part(e, 2);
     const char *fu = getenv("FB_FUSE_UPD");
     k.upd_in_fin = !(fu && fu[0] == '0');
+    // No drain between looks once three engines share the device; FB_LOOK_AHEAD=0: the draining loop,
+    // = 1: for a lone attack as well.  A stopping attack queues one more batch of launches that return on the stop flag.
+    const char *la = getenv("FB_LOOK_AHEAD");
+    k.look_ahead = la ? la[0] == '1' : fb_shared_gpu(e);
     const char *tk = getenv("FB_FIN_TICKET");
     k.fin_ticket = tk && tk[0] == '1';
     k.fin_xch = getenv("FB_FIN_COUNTER") == nullptr;
@@ -2709,10 +2756,8 @@ static int attack_loop(fb_engine *e, const fb_nes_params *p, int64_t N, const Fb
   FbCtlDev *ctl = e->ctl.as<FbCtlDev>();
   int ndp = 0;              // FB_SCORER_DEV: the distance partials of the batch the previous iteration's update wrote
   bool have_batch = false;  // ... if it wrote one
-  for (int done = 0; done < count;) {
-    const int nb = count - done < kn.look ? count - done : kn.look;
-    for (int k = 0; k < nb; ++k) {
-      const int it = it_base + done + k;
+  auto queue_iteration = [&](const int it) -> int {
+    {
       const double *noise_dev = nullptr;
       if (noise_all && half > 0) {
         FBCHK(h2d(e, e->noise.p, noise_all + (size_t)it * N * half, sizeof(double) * (size_t)N * half));
@@ -2784,16 +2829,73 @@ static int attack_loop(fb_engine *e, const fb_nes_params *p, int64_t N, const Fb
         e->nes_route[FB_NES_ROUTE_K_GRAD_UPDATE] += 1;
       }
     }
-    HIPCHK(hipMemcpyAsync(e->h_ctl, ctl, sizeof(FbCtlDev), hipMemcpyDeviceToHost, e->stream));
-    FBCHK(sync_stream(e));
-    if (sc.kind == FB_SCORER_NATIVE && e->gmm_pending) FBCHK(time_collect(e));
+    return FB_OK;
+  };
+  // The engine's own systems on Philox noise: batch n + 1 is queued BEFORE the host waits for batch n's control block, so the
+  // stream never runs dry at a look (one stream synchronisation and the relaunch of an empty stream per look otherwise:
+  // DESIGN.md section 7).  Two pinned copies of the block and an event each; the timing events alternate between two banks
+  // with them.  Kernels queued behind the stopping iteration return on the stop flag and leave the block as it is, so the
+  // block of the last batch waited for is the attack's final one.  Uploaded normals (e->noise is rewritten per iteration
+  // from the host), a host callback and a foreign model on the device (every batch queued is a query of the victim) keep
+  // the draining loop.
+  const bool ahead = kn.look_ahead && sc.kind == FB_SCORER_NATIVE && !noise_all;
+  int waiting = -1;  // the copy (and timing bank) of the batch the host has not looked at yet
+  bool stop = false;
+  // a failed call ends the attack: nothing of it stays in flight (the batch queued ahead included), and the next call
+  // records its timing events into bank 0 again
+  auto abandon = [&](int rc) {
+    e->evg_cur = 0;
+    (void)hipStreamSynchronize(e->stream);
+    return rc;
+  };
+  for (int queued = 0, n = 0; (queued < count && !stop) || waiting >= 0; ++n) {
+    int cur = -1;
+    if (queued < count && !stop) {
+      const int nb = count - queued < kn.look ? count - queued : kn.look;
+      cur = ahead ? (n & 1) : 0;
+      e->evg_cur = cur;
+      int rc = FB_OK;
+      for (int k = 0; k < nb && rc == FB_OK; ++k) rc = queue_iteration(it_base + queued + k);
+      hipError_t he = hipSuccess;
+      if (rc == FB_OK) he = hipMemcpyAsync(ahead ? e->h_look[cur] : e->h_ctl, ctl, sizeof(FbCtlDev), hipMemcpyDeviceToHost, e->stream);
+      if (rc == FB_OK && he == hipSuccess && ahead) he = hipEventRecord(e->ev_look[cur], e->stream);
+      if (rc != FB_OK || he != hipSuccess) {
+        (void)abandon(rc);
+        HIPCHK(he);
+        return rc;
+      }
+      queued += nb;
+    }
+    const int look_at = ahead ? waiting : cur;
+    waiting = ahead ? cur : -1;
+    if (look_at < 0) continue;  // (the first batch of a loop that looks ahead: nothing to wait for yet)
+    if (ahead) {
+      const hipError_t he = hipEventSynchronize(e->ev_look[look_at]);
+      if (he != hipSuccess) {
+        (void)abandon(FB_OK);
+        HIPCHK(he);
+      }
+      *e->h_ctl = *e->h_look[look_at];
+    } else {
+      FBCHK(sync_stream(e));
+    }
+    if (sc.kind == FB_SCORER_NATIVE && e->evg_n[look_at] > 0) {
+      const int rc = time_collect_bank(e, look_at);
+      if (rc != FB_OK) return abandon(rc);
+    }
     // err on a foreign path is never set: k_loss sets it only when it has the voiced-frame counts (tv), and only the
     // native systems pass them (fb_nes_device.h)
-    if (e->h_ctl->err != 0)
+    if (e->h_ctl->err != 0) {
+      e->evg_cur = 0;
+      if (waiting >= 0) {  // the batch queued ahead returns on the stop flag the error set
+        FBCHK(sync_stream(e));
+        FBCHK(time_collect(e));
+      }
       return fb_fail(FB_E_NO_VOICED, "NES sample %d has no voiced frames", e->h_ctl->err - 1);
-    done += nb;
-    if (e->h_ctl->stop) break;
+    }
+    if (e->h_ctl->stop) stop = true;
   }
+  e->evg_cur = 0;
   return FB_OK;
 }
 
@@ -3534,7 +3636,15 @@ extern "C" int fb_debug_gmm_acc_rows(fb_engine *e, const float *feats, int T, fl
 
 extern "C" int fb_set_fused_chain(fb_engine *e, int on) {
   if (!e) return fb_fail(FB_E_ARG, "null engine");
-  e->fuse_opt = on < 0 ? -1 : (on ? 1 : 0);
+  const int opt = on < 0 ? -1 : (on ? 1 : 0);
+  shared_chain_count(e->device, (opt == 0) - (e->fuse_opt == 0));
+  e->fuse_opt = opt;
+  return FB_OK;
+}
+
+extern "C" int fb_debug_shared_chain_engines(fb_engine *e, int *count) {
+  if (!e || !count) return fb_fail(FB_E_ARG, "null argument");
+  *count = shared_chain_count(e->device, 0);
   return FB_OK;
 }
 

@@ -895,8 +895,15 @@ class Engine(object):
 
     def set_fused_chain(self, on):
         """True: 4 launches per NES iteration (best for one or two attacks per GPU); False: 6 launches, finalisation and loss on their own (better
-        with >= 3 engines sharing a GPU); None: library default.  Same trajectories (fb_set_fused_chain)."""
+        with >= 3 engines sharing a GPU -- and once three engines on the device are set to it, no drain between looks:
+        debug_shared_chain_engines); None: library default.  Same trajectories (fb_set_fused_chain)."""
         N.check(self._L.fb_set_fused_chain(self._h, C.c_int(-1 if on is None else (1 if on else 0))))
+
+    def debug_shared_chain_engines(self):
+        """Engines of this process on this engine's device with set_fused_chain(False) (fb_debug_shared_chain_engines)."""
+        n = C.c_int()
+        N.check(self._L.fb_debug_shared_chain_engines(self._h, C.byref(n)))
+        return n.value
 
     def bench_nes(self, params, audio, warmup, iters, time_gmm=False):
         """Runs warmup+iters NES iterations (identical work to attack(), early stop disabled).

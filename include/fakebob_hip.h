@@ -665,7 +665,11 @@ int fb_attack_dev(fb_engine *e, const fb_nes_params *p, int S, const fb_dev_mode
  * attacks per GPU, the reference's own use; on = 0: 6 launches -- finalisation and loss on their own, the front-end kernel at its own LDS size --, which interleave
  * better when several engines share a GPU (3 or more attacks in flight: +7 % NES iterations/s, profiles/r05_*;
  * FB_NO_FUSE=1: all 8); -1: default (fused unless
- * FB_NO_FUSE is set).  Trajectories are bit-identical either way. */
+ * FB_NO_FUSE is set).  Once three or more engines of the process on one device are set to 0 -- the shared GPU itself --
+ * their attacks queue the next look's iterations before they wait for the last look's control block (FB_LOOK_AHEAD=0:
+ * not; = 1: every attack of the engine's own systems on Philox noise), so that a stream does not run dry at a look; an
+ * attack that stops has then queued one more look of launches, which return on the stop flag.  Trajectories are
+ * bit-identical either way. */
 int fb_set_fused_chain(fb_engine *e, int on);
 
 /* Work counters since engine creation: what the driver reduces over ranks next to the success counter

@@ -175,6 +175,9 @@ int fb_debug_frontend_route(fb_engine *e, int *info);
  * that batch reports zeros.  Recorded on the host when the kernels are enqueued; read only.  FB_E_STATE before the first
  * batch. */
 int fb_debug_launch_shape(fb_engine *e, int *info);
+/* The engines of this process on e's device whose chain is the shared-GPU one (fb_set_fused_chain(e, 0)), e included when its
+ * own is: from three on, such an engine's next attack does not drain its stream between looks (FB_LOOK_AHEAD). */
+int fb_debug_shared_chain_engines(fb_engine *e, int *count);
 #define FB_SHAPE_GMM_NONE 0
 #define FB_SHAPE_GMM_FX2W 1          /* k_gmm_fx2w */
 #define FB_SHAPE_GMM_FX2 2           /* k_gmm_fx2 */
