@@ -195,10 +195,13 @@ def main(argv=None, model_factory=None, bob_factory=None):
                     help="universal perturbation: the next N utterances of the same speaker in the data directory ride along "
                          "with every attacked one (1 .. 31, times --eot-size at most 32); all are cropped to the shortest, "
                          "which is printed; default: 0")
-    ap.add_argument("--attack", default="nes", choices=["nes", "pso", "kenansville"],
+    ap.add_argument("--attack", default="nes", choices=["nes", "pso", "kenansville", "pgd"],
                     help="the search: FAKEBOB's NES gradient estimate (default), SirenAttack's particle swarm "
-                         "(fakebob_amd/pso.py; -epsilon, -max_iter, -adver and --seed apply, the other NES options do not) or "
-                         "Kenansville's decision-only spectral removal (fakebob_amd/kenansville.py; --kv-* and --seed apply)")
+                         "(fakebob_amd/pso.py; -epsilon, -max_iter, -adver and --seed apply, the other NES options do not), "
+                         "Kenansville's decision-only spectral removal (fakebob_amd/kenansville.py; --kv-* and --seed apply) or the "
+                         "white-box gradient attack (fakebob_amd/pgd.py: the analytic gradient of a GMM-UBM system in FAKEBOB's "
+                         "loop; -momentum 0 is PGD, -max_iter 1 the single step; -samples and -sigma do not apply; an undefended "
+                         "victim only)")
     ap.add_argument("--kv-window", dest="kv_window", default=100, type=int, help="--attack kenansville: samples per window (8 .. 128)")
     ap.add_argument("--kv-grid", dest="kv_grid", default=15, type=int, help="--attack kenansville: candidates per round (1 .. 64)")
     ap.add_argument("--kv-max-factor", dest="kv_max_factor", default=1.0, type=float,
@@ -227,6 +230,18 @@ def main(argv=None, model_factory=None, bob_factory=None):
             ap.error("--attack kenansville does not run under expectation over transformation (--eot-size %d)" % args.eot_size)
         if args.companions > 0:
             ap.error("--attack kenansville does not take companion utterances (--companions %d)" % args.companions)
+
+    if args.attack == "pgd":      # likewise: the gradient is that of an undefended GMM-UBM victim (no BPDA, no EOT in this version)
+        if args.architecture != "gmm":
+            ap.error("--attack pgd differentiates GMM-UBM systems only (--architecture %s)" % args.architecture)
+        if args.eot_size is not None and args.eot_size > 1:
+            ap.error("--attack pgd does not run under expectation over transformation (--eot-size %d)" % args.eot_size)
+        if args.companions > 0:
+            ap.error("--attack pgd does not take companion utterances (--companions %d)" % args.companions)
+        for flag, val in (("--input-transform", args.input_transform), ("--air-channel", args.air_channel),
+                          ("--codec", None if args.codec == "none" else args.codec), ("--feco", args.feco), ("--dither", args.dither)):
+            if val is not None:
+                ap.error("--attack pgd attacks an undefended victim: %s %s is not differentiated in this version" % (flag, val))
 
     task, attack_type, spk_id_list = args.task, args.attack_type, args.speaker_id
     if task == "SV":                      # SV only supports one enrolled speaker (:449-451)
@@ -271,7 +286,13 @@ def main(argv=None, model_factory=None, bob_factory=None):
                   w_init=args.pso_w[0], w_end=args.pso_w[1], c1=args.pso_c[0], c2=args.pso_c[1], v_max=args.pso_vmax)
     if args.attack == "kenansville":
         hp = dict(window=args.kv_window, grid=args.kv_grid, max_factor=args.kv_max_factor)
-    if bob_factory is None and args.attack == "kenansville":
+    if args.attack == "pgd":
+        hp = dict(adver_thresh=args.adver_thresh, epsilon=args.epsilon, max_iter=args.max_iter, max_lr=args.max_lr,
+                  min_lr=args.min_lr, momentum=args.momentum, plateau_length=args.plateau_length, plateau_drop=args.plateau_drop)
+    if bob_factory is None and args.attack == "pgd":
+        from .pgd import PGD
+        bobs = [PGD(task, attack_type, m, seed=seed, verbose=False, **hp) for m in models]
+    elif bob_factory is None and args.attack == "kenansville":
         from .kenansville import Kenansville
         bobs = [Kenansville(task, attack_type, m, seed=seed, verbose=False, **hp) for m in models]
     elif bob_factory is None and args.attack == "pso":

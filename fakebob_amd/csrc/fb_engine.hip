@@ -209,6 +209,12 @@ struct fb_engine {
   DevBuf kv_x, kv_best, kv_tab;         // fb_attack_kenansville: the int16 cast of the audio [N], the candidate of hi [N], the four tables [4][W]
   DevBuf kv_ma, kv_mb, kv_cum, kv_E;    // ... the analysis: m a, m b [nw][K] int32, cum [nw][K] and E [nw] int64
   DevBuf kv_look;                       // ... and what its host reads per round: {FbNesDev, loss[G], scores[G][S], tv[G]}
+  // white-box gradients (fb_get_grad_wb / fb_attack_wb): fb_load_gmm's plain float32 parameters, kept on the host and uploaded
+  // by the first white-box call after the load; the weights w[M], the GMM backward's per-model rows and the cotangent g on the
+  // compacted rows, the front-end backward's float64 stages, a status word (1: the recomputed voiced mask is not the forward's)
+  std::vector<float> h_wb_gc, h_wb_miv, h_wb_iv;
+  bool wb_uploaded = false;
+  DevBuf wb_gc, wb_miv, wb_iv, wb_w, wb_part, wb_g, wb_rank, wb_dcm, wb_ddf, wb_dmf, wb_dxf, wb_status;
   FbNesDev *h_out = nullptr;  // pinned
   int *h_tv = nullptr;        // pinned, grows
   size_t h_tv_cap = 0;
@@ -1111,6 +1117,12 @@ extern "C" int fb_load_gmm(fb_engine *e, int M, int C, int D, const float *gcons
   g.anchor = g.delta_p ? e->gmm_anchor.as<float>() : nullptr;
   g.item_model = e->gmm_items.as<int>();
   g.item_model_host_q_first = (G == 1) ? 1 : 0;  // one group: the list built above is {Q, 0, 1, ..., M-1}
+  // the white-box path differentiates the plain parameters: kept here, uploaded by its first call, freed on reload
+  e->h_wb_gc.assign(gconsts, gconsts + (size_t)M * C);
+  e->h_wb_miv.assign(miv, miv + (size_t)M * C * D);
+  e->h_wb_iv.assign(iv, iv + (size_t)M * C * D);
+  e->wb_uploaded = false;
+  e->wb_gc.release(); e->wb_miv.release(); e->wb_iv.release();
   e->n_groups = G;
   e->have_gmm = true;
   e->kind = 0;
@@ -2981,6 +2993,194 @@ extern "C" int fb_attack_dev(fb_engine *e, const fb_nes_params *p, int S, const 
                     trace, n_trace, success_flag);
 }
 
+// ------------------------------------------------- white-box gradients: fb_get_grad_wb / fb_attack_wb
+// The analytic gradient of the loss with respect to the samples ("white-box gradients" in fakebob_hip.h): GMM-UBM systems on
+// an undefended victim.  Everything else is refused by name.
+static int wb_check(fb_engine *e, const fb_nes_params *p, const double *audio, int64_t N, fb_nes_params *q) {
+  if (!e || !p || !audio) return fb_fail(FB_E_ARG, "null argument");
+  if (!e->have_gmm) return fb_fail(FB_E_STATE, "no model loaded");
+  if (e->kind != 0) return fb_fail(FB_E_STATE, "white-box gradients: an i-vector system is loaded (GMM-UBM systems only in this version)");
+  if (e->eot > 1) return fb_fail(FB_E_STATE, "white-box gradients: fb_set_eot(%d) is in force (set 1)", e->eot);
+  if (e->comp_K1 > 0) return fb_fail(FB_E_STATE, "white-box gradients: companions are set (fb_set_companions: clear them)");
+  if (e->tf.n > 0) return fb_fail(FB_E_STATE, "white-box gradients: an input-transform chain is set (no BPDA through defences in this version)");
+  if (e->air.L > 0) return fb_fail(FB_E_STATE, "white-box gradients: an air channel is set (fb_set_air_channel: clear it)");
+  if (e->codec != FB_CODEC_NONE) return fb_fail(FB_E_STATE, "white-box gradients: a codec is set (fb_set_codec: clear it)");
+  if (e->feco_iters > 0) return fb_fail(FB_E_STATE, "white-box gradients: feature compression is on (fb_set_feature_compression: switch it off)");
+  if (e->cfg.dither > 0.0) return fb_fail(FB_E_STATE, "white-box gradients: dither %g > 0 (the function is differentiated at a fixed victim)", e->cfg.dither);
+  // one row is scored per iteration; the NES-only fields are not read
+  *q = *p;
+  q->samples_per_draw = 0;
+  q->sigma = 1.0;
+  return check_params(e, q, N);
+}
+
+// the plain parameters on the device (once per fb_load_gmm) and the workspace of one utterance of N samples / T frames
+static int wb_prepare(fb_engine *e, int64_t N, int T, bool need_gmm) {
+  const FbFrontendDev &fe = e->fe;
+  if (need_gmm) {
+    const FbGmmDev &g = e->gmm;
+    if (!e->wb_uploaded) {
+      FBCHK(e->wb_gc.ensure(sizeof(float) * e->h_wb_gc.size()));
+      FBCHK(e->wb_miv.ensure(sizeof(float) * e->h_wb_miv.size()));
+      FBCHK(e->wb_iv.ensure(sizeof(float) * e->h_wb_iv.size()));
+      FBCHK(sync_stream(e));
+      HIPCHK(hipMemcpy(e->wb_gc.p, e->h_wb_gc.data(), sizeof(float) * e->h_wb_gc.size(), hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(e->wb_miv.p, e->h_wb_miv.data(), sizeof(float) * e->h_wb_miv.size(), hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(e->wb_iv.p, e->h_wb_iv.data(), sizeof(float) * e->h_wb_iv.size(), hipMemcpyHostToDevice));
+      e->wb_uploaded = true;
+    }
+    FBCHK(e->wb_w.ensure(sizeof(double) * (size_t)g.M));
+    FBCHK(e->wb_part.ensure(sizeof(float) * (size_t)g.M * T * g.D));
+  }
+  FBCHK(e->wb_g.ensure(sizeof(double) * (size_t)T * fe.dim));
+  FBCHK(e->wb_rank.ensure(sizeof(int) * (size_t)T));
+  FBCHK(e->wb_dcm.ensure(sizeof(double) * (size_t)T * fe.dim));
+  FBCHK(e->wb_ddf.ensure(sizeof(double) * (size_t)T * fe.dim));
+  FBCHK(e->wb_dmf.ensure(sizeof(double) * (size_t)T * fe.nc));
+  FBCHK(e->wb_dxf.ensure(sizeof(double) * (size_t)T * fe.L));
+  FBCHK(e->grad.ensure(sizeof(double) * (size_t)N));
+  if (!e->wb_status.p) FBCHK(e->wb_status.ensure(sizeof(int)));
+  HIPCHK(hipMemsetAsync(e->wb_status.p, 0, sizeof(int), e->stream));
+  return FB_OK;
+}
+
+// the GMM backward on the n rows (*n_rows_ptr <= T) of e->feats with the weights in e->wb_w: the cotangent lands in e->wb_g
+static void wb_launch_gmm_backward(fb_engine *e, const int *n_rows_ptr, int T, const int *stop) {
+  const FbGmmDev &g = e->gmm;
+  fb_launch_wb_gmm_backward(e->stream, g.M, g.C, g.D, e->wb_gc.as<float>(), e->wb_miv.as<float>(), e->wb_iv.as<float>(),
+                            e->feats.as<float>(), n_rows_ptr, T, e->wb_w.as<double>(), e->wb_part.as<float>(), e->wb_g.as<double>(),
+                            stop);
+}
+// the front-end backward of the utterance in e->wav (N samples, T frames, its MFCC matrix in e->mfcc): e->grad = scale * the
+// cotangent on the int16 samples
+static void wb_launch_frontend_vjp(fb_engine *e, int64_t N, int T, double scale, const int *stop) {
+  fb_launch_wb_frontend_vjp(e->stream, e->fe, e->wav.as<int16_t>(), N, T, e->mfcc.as<float>(), e->wb_g.as<double>(), e->tv.as<int>(),
+                            e->wb_rank.as<int>(), e->wb_dcm.as<double>(), e->wb_ddf.as<double>(), e->wb_dmf.as<double>(),
+                            e->wb_dxf.as<double>(), scale, e->grad.as<double>(), e->wb_status.as<int>(), stop);
+}
+
+// One white-box iteration on the device-resident adver, asynchronous: the forward of fb_get_grad on ONE row -- the cast
+// (k_perturb without noise), the scoring chain, k_loss --, then the weights (and, with ctl, the loop control), the GMM
+// backward and the front-end backward.  q: the call's parameters with samples_per_draw = 0.
+static int wb_enqueue(fb_engine *e, const fb_nes_params *q, int64_t N, uint32_t it, bool with_dist, FbCtlDev *ctl, double *trace_dev) {
+  const int *stop = ctl ? &ctl->stop : nullptr;
+  int ndp = 0;
+  fb_launch_perturb(e->stream, e->adver.as<double>(), with_dist ? e->audio.as<double>() : nullptr, N, 0, q->sigma, q->seed, it,
+                    q->stream, nullptr, e->wav.as<int16_t>(), e->dist_part.as<double>(), &ndp, nullptr, stop, nes_bits(q));
+  e->pre_iter = -1;
+  FbScoreCall call{FbRngPoint{q->seed, q->stream, it, 0}};
+  call.stop = stop;
+  const int T = e->h_frame_off[1];
+  FBCHK(run_scoring(e, call, 1, T));
+  fb_launch_loss(e->stream, e->raw.as<double>(), e->tv.as<int>(), 1, e->n_out, q->task, e->kind, q->attack_type,
+                 e->zmean.as<double>(), e->zstd.as<double>(), q->threshold, q->adver_thresh, q->target, q->true_label,
+                 e->dist_part.as<double>(), with_dist ? ndp : 0, e->scores.as<double>(), e->loss.as<double>(),
+                 e->nes_out.as<FbNesDev>());
+  e->nes_route[FB_NES_ROUTE_K_LOSS] += 1;
+  fb_launch_wb_ctl(e->stream, e->scores.as<double>(), e->nes_out.as<FbNesDev>(), e->gmm.M, q->task, q->attack_type,
+                   e->zstd.as<double>(), q->threshold, q->target, q->true_label, e->wb_w.as<double>(), ctl, trace_dev, (int)it);
+  wb_launch_gmm_backward(e, e->row_off.as<int>() + 1, T, stop);
+  wb_launch_frontend_vjp(e, N, T, ldexp(1.0, nes_bits(q) - 1), stop);
+  return FB_OK;
+}
+
+static int wb_status_check(fb_engine *e, int status) {
+  if (status != 0) return fb_fail(FB_E_HIP, "white-box gradients: the voiced mask recomputed by the backward is not the forward's");
+  return FB_OK;
+}
+
+// mirrors FakeBob.get_grad + loss_fn (FAKEBOB.py:223-299) with the analytic gradient in place of the NES estimate
+extern "C" int fb_get_grad_wb(fb_engine *e, const fb_nes_params *p, const double *audio, int64_t N, double *adver_loss,
+                              double *grad, double *score0) {
+  if (e) e->bench_it = -1;
+  if (e) memset(e->nes_route, 0, sizeof(e->nes_route));
+  fb_nes_params q;
+  FBCHK(wb_check(e, p, audio, N, &q));
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(prepare_nes_replicas(e, N, 1));
+  FBCHK(ensure_nes_buffers(e, N, 1));
+  FBCHK(wb_prepare(e, N, e->h_frame_off[1], true));
+  FBCHK(h2d(e, e->adver.p, audio, sizeof(double) * (size_t)N));
+  FBCHK(wb_enqueue(e, &q, N, 0, false, nullptr, nullptr));
+  int status = 0;
+  if (grad) FBCHK(d2h(e, grad, e->grad.p, sizeof(double) * (size_t)N));
+  FBCHK(d2h(e, &status, e->wb_status.p, sizeof(int)));
+  FBCHK(fetch_out(e, true));
+  HIPCHK(hipGetLastError());
+  FBCHK(wb_status_check(e, status));
+  e->nes_iters += 1;
+  if (adver_loss) *adver_loss = e->h_out->adver_loss;
+  if (score0) for (int s = 0; s < fb_num_speakers(e); ++s) score0[s] = e->h_out->score0[s];
+  return FB_OK;
+}
+
+// mirrors FakeBob.attack (FAKEBOB.py:139-221) with the analytic gradient in place of get_grad: the loop control runs on the
+// device (k_wb_ctl), the host looks at the control block once per FB_ATTACK_BATCH iterations, as attack_loop does
+extern "C" int fb_attack_wb(fb_engine *e, const fb_nes_params *p, const double *audio, int64_t N, int16_t *adv_i16,
+                            double *adver_f64, double *trace, int *n_trace, int *success_flag) {
+  if (e) e->bench_it = -1;
+  if (e) memset(e->nes_route, 0, sizeof(e->nes_route));
+  if (!adv_i16 || !success_flag) return fb_fail(FB_E_ARG, "null argument");
+  fb_nes_params q;
+  FBCHK(wb_check(e, p, audio, N, &q));
+  if (p->max_iter <= 0) return fb_fail(FB_E_ARG, "max_iter must be > 0");
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(prepare_nes_replicas(e, N, 1));
+  FBCHK(ensure_nes_buffers(e, N, 1));
+  FBCHK(wb_prepare(e, N, e->h_frame_off[1], true));
+  const int S = fb_num_speakers(e);
+  FBCHK(attack_start(e, audio, N, 0, nullptr));
+  double *trace_dev = nullptr;
+  if (trace) {
+    FBCHK(e->trace_dev.ensure(sizeof(double) * (size_t)p->max_iter * (3 + S)));
+    trace_dev = e->trace_dev.as<double>();
+  }
+  FBCHK(e->ticks.ensure(sizeof(unsigned long long) * ((size_t)p->max_iter + 1)));
+  FBCHK(ctl_reset(e, &q, true, false, e->ticks.as<unsigned long long>()));
+  FbCtlDev *ctl = e->ctl.as<FbCtlDev>();
+  const char *ev = getenv("FB_ATTACK_BATCH");
+  const int b = ev ? atoi(ev) : 4;
+  const int look = b < 1 ? 1 : (b > 16 ? 16 : b);
+  const double one_minus_m = 1.0 - p->momentum;
+  for (int queued = 0; queued < p->max_iter;) {
+    const int nb = p->max_iter - queued < look ? p->max_iter - queued : look;
+    int rc = FB_OK, status = 0;
+    for (int k = 0; k < nb && rc == FB_OK; ++k) {
+      rc = wb_enqueue(e, &q, N, (uint32_t)(queued + k), true, ctl, trace_dev);
+      if (rc == FB_OK)
+        fb_launch_wb_update(e->stream, e->grad.as<double>(), N, p->momentum, one_minus_m, p->epsilon, e->audio.as<double>(),
+                            e->grad_m.as<double>(), e->adver.as<double>(), ctl);
+    }
+    hipError_t he = hipSuccess;
+    if (rc == FB_OK) he = hipMemcpyAsync(e->h_ctl, ctl, sizeof(FbCtlDev), hipMemcpyDeviceToHost, e->stream);
+    if (rc == FB_OK && he == hipSuccess) rc = d2h(e, &status, e->wb_status.p, sizeof(int));
+    if (rc != FB_OK || he != hipSuccess) {
+      (void)hipStreamSynchronize(e->stream);
+      HIPCHK(he);
+      return rc;
+    }
+    queued += nb;
+    FBCHK(sync_stream(e));
+    if (e->gmm_pending) FBCHK(time_collect(e));
+    FBCHK(wb_status_check(e, status));
+    if (e->h_ctl->err != 0) return fb_fail(FB_E_NO_VOICED, "the adversarial audio has no voiced frames");
+    if (e->h_ctl->stop) break;
+  }
+  HIPCHK(hipGetLastError());
+  const int rows = e->h_ctl->iters_done;  // one trace row per executed iteration, the stopping one included
+  e->nes_iters += rows;
+  FBCHK(collect_iter_seconds(e, rows));
+  if (trace && rows > 0) FBCHK(d2h(e, trace, trace_dev, sizeof(double) * (size_t)rows * (3 + S)));
+  const int last_iter = e->h_ctl->broke ? e->h_ctl->stop_iter : p->max_iter - 1;
+  *success_flag = (last_iter < p->max_iter - 1) ? 1 : -1;  // :219
+  if (n_trace) *n_trace = rows;
+  fb_launch_quantize(e->stream, e->adver.as<double>(), N, nes_bits(p), e->wav.as<int16_t>());  // :220
+  FBCHK(d2h(e, adv_i16, e->wav.p, sizeof(int16_t) * (size_t)N));
+  if (adver_f64) FBCHK(d2h(e, adver_f64, e->adver.p, sizeof(double) * (size_t)N));
+  FBCHK(sync_stream(e));
+  return FB_OK;
+}
+
 extern "C" int fb_debug_nes_route(fb_engine *e, int *info) {
   if (!e || !info) return fb_fail(FB_E_ARG, "null argument");
   for (int i = 0; i < FB_NES_ROUTE_N; ++i) info[i] = e->nes_route[i];
@@ -4123,6 +4323,55 @@ static int debug_feats(fb_engine *e, const int16_t *wav, int64_t n, const FbRngP
     HIPCHK(hipMemcpy(feats, e->feats.p, sizeof(float) * (size_t)tv * e->fe.dim, hipMemcpyDeviceToHost));
   *Tv = tv;
   if (T_out) *T_out = T;
+  return FB_OK;
+}
+
+// Test hook: the GMM backward alone -- the launches of wb_enqueue's k_wb_gmm_bwd / k_wb_sum_models -- on Tv rows of features
+// and weights w[M] handed in as they are; out[Tv][D] float64
+extern "C" int fb_debug_gmm_feat_grad(fb_engine *e, const float *feats, int Tv, const double *w, double *out) {
+  if (!e || !feats || !w || !out || Tv <= 0) return fb_fail(FB_E_ARG, "bad argument");
+  if (!e->have_gmm || e->kind != 0) return fb_fail(FB_E_STATE, "load a diagonal GMM system first");
+  HIPCHK(hipSetDevice(e->device));
+  const FbGmmDev &g = e->gmm;
+  FBCHK(sync_stream(e));
+  FBCHK(wb_prepare(e, 1, Tv, true));
+  FBCHK(e->feats.ensure(sizeof(float) * (size_t)Tv * g.D));
+  FBCHK(e->row_off.ensure(sizeof(int) * 2));
+  const int rows_host[2] = {0, Tv};
+  HIPCHK(hipMemcpy(e->feats.p, feats, sizeof(float) * (size_t)Tv * g.D, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(e->row_off.p, rows_host, sizeof(rows_host), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(e->wb_w.p, w, sizeof(double) * (size_t)g.M, hipMemcpyHostToDevice));
+  e->last_total_frames = 0;  // the feature buffer no longer belongs to a scored batch
+  wb_launch_gmm_backward(e, e->row_off.as<int>() + 1, Tv, nullptr);
+  FBCHK(d2h(e, out, e->wb_g.p, sizeof(double) * (size_t)Tv * g.D));
+  FBCHK(sync_stream(e));
+  HIPCHK(hipGetLastError());
+  return FB_OK;
+}
+
+// Test hook: the front-end backward alone -- the forward of fb_debug_feats, then wb_enqueue's front-end launches -- with a
+// cotangent cot[Tv][dim] on the compacted rows handed in: dwav[n] = d <cot, feats> / d wav (int16 units, float64) and the
+// voiced mask voiced[T] (0 / 1) the backward used
+extern "C" int fb_debug_frontend_vjp(fb_engine *e, const int16_t *wav, int64_t n, const double *cot, double *dwav,
+                                     unsigned char *voiced) {
+  if (!cot || !dwav) return fb_fail(FB_E_ARG, "bad argument");
+  FBCHK(debug_frontend(e, wav, n));
+  const int T = e->h_frame_off[1];
+  int tv = 0, status = 0;
+  FBCHK(d2h(e, &tv, e->tv.p, sizeof(int)));
+  FBCHK(sync_stream(e));
+  if (tv <= 0) return fb_fail(FB_E_NO_VOICED, "the utterance has no voiced frames");
+  FBCHK(wb_prepare(e, n, T, false));
+  FBCHK(h2d(e, e->wb_g.p, cot, sizeof(double) * (size_t)tv * e->fe.dim));
+  wb_launch_frontend_vjp(e, n, T, 1.0, nullptr);
+  std::vector<int> rank((size_t)T);
+  FBCHK(d2h(e, dwav, e->grad.p, sizeof(double) * (size_t)n));
+  FBCHK(d2h(e, rank.data(), e->wb_rank.p, sizeof(int) * (size_t)T));
+  FBCHK(d2h(e, &status, e->wb_status.p, sizeof(int)));
+  FBCHK(sync_stream(e));
+  HIPCHK(hipGetLastError());
+  FBCHK(wb_status_check(e, status));
+  if (voiced) for (int t = 0; t < T; ++t) voiced[t] = rank[t] >= 0 ? 1 : 0;
   return FB_OK;
 }
 

@@ -289,6 +289,30 @@ void fb_launch_grad_update(hipStream_t s, const double *loss, int64_t N, int hal
                            double momentum, double one_minus_m, double lr, double epsilon,
                            const double *audio, double *grad_m, double *adver, const FbCtlDev *ctl = nullptr);
 
+// ---- white-box gradients (fb_get_grad_wb / fb_attack_wb; whitebox_kernels.hip) --------------------------------------
+// w[M] = d loss / d raw[m] from row 0 of the loss launch's scores[S] (first-maximum subgradients) and, with ctl, FakeBob.attack's
+// loop control on out->adver_loss: the stop rule, the plateau rule (the window holds adver_loss), trace row `it`, the clock stamp.
+// A launch behind the stopping iteration returns at once, as every launch below does on `stop`
+void fb_launch_wb_ctl(hipStream_t s, const double *scores, const FbNesDev *out, int M, int task, int attack_type,
+                      const double *z_std, double threshold, int target, int true_label, double *w, FbCtlDev *ctl, double *trace,
+                      int it);
+// g[t][d] = (1 / Tv) sum_m w[m] sum_c gamma_mtc (miv_mc[d] - iv_mc[d] x_t[d]) on the Tv = *n_rows_ptr (<= rows_cap) rows of feats;
+// gc [M][C], miv / iv [M][C][D]: plain float32 parameters; part: [M][rows_cap][D] floats of workspace; models with w[m] == 0
+// are skipped, all zero gives exact zeros
+void fb_launch_wb_gmm_backward(hipStream_t s, int M, int C, int D, const float *gc, const float *miv, const float *iv,
+                               const float *feats, const int *n_rows_ptr, int rows_cap, const double *w, float *part, double *g,
+                               const int *stop);
+// grad[n] = scale * d <cot, feats(wav)> / d wav for ONE utterance of n samples / T frames whose MFCC matrix the forward left in
+// mfcc; cot [Tv][dim] on the compacted rows.  rank [T] (out: the voiced row of a frame or -1), dcm / ddf [T][dim], dmf [T][nc],
+// dxf [T][L]: float64 workspace.  tv_fwd (nullable): the forward's voiced count; *status = 1 if the mask recomputed here counts
+// differently
+void fb_launch_wb_frontend_vjp(hipStream_t s, const FbFrontendDev &fe, const int16_t *wav, int64_t n, int T, const float *mfcc,
+                               const double *cot, const int *tv_fwd, int *rank, double *dcm, double *ddf, double *dmf, double *dxf,
+                               double scale, double *grad, int *status, const int *stop);
+// FAKEBOB.py:193-203 on the gradient vector g with the step size of ctl
+void fb_launch_wb_update(hipStream_t s, const double *g, int64_t N, double momentum, double one_minus_m, double epsilon,
+                         const double *audio, double *grad_m, double *adver, const FbCtlDev *ctl);
+
 // ---- front-end ------------------------------------------------------------
 // MFCC of every frame of a (ragged) batch.  wav_off[B+1], frame_off[B+1] device arrays.
 // frame_rec: [total_frames][4] int32 = {absolute start sample (int64 in two words), start within the

@@ -528,6 +528,56 @@ class Engine(object):
                        C.byref(flag))
         return adv, flag.value, adv_f, trace[:nt.value]
 
+    # ---- white-box gradients (GMM-UBM systems on an undefended victim)
+    def get_grad_wb(self, params, audio, want_grad=True):
+        """fb_get_grad_wb: the analytic gradient of the loss at `audio` -> (grad (N,) float64 = d loss / d audio, in the
+        units of get_grad's estimate; adver_loss; score0 (S,)).  adver_loss and score0 are get_grad's own: the same forward.
+        samples_per_draw, sigma, seed and stream are not read.  Refused (NativeError, FB_E_STATE) for i-vector systems
+        and while an input transform, air channel, codec, feature compression, dither, EOT or companions are set."""
+        audio = np.ascontiguousarray(audio, np.float64).reshape(-1)
+        n = audio.size
+        grad = np.empty(n, np.float64) if want_grad else None
+        al = C.c_double()
+        sc = np.empty(max(self.n_speakers, 1), np.float64)
+        N.check(self._L.fb_get_grad_wb(self._h, C.byref(params), N.ptr(audio), C.c_int64(n), C.byref(al),
+                                       None if grad is None else N.ptr(grad), N.ptr(sc)))
+        return grad, al.value, sc
+
+    def attack_wb(self, params, audio):
+        """fb_attack_wb: FakeBob.attack's loop with the analytic gradient in place of the NES estimate (momentum = 0: PGD
+        with the margin loss; max_iter = 1: the single-step attack) -> (int16 adv, flag, float64 adv, trace), as attack."""
+        audio = np.ascontiguousarray(audio, np.float64).reshape(-1)
+        n, S = audio.size, max(self.n_speakers, 1)
+        adv = np.empty(n, np.int16)
+        adv_f = np.empty(n, np.float64)
+        trace = np.zeros((max(params.max_iter, 1), 3 + S), np.float64)
+        nt, flag = C.c_int(), C.c_int()
+        N.check(self._L.fb_attack_wb(self._h, C.byref(params), N.ptr(audio), C.c_int64(n), N.ptr(adv), N.ptr(adv_f),
+                                     N.ptr(trace), C.byref(nt), C.byref(flag)))
+        return adv, flag.value, adv_f, trace[:nt.value]
+
+    def debug_gmm_feat_grad(self, feats, w):
+        """The GMM backward alone (fb_debug_gmm_feat_grad): feats (Tv, D) float32 handed in as they are, w (M,) the
+        weights d loss / d raw[m] -> (Tv, D) float64."""
+        feats = np.ascontiguousarray(feats, np.float32)
+        w = np.ascontiguousarray(w, np.float64).reshape(-1)
+        Cn, D = self._gmm_shape
+        if feats.ndim != 2 or feats.shape[1] != D or w.size != self.n_models:
+            raise ValueError("debug_gmm_feat_grad takes rows of %d features and %d weights" % (D, self.n_models))
+        out = np.empty(feats.shape, np.float64)
+        N.check(self._L.fb_debug_gmm_feat_grad(self._h, N.ptr(feats), C.c_int(feats.shape[0]), N.ptr(w), N.ptr(out)))
+        return out
+
+    def debug_frontend_vjp(self, wav, cot):
+        """The front-end backward alone (fb_debug_frontend_vjp): int16 samples and a cotangent (Tv, feat_dim) on the
+        compacted voiced rows -> (dwav (n,) float64 in int16 units, the voiced mask (T,) bool the backward used)."""
+        wav = np.ascontiguousarray(wav, np.int16).reshape(-1)
+        cot = np.ascontiguousarray(cot, np.float64)
+        dwav = np.empty(wav.size, np.float64)
+        voiced = np.zeros(max(self._num_frames(wav.size), 1), np.uint8)
+        N.check(self._L.fb_debug_frontend_vjp(self._h, N.ptr(wav), C.c_int64(wav.size), N.ptr(cot), N.ptr(dwav), N.ptr(voiced)))
+        return dwav, voiced[:self._num_frames(wav.size)].astype(bool)
+
     # ---- particle swarm
     def attack_pso(self, params, pso, audio):
         """fb_attack_pso: the particle-swarm attack on this engine's system -> (int16 adv, flag, float64 adv, trace

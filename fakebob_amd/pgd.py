@@ -1,0 +1,104 @@
+"""PGD: the white-box gradient attacks of SpeakerGuard's evaluation (FGSM, PGD, the margin-loss CW-inf) on the engine's own
+GMM-UBM systems, behind FakeBob's interface.
+
+The loop is FakeBob.attack's (FAKEBOB.py:139-221) with the analytic gradient of the loss in place of the NES estimate
+(fb_attack_wb): momentum sign steps inside the epsilon ball, the plateau learning-rate rule on the clean loss, the early
+stop on adver_loss < 0.  momentum = 0 is plain PGD with the margin loss; max_iter = 1 is the single-step attack.  There
+is no random start, so a run is reproducible.  The victim has to be undefended: input transforms, the air channel, codecs,
+feature compression, dither, EOT and companions are refused (no BPDA in this version), as are i-vector systems and
+foreign models -- the gradient is that of this library's own forward.
+"""
+import pickle
+import time
+
+import numpy as np
+
+from .attack import FakeBob, _check_bits, _col
+from .engine import nes_params
+
+
+class PGD(object):
+
+    def __init__(self, task, attack_type, model, adver_thresh=0., epsilon=0.002, max_iter=1000, max_lr=0.001, min_lr=1e-6,
+                 momentum=0.9, plateau_length=5, plateau_drop=2., seed=None, verbose=True):
+        if task not in ("OSI", "CSI", "SV"):
+            raise ValueError("task must be OSI, CSI or SV")
+        if not hasattr(model, "engine"):
+            raise TypeError("PGD differentiates this library's own GMM-UBM systems: the model has no engine")
+        if getattr(model, "task", task) != task:
+            raise ValueError("model implements task %s, attack asked for %s" % (model.task, task))
+        if getattr(model.engine, "kind", "gmm") != "gmm":
+            raise ValueError("PGD: i-vector systems are out of this version (GMM-UBM systems only)")
+        self.task = task
+        self.attack_type = attack_type
+        self.model = model
+        self.adver_thresh = adver_thresh
+        self.epsilon = epsilon
+        self.max_iter = max_iter
+        self.max_lr = max_lr
+        self.min_lr = min_lr
+        self.momentum = momentum
+        self.plateau_length = plateau_length
+        self.plateau_drop = plateau_drop
+        self.threshold = 0.
+        self.true = None
+        self.target = None
+        self.verbose = verbose
+        # the attack itself draws nothing; the seed keys the threshold sweep, which is FakeBob's (estimate_threshold)
+        self.seed = int(np.random.randint(0, 2 ** 31 - 1)) if seed is None else int(seed)
+        self._stream = 0
+
+    def estimate_threshold(self, audio, fs=16000, bits_per_sample=16, n_jobs=10, debug=False, **kw):
+        """The white-box attack has no threshold sweep of its own: the sweep is FakeBob's (FAKEBOB.py:39-137), run by a
+        FakeBob over the same model with its default NES hyper-parameters and this attack's seed, epsilon and adver_thresh.
+        Returns what FakeBob.estimate_threshold returns and keeps the estimate in self.threshold."""
+        fb = FakeBob(self.task, self.attack_type, self.model, adver_thresh=self.adver_thresh, epsilon=self.epsilon,
+                     seed=self.seed, verbose=self.verbose)
+        fb._stream = self._stream
+        res = fb.estimate_threshold(audio, fs=fs, bits_per_sample=bits_per_sample, n_jobs=n_jobs, debug=debug, **kw)
+        self._stream = fb._stream
+        if res is not None:
+            self.threshold = fb.threshold
+        return res
+
+    def _params(self, bits_per_sample=16):
+        return nes_params(self.task, self.attack_type, adver_thresh=self.adver_thresh, epsilon=self.epsilon,
+                          max_iter=self.max_iter, max_lr=self.max_lr, min_lr=self.min_lr, samples_per_draw=0, sigma=0.0,
+                          momentum=self.momentum, plateau_length=self.plateau_length, plateau_drop=self.plateau_drop,
+                          threshold=self.threshold, target=self.target, true=self.true, seed=0, stream=0,
+                          bits_per_sample=bits_per_sample)
+
+    def get_grad(self, audio, fs=16000, bits_per_sample=16, n_jobs=10, debug=False):
+        """-> (grad (N,1) = d loss / d audio, adver_loss (1,), score), the analytic twin of FakeBob.get_grad's last three."""
+        audio = _col(audio)
+        grad, al, sc = self.model.engine.get_grad_wb(self._params(_check_bits(bits_per_sample)), audio[:, 0])
+        S = self.model.engine.n_speakers
+        return grad[:, np.newaxis], np.array([al]), (sc[0] if self.task == "SV" else sc[:S].copy())
+
+    def attack(self, audio, checkpoint_path, threshold=0., true=None, target=None, fs=16000, bits_per_sample=16, n_jobs=10,
+               debug=False):
+        """FakeBob.attack's signature and results: (int16 adversarial audio (N,1), success_flag +-1), and the trace
+        [distance, adver_loss, score, used_time] per iteration pickled to checkpoint_path (protocol -1)."""
+        audio = _col(audio)
+        bits = _check_bits(bits_per_sample)
+        self.threshold = threshold
+        self.true = true
+        self.target = target
+        eng = self.model.engine
+        t0 = time.time()
+        adv, flag, _advf, trace = eng.attack_wb(self._params(bits), audio[:, 0])
+        dt = time.time() - t0
+        n = trace.shape[0]
+        used_time = eng.attack_iter_seconds(n)
+        cp_global = []
+        for r in range(n):
+            used = 0. if (r == n - 1 and trace[r, 1] < 0) else float(used_time[r])  # the early-stop row stores 0. (:187)
+            sc = trace[r, 3:]
+            cp_global.append([trace[r, 0], np.array([trace[r, 1]]), sc[0] if self.task == "SV" else sc.copy(), used])
+        if checkpoint_path:
+            with open(checkpoint_path, "wb") as writer:
+                pickle.dump(cp_global, writer, protocol=-1)
+        if self.verbose:
+            print("--- %d iters, distance:%f, loss:%f, %.1f iters/s ---" %
+                  (n, trace[-1, 0], trace[-1, 1], n / dt if dt > 0 else 0.0))
+        return adv[:, np.newaxis], flag

@@ -32,6 +32,9 @@
  *                             attack of SpeakerGuard's evaluation, on this library's own systems)
  *   fb_attack_kenansville     (none in FAKEBOB: Kenansville, the decision-only black-box attack of that evaluation -- spectral
  *                             content is removed until the decision changes)
+ *   fb_get_grad_wb / fb_attack_wb     FakeBob.get_grad + loss_fn (FAKEBOB.py:223-299) and FakeBob.attack (:139-221) with the
+ *                             ANALYTIC gradient of the loss in place of the NES estimate: the white-box attacks of
+ *                             SpeakerGuard's evaluation (FGSM, PGD, the margin-loss CW-inf) on a GMM-UBM system
  *   fb_get_grad_ext / fb_attack_ext   the same around a foreign `model` (README.md:136)
  *   fb_get_grad_dev / fb_attack_dev   ... around a foreign model that runs on the
  *                             same GPU: the batch and the scores stay on the device
@@ -497,6 +500,53 @@ int fb_attack_kenansville(fb_engine *e, const fb_nes_params *p, const fb_kv_para
                           const double *audio, int64_t N, int16_t *adv_i16, int *success, int *factor, int *n_queries,
                           int *n_rounds, int *qs /*[max_rounds][G]*/, int *decisions /*[max_rounds][G]*/,
                           double *scores /*[max_rounds][G][S]*/, int *trace /*[max_rounds][3]*/);
+
+/* ---- white-box gradients: backpropagation through the GMM-UBM victim ------------------------------------------------------
+ * fb_get_grad estimates the gradient of the loss from scores (NES); the victim lives in the engine, so the gradient itself
+ * can be computed.  fb_get_grad_wb returns it, fb_attack_wb runs FakeBob.attack's loop on it.  Scope of this version: GMM-UBM
+ * systems (OSI, CSI, SV) on an UNDEFENDED victim; everything else is refused, not ignored ("Refusals").  BPDA through the
+ * defences, expectation over transformation and the i-vector back end are out of this version.
+ * The function that is differentiated.  Input: float audio a in [-1, 1].  The forward is the engine's ordinary one, as
+ * configured: the int16 cast with 2^(bits_per_sample - 1); MFCC, VAD, add-deltas, sliding CMVN, the voiced rows; per-model mean
+ * frame log-likelihood; fb_system_scores; the reference's loss_fn (FAKEBOB.py:248-299).  adver_loss and score0 are exactly
+ * what fb_get_grad returns for a batch of that one row (samples_per_draw = 0): the same launches.  The gradient is that of the
+ * real-valued function at the point the forward reached:
+ *  - the cast, the float32 storage points and the compress_feats, text_scores and mfcc_f32 roundings are identities
+ *    (straight-through);
+ *  - the voiced mask is the forward's own, recomputed from the forward's MFCC matrix by the arithmetic of its VAD and checked
+ *    against its count (FB_E_HIP if they ever differ), and held constant;
+ *  - a floor that is active contributes zero: log(max(E, FLT_EPSILON)) on a mel bin or a frame energy, and energy_floor;
+ *  - the loss's maxima take the subgradient of the index the forward's maximum selected: the first maximum, as make_decisions
+ *    does; np.maximum(other, threshold) passes the speaker only when it is strictly greater.
+ * grad[n] = d loss / d a[n], in the audio units of fb_get_grad's estimate: 2^(bits_per_sample - 1) times the derivative with
+ * respect to the int16 sample.  The per-model weights w[M] = d loss / d raw[m] follow from the branch of loss_fn -- OSI / SV:
+ * -+1 on at most two speakers, the opposite on the UBM; CSI: +-1 / z_std -- and are formed on the device from the scores it has.
+ * The arithmetic behind them: for every voiced row x_t, gamma the posteriors of model m,
+ *     g_t = (1 / Tv) sum_m w_m sum_c gamma_mtc (means_invvars_mc - inv_vars_mc * x_t)           (models with w_m = 0 skipped)
+ * with float32 matrix-core products and a float32 online soft-max over component tiles, the per-model rows combined in
+ * float64, models ascending; then the transposes of the front end in float64 -- scatter to the voiced frames, sliding CMVN
+ * (both clamped ends, T > cmn_window), deltas (clamped time index), MFCC per frame (C0 from the raw log-energy when use_energy;
+ * lifter, DCT, 1 / mel energy, mel weights; the frame's FFT recomputed from the int16 row, one inverse transform of dP_k F_k;
+ * window, pre-emphasis, DC removal) -- and an overlap-add through the forward's frame index rule, repeated reflection
+ * included.  No floating-point atomics: a sample sums its frames' contributions in ascending frame order, and the same call
+ * gives the same bits on a fresh engine.  Every front-end shape fb_set_frontend takes is taken.
+ * fb_get_grad_wb(e, p, audio, N, adver_loss, grad[N] (nullable), score0[S]).
+ * fb_attack_wb: FakeBob.attack's loop with that gradient in place of get_grad.  Unchanged from the reference: the early stop
+ * adver_loss < 0 before the step, the plateau rule, the trace rows {distance, adver_loss, lr_after, score0[S]}, the
+ * iter < max_iter - 1 flag, the final cast, the step (FAKEBOB.py:193-203: grad_m = momentum grad_m + (1 - momentum) g;
+ * adver -= lr sign(grad_m); the clips to the epsilon ball and to [-1, 1], float64 as in fb_attack).  One row is scored per
+ * iteration; the plateau window holds adver_loss (there is no noisy mean); samples_per_draw, sigma, seed and stream are not
+ * read.  momentum = 0 is plain PGD with the margin loss (SpeakerGuard's CW-inf / PGD), max_iter = 1 the single-step case;
+ * there is no random start, so a result is reproducible.  The loop control runs on the device and the host looks at it once
+ * per FB_ATTACK_BATCH iterations (default 4), as in fb_attack; fb_attack_iter_seconds and fb_stats work as for fb_attack.
+ * Refusals, each with a message naming the cause.  FB_E_STATE: no model, an i-vector system is loaded, fb_set_eot(r > 1) is
+ * in force, companions are set, an input-transform chain, an air channel or a codec is set, feature compression is on,
+ * dither > 0.  FB_E_ARG: audio shorter than one frame, max_iter < 1 (fb_attack_wb), the task, target, true-label and
+ * bits_per_sample rules of fb_attack_pso.  FB_E_NO_VOICED: a row without voiced frames, as in fb_attack. */
+int fb_get_grad_wb(fb_engine *e, const fb_nes_params *p, const double *audio, int64_t N, double *adver_loss,
+                   double *grad /*[N], nullable*/, double *score0 /*[S]*/);
+int fb_attack_wb(fb_engine *e, const fb_nes_params *p, const double *audio, int64_t N, int16_t *adv_i16, double *adver_f64,
+                 double *trace, int *n_trace, int *success_flag);
 
 const char *fb_last_error(void);
 int fb_version(void);

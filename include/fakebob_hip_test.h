@@ -274,6 +274,17 @@ int fb_bench_nes(fb_engine *e, const fb_nes_params *p, const double *audio,
  * iteration.  Any output may be NULL. */
 int fb_bench_nes_state(fb_engine *e, double *adver, double *scores, double *loss, double *summary);
 
+/* White-box gradients (fakebob_hip.h: "white-box gradients", fb_get_grad_wb / fb_attack_wb).  Each hook runs exactly the
+ * launches an attack iteration runs for its stage.
+ * fb_debug_gmm_feat_grad: the GMM backward alone on Tv rows of features handed in as they are (float32 [Tv][D]) with weights
+ * w[M] = d loss / d raw[m]: out[Tv][D] float64 = (1 / Tv) sum_m w_m sum_c gamma_mtc (means_invvars_mc - inv_vars_mc * x_t).
+ * Models with w_m = 0 are skipped; an all-zero w gives exact zeros.
+ * fb_debug_frontend_vjp: the front-end backward alone: the forward of fb_debug_feats on wav[n], then the vector-Jacobian
+ * product of the cotangent cot[Tv][dim] (float64, on the compacted voiced rows): dwav[n] float64 = d <cot, feats> / d wav in
+ * int16 units, and voiced[T] (nullable; 0 / 1), the mask the backward used.  FB_E_NO_VOICED without voiced frames. */
+int fb_debug_gmm_feat_grad(fb_engine *e, const float *feats, int Tv, const double *w, double *out);
+int fb_debug_frontend_vjp(fb_engine *e, const int16_t *wav, int64_t n, const double *cot, double *dwav, unsigned char *voiced);
+
 #ifdef __cplusplus
 }
 #endif
