@@ -66,13 +66,8 @@
 // Parameter items arrive by LDS-DMA (global_load_lds_dwordx4: no staging registers, no ds_write pass) into two LDS
 // slots, a group of items each, requested a whole group of steps ahead of the barrier that publishes them
 // (fb_fxw_fetch and the loop below).
-__device__ __forceinline__ void fb_glds16(const void *gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
 // N (1 .. 4) consecutive 1 KB pieces with one M0 set-up: the instruction offset moves the global source AND the LDS
-// destination (tools/probes/glds_offset_probe.hip)
+// destination (tools/probes/glds_offset_probe.hip).  The prologues' form: a whole group at once.
 template <int N>
 __device__ __forceinline__ void fb_glds16_run(const void *gsrc, unsigned lds_dst) {
   unsigned keep;
@@ -91,6 +86,29 @@ __device__ __forceinline__ void fb_glds16_run(const void *gsrc, unsigned lds_dst
 #undef FB_GLDS_HEAD
 #undef FB_GLDS_AT
 #undef FB_GLDS_TAIL
+}
+// Piece q of a stream of consecutive 1 KB pieces (q a constant after unrolling), a run of four behind ONE address: the
+// pieces 4 r .. 4 r + 3 share the M0 value and the address register pair of piece 4 r, the rest is the instruction
+// offset.  Through the compiler's builtin, not an asm: hipcc then owns M0 -- one s_mov_b32 per run instead of a save, a
+// set and a restore per piece -- and computes a run's address once: gsrc is the same in every lane, a scalar register
+// pair, and a run costs one 64-bit add of the lane's 16-byte offset to it (tests/test_fxw_tile_instruction_budget.py
+// counts what the compiler makes of it).
+__device__ __forceinline__ void fb_glds16_at(const u32x4 *gsrc, unsigned lds_dst, const int q, const int lane) {
+  typedef const __attribute__((address_space(1))) void *gptr_t;
+  typedef __attribute__((address_space(3))) void *lptr_t;
+  // (readfirstlane: free on a scalar, and it keeps hipcc from folding the lane's offset into a 64-bit vector address)
+  const unsigned long long ua = (unsigned long long)(gsrc + (q & ~3) * 64);
+  const unsigned s_hi = (unsigned)__builtin_amdgcn_readfirstlane((unsigned)(ua >> 32));  // (the builtin returns an int:
+  const unsigned s_lo = (unsigned)__builtin_amdgcn_readfirstlane((unsigned)ua);          //  no sign extension below)
+  const unsigned long long sa = ((unsigned long long)s_hi << 32) | (unsigned long long)s_lo;
+  const gptr_t gp = (gptr_t)(reinterpret_cast<const char *>(sa) + (unsigned)lane * 16u);
+  const lptr_t lp = (lptr_t)(size_t)(lds_dst + (unsigned)(q & ~3) * 1024u);
+  switch (q & 3) {
+    case 0: __builtin_amdgcn_global_load_lds(gp, lp, 16, 0, 0); break;
+    case 1: __builtin_amdgcn_global_load_lds(gp, lp, 16, 1024, 0); break;
+    case 2: __builtin_amdgcn_global_load_lds(gp, lp, 16, 2048, 0); break;
+    default: __builtin_amdgcn_global_load_lds(gp, lp, 16, 3072, 0); break;
+  }
 }
 // A group of NITEMS consecutive parameter items (NPIECE KB each, contiguous in the image buffer) -> LDS: wave wv brings
 // the pieces [wv PW, (wv + 1) PW), PW = ceil(total / 4) -- up to 3 pieces past the group's end when the total is not
@@ -167,8 +185,16 @@ extern "C" int fb_debug_fxw_stamps(unsigned long long *out) {
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_fxw_stamps), sizeof(g_fxw_stamps)) == hipSuccess ? 0 : -1;
 }
 #define FXW_STAMP(i) do { if (blockIdx.x == 8 && threadIdx.x == 0) g_fxw_stamps[i] = wall_clock64(); } while (0)
+// the steps of the P = 1 tiles of a launch with seven items per tile (UBM + 5): shader clocks (s_memtime) of wave 0, summed
+// per step over the workgroup's tiles -> stamps 9 .. 15, the tiles counted in stamp 8.  A stamp waits for the wave's LDS
+// reads (lgkmcnt), the next item's chunk 0 among them: read the steps against each other, not their sum.
+#define FXW_STEP_BEGIN() do { if (P == 1 && NI == 7) { fxw_tk = __builtin_amdgcn_s_memtime(); ++fxw_cyc[0]; } } while (0)
+#define FXW_STEP_END(jj) do { if (P == 1 && NI == 7) { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); \
+                                                       fxw_cyc[1 + (jj)] += now_ - fxw_tk; fxw_tk = now_; } } while (0)
 #else
 #define FXW_STAMP(i) do { } while (0)
+#define FXW_STEP_BEGIN() do { } while (0)
+#define FXW_STEP_END(jj) do { } while (0)
 #endif
 #define FB_FXW_ROFF 64.0f
 #define FB_FXW_SMAX 1.2676506002282294e30f  // 2^100
@@ -263,7 +289,7 @@ __device__ __forceinline__ void fb_fxw_step(const u32x4 *__restrict__ cur4, cons
       z1 = nxt4[(0 * NK + 0) * 64 + lane];
       z2 = nxt4[(1 * NK + 0) * 64 + lane];
     }
-    if (kk == (KP > 3 ? 3 : KP - 1) && c < dn) fb_glds16(dsrc + (dq0 + c) * 64, ddst + (unsigned)(dq0 + c) * 1024u);
+    if (kk == (KP > 3 ? 3 : KP - 1) && c < dn) fb_glds16_at(dsrc + dq0 * 64, ddst + (unsigned)dq0 * 1024u, c, lane);
     if constexpr (UPD) {
       // the 20 slices as 80 single instructions -- a slice = {addition half 0, addition half 1, exponential half 0,
       // exponential half 1} --, dealt evenly over the gaps: with 30 MFMAs per step a gap carries two or three of them
@@ -372,7 +398,7 @@ __device__ __forceinline__ void fb_fxw_step6(const u32x4 *__restrict__ cur4, con
       if (kk == 0) FB_FX_MFMA(a1, b1[0][c], x0);
       else FB_FX_MFMA(a1, b1[1][c], x1);
       if (pf0 && g == 3) z1 = nxt4[lane];  // chunk 0's register is free: the next item's chunk 0 (an F6 item again)
-      if (kk == 1 && c < dn) fb_glds16(dsrc + (dq0 + c) * 64, ddst + (unsigned)(dq0 + c) * 1024u);
+      if (kk == 1 && c < dn) fb_glds16_at(dsrc + dq0 * 64, ddst + (unsigned)dq0 * 1024u, c, lane);
     } else {
       const int blk = (g - NM) / 2, hf = (g - NM) % 2;  // 0: block 0, 1: block L, 2: block 1, 3: block 2
       const int fb = blk == 0 || blk == 1 ? 0 : blk - 1;  // the frames' operand it meets
@@ -732,7 +758,9 @@ __global__ __launch_bounds__(256, 1) void k_gmm_fx2w(FbGmmDev g, const float *__
   // slot A with group A of tile t + 1: a group is one contiguous piece of the image buffer, wave w brings the 1 KB
   // pieces [w PW, (w + 1) PW) of it, five per step (one behind the fourth MFMA of each K chunk) in the group's first
   // two steps -- at least a step ahead of the vmcnt(0) + barrier that publishes the slot (measured with s_memtime
-  // stamps: the wait is 16 cycles, the barrier ~90, of ~5 000 per group).
+  // stamps: the wait is 16 cycles, the barrier ~90, of ~5 000 per group).  Each five are a run of four behind one M0 write
+  // and one address, and a run of one (fb_glds16_at): a fetch costs the wave ~35 cycles of issue, ~45 with an M0 save / set /
+  // restore and an address add of its own (profiles/fxw_fetch_issue_stamps.txt).
   constexpr int NPIECE = IMG4 / 64;
   const int wv = __builtin_amdgcn_readfirstlane(w);
   const unsigned ring_lds = (unsigned)(unsigned long long)(__attribute__((address_space(3))) void *)lds;
@@ -789,9 +817,13 @@ __global__ __launch_bounds__(256, 1) void k_gmm_fx2w(FbGmmDev g, const float *__
   FXW_STAMP(4);
   u32x4 z1, z2;  // chunk 0 of the item in front (fb_fxw_step)
   constexpr int PW_A = (GA * NPIECE + 3) / 4, PW_B = (GB * NPIECE + 3) / 4;  // LDS-DMA pieces per wave for a group
+#ifdef FB_FXW_STAMP
+  unsigned long long fxw_tk = 0, fxw_cyc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#endif
   // one tile with P products per K chunk in its delta items (a compile-time constant: the tile is straight-line code)
   auto tile = [&](auto pc, const int t) __attribute__((always_inline)) {
     constexpr int P = decltype(pc)::value;
+    FXW_STEP_BEGIN();
     // a rescue of the last tile proposed a new reference for some frame: from this tile on (the two deferred updates
     // below still belong to the old one, rp)
     rp[0] = rc[0]; rp[1] = rc[1];
@@ -818,8 +850,8 @@ __global__ __launch_bounds__(256, 1) void k_gmm_fx2w(FbGmmDev g, const float *__
     }
     // this wave's share of the groups requested during this tile: group B of this tile (while A runs), group A of the
     // chunk's next one (while B runs); past the chunk's end the last tile's group A is read again and never used
-    const u32x4 *srcB = gimg + ((size_t)tile_of(t) * NI + GA) * IMG4 + (size_t)wv * (PW_B * 64) + lane;
-    const u32x4 *srcA = gimg + (size_t)tile_of(t + 1) * NI * IMG4 + (size_t)wv * (PW_A * 64) + lane;
+    const u32x4 *srcB = gimg + ((size_t)tile_of(t) * NI + GA) * IMG4 + (size_t)wv * (PW_B * 64);  // (the same in every lane)
+    const u32x4 *srcA = gimg + (size_t)tile_of(t + 1) * NI * IMG4 + (size_t)wv * (PW_A * 64);
     const unsigned dstB = ring_lds + SLOTB4 * 16 + (unsigned)wv * (PW_B * 1024), dstA = ring_lds + (unsigned)wv * (PW_A * 1024);
 #pragma clang loop unroll(full)
     for (int jj = 0; jj < NI; ++jj) {   // compile-time item index within the tile: 0 = Q, 1 + m = model m
@@ -837,7 +869,7 @@ __global__ __launch_bounds__(256, 1) void k_gmm_fx2w(FbGmmDev g, const float *__
       const unsigned ddst = jj < GA ? dstB : dstA;
       if (first_of_group) {  // behind the chunk-0 reads just issued: their latency is there anyway
 #pragma unroll
-        for (int q = 0; q < dn; ++q) fb_glds16(dsrc + q * 64, ddst + (unsigned)q * 1024u);
+        for (int q = 0; q < dn; ++q) fb_glds16_at(dsrc, ddst, q, lane);
         dn = 0;
       }
       // the MFMAs of this item with the update of the pending accumulator set threaded between them (fb_fxw_step):
@@ -890,7 +922,12 @@ __global__ __launch_bounds__(256, 1) void k_gmm_fx2w(FbGmmDev g, const float *__
                                    acc[(jj - 2) & 1][0], acc[(jj - 2) & 1][1], ps, 1.f, 1.f, uu, dsrc, ddst, dq0, dn);
         settle(acc[(jj - 2) & 1][0], acc[(jj - 2) & 1][1], pm, ps, rc, uu);
       }
+      // the base model's values stay where they are to the end of the tile: dead after the last delta item, hipcc let
+      // that item accumulate in THEIR registers and copied the set to its own at the loop's back edge (16 v_mov_b64
+      // behind the tile's last MFMAs, and an s_nop for those to finish)
+      if (jj == NI - 1) asm volatile("" : : "v"(hq[0]), "v"(hq[1]));
       if (jj == GA - 1 || jj == NI - 1) publish();
+      FXW_STEP_END(jj);
     }
   };
   {
@@ -901,6 +938,10 @@ __global__ __launch_bounds__(256, 1) void k_gmm_fx2w(FbGmmDev g, const float *__
     for (; t < n_t; ++t) tile(std::integral_constant<int, 1>{}, t);
   }
   FXW_STAMP(5);
+#ifdef FB_FXW_STAMP
+  if (blockIdx.x == 8 && threadIdx.x == 0 && sub == n_sub - 1)
+    for (int i = 0; i < 8; ++i) g_fxw_stamps[8 + i] = fxw_cyc[i];
+#endif
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   // the updates the last tile deferred: the fast form (one exponential and one addition per value, the guard, the cold
   // rescue) without MFMAs to thread it through -- the classical form here (a maximum, a re-reference, fma + exp + add
@@ -1103,8 +1144,8 @@ __global__ __launch_bounds__(256, 1) void k_gsel_w(FbGmmDev g, const float *__re
     }
   };
   for (int gp = 0; gp < n_grp; gp += 2) {   // slot A = group gp, slot B = group gp + 1
-    const u32x4 *srcB = gimg + (size_t)min(gp + 1, n_grp - 1) * SLOT4 + (size_t)wv * (PW * 64) + lane;
-    const u32x4 *srcA = gimg + (size_t)min(gp + 2, n_grp - 1) * SLOT4 + (size_t)wv * (PW * 64) + lane;
+    const u32x4 *srcB = gimg + (size_t)min(gp + 1, n_grp - 1) * SLOT4 + (size_t)wv * (PW * 64);
+    const u32x4 *srcA = gimg + (size_t)min(gp + 2, n_grp - 1) * SLOT4 + (size_t)wv * (PW * 64);
     const unsigned dstB = ring_lds + SLOT4 * 16 + (unsigned)wv * (PW * 1024), dstA = ring_lds + (unsigned)wv * (PW * 1024);
 #pragma clang loop unroll(full)
     for (int jj = 0; jj < 2 * NIG; ++jj) {
@@ -1123,7 +1164,7 @@ __global__ __launch_bounds__(256, 1) void k_gsel_w(FbGmmDev g, const float *__re
       int dn = dq0 < PW ? (PW - dq0 < 5 ? PW - dq0 : 5) : 0;
       if (gs == 0) {
 #pragma unroll
-        for (int q = 0; q < dn; ++q) fb_glds16(dsrc + q * 64, ddst + (unsigned)q * 1024u);
+        for (int q = 0; q < dn; ++q) fb_glds16_at(dsrc, ddst, q, lane);
         dn = 0;
       }
       constexpr int dummy = 0; (void)dummy;

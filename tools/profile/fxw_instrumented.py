@@ -38,4 +38,22 @@ else:
     for i, n in enumerate(names):
         print("%-36s %6.2f us" % (n, (t[i + 1] - t[i]) / 100.0))
     print("workgroup 8: %.2f us; launch %.1f us (%d rows)" % ((t[7] - t[0]) / 100.0, 1e3 * ms, rows))
+
+    def steps(label):
+        """shader clocks per step of the P = 1 tiles (stamps 8 .. 15), wave 0 of workgroup 8, its last component chunk"""
+        out = np.zeros(16, np.uint64)
+        lib.fb_debug_fxw_stamps(out.ctypes.data_as(C.c_void_p))
+        t = out.astype(np.int64)
+        n = max(1, int(t[8]))
+        per = [t[9 + k] / n for k in range(7)]
+        loop_us = (t[5] - t[4]) / 100.0
+        print("%s: %d P = 1 tiles; cycles per step  Q %.0f  base %.0f  d1 %.0f  d2 %.0f  d3 %.0f  d4 %.0f  d5 %.0f  | tile %.0f; "
+              "tile loop of the last chunk %.2f us" % ((label, n) + tuple(per) + (sum(per), loop_us)))
+
+    for sub in ("1", "2"):   # the whole-chip launch and the half grid of a shared GPU (two chunks per workgroup)
+        os.environ["FB_GMM_SUB"] = sub
+        for _ in range(2):
+            ms, rows = e.bench_gmm_kernel(10)
+        steps("FB_GMM_SUB=%s, launch %.1f us" % (sub, 1e3 * ms))
+    os.environ.pop("FB_GMM_SUB")
 e.close()
