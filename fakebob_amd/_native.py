@@ -68,6 +68,31 @@ class IvectorSystem(C.Structure):
     ]
 
 
+def ivector_struct(system):
+    """models.IvectorSystem -> (fb_ivector_system, the arrays it points into: keep them alive for the call)"""
+    sy = IvectorSystem()
+    sy.C, sy.D, sy.R, sy.L, sy.S = system.C, system.D, system.R, system.L, system.S
+    sy.lda_cols = system.lda.shape[1]
+    sy.num_gselect = system.num_gselect
+    sy.min_post = system.min_post
+    sy.prior_offset = system.prior_offset
+    keep = []
+    for name in ("fg_weights", "fg_means_invcovars", "fg_inv_covars", "ie_M", "ie_sigma_inv", "mean_vec",
+                 "lda", "plda_mean", "plda_transform", "plda_psi", "enrolled", "z_mean", "z_std"):
+        a = getattr(system, name)
+        keep.append(a)
+        setattr(sy, name, a.ctypes.data)
+    return sy, keep
+
+
+class GmmPlan(C.Structure):
+    """fb_gmm_plan (include/fakebob_hip_test.h)"""
+    _fields_ = [("mode", C.c_int), ("NK", C.c_int), ("NKF", C.c_int), ("kx", C.c_int), ("kx2", C.c_int), ("kacc", C.c_int),
+                ("n_tiles", C.c_int), ("n_items", C.c_int), ("n_groups", C.c_int),
+                ("delta_p", C.c_int), ("t3", C.c_int), ("t6", C.c_int), ("t2", C.c_int), ("n_pass", C.c_int),
+                ("pass_lo", C.c_int * 4), ("delta_rms", C.c_double)]
+
+
 # fb_score_cb: int (*)(void *ctx, const double *audios, int64_t N, int B, double *scores)
 SCORE_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int64, C.c_int, C.POINTER(C.c_double))
 
@@ -107,6 +132,7 @@ EXPORTS = [
     "fb_score_i16", "fb_score_f64", "fb_system_scores", "fb_get_grad", "fb_attack", "fb_get_grad_wb", "fb_attack_wb", "fb_attack_pso", "fb_attack_kenansville", "fb_attack_iter_seconds", "fb_get_grad_ext", "fb_attack_ext",
     "fb_get_grad_dev", "fb_attack_dev", "fb_debug_foreign_path", "fb_debug_nes_route", "fb_debug_shared_chain_engines",
     "fb_estimate_threshold", "fb_debug_noise", "fb_debug_quantize", "fb_debug_mfcc", "fb_debug_feats", "fb_debug_dither_noise", "fb_debug_mfcc_dither", "fb_debug_feats_dither", "fb_debug_input_transform", "fb_debug_tf_noise", "fb_debug_input_transform_eot", "fb_debug_compose", "fb_debug_air_taps", "fb_debug_air_convolve", "fb_debug_codec", "fb_debug_feature_compress", "fb_debug_feco_keys", "fb_debug_pso_init", "fb_debug_pso_step", "fb_debug_kv_analyse", "fb_debug_kv_candidates", "fb_debug_gmm_frames", "fb_debug_gmm_acc_rows", "fb_debug_gmm_feat_grad", "fb_debug_frontend_vjp", "fb_debug_iv_active", "fb_debug_iv_gselect", "fb_debug_frontend_route", "fb_debug_launch_shape", "fb_stats", "fb_gmm_acc_stats", "fb_last_ivectors", "fb_gmm_kernel_mode", "fb_gmm_kernel_variant", "fb_gmm_delta_tiles", "fb_gmm_delta_tiles_f6", "fb_set_fused_chain",
+    "fb_debug_prepare_gmm", "fb_debug_prepare_ivector", "fb_debug_prepare_frontend",
     "fb_bench_gmm_kernel", "fb_bench_kv_kernels", "fb_bench_nes", "fb_bench_nes_state",
 ]
 

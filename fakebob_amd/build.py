@@ -16,12 +16,28 @@ LIBDIR = os.path.join(HERE, "lib")
 OBJDIR = os.path.join(HERE, "build")
 LIB = os.path.join(LIBDIR, "libfakebob_hip.so")
 SOURCES = ["nes_kernels.hip", "whitebox_kernels.hip", "pso_kernels.hip", "kenansville_kernels.hip", "input_transform_kernel.hip", "air_channel_kernel.hip", "codec_kernel.hip", "feature_compress_kernel.hip", "frontend_kernels.hip", "frontend_f32_kernels.hip", "gmm_kernels.hip", "gmm_wide_kernel.hip", "ivector_kernels.hip", "ivector_solve.hip",
-           "fb_engine.hip"]
+           "fb_engine.hip",
+           # host-only C++ (no HIP header, no HIP call): the tables the loaders upload (csrc/fb_prepare.h)
+           "fb_prepare_gmm.cpp", "fb_prepare_ivector.cpp", "fb_prepare_frontend.cpp"]
 # per-source flags.  k_gmm_fx2w keeps its MFMA accumulators in vector registers (the logsumexp update reads them in
 # place) and its parked frame operands in accumulation registers: hipcc picks that form of the MFMA with this option
 SOURCE_FLAGS = {"gmm_wide_kernel.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-fast-math", "-Wall", "-Wno-unused-function"]
+# .cpp sources are compiled as plain C++ with the same optimisation and floating-point flags, without the HIP-only ones
+HIP_ONLY_FLAGS = ("--offload-arch=gfx950", "-fhip-fp32-correctly-rounded-divide-sqrt")
+
+
+def _obj_name(src):
+    return os.path.splitext(src)[0] + ".o"
+
+
+def _compile_cmd(hipcc, src, extra, obj):
+    if src.endswith(".cpp"):
+        flags = ["-x", "c++"] + [f for f in FLAGS if f not in HIP_ONLY_FLAGS]
+    else:
+        flags = FLAGS + SOURCE_FLAGS.get(src, [])
+    return [hipcc] + flags + extra + ["-c", os.path.join(CSRC, src), "-o", obj]
 
 
 def _hipcc():
@@ -69,8 +85,8 @@ def build_variant(name, force=False):
     os.makedirs(odir, exist_ok=True)
 
     def comp(src):
-        obj = os.path.join(odir, src.replace(".hip", ".o"))
-        cmd = [hipcc] + FLAGS + SOURCE_FLAGS.get(src, []) + flags + ["-c", os.path.join(CSRC, src), "-o", obj]
+        obj = os.path.join(odir, _obj_name(src))
+        cmd = _compile_cmd(hipcc, src, flags, obj)
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
         if r.returncode != 0:
             raise RuntimeError("hipcc failed on %s (%s):\n%s" % (src, name, r.stdout))
@@ -78,7 +94,7 @@ def build_variant(name, force=False):
 
     with cf.ThreadPoolExecutor(max_workers=len(own)) as ex:
         objs = list(ex.map(comp, own))
-    objs += [os.path.join(OBJDIR, s.replace(".hip", ".o")) for s in SOURCES if s not in own]
+    objs += [os.path.join(OBJDIR, _obj_name(s)) for s in SOURCES if s not in own]
     r = subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs, stdout=subprocess.PIPE,
                        stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:
@@ -95,9 +111,9 @@ def build(force=False, verbose=False):
     srcs = [s for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
 
     def comp(src):
-        obj = os.path.join(OBJDIR, src.replace(".hip", ".o"))
+        obj = os.path.join(OBJDIR, _obj_name(src))
         extra = os.environ.get("FB_EXTRA_HIPCC_FLAGS", "").split()
-        cmd = [hipcc] + FLAGS + SOURCE_FLAGS.get(src, []) + extra + ["-c", os.path.join(CSRC, src), "-o", obj]
+        cmd = _compile_cmd(hipcc, src, extra, obj)
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
         return src, obj, r.returncode, r.stdout
 

@@ -1,5 +1,10 @@
-// fb_engine.hip -- host side of libfakebob_hip.so: engine state, device buffers,
-// model/front-end table preparation and the C ABI (include/fakebob_hip.h).
+// fb_engine.hip -- host side of libfakebob_hip.so: engine state, device buffers and the C ABI (include/fakebob_hip.h).
+//
+// The tables a model or a front-end configuration needs on the device are computed by the GPU-free unit fb_prepare.h
+// (fb_prepare_gmm.cpp, fb_prepare_ivector.cpp, fb_prepare_frontend.cpp).  The loaders here -- fb_load_gmm,
+// fb_load_ivector, fb_set_frontend -- validate their arguments, read the environment, prepare on the host, and only
+// then synchronise the stream, ensure every buffer, upload and assign the engine's fields: a call refused for its
+// arguments or its environment leaves the engine and the device exactly as they were.
 //
 // One engine = one GPU + one HIP stream.  A NES iteration is a fixed chain of
 // launches on that stream with a single 8-byte-aligned result block copied back
@@ -18,6 +23,7 @@
 #include <vector>
 
 #include "fb_kernels.h"
+#include "fb_prepare.h"
 
 static thread_local std::string g_err;
 static int fb_fail(int code, const char *fmt, ...) {
@@ -362,11 +368,18 @@ extern "C" void fb_default_frontend(fb_frontend_cfg *c) {
   c->dither = 0.0;
 }
 
-static double mel_scale(double f) { return 1127.0 * log(1.0 + f / 700.0); }
 int fb_mfcc_layout_doubles(int P, int L, int nb, int nc, int melw_n);  // frontend_kernels.hip
 
-extern "C" int fb_set_frontend(fb_engine *e, const fb_frontend_cfg *c) {
-  if (!e || !c) return fb_fail(FB_E_ARG, "null argument");
+// fb_set_frontend's checks and host tables (fb_prepare.h), nothing of the engine: every check that can refuse the
+// configuration runs here, on locals
+struct FrontendPrepared {
+  FbFrontendTables t;
+  FbFrontendBlob blob;
+  bool f32_shape = false;    // k_mfcc_f32's tables exist for this configuration
+  std::vector<float> t32;    // ... and are these
+  int dim = 0;
+};
+static int prepare_frontend(const fb_frontend_cfg *c, FrontendPrepared *out) {
   const int L = c->frame_length, P = c->padded_length, nb = c->num_mel_bins, nc = c->num_ceps;
   if (L <= 1 || L > 512 || P < L || (P & (P - 1)) || P < 8 || P > 512)
     return fb_fail(FB_E_ARG, "frame_length %d / padded_length %d unsupported (need L<=512, P power of 2)", L, P);
@@ -379,132 +392,59 @@ extern "C" int fb_set_frontend(fb_engine *e, const fb_frontend_cfg *c) {
   if (c->cmn_window < 1) return fb_fail(FB_E_ARG, "cmn_window %d < 1", c->cmn_window);
   if (c->vad_frames_context < 0) return fb_fail(FB_E_ARG, "vad_frames_context %d < 0", c->vad_frames_context);
   if (!(c->dither >= 0.0) || !std::isfinite(c->dither)) return fb_fail(FB_E_ARG, "dither %g is not a finite value >= 0", c->dither);
-  const int dim = nc * (c->delta_order + 1);
-  if (dim > 256) return fb_fail(FB_E_ARG, "feature dim %d > 256 unsupported", dim);
-  HIPCHK(hipSetDevice(e->device));
-  const int Nc = P / 2;
-  // ---- host tables; float32-stored Kaldi constants are rounded to float first
-  std::vector<double> window(L), tw_half(2 * (size_t)(Nc > 1 ? Nc : 1)), tw_full(2 * (size_t)(Nc + 1));
-  const double a = 2.0 * M_PI / (L - 1);
-  for (int i = 0; i < L; ++i) window[i] = (double)(float)pow(0.5 - 0.5 * cos(a * i), 0.85);
-  for (int m = 0; m < Nc; ++m) { tw_half[2 * m] = cos(-2.0 * M_PI * m / Nc); tw_half[2 * m + 1] = sin(-2.0 * M_PI * m / Nc); }
-  for (int k = 0; k <= Nc; ++k) { tw_full[2 * k] = cos(-2.0 * M_PI * k / P); tw_full[2 * k + 1] = sin(-2.0 * M_PI * k / P); }
-  std::vector<int> mel_first(nb), mel_len(nb), mel_off(nb);
-  std::vector<double> mel_w;
-  {
-    const double nyq = 0.5 * c->sample_freq;
-    const double hi = c->high_freq > 0.0 ? c->high_freq : nyq + c->high_freq;
-    if (c->low_freq < 0.0 || hi <= c->low_freq || hi > nyq) return fb_fail(FB_E_ARG, "bad mel frequency range");
-    const double bw = c->sample_freq / P;
-    const double mlo = mel_scale(c->low_freq), mhi = mel_scale(hi), md = (mhi - mlo) / (nb + 1);
-    for (int b = 0; b < nb; ++b) {
-      const double left = mlo + b * md, center = mlo + (b + 1) * md, right = mlo + (b + 2) * md;
-      int first = -1, last = -1;
-      std::vector<double> wts;
-      for (int i = 0; i < Nc; ++i) {
-        const double mel = mel_scale(bw * i);
-        if (mel > left && mel < right) {
-          const double wv = mel <= center ? (mel - left) / (center - left) : (right - mel) / (right - center);
-          if (first < 0) first = i;
-          last = i;
-          wts.push_back((double)(float)wv);
-        }
-      }
-      // [EXT] Kaldi's MelBanks refuses a bin that takes no FFT bin ("You may have set --num-mel-bins too large"): its
-      // log-energy would be the constant log(FLT_EPSILON)
-      if (first < 0) return fb_fail(FB_E_ARG, "mel bin %d covers no FFT bin (num_mel_bins %d too large)", b, nb);
-      mel_first[b] = first;
-      mel_len[b] = last - first + 1;
-      mel_off[b] = (int)mel_w.size();
-      mel_w.insert(mel_w.end(), wts.begin(), wts.end());
-    }
-  }
-  std::vector<double> dct((size_t)nc * nb), lifter(nc);
-  for (int k = 0; k < nc; ++k)
-    for (int n = 0; n < nb; ++n)
-      dct[(size_t)k * nb + n] = (k == 0) ? (double)(float)sqrt(1.0 / nb)
-                                         : (double)(float)(sqrt(2.0 / nb) * cos(M_PI / nb * (n + 0.5) * k));
-  for (int i = 0; i < nc; ++i)
-    lifter[i] = c->cepstral_lifter != 0.0
-                    ? (double)(float)(1.0 + 0.5 * c->cepstral_lifter * sin(M_PI * i / c->cepstral_lifter))
-                    : 1.0;
-  const int order = c->delta_order, W = c->delta_window, maxlen = 2 * order * W + 1;
-  std::vector<double> dscale((size_t)(order + 1) * maxlen, 0.0);
-  dscale[0] = 1.0;
-  for (int i = 1; i <= order; ++i) {
-    const double *prev = &dscale[(size_t)(i - 1) * maxlen];
-    double *cur = &dscale[(size_t)i * maxlen];
-    const int poff = (i - 1) * W, coff = i * W;
-    double normalizer = 0.0;
-    for (int j = -W; j <= W; ++j) {
-      normalizer += (double)j * j;
-      for (int k = -poff; k <= poff; ++k) cur[j + k + coff] += (double)j * prev[k + poff];
-    }
-    for (int k = 0; k < 2 * coff + 1; ++k) cur[k] = (double)(float)(cur[k] / normalizer);
-  }
-  // ---- pack into one device allocation
-  auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
-  size_t off = 0;
-  const size_t o_window = off; off = al(off + sizeof(double) * window.size());
-  const size_t o_twh = off; off = al(off + sizeof(double) * tw_half.size());
-  const size_t o_twf = off; off = al(off + sizeof(double) * tw_full.size());
-  const size_t o_mf = off; off = al(off + sizeof(int) * nb);
-  const size_t o_ml = off; off = al(off + sizeof(int) * nb);
-  const size_t o_mo = off; off = al(off + sizeof(int) * nb);
-  const size_t o_mw = off; off = al(off + sizeof(double) * (mel_w.size() + 1));
-  const size_t o_dct = off; off = al(off + sizeof(double) * dct.size());
-  const size_t o_lift = off; off = al(off + sizeof(double) * lifter.size());
-  const size_t o_ds = off; off = al(off + sizeof(double) * dscale.size());
-  std::vector<char> host(off, 0);
-  memcpy(&host[o_window], window.data(), sizeof(double) * window.size());
-  memcpy(&host[o_twh], tw_half.data(), sizeof(double) * tw_half.size());
-  memcpy(&host[o_twf], tw_full.data(), sizeof(double) * tw_full.size());
-  memcpy(&host[o_mf], mel_first.data(), sizeof(int) * nb);
-  memcpy(&host[o_ml], mel_len.data(), sizeof(int) * nb);
-  memcpy(&host[o_mo], mel_off.data(), sizeof(int) * nb);
-  if (!mel_w.empty()) memcpy(&host[o_mw], mel_w.data(), sizeof(double) * mel_w.size());
-  memcpy(&host[o_dct], dct.data(), sizeof(double) * dct.size());
-  memcpy(&host[o_lift], lifter.data(), sizeof(double) * lifter.size());
-  memcpy(&host[o_ds], dscale.data(), sizeof(double) * dscale.size());
-  // every check that can refuse the configuration runs on locals: a refused call leaves e->fe, e->cfg and the device
-  // tables exactly as they were
-  if (sizeof(double) * (size_t)(fb_mfcc_layout_doubles(P, L, nb, nc, (int)mel_w.size())) > 150 * 1024)
+  out->dim = nc * (c->delta_order + 1);
+  if (out->dim > 256) return fb_fail(FB_E_ARG, "feature dim %d > 256 unsupported", out->dim);
+  std::string err;
+  const int rc = fb_frontend_tables(c, &out->t, &err);
+  if (rc != FB_OK) return fb_fail(rc, "%s", err.c_str());
+  const FbFrontendTables &t = out->t;
+  out->blob = fb_frontend_pack(t);
+  if (sizeof(double) * (size_t)(fb_mfcc_layout_doubles(P, L, nb, nc, (int)t.mel_w.size())) > 150 * 1024)
     return fb_fail(FB_E_ARG, "front-end tables do not fit LDS (padded_length %d, %d mel bins)", P, nb);
-  const bool f32_shape = P == 512 && nb <= 31 && nc <= 32 && (L & 1) == 0 && fb_mfcc_f32_mel_pieces(mel_len.data(), nb) <= 64;  // k_mfcc_f32's tables exist for these
-  if (c->mfcc_f32 && !(f32_shape && c->raw_energy != 0))
+  out->f32_shape = P == 512 && nb <= 31 && nc <= 32 && (L & 1) == 0 && fb_mfcc_f32_mel_pieces(t.mel_len.data(), nb) <= 64;
+  if (c->mfcc_f32 && !(out->f32_shape && c->raw_energy != 0))
     return fb_fail(FB_E_ARG, "mfcc_f32 needs padded_length 512, raw_energy, <= 31 mel bins, <= 32 cepstra and an even frame length");
-  std::vector<float> t32;
-  if (f32_shape)  // (any precision setting: the flag may come later)
-    t32 = fb_mfcc_f32_table(L, nb, nc, window.data(), tw_half.data(), tw_full.data(), mel_first.data(), mel_len.data(),
-                            mel_off.data(), mel_w.data(), (int)mel_w.size(), dct.data(), lifter.data());
+  if (out->f32_shape)  // (any precision setting: the flag may come later)
+    out->t32 = fb_mfcc_f32_table(L, nb, nc, t.window.data(), t.tw_half.data(), t.tw_full.data(), t.mel_first.data(), t.mel_len.data(),
+                                 t.mel_off.data(), t.mel_w.data(), (int)t.mel_w.size(), t.dct.data(), t.lifter.data());
+  return FB_OK;
+}
+
+extern "C" int fb_set_frontend(fb_engine *e, const fb_frontend_cfg *c) {
+  if (!e || !c) return fb_fail(FB_E_ARG, "null argument");
+  FrontendPrepared p;
+  FBCHK(prepare_frontend(c, &p));  // a refused call leaves e->fe, e->cfg and the device tables exactly as they were
+  HIPCHK(hipSetDevice(e->device));
   FBCHK(sync_stream(e));
-  FBCHK(e->fe_tables.ensure(off));
-  if (f32_shape) FBCHK(e->fe_tables32.ensure(sizeof(float) * t32.size()));
-  HIPCHK(hipMemcpy(e->fe_tables.p, host.data(), off, hipMemcpyHostToDevice));
-  if (f32_shape) HIPCHK(hipMemcpy(e->fe_tables32.p, t32.data(), sizeof(float) * t32.size(), hipMemcpyHostToDevice));
+  FBCHK(e->fe_tables.ensure(p.blob.bytes.size()));
+  if (p.f32_shape) FBCHK(e->fe_tables32.ensure(sizeof(float) * p.t32.size()));
+  HIPCHK(hipMemcpy(e->fe_tables.p, p.blob.bytes.data(), p.blob.bytes.size(), hipMemcpyHostToDevice));
+  if (p.f32_shape) HIPCHK(hipMemcpy(e->fe_tables32.p, p.t32.data(), sizeof(float) * p.t32.size(), hipMemcpyHostToDevice));
   char *base = e->fe_tables.as<char>();
+  const FbFrontendBlob &b = p.blob;
   FbFrontendDev &fe = e->fe;
-  fe.L = L; fe.P = P; fe.shift = c->frame_shift; fe.nb = nb; fe.nc = nc; fe.dim = dim; fe.order = order;
-  fe.dwin = W; fe.cmn_window = c->cmn_window; fe.snip_edges = c->snip_edges; fe.remove_dc = c->remove_dc;
+  fe.L = c->frame_length; fe.P = c->padded_length; fe.shift = c->frame_shift; fe.nb = c->num_mel_bins; fe.nc = c->num_ceps;
+  fe.dim = p.dim; fe.order = c->delta_order;
+  fe.dwin = c->delta_window; fe.cmn_window = c->cmn_window; fe.snip_edges = c->snip_edges; fe.remove_dc = c->remove_dc;
   fe.use_energy = c->use_energy; fe.raw_energy = c->raw_energy; fe.vad_ctx = c->vad_frames_context;
   fe.preemph = c->preemph;
   fe.mfcc_f32 = c->mfcc_f32 ? 1 : 0;
   fe.log_energy_floor = c->energy_floor > 0.0 ? log(c->energy_floor) : -INFINITY;
   fe.vad_thr = c->vad_energy_threshold; fe.vad_mean_scale = c->vad_energy_mean_scale;
   fe.vad_prop = (float)c->vad_proportion_threshold;
-  fe.window = (const double *)(base + o_window); fe.tw_half = (const double *)(base + o_twh);
-  fe.tw_full = (const double *)(base + o_twf); fe.mel_first = (const int *)(base + o_mf);
-  fe.mel_len = (const int *)(base + o_ml); fe.mel_off = (const int *)(base + o_mo);
-  fe.mel_w = (const double *)(base + o_mw); fe.dct = (const double *)(base + o_dct);
-  fe.lifter = (const double *)(base + o_lift); fe.dscale = (const double *)(base + o_ds);
-  e->melw_n = (int)mel_w.size();
-  fe.f32_tab = f32_shape ? e->fe_tables32.as<float>() : nullptr;
+  fe.window = (const double *)(base + b.o_window); fe.tw_half = (const double *)(base + b.o_twh);
+  fe.tw_full = (const double *)(base + b.o_twf); fe.mel_first = (const int *)(base + b.o_mf);
+  fe.mel_len = (const int *)(base + b.o_ml); fe.mel_off = (const int *)(base + b.o_mo);
+  fe.mel_w = (const double *)(base + b.o_mw); fe.dct = (const double *)(base + b.o_dct);
+  fe.lifter = (const double *)(base + b.o_lift); fe.dscale = (const double *)(base + b.o_ds);
+  e->melw_n = (int)p.t.mel_w.size();
+  fe.f32_tab = p.f32_shape ? e->fe_tables32.as<float>() : nullptr;
   e->cfg = *c;
   e->gmm.text_scores = c->text_scores;
   e->iv.text_scores = c->text_scores;
   e->have_fe = true;
   e->cached_B = -1;
-  if (e->have_gmm && e->gmm.D != dim) e->have_gmm = false;
+  if (e->have_gmm && e->gmm.D != p.dim) e->have_gmm = false;
   return FB_OK;
 }
 
@@ -514,627 +454,123 @@ static int num_frames(const fb_frontend_cfg &c, int64_t n) {
 }
 
 // --------------------------------------------------------------------- gmm
-extern "C" int fb_load_gmm(fb_engine *e, int M, int C, int D, const float *gconsts, const float *miv,
-                           const float *iv) {
-  if (!e || !gconsts || !miv || !iv) return fb_fail(FB_E_ARG, "null argument");
-  if (M <= 0 || C <= 0 || D <= 0) return fb_fail(FB_E_ARG, "bad GMM shape M=%d C=%d D=%d", M, C, D);
-  if (M > 60) return fb_fail(FB_E_ARG, "at most 60 models per engine (got %d)", M);
-  if (!e->have_fe || e->fe.dim != D)
-    return fb_fail(FB_E_ARG, "GMM dim %d != front-end feature dim %d", D, e->have_fe ? e->fe.dim : -1);
-  if (D > 80) return fb_fail(FB_E_ARG, "feature dim %d > 80 unsupported by the MFMA kernels", D);
-  HIPCHK(hipSetDevice(e->device));
-  // groups of models with bitwise-identical inv_vars
-  std::vector<int> group_of(M, -1);
-  std::vector<int> group_rep;
-  for (int m = 0; m < M; ++m) {
-    for (size_t g = 0; g < group_rep.size(); ++g)
-      if (memcmp(iv + (size_t)m * C * D, iv + (size_t)group_rep[g] * C * D, sizeof(float) * (size_t)C * D) == 0) {
-        group_of[m] = (int)g;
-        break;
-      }
-    if (group_of[m] < 0) { group_of[m] = (int)group_rep.size(); group_rep.push_back(m); }
-  }
-  const int G = (int)group_rep.size();
-  std::vector<int> item_model;
-  for (int g = 0; g < G; ++g) {
-    item_model.push_back(-1 - g);  // Q item of group g (any negative = Q)
-    for (int m = 0; m < M; ++m) if (group_of[m] == g) item_model.push_back(m);
-  }
-  const int n_items = (int)item_model.size();
-  const int n_tiles = (C + 31) / 32;
-  FBCHK(sync_stream(e));
-  // bf16x3 images (k_gmm_bx3): exact 3-way bf16 split of every parameter, gconst in the K padding
-  const int NK = (D + 3 + 15) / 16 < 3 ? 3 : (D + 3 + 15) / 16;  // kernels are instantiated for NK = 3..6 (zero padding is free)
+// FB_GMM_MODE, FB_GMM_DELTA_BUDGET, FB_GMM_DELTA_F6, FB_GMM_DELTA_P -> the options of fb_prepare_gmm; the one place that
+// reads them.  A value that is refused is refused whatever the model's shape.
+static int gmm_options_from_env(FbGmmPrepOptions *o) {
+  *o = FbGmmPrepOptions();
   const char *mode_env = getenv("FB_GMM_MODE");
-  int mode = FB_GMM_MODE_FX2;
-  if (mode_env && strcmp(mode_env, "bx3") == 0) mode = FB_GMM_MODE_BX3;  // force the fallback kernel (tests)
+  if (mode_env && strcmp(mode_env, "bx3") == 0) o->forced_mode = FB_GMM_MODE_BX3;  // force the fallback kernel (tests)
   else if (mode_env && *mode_env && strcmp(mode_env, "fx2") != 0)
     return fb_fail(FB_E_ARG, "FB_GMM_MODE must be fx2 or bx3 (got '%s')", mode_env);
-  // f16x2 images (k_gmm_fx2): two-term f16 split (residual scaled by 2^12), gconst at K position D.
-  // Needs every parameter inside f16's range; a model that does not fit runs on the bf16x3 kernel.
-  const int NKF = (D + 1 + 15) / 16 < 2 ? 2 : (D + 1 + 15) / 16;  // instantiated for 2..6
-  int kx = 0, kx2 = 0, kacc = 0, kl = 0, kq = 0, delta_p = 0, delta_t3 = 0, delta_t2 = 0, delta_t6 = 0;
-  int n_pass = 0, pass_lo[FB_FXW_MAX_PASS + 1] = {1, 1, 1, 1};
-  e->gmm_delta_rms = 0.0;
-  // k_gmm_fx2w scores the models of ONE variance group as deltas from model 0 (the UBM for OSI / SV, the first
-  // speaker for CSI): delta images are built when the kernel's shape conditions hold (fb_gmm_use_wide)
-  // More than FB_FXW_MAX_M models (the LDS holds a tile of 1 + M items and the state of M models) run as SEVERAL
-  // PASSES of the kernel: pass p scores the base model again and its share of the others (FB_FXW_MAX_PASS passes of up
-  // to FB_FXW_MAX_M - 1 delta models each); beyond that the general kernel takes over
-  const int max_wide_models = 1 + (FB_FXW_MAX_M - 1) * FB_FXW_MAX_PASS;
-  if (G == 1 && M > max_wide_models && (C & 31) == 0) {
-    static bool warned = false;
-    if (!warned) {
-      warned = true;
-      fprintf(stderr, "[fakebob_hip] note: %d models in one variance group: k_gmm_fx2w takes at most %d (in %d passes), this "
-                      "system is scored by the general kernel k_gmm_fx2 (about twice the time per model)\n", M, max_wide_models,
-              FB_FXW_MAX_PASS);
-    }
+  if (const char *be = getenv("FB_GMM_DELTA_BUDGET")) {
+    const double v = atof(be);
+    if (!(v >= 1e-7 && v <= 1e-4)) return fb_fail(FB_E_ARG, "FB_GMM_DELTA_BUDGET must be in [1e-7, 1e-4] (got '%s')", be);
+    o->budget = v;
   }
-  const bool want_delta = G == 1 && M >= 2 && M <= max_wide_models && (C & 31) == 0 && NKF == 5 && D + 5 <= 16 * NKF && (D & 3) == 0;  // (K places for the constants' three terms and the frames' reference)
-  if (mode == FB_GMM_MODE_FX2) {
-    const float lim = 32768.0f;
-    float max_q = 0.0f, max_l = 0.0f, max_g = 0.0f;
-    bool finite = true;
-    for (size_t i = 0; i < (size_t)M * C * D; ++i) {
-      max_q = std::max(max_q, 0.5f * fabsf(iv[i]));
-      max_l = std::max(max_l, fabsf(miv[i]));
-      finite = finite && std::isfinite(iv[i]) && std::isfinite(miv[i]);
-    }
-    for (size_t i = 0; i < (size_t)M * C; ++i) {
-      max_g = std::max(max_g, fabsf(gconsts[i]));
-      finite = finite && std::isfinite(gconsts[i]);
-    }
-    if (want_delta && finite) {  // the deltas share the scaling of the full parameters
-      for (int m = 1; m < M; ++m) {
-        for (size_t i = 0; i < (size_t)C * D; ++i) max_l = std::max(max_l, fabsf(miv[(size_t)m * C * D + i] - miv[i]));
-        for (int c = 0; c < C; ++c) max_g = std::max(max_g, fabsf(gconsts[(size_t)m * C + c] - gconsts[c]));
-      }
-    }
-    if (!finite || max_l >= lim || max_g >= lim || max_q >= lim || NKF > 6) {
-      mode = FB_GMM_MODE_BX3;
-    } else {
-      // one accumulator, unscaled residuals: operands are moved up by exact powers of two so that the residuals
-      // of typical values are normal f16 numbers (subnormal ones keep an absolute precision of 2^-25):
-      //   linear:    (mu/sigma^2, gconst) * 2^kl  x  (x, 1) * 2^kx         kl <= 4, kx = 4
-      //   quadratic: -1/(2 sigma^2)      * 2^kq  x  x^2 * 2^kx2           kq + kx2 = kl + kx = kacc
-      auto headroom = [&](float mx) { int k = 0; while (k < 15 && mx * (float)(2 << k) < lim) ++k; return k; };
-      kl = std::min(4, headroom(std::max(max_l, max_g)));
-      kx = 4;
-      kacc = kl + kx;
-      kq = std::min(headroom(max_q), kacc + 2);  // x^2 * 2^-2 at most: keeps |x| < 511 and small squares precise
-      if (kq < kacc - 4) {
-        mode = FB_GMM_MODE_BX3;                   // would need x^2 * 2^5 or more: |x| < 45 is too tight
-      } else {
-        kx2 = kacc - kq;
-      }
-    }
+  if (const char *fe6 = getenv("FB_GMM_DELTA_F6")) o->use_f6 = !(fe6[0] == '0' && fe6[1] == 0);
+  const char *pe = getenv("FB_GMM_DELTA_P");
+  if (pe && *pe) {
+    const int v = atoi(pe);
+    if (!(v >= 1 && v <= 3) && v != 6) return fb_fail(FB_E_ARG, "FB_GMM_DELTA_P must be 1, 2, 3 or 6 (got '%s')", pe);
+    o->forced_p = v;
   }
-  if (mode == FB_GMM_MODE_FX2) {
-    const size_t per_item = (size_t)2 * NKF * 64 * 8;  // f16 values
-    std::vector<uint16_t> fx((size_t)n_tiles * n_items * per_item, 0);
-    auto split2 = [](float v, uint16_t out[2]) {
-      const _Float16 a = (_Float16)v;  // round to nearest even
-      const float r = v - (float)a;    // exact; may be a subnormal f16 (kept by the matrix pipe)
-      const _Float16 b = (_Float16)r;
-      memcpy(&out[0], &a, 2);
-      memcpy(&out[1], &b, 2);
-    };
-    const float qscale = -0.5f * ldexpf(1.0f, kq), lscale = ldexpf(1.0f, kl);
-    for (int t = 0; t < n_tiles; ++t)
-      for (int it = 0; it < n_items; ++it) {
-        uint16_t *im = &fx[((size_t)t * n_items + it) * per_item];
-        const int im_model = item_model[it];
-        for (int cc = 0; cc < 32; ++cc) {
-          const int c = t * 32 + cc;
-          for (int k = 0; k < 16 * NKF; ++k) {
-            uint16_t sp[2] = {0, 0};
-            if (k < D) {
-              if (c < C)
-                split2(im_model < 0 ? qscale * iv[((size_t)group_rep[-1 - im_model] * C + c) * D + k]
-                                    : lscale * miv[((size_t)im_model * C + c) * D + k], sp);
-            } else if (k == D && im_model >= 0) {  // gconst against 2^kx in the frame operand
-              split2(c < C ? lscale * gconsts[(size_t)im_model * C + c] : -60000.0f, sp);  // padding components: exp() == 0
-            }
-            const int ch = k / 16, hh = (k % 16) / 8, i = k % 8, lane = hh * 32 + cc;
-            for (int s2 = 0; s2 < 2; ++s2) im[(((size_t)s2 * NKF + ch) * 64 + lane) * 8 + i] = sp[s2];
-          }
-        }
-      }
-    FBCHK(e->gmm_images_fx.ensure(sizeof(uint16_t) * fx.size()));
-    HIPCHK(hipMemcpy(e->gmm_images_fx.p, fx.data(), sizeof(uint16_t) * fx.size(), hipMemcpyHostToDevice));
-    if (want_delta) {
-      // Delta images of k_gmm_fx2w: items {Q, model 0, delta_1 .. delta_{M-1}} per tile.  Mean-only MAP adaptation
-      // (build_spk_models.py:170, gmm-global-est-map.cc:81) leaves weights and variances alone, so
-      //   ll_m,k(x) = ll_0,k(x) + (gconst_m,k - gconst_0,k) + (means_invvars_m,k - means_invvars_0,k) . x
-      // and the second line is small: the kernel continues the base model's finished accumulator with the delta
-      // item.  The deltas are float32 differences (exact by Sterbenz's lemma for the close values adaptation
-      // produces, correctly rounded otherwise).
-      //
-      // Products per K chunk of the delta items, PER COMPONENT TILE.  P = 2 drops the frames' second f16 term -- an
-      // error of 2^-12 |delta . x| per (frame, component), random in sign from frame to frame --, P = 1 also the
-      // deltas' second term.  b_mk = 2^-12 |delta_mk * (|mu_k| + 3 sigma_k)|_2 bounds the former where component k
-      // matters (x within 3 sigma of its mean).  A frame's error is that of the components that explain it, so the error
-      // of an utterance average is ~c sqrt(sum_k p_k b_mk^2), p_k the share of frames component k explains -- its weight
-      // w_k under the model's own distribution --, with c ~ 0.07 for P = 2 and ~0.14 for P = 1 measured in a float64
-      // numpy model of the split (with equal weights that is the 0.07 / 0.14 rms_k(b) of round 3).
-      // Means-only MAP adaptation moves a component by alpha_k = n_k / (n_k + tau) of the way to the enrolment data's
-      // mean (gmm-global-est-map.cc:31,81): the components the enrolment data occupied move far, the others hardly.  So
-      // the components are SORTED by their contribution w_k max_m b_mk^2 (the order is free under logsumexp; the same
-      // permutation for the quadratic item, the base model and every delta image), and the leading tiles get three
-      // products, the next ones two, the tail one: the smallest sets for which the predicted error of the worst model,
-      //     e^2 = 0.07^2 sum_{k in P = 2 tiles} w_k b_mk^2 + 0.14^2 sum_{k in P = 1 tiles} w_k b_mk^2,
-      // stays below (6e-6)^2 -- under half a float32 ulp of the ~-150 results and inside the ~3.3e-6 float32
-      // accumulation error every variant carries (tests/test_gpu_parity.py).  Models adapted far everywhere (enrolment
-      // on many frames, a small tau, unrelated means) get three products in every tile -- the arithmetic of the non-delta
-      // kernels.
-      std::vector<double> b2((size_t)(M - 1) * C, 0.0), wk(C, 0.0), key(C, 0.0);
-      {
-        const double LOG2PI = 1.8378770664093454835606594728112;
-        double wsum = 0.0;
-        for (int c = 0; c < C; ++c) {  // w_k from the base model's gconst (DiagGmm::ComputeGconsts)
-          double lw = (double)gconsts[c] + 0.5 * D * LOG2PI;
-          for (int k = 0; k < D; ++k) {
-            const double ivk = (double)iv[(size_t)c * D + k], mk = (double)miv[(size_t)c * D + k];
-            lw += 0.5 * (mk * mk / ivk - log(ivk));
-          }
-          wk[c] = std::isfinite(lw) ? exp(std::min(lw, 0.0)) : 0.0;
-          wsum += wk[c];
-        }
-        for (int c = 0; c < C; ++c) wk[c] = wsum > 0.0 ? wk[c] / wsum : 1.0 / C;
-        for (int m = 1; m < M; ++m)
-          for (int c = 0; c < C; ++c) {
-            double sq = 0.0;
-            for (int k = 0; k < D; ++k) {
-              const double ivk = (double)iv[(size_t)c * D + k];
-              const double reach = (fabs((double)miv[(size_t)c * D + k]) + 3.0 * sqrt(ivk)) / ivk;  // |mu| + 3 sigma
-              const double dl = (double)miv[((size_t)m * C + c) * D + k] - (double)miv[(size_t)c * D + k];
-              sq += dl * dl * reach * reach;
-            }
-            b2[(size_t)(m - 1) * C + c] = ldexp(sq, -24);
-            // (the floor keeps a component no frame is expected in from hiding an arbitrarily large shift in the tail)
-            key[c] = std::max(key[c], std::max(wk[c], 0.01 / C) * b2[(size_t)(m - 1) * C + c]);
-          }
-      }
-      std::vector<int> perm(C);
-      for (int c = 0; c < C; ++c) perm[c] = c;
-      std::stable_sort(perm.begin(), perm.end(), [&](int x, int y) { return key[x] > key[y]; });
-      // e1[t] / e2[t]: worst model's sum over the components of the tiles >= t / of tile t alone
-      std::vector<double> tail(n_tiles + 1, 0.0);
-      std::vector<std::vector<double>> tsum(M - 1, std::vector<double>(n_tiles, 0.0));
-      for (int m = 0; m < M - 1; ++m)
-        for (int t = 0; t < n_tiles; ++t)
-          for (int cc = 0; cc < 32; ++cc) {
-            const int c = perm[t * 32 + cc];
-            tsum[m][t] += std::max(wk[c], 0.01 / C) * b2[(size_t)m * C + c];
-          }
-      auto worst_sum = [&](int t_lo, int t_hi) {
-        double w = 0.0;
-        for (int m = 0; m < M - 1; ++m) {
-          double a = 0.0;
-          for (int t = t_lo; t < t_hi; ++t) a += tsum[m][t];
-          w = std::max(w, a);
-        }
-        return w;
-      };
-      // FB_GMM_DELTA_BUDGET: the error budget of the rule (default 6e-6: float32-equivalent scores).  north_star asks
-      // for 1e-4 against the reference; a caller who wants only that can say so (e.g. 5e-5) and gets two products where
-      // the default insists on three -- measured and reported separately by bench.py, never the headline
-      double budget = 6.0e-6;
-      if (const char *be = getenv("FB_GMM_DELTA_BUDGET")) {
-        const double v = atof(be);
-        if (!(v >= 1e-7 && v <= 1e-4)) return fb_fail(FB_E_ARG, "FB_GMM_DELTA_BUDGET must be in [1e-7, 1e-4] (got '%s')", be);
-        budget = v;
-      }
-      // The F6 class (round 4): the two products P = 1 leaves out -- delta's second term against the frames' leading
-      // term, delta's leading term against the frames' second -- taken in block-scaled fp6 / fp4 by four
-      // v_mfma_scale_f32_32x32x64_f8f6f4 per 32-frame half (K = 64 each at the price of one K = 16 f16 product: ~20 ns,
-      // tools/probes/f6_mfma_probe.hip) instead of ten f16 products; operands and their layout: the F6 item below.
-      // What an utterance average keeps of their rounding, measured on the realistic enrolment with the class in every
-      // tile: max |err| 7.1e-6 against 3.2e-4 for P = 1, 6.8e-5 for P = 2 and 3.3e-6 for P = 3 (the float32 accumulation
-      // error every variant carries) -- c = 0.003 in the model above, cheaper AND closer than P = 2, which the rule
-      // therefore no longer chooses (FB_GMM_DELTA_F6=0 brings the earlier rule back: P = 2 in the middle, no F6 tiles).
-      // (ce6: 0.003 reproduced the MEAN of the measured cases; the worst one -- the class in every tile of the realistic
-      //  enrolment, 8 utterances: 7.1e-6 in all, i.e. sqrt(7.1^2 - 3.3^2) = 6.3e-6 of its own beside the float32 floor --
-      //  sat 20 % above the prediction: the parameters' rounding is the same for every frame and does not average out
-      //  the way the sqrt(sum w b^2) model assumes.  Round 5 calibrates on that worst case: 0.0036.)
-      const double budget2 = budget * budget, ce1 = 0.14 * 0.14, ce2 = 0.07 * 0.07, ce6 = 0.0036 * 0.0036;
-      bool use_f6 = true;
-      if (const char *fe6 = getenv("FB_GMM_DELTA_F6")) use_f6 = !(fe6[0] == '0' && fe6[1] == 0);
-      // tiles [0, t3): P = 3, [t3, t6): F6, [t6, t2): P = 2, [t2, n_tiles): P = 1
-      int t2 = n_tiles, t3 = n_tiles, t6 = n_tiles;
-      while (t2 > 0 && ce1 * worst_sum(t2 - 1, n_tiles) <= 0.75 * budget2) --t2;  // (the P = 1 tail may use 3/4 of the budget)
-      t3 = t6 = t2;
-      {
-        const double left = budget2 - ce1 * worst_sum(t2, n_tiles);
-        if (use_f6) {
-          while (t3 > 0 && ce6 * worst_sum(t3 - 1, t2) <= left) --t3;
-          t6 = t2;
-        } else {
-          while (t3 > 0 && ce2 * worst_sum(t3 - 1, t2) <= left) --t3;
-          t6 = t3;
-        }
-      }
-      const char *pe = getenv("FB_GMM_DELTA_P");  // tests / worst-case benchmark: the same class in every tile (6 = F6)
-      if (pe && *pe) {
-        const int v = atoi(pe);
-        if (!(v >= 1 && v <= 3) && v != 6) return fb_fail(FB_E_ARG, "FB_GMM_DELTA_P must be 1, 2, 3 or 6 (got '%s')", pe);
-        t3 = v == 3 ? n_tiles : 0;
-        t6 = v == 6 ? n_tiles : t3;
-        t2 = v >= 2 ? n_tiles : 0;
-      }
-      {  // (reported by fb_gmm_kernel_variant: the equal-weight statistic of round 3)
-        double sumsq = 0.0;
-        for (double v : b2) sumsq += v;
-        e->gmm_delta_rms = sqrt(sumsq / ((double)(M - 1) * C));
-      }
-      auto tile_p = [&](int t) { return t < t3 ? 3 : (t < t6 ? 6 : (t < t2 ? 2 : 1)); };
-      int want_p = 1;  // what most tiles run
-      {
-        const int cnt[4] = {n_tiles - t2, t2 - t6, t3, t6 - t3}, cls[4] = {1, 2, 3, 6};
-        int best = 0;
-        for (int i = 1; i < 4; ++i)
-          if (cnt[i] > cnt[best]) best = i;
-        want_p = cls[best];
-      }
+  return FB_OK;
+}
 
-      // The images are in LOG2 units: every parameter is multiplied by log2 e in float64 and then split into its f16
-      // terms -- the accumulators of k_gmm_fx2w then hold the exponent of 2 directly and its logsumexp update needs
-      // no multiplication (gmm_wide_kernel.hip).  There is no common power-of-two factor to undo either; instead every
-      // DIMENSION d is balanced by an exact power of two of its own: the frames' x_d is multiplied by 2^kd[d], the
-      // linear parameters by 2^-kd[d] (x_d^2 by 2^kq[d], the quadratic ones by 2^-kq[d]), chosen from the spread
-      // sd[d] of the dimension under the base model so that |x_d| 2^kd ~ 1 and x_d^2 2^kq ~ 1: the parameters -- whose
-      // rounding is the same for every frame -- then sit around 1 .. 10 where both f16 terms are normal numbers (22
-      // significant bits), the frames keep theirs down to |x_d| = sd/8 and an absolute 2^-25 below.
-      // The constants (gconst of the base model, its difference for the others) stand in the K padding against 1.0 in
-      // the frame operand, as THREE f16 terms at K = D, D + 1, D + 2 of the FIRST parameter term: they come out with 33
-      // bits whatever P.  With P = 1 a delta item's linear parameters are their leading f16 term only; what that
-      // leaves out at the component's own mean, sum_d (delta' - f16(delta'))_kd mu'_kd -- a constant per (model,
-      // component), the same for every frame the component explains --, goes into that constant.
-      const double L2E = 1.4426950408889634;
-      auto f16r = [](double v) { return (double)(_Float16)v; };  // round to nearest even
-      auto put16 = [](double v, uint16_t *out) { const _Float16 a = (_Float16)v; memcpy(out, &a, 2); };
-      std::vector<int> kd(16 * NKF, 0), kq(16 * NKF, 0);
-      bool fits = true;
-      for (int k = 0; k < D; ++k) {
-        double m1 = 0.0, m2 = 0.0, vs = 0.0;  // spread of dimension k: mean component variance + variance of the means
-        for (int c = 0; c < C; ++c) {
-          const double var = 1.0 / (double)iv[(size_t)c * D + k], mu = (double)miv[(size_t)c * D + k] * var;
-          m1 += mu; m2 += mu * mu; vs += var;
-        }
-        const double sd2 = vs / C + std::max(0.0, m2 / C - (m1 / C) * (m1 / C));
-        const int e2 = sd2 > 0.0 && std::isfinite(sd2) ? (int)lrint(-0.5 * log2(sd2)) : 0;
-        kd[k] = std::min(24, std::max(-24, e2));
-        kq[k] = 2 * kd[k];
-        double pl = 0.0, pq = 0.0;  // the largest scaled parameters must stay inside f16's range
-        for (int m = 0; m < M; ++m)
-          for (int c = 0; c < C; ++c) pl = std::max(pl, fabs((double)miv[((size_t)m * C + c) * D + k]));
-        for (int c = 0; c < C; ++c) pq = std::max(pq, 0.5 * (double)iv[(size_t)c * D + k]);
-        fits = fits && ldexp(L2E * pl, -kd[k]) < 60000.0 && ldexp(L2E * pq, -kq[k]) < 60000.0;
-      }
-      for (int c = 0; c < M * C; ++c) fits = fits && L2E * fabs((double)gconsts[c]) < 60000.0;
-      // passes: the M - 1 delta models dealt evenly over ceil((M - 1) / (FB_FXW_MAX_M - 1)) launches
-      n_pass = (M - 1 + FB_FXW_MAX_M - 2) / (FB_FXW_MAX_M - 1);
-      for (int p = 0; p <= n_pass; ++p) pass_lo[p] = 1 + (int)(((long long)(M - 1) * p) / n_pass);
-      DevBuf *pass_buf[FB_FXW_MAX_PASS] = {&e->gmm_images_fd, &e->gmm_images_fd2, &e->gmm_images_fd3};
-      for (int pass = 0; fits && pass < n_pass; ++pass) {  // (k_gmm_fx2 scores a model that does not fit)
-        const int n_items_p = 2 + pass_lo[pass + 1] - pass_lo[pass];  // Q, base, the pass's deltas
-        std::vector<uint16_t> fd((size_t)n_tiles * n_items_p * per_item, 0);
-        for (int t = 0; t < n_tiles; ++t)
-          for (int it = 0; it < n_items_p; ++it) {
-            uint16_t *im = &fd[((size_t)t * n_items_p + it) * per_item];
-            const int m = it < 2 ? it - 1 : pass_lo[pass] + it - 2;  // -1: the quadratic item, 0: the base model
-            auto at = [&](int term, int k, int cc) -> uint16_t * {
-              const int ch = k / 16, hh = (k % 16) / 8, i = k % 8, lane = hh * 32 + cc;
-              return &im[(((size_t)term * NKF + ch) * 64 + lane) * 8 + i];
-            };
-            for (int cc = 0; cc < 32; ++cc) {
-              const int c = perm[t * 32 + cc];
-              double cst = m == 0 ? L2E * (double)gconsts[c]
-                                  : (m > 0 ? L2E * (double)(gconsts[(size_t)m * C + c] - gconsts[c]) : 0.0);
-              double vv[96] = {0.0}, aa[96] = {0.0};  // the linear parameters and their leading f16 terms (F6 items)
-              for (int k = 0; k < D; ++k) {
-                double v;
-                if (m < 0) v = ldexp(L2E * (double)(-0.5f * iv[(size_t)c * D + k]), -kq[k]);
-                else if (m == 0) v = ldexp(L2E * (double)miv[(size_t)c * D + k], -kd[k]);
-                else v = ldexp(L2E * (double)(miv[((size_t)m * C + c) * D + k] - miv[(size_t)c * D + k]), -kd[k]);
-                const double a = f16r(v);
-                put16(a, at(0, k, cc));
-                vv[k] = v;
-                aa[k] = a;
-                if (m > 0 && tile_p(t) == 6) continue;  // (the second half of the item holds the fp6 operands: below)
-                put16(v - a, at(1, k, cc));
-                if (m > 0 && tile_p(t) == 1)  // the dropped second term at the component's mean (mu' = mu 2^kd)
-                  cst += (v - a) * ldexp((double)miv[(size_t)c * D + k] / (double)iv[(size_t)c * D + k], kd[k]);
-              }
-              if (m > 0 && tile_p(t) == 6) {
-                // F6 item: [0, 5 KB) the leading f16 term as above; then, per lane (kh, cc) -- the lane that holds the
-                // component's K places 8 kh .. 8 kh + 7 of every chunk, as in the f16 fragments -- blocks of 32 codes with
-                // one power-of-two scale each (value u in bits [6u, 6u + 6) resp. [4u, 4u + 4) of the lane's operand):
-                //   block 0 (e2m3): u = 8 c + i, c < 4: delta's SECOND term d2 at dimension 16 c + 8 kh + i  (against x_1)
-                //   block L (e2m1): the same places: what block 0's codes leave of d2                     (against x_1)
-                //   block 1 (e2m3): the same places: delta's LEADING term times 2^-12                (against x_2 2^12)
-                //   block 2 (e2m3, lanes kh = 0 only -- the frames' side is zero for kh = 1 --): u < 8: d2 at dimension
-                //            64 + u; 8 <= u < 16: leading term 2^-12 at 64 + u - 8; 16 <= u < 24: what the first eight
-                //            codes leave of d2; zero where the dimension is past D and for u >= 24
-                // The parameters are the same for every frame, so what their rounding leaves does not average out over
-                // an utterance the way the frames' does: d2 in ONE e2m3 term left 1.45e-5 of an utterance average in the
-                // float64 model of this class (tools/probes/f6_corr_emul.py, scratch of round 4: the frames' 4 bits and
-                // the leading term's cost ~1e-6 each), the second term brings that to 3.8e-6.  (The 2^-12 / 2^12 pair
-                // keeps block 2's kinds of values inside one scale's range on both sides.)
-                // Bytes: 5120 block 0 bits 0 .. 127 [64] x 16, 6144 its bits 128 .. 191 [64] x 8, 6656 / 7680 block 1
-                // likewise, 8192 block L [64] x 16, 9216 / 9728 block 2 [32] x 16 / [32] x 8, 9984 [64] x 4: the scale
-                // bytes (e8m0: 2^(byte - 127)) of blocks 0, 1, L, 2.
-                uint8_t *ib = reinterpret_cast<uint8_t *>(im);
-                const int DC = 64;  // dimensions of the chunks 0 .. 3
-                auto scale_for = [](const double *val, int n, double top) {  // smallest e with max |val| 2^-e <= top
-                  double mx = 0.0;
-                  for (int u = 0; u < n; ++u) mx = std::max(mx, fabs(val[u]));
-                  int ex = -126;
-                  if (mx > 0.0) {
-                    ex = (int)ceil(log2(mx / top));
-                    while (ldexp(mx, -ex) > top) ++ex;
-                    while (ldexp(mx, -(ex - 1)) <= top) --ex;
-                    ex = std::min(127, std::max(-126, ex));
-                  }
-                  return ex;
-                };
-                auto code_e2m3 = [](double v, int ex, double *got) {  // nearest code (ties to even), |v| 2^-ex <= 7.5
-                  const double q = fabs(ldexp(v, -ex));
-                  const double step = q < 2.0 ? 0.125 : (q < 4.0 ? 0.25 : 0.5), base = q < 2.0 ? 0.0 : (q < 4.0 ? 2.0 : 4.0);
-                  int code = std::min((q < 2.0 ? 0 : (q < 4.0 ? 16 : 24)) + (int)nearbyint((q - base) / step), 31);
-                  const double dq = code < 16 ? code * 0.125 : (code < 24 ? 2.0 + (code - 16) * 0.25 : 4.0 + (code - 24) * 0.5);
-                  *got = (v < 0.0 ? -1.0 : 1.0) * ldexp(dq, ex);
-                  return code | (v < 0.0 ? 32 : 0);
-                };
-                auto code_e2m1 = [](double v, int ex, double *got) {  // 0, .5, 1, 1.5, 2, 3, 4, 6
-                  const double q = fabs(ldexp(v, -ex));
-                  const double step = q < 2.0 ? 0.5 : (q < 4.0 ? 1.0 : 2.0), base = q < 2.0 ? 0.0 : (q < 4.0 ? 2.0 : 4.0);
-                  int code = std::min((q < 2.0 ? 0 : (q < 4.0 ? 4 : 6)) + (int)nearbyint((q - base) / step), 7);
-                  const double dq = code < 4 ? code * 0.5 : (code < 6 ? 2.0 + (code - 4) * 1.0 : 4.0 + (code - 6) * 2.0);
-                  *got = (v < 0.0 ? -1.0 : 1.0) * ldexp(dq, ex);
-                  return code | (v < 0.0 ? 8 : 0);
-                };
-                auto put6 = [](uint64_t (&bits)[3], int u, int code) {
-                  const int bit = 6 * u;
-                  bits[bit >> 6] |= (uint64_t)code << (bit & 63);
-                  if ((bit & 63) > 58) bits[(bit >> 6) + 1] |= (uint64_t)code >> (64 - (bit & 63));
-                };
-                auto mean_at = [&](int k) { return ldexp((double)miv[(size_t)c * D + k] / (double)iv[(size_t)c * D + k], kd[k]); };
-                for (int kh = 0; kh < 2; ++kh) {
-                  const int lane = kh * 32 + cc;
-                  uint32_t scales = 0;
-                  int dim[32];
-                  double v2[32], v1[32], left[32], got;
-                  for (int u = 0; u < 32; ++u) {
-                    const int k = 16 * (u / 8) + 8 * kh + (u % 8);
-                    dim[u] = k < D && k < DC ? k : -1;
-                    v2[u] = dim[u] < 0 ? 0.0 : vv[k] - aa[k];
-                    v1[u] = dim[u] < 0 ? 0.0 : ldexp(aa[k], -12);
-                  }
-                  {  // block 0 and block L
-                    const int ex = scale_for(v2, 32, 7.5);
-                    uint64_t bits[3] = {0, 0, 0};
-                    for (int u = 0; u < 32; ++u) {
-                      put6(bits, u, code_e2m3(v2[u], ex, &got));
-                      left[u] = v2[u] - got;
-                    }
-                    memcpy(ib + 5120 + (size_t)lane * 16, &bits[0], 16);
-                    memcpy(ib + 6144 + (size_t)lane * 8, &bits[2], 8);
-                    scales |= (uint32_t)(ex + 127);
-                    const int exl = scale_for(left, 32, 6.0);
-                    uint64_t lb[2] = {0, 0};
-                    for (int u = 0; u < 32; ++u) {
-                      lb[(4 * u) >> 6] |= (uint64_t)code_e2m1(left[u], exl, &got) << ((4 * u) & 63);
-                      if (dim[u] >= 0) cst += (left[u] - got) * mean_at(dim[u]);  // what both terms leave, at the component's mean
-                    }
-                    memcpy(ib + 8192 + (size_t)lane * 16, lb, 16);
-                    scales |= (uint32_t)(exl + 127) << 16;
-                  }
-                  {  // block 1
-                    const int ex = scale_for(v1, 32, 7.5);
-                    uint64_t bits[3] = {0, 0, 0};
-                    for (int u = 0; u < 32; ++u) put6(bits, u, code_e2m3(v1[u], ex, &got));
-                    memcpy(ib + 6656 + (size_t)lane * 16, &bits[0], 16);
-                    memcpy(ib + 7680 + (size_t)lane * 8, &bits[2], 8);
-                    scales |= (uint32_t)(ex + 127) << 8;
-                  }
-                  if (kh == 0) {  // block 2: the dimensions of chunk 4
-                    double val[32] = {0.0};
-                    for (int u = 0; u < 8; ++u) {
-                      const int k = DC + u;
-                      if (k < D) { val[u] = vv[k] - aa[k]; val[8 + u] = ldexp(aa[k], -12); }
-                    }
-                    const int ex = scale_for(val, 16, 7.5);
-                    uint64_t bits[3] = {0, 0, 0};
-                    for (int u = 0; u < 16; ++u) {
-                      put6(bits, u, code_e2m3(val[u], ex, &got));
-                      if (u < 8) val[16 + u] = val[u] - got;
-                    }
-                    for (int u = 16; u < 24; ++u) {
-                      put6(bits, u, code_e2m3(val[u], ex, &got));
-                      if (DC + u - 16 < D) cst += (val[u] - got) * mean_at(DC + u - 16);
-                    }
-                    memcpy(ib + 9216 + (size_t)cc * 16, &bits[0], 16);
-                    memcpy(ib + 9728 + (size_t)cc * 8, &bits[2], 8);
-                    scales |= (uint32_t)(ex + 127) << 24;
-                  } else {
-                    scales |= 127u << 24;
-                  }
-                  memcpy(ib + 9984 + (size_t)lane * 4, &scales, 4);
-                }
-              }
-              if (m < 0) {  // the frames' reference stands in their x^2 operand as -(R mod 2048), -(R div 2048) (gmm_wide_kernel.hip)
-                put16(1.0, at(0, D + 3, cc));
-                put16(2048.0, at(0, D + 4, cc));
-              }
-              if (m >= 0) {
-                const double c1 = f16r(cst), c2 = f16r(cst - c1);
-                put16(c1, at(0, D, cc));
-                put16(c2, at(0, D + 1, cc));
-                put16(cst - c1 - c2, at(0, D + 2, cc));
-              }
-            }
-          }
-        FBCHK(pass_buf[pass]->ensure(sizeof(uint16_t) * fd.size() + 4096));  // k_gmm_fx2w fetches whole 1 KB pieces: up to 3 past the end
-        HIPCHK(hipMemcpy(pass_buf[pass]->p, fd.data(), sizeof(uint16_t) * fd.size(), hipMemcpyHostToDevice));
-      }
-      if (fits) {
-        // The anchors of k_gmm_fx2w's reference: the base model's FB_FXW_ANCHORS widest components.  The log2-likelihood
-        // of a frame under one of them is a lower bound of the base model's log2 sum; every other model's sum is at least
-        // that minus |dgconst| + |dlinear|_2 |x|_2 (Cauchy-Schwarz on the delta line above, in the frames' balanced units),
-        // whose two maxima over the models go along.  Table: [0, 80) the frames' balancing factors 2^kd, [80, 160) those of
-        // their squares 2^kq, then per anchor {80 linear terms with gconst at D, 80 quadratic terms -- in balanced units:
-        // the kernel evaluates them on the leading f16 term of its frame operand, hence the + 2 --, max |dgconst| + 2,
-        // max |dlinear|_2, 0, 0}.
-        std::vector<int> order(C);
-        std::vector<double> vol(C);
-        for (int c = 0; c < C; ++c) {
-          order[c] = c;
-          double lv = 0.0;
-          for (int k = 0; k < D; ++k) lv -= log((double)iv[(size_t)c * D + k]);
-          vol[c] = lv;
-        }
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return vol[a] > vol[b]; });
-        const int W = 16 * NKF;
-        std::vector<float> an(2 * W + FB_FXW_ANCHORS * (2 * W + 4), 0.0f);
-        for (int k = 0; k < W; ++k) {
-          an[k] = ldexpf(1.0f, kd[k]);
-          an[W + k] = ldexpf(1.0f, kq[k]);
-        }
-        for (int a = 0; a < FB_FXW_ANCHORS; ++a) {
-          const int ks = order[std::min(a, C - 1)];
-          float *at = &an[2 * W + (size_t)a * (2 * W + 4)];
-          for (int k = 0; k < D; ++k) {
-            at[k] = (float)ldexp(L2E * (double)miv[(size_t)ks * D + k], -kd[k]);
-            at[W + k] = (float)ldexp(L2E * (double)(-0.5f * iv[(size_t)ks * D + k]), -kq[k]);
-          }
-          at[D] = (float)(L2E * (double)gconsts[ks]);
-          double mg = 0.0, ml = 0.0;
-          for (int m = 1; m < M; ++m) {
-            double l2 = 0.0;
-            for (int k = 0; k < D; ++k) {
-              const double dl = ldexp((double)miv[((size_t)m * C + ks) * D + k] - (double)miv[(size_t)ks * D + k], -kd[k]);
-              l2 += dl * dl;
-            }
-            ml = std::max(ml, L2E * sqrt(l2));
-            mg = std::max(mg, L2E * fabs((double)gconsts[(size_t)m * C + ks] - (double)gconsts[ks]));
-          }
-          at[2 * W] = (float)(mg * 1.000001 + 4.0);
-          at[2 * W + 1] = (float)(ml * 1.000001);
-        }
-        {  // f16 copies of the anchors' 2 x W terms behind the float table: what the kernel's packed dot products read.
-           // The bound stays a bound: the rounding of the copies and of the f16 squares (2^-11 each, relative to terms
-           // that add up to a few hundred at most) is inside the + 2 of the slack above
-          const size_t nf = an.size();
-          an.resize(nf + (size_t)FB_FXW_ANCHORS * W, 0.0f);
-          uint16_t *hp = reinterpret_cast<uint16_t *>(&an[nf]);
-          for (int a = 0; a < FB_FXW_ANCHORS; ++a)
-            for (int k = 0; k < 2 * W; ++k) {
-              const float v = an[2 * W + (size_t)a * (2 * W + 4) + k];
-              fits = fits && fabsf(v) < 60000.0f;
-              const _Float16 hv = (_Float16)v;
-              memcpy(&hp[(size_t)a * 2 * W + k], &hv, 2);
-            }
-        }
-        FBCHK(e->gmm_anchor.ensure(sizeof(float) * an.size()));
-        HIPCHK(hipMemcpy(e->gmm_anchor.p, an.data(), sizeof(float) * an.size(), hipMemcpyHostToDevice));
-        if (fits) { delta_p = want_p; delta_t3 = t3; delta_t2 = t2; delta_t6 = t6; }
-      }
-    }
-  }
-  if (mode == FB_GMM_MODE_BX3) {
-    const size_t per_item = (size_t)3 * NK * 64 * 8;  // bf16 values
-    std::vector<uint16_t> bx((size_t)n_tiles * n_items * per_item, 0);
-    auto split3 = [](float v, uint16_t out[3]) {
-      for (int s = 0; s < 3; ++s) {
-        uint32_t u;
-        memcpy(&u, &v, 4);
-        u = (u + 0x7fffu + ((u >> 16) & 1u)) & 0xffff0000u;  // round to nearest even, 8 significant bits
-        float t;
-        memcpy(&t, &u, 4);
-        out[s] = (uint16_t)(u >> 16);
-        v -= t;  // exact
-      }
-    };
-    for (int t = 0; t < n_tiles; ++t)
-      for (int it = 0; it < n_items; ++it) {
-        uint16_t *im = &bx[((size_t)t * n_items + it) * per_item];
-        const int im_model = item_model[it];
-        for (int cc = 0; cc < 32; ++cc) {
-          const int c = t * 32 + cc;
-          for (int k = 0; k < 16 * NK; ++k) {
-            float v = 0.0f;
-            if (k < D) {
-              if (c < C)
-                v = im_model < 0 ? -0.5f * iv[((size_t)group_rep[-1 - im_model] * C + c) * D + k]
-                                 : miv[((size_t)im_model * C + c) * D + k];
-            }
-            uint16_t sp[3] = {0, 0, 0};
-            if (k < D) {
-              split3(v, sp);
-            } else if (k < D + 3 && im_model >= 0) {  // gconst term k-D against 1.0 in the frame operand
-              uint16_t gs[3];
-              split3(c < C ? gconsts[(size_t)im_model * C + c] : -1.0e30f, gs);
-              sp[0] = gs[k - D];
-            }
-            const int ch = k / 16, hh = (k % 16) / 8, i = k % 8, lane = hh * 32 + cc;
-            for (int s = 0; s < 3; ++s) im[(((size_t)s * NK + ch) * 64 + lane) * 8 + i] = sp[s];
-          }
-        }
-      }
-    FBCHK(e->gmm_images_bx.ensure(sizeof(uint16_t) * bx.size()));
-    HIPCHK(hipMemcpy(e->gmm_images_bx.p, bx.data(), sizeof(uint16_t) * bx.size(), hipMemcpyHostToDevice));
-  }
-  std::vector<int> im_dev(item_model);
-  FBCHK(e->gmm_items.ensure(sizeof(int) * im_dev.size()));
-  HIPCHK(hipMemcpy(e->gmm_items.p, im_dev.data(), sizeof(int) * im_dev.size(), hipMemcpyHostToDevice));
+// steps 1 and 2 of fb_load_gmm: the argument checks and the host images.  e == nullptr (fb_debug_prepare_gmm): no
+// front end to agree with
+static int prepare_gmm(const fb_engine *e, int M, int C, int D, const float *gconsts, const float *miv, const float *iv,
+                       FbGmmPrepared *out) {
+  if (!gconsts || !miv || !iv) return fb_fail(FB_E_ARG, "null argument");
+  if (M <= 0 || C <= 0 || D <= 0) return fb_fail(FB_E_ARG, "bad GMM shape M=%d C=%d D=%d", M, C, D);
+  if (M > 60) return fb_fail(FB_E_ARG, "at most 60 models per engine (got %d)", M);
+  if (e && (!e->have_fe || e->fe.dim != D))
+    return fb_fail(FB_E_ARG, "GMM dim %d != front-end feature dim %d", D, e->have_fe ? e->fe.dim : -1);
+  FbGmmPrepOptions opt;
+  FBCHK(gmm_options_from_env(&opt));
+  std::string err;
+  const int rc = fb_prepare_gmm(FbGmmParams{M, C, D, gconsts, miv, iv}, opt, out, &err);
+  return rc == FB_OK ? FB_OK : fb_fail(rc, "%s", err.c_str());
+}
+
+// steps 4 to 6: ensure every buffer, upload, assign the engine's fields (the stream is idle: the caller synchronised)
+static int commit_gmm(fb_engine *e, const FbGmmPrepared &p, const float *gconsts, const float *miv, const float *iv) {
+  const int M = p.M, C = p.C, D = p.D;
+  DevBuf *pass_buf[FB_FXW_MAX_PASS] = {&e->gmm_images_fd, &e->gmm_images_fd2, &e->gmm_images_fd3};
+  auto bytes = [](const auto &v) { return sizeof(v[0]) * v.size(); };
+  if (!p.fx.empty()) FBCHK(e->gmm_images_fx.ensure(bytes(p.fx)));
+  if (!p.bx.empty()) FBCHK(e->gmm_images_bx.ensure(bytes(p.bx)));
+  for (int q = 0; q < FB_FXW_MAX_PASS; ++q)
+    if (!p.fd[q].empty()) FBCHK(pass_buf[q]->ensure(bytes(p.fd[q]) + 4096));  // k_gmm_fx2w fetches whole 1 KB pieces: up to 3 past the end
+  if (!p.anchor.empty()) FBCHK(e->gmm_anchor.ensure(bytes(p.anchor)));
+  FBCHK(e->gmm_items.ensure(bytes(p.item_model)));
+  FBCHK(e->zmean.ensure(sizeof(double) * M));
+  FBCHK(e->zstd.ensure(sizeof(double) * M));
+  auto upload = [](DevBuf &dst, const auto &v) {
+    return v.empty() ? hipSuccess : hipMemcpy(dst.p, v.data(), sizeof(v[0]) * v.size(), hipMemcpyHostToDevice);
+  };
+  HIPCHK(upload(e->gmm_images_fx, p.fx));
+  HIPCHK(upload(e->gmm_images_bx, p.bx));
+  for (int q = 0; q < FB_FXW_MAX_PASS; ++q) HIPCHK(upload(*pass_buf[q], p.fd[q]));
+  HIPCHK(upload(e->gmm_anchor, p.anchor));
+  HIPCHK(upload(e->gmm_items, p.item_model));
+  // default system: OSI (UBM first) without z-norm
+  e->h_zmean.assign(M, 0.0);
+  e->h_zstd.assign(M, 1.0);
+  HIPCHK(upload(e->zmean, e->h_zmean));
+  HIPCHK(upload(e->zstd, e->h_zstd));
+  using Images = decltype(e->gmm.images_fd);
   FbGmmDev &g = e->gmm;
-  g.M = M; g.C = C; g.D = D; g.n_tiles = n_tiles; g.n_items = n_items;
-  g.mode = mode; g.NK = NK;
+  g.M = M; g.C = C; g.D = D; g.n_tiles = p.n_tiles; g.n_items = p.n_items;
+  g.mode = p.mode; g.NK = p.NK;
   g.text_scores = e->cfg.text_scores;
   g.only_if = nullptr;
   g.fxw_sub = 0;
-  g.images_bx = reinterpret_cast<decltype(g.images_bx)>(e->gmm_images_bx.p);
-  g.NKF = NKF;
-  g.kx = kx; g.kx2 = kx2; g.kacc = kacc;
-  g.images_fx = reinterpret_cast<decltype(g.images_fx)>(e->gmm_images_fx.p);
-  g.delta_p = mode == FB_GMM_MODE_FX2 ? delta_p : 0;
-  g.delta_t3 = g.delta_p ? delta_t3 : 0;
-  g.delta_t2 = g.delta_p ? delta_t2 : 0;
-  g.delta_t6 = g.delta_p ? delta_t6 : 0;
-  g.images_fd = g.delta_p ? reinterpret_cast<decltype(g.images_fd)>(e->gmm_images_fd.p) : nullptr;
-  g.n_pass = g.delta_p ? n_pass : 0;
+  g.images_bx = reinterpret_cast<Images>(e->gmm_images_bx.p);
+  g.NKF = p.NKF;
+  g.kx = p.kx; g.kx2 = p.kx2; g.kacc = p.kacc;
+  g.images_fx = reinterpret_cast<Images>(e->gmm_images_fx.p);
+  g.delta_p = p.delta_p; g.delta_t3 = p.delta_t3; g.delta_t2 = p.delta_t2; g.delta_t6 = p.delta_t6;
+  g.images_fd = g.delta_p ? reinterpret_cast<Images>(e->gmm_images_fd.p) : nullptr;
+  g.n_pass = p.n_pass;
   g.pass_first = 1;
-  {
-    DevBuf *pb[FB_FXW_MAX_PASS] = {&e->gmm_images_fd, &e->gmm_images_fd2, &e->gmm_images_fd3};
-    for (int p = 0; p < FB_FXW_MAX_PASS; ++p) {
-      g.pass_images[p] = (g.delta_p && p < n_pass) ? reinterpret_cast<decltype(g.images_fd)>(pb[p]->p) : nullptr;
-      g.pass_lo[p] = pass_lo[p];
-    }
-    g.pass_lo[FB_FXW_MAX_PASS] = pass_lo[FB_FXW_MAX_PASS];
-  }
+  for (int q = 0; q < FB_FXW_MAX_PASS; ++q) g.pass_images[q] = q < p.n_pass ? reinterpret_cast<Images>(pass_buf[q]->p) : nullptr;
+  for (int q = 0; q <= FB_FXW_MAX_PASS; ++q) g.pass_lo[q] = p.pass_lo[q];
   g.anchor = g.delta_p ? e->gmm_anchor.as<float>() : nullptr;
   g.item_model = e->gmm_items.as<int>();
-  g.item_model_host_q_first = (G == 1) ? 1 : 0;  // one group: the list built above is {Q, 0, 1, ..., M-1}
+  g.item_model_host_q_first = (p.n_groups == 1) ? 1 : 0;  // one group: the item list is {Q, 0, 1, ..., M-1}
+  e->gmm_delta_rms = p.delta_rms;
   // the white-box path differentiates the plain parameters: kept here, uploaded by its first call, freed on reload
   e->h_wb_gc.assign(gconsts, gconsts + (size_t)M * C);
   e->h_wb_miv.assign(miv, miv + (size_t)M * C * D);
   e->h_wb_iv.assign(iv, iv + (size_t)M * C * D);
   e->wb_uploaded = false;
   e->wb_gc.release(); e->wb_miv.release(); e->wb_iv.release();
-  e->n_groups = G;
+  e->n_groups = p.n_groups;
   e->have_gmm = true;
   e->kind = 0;
   e->n_out = M;
-  // default system: OSI (UBM first) without z-norm
-  e->h_zmean.assign(M, 0.0);
-  e->h_zstd.assign(M, 1.0);
-  FBCHK(e->zmean.ensure(sizeof(double) * M));
-  FBCHK(e->zstd.ensure(sizeof(double) * M));
-  HIPCHK(hipMemcpy(e->zmean.p, e->h_zmean.data(), sizeof(double) * M, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(e->zstd.p, e->h_zstd.data(), sizeof(double) * M, hipMemcpyHostToDevice));
   return FB_OK;
+}
+
+static void note_too_many_for_wide(int M) {
+  static bool warned = false;
+  if (warned) return;
+  warned = true;
+  fprintf(stderr, "[fakebob_hip] note: %d models in one variance group: k_gmm_fx2w takes at most %d (in %d passes), this "
+                  "system is scored by the general kernel k_gmm_fx2 (about twice the time per model)\n", M,
+          fb_gmm_max_wide_models(), FB_FXW_MAX_PASS);
+}
+
+extern "C" int fb_load_gmm(fb_engine *e, int M, int C, int D, const float *gconsts, const float *miv,
+                           const float *iv) {
+  if (!e) return fb_fail(FB_E_ARG, "null argument");
+  FbGmmPrepared p;
+  FBCHK(prepare_gmm(e, M, C, D, gconsts, miv, iv, &p));  // a refused call leaves the engine and the device as they were
+  if (p.too_many_for_wide) note_too_many_for_wide(M);
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  return commit_gmm(e, p, gconsts, miv, iv);
 }
 
 extern "C" int fb_set_system(fb_engine *e, int task, const double *z_mean, const double *z_std) {
@@ -1867,277 +1303,90 @@ extern "C" int fb_system_scores(fb_engine *e, const double *raw, int B, double *
 
 
 // ----------------------------------------------------------------- i-vector
-// in-place Cholesky of a dense SPD matrix (lower), returns false when not PD
-static bool host_chol(std::vector<double> &A, int n) {
-  for (int j = 0; j < n; ++j) {
-    double d = A[(size_t)j * n + j];
-    for (int k = 0; k < j; ++k) d -= A[(size_t)j * n + k] * A[(size_t)j * n + k];
-    if (!(d > 0.0)) return false;
-    d = sqrt(d);
-    A[(size_t)j * n + j] = d;
-    for (int i = j + 1; i < n; ++i) {
-      double v = A[(size_t)i * n + j];
-      for (int k = 0; k < j; ++k) v -= A[(size_t)i * n + k] * A[(size_t)j * n + k];
-      A[(size_t)i * n + j] = v / d;
-    }
-  }
-  return true;
-}
-static void host_chol_solve(const std::vector<double> &Lm, int n, double *b) {
-  for (int i = 0; i < n; ++i) {
-    double v = b[i];
-    for (int k = 0; k < i; ++k) v -= Lm[(size_t)i * n + k] * b[k];
-    b[i] = v / Lm[(size_t)i * n + i];
-  }
-  for (int i = n - 1; i >= 0; --i) {
-    double v = b[i];
-    for (int k = i + 1; k < n; ++k) v -= Lm[(size_t)k * n + i] * b[k];
-    b[i] = v / Lm[(size_t)i * n + i];
-  }
-}
-
-// raw i-vector -> PLDA space, host float64 (same math as k_iv_backend; used once per enrolled
-// speaker at load time): ivector-subtract-global-mean | transform-vec | ivector-normalize-length,
-// then Plda::TransformIvector (normalize_length, n = 1)  ([EXT] SURVEY.md A.10)
-static void host_backend(const fb_ivector_system *sy, const float *ivec, double *y) {
-  const int R = sy->R, L = sy->L;
-  std::vector<double> x(R), z(L);
-  for (int r = 0; r < R; ++r) x[r] = (double)ivec[r] - (double)sy->mean_vec[r];
-  double nrm = 0.0;
-  for (int l = 0; l < L; ++l) {
-    const float *row = sy->lda + (size_t)l * sy->lda_cols;
-    double acc = sy->lda_cols == R + 1 ? (double)row[R] : 0.0;
-    for (int r = 0; r < R; ++r) acc += (double)row[r] * x[r];
-    z[l] = acc;
-    nrm += acc * acc;
-  }
-  const double ratio = sqrt(nrm) / sqrt((double)L);
-  if (ratio != 0.0) for (int l = 0; l < L; ++l) z[l] /= ratio;
-  double dot = 0.0;
-  for (int l = 0; l < L; ++l) {
-    const double *row = sy->plda_transform + (size_t)l * L;
-    double acc = 0.0;
-    for (int m = 0; m < L; ++m) acc += row[m] * (z[m] - sy->plda_mean[m]);
-    y[l] = acc;
-    dot += acc * acc / (sy->plda_psi[l] + 1.0);
-  }
-  const double nf = sqrt((double)L / dot);
-  for (int l = 0; l < L; ++l) y[l] *= nf;
-}
-
-extern "C" int fb_load_ivector(fb_engine *e, const fb_ivector_system *sy, int task) {
-  if (!e || !sy) return fb_fail(FB_E_ARG, "null argument");
-  if (task != FB_TASK_OSI && task != FB_TASK_CSI && task != FB_TASK_SV) return fb_fail(FB_E_ARG, "bad task");
+// fb_load_ivector's argument checks.  e == nullptr (fb_debug_prepare_ivector): no front end to agree with, no task
+static int check_ivector_args(const fb_engine *e, const fb_ivector_system *sy, int task) {
+  if (!sy) return fb_fail(FB_E_ARG, "null argument");
+  if (e && task != FB_TASK_OSI && task != FB_TASK_CSI && task != FB_TASK_SV) return fb_fail(FB_E_ARG, "bad task");
   const int C = sy->C, D = sy->D, R = sy->R, L = sy->L, S = sy->S;
   if (C <= 0 || D <= 0 || R <= 0 || L <= 0 || S <= 0) return fb_fail(FB_E_ARG, "bad i-vector system shape");
-  if (!e->have_fe || e->fe.dim != D) return fb_fail(FB_E_ARG, "UBM dim %d != front-end feature dim %d", D, e->have_fe ? e->fe.dim : -1);
+  if (e && (!e->have_fe || e->fe.dim != D)) return fb_fail(FB_E_ARG, "UBM dim %d != front-end feature dim %d", D, e->have_fe ? e->fe.dim : -1);
   if (R > 512 || L > 512 || D > 80 || D > 255) return fb_fail(FB_E_ARG, "unsupported sizes R=%d L=%d D=%d (R,L <= 512, D <= 80)", R, L, D);
   if (C > 4096) return fb_fail(FB_E_LIMIT, "at most 4096 Gaussians in the i-vector UBM (got %d)", C);
   if (S > 60) return fb_fail(FB_E_ARG, "at most 60 enrolled speakers per engine");
-  if (task == FB_TASK_SV && S != 1) return fb_fail(FB_E_ARG, "SV takes exactly one enrolled speaker");
+  if (e && task == FB_TASK_SV && S != 1) return fb_fail(FB_E_ARG, "SV takes exactly one enrolled speaker");
   if (sy->num_gselect <= 0 || sy->num_gselect > 64 || sy->num_gselect > C) return fb_fail(FB_E_ARG, "num_gselect must be in [1, min(64, C)]");
   if (sy->lda_cols != R && sy->lda_cols != R + 1) return fb_fail(FB_E_ARG, "transform.mat must have R or R+1 columns");
   if (!sy->fg_weights || !sy->fg_means_invcovars || !sy->fg_inv_covars || !sy->ie_M || !sy->ie_sigma_inv ||
       !sy->mean_vec || !sy->lda || !sy->plda_mean || !sy->plda_transform || !sy->plda_psi || !sy->enrolled ||
       !sy->z_mean || !sy->z_std)
     return fb_fail(FB_E_ARG, "null array in fb_ivector_system");
+  return FB_OK;
+}
+static int prepare_ivector(const fb_ivector_system *sy, FbIvPrepared *out) {
+  std::string err;
+  const int rc = fb_prepare_ivector(sy, out, &err);
+  return rc == FB_OK ? FB_OK : fb_fail(rc, "%s", err.c_str());
+}
+
+extern "C" int fb_load_ivector(fb_engine *e, const fb_ivector_system *sy, int task) {
+  if (!e) return fb_fail(FB_E_ARG, "null argument");
+  FBCHK(check_ivector_args(e, sy, task));
+  const int C = sy->C, D = sy->D, R = sy->R, L = sy->L, S = sy->S;
+  // the system's own tables and the images of its diagonalised UBM (the GMM path, M = 1), all on the host: a refused
+  // call leaves the engine and the device as they were
+  FbIvPrepared p;
+  FbGmmPrepared pg;
+  FBCHK(prepare_ivector(sy, &p));
+  FBCHK(prepare_gmm(e, 1, C, D, p.dg_gc.data(), p.dg_miv.data(), p.dg_iv.data(), &pg));
+  const int triD = p.triD, triR = p.triR;
   HIPCHK(hipSetDevice(e->device));
   FBCHK(sync_stream(e));
-  const int triD = D * (D + 1) / 2, triR = R * (R + 1) / 2;
-  // ---- fgmm-global-to-gmm (DiagGmm::CopyFromFullGmm) + FullGmm::ComputeGconsts, float64 on host
-  std::vector<float> dg_gc(C), dg_miv((size_t)C * D), dg_iv((size_t)C * D), fg_gc(C);
-  {
-    std::vector<double> P((size_t)D * D), col(D), mean(D);
-    const double LOG2PI = 1.8378770664093454835606594728112;
-    for (int k = 0; k < C; ++k) {
-      const float *pk = sy->fg_inv_covars + (size_t)k * triD;
-      for (int r = 0; r < D; ++r)
-        for (int c = 0; c <= r; ++c) { P[(size_t)r * D + c] = (double)pk[(size_t)r * (r + 1) / 2 + c]; P[(size_t)c * D + r] = P[(size_t)r * D + c]; }
-      std::vector<double> Lc(P);
-      if (!host_chol(Lc, D)) return fb_fail(FB_E_ARG, "full-covariance Gaussian %d is not positive definite", k);
-      double logdet_inv = 0.0;
-      for (int d = 0; d < D; ++d) logdet_inv += 2.0 * log(Lc[(size_t)d * D + d]);
-      // mean = covar * means_invcovars ; covar diag via solves with unit vectors
-      for (int d = 0; d < D; ++d) mean[d] = (double)sy->fg_means_invcovars[(size_t)k * D + d];
-      double quad = 0.0;
-      {
-        std::vector<double> t(mean);
-        host_chol_solve(Lc, D, t.data());
-        for (int d = 0; d < D; ++d) quad += (double)sy->fg_means_invcovars[(size_t)k * D + d] * t[d];
-        mean = t;
-      }
-      const double w = (double)sy->fg_weights[k];
-      fg_gc[k] = (float)(log(w) - 0.5 * (D * LOG2PI - logdet_inv + quad));
-      double gc = log(w) - 0.5 * D * LOG2PI;
-      for (int d = 0; d < D; ++d) {
-        for (int q = 0; q < D; ++q) col[q] = q == d ? 1.0 : 0.0;
-        host_chol_solve(Lc, D, col.data());
-        const float ivf = (float)(1.0 / col[d]);
-        const float mivf = (float)(mean[d] * (1.0 / col[d]));
-        dg_iv[(size_t)k * D + d] = ivf;
-        dg_miv[(size_t)k * D + d] = mivf;
-        gc += 0.5 * log((double)ivf) - 0.5 * (double)mivf * (double)mivf / (double)ivf;
-      }
-      dg_gc[k] = (float)gc;
-    }
-  }
-  FBCHK(fb_load_gmm(e, 1, C, D, dg_gc.data(), dg_miv.data(), dg_iv.data()));
-  // ---- full UBM + packed-index tables
-  {
-    const size_t n_gc = C, n_mic = (size_t)C * D, n_P = (size_t)C * triD;
-    FBCHK(e->iv_fg.ensure(sizeof(float) * (n_gc + n_mic + n_P)));
-    float *base = e->iv_fg.as<float>();
-    HIPCHK(hipMemcpy(base, fg_gc.data(), sizeof(float) * n_gc, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(base + n_gc, sy->fg_means_invcovars, sizeof(float) * n_mic, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(base + n_gc + n_mic, sy->fg_inv_covars, sizeof(float) * n_P, hipMemcpyHostToDevice));
-    std::vector<unsigned char> tr(2 * (size_t)triD);
-    for (int r = 0, idx = 0; r < D; ++r)
-      for (int c = 0; c <= r; ++c, ++idx) { tr[idx] = (unsigned char)r; tr[triD + idx] = (unsigned char)c; }
-    FBCHK(e->iv_tri.ensure(tr.size()));
-    HIPCHK(hipMemcpy(e->iv_tri.p, tr.data(), tr.size(), hipMemcpyHostToDevice));
-    e->iv.fg_gconsts = base; e->iv.fg_mic = base + n_gc; e->iv.fg_P = base + n_gc + n_mic;
-    {  // float64 image of the same numbers for the register-blocked full-covariance kernel
-      const size_t stride = (size_t)triD + D + 1;
-      std::vector<double> f64((size_t)C * stride);
-      for (int c = 0; c < C; ++c) {
-        double *o = &f64[(size_t)c * stride];
-        const float *P = sy->fg_inv_covars + (size_t)c * triD;
-        for (int r = 0, idx = 0; r < D; ++r)
-          for (int cc = 0; cc <= r; ++cc, ++idx) o[idx] = (cc == r) ? 0.5 * (double)P[idx] : (double)P[idx];
-        for (int d = 0; d < D; ++d) o[triD + d] = (double)sy->fg_means_invcovars[(size_t)c * D + d];
-        o[triD + D] = (double)fg_gc[c];
-      }
-      FBCHK(e->iv_fg64.ensure(sizeof(double) * f64.size()));
-      HIPCHK(hipMemcpy(e->iv_fg64.p, f64.data(), sizeof(double) * f64.size(), hipMemcpyHostToDevice));
-      e->iv.fg64 = e->iv_fg64.as<double>();
-    }
-    e->iv.fgL = nullptr;
-    if (D == 72) {
-      // Cholesky image of the same function for k_iv_fullcov_mfma (ivector_kernels.hip): with P = L L' and any mu,
-      //   gconst + mic . x - 1/2 x'Px = [gconst + 1/2 mu'P mu] + (mic - P mu) . x - 1/2 |L'(x - mu)|^2;
-      // mu = P^-1 mic refined in long double until the residual's term is far below the float64 rounding of the
-      // rest (it is then dropped); L from a long double factorisation of the float32 parameters as they are, rounded
-      // once.  A component whose residual cannot be brought down keeps the whole batch on the triangle-form kernel.
-      const int NFR = 50, REC = NFR * 64 + 72 + 2;
-      std::vector<double> rec((size_t)C * REC, 0.0);
-      std::vector<long double> Pm((size_t)D * D), Lm((size_t)D * D), mu(D), rs(D), dx(D);
-      bool ok = true;
-      for (int c = 0; c < C && ok; ++c) {
-        const float *P = sy->fg_inv_covars + (size_t)c * triD;
-        const float *mic = sy->fg_means_invcovars + (size_t)c * D;
-        for (int r = 0, idx = 0; r < D; ++r)
-          for (int cc = 0; cc <= r; ++cc, ++idx) Pm[(size_t)r * D + cc] = Pm[(size_t)cc * D + r] = (long double)P[idx];
-        std::fill(Lm.begin(), Lm.end(), 0.0L);
-        for (int j = 0; j < D && ok; ++j) {
-          long double d = Pm[(size_t)j * D + j];
-          for (int q = 0; q < j; ++q) d -= Lm[(size_t)j * D + q] * Lm[(size_t)j * D + q];
-          if (!(d > 0.0L)) { ok = false; break; }
-          const long double lj = sqrtl(d);
-          Lm[(size_t)j * D + j] = lj;
-          for (int i = j + 1; i < D; ++i) {
-            long double v = Pm[(size_t)i * D + j];
-            for (int q = 0; q < j; ++q) v -= Lm[(size_t)i * D + q] * Lm[(size_t)j * D + q];
-            Lm[(size_t)i * D + j] = v / lj;
-          }
-        }
-        if (!ok) break;
-        auto solve = [&](std::vector<long double> &b) {  // b <- P^-1 b through L
-          for (int i = 0; i < D; ++i) {
-            long double v = b[i];
-            for (int q = 0; q < i; ++q) v -= Lm[(size_t)i * D + q] * b[q];
-            b[i] = v / Lm[(size_t)i * D + i];
-          }
-          for (int i = D - 1; i >= 0; --i) {
-            long double v = b[i];
-            for (int q = i + 1; q < D; ++q) v -= Lm[(size_t)q * D + i] * b[q];
-            b[i] = v / Lm[(size_t)i * D + i];
-          }
-        };
-        for (int d = 0; d < D; ++d) mu[d] = (long double)mic[d];
-        solve(mu);
-        double *o = &rec[(size_t)c * REC];
-        long double res_term = 0.0L;
-        for (int it = 0; it < 4; ++it) {
-          // the kernel uses mu rounded to float64: refine THAT vector's residual
-          long double mx = 0.0L, sc = 0.0L;
-          for (int i = 0; i < D; ++i) {
-            long double v = (long double)mic[i];
-            for (int q = 0; q < D; ++q) v -= Pm[(size_t)i * D + q] * (long double)(double)mu[q];
-            rs[i] = v;
-            mx = std::max(mx, fabsl(v));
-            sc = std::max(sc, fabsl((long double)mic[i]));
-          }
-          res_term = mx / (sc > 0.0L ? sc : 1.0L);
-          if (it == 3) break;
-          dx = rs;
-          solve(dx);
-          for (int i = 0; i < D; ++i) mu[i] = (long double)(double)mu[i] + dx[i];
-        }
-        // (mic - P mu) . x relative to mic . x: float64 rounding of mu leaves ~1e-16 kappa; the term is dropped, so it has
-        // to be invisible next to the 1e-13 the float64 sums themselves carry
-        if (!(res_term < 1.0e-11L)) { ok = false; break; }
-        long double q2 = 0.0L;
-        for (int i = 0; i < D; ++i)
-          for (int q = 0; q < D; ++q) q2 += (long double)(double)mu[i] * Pm[(size_t)i * D + q] * (long double)(double)mu[q];
-        int f = 0;
-        for (int jt = 0; jt < 5; ++jt)
-          for (int s2 = 4 * jt; s2 < D / 4; ++s2, ++f)
-            for (int l = 0; l < 64; ++l) {
-              const int q = l >> 4;  // the kernel's K order: a lane's four places of a 16-row block are consecutive rows
-              const int row = s2 < 16 ? 16 * (s2 / 4) + 4 * q + (s2 % 4) : 64 + 2 * q + (s2 - 16), col = 16 * jt + (l & 15);
-              o[(size_t)f * 64 + l] = (col <= row && col < D) ? (double)Lm[(size_t)row * D + col] : 0.0;
-            }
-        for (int d = 0; d < D; ++d) o[(size_t)NFR * 64 + d] = (double)mu[d];
-        o[(size_t)NFR * 64 + D] = (double)((long double)fg_gc[c] + 0.5L * q2);
-      }
-      if (ok) {
-        FBCHK(e->iv_fgL.ensure(sizeof(double) * rec.size()));
-        HIPCHK(hipMemcpy(e->iv_fgL.p, rec.data(), sizeof(double) * rec.size(), hipMemcpyHostToDevice));
-        e->iv.fgL = e->iv_fgL.as<double>();
-      }
-    }
-    e->iv.tri_r = e->iv_tri.as<unsigned char>(); e->iv.tri_c = e->iv.tri_r + triD;
-  }
-  // ---- extractor: Sigma^-1 M and U derived on the device (IvectorExtractor::ComputeDerivedVars)
-  {
-    DevBuf dM, dS;
-    const size_t nM = (size_t)C * D * R;
-    FBCHK(dM.ensure(sizeof(double) * nM));
-    FBCHK(dS.ensure(sizeof(double) * (size_t)C * triD));
-    FBCHK(e->iv_sim.ensure(sizeof(double) * nM));
-    FBCHK(e->iv_u.ensure(sizeof(double) * (size_t)C * triR));
-    HIPCHK(hipMemcpy(dM.p, sy->ie_M, sizeof(double) * nM, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dS.p, sy->ie_sigma_inv, sizeof(double) * (size_t)C * triD, hipMemcpyHostToDevice));
-    fb_launch_iv_derive(e->stream, C, D, R, dM.as<double>(), dS.as<double>(), e->iv_sim.as<double>(), e->iv_u.as<double>());
-    FBCHK(sync_stream(e));
-    e->iv.sim = e->iv_sim.as<double>();
-    e->iv.u = e->iv_u.as<double>();
-  }
-  // ---- back-end tables
-  {
-    const int lc = sy->lda_cols;
-    std::vector<double> host;
-    const size_t o_mean = 0; host.resize(R);
-    for (int r = 0; r < R; ++r) host[o_mean + r] = (double)sy->mean_vec[r];
-    const size_t o_lda = host.size(); host.resize(o_lda + (size_t)lc * L);
-    for (int l = 0; l < L; ++l) for (int c = 0; c < lc; ++c) host[o_lda + (size_t)c * L + l] = (double)sy->lda[(size_t)l * lc + c];
-    const size_t o_pm = host.size(); host.resize(o_pm + L);
-    for (int l = 0; l < L; ++l) host[o_pm + l] = sy->plda_mean[l];
-    const size_t o_pt = host.size(); host.resize(o_pt + (size_t)L * L);
-    for (int l = 0; l < L; ++l) for (int m = 0; m < L; ++m) host[o_pt + (size_t)m * L + l] = sy->plda_transform[(size_t)l * L + m];
-    const size_t o_psi = host.size(); host.resize(o_psi + L);
-    for (int l = 0; l < L; ++l) host[o_psi + l] = sy->plda_psi[l];
-    const size_t o_tr = host.size(); host.resize(o_tr + (size_t)S * L);
-    for (int sp = 0; sp < S; ++sp) host_backend(sy, sy->enrolled + (size_t)sp * R, &host[o_tr + (size_t)sp * L]);
-    FBCHK(e->iv_backend.ensure(sizeof(double) * host.size()));
-    HIPCHK(hipMemcpy(e->iv_backend.p, host.data(), sizeof(double) * host.size(), hipMemcpyHostToDevice));
-    const double *b = e->iv_backend.as<double>();
-    e->iv.mean_vec = b + o_mean; e->iv.ldaT = b + o_lda; e->iv.plda_mean = b + o_pm; e->iv.pldaT = b + o_pt;
-    e->iv.plda_psi = b + o_psi; e->iv.train = b + o_tr;
-  }
+  FBCHK(commit_gmm(e, pg, p.dg_gc.data(), p.dg_miv.data(), p.dg_iv.data()));
+  // ---- ensure: the full UBM {gconsts, means_invcovars, inv_covars}, its images, the extractor, the back end
+  const size_t n_gc = C, n_mic = (size_t)C * D, n_P = (size_t)C * triD, nM = (size_t)C * D * R;
+  DevBuf dM, dS;  // the extractor's M and Sigma^-1 as they come: inputs of the derive launch, freed on return
+  FBCHK(e->iv_fg.ensure(sizeof(float) * (n_gc + n_mic + n_P)));
+  FBCHK(e->iv_tri.ensure(p.tri.size()));
+  FBCHK(e->iv_fg64.ensure(sizeof(double) * p.fg64.size()));
+  if (!p.fgL.empty()) FBCHK(e->iv_fgL.ensure(sizeof(double) * p.fgL.size()));
+  FBCHK(dM.ensure(sizeof(double) * nM));
+  FBCHK(dS.ensure(sizeof(double) * (size_t)C * triD));
+  FBCHK(e->iv_sim.ensure(sizeof(double) * nM));
+  FBCHK(e->iv_u.ensure(sizeof(double) * (size_t)C * triR));
+  FBCHK(e->iv_backend.ensure(sizeof(double) * p.backend.size()));
+  FBCHK(e->zmean.ensure(sizeof(double) * S));
+  FBCHK(e->zstd.ensure(sizeof(double) * S));
+  // ---- upload
+  float *base = e->iv_fg.as<float>();
+  HIPCHK(hipMemcpy(base, p.fg_gc.data(), sizeof(float) * n_gc, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(base + n_gc, sy->fg_means_invcovars, sizeof(float) * n_mic, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(base + n_gc + n_mic, sy->fg_inv_covars, sizeof(float) * n_P, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(e->iv_tri.p, p.tri.data(), p.tri.size(), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(e->iv_fg64.p, p.fg64.data(), sizeof(double) * p.fg64.size(), hipMemcpyHostToDevice));
+  if (!p.fgL.empty()) HIPCHK(hipMemcpy(e->iv_fgL.p, p.fgL.data(), sizeof(double) * p.fgL.size(), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(e->iv_backend.p, p.backend.data(), sizeof(double) * p.backend.size(), hipMemcpyHostToDevice));
+  e->h_zmean.assign(sy->z_mean, sy->z_mean + S);
+  e->h_zstd.assign(sy->z_std, sy->z_std + S);
+  HIPCHK(hipMemcpy(e->zmean.p, e->h_zmean.data(), sizeof(double) * S, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(e->zstd.p, e->h_zstd.data(), sizeof(double) * S, hipMemcpyHostToDevice));
+  // the extractor: Sigma^-1 M and U derived on the device (IvectorExtractor::ComputeDerivedVars)
+  HIPCHK(hipMemcpy(dM.p, sy->ie_M, sizeof(double) * nM, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dS.p, sy->ie_sigma_inv, sizeof(double) * (size_t)C * triD, hipMemcpyHostToDevice));
+  fb_launch_iv_derive(e->stream, C, D, R, dM.as<double>(), dS.as<double>(), e->iv_sim.as<double>(), e->iv_u.as<double>());
+  FBCHK(sync_stream(e));
   // the bucket workspace is laid out by C: a different system must not inherit stale `flags`
   if (e->iv_bws.p) HIPCHK(hipMemset(e->iv_bws.p, 0, e->iv_bws.cap));
+  // ---- assign
   FbIvDev &iv = e->iv;
+  iv.fg_gconsts = base; iv.fg_mic = base + n_gc; iv.fg_P = base + n_gc + n_mic;
+  iv.fg64 = e->iv_fg64.as<double>();
+  iv.fgL = p.fgL.empty() ? nullptr : e->iv_fgL.as<double>();
+  iv.tri_r = e->iv_tri.as<unsigned char>(); iv.tri_c = iv.tri_r + triD;
+  iv.sim = e->iv_sim.as<double>();
+  iv.u = e->iv_u.as<double>();
+  const double *b = e->iv_backend.as<double>();
+  iv.mean_vec = b + p.o_mean; iv.ldaT = b + p.o_lda; iv.plda_mean = b + p.o_pm; iv.pldaT = b + p.o_pt;
+  iv.plda_psi = b + p.o_psi; iv.train = b + p.o_tr;
   iv.text_scores = e->cfg.text_scores;
   iv.C = C; iv.Cpad = e->gmm.n_tiles * 32; iv.D = D; iv.R = R; iv.L = L; iv.S = S; iv.lda_cols = sy->lda_cols;
   iv.nsel = sy->num_gselect; iv.triD = triD; iv.triR = triR; iv.min_post = (float)sy->min_post;
@@ -2145,17 +1394,79 @@ extern "C" int fb_load_ivector(fb_engine *e, const fb_ivector_system *sy, int ta
   e->kind = 1;
   e->n_out = S;
   e->task = task;
-  e->h_zmean.assign(sy->z_mean, sy->z_mean + S);
-  e->h_zstd.assign(sy->z_std, sy->z_std + S);
-  FBCHK(e->zmean.ensure(sizeof(double) * S));
-  FBCHK(e->zstd.ensure(sizeof(double) * S));
-  HIPCHK(hipMemcpy(e->zmean.p, e->h_zmean.data(), sizeof(double) * S, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(e->zstd.p, e->h_zstd.data(), sizeof(double) * S, hipMemcpyHostToDevice));
-  // split of the (C*D)-long contraction: enough workgroups to stream Sigma^-1 M at HBM rate
-  const int64_t Q = (int64_t)C * D;
-  (void)Q;
   e->iv_kchunks = C / 8 > 128 ? 128 : (C / 8 < 1 ? 1 : C / 8);  // chunks of the active-component list
   return FB_OK;
+}
+
+// ------------------------------------------------- the loaders' host preparation without an engine (fakebob_hip_test.h)
+// size-then-fill: *size = the named buffer's bytes; with out != NULL it is copied there (cap bytes must hold it)
+static int give_bytes(const char *name, const void *src, size_t n, void *out, int64_t cap, int64_t *size) {
+  if (size) *size = (int64_t)n;
+  if (!out) return FB_OK;
+  if (cap < (int64_t)n) return fb_fail(FB_E_ARG, "out holds %lld bytes, buffer '%s' needs %lld", (long long)cap, name, (long long)n);
+  if (n) memcpy(out, src, n);
+  return FB_OK;
+}
+template <typename T> static int give_vector(const char *name, const std::vector<T> &v, void *out, int64_t cap, int64_t *size) {
+  return give_bytes(name, v.data(), sizeof(T) * v.size(), out, cap, size);
+}
+
+extern "C" int fb_debug_prepare_gmm(int M, int C, int D, const float *gconsts, const float *means_invvars, const float *inv_vars,
+                                    fb_gmm_plan *plan, int *perm, const char *buffer, int pass, void *out, int64_t cap,
+                                    int64_t *size) {
+  FbGmmPrepared p;
+  FBCHK(prepare_gmm(nullptr, M, C, D, gconsts, means_invvars, inv_vars, &p));
+  if (plan) {
+    *plan = fb_gmm_plan{p.mode, p.NK, p.NKF, p.kx, p.kx2, p.kacc, p.n_tiles, p.n_items, p.n_groups, p.delta_p, p.delta_t3,
+                        p.delta_t6, p.delta_t2, p.n_pass, {p.pass_lo[0], p.pass_lo[1], p.pass_lo[2], p.pass_lo[3]}, p.delta_rms};
+  }
+  if (perm)
+    for (int c = 0; c < C; ++c) perm[c] = p.delta_p ? p.perm[c] : c;
+  if (!buffer) return FB_OK;
+  if (strcmp(buffer, "fx") == 0) return give_vector(buffer, p.fx, out, cap, size);
+  if (strcmp(buffer, "bx") == 0) return give_vector(buffer, p.bx, out, cap, size);
+  if (strcmp(buffer, "anchor") == 0) return give_vector(buffer, p.anchor, out, cap, size);
+  if (strcmp(buffer, "item_model") == 0) return give_vector(buffer, p.item_model, out, cap, size);
+  if (strcmp(buffer, "fd") == 0) {
+    if (pass < 0 || pass >= FB_FXW_MAX_PASS) return fb_fail(FB_E_ARG, "pass %d out of range (0 .. %d)", pass, FB_FXW_MAX_PASS - 1);
+    return give_vector(buffer, p.fd[pass], out, cap, size);
+  }
+  return fb_fail(FB_E_ARG, "no GMM buffer '%s' (fx, bx, fd, anchor, item_model)", buffer);
+}
+
+extern "C" int fb_debug_prepare_ivector(const fb_ivector_system *sy, const char *buffer, void *out, int64_t cap, int64_t *size) {
+  FBCHK(check_ivector_args(nullptr, sy, 0));
+  if (!buffer) return fb_fail(FB_E_ARG, "null argument");
+  FbIvPrepared p;
+  FBCHK(prepare_ivector(sy, &p));
+  if (strcmp(buffer, "dg_gc") == 0) return give_vector(buffer, p.dg_gc, out, cap, size);
+  if (strcmp(buffer, "dg_miv") == 0) return give_vector(buffer, p.dg_miv, out, cap, size);
+  if (strcmp(buffer, "dg_iv") == 0) return give_vector(buffer, p.dg_iv, out, cap, size);
+  if (strcmp(buffer, "fg_gc") == 0) return give_vector(buffer, p.fg_gc, out, cap, size);
+  if (strcmp(buffer, "tri") == 0) return give_vector(buffer, p.tri, out, cap, size);
+  if (strcmp(buffer, "fg64") == 0) return give_vector(buffer, p.fg64, out, cap, size);
+  if (strcmp(buffer, "fgL") == 0) return give_vector(buffer, p.fgL, out, cap, size);
+  if (strcmp(buffer, "backend") == 0) return give_vector(buffer, p.backend, out, cap, size);
+  if (strcmp(buffer, "backend_offsets") == 0) {
+    const std::vector<int64_t> o = {(int64_t)p.o_mean, (int64_t)p.o_lda, (int64_t)p.o_pm, (int64_t)p.o_pt, (int64_t)p.o_psi, (int64_t)p.o_tr};
+    return give_vector(buffer, o, out, cap, size);
+  }
+  return fb_fail(FB_E_ARG, "no i-vector buffer '%s' (dg_gc, dg_miv, dg_iv, fg_gc, tri, fg64, fgL, backend, backend_offsets)", buffer);
+}
+
+extern "C" int fb_debug_prepare_frontend(const fb_frontend_cfg *c, const char *buffer, void *out, int64_t cap, int64_t *size) {
+  if (!c || !buffer) return fb_fail(FB_E_ARG, "null argument");
+  FrontendPrepared p;
+  FBCHK(prepare_frontend(c, &p));
+  const FbFrontendBlob &b = p.blob;
+  if (strcmp(buffer, "blob") == 0) return give_vector(buffer, b.bytes, out, cap, size);
+  if (strcmp(buffer, "f32") == 0) return give_vector(buffer, p.t32, out, cap, size);
+  if (strcmp(buffer, "offsets") == 0) {
+    const std::vector<int64_t> o = {(int64_t)b.o_window, (int64_t)b.o_twh, (int64_t)b.o_twf, (int64_t)b.o_mf, (int64_t)b.o_ml,
+                                    (int64_t)b.o_mo, (int64_t)b.o_mw, (int64_t)b.o_dct, (int64_t)b.o_lift, (int64_t)b.o_ds};
+    return give_vector(buffer, o, out, cap, size);
+  }
+  return fb_fail(FB_E_ARG, "no front-end buffer '%s' (blob, f32, offsets)", buffer);
 }
 
 extern "C" int fb_debug_iv_active(fb_engine *e, int *n_active) {

@@ -5,6 +5,7 @@
 
 #include "../../include/fakebob_hip.h"
 #include "../../include/fakebob_hip_test.h"
+#include "fb_gmm_limits.h"  // FB_FXW_MAX_PASS, FB_FXW_MAX_M, FB_FXW_ANCHORS, FB_GMM_MODE_*: shared with fb_prepare.h
 
 // ---- device-resident front-end tables (built on the host at fb_set_frontend)
 struct FbFrontendDev {
@@ -400,17 +401,17 @@ struct FbGmmDev {
   // chunk a delta item needs fall from tile to tile: tiles [0, delta_t3) are evaluated with 3, [delta_t6, delta_t2)
   // with 2, the rest with 1.  delta_p = the class most tiles use (1 .. 3, 6 = F6; 0: no delta images); anchor = the frames'
   // balancing factors and the components whose log2-likelihoods start the kernel's per-frame reference (layout:
-  // fb_load_gmm)
+  // fb_gmm_anchor_table; every image of this struct is packed by fb_prepare_gmm.cpp)
   const unsigned int __attribute__((ext_vector_type(4))) * images_fd;
   int delta_p, delta_t3, delta_t2;
-  int delta_t6;  // tiles [delta_t3, delta_t6): the F6 class (delta_t3 <= delta_t6 <= delta_t2; fb_load_gmm, gmm_wide_kernel.hip)
+  int delta_t6;  // tiles [delta_t3, delta_t6): the F6 class (delta_t3 <= delta_t6 <= delta_t2; fb_gmm_delta_plan, gmm_wide_kernel.hip)
   // passes of k_gmm_fx2w (more than FB_FXW_MAX_M models): pass p scores the base model and the models pass_lo[p] ..
   // pass_lo[p + 1] - 1 from its own image buffer {Q, base, its deltas}; the launcher hands the kernel a copy of this
   // struct with images_fd = pass_images[p] and pass_first = pass_lo[p] (local model m >= 1 is model pass_first + m - 1 of
   // the M the partial sums are laid out for)
   int n_pass, pass_first;
-  const unsigned int __attribute__((ext_vector_type(4))) * pass_images[3];
-  int pass_lo[4];
+  const unsigned int __attribute__((ext_vector_type(4))) * pass_images[FB_FXW_MAX_PASS];
+  int pass_lo[FB_FXW_MAX_PASS + 1];
   const float *anchor;
   const int *stop;  // nullable device flag: != 0 -> the launch does nothing (attack already stopped)
   const int *only_if;  // nullable device flag: == 0 -> the DUMP launch does nothing (the gselect rescue: fb_launch_gsel)
@@ -418,11 +419,6 @@ struct FbGmmDev {
   int fxw_sub;      // k_gmm_fx2w: component chunks ONE workgroup scores one after the other (0 / 1: one; 2: the launch of a GPU shared
                     // by three or more attacks -- half as many workgroups as compute units, the same partial sums bit for bit)
 };
-#define FB_FXW_MAX_PASS 3 // launches of k_gmm_fx2w per batch: 1 + 9 x 3 = 28 models (fb_load_gmm)
-#define FB_FXW_MAX_M 10   // models ONE launch of k_gmm_fx2w takes: (1 + M) 10 KB items + the state of 2 M x 256 frames = 156 KB of LDS at M = 10
-#define FB_FXW_ANCHORS 2  // anchor components of k_gmm_fx2w's per-frame reference (FbGmmDev::anchor)
-#define FB_GMM_MODE_BX3 1
-#define FB_GMM_MODE_FX2 2
 #ifndef FB_FX_OCC
 #define FB_FX_OCC 2  // k_gmm_fx2 workgroups per CU (launch bound and the launch's target block count)
 

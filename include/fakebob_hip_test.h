@@ -234,6 +234,32 @@ int fb_gmm_delta_tiles(fb_engine *e, int *tiles_p1, int *tiles_p2, int *tiles_p3
  * keeps the rule from choosing it).  tiles_p1 + tiles_p2 + tiles_p3 + this = the model's component tiles. */
 int fb_gmm_delta_tiles_f6(fb_engine *e);
 
+/* The loaders' host preparation, without an engine and without a GPU: what fb_load_gmm, fb_load_ivector and
+ * fb_set_frontend compute on the host before they touch the device (csrc/fb_prepare.h), under the same argument checks
+ * and the same environment variables (FB_GMM_MODE, FB_GMM_DELTA_BUDGET, FB_GMM_DELTA_F6, FB_GMM_DELTA_P), with the
+ * loaders' error codes and texts.  Named buffers come back size-then-fill: *size (nullable) receives the buffer's bytes;
+ * with out != NULL the bytes are copied there, FB_E_ARG when cap is smaller.  A buffer the preparation did not build has
+ * size 0.
+ * fb_debug_prepare_gmm: plan (nullable) as below -- t3 / t6 / t2: tiles [0, t3) run three products, [t3, t6) the F6
+ * class, [t6, t2) two, the rest one; all zero with delta_p = 0, when no delta images are built --; perm[C] (nullable): the
+ * component at each place of the delta images (the identity without them); buffer (nullable): "fx", "bx", "fd" (of
+ * pass `pass`), "anchor", "item_model".
+ * fb_debug_prepare_ivector: "dg_gc", "dg_miv", "dg_iv" (the diagonalised UBM), "fg_gc", "tri", "fg64", "fgL" (the D = 72
+ * Cholesky image; size 0 when not usable), "backend", "backend_offsets" (int64[6], in doubles: mean_vec, ldaT, plda_mean,
+ * pldaT, plda_psi, train).
+ * fb_debug_prepare_frontend: "blob" (the packed tables), "offsets" (int64[10], in bytes: window, tw_half, tw_full,
+ * mel_first, mel_len, mel_off, mel_w, dct, lifter, dscale), "f32" (k_mfcc_f32's table; size 0 when the shape has none). */
+typedef struct {
+  int mode, NK, NKF, kx, kx2, kacc;
+  int n_tiles, n_items, n_groups;
+  int delta_p, t3, t6, t2, n_pass, pass_lo[4];
+  double delta_rms;
+} fb_gmm_plan;
+int fb_debug_prepare_gmm(int M, int C, int D, const float *gconsts, const float *means_invvars, const float *inv_vars,
+                         fb_gmm_plan *plan, int *perm, const char *buffer, int pass, void *out, int64_t cap, int64_t *size);
+int fb_debug_prepare_ivector(const fb_ivector_system *sy, const char *buffer, void *out, int64_t cap, int64_t *size);
+int fb_debug_prepare_frontend(const fb_frontend_cfg *c, const char *buffer, void *out, int64_t cap, int64_t *size);
+
 /* the GMM kernel the engine scores with, on T rows of D features handed in as they are (no front-end): per-frame
  * log-likelihoods out[m * T + t] of every model (gmm-global-get-frame-likes without --average).  Lets the tests reach
  * inputs the front-end never produces: outliers, huge magnitudes, frames far from every component. */
