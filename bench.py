@@ -21,6 +21,12 @@ Multi-GPU: utterances are independent (attackMain.py:324-409), so each rank atta
 utterance ("weak" scaling, no data-path collective); RCCL is used only for the barrier, the
 max-over-ranks time and the final counter reduction.
 
+A plain run does what the headline figure needs and no more: set-up, precondition and warm-up, the timed windows,
+--dump-outputs, the line.  `--full` adds everything else to the same line, unchanged: the dominant kernel with the chip
+to itself (roofline.solo_*, whole_chip_grid), `single_attack`, `secondary` (other configurations, whole attacks with
+the early stop on, the i-vector systems), `cpu_baseline`; --no-single / --no-secondary / --no-cpu-baseline take parts
+of it away again.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -345,9 +351,9 @@ def bench_ivector(args, torch):
     its = total_steps / dt
     single = None
     solve_ms = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # one attack in flight, same step count: the latency view, and the pass that times k_iv_solve_ll
-        # (HIP events around each of its launches on the attack's stream)
+        # (HIP events around each of its launches on the attack's stream); without --full roofline_solve has no time
         eng.set_fused_chain(True if args.chain == "auto" else fused)
         d1s = []
         for _ in range(3):   # (median of three passes)
@@ -385,11 +391,11 @@ def bench_ivector(args, torch):
                                       "utterances per NES batch), N=48000, %d attacks in flight per GPU"
                                       % (task, n_spk, spd, B, K), "attacks_in_flight_per_gpu": K,
                           "voiced_rows_per_iter": rows, "model_load_s": t_load,
-                          "launch_chain": "fused" if fused else "unfused",
+                          "launch_chain": "fused" if fused else "unfused", "full": bool(args.full),
                           **windows_fields(dts),
                           "timing": "median of `repeats` consecutive windows of `steps` steps each"},
                "roofline": dominant, "roofline_contraction": contraction, "roofline_solve": solve}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             from oracle import oracle as O
             import numpy as np
             ctx = O.IvSystemCtx(O.default_cfg(mfcc_f32=int(args.frontend == "f32")), sy, nthreads=1)
@@ -575,10 +581,15 @@ def main():
     ap.add_argument("--streams", type=int, default=3, help="attacks in flight per GPU (one engine/stream each)")
     ap.add_argument("--repeats", type=int, default=9,
                     help="consecutive timed windows of --steps steps each; the line reports their median (config.windows_ms: all)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-single", action="store_true", help="skip the extra one-attack-in-flight measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps (and, for the solo kernel launches, between the precondition and the warm-up) also "
+                         "measure everything the headline figure does not need: the dominant kernel with the chip to itself, one "
+                         "attack in flight, the secondary configurations, whole attacks with the early stop on, the CPU baseline.  "
+                         "Without it the run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-single", action="store_true", help="--full: skip the extra one-attack-in-flight measurement")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary measurements of the default line (forced three products, realistic enrolment, "
+                    help="--full: skip the secondary measurements (forced three products, realistic enrolment, "
                          "reference-pipeline mode, GMM CSI, i-vector SV / OSI)")
     ap.add_argument("--arch", default="gmm", choices=["gmm", "iv"], help="gmm = headline (configs[1]); iv = configs[2]")
     ap.add_argument("--e2e-only", action="store_true",
@@ -677,16 +688,16 @@ def main():
             dist.barrier()
             dist.destroy_process_group()
         return
-    # outside everything: module load, first-touch allocations, the clock ramp of a cold GPU, and the same GMM
+    # outside everything: module load, first-touch allocations, the clock ramp of a cold GPU, and (--full) the same GMM
     # launch with the chip to itself
     aset = AttackSet(engs, prms, auds)
     aset.run(max(2, args.precondition), False)
-    solo_ms, solo_rows = engs[0].bench_gmm_kernel(20)
+    solo_ms, solo_rows = engs[0].bench_gmm_kernel(20) if args.full else (None, None)
     # ... and the same launch as one workgroup per compute unit (what a lone attack runs): with three or more attacks per GPU the
     # engine launches HALF as many workgroups, each scoring two component chunks one after the other -- slower alone, faster for
     # the job (fb_engine.hip, run_scoring)
     full_ms = None
-    if "FB_GMM_SUB" not in os.environ and not fused:
+    if args.full and "FB_GMM_SUB" not in os.environ and not fused:
         os.environ["FB_GMM_SUB"] = "1"
         try:
             full_ms, _ = engs[0].bench_gmm_kernel(20)
@@ -710,7 +721,7 @@ def main():
         assert total_scored == total_steps * (SPD + 1)
     its = total_steps / dt
     single = None
-    if rank == 0 and K > 1 and not args.no_single:
+    if rank == 0 and K > 1 and args.full and not args.no_single:
         # the same K steps with ONE attack in flight (a single launch chain): the latency view of the same path
         engs[0].set_fused_chain(True if args.chain == "auto" else fused)   # what a lone attack runs (auto: fused)
         d1s = []
@@ -746,7 +757,7 @@ def main():
                                    "(1 step = 1 NES iteration of each)%s%s"
                                    % (wl, K, "; reference-pipeline round trips ON (compress_feats, text_scores)" if args.faithful else "",
                                       "; speakers enrolled on 20 000 frames (models.ENROL_REALISTIC)" if args.enrol == "realistic" else ""),
-                       "faithful_pipeline": bool(args.faithful), "enrolment": args.enrol,
+                       "faithful_pipeline": bool(args.faithful), "enrolment": args.enrol, "full": bool(args.full),
                        "frontend_precision": {"f32": "float32 MFCC (Kaldi's BaseFloat; C0 from the exact integer energy), float64 "
                                                      "deltas / CMVN sums", "f64": "float64 between Kaldi's float32 storage points"}[args.frontend],
                        "attacks_in_flight_per_gpu": K, "precondition_steps": max(2, args.precondition),
@@ -768,7 +779,7 @@ def main():
                              note="avg_launch_ms: HIP events around every launch of the timed region on each attack's own "
                                   "stream; with several attacks in flight a launch shares the chip with other attacks' "
                                   "kernels (the rocprofv3 average of the same command agrees: profiles/); solo_*: the same "
-                                  "launch with the chip to itself, measured before the warm-up"),
+                                  "launch with the chip to itself, measured before the warm-up (--full only)"),
         }
         if full_ms:
             fl_solo = n_models * C_GAUSS * 4 * D_FEAT * solo_rows
@@ -783,8 +794,8 @@ def main():
         tr, prov = committed_traffic(GMM_TRAFFIC_KEY if n_models == S_SPK + 1 else GMM_TRAFFIC_KEY.replace("6", str(n_models)))
         out["roofline"]["traffic"] = tr
         out["roofline"].update(prov)
-    if rank == 0 and world == 1 and not args.no_secondary and not args.faithful and args.enrol == "survey" and gmm_task == "OSI" \
-            and GMM_MODE == "fx2":
+    if rank == 0 and world == 1 and args.full and not args.no_secondary and not args.faithful and args.enrol == "survey" \
+            and gmm_task == "OSI" and GMM_MODE == "fx2":
         # ---- secondary measurements of the same run (rank 0, single GPU): small step counts, same code paths.  They
         #      bracket the headline (three delta products forced in every tile = the cost for ANY speaker models) and put
         #      the other configurations of BASELINE.json under the driver's eyes.
@@ -874,7 +885,7 @@ def main():
         except Exception as ex:  # noqa: BLE001
             out["secondary"]["ivector_error"] = repr(ex)[:300]
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline and gmm_task == "OSI":
+        if world == 1 and args.full and not args.no_cpu_baseline and gmm_task == "OSI":
             ckw = dict(kw)
             out["cpu_baseline"] = cpu_baseline(audio, models, ckw, args.faithful, int(args.frontend == "f32"))
             out["gpu_over_cpu_port"] = its / out["cpu_baseline"]["value"]

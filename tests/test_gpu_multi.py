@@ -104,8 +104,7 @@ def test_bench_self_launch_two_ranks_on_one_gpu_weak_scaling_arithmetic():
     twice it (never: they share the chip), with room for launch-gap filling."""
     import json
     env = dict(os.environ, PYTHONPATH=ROOT, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4")
-    common = ["--steps", "30", "--warmup", "5", "--streams", "1", "--no-cpu-baseline", "--no-secondary", "--no-single",
-              "--precondition", "20"]
+    common = ["--steps", "30", "--warmup", "5", "--streams", "1", "--precondition", "20"]   # plain runs: the headline only
 
     def run(extra):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + common + extra, stdout=subprocess.PIPE,
@@ -121,6 +120,10 @@ def test_bench_self_launch_two_ranks_on_one_gpu_weak_scaling_arithmetic():
     for d in (one, two):
         assert d["metric"].startswith("NES iterations/sec") and d["unit"] == "NES iterations/s"
         assert abs(d["scored_utts_per_s"] - 51 * d["value"]) <= 1e-6 * d["scored_utts_per_s"]
+        # without --full nothing beside the headline is measured: no solo kernel time, no extra passes, no CPU baseline
+        assert d["config"]["full"] is False and d["single_attack"] is None
+        assert "secondary" not in d and "cpu_baseline" not in d and "whole_chip_grid" not in d["roofline"]
+        assert not [k for k in d["roofline"] if k.startswith("solo_")] and d["roofline"]["avg_launch_ms"] > 0
     # value = (world x steps x attacks) / max-over-ranks time
     assert abs(two["value"] - 2 * 30 / (two["ms_per_step"] * 30 * 1e-3)) <= 1e-6 * two["value"]
     assert abs(one["value"] - 1 * 30 / (one["ms_per_step"] * 30 * 1e-3)) <= 1e-6 * one["value"]

@@ -417,6 +417,31 @@ def test_bench_roofline_object_and_traffic_file_follow_the_contract():
         assert val is None and prov["traffic_stale"] is True
 
 
+def test_bench_plain_run_roofline_has_no_solo_figures_and_full_is_an_option():
+    """A plain bench.py run times no kernel on its own: its roofline object (solo_ms = None) keeps the contract's keys
+    and carries no solo_* figure; `--full`, off by default, is the option that brings them (and every other extra
+    measurement) back, and the options that take parts of it away are still there."""
+    import importlib.util
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("fb_bench", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    flops = 6 * 2048 * 288 * 15300
+    r = bench._gmm_roofline(flops, 0.115, None, None, "fx2w/1", (64, 0, 0, 0))
+    for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "avg_launch_ms", "executed_frac"):
+        assert k in r
+    assert not [k for k in r if k.startswith("solo_")]
+    assert abs(r["achieved"] - flops / 115e-6 / 1e12) < 1e-6
+    h = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--help"], stdout=subprocess.PIPE,
+                       stderr=subprocess.PIPE, text=True, timeout=60)
+    assert h.returncode == 0, h.stderr[-2000:]
+    for opt in ("--full", "--no-cpu-baseline", "--no-single", "--no-secondary", "--dump-outputs"):
+        assert opt in h.stdout
+    assert "[--full]" in h.stdout                                           # a flag: off unless given
+
+
 def test_kaldi_text_spmatrix_is_lower_triangular_and_writers_round_trip(tmp_path):
     """Kaldi writes a text SpMatrix as its lower triangle, row i holding i + 1 numbers (PackedMatrix::Write): a
     hand-written text final.ubm must load; and the binary writers round-trip a synthetic i-vector system through

@@ -2,7 +2,7 @@
 # solo k_gmm_fx2w launch time (auto P and forced P=3) + 3-attack throughput
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$1; mkdir -p $O; cd $R
 for p in "" 3; do
-  FB_GMM_DELTA_P=$p python bench.py --steps 60 --warmup 10 --no-cpu-baseline --no-secondary > $O/q_p${p:-auto}.json 2>/dev/null
+  FB_GMM_DELTA_P=$p python bench.py --full --steps 60 --warmup 10 --no-cpu-baseline --no-secondary > $O/q_p${p:-auto}.json 2>/dev/null
   python - $O/q_p${p:-auto}.json <<'PY'
 import json,sys
 d=json.load(open(sys.argv[1])); r=d["roofline"]

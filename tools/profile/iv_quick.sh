@@ -3,7 +3,7 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$1; mkdir -p $O; cd $R
 for m in rw ll; do
   export FB_IV_SOLVE=$m
-  timeout 300 python bench.py --arch iv --steps 30 --warmup 5 --no-cpu-baseline > $O/iv_$m.json 2>$O/iv_$m.err
+  timeout 300 python bench.py --full --arch iv --steps 30 --warmup 5 --no-cpu-baseline > $O/iv_$m.json 2>$O/iv_$m.err
   python - $O/iv_$m.json $m <<'PY'
 import json,sys
 try:

@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT; tag=$1; O=$R/gpurun_out/$tag; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 prof() {  # name, bench args...
   local name=$1; shift
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/tmp_$name -o p -- python $R/bench.py "$@" --no-cpu-baseline > $O/${name}_bench.json 2>/dev/null
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/tmp_$name -o p -- python $R/bench.py --full "$@" --no-cpu-baseline > $O/${name}_bench.json 2>/dev/null
   f=$(find $O/tmp_$name -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/${name}_kernel_stats.csv
   rm -rf $O/tmp_$name
 }
@@ -18,20 +18,20 @@ prof iv_sv_1attack --arch iv --steps 50 --warmup 5 --streams 1
 prof iv_osi_b201_1attack --arch iv --task OSI --speakers 10 --spd 200 --steps 20 --warmup 3 --streams 1
 for grp in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum"; do
   name=$(echo $grp | cut -d' ' -f1)
-  rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $O/pmc_$name -o p -- python $R/bench.py --steps 20 --warmup 3 --streams 1 --no-cpu-baseline > /dev/null 2>&1
-  rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $O/pmciv_$name -o p -- python $R/bench.py --arch iv --steps 10 --warmup 2 --streams 1 --no-cpu-baseline > /dev/null 2>&1
+  rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $O/pmc_$name -o p -- python $R/bench.py --full --steps 20 --warmup 3 --streams 1 --no-cpu-baseline > /dev/null 2>&1
+  rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $O/pmciv_$name -o p -- python $R/bench.py --full --arch iv --steps 10 --warmup 2 --streams 1 --no-cpu-baseline > /dev/null 2>&1
 done
 cd $R
-python bench.py > $O/bench.json 2>/dev/null
-python bench.py --steps 20 --warmup 5 > $O/bench_driver_args.json 2>/dev/null
-python bench.py --faithful > $O/bench_faithful.json 2>/dev/null
-python bench.py --arch iv > $O/iv_bench.json 2>/dev/null
-python bench.py --arch iv --task OSI --speakers 10 --spd 200 --steps 30 --warmup 5 > $O/iv_osi_b201_bench.json 2>/dev/null
+python bench.py --full > $O/bench.json 2>/dev/null
+python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_args.json 2>/dev/null
+python bench.py --full --faithful > $O/bench_faithful.json 2>/dev/null
+python bench.py --full --arch iv > $O/iv_bench.json 2>/dev/null
+python bench.py --full --arch iv --task OSI --speakers 10 --spd 200 --steps 30 --warmup 5 > $O/iv_osi_b201_bench.json 2>/dev/null
 python - $O <<'PY'
 import csv, collections, glob, json, sys
 O = sys.argv[1]
 out = {"source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE | TCC_HIT_sum TCC_MISS_sum (three separate passes each) -- "
-                 "python bench.py [--arch iv] --streams 1 --no-cpu-baseline; per-launch averages; FETCH_SIZE/WRITE_SIZE in KiB as reported",
+                 "python bench.py --full [--arch iv] --streams 1 --no-cpu-baseline; per-launch averages; FETCH_SIZE/WRITE_SIZE in KiB as reported",
        "correction": "MI355X_MICROARCH.md HBM section: on gfx950 FETCH_SIZE reports half of the bytes of wide coalesced reads -> "
                      "hbm_bytes = (2*FETCH_SIZE + WRITE_SIZE) * 1024", "kernels": {}}
 for pre in ("pmc_", "pmciv_"):

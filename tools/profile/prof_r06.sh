@@ -9,7 +9,7 @@ R=$GRAFT_REPO_ROOT; tag=$1; commit=${2:-unknown}; O=$R/gpurun_out/$tag; mkdir -p
 cd /tmp && export TMPDIR=/tmp
 prof() {  # name, bench args...
   local name=$1; shift
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/tmp_$name -o p -- python $R/bench.py "$@" --no-cpu-baseline --no-secondary > $O/${name}_bench.json 2>/dev/null
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/tmp_$name -o p -- python $R/bench.py --full "$@" --no-cpu-baseline --no-secondary > $O/${name}_bench.json 2>/dev/null
   f=$(find $O/tmp_$name -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/${name}_kernel_stats.csv
   rm -rf $O/tmp_$name
 }
@@ -25,8 +25,8 @@ prof iv_sv_1attack --arch iv --steps 50 --warmup 5 --streams 1
 prof iv_osi_b201_1attack --arch iv --task OSI --speakers 10 --spd 200 --steps 20 --warmup 3 --streams 1
 for grp in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum"; do
   name=$(echo $grp | cut -d' ' -f1)
-  rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $O/pmc_$name -o p -- python $R/bench.py --steps 20 --warmup 3 --streams 1 --chain unfused --no-cpu-baseline --no-secondary > /dev/null 2>&1
-  rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $O/pmciv_$name -o p -- python $R/bench.py --arch iv --steps 10 --warmup 2 --streams 1 --no-cpu-baseline > /dev/null 2>&1
+  rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $O/pmc_$name -o p -- python $R/bench.py --full --steps 20 --warmup 3 --streams 1 --chain unfused --no-cpu-baseline --no-secondary > /dev/null 2>&1
+  rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $O/pmciv_$name -o p -- python $R/bench.py --full --arch iv --steps 10 --warmup 2 --streams 1 --no-cpu-baseline > /dev/null 2>&1
 done
 cd $R
 python - $O $commit <<'PY'
@@ -34,7 +34,7 @@ import csv, collections, glob, json, sys, importlib.util
 O, commit = sys.argv[1], sys.argv[2]
 spec = importlib.util.spec_from_file_location("fb_bench", "bench.py"); bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
 out = {"source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE | TCC_HIT_sum TCC_MISS_sum (three separate passes each) -- "
-                 "python bench.py [--arch iv] --streams 1 --no-cpu-baseline --no-secondary; per-launch averages; FETCH_SIZE/WRITE_SIZE in KiB as reported",
+                 "python bench.py --full [--arch iv] --streams 1 --no-cpu-baseline --no-secondary; per-launch averages; FETCH_SIZE/WRITE_SIZE in KiB as reported",
        "correction": "MI355X_MICROARCH.md HBM section: on gfx950 FETCH_SIZE reports half of the bytes of wide coalesced reads -> "
                      "hbm_bytes = (2*FETCH_SIZE + WRITE_SIZE) * 1024",
        "kernel_source_sha16": bench.kernel_source_hash(), "commit": commit, "kernels": {}}
@@ -69,11 +69,11 @@ PY
 rm -rf $O/pmc_* $O/pmciv_*
 # the default lines read the traffic file just written (same sources): put it where bench.py looks
 cp $O/traffic.json $R/profiles/r06_traffic.json
-python bench.py > $O/bench.json 2> $O/bench.err
-python bench.py --steps 20 --warmup 5 > $O/bench_driver_args.json 2>/dev/null
-python bench.py --faithful --no-secondary > $O/bench_faithful.json 2>/dev/null
-python bench.py --task CSI --no-secondary > $O/bench_gmm_csi.json 2>/dev/null
-python bench.py --enrol realistic --no-secondary > $O/bench_realistic.json 2>/dev/null
-python bench.py --arch iv > $O/iv_bench.json 2>/dev/null
-python bench.py --arch iv --task OSI --speakers 10 --spd 200 --steps 30 --warmup 5 > $O/iv_osi_b201_bench.json 2>/dev/null
+python bench.py --full > $O/bench.json 2> $O/bench.err
+python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_args.json 2>/dev/null
+python bench.py --full --faithful --no-secondary > $O/bench_faithful.json 2>/dev/null
+python bench.py --full --task CSI --no-secondary > $O/bench_gmm_csi.json 2>/dev/null
+python bench.py --full --enrol realistic --no-secondary > $O/bench_realistic.json 2>/dev/null
+python bench.py --full --arch iv > $O/iv_bench.json 2>/dev/null
+python bench.py --full --arch iv --task OSI --speakers 10 --spd 200 --steps 30 --warmup 5 > $O/iv_osi_b201_bench.json 2>/dev/null
 ls $O

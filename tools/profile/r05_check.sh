@@ -5,7 +5,7 @@ cd $R
 timeout 1500 python -m pytest tests -m gpu -x -q -s > $O/pytest.log 2>&1; echo "pytest rc $?" >> $O/pytest.log
 grep -v "^\." $O/pytest.log | grep -i "enrolment\|max |err|\|  auto\|  p1\|  p3\|attack of the tail\|passed\|failed\|error\|rc " | tail -40
 timeout 600 bash tools/profile/fxw_instrumented.sh gpurun_out/$tag/fxw > $O/fxw.log 2>&1; tail -4 $O/fxw.log
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench_driver_args.json 2> $O/bench_driver_args.err
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_args.json 2> $O/bench_driver_args.err
 python - $O <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1] + "/bench_driver_args.json"))

@@ -7,7 +7,7 @@ tail -4 $O/pytest_gmm.log
 cd /tmp && export TMPDIR=/tmp
 prof() {
   local name=$1; shift
-  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/tmp_$name -o p -- python $R/bench.py "$@" --no-cpu-baseline --no-secondary > $O/${name}_bench.json 2>/dev/null
+  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/tmp_$name -o p -- python $R/bench.py --full "$@" --no-cpu-baseline --no-secondary > $O/${name}_bench.json 2>/dev/null
   f=$(find $O/tmp_$name -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/${name}_kernel_stats.csv
   rm -rf $O/tmp_$name
 }
@@ -27,6 +27,6 @@ for n in ("gmm_1attack", "gmm_1attack_split"):
         print(n, "sum %.1f us; ms/step %.4f value %.0f" % (tot, d["ms_per_step"], d["value"]))
     except Exception as ex: print(n, ex)
 PY
-timeout 300 python bench.py --no-cpu-baseline --no-secondary --steps 100 --warmup 10 > $O/bench3.json 2>/dev/null
+timeout 300 python bench.py --full --no-cpu-baseline --no-secondary --steps 100 --warmup 10 > $O/bench3.json 2>/dev/null
 python -c "
 import json; d=json.load(open('$O/bench3.json')); print('3 attacks', d['value'], 'single', d['single_attack'])"

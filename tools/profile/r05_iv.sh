@@ -6,14 +6,14 @@ timeout 900 python -m pytest tests/test_gpu_ivector.py tests/test_gpu_fullsize_i
 cd /tmp && export TMPDIR=/tmp
 prof() {
   local name=$1; shift
-  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/tmp_$name -o p -- python $R/bench.py "$@" --no-cpu-baseline --no-secondary > $O/${name}_bench.json 2>/dev/null
+  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/tmp_$name -o p -- python $R/bench.py --full "$@" --no-cpu-baseline --no-secondary > $O/${name}_bench.json 2>/dev/null
   f=$(find $O/tmp_$name -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/${name}_kernel_stats.csv
   rm -rf $O/tmp_$name
 }
 prof iv_sv_1attack --arch iv --steps 50 --warmup 5 --streams 1
 prof iv_osi_b201_1attack --arch iv --task OSI --speakers 10 --spd 200 --steps 20 --warmup 3 --streams 1
 cd $R
-timeout 600 python bench.py --arch iv --no-cpu-baseline > $O/iv_bench.json 2>/dev/null
+timeout 600 python bench.py --full --arch iv --no-cpu-baseline > $O/iv_bench.json 2>/dev/null
 tail -4 $O/pytest_iv.log
 python - $O <<'PY'
 import csv, json, sys

@@ -7,7 +7,7 @@ tail -6 $O/pytest_mfcc.log
 cd /tmp && export TMPDIR=/tmp
 prof() {
   local name=$1; shift
-  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/tmp_$name -o p -- python $R/bench.py "$@" --no-cpu-baseline --no-secondary > $O/${name}_bench.json 2>/dev/null
+  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/tmp_$name -o p -- python $R/bench.py --full "$@" --no-cpu-baseline --no-secondary > $O/${name}_bench.json 2>/dev/null
   f=$(find $O/tmp_$name -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/${name}_kernel_stats.csv
   rm -rf $O/tmp_$name
 }
@@ -27,7 +27,7 @@ for n in ("gmm_1attack", "gmm_1attack_records"):
         print(n, "sum %.1f us; ms/step %.4f value %.0f" % (tot, d["ms_per_step"], d["value"]))
     except Exception as ex: print(n, ex)
 PY
-timeout 300 python bench.py --no-cpu-baseline --no-secondary --steps 200 --warmup 20 > $O/bench3.json 2>/dev/null
+timeout 300 python bench.py --full --no-cpu-baseline --no-secondary --steps 200 --warmup 20 > $O/bench3.json 2>/dev/null
 python -c "
 import json; d=json.load(open('$O/bench3.json')); print('3 attacks', d['value'], d['secondary'].get('single_attack') if 'secondary' in d else '')"
 bash tools/profile/mfcc_instrumented.sh gpurun_out/$tag/stamps > /dev/null 2>&1; cat gpurun_out/$tag/stamps/mfcc_stamps.txt | head -12

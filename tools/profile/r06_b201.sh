@@ -3,7 +3,7 @@
 R=$GRAFT_REPO_ROOT; tag=${1:-r06_b201}; O=$R/gpurun_out/$tag; mkdir -p $O; cd $R
 for m in new dump; do
   unset FB_IV_GSEL_DUMP; [ $m = dump ] && export FB_IV_GSEL_DUMP=1
-  timeout 600 python bench.py --arch iv --task OSI --speakers 10 --spd 200 --steps 10 --warmup 3 --no-cpu-baseline > $O/b201_$m.json 2>$O/b201_$m.err
+  timeout 600 python bench.py --full --arch iv --task OSI --speakers 10 --spd 200 --steps 10 --warmup 3 --no-cpu-baseline > $O/b201_$m.json 2>$O/b201_$m.err
   python - $O/b201_$m.json $m <<'PY'
 import json,sys
 try:

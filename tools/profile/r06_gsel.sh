@@ -8,7 +8,7 @@ timeout 900 python -m pytest tests/test_gpu_ivector.py tests/test_gpu_fullsize_i
 tail -5 $O/pytest_iv.log
 for m in new dump; do
   unset FB_IV_GSEL_DUMP FB_GSEL_NARROW; [ $m = dump ] && export FB_IV_GSEL_DUMP=1
-  timeout 300 python bench.py --arch iv --steps 30 --warmup 5 --no-cpu-baseline > $O/iv_$m.json 2>$O/iv_$m.err
+  timeout 300 python bench.py --full --arch iv --steps 30 --warmup 5 --no-cpu-baseline > $O/iv_$m.json 2>$O/iv_$m.err
   python - $O/iv_$m.json $m <<'PY'
 import json,sys
 try:
@@ -18,7 +18,7 @@ PY
 done
 unset FB_IV_GSEL_DUMP FB_GSEL_NARROW
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/tmp_iv -o p -- python $R/bench.py --arch iv --steps 50 --warmup 5 --streams 1 --no-cpu-baseline --no-secondary > $O/iv_sv_1attack_bench.json 2>/dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/tmp_iv -o p -- python $R/bench.py --full --arch iv --steps 50 --warmup 5 --streams 1 --no-cpu-baseline --no-secondary > $O/iv_sv_1attack_bench.json 2>/dev/null
 f=$(find $O/tmp_iv -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/iv_sv_1attack_kernel_stats.csv
 rm -rf $O/tmp_iv
 python - $O/iv_sv_1attack_kernel_stats.csv <<'PY'

@@ -7,9 +7,9 @@ FB_IV_SOLVE=ll timeout 900 python -m pytest tests/test_gpu_ivector.py tests/test
 bash tools/profile/rw_instrumented.sh gpurun_out/$tag/rw 2>&1 | tail -16
 rm -f gpurun_out/$tag/rw/*.o gpurun_out/$tag/rw/*.so
 for v in tree; do
-  timeout 300 python bench.py --arch iv --steps 40 --warmup 5 --streams 1 --no-cpu-baseline > $O/sv_$v.json 2>$O/sv_$v.err
-  timeout 300 python bench.py --arch iv --task OSI --speakers 10 --spd 200 --steps 10 --warmup 3 --streams 1 --no-cpu-baseline > $O/b201_$v.json 2>$O/b201_$v.err
-  timeout 300 python bench.py --arch iv --steps 40 --warmup 5 --streams 3 --no-cpu-baseline > $O/sv3_$v.json 2>$O/sv3_$v.err
+  timeout 300 python bench.py --full --arch iv --steps 40 --warmup 5 --streams 1 --no-cpu-baseline > $O/sv_$v.json 2>$O/sv_$v.err
+  timeout 300 python bench.py --full --arch iv --task OSI --speakers 10 --spd 200 --steps 10 --warmup 3 --streams 1 --no-cpu-baseline > $O/b201_$v.json 2>$O/b201_$v.err
+  timeout 300 python bench.py --full --arch iv --steps 40 --warmup 5 --streams 3 --no-cpu-baseline > $O/sv3_$v.json 2>$O/sv3_$v.err
   python - $O $v <<'PY'
 import json,sys
 for n in ("sv","b201","sv3"):

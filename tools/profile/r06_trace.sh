@@ -1,6 +1,6 @@
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r06_trace; mkdir -p $O
-rocprofv3 --kernel-trace --output-format csv -d $O/t -o p -- python $R/bench.py --steps 60 --warmup 10 --repeats 3 --no-cpu-baseline --no-secondary --no-single > $O/bench.json 2>/dev/null
+rocprofv3 --kernel-trace --output-format csv -d $O/t -o p -- python $R/bench.py --full --steps 60 --warmup 10 --repeats 3 --no-cpu-baseline --no-secondary --no-single > $O/bench.json 2>/dev/null
 f=$(find $O/t -name "*kernel_trace.csv" | head -1)
 python - $f <<'PY'
 import csv, sys

@@ -1,6 +1,6 @@
 """How k_update_perturb meets the other attacks' k_gmm_fx2w launches on a shared GPU, from a rocprofv3 kernel trace:
 
-    rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o p -- python bench.py --no-cpu-baseline --no-secondary
+    rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o p -- python bench.py --full --no-cpu-baseline --no-secondary
     python tools/profile/update_shape_trace.py <dir>/.../p_kernel_trace.csv
 
 For every k_update_perturb dispatch: how many k_gmm_fx2w dispatches of OTHER streams were running when it started, and the

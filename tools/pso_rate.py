@@ -7,7 +7,7 @@ D = 72, float32 MFCC, 3 s of audio): one engine, one attack in flight, the stop 
 Prints one JSON line per swarm size: iterations/s over the whole fb_attack_pso call (wall clock around it, after a short
 warm-up attack), the mean and the median of the per-iteration host times (fb_attack_iter_seconds) and the best loss at both
 ends.  A P = 51 iteration scores the batch an NES iteration at samples_per_draw = 50 scores, plus one look of the host: compare
-with bench.py's `single_attack` on the same machine in the same session.  k_pso_step's own time comes from a kernel trace of
+with `bench.py --full`'s `single_attack` on the same machine in the same session.  k_pso_step's own time comes from a kernel trace of
 this script (rocprofv3 --kernel-trace --stats -- python tools/pso_rate.py ...), not from here."""
 import argparse
 import json
