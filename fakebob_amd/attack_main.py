@@ -201,7 +201,11 @@ def main(argv=None, model_factory=None, bob_factory=None):
                          "Kenansville's decision-only spectral removal (fakebob_amd/kenansville.py; --kv-* and --seed apply) or the "
                          "white-box gradient attack (fakebob_amd/pgd.py: the analytic gradient of a GMM-UBM system in FAKEBOB's "
                          "loop; -momentum 0 is PGD, -max_iter 1 the single step; -samples and -sigma do not apply; an undefended "
-                         "victim only)")
+                         "victim unless --bpda is given)")
+    ap.add_argument("--bpda", action="store_true",
+                    help="--attack pgd: the adaptive attack on a defended victim -- BPDA through --input-transform and --codec, "
+                         "expectation over --eot-size draws of the random stages; --air-channel, --feco, --dither and "
+                         "--companions stay refused")
     ap.add_argument("--kv-window", dest="kv_window", default=100, type=int, help="--attack kenansville: samples per window (8 .. 128)")
     ap.add_argument("--kv-grid", dest="kv_grid", default=15, type=int, help="--attack kenansville: candidates per round (1 .. 64)")
     ap.add_argument("--kv-max-factor", dest="kv_max_factor", default=1.0, type=float,
@@ -231,16 +235,18 @@ def main(argv=None, model_factory=None, bob_factory=None):
         if args.companions > 0:
             ap.error("--attack kenansville does not take companion utterances (--companions %d)" % args.companions)
 
-    if args.attack == "pgd":      # likewise: the gradient is that of an undefended GMM-UBM victim (no BPDA, no EOT in this version)
+    if args.bpda and args.attack != "pgd":
+        ap.error("--bpda belongs to --attack pgd (--attack %s)" % args.attack)
+    if args.attack == "pgd":      # likewise: the gradient is that of a GMM-UBM victim, undefended unless --bpda is given
         if args.architecture != "gmm":
             ap.error("--attack pgd differentiates GMM-UBM systems only (--architecture %s)" % args.architecture)
-        if args.eot_size is not None and args.eot_size > 1:
+        if not args.bpda and args.eot_size is not None and args.eot_size > 1:
             ap.error("--attack pgd does not run under expectation over transformation (--eot-size %d)" % args.eot_size)
         if args.companions > 0:
             ap.error("--attack pgd does not take companion utterances (--companions %d)" % args.companions)
         for flag, val in (("--input-transform", args.input_transform), ("--air-channel", args.air_channel),
                           ("--codec", None if args.codec == "none" else args.codec), ("--feco", args.feco), ("--dither", args.dither)):
-            if val is not None:
+            if val is not None and not (args.bpda and flag in ("--input-transform", "--codec")):
                 ap.error("--attack pgd attacks an undefended victim: %s %s is not differentiated in this version" % (flag, val))
 
     task, attack_type, spk_id_list = args.task, args.attack_type, args.speaker_id
@@ -289,9 +295,11 @@ def main(argv=None, model_factory=None, bob_factory=None):
     if args.attack == "pgd":
         hp = dict(adver_thresh=args.adver_thresh, epsilon=args.epsilon, max_iter=args.max_iter, max_lr=args.max_lr,
                   min_lr=args.min_lr, momentum=args.momentum, plateau_length=args.plateau_length, plateau_drop=args.plateau_drop)
+        if args.bpda:  # (absent otherwise: a bob_factory of the driver-rule tests sees the keywords it always saw)
+            hp.update(bpda=True, eot_size=args.eot_size if args.eot_size is not None else 1)
     if bob_factory is None and args.attack == "pgd":
-        from .pgd import PGD
-        bobs = [PGD(task, attack_type, m, seed=seed, verbose=False, **hp) for m in models]
+        from .pgd import PGD, AdaptivePGD
+        bobs = [(AdaptivePGD if args.bpda else PGD)(task, attack_type, m, seed=seed, verbose=False, **hp) for m in models]
     elif bob_factory is None and args.attack == "kenansville":
         from .kenansville import Kenansville
         bobs = [Kenansville(task, attack_type, m, seed=seed, verbose=False, **hp) for m in models]

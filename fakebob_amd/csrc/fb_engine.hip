@@ -48,7 +48,7 @@ static int fb_fail(int code, const char *fmt, ...) {
   } while (0)
 
 extern "C" const char *fb_last_error(void) { return g_err.c_str(); }
-extern "C" int fb_version(void) { return 100; }
+extern "C" int fb_version(void) { return 101; }
 extern "C" int fb_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -221,6 +221,11 @@ struct fb_engine {
   std::vector<float> h_wb_gc, h_wb_miv, h_wb_iv;
   bool wb_uploaded = false;
   DevBuf wb_gc, wb_miv, wb_iv, wb_w, wb_part, wb_g, wb_rank, wb_dcm, wb_ddf, wb_dmf, wb_dxf, wb_status;
+  // white-box gradients through a defended victim (fb_set_wb_bpda)
+  int wb_bpda = 0;                     // the switch: 0 (as created) refuses every defence, as before it existed
+  DevBuf wb_gj;                        // one replica's cotangent on the row the front end read [N]
+  const int16_t *fe_wav = nullptr;     // the int16 batch the last launch_mfcc handed to the front end (a device buffer of the engine's)
+  int wb_route[FB_WB_ROUTE_N] = {};    // launches of the white-box backward the last call enqueued (fb_debug_wb_route)
   FbNesDev *h_out = nullptr;  // pinned
   int *h_tv = nullptr;        // pinned, grows
   size_t h_tv_cap = 0;
@@ -893,6 +898,7 @@ static int launch_mfcc(fb_engine *e, const FbScoreCall &call, const FbFrontendDe
   hipStream_t s = e->stream;
   const int16_t *wav = nullptr;
   FBCHK(transformed_wav(e, call, e->h_wav_off.data(), B, &wav));
+  e->fe_wav = wav;
   e->have_route = true;
   e->route[3] = e->t_max;
   e->route[4] = B;
@@ -2306,19 +2312,22 @@ extern "C" int fb_attack_dev(fb_engine *e, const fb_nes_params *p, int S, const 
 
 // ------------------------------------------------- white-box gradients: fb_get_grad_wb / fb_attack_wb
 // The analytic gradient of the loss with respect to the samples ("white-box gradients" in fakebob_hip.h): GMM-UBM systems on
-// an undefended victim.  Everything else is refused by name.
+// an undefended victim; with fb_set_wb_bpda(e, 1) through an input-transform chain, a codec and EOT replicas as well
+// (BPDA / EOT, the same contract).  Everything else is refused by name.
 static int wb_check(fb_engine *e, const fb_nes_params *p, const double *audio, int64_t N, fb_nes_params *q) {
   if (!e || !p || !audio) return fb_fail(FB_E_ARG, "null argument");
   if (!e->have_gmm) return fb_fail(FB_E_STATE, "no model loaded");
   if (e->kind != 0) return fb_fail(FB_E_STATE, "white-box gradients: an i-vector system is loaded (GMM-UBM systems only in this version)");
-  if (e->eot > 1) return fb_fail(FB_E_STATE, "white-box gradients: fb_set_eot(%d) is in force (set 1)", e->eot);
+  if (e->eot > 1 && !e->wb_bpda) return fb_fail(FB_E_STATE, "white-box gradients: fb_set_eot(%d) is in force (set 1)", e->eot);
   if (e->comp_K1 > 0) return fb_fail(FB_E_STATE, "white-box gradients: companions are set (fb_set_companions: clear them)");
-  if (e->tf.n > 0) return fb_fail(FB_E_STATE, "white-box gradients: an input-transform chain is set (no BPDA through defences in this version)");
+  if (e->tf.n > 0 && !e->wb_bpda)
+    return fb_fail(FB_E_STATE, "white-box gradients: an input-transform chain is set (no BPDA through defences in this version)");
+  // (the channel's transpose is not in this version: refused with the switch on as well)
   if (e->air.L > 0) return fb_fail(FB_E_STATE, "white-box gradients: an air channel is set (fb_set_air_channel: clear it)");
-  if (e->codec != FB_CODEC_NONE) return fb_fail(FB_E_STATE, "white-box gradients: a codec is set (fb_set_codec: clear it)");
+  if (e->codec != FB_CODEC_NONE && !e->wb_bpda) return fb_fail(FB_E_STATE, "white-box gradients: a codec is set (fb_set_codec: clear it)");
   if (e->feco_iters > 0) return fb_fail(FB_E_STATE, "white-box gradients: feature compression is on (fb_set_feature_compression: switch it off)");
   if (e->cfg.dither > 0.0) return fb_fail(FB_E_STATE, "white-box gradients: dither %g > 0 (the function is differentiated at a fixed victim)", e->cfg.dither);
-  // one row is scored per iteration; the NES-only fields are not read
+  // one row is scored per iteration; of the NES-only fields seed and stream key the draws of a randomised defence
   *q = *p;
   q->samples_per_draw = 0;
   q->sigma = 1.0;
@@ -2350,48 +2359,91 @@ static int wb_prepare(fb_engine *e, int64_t N, int T, bool need_gmm) {
   FBCHK(e->wb_dmf.ensure(sizeof(double) * (size_t)T * fe.nc));
   FBCHK(e->wb_dxf.ensure(sizeof(double) * (size_t)T * fe.L));
   FBCHK(e->grad.ensure(sizeof(double) * (size_t)N));
+  if (e->wb_bpda) FBCHK(e->wb_gj.ensure(sizeof(double) * (size_t)N));
   if (!e->wb_status.p) FBCHK(e->wb_status.ensure(sizeof(int)));
   HIPCHK(hipMemsetAsync(e->wb_status.p, 0, sizeof(int), e->stream));
   return FB_OK;
 }
 
 // the GMM backward on the n rows (*n_rows_ptr <= T) of e->feats with the weights in e->wb_w: the cotangent lands in e->wb_g
-static void wb_launch_gmm_backward(fb_engine *e, const int *n_rows_ptr, int T, const int *stop) {
+// row_base_ptr (nullable): the first of the rows, when they are a replica's within the batch
+static void wb_launch_gmm_backward(fb_engine *e, const int *n_rows_ptr, int T, const int *stop, const int *row_base_ptr = nullptr) {
   const FbGmmDev &g = e->gmm;
   fb_launch_wb_gmm_backward(e->stream, g.M, g.C, g.D, e->wb_gc.as<float>(), e->wb_miv.as<float>(), e->wb_iv.as<float>(),
                             e->feats.as<float>(), n_rows_ptr, T, e->wb_w.as<double>(), e->wb_part.as<float>(), e->wb_g.as<double>(),
+                            stop, row_base_ptr);
+}
+// the front-end backward of row j of the batch the front end read (`wav`: rows of N samples, T frames each, their MFCC
+// matrices in e->mfcc): out = scale * the cotangent on that row's int16 samples
+static void wb_launch_frontend_vjp(fb_engine *e, const int16_t *wav, int j, int64_t N, int T, double scale, double *out, const int *stop) {
+  fb_launch_wb_frontend_vjp(e->stream, e->fe, wav + (size_t)j * (size_t)N, N, T, e->mfcc.as<float>() + (size_t)j * T * e->fe.nc,
+                            e->wb_g.as<double>(), e->tv.as<int>() + j, e->wb_rank.as<int>(), e->wb_dcm.as<double>(),
+                            e->wb_ddf.as<double>(), e->wb_dmf.as<double>(), e->wb_dxf.as<double>(), scale, out, e->wb_status.as<int>(),
                             stop);
 }
-// the front-end backward of the utterance in e->wav (N samples, T frames, its MFCC matrix in e->mfcc): e->grad = scale * the
-// cotangent on the int16 samples
-static void wb_launch_frontend_vjp(fb_engine *e, int64_t N, int T, double scale, const int *stop) {
-  fb_launch_wb_frontend_vjp(e->stream, e->fe, e->wav.as<int16_t>(), N, T, e->mfcc.as<float>(), e->wb_g.as<double>(), e->tv.as<int>(),
-                            e->wb_rank.as<int>(), e->wb_dcm.as<double>(), e->wb_ddf.as<double>(), e->wb_dmf.as<double>(),
-                            e->wb_dxf.as<double>(), scale, e->grad.as<double>(), e->wb_status.as<int>(), stop);
+// the chain's transpose for replica j at the call's point: grad (+)= the vector-Jacobian product of cot through the chain
+// applied to the un-replicated row in e->wav (k_tf_power's sum of the forward is still in e->tf_power)
+static int wb_launch_chain_t(fb_engine *e, const FbRngPoint &pt, int j, int64_t N, const double *cot, double *grad, bool accumulate,
+                             const int *stop) {
+  FbTfRnd rn = fb_tf_rnd(pt, e->eot);
+  rn.power = tf_noise_stages(e->tf, true) > 0 ? e->tf_power.as<unsigned long long>() : nullptr;
+  if (!fb_launch_wb_chain_t(e->stream, e->tf, e->tf_taps.as<double>(), e->wav.as<int16_t>(), N, rn, j, cot, grad, accumulate ? 1 : 0, stop))
+    return fb_fail(FB_E_HIP, "k_wb_chain_t: %zu bytes of LDS were refused", fb_wb_chain_t_lds_bytes(e->tf));
+  e->wb_route[FB_WB_ROUTE_CHAIN_T] += 1;
+  return FB_OK;
 }
 
 // One white-box iteration on the device-resident adver, asynchronous: the forward of fb_get_grad on ONE row -- the cast
 // (k_perturb without noise), the scoring chain, k_loss --, then the weights (and, with ctl, the loop control), the GMM
 // backward and the front-end backward.  q: the call's parameters with samples_per_draw = 0.
+// With fb_set_wb_bpda on and a defence or EOT replicas set: the forward scores the r replicas of the row (k_loss_eot when
+// r > 1), and behind it the replicas follow one by one -- weights of replica j, GMM backward on its voiced rows, front-end
+// backward on the row ITS front end read, the chain's transpose, which also adds replica j to e->grad (j ascending).
 static int wb_enqueue(fb_engine *e, const fb_nes_params *q, int64_t N, uint32_t it, bool with_dist, FbCtlDev *ctl, double *trace_dev) {
   const int *stop = ctl ? &ctl->stop : nullptr;
+  const int r = e->eot;  // (companions are refused: the replicas are the EOT draws)
   int ndp = 0;
   fb_launch_perturb(e->stream, e->adver.as<double>(), with_dist ? e->audio.as<double>() : nullptr, N, 0, q->sigma, q->seed, it,
                     q->stream, nullptr, e->wav.as<int16_t>(), e->dist_part.as<double>(), &ndp, nullptr, stop, nes_bits(q));
   e->pre_iter = -1;
-  FbScoreCall call{FbRngPoint{q->seed, q->stream, it, 0}};
+  const FbRngPoint pt{q->seed, q->stream, it, 0};
+  FbScoreCall call{pt};
+  call.eot = r;
   call.stop = stop;
   const int T = e->h_frame_off[1];
-  FBCHK(run_scoring(e, call, 1, T));
-  fb_launch_loss(e->stream, e->raw.as<double>(), e->tv.as<int>(), 1, e->n_out, q->task, e->kind, q->attack_type,
-                 e->zmean.as<double>(), e->zstd.as<double>(), q->threshold, q->adver_thresh, q->target, q->true_label,
-                 e->dist_part.as<double>(), with_dist ? ndp : 0, e->scores.as<double>(), e->loss.as<double>(),
-                 e->nes_out.as<FbNesDev>());
+  FBCHK(run_scoring(e, call, r, e->h_frame_off[r]));
+  const double scale = ldexp(1.0, nes_bits(q) - 1);
+  if (r > 1) {
+    fb_launch_loss_eot(e->stream, e->raw.as<double>(), e->tv.as<int>(), 1, r, e->n_out, q->task, e->kind, q->attack_type,
+                       e->zmean.as<double>(), e->zstd.as<double>(), q->threshold, q->adver_thresh, q->target, q->true_label,
+                       e->dist_part.as<double>(), with_dist ? ndp : 0, e->eot_sc.as<double>(), e->eot_l.as<double>(),
+                       e->scores.as<double>(), e->loss.as<double>(), e->nes_out.as<FbNesDev>(), nullptr, nullptr, 0);
+  } else {
+    fb_launch_loss(e->stream, e->raw.as<double>(), e->tv.as<int>(), 1, e->n_out, q->task, e->kind, q->attack_type,
+                   e->zmean.as<double>(), e->zstd.as<double>(), q->threshold, q->adver_thresh, q->target, q->true_label,
+                   e->dist_part.as<double>(), with_dist ? ndp : 0, e->scores.as<double>(), e->loss.as<double>(),
+                   e->nes_out.as<FbNesDev>());
+  }
   e->nes_route[FB_NES_ROUTE_K_LOSS] += 1;
-  fb_launch_wb_ctl(e->stream, e->scores.as<double>(), e->nes_out.as<FbNesDev>(), e->gmm.M, q->task, q->attack_type,
-                   e->zstd.as<double>(), q->threshold, q->target, q->true_label, e->wb_w.as<double>(), ctl, trace_dev, (int)it);
-  wb_launch_gmm_backward(e, e->row_off.as<int>() + 1, T, stop);
-  wb_launch_frontend_vjp(e, N, T, ldexp(1.0, nes_bits(q) - 1), stop);
+  const bool through_chain = e->tf.n > 0 || r > 1;  // (a codec alone is the identity: the front-end backward writes e->grad)
+  const int S = fb_num_speakers(e);
+  for (int j = 0; j < r; ++j) {
+    if (r > 1) {
+      fb_launch_wb_ctl_rep(e->stream, e->eot_sc.as<double>() + (size_t)j * S, e->scores.as<double>(), e->nes_out.as<FbNesDev>(),
+                           e->gmm.M, r, q->task, q->attack_type, e->zstd.as<double>(), q->threshold, q->target, q->true_label,
+                           e->wb_w.as<double>(), ctl, j == 0 ? 1 : 0, trace_dev, (int)it);
+      e->wb_route[FB_WB_ROUTE_CTL_REP] += 1;
+    } else {
+      fb_launch_wb_ctl(e->stream, e->scores.as<double>(), e->nes_out.as<FbNesDev>(), e->gmm.M, q->task, q->attack_type,
+                       e->zstd.as<double>(), q->threshold, q->target, q->true_label, e->wb_w.as<double>(), ctl, trace_dev, (int)it);
+      e->wb_route[FB_WB_ROUTE_CTL] += 1;
+    }
+    // (row_off[0] = 0 and tv[0] = row_off[1]: replica 0 of an unreplicated batch is what the launch always took)
+    wb_launch_gmm_backward(e, r > 1 ? e->tv.as<int>() + j : e->row_off.as<int>() + 1, T, stop, r > 1 ? e->row_off.as<int>() + j : nullptr);
+    wb_launch_frontend_vjp(e, e->fe_wav, j, N, T, scale, through_chain ? e->wb_gj.as<double>() : e->grad.as<double>(), stop);
+    e->wb_route[FB_WB_ROUTE_BACKWARD] += 1;
+    if (through_chain) FBCHK(wb_launch_chain_t(e, pt, j, N, e->wb_gj.as<double>(), e->grad.as<double>(), j > 0, stop));
+  }
   return FB_OK;
 }
 
@@ -2401,10 +2453,12 @@ static int wb_status_check(fb_engine *e, int status) {
 }
 
 // mirrors FakeBob.get_grad + loss_fn (FAKEBOB.py:223-299) with the analytic gradient in place of the NES estimate
-extern "C" int fb_get_grad_wb(fb_engine *e, const fb_nes_params *p, const double *audio, int64_t N, double *adver_loss,
-                              double *grad, double *score0) {
+extern "C" int fb_get_grad_wb_iter(fb_engine *e, const fb_nes_params *p, const double *audio, int64_t N, int iter,
+                                   double *adver_loss, double *grad, double *score0) {
   if (e) e->bench_it = -1;
   if (e) memset(e->nes_route, 0, sizeof(e->nes_route));
+  if (e) memset(e->wb_route, 0, sizeof(e->wb_route));
+  if (iter < 0) return fb_fail(FB_E_ARG, "iter must be >= 0");
   fb_nes_params q;
   FBCHK(wb_check(e, p, audio, N, &q));
   HIPCHK(hipSetDevice(e->device));
@@ -2412,7 +2466,7 @@ extern "C" int fb_get_grad_wb(fb_engine *e, const fb_nes_params *p, const double
   FBCHK(ensure_nes_buffers(e, N, 1));
   FBCHK(wb_prepare(e, N, e->h_frame_off[1], true));
   FBCHK(h2d(e, e->adver.p, audio, sizeof(double) * (size_t)N));
-  FBCHK(wb_enqueue(e, &q, N, 0, false, nullptr, nullptr));
+  FBCHK(wb_enqueue(e, &q, N, (uint32_t)iter, false, nullptr, nullptr));
   int status = 0;
   if (grad) FBCHK(d2h(e, grad, e->grad.p, sizeof(double) * (size_t)N));
   FBCHK(d2h(e, &status, e->wb_status.p, sizeof(int)));
@@ -2424,6 +2478,17 @@ extern "C" int fb_get_grad_wb(fb_engine *e, const fb_nes_params *p, const double
   if (score0) for (int s = 0; s < fb_num_speakers(e); ++s) score0[s] = e->h_out->score0[s];
   return FB_OK;
 }
+extern "C" int fb_get_grad_wb(fb_engine *e, const fb_nes_params *p, const double *audio, int64_t N, double *adver_loss,
+                              double *grad, double *score0) {
+  return fb_get_grad_wb_iter(e, p, audio, N, 0, adver_loss, grad, score0);
+}
+
+extern "C" int fb_set_wb_bpda(fb_engine *e, int on) {
+  if (!e) return fb_fail(FB_E_ARG, "null engine");
+  if (on != 0 && on != 1) return fb_fail(FB_E_ARG, "fb_set_wb_bpda takes 0 or 1, not %d", on);
+  e->wb_bpda = on;
+  return FB_OK;
+}
 
 // mirrors FakeBob.attack (FAKEBOB.py:139-221) with the analytic gradient in place of get_grad: the loop control runs on the
 // device (k_wb_ctl), the host looks at the control block once per FB_ATTACK_BATCH iterations, as attack_loop does
@@ -2431,6 +2496,7 @@ extern "C" int fb_attack_wb(fb_engine *e, const fb_nes_params *p, const double *
                             double *adver_f64, double *trace, int *n_trace, int *success_flag) {
   if (e) e->bench_it = -1;
   if (e) memset(e->nes_route, 0, sizeof(e->nes_route));
+  if (e) memset(e->wb_route, 0, sizeof(e->wb_route));
   if (!adv_i16 || !success_flag) return fb_fail(FB_E_ARG, "null argument");
   fb_nes_params q;
   FBCHK(wb_check(e, p, audio, N, &q));
@@ -3674,7 +3740,7 @@ extern "C" int fb_debug_frontend_vjp(fb_engine *e, const int16_t *wav, int64_t n
   if (tv <= 0) return fb_fail(FB_E_NO_VOICED, "the utterance has no voiced frames");
   FBCHK(wb_prepare(e, n, T, false));
   FBCHK(h2d(e, e->wb_g.p, cot, sizeof(double) * (size_t)tv * e->fe.dim));
-  wb_launch_frontend_vjp(e, n, T, 1.0, nullptr);
+  wb_launch_frontend_vjp(e, e->fe_wav, 0, n, T, 1.0, e->grad.as<double>(), nullptr);
   std::vector<int> rank((size_t)T);
   FBCHK(d2h(e, dwav, e->grad.p, sizeof(double) * (size_t)n));
   FBCHK(d2h(e, rank.data(), e->wb_rank.p, sizeof(int) * (size_t)T));
@@ -3683,6 +3749,45 @@ extern "C" int fb_debug_frontend_vjp(fb_engine *e, const int16_t *wav, int64_t n
   HIPCHK(hipGetLastError());
   FBCHK(wb_status_check(e, status));
   if (voiced) for (int t = 0; t < T; ++t) voiced[t] = rank[t] >= 0 ? 1 : 0;
+  return FB_OK;
+}
+
+extern "C" int fb_debug_wb_route(fb_engine *e, int *info) {
+  if (!e || !info) return fb_fail(FB_E_ARG, "null argument");
+  for (int i = 0; i < FB_WB_ROUTE_N; ++i) info[i] = e->wb_route[i];
+  return FB_OK;
+}
+
+// Test hook: the defences alone -- the forward of the chain and the codec on ONE row for the engine's r replicas at the given
+// point, as an attack iteration's scoring call runs it, then wb_enqueue's transposes on a cotangent per replica
+extern "C" int fb_debug_defence_vjp(fb_engine *e, const int16_t *wav, int64_t n, uint64_t seed, uint32_t stream, int iter,
+                                    const double *cot, double *dwav, int16_t *out) {
+  if (!e || !wav || !cot || !dwav || n <= 0 || iter < 0) return fb_fail(FB_E_ARG, "bad argument");
+  if (n > 0x7fffffffLL) return fb_fail(FB_E_LIMIT, "utterance longer than 2^31 samples");
+  if (e->air.L > 0) return fb_fail(FB_E_STATE, "white-box gradients: an air channel is set (fb_set_air_channel: clear it)");
+  if (e->comp_K1 > 0) return fb_fail(FB_E_STATE, "white-box gradients: companions are set (fb_set_companions: clear them)");
+  if (num_frames(e->cfg, n) <= 0) return fb_fail(FB_E_ARG, "audio shorter than one frame");
+  HIPCHK(hipSetDevice(e->device));
+  e->bench_it = -1;
+  memset(e->wb_route, 0, sizeof(e->wb_route));
+  const int r = e->eot;
+  FBCHK(prepare_nes_replicas(e, n, 1));
+  FBCHK(e->wb_gj.ensure(sizeof(double) * (size_t)n));
+  FBCHK(e->grad.ensure(sizeof(double) * (size_t)n));
+  FBCHK(h2d(e, e->wav.p, wav, sizeof(int16_t) * (size_t)n));
+  const FbRngPoint pt{seed, stream, (uint32_t)iter, 0};
+  FbScoreCall call{pt};
+  call.eot = r;
+  const int16_t *res = nullptr;
+  FBCHK(transformed_wav(e, call, e->h_wav_off.data(), r, &res));
+  if (out) FBCHK(d2h(e, out, res, sizeof(int16_t) * (size_t)n * r));
+  for (int j = 0; j < r; ++j) {
+    FBCHK(h2d(e, e->wb_gj.p, cot + (size_t)j * n, sizeof(double) * (size_t)n));
+    FBCHK(wb_launch_chain_t(e, pt, j, n, e->wb_gj.as<double>(), e->grad.as<double>(), false, nullptr));
+    FBCHK(d2h(e, dwav + (size_t)j * n, e->grad.p, sizeof(double) * (size_t)n));
+    FBCHK(sync_stream(e));
+  }
+  HIPCHK(hipGetLastError());
   return FB_OK;
 }
 

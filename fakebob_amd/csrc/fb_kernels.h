@@ -302,7 +302,7 @@ void fb_launch_wb_ctl(hipStream_t s, const double *scores, const FbNesDev *out, 
 // are skipped, all zero gives exact zeros
 void fb_launch_wb_gmm_backward(hipStream_t s, int M, int C, int D, const float *gc, const float *miv, const float *iv,
                                const float *feats, const int *n_rows_ptr, int rows_cap, const double *w, float *part, double *g,
-                               const int *stop);
+                               const int *stop, const int *row_base_ptr = nullptr);
 // grad[n] = scale * d <cot, feats(wav)> / d wav for ONE utterance of n samples / T frames whose MFCC matrix the forward left in
 // mfcc; cot [Tv][dim] on the compacted rows.  rank [T] (out: the voiced row of a frame or -1), dcm / ddf [T][dim], dmf [T][nc],
 // dxf [T][L]: float64 workspace.  tv_fwd (nullable): the forward's voiced count; *status = 1 if the mask recomputed here counts
@@ -313,6 +313,20 @@ void fb_launch_wb_frontend_vjp(hipStream_t s, const FbFrontendDev &fe, const int
 // FAKEBOB.py:193-203 on the gradient vector g with the step size of ctl
 void fb_launch_wb_update(hipStream_t s, const double *g, int64_t N, double momentum, double one_minus_m, double epsilon,
                          const double *audio, double *grad_m, double *adver, const FbCtlDev *ctl);
+
+// ---- white-box gradients through a defended victim (fb_set_wb_bpda; whitebox_bpda_kernels.hip) ----------------------
+#define FB_WBT_TILE 2048      // samples of dx of one k_wb_chain_t workgroup
+// replica j's weights w = w_j / r from its own scores rep_scores[S]; with do_ctl the loop control of k_wb_ctl on `out` and
+// mean_scores[S] (the EOT means k_loss_eot left) as well
+void fb_launch_wb_ctl_rep(hipStream_t s, const double *rep_scores, const double *mean_scores, const FbNesDev *out, int M, int r,
+                          int task, int attack_type, const double *z_std, double threshold, int target, int true_label, double *w,
+                          FbCtlDev *ctl, int do_ctl, double *trace, int it);
+// grad[n] (accumulate: += , else =) the vector-Jacobian product of cot[n], a cotangent on the chain's output, through the chain
+// ch applied to wav[n] as replica `replica` of utterance 0 at rn's point of the noise contract (rn.power: k_tf_power's sum for
+// SNR stages).  ch.n == 0 copies / adds.  false: the LDS opt-in failed (nothing was launched)
+size_t fb_wb_chain_t_lds_bytes(const FbTfChain &ch);
+bool fb_launch_wb_chain_t(hipStream_t s, const FbTfChain &ch, const double *taps, const int16_t *wav, int64_t n, const FbTfRnd &rn,
+                          int replica, const double *cot, double *grad, int accumulate, const int *stop);
 
 // ---- front-end ------------------------------------------------------------
 // MFCC of every frame of a (ragged) batch.  wav_off[B+1], frame_off[B+1] device arrays.

@@ -17,6 +17,7 @@
 
 #include "fb_device.h"
 #include "fb_kernels.h"
+#include "whitebox_device.h"
 
 typedef float wb_f32x4 __attribute__((ext_vector_type(4)));
 
@@ -29,69 +30,8 @@ __global__ __launch_bounds__(64) void k_wb_ctl(const double *__restrict__ scores
                                                double *__restrict__ trace, int it) {
   if (threadIdx.x != 0) return;
   if (ctl && ctl->stop) return;
-  const int S = task == FB_TASK_CSI ? M : M - 1;
-  for (int m = 0; m < M; ++m) w[m] = 0.0;
-  auto first_max_but = [&](int skip) -> int {
-    int idx = -1;
-    double om = -INFINITY;
-    for (int m = 0; m < S; ++m)
-      if (m != skip && scores[m] > om) { om = scores[m]; idx = m; }
-    return idx;
-  };
-  if (task == FB_TASK_SV) {                                     // (thr + kappa) - s[0]
-    w[1] = -1.0; w[0] = 1.0;
-  } else if (task == FB_TASK_OSI && attack_type == FB_UNTARGETED) {   // (thr + kappa) - max s
-    const int j = first_max_but(-1);
-    if (j >= 0) { w[1 + j] = -1.0; w[0] = 1.0; }
-  } else if (task == FB_TASK_OSI) {                             // (max(max_{j != t} s[j], thr) + kappa) - s[t]
-    const int j = first_max_but(target);
-    double ubm = 1.0;
-    w[1 + target] = -1.0;
-    if (j >= 0 && scores[j] > threshold) { w[1 + j] = 1.0; ubm = 0.0; }
-    w[0] = ubm;
-  } else if (attack_type == FB_TARGETED) {                      // (max_{j != t} s[j] + kappa) - s[t]
-    const int j = first_max_but(target);
-    w[target] = -1.0 / z_std[target];
-    if (j >= 0) w[j] = 1.0 / z_std[j];
-  } else {                                                      // (s[true] + kappa) - max_{j != true} s[j]
-    const int j = first_max_but(true_label);
-    w[true_label] = 1.0 / z_std[true_label];
-    if (j >= 0) w[j] = -1.0 / z_std[j];
-  }
-  if (!ctl) return;
-  // FakeBob.attack's loop control (FAKEBOB.py:181, :195-200) with adver_loss in the plateau window: there is no noisy mean
-  if (out->err) { ctl->err = out->err; ctl->stop = 1; return; }
-  const double al = out->adver_loss;
-  double lr = ctl->lr;
-  if (al < 0.0 && !ctl->disable_stop) {
-    ctl->stop = 1; ctl->broke = 1; ctl->stop_iter = it;
-  } else if (ctl->plateau_length > 0) {
-    const int PL = ctl->plateau_length;
-    int n = ctl->n_ls;
-    double *ls = ctl->ls;
-    if (n < PL) {
-      ls[n++] = al;
-    } else {
-      for (int i = 1; i < PL; ++i) ls[i - 1] = ls[i];
-      ls[PL - 1] = al;
-    }
-    if (n == PL && ls[PL - 1] > ls[0]) {
-      if (lr > ctl->min_lr) {
-        const double l2 = lr / ctl->plateau_drop;
-        lr = l2 > ctl->min_lr ? l2 : ctl->min_lr;
-        ctl->lr = lr;
-      }
-      n = 0;
-    }
-    ctl->n_ls = n;
-  }
-  if (trace) {
-    double *row = trace + (size_t)it * (3 + S);
-    row[0] = out->distance; row[1] = al; row[2] = lr;
-    for (int m = 0; m < S; ++m) row[3 + m] = scores[m];
-  }
-  if (ctl->ticks) ctl->ticks[it + 1] = wall_clock64();
-  ctl->iters_done = it + 1;
+  fb_wb_weights(scores, M, task, attack_type, z_std, threshold, target, true_label, w);
+  if (ctl) fb_wb_loop_control(scores, out, M, task, ctl, trace, it);
 }
 
 void fb_launch_wb_ctl(hipStream_t s, const double *scores, const FbNesDev *out, int M, int task, int attack_type,
@@ -103,7 +43,8 @@ void fb_launch_wb_ctl(hipStream_t s, const double *scores, const FbNesDev *out, 
 
 // ------------------------------------------------------------------------------------------------ GMM backward
 // part[m][t][d] = sum_c gamma_mtc (miv_mc[d] - iv_mc[d] x_t[d]) for the voiced rows x_t of `feats` and every model with
-// w[m] != 0 (the others return at once).  A workgroup takes 16 rows of one model; its four waves take the 16-component tiles
+// w[m] != 0 (the others return at once); row_base_ptr (nullable): the first of them, a row index into `feats`.  A workgroup
+// takes 16 rows of one model; its four waves take the 16-component tiles
 // c, c + 4, ... and merge their online soft-max states through LDS in wave order.  Everything is the transposed problem, so
 // that no value changes lanes between the two products:
 //   S^T [comp][row] = P [comp][k] E [k][row],  k over {x (D, padded to quads), -x^2 / 2 (likewise), 1}   v_mfma_f32_16x16x4_f32
@@ -117,12 +58,14 @@ void fb_launch_wb_ctl(hipStream_t s, const double *scores, const FbNesDev *out, 
 
 __global__ __launch_bounds__(256) void k_wb_gmm_bwd(int C, int D, const float *__restrict__ gc, const float *__restrict__ miv,
                                                     const float *__restrict__ iv, const float *__restrict__ feats,
-                                                    const int *__restrict__ n_rows_ptr, int rows_cap, const double *__restrict__ w,
+                                                    const int *__restrict__ n_rows_ptr, const int *__restrict__ row_base_ptr,
+                                                    int rows_cap, const double *__restrict__ w,
                                                     float *__restrict__ part, const int *__restrict__ stop) {
   if (stop && *stop) return;
   const int m = blockIdx.y;
   if (w[m] == 0.0) return;
   const int n_rows = min(*n_rows_ptr, rows_cap);
+  if (row_base_ptr) feats += (size_t)*row_base_ptr * D;   // (a replica's rows within the batch's compacted rows)
   const int f0 = blockIdx.x * FB_WB_ROWS;
   if (f0 >= n_rows) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -254,9 +197,9 @@ __global__ __launch_bounds__(256) void k_wb_sum_models(int M, int D, const int *
 
 void fb_launch_wb_gmm_backward(hipStream_t s, int M, int C, int D, const float *gc, const float *miv, const float *iv,
                                const float *feats, const int *n_rows_ptr, int rows_cap, const double *w, float *part, double *g,
-                               const int *stop) {
+                               const int *stop, const int *row_base_ptr) {
   hipLaunchKernelGGL(k_wb_gmm_bwd, dim3((unsigned)((rows_cap + FB_WB_ROWS - 1) / FB_WB_ROWS), (unsigned)M), dim3(256), 0, s, C, D, gc,
-                     miv, iv, feats, n_rows_ptr, rows_cap, w, part, stop);
+                     miv, iv, feats, n_rows_ptr, row_base_ptr, rows_cap, w, part, stop);
   hipLaunchKernelGGL(k_wb_sum_models, dim3((unsigned)(((size_t)rows_cap * D + 255) / 256)), dim3(256), 0, s, M, D, n_rows_ptr, rows_cap,
                      w, part, g, stop);
 }

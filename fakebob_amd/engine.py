@@ -57,6 +57,7 @@ class Engine(object):
         self.air_channel = None
         self.codec = None
         self.eot = 1
+        self.wb_bpda = False
         self.companions = None
         self.feature_compression = None
 
@@ -518,18 +519,30 @@ class Engine(object):
         return adv, flag.value, adv_f, trace[:nt.value]
 
     # ---- white-box gradients (GMM-UBM systems on an undefended victim)
+    def set_wb_bpda(self, on):
+        """fb_set_wb_bpda: with True, get_grad_wb and attack_wb differentiate through an input-transform chain, a codec and
+        the replicas of set_eot -- BPDA through the non-differentiable stages, EOT over the random ones (the derivative rules
+        are in include/fakebob_hip.h).  False (as created): every defence is refused and nothing else changes."""
+        N.check(self._L.fb_set_wb_bpda(self._h, C.c_int(1 if on else 0)))
+        self.wb_bpda = bool(on)
+
     def get_grad_wb(self, params, audio, want_grad=True):
-        """fb_get_grad_wb: the analytic gradient of the loss at `audio` -> (grad (N,) float64 = d loss / d audio, in the
+        """fb_get_grad_wb: get_grad_wb_iter at iter = 0."""
+        return self.get_grad_wb_iter(params, audio, 0, want_grad)
+
+    def get_grad_wb_iter(self, params, audio, iter=0, want_grad=True):
+        """fb_get_grad_wb_iter: the analytic gradient of the loss at `audio` -> (grad (N,) float64 = d loss / d audio, in the
         units of get_grad's estimate; adver_loss; score0 (S,)).  adver_loss and score0 are get_grad's own: the same forward.
-        samples_per_draw, sigma, seed and stream are not read.  Refused (NativeError, FB_E_STATE) for i-vector systems
-        and while an input transform, air channel, codec, feature compression, dither, EOT or companions are set."""
+        samples_per_draw and sigma are not read; seed, stream and `iter` (the epoch of the draws, as get_grad's `it`) key the
+        random stages of a defended victim.  Refused (NativeError, FB_E_STATE) for i-vector systems and while an air channel,
+        feature compression, dither or companions are set; an input transform, a codec and EOT only after set_wb_bpda(True)."""
         audio = np.ascontiguousarray(audio, np.float64).reshape(-1)
         n = audio.size
         grad = np.empty(n, np.float64) if want_grad else None
         al = C.c_double()
         sc = np.empty(max(self.n_speakers, 1), np.float64)
-        N.check(self._L.fb_get_grad_wb(self._h, C.byref(params), N.ptr(audio), C.c_int64(n), C.byref(al),
-                                       None if grad is None else N.ptr(grad), N.ptr(sc)))
+        N.check(self._L.fb_get_grad_wb_iter(self._h, C.byref(params), N.ptr(audio), C.c_int64(n), C.c_int(int(iter)), C.byref(al),
+                                            None if grad is None else N.ptr(grad), N.ptr(sc)))
         return grad, al.value, sc
 
     def attack_wb(self, params, audio):
@@ -544,6 +557,25 @@ class Engine(object):
         N.check(self._L.fb_attack_wb(self._h, C.byref(params), N.ptr(audio), C.c_int64(n), N.ptr(adv), N.ptr(adv_f),
                                      N.ptr(trace), C.byref(nt), C.byref(flag)))
         return adv, flag.value, adv_f, trace[:nt.value]
+
+    def debug_defence_vjp(self, wav, cot, seed=0, stream=0, iter=0):
+        """The defences' transposes alone (fb_debug_defence_vjp): wav (n,) int16, cot (r, n) float64 on the rows the front
+        end would read, r = the engine's EOT size -> (dwav (r, n) float64, out (r, n) int16 = those rows)."""
+        wav = np.ascontiguousarray(wav, np.int16).reshape(-1)
+        r = int(getattr(self, "eot", 1))
+        cot = np.ascontiguousarray(cot, np.float64).reshape(r, wav.size)
+        dwav = np.empty((r, wav.size), np.float64)
+        out = np.empty((r, wav.size), np.int16)
+        N.check(self._L.fb_debug_defence_vjp(self._h, N.ptr(wav), C.c_int64(wav.size), C.c_uint64(int(seed)), C.c_uint32(int(stream)),
+                                             C.c_int(int(iter)), N.ptr(cot), N.ptr(dwav), N.ptr(out)))
+        return dwav, out
+
+    def debug_wb_route(self):
+        """Launches of the white-box backward the last get_grad_wb / attack_wb / debug_defence_vjp call enqueued
+        (fb_debug_wb_route): a dict ctl, ctl_rep, backward, chain_t."""
+        info = (C.c_int * 4)()
+        N.check(self._L.fb_debug_wb_route(self._h, info))
+        return dict(zip(("ctl", "ctl_rep", "backward", "chain_t"), [int(v) for v in info]))
 
     def debug_gmm_feat_grad(self, feats, w):
         """The GMM backward alone (fb_debug_gmm_feat_grad): feats (Tv, D) float32 handed in as they are, w (M,) the

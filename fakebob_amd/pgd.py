@@ -4,9 +4,11 @@ GMM-UBM systems, behind FakeBob's interface.
 The loop is FakeBob.attack's (FAKEBOB.py:139-221) with the analytic gradient of the loss in place of the NES estimate
 (fb_attack_wb): momentum sign steps inside the epsilon ball, the plateau learning-rate rule on the clean loss, the early
 stop on adver_loss < 0.  momentum = 0 is plain PGD with the margin loss; max_iter = 1 is the single-step attack.  There
-is no random start, so a run is reproducible.  The victim has to be undefended: input transforms, the air channel, codecs,
-feature compression, dither, EOT and companions are refused (no BPDA in this version), as are i-vector systems and
-foreign models -- the gradient is that of this library's own forward.
+is no random start, so a run is reproducible.  PGD's victim has to be undefended.  AdaptivePGD is the adaptive attack on a
+defended one (Engine.set_wb_bpda): BPDA through the model's input-transform chain and codec, and with eot_size = r > 1 an
+expectation over r draws of its random stages per iteration, keyed by the attack's seed and stream.  The air channel,
+feature compression, dither and companions stay refused, as are i-vector systems and foreign models -- the gradient is
+that of this library's own forward.
 """
 import pickle
 import time
@@ -29,6 +31,8 @@ class PGD(object):
             raise ValueError("model implements task %s, attack asked for %s" % (model.task, task))
         if getattr(model.engine, "kind", "gmm") != "gmm":
             raise ValueError("PGD: i-vector systems are out of this version (GMM-UBM systems only)")
+        self.bpda = False   # (AdaptivePGD: True -- the engine's switch is on and seed / stream key the victim's draws)
+        self.eot_size = 1
         self.task = task
         self.attack_type = attack_type
         self.model = model
@@ -44,7 +48,8 @@ class PGD(object):
         self.true = None
         self.target = None
         self.verbose = verbose
-        # the attack itself draws nothing; the seed keys the threshold sweep, which is FakeBob's (estimate_threshold)
+        # an undefended attack draws nothing; the seed keys the threshold sweep, which is FakeBob's (estimate_threshold), and
+        # in AdaptivePGD the draws of the victim's random stages
         self.seed = int(np.random.randint(0, 2 ** 31 - 1)) if seed is None else int(seed)
         self._stream = 0
 
@@ -55,7 +60,16 @@ class PGD(object):
         fb = FakeBob(self.task, self.attack_type, self.model, adver_thresh=self.adver_thresh, epsilon=self.epsilon,
                      seed=self.seed, verbose=self.verbose)
         fb._stream = self._stream
-        res = fb.estimate_threshold(audio, fs=fs, bits_per_sample=bits_per_sample, n_jobs=n_jobs, debug=debug, **kw)
+        # (the sweep does not run under EOT: with bpda and eot_size > 1 it scores single draws, and the size is put back)
+        eng = self.model.engine
+        r = self.eot_size if self.bpda else 1
+        if r > 1:
+            eng.set_eot(1)
+        try:
+            res = fb.estimate_threshold(audio, fs=fs, bits_per_sample=bits_per_sample, n_jobs=n_jobs, debug=debug, **kw)
+        finally:
+            if r > 1:
+                eng.set_eot(r)
         self._stream = fb._stream
         if res is not None:
             self.threshold = fb.threshold
@@ -65,8 +79,8 @@ class PGD(object):
         return nes_params(self.task, self.attack_type, adver_thresh=self.adver_thresh, epsilon=self.epsilon,
                           max_iter=self.max_iter, max_lr=self.max_lr, min_lr=self.min_lr, samples_per_draw=0, sigma=0.0,
                           momentum=self.momentum, plateau_length=self.plateau_length, plateau_drop=self.plateau_drop,
-                          threshold=self.threshold, target=self.target, true=self.true, seed=0, stream=0,
-                          bits_per_sample=bits_per_sample)
+                          threshold=self.threshold, target=self.target, true=self.true, seed=self.seed if self.bpda else 0,
+                          stream=self._stream if self.bpda else 0, bits_per_sample=bits_per_sample)
 
     def get_grad(self, audio, fs=16000, bits_per_sample=16, n_jobs=10, debug=False):
         """-> (grad (N,1) = d loss / d audio, adver_loss (1,), score), the analytic twin of FakeBob.get_grad's last three."""
@@ -102,3 +116,25 @@ class PGD(object):
             print("--- %d iters, distance:%f, loss:%f, %.1f iters/s ---" %
                   (n, trace[-1, 0], trace[-1, 1], n / dt if dt > 0 else 0.0))
         return adv[:, np.newaxis], flag
+
+
+class AdaptivePGD(PGD):
+    """PGD on a DEFENDED victim: the adaptive white-box attack of SpeakerGuard's evaluation matrix.  bpda=True switches the
+    engine to differentiate through the model's input-transform chain and codec (Engine.set_wb_bpda; the derivative rules are
+    in include/fakebob_hip.h), eot_size = r takes the mean loss and gradient over r draws of the random stages per iteration
+    (Engine.set_eot).  Everything else -- knobs, attack(), get_grad(), return pair, checkpoint layout -- is PGD's.  The
+    constructor sets both on the model's engine and they stay set; bpda=False with eot_size=1 is PGD itself."""
+
+    def __init__(self, task, attack_type, model, bpda=True, eot_size=1, **kw):
+        eot_size = int(eot_size)
+        if not 1 <= eot_size <= 32:
+            raise ValueError("AdaptivePGD: eot_size %d outside 1 .. 32" % eot_size)
+        if eot_size > 1 and not bpda:
+            raise ValueError("AdaptivePGD: eot_size %d needs bpda=True (expectation over transformation is part of the "
+                             "adaptive attack)" % eot_size)
+        PGD.__init__(self, task, attack_type, model, **kw)
+        self.bpda = bool(bpda)
+        self.eot_size = eot_size
+        if self.bpda:  # (left alone otherwise: the engine's own refusals then name what is set)
+            model.engine.set_eot(eot_size)
+            model.engine.set_wb_bpda(True)

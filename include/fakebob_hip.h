@@ -35,6 +35,8 @@
  *   fb_get_grad_wb / fb_attack_wb     FakeBob.get_grad + loss_fn (FAKEBOB.py:223-299) and FakeBob.attack (:139-221) with the
  *                             ANALYTIC gradient of the loss in place of the NES estimate: the white-box attacks of
  *                             SpeakerGuard's evaluation (FGSM, PGD, the margin-loss CW-inf) on a GMM-UBM system
+ *   fb_set_wb_bpda / fb_get_grad_wb_iter   (none in FAKEBOB: the adaptive form of those attacks on a DEFENDED victim -- BPDA
+ *                             through the input-transform chain and the codec, EOT over the random stages)
  *   fb_get_grad_ext / fb_attack_ext   the same around a foreign `model` (README.md:136)
  *   fb_get_grad_dev / fb_attack_dev   ... around a foreign model that runs on the
  *                             same GPU: the batch and the scores stay on the device
@@ -504,8 +506,9 @@ int fb_attack_kenansville(fb_engine *e, const fb_nes_params *p, const fb_kv_para
 /* ---- white-box gradients: backpropagation through the GMM-UBM victim ------------------------------------------------------
  * fb_get_grad estimates the gradient of the loss from scores (NES); the victim lives in the engine, so the gradient itself
  * can be computed.  fb_get_grad_wb returns it, fb_attack_wb runs FakeBob.attack's loop on it.  Scope of this version: GMM-UBM
- * systems (OSI, CSI, SV) on an UNDEFENDED victim; everything else is refused, not ignored ("Refusals").  BPDA through the
- * defences, expectation over transformation and the i-vector back end are out of this version.
+ * systems (OSI, CSI, SV) on an UNDEFENDED victim; everything else is refused, not ignored ("Refusals").  With
+ * fb_set_wb_bpda(e, 1) the same calls differentiate THROUGH an input-transform chain, a codec and the replicas of fb_set_eot
+ * ("Defended victims: BPDA and EOT", below).  The air channel's transpose and the i-vector back end are out of this version.
  * The function that is differentiated.  Input: float audio a in [-1, 1].  The forward is the engine's ordinary one, as
  * configured: the int16 cast with 2^(bits_per_sample - 1); MFCC, VAD, add-deltas, sliding CMVN, the voiced rows; per-model mean
  * frame log-likelihood; fb_system_scores; the reference's loss_fn (FAKEBOB.py:248-299).  adver_loss and score0 are exactly
@@ -535,14 +538,55 @@ int fb_attack_kenansville(fb_engine *e, const fb_nes_params *p, const fb_kv_para
  * adver_loss < 0 before the step, the plateau rule, the trace rows {distance, adver_loss, lr_after, score0[S]}, the
  * iter < max_iter - 1 flag, the final cast, the step (FAKEBOB.py:193-203: grad_m = momentum grad_m + (1 - momentum) g;
  * adver -= lr sign(grad_m); the clips to the epsilon ball and to [-1, 1], float64 as in fb_attack).  One row is scored per
- * iteration; the plateau window holds adver_loss (there is no noisy mean); samples_per_draw, sigma, seed and stream are not
- * read.  momentum = 0 is plain PGD with the margin loss (SpeakerGuard's CW-inf / PGD), max_iter = 1 the single-step case;
+ * iteration; the plateau window holds adver_loss (there is no noisy mean); samples_per_draw and sigma are not read; seed
+ * and stream are not read on an undefended victim and ARE read once a random stage is set (below).  momentum = 0 is plain PGD with the margin loss (SpeakerGuard's CW-inf / PGD), max_iter = 1 the single-step case;
  * there is no random start, so a result is reproducible.  The loop control runs on the device and the host looks at it once
  * per FB_ATTACK_BATCH iterations (default 4), as in fb_attack; fb_attack_iter_seconds and fb_stats work as for fb_attack.
  * Refusals, each with a message naming the cause.  FB_E_STATE: no model, an i-vector system is loaded, fb_set_eot(r > 1) is
  * in force, companions are set, an input-transform chain, an air channel or a codec is set, feature compression is on,
  * dither > 0.  FB_E_ARG: audio shorter than one frame, max_iter < 1 (fb_attack_wb), the task, target, true-label and
- * bits_per_sample rules of fb_attack_pso.  FB_E_NO_VOICED: a row without voiced frames, as in fb_attack. */
+ * bits_per_sample rules of fb_attack_pso.  FB_E_NO_VOICED: a row without voiced frames, as in fb_attack.
+ *
+ * Defended victims: BPDA and EOT (fb_set_wb_bpda).  A defence judged only by score-based attacks is the textbook case of
+ * obfuscated gradients; the adaptive white-box attack is PGD with BPDA (a differentiable surrogate in the backward pass)
+ * through the non-differentiable stages and an expectation over the random ones.  It is an approximation the attacker
+ * chooses, hence a switch: fb_set_wb_bpda(e, on), on = 0 or 1 (anything else: FB_E_ARG, the setting stays), 0 at engine
+ * creation.  With 0 no call queues another launch or returns another value than before the switch existed, and every refusal
+ * above stands.  With 1, fb_get_grad_wb, fb_get_grad_wb_iter and fb_attack_wb accept an input-transform chain (all five stage
+ * kinds), a codec, fb_set_eot(r), 1 <= r <= 32, and any combination; with nothing of these set they queue exactly the
+ * launches of the undefended call.  Still FB_E_STATE with the switch on, the cause named: an i-vector system, companions,
+ * feature compression, dither > 0 -- and an AIR CHANNEL: the transpose of the drawn room response is not in this version.
+ * fb_get_grad_wb_iter is fb_get_grad_wb with the epoch of the random draws given: `iter` (>= 0) means what fb_get_grad's
+ * iter means in the noise RNG contract; fb_get_grad_wb is iter = 0; fb_attack_wb draws with its loop index, as fb_attack
+ * does.  p->seed and p->stream key the draws.
+ * Forward.  The engine's ordinary forward for a batch of one row under the defences set: cast, chain, codec, front end, GMM,
+ * fb_system_scores and loss_fn per replica, then the EOT mean in fb_set_eot's float64 order.  adver_loss and score0 are bit
+ * for bit what fb_get_grad returns at samples_per_draw = 0 with the same iter, seed, stream and settings -- the same launches
+ * -- so fb_attack_wb's stop test reads the mean over the replicas, as fb_attack's does.
+ * Backward.  The gradient of a real-valued surrogate at the point the forward reached, replica by replica:
+ *     grad = sum_j grad_j, j ascending, float64, grad_j computed with the weights w_j[M] / r of replica j's OWN scores (its
+ *     first-maximum index may differ from another replica's): k_wb_gmm_bwd on replica j's voiced rows, the front-end
+ *     backward on replica j's TRANSFORMED int16 row and MFCC matrix, then the transposes of the defence stages.
+ * Every stage's VALUES are the forward's own (recomputed: the forward keeps no intermediates); its derivative is
+ *   rounding (rint, floor_div)   the identity
+ *   saturation                   a sample whose value after rounding, before the clip, lies outside [-32768, 32767] passes zero,
+ *                                in any stage -- the rule "an active floor contributes zero"
+ *   FB_TF_QUANT                  the identity (straight-through), except under saturation
+ *   FB_TF_MEDIAN                 the exact subgradient: the cotangent of y[i] goes to the ONE window position the median
+ *                                selected -- the 2r + 1 window entries, zero padding outside [0, n) included, ordered by
+ *                                (value, position), both ascending; the entry of rank r.  A selected padding position absorbs it.
+ *   FB_TF_FIR                    the transpose: dx[m] = sum_j taps[j] * dy[m - c + j] over the j whose index lies in [0, n),
+ *                                j ascending, float64 (one rounding per product and per sum), dy zeroed where saturated
+ *   FB_TF_DECIMATE               passes dy[i] where i mod q = 0, zero elsewhere
+ *   FB_TF_NOISE                  the identity, except under saturation; the scale s of an SNR stage is held constant, as the
+ *                                voiced mask is; the normals are redrawn by the forward's rule for (stage, replica j)
+ *   codec (ulaw, alaw, adpcm)    the identity: BPDA in the strict sense.  A segment-slope derivative for G.711 is not in
+ *                                this version.
+ * No floating-point atomics and a fixed order in every sum: the same call on a fresh engine gives the same bits.  The
+ * 2^(bits_per_sample - 1) scale and the units of grad are unchanged. */
+int fb_set_wb_bpda(fb_engine *e, int on);
+int fb_get_grad_wb_iter(fb_engine *e, const fb_nes_params *p, const double *audio, int64_t N, int iter, double *adver_loss,
+                        double *grad /*[N], nullable*/, double *score0 /*[S]*/);
 int fb_get_grad_wb(fb_engine *e, const fb_nes_params *p, const double *audio, int64_t N, double *adver_loss,
                    double *grad /*[N], nullable*/, double *score0 /*[S]*/);
 int fb_attack_wb(fb_engine *e, const fb_nes_params *p, const double *audio, int64_t N, int16_t *adv_i16, double *adver_f64,

@@ -311,6 +311,25 @@ int fb_bench_nes_state(fb_engine *e, double *adver, double *scores, double *loss
 int fb_debug_gmm_feat_grad(fb_engine *e, const float *feats, int Tv, const double *w, double *out);
 int fb_debug_frontend_vjp(fb_engine *e, const int16_t *wav, int64_t n, const double *cot, double *dwav, unsigned char *voiced);
 
+/* White-box gradients through a defended victim (fakebob_hip.h: fb_set_wb_bpda).
+ * fb_debug_defence_vjp: the defences alone.  The forward of the defences currently set -- input-transform chain, codec -- on
+ * the ONE row wav[n] for the engine's r = fb_set_eot replicas at (seed, stream, epoch = iter) of the noise RNG contract, as the
+ * scoring call of a white-box iteration runs it; then the transposes alone: dwav[j][n] = the vector-Jacobian product of the
+ * cotangent cot[j][n] (on the row the front end would read) through codec and chain of replica j, by the derivative rules of the
+ * contract; out[j][n] (nullable) = the transformed row the front end would read.  It runs exactly the launches an attack
+ * iteration runs for this stage (an empty chain copies).  The switch need not be on.  FB_E_STATE with an air channel or
+ * companions set.
+ * fb_debug_wb_route: info[FB_WB_ROUTE_N] counts the launches of the white-box backward the last fb_get_grad_wb* /
+ * fb_attack_wb / fb_debug_defence_vjp call enqueued, recorded on the host as fb_debug_nes_route's are. */
+#define FB_WB_ROUTE_CTL 0        /* k_wb_ctl: weights from the scores of the one row (+ loop control) */
+#define FB_WB_ROUTE_CTL_REP 1    /* k_wb_ctl_rep: weights of one replica of r > 1 (replica 0: + loop control) */
+#define FB_WB_ROUTE_BACKWARD 2   /* GMM backward + front-end backward of one replica (seven launches) */
+#define FB_WB_ROUTE_CHAIN_T 3    /* k_wb_chain_t: the chain's transpose of one replica, adding it to the gradient */
+#define FB_WB_ROUTE_N 4
+int fb_debug_defence_vjp(fb_engine *e, const int16_t *wav, int64_t n, uint64_t seed, uint32_t stream, int iter,
+                         const double *cot /*[r][n]*/, double *dwav /*[r][n]*/, int16_t *out /*[r][n], nullable*/);
+int fb_debug_wb_route(fb_engine *e, int *info);
+
 #ifdef __cplusplus
 }
 #endif
