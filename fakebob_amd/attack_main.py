@@ -206,6 +206,9 @@ def main(argv=None, model_factory=None, bob_factory=None):
                     help="--attack pgd: the adaptive attack on a defended victim -- BPDA through --input-transform and --codec, "
                          "expectation over --eot-size draws of the random stages; --air-channel, --feco, --dither and "
                          "--companions stay refused")
+    ap.add_argument("--wb-ivector", dest="wb_ivector", action="store_true",
+                    help="--attack pgd -archi iv: differentiate the i-vector-PLDA victim (fakebob_amd/pgd.py: IvectorPGD; the "
+                         "frames' component selection and pruned sets held constant); never under --eot-size > 1")
     ap.add_argument("--kv-window", dest="kv_window", default=100, type=int, help="--attack kenansville: samples per window (8 .. 128)")
     ap.add_argument("--kv-grid", dest="kv_grid", default=15, type=int, help="--attack kenansville: candidates per round (1 .. 64)")
     ap.add_argument("--kv-max-factor", dest="kv_max_factor", default=1.0, type=float,
@@ -237,8 +240,13 @@ def main(argv=None, model_factory=None, bob_factory=None):
 
     if args.bpda and args.attack != "pgd":
         ap.error("--bpda belongs to --attack pgd (--attack %s)" % args.attack)
+    if args.wb_ivector and args.attack != "pgd":
+        ap.error("--wb-ivector belongs to --attack pgd (--attack %s)" % args.attack)
     if args.attack == "pgd":      # likewise: the gradient is that of a GMM-UBM victim, undefended unless --bpda is given
-        if args.architecture != "gmm":
+        if args.architecture == "iv" and args.wb_ivector and args.eot_size is not None and args.eot_size > 1:
+            ap.error("--attack pgd --wb-ivector does not run under expectation over transformation (--eot-size %d: an i-vector "
+                     "system keeps one row's state)" % args.eot_size)
+        if args.architecture != "gmm" and not args.wb_ivector:
             ap.error("--attack pgd differentiates GMM-UBM systems only (--architecture %s)" % args.architecture)
         if not args.bpda and args.eot_size is not None and args.eot_size > 1:
             ap.error("--attack pgd does not run under expectation over transformation (--eot-size %d)" % args.eot_size)
@@ -297,7 +305,12 @@ def main(argv=None, model_factory=None, bob_factory=None):
                   min_lr=args.min_lr, momentum=args.momentum, plateau_length=args.plateau_length, plateau_drop=args.plateau_drop)
         if args.bpda:  # (absent otherwise: a bob_factory of the driver-rule tests sees the keywords it always saw)
             hp.update(bpda=True, eot_size=args.eot_size if args.eot_size is not None else 1)
-    if bob_factory is None and args.attack == "pgd":
+        if args.wb_ivector:  # IvectorPGD has no eot_size
+            hp.pop("eot_size", None)
+    if bob_factory is None and args.attack == "pgd" and args.wb_ivector:
+        from .pgd import IvectorPGD
+        bobs = [IvectorPGD(task, attack_type, m, seed=seed, verbose=False, **hp) for m in models]
+    elif bob_factory is None and args.attack == "pgd":
         from .pgd import PGD, AdaptivePGD
         bobs = [(AdaptivePGD if args.bpda else PGD)(task, attack_type, m, seed=seed, verbose=False, **hp) for m in models]
     elif bob_factory is None and args.attack == "kenansville":

@@ -48,7 +48,7 @@ static int fb_fail(int code, const char *fmt, ...) {
   } while (0)
 
 extern "C" const char *fb_last_error(void) { return g_err.c_str(); }
-extern "C" int fb_version(void) { return 101; }
+extern "C" int fb_version(void) { return 102; }
 extern "C" int fb_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -222,6 +222,11 @@ struct fb_engine {
   bool wb_uploaded = false;
   DevBuf wb_gc, wb_miv, wb_iv, wb_w, wb_part, wb_g, wb_rank, wb_dcm, wb_ddf, wb_dmf, wb_dxf, wb_status;
   // white-box gradients through a defended victim (fb_set_wb_bpda)
+  // white-box gradients through the i-vector-PLDA back end (fb_set_wb_ivector)
+  int wb_ivector = 0;                  // the switch: 0 (as created) refuses an i-vector system, as before it existed
+  DevBuf wb_iv_quad, wb_iv_A, wb_iv_linv, wb_iv_fail;   // the adjoint solve: the forward's matrix, k_iv_solve_ll's workspace
+  DevBuf wb_iv_wbar, wb_iv_lam, wb_iv_fbar, wb_iv_nbar, wb_iv_npart;   // wbar [R], lambda [R], Fbar [C][D], Nbar [C], partials
+  int wb_iv_A_R = -1;
   int wb_bpda = 0;                     // the switch: 0 (as created) refuses every defence, as before it existed
   DevBuf wb_gj;                        // one replica's cotangent on the row the front end read [N]
   const int16_t *fe_wav = nullptr;     // the int16 batch the last launch_mfcc handed to the front end (a device buffer of the engine's)
@@ -799,6 +804,8 @@ struct FbScoreCall {
   bool defer_finalize = false;   // the GMM finalisation is left to the caller's fused finalize + loss launch
   const FbIvTail *tail_loss = nullptr;  // i-vector systems: the loss body the solve kernels' tail should take along (null: none)
   bool tail_loss_done = false;   // out: it did
+  bool feats_given = false;      // e->feats / e->row_off / e->tv already hold the batch's rows: no front end (fb_debug_iv_feat_grad)
+  bool keep_iv_quad = false;     // i-vector systems: row 0 of quad as the contraction left it is copied to e->wb_iv_quad (white box)
   int replicas() const { return K * eot; }
 };
 // The replicating / composing transform launch: rn.r replicas of every utterance of `in` (in_off[B_in + 1]; longest: n_max) --
@@ -1034,9 +1041,11 @@ static int run_scoring(fb_engine *e, FbScoreCall &call, int B, int total_frames)
   FbFrontendDev fe = e->fe;
   FbGmmDev g = e->gmm;
   fe.stop = g.stop = call.stop;
-  FBCHK(launch_mfcc(e, call, fe, B, total_frames));
-  FBCHK(run_post_mfcc(e, fe, B));
-  if (e->feco_iters > 0) FBCHK(feature_compress(e, call, B, total_frames));
+  if (!call.feats_given) {
+    FBCHK(launch_mfcc(e, call, fe, B, total_frames));
+    FBCHK(run_post_mfcc(e, fe, B));
+    if (e->feco_iters > 0) FBCHK(feature_compress(e, call, B, total_frames));
+  }
   if (e->kind == 0) {
     // A GPU shared by three or more attacks (fb_set_fused_chain(e, 0)): k_gmm_fx2w takes a whole compute unit per workgroup (one
     // wave per SIMD with the full register file), and so does k_mfcc_f32 (four waves per SIMD at 122 registers) -- with a
@@ -1172,6 +1181,9 @@ static int run_scoring(fb_engine *e, FbScoreCall &call, int B, int total_frames)
                           e->iv_fail.as<int>());
     FBCHK(time_end(e));
     FB_DBG_SYNC(e, "contract");
+    // the solve below factorises quad in place: the white-box adjoint solve takes the matrix from this copy
+    if (call.keep_iv_quad)
+      HIPCHK(hipMemcpyAsync(e->wb_iv_quad.p, e->iv_quad.p, sizeof(double) * (size_t)iv.triR, hipMemcpyDeviceToDevice, s));
     // the back-end and, inside the NES loop, the loss body run in the solve kernels' tail (fb_iv_tail.h); FB_IV_TAIL=split
     // keeps the separate k_iv_backend / k_loss launches (A/B, tests: same numbers bit for bit)
     FbIvTail tail = {};
@@ -2313,11 +2325,15 @@ extern "C" int fb_attack_dev(fb_engine *e, const fb_nes_params *p, int S, const 
 // ------------------------------------------------- white-box gradients: fb_get_grad_wb / fb_attack_wb
 // The analytic gradient of the loss with respect to the samples ("white-box gradients" in fakebob_hip.h): GMM-UBM systems on
 // an undefended victim; with fb_set_wb_bpda(e, 1) through an input-transform chain, a codec and EOT replicas as well
-// (BPDA / EOT, the same contract).  Everything else is refused by name.
+// (BPDA / EOT, the same contract); with fb_set_wb_ivector(e, 1) i-vector-PLDA systems too.  Everything else is refused by name.
 static int wb_check(fb_engine *e, const fb_nes_params *p, const double *audio, int64_t N, fb_nes_params *q) {
   if (!e || !p || !audio) return fb_fail(FB_E_ARG, "null argument");
   if (!e->have_gmm) return fb_fail(FB_E_STATE, "no model loaded");
-  if (e->kind != 0) return fb_fail(FB_E_STATE, "white-box gradients: an i-vector system is loaded (GMM-UBM systems only in this version)");
+  if (e->kind != 0 && !e->wb_ivector)
+    return fb_fail(FB_E_STATE, "white-box gradients: an i-vector system is loaded (GMM-UBM systems only in this version)");
+  // (the forward keeps the selection, posteriors and statistics of ONE row for the backward, not those of r replicas)
+  if (e->kind != 0 && e->eot > 1)
+    return fb_fail(FB_E_STATE, "white-box gradients: fb_set_eot(%d) is in force on an i-vector system (per-replica i-vector state is not kept: set 1)", e->eot);
   if (e->eot > 1 && !e->wb_bpda) return fb_fail(FB_E_STATE, "white-box gradients: fb_set_eot(%d) is in force (set 1)", e->eot);
   if (e->comp_K1 > 0) return fb_fail(FB_E_STATE, "white-box gradients: companions are set (fb_set_companions: clear them)");
   if (e->tf.n > 0 && !e->wb_bpda)
@@ -2337,7 +2353,27 @@ static int wb_check(fb_engine *e, const fb_nes_params *p, const double *audio, i
 // the plain parameters on the device (once per fb_load_gmm) and the workspace of one utterance of N samples / T frames
 static int wb_prepare(fb_engine *e, int64_t N, int T, bool need_gmm) {
   const FbFrontendDev &fe = e->fe;
-  if (need_gmm) {
+  if (need_gmm && e->kind == 1) {
+    // the i-vector back end's backward: weights, the adjoint solve's matrix and workspace (k_iv_solve_ll wants a row of
+    // R + 64 zeros behind the right-hand side row and its own slots for the inverted diagonal blocks), Fbar / Nbar
+    const FbIvDev &iv = e->iv;
+    const size_t npanel = ((size_t)iv.R + 31) / 32;
+    FBCHK(e->wb_w.ensure(sizeof(double) * (size_t)iv.S));
+    FBCHK(e->wb_iv_quad.ensure(sizeof(double) * (size_t)iv.triR));
+    FBCHK(e->wb_iv_linv.ensure(sizeof(double) * npanel * 32 * 32));
+    FBCHK(e->wb_iv_wbar.ensure(sizeof(double) * (size_t)iv.R));
+    FBCHK(e->wb_iv_lam.ensure(sizeof(double) * (size_t)iv.R));
+    FBCHK(e->wb_iv_fbar.ensure(sizeof(double) * (size_t)iv.C * iv.D));
+    FBCHK(e->wb_iv_nbar.ensure(sizeof(double) * (size_t)iv.C));
+    FBCHK(e->wb_iv_npart.ensure(sizeof(double) * (size_t)fb_wb_iv_uchunks(iv) * iv.C));
+    if (!e->wb_iv_fail.p) FBCHK(e->wb_iv_fail.ensure(sizeof(int)));
+    const size_t had = e->wb_iv_A.cap;
+    FBCHK(e->wb_iv_A.ensure(sizeof(double) * (2 * (size_t)iv.R + 64)));
+    if (e->wb_iv_A.cap != had || e->wb_iv_A_R != iv.R) {
+      HIPCHK(hipMemsetAsync(e->wb_iv_A.p, 0, e->wb_iv_A.cap, e->stream));
+      e->wb_iv_A_R = iv.R;
+    }
+  } else if (need_gmm) {
     const FbGmmDev &g = e->gmm;
     if (!e->wb_uploaded) {
       FBCHK(e->wb_gc.ensure(sizeof(float) * e->h_wb_gc.size()));
@@ -2373,6 +2409,30 @@ static void wb_launch_gmm_backward(fb_engine *e, const int *n_rows_ptr, int T, c
                             e->feats.as<float>(), n_rows_ptr, T, e->wb_w.as<double>(), e->wb_part.as<float>(), e->wb_g.as<double>(),
                             stop, row_base_ptr);
 }
+// the i-vector back end's backward (fb_set_wb_ivector), in two parts.  First wbar = d (sum_s w_s LLR_s) / d ivec from the weights
+// in e->wb_w at the i-vector `ivec` (device, [R]) ...
+static void wb_launch_iv_backend_t(fb_engine *e, const double *ivec, const int *stop) {
+  fb_launch_wb_iv_backend_t(e->stream, e->iv, ivec, e->wb_w.as<double>(), e->wb_iv_wbar.as<double>(), stop);
+  e->wb_route[FB_WB_ROUTE_IV_BACKEND_T] += 1;
+}
+// ... then, from the cotangent e->wb_iv_wbar on the i-vector of row 0 of the batch the forward just scored (sel / post / the
+// active list / the i-vector as it left them, quad in e->wb_iv_quad): the adjoint solve lambda = quad^-1 wbar -- the forward's
+// own k_iv_solve_ll on the copy of the matrix, one right-hand side, no prior offset, no tail --, the parameter stream, and the
+// per-frame transpose.  The cotangent on the *n_rows_ptr (<= T) voiced rows lands in e->wb_g.
+static void wb_launch_iv_backward(fb_engine *e, const int *n_rows_ptr, int T, const int *stop) {
+  FbIvDev iv0 = e->iv;
+  iv0.prior_offset = 0.0;   // (the solve adds it to element 0 of the right-hand side and takes it off the solution: lin's, not wbar's)
+  const FbIvTail none = {};
+  fb_launch_iv_solve_ll(e->stream, iv0, e->wb_iv_quad.as<double>(), e->wb_iv_wbar.as<double>(), 1, 1, e->wb_iv_A.as<double>(),
+                        e->wb_iv_linv.as<double>(), e->wb_iv_lam.as<double>(), e->wb_iv_fail.as<int>(), none);
+  e->wb_route[FB_WB_ROUTE_IV_SOLVE] += 1;
+  fb_launch_wb_iv_stats_t(e->stream, e->iv, e->iv_active.as<int>(), e->wb_iv_lam.as<double>(), e->iv_ivec.as<double>(),
+                          e->wb_iv_fbar.as<double>(), e->wb_iv_npart.as<double>(), e->wb_iv_nbar.as<double>(), stop);
+  e->wb_route[FB_WB_ROUTE_IV_STATS_T] += 1;
+  fb_launch_wb_iv_post_t(e->stream, e->iv, e->feats.as<float>(), n_rows_ptr, T, e->iv_sel.as<int>(), e->iv_post.as<float>(),
+                         e->wb_iv_fbar.as<double>(), e->wb_iv_nbar.as<double>(), e->wb_g.as<double>(), stop);
+  e->wb_route[FB_WB_ROUTE_IV_POST_T] += 1;
+}
 // the front-end backward of row j of the batch the front end read (`wav`: rows of N samples, T frames each, their MFCC
 // matrices in e->mfcc): out = scale * the cotangent on that row's int16 samples
 static void wb_launch_frontend_vjp(fb_engine *e, const int16_t *wav, int j, int64_t N, int T, double scale, double *out, const int *stop) {
@@ -2399,6 +2459,8 @@ static int wb_launch_chain_t(fb_engine *e, const FbRngPoint &pt, int j, int64_t 
 // With fb_set_wb_bpda on and a defence or EOT replicas set: the forward scores the r replicas of the row (k_loss_eot when
 // r > 1), and behind it the replicas follow one by one -- weights of replica j, GMM backward on its voiced rows, front-end
 // backward on the row ITS front end read, the chain's transpose, which also adds replica j to e->grad (j ascending).
+// With fb_set_wb_ivector on and an i-vector system loaded (r = 1: wb_check): the same forward with a copy of quad kept, then
+// k_wb_iv_ctl and the i-vector back end's backward (wb_launch_iv_backend_t, wb_launch_iv_backward) in the GMM backward's place.
 static int wb_enqueue(fb_engine *e, const fb_nes_params *q, int64_t N, uint32_t it, bool with_dist, FbCtlDev *ctl, double *trace_dev) {
   const int *stop = ctl ? &ctl->stop : nullptr;
   const int r = e->eot;  // (companions are refused: the replicas are the EOT draws)
@@ -2410,6 +2472,7 @@ static int wb_enqueue(fb_engine *e, const fb_nes_params *q, int64_t N, uint32_t 
   FbScoreCall call{pt};
   call.eot = r;
   call.stop = stop;
+  call.keep_iv_quad = e->kind == 1;
   const int T = e->h_frame_off[1];
   FBCHK(run_scoring(e, call, r, e->h_frame_off[r]));
   const double scale = ldexp(1.0, nes_bits(q) - 1);
@@ -2433,13 +2496,22 @@ static int wb_enqueue(fb_engine *e, const fb_nes_params *q, int64_t N, uint32_t 
                            e->gmm.M, r, q->task, q->attack_type, e->zstd.as<double>(), q->threshold, q->target, q->true_label,
                            e->wb_w.as<double>(), ctl, j == 0 ? 1 : 0, trace_dev, (int)it);
       e->wb_route[FB_WB_ROUTE_CTL_REP] += 1;
+    } else if (e->kind == 1) {
+      fb_launch_wb_iv_ctl(e->stream, e->scores.as<double>(), e->nes_out.as<FbNesDev>(), S, q->task, q->attack_type,
+                          e->zstd.as<double>(), q->threshold, q->target, q->true_label, e->wb_w.as<double>(), ctl, trace_dev, (int)it);
+      e->wb_route[FB_WB_ROUTE_IV_CTL] += 1;
     } else {
       fb_launch_wb_ctl(e->stream, e->scores.as<double>(), e->nes_out.as<FbNesDev>(), e->gmm.M, q->task, q->attack_type,
                        e->zstd.as<double>(), q->threshold, q->target, q->true_label, e->wb_w.as<double>(), ctl, trace_dev, (int)it);
       e->wb_route[FB_WB_ROUTE_CTL] += 1;
     }
     // (row_off[0] = 0 and tv[0] = row_off[1]: replica 0 of an unreplicated batch is what the launch always took)
-    wb_launch_gmm_backward(e, r > 1 ? e->tv.as<int>() + j : e->row_off.as<int>() + 1, T, stop, r > 1 ? e->row_off.as<int>() + j : nullptr);
+    if (e->kind == 1) {
+      wb_launch_iv_backend_t(e, e->iv_ivec.as<double>(), stop);
+      wb_launch_iv_backward(e, e->row_off.as<int>() + 1, T, stop);
+    } else {
+      wb_launch_gmm_backward(e, r > 1 ? e->tv.as<int>() + j : e->row_off.as<int>() + 1, T, stop, r > 1 ? e->row_off.as<int>() + j : nullptr);
+    }
     wb_launch_frontend_vjp(e, e->fe_wav, j, N, T, scale, through_chain ? e->wb_gj.as<double>() : e->grad.as<double>(), stop);
     e->wb_route[FB_WB_ROUTE_BACKWARD] += 1;
     if (through_chain) FBCHK(wb_launch_chain_t(e, pt, j, N, e->wb_gj.as<double>(), e->grad.as<double>(), j > 0, stop));
@@ -2470,8 +2542,11 @@ extern "C" int fb_get_grad_wb_iter(fb_engine *e, const fb_nes_params *p, const d
   int status = 0;
   if (grad) FBCHK(d2h(e, grad, e->grad.p, sizeof(double) * (size_t)N));
   FBCHK(d2h(e, &status, e->wb_status.p, sizeof(int)));
+  int iv_fail = 0;
+  if (e->kind == 1) FBCHK(d2h(e, &iv_fail, e->iv_fail.p, sizeof(int)));
   FBCHK(fetch_out(e, true));
   HIPCHK(hipGetLastError());
+  if (iv_fail) return fb_fail(FB_E_ARG, "i-vector system of utterance %d is not positive definite", iv_fail - 1);
   FBCHK(wb_status_check(e, status));
   e->nes_iters += 1;
   if (adver_loss) *adver_loss = e->h_out->adver_loss;
@@ -2487,6 +2562,67 @@ extern "C" int fb_set_wb_bpda(fb_engine *e, int on) {
   if (!e) return fb_fail(FB_E_ARG, "null engine");
   if (on != 0 && on != 1) return fb_fail(FB_E_ARG, "fb_set_wb_bpda takes 0 or 1, not %d", on);
   e->wb_bpda = on;
+  return FB_OK;
+}
+
+extern "C" int fb_set_wb_ivector(fb_engine *e, int on) {
+  if (!e) return fb_fail(FB_E_ARG, "null engine");
+  if (on != 0 && on != 1) return fb_fail(FB_E_ARG, "fb_set_wb_ivector takes 0 or 1, not %d", on);
+  e->wb_ivector = on;
+  return FB_OK;
+}
+
+// Test hook: k_wb_iv_backend_t alone, on an i-vector and weights handed in
+extern "C" int fb_debug_iv_backend_grad(fb_engine *e, const double *ivec, const double *w, double *out) {
+  if (!e || !ivec || !w || !out) return fb_fail(FB_E_ARG, "null argument");
+  if (!e->have_gmm || e->kind != 1) return fb_fail(FB_E_STATE, "load an i-vector system first");
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  const FbIvDev &iv = e->iv;
+  memset(e->wb_route, 0, sizeof(e->wb_route));
+  FBCHK(e->wb_w.ensure(sizeof(double) * (size_t)iv.S));
+  FBCHK(e->wb_iv_wbar.ensure(sizeof(double) * (size_t)iv.R));
+  FBCHK(e->wb_iv_lam.ensure(sizeof(double) * (size_t)iv.R));
+  FBCHK(h2d(e, e->wb_w.p, w, sizeof(double) * (size_t)iv.S));
+  FBCHK(h2d(e, e->wb_iv_lam.p, ivec, sizeof(double) * (size_t)iv.R));   // (lambda's place is free until the solve)
+  wb_launch_iv_backend_t(e, e->wb_iv_lam.as<double>(), nullptr);
+  FBCHK(d2h(e, out, e->wb_iv_wbar.p, sizeof(double) * (size_t)iv.R));
+  FBCHK(sync_stream(e));
+  HIPCHK(hipGetLastError());
+  return FB_OK;
+}
+
+// Test hook: the i-vector extractor's forward on Tv rows of features handed in as they are -- run_scoring's own launches behind
+// the front end, as one utterance --, then wb_enqueue's launches from a cotangent cot[R] on the i-vector to the rows
+extern "C" int fb_debug_iv_feat_grad(fb_engine *e, const float *feats, int Tv, const double *cot, double *out) {
+  if (!e || !feats || !cot || !out || Tv <= 0) return fb_fail(FB_E_ARG, "bad argument");
+  if (!e->have_gmm || e->kind != 1) return fb_fail(FB_E_STATE, "load an i-vector system first");
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  const FbIvDev &iv = e->iv;
+  e->bench_it = -1;
+  memset(e->wb_route, 0, sizeof(e->wb_route));
+  FBCHK(wb_prepare(e, 1, Tv, true));
+  FBCHK(e->feats.ensure(sizeof(float) * (size_t)Tv * iv.D));
+  FBCHK(e->row_off.ensure(sizeof(int) * 2));
+  FBCHK(e->tv.ensure(sizeof(int)));
+  const int rows_host[2] = {0, Tv};
+  HIPCHK(hipMemcpy(e->feats.p, feats, sizeof(float) * (size_t)Tv * iv.D, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(e->row_off.p, rows_host, sizeof(rows_host), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(e->tv.p, &Tv, sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(e->wb_iv_wbar.p, cot, sizeof(double) * (size_t)iv.R, hipMemcpyHostToDevice));
+  e->cached_B = -1;
+  FbScoreCall call{scoring_call_point(e)};
+  call.feats_given = true;
+  call.keep_iv_quad = true;
+  FBCHK(run_scoring(e, call, 1, Tv));
+  wb_launch_iv_backward(e, e->row_off.as<int>() + 1, Tv, nullptr);
+  FBCHK(d2h(e, out, e->wb_g.p, sizeof(double) * (size_t)Tv * iv.D));
+  int fail = 0;
+  FBCHK(d2h(e, &fail, e->iv_fail.p, sizeof(int)));
+  FBCHK(sync_stream(e));
+  HIPCHK(hipGetLastError());
+  if (fail) return fb_fail(FB_E_ARG, "i-vector system of utterance %d is not positive definite", fail - 1);
   return FB_OK;
 }
 

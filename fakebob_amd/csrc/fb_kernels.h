@@ -328,6 +328,24 @@ size_t fb_wb_chain_t_lds_bytes(const FbTfChain &ch);
 bool fb_launch_wb_chain_t(hipStream_t s, const FbTfChain &ch, const double *taps, const int16_t *wav, int64_t n, const FbTfRnd &rn,
                           int replica, const double *cot, double *grad, int accumulate, const int *stop);
 
+// ---- white-box gradients through the i-vector-PLDA back end (fb_set_wb_ivector; whitebox_iv_kernels.hip) ------------
+struct FbIvDev;
+// k_wb_ctl for an i-vector system: w[S] = d loss / d raw[s] (every task z-normalises: the 1 / z_std is in w), the same loop control
+void fb_launch_wb_iv_ctl(hipStream_t s, const double *scores, const FbNesDev *out, int S, int task, int attack_type,
+                         const double *z_std, double threshold, int target, int true_label, double *w, FbCtlDev *ctl, double *trace,
+                         int it);
+// wbar[R] = d (sum_s w[s] LLR_s) / d ivec at the i-vector ivec[R] (raw LLRs, before the z-norm)
+void fb_launch_wb_iv_backend_t(hipStream_t s, const FbIvDev &iv, const double *ivec, const double *w, double *wbar, const int *stop);
+// With lam = quad^-1 wbar and ivec the forward's i-vector, for the components of the forward's active list (active[C] = their
+// number): fbar[k][D] = (Sigma^-1 M)_k lam and nbar[k] = - lam' U_k w.  npart: fb_wb_iv_uchunks(iv) * C doubles of workspace.
+// Entries of the other components are not written
+int fb_wb_iv_uchunks(const FbIvDev &iv);
+void fb_launch_wb_iv_stats_t(hipStream_t s, const FbIvDev &iv, const int *active, const double *lam, const double *ivec, double *fbar,
+                             double *npart, double *nbar, const int *stop);
+// g[t][D] = the cotangent on the voiced feature rows t < *n_rows_ptr (<= rows_cap) from the forward's sel / post [rows][nsel]
+void fb_launch_wb_iv_post_t(hipStream_t s, const FbIvDev &iv, const float *feats, const int *n_rows_ptr, int rows_cap, const int *sel,
+                            const float *post, const double *fbar, const double *nbar, double *g, const int *stop);
+
 // ---- front-end ------------------------------------------------------------
 // MFCC of every frame of a (ragged) batch.  wav_off[B+1], frame_off[B+1] device arrays.
 // frame_rec: [total_frames][4] int32 = {absolute start sample (int64 in two words), start within the

@@ -58,6 +58,7 @@ class Engine(object):
         self.codec = None
         self.eot = 1
         self.wb_bpda = False
+        self.wb_ivector = False
         self.companions = None
         self.feature_compression = None
 
@@ -312,6 +313,7 @@ class Engine(object):
         """system: models.IvectorSystem"""
         sy, keep = N.ivector_struct(system)
         self._iv_nsel = system.num_gselect
+        self._iv_shape = (system.C, system.D, system.R, system.S)
         N.check(self._L.fb_load_ivector(self._h, C.byref(sy), C.c_int(N.TASK[task])))
         self.n_models = system.S
         self.task = task
@@ -526,6 +528,13 @@ class Engine(object):
         N.check(self._L.fb_set_wb_bpda(self._h, C.c_int(1 if on else 0)))
         self.wb_bpda = bool(on)
 
+    def set_wb_ivector(self, on):
+        """fb_set_wb_ivector: with True, get_grad_wb and attack_wb differentiate through a loaded i-vector-PLDA system (the
+        selection and the pruned set held constant: the rules are in include/fakebob_hip.h).  False (as created): an
+        i-vector system is refused and nothing else changes; a GMM-UBM system runs the same launches either way."""
+        N.check(self._L.fb_set_wb_ivector(self._h, C.c_int(1 if on is True else 0 if on is False else int(on))))
+        self.wb_ivector = bool(on)
+
     def get_grad_wb(self, params, audio, want_grad=True):
         """fb_get_grad_wb: get_grad_wb_iter at iter = 0."""
         return self.get_grad_wb_iter(params, audio, 0, want_grad)
@@ -535,7 +544,8 @@ class Engine(object):
         units of get_grad's estimate; adver_loss; score0 (S,)).  adver_loss and score0 are get_grad's own: the same forward.
         samples_per_draw and sigma are not read; seed, stream and `iter` (the epoch of the draws, as get_grad's `it`) key the
         random stages of a defended victim.  Refused (NativeError, FB_E_STATE) for i-vector systems and while an air channel,
-        feature compression, dither or companions are set; an input transform, a codec and EOT only after set_wb_bpda(True)."""
+        feature compression, dither or companions are set; an input transform, a codec and EOT only after set_wb_bpda(True).
+        After set_wb_ivector(True) an i-vector system is differentiated as well (never with set_eot > 1)."""
         audio = np.ascontiguousarray(audio, np.float64).reshape(-1)
         n = audio.size
         grad = np.empty(n, np.float64) if want_grad else None
@@ -547,7 +557,8 @@ class Engine(object):
 
     def attack_wb(self, params, audio):
         """fb_attack_wb: FakeBob.attack's loop with the analytic gradient in place of the NES estimate (momentum = 0: PGD
-        with the margin loss; max_iter = 1: the single-step attack) -> (int16 adv, flag, float64 adv, trace), as attack."""
+        with the margin loss; max_iter = 1: the single-step attack) -> (int16 adv, flag, float64 adv, trace), as attack.
+        GMM-UBM systems; i-vector systems after set_wb_ivector(True), with the same loop, trace layout and stop test."""
         audio = np.ascontiguousarray(audio, np.float64).reshape(-1)
         n, S = audio.size, max(self.n_speakers, 1)
         adv = np.empty(n, np.int16)
@@ -572,10 +583,41 @@ class Engine(object):
 
     def debug_wb_route(self):
         """Launches of the white-box backward the last get_grad_wb / attack_wb / debug_defence_vjp call enqueued
-        (fb_debug_wb_route): a dict ctl, ctl_rep, backward, chain_t."""
-        info = (C.c_int * 4)()
+        (fb_debug_wb_route): a dict ctl, ctl_rep, backward, chain_t; with an i-vector system loaded also iv_ctl,
+        iv_backend_t, iv_solve, iv_stats_t, iv_post_t (all zero for a GMM-UBM system, and left out for one)."""
+        info = (C.c_int * 9)()
         N.check(self._L.fb_debug_wb_route(self._h, info))
-        return dict(zip(("ctl", "ctl_rep", "backward", "chain_t"), [int(v) for v in info]))
+        names = ("ctl", "ctl_rep", "backward", "chain_t", "iv_ctl", "iv_backend_t", "iv_solve", "iv_stats_t", "iv_post_t")
+        return dict(list(zip(names, [int(v) for v in info]))[:9 if getattr(self, "kind", None) == "iv" else 4])
+
+    def debug_iv_backend_grad(self, ivec, w):
+        """k_wb_iv_backend_t alone (fb_debug_iv_backend_grad): ivec (R,), w (S,) -> (R,) float64, the gradient of
+        sum_s w[s] * LLR_s (raw, before the z-norm) with respect to the i-vector."""
+        if getattr(self, "kind", None) != "iv":
+            raise ValueError("debug_iv_backend_grad needs a loaded i-vector system")
+        Cn, D, R, S = self._iv_shape
+        ivec = np.ascontiguousarray(ivec, np.float64).reshape(-1)
+        w = np.ascontiguousarray(w, np.float64).reshape(-1)
+        if ivec.size != R or w.size != S:
+            raise ValueError("debug_iv_backend_grad takes an i-vector of %d and %d weights" % (R, S))
+        out = np.empty(R, np.float64)
+        N.check(self._L.fb_debug_iv_backend_grad(self._h, N.ptr(ivec), N.ptr(w), N.ptr(out)))
+        return out
+
+    def debug_iv_feat_grad(self, feats, cot):
+        """The extractor's backward alone (fb_debug_iv_feat_grad): feats (Tv, D) float32 handed in as they are, cot (R,) a
+        cotangent on the i-vector -> (Tv, D) float64 = d <cot, ivec(feats)> / d feats.  debug_iv_gselect and last_ivectors
+        afterwards describe the forward it ran."""
+        if getattr(self, "kind", None) != "iv":
+            raise ValueError("debug_iv_feat_grad needs a loaded i-vector system")
+        Cn, D, R, S = self._iv_shape
+        feats = np.ascontiguousarray(feats, np.float32)
+        cot = np.ascontiguousarray(cot, np.float64).reshape(-1)
+        if feats.ndim != 2 or feats.shape[1] != D or feats.shape[0] < 1 or cot.size != R:
+            raise ValueError("debug_iv_feat_grad takes rows of %d features and a cotangent of %d" % (D, R))
+        out = np.empty(feats.shape, np.float64)
+        N.check(self._L.fb_debug_iv_feat_grad(self._h, N.ptr(feats), C.c_int(feats.shape[0]), N.ptr(cot), N.ptr(out)))
+        return out
 
     def debug_gmm_feat_grad(self, feats, w):
         """The GMM backward alone (fb_debug_gmm_feat_grad): feats (Tv, D) float32 handed in as they are, w (M,) the

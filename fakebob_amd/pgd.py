@@ -8,7 +8,9 @@ is no random start, so a run is reproducible.  PGD's victim has to be undefended
 defended one (Engine.set_wb_bpda): BPDA through the model's input-transform chain and codec, and with eot_size = r > 1 an
 expectation over r draws of its random stages per iteration, keyed by the attack's seed and stream.  The air channel,
 feature compression, dither and companions stay refused, as are i-vector systems and foreign models -- the gradient is
-that of this library's own forward.
+that of this library's own forward.  IvectorPGD is the same attack on an i-vector-PLDA system (Engine.set_wb_ivector): the
+gradient through the PLDA back end, both length normalisations, the posterior solve and the full-covariance posteriors, with
+the frames' component selection and pruned sets held constant; PGD and AdaptivePGD keep refusing such a system.
 """
 import pickle
 import time
@@ -20,6 +22,7 @@ from .engine import nes_params
 
 
 class PGD(object):
+    KINDS = ("gmm",)   # engine kinds the class differentiates (IvectorPGD: the i-vector back end as well)
 
     def __init__(self, task, attack_type, model, adver_thresh=0., epsilon=0.002, max_iter=1000, max_lr=0.001, min_lr=1e-6,
                  momentum=0.9, plateau_length=5, plateau_drop=2., seed=None, verbose=True):
@@ -29,7 +32,7 @@ class PGD(object):
             raise TypeError("PGD differentiates this library's own GMM-UBM systems: the model has no engine")
         if getattr(model, "task", task) != task:
             raise ValueError("model implements task %s, attack asked for %s" % (model.task, task))
-        if getattr(model.engine, "kind", "gmm") != "gmm":
+        if getattr(model.engine, "kind", "gmm") not in self.KINDS:
             raise ValueError("PGD: i-vector systems are out of this version (GMM-UBM systems only)")
         self.bpda = False   # (AdaptivePGD: True -- the engine's switch is on and seed / stream key the victim's draws)
         self.eot_size = 1
@@ -137,4 +140,20 @@ class AdaptivePGD(PGD):
         self.eot_size = eot_size
         if self.bpda:  # (left alone otherwise: the engine's own refusals then name what is set)
             model.engine.set_eot(eot_size)
+            model.engine.set_wb_bpda(True)
+
+
+class IvectorPGD(PGD):
+    """PGD on an i-vector-PLDA victim (and, unchanged, on a GMM-UBM one).  The constructor switches the model's engine to
+    differentiate through the i-vector back end (Engine.set_wb_ivector; the rules are in include/fakebob_hip.h) and, with
+    bpda=True, through an input-transform chain and a codec as well (Engine.set_wb_bpda); both stay set.  There is no
+    expectation over transformation for an i-vector system.  Knobs, attack(), get_grad(), estimate_threshold(), the return
+    pair and the checkpoint layout are PGD's."""
+    KINDS = ("gmm", "iv")
+
+    def __init__(self, task, attack_type, model, bpda=False, **kw):
+        PGD.__init__(self, task, attack_type, model, **kw)
+        self.bpda = bool(bpda)
+        model.engine.set_wb_ivector(True)
+        if self.bpda:
             model.engine.set_wb_bpda(True)

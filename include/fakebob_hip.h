@@ -37,6 +37,8 @@
  *                             SpeakerGuard's evaluation (FGSM, PGD, the margin-loss CW-inf) on a GMM-UBM system
  *   fb_set_wb_bpda / fb_get_grad_wb_iter   (none in FAKEBOB: the adaptive form of those attacks on a DEFENDED victim -- BPDA
  *                             through the input-transform chain and the codec, EOT over the random stages)
+ *   fb_set_wb_ivector         (none in FAKEBOB: the same white-box calls on an i-vector-PLDA system, the frames' component
+ *                             selection and pruned sets held constant)
  *   fb_get_grad_ext / fb_attack_ext   the same around a foreign `model` (README.md:136)
  *   fb_get_grad_dev / fb_attack_dev   ... around a foreign model that runs on the
  *                             same GPU: the batch and the scores stay on the device
@@ -583,8 +585,42 @@ int fb_attack_kenansville(fb_engine *e, const fb_nes_params *p, const fb_kv_para
  *   codec (ulaw, alaw, adpcm)    the identity: BPDA in the strict sense.  A segment-slope derivative for G.711 is not in
  *                                this version.
  * No floating-point atomics and a fixed order in every sum: the same call on a fresh engine gives the same bits.  The
- * 2^(bits_per_sample - 1) scale and the units of grad are unchanged. */
+ * 2^(bits_per_sample - 1) scale and the units of grad are unchanged.
+ *
+ * The i-vector-PLDA victim (fb_set_wb_ivector).  A second switch, for the same reason as the first: fb_set_wb_ivector(e, on),
+ * on = 0 or 1 (anything else: FB_E_ARG, the setting stays), 0 at engine creation, kept across fb_load_*.  With 0 every call,
+ * launch, value and message is what it was before the switch existed.  With 1 a GMM-UBM system still takes the very same
+ * launches, and fb_get_grad_wb, fb_get_grad_wb_iter and fb_attack_wb accept a loaded i-vector system, all three tasks and
+ * both attack types.  The function that is differentiated is the engine's own forward:
+ *  - the front end as above: straight-through cast, the voiced mask held constant, an active floor contributes zero;
+ *  - gmm-gselect is a constant: the num_gselect components a frame selected on the diagonalised UBM are the forward's;
+ *  - --min-post pruning is a constant set: the slots whose float32 posterior the forward dropped stay dropped, and on the
+ *    kept set K_t the posterior is the soft-max of the full-covariance log-likelihoods
+ *    ll_tk = gconst_k + (Sigma_k^-1 mu_k) . x - 1/2 x' Sigma_k^-1 x restricted to K_t (what "drop, renormalise" equals), so
+ *    d gamma_tk / d ll_tj = gamma_tk (delta_kj - gamma_tj) for j, k in K_t; the rescue of a frame whose posteriors all
+ *    fell below min_post (one slot set to 1) is a constant posterior;
+ *  - the float32 storage points (features, ll, posteriors, the i-vector's text form) and text_scores are identities;
+ *  - N_k = sum_t gamma_tk, F_k = sum_t gamma_tk x_t; lin = sum_k A_k' F_k + prior e_0 with A_k = Sigma_k^-1 M_k;
+ *    quad = I + sum_k N_k U_k; w = quad^-1 lin; the i-vector is w - prior e_0;
+ *  - the back end: - mean.vec; LDA, with or without the offset column; * sqrt(L) / |.|; PLDA y0 = A (c - m), then
+ *    * sqrt(L / sum_i y0_i^2 / (psi_i + 1)); the closed-form LLR against each enrolled vector with n = 1; the wrappers'
+ *    z-norm (every task); loss_fn with the first-maximum subgradient, as above.
+ * Backward, all float64, the posteriors and the selection read from what the forward left on the device: the weights
+ * w[S] = d loss / d raw[s] (k_wb_iv_ctl: the 1 / z_std inside); wbar = d (sum_s w_s LLR_s) / d ivec (k_wb_iv_backend_t: the
+ * back end recomputed, then transposed); lambda = quad^-1 wbar by the forward's own k_iv_solve_ll on a copy of the matrix
+ * taken before the forward factorised it; for the components of the forward's active list Fbar_k = A_k lambda and
+ * Nbar_k = - lambda' U_k w (k_wb_iv_stats_t: one stream over Sigma^-1 M and the packed U; an off-diagonal packed element
+ * stands for two, the diagonal for one); per voiced frame over its kept slots (k_wb_iv_post_t)
+ *     gammabar_tk = Nbar_k + Fbar_k . x_t,   llbar_tk = gamma_tk (gammabar_tk - sum_j gamma_tj gammabar_tj),
+ *     xbar_t = sum_k gamma_tk Fbar_k + sum_k llbar_tk (Sigma_k^-1 mu_k - Sigma_k^-1 x_t);
+ * then the front-end backward above, unchanged.  adver_loss and score0 are bit for bit fb_get_grad's at samples_per_draw = 0:
+ * the same scoring call.  fb_attack_wb is the same loop, trace layout and stop test.
+ * Refused for an i-vector system with the switch on, FB_E_STATE, the cause named: companions, an air channel, feature
+ * compression, dither > 0, and fb_set_eot(r > 1) -- the last with fb_set_wb_bpda on as well ("i-vector", "fb_set_eot": the
+ * forward keeps one row's i-vector state, not r replicas').  An input-transform chain and a codec need fb_set_wb_bpda(e, 1), as
+ * for a GMM-UBM system, and are then taken at r = 1.  FB_E_NO_VOICED and the "not positive definite" error are scoring's. */
 int fb_set_wb_bpda(fb_engine *e, int on);
+int fb_set_wb_ivector(fb_engine *e, int on);
 int fb_get_grad_wb_iter(fb_engine *e, const fb_nes_params *p, const double *audio, int64_t N, int iter, double *adver_loss,
                         double *grad /*[N], nullable*/, double *score0 /*[S]*/);
 int fb_get_grad_wb(fb_engine *e, const fb_nes_params *p, const double *audio, int64_t N, double *adver_loss,

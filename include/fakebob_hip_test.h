@@ -325,10 +325,27 @@ int fb_debug_frontend_vjp(fb_engine *e, const int16_t *wav, int64_t n, const dou
 #define FB_WB_ROUTE_CTL_REP 1    /* k_wb_ctl_rep: weights of one replica of r > 1 (replica 0: + loop control) */
 #define FB_WB_ROUTE_BACKWARD 2   /* GMM backward + front-end backward of one replica (seven launches) */
 #define FB_WB_ROUTE_CHAIN_T 3    /* k_wb_chain_t: the chain's transpose of one replica, adding it to the gradient */
-#define FB_WB_ROUTE_N 4
+#define FB_WB_ROUTE_IV_CTL 4        /* k_wb_iv_ctl: an i-vector system's weights (+ loop control) */
+#define FB_WB_ROUTE_IV_BACKEND_T 5  /* k_wb_iv_backend_t: the cotangent on the i-vector */
+#define FB_WB_ROUTE_IV_SOLVE 6      /* the adjoint solve (k_iv_solve_ll on the copy of the forward's matrix) */
+#define FB_WB_ROUTE_IV_STATS_T 7    /* k_wb_iv_stats_t + k_wb_iv_nbar: the stream over Sigma^-1 M and U */
+#define FB_WB_ROUTE_IV_POST_T 8     /* k_wb_iv_post_t: the cotangent on the voiced feature rows */
+#define FB_WB_ROUTE_N 9
 int fb_debug_defence_vjp(fb_engine *e, const int16_t *wav, int64_t n, uint64_t seed, uint32_t stream, int iter,
                          const double *cot /*[r][n]*/, double *dwav /*[r][n]*/, int16_t *out /*[r][n], nullable*/);
 int fb_debug_wb_route(fb_engine *e, int *info);
+
+/* White-box gradients through the i-vector-PLDA back end (fakebob_hip.h: fb_set_wb_ivector).  Both hooks need a loaded i-vector
+ * system (FB_E_STATE otherwise) and run whatever the switch says, with exactly the launches an attack iteration runs for
+ * their stage.
+ * fb_debug_iv_backend_grad: out[R] = the gradient of sum_s w[s] LLR_s -- the raw LLRs, before the z-norm -- with respect to the
+ * i-vector, at ivec[R].
+ * fb_debug_iv_feat_grad: <cot, ivec(feats)> differentiated with respect to the Tv feature rows handed in as they are (float32
+ * [Tv][D]; cot[R]): the forward's selection, posteriors, statistics and solve on those rows, then the adjoint solve,
+ * k_wb_iv_stats_t and k_wb_iv_post_t; out[Tv][D] float64.  fb_debug_iv_gselect and fb_last_ivectors afterwards describe that
+ * forward. */
+int fb_debug_iv_backend_grad(fb_engine *e, const double *ivec /*[R]*/, const double *w /*[S]*/, double *out /*[R]*/);
+int fb_debug_iv_feat_grad(fb_engine *e, const float *feats, int Tv, const double *cot /*[R]*/, double *out /*[Tv*D]*/);
 
 #ifdef __cplusplus
 }
