@@ -204,8 +204,12 @@ def main(argv=None, model_factory=None, bob_factory=None):
                          "victim unless --bpda is given)")
     ap.add_argument("--bpda", action="store_true",
                     help="--attack pgd: the adaptive attack on a defended victim -- BPDA through --input-transform and --codec, "
-                         "expectation over --eot-size draws of the random stages; --air-channel, --feco, --dither and "
-                         "--companions stay refused")
+                         "expectation over --eot-size draws of the random stages; --air-channel is refused unless --wb-air is "
+                         "given, --feco, --dither and --companions stay refused")
+    ap.add_argument("--wb-air", dest="wb_air", action="store_true",
+                    help="--attack pgd: differentiate through --air-channel as well (fakebob_amd/pgd.py: air=True; the forward's "
+                         "drawn room responses transposed, with --bpda --eot-size r the expectation over r rooms per iteration); "
+                         "on a GMM-UBM system with --bpda, on -archi iv with --wb-ivector")
     ap.add_argument("--wb-ivector", dest="wb_ivector", action="store_true",
                     help="--attack pgd -archi iv: differentiate the i-vector-PLDA victim (fakebob_amd/pgd.py: IvectorPGD; the "
                          "frames' component selection and pruned sets held constant); never under --eot-size > 1")
@@ -242,18 +246,24 @@ def main(argv=None, model_factory=None, bob_factory=None):
         ap.error("--bpda belongs to --attack pgd (--attack %s)" % args.attack)
     if args.wb_ivector and args.attack != "pgd":
         ap.error("--wb-ivector belongs to --attack pgd (--attack %s)" % args.attack)
+    if args.wb_air and args.attack != "pgd":
+        ap.error("--wb-air belongs to --attack pgd (--attack %s)" % args.attack)
     if args.attack == "pgd":      # likewise: the gradient is that of a GMM-UBM victim, undefended unless --bpda is given
         if args.architecture == "iv" and args.wb_ivector and args.eot_size is not None and args.eot_size > 1:
             ap.error("--attack pgd --wb-ivector does not run under expectation over transformation (--eot-size %d: an i-vector "
                      "system keeps one row's state)" % args.eot_size)
         if args.architecture != "gmm" and not args.wb_ivector:
             ap.error("--attack pgd differentiates GMM-UBM systems only (--architecture %s)" % args.architecture)
+        if args.wb_air and not args.bpda and not args.wb_ivector and args.air_channel is None:
+            ap.error("--attack pgd --wb-air belongs to the adaptive attack: give --bpda (GMM-UBM) or --wb-ivector (-archi iv)")
         if not args.bpda and args.eot_size is not None and args.eot_size > 1:
             ap.error("--attack pgd does not run under expectation over transformation (--eot-size %d)" % args.eot_size)
         if args.companions > 0:
             ap.error("--attack pgd does not take companion utterances (--companions %d)" % args.companions)
         for flag, val in (("--input-transform", args.input_transform), ("--air-channel", args.air_channel),
                           ("--codec", None if args.codec == "none" else args.codec), ("--feco", args.feco), ("--dither", args.dither)):
+            if flag == "--air-channel" and val is not None and args.wb_air and (args.wb_ivector if args.architecture == "iv" else args.bpda):
+                continue
             if val is not None and not (args.bpda and flag in ("--input-transform", "--codec")):
                 ap.error("--attack pgd attacks an undefended victim: %s %s is not differentiated in this version" % (flag, val))
 
@@ -307,6 +317,8 @@ def main(argv=None, model_factory=None, bob_factory=None):
             hp.update(bpda=True, eot_size=args.eot_size if args.eot_size is not None else 1)
         if args.wb_ivector:  # IvectorPGD has no eot_size
             hp.pop("eot_size", None)
+        if args.wb_air:
+            hp.update(air=True)
     if bob_factory is None and args.attack == "pgd" and args.wb_ivector:
         from .pgd import IvectorPGD
         bobs = [IvectorPGD(task, attack_type, m, seed=seed, verbose=False, **hp) for m in models]

@@ -15,6 +15,9 @@
 //              blocks of 16 x 16 outputs; they share one H fragment per K step.
 // Nothing is exchanged between workgroups, there are no atomics, every global index is checked against [0, n), and the
 // `stop` flag is honoured as the transform kernels honour it.
+// k_air_conv is a template on KEEP_SAT: <true>, taken by white-box calls under fb_set_wb_air only, also writes one byte per
+// output sample -- saturated before the clip or not -- for the transposed kernel (whitebox_air_kernels.hip); <false> is the
+// kernel every other caller takes.
 //
 // f64 MFMA lane maps (they are not the f32 ones): A -- lane l holds X[row l & 15][k = l >> 4]; B -- H[k = l >> 4][col l & 15];
 // C / D -- register g of lane l is Y[row (l >> 4) + 4 g][col l & 15].  So register g of a block holds outputs
@@ -96,10 +99,14 @@ __global__ __launch_bounds__(AIR_THREADS) void k_air_taps(FbAir ac, int rep0, in
 }
 
 // out row R (at out_off[R]) = the convolution of input row R / r (in_off) -- with cn.K > 1 utterance (R % r) / eot of that
-// row as composed -- with taps[R][L]; r: output rows per input row
+// row as composed -- with taps[R][L]; r: output rows per input row.  KEEP_SAT (the white-box call under fb_set_wb_air): sat,
+// laid out as out, gets one byte per output sample -- 1 where (y + 8192) >> 14 lay outside [-32768, 32767] before the clip;
+// the instantiation every other caller takes, <false>, is the kernel as it was and touches no sat
+template <bool KEEP_SAT>
 __global__ __launch_bounds__(AIR_THREADS) void k_air_conv(const int16_t *__restrict__ wav, const int64_t *__restrict__ in_off, int r, int eot,
                                                           const int16_t *__restrict__ taps, int L, int16_t *__restrict__ out,
-                                                          const int64_t *__restrict__ out_off, FbTfComp cn, const int *__restrict__ stop) {
+                                                          const int64_t *__restrict__ out_off, FbTfComp cn, const int *__restrict__ stop,
+                                                          unsigned char *__restrict__ sat) {
   extern __shared__ int16_t air_lds[];
   if (stop && *stop) return;
   const int R = blockIdx.y, u = R / r;
@@ -160,6 +167,7 @@ __global__ __launch_bounds__(AIR_THREADS) void k_air_conv(const int16_t *__restr
         const long long y = (long long)acc[T][g];  // an exact integer, |y| < 2^42
         const long long o = (y + 8192) >> 14;      // (arithmetic shift: floor)
         out[obase + i] = (int16_t)(o < -32768 ? -32768 : (o > 32767 ? 32767 : o));
+        if (KEEP_SAT) sat[obase + i] = (o < -32768 || o > 32767) ? 1 : 0;
       }
     }
   }
@@ -175,8 +183,15 @@ size_t fb_air_conv_lds_bytes(int L) {
 }
 
 void fb_launch_air_conv(hipStream_t s, const int16_t *wav, const int64_t *in_off, int rows, int r, int eot, int64_t n_max,
-                        const int16_t *taps, int L, int16_t *out, const int64_t *out_off, const FbTfComp *cn, const int *stop) {
+                        const int16_t *taps, int L, int16_t *out, const int64_t *out_off, const FbTfComp *cn, const int *stop,
+                        unsigned char *sat) {
   const unsigned chunks = (unsigned)((n_max + AIR_CHUNK - 1) / AIR_CHUNK);
-  hipLaunchKernelGGL(k_air_conv, dim3(chunks > 0 ? chunks : 1, rows), dim3(AIR_THREADS), fb_air_conv_lds_bytes(L), s, wav, in_off, r,
-                     eot, taps, L, out, out_off, cn ? *cn : FbTfComp{1, 0, nullptr, nullptr}, stop);
+  const dim3 grid(chunks > 0 ? chunks : 1, rows);
+  const FbTfComp none{1, 0, nullptr, nullptr};
+  if (sat)
+    hipLaunchKernelGGL(k_air_conv<true>, grid, dim3(AIR_THREADS), fb_air_conv_lds_bytes(L), s, wav, in_off, r, eot, taps, L, out, out_off,
+                       cn ? *cn : none, stop, sat);
+  else
+    hipLaunchKernelGGL(k_air_conv<false>, grid, dim3(AIR_THREADS), fb_air_conv_lds_bytes(L), s, wav, in_off, r, eot, taps, L, out, out_off,
+                       cn ? *cn : none, stop, sat);
 }

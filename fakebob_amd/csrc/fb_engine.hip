@@ -48,7 +48,7 @@ static int fb_fail(int code, const char *fmt, ...) {
   } while (0)
 
 extern "C" const char *fb_last_error(void) { return g_err.c_str(); }
-extern "C" int fb_version(void) { return 102; }
+extern "C" int fb_version(void) { return 103; }
 extern "C" int fb_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -231,6 +231,11 @@ struct fb_engine {
   DevBuf wb_gj;                        // one replica's cotangent on the row the front end read [N]
   const int16_t *fe_wav = nullptr;     // the int16 batch the last launch_mfcc handed to the front end (a device buffer of the engine's)
   int wb_route[FB_WB_ROUTE_N] = {};    // launches of the white-box backward the last call enqueued (fb_debug_wb_route)
+  // white-box gradients through the over-the-air channel (fb_set_wb_air)
+  int wb_air = 0;                      // the switch: 0 (as created) refuses a channel, as before it existed
+  DevBuf wb_air_cot, wb_air_dx;        // the replicas' cotangents on the channel's output [r][N], k_air_conv_t's output [r][N] (r > 1)
+  DevBuf wb_air_sat;                   // the forward's saturation bytes, laid out as wav_air (k_air_conv<true>)
+  int wb_air_launches = 0;             // k_air_conv_t launches of the last call (fb_debug_wb_air_route)
   FbNesDev *h_out = nullptr;  // pinned
   int *h_tv = nullptr;        // pinned, grows
   size_t h_tv_cap = 0;
@@ -806,6 +811,7 @@ struct FbScoreCall {
   bool tail_loss_done = false;   // out: it did
   bool feats_given = false;      // e->feats / e->row_off / e->tv already hold the batch's rows: no front end (fb_debug_iv_feat_grad)
   bool keep_iv_quad = false;     // i-vector systems: row 0 of quad as the contraction left it is copied to e->wb_iv_quad (white box)
+  bool keep_air_sat = false;     // an air channel: k_air_conv also writes its saturation bytes to e->wb_air_sat (white box)
   int replicas() const { return K * eot; }
 };
 // The replicating / composing transform launch: rn.r replicas of every utterance of `in` (in_off[B_in + 1]; longest: n_max) --
@@ -828,15 +834,18 @@ static int launch_transform_replicas(fb_engine *e, const int16_t *in, const int6
 // The over-the-air channel and the chain behind it: rows = B_in * r output rows (row R = replica R % r of utterance row R / r
 // of `in`; with cn utterance (R % r) / eot of that row as composed) go through k_air_taps + k_air_conv into e->wav_air at
 // out_off, then -- if a chain is set -- through the chain's launch in its "input already replicated" mode into e->wav_tf
-// (both buffers sized by the caller: out_samples).  *res: the buffer that holds the result.
+// (both buffers sized by the caller: out_samples).  *res: the buffer that holds the result.  keep_sat: the white-box call's
+// FbScoreCall::keep_air_sat.
 static int launch_air_path(fb_engine *e, const int16_t *in, const int64_t *in_off, int B_in, int r, int eot, int64_t n_max,
                            size_t out_samples, const int64_t *out_off, const FbRngPoint &pt, const FbTfComp *cn, const int *stop,
-                           const int16_t **res) {
+                           const int16_t **res, bool keep_sat = false) {
   const int rows = B_in * r, L = e->air.L;
   FBCHK(e->wav_air.ensure(sizeof(int16_t) * out_samples));
   FBCHK(e->air_taps.ensure(sizeof(int16_t) * (size_t)rows * (size_t)L));
+  if (keep_sat) FBCHK(e->wb_air_sat.ensure(out_samples));
   fb_launch_air_taps(e->stream, fb_air_key(pt, e->air, r), 0, rows, e->air_taps.as<int16_t>(), nullptr, nullptr, stop);
-  fb_launch_air_conv(e->stream, in, in_off, rows, r, eot, n_max, e->air_taps.as<int16_t>(), L, e->wav_air.as<int16_t>(), out_off, cn, stop);
+  fb_launch_air_conv(e->stream, in, in_off, rows, r, eot, n_max, e->air_taps.as<int16_t>(), L, e->wav_air.as<int16_t>(), out_off, cn, stop,
+                     keep_sat ? e->wb_air_sat.as<unsigned char>() : nullptr);
   *res = e->wav_air.as<int16_t>();
   if (e->tf.n == 0) return FB_OK;
   FBCHK(e->wav_tf.ensure(sizeof(int16_t) * out_samples));
@@ -866,7 +875,7 @@ static int chained_wav(fb_engine *e, const FbScoreCall &call, const int64_t *off
   if (e->air.L > 0) {  // (fb_set_air_channel) the channel writes the replicas, the chain follows row by row
     const FbTfComp cn{call.K, e->comp_N, e->comp_a0.as<int16_t>(), e->comp_wav.as<int16_t>()};
     return launch_air_path(e, e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), B / r, r, call.eot, n_max, (size_t)off[B],
-                           e->wav_off.as<int64_t>(), call.pt, call.K > 1 ? &cn : nullptr, call.stop, wav);
+                           e->wav_off.as<int64_t>(), call.pt, call.K > 1 ? &cn : nullptr, call.stop, wav, call.keep_air_sat);
   }
   FBCHK(e->wav_tf.ensure(sizeof(int16_t) * (size_t)off[B]));
   if (r == 1 && tf_noise_stages(e->tf, false) == 0) {
@@ -2325,7 +2334,8 @@ extern "C" int fb_attack_dev(fb_engine *e, const fb_nes_params *p, int S, const 
 // ------------------------------------------------- white-box gradients: fb_get_grad_wb / fb_attack_wb
 // The analytic gradient of the loss with respect to the samples ("white-box gradients" in fakebob_hip.h): GMM-UBM systems on
 // an undefended victim; with fb_set_wb_bpda(e, 1) through an input-transform chain, a codec and EOT replicas as well
-// (BPDA / EOT, the same contract); with fb_set_wb_ivector(e, 1) i-vector-PLDA systems too.  Everything else is refused by name.
+// (BPDA / EOT, the same contract); with fb_set_wb_ivector(e, 1) i-vector-PLDA systems too; with fb_set_wb_air(e, 1) through an
+// over-the-air channel.  Everything else is refused by name.
 static int wb_check(fb_engine *e, const fb_nes_params *p, const double *audio, int64_t N, fb_nes_params *q) {
   if (!e || !p || !audio) return fb_fail(FB_E_ARG, "null argument");
   if (!e->have_gmm) return fb_fail(FB_E_STATE, "no model loaded");
@@ -2338,8 +2348,8 @@ static int wb_check(fb_engine *e, const fb_nes_params *p, const double *audio, i
   if (e->comp_K1 > 0) return fb_fail(FB_E_STATE, "white-box gradients: companions are set (fb_set_companions: clear them)");
   if (e->tf.n > 0 && !e->wb_bpda)
     return fb_fail(FB_E_STATE, "white-box gradients: an input-transform chain is set (no BPDA through defences in this version)");
-  // (the channel's transpose is not in this version: refused with the switch on as well)
-  if (e->air.L > 0) return fb_fail(FB_E_STATE, "white-box gradients: an air channel is set (fb_set_air_channel: clear it)");
+  // (the channel's transpose is a switch of its own, fb_set_wb_air: refused with the other two on as well)
+  if (e->air.L > 0 && !e->wb_air) return fb_fail(FB_E_STATE, "white-box gradients: an air channel is set (fb_set_air_channel: clear it)");
   if (e->codec != FB_CODEC_NONE && !e->wb_bpda) return fb_fail(FB_E_STATE, "white-box gradients: a codec is set (fb_set_codec: clear it)");
   if (e->feco_iters > 0) return fb_fail(FB_E_STATE, "white-box gradients: feature compression is on (fb_set_feature_compression: switch it off)");
   if (e->cfg.dither > 0.0) return fb_fail(FB_E_STATE, "white-box gradients: dither %g > 0 (the function is differentiated at a fixed victim)", e->cfg.dither);
@@ -2396,6 +2406,10 @@ static int wb_prepare(fb_engine *e, int64_t N, int T, bool need_gmm) {
   FBCHK(e->wb_dxf.ensure(sizeof(double) * (size_t)T * fe.L));
   FBCHK(e->grad.ensure(sizeof(double) * (size_t)N));
   if (e->wb_bpda) FBCHK(e->wb_gj.ensure(sizeof(double) * (size_t)N));
+  if (e->wb_air && e->air.L > 0) {  // the r replicas' cotangents are kept for the one k_air_conv_t launch behind the loop
+    FBCHK(e->wb_air_cot.ensure(sizeof(double) * (size_t)e->eot * (size_t)N));
+    if (e->eot > 1) FBCHK(e->wb_air_dx.ensure(sizeof(double) * (size_t)e->eot * (size_t)N));
+  }
   if (!e->wb_status.p) FBCHK(e->wb_status.ensure(sizeof(int)));
   HIPCHK(hipMemsetAsync(e->wb_status.p, 0, sizeof(int), e->stream));
   return FB_OK;
@@ -2442,15 +2456,30 @@ static void wb_launch_frontend_vjp(fb_engine *e, const int16_t *wav, int j, int6
                             stop);
 }
 // the chain's transpose for replica j at the call's point: grad (+)= the vector-Jacobian product of cot through the chain
-// applied to the un-replicated row in e->wav (k_tf_power's sum of the forward is still in e->tf_power)
+// applied to the un-replicated row in e->wav (k_tf_power's sum of the forward is still in e->tf_power).  With an air channel
+// the chain read replica j's row of e->wav_air -- intact: a codec behind a chain runs in place on wav_tf -- and k_tf_power
+// summed the channel's output rows, so the row's sum is tf_power[j]; the noise counters are (utterance row 0, replica j)
+// either way (FbTfRnd::pre = r in the forward).
 static int wb_launch_chain_t(fb_engine *e, const FbRngPoint &pt, int j, int64_t N, const double *cot, double *grad, bool accumulate,
                              const int *stop) {
+  const bool air = e->air.L > 0;
   FbTfRnd rn = fb_tf_rnd(pt, e->eot);
-  rn.power = tf_noise_stages(e->tf, true) > 0 ? e->tf_power.as<unsigned long long>() : nullptr;
-  if (!fb_launch_wb_chain_t(e->stream, e->tf, e->tf_taps.as<double>(), e->wav.as<int16_t>(), N, rn, j, cot, grad, accumulate ? 1 : 0, stop))
+  rn.power = tf_noise_stages(e->tf, true) > 0 ? e->tf_power.as<unsigned long long>() + (air ? j : 0) : nullptr;
+  const int16_t *row = air ? e->wav_air.as<int16_t>() + (size_t)j * (size_t)N : e->wav.as<int16_t>();
+  if (!fb_launch_wb_chain_t(e->stream, e->tf, e->tf_taps.as<double>(), row, N, rn, j, cot, grad, accumulate ? 1 : 0, stop))
     return fb_fail(FB_E_HIP, "k_wb_chain_t: %zu bytes of LDS were refused", fb_wb_chain_t_lds_bytes(e->tf));
   e->wb_route[FB_WB_ROUTE_CHAIN_T] += 1;
   return FB_OK;
+}
+// the channel's transpose for all r replicas of the one row (fb_set_wb_air), ONE launch: the cotangents e->wb_air_cot [r][N] on
+// the channel's output, the forward's saturation bytes and the forward's own responses in e->air_taps -- nothing is redrawn --
+// give dx[r][N]; out (device, [N]) = their sum, j ascending (r = 1: k_air_conv_t writes out itself)
+static void wb_launch_air_t(fb_engine *e, int r, int64_t N, double *out, const int *stop) {
+  double *dx = r > 1 ? e->wb_air_dx.as<double>() : out;
+  fb_launch_air_conv_t(e->stream, e->wb_air_cot.as<double>(), e->wb_air_sat.as<unsigned char>(), r, N, e->air_taps.as<int16_t>(), e->air.L,
+                       dx, stop);
+  e->wb_air_launches += 1;
+  if (r > 1) fb_launch_air_sum_t(e->stream, dx, r, N, out, stop);
 }
 
 // One white-box iteration on the device-resident adver, asynchronous: the forward of fb_get_grad on ONE row -- the cast
@@ -2461,6 +2490,9 @@ static int wb_launch_chain_t(fb_engine *e, const FbRngPoint &pt, int j, int64_t 
 // backward on the row ITS front end read, the chain's transpose, which also adds replica j to e->grad (j ascending).
 // With fb_set_wb_ivector on and an i-vector system loaded (r = 1: wb_check): the same forward with a copy of quad kept, then
 // k_wb_iv_ctl and the i-vector back end's backward (wb_launch_iv_backend_t, wb_launch_iv_backward) in the GMM backward's place.
+// With fb_set_wb_air on and an air channel set: the forward keeps the channel's saturation bytes; replica j's cotangent on the
+// channel's output -- the front-end backward's, or behind a chain the chain transpose's, non-accumulating -- goes to slot j of
+// e->wb_air_cot, and behind the loop one k_air_conv_t launch over all r replicas and their ascending sum write e->grad.
 static int wb_enqueue(fb_engine *e, const fb_nes_params *q, int64_t N, uint32_t it, bool with_dist, FbCtlDev *ctl, double *trace_dev) {
   const int *stop = ctl ? &ctl->stop : nullptr;
   const int r = e->eot;  // (companions are refused: the replicas are the EOT draws)
@@ -2473,6 +2505,8 @@ static int wb_enqueue(fb_engine *e, const fb_nes_params *q, int64_t N, uint32_t 
   call.eot = r;
   call.stop = stop;
   call.keep_iv_quad = e->kind == 1;
+  const bool air = e->air.L > 0;  // (wb_check: only under fb_set_wb_air)
+  call.keep_air_sat = air;
   const int T = e->h_frame_off[1];
   FBCHK(run_scoring(e, call, r, e->h_frame_off[r]));
   const double scale = ldexp(1.0, nes_bits(q) - 1);
@@ -2488,7 +2522,9 @@ static int wb_enqueue(fb_engine *e, const fb_nes_params *q, int64_t N, uint32_t 
                    e->nes_out.as<FbNesDev>());
   }
   e->nes_route[FB_NES_ROUTE_K_LOSS] += 1;
-  const bool through_chain = e->tf.n > 0 || r > 1;  // (a codec alone is the identity: the front-end backward writes e->grad)
+  // (a codec alone is the identity: the front-end backward writes e->grad -- or, with a channel, its slot of e->wb_air_cot,
+  //  where the replicas are summed behind the channel's transpose and an empty chain has nothing to add)
+  const bool through_chain = e->tf.n > 0 || (r > 1 && !air);
   const int S = fb_num_speakers(e);
   for (int j = 0; j < r; ++j) {
     if (r > 1) {
@@ -2512,10 +2548,13 @@ static int wb_enqueue(fb_engine *e, const fb_nes_params *q, int64_t N, uint32_t 
     } else {
       wb_launch_gmm_backward(e, r > 1 ? e->tv.as<int>() + j : e->row_off.as<int>() + 1, T, stop, r > 1 ? e->row_off.as<int>() + j : nullptr);
     }
-    wb_launch_frontend_vjp(e, e->fe_wav, j, N, T, scale, through_chain ? e->wb_gj.as<double>() : e->grad.as<double>(), stop);
+    double *slot = air ? e->wb_air_cot.as<double>() + (size_t)j * (size_t)N : nullptr;  // replica j's cotangent on the channel's output
+    double *fe_out = through_chain ? e->wb_gj.as<double>() : air ? slot : e->grad.as<double>();
+    wb_launch_frontend_vjp(e, e->fe_wav, j, N, T, scale, fe_out, stop);
     e->wb_route[FB_WB_ROUTE_BACKWARD] += 1;
-    if (through_chain) FBCHK(wb_launch_chain_t(e, pt, j, N, e->wb_gj.as<double>(), e->grad.as<double>(), j > 0, stop));
+    if (through_chain) FBCHK(wb_launch_chain_t(e, pt, j, N, e->wb_gj.as<double>(), air ? slot : e->grad.as<double>(), !air && j > 0, stop));
   }
+  if (air) wb_launch_air_t(e, r, N, e->grad.as<double>(), stop);
   return FB_OK;
 }
 
@@ -2530,6 +2569,7 @@ extern "C" int fb_get_grad_wb_iter(fb_engine *e, const fb_nes_params *p, const d
   if (e) e->bench_it = -1;
   if (e) memset(e->nes_route, 0, sizeof(e->nes_route));
   if (e) memset(e->wb_route, 0, sizeof(e->wb_route));
+  if (e) e->wb_air_launches = 0;
   if (iter < 0) return fb_fail(FB_E_ARG, "iter must be >= 0");
   fb_nes_params q;
   FBCHK(wb_check(e, p, audio, N, &q));
@@ -2571,6 +2611,49 @@ extern "C" int fb_set_wb_ivector(fb_engine *e, int on) {
   e->wb_ivector = on;
   return FB_OK;
 }
+
+extern "C" int fb_set_wb_air(fb_engine *e, int on) {
+  if (!e) return fb_fail(FB_E_ARG, "null engine");
+  if (on != 0 && on != 1) return fb_fail(FB_E_ARG, "fb_set_wb_air takes 0 or 1, not %d", on);
+  e->wb_air = on;
+  return FB_OK;
+}
+
+// Test hook: k_air_conv_t alone, on taps, cotangents and saturation bytes handed in: B rows of n samples, one launch
+extern "C" int fb_debug_air_conv_t(fb_engine *e, const int16_t *taps, int B, int L, int64_t n, const double *cot, const unsigned char *sat,
+                                   double *dx) {
+  if (!e || !taps || !cot || !dx || B <= 0 || B > 65535 || L < 2 || L > 4096 || n <= 0) return fb_fail(FB_E_ARG, "bad argument");
+  if (n > 0x7fffffffLL) return fb_fail(FB_E_LIMIT, "row longer than 2^31 samples");
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  const size_t samples = (size_t)B * (size_t)n;
+  DevBuf d_t, d_cot, d_sat, d_dx;
+  FBCHK(d_t.ensure(sizeof(int16_t) * (size_t)B * (size_t)L));
+  FBCHK(d_cot.ensure(sizeof(double) * samples));
+  FBCHK(d_dx.ensure(sizeof(double) * samples));
+  FBCHK(h2d(e, d_t.p, taps, sizeof(int16_t) * (size_t)B * (size_t)L));
+  FBCHK(h2d(e, d_cot.p, cot, sizeof(double) * samples));
+  if (sat) {
+    FBCHK(d_sat.ensure(samples));
+    FBCHK(h2d(e, d_sat.p, sat, samples));
+  }
+  e->wb_air_launches = 0;
+  fb_launch_air_conv_t(e->stream, d_cot.as<double>(), sat ? d_sat.as<unsigned char>() : nullptr, B, n, d_t.as<int16_t>(), L, d_dx.as<double>(),
+                       nullptr);
+  e->wb_air_launches += 1;
+  HIPCHK(hipGetLastError());
+  FBCHK(d2h(e, dx, d_dx.p, sizeof(double) * samples));
+  FBCHK(sync_stream(e));
+  return FB_OK;
+}
+
+extern "C" int fb_debug_wb_air_route(fb_engine *e, int *n_launches) {
+  if (!e || !n_launches) return fb_fail(FB_E_ARG, "null argument");
+  *n_launches = e->wb_air_launches;
+  return FB_OK;
+}
+
+extern "C" int fb_debug_air_conv_t_chunk(void) { return fb_air_conv_t_chunk(); }
 
 // Test hook: k_wb_iv_backend_t alone, on an i-vector and weights handed in
 extern "C" int fb_debug_iv_backend_grad(fb_engine *e, const double *ivec, const double *w, double *out) {
@@ -2633,6 +2716,7 @@ extern "C" int fb_attack_wb(fb_engine *e, const fb_nes_params *p, const double *
   if (e) e->bench_it = -1;
   if (e) memset(e->nes_route, 0, sizeof(e->nes_route));
   if (e) memset(e->wb_route, 0, sizeof(e->wb_route));
+  if (e) e->wb_air_launches = 0;
   if (!adv_i16 || !success_flag) return fb_fail(FB_E_ARG, "null argument");
   fb_nes_params q;
   FBCHK(wb_check(e, p, audio, N, &q));
@@ -3900,12 +3984,14 @@ extern "C" int fb_debug_defence_vjp(fb_engine *e, const int16_t *wav, int64_t n,
                                     const double *cot, double *dwav, int16_t *out) {
   if (!e || !wav || !cot || !dwav || n <= 0 || iter < 0) return fb_fail(FB_E_ARG, "bad argument");
   if (n > 0x7fffffffLL) return fb_fail(FB_E_LIMIT, "utterance longer than 2^31 samples");
-  if (e->air.L > 0) return fb_fail(FB_E_STATE, "white-box gradients: an air channel is set (fb_set_air_channel: clear it)");
+  const bool air = e->air.L > 0;
+  if (air && !e->wb_air) return fb_fail(FB_E_STATE, "white-box gradients: an air channel is set (fb_set_air_channel: clear it)");
   if (e->comp_K1 > 0) return fb_fail(FB_E_STATE, "white-box gradients: companions are set (fb_set_companions: clear them)");
   if (num_frames(e->cfg, n) <= 0) return fb_fail(FB_E_ARG, "audio shorter than one frame");
   HIPCHK(hipSetDevice(e->device));
   e->bench_it = -1;
   memset(e->wb_route, 0, sizeof(e->wb_route));
+  e->wb_air_launches = 0;
   const int r = e->eot;
   FBCHK(prepare_nes_replicas(e, n, 1));
   FBCHK(e->wb_gj.ensure(sizeof(double) * (size_t)n));
@@ -3914,9 +4000,29 @@ extern "C" int fb_debug_defence_vjp(fb_engine *e, const int16_t *wav, int64_t n,
   const FbRngPoint pt{seed, stream, (uint32_t)iter, 0};
   FbScoreCall call{pt};
   call.eot = r;
+  call.keep_air_sat = air;
   const int16_t *res = nullptr;
   FBCHK(transformed_wav(e, call, e->h_wav_off.data(), r, &res));
   if (out) FBCHK(d2h(e, out, res, sizeof(int16_t) * (size_t)n * r));
+  if (air) {  // wb_enqueue's order: every replica's cotangent to its slot (through the chain's transpose when a chain is set),
+              // then the channel's transpose of all r in one launch; dwav row j = k_air_conv_t's row j, not the replicas' sum
+    const size_t bytes = sizeof(double) * (size_t)r * (size_t)n;
+    FBCHK(e->wb_air_cot.ensure(bytes));
+    FBCHK(e->wb_air_dx.ensure(bytes));
+    if (e->tf.n == 0) FBCHK(h2d(e, e->wb_air_cot.p, cot, bytes));
+    for (int j = 0; j < r && e->tf.n > 0; ++j) {
+      FBCHK(h2d(e, e->wb_gj.p, cot + (size_t)j * n, sizeof(double) * (size_t)n));
+      FBCHK(wb_launch_chain_t(e, pt, j, n, e->wb_gj.as<double>(), e->wb_air_cot.as<double>() + (size_t)j * (size_t)n, false, nullptr));
+      FBCHK(sync_stream(e));
+    }
+    fb_launch_air_conv_t(e->stream, e->wb_air_cot.as<double>(), e->wb_air_sat.as<unsigned char>(), r, n, e->air_taps.as<int16_t>(), e->air.L,
+                         e->wb_air_dx.as<double>(), nullptr);
+    e->wb_air_launches += 1;
+    FBCHK(d2h(e, dwav, e->wb_air_dx.p, bytes));
+    FBCHK(sync_stream(e));
+    HIPCHK(hipGetLastError());
+    return FB_OK;
+  }
   for (int j = 0; j < r; ++j) {
     FBCHK(h2d(e, e->wb_gj.p, cot + (size_t)j * n, sizeof(double) * (size_t)n));
     FBCHK(wb_launch_chain_t(e, pt, j, n, e->wb_gj.as<double>(), e->grad.as<double>(), false, nullptr));

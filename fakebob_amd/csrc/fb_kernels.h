@@ -124,9 +124,19 @@ static inline FbAir fb_air_key(const FbRngPoint &pt, const FbAir &set, int r = 1
 void fb_launch_air_taps(hipStream_t s, const FbAir &ac, int rep0, int rows, int16_t *taps, float *z, uint32_t *w, const int *stop);
 // out row R (at out_off[R]; R = 0 .. rows - 1) = row R / r of wav (in_off) -- with cn (nullable) utterance (R % r) / eot of
 // that row as composed -- convolved with taps[R][L]; n_max = the longest row.  Honours `stop`.
+// sat (nullable; laid out as out): one byte per output sample, 1 where the value before the clip lay outside the int16 range
+// (k_air_conv<true>; null: the kernel every caller took before the white-box path through the channel existed)
 void fb_launch_air_conv(hipStream_t s, const int16_t *wav, const int64_t *in_off, int rows, int r, int eot, int64_t n_max,
-                        const int16_t *taps, int L, int16_t *out, const int64_t *out_off, const FbTfComp *cn, const int *stop);
+                        const int16_t *taps, int L, int16_t *out, const int64_t *out_off, const FbTfComp *cn, const int *stop,
+                        unsigned char *sat = nullptr);
 size_t fb_air_conv_lds_bytes(int L);
+// the channel transposed (fb_set_wb_air; whitebox_air_kernels.hip): dx[rows][n] = 2^-14 * the correlation of cot[rows][n] --
+// zeroed where sat[rows][n] (nullable) is set -- with taps[rows][L], one launch for all rows; then grad[n] = the sum of the
+// r rows of dx, ascending.  Both honour `stop`.  fb_air_conv_t_chunk: samples of dx per workgroup.
+void fb_launch_air_conv_t(hipStream_t s, const double *cot, const unsigned char *sat, int rows, int64_t n, const int16_t *taps, int L,
+                          double *dx, const int *stop);
+void fb_launch_air_sum_t(hipStream_t s, const double *dx, int r, int64_t n, double *grad, const int *stop);
+int fb_air_conv_t_chunk(void);
 
 // ---- telephone-line codec (fb_set_codec; codec_kernel.hip) -------------------------------------------------------
 // out row R (at off[R], as in wav; R = 0 .. B - 1) = the round trip of row R of wav through codec `kind` (FB_CODEC_ULAW,

@@ -59,6 +59,7 @@ class Engine(object):
         self.eot = 1
         self.wb_bpda = False
         self.wb_ivector = False
+        self.wb_air = False
         self.companions = None
         self.feature_compression = None
 
@@ -535,6 +536,43 @@ class Engine(object):
         N.check(self._L.fb_set_wb_ivector(self._h, C.c_int(1 if on is True else 0 if on is False else int(on))))
         self.wb_ivector = bool(on)
 
+    def set_wb_air(self, on):
+        """fb_set_wb_air: with True, get_grad_wb and attack_wb differentiate through the over-the-air channel of
+        set_air_channel -- the forward's own drawn responses transposed, a saturated output passing zero; with set_eot(r) the
+        EOT-over-rooms gradient (the rules are in include/fakebob_hip.h).  A chain, a codec and r > 1 still need
+        set_wb_bpda(True), an i-vector system set_wb_ivector(True).  False (as created): a channel is refused and nothing else
+        changes.  0 / 1 and booleans only; anything else is handed to the library, which refuses it."""
+        N.check(self._L.fb_set_wb_air(self._h, C.c_int(1 if on is True else 0 if on is False else int(on))))
+        self.wb_air = bool(on)
+
+    def debug_air_conv_t(self, taps, cot, sat=None):
+        """k_air_conv_t alone (fb_debug_air_conv_t): int16 taps (B, L) -- or (L,) for one row --, float64 cotangents (B, n) and
+        (optional) saturation bytes (B, n) -> dx (B, n) float64 = 2^-14 * the correlation of the masked cotangent with the
+        row's taps, all rows in one launch."""
+        taps = np.ascontiguousarray(taps, np.int16)
+        taps = taps.reshape(1, -1) if taps.ndim == 1 else taps
+        cot = np.ascontiguousarray(cot, np.float64)
+        cot = cot.reshape(1, -1) if cot.ndim == 1 else cot
+        if cot.shape[0] != taps.shape[0]:
+            raise ValueError("%d responses for %d rows" % (taps.shape[0], cot.shape[0]))
+        if sat is not None:
+            sat = np.ascontiguousarray(sat, np.uint8).reshape(cot.shape)
+        dx = np.empty_like(cot)
+        N.check(self._L.fb_debug_air_conv_t(self._h, N.ptr(taps), C.c_int(taps.shape[0]), C.c_int(taps.shape[1]),
+                                            C.c_int64(cot.shape[1]), N.ptr(cot), None if sat is None else N.ptr(sat), N.ptr(dx)))
+        return dx
+
+    def debug_air_conv_t_chunk(self):
+        """Samples of dx one workgroup of k_air_conv_t computes (fb_debug_air_conv_t_chunk)."""
+        return int(self._L.fb_debug_air_conv_t_chunk())
+
+    def debug_wb_air_route(self):
+        """k_air_conv_t launches of the last get_grad_wb / attack_wb / debug_defence_vjp / debug_air_conv_t call
+        (fb_debug_wb_air_route): one per iteration whatever the EOT size, none without a channel."""
+        n = C.c_int(0)
+        N.check(self._L.fb_debug_wb_air_route(self._h, C.byref(n)))
+        return int(n.value)
+
     def get_grad_wb(self, params, audio, want_grad=True):
         """fb_get_grad_wb: get_grad_wb_iter at iter = 0."""
         return self.get_grad_wb_iter(params, audio, 0, want_grad)
@@ -545,7 +583,8 @@ class Engine(object):
         samples_per_draw and sigma are not read; seed, stream and `iter` (the epoch of the draws, as get_grad's `it`) key the
         random stages of a defended victim.  Refused (NativeError, FB_E_STATE) for i-vector systems and while an air channel,
         feature compression, dither or companions are set; an input transform, a codec and EOT only after set_wb_bpda(True).
-        After set_wb_ivector(True) an i-vector system is differentiated as well (never with set_eot > 1)."""
+        After set_wb_ivector(True) an i-vector system is differentiated as well (never with set_eot > 1); after
+        set_wb_air(True) an air channel is too (the forward's drawn responses transposed)."""
         audio = np.ascontiguousarray(audio, np.float64).reshape(-1)
         n = audio.size
         grad = np.empty(n, np.float64) if want_grad else None

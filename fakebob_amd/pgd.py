@@ -6,9 +6,10 @@ The loop is FakeBob.attack's (FAKEBOB.py:139-221) with the analytic gradient of 
 stop on adver_loss < 0.  momentum = 0 is plain PGD with the margin loss; max_iter = 1 is the single-step attack.  There
 is no random start, so a run is reproducible.  PGD's victim has to be undefended.  AdaptivePGD is the adaptive attack on a
 defended one (Engine.set_wb_bpda): BPDA through the model's input-transform chain and codec, and with eot_size = r > 1 an
-expectation over r draws of its random stages per iteration, keyed by the attack's seed and stream.  The air channel,
-feature compression, dither and companions stay refused, as are i-vector systems and foreign models -- the gradient is
-that of this library's own forward.  IvectorPGD is the same attack on an i-vector-PLDA system (Engine.set_wb_ivector): the
+expectation over r draws of its random stages per iteration, keyed by the attack's seed and stream.  The air channel is
+refused unless air=True (Engine.set_wb_air: the gradient through the drawn rooms, with eot_size = r the EOT-over-rooms
+gradient of the robust over-the-air attack); feature compression, dither and companions stay refused, as are i-vector
+systems and foreign models -- the gradient is that of this library's own forward.  IvectorPGD is the same attack on an i-vector-PLDA system (Engine.set_wb_ivector): the
 gradient through the PLDA back end, both length normalisations, the posterior solve and the full-covariance posteriors, with
 the frames' component selection and pruned sets held constant; PGD and AdaptivePGD keep refusing such a system.
 """
@@ -35,6 +36,7 @@ class PGD(object):
         if getattr(model.engine, "kind", "gmm") not in self.KINDS:
             raise ValueError("PGD: i-vector systems are out of this version (GMM-UBM systems only)")
         self.bpda = False   # (AdaptivePGD: True -- the engine's switch is on and seed / stream key the victim's draws)
+        self.air = False    # (air=True of AdaptivePGD / IvectorPGD: Engine.set_wb_air is on; seed / stream key the rooms)
         self.eot_size = 1
         self.task = task
         self.attack_type = attack_type
@@ -82,8 +84,8 @@ class PGD(object):
         return nes_params(self.task, self.attack_type, adver_thresh=self.adver_thresh, epsilon=self.epsilon,
                           max_iter=self.max_iter, max_lr=self.max_lr, min_lr=self.min_lr, samples_per_draw=0, sigma=0.0,
                           momentum=self.momentum, plateau_length=self.plateau_length, plateau_drop=self.plateau_drop,
-                          threshold=self.threshold, target=self.target, true=self.true, seed=self.seed if self.bpda else 0,
-                          stream=self._stream if self.bpda else 0, bits_per_sample=bits_per_sample)
+                          threshold=self.threshold, target=self.target, true=self.true, seed=self.seed if (self.bpda or self.air) else 0,
+                          stream=self._stream if (self.bpda or self.air) else 0, bits_per_sample=bits_per_sample)
 
     def get_grad(self, audio, fs=16000, bits_per_sample=16, n_jobs=10, debug=False):
         """-> (grad (N,1) = d loss / d audio, adver_loss (1,), score), the analytic twin of FakeBob.get_grad's last three."""
@@ -126,9 +128,11 @@ class AdaptivePGD(PGD):
     engine to differentiate through the model's input-transform chain and codec (Engine.set_wb_bpda; the derivative rules are
     in include/fakebob_hip.h), eot_size = r takes the mean loss and gradient over r draws of the random stages per iteration
     (Engine.set_eot).  Everything else -- knobs, attack(), get_grad(), return pair, checkpoint layout -- is PGD's.  The
-    constructor sets both on the model's engine and they stay set; bpda=False with eot_size=1 is PGD itself."""
+    constructor sets both on the model's engine and they stay set; bpda=False with eot_size=1 is PGD itself.  air=True also
+    switches the engine to differentiate through the model's over-the-air channel (Engine.set_wb_air): each iteration then
+    takes the gradient through the eot_size rooms its forward drew."""
 
-    def __init__(self, task, attack_type, model, bpda=True, eot_size=1, **kw):
+    def __init__(self, task, attack_type, model, bpda=True, eot_size=1, air=False, **kw):
         eot_size = int(eot_size)
         if not 1 <= eot_size <= 32:
             raise ValueError("AdaptivePGD: eot_size %d outside 1 .. 32" % eot_size)
@@ -141,19 +145,26 @@ class AdaptivePGD(PGD):
         if self.bpda:  # (left alone otherwise: the engine's own refusals then name what is set)
             model.engine.set_eot(eot_size)
             model.engine.set_wb_bpda(True)
+        self.air = bool(air)
+        if self.air:
+            model.engine.set_wb_air(True)
 
 
 class IvectorPGD(PGD):
     """PGD on an i-vector-PLDA victim (and, unchanged, on a GMM-UBM one).  The constructor switches the model's engine to
     differentiate through the i-vector back end (Engine.set_wb_ivector; the rules are in include/fakebob_hip.h) and, with
     bpda=True, through an input-transform chain and a codec as well (Engine.set_wb_bpda); both stay set.  There is no
-    expectation over transformation for an i-vector system.  Knobs, attack(), get_grad(), estimate_threshold(), the return
-    pair and the checkpoint layout are PGD's."""
+    expectation over transformation for an i-vector system.  air=True: through the model's over-the-air channel too
+    (Engine.set_wb_air), one room per iteration.  Knobs, attack(), get_grad(), estimate_threshold(), the return pair and the
+    checkpoint layout are PGD's."""
     KINDS = ("gmm", "iv")
 
-    def __init__(self, task, attack_type, model, bpda=False, **kw):
+    def __init__(self, task, attack_type, model, bpda=False, air=False, **kw):
         PGD.__init__(self, task, attack_type, model, **kw)
         self.bpda = bool(bpda)
         model.engine.set_wb_ivector(True)
         if self.bpda:
             model.engine.set_wb_bpda(True)
+        self.air = bool(air)
+        if self.air:
+            model.engine.set_wb_air(True)

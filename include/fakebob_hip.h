@@ -557,7 +557,7 @@ int fb_attack_kenansville(fb_engine *e, const fb_nes_params *p, const fb_kv_para
  * above stands.  With 1, fb_get_grad_wb, fb_get_grad_wb_iter and fb_attack_wb accept an input-transform chain (all five stage
  * kinds), a codec, fb_set_eot(r), 1 <= r <= 32, and any combination; with nothing of these set they queue exactly the
  * launches of the undefended call.  Still FB_E_STATE with the switch on, the cause named: an i-vector system, companions,
- * feature compression, dither > 0 -- and an AIR CHANNEL: the transpose of the drawn room response is not in this version.
+ * feature compression, dither > 0 -- and an AIR CHANNEL: refused unless fb_set_wb_air ("The over-the-air channel", below).
  * fb_get_grad_wb_iter is fb_get_grad_wb with the epoch of the random draws given: `iter` (>= 0) means what fb_get_grad's
  * iter means in the noise RNG contract; fb_get_grad_wb is iter = 0; fb_attack_wb draws with its loop index, as fb_attack
  * does.  p->seed and p->stream key the draws.
@@ -586,6 +586,27 @@ int fb_attack_kenansville(fb_engine *e, const fb_nes_params *p, const fb_kv_para
  *                                this version.
  * No floating-point atomics and a fixed order in every sum: the same call on a fresh engine gives the same bits.  The
  * 2^(bits_per_sample - 1) scale and the units of grad are unchanged.
+ * The over-the-air channel (fb_set_wb_air).  The gradient of the loss through the drawn room -- with fb_set_eot(r) the EOT-over-
+ * rooms gradient of the robust over-the-air attack -- behind a third switch: fb_set_wb_air(e, on), on = 0 or 1 (anything else:
+ * FB_E_ARG, the setting stays), 0 at engine creation, kept across fb_load_*.  With 0 every call, launch, value and refusal
+ * message is what it was before the switch existed: an air channel is refused whatever the other two switches say.  With 1,
+ * fb_get_grad_wb, fb_get_grad_wb_iter and fb_attack_wb accept an air channel: a GMM-UBM system in any combination the BPDA
+ * switch allows -- the channel alone needs no other switch; a chain, a codec and fb_set_eot(r > 1) still need
+ * fb_set_wb_bpda(e, 1) --, an i-vector system under fb_set_wb_ivector(e, 1), at r = 1 only, as without a channel.  Companions,
+ * feature compression and dither stay refused, by name; with no channel set the calls queue exactly the launches they
+ * queued before.
+ * Forward.  The engine's own, unchanged: cast, air channel, chain, codec, front end.  adver_loss and score0 are bit for bit
+ * fb_get_grad's at samples_per_draw = 0 with the same iter, seed, stream and settings.
+ * Backward.  Replica j of the one row runs the front-end backward, (codec: the identity), (the chain transposed: on the row the
+ * chain read, the channel's output row j, with that row's SNR power and the noise counters of (utterance row 0, replica j)),
+ * then the channel transposed.  The taps t_j[0 .. L) are the forward's own draw for (epoch, row 0, replica j) and are
+ * constants.  Rounding and the shift are the identity.  An output whose value (y[i] + 8192) >> 14, before the clip, lies
+ * outside [-32768, 32767] passes zero -- the saturation rule above, decided on the exact integer y (a sample AT a rail that
+ * was not clipped passes).  With g_j the cotangent on the channel's output, saturated positions zeroed,
+ *     dx_j[m] = 2^-14 * sum_{k = 0 .. min(L - 1, n - 1 - m)} t_j[k] * g_j[m + k]
+ * in float64 on the matrix cores (k_air_conv_t); the order of the sum over k is the kernel's: fixed, not specified.  Then
+ *     grad = sum_j dx_j, j ascending, float64.
+ * No floating-point atomics: the same call on a fresh engine gives the same bits.
  *
  * The i-vector-PLDA victim (fb_set_wb_ivector).  A second switch, for the same reason as the first: fb_set_wb_ivector(e, on),
  * on = 0 or 1 (anything else: FB_E_ARG, the setting stays), 0 at engine creation, kept across fb_load_*.  With 0 every call,
@@ -615,12 +636,13 @@ int fb_attack_kenansville(fb_engine *e, const fb_nes_params *p, const fb_kv_para
  *     xbar_t = sum_k gamma_tk Fbar_k + sum_k llbar_tk (Sigma_k^-1 mu_k - Sigma_k^-1 x_t);
  * then the front-end backward above, unchanged.  adver_loss and score0 are bit for bit fb_get_grad's at samples_per_draw = 0:
  * the same scoring call.  fb_attack_wb is the same loop, trace layout and stop test.
- * Refused for an i-vector system with the switch on, FB_E_STATE, the cause named: companions, an air channel, feature
+ * Refused for an i-vector system with the switch on, FB_E_STATE, the cause named: companions, an air channel (unless fb_set_wb_air), feature
  * compression, dither > 0, and fb_set_eot(r > 1) -- the last with fb_set_wb_bpda on as well ("i-vector", "fb_set_eot": the
  * forward keeps one row's i-vector state, not r replicas').  An input-transform chain and a codec need fb_set_wb_bpda(e, 1), as
  * for a GMM-UBM system, and are then taken at r = 1.  FB_E_NO_VOICED and the "not positive definite" error are scoring's. */
 int fb_set_wb_bpda(fb_engine *e, int on);
 int fb_set_wb_ivector(fb_engine *e, int on);
+int fb_set_wb_air(fb_engine *e, int on);
 int fb_get_grad_wb_iter(fb_engine *e, const fb_nes_params *p, const double *audio, int64_t N, int iter, double *adver_loss,
                         double *grad /*[N], nullable*/, double *score0 /*[S]*/);
 int fb_get_grad_wb(fb_engine *e, const fb_nes_params *p, const double *audio, int64_t N, double *adver_loss,

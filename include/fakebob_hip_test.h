@@ -318,7 +318,9 @@ int fb_debug_frontend_vjp(fb_engine *e, const int16_t *wav, int64_t n, const dou
  * cotangent cot[j][n] (on the row the front end would read) through codec and chain of replica j, by the derivative rules of the
  * contract; out[j][n] (nullable) = the transformed row the front end would read.  It runs exactly the launches an attack
  * iteration runs for this stage (an empty chain copies).  The switch need not be on.  FB_E_STATE with an air channel or
- * companions set.
+ * companions set.  With fb_set_wb_air(e, 1), and only then, an air channel is accepted: the forward is channel, chain, codec,
+ * out[j] still the row the front end would read, and dwav[j] = cot[j] through codec, chain (when one is set) and the channel
+ * of replica j -- k_air_conv_t's row j, all r in the one launch an iteration runs.
  * fb_debug_wb_route: info[FB_WB_ROUTE_N] counts the launches of the white-box backward the last fb_get_grad_wb* /
  * fb_attack_wb / fb_debug_defence_vjp call enqueued, recorded on the host as fb_debug_nes_route's are. */
 #define FB_WB_ROUTE_CTL 0        /* k_wb_ctl: weights from the scores of the one row (+ loop control) */
@@ -334,6 +336,20 @@ int fb_debug_frontend_vjp(fb_engine *e, const int16_t *wav, int64_t n, const dou
 int fb_debug_defence_vjp(fb_engine *e, const int16_t *wav, int64_t n, uint64_t seed, uint32_t stream, int iter,
                          const double *cot /*[r][n]*/, double *dwav /*[r][n]*/, int16_t *out /*[r][n], nullable*/);
 int fb_debug_wb_route(fb_engine *e, int *info);
+
+/* White-box gradients through the over-the-air channel (fakebob_hip.h: fb_set_wb_air).
+ * fb_debug_air_conv_t: k_air_conv_t alone, ONE launch, on taps handed in as they are -- taps[B][L] int16, any values, L in
+ * 2 .. 4096 -- over B rows of n >= 1 samples each: dx[B][n] = 2^-14 * the correlation of cot[B][n] (float64), zeroed where
+ * sat[B][n] is non-zero (nullable: nothing saturated), with the row's taps.  The engine's settings are neither used nor changed.
+ * fb_debug_air_conv_t_chunk: the samples of dx one workgroup of k_air_conv_t computes (row lengths around its multiples are
+ * the kernel's edges).
+ * fb_debug_wb_air_route: *n_launches = the k_air_conv_t launches the last fb_get_grad_wb* / fb_attack_wb /
+ * fb_debug_defence_vjp / fb_debug_air_conv_t call enqueued -- one per iteration whatever r, none without a channel.  (It is
+ * not an index of fb_debug_wb_route: FB_WB_ROUTE_N stays 9.) */
+int fb_debug_air_conv_t(fb_engine *e, const int16_t *taps /*[B][L]*/, int B, int L, int64_t n, const double *cot /*[B][n]*/,
+                        const unsigned char *sat /*[B][n], nullable*/, double *dx /*[B][n]*/);
+int fb_debug_air_conv_t_chunk(void);
+int fb_debug_wb_air_route(fb_engine *e, int *n_launches);
 
 /* White-box gradients through the i-vector-PLDA back end (fakebob_hip.h: fb_set_wb_ivector).  Both hooks need a loaded i-vector
  * system (FB_E_STATE otherwise) and run whatever the switch says, with exactly the launches an attack iteration runs for
