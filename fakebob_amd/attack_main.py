@@ -205,11 +205,15 @@ def main(argv=None, model_factory=None, bob_factory=None):
     ap.add_argument("--bpda", action="store_true",
                     help="--attack pgd: the adaptive attack on a defended victim -- BPDA through --input-transform and --codec, "
                          "expectation over --eot-size draws of the random stages; --air-channel is refused unless --wb-air is "
-                         "given, --feco, --dither and --companions stay refused")
+                         "given, --feco and --dither unless --wb-frontend is given; --companions stay refused")
     ap.add_argument("--wb-air", dest="wb_air", action="store_true",
                     help="--attack pgd: differentiate through --air-channel as well (fakebob_amd/pgd.py: air=True; the forward's "
                          "drawn room responses transposed, with --bpda --eot-size r the expectation over r rooms per iteration); "
                          "on a GMM-UBM system with --bpda, on -archi iv with --wb-ivector")
+    ap.add_argument("--wb-frontend", dest="wb_frontend", action="store_true",
+                    help="--attack pgd: differentiate through --feco and --dither as well (fakebob_amd/pgd.py: frontend=True; the "
+                         "forward's final k-means assignment and its dither draws held constant, with --bpda --eot-size r the "
+                         "expectation over r draws per iteration); needs no other switch at --eot-size 1")
     ap.add_argument("--wb-ivector", dest="wb_ivector", action="store_true",
                     help="--attack pgd -archi iv: differentiate the i-vector-PLDA victim (fakebob_amd/pgd.py: IvectorPGD; the "
                          "frames' component selection and pruned sets held constant); never under --eot-size > 1")
@@ -248,6 +252,8 @@ def main(argv=None, model_factory=None, bob_factory=None):
         ap.error("--wb-ivector belongs to --attack pgd (--attack %s)" % args.attack)
     if args.wb_air and args.attack != "pgd":
         ap.error("--wb-air belongs to --attack pgd (--attack %s)" % args.attack)
+    if args.wb_frontend and args.attack != "pgd":
+        ap.error("--wb-frontend belongs to --attack pgd (--attack %s)" % args.attack)
     if args.attack == "pgd":      # likewise: the gradient is that of a GMM-UBM victim, undefended unless --bpda is given
         if args.architecture == "iv" and args.wb_ivector and args.eot_size is not None and args.eot_size > 1:
             ap.error("--attack pgd --wb-ivector does not run under expectation over transformation (--eot-size %d: an i-vector "
@@ -263,6 +269,8 @@ def main(argv=None, model_factory=None, bob_factory=None):
         for flag, val in (("--input-transform", args.input_transform), ("--air-channel", args.air_channel),
                           ("--codec", None if args.codec == "none" else args.codec), ("--feco", args.feco), ("--dither", args.dither)):
             if flag == "--air-channel" and val is not None and args.wb_air and (args.wb_ivector if args.architecture == "iv" else args.bpda):
+                continue
+            if flag in ("--feco", "--dither") and args.wb_frontend:
                 continue
             if val is not None and not (args.bpda and flag in ("--input-transform", "--codec")):
                 ap.error("--attack pgd attacks an undefended victim: %s %s is not differentiated in this version" % (flag, val))
@@ -319,12 +327,16 @@ def main(argv=None, model_factory=None, bob_factory=None):
             hp.pop("eot_size", None)
         if args.wb_air:
             hp.update(air=True)
+        if args.wb_frontend:
+            hp.update(frontend=True)
+            if not args.bpda and not args.wb_ivector:  # (AdaptivePGD's default is bpda=True)
+                hp.update(bpda=False)
     if bob_factory is None and args.attack == "pgd" and args.wb_ivector:
         from .pgd import IvectorPGD
         bobs = [IvectorPGD(task, attack_type, m, seed=seed, verbose=False, **hp) for m in models]
     elif bob_factory is None and args.attack == "pgd":
         from .pgd import PGD, AdaptivePGD
-        bobs = [(AdaptivePGD if args.bpda else PGD)(task, attack_type, m, seed=seed, verbose=False, **hp) for m in models]
+        bobs = [(AdaptivePGD if (args.bpda or args.wb_frontend) else PGD)(task, attack_type, m, seed=seed, verbose=False, **hp) for m in models]
     elif bob_factory is None and args.attack == "kenansville":
         from .kenansville import Kenansville
         bobs = [Kenansville(task, attack_type, m, seed=seed, verbose=False, **hp) for m in models]

@@ -236,6 +236,13 @@ struct fb_engine {
   DevBuf wb_air_cot, wb_air_dx;        // the replicas' cotangents on the channel's output [r][N], k_air_conv_t's output [r][N] (r > 1)
   DevBuf wb_air_sat;                   // the forward's saturation bytes, laid out as wav_air (k_air_conv<true>)
   int wb_air_launches = 0;             // k_air_conv_t launches of the last call (fb_debug_wb_air_route)
+  // white-box gradients through feature compression and dither (fb_set_wb_frontend)
+  int wb_frontend = 0;                 // the switch: 0 (as created) refuses both, as before it existed
+  DevBuf wb_feco_label, wb_feco_cnt;   // the forward's final assignment: label per voiced row (laid out as feats_fc after the swap: the
+                                       // input rows), member count per centre (laid out as feats: the centres)
+  DevBuf wb_feco_k;                    // ... and k per replicated row: the rows the back end scored
+  DevBuf wb_xbar;                      // k_wb_feco_t's output [T][dim]: the cotangent on one replica's voiced rows
+  int wb_feco_launches = 0;            // k_wb_feco_t launches of the last call (fb_debug_wb_feco_route)
   FbNesDev *h_out = nullptr;  // pinned
   int *h_tv = nullptr;        // pinned, grows
   size_t h_tv_cap = 0;
@@ -812,6 +819,7 @@ struct FbScoreCall {
   bool feats_given = false;      // e->feats / e->row_off / e->tv already hold the batch's rows: no front end (fb_debug_iv_feat_grad)
   bool keep_iv_quad = false;     // i-vector systems: row 0 of quad as the contraction left it is copied to e->wb_iv_quad (white box)
   bool keep_air_sat = false;     // an air channel: k_air_conv also writes its saturation bytes to e->wb_air_sat (white box)
+  bool keep_feco = false;        // feature compression: k_feature_compress also writes its final labels, counts and k's to e->wb_feco_* (white box)
   int replicas() const { return K * eot; }
 };
 // The replicating / composing transform launch: rn.r replicas of every utterance of `in` (in_off[B_in + 1]; longest: n_max) --
@@ -1023,8 +1031,15 @@ static int feature_compress(fb_engine *e, const FbScoreCall &call, int B, int to
   FBCHK(e->row_off_fc.ensure(sizeof(int) * (size_t)(B + 1)));
   FBCHK(e->feco_ws.ensure(sizeof(int) * (size_t)FB_FECO_WS_INTS * (size_t)(total_frames > 0 ? total_frames : 1)));
   const FbFeco fc = fb_feco_key(call.pt, e->feco_ratio, e->feco_iters, call.replicas());
+  if (call.keep_feco) {  // (FbScoreCall::keep_feco: the white-box call; k <= T per row, so the counts fit a buffer of the labels' size)
+    FBCHK(e->wb_feco_label.ensure(sizeof(int) * (size_t)(total_frames > 0 ? total_frames : 1)));
+    FBCHK(e->wb_feco_cnt.ensure(sizeof(int) * (size_t)(total_frames > 0 ? total_frames : 1)));
+    FBCHK(e->wb_feco_k.ensure(sizeof(int) * (size_t)B));
+  }
   if (!fb_launch_feature_compress(e->stream, fc, D, e->feats.as<float>(), e->row_off.as<int>(), B, e->t_max,
-                                  e->feats_fc.as<float>(), e->row_off_fc.as<int>(), e->feco_ws.as<int>(), call.stop))
+                                  e->feats_fc.as<float>(), e->row_off_fc.as<int>(), e->feco_ws.as<int>(), call.stop,
+                                  call.keep_feco ? e->wb_feco_label.as<int>() : nullptr, call.keep_feco ? e->wb_feco_cnt.as<int>() : nullptr,
+                                  call.keep_feco ? e->wb_feco_k.as<int>() : nullptr))
     return fb_fail(FB_E_HIP, "k_feature_compress: the dynamic-LDS opt-in failed");
   std::swap(e->feats, e->feats_fc);
   std::swap(e->row_off, e->row_off_fc);
@@ -2335,7 +2350,7 @@ extern "C" int fb_attack_dev(fb_engine *e, const fb_nes_params *p, int S, const 
 // The analytic gradient of the loss with respect to the samples ("white-box gradients" in fakebob_hip.h): GMM-UBM systems on
 // an undefended victim; with fb_set_wb_bpda(e, 1) through an input-transform chain, a codec and EOT replicas as well
 // (BPDA / EOT, the same contract); with fb_set_wb_ivector(e, 1) i-vector-PLDA systems too; with fb_set_wb_air(e, 1) through an
-// over-the-air channel.  Everything else is refused by name.
+// over-the-air channel; with fb_set_wb_frontend(e, 1) through feature compression and dither.  Everything else is refused by name.
 static int wb_check(fb_engine *e, const fb_nes_params *p, const double *audio, int64_t N, fb_nes_params *q) {
   if (!e || !p || !audio) return fb_fail(FB_E_ARG, "null argument");
   if (!e->have_gmm) return fb_fail(FB_E_STATE, "no model loaded");
@@ -2351,8 +2366,10 @@ static int wb_check(fb_engine *e, const fb_nes_params *p, const double *audio, i
   // (the channel's transpose is a switch of its own, fb_set_wb_air: refused with the other two on as well)
   if (e->air.L > 0 && !e->wb_air) return fb_fail(FB_E_STATE, "white-box gradients: an air channel is set (fb_set_air_channel: clear it)");
   if (e->codec != FB_CODEC_NONE && !e->wb_bpda) return fb_fail(FB_E_STATE, "white-box gradients: a codec is set (fb_set_codec: clear it)");
-  if (e->feco_iters > 0) return fb_fail(FB_E_STATE, "white-box gradients: feature compression is on (fb_set_feature_compression: switch it off)");
-  if (e->cfg.dither > 0.0) return fb_fail(FB_E_STATE, "white-box gradients: dither %g > 0 (the function is differentiated at a fixed victim)", e->cfg.dither);
+  // (feature compression and dither have the fourth switch, fb_set_wb_frontend: refused with the other three on as well)
+  if (e->feco_iters > 0 && !e->wb_frontend)
+    return fb_fail(FB_E_STATE, "white-box gradients: feature compression is on (fb_set_feature_compression: switch it off)");
+  if (e->cfg.dither > 0.0 && !e->wb_frontend) return fb_fail(FB_E_STATE, "white-box gradients: dither %g > 0 (the function is differentiated at a fixed victim)", e->cfg.dither);
   // one row is scored per iteration; of the NES-only fields seed and stream key the draws of a randomised defence
   *q = *p;
   q->samples_per_draw = 0;
@@ -2410,6 +2427,12 @@ static int wb_prepare(fb_engine *e, int64_t N, int T, bool need_gmm) {
     FBCHK(e->wb_air_cot.ensure(sizeof(double) * (size_t)e->eot * (size_t)N));
     if (e->eot > 1) FBCHK(e->wb_air_dx.ensure(sizeof(double) * (size_t)e->eot * (size_t)N));
   }
+  if (e->wb_frontend && e->feco_iters > 0) {  // the r replicas' kept assignments, and one replica's cotangent on its voiced rows
+    FBCHK(e->wb_feco_label.ensure(sizeof(int) * (size_t)e->eot * (size_t)T));
+    FBCHK(e->wb_feco_cnt.ensure(sizeof(int) * (size_t)e->eot * (size_t)T));
+    FBCHK(e->wb_feco_k.ensure(sizeof(int) * (size_t)e->eot));
+    FBCHK(e->wb_xbar.ensure(sizeof(double) * (size_t)T * fe.dim));
+  }
   if (!e->wb_status.p) FBCHK(e->wb_status.ensure(sizeof(int)));
   HIPCHK(hipMemsetAsync(e->wb_status.p, 0, sizeof(int), e->stream));
   return FB_OK;
@@ -2448,12 +2471,22 @@ static void wb_launch_iv_backward(fb_engine *e, const int *n_rows_ptr, int T, co
   e->wb_route[FB_WB_ROUTE_IV_POST_T] += 1;
 }
 // the front-end backward of row j of the batch the front end read (`wav`: rows of N samples, T frames each, their MFCC
-// matrices in e->mfcc): out = scale * the cotangent on that row's int16 samples
-static void wb_launch_frontend_vjp(fb_engine *e, const int16_t *wav, int j, int64_t N, int T, double scale, double *out, const int *stop) {
+// matrices in e->mfcc): out = scale * the cotangent on that row's int16 samples.  cot (null: e->wb_g): the cotangent on the
+// row's voiced rows; dk (nullable): the forward's dither key with the row's utterance index (fb_set_wb_frontend)
+static void wb_launch_frontend_vjp(fb_engine *e, const int16_t *wav, int j, int64_t N, int T, double scale, double *out, const int *stop,
+                                   const double *cot = nullptr, const FbDitherKey *dk = nullptr) {
   fb_launch_wb_frontend_vjp(e->stream, e->fe, wav + (size_t)j * (size_t)N, N, T, e->mfcc.as<float>() + (size_t)j * T * e->fe.nc,
-                            e->wb_g.as<double>(), e->tv.as<int>() + j, e->wb_rank.as<int>(), e->wb_dcm.as<double>(),
+                            cot ? cot : e->wb_g.as<double>(), e->tv.as<int>() + j, e->wb_rank.as<int>(), e->wb_dcm.as<double>(),
                             e->wb_ddf.as<double>(), e->wb_dmf.as<double>(), e->wb_dxf.as<double>(), scale, out, e->wb_status.as<int>(),
-                            stop);
+                            stop, dk);
+}
+// feature compression transposed for replica j of the batch the forward just scored (fb_set_wb_frontend): the cotangent on its
+// k_j centres in e->wb_g goes back to its voiced rows in e->wb_xbar under the assignment the forward kept.  After the swap in
+// feature_compress e->row_off holds the centres' offsets and e->row_off_fc the voiced rows'.
+static void wb_launch_feco_t(fb_engine *e, int j, int T, const int *stop) {
+  fb_launch_wb_feco_t(e->stream, e->fe.dim, e->wb_feco_label.as<int>(), e->wb_feco_cnt.as<int>(), e->row_off_fc.as<int>(),
+                      e->row_off.as<int>(), j, 1, T, false, e->wb_g.as<double>(), e->wb_xbar.as<double>(), stop);
+  e->wb_feco_launches += 1;
 }
 // the chain's transpose for replica j at the call's point: grad (+)= the vector-Jacobian product of cot through the chain
 // applied to the un-replicated row in e->wav (k_tf_power's sum of the forward is still in e->tf_power).  With an air channel
@@ -2493,6 +2526,9 @@ static void wb_launch_air_t(fb_engine *e, int r, int64_t N, double *out, const i
 // With fb_set_wb_air on and an air channel set: the forward keeps the channel's saturation bytes; replica j's cotangent on the
 // channel's output -- the front-end backward's, or behind a chain the chain transpose's, non-accumulating -- goes to slot j of
 // e->wb_air_cot, and behind the loop one k_air_conv_t launch over all r replicas and their ascending sum write e->grad.
+// With fb_set_wb_frontend on: under feature compression the forward keeps every replica's final labels, counts and k; the back
+// end's backward runs on replica j's k_j centres and k_wb_feco_t takes its cotangent back to the voiced rows (e->wb_xbar), which
+// the front-end backward then reads; under dither the front-end backward gets the forward's key with utterance index j.
 static int wb_enqueue(fb_engine *e, const fb_nes_params *q, int64_t N, uint32_t it, bool with_dist, FbCtlDev *ctl, double *trace_dev) {
   const int *stop = ctl ? &ctl->stop : nullptr;
   const int r = e->eot;  // (companions are refused: the replicas are the EOT draws)
@@ -2507,6 +2543,8 @@ static int wb_enqueue(fb_engine *e, const fb_nes_params *q, int64_t N, uint32_t 
   call.keep_iv_quad = e->kind == 1;
   const bool air = e->air.L > 0;  // (wb_check: only under fb_set_wb_air)
   call.keep_air_sat = air;
+  const bool feco = e->feco_iters > 0;  // (wb_check: only under fb_set_wb_frontend, like a dither > 0)
+  call.keep_feco = feco;
   const int T = e->h_frame_off[1];
   FBCHK(run_scoring(e, call, r, e->h_frame_off[r]));
   const double scale = ldexp(1.0, nes_bits(q) - 1);
@@ -2546,11 +2584,19 @@ static int wb_enqueue(fb_engine *e, const fb_nes_params *q, int64_t N, uint32_t 
       wb_launch_iv_backend_t(e, e->iv_ivec.as<double>(), stop);
       wb_launch_iv_backward(e, e->row_off.as<int>() + 1, T, stop);
     } else {
-      wb_launch_gmm_backward(e, r > 1 ? e->tv.as<int>() + j : e->row_off.as<int>() + 1, T, stop, r > 1 ? e->row_off.as<int>() + j : nullptr);
+      // (under feature compression the rows scored are replica j's k_j centres -- the kept k, not the VAD's count e->tv[j],
+      //  which the front-end backward still checks its mask against; e->feats / e->row_off are the compressed pair)
+      const int *n_rows = feco ? e->wb_feco_k.as<int>() + j : r > 1 ? e->tv.as<int>() + j : e->row_off.as<int>() + 1;
+      wb_launch_gmm_backward(e, n_rows, T, stop, r > 1 ? e->row_off.as<int>() + j : nullptr);
     }
+    if (feco) wb_launch_feco_t(e, j, T, stop);
     double *slot = air ? e->wb_air_cot.as<double>() + (size_t)j * (size_t)N : nullptr;  // replica j's cotangent on the channel's output
     double *fe_out = through_chain ? e->wb_gj.as<double>() : air ? slot : e->grad.as<double>();
-    wb_launch_frontend_vjp(e, e->fe_wav, j, N, T, scale, fe_out, stop);
+    FbRngPoint ptj = pt;
+    ptj.utt0 = pt.utt0 + (uint32_t)j;   // the forward's dither draws of replicated row j
+    const FbDitherKey dith = fb_dither_key(ptj, e->cfg.dither);
+    wb_launch_frontend_vjp(e, e->fe_wav, j, N, T, scale, fe_out, stop, feco ? e->wb_xbar.as<double>() : nullptr,
+                           e->cfg.dither > 0.0 ? &dith : nullptr);
     e->wb_route[FB_WB_ROUTE_BACKWARD] += 1;
     if (through_chain) FBCHK(wb_launch_chain_t(e, pt, j, N, e->wb_gj.as<double>(), air ? slot : e->grad.as<double>(), !air && j > 0, stop));
   }
@@ -2570,6 +2616,7 @@ extern "C" int fb_get_grad_wb_iter(fb_engine *e, const fb_nes_params *p, const d
   if (e) memset(e->nes_route, 0, sizeof(e->nes_route));
   if (e) memset(e->wb_route, 0, sizeof(e->wb_route));
   if (e) e->wb_air_launches = 0;
+  if (e) e->wb_feco_launches = 0;
   if (iter < 0) return fb_fail(FB_E_ARG, "iter must be >= 0");
   fb_nes_params q;
   FBCHK(wb_check(e, p, audio, N, &q));
@@ -2616,6 +2663,43 @@ extern "C" int fb_set_wb_air(fb_engine *e, int on) {
   if (!e) return fb_fail(FB_E_ARG, "null engine");
   if (on != 0 && on != 1) return fb_fail(FB_E_ARG, "fb_set_wb_air takes 0 or 1, not %d", on);
   e->wb_air = on;
+  return FB_OK;
+}
+
+extern "C" int fb_set_wb_frontend(fb_engine *e, int on) {
+  if (!e) return fb_fail(FB_E_ARG, "null engine");
+  if (on != 0 && on != 1) return fb_fail(FB_E_ARG, "fb_set_wb_frontend takes 0 or 1, not %d", on);
+  e->wb_frontend = on;
+  return FB_OK;
+}
+
+extern "C" int fb_debug_wb_feco_route(fb_engine *e, int *n_launches) {
+  if (!e || !n_launches) return fb_fail(FB_E_ARG, "null argument");
+  *n_launches = e->wb_feco_launches;
+  return FB_OK;
+}
+
+// Test hook: what the forward of the last fb_get_grad_wb* call kept of replica j's feature compression (valid until the next
+// scoring call): *Tv voiced rows, *k centres, labels[Tv], counts[k]; cap = the ints each array holds
+extern "C" int fb_debug_wb_feco_state(fb_engine *e, int j, int cap, int *labels, int *counts, int *Tv, int *k) {
+  if (!e || !labels || !counts || !Tv || !k || cap < 0) return fb_fail(FB_E_ARG, "bad argument");
+  if (!e->wb_frontend || e->feco_iters <= 0 || !e->wb_feco_k.p || !e->row_off_fc.p)
+    return fb_fail(FB_E_STATE, "no kept assignment: fb_set_wb_frontend, fb_set_feature_compression and a white-box call first");
+  if (j < 0 || j >= e->eot) return fb_fail(FB_E_ARG, "replica %d of %d", j, e->eot);
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  int in_off[2], out_off[2], kept = 0;
+  FBCHK(d2h(e, in_off, e->row_off_fc.as<int>() + j, sizeof(in_off)));
+  FBCHK(d2h(e, out_off, e->row_off.as<int>() + j, sizeof(out_off)));
+  FBCHK(d2h(e, &kept, e->wb_feco_k.as<int>() + j, sizeof(int)));
+  FBCHK(sync_stream(e));
+  *Tv = in_off[1] - in_off[0];
+  *k = out_off[1] - out_off[0];
+  if (kept != *k) return fb_fail(FB_E_HIP, "the kept k %d is not the row's centre count %d", kept, *k);
+  if (*Tv < 0 || *k < 0 || *Tv > cap || *k > cap) return fb_fail(FB_E_ARG, "%d rows, %d centres: more than the arrays hold (%d)", *Tv, *k, cap);
+  if (*Tv > 0) FBCHK(d2h(e, labels, e->wb_feco_label.as<int>() + in_off[0], sizeof(int) * (size_t)*Tv));
+  if (*k > 0) FBCHK(d2h(e, counts, e->wb_feco_cnt.as<int>() + out_off[0], sizeof(int) * (size_t)*k));
+  FBCHK(sync_stream(e));
   return FB_OK;
 }
 
@@ -2717,6 +2801,7 @@ extern "C" int fb_attack_wb(fb_engine *e, const fb_nes_params *p, const double *
   if (e) memset(e->nes_route, 0, sizeof(e->nes_route));
   if (e) memset(e->wb_route, 0, sizeof(e->wb_route));
   if (e) e->wb_air_launches = 0;
+  if (e) e->wb_feco_launches = 0;
   if (!adv_i16 || !success_flag) return fb_fail(FB_E_ARG, "null argument");
   fb_nes_params q;
   FBCHK(wb_check(e, p, audio, N, &q));
@@ -3823,6 +3908,68 @@ extern "C" int fb_debug_feature_compress(fb_engine *e, const float *feats, const
     FBCHK(d2h(e, out, d_out.p, sizeof(float) * (size_t)out_off[rows] * D));
     FBCHK(sync_stream(e));
   }
+  return FB_OK;
+}
+
+// Test hook: fb_debug_feature_compress with the keep outputs on, then k_wb_feco_t on cotangents handed in.  cots: float64, laid
+// out as `out` (row R's k_R x D block at out_off[R]; k_R = max(1, floor(T_R * ratio)), 0 for an empty row -- the caller sizes it
+// by that rule, cot_rows = the rows it holds, checked here against the kernel's total); labels: one int per input row; counts: one
+// per centre, laid out as out's rows; xbar: float64, laid out as feats.
+extern "C" int fb_debug_feature_compress_vjp(fb_engine *e, const float *feats, const int *row_off, int B, int r, uint64_t seed,
+                                             uint32_t stream, uint32_t epoch, const double *cots, int cot_rows, int *out_off,
+                                             int *labels, int *counts, double *xbar) {
+  if (!e || !feats || !row_off || !cots || !out_off || !labels || !counts || !xbar || B <= 0 || r < 1 || r > 32 || (int64_t)B * r > 65535)
+    return fb_fail(FB_E_ARG, "bad argument");
+  if (e->feco_iters <= 0) return fb_fail(FB_E_STATE, "feature compression is off: fb_set_feature_compression first");
+  const int rows = B * r, D = e->fe.dim;
+  if (row_off[0] != 0) return fb_fail(FB_E_ARG, "row_off[0] must be 0");
+  int t_max = 0;
+  for (int u = 0; u < rows; ++u) {
+    if (row_off[u + 1] < row_off[u]) return fb_fail(FB_E_ARG, "row_off decreases at row %d", u);
+    t_max = std::max(t_max, row_off[u + 1] - row_off[u]);
+  }
+  const size_t total = (size_t)row_off[rows];
+  if (total == 0 || total * (size_t)D > 0x7fffffffull) return fb_fail(FB_E_ARG, "the batch holds no row, or more than the hook takes");
+  if (cot_rows < 0 || (size_t)cot_rows > total) return fb_fail(FB_E_ARG, "more cotangent rows than input rows");
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  e->wb_feco_launches = 0;
+  DevBuf d_in, d_off, d_out, d_ooff, d_ws, d_lab, d_cnt, d_k, d_cot, d_xbar;
+  FBCHK(d_in.ensure(sizeof(float) * total * D));
+  FBCHK(d_off.ensure(sizeof(int) * (size_t)(rows + 1)));
+  FBCHK(d_out.ensure(sizeof(float) * total * D));
+  FBCHK(d_ooff.ensure(sizeof(int) * (size_t)(rows + 1)));
+  FBCHK(d_ws.ensure(sizeof(int) * FB_FECO_WS_INTS * total));
+  FBCHK(d_lab.ensure(sizeof(int) * total));
+  FBCHK(d_cnt.ensure(sizeof(int) * total));
+  FBCHK(d_k.ensure(sizeof(int) * (size_t)rows));
+  FBCHK(d_cot.ensure(sizeof(double) * total * D));
+  FBCHK(d_xbar.ensure(sizeof(double) * total * D));
+  FBCHK(h2d(e, d_in.p, feats, sizeof(float) * total * D));
+  FBCHK(h2d(e, d_off.p, row_off, sizeof(int) * (size_t)(rows + 1)));
+  const FbFeco fc = fb_feco_key(FbRngPoint{seed, stream, epoch, 0}, e->feco_ratio, e->feco_iters, r);
+  if (!fb_launch_feature_compress(e->stream, fc, D, d_in.as<float>(), d_off.as<int>(), rows, t_max, d_out.as<float>(),
+                                  d_ooff.as<int>(), d_ws.as<int>(), nullptr, d_lab.as<int>(), d_cnt.as<int>(), d_k.as<int>()))
+    return fb_fail(FB_E_HIP, "k_feature_compress: the dynamic-LDS opt-in failed");
+  HIPCHK(hipGetLastError());
+  FBCHK(d2h(e, out_off, d_ooff.p, sizeof(int) * (size_t)(rows + 1)));
+  FBCHK(sync_stream(e));
+  if (out_off[rows] != cot_rows)
+    return fb_fail(FB_E_ARG, "the cotangents hold %d rows, the kernel wrote %d centres", cot_rows, out_off[rows]);
+  std::vector<int> ks((size_t)rows);
+  FBCHK(d2h(e, ks.data(), d_k.p, sizeof(int) * (size_t)rows));
+  FBCHK(sync_stream(e));
+  for (int u = 0; u < rows; ++u)
+    if (ks[(size_t)u] != out_off[u + 1] - out_off[u]) return fb_fail(FB_E_HIP, "the kept k of row %d is not the row's centre count", u);
+  if (cot_rows > 0) FBCHK(h2d(e, d_cot.p, cots, sizeof(double) * (size_t)cot_rows * D));
+  fb_launch_wb_feco_t(e->stream, D, d_lab.as<int>(), d_cnt.as<int>(), d_off.as<int>(), d_ooff.as<int>(), 0, rows, t_max, true,
+                      d_cot.as<double>(), d_xbar.as<double>(), nullptr);
+  e->wb_feco_launches += 1;
+  HIPCHK(hipGetLastError());
+  FBCHK(d2h(e, labels, d_lab.p, sizeof(int) * total));
+  if (cot_rows > 0) FBCHK(d2h(e, counts, d_cnt.p, sizeof(int) * (size_t)cot_rows));
+  FBCHK(d2h(e, xbar, d_xbar.p, sizeof(double) * total * D));
+  FBCHK(sync_stream(e));
   return FB_OK;
 }
 

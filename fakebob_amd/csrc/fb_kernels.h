@@ -160,8 +160,18 @@ static inline FbFeco fb_feco_key(const FbRngPoint &pt, double ratio, int iters, 
 // k-means over the rows of every utterance row (row_off[rows + 1]; row b * fc.r + j = replica j of utterance b): the centres
 // to out, their offsets to out_off[rows + 1]; ws: FB_FECO_WS_INTS ints per input row; t_max: an upper bound of the longest
 // row (it sizes the LDS request); honours `stop` (nullable) like the MFCC kernels.  false: the LDS opt-in failed
+// keep_label / keep_cnt / keep_k (nullable, the white-box call under fb_set_wb_frontend): the final assignment -- the label of
+// every input row (laid out as feats' rows), the member count of every centre (laid out as out's rows), k of every row --,
+// written once at the end; with null pointers the results are what they were before the outputs existed
 bool fb_launch_feature_compress(hipStream_t s, const FbFeco &fc, int D, const float *feats, const int *row_off, int rows,
-                                int t_max, float *out, int *out_off, int *ws, const int *stop);
+                                int t_max, float *out, int *out_off, int *ws, const int *stop, int *keep_label = nullptr,
+                                int *keep_cnt = nullptr, int *keep_k = nullptr);
+// the stage transposed at that assignment (k_wb_feco_t): xbar[t][d] = cbar[label[t]][d] / (double) count[label[t]] for the rows
+// row0 .. row0 + rows - 1 of the batch (in_off: the input rows' offsets, out_off: the centres'; t_max: an upper bound of a
+// row's length).  packed: cbar / xbar are laid out as out / feats; else they hold ONE row (rows == 1), from index 0.
+// Honours `stop`.
+void fb_launch_wb_feco_t(hipStream_t s, int D, const int *label, const int *cnt, const int *in_off, const int *out_off, int row0,
+                         int rows, int t_max, bool packed, const double *cbar, double *xbar, const int *stop);
 // keys[T] of one (utterance fc.utt0, replica) of the contract (fb_debug_feco_keys)
 void fb_launch_feco_keys(hipStream_t s, const FbFeco &fc, int replica, int T, uint32_t *keys);
 
@@ -316,10 +326,11 @@ void fb_launch_wb_gmm_backward(hipStream_t s, int M, int C, int D, const float *
 // grad[n] = scale * d <cot, feats(wav)> / d wav for ONE utterance of n samples / T frames whose MFCC matrix the forward left in
 // mfcc; cot [Tv][dim] on the compacted rows.  rank [T] (out: the voiced row of a frame or -1), dcm / ddf [T][dim], dmf [T][nc],
 // dxf [T][L]: float64 workspace.  tv_fwd (nullable): the forward's voiced count; *status = 1 if the mask recomputed here counts
-// differently
+// differently.  dk (nullable; fb_set_wb_frontend): the forward's dither -- the frames are recomputed from x + amp z, z the normals
+// of utterance dk->utt0 under the dither RNG contract; null or amp = 0 draws nothing
 void fb_launch_wb_frontend_vjp(hipStream_t s, const FbFrontendDev &fe, const int16_t *wav, int64_t n, int T, const float *mfcc,
                                const double *cot, const int *tv_fwd, int *rank, double *dcm, double *ddf, double *dmf, double *dxf,
-                               double scale, double *grad, int *status, const int *stop);
+                               double scale, double *grad, int *status, const int *stop, const FbDitherKey *dk = nullptr);
 // FAKEBOB.py:193-203 on the gradient vector g with the step size of ctl
 void fb_launch_wb_update(hipStream_t s, const double *g, int64_t N, double momentum, double one_minus_m, double epsilon,
                          const double *audio, double *grad_m, double *adver, const FbCtlDev *ctl);

@@ -22,6 +22,8 @@
 //            frames of the same label), then a thread per (centre, dimension) adds its members in ascending t in float64
 // The loop stops early once an iteration changes no assignment (the contract allows it: the centres are a function of
 // the assignment).
+// White-box calls (fb_set_wb_frontend) ask the kernel to keep that final assignment -- labels, member counts, k -- and
+// k_wb_feco_t, below, is the stage transposed at it.
 #include "fb_device.h"
 #include "fb_kernels.h"
 
@@ -197,7 +199,8 @@ __global__ __launch_bounds__(FC_THREADS) void k_feature_compress(FbFeco fc, int 
                                                                   const int *__restrict__ row_off, int rows,
                                                                   float *__restrict__ out, int *__restrict__ out_off,
                                                                   int *__restrict__ ws, int lds_bytes,
-                                                                  const int *__restrict__ stop) {
+                                                                  const int *__restrict__ stop, int *__restrict__ keep_label,
+                                                                  int *__restrict__ keep_cnt, int *__restrict__ keep_k) {
   extern __shared__ __attribute__((aligned(16))) float fc_lds[];
   __shared__ float s_bd[FC_THREADS];
   __shared__ int s_bj[FC_THREADS];
@@ -220,12 +223,14 @@ __global__ __launch_bounds__(FC_THREADS) void k_feature_compress(FbFeco fc, int 
   if (tid == 0) {
     out_off[u] = o_off;
     if (u == rows - 1) out_off[rows] = o_off + k;
+    if (keep_k) keep_k[u] = k;
   }
   if (T <= 0) return;
   const float *X = feats + (size_t)i_off * D;
   float *O = out + (size_t)o_off * D;
   const uint32_t utt = fc.utt0 + (uint32_t)(u / fc.r);
   const int replica = u % fc.r;
+  const int *aux_end;  // the five arrays as fc_body left them: labels at T, counts at 3 T
   if (fc_lds_bytes(T, k, D) <= (size_t)lds_bytes) {
     const int xs = fc_xs(D), cs = fc_cs(D);
     float *Cl = fc_lds, *Xl = fc_lds + (size_t)k * cs;
@@ -241,9 +246,48 @@ __global__ __launch_bounds__(FC_THREADS) void k_feature_compress(FbFeco fc, int 
       const int j = (int)(i / D), d = (int)(i - (long long)j * D);
       O[i] = Cl[(size_t)j * cs + d];
     }
+    aux_end = aux;
   } else {
-    fc_body<false>(fc, utt, replica, X, D, O, D, ws + (size_t)FB_FECO_WS_INTS * i_off, T, k, D, s_bd, s_bj, &s_changed);
+    int *aux = ws + (size_t)FB_FECO_WS_INTS * i_off;
+    fc_body<false>(fc, utt, replica, X, D, O, D, aux, T, k, D, s_bd, s_bj, &s_changed);
+    __syncthreads();
+    aux_end = aux;
   }
+  // the assignment the centres were last written under (after the last update, or at the early break, where it is the one
+  // that update used) and its member counts, kept for the white-box backward: label of input row i_off + t, count of
+  // centre o_off + j
+  if (keep_label)
+    for (int t = tid; t < T; t += FC_THREADS) keep_label[(size_t)i_off + t] = aux_end[(size_t)T + t];
+  if (keep_cnt)
+    for (int j = tid; j < k; j += FC_THREADS) keep_cnt[(size_t)o_off + j] = aux_end[3 * (size_t)T + j];
+}
+
+// The k-means stage transposed at a constant assignment (fb_set_wb_frontend; "White-box gradients through the front end" in
+// include/fakebob_hip.h): a centre with members is their mean, so frame t of row R receives its centre's cotangent divided by
+// the member count -- xbar[t][d] = cbar[label[t]][d] / (double) n_label[t], one correctly rounded division, no sum at all; a
+// centre without members kept an earlier value and its cotangent is read by nobody.  One thread per (frame, dimension) of row
+// row0 + blockIdx.y; offsets and counts are read here.  packed: cbar / xbar hold every row (at out_off / in_off); else they
+// hold the one row alone, from 0.
+__global__ __launch_bounds__(256) void k_wb_feco_t(int D, const int *__restrict__ label, const int *__restrict__ cnt,
+                                                   const int *__restrict__ in_off, const int *__restrict__ out_off, int row0,
+                                                   int packed, const double *__restrict__ cbar, double *__restrict__ xbar,
+                                                   const int *__restrict__ stop) {
+  if (stop && *stop) return;
+  const int R = row0 + blockIdx.y;
+  const int i_off = in_off[R], T = in_off[R + 1] - i_off, o_off = out_off[R], k = out_off[R + 1] - o_off;
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long long)T * D) return;
+  const int t = (int)(i / D), d = (int)(i - (long long)t * D);
+  const int l = label[(size_t)i_off + t];
+  if (l < 0 || l >= k) return;  // (never: every frame of a row with T > 0 is assigned)
+  const double c = cbar[((size_t)(packed ? o_off : 0) + l) * D + d];
+  xbar[((size_t)(packed ? i_off : 0) + t) * D + d] = __ddiv_rn(c, (double)cnt[(size_t)o_off + l]);
+}
+void fb_launch_wb_feco_t(hipStream_t s, int D, const int *label, const int *cnt, const int *in_off, const int *out_off, int row0,
+                         int rows, int t_max, bool packed, const double *cbar, double *xbar, const int *stop) {
+  if (rows <= 0 || t_max <= 0) return;
+  hipLaunchKernelGGL(k_wb_feco_t, dim3((unsigned)(((size_t)t_max * D + 255) / 256), (unsigned)rows), dim3(256), 0, s, D, label, cnt,
+                     in_off, out_off, row0, packed ? 1 : 0, cbar, xbar, stop);
 }
 
 __global__ __launch_bounds__(256) void k_feco_keys(FbFeco fc, int replica, int T, uint32_t *__restrict__ keys) {
@@ -255,7 +299,8 @@ void fb_launch_feco_keys(hipStream_t s, const FbFeco &fc, int replica, int T, ui
 }
 
 bool fb_launch_feature_compress(hipStream_t s, const FbFeco &fc, int D, const float *feats, const int *row_off, int rows,
-                                int t_max, float *out, int *out_off, int *ws, const int *stop) {
+                                int t_max, float *out, int *out_off, int *ws, const int *stop, int *keep_label, int *keep_cnt,
+                                int *keep_k) {
   if (rows <= 0) return true;
   // the LDS the longest row could need (k grows with T), capped: rows beyond it take the general path
   size_t shm = fc_lds_bytes(t_max, fc_k(t_max, fc.ratio), D);
@@ -271,6 +316,6 @@ bool fb_launch_feature_compress(hipStream_t s, const FbFeco &fc, int D, const fl
     }
   }
   hipLaunchKernelGGL(k_feature_compress, dim3((unsigned)rows), dim3(FC_THREADS), shm, s, fc, D, feats, row_off, rows, out,
-                     out_off, ws, (int)shm, stop);
+                     out_off, ws, (int)shm, stop, keep_label, keep_cnt, keep_k);
   return true;
 }

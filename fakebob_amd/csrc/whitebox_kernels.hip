@@ -347,9 +347,13 @@ __device__ __forceinline__ void wb_fft(double *re, double *im, int P, const doub
 #define FB_WB_MAX_NB 128
 // One workgroup per frame: dxf[f][s] = d <dmf[f], mfcc(frame f)> / d (the frame's s-th sample as extracted), float64.
 // A floor that is active contributes nothing: a mel energy below FLT_EPSILON, a frame energy below it, energy_floor.
+// dk (fb_set_wb_frontend): with dk.amp > 0 the frame is recomputed from what the forward extracted under Kaldi's dither,
+// (double) x + amp (double) z, z the normal of (utterance dk.utt0, frame f, sample s) of the dither RNG contract -- the draws
+// k_mfcc / k_mfcc_f32 added, constants here (additive: the derivative with respect to the sample is unchanged).  amp = 0 draws
+// nothing and computes what the kernel computed before it took the key.
 __global__ __launch_bounds__(256) void k_wb_mfcc_t(FbFrontendDev fe, const int16_t *__restrict__ wav, int64_t n,
                                                    const double *__restrict__ dmf, double *__restrict__ dxf,
-                                                   const int *__restrict__ stop) {
+                                                   const int *__restrict__ stop, FbDitherKey dk) {
   if (stop && *stop) return;
   __shared__ double re[FB_WB_MAX_P], im[FB_WB_MAX_P], xs[FB_WB_MAX_P], aux[FB_WB_MAX_P], red[256];
   __shared__ double s_de[FB_WB_MAX_NB], s_dc[FB_WB_MAX_NB];
@@ -358,7 +362,18 @@ __global__ __launch_bounds__(256) void k_wb_mfcc_t(FbFrontendDev fe, const int16
   const double eps = (double)FLT_EPSILON;
   // ---- the frame's forward
   double v = 0.0;
-  for (int s = threadIdx.x; s < L; s += 256) { xs[s] = (double)wav[wb_reflect(start + s, n)]; v += xs[s]; }
+  if (dk.amp > 0.0) {
+    for (int s = threadIdx.x; s < L; s += 256) {
+      float z0, z1;
+      fb_dither2(dk.k0, dk.k1, dk.epoch, dk.utt0, (unsigned)f, (unsigned)(s >> 2), (s >> 1) & 1, z0, z1);
+      double x = (double)wav[wb_reflect(start + s, n)];
+      x += dk.amp * (double)((s & 1) ? z1 : z0);
+      xs[s] = x;
+      v += x;
+    }
+  } else {
+    for (int s = threadIdx.x; s < L; s += 256) { xs[s] = (double)wav[wb_reflect(start + s, n)]; v += xs[s]; }
+  }
   if (fe.remove_dc) {
     const double mean = wb_block_sum(v, red) / (double)L;
     for (int s = threadIdx.x; s < L; s += 256) xs[s] -= mean;
@@ -457,11 +472,12 @@ __global__ __launch_bounds__(256) void k_wb_overlap_add(FbFrontendDev fe, int T,
 
 void fb_launch_wb_frontend_vjp(hipStream_t s, const FbFrontendDev &fe, const int16_t *wav, int64_t n, int T, const float *mfcc,
                                const double *cot, const int *tv_fwd, int *rank, double *dcm, double *ddf, double *dmf, double *dxf,
-                               double scale, double *grad, int *status, const int *stop) {
+                               double scale, double *grad, int *status, const int *stop, const FbDitherKey *dk) {
+  const FbDitherKey dkv = (dk && dk->amp > 0.0) ? *dk : FbDitherKey{};
   hipLaunchKernelGGL(k_wb_vad_scatter, dim3(1), dim3(256), 0, s, fe, mfcc, T, cot, tv_fwd, rank, dcm, status, stop);
   hipLaunchKernelGGL(k_wb_cmvn_t, dim3((unsigned)((T * fe.dim + 255) / 256)), dim3(256), 0, s, T, fe.dim, fe.cmn_window, dcm, ddf, stop);
   hipLaunchKernelGGL(k_wb_delta_t, dim3((unsigned)((T * fe.nc + 255) / 256)), dim3(256), 0, s, fe, T, ddf, dmf, stop);
-  hipLaunchKernelGGL(k_wb_mfcc_t, dim3((unsigned)T), dim3(256), 0, s, fe, wav, n, dmf, dxf, stop);
+  hipLaunchKernelGGL(k_wb_mfcc_t, dim3((unsigned)T), dim3(256), 0, s, fe, wav, n, dmf, dxf, stop, dkv);
   hipLaunchKernelGGL(k_wb_overlap_add, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, fe, T, n, dxf, scale, grad, stop);
 }
 

@@ -60,6 +60,7 @@ class Engine(object):
         self.wb_bpda = False
         self.wb_ivector = False
         self.wb_air = False
+        self.wb_frontend = False
         self.companions = None
         self.feature_compression = None
 
@@ -259,6 +260,36 @@ class Engine(object):
                                                   C.c_uint64(int(seed)), C.c_uint32(int(stream)), C.c_uint32(int(epoch)),
                                                   N.ptr(out), N.ptr(out_off)))
         return [[out[out_off[b * r + j]:out_off[b * r + j + 1]].copy() for j in range(r)] for b in range(len(lst))]
+
+    def debug_feature_compress_vjp(self, mats, r, seed, stream, epoch, cots):
+        """debug_feature_compress with the kernel's keep outputs on, then k_wb_feco_t on float64 cotangents handed in
+        (fb_debug_feature_compress_vjp): `cots`, a list of B lists of r arrays (k_b, feat_dim), k_b = max(1, floor(T_b * ratio))
+        (0 rows for T_b = 0) -> (labels, counts, xbar): lists of B lists of r arrays, int32 (T_b,), int32 (k_b,) and float64
+        (T_b, feat_dim) = cots[label] / counts[label]."""
+        D, r = self.feat_dim, int(r)
+        lst = [np.ascontiguousarray(m, np.float32).reshape(-1, D) for m in mats]
+        rep = [m for m in lst for _ in range(r)]
+        off = np.zeros(len(rep) + 1, np.int32)
+        off[1:] = np.cumsum([m.shape[0] for m in rep])
+        cat = np.ascontiguousarray(np.concatenate(rep, axis=0))
+        crep = [np.ascontiguousarray(cots[b][j], np.float64).reshape(-1, D) for b in range(len(lst)) for j in range(r)]
+        ccat = np.ascontiguousarray(np.concatenate(crep, axis=0)) if crep else np.zeros((0, D), np.float64)
+        out_off = np.empty_like(off)
+        labels = np.full(cat.shape[0], -1, np.int32)
+        counts = np.zeros(max(ccat.shape[0], 1), np.int32)
+        xbar = np.zeros(cat.shape, np.float64)
+        N.check(self._L.fb_debug_feature_compress_vjp(self._h, N.ptr(cat), N.ptr(off), C.c_int(len(lst)), C.c_int(r),
+                                                      C.c_uint64(int(seed)), C.c_uint32(int(stream)), C.c_uint32(int(epoch)),
+                                                      N.ptr(ccat if ccat.size else np.zeros((1, D), np.float64)),
+                                                      C.c_int(ccat.shape[0]), N.ptr(out_off), N.ptr(labels), N.ptr(counts),
+                                                      N.ptr(xbar)))
+        for R, c in enumerate(crep):
+            if out_off[R + 1] - out_off[R] != c.shape[0]:
+                raise ValueError("row %d: %d cotangent rows for %d centres" % (R, c.shape[0], out_off[R + 1] - out_off[R]))
+        rows = range(len(lst))
+        return ([[labels[off[b * r + j]:off[b * r + j + 1]].copy() for j in range(r)] for b in rows],
+                [[counts[out_off[b * r + j]:out_off[b * r + j + 1]].copy() for j in range(r)] for b in rows],
+                [[xbar[off[b * r + j]:off[b * r + j + 1]].copy() for j in range(r)] for b in rows])
 
     def debug_feco_keys(self, seed, stream, epoch, utt, replica, T):
         """The uint32 initialisation keys of frames 0 .. T - 1 of (utterance row `utt`, replica) (fb_debug_feco_keys)."""
@@ -545,6 +576,32 @@ class Engine(object):
         N.check(self._L.fb_set_wb_air(self._h, C.c_int(1 if on is True else 0 if on is False else int(on))))
         self.wb_air = bool(on)
 
+    def set_wb_frontend(self, on):
+        """fb_set_wb_frontend: with True, get_grad_wb and attack_wb differentiate through feature compression (the forward's
+        final k-means assignment held constant: a centre is the mean of its members) and through Kaldi's dither (the forward's
+        draws, redrawn as constants); the rules are in include/fakebob_hip.h.  Neither needs another switch at r = 1; a chain, a
+        codec and r > 1 still need set_wb_bpda(True), an air channel set_wb_air(True), an i-vector system set_wb_ivector(True).
+        False (as created): both are refused and nothing else changes.  0 / 1 and booleans only; anything else is handed to
+        the library, which refuses it."""
+        N.check(self._L.fb_set_wb_frontend(self._h, C.c_int(1 if on is True else 0 if on is False else int(on))))
+        self.wb_frontend = bool(on)
+
+    def debug_wb_feco_route(self):
+        """k_wb_feco_t launches of the last get_grad_wb / attack_wb / debug_feature_compress_vjp call
+        (fb_debug_wb_feco_route): r per iteration with feature compression on, none otherwise."""
+        n = C.c_int(0)
+        N.check(self._L.fb_debug_wb_feco_route(self._h, C.byref(n)))
+        return int(n.value)
+
+    def debug_wb_feco_state(self, j=0, cap=1 << 16):
+        """What the forward of the last get_grad_wb call kept of replica j's feature compression (fb_debug_wb_feco_state; read
+        it before any other scoring call) -> (labels (Tv,) int32, counts (k,) int32)."""
+        labels, counts = np.empty(int(cap), np.int32), np.empty(int(cap), np.int32)
+        tv, k = C.c_int(0), C.c_int(0)
+        N.check(self._L.fb_debug_wb_feco_state(self._h, C.c_int(int(j)), C.c_int(int(cap)), N.ptr(labels), N.ptr(counts),
+                                               C.byref(tv), C.byref(k)))
+        return labels[:tv.value].copy(), counts[:k.value].copy()
+
     def debug_air_conv_t(self, taps, cot, sat=None):
         """k_air_conv_t alone (fb_debug_air_conv_t): int16 taps (B, L) -- or (L,) for one row --, float64 cotangents (B, n) and
         (optional) saturation bytes (B, n) -> dx (B, n) float64 = 2^-14 * the correlation of the masked cotangent with the
@@ -584,7 +641,8 @@ class Engine(object):
         random stages of a defended victim.  Refused (NativeError, FB_E_STATE) for i-vector systems and while an air channel,
         feature compression, dither or companions are set; an input transform, a codec and EOT only after set_wb_bpda(True).
         After set_wb_ivector(True) an i-vector system is differentiated as well (never with set_eot > 1); after
-        set_wb_air(True) an air channel is too (the forward's drawn responses transposed)."""
+        set_wb_air(True) an air channel is too (the forward's drawn responses transposed); after set_wb_frontend(True) feature
+        compression and dither are (the forward's final assignment and its dither draws held constant)."""
         audio = np.ascontiguousarray(audio, np.float64).reshape(-1)
         n = audio.size
         grad = np.empty(n, np.float64) if want_grad else None

@@ -8,7 +8,8 @@ is no random start, so a run is reproducible.  PGD's victim has to be undefended
 defended one (Engine.set_wb_bpda): BPDA through the model's input-transform chain and codec, and with eot_size = r > 1 an
 expectation over r draws of its random stages per iteration, keyed by the attack's seed and stream.  The air channel is
 refused unless air=True (Engine.set_wb_air: the gradient through the drawn rooms, with eot_size = r the EOT-over-rooms
-gradient of the robust over-the-air attack); feature compression, dither and companions stay refused, as are i-vector
+gradient of the robust over-the-air attack); feature compression and dither are refused unless frontend=True
+(Engine.set_wb_frontend: the forward's final k-means assignment and its dither draws held constant); companions stay refused, as are i-vector
 systems and foreign models -- the gradient is that of this library's own forward.  IvectorPGD is the same attack on an i-vector-PLDA system (Engine.set_wb_ivector): the
 gradient through the PLDA back end, both length normalisations, the posterior solve and the full-covariance posteriors, with
 the frames' component selection and pruned sets held constant; PGD and AdaptivePGD keep refusing such a system.
@@ -37,6 +38,7 @@ class PGD(object):
             raise ValueError("PGD: i-vector systems are out of this version (GMM-UBM systems only)")
         self.bpda = False   # (AdaptivePGD: True -- the engine's switch is on and seed / stream key the victim's draws)
         self.air = False    # (air=True of AdaptivePGD / IvectorPGD: Engine.set_wb_air is on; seed / stream key the rooms)
+        self.frontend = False   # (frontend=True of the two: Engine.set_wb_frontend is on; seed / stream key the k-means and dither draws)
         self.eot_size = 1
         self.task = task
         self.attack_type = attack_type
@@ -84,8 +86,8 @@ class PGD(object):
         return nes_params(self.task, self.attack_type, adver_thresh=self.adver_thresh, epsilon=self.epsilon,
                           max_iter=self.max_iter, max_lr=self.max_lr, min_lr=self.min_lr, samples_per_draw=0, sigma=0.0,
                           momentum=self.momentum, plateau_length=self.plateau_length, plateau_drop=self.plateau_drop,
-                          threshold=self.threshold, target=self.target, true=self.true, seed=self.seed if (self.bpda or self.air) else 0,
-                          stream=self._stream if (self.bpda or self.air) else 0, bits_per_sample=bits_per_sample)
+                          threshold=self.threshold, target=self.target, true=self.true, seed=self.seed if (self.bpda or self.air or self.frontend) else 0,
+                          stream=self._stream if (self.bpda or self.air or self.frontend) else 0, bits_per_sample=bits_per_sample)
 
     def get_grad(self, audio, fs=16000, bits_per_sample=16, n_jobs=10, debug=False):
         """-> (grad (N,1) = d loss / d audio, adver_loss (1,), score), the analytic twin of FakeBob.get_grad's last three."""
@@ -130,9 +132,11 @@ class AdaptivePGD(PGD):
     (Engine.set_eot).  Everything else -- knobs, attack(), get_grad(), return pair, checkpoint layout -- is PGD's.  The
     constructor sets both on the model's engine and they stay set; bpda=False with eot_size=1 is PGD itself.  air=True also
     switches the engine to differentiate through the model's over-the-air channel (Engine.set_wb_air): each iteration then
-    takes the gradient through the eot_size rooms its forward drew."""
+    takes the gradient through the eot_size rooms its forward drew.  frontend=True switches it to differentiate through the
+    model's feature compression and dither (Engine.set_wb_frontend): the gradient at the k-means assignment and the dither
+    draws of each of the eot_size forwards."""
 
-    def __init__(self, task, attack_type, model, bpda=True, eot_size=1, air=False, **kw):
+    def __init__(self, task, attack_type, model, bpda=True, eot_size=1, air=False, frontend=False, **kw):
         eot_size = int(eot_size)
         if not 1 <= eot_size <= 32:
             raise ValueError("AdaptivePGD: eot_size %d outside 1 .. 32" % eot_size)
@@ -148,6 +152,9 @@ class AdaptivePGD(PGD):
         self.air = bool(air)
         if self.air:
             model.engine.set_wb_air(True)
+        self.frontend = bool(frontend)
+        if self.frontend:
+            model.engine.set_wb_frontend(True)
 
 
 class IvectorPGD(PGD):
@@ -155,11 +162,12 @@ class IvectorPGD(PGD):
     differentiate through the i-vector back end (Engine.set_wb_ivector; the rules are in include/fakebob_hip.h) and, with
     bpda=True, through an input-transform chain and a codec as well (Engine.set_wb_bpda); both stay set.  There is no
     expectation over transformation for an i-vector system.  air=True: through the model's over-the-air channel too
-    (Engine.set_wb_air), one room per iteration.  Knobs, attack(), get_grad(), estimate_threshold(), the return pair and the
+    (Engine.set_wb_air), one room per iteration; frontend=True: through feature compression and dither
+    (Engine.set_wb_frontend), one draw per iteration.  Knobs, attack(), get_grad(), estimate_threshold(), the return pair and the
     checkpoint layout are PGD's."""
     KINDS = ("gmm", "iv")
 
-    def __init__(self, task, attack_type, model, bpda=False, air=False, **kw):
+    def __init__(self, task, attack_type, model, bpda=False, air=False, frontend=False, **kw):
         PGD.__init__(self, task, attack_type, model, **kw)
         self.bpda = bool(bpda)
         model.engine.set_wb_ivector(True)
@@ -168,3 +176,6 @@ class IvectorPGD(PGD):
         self.air = bool(air)
         if self.air:
             model.engine.set_wb_air(True)
+        self.frontend = bool(frontend)
+        if self.frontend:
+            model.engine.set_wb_frontend(True)

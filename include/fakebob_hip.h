@@ -557,7 +557,8 @@ int fb_attack_kenansville(fb_engine *e, const fb_nes_params *p, const fb_kv_para
  * above stands.  With 1, fb_get_grad_wb, fb_get_grad_wb_iter and fb_attack_wb accept an input-transform chain (all five stage
  * kinds), a codec, fb_set_eot(r), 1 <= r <= 32, and any combination; with nothing of these set they queue exactly the
  * launches of the undefended call.  Still FB_E_STATE with the switch on, the cause named: an i-vector system, companions,
- * feature compression, dither > 0 -- and an AIR CHANNEL: refused unless fb_set_wb_air ("The over-the-air channel", below).
+ * feature compression, dither > 0 (both: unless fb_set_wb_frontend, "Feature compression and dither", below) -- and an
+ * AIR CHANNEL: refused unless fb_set_wb_air ("The over-the-air channel", below).
  * fb_get_grad_wb_iter is fb_get_grad_wb with the epoch of the random draws given: `iter` (>= 0) means what fb_get_grad's
  * iter means in the noise RNG contract; fb_get_grad_wb is iter = 0; fb_attack_wb draws with its loop index, as fb_attack
  * does.  p->seed and p->stream key the draws.
@@ -593,7 +594,7 @@ int fb_attack_kenansville(fb_engine *e, const fb_nes_params *p, const fb_kv_para
  * fb_get_grad_wb, fb_get_grad_wb_iter and fb_attack_wb accept an air channel: a GMM-UBM system in any combination the BPDA
  * switch allows -- the channel alone needs no other switch; a chain, a codec and fb_set_eot(r > 1) still need
  * fb_set_wb_bpda(e, 1) --, an i-vector system under fb_set_wb_ivector(e, 1), at r = 1 only, as without a channel.  Companions,
- * feature compression and dither stay refused, by name; with no channel set the calls queue exactly the launches they
+ * feature compression and dither (unless fb_set_wb_frontend) stay refused, by name; with no channel set the calls queue exactly the launches they
  * queued before.
  * Forward.  The engine's own, unchanged: cast, air channel, chain, codec, front end.  adver_loss and score0 are bit for bit
  * fb_get_grad's at samples_per_draw = 0 with the same iter, seed, stream and settings.
@@ -607,6 +608,32 @@ int fb_attack_kenansville(fb_engine *e, const fb_nes_params *p, const fb_kv_para
  * in float64 on the matrix cores (k_air_conv_t); the order of the sum over k is the kernel's: fixed, not specified.  Then
  *     grad = sum_j dx_j, j ascending, float64.
  * No floating-point atomics: the same call on a fresh engine gives the same bits.
+ * Feature compression and dither (fb_set_wb_frontend).  Both stages are differentiated by the rule of gselect, the min-post set
+ * and the voiced mask -- the forward's hard decisions are held constant; no surrogate is invented -- behind a fourth switch:
+ * fb_set_wb_frontend(e, on), on = 0 or 1 (anything else: FB_E_ARG, the setting stays), 0 at engine creation, kept across
+ * fb_load_*.  With 0 every call, launch, value and refusal message is what it was before the switch existed: feature
+ * compression and dither > 0 are refused whatever the other three switches say.  With 1, fb_get_grad_wb, fb_get_grad_wb_iter
+ * and fb_attack_wb accept feature compression and dither > 0, alone or together; neither needs fb_set_wb_bpda at r = 1 (the
+ * gradient at a fixed draw is exact).  A chain, a codec and fb_set_eot(r > 1) still need fb_set_wb_bpda, an air channel
+ * fb_set_wb_air, an i-vector system fb_set_wb_ivector (r = 1 only); companions stay refused; with neither stage set the calls
+ * queue exactly the launches they queued before.
+ * Forward.  The engine's own, unchanged.  adver_loss and score0 are bit for bit fb_get_grad's at samples_per_draw = 0 with the
+ * same iter, seed, stream and settings.
+ * Feature compression: the final assignment is a constant.  For utterance row u the forward keeps the label of every voiced
+ * frame, the member count n_j of every centre and k, taken where the centres were last written: after the last update, or at
+ * the early break, where the assignment equals the one the last update used.  A centre with n_j > 0 is the mean of its members;
+ * its float32 storage is the identity.  A centre with n_j = 0 kept an earlier value: a constant, its cotangent is dropped (the
+ * rule "an active floor contributes zero").  The back end -- GMM or i-vector -- is differentiated on the k centre rows as it is
+ * on the voiced rows without the stage; the mean over scored rows is over k, not over the VAD's count.  Then (k_wb_feco_t)
+ *     xbar[t][d] = cbar[label[t]][d] / (double) n_label[t]
+ * one correctly rounded float64 division per element, no atomics, nothing summed; from xbar the front-end backward is the one
+ * above (its voiced mask is still recomputed from the forward's MFCC matrix and checked against the VAD's count).
+ * Dither: the draws are the forward's, and constants.  The per-frame recomputation of the front-end backward reads
+ * (double) x + amp * (double) z(u, t, s) where it reads (double) x without dither, z from the dither RNG contract at the call's
+ * (seed, stream, epoch = iter) with utterance index = the replicated row j -- what k_mfcc and k_mfcc_f32 add; both form the
+ * dithered sample in float64.  The noise is additive: the derivative with respect to the sample is unchanged.
+ * EOT: replica j uses its own labels and its own dither; grad = sum_j grad_j, j ascending.  The same call on a fresh engine
+ * gives the same bits.
  *
  * The i-vector-PLDA victim (fb_set_wb_ivector).  A second switch, for the same reason as the first: fb_set_wb_ivector(e, on),
  * on = 0 or 1 (anything else: FB_E_ARG, the setting stays), 0 at engine creation, kept across fb_load_*.  With 0 every call,
@@ -637,12 +664,13 @@ int fb_attack_kenansville(fb_engine *e, const fb_nes_params *p, const fb_kv_para
  * then the front-end backward above, unchanged.  adver_loss and score0 are bit for bit fb_get_grad's at samples_per_draw = 0:
  * the same scoring call.  fb_attack_wb is the same loop, trace layout and stop test.
  * Refused for an i-vector system with the switch on, FB_E_STATE, the cause named: companions, an air channel (unless fb_set_wb_air), feature
- * compression, dither > 0, and fb_set_eot(r > 1) -- the last with fb_set_wb_bpda on as well ("i-vector", "fb_set_eot": the
+ * compression and dither > 0 (unless fb_set_wb_frontend), and fb_set_eot(r > 1) -- the last with fb_set_wb_bpda on as well ("i-vector", "fb_set_eot": the
  * forward keeps one row's i-vector state, not r replicas').  An input-transform chain and a codec need fb_set_wb_bpda(e, 1), as
  * for a GMM-UBM system, and are then taken at r = 1.  FB_E_NO_VOICED and the "not positive definite" error are scoring's. */
 int fb_set_wb_bpda(fb_engine *e, int on);
 int fb_set_wb_ivector(fb_engine *e, int on);
 int fb_set_wb_air(fb_engine *e, int on);
+int fb_set_wb_frontend(fb_engine *e, int on);
 int fb_get_grad_wb_iter(fb_engine *e, const fb_nes_params *p, const double *audio, int64_t N, int iter, double *adver_loss,
                         double *grad /*[N], nullable*/, double *score0 /*[S]*/);
 int fb_get_grad_wb(fb_engine *e, const fb_nes_params *p, const double *audio, int64_t N, double *adver_loss,

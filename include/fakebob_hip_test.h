@@ -351,6 +351,25 @@ int fb_debug_air_conv_t(fb_engine *e, const int16_t *taps /*[B][L]*/, int B, int
 int fb_debug_air_conv_t_chunk(void);
 int fb_debug_wb_air_route(fb_engine *e, int *n_launches);
 
+/* White-box gradients through feature compression and dither (fakebob_hip.h: fb_set_wb_frontend).
+ * fb_debug_feature_compress_vjp: fb_debug_feature_compress (same arguments, same launch) with the kernel's keep outputs on,
+ * followed by ONE k_wb_feco_t launch over all B * r rows on cotangents handed in: cots, float64, laid out as the compressed rows
+ * -- row R's k_R x D block at out_off[R], k_R = max(1, floor(T_R * ratio)), 0 for an empty row; cot_rows = the rows it holds
+ * (FB_E_ARG unless that is the kernel's total).  Returned: out_off[B * r + 1]; labels, one per input row, = the centre (within
+ * its utterance row) the frame belonged to when the centres were last written; counts, one per centre, laid out as the
+ * compressed rows; xbar, float64, laid out as feats: xbar[t][d] = cots[label[t]][d] / (double) counts[label[t]].
+ * fb_debug_wb_feco_route: *n_launches = the k_wb_feco_t launches of the last fb_get_grad_wb* / fb_attack_wb /
+ * fb_debug_feature_compress_vjp call -- r per iteration with feature compression on, none otherwise.  (Not an index of
+ * fb_debug_wb_route either.) */
+int fb_debug_feature_compress_vjp(fb_engine *e, const float *feats, const int *row_off, int B, int r, uint64_t seed,
+                                  uint32_t stream, uint32_t epoch, const double *cots, int cot_rows, int *out_off, int *labels,
+                                  int *counts, double *xbar);
+int fb_debug_wb_feco_route(fb_engine *e, int *n_launches);
+/* fb_debug_wb_feco_state: what the forward of the last fb_get_grad_wb* call kept of replica j (0 <= j < the EOT size), read
+ * before any other scoring call: *Tv voiced rows, *k centres, labels[*Tv], counts[*k]; cap = the ints either array holds
+ * (FB_E_ARG when too few).  FB_E_STATE without the switch, the stage and such a call. */
+int fb_debug_wb_feco_state(fb_engine *e, int j, int cap, int *labels, int *counts, int *Tv, int *k);
+
 /* White-box gradients through the i-vector-PLDA back end (fakebob_hip.h: fb_set_wb_ivector).  Both hooks need a loaded i-vector
  * system (FB_E_STATE otherwise) and run whatever the switch says, with exactly the launches an attack iteration runs for
  * their stage.
