@@ -205,7 +205,7 @@ def main(argv=None, model_factory=None, bob_factory=None):
     ap.add_argument("--bpda", action="store_true",
                     help="--attack pgd: the adaptive attack on a defended victim -- BPDA through --input-transform and --codec, "
                          "expectation over --eot-size draws of the random stages; --air-channel is refused unless --wb-air is "
-                         "given, --feco and --dither unless --wb-frontend is given; --companions stay refused")
+                         "given, --feco and --dither unless --wb-frontend is given, --companions unless --wb-universal is given")
     ap.add_argument("--wb-air", dest="wb_air", action="store_true",
                     help="--attack pgd: differentiate through --air-channel as well (fakebob_amd/pgd.py: air=True; the forward's "
                          "drawn room responses transposed, with --bpda --eot-size r the expectation over r rooms per iteration); "
@@ -214,9 +214,13 @@ def main(argv=None, model_factory=None, bob_factory=None):
                     help="--attack pgd: differentiate through --feco and --dither as well (fakebob_amd/pgd.py: frontend=True; the "
                          "forward's final k-means assignment and its dither draws held constant, with --bpda --eot-size r the "
                          "expectation over r draws per iteration); needs no other switch at --eot-size 1")
+    ap.add_argument("--wb-universal", dest="wb_universal", action="store_true",
+                    help="--attack pgd: take --companions N (fakebob_amd/pgd.py: universal=True; the gradient of the loss averaged "
+                         "over the N + 1 utterances, with --bpda --eot-size r over r draws of each); needs no other switch on an "
+                         "undefended GMM-UBM victim; on -archi iv with --wb-ivector, where it also allows --bpda --eot-size r")
     ap.add_argument("--wb-ivector", dest="wb_ivector", action="store_true",
                     help="--attack pgd -archi iv: differentiate the i-vector-PLDA victim (fakebob_amd/pgd.py: IvectorPGD; the "
-                         "frames' component selection and pruned sets held constant); never under --eot-size > 1")
+                         "frames' component selection and pruned sets held constant); under --eot-size > 1 only with --wb-universal")
     ap.add_argument("--kv-window", dest="kv_window", default=100, type=int, help="--attack kenansville: samples per window (8 .. 128)")
     ap.add_argument("--kv-grid", dest="kv_grid", default=15, type=int, help="--attack kenansville: candidates per round (1 .. 64)")
     ap.add_argument("--kv-max-factor", dest="kv_max_factor", default=1.0, type=float,
@@ -254,8 +258,10 @@ def main(argv=None, model_factory=None, bob_factory=None):
         ap.error("--wb-air belongs to --attack pgd (--attack %s)" % args.attack)
     if args.wb_frontend and args.attack != "pgd":
         ap.error("--wb-frontend belongs to --attack pgd (--attack %s)" % args.attack)
+    if args.wb_universal and args.attack != "pgd":
+        ap.error("--wb-universal belongs to --attack pgd (--attack %s)" % args.attack)
     if args.attack == "pgd":      # likewise: the gradient is that of a GMM-UBM victim, undefended unless --bpda is given
-        if args.architecture == "iv" and args.wb_ivector and args.eot_size is not None and args.eot_size > 1:
+        if args.architecture == "iv" and args.wb_ivector and args.eot_size is not None and args.eot_size > 1 and not args.wb_universal:
             ap.error("--attack pgd --wb-ivector does not run under expectation over transformation (--eot-size %d: an i-vector "
                      "system keeps one row's state)" % args.eot_size)
         if args.architecture != "gmm" and not args.wb_ivector:
@@ -264,7 +270,7 @@ def main(argv=None, model_factory=None, bob_factory=None):
             ap.error("--attack pgd --wb-air belongs to the adaptive attack: give --bpda (GMM-UBM) or --wb-ivector (-archi iv)")
         if not args.bpda and args.eot_size is not None and args.eot_size > 1:
             ap.error("--attack pgd does not run under expectation over transformation (--eot-size %d)" % args.eot_size)
-        if args.companions > 0:
+        if args.companions > 0 and not args.wb_universal:
             ap.error("--attack pgd does not take companion utterances (--companions %d)" % args.companions)
         for flag, val in (("--input-transform", args.input_transform), ("--air-channel", args.air_channel),
                           ("--codec", None if args.codec == "none" else args.codec), ("--feco", args.feco), ("--dither", args.dither)):
@@ -323,7 +329,7 @@ def main(argv=None, model_factory=None, bob_factory=None):
                   min_lr=args.min_lr, momentum=args.momentum, plateau_length=args.plateau_length, plateau_drop=args.plateau_drop)
         if args.bpda:  # (absent otherwise: a bob_factory of the driver-rule tests sees the keywords it always saw)
             hp.update(bpda=True, eot_size=args.eot_size if args.eot_size is not None else 1)
-        if args.wb_ivector:  # IvectorPGD has no eot_size
+        if args.wb_ivector and not args.wb_universal:  # IvectorPGD has no eot_size without universal=True
             hp.pop("eot_size", None)
         if args.wb_air:
             hp.update(air=True)
@@ -331,12 +337,16 @@ def main(argv=None, model_factory=None, bob_factory=None):
             hp.update(frontend=True)
             if not args.bpda and not args.wb_ivector:  # (AdaptivePGD's default is bpda=True)
                 hp.update(bpda=False)
+        if args.wb_universal:
+            hp.update(universal=True)
+            if not args.bpda and not args.wb_ivector:
+                hp.update(bpda=False)
     if bob_factory is None and args.attack == "pgd" and args.wb_ivector:
         from .pgd import IvectorPGD
         bobs = [IvectorPGD(task, attack_type, m, seed=seed, verbose=False, **hp) for m in models]
     elif bob_factory is None and args.attack == "pgd":
         from .pgd import PGD, AdaptivePGD
-        bobs = [(AdaptivePGD if (args.bpda or args.wb_frontend) else PGD)(task, attack_type, m, seed=seed, verbose=False, **hp) for m in models]
+        bobs = [(AdaptivePGD if (args.bpda or args.wb_frontend or args.wb_universal) else PGD)(task, attack_type, m, seed=seed, verbose=False, **hp) for m in models]
     elif bob_factory is None and args.attack == "kenansville":
         from .kenansville import Kenansville
         bobs = [Kenansville(task, attack_type, m, seed=seed, verbose=False, **hp) for m in models]
@@ -389,8 +399,12 @@ def main(argv=None, model_factory=None, bob_factory=None):
             true = it["true"] if (task == "CSI" and attack_type == "untargeted") else None
             if args.companions > 0:
                 audio, comp = with_companions(items, idx, args.companions)
-                adv, flag = bob.attack(audio, it["cp_path"], threshold=threshold, true=true, target=it["target"], fs=fs,
-                                       bits_per_sample=bits_per_sample, companions=comp)
+                if hasattr(bob, "attack_universal"):   # (the PGD classes: PGD.attack keeps FakeBob.attack's plain signature)
+                    adv, flag = bob.attack_universal(audio, it["cp_path"], comp, threshold=threshold, true=true, target=it["target"],
+                                                     fs=fs, bits_per_sample=bits_per_sample)
+                else:
+                    adv, flag = bob.attack(audio, it["cp_path"], threshold=threshold, true=true, target=it["target"], fs=fs,
+                                           bits_per_sample=bits_per_sample, companions=comp)
                 write(it["wav_path"], fs, adv)
                 with lock:
                     results[idx] = flag

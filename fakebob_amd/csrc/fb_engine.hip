@@ -243,6 +243,11 @@ struct fb_engine {
   DevBuf wb_feco_k;                    // ... and k per replicated row: the rows the back end scored
   DevBuf wb_xbar;                      // k_wb_feco_t's output [T][dim]: the cotangent on one replica's voiced rows
   int wb_feco_launches = 0;            // k_wb_feco_t launches of the last call (fb_debug_wb_feco_route)
+  // white-box gradients of a universal perturbation (fb_set_wb_universal)
+  int wb_universal = 0;                // the switch: 0 (as created) refuses companions, as before it existed
+  DevBuf wb_uni_cot;                   // the R replicas' cotangents on their composed rows [R][N] (K > 1, no air channel)
+  DevBuf wb_uni_rows;                  // the K composed rows the chain read [K][N] (K > 1 under a chain without an air channel)
+  int wb_universal_launches = 0;       // k_wb_compose_t launches of the last call (fb_debug_wb_universal_route)
   FbNesDev *h_out = nullptr;  // pinned
   int *h_tv = nullptr;        // pinned, grows
   size_t h_tv_cap = 0;
@@ -818,6 +823,7 @@ struct FbScoreCall {
   bool tail_loss_done = false;   // out: it did
   bool feats_given = false;      // e->feats / e->row_off / e->tv already hold the batch's rows: no front end (fb_debug_iv_feat_grad)
   bool keep_iv_quad = false;     // i-vector systems: row 0 of quad as the contraction left it is copied to e->wb_iv_quad (white box)
+  int keep_iv_quad_rows = 1;     // ... rows 0 .. this - 1: every replica's under fb_set_wb_universal
   bool keep_air_sat = false;     // an air channel: k_air_conv also writes its saturation bytes to e->wb_air_sat (white box)
   bool keep_feco = false;        // feature compression: k_feature_compress also writes its final labels, counts and k's to e->wb_feco_* (white box)
   int replicas() const { return K * eot; }
@@ -1207,7 +1213,8 @@ static int run_scoring(fb_engine *e, FbScoreCall &call, int B, int total_frames)
     FB_DBG_SYNC(e, "contract");
     // the solve below factorises quad in place: the white-box adjoint solve takes the matrix from this copy
     if (call.keep_iv_quad)
-      HIPCHK(hipMemcpyAsync(e->wb_iv_quad.p, e->iv_quad.p, sizeof(double) * (size_t)iv.triR, hipMemcpyDeviceToDevice, s));
+      HIPCHK(hipMemcpyAsync(e->wb_iv_quad.p, e->iv_quad.p, sizeof(double) * (size_t)std::min(call.keep_iv_quad_rows, B) * (size_t)iv.triR,
+                            hipMemcpyDeviceToDevice, s));
     // the back-end and, inside the NES loop, the loss body run in the solve kernels' tail (fb_iv_tail.h); FB_IV_TAIL=split
     // keeps the separate k_iv_backend / k_loss launches (A/B, tests: same numbers bit for bit)
     FbIvTail tail = {};
@@ -2350,17 +2357,20 @@ extern "C" int fb_attack_dev(fb_engine *e, const fb_nes_params *p, int S, const 
 // The analytic gradient of the loss with respect to the samples ("white-box gradients" in fakebob_hip.h): GMM-UBM systems on
 // an undefended victim; with fb_set_wb_bpda(e, 1) through an input-transform chain, a codec and EOT replicas as well
 // (BPDA / EOT, the same contract); with fb_set_wb_ivector(e, 1) i-vector-PLDA systems too; with fb_set_wb_air(e, 1) through an
-// over-the-air channel; with fb_set_wb_frontend(e, 1) through feature compression and dither.  Everything else is refused by name.
+// over-the-air channel; with fb_set_wb_frontend(e, 1) through feature compression and dither; with fb_set_wb_universal(e, 1) over
+// the companions of a universal perturbation.  Everything else is refused by name.
 static int wb_check(fb_engine *e, const fb_nes_params *p, const double *audio, int64_t N, fb_nes_params *q) {
   if (!e || !p || !audio) return fb_fail(FB_E_ARG, "null argument");
   if (!e->have_gmm) return fb_fail(FB_E_STATE, "no model loaded");
   if (e->kind != 0 && !e->wb_ivector)
     return fb_fail(FB_E_STATE, "white-box gradients: an i-vector system is loaded (GMM-UBM systems only in this version)");
   // (the forward keeps the selection, posteriors and statistics of ONE row for the backward, not those of r replicas)
-  if (e->kind != 0 && e->eot > 1)
+  // (... unless fb_set_wb_universal: the forward then keeps quad of every replica, and sel / post / the i-vectors are per row anyway)
+  if (e->kind != 0 && e->eot > 1 && !e->wb_universal)
     return fb_fail(FB_E_STATE, "white-box gradients: fb_set_eot(%d) is in force on an i-vector system (per-replica i-vector state is not kept: set 1)", e->eot);
   if (e->eot > 1 && !e->wb_bpda) return fb_fail(FB_E_STATE, "white-box gradients: fb_set_eot(%d) is in force (set 1)", e->eot);
-  if (e->comp_K1 > 0) return fb_fail(FB_E_STATE, "white-box gradients: companions are set (fb_set_companions: clear them)");
+  // (the universal perturbation has the fifth switch, fb_set_wb_universal: refused with the other four on as well)
+  if (e->comp_K1 > 0 && !e->wb_universal) return fb_fail(FB_E_STATE, "white-box gradients: companions are set (fb_set_companions: clear them)");
   if (e->tf.n > 0 && !e->wb_bpda)
     return fb_fail(FB_E_STATE, "white-box gradients: an input-transform chain is set (no BPDA through defences in this version)");
   // (the channel's transpose is a switch of its own, fb_set_wb_air: refused with the other two on as well)
@@ -2386,7 +2396,8 @@ static int wb_prepare(fb_engine *e, int64_t N, int T, bool need_gmm) {
     const FbIvDev &iv = e->iv;
     const size_t npanel = ((size_t)iv.R + 31) / 32;
     FBCHK(e->wb_w.ensure(sizeof(double) * (size_t)iv.S));
-    FBCHK(e->wb_iv_quad.ensure(sizeof(double) * (size_t)iv.triR));
+    // (under fb_set_wb_universal every replica's copy of quad: R * triR doubles, about 20 MB at R = 32 for the recipe's size)
+    FBCHK(e->wb_iv_quad.ensure(sizeof(double) * (size_t)(e->wb_universal ? nes_replicas(e) : 1) * (size_t)iv.triR));
     FBCHK(e->wb_iv_linv.ensure(sizeof(double) * npanel * 32 * 32));
     FBCHK(e->wb_iv_wbar.ensure(sizeof(double) * (size_t)iv.R));
     FBCHK(e->wb_iv_lam.ensure(sizeof(double) * (size_t)iv.R));
@@ -2422,15 +2433,22 @@ static int wb_prepare(fb_engine *e, int64_t N, int T, bool need_gmm) {
   FBCHK(e->wb_dmf.ensure(sizeof(double) * (size_t)T * fe.nc));
   FBCHK(e->wb_dxf.ensure(sizeof(double) * (size_t)T * fe.L));
   FBCHK(e->grad.ensure(sizeof(double) * (size_t)N));
-  if (e->wb_bpda) FBCHK(e->wb_gj.ensure(sizeof(double) * (size_t)N));
-  if (e->wb_air && e->air.L > 0) {  // the r replicas' cotangents are kept for the one k_air_conv_t launch behind the loop
-    FBCHK(e->wb_air_cot.ensure(sizeof(double) * (size_t)e->eot * (size_t)N));
-    if (e->eot > 1) FBCHK(e->wb_air_dx.ensure(sizeof(double) * (size_t)e->eot * (size_t)N));
+  // (the replicas of the one row: the EOT draws, times the utterances of a universal perturbation -- wb_check: only under
+  //  fb_set_wb_universal)
+  const size_t R = (size_t)nes_replicas(e);
+  const bool uni = e->comp_K1 > 0;
+  if (e->wb_bpda || (uni && e->tf.n > 0)) FBCHK(e->wb_gj.ensure(sizeof(double) * (size_t)N));
+  if (e->wb_air && e->air.L > 0) {  // the R replicas' cotangents are kept for the one k_air_conv_t launch behind the loop
+    FBCHK(e->wb_air_cot.ensure(sizeof(double) * R * (size_t)N));
+    if (R > 1) FBCHK(e->wb_air_dx.ensure(sizeof(double) * R * (size_t)N));
+  } else if (uni) {                 // ... and without a channel for k_wb_compose_t
+    FBCHK(e->wb_uni_cot.ensure(sizeof(double) * R * (size_t)N));
+    if (e->tf.n > 0) FBCHK(e->wb_uni_rows.ensure(sizeof(int16_t) * (size_t)(e->comp_K1 + 1) * (size_t)N));
   }
-  if (e->wb_frontend && e->feco_iters > 0) {  // the r replicas' kept assignments, and one replica's cotangent on its voiced rows
-    FBCHK(e->wb_feco_label.ensure(sizeof(int) * (size_t)e->eot * (size_t)T));
-    FBCHK(e->wb_feco_cnt.ensure(sizeof(int) * (size_t)e->eot * (size_t)T));
-    FBCHK(e->wb_feco_k.ensure(sizeof(int) * (size_t)e->eot));
+  if (e->wb_frontend && e->feco_iters > 0) {  // the R replicas' kept assignments, and one replica's cotangent on its voiced rows
+    FBCHK(e->wb_feco_label.ensure(sizeof(int) * R * (size_t)T));
+    FBCHK(e->wb_feco_cnt.ensure(sizeof(int) * R * (size_t)T));
+    FBCHK(e->wb_feco_k.ensure(sizeof(int) * R));
     FBCHK(e->wb_xbar.ensure(sizeof(double) * (size_t)T * fe.dim));
   }
   if (!e->wb_status.p) FBCHK(e->wb_status.ensure(sizeof(int)));
@@ -2456,18 +2474,26 @@ static void wb_launch_iv_backend_t(fb_engine *e, const double *ivec, const int *
 // active list / the i-vector as it left them, quad in e->wb_iv_quad): the adjoint solve lambda = quad^-1 wbar -- the forward's
 // own k_iv_solve_ll on the copy of the matrix, one right-hand side, no prior offset, no tail --, the parameter stream, and the
 // per-frame transpose.  The cotangent on the *n_rows_ptr (<= T) voiced rows lands in e->wb_g.
-static void wb_launch_iv_backward(fb_engine *e, const int *n_rows_ptr, int T, const int *stop) {
+// j, row_base_ptr (fb_set_wb_universal; 0 and null: the one row): replica j of the batch -- ITS copy of quad, ITS i-vector, and ITS
+// rows of feats / sel / post from *row_base_ptr on.  k_iv_solve_ll leaves the zero padding of e->wb_iv_A as it found it, so the
+// replicas' solves follow one another on the one workspace; a solve that fails sets the sticky e->wb_iv_fail, but the matrix is
+// the one the forward factorised, and the forward's own flag (e->iv_fail, every row of the batch) is the one the calls read.
+static void wb_launch_iv_backward(fb_engine *e, const int *n_rows_ptr, int T, const int *stop, int j = 0, const int *row_base_ptr = nullptr) {
   FbIvDev iv0 = e->iv;
+  double *quad = e->wb_iv_quad.as<double>() + (size_t)j * (size_t)e->iv.triR;
+  const double *ivec = e->iv_ivec.as<double>() + (size_t)j * (size_t)e->iv.R;
   iv0.prior_offset = 0.0;   // (the solve adds it to element 0 of the right-hand side and takes it off the solution: lin's, not wbar's)
   const FbIvTail none = {};
-  fb_launch_iv_solve_ll(e->stream, iv0, e->wb_iv_quad.as<double>(), e->wb_iv_wbar.as<double>(), 1, 1, e->wb_iv_A.as<double>(),
+  fb_launch_iv_solve_ll(e->stream, iv0, quad, e->wb_iv_wbar.as<double>(), 1, 1, e->wb_iv_A.as<double>(),
                         e->wb_iv_linv.as<double>(), e->wb_iv_lam.as<double>(), e->wb_iv_fail.as<int>(), none);
   e->wb_route[FB_WB_ROUTE_IV_SOLVE] += 1;
-  fb_launch_wb_iv_stats_t(e->stream, e->iv, e->iv_active.as<int>(), e->wb_iv_lam.as<double>(), e->iv_ivec.as<double>(),
+  // (the active list is the batch's: a superset of every replica's own -- the components none of its frames kept get an Fbar /
+  //  Nbar that k_wb_iv_post_t never reads)
+  fb_launch_wb_iv_stats_t(e->stream, e->iv, e->iv_active.as<int>(), e->wb_iv_lam.as<double>(), ivec,
                           e->wb_iv_fbar.as<double>(), e->wb_iv_npart.as<double>(), e->wb_iv_nbar.as<double>(), stop);
   e->wb_route[FB_WB_ROUTE_IV_STATS_T] += 1;
   fb_launch_wb_iv_post_t(e->stream, e->iv, e->feats.as<float>(), n_rows_ptr, T, e->iv_sel.as<int>(), e->iv_post.as<float>(),
-                         e->wb_iv_fbar.as<double>(), e->wb_iv_nbar.as<double>(), e->wb_g.as<double>(), stop);
+                         e->wb_iv_fbar.as<double>(), e->wb_iv_nbar.as<double>(), e->wb_g.as<double>(), stop, row_base_ptr);
   e->wb_route[FB_WB_ROUTE_IV_POST_T] += 1;
 }
 // the front-end backward of row j of the batch the front end read (`wav`: rows of N samples, T frames each, their MFCC
@@ -2493,16 +2519,28 @@ static void wb_launch_feco_t(fb_engine *e, int j, int T, const int *stop) {
 // the chain read replica j's row of e->wav_air -- intact: a codec behind a chain runs in place on wav_tf -- and k_tf_power
 // summed the channel's output rows, so the row's sum is tf_power[j]; the noise counters are (utterance row 0, replica j)
 // either way (FbTfRnd::pre = r in the forward).
+// With companions (fb_set_wb_universal) j is rho = u * eot + j': without a channel the chain read utterance u's COMPOSED row,
+// which wb_enqueue wrote to e->wb_uni_rows (the forward had it in LDS only), and its SNR power is tf_power[0 * K + u], as the
+// forward indexed it; the noise counters are (utterance row 0, replica rho) there as well.
 static int wb_launch_chain_t(fb_engine *e, const FbRngPoint &pt, int j, int64_t N, const double *cot, double *grad, bool accumulate,
                              const int *stop) {
   const bool air = e->air.L > 0;
+  const int u = e->comp_K1 > 0 ? j / e->eot : 0;
   FbTfRnd rn = fb_tf_rnd(pt, e->eot);
-  rn.power = tf_noise_stages(e->tf, true) > 0 ? e->tf_power.as<unsigned long long>() + (air ? j : 0) : nullptr;
-  const int16_t *row = air ? e->wav_air.as<int16_t>() + (size_t)j * (size_t)N : e->wav.as<int16_t>();
+  rn.power = tf_noise_stages(e->tf, true) > 0 ? e->tf_power.as<unsigned long long>() + (air ? j : u) : nullptr;
+  const int16_t *row = air ? e->wav_air.as<int16_t>() + (size_t)j * (size_t)N
+                           : e->comp_K1 > 0 ? e->wb_uni_rows.as<int16_t>() + (size_t)u * (size_t)N : e->wav.as<int16_t>();
   if (!fb_launch_wb_chain_t(e->stream, e->tf, e->tf_taps.as<double>(), row, N, rn, j, cot, grad, accumulate ? 1 : 0, stop))
     return fb_fail(FB_E_HIP, "k_wb_chain_t: %zu bytes of LDS were refused", fb_wb_chain_t_lds_bytes(e->tf));
   e->wb_route[FB_WB_ROUTE_CHAIN_T] += 1;
   return FB_OK;
+}
+// the composition transposed (fb_set_wb_universal), ONE launch: the R = K * eot cotangents cot [R][N] on the composed rows, the
+// un-replicated q still in e->wav, a_0 and the companions give out [N], rho ascending
+static void wb_launch_compose_t(fb_engine *e, const double *cot, int64_t N, double *out, const int *stop) {
+  fb_launch_wb_compose_t(e->stream, cot, e->wav.as<int16_t>(), e->comp_a0.as<int16_t>(), e->comp_wav.as<int16_t>(), e->comp_K1 + 1, e->eot,
+                         N, out, stop);
+  e->wb_universal_launches += 1;
 }
 // the channel's transpose for all r replicas of the one row (fb_set_wb_air), ONE launch: the cotangents e->wb_air_cot [r][N] on
 // the channel's output, the forward's saturation bytes and the forward's own responses in e->air_taps -- nothing is redrawn --
@@ -2512,7 +2550,8 @@ static void wb_launch_air_t(fb_engine *e, int r, int64_t N, double *out, const i
   fb_launch_air_conv_t(e->stream, e->wb_air_cot.as<double>(), e->wb_air_sat.as<unsigned char>(), r, N, e->air_taps.as<int16_t>(), e->air.L,
                        dx, stop);
   e->wb_air_launches += 1;
-  if (r > 1) fb_launch_air_sum_t(e->stream, dx, r, N, out, stop);
+  if (e->comp_K1 > 0) wb_launch_compose_t(e, dx, N, out, stop);  // (r = K * eot: dx_rho is the cotangent on utterance u(rho)'s composed row)
+  else if (r > 1) fb_launch_air_sum_t(e->stream, dx, r, N, out, stop);
 }
 
 // One white-box iteration on the device-resident adver, asynchronous: the forward of fb_get_grad on ONE row -- the cast
@@ -2529,18 +2568,28 @@ static void wb_launch_air_t(fb_engine *e, int r, int64_t N, double *out, const i
 // With fb_set_wb_frontend on: under feature compression the forward keeps every replica's final labels, counts and k; the back
 // end's backward runs on replica j's k_j centres and k_wb_feco_t takes its cotangent back to the voiced rows (e->wb_xbar), which
 // the front-end backward then reads; under dither the front-end backward gets the forward's key with utterance index j.
+// With fb_set_wb_universal on and companions set: the forward scores the R = K * eot replicas of the composed utterances; replica
+// rho's cotangent on ITS composed row goes to slot rho (of e->wb_uni_cot, or under a channel of e->wb_air_cot), a chain's
+// transpose reading the composed row from e->wb_uni_rows; behind the loop ONE k_wb_compose_t launch masks the companions' clipped
+// samples and sums the slots, rho ascending, into e->grad.  On an i-vector system the forward then keeps quad of all R rows and
+// replica rho takes its own copy, i-vector and rows (k_wb_iv_ctl_rep for its weights) -- which is also what lets fb_set_eot(r > 1)
+// run there without companions.
 static int wb_enqueue(fb_engine *e, const fb_nes_params *q, int64_t N, uint32_t it, bool with_dist, FbCtlDev *ctl, double *trace_dev) {
   const int *stop = ctl ? &ctl->stop : nullptr;
-  const int r = e->eot;  // (companions are refused: the replicas are the EOT draws)
+  // the replicas of the one row: the EOT draws, and under fb_set_wb_universal rho = u * eot + j over the K composed utterances
+  const int K = e->comp_K1 + 1, r = K * e->eot;
+  const bool uni = K > 1;
   int ndp = 0;
   fb_launch_perturb(e->stream, e->adver.as<double>(), with_dist ? e->audio.as<double>() : nullptr, N, 0, q->sigma, q->seed, it,
                     q->stream, nullptr, e->wav.as<int16_t>(), e->dist_part.as<double>(), &ndp, nullptr, stop, nes_bits(q));
   e->pre_iter = -1;
   const FbRngPoint pt{q->seed, q->stream, it, 0};
   FbScoreCall call{pt};
-  call.eot = r;
+  call.eot = e->eot;
+  call.K = K;
   call.stop = stop;
   call.keep_iv_quad = e->kind == 1;
+  call.keep_iv_quad_rows = e->wb_universal ? r : 1;  // (r > 1 on an i-vector system: wb_check, only under fb_set_wb_universal)
   const bool air = e->air.L > 0;  // (wb_check: only under fb_set_wb_air)
   call.keep_air_sat = air;
   const bool feco = e->feco_iters > 0;  // (wb_check: only under fb_set_wb_frontend, like a dither > 0)
@@ -2562,10 +2611,22 @@ static int wb_enqueue(fb_engine *e, const fb_nes_params *q, int64_t N, uint32_t 
   e->nes_route[FB_NES_ROUTE_K_LOSS] += 1;
   // (a codec alone is the identity: the front-end backward writes e->grad -- or, with a channel, its slot of e->wb_air_cot,
   //  where the replicas are summed behind the channel's transpose and an empty chain has nothing to add)
-  const bool through_chain = e->tf.n > 0 || (r > 1 && !air);
+  // (a universal perturbation: every replica's cotangent on ITS composed row goes to slot rho -- of e->wb_air_cot under a
+  //  channel, of e->wb_uni_cot without -- and k_wb_compose_t behind the loop masks and sums them, so an empty chain adds nothing
+  //  here either; a chain without a channel read utterance u's composed row, which existed in the forward's LDS only: the K
+  //  rows are written once per iteration.  At K = 1 none of this is queued.)
+  const bool through_chain = e->tf.n > 0 || (r > 1 && !air && !uni);
+  if (uni && e->tf.n > 0 && !air)
+    fb_launch_wb_compose_rows(e->stream, e->wav.as<int16_t>(), e->comp_a0.as<int16_t>(), e->comp_wav.as<int16_t>(), K, N,
+                              e->wb_uni_rows.as<int16_t>(), stop);
   const int S = fb_num_speakers(e);
   for (int j = 0; j < r; ++j) {
-    if (r > 1) {
+    if (r > 1 && e->kind == 1) {
+      fb_launch_wb_iv_ctl_rep(e->stream, e->eot_sc.as<double>() + (size_t)j * S, e->scores.as<double>(), e->nes_out.as<FbNesDev>(), S, r,
+                              q->task, q->attack_type, e->zstd.as<double>(), q->threshold, q->target, q->true_label,
+                              e->wb_w.as<double>(), ctl, j == 0 ? 1 : 0, trace_dev, (int)it);
+      e->wb_route[FB_WB_ROUTE_CTL_REP] += 1;
+    } else if (r > 1) {
       fb_launch_wb_ctl_rep(e->stream, e->eot_sc.as<double>() + (size_t)j * S, e->scores.as<double>(), e->nes_out.as<FbNesDev>(),
                            e->gmm.M, r, q->task, q->attack_type, e->zstd.as<double>(), q->threshold, q->target, q->true_label,
                            e->wb_w.as<double>(), ctl, j == 0 ? 1 : 0, trace_dev, (int)it);
@@ -2580,7 +2641,10 @@ static int wb_enqueue(fb_engine *e, const fb_nes_params *q, int64_t N, uint32_t 
       e->wb_route[FB_WB_ROUTE_CTL] += 1;
     }
     // (row_off[0] = 0 and tv[0] = row_off[1]: replica 0 of an unreplicated batch is what the launch always took)
-    if (e->kind == 1) {
+    if (e->kind == 1 && r > 1) {  // replica j's own i-vector, quad, rows (under feature compression its k_j centres)
+      wb_launch_iv_backend_t(e, e->iv_ivec.as<double>() + (size_t)j * (size_t)e->iv.R, stop);
+      wb_launch_iv_backward(e, feco ? e->wb_feco_k.as<int>() + j : e->tv.as<int>() + j, T, stop, j, e->row_off.as<int>() + j);
+    } else if (e->kind == 1) {
       wb_launch_iv_backend_t(e, e->iv_ivec.as<double>(), stop);
       wb_launch_iv_backward(e, e->row_off.as<int>() + 1, T, stop);
     } else {
@@ -2590,17 +2654,20 @@ static int wb_enqueue(fb_engine *e, const fb_nes_params *q, int64_t N, uint32_t 
       wb_launch_gmm_backward(e, n_rows, T, stop, r > 1 ? e->row_off.as<int>() + j : nullptr);
     }
     if (feco) wb_launch_feco_t(e, j, T, stop);
-    double *slot = air ? e->wb_air_cot.as<double>() + (size_t)j * (size_t)N : nullptr;  // replica j's cotangent on the channel's output
-    double *fe_out = through_chain ? e->wb_gj.as<double>() : air ? slot : e->grad.as<double>();
+    // replica j's cotangent on the channel's output, or (a universal perturbation without a channel) on its composed row
+    double *slot = air ? e->wb_air_cot.as<double>() + (size_t)j * (size_t)N
+                       : uni ? e->wb_uni_cot.as<double>() + (size_t)j * (size_t)N : nullptr;
+    double *fe_out = through_chain ? e->wb_gj.as<double>() : slot ? slot : e->grad.as<double>();
     FbRngPoint ptj = pt;
     ptj.utt0 = pt.utt0 + (uint32_t)j;   // the forward's dither draws of replicated row j
     const FbDitherKey dith = fb_dither_key(ptj, e->cfg.dither);
     wb_launch_frontend_vjp(e, e->fe_wav, j, N, T, scale, fe_out, stop, feco ? e->wb_xbar.as<double>() : nullptr,
                            e->cfg.dither > 0.0 ? &dith : nullptr);
     e->wb_route[FB_WB_ROUTE_BACKWARD] += 1;
-    if (through_chain) FBCHK(wb_launch_chain_t(e, pt, j, N, e->wb_gj.as<double>(), air ? slot : e->grad.as<double>(), !air && j > 0, stop));
+    if (through_chain) FBCHK(wb_launch_chain_t(e, pt, j, N, e->wb_gj.as<double>(), slot ? slot : e->grad.as<double>(), !slot && j > 0, stop));
   }
   if (air) wb_launch_air_t(e, r, N, e->grad.as<double>(), stop);
+  else if (uni) wb_launch_compose_t(e, e->wb_uni_cot.as<double>(), N, e->grad.as<double>(), stop);
   return FB_OK;
 }
 
@@ -2610,13 +2677,15 @@ static int wb_status_check(fb_engine *e, int status) {
 }
 
 // mirrors FakeBob.get_grad + loss_fn (FAKEBOB.py:223-299) with the analytic gradient in place of the NES estimate
-extern "C" int fb_get_grad_wb_iter(fb_engine *e, const fb_nes_params *p, const double *audio, int64_t N, int iter,
-                                   double *adver_loss, double *grad, double *score0) {
+// original (nullable: audio itself): the audio whose int16 cast is a_0 of the composition (fb_set_wb_universal)
+extern "C" int fb_get_grad_wb_from(fb_engine *e, const fb_nes_params *p, const double *audio, const double *original, int64_t N,
+                                   int iter, double *adver_loss, double *grad, double *score0) {
   if (e) e->bench_it = -1;
   if (e) memset(e->nes_route, 0, sizeof(e->nes_route));
   if (e) memset(e->wb_route, 0, sizeof(e->wb_route));
   if (e) e->wb_air_launches = 0;
   if (e) e->wb_feco_launches = 0;
+  if (e) e->wb_universal_launches = 0;
   if (iter < 0) return fb_fail(FB_E_ARG, "iter must be >= 0");
   fb_nes_params q;
   FBCHK(wb_check(e, p, audio, N, &q));
@@ -2625,6 +2694,10 @@ extern "C" int fb_get_grad_wb_iter(fb_engine *e, const fb_nes_params *p, const d
   FBCHK(ensure_nes_buffers(e, N, 1));
   FBCHK(wb_prepare(e, N, e->h_frame_off[1], true));
   FBCHK(h2d(e, e->adver.p, audio, sizeof(double) * (size_t)N));
+  if (e->comp_K1 > 0) {  // a_0: cast once per call, by the batch's cast rule
+    if (original) FBCHK(h2d(e, e->audio.p, original, sizeof(double) * (size_t)N));
+    cast_a0(e, &q, original ? e->audio.as<double>() : e->adver.as<double>(), N);
+  }
   FBCHK(wb_enqueue(e, &q, N, (uint32_t)iter, false, nullptr, nullptr));
   int status = 0;
   if (grad) FBCHK(d2h(e, grad, e->grad.p, sizeof(double) * (size_t)N));
@@ -2640,9 +2713,56 @@ extern "C" int fb_get_grad_wb_iter(fb_engine *e, const fb_nes_params *p, const d
   if (score0) for (int s = 0; s < fb_num_speakers(e); ++s) score0[s] = e->h_out->score0[s];
   return FB_OK;
 }
+extern "C" int fb_get_grad_wb_iter(fb_engine *e, const fb_nes_params *p, const double *audio, int64_t N, int iter,
+                                   double *adver_loss, double *grad, double *score0) {
+  return fb_get_grad_wb_from(e, p, audio, nullptr, N, iter, adver_loss, grad, score0);
+}
 extern "C" int fb_get_grad_wb(fb_engine *e, const fb_nes_params *p, const double *audio, int64_t N, double *adver_loss,
                               double *grad, double *score0) {
   return fb_get_grad_wb_iter(e, p, audio, N, 0, adver_loss, grad, score0);
+}
+
+extern "C" int fb_set_wb_universal(fb_engine *e, int on) {
+  if (!e) return fb_fail(FB_E_ARG, "null engine");
+  if (on != 0 && on != 1) return fb_fail(FB_E_ARG, "fb_set_wb_universal takes 0 or 1, not %d", on);
+  e->wb_universal = on;
+  return FB_OK;
+}
+
+extern "C" int fb_debug_wb_universal_route(fb_engine *e, int *n_launches) {
+  if (!e || !n_launches) return fb_fail(FB_E_ARG, "null argument");
+  *n_launches = e->wb_universal_launches;
+  return FB_OK;
+}
+
+// Test hook: k_wb_compose_t alone, ONE launch, on arrays handed in: cot [K * eot][n], q / a0 [n], comp [K - 1][n] (K = 1: not read)
+extern "C" int fb_debug_wb_compose_t(fb_engine *e, const double *cot, const int16_t *q, const int16_t *a0, const int16_t *comp, int K,
+                                     int eot, int64_t n, double *grad) {
+  if (!e || !cot || !q || !a0 || !grad || K < 1 || eot < 1 || K * eot > 32 || n <= 0 || (K > 1 && !comp)) return fb_fail(FB_E_ARG, "bad argument");
+  if (n > 0x7fffffffLL) return fb_fail(FB_E_LIMIT, "row longer than 2^31 samples");
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  const size_t R = (size_t)K * (size_t)eot, ns = (size_t)n;
+  DevBuf d_cot, d_q, d_a0, d_comp, d_grad;
+  FBCHK(d_cot.ensure(sizeof(double) * R * ns));
+  FBCHK(d_q.ensure(sizeof(int16_t) * ns));
+  FBCHK(d_a0.ensure(sizeof(int16_t) * ns));
+  FBCHK(d_grad.ensure(sizeof(double) * ns));
+  FBCHK(h2d(e, d_cot.p, cot, sizeof(double) * R * ns));
+  FBCHK(h2d(e, d_q.p, q, sizeof(int16_t) * ns));
+  FBCHK(h2d(e, d_a0.p, a0, sizeof(int16_t) * ns));
+  if (K > 1) {
+    FBCHK(d_comp.ensure(sizeof(int16_t) * (size_t)(K - 1) * ns));
+    FBCHK(h2d(e, d_comp.p, comp, sizeof(int16_t) * (size_t)(K - 1) * ns));
+  }
+  e->wb_universal_launches = 0;
+  fb_launch_wb_compose_t(e->stream, d_cot.as<double>(), d_q.as<int16_t>(), d_a0.as<int16_t>(), K > 1 ? d_comp.as<int16_t>() : nullptr, K, eot, n,
+                         d_grad.as<double>(), nullptr);
+  e->wb_universal_launches += 1;
+  HIPCHK(hipGetLastError());
+  FBCHK(d2h(e, grad, d_grad.p, sizeof(double) * ns));
+  FBCHK(sync_stream(e));
+  return FB_OK;
 }
 
 extern "C" int fb_set_wb_bpda(fb_engine *e, int on) {
@@ -2685,7 +2805,7 @@ extern "C" int fb_debug_wb_feco_state(fb_engine *e, int j, int cap, int *labels,
   if (!e || !labels || !counts || !Tv || !k || cap < 0) return fb_fail(FB_E_ARG, "bad argument");
   if (!e->wb_frontend || e->feco_iters <= 0 || !e->wb_feco_k.p || !e->row_off_fc.p)
     return fb_fail(FB_E_STATE, "no kept assignment: fb_set_wb_frontend, fb_set_feature_compression and a white-box call first");
-  if (j < 0 || j >= e->eot) return fb_fail(FB_E_ARG, "replica %d of %d", j, e->eot);
+  if (j < 0 || j >= nes_replicas(e)) return fb_fail(FB_E_ARG, "replica %d of %d", j, nes_replicas(e));   // (companions: rho of K * eot)
   HIPCHK(hipSetDevice(e->device));
   FBCHK(sync_stream(e));
   int in_off[2], out_off[2], kept = 0;
@@ -2802,6 +2922,7 @@ extern "C" int fb_attack_wb(fb_engine *e, const fb_nes_params *p, const double *
   if (e) memset(e->wb_route, 0, sizeof(e->wb_route));
   if (e) e->wb_air_launches = 0;
   if (e) e->wb_feco_launches = 0;
+  if (e) e->wb_universal_launches = 0;
   if (!adv_i16 || !success_flag) return fb_fail(FB_E_ARG, "null argument");
   fb_nes_params q;
   FBCHK(wb_check(e, p, audio, N, &q));
@@ -2812,6 +2933,7 @@ extern "C" int fb_attack_wb(fb_engine *e, const fb_nes_params *p, const double *
   FBCHK(wb_prepare(e, N, e->h_frame_off[1], true));
   const int S = fb_num_speakers(e);
   FBCHK(attack_start(e, audio, N, 0, nullptr));
+  cast_a0(e, &q, e->audio.as<double>(), N);  // (fb_set_wb_universal: a_0 = the audio the attack was handed, as in fb_attack)
   double *trace_dev = nullptr;
   if (trace) {
     FBCHK(e->trace_dev.ensure(sizeof(double) * (size_t)p->max_iter * (3 + S)));

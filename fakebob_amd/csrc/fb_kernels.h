@@ -349,6 +349,16 @@ size_t fb_wb_chain_t_lds_bytes(const FbTfChain &ch);
 bool fb_launch_wb_chain_t(hipStream_t s, const FbTfChain &ch, const double *taps, const int16_t *wav, int64_t n, const FbTfRnd &rn,
                           int replica, const double *cot, double *grad, int accumulate, const int *stop);
 
+// ---- white-box gradients of a universal perturbation (fb_set_wb_universal; whitebox_universal_kernels.hip) ----------
+// the composition of fb_set_companions transposed, ONE launch for the R = K * eot replicas: grad[i] = sum over rho = u * eot + j,
+// ascending, float64 from +0.0, of cot[rho][i] where u = 0 or comp[u - 1][i] + q[i] - a0[i] (int32) lies inside
+// [-32768, 32767], of +0.0 elsewhere.  cot [R][n], comp [K - 1][n], q / a0 / grad [n]; cot and grad on 16-byte boundaries
+void fb_launch_wb_compose_t(hipStream_t s, const double *cot, const int16_t *q, const int16_t *a0, const int16_t *comp, int K, int eot,
+                            int64_t n, double *grad, const int *stop);
+// rows[K][n]: the composed rows as the forward's tf_composed forms them (row 0 = q), for the chain's transpose
+void fb_launch_wb_compose_rows(hipStream_t s, const int16_t *q, const int16_t *a0, const int16_t *comp, int K, int64_t n, int16_t *rows,
+                               const int *stop);
+
 // ---- white-box gradients through the i-vector-PLDA back end (fb_set_wb_ivector; whitebox_iv_kernels.hip) ------------
 struct FbIvDev;
 // k_wb_ctl for an i-vector system: w[S] = d loss / d raw[s] (every task z-normalises: the 1 / z_std is in w), the same loop control
@@ -364,8 +374,15 @@ int fb_wb_iv_uchunks(const FbIvDev &iv);
 void fb_launch_wb_iv_stats_t(hipStream_t s, const FbIvDev &iv, const int *active, const double *lam, const double *ivec, double *fbar,
                              double *npart, double *nbar, const int *stop);
 // g[t][D] = the cotangent on the voiced feature rows t < *n_rows_ptr (<= rows_cap) from the forward's sel / post [rows][nsel]
+// row_base_ptr (nullable): the first of the rows within feats / sel / post, when they are a replica's within the batch
 void fb_launch_wb_iv_post_t(hipStream_t s, const FbIvDev &iv, const float *feats, const int *n_rows_ptr, int rows_cap, const int *sel,
-                            const float *post, const double *fbar, const double *nbar, double *g, const int *stop);
+                            const float *post, const double *fbar, const double *nbar, double *g, const int *stop,
+                            const int *row_base_ptr = nullptr);
+// k_wb_iv_ctl for replica rho of R > 1 (fb_set_wb_universal; whitebox_universal_kernels.hip): w[S] = the weights of ITS scores
+// rep_scores[S], over R; with do_ctl the loop control on `out` and mean_scores[S] (the means k_loss_eot left) as well
+void fb_launch_wb_iv_ctl_rep(hipStream_t s, const double *rep_scores, const double *mean_scores, const FbNesDev *out, int S, int R,
+                             int task, int attack_type, const double *z_std, double threshold, int target, int true_label, double *w,
+                             FbCtlDev *ctl, int do_ctl, double *trace, int it);
 
 // ---- front-end ------------------------------------------------------------
 // MFCC of every frame of a (ragged) batch.  wav_off[B+1], frame_off[B+1] device arrays.

@@ -1,5 +1,6 @@
-// whitebox_device.h -- the two one-thread bodies of the white-box loop, shared by k_wb_ctl (whitebox_kernels.hip) and its
-// per-replica form k_wb_ctl_rep (whitebox_bpda_kernels.hip).
+// whitebox_device.h -- the one-thread bodies of the white-box loop, shared by k_wb_ctl (whitebox_kernels.hip) and its
+// per-replica form k_wb_ctl_rep (whitebox_bpda_kernels.hip), and by k_wb_iv_ctl (whitebox_iv_kernels.hip) and its per-replica
+// form k_wb_iv_ctl_rep (whitebox_universal_kernels.hip).
 #pragma once
 #include <math.h>
 
@@ -36,6 +37,39 @@ __device__ __forceinline__ void fb_wb_weights(const double *__restrict__ scores,
     w[target] = -1.0 / z_std[target];
     if (j >= 0) w[j] = 1.0 / z_std[j];
   } else {                                                      // (s[true] + kappa) - max_{j != true} s[j]
+    const int j = first_max_but(true_label);
+    w[true_label] = 1.0 / z_std[true_label];
+    if (j >= 0) w[j] = -1.0 / z_std[j];
+  }
+}
+
+// ... for an i-vector system: w[S] = d loss / d raw[s].  Such a system scores (raw[s] - z_mean[s]) / z_std[s] in every task
+// (fb_loss_row, znorm_all), so d loss / d raw[s] = (d loss / d score_s) / z_std[s]; the same first-maximum rule
+__device__ __forceinline__ void fb_wb_iv_weights(const double *__restrict__ scores, int S, int task, int attack_type,
+                                                 const double *__restrict__ z_std, double threshold, int target, int true_label,
+                                                 double *__restrict__ w) {
+  for (int s = 0; s < S; ++s) w[s] = 0.0;
+  auto first_max_but = [&](int skip) -> int {
+    int idx = -1;
+    double om = -INFINITY;
+    for (int m = 0; m < S; ++m)
+      if (m != skip && scores[m] > om) { om = scores[m]; idx = m; }
+    return idx;
+  };
+  if (task == FB_TASK_SV) {                                           // (thr + kappa) - s[0]
+    w[0] = -1.0 / z_std[0];
+  } else if (task == FB_TASK_OSI && attack_type == FB_UNTARGETED) {   // (thr + kappa) - max s
+    const int j = first_max_but(-1);
+    if (j >= 0) w[j] = -1.0 / z_std[j];
+  } else if (task == FB_TASK_OSI) {                                   // (max(max_{j != t} s[j], thr) + kappa) - s[t]
+    const int j = first_max_but(target);
+    w[target] = -1.0 / z_std[target];
+    if (j >= 0 && scores[j] > threshold) w[j] = 1.0 / z_std[j];
+  } else if (attack_type == FB_TARGETED) {                            // (max_{j != t} s[j] + kappa) - s[t]
+    const int j = first_max_but(target);
+    w[target] = -1.0 / z_std[target];
+    if (j >= 0) w[j] = 1.0 / z_std[j];
+  } else {                                                            // (s[true] + kappa) - max_{j != true} s[j]
     const int j = first_max_but(true_label);
     w[true_label] = 1.0 / z_std[true_label];
     if (j >= 0) w[j] = -1.0 / z_std[j];

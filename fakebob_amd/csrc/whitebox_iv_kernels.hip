@@ -18,40 +18,14 @@
 #include "whitebox_device.h"
 
 // ------------------------------------------------------------------------------------------------ weights + loop control
-// One thread.  An i-vector system scores (raw[s] - z_mean[s]) / z_std[s] in every task (fb_loss_row, znorm_all), so
-// d loss / d raw[s] = (d loss / d score_s) / z_std[s]; the maxima take the FIRST maximal index, as fb_wb_weights.
+// One thread.  The weights are whitebox_device.h's fb_wb_iv_weights (the 1 / z_std inside, first-maximum index).
 __global__ __launch_bounds__(64) void k_wb_iv_ctl(const double *__restrict__ scores, const FbNesDev *__restrict__ out, int S, int task,
                                                   int attack_type, const double *__restrict__ z_std, double threshold, int target,
                                                   int true_label, double *__restrict__ w, FbCtlDev *__restrict__ ctl,
                                                   double *__restrict__ trace, int it) {
   if (threadIdx.x != 0) return;
   if (ctl && ctl->stop) return;
-  for (int s = 0; s < S; ++s) w[s] = 0.0;
-  auto first_max_but = [&](int skip) -> int {
-    int idx = -1;
-    double om = -INFINITY;
-    for (int m = 0; m < S; ++m)
-      if (m != skip && scores[m] > om) { om = scores[m]; idx = m; }
-    return idx;
-  };
-  if (task == FB_TASK_SV) {                                           // (thr + kappa) - s[0]
-    w[0] = -1.0 / z_std[0];
-  } else if (task == FB_TASK_OSI && attack_type == FB_UNTARGETED) {   // (thr + kappa) - max s
-    const int j = first_max_but(-1);
-    if (j >= 0) w[j] = -1.0 / z_std[j];
-  } else if (task == FB_TASK_OSI) {                                   // (max(max_{j != t} s[j], thr) + kappa) - s[t]
-    const int j = first_max_but(target);
-    w[target] = -1.0 / z_std[target];
-    if (j >= 0 && scores[j] > threshold) w[j] = 1.0 / z_std[j];
-  } else if (attack_type == FB_TARGETED) {                            // (max_{j != t} s[j] + kappa) - s[t]
-    const int j = first_max_but(target);
-    w[target] = -1.0 / z_std[target];
-    if (j >= 0) w[j] = 1.0 / z_std[j];
-  } else {                                                            // (s[true] + kappa) - max_{j != true} s[j]
-    const int j = first_max_but(true_label);
-    w[true_label] = 1.0 / z_std[true_label];
-    if (j >= 0) w[j] = -1.0 / z_std[j];
-  }
+  fb_wb_iv_weights(scores, S, task, attack_type, z_std, threshold, target, true_label, w);
   // (fb_wb_loop_control counts M - 1 scores outside CSI: hand it the M that gives S)
   if (ctl) fb_wb_loop_control(scores, out, task == FB_TASK_CSI ? S : S + 1, task, ctl, trace, it);
 }
@@ -317,13 +291,16 @@ void fb_launch_wb_iv_stats_t(hipStream_t s, const FbIvDev &iv, const int *active
 __global__ __launch_bounds__(256) void k_wb_iv_post_t(FbIvDev iv, const float *__restrict__ feats, const int *__restrict__ n_rows_ptr,
                                                       int rows_cap, const int *__restrict__ sel, const float *__restrict__ post,
                                                       const double *__restrict__ fbar, const double *__restrict__ nbar,
-                                                      double *__restrict__ g, const int *__restrict__ stop) {
+                                                      double *__restrict__ g, const int *__restrict__ stop,
+                                                      const int *__restrict__ row_base_ptr) {
   if (stop && *stop) return;
   __shared__ double xs[4][128];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int row = blockIdx.x * 4 + wv;
+  const int out_row = blockIdx.x * 4 + wv;
   const int n_rows = min(*n_rows_ptr, rows_cap);
-  if (row >= n_rows) return;   // (wave-uniform; no workgroup barrier below)
+  if (out_row >= n_rows) return;   // (wave-uniform; no workgroup barrier below)
+  // (row_base_ptr: the rows are a replica's within the batch -- feats / sel / post are read from there, g is the replica's own)
+  const int row = out_row + (row_base_ptr ? *row_base_ptr : 0);
   const int D = iv.D, nsel = iv.nsel, triD = iv.triD;
   double *x = xs[wv];
   for (int d = lane; d < 128; d += 64) x[d] = d < D ? (double)feats[(size_t)row * D + d] : 0.0;
@@ -374,12 +351,13 @@ __global__ __launch_bounds__(256) void k_wb_iv_post_t(FbIvDev iv, const float *_
       }
     }
   }
-  if (d0 < D) g[(size_t)row * D + d0] = o0;
-  if (two) g[(size_t)row * D + d1] = o1;
+  if (d0 < D) g[(size_t)out_row * D + d0] = o0;
+  if (two) g[(size_t)out_row * D + d1] = o1;
 }
 void fb_launch_wb_iv_post_t(hipStream_t s, const FbIvDev &iv, const float *feats, const int *n_rows_ptr, int rows_cap, const int *sel,
-                            const float *post, const double *fbar, const double *nbar, double *g, const int *stop) {
+                            const float *post, const double *fbar, const double *nbar, double *g, const int *stop,
+                            const int *row_base_ptr) {
   if (rows_cap <= 0) return;
   hipLaunchKernelGGL(k_wb_iv_post_t, dim3((rows_cap + 3) / 4), dim3(256), 0, s, iv, feats, n_rows_ptr, rows_cap, sel, post, fbar, nbar,
-                     g, stop);
+                     g, stop, row_base_ptr);
 }

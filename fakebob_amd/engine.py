@@ -61,6 +61,7 @@ class Engine(object):
         self.wb_ivector = False
         self.wb_air = False
         self.wb_frontend = False
+        self.wb_universal = False
         self.companions = None
         self.feature_compression = None
 
@@ -586,6 +587,39 @@ class Engine(object):
         N.check(self._L.fb_set_wb_frontend(self._h, C.c_int(1 if on is True else 0 if on is False else int(on))))
         self.wb_frontend = bool(on)
 
+    def set_wb_universal(self, on):
+        """fb_set_wb_universal: with True, get_grad_wb and attack_wb accept the companions of set_companions on a GMM-UBM
+        system: the exact gradient of the loss averaged over the K utterances one perturbation is scored on, through the
+        composition's clip (a clipped sample passes zero; the rules are in include/fakebob_hip.h).  Companions need no other
+        switch at eot = 1; a chain, a codec and r > 1 still need set_wb_bpda(True), an air channel set_wb_air(True), feature
+        compression and dither set_wb_frontend(True).  False (as created): companions are refused and nothing else changes.
+        0 / 1 and booleans only; anything else is handed to the library, which refuses it."""
+        N.check(self._L.fb_set_wb_universal(self._h, C.c_int(1 if on is True else 0 if on is False else int(on))))
+        self.wb_universal = bool(on)
+
+    def debug_wb_universal_route(self):
+        """k_wb_compose_t launches of the last get_grad_wb / attack_wb / debug_wb_compose_t call
+        (fb_debug_wb_universal_route): one per iteration with companions set, none without."""
+        n = C.c_int(0)
+        N.check(self._L.fb_debug_wb_universal_route(self._h, C.byref(n)))
+        return int(n.value)
+
+    def debug_wb_compose_t(self, cot, q, a0, comp, eot=1):
+        """k_wb_compose_t alone (fb_debug_wb_compose_t): float64 cotangents (K * eot, n), int16 q (n,), a0 (n,) and companions
+        (K - 1, n) -> grad (n,) float64: the replicas' cotangents summed, rho ascending, a companion's clipped samples masked."""
+        q = np.ascontiguousarray(q, np.int16).reshape(-1)
+        a0 = np.ascontiguousarray(a0, np.int16).reshape(-1)
+        n = q.size
+        comp = np.ascontiguousarray(comp, np.int16).reshape(-1, n) if comp is not None and np.size(comp) else None
+        K = 1 if comp is None else comp.shape[0] + 1
+        cot = np.ascontiguousarray(cot, np.float64).reshape(K * int(eot), n)
+        if a0.size != n:
+            raise ValueError("a0 has %d samples, q %d" % (a0.size, n))
+        grad = np.empty(n, np.float64)
+        N.check(self._L.fb_debug_wb_compose_t(self._h, N.ptr(cot), N.ptr(q), N.ptr(a0), None if comp is None else N.ptr(comp),
+                                              C.c_int(K), C.c_int(int(eot)), C.c_int64(n), N.ptr(grad)))
+        return grad
+
     def debug_wb_feco_route(self):
         """k_wb_feco_t launches of the last get_grad_wb / attack_wb / debug_feature_compress_vjp call
         (fb_debug_wb_feco_route): r per iteration with feature compression on, none otherwise."""
@@ -642,14 +676,29 @@ class Engine(object):
         feature compression, dither or companions are set; an input transform, a codec and EOT only after set_wb_bpda(True).
         After set_wb_ivector(True) an i-vector system is differentiated as well (never with set_eot > 1); after
         set_wb_air(True) an air channel is too (the forward's drawn responses transposed); after set_wb_frontend(True) feature
-        compression and dither are (the forward's final assignment and its dither draws held constant)."""
+        compression and dither are (the forward's final assignment and its dither draws held constant); after
+        set_wb_universal(True) companions are: the gradient of the mean loss over the K utterances, a_0 of the composition being
+        the cast of `audio` itself (get_grad_wb_from: a_0 given)."""
+        return self.get_grad_wb_from(params, audio, None, iter, want_grad)
+
+    def get_grad_wb_from(self, params, audio, original=None, iter=0, want_grad=True):
+        """fb_get_grad_wb_from: get_grad_wb_iter with a_0 of the composition given (set_wb_universal, set_companions): original
+        (None: audio itself, the call is then fb_get_grad_wb_iter) is the audio whose int16 cast is a_0, as the attack's start
+        is in attack_wb -- audio - original is the perturbation the companions carry.  Without companions it is not read."""
         audio = np.ascontiguousarray(audio, np.float64).reshape(-1)
         n = audio.size
         grad = np.empty(n, np.float64) if want_grad else None
         al = C.c_double()
         sc = np.empty(max(self.n_speakers, 1), np.float64)
-        N.check(self._L.fb_get_grad_wb_iter(self._h, C.byref(params), N.ptr(audio), C.c_int64(n), C.c_int(int(iter)), C.byref(al),
-                                            None if grad is None else N.ptr(grad), N.ptr(sc)))
+        if original is None:
+            N.check(self._L.fb_get_grad_wb_iter(self._h, C.byref(params), N.ptr(audio), C.c_int64(n), C.c_int(int(iter)), C.byref(al),
+                                                None if grad is None else N.ptr(grad), N.ptr(sc)))
+            return grad, al.value, sc
+        original = np.ascontiguousarray(original, np.float64).reshape(-1)
+        if original.size != n:
+            raise ValueError("original has %d samples, audio %d" % (original.size, n))
+        N.check(self._L.fb_get_grad_wb_from(self._h, C.byref(params), N.ptr(audio), N.ptr(original), C.c_int64(n), C.c_int(int(iter)),
+                                            C.byref(al), None if grad is None else N.ptr(grad), N.ptr(sc)))
         return grad, al.value, sc
 
     def attack_wb(self, params, audio):

@@ -9,7 +9,9 @@ defended one (Engine.set_wb_bpda): BPDA through the model's input-transform chai
 expectation over r draws of its random stages per iteration, keyed by the attack's seed and stream.  The air channel is
 refused unless air=True (Engine.set_wb_air: the gradient through the drawn rooms, with eot_size = r the EOT-over-rooms
 gradient of the robust over-the-air attack); feature compression and dither are refused unless frontend=True
-(Engine.set_wb_frontend: the forward's final k-means assignment and its dither draws held constant); companions stay refused, as are i-vector
+(Engine.set_wb_frontend: the forward's final k-means assignment and its dither draws held constant); companions are refused
+unless universal=True (Engine.set_wb_universal: attack(..., companions=[...]) then takes the gradient of the loss averaged over
+the utterances -- the white-box twin of FakeBob.attack(..., companions=)); refused as well are i-vector
 systems and foreign models -- the gradient is that of this library's own forward.  IvectorPGD is the same attack on an i-vector-PLDA system (Engine.set_wb_ivector): the
 gradient through the PLDA back end, both length normalisations, the posterior solve and the full-covariance posteriors, with
 the frames' component selection and pruned sets held constant; PGD and AdaptivePGD keep refusing such a system.
@@ -39,6 +41,7 @@ class PGD(object):
         self.bpda = False   # (AdaptivePGD: True -- the engine's switch is on and seed / stream key the victim's draws)
         self.air = False    # (air=True of AdaptivePGD / IvectorPGD: Engine.set_wb_air is on; seed / stream key the rooms)
         self.frontend = False   # (frontend=True of the two: Engine.set_wb_frontend is on; seed / stream key the k-means and dither draws)
+        self.universal = False  # (universal=True of AdaptivePGD: Engine.set_wb_universal is on; attack() takes companions)
         self.eot_size = 1
         self.task = task
         self.attack_type = attack_type
@@ -99,15 +102,43 @@ class PGD(object):
     def attack(self, audio, checkpoint_path, threshold=0., true=None, target=None, fs=16000, bits_per_sample=16, n_jobs=10,
                debug=False):
         """FakeBob.attack's signature and results: (int16 adversarial audio (N,1), success_flag +-1), and the trace
-        [distance, adver_loss, score, used_time] per iteration pickled to checkpoint_path (protocol -1)."""
+        [distance, adver_loss, score, used_time] per iteration pickled to checkpoint_path (protocol -1).  The pair is a
+        companions.AttackResult, as FakeBob.attack's is: it also carries perturbation_i16 and apply_perturbation(wavs).  PGD
+        The signature is FakeBob.attack's without its extensions: companions go through attack_universal."""
+        return self._attack(audio, checkpoint_path, threshold, true, target, fs, bits_per_sample, n_jobs, debug, None)
+
+    def attack_universal(self, audio, checkpoint_path, companions, threshold=0., true=None, target=None, fs=16000, bits_per_sample=16,
+                         n_jobs=10, debug=False):
+        """attack() with FakeBob.attack's companions, for the classes that take universal=True (AdaptivePGD, whose attack() also
+        has the keyword, and IvectorPGD); ValueError without it."""
+        return self._attack(audio, checkpoint_path, threshold, true, target, fs, bits_per_sample, n_jobs, debug, companions)
+
+    def _attack(self, audio, checkpoint_path, threshold, true, target, fs, bits_per_sample, n_jobs, debug, companions):
+        """attack() with FakeBob.attack's companions (universal=True only; ValueError otherwise): utterances as long as `audio`
+        that ride along for this call, ONE perturbation over all of them, the loop's losses their means; the result then also
+        carries per_utterance -- every composed utterance re-scored through model.make_decisions, with its success."""
         audio = _col(audio)
         bits = _check_bits(bits_per_sample)
+        from . import companions as CP
+        comp = None
+        if companions is not None:
+            if not self.universal:
+                raise ValueError("PGD: companions need universal=True (AdaptivePGD / IvectorPGD: Engine.set_wb_universal)")
+            comp = CP.as_companions(companions, audio.shape[0], bits)
         self.threshold = threshold
         self.true = true
         self.target = target
         eng = self.model.engine
         t0 = time.time()
-        adv, flag, _advf, trace = eng.attack_wb(self._params(bits), audio[:, 0])
+        if companions is None:
+            adv, flag, _advf, trace = eng.attack_wb(self._params(bits), audio[:, 0])
+        else:
+            before = eng.companions
+            eng.set_companions(comp)
+            try:
+                adv, flag, _advf, trace = eng.attack_wb(self._params(bits), audio[:, 0])
+            finally:
+                eng.set_companions(before)
         dt = time.time() - t0
         n = trace.shape[0]
         used_time = eng.attack_iter_seconds(n)
@@ -122,7 +153,17 @@ class PGD(object):
         if self.verbose:
             print("--- %d iters, distance:%f, loss:%f, %.1f iters/s ---" %
                   (n, trace[-1, 0], trace[-1, 1], n / dt if dt > 0 else 0.0))
-        return adv[:, np.newaxis], flag
+        a0 = CP.cast_i16(audio[:, 0], bits)
+        delta = adv.astype(np.int32) - a0.astype(np.int32)
+        per = None
+        if comp is not None:
+            kw = dict(fs=fs, bits_per_sample=bits_per_sample, n_jobs=n_jobs, debug=debug)
+            per = []
+            for u, w in enumerate([adv] + CP.apply_perturbation(delta, list(comp))):
+                dec, sc = self.model.make_decisions(w, **kw)
+                per.append(dict(utterance=u, audio_i16=w, decision=dec, score=sc,
+                                success=CP.succeeded(self.task, self.attack_type, dec, target=target, true=true)))
+        return CP.AttackResult(adv[:, np.newaxis], flag, delta, bits, per)
 
 
 class AdaptivePGD(PGD):
@@ -134,9 +175,11 @@ class AdaptivePGD(PGD):
     switches the engine to differentiate through the model's over-the-air channel (Engine.set_wb_air): each iteration then
     takes the gradient through the eot_size rooms its forward drew.  frontend=True switches it to differentiate through the
     model's feature compression and dither (Engine.set_wb_frontend): the gradient at the k-means assignment and the dither
-    draws of each of the eot_size forwards."""
+    draws of each of the eot_size forwards.  universal=True switches it to take companions (Engine.set_wb_universal):
+    attack(..., companions=[...]) then descends the loss averaged over the utterances (times the eot_size draws of each); it needs
+    no other switch on an undefended victim (bpda=False)."""
 
-    def __init__(self, task, attack_type, model, bpda=True, eot_size=1, air=False, frontend=False, **kw):
+    def __init__(self, task, attack_type, model, bpda=True, eot_size=1, air=False, frontend=False, universal=False, **kw):
         eot_size = int(eot_size)
         if not 1 <= eot_size <= 32:
             raise ValueError("AdaptivePGD: eot_size %d outside 1 .. 32" % eot_size)
@@ -155,19 +198,35 @@ class AdaptivePGD(PGD):
         self.frontend = bool(frontend)
         if self.frontend:
             model.engine.set_wb_frontend(True)
+        self.universal = bool(universal)
+        if self.universal:
+            model.engine.set_wb_universal(True)
+
+    def attack(self, audio, checkpoint_path, threshold=0., true=None, target=None, fs=16000, bits_per_sample=16, n_jobs=10,
+               debug=False, companions=None):
+        """PGD.attack with FakeBob.attack's companions (universal=True; ValueError otherwise): the same setting and clearing of
+        the engine's companions for this call, the same AttackResult with per_utterance."""
+        return self._attack(audio, checkpoint_path, threshold, true, target, fs, bits_per_sample, n_jobs, debug, companions)
 
 
 class IvectorPGD(PGD):
     """PGD on an i-vector-PLDA victim (and, unchanged, on a GMM-UBM one).  The constructor switches the model's engine to
     differentiate through the i-vector back end (Engine.set_wb_ivector; the rules are in include/fakebob_hip.h) and, with
-    bpda=True, through an input-transform chain and a codec as well (Engine.set_wb_bpda); both stay set.  There is no
-    expectation over transformation for an i-vector system.  air=True: through the model's over-the-air channel too
-    (Engine.set_wb_air), one room per iteration; frontend=True: through feature compression and dither
-    (Engine.set_wb_frontend), one draw per iteration.  Knobs, attack(), get_grad(), estimate_threshold(), the return pair and the
+    bpda=True, through an input-transform chain and a codec as well (Engine.set_wb_bpda); both stay set.  air=True: through the
+    model's over-the-air channel too (Engine.set_wb_air); frontend=True: through feature compression and dither
+    (Engine.set_wb_frontend).  universal=True (Engine.set_wb_universal): attack_universal(audio, cp, companions) descends the loss
+    averaged over the utterances, and -- the forward then keeps every replica's i-vector state -- eot_size = r > 1 takes the expectation
+    over r draws of the random stages per iteration (with bpda=True, as in AdaptivePGD).  Without it there is no expectation
+    over transformation for an i-vector system.  Knobs, attack(), get_grad(), estimate_threshold(), the return pair and the
     checkpoint layout are PGD's."""
     KINDS = ("gmm", "iv")
 
-    def __init__(self, task, attack_type, model, bpda=False, air=False, frontend=False, **kw):
+    def __init__(self, task, attack_type, model, bpda=False, air=False, frontend=False, universal=False, eot_size=1, **kw):
+        eot_size = int(eot_size)
+        if not 1 <= eot_size <= 32:
+            raise ValueError("IvectorPGD: eot_size %d outside 1 .. 32" % eot_size)
+        if eot_size > 1 and not (universal and bpda):
+            raise ValueError("IvectorPGD: eot_size %d needs universal=True (per-replica i-vector state) and bpda=True" % eot_size)
         PGD.__init__(self, task, attack_type, model, **kw)
         self.bpda = bool(bpda)
         model.engine.set_wb_ivector(True)
@@ -179,3 +238,9 @@ class IvectorPGD(PGD):
         self.frontend = bool(frontend)
         if self.frontend:
             model.engine.set_wb_frontend(True)
+        self.universal = bool(universal)
+        if self.universal:
+            model.engine.set_wb_universal(True)
+            self.eot_size = eot_size
+            if self.bpda:
+                model.engine.set_eot(eot_size)

@@ -634,6 +634,45 @@ int fb_attack_kenansville(fb_engine *e, const fb_nes_params *p, const fb_kv_para
  * dithered sample in float64.  The noise is additive: the derivative with respect to the sample is unchanged.
  * EOT: replica j uses its own labels and its own dither; grad = sum_j grad_j, j ascending.  The same call on a fresh engine
  * gives the same bits.
+ * Universal perturbations (fb_set_wb_universal).  The white-box twin of fb_set_companions: the exact gradient of the loss
+ * averaged over the K = K1 + 1 utterances one delta is scored on, behind a fifth switch: fb_set_wb_universal(e, on), on = 0 or 1
+ * (anything else: FB_E_ARG, the setting stays), 0 at engine creation, kept across fb_load_*.  With 0 every call, launch, value
+ * and refusal message is what it was before the switch existed: companions are refused whatever the other four switches say.
+ * With 1 and no companions set (K = 1) the calls queue exactly the launches they queued before.  With 1 and companions set,
+ * fb_get_grad_wb, fb_get_grad_wb_iter, fb_get_grad_wb_from and fb_attack_wb accept them.
+ * Forward.  The engine's own, unchanged: it scores R = K * eot replicas of the one row, replica rho = u * eot + j being the rho
+ * of the Composition, Row order and Averaging paragraphs.  adver_loss and score0 are bit for bit fb_get_grad's at
+ * samples_per_draw = 0 with the same iter, seed, stream, settings and a_0.
+ * Backward.  The gradient of the AVERAGED loss: replica rho's weights are w_rho[M] / R, from its own scores (k_wb_ctl_rep with R
+ * where it takes r).  Each replica goes through the backward above for the defences set, keyed by rho where it is keyed by j:
+ * the noise and dither draws, feature compression's kept labels, counts and k, the room response and its saturation bytes; the
+ * chain's transpose runs on the row the chain read -- utterance u(rho)'s composed row, or with an air channel the channel's
+ * output row rho -- with that row's SNR power.  This yields g_rho[i], the cotangent on sample i of the composed row of
+ * utterance u(rho) as it was handed to the air channel, the chain or the front end.
+ * Composition transposed.  The saturation rule above, decided on the exact integer (a sample AT a rail that was not clipped
+ * passes): m_0[i] = 1; for u >= 1, m_u[i] = 1 where v = a_u[i] + q[i] - a_0[i], in int32, lies inside [-32768, 32767], and 0
+ * elsewhere (q: the int16 cast of the call's audio; a_0 is a constant).  Then (k_wb_compose_t, one launch)
+ *     grad[i] = sum_rho m_{u(rho)}[i] * g_rho[i]
+ * in float64, rho ascending, one rounding per addition, starting from +0.0; a masked term adds +0.0.  No atomics: the same
+ * call on a fresh engine gives the same bits.  The 2^(bits_per_sample - 1) scale of the cast is applied where the front-end
+ * backward applies it without companions.
+ * a_0.  In fb_get_grad_wb and fb_get_grad_wb_iter a_0 is the cast of the call's own audio, so q = a_0, every composed row is
+ * the companion itself and no sample clips.  fb_get_grad_wb_from(e, p, audio, original, N, iter, ...) is fb_get_grad_wb_iter
+ * with a_0 given: original, float64 [N], is cast once, by the batch's cast rule, and becomes a_0; original == NULL means audio,
+ * and the call is then fb_get_grad_wb_iter.  Without companions original is not read.  fb_attack_wb keeps a_0 = the audio it
+ * was handed, as fb_attack does; its stop test reads the mean over the replicas and its trace rows hold the averaged scores.
+ * What each setting needs, each refusal naming its cause: companions need this switch only (at eot = 1 the gradient at a fixed
+ * victim is exact); a chain, a codec and fb_set_eot(r > 1) still need fb_set_wb_bpda, an air channel fb_set_wb_air, feature
+ * compression and dither fb_set_wb_frontend, an i-vector system fb_set_wb_ivector.
+ * i-vector systems.  With this switch on the forward keeps the contraction's matrix (quad) of ALL R rows -- R * R_iv (R_iv + 1) / 2
+ * float64, about 20 MB at R = 32 for the recipe's size -- and replica rho's backward takes ITS weights (k_wb_iv_ctl_rep: k_wb_iv_ctl's
+ * with R), ITS i-vector, ITS copy of quad for the adjoint solve, and ITS rows of the selection and the posteriors; the forward's
+ * active list is the batch's, a superset of every replica's.  So an i-vector system then takes companions, and -- with or without
+ * companions -- fb_set_eot(r > 1) under fb_set_wb_bpda, as a GMM-UBM system does; with the switch off both stay refused by the
+ * messages of "The i-vector-PLDA victim" below.
+ * Limits.  K * eot <= 32 (FB_E_ARG at the setters), N must equal the companions' N (FB_E_ARG), FB_E_NO_VOICED if any composed
+ * row has no voiced frames -- all as in fb_get_grad.  fb_attack_pso, fb_attack_kenansville and fb_estimate_threshold still
+ * refuse companions; foreign models ignore them, as before.
  *
  * The i-vector-PLDA victim (fb_set_wb_ivector).  A second switch, for the same reason as the first: fb_set_wb_ivector(e, on),
  * on = 0 or 1 (anything else: FB_E_ARG, the setting stays), 0 at engine creation, kept across fb_load_*.  With 0 every call,
@@ -663,14 +702,17 @@ int fb_attack_kenansville(fb_engine *e, const fb_nes_params *p, const fb_kv_para
  *     xbar_t = sum_k gamma_tk Fbar_k + sum_k llbar_tk (Sigma_k^-1 mu_k - Sigma_k^-1 x_t);
  * then the front-end backward above, unchanged.  adver_loss and score0 are bit for bit fb_get_grad's at samples_per_draw = 0:
  * the same scoring call.  fb_attack_wb is the same loop, trace layout and stop test.
- * Refused for an i-vector system with the switch on, FB_E_STATE, the cause named: companions, an air channel (unless fb_set_wb_air), feature
+ * Refused for an i-vector system with the switch on, FB_E_STATE, the cause named: companions (unless fb_set_wb_universal), an air channel (unless fb_set_wb_air), feature
  * compression and dither > 0 (unless fb_set_wb_frontend), and fb_set_eot(r > 1) -- the last with fb_set_wb_bpda on as well ("i-vector", "fb_set_eot": the
- * forward keeps one row's i-vector state, not r replicas').  An input-transform chain and a codec need fb_set_wb_bpda(e, 1), as
+ * forward keeps one row's i-vector state, not r replicas' -- unless fb_set_wb_universal, "Universal perturbations" above).  An input-transform chain and a codec need fb_set_wb_bpda(e, 1), as
  * for a GMM-UBM system, and are then taken at r = 1.  FB_E_NO_VOICED and the "not positive definite" error are scoring's. */
 int fb_set_wb_bpda(fb_engine *e, int on);
 int fb_set_wb_ivector(fb_engine *e, int on);
 int fb_set_wb_air(fb_engine *e, int on);
 int fb_set_wb_frontend(fb_engine *e, int on);
+int fb_set_wb_universal(fb_engine *e, int on);
+int fb_get_grad_wb_from(fb_engine *e, const fb_nes_params *p, const double *audio, const double *original /*[N], nullable*/,
+                        int64_t N, int iter, double *adver_loss, double *grad /*[N], nullable*/, double *score0 /*[S]*/);
 int fb_get_grad_wb_iter(fb_engine *e, const fb_nes_params *p, const double *audio, int64_t N, int iter, double *adver_loss,
                         double *grad /*[N], nullable*/, double *score0 /*[S]*/);
 int fb_get_grad_wb(fb_engine *e, const fb_nes_params *p, const double *audio, int64_t N, double *adver_loss,

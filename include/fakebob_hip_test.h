@@ -365,10 +365,21 @@ int fb_debug_feature_compress_vjp(fb_engine *e, const float *feats, const int *r
                                   uint32_t stream, uint32_t epoch, const double *cots, int cot_rows, int *out_off, int *labels,
                                   int *counts, double *xbar);
 int fb_debug_wb_feco_route(fb_engine *e, int *n_launches);
-/* fb_debug_wb_feco_state: what the forward of the last fb_get_grad_wb* call kept of replica j (0 <= j < the EOT size), read
+/* fb_debug_wb_feco_state: what the forward of the last fb_get_grad_wb* call kept of replica j (0 <= j < the EOT size; with companions rho of K * eot), read
  * before any other scoring call: *Tv voiced rows, *k centres, labels[*Tv], counts[*k]; cap = the ints either array holds
  * (FB_E_ARG when too few).  FB_E_STATE without the switch, the stage and such a call. */
 int fb_debug_wb_feco_state(fb_engine *e, int j, int cap, int *labels, int *counts, int *Tv, int *k);
+
+/* White-box gradients of a universal perturbation (fakebob_hip.h: fb_set_wb_universal).
+ * fb_debug_wb_compose_t: k_wb_compose_t alone, ONE launch, on arrays handed in as they are: cot[K * eot][n] float64, q[n], a0[n]
+ * and comp[K - 1][n] int16 (K = 1: comp is not read), K >= 1, eot >= 1, K * eot <= 32, n >= 1; grad[n] = the sum of the
+ * "Composition transposed" rule.  The engine's settings are neither used nor changed.
+ * fb_debug_wb_universal_route: *n_launches = the k_wb_compose_t launches the last fb_get_grad_wb* / fb_attack_wb /
+ * fb_debug_wb_compose_t call enqueued -- one per iteration with companions set, none at K = 1.  (Not an index of
+ * fb_debug_wb_route: FB_WB_ROUTE_N stays 9.) */
+int fb_debug_wb_compose_t(fb_engine *e, const double *cot /*[K*eot][n]*/, const int16_t *q, const int16_t *a0,
+                          const int16_t *comp /*[K-1][n], nullable at K = 1*/, int K, int eot, int64_t n, double *grad /*[n]*/);
+int fb_debug_wb_universal_route(fb_engine *e, int *n_launches);
 
 /* White-box gradients through the i-vector-PLDA back end (fakebob_hip.h: fb_set_wb_ivector).  Both hooks need a loaded i-vector
  * system (FB_E_STATE otherwise) and run whatever the switch says, with exactly the launches an attack iteration runs for
