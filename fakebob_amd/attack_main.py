@@ -195,13 +195,21 @@ def main(argv=None, model_factory=None, bob_factory=None):
                     help="universal perturbation: the next N utterances of the same speaker in the data directory ride along "
                          "with every attacked one (1 .. 31, times --eot-size at most 32); all are cropped to the shortest, "
                          "which is printed; default: 0")
-    ap.add_argument("--attack", default="nes", choices=["nes", "pso", "kenansville", "pgd"],
+    ap.add_argument("--attack", default="nes", choices=["nes", "pso", "kenansville", "pgd", "cw2"],
                     help="the search: FAKEBOB's NES gradient estimate (default), SirenAttack's particle swarm "
                          "(fakebob_amd/pso.py; -epsilon, -max_iter, -adver and --seed apply, the other NES options do not), "
                          "Kenansville's decision-only spectral removal (fakebob_amd/kenansville.py; --kv-* and --seed apply) or the "
                          "white-box gradient attack (fakebob_amd/pgd.py: the analytic gradient of a GMM-UBM system in FAKEBOB's "
                          "loop; -momentum 0 is PGD, -max_iter 1 the single step; -samples and -sigma do not apply; an undefended "
-                         "victim unless --bpda is given)")
+                         "victim unless --bpda is given); cw2: Carlini-Wagner's L2 attack on the same gradient "
+                         "(fakebob_amd/cw2.py: tanh space, Adam, a binary search over the constant; it minimises the distortion; "
+                         "-max_iter counts the iterations of one search step, -adver is CW's confidence, --cw2-* apply; --bpda "
+                         "--eot-size and -archi iv --wb-ivector as for pgd)")
+    ap.add_argument("--cw2-const", dest="cw2_const", default=1e-3, type=float, help="--attack cw2: the initial trade-off constant c")
+    ap.add_argument("--cw2-steps", dest="cw2_steps", default=9, type=int, help="--attack cw2: binary search steps over c (1 .. 32)")
+    ap.add_argument("--cw2-lr", dest="cw2_lr", default=1e-2, type=float, help="--attack cw2: Adam's learning rate in tanh space")
+    ap.add_argument("--cw2-abort-every", dest="cw2_abort_every", default=1000, type=int,
+                    help="--attack cw2: every this many iterations a search step ends unless its objective fell by 0.01 %%; 0: never")
     ap.add_argument("--bpda", action="store_true",
                     help="--attack pgd: the adaptive attack on a defended victim -- BPDA through --input-transform and --codec, "
                          "expectation over --eot-size draws of the random stages; --air-channel is refused unless --wb-air is "
@@ -250,9 +258,9 @@ def main(argv=None, model_factory=None, bob_factory=None):
         if args.companions > 0:
             ap.error("--attack kenansville does not take companion utterances (--companions %d)" % args.companions)
 
-    if args.bpda and args.attack != "pgd":
+    if args.bpda and args.attack not in ("pgd", "cw2"):
         ap.error("--bpda belongs to --attack pgd (--attack %s)" % args.attack)
-    if args.wb_ivector and args.attack != "pgd":
+    if args.wb_ivector and args.attack not in ("pgd", "cw2"):
         ap.error("--wb-ivector belongs to --attack pgd (--attack %s)" % args.attack)
     if args.wb_air and args.attack != "pgd":
         ap.error("--wb-air belongs to --attack pgd (--attack %s)" % args.attack)
@@ -280,6 +288,28 @@ def main(argv=None, model_factory=None, bob_factory=None):
                 continue
             if val is not None and not (args.bpda and flag in ("--input-transform", "--codec")):
                 ap.error("--attack pgd attacks an undefended victim: %s %s is not differentiated in this version" % (flag, val))
+    if args.attack == "cw2":      # likewise; what fb_attack_cw2 refuses whatever the switches say is refused here by name
+        if args.architecture != "gmm" and not args.wb_ivector:
+            ap.error("--attack cw2 differentiates an i-vector system only with --wb-ivector (--architecture %s)" % args.architecture)
+        if args.eot_size is not None and args.eot_size > 1 and (not args.bpda or args.architecture != "gmm"):
+            ap.error("--attack cw2 runs under expectation over transformation only with --bpda on a GMM-UBM system "
+                     "(--eot-size %d)" % args.eot_size)
+        if args.companions > 0:
+            ap.error("--attack cw2 does not take companion utterances in this version (--companions %d)" % args.companions)
+        for flag, val in (("--air-channel", args.air_channel), ("--feco", args.feco), ("--dither", args.dither)):
+            if val is not None:
+                ap.error("--attack cw2 does not differentiate %s %s in this version" % (flag, val))
+        for flag, val in (("--input-transform", args.input_transform), ("--codec", None if args.codec == "none" else args.codec)):
+            if val is not None and not args.bpda:
+                ap.error("--attack cw2 attacks an undefended victim unless --bpda is given: %s %s" % (flag, val))
+        from .cw2 import check_cw2_params
+        try:
+            check_cw2_params(args.cw2_const, args.cw2_steps, args.max_iter, args.cw2_lr, max(args.cw2_abort_every, 1),
+                             args.eot_size if args.eot_size is not None else 1, args.bpda)
+            if args.cw2_abort_every < 0:
+                raise ValueError("CW2: --cw2-abort-every must be >= 0")
+        except ValueError as ex:
+            ap.error(str(ex))
 
     task, attack_type, spk_id_list = args.task, args.attack_type, args.speaker_id
     if task == "SV":                      # SV only supports one enrolled speaker (:449-451)
@@ -341,7 +371,18 @@ def main(argv=None, model_factory=None, bob_factory=None):
             hp.update(universal=True)
             if not args.bpda and not args.wb_ivector:
                 hp.update(bpda=False)
-    if bob_factory is None and args.attack == "pgd" and args.wb_ivector:
+    if args.attack == "cw2":
+        hp = dict(confidence=args.adver_thresh, initial_const=args.cw2_const, binary_search_steps=args.cw2_steps,
+                  max_iter=args.max_iter, lr=args.cw2_lr, stop_early=args.cw2_abort_every > 0,
+                  stop_early_iter=max(args.cw2_abort_every, 1))
+        if args.bpda:
+            hp.update(bpda=True, eot_size=args.eot_size if args.eot_size is not None else 1)
+        if args.wb_ivector:
+            hp.update(ivector=True)
+    if bob_factory is None and args.attack == "cw2":
+        from .cw2 import CW2
+        bobs = [CW2(task, attack_type, m, seed=seed, verbose=False, **hp) for m in models]
+    elif bob_factory is None and args.attack == "pgd" and args.wb_ivector:
         from .pgd import IvectorPGD
         bobs = [IvectorPGD(task, attack_type, m, seed=seed, verbose=False, **hp) for m in models]
     elif bob_factory is None and args.attack == "pgd":
@@ -409,8 +450,11 @@ def main(argv=None, model_factory=None, bob_factory=None):
                 with lock:
                     results[idx] = flag
                 continue
-            adv, flag = bob.attack(it["audio"], it["cp_path"], threshold=threshold, true=true,
-                                   target=it["target"], fs=fs, bits_per_sample=bits_per_sample)
+            res = bob.attack(it["audio"], it["cp_path"], threshold=threshold, true=true,
+                             target=it["target"], fs=fs, bits_per_sample=bits_per_sample)
+            adv, flag = res
+            if args.attack == "cw2" and hasattr(res, "best_l2"):   # the figure this attack is run for
+                print("cw2 %s: success %d, l2 %.6g, snr %.2f dB, c %.3g" % (it["name"], flag, res.best_l2, res.snr_db, res.const))
             write(it["wav_path"], fs, adv)
             with lock:
                 results[idx] = flag

@@ -231,8 +231,11 @@ struct fb_engine {
   DevBuf wb_gj;                        // one replica's cotangent on the row the front end read [N]
   const int16_t *fe_wav = nullptr;     // the int16 batch the last launch_mfcc handed to the front end (a device buffer of the engine's)
   int wb_route[FB_WB_ROUTE_N] = {};    // launches of the white-box backward the last call enqueued (fb_debug_wb_route)
+  // the L2 white-box attack (fb_attack_cw2): w0, mod, the second moment (the first lives in grad_m) and the best iterate
+  // [N] float64, the best int16 row [N], the L2 partials [ceil(N / 256)], the search step's control block
+  DevBuf cw2_w0, cw2_mod, cw2_m2, cw2_best_x, cw2_best_row, cw2_l2part, cw2_ctl;
   // white-box gradients through the over-the-air channel (fb_set_wb_air)
-  int wb_air = 0;                      // the switch: 0 (as created) refuses a channel, as before it existed
+  int wb_air = 0;                     // the switch: 0 (as created) refuses a channel, as before it existed
   DevBuf wb_air_cot, wb_air_dx;        // the replicas' cotangents on the channel's output [r][N], k_air_conv_t's output [r][N] (r > 1)
   DevBuf wb_air_sat;                   // the forward's saturation bytes, laid out as wav_air (k_air_conv<true>)
   int wb_air_launches = 0;             // k_air_conv_t launches of the last call (fb_debug_wb_air_route)
@@ -2982,6 +2985,223 @@ extern "C" int fb_attack_wb(fb_engine *e, const fb_nes_params *p, const double *
   FBCHK(d2h(e, adv_i16, e->wav.p, sizeof(int16_t) * (size_t)N));
   if (adver_f64) FBCHK(d2h(e, adver_f64, e->adver.p, sizeof(double) * (size_t)N));
   FBCHK(sync_stream(e));
+  return FB_OK;
+}
+
+// ------------------------------------------------- the L2 white-box attack
+// fb_attack_cw2 (the "CW2" section of fakebob_hip.h): Carlini-Wagner's L2 attack on wb_enqueue's gradient.  Per search step a
+// reset launch; per iteration wb_enqueue (its control launch forms the weights with the stop on adver_loss < 0 disabled and
+// writes no trace row) + k_cw2_ctl + k_cw2_step.  The host looks once per FB_ATTACK_BATCH iterations and between search steps,
+// where it also moves the constant.
+static int cw2_check(const fb_engine *e, const fb_nes_params *p, const fb_cw2_params *c) {
+  // refused by name whatever the white-box switches say: none of them has a CW2 test of its own in this version
+  if (e->comp_K1 > 0) return fb_fail(FB_E_STATE, "CW2: companions are set (fb_set_companions: clear them)");
+  if (e->air.L > 0) return fb_fail(FB_E_STATE, "CW2: an air channel is set (fb_set_air_channel: clear it)");
+  if (e->feco_iters > 0) return fb_fail(FB_E_STATE, "CW2: feature compression is on (fb_set_feature_compression: switch it off)");
+  if (e->cfg.dither > 0.0) return fb_fail(FB_E_STATE, "CW2: dither %g > 0 (set 0)", e->cfg.dither);
+  if (c->search_steps < 1 || c->search_steps > 32) return fb_fail(FB_E_ARG, "CW2: search_steps %d outside 1 .. 32", c->search_steps);
+  if (!isfinite(c->initial_const) || !(c->initial_const > 0.0)) return fb_fail(FB_E_ARG, "CW2: initial_const must be finite and > 0");
+  if (!isfinite(c->lr) || !(c->lr > 0.0)) return fb_fail(FB_E_ARG, "CW2: lr must be finite and > 0");
+  if (!isfinite(c->adam_eps) || !(c->adam_eps > 0.0)) return fb_fail(FB_E_ARG, "CW2: adam_eps must be finite and > 0");
+  if (!(c->beta1 >= 0.0 && c->beta1 < 1.0) || !(c->beta2 >= 0.0 && c->beta2 < 1.0))
+    return fb_fail(FB_E_ARG, "CW2: beta1 and beta2 must lie in [0, 1)");
+  if (c->abort_every < 0) return fb_fail(FB_E_ARG, "CW2: abort_every must be >= 0");
+  if (p->max_iter < 1) return fb_fail(FB_E_ARG, "max_iter must be > 0");
+  if ((int64_t)c->search_steps * p->max_iter > (int64_t)1 << 30)
+    return fb_fail(FB_E_ARG, "CW2: search_steps * max_iter = %lld iterations: at most 2^30", (long long)c->search_steps * p->max_iter);
+  return FB_OK;
+}
+static int cw2_buffers(fb_engine *e, int64_t N) {
+  for (DevBuf *b : {&e->cw2_w0, &e->cw2_mod, &e->cw2_m2, &e->cw2_best_x}) FBCHK(b->ensure(sizeof(double) * (size_t)N));
+  FBCHK(e->cw2_best_row.ensure(sizeof(int16_t) * (size_t)N));
+  FBCHK(e->cw2_l2part.ensure(sizeof(double) * (size_t)((N + 255) / 256)));
+  FBCHK(e->cw2_ctl.ensure(sizeof(FbCw2Dev)));
+  return FB_OK;
+}
+// the binary search over the constant between two search steps (SpeakerGuard's CW2: lower / upper bound, tenfold while no
+// success has bounded it)
+static void cw2_next_const(bool found, double *lo, double *hi, double *c) {
+  if (found) {
+    *hi = *hi < *c ? *hi : *c;
+    *c = (*lo + *hi) / 2.0;
+  } else {
+    *lo = *lo > *c ? *lo : *c;
+    *c = *hi < 1e9 ? (*lo + *hi) / 2.0 : *c * 10.0;
+  }
+}
+
+extern "C" int fb_attack_cw2(fb_engine *e, const fb_nes_params *p, const fb_cw2_params *c, const double *audio, int64_t N,
+                             int16_t *adv_i16, double *adver_f64, double *trace, int *n_trace, int *rows_per_step, int *success_flag,
+                             double *best_l2, double *final_const) {
+  if (e) e->bench_it = -1;
+  if (e) memset(e->nes_route, 0, sizeof(e->nes_route));
+  if (e) memset(e->wb_route, 0, sizeof(e->wb_route));
+  if (e) e->wb_air_launches = 0;
+  if (e) e->wb_feco_launches = 0;
+  if (e) e->wb_universal_launches = 0;
+  if (!e || !p || !c || !audio || !adv_i16 || !success_flag || !rows_per_step || !best_l2 || !final_const)
+    return fb_fail(FB_E_ARG, "null argument");
+  if (!e->have_gmm) return fb_fail(FB_E_STATE, "no model loaded");
+  FBCHK(cw2_check(e, p, c));
+  fb_nes_params q;
+  FBCHK(wb_check(e, p, audio, N, &q));
+  q.plateau_length = 0;   // (the loop control of wb_enqueue's control launch: no plateau rule, no stop of its own)
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(prepare_nes_replicas(e, N, 1));
+  FBCHK(ensure_nes_buffers(e, N, 1));
+  FBCHK(wb_prepare(e, N, e->h_frame_off[1], true));
+  FBCHK(cw2_buffers(e, N));
+  const int S = fb_num_speakers(e);
+  const int steps = c->search_steps, max_iter = p->max_iter;
+  const size_t total = (size_t)steps * (size_t)max_iter;
+  {  // w0 = atanh(0.999999 a0) on the host: the device never evaluates atanh
+    std::vector<double> w0((size_t)N);
+    for (int64_t n = 0; n < N; ++n) w0[(size_t)n] = atanh(0.999999 * audio[n]);
+    FBCHK(h2d(e, e->cw2_w0.p, w0.data(), sizeof(double) * (size_t)N));
+    FBCHK(sync_stream(e));
+  }
+  FBCHK(attack_start(e, audio, N, 0, nullptr));
+  // the best slots before any success: the cast of the original audio and the audio itself
+  fb_launch_quantize(e->stream, e->audio.as<double>(), N, nes_bits(p), e->cw2_best_row.as<int16_t>());
+  HIPCHK(hipMemcpyAsync(e->cw2_best_x.p, e->audio.p, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, e->stream));
+  double *trace_dev = nullptr;
+  if (trace) {
+    FBCHK(e->trace_dev.ensure(sizeof(double) * total * (3 + S)));
+    trace_dev = e->trace_dev.as<double>();
+  }
+  FBCHK(e->ticks.ensure(sizeof(unsigned long long) * (total + 1)));
+  FBCHK(ctl_reset(e, &q, true, true, e->ticks.as<unsigned long long>()));
+  FbCtlDev *ctl = e->ctl.as<FbCtlDev>();
+  FbCw2Dev *cw = e->cw2_ctl.as<FbCw2Dev>();
+  FbCw2Dev h_cw;
+  memset(&h_cw, 0, sizeof(h_cw));
+  h_cw.gbest_l2 = INFINITY;
+  h_cw.prev = INFINITY;
+  FBCHK(h2d(e, cw, &h_cw, sizeof(h_cw)));
+  const char *ev = getenv("FB_ATTACK_BATCH");
+  const int b = ev ? atoi(ev) : 4;
+  const int look = b < 1 ? 1 : (b > 16 ? 16 : b);
+  double cc = c->initial_const, lo = 0.0, hi = 1e10;
+  int rows = 0;
+  for (int s = 0; s < steps; ++s) {
+    fb_launch_cw2_reset(e->stream, e->cw2_w0.as<double>(), e->audio.as<double>(), N, cc, e->cw2_mod.as<double>(), e->grad_m.as<double>(),
+                        e->cw2_m2.as<double>(), e->adver.as<double>(), e->cw2_l2part.as<double>(), cw, ctl);
+    double p1 = 1.0, p2 = 1.0;
+    for (int queued = 0; queued < max_iter;) {
+      const int nb = max_iter - queued < look ? max_iter - queued : look;
+      int rc = FB_OK, status = 0;
+      for (int k = 0; k < nb && rc == FB_OK; ++k) {
+        const int t = queued + k;
+        rc = wb_enqueue(e, &q, N, (uint32_t)((size_t)s * (size_t)max_iter + (size_t)t), false, ctl, nullptr);
+        if (rc != FB_OK) break;
+        p1 *= c->beta1;
+        p2 *= c->beta2;
+        fb_launch_cw2_ctl(e->stream, e->nes_out.as<FbNesDev>(), e->scores.as<double>(), S, e->cw2_l2part.as<double>(), N, cw, ctl,
+                          trace_dev, t, c->abort_every);
+        fb_launch_cw2_step(e->stream, e->grad.as<double>(), e->audio.as<double>(), e->cw2_w0.as<double>(), N, c->beta1, c->beta2,
+                           c->lr / (1.0 - p1), sqrt(1.0 - p2), c->adam_eps, e->cw2_mod.as<double>(), e->grad_m.as<double>(),
+                           e->cw2_m2.as<double>(), e->adver.as<double>(), e->wav.as<int16_t>(), e->cw2_best_row.as<int16_t>(),
+                           e->cw2_best_x.as<double>(), e->cw2_l2part.as<double>(), cw);
+      }
+      hipError_t he = hipSuccess;
+      if (rc == FB_OK) he = hipMemcpyAsync(e->h_ctl, ctl, sizeof(FbCtlDev), hipMemcpyDeviceToHost, e->stream);
+      if (rc == FB_OK && he == hipSuccess) rc = d2h(e, &status, e->wb_status.p, sizeof(int));
+      if (rc == FB_OK && he == hipSuccess) rc = d2h(e, &h_cw, cw, sizeof(h_cw));
+      if (rc != FB_OK || he != hipSuccess) {
+        (void)sync_stream(e);
+        HIPCHK(he);
+        return rc;
+      }
+      queued += nb;
+      FBCHK(sync_stream(e));
+      if (e->gmm_pending) FBCHK(time_collect(e));
+      FBCHK(wb_status_check(e, status));
+      if (e->h_ctl->err != 0) return fb_fail(FB_E_NO_VOICED, "the adversarial audio has no voiced frames");
+      if (e->h_ctl->stop) break;   // the abort rule
+    }
+    rows_per_step[s] = h_cw.rows - rows;
+    rows = h_cw.rows;
+    cw2_next_const(h_cw.found != 0, &lo, &hi, &cc);
+  }
+  HIPCHK(hipGetLastError());
+  e->nes_iters += rows;
+  FBCHK(collect_iter_seconds(e, rows));
+  if (trace && rows > 0) FBCHK(d2h(e, trace, trace_dev, sizeof(double) * (size_t)rows * (3 + S)));
+  *success_flag = h_cw.gbest_l2 < INFINITY ? 1 : -1;
+  *best_l2 = h_cw.gbest_l2;
+  *final_const = cc;
+  if (n_trace) *n_trace = rows;
+  FBCHK(d2h(e, adv_i16, e->cw2_best_row.p, sizeof(int16_t) * (size_t)N));
+  if (adver_f64) FBCHK(d2h(e, adver_f64, e->cw2_best_x.p, sizeof(double) * (size_t)N));
+  FBCHK(sync_stream(e));
+  return FB_OK;
+}
+
+// Test hook: one k_cw2_ctl + k_cw2_step pair on arrays handed in (fakebob_hip_test.h); no system has to be loaded
+extern "C" int fb_debug_cw2_step(fb_engine *e, const fb_cw2_params *c, int64_t N, const double *g, const double *x, const double *a0,
+                                 const double *w0, const double *mod, const double *m1, const double *m2, double adver_loss,
+                                 double cc, double gbest_l2, int t, double p1, double p2, double *mod_out, double *m1_out,
+                                 double *m2_out, double *x_next, double *l2_now, double *l2_next, int *gate, int *take,
+                                 int16_t *best_row, double *best_x) {
+  if (!e || !c || !g || !x || !a0 || !w0 || !mod || !m1 || !m2 || !mod_out || !m1_out || !m2_out || !x_next || !l2_now || !l2_next ||
+      !gate || !take || !best_row || !best_x || N <= 0 || t < 0)
+    return fb_fail(FB_E_ARG, "bad argument");
+  if (!(p1 >= 0.0 && p1 < 1.0) || !(p2 >= 0.0 && p2 < 1.0)) return fb_fail(FB_E_ARG, "p1 and p2 must lie in [0, 1)");
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  e->cached_B = -1;
+  FBCHK(ensure_nes_buffers(e, N, 1, 1));
+  FBCHK(e->wav.ensure(sizeof(int16_t) * (size_t)N));
+  FBCHK(cw2_buffers(e, N));
+  const size_t nb = sizeof(double) * (size_t)N;
+  FBCHK(h2d(e, e->grad.p, g, nb));
+  FBCHK(h2d(e, e->adver.p, x, nb));
+  FBCHK(h2d(e, e->audio.p, a0, nb));
+  FBCHK(h2d(e, e->cw2_w0.p, w0, nb));
+  FBCHK(h2d(e, e->cw2_mod.p, mod, nb));
+  FBCHK(h2d(e, e->grad_m.p, m1, nb));
+  FBCHK(h2d(e, e->cw2_m2.p, m2, nb));
+  fb_nes_params q;
+  memset(&q, 0, sizeof(q));
+  FBCHK(ctl_reset(e, &q, false, true, nullptr));
+  FbNesDev h_out;
+  memset(&h_out, 0, sizeof(h_out));
+  h_out.adver_loss = adver_loss;
+  FBCHK(h2d(e, e->nes_out.p, &h_out, sizeof(h_out)));
+  FbCw2Dev h_cw;
+  memset(&h_cw, 0, sizeof(h_cw));
+  h_cw.c = cc; h_cw.gbest_l2 = gbest_l2; h_cw.prev = INFINITY;
+  FbCw2Dev *cw = e->cw2_ctl.as<FbCw2Dev>();
+  FBCHK(h2d(e, cw, &h_cw, sizeof(h_cw)));
+  // the row the forward would have scored, and the best slots as an attack without a success holds them
+  fb_launch_quantize(e->stream, e->adver.as<double>(), N, 16, e->wav.as<int16_t>());
+  fb_launch_quantize(e->stream, e->audio.as<double>(), N, 16, e->cw2_best_row.as<int16_t>());
+  HIPCHK(hipMemcpyAsync(e->cw2_best_x.p, e->audio.p, nb, hipMemcpyDeviceToDevice, e->stream));
+  fb_launch_cw2_l2(e->stream, e->adver.as<double>(), e->audio.as<double>(), N, e->cw2_l2part.as<double>());
+  fb_launch_cw2_ctl(e->stream, e->nes_out.as<FbNesDev>(), e->scores.as<double>(), 0, e->cw2_l2part.as<double>(), N, cw, e->ctl.as<FbCtlDev>(),
+                    nullptr, t, c->abort_every);
+  FBCHK(d2h(e, &h_cw, cw, sizeof(h_cw)));   // (queued before the step launch: l2 of x, gate and take as k_cw2_ctl left them)
+  fb_launch_cw2_step(e->stream, e->grad.as<double>(), e->audio.as<double>(), e->cw2_w0.as<double>(), N, c->beta1, c->beta2,
+                     c->lr / (1.0 - p1), sqrt(1.0 - p2), c->adam_eps, e->cw2_mod.as<double>(), e->grad_m.as<double>(),
+                     e->cw2_m2.as<double>(), e->adver.as<double>(), e->wav.as<int16_t>(), e->cw2_best_row.as<int16_t>(),
+                     e->cw2_best_x.as<double>(), e->cw2_l2part.as<double>(), cw);
+  const size_t np = (size_t)((N + 255) / 256);
+  std::vector<double> part(np);
+  FBCHK(d2h(e, part.data(), e->cw2_l2part.p, sizeof(double) * np));
+  FBCHK(d2h(e, mod_out, e->cw2_mod.p, nb));
+  FBCHK(d2h(e, m1_out, e->grad_m.p, nb));
+  FBCHK(d2h(e, m2_out, e->cw2_m2.p, nb));
+  FBCHK(d2h(e, x_next, e->adver.p, nb));
+  FBCHK(d2h(e, best_row, e->cw2_best_row.p, sizeof(int16_t) * (size_t)N));
+  FBCHK(d2h(e, best_x, e->cw2_best_x.p, nb));
+  FBCHK(sync_stream(e));
+  HIPCHK(hipGetLastError());
+  double l2 = 0.0;
+  for (size_t i = 0; i < np; ++i) l2 += part[i];   // ascending block order, as k_cw2_ctl adds them
+  *l2_next = l2;
+  *l2_now = h_cw.l2;
+  *gate = h_cw.gate;
+  *take = h_cw.take;
   return FB_OK;
 }
 

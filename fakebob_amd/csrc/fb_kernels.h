@@ -384,6 +384,36 @@ void fb_launch_wb_iv_ctl_rep(hipStream_t s, const double *rep_scores, const doub
                              int task, int attack_type, const double *z_std, double threshold, int target, int true_label, double *w,
                              FbCtlDev *ctl, int do_ctl, double *trace, int it);
 
+// ---- the L2 white-box attack (fb_attack_cw2; cw2_kernels.hip) ---------------------------------------------------------
+// Device-side control of a CW2 search step: what k_cw2_ctl (one thread) decides for the element-wise launch behind it
+struct FbCw2Dev {
+  double c;          // the trade-off constant of the search step
+  double gbest_l2;   // the smallest l2 over the successful iterates of the whole attack (+inf: none yet)
+  double prev;       // the abort rule's last L (+inf at the start of a search step)
+  double l2;         // l2 of the iterate just scored
+  int gate;          // adver_loss > 0
+  int take;          // this iterate goes to the best slots
+  int mode;          // what k_cw2_step does: bit 0 the copy to the best slots, bit 1 the Adam step; 0 = return at once
+  int found;         // some iterate of this search step had adver_loss < 0
+  int aborted;       // the abort rule ended this search step
+  int rows;          // trace rows written since the start of the attack
+};
+// the start of a search step with constant c: mod = m1 = m2 = 0, x = tanh(w0), l2_part[ceil(N / 256)] of x; found / prev / the
+// abort flag and ctl->stop (unless ctl->err) start over
+void fb_launch_cw2_reset(hipStream_t s, const double *w0, const double *a0, int64_t N, double c, double *mod, double *m1, double *m2,
+                         double *x, double *l2_part, FbCw2Dev *cw, FbCtlDev *ctl);
+// l2_part[b] = the sum of (x[n] - a0[n])^2 over block b of 256 consecutive samples, by the tree of cw2_block_sum
+void fb_launch_cw2_l2(hipStream_t s, const double *x, const double *a0, int64_t N, double *l2_part);
+// gate / take / found / gbest_l2 / the abort rule / trace row cw->rows / the clock stamp, from the loss launch's block and the
+// partials of the iterate it scored; a launch behind the stopping one only sets cw->mode = 0
+void fb_launch_cw2_ctl(hipStream_t s, const FbNesDev *out, const double *scores, int S, const double *l2_part, int64_t N, FbCw2Dev *cw,
+                       FbCtlDev *ctl, double *trace, int t, int abort_every);
+// the copy of (row, x) to the best slots when cw->mode says so, then the Adam step on mod with the gradient g = d loss / d x and
+// x = tanh(w0 + mod), l2_part of the new x; step_size = lr / (1 - beta1^(t+1)), bc2s = sqrt(1 - beta2^(t+1))
+void fb_launch_cw2_step(hipStream_t s, const double *g, const double *a0, const double *w0, int64_t N, double beta1, double beta2,
+                        double step_size, double bc2s, double adam_eps, double *mod, double *m1, double *m2, double *x,
+                        const int16_t *row, int16_t *best_row, double *best_x, double *l2_part, const FbCw2Dev *cw);
+
 // ---- front-end ------------------------------------------------------------
 // MFCC of every frame of a (ragged) batch.  wav_off[B+1], frame_off[B+1] device arrays.
 // frame_rec: [total_frames][4] int32 = {absolute start sample (int64 in two words), start within the

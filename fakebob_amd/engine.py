@@ -36,6 +36,14 @@ def pso_params(particles=25, w_init=0.9, w_end=0.1, c1=1.4961, c2=1.4961, v_max=
     return q
 
 
+def cw2_params(initial_const=1e-3, search_steps=9, lr=1e-2, beta1=0.9, beta2=0.999, adam_eps=1e-8, abort_every=1000):
+    """fb_cw2_params: the search of Engine.attack_cw2 (fakebob_hip.h, "CW2"); SpeakerGuard's and torch.optim.Adam's defaults."""
+    q = N.Cw2Params()
+    q.initial_const = float(initial_const); q.search_steps = int(search_steps); q.lr = float(lr)
+    q.beta1 = float(beta1); q.beta2 = float(beta2); q.adam_eps = float(adam_eps); q.abort_every = int(abort_every)
+    return q
+
+
 def kv_params(window=100, grid=15, q_max=65536, max_rounds=32):
     """fb_kv_params: the search of Engine.attack_kenansville (fakebob_hip.h, "decision-only attack")."""
     k = N.KvParams()
@@ -714,6 +722,44 @@ class Engine(object):
         N.check(self._L.fb_attack_wb(self._h, C.byref(params), N.ptr(audio), C.c_int64(n), N.ptr(adv), N.ptr(adv_f),
                                      N.ptr(trace), C.byref(nt), C.byref(flag)))
         return adv, flag.value, adv_f, trace[:nt.value]
+
+    def attack_cw2(self, params, cw2, audio):
+        """fb_attack_cw2: Carlini-Wagner's L2 attack on the analytic gradient (tanh space, Adam, a binary search over the
+        constant; fakebob_hip.h, "CW2") -> dict(adv (N,) int16, success +-1, adver_f64 (N,), trace (rows, 3 + S) of
+        {l2, adver_loss, c, score0}, rows_per_step (search_steps,), best_l2, const).  params.max_iter counts the iterations of
+        ONE search step.  Victims as attack_wb takes them, except companions, an air channel, feature compression and dither,
+        which are refused whatever the switches say."""
+        audio = np.ascontiguousarray(audio, np.float64).reshape(-1)
+        n, S = audio.size, max(self.n_speakers, 1)
+        steps = int(cw2.search_steps)
+        total = max(steps, 0) * max(int(params.max_iter), 0)
+        if not 1 <= steps <= 32 or total > 2 ** 30:   # (the library says which; nothing of that size is allocated for it here)
+            total = 1
+        adv = np.empty(n, np.int16)
+        adv_f = np.empty(n, np.float64)
+        trace = np.zeros((max(total, 1), 3 + S), np.float64)
+        per = np.zeros(32, np.int32)
+        nt, flag, l2, cc = C.c_int(), C.c_int(), C.c_double(), C.c_double()
+        N.check(self._L.fb_attack_cw2(self._h, C.byref(params), C.byref(cw2), N.ptr(audio), C.c_int64(n), N.ptr(adv), N.ptr(adv_f),
+                                      N.ptr(trace), C.byref(nt), N.ptr(per), C.byref(flag), C.byref(l2), C.byref(cc)))
+        return dict(adv=adv, success=flag.value, adver_f64=adv_f, trace=trace[:nt.value].copy(), rows_per_step=per[:steps].copy(),
+                    best_l2=l2.value, const=cc.value)
+
+    def debug_cw2_step(self, cw2, g, x, a0, w0, mod, m1, m2, adver_loss, c, gbest_l2, t, p1, p2):
+        """One k_cw2_ctl + k_cw2_step pair on arrays handed in (fb_debug_cw2_step) -> dict(mod, m1, m2, x_next, l2, l2_next,
+        gate, take, best_row, best_x).  No system has to be loaded."""
+        arrs = [np.ascontiguousarray(a, np.float64).reshape(-1) for a in (g, x, a0, w0, mod, m1, m2)]
+        n = arrs[0].size
+        if any(a.size != n for a in arrs):
+            raise ValueError("debug_cw2_step: the seven arrays must have one length")
+        out = [np.empty(n, np.float64) for _ in range(4)]
+        best_row, best_x = np.empty(n, np.int16), np.empty(n, np.float64)
+        l2, l2n, gate, take = C.c_double(), C.c_double(), C.c_int(), C.c_int()
+        N.check(self._L.fb_debug_cw2_step(self._h, C.byref(cw2), C.c_int64(n), *([N.ptr(a) for a in arrs] + [
+            C.c_double(adver_loss), C.c_double(c), C.c_double(gbest_l2), C.c_int(int(t)), C.c_double(p1), C.c_double(p2)] +
+            [N.ptr(o) for o in out] + [C.byref(l2), C.byref(l2n), C.byref(gate), C.byref(take), N.ptr(best_row), N.ptr(best_x)])))
+        return dict(mod=out[0], m1=out[1], m2=out[2], x_next=out[3], l2=l2.value, l2_next=l2n.value, gate=gate.value,
+                    take=take.value, best_row=best_row, best_x=best_x)
 
     def debug_defence_vjp(self, wav, cot, seed=0, stream=0, iter=0):
         """The defences' transposes alone (fb_debug_defence_vjp): wav (n,) int16, cot (r, n) float64 on the rows the front

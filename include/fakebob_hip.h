@@ -35,6 +35,8 @@
  *   fb_get_grad_wb / fb_attack_wb     FakeBob.get_grad + loss_fn (FAKEBOB.py:223-299) and FakeBob.attack (:139-221) with the
  *                             ANALYTIC gradient of the loss in place of the NES estimate: the white-box attacks of
  *                             SpeakerGuard's evaluation (FGSM, PGD, the margin-loss CW-inf) on a GMM-UBM system
+ *   fb_attack_cw2             (none in FAKEBOB: SpeakerGuard's CW2 -- Carlini-Wagner's L2 attack in tanh space with Adam and
+ *                             a binary search over the constant, on that gradient; it minimises the distortion)
  *   fb_set_wb_bpda / fb_get_grad_wb_iter   (none in FAKEBOB: the adaptive form of those attacks on a DEFENDED victim -- BPDA
  *                             through the input-transform chain and the codec, EOT over the random stages)
  *   fb_set_wb_ivector         (none in FAKEBOB: the same white-box calls on an i-vector-PLDA system, the frames' component
@@ -719,6 +721,61 @@ int fb_get_grad_wb(fb_engine *e, const fb_nes_params *p, const double *audio, in
                    double *grad /*[N], nullable*/, double *score0 /*[S]*/);
 int fb_attack_wb(fb_engine *e, const fb_nes_params *p, const double *audio, int64_t N, int16_t *adv_i16, double *adver_f64,
                  double *trace, int *n_trace, int *success_flag);
+
+/* ---- CW2: the L2 white-box attack (Carlini-Wagner in tanh space, Adam, a binary search over the constant c) -----------------
+ * fb_attack_wb spends a fixed epsilon budget; fb_attack_cw2 MINIMISES the distortion: it answers "how small a perturbation
+ * breaks this system".  The gradient is fb_get_grad_wb_iter's (the same launches), the loop control runs on the device and the
+ * host looks once per FB_ATTACK_BATCH iterations and between search steps; the result does not depend on that variable.
+ * Read of fb_nes_params: task, attack_type, target, true_label, threshold, adver_thresh (CW's confidence kappa: it sits
+ * inside loss_fn), max_iter (iterations per search step), bits_per_sample; with a random stage set also seed and stream.  Not
+ * read: epsilon, the learning rates, momentum, the plateau knobs.  fb_cw2_params: initial_const (SpeakerGuard: 1e-3),
+ * search_steps (9), lr (1e-2), beta1 (0.9), beta2 (0.999), adam_eps (1e-8) -- torch.optim.Adam's --, abort_every (1000; 0: never).
+ * a0[N]: the float audio in [-1, 1].  w0 = atanh(0.999999 a0) is computed on the host in float64 (libm) and uploaded.  All
+ * device arithmetic is float64 with one rounding per operation, nothing contracted; products and quotients associate from the
+ * left as written:
+ *   c = initial_const; lo = 0; hi = 1e10; gbest_l2 = +inf; gbest_row = cast(a0); gbest_x = a0
+ *   for s in 0 .. search_steps-1:
+ *       mod = m1 = m2 = 0;  x = tanh(w0)                     (the first iterate is tanh(w0), not a0)
+ *       p1 = p2 = 1;  prev = +inf;  found = False
+ *       for t in 0 .. max_iter-1:
+ *           epoch = s*max_iter + t                           (the `iter` of fb_get_grad_wb_iter: the draws of random stages)
+ *           g, adver_loss, score0 = fb_get_grad_wb_iter at x (the forward casts x to int16)
+ *           l2 = sum_n (x[n]-a0[n])^2                        (the fixed order below)
+ *           gate = 1 if adver_loss > 0 else 0                (CW's max(f, 0): the margin stops pulling once past kappa)
+ *           L = (c*gate)*adver_loss + l2
+ *           trace row = {l2, adver_loss, c, score0[S]}       (rows are consecutive: an aborted step leaves no gap)
+ *           if adver_loss < 0 and l2 < gbest_l2: gbest_l2 = l2; gbest_row = the int16 row the forward scored; gbest_x = x
+ *           if adver_loss < 0: found = True
+ *           if abort_every > 0 and t % abort_every == 0:
+ *               if L > 0.9999*prev: break                    (the row is written, no step is taken)
+ *               prev = L
+ *           p1 *= beta1; p2 *= beta2                         (on the host, by repeated multiplication)
+ *           G = ((c*gate)*g + 2*(x-a0)) * (1 - x*x)
+ *           m1 = beta1*m1 + (1-beta1)*G;  m2 = beta2*m2 + ((1-beta2)*G)*G
+ *           mod = mod - ((lr/(1-p1)) * m1) / (sqrt(m2)/sqrt(1-p2) + adam_eps)
+ *           x = tanh(w0 + mod)
+ *       if found: hi = min(hi, c); c = (lo+hi)/2
+ *       else:     lo = max(lo, c); c = (lo+hi)/2 if hi < 1e9 else c*10
+ *   adv_i16 = gbest_row, adver_f64 = gbest_x, success_flag = +1 if gbest_l2 < inf else -1, best_l2 = gbest_l2, final_const = c
+ * The L2 sum: blocks of 256 consecutive samples, terms past N being +0.0; within a block d[i] += d[i + h] for all i < h, for
+ * h = 128, 64, 32, 16, 8, 4, 2, 1 in this order, the block's partial being d[0]; the partials are added in ascending block order
+ * from +0.0.  No floating-point atomics.  Division and square root are correctly rounded, so m1, m2 and mod are bit-exact
+ * contracts; tanh is the device library's and is not: it is the one place where a host restatement agrees to a tolerance.
+ * "Success" is FAKEBOB's own test adver_loss < 0 -- the loss of the int16 row actually scored, under fb_set_eot the mean over
+ * the replicas.  SpeakerGuard's CW2 reads a decision instead; with kappa = 0 the two coincide except on ties.  Unlike
+ * fb_attack_wb the loop does not stop at the first success: it keeps the smallest successful iterate.
+ * trace [search_steps*max_iter][3 + S] (nullable), *n_trace rows written; rows_per_step[search_steps].  fb_attack_iter_seconds
+ * and fb_stats (nes_iters: one per row) work as for fb_attack_wb.
+ * Victims: an undefended GMM-UBM system; an i-vector system under fb_set_wb_ivector; an input-transform chain, a codec and
+ * fb_set_eot(r) under fb_set_wb_bpda, exactly as fb_attack_wb accepts them.  Refused by name, FB_E_STATE, whatever the
+ * switches say, in this version: companions, an air channel, feature compression, dither > 0.  FB_E_ARG: null arguments,
+ * search_steps outside 1 .. 32, a non-finite or non-positive initial_const, lr or adam_eps, a beta outside [0, 1),
+ * abort_every < 0, max_iter < 1, search_steps * max_iter above 2^30, and the task, target, true-label and bits_per_sample
+ * rules of fb_attack_wb.  A refusal leaves the engine as it was. */
+typedef struct { double initial_const; int search_steps; double lr, beta1, beta2, adam_eps; int abort_every; } fb_cw2_params;
+int fb_attack_cw2(fb_engine *e, const fb_nes_params *p, const fb_cw2_params *q, const double *audio, int64_t N, int16_t *adv_i16,
+                  double *adver_f64 /*[N], nullable*/, double *trace /*[search_steps*max_iter][3+S], nullable*/, int *n_trace,
+                  int *rows_per_step /*[search_steps]*/, int *success_flag, double *best_l2, double *final_const);
 
 const char *fb_last_error(void);
 int fb_version(void);

@@ -311,6 +311,18 @@ int fb_bench_nes_state(fb_engine *e, double *adver, double *scores, double *loss
 int fb_debug_gmm_feat_grad(fb_engine *e, const float *feats, int Tv, const double *w, double *out);
 int fb_debug_frontend_vjp(fb_engine *e, const int16_t *wav, int64_t n, const double *cot, double *dwav, unsigned char *voiced);
 
+/* CW2 (fakebob_hip.h: "CW2", its pseudo-code).  fb_debug_cw2_step runs ONE k_cw2_ctl + k_cw2_step pair of an attack iteration on
+ * arrays handed in as they are; no system has to be loaded.  In: the gradient g, the iterate x, a0, w0, mod, m1, m2 (all [N]
+ * float64), adver_loss as the loss launch would have left it, the constant c, gbest_l2, the iteration t within its search step
+ * (the abort rule of q->abort_every starts from prev = +inf), and p1 = beta1^(t+1), p2 = beta2^(t+1) as the host's repeated
+ * multiplication has them.  q: lr, beta1, beta2, adam_eps, abort_every.  Out: the new mod, m1, m2, x_next = tanh(w0 + mod), l2_now of
+ * x and l2_next of x_next in the contract's summation order, gate, take, and the best slots -- which start as an attack without a
+ * success holds them, the 16-bit cast of a0 and a0, and hold the cast of x and x when take = 1. */
+int fb_debug_cw2_step(fb_engine *e, const fb_cw2_params *q, int64_t N, const double *g, const double *x, const double *a0,
+                      const double *w0, const double *mod, const double *m1, const double *m2, double adver_loss, double c,
+                      double gbest_l2, int t, double p1, double p2, double *mod_out, double *m1_out, double *m2_out, double *x_next,
+                      double *l2_now, double *l2_next, int *gate, int *take, int16_t *best_row, double *best_x);
+
 /* White-box gradients through a defended victim (fakebob_hip.h: fb_set_wb_bpda).
  * fb_debug_defence_vjp: the defences alone.  The forward of the defences currently set -- input-transform chain, codec -- on
  * the ONE row wav[n] for the engine's r = fb_set_eot replicas at (seed, stream, epoch = iter) of the noise RNG contract, as the
