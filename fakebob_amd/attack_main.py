@@ -195,7 +195,7 @@ def main(argv=None, model_factory=None, bob_factory=None):
                     help="universal perturbation: the next N utterances of the same speaker in the data directory ride along "
                          "with every attacked one (1 .. 31, times --eot-size at most 32); all are cropped to the shortest, "
                          "which is printed; default: 0")
-    ap.add_argument("--attack", default="nes", choices=["nes", "pso", "kenansville", "pgd", "cw2"],
+    ap.add_argument("--attack", default="nes", choices=["nes", "pso", "kenansville", "pgd", "cw2", "psy"],
                     help="the search: FAKEBOB's NES gradient estimate (default), SirenAttack's particle swarm "
                          "(fakebob_amd/pso.py; -epsilon, -max_iter, -adver and --seed apply, the other NES options do not), "
                          "Kenansville's decision-only spectral removal (fakebob_amd/kenansville.py; --kv-* and --seed apply) or the "
@@ -204,7 +204,13 @@ def main(argv=None, model_factory=None, bob_factory=None):
                          "victim unless --bpda is given); cw2: Carlini-Wagner's L2 attack on the same gradient "
                          "(fakebob_amd/cw2.py: tanh space, Adam, a binary search over the constant; it minimises the distortion; "
                          "-max_iter counts the iterations of one search step, -adver is CW's confidence, --cw2-* apply; --bpda "
-                         "--eot-size and -archi iv --wb-ivector as for pgd)")
+                         "--eot-size and -archi iv --wb-ivector as for pgd); psy: cw2's loop with the psychoacoustic masking "
+                         "distortion in its place (fakebob_amd/psy.py; --psy-window, --psy-l2-weight and --cw2-* apply)")
+    ap.add_argument("--psy-window", dest="psy_window", default=2048, type=int, choices=[512, 1024, 2048],
+                    help="--attack psy: CW2's loop with the psychoacoustic masking distortion in place of |delta|^2 "
+                         "(fakebob_amd/psy.py; --cw2-* apply as for cw2); this is the STFT window of the masking model, hop = window/4")
+    ap.add_argument("--psy-l2-weight", dest="psy_l2_weight", default=0.0, type=float,
+                    help="--attack psy: this much of CW2's |delta|^2 is added to the masking distortion (default 0: masking alone)")
     ap.add_argument("--cw2-const", dest="cw2_const", default=1e-3, type=float, help="--attack cw2: the initial trade-off constant c")
     ap.add_argument("--cw2-steps", dest="cw2_steps", default=9, type=int, help="--attack cw2: binary search steps over c (1 .. 32)")
     ap.add_argument("--cw2-lr", dest="cw2_lr", default=1e-2, type=float, help="--attack cw2: Adam's learning rate in tanh space")
@@ -258,9 +264,9 @@ def main(argv=None, model_factory=None, bob_factory=None):
         if args.companions > 0:
             ap.error("--attack kenansville does not take companion utterances (--companions %d)" % args.companions)
 
-    if args.bpda and args.attack not in ("pgd", "cw2"):
+    if args.bpda and args.attack not in ("pgd", "cw2", "psy"):
         ap.error("--bpda belongs to --attack pgd (--attack %s)" % args.attack)
-    if args.wb_ivector and args.attack not in ("pgd", "cw2"):
+    if args.wb_ivector and args.attack not in ("pgd", "cw2", "psy"):
         ap.error("--wb-ivector belongs to --attack pgd (--attack %s)" % args.attack)
     if args.wb_air and args.attack != "pgd":
         ap.error("--wb-air belongs to --attack pgd (--attack %s)" % args.attack)
@@ -288,26 +294,28 @@ def main(argv=None, model_factory=None, bob_factory=None):
                 continue
             if val is not None and not (args.bpda and flag in ("--input-transform", "--codec")):
                 ap.error("--attack pgd attacks an undefended victim: %s %s is not differentiated in this version" % (flag, val))
-    if args.attack == "cw2":      # likewise; what fb_attack_cw2 refuses whatever the switches say is refused here by name
+    if args.attack in ("cw2", "psy"):      # likewise; what fb_attack_cw2 refuses whatever the switches say is refused here by name
         if args.architecture != "gmm" and not args.wb_ivector:
-            ap.error("--attack cw2 differentiates an i-vector system only with --wb-ivector (--architecture %s)" % args.architecture)
+            ap.error("--attack %s differentiates an i-vector system only with --wb-ivector (--architecture %s)" % (args.attack, args.architecture))
         if args.eot_size is not None and args.eot_size > 1 and (not args.bpda or args.architecture != "gmm"):
-            ap.error("--attack cw2 runs under expectation over transformation only with --bpda on a GMM-UBM system "
-                     "(--eot-size %d)" % args.eot_size)
+            ap.error("--attack %s runs under expectation over transformation only with --bpda on a GMM-UBM system "
+                     "(--eot-size %d)" % (args.attack, args.eot_size))
         if args.companions > 0:
-            ap.error("--attack cw2 does not take companion utterances in this version (--companions %d)" % args.companions)
+            ap.error("--attack %s does not take companion utterances in this version (--companions %d)" % (args.attack, args.companions))
         for flag, val in (("--air-channel", args.air_channel), ("--feco", args.feco), ("--dither", args.dither)):
             if val is not None:
-                ap.error("--attack cw2 does not differentiate %s %s in this version" % (flag, val))
+                ap.error("--attack %s does not differentiate %s %s in this version" % (args.attack, flag, val))
         for flag, val in (("--input-transform", args.input_transform), ("--codec", None if args.codec == "none" else args.codec)):
             if val is not None and not args.bpda:
-                ap.error("--attack cw2 attacks an undefended victim unless --bpda is given: %s %s" % (flag, val))
+                ap.error("--attack %s attacks an undefended victim unless --bpda is given: %s %s" % (args.attack, flag, val))
         from .cw2 import check_cw2_params
         try:
             check_cw2_params(args.cw2_const, args.cw2_steps, args.max_iter, args.cw2_lr, max(args.cw2_abort_every, 1),
                              args.eot_size if args.eot_size is not None else 1, args.bpda)
             if args.cw2_abort_every < 0:
                 raise ValueError("CW2: --cw2-abort-every must be >= 0")
+            if args.attack == "psy" and not (args.psy_l2_weight >= 0.0 and args.psy_l2_weight < float("inf")):
+                raise ValueError("--psy-l2-weight must be finite and >= 0")
         except ValueError as ex:
             ap.error(str(ex))
 
@@ -371,7 +379,7 @@ def main(argv=None, model_factory=None, bob_factory=None):
             hp.update(universal=True)
             if not args.bpda and not args.wb_ivector:
                 hp.update(bpda=False)
-    if args.attack == "cw2":
+    if args.attack in ("cw2", "psy"):
         hp = dict(confidence=args.adver_thresh, initial_const=args.cw2_const, binary_search_steps=args.cw2_steps,
                   max_iter=args.max_iter, lr=args.cw2_lr, stop_early=args.cw2_abort_every > 0,
                   stop_early_iter=max(args.cw2_abort_every, 1))
@@ -379,7 +387,11 @@ def main(argv=None, model_factory=None, bob_factory=None):
             hp.update(bpda=True, eot_size=args.eot_size if args.eot_size is not None else 1)
         if args.wb_ivector:
             hp.update(ivector=True)
-    if bob_factory is None and args.attack == "cw2":
+    if bob_factory is None and args.attack == "psy":
+        from .psy import Imperceptible
+        bobs = [Imperceptible(task, attack_type, m, window=args.psy_window, l2_weight=args.psy_l2_weight, seed=seed, verbose=False, **hp)
+                for m in models]
+    elif bob_factory is None and args.attack == "cw2":
         from .cw2 import CW2
         bobs = [CW2(task, attack_type, m, seed=seed, verbose=False, **hp) for m in models]
     elif bob_factory is None and args.attack == "pgd" and args.wb_ivector:
@@ -453,6 +465,9 @@ def main(argv=None, model_factory=None, bob_factory=None):
             res = bob.attack(it["audio"], it["cp_path"], threshold=threshold, true=true,
                              target=it["target"], fs=fs, bits_per_sample=bits_per_sample)
             adv, flag = res
+            if args.attack == "psy" and hasattr(res, "best_dist"):
+                print("psy %s: success %d, dist %.6g, over %d, l2 %.6g, snr %.2f dB, c %.3g" %
+                      (it["name"], flag, res.best_dist, res.n_over, res.best_l2, res.snr_db, res.const))
             if args.attack == "cw2" and hasattr(res, "best_l2"):   # the figure this attack is run for
                 print("cw2 %s: success %d, l2 %.6g, snr %.2f dB, c %.3g" % (it["name"], flag, res.best_l2, res.snr_db, res.const))
             write(it["wav_path"], fs, adv)

@@ -234,6 +234,11 @@ struct fb_engine {
   // the L2 white-box attack (fb_attack_cw2): w0, mod, the second moment (the first lives in grad_m) and the best iterate
   // [N] float64, the best int16 row [N], the L2 partials [ceil(N / 256)], the search step's control block
   DevBuf cw2_w0, cw2_mod, cw2_m2, cw2_best_x, cw2_best_row, cw2_l2part, cw2_ctl;
+  // the psychoacoustic attack (fb_attack_psy; it borrows the CW2 buffers above): the twiddle table [W] of psy_tw_W, the
+  // threshold in bit-reversed order [F][W], the frames' gradients [F][W], their hinge and count partials [F], P [F][K] (the
+  // test hook), the search step's control block
+  DevBuf psy_tw, psy_theta, psy_gf, psy_dpart, psy_npart, psy_P, psy_ctl;
+  int psy_tw_W = 0;
   // white-box gradients through the over-the-air channel (fb_set_wb_air)
   int wb_air = 0;                     // the switch: 0 (as created) refuses a channel, as before it existed
   DevBuf wb_air_cot, wb_air_dx;        // the replicas' cotangents on the channel's output [r][N], k_air_conv_t's output [r][N] (r > 1)
@@ -3202,6 +3207,312 @@ extern "C" int fb_debug_cw2_step(fb_engine *e, const fb_cw2_params *c, int64_t N
   *l2_now = h_cw.l2;
   *gate = h_cw.gate;
   *take = h_cw.take;
+  return FB_OK;
+}
+
+// ------------------------------------------------- the psychoacoustic white-box attack
+// fb_attack_psy (the "masking" section of fakebob_hip.h): fb_attack_cw2's loop with the distortion D(delta) + l2_weight * l2.
+// Per iteration wb_enqueue + k_psy_frames + k_psy_ctl + k_psy_step; the reset launch of a search step is CW2's.
+static int psy_frames_of(int64_t N, int W) {
+  const int hop = W / 4;
+  return N == W ? 1 : (int)((N - W + hop - 1) / hop) + 1;
+}
+static int psy_check(const fb_psy_params *m, int64_t N) {
+  if (!m->theta) return fb_fail(FB_E_ARG, "masking: null threshold");
+  const int W = m->window;
+  if (W != 512 && W != 1024 && W != 2048) return fb_fail(FB_E_ARG, "masking: window %d is not 512, 1024 or 2048", W);
+  if (N < W) return fb_fail(FB_E_ARG, "masking: %lld samples are fewer than the window %d", (long long)N, W);
+  const int F = psy_frames_of(N, W);
+  if (m->n_frames != F) return fb_fail(FB_E_ARG, "masking: n_frames %d, but %lld samples at window %d make %d", m->n_frames, (long long)N, W, F);
+  if (!isfinite(m->psd_max) || !(m->psd_max > 0.0)) return fb_fail(FB_E_ARG, "masking: psd_max must be finite and > 0");
+  if (!isfinite(m->l2_weight) || m->l2_weight < 0.0) return fb_fail(FB_E_ARG, "masking: l2_weight must be finite and >= 0");
+  const size_t n = (size_t)F * (size_t)(W / 2 + 1);
+  for (size_t i = 0; i < n; ++i)
+    if (!isfinite(m->theta[i]) || m->theta[i] < 0.0)
+      return fb_fail(FB_E_ARG, "masking: theta[%zu] = %g is not a finite, non-negative power", i, m->theta[i]);
+  return FB_OK;
+}
+// cos and sin of 2 pi t / W for t < W / 2, from arguments of at most pi / 4: exact at the octants and symmetric about them,
+// as sincospi would give them
+static void psy_twiddle(int t, int W, double *c, double *s) {
+  const double w = 2.0 * M_PI / (double)W;
+  if (8 * t == W) { *c = M_SQRT1_2; *s = M_SQRT1_2; }
+  else if (8 * t == 3 * W) { *c = -M_SQRT1_2; *s = M_SQRT1_2; }
+  else if (8 * t < W) { *c = cos(w * t); *s = sin(w * t); }
+  else if (4 * t <= W) { *c = sin(w * (W / 4 - t)); *s = cos(w * (W / 4 - t)); }
+  else if (8 * t < 3 * W) { *c = -sin(w * (t - W / 4)); *s = cos(w * (t - W / 4)); }
+  else { *c = -cos(w * (W / 2 - t)); *s = sin(w * (W / 2 - t)); }
+}
+// the twiddle table of the window (once per window), the threshold in bit-reversed order, the frames' workspace
+static int psy_upload(fb_engine *e, const fb_psy_params *m, int64_t N, bool want_P) {
+  const int W = m->window, H = W / 2, K = H + 1, F = m->n_frames;
+  if (e->psy_tw_W != W) {
+    std::vector<double> tw((size_t)W);
+    for (int t = 0; t < H; ++t) psy_twiddle(t, W, &tw[(size_t)t], &tw[(size_t)(H + t)]);
+    FBCHK(e->psy_tw.ensure(sizeof(double) * (size_t)W));
+    FBCHK(h2d(e, e->psy_tw.p, tw.data(), sizeof(double) * (size_t)W));
+    FBCHK(sync_stream(e));
+    e->psy_tw_W = W;
+  }
+  int logw = 0;
+  while ((1 << logw) < W) ++logw;
+  std::vector<double> br((size_t)F * (size_t)W);
+  for (int f = 0; f < F; ++f)
+    for (int pos = 0; pos < W; ++pos) {
+      int k = 0;
+      for (int b = 0; b < logw; ++b) k |= ((pos >> b) & 1) << (logw - 1 - b);
+      br[(size_t)f * W + pos] = k <= H ? m->theta[(size_t)f * K + k] : INFINITY;
+    }
+  FBCHK(e->psy_theta.ensure(sizeof(double) * br.size()));
+  FBCHK(e->psy_gf.ensure(sizeof(double) * (br.size() > (size_t)N ? br.size() : (size_t)N)));
+  FBCHK(e->psy_dpart.ensure(sizeof(double) * (size_t)F));
+  FBCHK(e->psy_npart.ensure(sizeof(int) * (size_t)F));
+  FBCHK(e->psy_ctl.ensure(sizeof(FbPsyDev)));
+  if (want_P) FBCHK(e->psy_P.ensure(sizeof(double) * (size_t)F * K));
+  FBCHK(h2d(e, e->psy_theta.p, br.data(), sizeof(double) * br.size()));
+  FBCHK(sync_stream(e));   // (br is a local)
+  return FB_OK;
+}
+static void psy_scales(const fb_psy_params *m, double *scale, double *coef) {
+  const double W = (double)m->window;
+  *scale = (8.0 / 3.0) / (W * W) * (pow(10.0, 9.6) / m->psd_max);
+  *coef = 2.0 * *scale / ((double)m->n_frames * (double)(m->window / 2 + 1));
+}
+
+extern "C" int fb_attack_psy(fb_engine *e, const fb_nes_params *p, const fb_cw2_params *c, const fb_psy_params *m,
+                             const double *audio, int64_t N, int16_t *adv_i16, double *adver_f64, double *trace, int *n_trace,
+                             int *rows_per_step, int *success_flag, double *best_dist, double *best_l2, int *best_n_over,
+                             double *final_const) {
+  if (e) e->bench_it = -1;
+  if (e) memset(e->nes_route, 0, sizeof(e->nes_route));
+  if (e) memset(e->wb_route, 0, sizeof(e->wb_route));
+  if (e) e->wb_air_launches = 0;
+  if (e) e->wb_feco_launches = 0;
+  if (e) e->wb_universal_launches = 0;
+  if (!e || !p || !c || !m || !audio || !adv_i16 || !success_flag || !rows_per_step || !best_dist || !best_l2 || !best_n_over ||
+      !final_const)
+    return fb_fail(FB_E_ARG, "null argument");
+  if (!e->have_gmm) return fb_fail(FB_E_STATE, "no model loaded");
+  FBCHK(cw2_check(e, p, c));   // (CW2's own checks and messages)
+  fb_nes_params q;
+  FBCHK(wb_check(e, p, audio, N, &q));
+  FBCHK(psy_check(m, N));
+  q.plateau_length = 0;   // (the loop control of wb_enqueue's control launch: no plateau rule, no stop of its own)
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(prepare_nes_replicas(e, N, 1));
+  FBCHK(ensure_nes_buffers(e, N, 1));
+  FBCHK(wb_prepare(e, N, e->h_frame_off[1], true));
+  FBCHK(cw2_buffers(e, N));
+  FBCHK(psy_upload(e, m, N, false));
+  const int S = fb_num_speakers(e);
+  const int W = m->window, F = m->n_frames, K = W / 2 + 1;
+  double scale, coef;
+  psy_scales(m, &scale, &coef);
+  const int steps = c->search_steps, max_iter = p->max_iter;
+  const size_t total = (size_t)steps * (size_t)max_iter;
+  {  // w0 = atanh(0.999999 a0) on the host: the device never evaluates atanh
+    std::vector<double> w0((size_t)N);
+    for (int64_t n = 0; n < N; ++n) w0[(size_t)n] = atanh(0.999999 * audio[n]);
+    FBCHK(h2d(e, e->cw2_w0.p, w0.data(), sizeof(double) * (size_t)N));
+    FBCHK(sync_stream(e));
+  }
+  FBCHK(attack_start(e, audio, N, 0, nullptr));
+  // the best slots before any success: the cast of the original audio and the audio itself
+  fb_launch_quantize(e->stream, e->audio.as<double>(), N, nes_bits(p), e->cw2_best_row.as<int16_t>());
+  HIPCHK(hipMemcpyAsync(e->cw2_best_x.p, e->audio.p, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, e->stream));
+  double *trace_dev = nullptr;
+  if (trace) {
+    FBCHK(e->trace_dev.ensure(sizeof(double) * total * (5 + S)));
+    trace_dev = e->trace_dev.as<double>();
+  }
+  FBCHK(e->ticks.ensure(sizeof(unsigned long long) * (total + 1)));
+  FBCHK(ctl_reset(e, &q, true, true, e->ticks.as<unsigned long long>()));
+  FbCtlDev *ctl = e->ctl.as<FbCtlDev>();
+  FbPsyDev *ps = e->psy_ctl.as<FbPsyDev>();
+  FbPsyDev h_ps;
+  memset(&h_ps, 0, sizeof(h_ps));
+  h_ps.gbest_dist = INFINITY;
+  h_ps.cw.gbest_l2 = INFINITY;
+  h_ps.cw.prev = INFINITY;
+  FBCHK(h2d(e, ps, &h_ps, sizeof(h_ps)));
+  const char *ev = getenv("FB_ATTACK_BATCH");
+  const int b = ev ? atoi(ev) : 4;
+  const int look = b < 1 ? 1 : (b > 16 ? 16 : b);
+  double cc = c->initial_const, lo = 0.0, hi = 1e10;
+  int rows = 0;
+  for (int s = 0; s < steps; ++s) {
+    fb_launch_cw2_reset(e->stream, e->cw2_w0.as<double>(), e->audio.as<double>(), N, cc, e->cw2_mod.as<double>(), e->grad_m.as<double>(),
+                        e->cw2_m2.as<double>(), e->adver.as<double>(), e->cw2_l2part.as<double>(), &ps->cw, ctl);
+    double p1 = 1.0, p2 = 1.0;
+    for (int queued = 0; queued < max_iter;) {
+      const int nb = max_iter - queued < look ? max_iter - queued : look;
+      int rc = FB_OK, status = 0;
+      for (int k = 0; k < nb && rc == FB_OK; ++k) {
+        const int t = queued + k;
+        rc = wb_enqueue(e, &q, N, (uint32_t)((size_t)s * (size_t)max_iter + (size_t)t), false, ctl, nullptr);
+        if (rc != FB_OK) break;
+        p1 *= c->beta1;
+        p2 *= c->beta2;
+        fb_launch_psy_frames(e->stream, W, F, e->adver.as<double>(), e->audio.as<double>(), N, e->psy_tw.as<double>(),
+                             e->psy_theta.as<double>(), scale, coef, e->psy_gf.as<double>(), e->psy_dpart.as<double>(),
+                             e->psy_npart.as<int>(), nullptr, ctl);
+        fb_launch_psy_ctl(e->stream, e->nes_out.as<FbNesDev>(), e->scores.as<double>(), S, e->cw2_l2part.as<double>(), N,
+                          e->psy_dpart.as<double>(), e->psy_npart.as<int>(), F, K, m->l2_weight, ps, ctl, trace_dev, t, c->abort_every);
+        fb_launch_psy_step(e->stream, e->grad.as<double>(), e->psy_gf.as<double>(), F, W, e->audio.as<double>(), e->cw2_w0.as<double>(),
+                           N, m->l2_weight, c->beta1, c->beta2, c->lr / (1.0 - p1), sqrt(1.0 - p2), c->adam_eps,
+                           e->cw2_mod.as<double>(), e->grad_m.as<double>(), e->cw2_m2.as<double>(), e->adver.as<double>(),
+                           e->wav.as<int16_t>(), e->cw2_best_row.as<int16_t>(), e->cw2_best_x.as<double>(),
+                           e->cw2_l2part.as<double>(), ps);
+      }
+      hipError_t he = hipSuccess;
+      if (rc == FB_OK) he = hipMemcpyAsync(e->h_ctl, ctl, sizeof(FbCtlDev), hipMemcpyDeviceToHost, e->stream);
+      if (rc == FB_OK && he == hipSuccess) rc = d2h(e, &status, e->wb_status.p, sizeof(int));
+      if (rc == FB_OK && he == hipSuccess) rc = d2h(e, &h_ps, ps, sizeof(h_ps));
+      if (rc != FB_OK || he != hipSuccess) {
+        (void)sync_stream(e);
+        HIPCHK(he);
+        return rc;
+      }
+      queued += nb;
+      FBCHK(sync_stream(e));
+      if (e->gmm_pending) FBCHK(time_collect(e));
+      FBCHK(wb_status_check(e, status));
+      if (e->h_ctl->err != 0) return fb_fail(FB_E_NO_VOICED, "the adversarial audio has no voiced frames");
+      if (e->h_ctl->stop) break;   // the abort rule
+    }
+    rows_per_step[s] = h_ps.cw.rows - rows;
+    rows = h_ps.cw.rows;
+    cw2_next_const(h_ps.cw.found != 0, &lo, &hi, &cc);
+  }
+  HIPCHK(hipGetLastError());
+  e->nes_iters += rows;
+  FBCHK(collect_iter_seconds(e, rows));
+  if (trace && rows > 0) FBCHK(d2h(e, trace, trace_dev, sizeof(double) * (size_t)rows * (5 + S)));
+  *success_flag = h_ps.gbest_dist < INFINITY ? 1 : -1;
+  *best_dist = h_ps.gbest_dist;
+  *best_l2 = h_ps.cw.gbest_l2;
+  *best_n_over = h_ps.gbest_dist < INFINITY ? h_ps.gbest_n_over : 0;
+  *final_const = cc;
+  if (n_trace) *n_trace = rows;
+  FBCHK(d2h(e, adv_i16, e->cw2_best_row.p, sizeof(int16_t) * (size_t)N));
+  if (adver_f64) FBCHK(d2h(e, adver_f64, e->cw2_best_x.p, sizeof(double) * (size_t)N));
+  FBCHK(sync_stream(e));
+  return FB_OK;
+}
+
+// Test hook: the masking loss and its gradient at a perturbation handed in (fakebob_hip_test.h); no system has to be loaded
+extern "C" int fb_debug_psy_loss(fb_engine *e, const fb_psy_params *m, int64_t N, const double *delta, double *D, int *n_over,
+                                 double *gd, double *P) {
+  if (!e || !m || !delta || !D || !n_over || !gd || N <= 0) return fb_fail(FB_E_ARG, "bad argument");
+  FBCHK(psy_check(m, N));
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  e->cached_B = -1;
+  FBCHK(ensure_nes_buffers(e, N, 1, 1));
+  FBCHK(psy_upload(e, m, N, P != nullptr));
+  const int W = m->window, F = m->n_frames, K = W / 2 + 1;
+  const size_t nb = sizeof(double) * (size_t)N;
+  double scale, coef;
+  psy_scales(m, &scale, &coef);
+  FBCHK(h2d(e, e->adver.p, delta, nb));
+  HIPCHK(hipMemsetAsync(e->audio.p, 0, nb, e->stream));   // delta = x - a0 with a0 = +0.0: exact
+  fb_launch_psy_frames(e->stream, W, F, e->adver.as<double>(), e->audio.as<double>(), N, e->psy_tw.as<double>(),
+                       e->psy_theta.as<double>(), scale, coef, e->psy_gf.as<double>(), e->psy_dpart.as<double>(), e->psy_npart.as<int>(),
+                       P ? e->psy_P.as<double>() : nullptr, nullptr);
+  fb_launch_psy_ola(e->stream, e->psy_gf.as<double>(), F, W, N, e->grad.as<double>());
+  std::vector<double> dp((size_t)F);
+  std::vector<int> np((size_t)F);
+  FBCHK(d2h(e, dp.data(), e->psy_dpart.p, sizeof(double) * (size_t)F));
+  FBCHK(d2h(e, np.data(), e->psy_npart.p, sizeof(int) * (size_t)F));
+  FBCHK(d2h(e, gd, e->grad.p, nb));
+  if (P) FBCHK(d2h(e, P, e->psy_P.p, sizeof(double) * (size_t)F * K));
+  FBCHK(sync_stream(e));
+  HIPCHK(hipGetLastError());
+  double d = 0.0;
+  int cnt = 0;
+  for (int f = 0; f < F; ++f) { d += dp[(size_t)f]; cnt += np[(size_t)f]; }   // ascending frames, as k_psy_ctl adds them
+  *D = d / ((double)F * (double)K);
+  *n_over = cnt;
+  return FB_OK;
+}
+
+// Test hook: one k_psy_ctl + k_psy_step pair on arrays handed in (fakebob_hip_test.h); no system has to be loaded
+extern "C" int fb_debug_psy_step(fb_engine *e, const fb_cw2_params *c, double l2_weight, int64_t N, const double *g, const double *gd,
+                                 const double *x, const double *a0, const double *w0, const double *mod, const double *m1,
+                                 const double *m2, double adver_loss, double cc, double D, int n_over, double gbest_dist, int t,
+                                 double p1, double p2, double *mod_out, double *m1_out, double *m2_out, double *x_next,
+                                 double *l2_now, double *dist_now, double *l2_next, int *gate, int *take, int16_t *best_row,
+                                 double *best_x) {
+  if (!e || !c || !g || !gd || !x || !a0 || !w0 || !mod || !m1 || !m2 || !mod_out || !m1_out || !m2_out || !x_next || !l2_now ||
+      !dist_now || !l2_next || !gate || !take || !best_row || !best_x || N <= 0 || t < 0)
+    return fb_fail(FB_E_ARG, "bad argument");
+  if (!(p1 >= 0.0 && p1 < 1.0) || !(p2 >= 0.0 && p2 < 1.0)) return fb_fail(FB_E_ARG, "p1 and p2 must lie in [0, 1)");
+  if (!isfinite(l2_weight) || l2_weight < 0.0) return fb_fail(FB_E_ARG, "masking: l2_weight must be finite and >= 0");
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  e->cached_B = -1;
+  FBCHK(ensure_nes_buffers(e, N, 1, 1));
+  FBCHK(e->wav.ensure(sizeof(int16_t) * (size_t)N));
+  FBCHK(cw2_buffers(e, N));
+  const size_t nb = sizeof(double) * (size_t)N;
+  FBCHK(e->psy_gf.ensure(nb));
+  FBCHK(e->psy_dpart.ensure(sizeof(double)));
+  FBCHK(e->psy_npart.ensure(sizeof(int)));
+  FBCHK(e->psy_ctl.ensure(sizeof(FbPsyDev)));
+  FBCHK(h2d(e, e->grad.p, g, nb));
+  FBCHK(h2d(e, e->psy_gf.p, gd, nb));
+  FBCHK(h2d(e, e->adver.p, x, nb));
+  FBCHK(h2d(e, e->audio.p, a0, nb));
+  FBCHK(h2d(e, e->cw2_w0.p, w0, nb));
+  FBCHK(h2d(e, e->cw2_mod.p, mod, nb));
+  FBCHK(h2d(e, e->grad_m.p, m1, nb));
+  FBCHK(h2d(e, e->cw2_m2.p, m2, nb));
+  FBCHK(h2d(e, e->psy_dpart.p, &D, sizeof(double)));   // one "frame" of one bin: D = D / (1 * 1)
+  FBCHK(h2d(e, e->psy_npart.p, &n_over, sizeof(int)));
+  fb_nes_params q;
+  memset(&q, 0, sizeof(q));
+  FBCHK(ctl_reset(e, &q, false, true, nullptr));
+  FbNesDev h_out;
+  memset(&h_out, 0, sizeof(h_out));
+  h_out.adver_loss = adver_loss;
+  FBCHK(h2d(e, e->nes_out.p, &h_out, sizeof(h_out)));
+  FbPsyDev h_ps;
+  memset(&h_ps, 0, sizeof(h_ps));
+  h_ps.cw.c = cc; h_ps.gbest_dist = gbest_dist; h_ps.cw.gbest_l2 = INFINITY; h_ps.cw.prev = INFINITY;
+  FbPsyDev *ps = e->psy_ctl.as<FbPsyDev>();
+  FBCHK(h2d(e, ps, &h_ps, sizeof(h_ps)));
+  FBCHK(sync_stream(e));   // (D and n_over are arguments)
+  // the row the forward would have scored, and the best slots as an attack without a success holds them
+  fb_launch_quantize(e->stream, e->adver.as<double>(), N, 16, e->wav.as<int16_t>());
+  fb_launch_quantize(e->stream, e->audio.as<double>(), N, 16, e->cw2_best_row.as<int16_t>());
+  HIPCHK(hipMemcpyAsync(e->cw2_best_x.p, e->audio.p, nb, hipMemcpyDeviceToDevice, e->stream));
+  fb_launch_cw2_l2(e->stream, e->adver.as<double>(), e->audio.as<double>(), N, e->cw2_l2part.as<double>());
+  fb_launch_psy_ctl(e->stream, e->nes_out.as<FbNesDev>(), e->scores.as<double>(), 0, e->cw2_l2part.as<double>(), N,
+                    e->psy_dpart.as<double>(), e->psy_npart.as<int>(), 1, 1, l2_weight, ps, e->ctl.as<FbCtlDev>(), nullptr, t,
+                    c->abort_every);
+  FBCHK(d2h(e, &h_ps, ps, sizeof(h_ps)));   // (queued before the step launch: l2, dist, gate and take as k_psy_ctl left them)
+  fb_launch_psy_step(e->stream, e->grad.as<double>(), e->psy_gf.as<double>(), 0, 0, e->audio.as<double>(), e->cw2_w0.as<double>(), N,
+                     l2_weight, c->beta1, c->beta2, c->lr / (1.0 - p1), sqrt(1.0 - p2), c->adam_eps, e->cw2_mod.as<double>(),
+                     e->grad_m.as<double>(), e->cw2_m2.as<double>(), e->adver.as<double>(), e->wav.as<int16_t>(),
+                     e->cw2_best_row.as<int16_t>(), e->cw2_best_x.as<double>(), e->cw2_l2part.as<double>(), ps);
+  const size_t np = (size_t)((N + 255) / 256);
+  std::vector<double> part(np);
+  FBCHK(d2h(e, part.data(), e->cw2_l2part.p, sizeof(double) * np));
+  FBCHK(d2h(e, mod_out, e->cw2_mod.p, nb));
+  FBCHK(d2h(e, m1_out, e->grad_m.p, nb));
+  FBCHK(d2h(e, m2_out, e->cw2_m2.p, nb));
+  FBCHK(d2h(e, x_next, e->adver.p, nb));
+  FBCHK(d2h(e, best_row, e->cw2_best_row.p, sizeof(int16_t) * (size_t)N));
+  FBCHK(d2h(e, best_x, e->cw2_best_x.p, nb));
+  FBCHK(sync_stream(e));
+  HIPCHK(hipGetLastError());
+  double l2 = 0.0;
+  for (size_t i = 0; i < np; ++i) l2 += part[i];   // ascending block order, as k_psy_ctl adds them
+  *l2_next = l2;
+  *l2_now = h_ps.cw.l2;
+  *dist_now = h_ps.dist;
+  *gate = h_ps.cw.gate;
+  *take = h_ps.cw.take;
   return FB_OK;
 }
 

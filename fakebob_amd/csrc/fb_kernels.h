@@ -414,8 +414,37 @@ void fb_launch_cw2_step(hipStream_t s, const double *g, const double *a0, const 
                         double step_size, double bc2s, double adam_eps, double *mod, double *m1, double *m2, double *x,
                         const int16_t *row, int16_t *best_row, double *best_x, double *l2_part, const FbCw2Dev *cw);
 
+// ---- the psychoacoustic white-box attack (fb_attack_psy; psy_kernels.hip) ----------------------------------------------
+// Device-side control of a search step: k_cw2_reset starts `cw` over as for CW2; k_psy_ctl decides on dist instead of l2
+struct FbPsyDev {
+  FbCw2Dev cw;         // as in CW2; gbest_l2 is l2 of the best iterate (the best is chosen on gbest_dist)
+  double gbest_dist;   // the smallest dist over the successful iterates of the whole attack (+inf: none yet)
+  double dist, D;      // of the iterate just scored: dist = D + l2_weight * l2
+  int n_over;          // bins of the iterate just scored with P > theta
+  int gbest_n_over;    // n_over of the best iterate
+};
+// The masking loss of delta = x - a0 (zero past N), one workgroup per frame: W in {512, 1024, 2048}, hop W / 4, F frames.
+// tw[W]: cos(2 pi t / W), t < W / 2, then sin(2 pi t / W).  theta_br[F][W]: theta[f][k] at position bitrev(k), +inf where
+// k > W / 2.  P = |X|^2 * scale; d_part[f] = sum_k max(P - theta, 0), n_part[f] = #{P > theta}; gf[f][W] = the frame's share of
+// dD / d delta with coef = 2 scale / (F K).  P_out [F][W/2+1] and ctl are nullable; behind a stop (ctl->stop) nothing is written.
+void fb_launch_psy_frames(hipStream_t s, int W, int F, const double *x, const double *a0, int64_t N, const double *tw,
+                          const double *theta_br, double scale, double coef, double *gf, double *d_part, int *n_part, double *P_out,
+                          const FbCtlDev *ctl);
+// gd[n] = the overlap-add of gf[F][W] at hop W / 4, ascending f (the test hook; k_psy_step does it in passing)
+void fb_launch_psy_ola(hipStream_t s, const double *gf, int F, int W, int64_t N, double *gd);
+// k_cw2_ctl's decisions with dist = (sum_f d_part[f]) / (F K) + l2_weight * l2; trace row {dist, l2, n_over, adver_loss, c, score0[S]}
+void fb_launch_psy_ctl(hipStream_t s, const FbNesDev *out, const double *scores, int S, const double *l2_part, int64_t N,
+                       const double *d_part, const int *n_part, int F, int K, double l2_weight, FbPsyDev *ps, FbCtlDev *ctl,
+                       double *trace, int t, int abort_every);
+// k_cw2_step's update with G = (((c gate) g + gd) + l2_weight (2 (x - a0))) (1 - x x); gd[n] = the overlap-add of gf[F][W] in
+// ascending f, or gf[n] itself when F == 0
+void fb_launch_psy_step(hipStream_t s, const double *g, const double *gf, int F, int W, const double *a0, const double *w0, int64_t N,
+                        double l2_weight, double beta1, double beta2, double step_size, double bc2s, double adam_eps, double *mod,
+                        double *m1, double *m2, double *x, const int16_t *row, int16_t *best_row, double *best_x, double *l2_part,
+                        const FbPsyDev *ps);
+
 // ---- front-end ------------------------------------------------------------
-// MFCC of every frame of a (ragged) batch.  wav_off[B+1], frame_off[B+1] device arrays.
+// MFCC of every frame of a (ragged) batch. wav_off[B+1], frame_off[B+1] device arrays.
 // frame_rec: [total_frames][4] int32 = {absolute start sample (int64 in two words), start within the
 // utterance, utterance length} (used by the P = 512 kernel instead of a search in frame_off).  Returns the kernel it
 // launched: FB_ROUTE_MFCC_R16_* or FB_ROUTE_MFCC_GENERIC (fb_debug_frontend_route)

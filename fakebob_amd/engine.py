@@ -44,6 +44,21 @@ def cw2_params(initial_const=1e-3, search_steps=9, lr=1e-2, beta1=0.9, beta2=0.9
     return q
 
 
+def psy_params(theta, psd_max, window=2048, l2_weight=0.0):
+    """fb_psy_params: the masking threshold of Engine.attack_psy (fakebob_hip.h, "masking"; fakebob_amd.masking computes theta
+    and psd_max).  The structure keeps theta alive."""
+    theta = np.ascontiguousarray(theta, np.float64)
+    if theta.ndim != 2:
+        raise ValueError("psy_params: theta must be [F, K]")
+    m = N.PsyParams()
+    m._theta = theta
+    m.theta = theta.ctypes.data
+    m.n_frames = int(theta.shape[0]); m.window = int(window); m.psd_max = float(psd_max); m.l2_weight = float(l2_weight)
+    if theta.shape[1] != m.window // 2 + 1:
+        raise ValueError("psy_params: theta has %d bins, window %d has %d" % (theta.shape[1], m.window, m.window // 2 + 1))
+    return m
+
+
 def kv_params(window=100, grid=15, q_max=65536, max_rounds=32):
     """fb_kv_params: the search of Engine.attack_kenansville (fakebob_hip.h, "decision-only attack")."""
     k = N.KvParams()
@@ -760,6 +775,56 @@ class Engine(object):
             [N.ptr(o) for o in out] + [C.byref(l2), C.byref(l2n), C.byref(gate), C.byref(take), N.ptr(best_row), N.ptr(best_x)])))
         return dict(mod=out[0], m1=out[1], m2=out[2], x_next=out[3], l2=l2.value, l2_next=l2n.value, gate=gate.value,
                     take=take.value, best_row=best_row, best_x=best_x)
+
+    def attack_psy(self, params, cw2, psy, audio):
+        """fb_attack_psy: attack_cw2's loop with the psychoacoustic masking distortion D(delta) + l2_weight * l2 (fakebob_hip.h,
+        "masking") -> dict(adv (N,) int16, success +-1, adver_f64 (N,), trace (rows, 5 + S) of {dist, l2, n_over, adver_loss, c,
+        score0}, rows_per_step (search_steps,), best_dist, best_l2, n_over, const).  psy: psy_params(theta, psd_max, ...)."""
+        audio = np.ascontiguousarray(audio, np.float64).reshape(-1)
+        n, S = audio.size, max(self.n_speakers, 1)
+        steps = int(cw2.search_steps)
+        total = max(steps, 0) * max(int(params.max_iter), 0)
+        if not 1 <= steps <= 32 or total > 2 ** 30:   # (the library says which; nothing of that size is allocated for it here)
+            total = 1
+        adv = np.empty(n, np.int16)
+        adv_f = np.empty(n, np.float64)
+        trace = np.zeros((max(total, 1), 5 + S), np.float64)
+        per = np.zeros(32, np.int32)
+        nt, flag, no, dist, l2, cc = C.c_int(), C.c_int(), C.c_int(), C.c_double(), C.c_double(), C.c_double()
+        N.check(self._L.fb_attack_psy(self._h, C.byref(params), C.byref(cw2), C.byref(psy), N.ptr(audio), C.c_int64(n), N.ptr(adv),
+                                      N.ptr(adv_f), N.ptr(trace), C.byref(nt), N.ptr(per), C.byref(flag), C.byref(dist), C.byref(l2),
+                                      C.byref(no), C.byref(cc)))
+        return dict(adv=adv, success=flag.value, adver_f64=adv_f, trace=trace[:nt.value].copy(), rows_per_step=per[:steps].copy(),
+                    best_dist=dist.value, best_l2=l2.value, n_over=no.value, const=cc.value)
+
+    def debug_psy_loss(self, psy, delta, want_P=False):
+        """The masking loss and its gradient at a perturbation handed in (fb_debug_psy_loss) -> dict(D, n_over, gd (N,), P [F, K]
+        or None).  No system has to be loaded."""
+        delta = np.ascontiguousarray(delta, np.float64).reshape(-1)
+        n = delta.size
+        gd = np.empty(n, np.float64)
+        P = np.empty((max(int(psy.n_frames), 1), max(int(psy.window), 0) // 2 + 1), np.float64) if want_P else None
+        D, no = C.c_double(), C.c_int()
+        N.check(self._L.fb_debug_psy_loss(self._h, C.byref(psy), C.c_int64(n), N.ptr(delta), C.byref(D), C.byref(no), N.ptr(gd),
+                                          N.ptr(P) if want_P else None))
+        return dict(D=D.value, n_over=no.value, gd=gd, P=P)
+
+    def debug_psy_step(self, cw2, l2_weight, g, gd, x, a0, w0, mod, m1, m2, adver_loss, c, D, n_over, gbest_dist, t, p1, p2):
+        """One k_psy_ctl + k_psy_step pair on arrays handed in (fb_debug_psy_step) -> dict(mod, m1, m2, x_next, l2, dist, l2_next,
+        gate, take, best_row, best_x).  No system has to be loaded."""
+        arrs = [np.ascontiguousarray(a, np.float64).reshape(-1) for a in (g, gd, x, a0, w0, mod, m1, m2)]
+        n = arrs[0].size
+        if any(a.size != n for a in arrs):
+            raise ValueError("debug_psy_step: the eight arrays must have one length")
+        out = [np.empty(n, np.float64) for _ in range(4)]
+        best_row, best_x = np.empty(n, np.int16), np.empty(n, np.float64)
+        l2, dist, l2n, gate, take = C.c_double(), C.c_double(), C.c_double(), C.c_int(), C.c_int()
+        N.check(self._L.fb_debug_psy_step(self._h, C.byref(cw2), C.c_double(l2_weight), C.c_int64(n), *([N.ptr(a) for a in arrs] + [
+            C.c_double(adver_loss), C.c_double(c), C.c_double(D), C.c_int(int(n_over)), C.c_double(gbest_dist), C.c_int(int(t)),
+            C.c_double(p1), C.c_double(p2)] + [N.ptr(o) for o in out] + [C.byref(l2), C.byref(dist), C.byref(l2n), C.byref(gate),
+                                                                         C.byref(take), N.ptr(best_row), N.ptr(best_x)])))
+        return dict(mod=out[0], m1=out[1], m2=out[2], x_next=out[3], l2=l2.value, dist=dist.value, l2_next=l2n.value,
+                    gate=gate.value, take=take.value, best_row=best_row, best_x=best_x)
 
     def debug_defence_vjp(self, wav, cot, seed=0, stream=0, iter=0):
         """The defences' transposes alone (fb_debug_defence_vjp): wav (n,) int16, cot (r, n) float64 on the rows the front

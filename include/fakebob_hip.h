@@ -37,6 +37,7 @@
  *                             SpeakerGuard's evaluation (FGSM, PGD, the margin-loss CW-inf) on a GMM-UBM system
  *   fb_attack_cw2             (none in FAKEBOB: SpeakerGuard's CW2 -- Carlini-Wagner's L2 attack in tanh space with Adam and
  *                             a binary search over the constant, on that gradient; it minimises the distortion)
+ *   fb_attack_psy             (none in FAKEBOB: that attack with Qin et al.'s psychoacoustic masking loss as the distortion)
  *   fb_set_wb_bpda / fb_get_grad_wb_iter   (none in FAKEBOB: the adaptive form of those attacks on a DEFENDED victim -- BPDA
  *                             through the input-transform chain and the codec, EOT over the random stages)
  *   fb_set_wb_ivector         (none in FAKEBOB: the same white-box calls on an i-vector-PLDA system, the frames' component
@@ -776,6 +777,41 @@ typedef struct { double initial_const; int search_steps; double lr, beta1, beta2
 int fb_attack_cw2(fb_engine *e, const fb_nes_params *p, const fb_cw2_params *q, const double *audio, int64_t N, int16_t *adv_i16,
                   double *adver_f64 /*[N], nullable*/, double *trace /*[search_steps*max_iter][3+S], nullable*/, int *n_trace,
                   int *rows_per_step /*[search_steps]*/, int *success_flag, double *best_l2, double *final_const);
+
+/* ---- masking: the CW attack that hides under the voice (Qin et al., "Imperceptible, robust and targeted adversarial examples
+ * for ASR": the perturbation's short-time power spectrum is pushed under the masking threshold of the speech it rides on) -----
+ * fb_attack_psy is fb_attack_cw2 with a perceptual distortion in place of |delta|^2.  The threshold theta is host work, done
+ * once per attack (fakebob_amd/masking.py states the model); the library takes it as data.
+ * Framing.  Window W in {512, 1024, 2048}, hop = W/4, K = W/2 + 1 bins.  N >= W samples make F = 1 frames if N == W, else
+ * ceil((N - W) / hop) + 1; the signal is extended with zeros to (F-1)*hop + W, so every sample lies in a frame.  The window is
+ * the periodic Hann h[n] = 0.5 - 0.5 cos(2 pi n / W), and
+ *   p(v)[f,k] = (8/3) * |sum_n h[n] v[f*hop + n] exp(-2 pi i k n / W)|^2 / W^2.
+ * Loss.  With theta[F][K] >= 0 (linear power, from masking_threshold on a0) and psd_max = max p(a0):
+ *   P = p(delta) * (10^9.6 / psd_max)
+ *   D(delta) = (1 / (F K)) sum_{f,k} max(P - theta, 0)        n_over = #{(f,k) : P > theta}
+ *   gd = dD / d delta; a bin at equality (P == theta) contributes nothing to D, n_over or gd.
+ * The device evaluates P by a radix-2 FFT of the windowed frame in float64 (twiddles from a host table, exact at the octants),
+ * and gd as the transpose: the one-sided spectrum times [P > theta], the inverse transform, the window again, the overlap-add of
+ * the at most four frames that hold a sample in ascending f.  D is the frames' hinge sums added in ascending f, divided by
+ * F K.  No floating-point atomics: every sum has one fixed order, so a run repeats bit for bit and does not depend on
+ * FB_ATTACK_BATCH.  D, gd and P are NOT bit-exact contracts against a host DFT (an FFT rounds about log2 W times where a DFT
+ * matrix rounds once; DESIGN.md section 6 has the bar); n_over is exact wherever no bin sits within that error of its threshold.
+ * The attack is the pseudo-code of fb_attack_cw2 verbatim with these replacements:
+ *   delta = x - a0
+ *   dist = D(delta) + l2_weight * l2
+ *   L = (c*gate)*adver_loss + dist
+ *   G = (((c*gate)*g + gd) + l2_weight*(2*(x - a0))) * (1 - x*x)
+ *   best-so-far and `take` are decided on dist (gbest_dist in place of gbest_l2)
+ *   trace row = {dist, l2, n_over, adver_loss, c, score0[S]}
+ * Outputs: best_dist (+inf without a success), best_l2 and best_n_over of the iterate that holds it, the rest as fb_attack_cw2.
+ * Victims and refusals are those of fb_attack_cw2, by the same checks (one function serves both: its messages say "CW2").  Also FB_E_ARG: a null
+ * fb_psy_params or theta; a window outside the three; N < W; n_frames != F(N, W); a non-finite or negative theta entry; a
+ * non-finite or non-positive psd_max; a non-finite or negative l2_weight.  A refusal leaves the engine as it was. */
+typedef struct { const double *theta /*[n_frames][window/2 + 1]*/; int n_frames; int window; double psd_max; double l2_weight; } fb_psy_params;
+int fb_attack_psy(fb_engine *e, const fb_nes_params *p, const fb_cw2_params *q, const fb_psy_params *m, const double *audio, int64_t N,
+                  int16_t *adv_i16, double *adver_f64 /*[N], nullable*/, double *trace /*[search_steps*max_iter][5+S], nullable*/,
+                  int *n_trace, int *rows_per_step /*[search_steps]*/, int *success_flag, double *best_dist, double *best_l2,
+                  int *best_n_over, double *final_const);
 
 const char *fb_last_error(void);
 int fb_version(void);

@@ -323,6 +323,19 @@ int fb_debug_cw2_step(fb_engine *e, const fb_cw2_params *q, int64_t N, const dou
                       double gbest_l2, int t, double p1, double p2, double *mod_out, double *m1_out, double *m2_out, double *x_next,
                       double *l2_now, double *l2_next, int *gate, int *take, int16_t *best_row, double *best_x);
 
+/* Masking (fakebob_hip.h: "masking").  Neither hook needs a loaded system.
+ * fb_debug_psy_loss: k_psy_frames and the overlap-add of k_psy_step on a perturbation delta[N] handed in -> D, n_over, gd[N] and
+ * (nullable) P[F][K]; m as fb_attack_psy takes it (l2_weight is checked, not used), with its refusals.
+ * fb_debug_psy_step: ONE k_psy_ctl + k_psy_step pair as fb_debug_cw2_step runs CW2's, with gd[N] handed in beside g, and D and
+ * n_over of x as k_psy_frames would have left them.  Out, beside fb_debug_cw2_step's: dist_now = D + l2_weight * l2_now. */
+int fb_debug_psy_loss(fb_engine *e, const fb_psy_params *m, int64_t N, const double *delta, double *D, int *n_over, double *gd,
+                      double *P /*[F][K], nullable*/);
+int fb_debug_psy_step(fb_engine *e, const fb_cw2_params *q, double l2_weight, int64_t N, const double *g, const double *gd,
+                      const double *x, const double *a0, const double *w0, const double *mod, const double *m1, const double *m2,
+                      double adver_loss, double c, double D, int n_over, double gbest_dist, int t, double p1, double p2,
+                      double *mod_out, double *m1_out, double *m2_out, double *x_next, double *l2_now, double *dist_now,
+                      double *l2_next, int *gate, int *take, int16_t *best_row, double *best_x);
+
 /* White-box gradients through a defended victim (fakebob_hip.h: fb_set_wb_bpda).
  * fb_debug_defence_vjp: the defences alone.  The forward of the defences currently set -- input-transform chain, codec -- on
  * the ONE row wav[n] for the engine's r = fb_set_eot replicas at (seed, stream, epoch = iter) of the noise RNG contract, as the
