@@ -9,31 +9,9 @@
 //   k_cw2_step    element-wise: the copy to the best slots when `take`, the Adam step in tanh space, x_next, its L2 partials
 // All arithmetic is float64, one rounding per operation (no contraction); division and square root are correctly rounded, so
 // m1, m2 and mod are bit-exact contracts; tanh is the device library's.  No floating-point atomics: a block of 256 consecutive
-// samples is summed by the fixed tree below and the blocks are added in ascending order by one thread.
-#include <math.h>
-
-#include "fb_device.h"
-#include "fb_kernels.h"
-
-// The sum of the 256 terms d[0 .. 255] of a block (terms past N are +0.0), lane i holding d[i]: for h = 128, 64, 32, ..., 1 in
-// this order d[i] = d[i] + d[i + h] for every i < h; the block's sum is d[0].  (h = 128 and 64 through LDS, the rest inside
-// wave 0.)  Valid in thread 0.
-__device__ __forceinline__ double cw2_block_sum(double d, double *__restrict__ lds) {
-  const int i = threadIdx.x;
-  lds[i] = d;
-  __syncthreads();
-  if (i < 128) lds[i] = __dadd_rn(lds[i], lds[i + 128]);
-  __syncthreads();
-  if (i >= 64) return 0.0;
-  d = __dadd_rn(lds[i], lds[i + 64]);
-  for (int h = 32; h >= 1; h >>= 1) d = __dadd_rn(d, __shfl_down(d, h, 64));
-  return d;
-}
-
-__device__ __forceinline__ double cw2_sq_diff(double x, double a) {
-  const double d = __dsub_rn(x, a);
-  return __dmul_rn(d, d);
-}
+// samples is summed by a fixed tree and the blocks are added in ascending order by one thread.  Those two sums, the decisions of
+// k_cw2_ctl behind its `take` test and the Adam step of k_cw2_step behind its G are cw2_device.h's, shared with psy_kernels.hip.
+#include "cw2_device.h"
 
 __global__ __launch_bounds__(256) void k_cw2_reset(const double *__restrict__ w0, const double *__restrict__ a0, int64_t N, double c,
                                                    double *__restrict__ mod, double *__restrict__ m1, double *__restrict__ m2,
@@ -76,47 +54,21 @@ __global__ __launch_bounds__(64) void k_cw2_ctl(const FbNesDev *__restrict__ out
     if (lane == 0) cw->mode = 0;
     return;
   }
-  // the one wave fetches 64 partials at a time (one thread alone would wait for every load in turn: 13 us at 188 blocks);
-  // thread 0 adds them in ascending block order
-  double l2 = 0.0;
-  for (int base = 0; base < n_part; base += 64) {
-    part[lane] = base + lane < n_part ? l2_part[base + lane] : 0.0;
-    __syncthreads();
-    if (lane == 0) {
-      const int m = n_part - base < 64 ? n_part - base : 64;
-      for (int b = 0; b < m; ++b) l2 = __dadd_rn(l2, part[b]);
-    }
-    __syncthreads();
-  }
+  const double l2 = cw2_wave_sum(l2_part, n_part, part);   // ascending block order
   if (lane != 0) return;
-  const double al = out->adver_loss, c = cw->c;
-  const int gate = al > 0.0 ? 1 : 0;
-  const double L = __dadd_rn(__dmul_rn(gate ? c : 0.0, al), l2);
+  const double al = out->adver_loss;
   const int row = cw->rows;
   if (trace) {
     double *r = trace + (size_t)row * (3 + S);
-    r[0] = l2; r[1] = al; r[2] = c;
+    r[0] = l2; r[1] = al; r[2] = cw->c;
     for (int m = 0; m < S; ++m) r[3 + m] = scores[m];
   }
   int take = 0;
   if (al < 0.0 && l2 < cw->gbest_l2) { cw->gbest_l2 = l2; take = 1; }
-  if (al < 0.0) cw->found = 1;
-  int step = 1;
-  if (abort_every > 0 && t % abort_every == 0) {
-    if (L > __dmul_rn(0.9999, cw->prev)) { step = 0; cw->aborted = 1; ctl->stop = 1; }   // the row is written, no step is taken
-    else cw->prev = L;
-  }
-  cw->l2 = l2;
-  cw->gate = gate;
-  cw->take = take;
-  cw->mode = take | (step << 1);
-  cw->rows = row + 1;
-  ctl->iters_done = row + 1;
-  if (ctl->ticks) ctl->ticks[row + 1] = wall_clock64();
+  cw2_decide(cw, ctl, al, l2, l2, take, row, t, abort_every);
 }
 
-// step_size = lr / (1 - beta1^(t+1)) and bc2s = sqrt(1 - beta2^(t+1)) come from the host, the powers by repeated multiplication.
-// row: the int16 row the forward scored (the cast of x).
+// row: the int16 row the forward scored (the cast of x).  The Adam constants: cw2_adam_step.
 __global__ __launch_bounds__(256) void k_cw2_step(const double *__restrict__ g, const double *__restrict__ a0,
                                                   const double *__restrict__ w0, int64_t N, double beta1, double omb1, double beta2,
                                                   double omb2, double step_size, double bc2s, double adam_eps,
@@ -136,16 +88,7 @@ __global__ __launch_bounds__(256) void k_cw2_step(const double *__restrict__ g, 
     const double xn = x[n], an = a0[n];
     const double cg = cw->gate ? cw->c : 0.0;
     const double G = __dmul_rn(__dadd_rn(__dmul_rn(cg, g[n]), __dmul_rn(2.0, __dsub_rn(xn, an))), __dsub_rn(1.0, __dmul_rn(xn, xn)));
-    const double a = __dadd_rn(__dmul_rn(beta1, m1[n]), __dmul_rn(omb1, G));
-    const double b = __dadd_rn(__dmul_rn(beta2, m2[n]), __dmul_rn(__dmul_rn(omb2, G), G));
-    m1[n] = a;
-    m2[n] = b;
-    const double den = __dadd_rn(__ddiv_rn(__dsqrt_rn(b), bc2s), adam_eps);
-    const double md = __dsub_rn(mod[n], __ddiv_rn(__dmul_rn(step_size, a), den));
-    mod[n] = md;
-    const double xo = tanh(__dadd_rn(w0[n], md));
-    x[n] = xo;
-    d = cw2_sq_diff(xo, an);
+    d = cw2_adam_step(G, n, an, w0, beta1, omb1, beta2, omb2, step_size, bc2s, adam_eps, mod, m1, m2, x);
   }
   d = cw2_block_sum(d, lds);
   if (threadIdx.x == 0) l2_part[blockIdx.x] = d;

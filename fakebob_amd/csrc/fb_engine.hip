@@ -1734,6 +1734,13 @@ struct FbLoopKnobs {
   int upd_threads = 512;    // threads of a k_update_perturb(_x) workgroup (choose_update_threads)
   bool look_ahead = false;  // batch n + 1 is queued before the host waits for batch n's control block (FB_LOOK_AHEAD=0 | 1)
 };
+// FB_ATTACK_BATCH: iterations queued per host round trip (1 .. 16, default 4), read once at the start of an attack.  Beyond ~4
+// the host is off the critical path anyway, and every iteration queued behind the stopping one is (cheap, but not free) wasted work.
+static int attack_batch() {
+  const char *ev = getenv("FB_ATTACK_BATCH");
+  const int b = ev ? atoi(ev) : 4;
+  return b < 1 ? 1 : (b > 16 ? 16 : b);
+}
 static FbLoopKnobs loop_knobs(const fb_engine *e, const FbScorer &sc) {
   FbLoopKnobs k;
   k.upd_threads = choose_update_threads(e);
@@ -1741,11 +1748,7 @@ static FbLoopKnobs loop_knobs(const fb_engine *e, const FbScorer &sc) {
     k.look = sc.m->look_every > 0 ? sc.m->look_every : 4;
     k.fuse_upd = true;
   } else if (sc.kind == FB_SCORER_NATIVE) {
-    // Iterations queued per host round trip.  Beyond ~4 the host is off the critical path anyway, and
-    // every iteration queued behind the stopping one is (cheap, but not free) wasted work.
-    const char *ev = getenv("FB_ATTACK_BATCH");
-    const int b = ev ? atoi(ev) : 4;
-    k.look = b < 1 ? 1 : (b > 16 ? 16 : b);
+    k.look = attack_batch();
     k.fuse_fin = fb_fuse_part(e, 1) && nes_replicas(e) == 1;  // (fb_set_eot, fb_set_companions: the finalisation, then k_loss_eot)
     k.fuse_upd = fb_fuse_part(e, 2);
     const char *fu = getenv("FB_FUSE_UPD");
@@ -2679,8 +2682,38 @@ static int wb_enqueue(fb_engine *e, const fb_nes_params *q, int64_t N, uint32_t 
   return FB_OK;
 }
 
+// the start of every white-box entry point, before its arguments are looked at: the route counters of the call start at zero
+static void wb_call_begin(fb_engine *e) {
+  if (!e) return;
+  e->bench_it = -1;
+  memset(e->nes_route, 0, sizeof(e->nes_route));
+  memset(e->wb_route, 0, sizeof(e->wb_route));
+  e->wb_air_launches = 0;
+  e->wb_feco_launches = 0;
+  e->wb_universal_launches = 0;
+}
+
 static int wb_status_check(fb_engine *e, int status) {
   if (status != 0) return fb_fail(FB_E_HIP, "white-box gradients: the voiced mask recomputed by the backward is not the forward's");
+  return FB_OK;
+}
+// The host's look at an attack's control block behind a batch of queued iterations: the block to e->h_ctl, the backward's
+// status word and, where the attack keeps one, its own block (extra <- extra_dev), then the wait and what the three say.  The
+// caller reads e->h_ctl->stop.
+static int wb_look(fb_engine *e, void *extra, const void *extra_dev, size_t extra_bytes) {
+  int status = 0, rc = FB_OK;
+  const hipError_t he = hipMemcpyAsync(e->h_ctl, e->ctl.p, sizeof(FbCtlDev), hipMemcpyDeviceToHost, e->stream);
+  if (he == hipSuccess) rc = d2h(e, &status, e->wb_status.p, sizeof(int));
+  if (he == hipSuccess && rc == FB_OK && extra) rc = d2h(e, extra, extra_dev, extra_bytes);
+  if (he != hipSuccess || rc != FB_OK) {
+    (void)sync_stream(e);
+    HIPCHK(he);
+    return rc;
+  }
+  FBCHK(sync_stream(e));
+  if (e->gmm_pending) FBCHK(time_collect(e));
+  FBCHK(wb_status_check(e, status));
+  if (e->h_ctl->err != 0) return fb_fail(FB_E_NO_VOICED, "the adversarial audio has no voiced frames");
   return FB_OK;
 }
 
@@ -2688,12 +2721,7 @@ static int wb_status_check(fb_engine *e, int status) {
 // original (nullable: audio itself): the audio whose int16 cast is a_0 of the composition (fb_set_wb_universal)
 extern "C" int fb_get_grad_wb_from(fb_engine *e, const fb_nes_params *p, const double *audio, const double *original, int64_t N,
                                    int iter, double *adver_loss, double *grad, double *score0) {
-  if (e) e->bench_it = -1;
-  if (e) memset(e->nes_route, 0, sizeof(e->nes_route));
-  if (e) memset(e->wb_route, 0, sizeof(e->wb_route));
-  if (e) e->wb_air_launches = 0;
-  if (e) e->wb_feco_launches = 0;
-  if (e) e->wb_universal_launches = 0;
+  wb_call_begin(e);
   if (iter < 0) return fb_fail(FB_E_ARG, "iter must be >= 0");
   fb_nes_params q;
   FBCHK(wb_check(e, p, audio, N, &q));
@@ -2925,12 +2953,7 @@ extern "C" int fb_debug_iv_feat_grad(fb_engine *e, const float *feats, int Tv, c
 // device (k_wb_ctl), the host looks at the control block once per FB_ATTACK_BATCH iterations, as attack_loop does
 extern "C" int fb_attack_wb(fb_engine *e, const fb_nes_params *p, const double *audio, int64_t N, int16_t *adv_i16,
                             double *adver_f64, double *trace, int *n_trace, int *success_flag) {
-  if (e) e->bench_it = -1;
-  if (e) memset(e->nes_route, 0, sizeof(e->nes_route));
-  if (e) memset(e->wb_route, 0, sizeof(e->wb_route));
-  if (e) e->wb_air_launches = 0;
-  if (e) e->wb_feco_launches = 0;
-  if (e) e->wb_universal_launches = 0;
+  wb_call_begin(e);
   if (!adv_i16 || !success_flag) return fb_fail(FB_E_ARG, "null argument");
   fb_nes_params q;
   FBCHK(wb_check(e, p, audio, N, &q));
@@ -2950,32 +2973,20 @@ extern "C" int fb_attack_wb(fb_engine *e, const fb_nes_params *p, const double *
   FBCHK(e->ticks.ensure(sizeof(unsigned long long) * ((size_t)p->max_iter + 1)));
   FBCHK(ctl_reset(e, &q, true, false, e->ticks.as<unsigned long long>()));
   FbCtlDev *ctl = e->ctl.as<FbCtlDev>();
-  const char *ev = getenv("FB_ATTACK_BATCH");
-  const int b = ev ? atoi(ev) : 4;
-  const int look = b < 1 ? 1 : (b > 16 ? 16 : b);
+  const int look = attack_batch();
   const double one_minus_m = 1.0 - p->momentum;
   for (int queued = 0; queued < p->max_iter;) {
     const int nb = p->max_iter - queued < look ? p->max_iter - queued : look;
-    int rc = FB_OK, status = 0;
+    int rc = FB_OK;
     for (int k = 0; k < nb && rc == FB_OK; ++k) {
       rc = wb_enqueue(e, &q, N, (uint32_t)(queued + k), true, ctl, trace_dev);
       if (rc == FB_OK)
         fb_launch_wb_update(e->stream, e->grad.as<double>(), N, p->momentum, one_minus_m, p->epsilon, e->audio.as<double>(),
                             e->grad_m.as<double>(), e->adver.as<double>(), ctl);
     }
-    hipError_t he = hipSuccess;
-    if (rc == FB_OK) he = hipMemcpyAsync(e->h_ctl, ctl, sizeof(FbCtlDev), hipMemcpyDeviceToHost, e->stream);
-    if (rc == FB_OK && he == hipSuccess) rc = d2h(e, &status, e->wb_status.p, sizeof(int));
-    if (rc != FB_OK || he != hipSuccess) {
-      (void)hipStreamSynchronize(e->stream);
-      HIPCHK(he);
-      return rc;
-    }
+    if (rc != FB_OK) { (void)sync_stream(e); return rc; }   // (what was queued before the failure runs out first)
+    FBCHK(wb_look(e, nullptr, nullptr, 0));
     queued += nb;
-    FBCHK(sync_stream(e));
-    if (e->gmm_pending) FBCHK(time_collect(e));
-    FBCHK(wb_status_check(e, status));
-    if (e->h_ctl->err != 0) return fb_fail(FB_E_NO_VOICED, "the adversarial audio has no voiced frames");
     if (e->h_ctl->stop) break;
   }
   HIPCHK(hipGetLastError());
@@ -2997,7 +3008,7 @@ extern "C" int fb_attack_wb(fb_engine *e, const fb_nes_params *p, const double *
 // fb_attack_cw2 (the "CW2" section of fakebob_hip.h): Carlini-Wagner's L2 attack on wb_enqueue's gradient.  Per search step a
 // reset launch; per iteration wb_enqueue (its control launch forms the weights with the stop on adver_loss < 0 disabled and
 // writes no trace row) + k_cw2_ctl + k_cw2_step.  The host looks once per FB_ATTACK_BATCH iterations and between search steps,
-// where it also moves the constant.
+// where it also moves the constant.  The loop itself is tanh_attack's, below the masking attack's helpers.
 static int cw2_check(const fb_engine *e, const fb_nes_params *p, const fb_cw2_params *c) {
   // refused by name whatever the white-box switches say: none of them has a CW2 test of its own in this version
   if (e->comp_K1 > 0) return fb_fail(FB_E_STATE, "CW2: companions are set (fb_set_companions: clear them)");
@@ -3035,184 +3046,9 @@ static void cw2_next_const(bool found, double *lo, double *hi, double *c) {
   }
 }
 
-extern "C" int fb_attack_cw2(fb_engine *e, const fb_nes_params *p, const fb_cw2_params *c, const double *audio, int64_t N,
-                             int16_t *adv_i16, double *adver_f64, double *trace, int *n_trace, int *rows_per_step, int *success_flag,
-                             double *best_l2, double *final_const) {
-  if (e) e->bench_it = -1;
-  if (e) memset(e->nes_route, 0, sizeof(e->nes_route));
-  if (e) memset(e->wb_route, 0, sizeof(e->wb_route));
-  if (e) e->wb_air_launches = 0;
-  if (e) e->wb_feco_launches = 0;
-  if (e) e->wb_universal_launches = 0;
-  if (!e || !p || !c || !audio || !adv_i16 || !success_flag || !rows_per_step || !best_l2 || !final_const)
-    return fb_fail(FB_E_ARG, "null argument");
-  if (!e->have_gmm) return fb_fail(FB_E_STATE, "no model loaded");
-  FBCHK(cw2_check(e, p, c));
-  fb_nes_params q;
-  FBCHK(wb_check(e, p, audio, N, &q));
-  q.plateau_length = 0;   // (the loop control of wb_enqueue's control launch: no plateau rule, no stop of its own)
-  HIPCHK(hipSetDevice(e->device));
-  FBCHK(prepare_nes_replicas(e, N, 1));
-  FBCHK(ensure_nes_buffers(e, N, 1));
-  FBCHK(wb_prepare(e, N, e->h_frame_off[1], true));
-  FBCHK(cw2_buffers(e, N));
-  const int S = fb_num_speakers(e);
-  const int steps = c->search_steps, max_iter = p->max_iter;
-  const size_t total = (size_t)steps * (size_t)max_iter;
-  {  // w0 = atanh(0.999999 a0) on the host: the device never evaluates atanh
-    std::vector<double> w0((size_t)N);
-    for (int64_t n = 0; n < N; ++n) w0[(size_t)n] = atanh(0.999999 * audio[n]);
-    FBCHK(h2d(e, e->cw2_w0.p, w0.data(), sizeof(double) * (size_t)N));
-    FBCHK(sync_stream(e));
-  }
-  FBCHK(attack_start(e, audio, N, 0, nullptr));
-  // the best slots before any success: the cast of the original audio and the audio itself
-  fb_launch_quantize(e->stream, e->audio.as<double>(), N, nes_bits(p), e->cw2_best_row.as<int16_t>());
-  HIPCHK(hipMemcpyAsync(e->cw2_best_x.p, e->audio.p, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, e->stream));
-  double *trace_dev = nullptr;
-  if (trace) {
-    FBCHK(e->trace_dev.ensure(sizeof(double) * total * (3 + S)));
-    trace_dev = e->trace_dev.as<double>();
-  }
-  FBCHK(e->ticks.ensure(sizeof(unsigned long long) * (total + 1)));
-  FBCHK(ctl_reset(e, &q, true, true, e->ticks.as<unsigned long long>()));
-  FbCtlDev *ctl = e->ctl.as<FbCtlDev>();
-  FbCw2Dev *cw = e->cw2_ctl.as<FbCw2Dev>();
-  FbCw2Dev h_cw;
-  memset(&h_cw, 0, sizeof(h_cw));
-  h_cw.gbest_l2 = INFINITY;
-  h_cw.prev = INFINITY;
-  FBCHK(h2d(e, cw, &h_cw, sizeof(h_cw)));
-  const char *ev = getenv("FB_ATTACK_BATCH");
-  const int b = ev ? atoi(ev) : 4;
-  const int look = b < 1 ? 1 : (b > 16 ? 16 : b);
-  double cc = c->initial_const, lo = 0.0, hi = 1e10;
-  int rows = 0;
-  for (int s = 0; s < steps; ++s) {
-    fb_launch_cw2_reset(e->stream, e->cw2_w0.as<double>(), e->audio.as<double>(), N, cc, e->cw2_mod.as<double>(), e->grad_m.as<double>(),
-                        e->cw2_m2.as<double>(), e->adver.as<double>(), e->cw2_l2part.as<double>(), cw, ctl);
-    double p1 = 1.0, p2 = 1.0;
-    for (int queued = 0; queued < max_iter;) {
-      const int nb = max_iter - queued < look ? max_iter - queued : look;
-      int rc = FB_OK, status = 0;
-      for (int k = 0; k < nb && rc == FB_OK; ++k) {
-        const int t = queued + k;
-        rc = wb_enqueue(e, &q, N, (uint32_t)((size_t)s * (size_t)max_iter + (size_t)t), false, ctl, nullptr);
-        if (rc != FB_OK) break;
-        p1 *= c->beta1;
-        p2 *= c->beta2;
-        fb_launch_cw2_ctl(e->stream, e->nes_out.as<FbNesDev>(), e->scores.as<double>(), S, e->cw2_l2part.as<double>(), N, cw, ctl,
-                          trace_dev, t, c->abort_every);
-        fb_launch_cw2_step(e->stream, e->grad.as<double>(), e->audio.as<double>(), e->cw2_w0.as<double>(), N, c->beta1, c->beta2,
-                           c->lr / (1.0 - p1), sqrt(1.0 - p2), c->adam_eps, e->cw2_mod.as<double>(), e->grad_m.as<double>(),
-                           e->cw2_m2.as<double>(), e->adver.as<double>(), e->wav.as<int16_t>(), e->cw2_best_row.as<int16_t>(),
-                           e->cw2_best_x.as<double>(), e->cw2_l2part.as<double>(), cw);
-      }
-      hipError_t he = hipSuccess;
-      if (rc == FB_OK) he = hipMemcpyAsync(e->h_ctl, ctl, sizeof(FbCtlDev), hipMemcpyDeviceToHost, e->stream);
-      if (rc == FB_OK && he == hipSuccess) rc = d2h(e, &status, e->wb_status.p, sizeof(int));
-      if (rc == FB_OK && he == hipSuccess) rc = d2h(e, &h_cw, cw, sizeof(h_cw));
-      if (rc != FB_OK || he != hipSuccess) {
-        (void)sync_stream(e);
-        HIPCHK(he);
-        return rc;
-      }
-      queued += nb;
-      FBCHK(sync_stream(e));
-      if (e->gmm_pending) FBCHK(time_collect(e));
-      FBCHK(wb_status_check(e, status));
-      if (e->h_ctl->err != 0) return fb_fail(FB_E_NO_VOICED, "the adversarial audio has no voiced frames");
-      if (e->h_ctl->stop) break;   // the abort rule
-    }
-    rows_per_step[s] = h_cw.rows - rows;
-    rows = h_cw.rows;
-    cw2_next_const(h_cw.found != 0, &lo, &hi, &cc);
-  }
-  HIPCHK(hipGetLastError());
-  e->nes_iters += rows;
-  FBCHK(collect_iter_seconds(e, rows));
-  if (trace && rows > 0) FBCHK(d2h(e, trace, trace_dev, sizeof(double) * (size_t)rows * (3 + S)));
-  *success_flag = h_cw.gbest_l2 < INFINITY ? 1 : -1;
-  *best_l2 = h_cw.gbest_l2;
-  *final_const = cc;
-  if (n_trace) *n_trace = rows;
-  FBCHK(d2h(e, adv_i16, e->cw2_best_row.p, sizeof(int16_t) * (size_t)N));
-  if (adver_f64) FBCHK(d2h(e, adver_f64, e->cw2_best_x.p, sizeof(double) * (size_t)N));
-  FBCHK(sync_stream(e));
-  return FB_OK;
-}
-
-// Test hook: one k_cw2_ctl + k_cw2_step pair on arrays handed in (fakebob_hip_test.h); no system has to be loaded
-extern "C" int fb_debug_cw2_step(fb_engine *e, const fb_cw2_params *c, int64_t N, const double *g, const double *x, const double *a0,
-                                 const double *w0, const double *mod, const double *m1, const double *m2, double adver_loss,
-                                 double cc, double gbest_l2, int t, double p1, double p2, double *mod_out, double *m1_out,
-                                 double *m2_out, double *x_next, double *l2_now, double *l2_next, int *gate, int *take,
-                                 int16_t *best_row, double *best_x) {
-  if (!e || !c || !g || !x || !a0 || !w0 || !mod || !m1 || !m2 || !mod_out || !m1_out || !m2_out || !x_next || !l2_now || !l2_next ||
-      !gate || !take || !best_row || !best_x || N <= 0 || t < 0)
-    return fb_fail(FB_E_ARG, "bad argument");
-  if (!(p1 >= 0.0 && p1 < 1.0) || !(p2 >= 0.0 && p2 < 1.0)) return fb_fail(FB_E_ARG, "p1 and p2 must lie in [0, 1)");
-  HIPCHK(hipSetDevice(e->device));
-  FBCHK(sync_stream(e));
-  e->cached_B = -1;
-  FBCHK(ensure_nes_buffers(e, N, 1, 1));
-  FBCHK(e->wav.ensure(sizeof(int16_t) * (size_t)N));
-  FBCHK(cw2_buffers(e, N));
-  const size_t nb = sizeof(double) * (size_t)N;
-  FBCHK(h2d(e, e->grad.p, g, nb));
-  FBCHK(h2d(e, e->adver.p, x, nb));
-  FBCHK(h2d(e, e->audio.p, a0, nb));
-  FBCHK(h2d(e, e->cw2_w0.p, w0, nb));
-  FBCHK(h2d(e, e->cw2_mod.p, mod, nb));
-  FBCHK(h2d(e, e->grad_m.p, m1, nb));
-  FBCHK(h2d(e, e->cw2_m2.p, m2, nb));
-  fb_nes_params q;
-  memset(&q, 0, sizeof(q));
-  FBCHK(ctl_reset(e, &q, false, true, nullptr));
-  FbNesDev h_out;
-  memset(&h_out, 0, sizeof(h_out));
-  h_out.adver_loss = adver_loss;
-  FBCHK(h2d(e, e->nes_out.p, &h_out, sizeof(h_out)));
-  FbCw2Dev h_cw;
-  memset(&h_cw, 0, sizeof(h_cw));
-  h_cw.c = cc; h_cw.gbest_l2 = gbest_l2; h_cw.prev = INFINITY;
-  FbCw2Dev *cw = e->cw2_ctl.as<FbCw2Dev>();
-  FBCHK(h2d(e, cw, &h_cw, sizeof(h_cw)));
-  // the row the forward would have scored, and the best slots as an attack without a success holds them
-  fb_launch_quantize(e->stream, e->adver.as<double>(), N, 16, e->wav.as<int16_t>());
-  fb_launch_quantize(e->stream, e->audio.as<double>(), N, 16, e->cw2_best_row.as<int16_t>());
-  HIPCHK(hipMemcpyAsync(e->cw2_best_x.p, e->audio.p, nb, hipMemcpyDeviceToDevice, e->stream));
-  fb_launch_cw2_l2(e->stream, e->adver.as<double>(), e->audio.as<double>(), N, e->cw2_l2part.as<double>());
-  fb_launch_cw2_ctl(e->stream, e->nes_out.as<FbNesDev>(), e->scores.as<double>(), 0, e->cw2_l2part.as<double>(), N, cw, e->ctl.as<FbCtlDev>(),
-                    nullptr, t, c->abort_every);
-  FBCHK(d2h(e, &h_cw, cw, sizeof(h_cw)));   // (queued before the step launch: l2 of x, gate and take as k_cw2_ctl left them)
-  fb_launch_cw2_step(e->stream, e->grad.as<double>(), e->audio.as<double>(), e->cw2_w0.as<double>(), N, c->beta1, c->beta2,
-                     c->lr / (1.0 - p1), sqrt(1.0 - p2), c->adam_eps, e->cw2_mod.as<double>(), e->grad_m.as<double>(),
-                     e->cw2_m2.as<double>(), e->adver.as<double>(), e->wav.as<int16_t>(), e->cw2_best_row.as<int16_t>(),
-                     e->cw2_best_x.as<double>(), e->cw2_l2part.as<double>(), cw);
-  const size_t np = (size_t)((N + 255) / 256);
-  std::vector<double> part(np);
-  FBCHK(d2h(e, part.data(), e->cw2_l2part.p, sizeof(double) * np));
-  FBCHK(d2h(e, mod_out, e->cw2_mod.p, nb));
-  FBCHK(d2h(e, m1_out, e->grad_m.p, nb));
-  FBCHK(d2h(e, m2_out, e->cw2_m2.p, nb));
-  FBCHK(d2h(e, x_next, e->adver.p, nb));
-  FBCHK(d2h(e, best_row, e->cw2_best_row.p, sizeof(int16_t) * (size_t)N));
-  FBCHK(d2h(e, best_x, e->cw2_best_x.p, nb));
-  FBCHK(sync_stream(e));
-  HIPCHK(hipGetLastError());
-  double l2 = 0.0;
-  for (size_t i = 0; i < np; ++i) l2 += part[i];   // ascending block order, as k_cw2_ctl adds them
-  *l2_next = l2;
-  *l2_now = h_cw.l2;
-  *gate = h_cw.gate;
-  *take = h_cw.take;
-  return FB_OK;
-}
-
 // ------------------------------------------------- the psychoacoustic white-box attack
-// fb_attack_psy (the "masking" section of fakebob_hip.h): fb_attack_cw2's loop with the distortion D(delta) + l2_weight * l2.
-// Per iteration wb_enqueue + k_psy_frames + k_psy_ctl + k_psy_step; the reset launch of a search step is CW2's.
+// fb_attack_psy (the "masking" section of fakebob_hip.h): fb_attack_cw2's loop (tanh_attack) with the distortion D(delta) +
+// l2_weight * l2.  Per iteration wb_enqueue + k_psy_frames + k_psy_ctl + k_psy_step; the reset launch of a search step is CW2's.
 static int psy_frames_of(int64_t N, int W) {
   const int hop = W / 4;
   return N == W ? 1 : (int)((N - W + hop - 1) / hop) + 1;
@@ -3279,37 +3115,31 @@ static void psy_scales(const fb_psy_params *m, double *scale, double *coef) {
   *coef = 2.0 * *scale / ((double)m->n_frames * (double)(m->window / 2 + 1));
 }
 
-extern "C" int fb_attack_psy(fb_engine *e, const fb_nes_params *p, const fb_cw2_params *c, const fb_psy_params *m,
-                             const double *audio, int64_t N, int16_t *adv_i16, double *adver_f64, double *trace, int *n_trace,
-                             int *rows_per_step, int *success_flag, double *best_dist, double *best_l2, int *best_n_over,
-                             double *final_const) {
-  if (e) e->bench_it = -1;
-  if (e) memset(e->nes_route, 0, sizeof(e->nes_route));
-  if (e) memset(e->wb_route, 0, sizeof(e->wb_route));
-  if (e) e->wb_air_launches = 0;
-  if (e) e->wb_feco_launches = 0;
-  if (e) e->wb_universal_launches = 0;
-  if (!e || !p || !c || !m || !audio || !adv_i16 || !success_flag || !rows_per_step || !best_dist || !best_l2 || !best_n_over ||
-      !final_const)
-    return fb_fail(FB_E_ARG, "null argument");
+// The tanh-space attack both entry points run: m == nullptr is CW2, else the masking attack with *m.  The caller has looked at
+// its own arguments; h: the control block as the last look left it (CW2: its `cw` member alone), final_const: the constant
+// after the last search step.
+static_assert(offsetof(FbPsyDev, cw) == 0, "a CW2 control block is the head of a masking one");
+static int tanh_attack(fb_engine *e, const fb_nes_params *p, const fb_cw2_params *c, const fb_psy_params *m, const double *audio,
+                       int64_t N, int16_t *adv_i16, double *adver_f64, double *trace, int *n_trace, int *rows_per_step, FbPsyDev *h,
+                       double *final_const) {
   if (!e->have_gmm) return fb_fail(FB_E_STATE, "no model loaded");
-  FBCHK(cw2_check(e, p, c));   // (CW2's own checks and messages)
+  FBCHK(cw2_check(e, p, c));   // (CW2's own checks and messages for both)
   fb_nes_params q;
   FBCHK(wb_check(e, p, audio, N, &q));
-  FBCHK(psy_check(m, N));
+  if (m) FBCHK(psy_check(m, N));
   q.plateau_length = 0;   // (the loop control of wb_enqueue's control launch: no plateau rule, no stop of its own)
   HIPCHK(hipSetDevice(e->device));
   FBCHK(prepare_nes_replicas(e, N, 1));
   FBCHK(ensure_nes_buffers(e, N, 1));
   FBCHK(wb_prepare(e, N, e->h_frame_off[1], true));
   FBCHK(cw2_buffers(e, N));
-  FBCHK(psy_upload(e, m, N, false));
+  if (m) FBCHK(psy_upload(e, m, N, false));
   const int S = fb_num_speakers(e);
-  const int W = m->window, F = m->n_frames, K = W / 2 + 1;
-  double scale, coef;
-  psy_scales(m, &scale, &coef);
+  const int W = m ? m->window : 0, F = m ? m->n_frames : 0, K = W / 2 + 1;
+  double scale = 0.0, coef = 0.0;
+  if (m) psy_scales(m, &scale, &coef);
   const int steps = c->search_steps, max_iter = p->max_iter;
-  const size_t total = (size_t)steps * (size_t)max_iter;
+  const size_t total = (size_t)steps * (size_t)max_iter, width = (size_t)((m ? 5 : 3) + S);
   {  // w0 = atanh(0.999999 a0) on the host: the device never evaluates atanh
     std::vector<double> w0((size_t)N);
     for (int64_t n = 0; n < N; ++n) w0[(size_t)n] = atanh(0.999999 * audio[n]);
@@ -3322,81 +3152,104 @@ extern "C" int fb_attack_psy(fb_engine *e, const fb_nes_params *p, const fb_cw2_
   HIPCHK(hipMemcpyAsync(e->cw2_best_x.p, e->audio.p, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, e->stream));
   double *trace_dev = nullptr;
   if (trace) {
-    FBCHK(e->trace_dev.ensure(sizeof(double) * total * (5 + S)));
+    FBCHK(e->trace_dev.ensure(sizeof(double) * total * width));
     trace_dev = e->trace_dev.as<double>();
   }
   FBCHK(e->ticks.ensure(sizeof(unsigned long long) * (total + 1)));
   FBCHK(ctl_reset(e, &q, true, true, e->ticks.as<unsigned long long>()));
   FbCtlDev *ctl = e->ctl.as<FbCtlDev>();
-  FbPsyDev *ps = e->psy_ctl.as<FbPsyDev>();
-  FbPsyDev h_ps;
-  memset(&h_ps, 0, sizeof(h_ps));
-  h_ps.gbest_dist = INFINITY;
-  h_ps.cw.gbest_l2 = INFINITY;
-  h_ps.cw.prev = INFINITY;
-  FBCHK(h2d(e, ps, &h_ps, sizeof(h_ps)));
-  const char *ev = getenv("FB_ATTACK_BATCH");
-  const int b = ev ? atoi(ev) : 4;
-  const int look = b < 1 ? 1 : (b > 16 ? 16 : b);
+  FbPsyDev *ps = m ? e->psy_ctl.as<FbPsyDev>() : nullptr;
+  FbCw2Dev *cw = m ? &ps->cw : e->cw2_ctl.as<FbCw2Dev>();
+  const size_t block = m ? sizeof(FbPsyDev) : sizeof(FbCw2Dev);   // what is uploaded and fetched, at `cw` either way
+  memset(h, 0, sizeof(*h));
+  h->gbest_dist = INFINITY;
+  h->cw.gbest_l2 = INFINITY;
+  h->cw.prev = INFINITY;
+  FBCHK(h2d(e, cw, h, block));
+  const int look = attack_batch();
   double cc = c->initial_const, lo = 0.0, hi = 1e10;
   int rows = 0;
   for (int s = 0; s < steps; ++s) {
     fb_launch_cw2_reset(e->stream, e->cw2_w0.as<double>(), e->audio.as<double>(), N, cc, e->cw2_mod.as<double>(), e->grad_m.as<double>(),
-                        e->cw2_m2.as<double>(), e->adver.as<double>(), e->cw2_l2part.as<double>(), &ps->cw, ctl);
+                        e->cw2_m2.as<double>(), e->adver.as<double>(), e->cw2_l2part.as<double>(), cw, ctl);
     double p1 = 1.0, p2 = 1.0;
     for (int queued = 0; queued < max_iter;) {
       const int nb = max_iter - queued < look ? max_iter - queued : look;
-      int rc = FB_OK, status = 0;
+      int rc = FB_OK;
       for (int k = 0; k < nb && rc == FB_OK; ++k) {
         const int t = queued + k;
         rc = wb_enqueue(e, &q, N, (uint32_t)((size_t)s * (size_t)max_iter + (size_t)t), false, ctl, nullptr);
         if (rc != FB_OK) break;
         p1 *= c->beta1;
         p2 *= c->beta2;
-        fb_launch_psy_frames(e->stream, W, F, e->adver.as<double>(), e->audio.as<double>(), N, e->psy_tw.as<double>(),
-                             e->psy_theta.as<double>(), scale, coef, e->psy_gf.as<double>(), e->psy_dpart.as<double>(),
-                             e->psy_npart.as<int>(), nullptr, ctl);
-        fb_launch_psy_ctl(e->stream, e->nes_out.as<FbNesDev>(), e->scores.as<double>(), S, e->cw2_l2part.as<double>(), N,
-                          e->psy_dpart.as<double>(), e->psy_npart.as<int>(), F, K, m->l2_weight, ps, ctl, trace_dev, t, c->abort_every);
-        fb_launch_psy_step(e->stream, e->grad.as<double>(), e->psy_gf.as<double>(), F, W, e->audio.as<double>(), e->cw2_w0.as<double>(),
-                           N, m->l2_weight, c->beta1, c->beta2, c->lr / (1.0 - p1), sqrt(1.0 - p2), c->adam_eps,
-                           e->cw2_mod.as<double>(), e->grad_m.as<double>(), e->cw2_m2.as<double>(), e->adver.as<double>(),
-                           e->wav.as<int16_t>(), e->cw2_best_row.as<int16_t>(), e->cw2_best_x.as<double>(),
-                           e->cw2_l2part.as<double>(), ps);
+        const double step_size = c->lr / (1.0 - p1), bc2s = sqrt(1.0 - p2);
+        if (m) {
+          fb_launch_psy_frames(e->stream, W, F, e->adver.as<double>(), e->audio.as<double>(), N, e->psy_tw.as<double>(),
+                               e->psy_theta.as<double>(), scale, coef, e->psy_gf.as<double>(), e->psy_dpart.as<double>(),
+                               e->psy_npart.as<int>(), nullptr, ctl);
+          fb_launch_psy_ctl(e->stream, e->nes_out.as<FbNesDev>(), e->scores.as<double>(), S, e->cw2_l2part.as<double>(), N,
+                            e->psy_dpart.as<double>(), e->psy_npart.as<int>(), F, K, m->l2_weight, ps, ctl, trace_dev, t, c->abort_every);
+          fb_launch_psy_step(e->stream, e->grad.as<double>(), e->psy_gf.as<double>(), F, W, e->audio.as<double>(), e->cw2_w0.as<double>(),
+                             N, m->l2_weight, c->beta1, c->beta2, step_size, bc2s, c->adam_eps, e->cw2_mod.as<double>(),
+                             e->grad_m.as<double>(), e->cw2_m2.as<double>(), e->adver.as<double>(), e->wav.as<int16_t>(),
+                             e->cw2_best_row.as<int16_t>(), e->cw2_best_x.as<double>(), e->cw2_l2part.as<double>(), ps);
+        } else {
+          fb_launch_cw2_ctl(e->stream, e->nes_out.as<FbNesDev>(), e->scores.as<double>(), S, e->cw2_l2part.as<double>(), N, cw, ctl,
+                            trace_dev, t, c->abort_every);
+          fb_launch_cw2_step(e->stream, e->grad.as<double>(), e->audio.as<double>(), e->cw2_w0.as<double>(), N, c->beta1, c->beta2,
+                             step_size, bc2s, c->adam_eps, e->cw2_mod.as<double>(), e->grad_m.as<double>(), e->cw2_m2.as<double>(),
+                             e->adver.as<double>(), e->wav.as<int16_t>(), e->cw2_best_row.as<int16_t>(), e->cw2_best_x.as<double>(),
+                             e->cw2_l2part.as<double>(), cw);
+        }
       }
-      hipError_t he = hipSuccess;
-      if (rc == FB_OK) he = hipMemcpyAsync(e->h_ctl, ctl, sizeof(FbCtlDev), hipMemcpyDeviceToHost, e->stream);
-      if (rc == FB_OK && he == hipSuccess) rc = d2h(e, &status, e->wb_status.p, sizeof(int));
-      if (rc == FB_OK && he == hipSuccess) rc = d2h(e, &h_ps, ps, sizeof(h_ps));
-      if (rc != FB_OK || he != hipSuccess) {
-        (void)sync_stream(e);
-        HIPCHK(he);
-        return rc;
-      }
+      if (rc != FB_OK) { (void)sync_stream(e); return rc; }   // (what was queued before the failure runs out first)
+      FBCHK(wb_look(e, h, cw, block));
       queued += nb;
-      FBCHK(sync_stream(e));
-      if (e->gmm_pending) FBCHK(time_collect(e));
-      FBCHK(wb_status_check(e, status));
-      if (e->h_ctl->err != 0) return fb_fail(FB_E_NO_VOICED, "the adversarial audio has no voiced frames");
       if (e->h_ctl->stop) break;   // the abort rule
     }
-    rows_per_step[s] = h_ps.cw.rows - rows;
-    rows = h_ps.cw.rows;
-    cw2_next_const(h_ps.cw.found != 0, &lo, &hi, &cc);
+    rows_per_step[s] = h->cw.rows - rows;
+    rows = h->cw.rows;
+    cw2_next_const(h->cw.found != 0, &lo, &hi, &cc);
   }
   HIPCHK(hipGetLastError());
   e->nes_iters += rows;
   FBCHK(collect_iter_seconds(e, rows));
-  if (trace && rows > 0) FBCHK(d2h(e, trace, trace_dev, sizeof(double) * (size_t)rows * (5 + S)));
-  *success_flag = h_ps.gbest_dist < INFINITY ? 1 : -1;
-  *best_dist = h_ps.gbest_dist;
-  *best_l2 = h_ps.cw.gbest_l2;
-  *best_n_over = h_ps.gbest_dist < INFINITY ? h_ps.gbest_n_over : 0;
+  if (trace && rows > 0) FBCHK(d2h(e, trace, trace_dev, sizeof(double) * (size_t)rows * width));
   *final_const = cc;
   if (n_trace) *n_trace = rows;
   FBCHK(d2h(e, adv_i16, e->cw2_best_row.p, sizeof(int16_t) * (size_t)N));
   if (adver_f64) FBCHK(d2h(e, adver_f64, e->cw2_best_x.p, sizeof(double) * (size_t)N));
   FBCHK(sync_stream(e));
+  return FB_OK;
+}
+
+extern "C" int fb_attack_cw2(fb_engine *e, const fb_nes_params *p, const fb_cw2_params *c, const double *audio, int64_t N,
+                             int16_t *adv_i16, double *adver_f64, double *trace, int *n_trace, int *rows_per_step, int *success_flag,
+                             double *best_l2, double *final_const) {
+  wb_call_begin(e);
+  if (!e || !p || !c || !audio || !adv_i16 || !success_flag || !rows_per_step || !best_l2 || !final_const)
+    return fb_fail(FB_E_ARG, "null argument");
+  FbPsyDev h;
+  FBCHK(tanh_attack(e, p, c, nullptr, audio, N, adv_i16, adver_f64, trace, n_trace, rows_per_step, &h, final_const));
+  *success_flag = h.cw.gbest_l2 < INFINITY ? 1 : -1;
+  *best_l2 = h.cw.gbest_l2;
+  return FB_OK;
+}
+
+extern "C" int fb_attack_psy(fb_engine *e, const fb_nes_params *p, const fb_cw2_params *c, const fb_psy_params *m,
+                             const double *audio, int64_t N, int16_t *adv_i16, double *adver_f64, double *trace, int *n_trace,
+                             int *rows_per_step, int *success_flag, double *best_dist, double *best_l2, int *best_n_over,
+                             double *final_const) {
+  wb_call_begin(e);
+  if (!e || !p || !c || !m || !audio || !adv_i16 || !success_flag || !rows_per_step || !best_dist || !best_l2 || !best_n_over ||
+      !final_const)
+    return fb_fail(FB_E_ARG, "null argument");
+  FbPsyDev h;
+  FBCHK(tanh_attack(e, p, c, m, audio, N, adv_i16, adver_f64, trace, n_trace, rows_per_step, &h, final_const));
+  *success_flag = h.gbest_dist < INFINITY ? 1 : -1;
+  *best_dist = h.gbest_dist;
+  *best_l2 = h.cw.gbest_l2;
+  *best_n_over = h.gbest_dist < INFINITY ? h.gbest_n_over : 0;
   return FB_OK;
 }
 
@@ -3436,18 +3289,11 @@ extern "C" int fb_debug_psy_loss(fb_engine *e, const fb_psy_params *m, int64_t N
   return FB_OK;
 }
 
-// Test hook: one k_psy_ctl + k_psy_step pair on arrays handed in (fakebob_hip_test.h); no system has to be loaded
-extern "C" int fb_debug_psy_step(fb_engine *e, const fb_cw2_params *c, double l2_weight, int64_t N, const double *g, const double *gd,
-                                 const double *x, const double *a0, const double *w0, const double *mod, const double *m1,
-                                 const double *m2, double adver_loss, double cc, double D, int n_over, double gbest_dist, int t,
-                                 double p1, double p2, double *mod_out, double *m1_out, double *m2_out, double *x_next,
-                                 double *l2_now, double *dist_now, double *l2_next, int *gate, int *take, int16_t *best_row,
-                                 double *best_x) {
-  if (!e || !c || !g || !gd || !x || !a0 || !w0 || !mod || !m1 || !m2 || !mod_out || !m1_out || !m2_out || !x_next || !l2_now ||
-      !dist_now || !l2_next || !gate || !take || !best_row || !best_x || N <= 0 || t < 0)
-    return fb_fail(FB_E_ARG, "bad argument");
-  if (!(p1 >= 0.0 && p1 < 1.0) || !(p2 >= 0.0 && p2 < 1.0)) return fb_fail(FB_E_ARG, "p1 and p2 must lie in [0, 1)");
-  if (!isfinite(l2_weight) || l2_weight < 0.0) return fb_fail(FB_E_ARG, "masking: l2_weight must be finite and >= 0");
+// What the two step hooks (fakebob_hip_test.h; no system has to be loaded) stage before their own control and step launches: the
+// seven arrays, a fresh control block, adver_loss as the loss launch would have left it, the row the forward would have scored,
+// the best slots as an attack without a success holds them, the l2 partials of x
+static int tanh_step_stage(fb_engine *e, int64_t N, const double *g, const double *x, const double *a0, const double *w0,
+                           const double *mod, const double *m1, const double *m2, double adver_loss) {
   HIPCHK(hipSetDevice(e->device));
   FBCHK(sync_stream(e));
   e->cached_B = -1;
@@ -3455,20 +3301,13 @@ extern "C" int fb_debug_psy_step(fb_engine *e, const fb_cw2_params *c, double l2
   FBCHK(e->wav.ensure(sizeof(int16_t) * (size_t)N));
   FBCHK(cw2_buffers(e, N));
   const size_t nb = sizeof(double) * (size_t)N;
-  FBCHK(e->psy_gf.ensure(nb));
-  FBCHK(e->psy_dpart.ensure(sizeof(double)));
-  FBCHK(e->psy_npart.ensure(sizeof(int)));
-  FBCHK(e->psy_ctl.ensure(sizeof(FbPsyDev)));
   FBCHK(h2d(e, e->grad.p, g, nb));
-  FBCHK(h2d(e, e->psy_gf.p, gd, nb));
   FBCHK(h2d(e, e->adver.p, x, nb));
   FBCHK(h2d(e, e->audio.p, a0, nb));
   FBCHK(h2d(e, e->cw2_w0.p, w0, nb));
   FBCHK(h2d(e, e->cw2_mod.p, mod, nb));
   FBCHK(h2d(e, e->grad_m.p, m1, nb));
   FBCHK(h2d(e, e->cw2_m2.p, m2, nb));
-  FBCHK(h2d(e, e->psy_dpart.p, &D, sizeof(double)));   // one "frame" of one bin: D = D / (1 * 1)
-  FBCHK(h2d(e, e->psy_npart.p, &n_over, sizeof(int)));
   fb_nes_params q;
   memset(&q, 0, sizeof(q));
   FBCHK(ctl_reset(e, &q, false, true, nullptr));
@@ -3476,26 +3315,16 @@ extern "C" int fb_debug_psy_step(fb_engine *e, const fb_cw2_params *c, double l2
   memset(&h_out, 0, sizeof(h_out));
   h_out.adver_loss = adver_loss;
   FBCHK(h2d(e, e->nes_out.p, &h_out, sizeof(h_out)));
-  FbPsyDev h_ps;
-  memset(&h_ps, 0, sizeof(h_ps));
-  h_ps.cw.c = cc; h_ps.gbest_dist = gbest_dist; h_ps.cw.gbest_l2 = INFINITY; h_ps.cw.prev = INFINITY;
-  FbPsyDev *ps = e->psy_ctl.as<FbPsyDev>();
-  FBCHK(h2d(e, ps, &h_ps, sizeof(h_ps)));
-  FBCHK(sync_stream(e));   // (D and n_over are arguments)
-  // the row the forward would have scored, and the best slots as an attack without a success holds them
   fb_launch_quantize(e->stream, e->adver.as<double>(), N, 16, e->wav.as<int16_t>());
   fb_launch_quantize(e->stream, e->audio.as<double>(), N, 16, e->cw2_best_row.as<int16_t>());
   HIPCHK(hipMemcpyAsync(e->cw2_best_x.p, e->audio.p, nb, hipMemcpyDeviceToDevice, e->stream));
   fb_launch_cw2_l2(e->stream, e->adver.as<double>(), e->audio.as<double>(), N, e->cw2_l2part.as<double>());
-  fb_launch_psy_ctl(e->stream, e->nes_out.as<FbNesDev>(), e->scores.as<double>(), 0, e->cw2_l2part.as<double>(), N,
-                    e->psy_dpart.as<double>(), e->psy_npart.as<int>(), 1, 1, l2_weight, ps, e->ctl.as<FbCtlDev>(), nullptr, t,
-                    c->abort_every);
-  FBCHK(d2h(e, &h_ps, ps, sizeof(h_ps)));   // (queued before the step launch: l2, dist, gate and take as k_psy_ctl left them)
-  fb_launch_psy_step(e->stream, e->grad.as<double>(), e->psy_gf.as<double>(), 0, 0, e->audio.as<double>(), e->cw2_w0.as<double>(), N,
-                     l2_weight, c->beta1, c->beta2, c->lr / (1.0 - p1), sqrt(1.0 - p2), c->adam_eps, e->cw2_mod.as<double>(),
-                     e->grad_m.as<double>(), e->cw2_m2.as<double>(), e->adver.as<double>(), e->wav.as<int16_t>(),
-                     e->cw2_best_row.as<int16_t>(), e->cw2_best_x.as<double>(), e->cw2_l2part.as<double>(), ps);
-  const size_t np = (size_t)((N + 255) / 256);
+  return FB_OK;
+}
+// ... and what they fetch behind the step launch: mod, m1, m2, x_next, the best slots, and l2 of x_next from its partials
+static int tanh_step_fetch(fb_engine *e, int64_t N, double *mod_out, double *m1_out, double *m2_out, double *x_next, double *l2_next,
+                           int16_t *best_row, double *best_x) {
+  const size_t nb = sizeof(double) * (size_t)N, np = (size_t)((N + 255) / 256);
   std::vector<double> part(np);
   FBCHK(d2h(e, part.data(), e->cw2_l2part.p, sizeof(double) * np));
   FBCHK(d2h(e, mod_out, e->cw2_mod.p, nb));
@@ -3507,8 +3336,76 @@ extern "C" int fb_debug_psy_step(fb_engine *e, const fb_cw2_params *c, double l2
   FBCHK(sync_stream(e));
   HIPCHK(hipGetLastError());
   double l2 = 0.0;
-  for (size_t i = 0; i < np; ++i) l2 += part[i];   // ascending block order, as k_psy_ctl adds them
+  for (size_t i = 0; i < np; ++i) l2 += part[i];   // ascending block order, as the control kernels add them
   *l2_next = l2;
+  return FB_OK;
+}
+
+// Test hook: one k_cw2_ctl + k_cw2_step pair on arrays handed in
+extern "C" int fb_debug_cw2_step(fb_engine *e, const fb_cw2_params *c, int64_t N, const double *g, const double *x, const double *a0,
+                                 const double *w0, const double *mod, const double *m1, const double *m2, double adver_loss,
+                                 double cc, double gbest_l2, int t, double p1, double p2, double *mod_out, double *m1_out,
+                                 double *m2_out, double *x_next, double *l2_now, double *l2_next, int *gate, int *take,
+                                 int16_t *best_row, double *best_x) {
+  if (!e || !c || !g || !x || !a0 || !w0 || !mod || !m1 || !m2 || !mod_out || !m1_out || !m2_out || !x_next || !l2_now || !l2_next ||
+      !gate || !take || !best_row || !best_x || N <= 0 || t < 0)
+    return fb_fail(FB_E_ARG, "bad argument");
+  if (!(p1 >= 0.0 && p1 < 1.0) || !(p2 >= 0.0 && p2 < 1.0)) return fb_fail(FB_E_ARG, "p1 and p2 must lie in [0, 1)");
+  FBCHK(tanh_step_stage(e, N, g, x, a0, w0, mod, m1, m2, adver_loss));
+  FbCw2Dev h_cw;
+  memset(&h_cw, 0, sizeof(h_cw));
+  h_cw.c = cc; h_cw.gbest_l2 = gbest_l2; h_cw.prev = INFINITY;
+  FbCw2Dev *cw = e->cw2_ctl.as<FbCw2Dev>();
+  FBCHK(h2d(e, cw, &h_cw, sizeof(h_cw)));
+  fb_launch_cw2_ctl(e->stream, e->nes_out.as<FbNesDev>(), e->scores.as<double>(), 0, e->cw2_l2part.as<double>(), N, cw, e->ctl.as<FbCtlDev>(),
+                    nullptr, t, c->abort_every);
+  FBCHK(d2h(e, &h_cw, cw, sizeof(h_cw)));   // (queued before the step launch: l2 of x, gate and take as k_cw2_ctl left them)
+  fb_launch_cw2_step(e->stream, e->grad.as<double>(), e->audio.as<double>(), e->cw2_w0.as<double>(), N, c->beta1, c->beta2,
+                     c->lr / (1.0 - p1), sqrt(1.0 - p2), c->adam_eps, e->cw2_mod.as<double>(), e->grad_m.as<double>(),
+                     e->cw2_m2.as<double>(), e->adver.as<double>(), e->wav.as<int16_t>(), e->cw2_best_row.as<int16_t>(),
+                     e->cw2_best_x.as<double>(), e->cw2_l2part.as<double>(), cw);
+  FBCHK(tanh_step_fetch(e, N, mod_out, m1_out, m2_out, x_next, l2_next, best_row, best_x));
+  *l2_now = h_cw.l2;
+  *gate = h_cw.gate;
+  *take = h_cw.take;
+  return FB_OK;
+}
+
+// Test hook: one k_psy_ctl + k_psy_step pair on arrays handed in; D and n_over as one "frame" of one bin: D = D / (1 * 1)
+extern "C" int fb_debug_psy_step(fb_engine *e, const fb_cw2_params *c, double l2_weight, int64_t N, const double *g, const double *gd,
+                                 const double *x, const double *a0, const double *w0, const double *mod, const double *m1,
+                                 const double *m2, double adver_loss, double cc, double D, int n_over, double gbest_dist, int t,
+                                 double p1, double p2, double *mod_out, double *m1_out, double *m2_out, double *x_next,
+                                 double *l2_now, double *dist_now, double *l2_next, int *gate, int *take, int16_t *best_row,
+                                 double *best_x) {
+  if (!e || !c || !g || !gd || !x || !a0 || !w0 || !mod || !m1 || !m2 || !mod_out || !m1_out || !m2_out || !x_next || !l2_now ||
+      !dist_now || !l2_next || !gate || !take || !best_row || !best_x || N <= 0 || t < 0)
+    return fb_fail(FB_E_ARG, "bad argument");
+  if (!(p1 >= 0.0 && p1 < 1.0) || !(p2 >= 0.0 && p2 < 1.0)) return fb_fail(FB_E_ARG, "p1 and p2 must lie in [0, 1)");
+  if (!isfinite(l2_weight) || l2_weight < 0.0) return fb_fail(FB_E_ARG, "masking: l2_weight must be finite and >= 0");
+  FBCHK(tanh_step_stage(e, N, g, x, a0, w0, mod, m1, m2, adver_loss));
+  FBCHK(e->psy_gf.ensure(sizeof(double) * (size_t)N));
+  FBCHK(e->psy_dpart.ensure(sizeof(double)));
+  FBCHK(e->psy_npart.ensure(sizeof(int)));
+  FBCHK(e->psy_ctl.ensure(sizeof(FbPsyDev)));
+  FBCHK(h2d(e, e->psy_gf.p, gd, sizeof(double) * (size_t)N));
+  FBCHK(h2d(e, e->psy_dpart.p, &D, sizeof(double)));
+  FBCHK(h2d(e, e->psy_npart.p, &n_over, sizeof(int)));
+  FbPsyDev h_ps;
+  memset(&h_ps, 0, sizeof(h_ps));
+  h_ps.cw.c = cc; h_ps.gbest_dist = gbest_dist; h_ps.cw.gbest_l2 = INFINITY; h_ps.cw.prev = INFINITY;
+  FbPsyDev *ps = e->psy_ctl.as<FbPsyDev>();
+  FBCHK(h2d(e, ps, &h_ps, sizeof(h_ps)));
+  FBCHK(sync_stream(e));   // (D and n_over are arguments)
+  fb_launch_psy_ctl(e->stream, e->nes_out.as<FbNesDev>(), e->scores.as<double>(), 0, e->cw2_l2part.as<double>(), N,
+                    e->psy_dpart.as<double>(), e->psy_npart.as<int>(), 1, 1, l2_weight, ps, e->ctl.as<FbCtlDev>(), nullptr, t,
+                    c->abort_every);
+  FBCHK(d2h(e, &h_ps, ps, sizeof(h_ps)));   // (queued before the step launch: l2, dist, gate and take as k_psy_ctl left them)
+  fb_launch_psy_step(e->stream, e->grad.as<double>(), e->psy_gf.as<double>(), 0, 0, e->audio.as<double>(), e->cw2_w0.as<double>(), N,
+                     l2_weight, c->beta1, c->beta2, c->lr / (1.0 - p1), sqrt(1.0 - p2), c->adam_eps, e->cw2_mod.as<double>(),
+                     e->grad_m.as<double>(), e->cw2_m2.as<double>(), e->adver.as<double>(), e->wav.as<int16_t>(),
+                     e->cw2_best_row.as<int16_t>(), e->cw2_best_x.as<double>(), e->cw2_l2part.as<double>(), ps);
+  FBCHK(tanh_step_fetch(e, N, mod_out, m1_out, m2_out, x_next, l2_next, best_row, best_x));
   *l2_now = h_ps.cw.l2;
   *dist_now = h_ps.dist;
   *gate = h_ps.cw.gate;

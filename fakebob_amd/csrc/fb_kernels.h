@@ -384,7 +384,8 @@ void fb_launch_wb_iv_ctl_rep(hipStream_t s, const double *rep_scores, const doub
                              int task, int attack_type, const double *z_std, double threshold, int target, int true_label, double *w,
                              FbCtlDev *ctl, int do_ctl, double *trace, int it);
 
-// ---- the L2 white-box attack (fb_attack_cw2; cw2_kernels.hip) ---------------------------------------------------------
+// ---- the L2 white-box attack (fb_attack_cw2; cw2_kernels.hip; the device code it shares with the masking attack below:
+// ---- cw2_device.h; the host loop both run: tanh_attack, fb_engine.hip) -----------------------------------------------
 // Device-side control of a CW2 search step: what k_cw2_ctl (one thread) decides for the element-wise launch behind it
 struct FbCw2Dev {
   double c;          // the trade-off constant of the search step
@@ -402,7 +403,7 @@ struct FbCw2Dev {
 // abort flag and ctl->stop (unless ctl->err) start over
 void fb_launch_cw2_reset(hipStream_t s, const double *w0, const double *a0, int64_t N, double c, double *mod, double *m1, double *m2,
                          double *x, double *l2_part, FbCw2Dev *cw, FbCtlDev *ctl);
-// l2_part[b] = the sum of (x[n] - a0[n])^2 over block b of 256 consecutive samples, by the tree of cw2_block_sum
+// l2_part[b] = the sum of (x[n] - a0[n])^2 over block b of 256 consecutive samples, by the tree of cw2_block_sum (cw2_device.h)
 void fb_launch_cw2_l2(hipStream_t s, const double *x, const double *a0, int64_t N, double *l2_part);
 // gate / take / found / gbest_l2 / the abort rule / trace row cw->rows / the clock stamp, from the loss launch's block and the
 // partials of the iterate it scored; a launch behind the stopping one only sets cw->mode = 0
@@ -414,7 +415,7 @@ void fb_launch_cw2_step(hipStream_t s, const double *g, const double *a0, const 
                         double step_size, double bc2s, double adam_eps, double *mod, double *m1, double *m2, double *x,
                         const int16_t *row, int16_t *best_row, double *best_x, double *l2_part, const FbCw2Dev *cw);
 
-// ---- the psychoacoustic white-box attack (fb_attack_psy; psy_kernels.hip) ----------------------------------------------
+// ---- the psychoacoustic white-box attack (fb_attack_psy; psy_kernels.hip, on cw2_device.h's sums, decisions and Adam step) ----
 // Device-side control of a search step: k_cw2_reset starts `cw` over as for CW2; k_psy_ctl decides on dist instead of l2
 struct FbPsyDev {
   FbCw2Dev cw;         // as in CW2; gbest_l2 is l2 of the best iterate (the best is chosen on gbest_dist)

@@ -6,17 +6,15 @@
 //                 the threshold (uploaded in the same bit-reversed order, +inf above the Nyquist bin, so the one-sided mask is a
 //                 compare), the hinge and n_over partials of the frame, the masked spectrum through the decimation-in-time
 //                 inverse (bit-reversed in, natural out), the window again: gf[f][W], the frame's share of dD / d delta
-//   k_psy_ctl     one wave, thread 0 deciding: D and n_over from the frame partials and l2 from the block partials, each in
-//                 ascending order, then k_cw2_ctl's decisions on dist = D + l2_weight * l2
-//   k_psy_step    element-wise: gd by overlap-add of at most four frames in ascending f, then k_cw2_step's Adam step with
-//                 G = (((c gate) g + gd) + l2_weight (2 (x - a0))) (1 - x x)
+//   k_psy_ctl     one wave, thread 0 deciding: D and n_over from the frame partials and l2 from the block partials, the two
+//                 float64 sums in ascending order (cw2_wave_sum), its own trace row and `take` test, then k_cw2_ctl's
+//                 decisions on dist = D + l2_weight * l2 (cw2_decide)
+//   k_psy_step    element-wise: gd by overlap-add of at most four frames in ascending f, then k_cw2_step's Adam step
+//                 (cw2_adam_step, cw2_block_sum) with G = (((c gate) g + gd) + l2_weight (2 (x - a0))) (1 - x x)
 // All arithmetic is float64, nothing contracted; no floating-point atomics: every sum has one fixed order, so a run repeats bit
 // for bit.  The twiddles come from a host table (cos and sin of 2 pi t / W, t < W / 2, exact at the octants), copied to LDS
-// once per workgroup; the window is read off the same table.
-#include <math.h>
-
-#include "fb_device.h"
-#include "fb_kernels.h"
+// once per workgroup; the window is read off the same table.  What this attack shares with CW2 on the device is cw2_device.h's.
+#include "cw2_device.h"
 
 template <int W> struct PsyLog2;
 template <> struct PsyLog2<512> { static constexpr int v = 9; };
@@ -134,77 +132,33 @@ __global__ __launch_bounds__(64) void k_psy_ctl(const FbNesDev *__restrict__ out
                                                 FbPsyDev *__restrict__ ps, FbCtlDev *__restrict__ ctl, double *__restrict__ trace,
                                                 int t, int abort_every) {
   __shared__ double part[64];
-  __shared__ int ipart[64];
   const int lane = threadIdx.x;
   FbCw2Dev *cw = &ps->cw;
   if (ctl->stop) {   // behind the stopping iteration: k_psy_step has nothing to do
     if (lane == 0) cw->mode = 0;
     return;
   }
-  double l2 = 0.0, dsum = 0.0;
-  int n_over = 0;
-  for (int base = 0; base < n_l2; base += 64) {
-    part[lane] = base + lane < n_l2 ? l2_part[base + lane] : 0.0;
-    __syncthreads();
-    if (lane == 0) {
-      const int m = n_l2 - base < 64 ? n_l2 - base : 64;
-      for (int b = 0; b < m; ++b) l2 = __dadd_rn(l2, part[b]);
-    }
-    __syncthreads();
-  }
-  for (int base = 0; base < F; base += 64) {
-    part[lane] = base + lane < F ? d_part[base + lane] : 0.0;
-    ipart[lane] = base + lane < F ? n_part[base + lane] : 0;
-    __syncthreads();
-    if (lane == 0) {
-      const int m = F - base < 64 ? F - base : 64;
-      for (int b = 0; b < m; ++b) { dsum = __dadd_rn(dsum, part[b]); n_over += ipart[b]; }
-    }
-    __syncthreads();
-  }
+  const double l2 = cw2_wave_sum(l2_part, n_l2, part);   // ascending block order
+  const double dsum = cw2_wave_sum(d_part, F, part);     // ascending frames
+  int n_over = 0;                                        // (an integer sum: any order)
+  for (int f = lane; f < F; f += 64) n_over += n_part[f];
+  for (int h = 32; h >= 1; h >>= 1) n_over += __shfl_down(n_over, h, 64);
   if (lane != 0) return;
   const double D = __ddiv_rn(dsum, FK);
   const double dist = __dadd_rn(D, __dmul_rn(l2_weight, l2));
-  const double al = out->adver_loss, c = cw->c;
-  const int gate = al > 0.0 ? 1 : 0;
-  const double L = __dadd_rn(__dmul_rn(gate ? c : 0.0, al), dist);
+  const double al = out->adver_loss;
   const int row = cw->rows;
   if (trace) {
     double *r = trace + (size_t)row * (5 + S);
-    r[0] = dist; r[1] = l2; r[2] = (double)n_over; r[3] = al; r[4] = c;
+    r[0] = dist; r[1] = l2; r[2] = (double)n_over; r[3] = al; r[4] = cw->c;
     for (int m = 0; m < S; ++m) r[5 + m] = scores[m];
   }
   int take = 0;
   if (al < 0.0 && dist < ps->gbest_dist) { ps->gbest_dist = dist; cw->gbest_l2 = l2; ps->gbest_n_over = n_over; take = 1; }
-  if (al < 0.0) cw->found = 1;
-  int step = 1;
-  if (abort_every > 0 && t % abort_every == 0) {
-    if (L > __dmul_rn(0.9999, cw->prev)) { step = 0; cw->aborted = 1; ctl->stop = 1; }   // the row is written, no step is taken
-    else cw->prev = L;
-  }
-  cw->l2 = l2;
   ps->D = D;
   ps->dist = dist;
   ps->n_over = n_over;
-  cw->gate = gate;
-  cw->take = take;
-  cw->mode = take | (step << 1);
-  cw->rows = row + 1;
-  ctl->iters_done = row + 1;
-  if (ctl->ticks) ctl->ticks[row + 1] = wall_clock64();
-}
-
-// The sum of a block's 256 terms in the order of the CW2 contract (cw2_kernels.hip: cw2_block_sum); valid in thread 0.
-__device__ __forceinline__ double psy_block_sum(double d, double *__restrict__ lds) {
-  const int i = threadIdx.x;
-  lds[i] = d;
-  __syncthreads();
-  if (i < 128) lds[i] = __dadd_rn(lds[i], lds[i + 128]);
-  __syncthreads();
-  if (i >= 64) return 0.0;
-  d = __dadd_rn(lds[i], lds[i + 64]);
-  for (int h = 32; h >= 1; h >>= 1) d = __dadd_rn(d, __shfl_down(d, h, 64));
-  return d;
+  cw2_decide(cw, ctl, al, l2, dist, take, row, t, abort_every);
 }
 
 // gd[n] = sum_f gf[f][n - f hop] over the frames that hold sample n (hop = W / 4: at most four), added in ascending f
@@ -249,19 +203,9 @@ __global__ __launch_bounds__(256) void k_psy_step(const double *__restrict__ g, 
     const double cg = cw->gate ? cw->c : 0.0;
     const double G = __dmul_rn(__dadd_rn(__dadd_rn(__dmul_rn(cg, g[n]), gd), __dmul_rn(l2_weight, __dmul_rn(2.0, __dsub_rn(xn, an)))),
                                __dsub_rn(1.0, __dmul_rn(xn, xn)));
-    const double a = __dadd_rn(__dmul_rn(beta1, m1[n]), __dmul_rn(omb1, G));
-    const double b = __dadd_rn(__dmul_rn(beta2, m2[n]), __dmul_rn(__dmul_rn(omb2, G), G));
-    m1[n] = a;
-    m2[n] = b;
-    const double den = __dadd_rn(__ddiv_rn(__dsqrt_rn(b), bc2s), adam_eps);
-    const double md = __dsub_rn(mod[n], __ddiv_rn(__dmul_rn(step_size, a), den));
-    mod[n] = md;
-    const double xo = tanh(__dadd_rn(w0[n], md));
-    x[n] = xo;
-    const double e = __dsub_rn(xo, an);
-    d = __dmul_rn(e, e);
+    d = cw2_adam_step(G, n, an, w0, beta1, omb1, beta2, omb2, step_size, bc2s, adam_eps, mod, m1, m2, x);
   }
-  d = psy_block_sum(d, lds);
+  d = cw2_block_sum(d, lds);
   if (threadIdx.x == 0) l2_part[blockIdx.x] = d;
 }
 

@@ -120,13 +120,30 @@ class CW2(object):
         return cw2_params(initial_const=self.initial_const, search_steps=self.binary_search_steps, lr=self.lr,
                           abort_every=self.stop_early_iter if self.stop_early else 0)
 
+    # what a subclass with another distortion overrides (psy.Imperceptible): the trace columns of the checkpoint row's
+    # distortion, of adver_loss and of the first score; the result's own fields; the distortion's parameters; the engine
+    # call; the middle of the verbose line
+    _COLS = (0, 1, 3)
+    _FIELDS = ("best_l2",)
+
+    def _distortion_params(self, audio):
+        return None
+
+    def _engine_attack(self, eng, p, q, d, audio):
+        return eng.attack_cw2(p, q, audio)
+
+    def _describe(self, out):
+        return "l2:%g" % out.best_l2
+
     def attack(self, audio, checkpoint_path, threshold=0., true=None, target=None, fs=16000, bits_per_sample=16, n_jobs=10,
                debug=False):
-        """FakeBob.attack's signature and pair: (int16 adversarial audio (N, 1), success_flag +-1) -- the smallest successful
-        iterate, or the cast of `audio` with flag -1 --, a companions.AttackResult that also carries best_l2 (the squared L2
-        distance in float audio units), const (the constant after the last search step), snr_db (of the int16 perturbation)
-        and rows_per_step.  The checkpoint pickled to checkpoint_path (protocol -1) is one [l2, adver_loss, score, used_time]
-        row per iteration, the search steps one after the other."""
+        """FakeBob.attack's signature and pair: (int16 adversarial audio (N, 1), success_flag +-1) -- the successful iterate of
+        the smallest distortion, or the cast of `audio` with flag -1 --, a companions.AttackResult that also carries the
+        attack's own fields (_FIELDS), const (the constant after the last search step), snr_db (of the int16 perturbation) and
+        rows_per_step.  CW2: the distortion is l2, the squared L2 distance in float audio units, and the field is best_l2.
+        psy.Imperceptible: the distortion is dist = D + l2_weight * l2, and the fields are best_dist, best_l2 and n_over
+        (bins of the returned iterate above the masking threshold).  The checkpoint pickled to checkpoint_path (protocol -1)
+        is one [distortion, adver_loss, score, used_time] row per iteration, the search steps one after the other."""
         from . import companions as CP
         audio = _col(audio)
         bits = _check_bits(bits_per_sample)
@@ -134,16 +151,19 @@ class CW2(object):
         self.true = true
         self.target = target
         eng = self.model.engine
+        c_dist, c_loss, c_score = self._COLS
+        d = self._distortion_params(audio[:, 0])          # (outside the timed call)
         t0 = time.time()
-        res = eng.attack_cw2(self._params(bits), self._cw2_params(), audio[:, 0])
+        res = self._engine_attack(eng, self._params(bits), self._cw2_params(), d, audio[:, 0])
         dt = time.time() - t0
         trace = res["trace"]
         n = trace.shape[0]
         used_time = eng.attack_iter_seconds(n)
         cp_global = []
         for r in range(n):
-            sc = trace[r, 3:]
-            cp_global.append([trace[r, 0], np.array([trace[r, 1]]), sc[0] if self.task == "SV" else sc.copy(), float(used_time[r])])
+            sc = trace[r, c_score:]
+            cp_global.append([trace[r, c_dist], np.array([trace[r, c_loss]]), sc[0] if self.task == "SV" else sc.copy(),
+                              float(used_time[r])])
         if checkpoint_path:
             with open(checkpoint_path, "wb") as writer:
                 pickle.dump(cp_global, writer, protocol=-1)
@@ -151,11 +171,12 @@ class CW2(object):
         a0 = CP.cast_i16(audio[:, 0], bits)
         delta = adv.astype(np.int32) - a0.astype(np.int32)
         out = CP.AttackResult(adv[:, np.newaxis], res["success"], delta, bits, None)
-        out.best_l2 = res["best_l2"]
+        for k in self._FIELDS:
+            setattr(out, k, res[k])
         out.const = res["const"]
         out.snr_db = snr_db(a0, delta)
         out.rows_per_step = res["rows_per_step"]
         if self.verbose:
-            print("--- %d iters in %d search steps, success:%d, l2:%g, snr:%.2f dB, c:%g, %.1f iters/s ---" %
-                  (n, self.binary_search_steps, out[1], out.best_l2, out.snr_db, out.const, n / dt if dt > 0 else 0.0))
+            print("--- %d iters in %d search steps, success:%d, %s, snr:%.2f dB, c:%g, %.1f iters/s ---" %
+                  (n, self.binary_search_steps, out[1], self._describe(out), out.snr_db, out.const, n / dt if dt > 0 else 0.0))
         return out

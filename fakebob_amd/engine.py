@@ -744,6 +744,12 @@ class Engine(object):
         {l2, adver_loss, c, score0}, rows_per_step (search_steps,), best_l2, const).  params.max_iter counts the iterations of
         ONE search step.  Victims as attack_wb takes them, except companions, an air channel, feature compression and dither,
         which are refused whatever the switches say."""
+        return self._tanh_attack(self._L.fb_attack_cw2, params, cw2, [], audio, 3, [("best_l2", C.c_double)])
+
+    def _tanh_attack(self, fn, params, cw2, extra, audio, width, best):
+        """What attack_cw2 and attack_psy marshal: fn(handle, params, cw2, *extra, audio, N, adv, adver_f64, trace, n_trace,
+        rows_per_step, success, *best, const).  width: the trace columns in front of the scores; best: (key, ctypes type) of the
+        attack's own results, in the order of the call."""
         audio = np.ascontiguousarray(audio, np.float64).reshape(-1)
         n, S = audio.size, max(self.n_speakers, 1)
         steps = int(cw2.search_steps)
@@ -752,50 +758,49 @@ class Engine(object):
             total = 1
         adv = np.empty(n, np.int16)
         adv_f = np.empty(n, np.float64)
-        trace = np.zeros((max(total, 1), 3 + S), np.float64)
+        trace = np.zeros((max(total, 1), width + S), np.float64)
         per = np.zeros(32, np.int32)
-        nt, flag, l2, cc = C.c_int(), C.c_int(), C.c_double(), C.c_double()
-        N.check(self._L.fb_attack_cw2(self._h, C.byref(params), C.byref(cw2), N.ptr(audio), C.c_int64(n), N.ptr(adv), N.ptr(adv_f),
-                                      N.ptr(trace), C.byref(nt), N.ptr(per), C.byref(flag), C.byref(l2), C.byref(cc)))
-        return dict(adv=adv, success=flag.value, adver_f64=adv_f, trace=trace[:nt.value].copy(), rows_per_step=per[:steps].copy(),
-                    best_l2=l2.value, const=cc.value)
+        nt, flag, cc = C.c_int(), C.c_int(), C.c_double()
+        cells = [(key, ctype()) for key, ctype in best]
+        N.check(fn(self._h, C.byref(params), C.byref(cw2), *(extra + [N.ptr(audio), C.c_int64(n), N.ptr(adv), N.ptr(adv_f), N.ptr(trace),
+                                                                       C.byref(nt), N.ptr(per), C.byref(flag)] +
+                                                             [C.byref(c) for _key, c in cells] + [C.byref(cc)])))
+        out = dict(adv=adv, success=flag.value, adver_f64=adv_f, trace=trace[:nt.value].copy(), rows_per_step=per[:steps].copy())
+        out.update((key, c.value) for key, c in cells)
+        out["const"] = cc.value
+        return out
 
     def debug_cw2_step(self, cw2, g, x, a0, w0, mod, m1, m2, adver_loss, c, gbest_l2, t, p1, p2):
         """One k_cw2_ctl + k_cw2_step pair on arrays handed in (fb_debug_cw2_step) -> dict(mod, m1, m2, x_next, l2, l2_next,
         gate, take, best_row, best_x).  No system has to be loaded."""
-        arrs = [np.ascontiguousarray(a, np.float64).reshape(-1) for a in (g, x, a0, w0, mod, m1, m2)]
+        return self._tanh_step(self._L.fb_debug_cw2_step, "debug_cw2_step: the seven arrays", [C.byref(cw2)], (g, x, a0, w0, mod, m1, m2),
+                               [C.c_double(adver_loss), C.c_double(c), C.c_double(gbest_l2), C.c_int(int(t)), C.c_double(p1),
+                                C.c_double(p2)], ["l2"])
+
+    def _tanh_step(self, fn, what, head, arrays, scalars, now):
+        """What debug_cw2_step and debug_psy_step marshal: fn(handle, *head, N, *arrays, *scalars, mod, m1, m2, x_next, *now,
+        l2_next, gate, take, best_row, best_x).  now: the keys of the float64 results k_*_ctl left, in the order of the call."""
+        arrs = [np.ascontiguousarray(a, np.float64).reshape(-1) for a in arrays]
         n = arrs[0].size
         if any(a.size != n for a in arrs):
-            raise ValueError("debug_cw2_step: the seven arrays must have one length")
+            raise ValueError("%s must have one length" % what)
         out = [np.empty(n, np.float64) for _ in range(4)]
         best_row, best_x = np.empty(n, np.int16), np.empty(n, np.float64)
-        l2, l2n, gate, take = C.c_double(), C.c_double(), C.c_int(), C.c_int()
-        N.check(self._L.fb_debug_cw2_step(self._h, C.byref(cw2), C.c_int64(n), *([N.ptr(a) for a in arrs] + [
-            C.c_double(adver_loss), C.c_double(c), C.c_double(gbest_l2), C.c_int(int(t)), C.c_double(p1), C.c_double(p2)] +
-            [N.ptr(o) for o in out] + [C.byref(l2), C.byref(l2n), C.byref(gate), C.byref(take), N.ptr(best_row), N.ptr(best_x)])))
-        return dict(mod=out[0], m1=out[1], m2=out[2], x_next=out[3], l2=l2.value, l2_next=l2n.value, gate=gate.value,
-                    take=take.value, best_row=best_row, best_x=best_x)
+        cells = [C.c_double() for _ in now]
+        l2n, gate, take = C.c_double(), C.c_int(), C.c_int()
+        N.check(fn(self._h, *(head + [C.c_int64(n)] + [N.ptr(a) for a in arrs] + scalars + [N.ptr(o) for o in out] +
+                              [C.byref(c) for c in cells] + [C.byref(l2n), C.byref(gate), C.byref(take), N.ptr(best_row), N.ptr(best_x)])))
+        res = dict(mod=out[0], m1=out[1], m2=out[2], x_next=out[3])
+        res.update(zip(now, (c.value for c in cells)))
+        res.update(l2_next=l2n.value, gate=gate.value, take=take.value, best_row=best_row, best_x=best_x)
+        return res
 
     def attack_psy(self, params, cw2, psy, audio):
         """fb_attack_psy: attack_cw2's loop with the psychoacoustic masking distortion D(delta) + l2_weight * l2 (fakebob_hip.h,
         "masking") -> dict(adv (N,) int16, success +-1, adver_f64 (N,), trace (rows, 5 + S) of {dist, l2, n_over, adver_loss, c,
         score0}, rows_per_step (search_steps,), best_dist, best_l2, n_over, const).  psy: psy_params(theta, psd_max, ...)."""
-        audio = np.ascontiguousarray(audio, np.float64).reshape(-1)
-        n, S = audio.size, max(self.n_speakers, 1)
-        steps = int(cw2.search_steps)
-        total = max(steps, 0) * max(int(params.max_iter), 0)
-        if not 1 <= steps <= 32 or total > 2 ** 30:   # (the library says which; nothing of that size is allocated for it here)
-            total = 1
-        adv = np.empty(n, np.int16)
-        adv_f = np.empty(n, np.float64)
-        trace = np.zeros((max(total, 1), 5 + S), np.float64)
-        per = np.zeros(32, np.int32)
-        nt, flag, no, dist, l2, cc = C.c_int(), C.c_int(), C.c_int(), C.c_double(), C.c_double(), C.c_double()
-        N.check(self._L.fb_attack_psy(self._h, C.byref(params), C.byref(cw2), C.byref(psy), N.ptr(audio), C.c_int64(n), N.ptr(adv),
-                                      N.ptr(adv_f), N.ptr(trace), C.byref(nt), N.ptr(per), C.byref(flag), C.byref(dist), C.byref(l2),
-                                      C.byref(no), C.byref(cc)))
-        return dict(adv=adv, success=flag.value, adver_f64=adv_f, trace=trace[:nt.value].copy(), rows_per_step=per[:steps].copy(),
-                    best_dist=dist.value, best_l2=l2.value, n_over=no.value, const=cc.value)
+        return self._tanh_attack(self._L.fb_attack_psy, params, cw2, [C.byref(psy)], audio, 5,
+                                 [("best_dist", C.c_double), ("best_l2", C.c_double), ("n_over", C.c_int)])
 
     def debug_psy_loss(self, psy, delta, want_P=False):
         """The masking loss and its gradient at a perturbation handed in (fb_debug_psy_loss) -> dict(D, n_over, gd (N,), P [F, K]
@@ -812,19 +817,10 @@ class Engine(object):
     def debug_psy_step(self, cw2, l2_weight, g, gd, x, a0, w0, mod, m1, m2, adver_loss, c, D, n_over, gbest_dist, t, p1, p2):
         """One k_psy_ctl + k_psy_step pair on arrays handed in (fb_debug_psy_step) -> dict(mod, m1, m2, x_next, l2, dist, l2_next,
         gate, take, best_row, best_x).  No system has to be loaded."""
-        arrs = [np.ascontiguousarray(a, np.float64).reshape(-1) for a in (g, gd, x, a0, w0, mod, m1, m2)]
-        n = arrs[0].size
-        if any(a.size != n for a in arrs):
-            raise ValueError("debug_psy_step: the eight arrays must have one length")
-        out = [np.empty(n, np.float64) for _ in range(4)]
-        best_row, best_x = np.empty(n, np.int16), np.empty(n, np.float64)
-        l2, dist, l2n, gate, take = C.c_double(), C.c_double(), C.c_double(), C.c_int(), C.c_int()
-        N.check(self._L.fb_debug_psy_step(self._h, C.byref(cw2), C.c_double(l2_weight), C.c_int64(n), *([N.ptr(a) for a in arrs] + [
-            C.c_double(adver_loss), C.c_double(c), C.c_double(D), C.c_int(int(n_over)), C.c_double(gbest_dist), C.c_int(int(t)),
-            C.c_double(p1), C.c_double(p2)] + [N.ptr(o) for o in out] + [C.byref(l2), C.byref(dist), C.byref(l2n), C.byref(gate),
-                                                                         C.byref(take), N.ptr(best_row), N.ptr(best_x)])))
-        return dict(mod=out[0], m1=out[1], m2=out[2], x_next=out[3], l2=l2.value, dist=dist.value, l2_next=l2n.value,
-                    gate=gate.value, take=take.value, best_row=best_row, best_x=best_x)
+        return self._tanh_step(self._L.fb_debug_psy_step, "debug_psy_step: the eight arrays", [C.byref(cw2), C.c_double(l2_weight)],
+                               (g, gd, x, a0, w0, mod, m1, m2),
+                               [C.c_double(adver_loss), C.c_double(c), C.c_double(D), C.c_int(int(n_over)), C.c_double(gbest_dist),
+                                C.c_int(int(t)), C.c_double(p1), C.c_double(p2)], ["l2", "dist"])
 
     def debug_defence_vjp(self, wav, cot, seed=0, stream=0, iter=0):
         """The defences' transposes alone (fb_debug_defence_vjp): wav (n,) int16, cot (r, n) float64 on the rows the front

@@ -10,13 +10,9 @@ distortion (0: masking alone).  Qin's two-stage alpha schedule is not reproduced
 
 Victims and refusals are CW2's.
 """
-import pickle
-import time
-
 import numpy as np
 
-from .attack import _check_bits, _col
-from .cw2 import CW2, snr_db
+from .cw2 import CW2
 from .engine import psy_params
 from .masking import WINDOWS, masking_threshold
 
@@ -31,49 +27,16 @@ class Imperceptible(CW2):
         self.window = int(window)
         self.l2_weight = float(l2_weight)
 
-    def _psy_params(self, audio):
+    def _distortion_params(self, audio):
         theta, psd_max = masking_threshold(audio, float(self.model.engine.cfg.sample_freq), self.window)
         return psy_params(theta, psd_max, self.window, self.l2_weight)
 
-    def attack(self, audio, checkpoint_path, threshold=0., true=None, target=None, fs=16000, bits_per_sample=16, n_jobs=10,
-               debug=False):
-        """FakeBob.attack's signature and pair: (int16 adversarial audio (N, 1), success_flag +-1) -- the successful iterate of
-        the smallest distortion, or the cast of `audio` with flag -1 --, a companions.AttackResult that also carries best_dist
-        (D + l2_weight * l2), best_l2, n_over (bins of the returned iterate above the threshold), const, snr_db and
-        rows_per_step.  The checkpoint is CW2's layout, one [dist, adver_loss, score, used_time] row per iteration."""
-        from . import companions as CP
-        audio = _col(audio)
-        bits = _check_bits(bits_per_sample)
-        self.threshold = threshold
-        self.true = true
-        self.target = target
-        eng = self.model.engine
-        psy = self._psy_params(audio[:, 0])
-        t0 = time.time()
-        res = eng.attack_psy(self._params(bits), self._cw2_params(), psy, audio[:, 0])
-        dt = time.time() - t0
-        trace = res["trace"]
-        n = trace.shape[0]
-        used_time = eng.attack_iter_seconds(n)
-        cp_global = []
-        for r in range(n):
-            sc = trace[r, 5:]
-            cp_global.append([trace[r, 0], np.array([trace[r, 3]]), sc[0] if self.task == "SV" else sc.copy(), float(used_time[r])])
-        if checkpoint_path:
-            with open(checkpoint_path, "wb") as writer:
-                pickle.dump(cp_global, writer, protocol=-1)
-        adv = res["adv"]
-        a0 = CP.cast_i16(audio[:, 0], bits)
-        delta = adv.astype(np.int32) - a0.astype(np.int32)
-        out = CP.AttackResult(adv[:, np.newaxis], res["success"], delta, bits, None)
-        out.best_dist = res["best_dist"]
-        out.best_l2 = res["best_l2"]
-        out.n_over = res["n_over"]
-        out.const = res["const"]
-        out.snr_db = snr_db(a0, delta)
-        out.rows_per_step = res["rows_per_step"]
-        if self.verbose:
-            print("--- %d iters in %d search steps, success:%d, dist:%g, l2:%g, over:%d, snr:%.2f dB, c:%g, %.1f iters/s ---" %
-                  (n, self.binary_search_steps, out[1], out.best_dist, out.best_l2, out.n_over, out.snr_db, out.const,
-                   n / dt if dt > 0 else 0.0))
-        return out
+    # CW2.attack (its docstring speaks for both) on this attack's trace layout {dist, l2, n_over, adver_loss, c, score0[S]}
+    _COLS = (0, 3, 5)
+    _FIELDS = ("best_dist", "best_l2", "n_over")
+
+    def _engine_attack(self, eng, p, q, d, audio):
+        return eng.attack_psy(p, q, d, audio)
+
+    def _describe(self, out):
+        return "dist:%g, l2:%g, over:%d" % (out.best_dist, out.best_l2, out.n_over)

@@ -209,6 +209,25 @@ def test_a_whole_attack_is_its_replay(eng, small_system, monkeypatch, case, batc
                                                                                np.array_equal(_bits(got[k]), _bits(first[k]))), k
 
 
+# ------------------------------------------------------------------------------------- 3b. the abort rule
+@pytest.mark.parametrize("l2_weight", [0.0, 0.5])
+def test_abort_rule_ends_every_search_step_at_its_second_iteration(eng, small_system, l2_weight):
+    """CW2's test of this name with the masking distortion.  Adam's normalised step moves each mod[n] by about lr = 1e-12, so
+    L = c adver_loss + dist changes by far less than 0.01 % between t = 0 and t = 1, and prev is +inf at t = 0: every search
+    step writes two rows and takes one step.  The threshold is out of reach, so nothing is ever taken."""
+    _load(eng, small_system, "SV")
+    audio = R.test_audio(4000)
+    m = psy_params(*_theta(512, 4000), window=512, l2_weight=l2_weight)
+    p = nes_params("SV", "untargeted", max_iter=6, samples_per_draw=0, threshold=1e3)
+    got = eng.attack_psy(p, cw2_params(search_steps=3, lr=1e-12, abort_every=1), m, audio)
+    assert list(got["rows_per_step"]) == [2, 2, 2] and got["trace"].shape[0] == 6
+    assert list(got["trace"][:, 4]) == [1e-3, 1e-3, 1e-2, 1e-2, 1e-3 * 10.0 * 10.0, 1e-3 * 10.0 * 10.0]
+    assert got["success"] == -1 and got["best_dist"] == float("inf") and got["n_over"] == 0
+    assert np.array_equal(got["adv"], C2.cast_i16(audio)) and np.array_equal(_bits(got["adver_f64"]), _bits(audio))
+    never = eng.attack_psy(p, cw2_params(search_steps=3, lr=1e-12, abort_every=0), m, audio)
+    assert list(never["rows_per_step"]) == [6, 6, 6]
+
+
 # ------------------------------------------------------------------------------------- 4. it does what it is for
 def test_it_hides_under_the_threshold(eng, small_system):
     _load(eng, small_system, "SV")
