@@ -129,6 +129,17 @@ def with_companions(items, idx, count):
     return wavs[0], wavs[1:]
 
 
+def _int_pair(text):
+    """'A:B' -> (int A, int B): --hsj-evals"""
+    parts = text.split(":")
+    if len(parts) != 2:
+        raise argparse.ArgumentTypeError("expected A:B, got %r" % text)
+    try:
+        return int(parts[0]), int(parts[1])
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected two integers A:B, got %r" % text)
+
+
 def _pair(text):
     """'A:B' -> (float A, float B): --pso-w, --pso-c"""
     parts = text.split(":")
@@ -195,10 +206,12 @@ def main(argv=None, model_factory=None, bob_factory=None):
                     help="universal perturbation: the next N utterances of the same speaker in the data directory ride along "
                          "with every attacked one (1 .. 31, times --eot-size at most 32); all are cropped to the shortest, "
                          "which is printed; default: 0")
-    ap.add_argument("--attack", default="nes", choices=["nes", "pso", "kenansville", "pgd", "cw2", "psy"],
+    ap.add_argument("--attack", default="nes", choices=["nes", "pso", "kenansville", "hsj", "pgd", "cw2", "psy"],
                     help="the search: FAKEBOB's NES gradient estimate (default), SirenAttack's particle swarm "
                          "(fakebob_amd/pso.py; -epsilon, -max_iter, -adver and --seed apply, the other NES options do not), "
-                         "Kenansville's decision-only spectral removal (fakebob_amd/kenansville.py; --kv-* and --seed apply) or the "
+                         "Kenansville's decision-only spectral removal (fakebob_amd/kenansville.py; --kv-* and --seed apply), hsj: "
+                         "HopSkipJump, the decision-only attack that reaches a decision from a starting audio that already has it "
+                         "(fakebob_amd/hsj.py; --hsj-*, -max_iter and --seed apply; a targeted attack needs --hsj-init) or the "
                          "white-box gradient attack (fakebob_amd/pgd.py: the analytic gradient of a GMM-UBM system in FAKEBOB's "
                          "loop; -momentum 0 is PGD, -max_iter 1 the single step; -samples and -sigma do not apply; an undefended "
                          "victim unless --bpda is given); cw2: Carlini-Wagner's L2 attack on the same gradient "
@@ -239,6 +252,18 @@ def main(argv=None, model_factory=None, bob_factory=None):
     ap.add_argument("--kv-grid", dest="kv_grid", default=15, type=int, help="--attack kenansville: candidates per round (1 .. 64)")
     ap.add_argument("--kv-max-factor", dest="kv_max_factor", default=1.0, type=float,
                     help="--attack kenansville: the largest share of a window's spectral energy to remove, in (0, 1]")
+    ap.add_argument("--hsj-init", dest="hsj_init", default=None, metavar="WAV",
+                    help="--attack hsj: the starting audio, one the system already decides as wanted (the target speaker's own "
+                         "voice); cropped or tiled to each attacked utterance; an untargeted attack without it starts from noise")
+    ap.add_argument("--hsj-grid", dest="hsj_grid", default=15, type=int, help="--attack hsj: rows per search round and step batch (1 .. 64)")
+    ap.add_argument("--hsj-evals", dest="hsj_evals", default=(32, 256), type=_int_pair, metavar="B0:BMAX",
+                    help="--attack hsj: probes per iteration, min(BMAX, isqrt(B0^2 t)) at iteration t (1 <= B0 <= BMAX <= 1024)")
+    ap.add_argument("--hsj-max-queries", dest="hsj_max_queries", default=0, type=int,
+                    help="--attack hsj: no batch is scored that would take an attack's rows beyond this many (0: no cap)")
+    ap.add_argument("--hsj-sigma-min", dest="hsj_sigma_min", default=2.0 ** -15, type=float,
+                    help="--attack hsj: the floor of the probes' standard deviation (default: one int16 step)")
+    ap.add_argument("--hsj-probe-scale", dest="hsj_probe_scale", default=0.05, type=float,
+                    help="--attack hsj: the probes' standard deviation is this times |x - audio| / sqrt(N) above the floor")
     ap.add_argument("--particles", default=25, type=int, help="--attack pso: particles of the swarm (2 .. 64)")
     ap.add_argument("--pso-w", dest="pso_w", default=(0.9, 0.1), type=_pair, metavar="WI:WE",
                     help="--attack pso: inertia weight, falling linearly from WI to WE over max_iter iterations")
@@ -263,6 +288,13 @@ def main(argv=None, model_factory=None, bob_factory=None):
             ap.error("--attack kenansville does not run under expectation over transformation (--eot-size %d)" % args.eot_size)
         if args.companions > 0:
             ap.error("--attack kenansville does not take companion utterances (--companions %d)" % args.companions)
+    if args.attack == "hsj":      # likewise
+        if args.eot_size is not None and args.eot_size > 1:
+            ap.error("--attack hsj does not run under expectation over transformation (--eot-size %d)" % args.eot_size)
+        if args.companions > 0:
+            ap.error("--attack hsj does not take companion utterances (--companions %d)" % args.companions)
+        if args.hsj_init is None and (args.attack_type == "targeted" or args.task == "SV"):
+            ap.error("--attack hsj: a targeted attack needs --hsj-init, an audio the system already decides as the target")
 
     if args.bpda and args.attack not in ("pgd", "cw2", "psy"):
         ap.error("--bpda belongs to --attack pgd (--attack %s)" % args.attack)
@@ -362,6 +394,13 @@ def main(argv=None, model_factory=None, bob_factory=None):
                   w_init=args.pso_w[0], w_end=args.pso_w[1], c1=args.pso_c[0], c2=args.pso_c[1], v_max=args.pso_vmax)
     if args.attack == "kenansville":
         hp = dict(window=args.kv_window, grid=args.kv_grid, max_factor=args.kv_max_factor)
+    hsj_init = None
+    if args.attack == "hsj":
+        hp = dict(grid=args.hsj_grid, num_evals_init=args.hsj_evals[0], num_evals_max=args.hsj_evals[1],
+                  max_queries=args.hsj_max_queries, sigma_min=args.hsj_sigma_min, probe_scale=args.hsj_probe_scale,
+                  max_iter=args.max_iter)
+        if args.hsj_init is not None:
+            hsj_init = np.asarray(read(args.hsj_init)[1], np.float64).reshape(-1) / (2 ** (bits_per_sample - 1))
     if args.attack == "pgd":
         hp = dict(adver_thresh=args.adver_thresh, epsilon=args.epsilon, max_iter=args.max_iter, max_lr=args.max_lr,
                   min_lr=args.min_lr, momentum=args.momentum, plateau_length=args.plateau_length, plateau_drop=args.plateau_drop)
@@ -403,6 +442,9 @@ def main(argv=None, model_factory=None, bob_factory=None):
     elif bob_factory is None and args.attack == "kenansville":
         from .kenansville import Kenansville
         bobs = [Kenansville(task, attack_type, m, seed=seed, verbose=False, **hp) for m in models]
+    elif bob_factory is None and args.attack == "hsj":
+        from .hsj import HopSkipJump
+        bobs = [HopSkipJump(task, attack_type, m, seed=seed, verbose=False, **hp) for m in models]
     elif bob_factory is None and args.attack == "pso":
         from .pso import ParticleSwarm
         bobs = [ParticleSwarm(task, attack_type, m, seed=seed, verbose=False, **hp) for m in models]
@@ -462,8 +504,9 @@ def main(argv=None, model_factory=None, bob_factory=None):
                 with lock:
                     results[idx] = flag
                 continue
+            extra = dict(init=hsj_init) if args.attack == "hsj" else {}
             res = bob.attack(it["audio"], it["cp_path"], threshold=threshold, true=true,
-                             target=it["target"], fs=fs, bits_per_sample=bits_per_sample)
+                             target=it["target"], fs=fs, bits_per_sample=bits_per_sample, **extra)
             adv, flag = res
             if args.attack == "psy" and hasattr(res, "best_dist"):
                 print("psy %s: success %d, dist %.6g, over %d, l2 %.6g, snr %.2f dB, c %.3g" %

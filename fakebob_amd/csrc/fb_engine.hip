@@ -215,6 +215,9 @@ struct fb_engine {
   DevBuf kv_x, kv_best, kv_tab;         // fb_attack_kenansville: the int16 cast of the audio [N], the candidate of hi [N], the four tables [4][W]
   DevBuf kv_ma, kv_mb, kv_cum, kv_E;    // ... the analysis: m a, m b [nw][K] int32, cum [nw][K] and E [nw] int64
   DevBuf kv_look;                       // ... and what its host reads per round: {FbNesDev, loss[G], scores[G][S], tv[G]}
+  DevBuf hsj_init, hsj_y, hsj_x, hsj_v; // fb_attack_hsj: the starting audio, the step's end point, the boundary point, the direction [N] float64
+  DevBuf hsj_part, hsj_sc, hsj_w;       // ... ssq's chunk sums, the two sums {D2, S}, the probes' weights [B] int32
+  DevBuf hsj_best, hsj_look, hsj_z;     // ... the row of hi [N] int16, the host's look {FbNesDev, loss, scores, tv}, the probes' normals [B][N] float32
   // white-box gradients (fb_get_grad_wb / fb_attack_wb): fb_load_gmm's plain float32 parameters, kept on the host and uploaded
   // by the first white-box call after the load; the weights w[M], the GMM backward's per-model rows and the cotangent g on the
   // compacted rows, the front-end backward's float64 stages, a status word (1: the recomputed voiced mask is not the forward's)
@@ -3846,6 +3849,445 @@ extern "C" int fb_bench_kv_kernels(fb_engine *e, const int16_t *x, int64_t N, in
       if (which == 0) launch_kv_analyse(e, N, W);
       else launch_kv_candidates(e, N, W, rows, q, e->wav.as<int16_t>());
     }
+    HIPCHK(hipEventRecord(e->ev1, e->stream));
+    HIPCHK(hipEventSynchronize(e->ev1));
+    float t = 0.f;
+    HIPCHK(hipEventElapsedTime(&t, e->ev0, e->ev1));
+    ms[which] = (double)t / reps;
+  }
+  FBCHK(sync_stream(e));
+  HIPCHK(hipGetLastError());
+  return FB_OK;
+}
+
+// ------------------------------------------------- decision-only attack II: HopSkipJump
+// fb_attack_hsj (the "decision-only attack II" section of fakebob_hip.h).  Every batch -- a search round (k_hsj_line), an
+// iteration's probes (k_hsj_probes), its step sizes (k_hsj_step) -- goes as int16 rows into the NES batch, the ordinary path
+// scores it, k_loss forms scores[rows][S], and the host reads them with tv[rows] once, as fb_attack_kenansville does.
+static int check_hsj_params(const fb_hsj_params *k) {
+  if (k->grid < 1 || k->grid > FB_HSJ_MAX_GRID) return fb_fail(FB_E_ARG, "grid %d outside 1 .. %d", k->grid, FB_HSJ_MAX_GRID);
+  if (k->max_rounds < 1 || k->max_rounds > FB_HSJ_MAX_ROUNDS)
+    return fb_fail(FB_E_ARG, "max_rounds %d outside 1 .. %d", k->max_rounds, FB_HSJ_MAX_ROUNDS);
+  if (k->num_evals_init < 1 || k->num_evals_init > k->num_evals_max || k->num_evals_max > FB_HSJ_MAX_EVALS)
+    return fb_fail(FB_E_ARG, "num_evals %d : %d outside 1 <= init <= max <= %d", k->num_evals_init, k->num_evals_max, FB_HSJ_MAX_EVALS);
+  if (k->max_queries < 0) return fb_fail(FB_E_ARG, "max_queries %d < 0", k->max_queries);
+  if (!std::isfinite(k->sigma_min) || !(k->sigma_min > 0.0)) return fb_fail(FB_E_ARG, "sigma_min must be finite and > 0");
+  if (!std::isfinite(k->probe_scale) || !(k->probe_scale >= 0.0)) return fb_fail(FB_E_ARG, "probe_scale must be finite and >= 0");
+  return FB_OK;
+}
+// B_t = min(num_evals_max, isqrt(num_evals_init^2 t))
+static int hsj_evals(const fb_hsj_params *k, int t) {
+  const long long n = (long long)k->num_evals_init * k->num_evals_init * t;
+  long long r = (long long)std::sqrt((double)n);
+  while (r * r > n) --r;
+  while ((r + 1) * (r + 1) <= n) ++r;
+  return (int)std::min<long long>(r, k->num_evals_max);
+}
+extern "C" long long fb_hsj_max_rows(int max_iter, const fb_hsj_params *k) {
+  if (!k || max_iter < 0 || check_hsj_params(k) != FB_OK) return -1;
+  const long long G = k->grid, search = G * k->max_rounds;
+  long long total = search;
+  for (int t = 1; t <= max_iter; ++t) total += hsj_evals(k, t) + G + search;
+  if (k->max_queries > 0) total = std::min(total, std::max<long long>(k->max_queries, G));
+  return total;
+}
+// the buffers of N samples and of batches of up to max_rows rows
+static int prepare_hsj(fb_engine *e, int64_t N, int max_rows) {
+  const size_t n = (size_t)N;
+  FBCHK(e->audio.ensure(sizeof(double) * n));
+  FBCHK(e->hsj_init.ensure(sizeof(double) * n));
+  FBCHK(e->hsj_y.ensure(sizeof(double) * n));
+  FBCHK(e->hsj_x.ensure(sizeof(double) * n));
+  FBCHK(e->hsj_v.ensure(sizeof(double) * n));
+  FBCHK(e->hsj_part.ensure(sizeof(double) * (size_t)fb_hsj_chunks(N)));
+  FBCHK(e->hsj_sc.ensure(sizeof(double) * 2));
+  FBCHK(e->hsj_w.ensure(sizeof(int32_t) * FB_HSJ_MAX_EVALS));
+  FBCHK(e->hsj_best.ensure(sizeof(int16_t) * n));
+  (void)max_rows;
+  return FB_OK;
+}
+// the adopt launch and the sum of its partials: x = line(y, q), hsj_sc[0] = ssq(x - a)
+static void launch_hsj_adopt(fb_engine *e, const double *y, int64_t N, int q) {
+  fb_launch_hsj_adopt(e->stream, e->audio.as<double>(), y, N, q, e->hsj_x.as<double>(), e->hsj_part.as<double>());
+  fb_launch_hsj_sum(e->stream, e->hsj_part.as<double>(), fb_hsj_chunks(N), e->hsj_sc.as<double>());
+}
+// the direction launch and the sum of its partials: v = sum_j w_j z_j, hsj_sc[1] = ssq(v)
+static void launch_hsj_dir(fb_engine *e, int B, int64_t N, uint64_t seed, uint32_t stream, uint32_t t, const float *zkept) {
+  fb_launch_hsj_dir(e->stream, e->hsj_w.as<int32_t>(), B, N, seed, stream, t, zkept, e->hsj_v.as<double>(), e->hsj_part.as<double>());
+  fb_launch_hsj_sum(e->stream, e->hsj_part.as<double>(), fb_hsj_chunks(N), e->hsj_sc.as<double>() + 1);
+}
+
+extern "C" int fb_attack_hsj(fb_engine *e, const fb_nes_params *p, const fb_hsj_params *k, const double *audio, const double *init,
+                             int64_t N, int16_t *adv_i16, double *adv_f64, int *success, double *dist2, int *n_iters,
+                             int *n_queries, double *trace, int *decisions, long long decisions_cap, double *x_trace) {
+  if (e) e->bench_it = -1;
+  if (!e || !p || !k || !audio || !adv_i16 || !success || !dist2 || !n_iters || !n_queries || !trace || !decisions)
+    return fb_fail(FB_E_ARG, "null argument");
+  if (!init) return fb_fail(FB_E_ARG, "null init: HopSkipJump starts from an audio that is already decided as wanted");
+  if (!e->have_gmm) return fb_fail(FB_E_STATE, "no model loaded");
+  if (e->eot > 1)
+    return fb_fail(FB_E_STATE, "fb_attack_hsj does not run under expectation over transformation (fb_set_eot(%d)): set 1", e->eot);
+  if (e->comp_K1 > 0)
+    return fb_fail(FB_E_STATE, "fb_attack_hsj does not run with companion utterances (fb_set_companions: %d set): clear them", e->comp_K1);
+  FBCHK(check_hsj_params(k));
+  const int G = k->grid, bits = nes_bits(p);
+  if (p->max_iter < 0) return fb_fail(FB_E_ARG, "max_iter %d < 0", p->max_iter);
+  if (bits < 2 || bits > 16) return fb_fail(FB_E_ARG, "bits_per_sample %d unsupported (2 .. 16)", bits);
+  if (N <= 0) return fb_fail(FB_E_ARG, "empty audio");
+  if (p->task != e->task) return fb_fail(FB_E_ARG, "params.task %d != engine system task %d", p->task, e->task);
+  if (p->task != FB_TASK_SV && p->task != FB_TASK_OSI && p->task != FB_TASK_CSI) return fb_fail(FB_E_ARG, "bad task %d", p->task);
+  if (p->attack_type != FB_TARGETED && p->attack_type != FB_UNTARGETED) return fb_fail(FB_E_ARG, "bad attack_type %d", p->attack_type);
+  const int S = fb_num_speakers(e);
+  const bool targeted = p->attack_type == FB_TARGETED;
+  const int label = targeted ? p->target : p->true_label;   // a decision value
+  {
+    const bool ok = p->task == FB_TASK_SV ? (label == 1 || label == -1)
+                  : p->task == FB_TASK_OSI ? (label >= -1 && label < S) : (label >= 0 && label < S);
+    if (!ok) return fb_fail(FB_E_ARG, "%s %d is no decision of this system", targeted ? "target" : "true label", label);
+  }
+  if (num_frames(e->cfg, N) <= 0) return fb_fail(FB_E_ARG, "audio shorter than one frame");
+  const long long need = fb_hsj_max_rows(p->max_iter, k);
+  if (decisions_cap < need)
+    return fb_fail(FB_E_ARG, "the decision log holds %lld entries, this call may score %lld rows", decisions_cap, need);
+  HIPCHK(hipSetDevice(e->device));
+  const int max_rows = std::max(G, k->num_evals_max);
+  FBCHK(prepare_hsj(e, N, max_rows));
+  // the probes launch keeps its normals as float32 [B][N] for the direction launch: at B = 1024, N = 48 000 the pair takes
+  // 160 us so against 206 us with the direction launch drawing them again (tools/hsj_rate.py)
+  FBCHK(e->hsj_z.ensure(sizeof(float) * (size_t)N * (size_t)k->num_evals_max));
+  // what the host reads once per batch, in one block: k_loss's result block (not read), loss[R] (not read), scores[R][S], tv[R]
+  static_assert(sizeof(FbNesDev) % sizeof(double) == 0, "the result block is followed by doubles");
+  const size_t out_d = sizeof(FbNesDev) / sizeof(double), sc_d = out_d + (size_t)max_rows, tv_d = sc_d + (size_t)max_rows * S;
+  const size_t look_d = tv_d + ((size_t)max_rows + 1) / 2;
+  FBCHK(e->hsj_look.ensure(sizeof(double) * look_d));
+  FbNesDev *out_dev = e->hsj_look.as<FbNesDev>();
+  double *loss_dev = e->hsj_look.as<double>() + out_d, *scores_dev = e->hsj_look.as<double>() + sc_d;
+  int *tv_dev = reinterpret_cast<int *>(e->hsj_look.as<double>() + tv_d);
+  FBCHK(launch_state_reset(e));
+  e->iter_seconds.clear();
+
+  const double *a_dev = e->audio.as<double>();
+  FBCHK(h2d(e, e->audio.p, audio, sizeof(double) * (size_t)N));
+  FBCHK(h2d(e, e->hsj_init.p, init, sizeof(double) * (size_t)N));
+  std::vector<double> look(look_d);
+  std::vector<int> dec(max_rows), cand;
+  cand.reserve(G);
+  int queries = 0;
+  uint32_t epoch = 0;
+  bool stopped = false;   // max_queries: nothing is scored any more
+  auto over = [&](int rows) { return k->max_queries > 0 && (long long)queries + rows > k->max_queries; };
+  // scores the `rows` rows that stand in e->wav: dec[0 .. rows) and the log; one look
+  auto score = [&](int rows) -> int {
+    FbScoreCall call{FbRngPoint{p->seed, p->stream, epoch++, 0}};
+    FBCHK(run_scoring(e, call, rows, e->h_frame_off[rows]));
+    // (k_loss is here for the system scores of fb_loss_row alone: its loss and its labels are not this attack's)
+    fb_launch_loss(e->stream, e->raw.as<double>(), e->tv.as<int>(), rows, e->n_out, p->task, e->kind, FB_UNTARGETED,
+                   e->zmean.as<double>(), e->zstd.as<double>(), p->threshold, 0.0, 0, 0, nullptr, 0, scores_dev, loss_dev, out_dev);
+    HIPCHK(hipMemcpyAsync(tv_dev, e->tv.p, sizeof(int) * (size_t)rows, hipMemcpyDeviceToDevice, e->stream));
+    FBCHK(d2h(e, look.data(), e->hsj_look.p, sizeof(double) * look_d));
+    FBCHK(sync_stream(e));
+    const double *sc = look.data() + sc_d;
+    const int *tv = reinterpret_cast<const int *>(look.data() + tv_d);
+    for (int j = 0; j < rows; ++j) {
+      const double *s = sc + (size_t)j * S;
+      int d;
+      if (tv[j] <= 0) {
+        d = -2;   // no voiced frames: no decision
+      } else if (p->task == FB_TASK_SV) {
+        d = s[0] >= p->threshold ? 1 : -1;
+      } else {
+        int am = 0;
+        for (int m = 1; m < S; ++m) if (s[m] > s[am]) am = m;   // the first maximum
+        d = (p->task == FB_TASK_OSI && s[am] < p->threshold) ? -1 : am;
+      }
+      decisions[queries + j] = d;
+      dec[j] = (d != -2 && (targeted ? d == label : d != label)) ? 1 : 0;
+    }
+    queries += rows;
+    return FB_OK;
+  };
+  // the boundary search between a and y: hi (-1: failed) and the rounds scored; on success x, hsj_sc[0] and hsj_best are new
+  auto search = [&](const double *y_dev, bool first_exempt, int *hi_out, int *rounds_out) -> int {
+    int lo = 0, hi = -1, r = 0, rounds = 0;
+    for (;; ++r) {
+      cand.clear();
+      bool last = false;
+      if (r == 0) {
+        for (int j = 0; j < G; ++j) cand.push_back((int)(((long long)(j + 1) * FB_HSJ_Q) / G));
+      } else {
+        const int d = hi - lo;
+        if (d - 1 <= G) {
+          for (int qj = lo + 1; qj < hi; ++qj) cand.push_back(qj);
+          last = true;
+        } else {
+          for (int j = 0; j < G; ++j) cand.push_back(lo + (int)(((long long)(j + 1) * d) / (G + 1)));
+        }
+      }
+      const int rows = (int)cand.size();
+      if (!(r == 0 && first_exempt) && over(rows)) { stopped = true; break; }
+      FBCHK(prepare_nes_batch(e, N, rows));
+      fb_launch_hsj_line(e->stream, a_dev, y_dev, N, rows, cand.data(), bits, e->wav.as<int16_t>());
+      FBCHK(score(rows));
+      rounds = r + 1;
+      int first = -1;
+      for (int j = 0; j < rows && first < 0; ++j) if (dec[j]) first = j;
+      if (first >= 0) {
+        hi = cand[first];
+        // the row of hi is a row that was scored: kept before the next batch takes its place
+        HIPCHK(hipMemcpyAsync(e->hsj_best.p, e->wav.as<int16_t>() + (size_t)first * N, sizeof(int16_t) * (size_t)N,
+                              hipMemcpyDeviceToDevice, e->stream));
+        if (first > 0) lo = cand[first - 1];
+      } else if (hi >= 0) {
+        lo = cand[rows - 1];
+      }
+      if (hi < 0) break;   // nothing succeeded in round 0
+      if (hi - lo == 1 || last || r == k->max_rounds - 1) break;
+    }
+    if (hi >= 0) launch_hsj_adopt(e, y_dev, N, hi);
+    *hi_out = hi;
+    *rounds_out = rounds;
+    return FB_OK;
+  };
+  double D2 = 0.0;
+  auto read_D2 = [&]() -> int {   // one double, and x for the caller who asked for every x_t
+    FBCHK(d2h(e, &D2, e->hsj_sc.p, sizeof(double)));
+    FBCHK(sync_stream(e));
+    return FB_OK;
+  };
+  auto keep_x = [&](int t) -> int {
+    if (x_trace) FBCHK(d2h(e, x_trace + (size_t)t * N, e->hsj_x.p, sizeof(double) * (size_t)N));
+    return FB_OK;
+  };
+  auto row = [&](int t, double b, double np, double m, double hi, double rounds, double sigma) {
+    double *tr = trace + (size_t)t * 8;
+    tr[0] = D2; tr[1] = b; tr[2] = np; tr[3] = m; tr[4] = hi; tr[5] = rounds; tr[6] = (double)queries; tr[7] = sigma;
+  };
+
+  auto t_prev = std::chrono::steady_clock::now();
+  auto tick = [&]() {
+    const auto t_now = std::chrono::steady_clock::now();
+    e->iter_seconds.push_back(std::chrono::duration<double>(t_now - t_prev).count());
+    t_prev = t_now;
+  };
+  *success = -1;
+  *n_iters = 0;
+  int hi = -1, rounds = 0;
+  FBCHK(search(e->hsj_init.as<double>(), true, &hi, &rounds));
+  if (hi < 0) {   // the start is not decided as wanted: nothing to walk from
+    row(0, 0.0, 0.0, -1.0, -1.0, (double)rounds, 0.0);
+    tick();
+    fb_launch_quantize(e->stream, a_dev, N, bits, e->hsj_best.as<int16_t>());
+    FBCHK(d2h(e, adv_i16, e->hsj_best.p, sizeof(int16_t) * (size_t)N));
+    if (adv_f64) FBCHK(d2h(e, adv_f64, e->audio.p, sizeof(double) * (size_t)N));
+    FBCHK(sync_stream(e));
+    HIPCHK(hipGetLastError());
+    *dist2 = 0.0;
+    *n_queries = queries;
+    return FB_OK;
+  }
+  FBCHK(read_D2());
+  FBCHK(keep_x(0));
+  row(0, 0.0, 0.0, -1.0, (double)hi, (double)rounds, 0.0);
+  tick();
+  std::vector<int32_t> w(FB_HSJ_MAX_EVALS);
+  for (int t = 1; t <= p->max_iter && !stopped; ++t) {
+    const double dist = std::sqrt(D2);
+    // 1 probes
+    const int B = hsj_evals(k, t);
+    if (over(B)) break;
+    const double s0 = (k->probe_scale * dist) / std::sqrt((double)N), sigma = s0 > k->sigma_min ? s0 : k->sigma_min;
+    FBCHK(prepare_nes_batch(e, N, B));
+    fb_launch_hsj_probes(e->stream, e->hsj_x.as<double>(), N, B, sigma, p->seed, p->stream, (uint32_t)t, bits,
+                         e->wav.as<int16_t>(), e->hsj_z.as<float>());
+    FBCHK(score(B));
+    // 2 direction
+    int np = 0;
+    for (int j = 0; j < B; ++j) np += dec[j];
+    const bool mixed = np > 0 && np < B;
+    for (int j = 0; j < B; ++j) {
+      const int phi = dec[j] ? 1 : -1;
+      w[j] = mixed ? phi * B - (2 * np - B) : phi;
+    }
+    FBCHK(h2d(e, e->hsj_w.p, w.data(), sizeof(int32_t) * (size_t)B));
+    launch_hsj_dir(e, B, N, p->seed, p->stream, (uint32_t)t, e->hsj_z.as<float>());
+    // 3 step
+    if (over(G)) break;
+    const double xi = dist / std::sqrt((double)t);
+    FBCHK(prepare_nes_batch(e, N, G));
+    fb_launch_hsj_step(e->stream, e->hsj_x.as<double>(), e->hsj_v.as<double>(), e->hsj_sc.as<double>() + 1, xi, 0, G, N, bits,
+                       e->wav.as<int16_t>(), nullptr);
+    FBCHK(score(G));
+    int m = -1;
+    for (int j = 0; j < G && m < 0; ++j) if (dec[j]) m = j;
+    hi = -1;
+    rounds = 0;
+    if (m >= 0) {
+      fb_launch_hsj_step(e->stream, e->hsj_x.as<double>(), e->hsj_v.as<double>(), e->hsj_sc.as<double>() + 1, xi, m, 1, N, bits,
+                         nullptr, e->hsj_y.as<double>());
+      FBCHK(search(e->hsj_y.as<double>(), false, &hi, &rounds));
+      if (rounds == 0) break;   // stopped before the search scored a round: the iteration is dropped
+      if (hi >= 0) FBCHK(read_D2());
+    }
+    FBCHK(keep_x(t));
+    row(t, (double)B, (double)np, (double)m, (double)hi, (double)rounds, sigma);
+    *n_iters = t;
+    tick();
+  }
+  *success = 1;
+  *dist2 = D2;
+  *n_queries = queries;
+  FBCHK(d2h(e, adv_i16, e->hsj_best.p, sizeof(int16_t) * (size_t)N));
+  if (adv_f64) FBCHK(d2h(e, adv_f64, e->hsj_x.p, sizeof(double) * (size_t)N));
+  FBCHK(sync_stream(e));
+  HIPCHK(hipGetLastError());
+  return FB_OK;
+}
+
+// ---- the hooks: exactly the launches of the attack, on state handed in
+extern "C" int fb_debug_hsj_line(fb_engine *e, const double *a, const double *y, int64_t N, const int *q, int rows, int bits,
+                                 int16_t *out, double *x, double *D2) {
+  if (!e || !a || !y || !q || !out || !x || !D2 || N <= 0) return fb_fail(FB_E_ARG, "bad argument");
+  if (rows < 1 || rows > FB_HSJ_MAX_GRID) return fb_fail(FB_E_ARG, "rows %d outside 1 .. %d", rows, FB_HSJ_MAX_GRID);
+  if (bits < 2 || bits > 16) return fb_fail(FB_E_ARG, "bits_per_sample %d unsupported (2 .. 16)", bits);
+  for (int j = 0; j < rows; ++j)
+    if (q[j] < 0 || q[j] > FB_HSJ_Q) return fb_fail(FB_E_ARG, "q %d outside 0 .. %d", q[j], FB_HSJ_Q);
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  e->cached_B = -1;  // (e->wav takes the batch, without a batch layout)
+  FBCHK(prepare_hsj(e, N, rows));
+  FBCHK(e->wav.ensure(sizeof(int16_t) * (size_t)N * rows));
+  FBCHK(h2d(e, e->audio.p, a, sizeof(double) * (size_t)N));
+  FBCHK(h2d(e, e->hsj_y.p, y, sizeof(double) * (size_t)N));
+  fb_launch_hsj_line(e->stream, e->audio.as<double>(), e->hsj_y.as<double>(), N, rows, q, bits, e->wav.as<int16_t>());
+  launch_hsj_adopt(e, e->hsj_y.as<double>(), N, q[0]);
+  FBCHK(d2h(e, out, e->wav.p, sizeof(int16_t) * (size_t)N * rows));
+  FBCHK(d2h(e, x, e->hsj_x.p, sizeof(double) * (size_t)N));
+  FBCHK(d2h(e, D2, e->hsj_sc.p, sizeof(double)));
+  FBCHK(sync_stream(e));
+  HIPCHK(hipGetLastError());
+  return FB_OK;
+}
+
+extern "C" int fb_debug_hsj_probes(fb_engine *e, const double *x, int64_t N, double sigma, uint64_t seed, uint32_t stream,
+                                   uint32_t t, int B, int bits, int16_t *out) {
+  if (!e || !x || !out || N <= 0) return fb_fail(FB_E_ARG, "bad argument");
+  if (B < 1 || B > FB_HSJ_MAX_EVALS) return fb_fail(FB_E_ARG, "B %d outside 1 .. %d", B, FB_HSJ_MAX_EVALS);
+  if (bits < 2 || bits > 16) return fb_fail(FB_E_ARG, "bits_per_sample %d unsupported (2 .. 16)", bits);
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  e->cached_B = -1;
+  FBCHK(prepare_hsj(e, N, B));
+  FBCHK(e->wav.ensure(sizeof(int16_t) * (size_t)N * B));
+  FBCHK(e->hsj_z.ensure(sizeof(float) * (size_t)N * B));
+  FBCHK(h2d(e, e->hsj_x.p, x, sizeof(double) * (size_t)N));
+  fb_launch_hsj_probes(e->stream, e->hsj_x.as<double>(), N, B, sigma, seed, stream, t, bits, e->wav.as<int16_t>(),
+                       e->hsj_z.as<float>());
+  FBCHK(d2h(e, out, e->wav.p, sizeof(int16_t) * (size_t)N * B));
+  FBCHK(sync_stream(e));
+  HIPCHK(hipGetLastError());
+  return FB_OK;
+}
+
+extern "C" int fb_debug_hsj_dir(fb_engine *e, const int32_t *w, int B, uint64_t seed, uint32_t stream, uint32_t t, int64_t N,
+                                double *v, double *S) {
+  if (!e || !w || !v || !S || N <= 0) return fb_fail(FB_E_ARG, "bad argument");
+  if (B < 1 || B > FB_HSJ_MAX_EVALS) return fb_fail(FB_E_ARG, "B %d outside 1 .. %d", B, FB_HSJ_MAX_EVALS);
+  for (int j = 0; j < B; ++j)
+    if (w[j] < -2 * FB_HSJ_MAX_EVALS || w[j] > 2 * FB_HSJ_MAX_EVALS)
+      return fb_fail(FB_E_ARG, "weight %d outside +-%d", w[j], 2 * FB_HSJ_MAX_EVALS);
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  e->cached_B = -1;  // (e->wav takes the probes, without a batch layout)
+  FBCHK(prepare_hsj(e, N, B));
+  FBCHK(e->wav.ensure(sizeof(int16_t) * (size_t)N * B));
+  FBCHK(e->hsj_z.ensure(sizeof(float) * (size_t)N * B));
+  FBCHK(h2d(e, e->hsj_w.p, w, sizeof(int32_t) * (size_t)B));
+  // the attack's pair: the probes launch (here of x = 0, its rows not read) hands its normals to the direction launch
+  HIPCHK(hipMemsetAsync(e->hsj_x.p, 0, sizeof(double) * (size_t)N, e->stream));
+  fb_launch_hsj_probes(e->stream, e->hsj_x.as<double>(), N, B, 0x1p-15, seed, stream, t, 16, e->wav.as<int16_t>(), e->hsj_z.as<float>());
+  launch_hsj_dir(e, B, N, seed, stream, t, e->hsj_z.as<float>());
+  FBCHK(d2h(e, v, e->hsj_v.p, sizeof(double) * (size_t)N));
+  FBCHK(d2h(e, S, e->hsj_sc.as<double>() + 1, sizeof(double)));
+  FBCHK(sync_stream(e));
+  HIPCHK(hipGetLastError());
+  return FB_OK;
+}
+
+extern "C" int fb_debug_hsj_step(fb_engine *e, const double *x, const double *v, int64_t N, double S, double xi, int G, int bits,
+                                 int16_t *out, double *y) {
+  if (!e || !x || !v || !out || !y || N <= 0) return fb_fail(FB_E_ARG, "bad argument");
+  if (G < 1 || G > FB_HSJ_MAX_GRID) return fb_fail(FB_E_ARG, "grid %d outside 1 .. %d", G, FB_HSJ_MAX_GRID);
+  if (bits < 2 || bits > 16) return fb_fail(FB_E_ARG, "bits_per_sample %d unsupported (2 .. 16)", bits);
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  e->cached_B = -1;
+  FBCHK(prepare_hsj(e, N, G));
+  FBCHK(e->wav.ensure(sizeof(int16_t) * (size_t)N * G));
+  FBCHK(h2d(e, e->hsj_x.p, x, sizeof(double) * (size_t)N));
+  FBCHK(h2d(e, e->hsj_v.p, v, sizeof(double) * (size_t)N));
+  FBCHK(h2d(e, e->hsj_sc.as<double>() + 1, &S, sizeof(double)));
+  fb_launch_hsj_step(e->stream, e->hsj_x.as<double>(), e->hsj_v.as<double>(), e->hsj_sc.as<double>() + 1, xi, 0, G, N, bits,
+                     e->wav.as<int16_t>(), nullptr);
+  FBCHK(d2h(e, out, e->wav.p, sizeof(int16_t) * (size_t)N * G));
+  for (int m = 0; m < G; ++m) {   // the float64 launch of one m, as the attack runs it for the m it takes
+    fb_launch_hsj_step(e->stream, e->hsj_x.as<double>(), e->hsj_v.as<double>(), e->hsj_sc.as<double>() + 1, xi, m, 1, N, bits,
+                       nullptr, e->hsj_y.as<double>());
+    FBCHK(d2h(e, y + (size_t)m * N, e->hsj_y.p, sizeof(double) * (size_t)N));
+  }
+  FBCHK(sync_stream(e));
+  HIPCHK(hipGetLastError());
+  return FB_OK;
+}
+
+// tools/hsj_rate.py: `reps` launches of each kernel between two events, after one of each to warm up.  ms[8], per launch:
+// line (G rows), adopt + its sum, probes (B rows), probes that keep their normals, direction + its sum drawing the normals
+// again, direction + its sum reading the kept ones, step (G rows), the NES batch launch (k_perturb) of B rows (B odd: B - 1
+// rows drawn and one clean row; B even: B + 1 rows)
+extern "C" int fb_bench_hsj_kernels(fb_engine *e, const double *a, const double *y, int64_t N, int B, int G, int bits, int reps,
+                                    double *ms) {
+  if (!e || !a || !y || !ms || N <= 0 || reps < 1) return fb_fail(FB_E_ARG, "bad argument");
+  if (B < 1 || B > FB_HSJ_MAX_EVALS) return fb_fail(FB_E_ARG, "B %d outside 1 .. %d", B, FB_HSJ_MAX_EVALS);
+  if (G < 1 || G > FB_HSJ_MAX_GRID) return fb_fail(FB_E_ARG, "grid %d outside 1 .. %d", G, FB_HSJ_MAX_GRID);
+  if (bits < 2 || bits > 16) return fb_fail(FB_E_ARG, "bits_per_sample %d unsupported (2 .. 16)", bits);
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  e->cached_B = -1;
+  const int half = (B + 1) / 2, nes_rows = 2 * half + 1, rows = std::max(std::max(B, G), nes_rows);
+  FBCHK(prepare_hsj(e, N, rows));
+  FBCHK(ensure_nes_buffers(e, N, nes_rows));
+  FBCHK(e->wav.ensure(sizeof(int16_t) * (size_t)N * rows));
+  FBCHK(e->hsj_z.ensure(sizeof(float) * (size_t)N * B));
+  FBCHK(h2d(e, e->audio.p, a, sizeof(double) * (size_t)N));
+  FBCHK(h2d(e, e->hsj_y.p, y, sizeof(double) * (size_t)N));
+  FBCHK(h2d(e, e->adver.p, y, sizeof(double) * (size_t)N));
+  std::vector<int> q(G);
+  for (int j = 0; j < G; ++j) q[j] = (int)(((long long)(j + 1) * FB_HSJ_Q) / G);
+  std::vector<int32_t> w(B);
+  for (int j = 0; j < B; ++j) w[j] = (j & 1) ? B : -B;
+  FBCHK(h2d(e, e->hsj_w.p, w.data(), sizeof(int32_t) * (size_t)B));
+  const double sigma = 0x1p-15;
+  auto run = [&](int which) {
+    switch (which) {
+      case 0: fb_launch_hsj_line(e->stream, e->audio.as<double>(), e->hsj_y.as<double>(), N, G, q.data(), bits, e->wav.as<int16_t>()); break;
+      case 1: launch_hsj_adopt(e, e->hsj_y.as<double>(), N, q[0]); break;
+      case 2: fb_launch_hsj_probes(e->stream, e->hsj_x.as<double>(), N, B, sigma, 1234, 0, 1, bits, e->wav.as<int16_t>(), nullptr); break;
+      case 3: fb_launch_hsj_probes(e->stream, e->hsj_x.as<double>(), N, B, sigma, 1234, 0, 1, bits, e->wav.as<int16_t>(), e->hsj_z.as<float>()); break;
+      case 4: launch_hsj_dir(e, B, N, 1234, 0, 1, nullptr); break;
+      case 5: launch_hsj_dir(e, B, N, 1234, 0, 1, e->hsj_z.as<float>()); break;
+      case 6: fb_launch_hsj_step(e->stream, e->hsj_x.as<double>(), e->hsj_v.as<double>(), e->hsj_sc.as<double>() + 1, 0.01, 0, G, N, bits,
+                                 e->wav.as<int16_t>(), nullptr); break;
+      default: {
+        int n_part = 0;
+        fb_launch_perturb(e->stream, e->adver.as<double>(), e->audio.as<double>(), N, half, sigma, 1234, 1, 0, nullptr,
+                          e->wav.as<int16_t>(), e->dist_part.as<double>(), &n_part, e->zbuf.as<float>(), nullptr, bits);
+        break;
+      }
+    }
+  };
+  for (int which = 0; which < 8; ++which) run(which);   // warm up, in an order in which every launch finds its inputs
+  for (int which = 0; which < 8; ++which) {
+    HIPCHK(hipEventRecord(e->ev0, e->stream));
+    for (int i = 0; i < reps; ++i) run(which);
     HIPCHK(hipEventRecord(e->ev1, e->stream));
     HIPCHK(hipEventSynchronize(e->ev1));
     float t = 0.f;

@@ -227,6 +227,33 @@ void fb_launch_kv_analyse(hipStream_t s, const int16_t *x, int64_t N, int W, con
 void fb_launch_kv_candidates(hipStream_t s, const int16_t *x, int64_t N, int W, int rows, const int *q, const int32_t *tab,
                              const int32_t *ma, const int32_t *mb, const long long *cum, const long long *E, int16_t *out);
 
+// ---- decision-only attack II: HopSkipJump (fb_attack_hsj; hsj_kernels.hip) ------------------------------------------
+#define FB_HSJ_KEY 0x48534A50u   // "HSJP": the probes' normals have a Philox key of their own (seed_lo ^ key, seed_hi)
+#define FB_HSJ_MAX_GRID 64       // rows of a search round or of a step batch (the q list travels as one kernel argument)
+#define FB_HSJ_MAX_ROUNDS 32
+#define FB_HSJ_MAX_EVALS 1024    // probes of an iteration (the weights sit in LDS)
+#define FB_HSJ_Q 1048576         // Q = 2^20: line(y, Q) is the end point
+int fb_hsj_chunks(int64_t N);    // chunks of 1024 samples = workgroups = entries of a partial-sum buffer
+// rows j = 0 .. rows - 1 at out + j * N: the int16 cast of line(y, q[j]) = a + (q[j] 2^-20) (y - a); q a host array
+void fb_launch_hsj_line(hipStream_t s, const double *a, const double *y, int64_t N, int rows, const int *q, int bits,
+                        int16_t *out);
+// x = line(y, q) in float64, part[c] = the chunk sums of ssq(x - a)
+void fb_launch_hsj_adopt(hipStream_t s, const double *a, const double *y, int64_t N, int q, double *x, double *part);
+// *out = part[0] + part[1] + ... + part[n - 1] in that order (one workgroup)
+void fb_launch_hsj_sum(hipStream_t s, const double *part, int n, double *out);
+// rows j = 0 .. B - 1: the int16 cast of clip(x + sigma z_j, -1, 1), z_j = the NES generator's normals of iteration t under
+// the probes' key; zkeep (nullable): z as float32 [B][N] as well
+void fb_launch_hsj_probes(hipStream_t s, const double *x, int64_t N, int B, double sigma, uint64_t seed, uint32_t stream,
+                          uint32_t t, int bits, int16_t *out, float *zkeep);
+// v = sum_j w_j z_j (j ascending; k_hsj_dir), then part[c] = the chunk sums of ssq(v) (k_hsj_ssq); w: device int32 [B];
+// zkept (nullable): the probes launch's normals instead of drawing them again
+void fb_launch_hsj_dir(hipStream_t s, const int32_t *w, int B, int64_t N, uint64_t seed, uint32_t stream, uint32_t t,
+                       const float *zkept, double *v, double *part);
+// y_m = clip(x + c_m v, -1, 1), c_m = *S_dev > 0 ? (xi 2^-m) / sqrt(*S_dev) : 0: rows != null -- m = m0 .. m0 + count - 1 as
+// int16 rows; rows == null -- m = m0 alone, float64, in yout
+void fb_launch_hsj_step(hipStream_t s, const double *x, const double *v, const double *S_dev, double xi, int m0, int count,
+                        int64_t N, int bits, int16_t *rows, double *yout);
+
 // Device-side control block of an attack (FAKEBOB.py:171-203): early stop on loss[0] < 0 (:181), the
 // plateau learning-rate schedule (:195-200) and the per-iteration trace rows are handled by the loss
 // kernel itself, so the host can queue several NES iterations ahead and only looks at the block once

@@ -66,6 +66,16 @@ def kv_params(window=100, grid=15, q_max=65536, max_rounds=32):
     return k
 
 
+def hsj_params(grid=15, max_rounds=8, num_evals_init=32, num_evals_max=256, max_queries=0, sigma_min=2.0 ** -15,
+               probe_scale=0.05):
+    """fb_hsj_params: the search of Engine.attack_hsj (fakebob_hip.h, "decision-only attack II")."""
+    k = N.HsjParams()
+    k.grid = int(grid); k.max_rounds = int(max_rounds); k.num_evals_init = int(num_evals_init)
+    k.num_evals_max = int(num_evals_max); k.max_queries = int(max_queries)
+    k.sigma_min = float(sigma_min); k.probe_scale = float(probe_scale)
+    return k
+
+
 class Engine(object):
     def __init__(self, device=0):
         self._L = N.lib()
@@ -1012,9 +1022,92 @@ class Engine(object):
                                             C.c_int(q.size), C.c_int(int(reps)), N.ptr(ms)))
         return float(ms[0]), float(ms[1])
 
+    # ---- decision-only attack II: HopSkipJump
+    def attack_hsj(self, params, hsj, audio, init, keep_x=False, log_capacity=None):
+        """fb_attack_hsj: HopSkipJump on this engine's system, from `init` (decided as wanted) towards `audio` -> a dict: adv
+        (int16, a row that was scored), adv_f64 (the boundary point x), success (+-1), dist2, n_iters, n_queries, trace
+        (n_iters + 1, 8) = D2, B, n+, m, hi, rounds, queries so far, sigma (row 0: the start search), decisions (n_queries,)
+        in scoring order (-2: no voiced frames) and, keep_x=True, xs (n_iters + 1, N): x after the start and every iteration.
+        log_capacity=None: the decision log holds fb_hsj_max_rows entries."""
+        audio = np.ascontiguousarray(audio, np.float64).reshape(-1)
+        n = audio.size
+        if init is not None:
+            init = np.ascontiguousarray(init, np.float64).reshape(-1)
+            if init.size != n:
+                raise ValueError("init has %d samples, audio %d" % (init.size, n))
+        T = max(int(params.max_iter), 0)
+        cap = int(self._L.fb_hsj_max_rows(C.c_int(T), C.byref(hsj))) if log_capacity is None else int(log_capacity)
+        dec = np.full(max(cap, 1), -3, np.int32)
+        adv, adv_f = np.empty(n, np.int16), np.empty(n, np.float64)
+        trace = np.zeros((T + 1, 8), np.float64)
+        xs = np.zeros((T + 1, n), np.float64) if keep_x else None
+        flag, ni, nq, d2 = C.c_int(), C.c_int(), C.c_int(), C.c_double()
+        N.check(self._L.fb_attack_hsj(self._h, C.byref(params), C.byref(hsj), N.ptr(audio), N.ptr(init) if init is not None else None,
+                                      C.c_int64(n), N.ptr(adv), N.ptr(adv_f), C.byref(flag), C.byref(d2), C.byref(ni),
+                                      C.byref(nq), N.ptr(trace), N.ptr(dec), C.c_longlong(dec.size if cap >= 0 else -1),
+                                      N.ptr(xs) if keep_x else None))
+        res = dict(adv=adv, adv_f64=adv_f, success=flag.value, dist2=d2.value, n_iters=ni.value, n_queries=nq.value,
+                   trace=trace[:ni.value + 1], decisions=dec[:nq.value])
+        if keep_x:
+            res["xs"] = xs[:ni.value + 1] if flag.value == 1 else xs[:0]
+        return res
+
+    def debug_hsj_line(self, a, y, qs, bits_per_sample=16):
+        """fb_debug_hsj_line -> rows (len(qs), N) int16 of line(y, q), and for qs[0] the adopt launch: x (N,) float64, D2."""
+        a = np.ascontiguousarray(a, np.float64).reshape(-1)
+        y = np.ascontiguousarray(y, np.float64).reshape(-1)
+        if y.size != a.size:
+            raise ValueError("a and y must have the same length")
+        q = np.ascontiguousarray(qs, np.int32).reshape(-1)
+        out = np.empty((max(q.size, 1), a.size), np.int16)
+        x, d2 = np.empty(a.size, np.float64), C.c_double()
+        N.check(self._L.fb_debug_hsj_line(self._h, N.ptr(a), N.ptr(y), C.c_int64(a.size), N.ptr(q), C.c_int(q.size),
+                                          C.c_int(int(bits_per_sample)), N.ptr(out), N.ptr(x), C.byref(d2)))
+        return out, x, d2.value
+
+    def debug_hsj_probes(self, x, sigma, seed, stream, t, B, bits_per_sample=16):
+        """fb_debug_hsj_probes -> the B probe rows of x at iteration t, (B, N) int16."""
+        x = np.ascontiguousarray(x, np.float64).reshape(-1)
+        out = np.empty((max(int(B), 1), x.size), np.int16)
+        N.check(self._L.fb_debug_hsj_probes(self._h, N.ptr(x), C.c_int64(x.size), C.c_double(float(sigma)), C.c_uint64(int(seed)),
+                                            C.c_uint32(int(stream)), C.c_uint32(int(t)), C.c_int(int(B)),
+                                            C.c_int(int(bits_per_sample)), N.ptr(out)))
+        return out
+
+    def debug_hsj_dir(self, w, seed, stream, t, n):
+        """fb_debug_hsj_dir -> v (n,) float64 = sum_j w_j z_j of iteration t, and S = ssq(v)."""
+        w = np.ascontiguousarray(w, np.int32).reshape(-1)
+        v, S = np.empty(int(n), np.float64), C.c_double()
+        N.check(self._L.fb_debug_hsj_dir(self._h, N.ptr(w), C.c_int(w.size), C.c_uint64(int(seed)), C.c_uint32(int(stream)),
+                                         C.c_uint32(int(t)), C.c_int64(int(n)), N.ptr(v), C.byref(S)))
+        return v, S.value
+
+    def debug_hsj_step(self, x, v, S, xi, G, bits_per_sample=16):
+        """fb_debug_hsj_step -> the G step rows (G, N) int16 and y_m (G, N) float64."""
+        x = np.ascontiguousarray(x, np.float64).reshape(-1)
+        v = np.ascontiguousarray(v, np.float64).reshape(-1)
+        if v.size != x.size:
+            raise ValueError("x and v must have the same length")
+        G = int(G)
+        out, y = np.empty((max(G, 1), x.size), np.int16), np.empty((max(G, 1), x.size), np.float64)
+        N.check(self._L.fb_debug_hsj_step(self._h, N.ptr(x), N.ptr(v), C.c_int64(x.size), C.c_double(float(S)), C.c_double(float(xi)),
+                                          C.c_int(G), C.c_int(int(bits_per_sample)), N.ptr(out), N.ptr(y)))
+        return out, y
+
+    def bench_hsj_kernels(self, a, y, B, G=15, reps=20, bits_per_sample=16):
+        """Milliseconds per launch (fb_bench_hsj_kernels: device events around `reps` launches of each) -> a dict: line, adopt,
+        probes, probes_keep, dir_draw, dir_kept, step, nes_batch (k_perturb of 2 ceil(B / 2) + 1 rows)."""
+        a = np.ascontiguousarray(a, np.float64).reshape(-1)
+        y = np.ascontiguousarray(y, np.float64).reshape(-1)
+        ms = np.zeros(8, np.float64)
+        N.check(self._L.fb_bench_hsj_kernels(self._h, N.ptr(a), N.ptr(y), C.c_int64(a.size), C.c_int(int(B)), C.c_int(int(G)),
+                                             C.c_int(int(bits_per_sample)), C.c_int(int(reps)), N.ptr(ms)))
+        return dict(zip(("line", "adopt", "probes", "probes_keep", "dir_draw", "dir_kept", "step", "nes_batch"), ms.tolist()))
+
     def attack_iter_seconds(self, n):
         """Seconds per iteration of the last attack / attack_ext (device clock, fb_attack_iter_seconds); of the last
-        attack_pso and per round of the last attack_kenansville, as the host measured them."""
+        attack_pso, per round of the last attack_kenansville and per iteration of the last attack_hsj (entry 0: its start
+        search), as the host measured them."""
         out = np.zeros(max(int(n), 0), np.float64)
         if n > 0:
             N.check(self._L.fb_attack_iter_seconds(self._h, N.ptr(out), C.c_int(int(n))))

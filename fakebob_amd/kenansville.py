@@ -1,7 +1,8 @@
 """Kenansville: the decision-only black-box attack of the evaluation this package follows (SpeakerGuard runs it next to
-FAKEBOB and SirenAttack), on the engine's own systems.  It is the evasion attack of the three: the weakest spectral content
+FAKEBOB and SirenAttack), on the engine's own systems.  It is the decision-only EVASION attack: the weakest spectral content
 of short windows is removed until the system no longer gives the decision it gave, and the smallest removal that does so
-is looked for.
+is looked for.  It accepts a targeted call, but removing spectral content does not build someone else's voice: the
+decision-only attack that reaches a chosen decision is HopSkipJump (hsj.py, `attack_main --attack hsj`).
 
 Every candidate is a function of the audio and one integer factor q in 0 .. 65536; one launch analyses the utterance, one
 launch per round writes a round's candidates into the batch the front end scores, and the host reads the decisions once

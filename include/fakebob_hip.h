@@ -32,6 +32,8 @@
  *                             attack of SpeakerGuard's evaluation, on this library's own systems)
  *   fb_attack_kenansville     (none in FAKEBOB: Kenansville, the decision-only black-box attack of that evaluation -- spectral
  *                             content is removed until the decision changes)
+ *   fb_attack_hsj             (none in FAKEBOB: HopSkipJumpAttack, the decision-only attack that REACHES a decision -- from an
+ *                             audio the system already decides as wanted, along the decision boundary towards the utterance)
  *   fb_get_grad_wb / fb_attack_wb     FakeBob.get_grad + loss_fn (FAKEBOB.py:223-299) and FakeBob.attack (:139-221) with the
  *                             ANALYTIC gradient of the loss in place of the NES estimate: the white-box attacks of
  *                             SpeakerGuard's evaluation (FGSM, PGD, the margin-loss CW-inf) on a GMM-UBM system
@@ -507,6 +509,81 @@ int fb_attack_kenansville(fb_engine *e, const fb_nes_params *p, const fb_kv_para
                           const double *audio, int64_t N, int16_t *adv_i16, int *success, int *factor, int *n_queries,
                           int *n_rounds, int *qs /*[max_rounds][G]*/, int *decisions /*[max_rounds][G]*/,
                           double *scores /*[max_rounds][G][S]*/, int *trace /*[max_rounds][3]*/);
+
+/* ---- decision-only attack II: HopSkipJump (Chen, Jordan, Wainwright 2020), the decision-only attack that targets ----------
+ * fb_attack_kenansville only removes spectral content: it makes an enrolled speaker unrecognised.  fb_attack_hsj goes the other
+ * way from decisions alone: it starts from `init`, any audio of N samples that the system ALREADY decides as wanted (the
+ * target speaker's own voice, say), and walks along the decision boundary towards `audio`, so that an impostor is accepted (SV)
+ * or taken for a chosen speaker (OSI, CSI).  Every batch -- a round of a boundary search, an iteration's probes, its step
+ * sizes -- is written as int16 rows into the batch the front end scores and scored by the path that scores an NES batch; the
+ * host reads scores[rows][S] and tv[rows] once per batch and forms the decisions by the rule of the section above.
+ * Read from fb_nes_params: task, attack_type, max_iter, threshold, target, true_label, seed, stream and bits_per_sample; the
+ * labels are decision values, as in fb_attack_kenansville.  Nothing else of it is read or validated.
+ * Arithmetic.  Everything below is float64, round to nearest, one rounding per written operation, no fused multiply-add;
+ * clip(s, l, h) = min(max(s, l), h); the int16 cast is that of every NES row.  a = `audio` as given, i the sample index,
+ * Q = 2^20, G = grid.  A scored row d is "adversarial" iff d == target (targeted) or d != true_label and d != -2 (untargeted);
+ * -2 (no voiced frames) is no decision, never adversarial and never an error.
+ *   ssq(v)     the sum of squares in a fixed order.  Samples in chunks of 1024; thread t = 0 .. 255 of chunk c owns samples
+ *              1024 c + 4 t .. + 3 (zero beyond N):  s_t = ((v0^2 + v1^2) + v2^2) + v3^2, every square and every add rounded;
+ *              then for stride = 128, 64, .., 1:  s_t = s_t + s_{t + stride} for t < stride;  P_c = s_0;
+ *              ssq = ((0 + P_0) + P_1) + .. in ascending c.
+ *   line(y, q) for q = 0 .. Q:  a + (q 2^-20) (y - a) -- the difference, the exact scale, the product, the sum.  The scored
+ *              row is its cast.  line(y, 0) == a bit for bit.
+ *   search     the boundary search between a and an end point y: fb_attack_kenansville's bracket (lo, hi] on q with q_max = Q
+ *              and rows line(y, q_j) -- round 0  q_j = floor((j + 1) Q / G), so q = Q is scored; later rounds, the update of
+ *              lo and hi and the stops (hi - lo == 1, the last round, max_rounds) exactly as there.  No success in round 0: the
+ *              search FAILS and the caller keeps its x.  Otherwise x := line(y, hi) in float64 and D2 := ssq(x - a) (the
+ *              rounded differences), and dist = sqrt(D2) on the host.  The int16 row of hi is copied aside when it is scored.
+ *   start      the search between a and `init`.  Failure: *success = -1, adv_i16 = cast(a), adv_f64 = a, *dist2 = 0,
+ *              *n_iters = 0.  trace[0] = {D2, 0, 0, -1, hi, rounds, queries so far, 0} (hi = -1 and D2 = 0 on failure).
+ *   iteration  t = 1 .. max_iter:
+ *     1 probes     B_t = min(num_evals_max, isqrt(num_evals_init^2 t)) (integer square root, on the host);
+ *                  sigma_t = max(sigma_min, (probe_scale dist) / sqrt((double)N)) (host).  Row j = 0 .. B_t - 1 is the cast of
+ *                  clip(x + sigma_t (double)z_j[i], -1, 1) -- the product, the sum --, z_j[i] the NES generator's float32
+ *                  normal (the "NES RNG contract") with key (seed_lo ^ 0x48534A50 ("HSJP"), seed_hi) and counter
+ *                  (i >> 2, j, t, stream): the NES counter layout under a key of the probes' own.
+ *     2 direction  phi_j = +1 if row j is adversarial, else -1; n+ = the number of +1.  Integer weights
+ *                  w_j = phi_j B_t - (2 n+ - B_t) when 0 < n+ < B_t, else w_j = phi_j.
+ *                  v[i] = sum_j (double)w_j (double)z_j[i]: from 0.0, j ascending, one rounded add per j (every product is
+ *                  exact).  S = ssq(v).
+ *     3 step       xi_t = dist / sqrt((double)t) (host).  nrm = sqrt(S) (correctly rounded);
+ *                  c_m = S > 0 ? (xi_t 2^-m) / nrm : 0;  y_m = clip(x + c_m v, -1, 1), m = 0 .. G - 1: G rows in one batch.
+ *                  The smallest adversarial m is taken.  None: the iteration STALLS -- x, D2 and the returned row stay, m = -1.
+ *                  Otherwise y := y_m in float64 and the search between a and y follows; a failed search is a stall as well
+ *                  (line(y, Q) need not be y bit for bit).
+ *     4 trace      trace[t] = {D2 after, B_t, n+, m, hi (-1: stall), the search's rounds (0: none), queries so far, sigma_t}.
+ *   stops      max_iter; or max_queries > 0 and the NEXT batch would take the rows scored beyond it -- checked before every
+ *              batch except round 0 of the start search.  A search stopped so after its round 0 ends there, like at
+ *              max_rounds, and its iteration counts; an iteration stopped before its search has scored a round is dropped: it
+ *              leaves no trace row and x stays.  Nothing is scored after a stop.
+ *   result     *success = 1; adv_i16 = the row of hi of the last successful search -- ALWAYS a row that was scored and decided
+ *              adversarial --; adv_f64 = x (may be NULL); *dist2 = D2; *n_iters = the last t with a trace row; *n_queries = the
+ *              rows scored.  decisions[] holds every scored row's decision in scoring order; decisions_cap entries must hold
+ *              fb_hsj_max_rows(max_iter, k) of them (FB_E_ARG before anything runs otherwise).  x_trace (may be NULL)
+ *              [max_iter + 1][N]: x after the start (row 0) and after every iteration with a trace row.
+ * Victim.  The air channel, the input-transform chain, the codec, dither and feature compression act as in
+ * fb_attack_kenansville, keyed by the call's (seed, stream) with epoch = the running count of scoring batches in this call and
+ * utterance row = the row's index in its batch: an attack on a randomised victim is a function of (seed, stream).
+ * fb_attack_iter_seconds reports the host's seconds per iteration (entry 0: the start search).  fb_stats counts the rows as
+ * for any batch; nes_iters is not advanced.
+ * Parameters.  grid 1 .. 64; max_rounds 1 .. 32; 1 <= num_evals_init <= num_evals_max <= 1024; max_queries >= 0 (0: no cap);
+ * sigma_min finite and > 0; probe_scale finite and >= 0.  Defaults of the Python layer: 15, 8, 32, 256, 0, 2^-15 (one int16
+ * step), 0.05.
+ * Refusals.  FB_E_ARG: anything outside those ranges, max_iter < 0, a null `init`, bits_per_sample outside 2 .. 16, audio
+ * shorter than one frame, a task other than the engine's, a label that is no decision of the system, a decision log that is
+ * too small.  FB_E_STATE: no system loaded, or fb_set_eot(r > 1) or companions in force -- BOTH STAY OUT OF THIS VERSION: set
+ * 1 / clear them.  The engine's own systems only: there are no _ext / _dev twins.
+ * Deviations from the paper: the L2 variant only; grid rounds of G rows instead of one-query bisection and one-query step
+ * halving; Gaussian probes that are not normalised to the sphere; a probe radius with a floor of sigma_min, because the
+ * paper's delta = dist / d lies far below one int16 step for audio and the cast would erase it; keyed draws; a stall instead
+ * of unbounded halving. */
+typedef struct { int grid; int max_rounds; int num_evals_init; int num_evals_max; int max_queries; double sigma_min;
+                 double probe_scale; } fb_hsj_params;
+long long fb_hsj_max_rows(int max_iter, const fb_hsj_params *k);   /* -1: parameters out of range */
+int fb_attack_hsj(fb_engine *e, const fb_nes_params *p, const fb_hsj_params *k, const double *audio, const double *init,
+                  int64_t N, int16_t *adv_i16, double *adv_f64 /*nullable*/, int *success, double *dist2, int *n_iters,
+                  int *n_queries, double *trace /*[max_iter + 1][8]*/, int *decisions /*[decisions_cap]*/,
+                  long long decisions_cap, double *x_trace /*nullable [max_iter + 1][N]*/);
 
 /* ---- white-box gradients: backpropagation through the GMM-UBM victim ------------------------------------------------------
  * fb_get_grad estimates the gradient of the loss from scores (NES); the victim lives in the engine, so the gradient itself

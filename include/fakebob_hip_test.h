@@ -129,6 +129,29 @@ int fb_debug_kv_candidates(fb_engine *e, const int16_t *x, int64_t N, int W, con
 int fb_bench_kv_kernels(fb_engine *e, const int16_t *x, int64_t N, int W, const int32_t *tables, const int *q, int rows, int reps,
                         double *ms);
 
+/* Decision-only attack II (fakebob_hip.h: fb_attack_hsj and its contract).  Every hook runs exactly the launches the attack
+ * runs, on float64 state handed in as it is; no system has to be loaded.  N >= 1, bits 2 .. 16.
+ * fb_debug_hsj_line: the rows of line(y, q[0 .. rows)), rows = 1 .. 64, each q 0 .. 2^20 -> out [rows][N]; and the adopt
+ *   launch for q[0]: x [N] = line(y, q[0]) in float64, *D2 = ssq(x - a).
+ * fb_debug_hsj_probes: the probes of x at iteration t, B = 1 .. 1024 -> out [B][N].
+ * fb_debug_hsj_dir: v [N] = sum_j w_j z_j of iteration t (|w_j| <= 2048) and *S = ssq(v); the normals come from a probes
+ *   launch in front of it, as in the attack.
+ * fb_debug_hsj_step: the G = 1 .. 64 step rows of (x, v, S, xi) -> out [G][N], and y [G][N]: the float64 launch of one m,
+ *   for every m in turn. */
+int fb_debug_hsj_line(fb_engine *e, const double *a, const double *y, int64_t N, const int *q, int rows, int bits, int16_t *out,
+                      double *x, double *D2);
+int fb_debug_hsj_probes(fb_engine *e, const double *x, int64_t N, double sigma, uint64_t seed, uint32_t stream, uint32_t t, int B,
+                        int bits, int16_t *out);
+int fb_debug_hsj_dir(fb_engine *e, const int32_t *w, int B, uint64_t seed, uint32_t stream, uint32_t t, int64_t N, double *v,
+                     double *S);
+int fb_debug_hsj_step(fb_engine *e, const double *x, const double *v, int64_t N, double S, double xi, int G, int bits,
+                      int16_t *out, double *y);
+/* tools/hsj_rate.py: every launch alone, `reps` of each between two events after one of each to warm up -> ms[8] =
+ * milliseconds per launch of: line (G rows), adopt + sum, probes (B rows), probes that also keep their normals as float32
+ * [B][N], direction + sum drawing the normals again, direction + sum reading the kept ones, step (G rows), the NES batch
+ * launch (k_perturb) of 2 ceil(B / 2) + 1 rows. */
+int fb_bench_hsj_kernels(fb_engine *e, const double *a, const double *y, int64_t N, int B, int G, int bits, int reps, double *ms);
+
 /* What the front end of the last batch ran (fb_score_*, fb_get_grad, an NES iteration, fb_debug_mfcc / _feats, enrolment
  * statistics): info[5] = {the MFCC kernel, the chain after it, where the CompressedMatrix round trip ran, the longest
  * utterance of the batch in frames, the batch size}.  Recorded on the host when the kernels are enqueued; read only.
