@@ -176,6 +176,15 @@ struct fb_engine {
   int bench_B = 0;
   long long pre_iter = -1;  // >= 0: wav / zbuf / dist_part already hold the NES batch of this iteration (k_update_perturb)
   int pre_ndp = 0;
+  // fb_debug_nes_batch: the NES batch the launches of the last fb_get_grad* / fb_attack* / fb_bench_nes call left in wav /
+  // zbuf, recorded on the host as they are enqueued (`queued`) and published (`iter`) when the call has succeeded
+  struct {
+    long long iter = -1;    // Philox iteration index of the resident rows (-1: none; reset wherever bench_it is)
+    long long queued = -1;  // ... of the batch launch enqueued last
+    int64_t N = 0;
+    int half = 0;
+    bool q = false, z = false;  // wav holds its int16 rows (the engine's own systems), zbuf its normals (Philox noise)
+  } nes_rec;
   int vad_part_B = -1, vad_part_dim = -1;  // slot layout the sentinel-filled exchange buffer of k_vad_delta_cmvn_p was prepared for
   int ctl_seq = 0;         // loss bodies queued on the control block since its reset (FbCtlDev::pub_seq)
   unsigned vad_epoch = 0;  // launches of the fused VAD/CMVN kernels on vad_pub (its published counts carry the epoch)
@@ -640,7 +649,7 @@ extern "C" int fb_num_speakers(fb_engine *e) {
 // ------------------------------------------------------- scoring pipeline
 // Prepares offsets for a batch whose int16 samples are already in e->wav.
 static int prepare_batch(fb_engine *e, const int64_t *off, int B) {
-  e->bench_it = -1;  // whatever attack fb_bench_nes left resident is gone with the batch layout
+  e->bench_it = e->nes_rec.iter = -1;  // whatever attack fb_bench_nes left resident is gone with the batch layout
   if (e->vad_counter.p) HIPCHK(hipMemsetAsync(e->vad_counter.p, 0, sizeof(int), e->stream));  // see ctl_reset
   e->h_wav_off.assign(off, off + B + 1);
   e->h_frame_off.resize(B + 1);
@@ -812,6 +821,15 @@ static int choose_update_threads(const fb_engine *e) {
 static void record_update_threads(fb_engine *e, int threads) {
   e->shape_upd_threads = threads;
   e->have_shape = true;
+}
+// the NES batch of Philox iteration `iter` as its launch went out (fb_debug_nes_batch): q, the int16 rows are in e->wav; z, the
+// launch kept its normals in e->zbuf
+static void record_nes_batch(fb_engine *e, long long iter, int64_t N, int half, bool q, bool z) {
+  e->nes_rec.queued = iter;
+  e->nes_rec.N = N;
+  e->nes_rec.half = half;
+  e->nes_rec.q = q;
+  e->nes_rec.z = z;
 }
 // The batch the MFCC reads: e->wav, or -- with an input-transform chain set -- its transform in e->wav_tf, one more launch.
 // off: the batch's offsets on the host (off[0] = 0), already in e->wav_off on the device.
@@ -1785,6 +1803,7 @@ static int enqueue_get_grad(fb_engine *e, const fb_nes_params *p, int64_t N, uin
     fb_launch_perturb(e->stream, e->adver.as<double>(), with_dist ? e->audio.as<double>() : nullptr, N, half,
                       p->sigma, p->seed, iter, p->stream, noise_dev, e->wav.as<int16_t>(),
                       e->dist_part.as<double>(), &ndp, noise_dev ? nullptr : e->zbuf.as<float>(), stop, nes_bits(p));
+    record_nes_batch(e, iter, N, half, r == 1, !noise_dev);  // (r > 1: the composed rows are pinned elsewhere)
   }
   e->pre_iter = -1;
   // GMM systems inside the device-controlled loop: finalisation and loss share one launch
@@ -1918,6 +1937,7 @@ static int enqueue_get_grad_ext(fb_engine *e, const fb_nes_params *p, const FbSc
   fb_launch_perturb_f64(e->stream, e->adver.as<double>(), with_dist ? e->audio.as<double>() : nullptr, N, half,
                         p->sigma, p->seed, iter, p->stream, noise_dev, e->ext_x.as<double>(),
                         e->dist_part.as<double>(), &ndp, noise_dev ? nullptr : e->zbuf.as<float>());
+  record_nes_batch(e, iter, N, half, false, !noise_dev);
   const size_t xb = sizeof(double) * (size_t)N * B;
   std::vector<double> sc_h((size_t)B * S);
   if (xb <= FB_PIN_MAX) {  // the callback reads the pinned staging area directly
@@ -2047,7 +2067,7 @@ static int nes_setup(fb_engine *e, const fb_nes_params *p, int64_t N, FbScorer &
 static int nes_gradient(fb_engine *e, const fb_nes_params *p, FbScorer sc, const double *audio, int64_t N,
                         uint32_t iter, const double *noise_pos, double *final_loss, double *grad, double *adver_loss,
                         double *score0) {
-  if (e) e->bench_it = -1;
+  if (e) e->bench_it = e->nes_rec.iter = -1;
   if (e) memset(e->nes_route, 0, sizeof(e->nes_route));
   if (!audio) return fb_fail(FB_E_ARG, "audio is NULL");
   FBCHK(nes_setup(e, p, N, sc, false));
@@ -2073,6 +2093,7 @@ static int nes_gradient(fb_engine *e, const fb_nes_params *p, FbScorer sc, const
       fb_launch_perturb_x(e->stream, sc.m->x_dtype, e->adver.as<double>(), nullptr, N, half, p->sigma, p->seed, iter,
                           p->stream, noise_dev, sc.m->x, x_aligned(sc.m), e->dist_part.as<double>(), nullptr,
                           noise_dev ? nullptr : e->zbuf.as<float>(), nullptr);
+      record_nes_batch(e, iter, N, half, false, !noise_dev);
       FBCHK(enqueue_score_loss_dev(e, p, sc, N, 0, nullptr, nullptr, 0));
       break;
   }
@@ -2082,6 +2103,7 @@ static int nes_gradient(fb_engine *e, const fb_nes_params *p, FbScorer sc, const
   if (grad) FBCHK(d2h(e, grad, e->grad.p, sizeof(double) * (size_t)N));
   FBCHK(fetch_out(e, native));
   e->nes_iters += 1;
+  e->nes_rec.iter = e->nes_rec.queued;
   if (final_loss) *final_loss = e->h_out->final_loss;
   if (adver_loss) *adver_loss = e->h_out->adver_loss;
   if (score0) for (int s = 0; s < sc.S; ++s) score0[s] = e->h_out->score0[s];
@@ -2171,6 +2193,7 @@ static int attack_loop(fb_engine *e, const fb_nes_params *p, int64_t N, const Fb
           if (updated) {
             e->pre_ndp = (int)((N + 255) / 256);
             e->pre_iter = (long long)it + 1;
+            record_nes_batch(e, (long long)it + 1, N, half, nes_replicas(e) == 1, true);
             record_update_threads(e, 512);  // (the update workgroups of k_gmm_finalize_loss_update)
           } else if (upd_next) {
             e->pre_ndp = fb_launch_update_perturb(e->stream, e->loss.as<double>(), N, half, p->sigma, e->zbuf.as<float>(),
@@ -2181,6 +2204,7 @@ static int attack_loop(fb_engine *e, const fb_nes_params *p, int64_t N, const Fb
             record_update_threads(e, kn.upd_threads);
             e->nes_route[FB_NES_ROUTE_K_UPDATE_PERTURB] += 1;
             e->pre_iter = (long long)it + 1;
+            record_nes_batch(e, (long long)it + 1, N, half, nes_replicas(e) == 1, true);
             updated = true;
           }
           break;
@@ -2190,10 +2214,12 @@ static int attack_loop(fb_engine *e, const fb_nes_params *p, int64_t N, const Fb
           break;
         case FB_SCORER_DEV: {
           const int xv = x_aligned(sc.m) ? 1 : 0;
-          if (!have_batch)
+          if (!have_batch) {
             fb_launch_perturb_x(e->stream, sc.m->x_dtype, e->adver.as<double>(), e->audio.as<double>(), N, half, p->sigma,
                                 p->seed, (uint32_t)it, p->stream, noise_dev, sc.m->x, xv, e->dist_part.as<double>(), &ndp,
                                 noise_dev ? nullptr : e->zbuf.as<float>(), &ctl->stop);
+            record_nes_batch(e, it, N, half, false, !noise_dev);
+          }
           FBCHK(enqueue_score_loss_dev(e, p, sc, N, ndp, ctl, trace_dev, it - it_base));
           if (upd_next) {
             ndp = fb_launch_update_perturb_x(e->stream, sc.m->x_dtype, e->loss.as<double>(), N, half, p->sigma,
@@ -2202,6 +2228,7 @@ static int attack_loop(fb_engine *e, const fb_nes_params *p, int64_t N, const Fb
                                              p->seed, (uint32_t)(it + 1), p->stream, sc.m->x, xv,
                                              e->dist_part.as<double>(), kn.upd_threads);
             record_update_threads(e, kn.upd_threads);
+            record_nes_batch(e, (long long)it + 1, N, half, false, true);
             e->nes_route[FB_NES_ROUTE_K_UPDATE_PERTURB] += 1;
             have_batch = updated = true;
           }
@@ -2289,7 +2316,7 @@ static int attack_loop(fb_engine *e, const fb_nes_params *p, int64_t N, const Fb
 static int run_attack(fb_engine *e, const fb_nes_params *p, FbScorer sc, const double *audio, int64_t N,
                       const double *noise_all, int16_t *adv_i16, double *adver_f64, double *trace, int *n_trace,
                       int *success_flag) {
-  if (e) e->bench_it = -1;
+  if (e) e->bench_it = e->nes_rec.iter = -1;
   if (e) memset(e->nes_route, 0, sizeof(e->nes_route));
   if (!audio || !adv_i16 || !success_flag) return fb_fail(FB_E_ARG, "null argument");
   FBCHK(nes_setup(e, p, N, sc, true));
@@ -2322,6 +2349,8 @@ static int run_attack(fb_engine *e, const fb_nes_params *p, FbScorer sc, const d
   FBCHK(d2h(e, adv_i16, e->wav.p, sizeof(int16_t) * (size_t)N));
   if (adver_f64) FBCHK(d2h(e, adver_f64, e->adver.p, sizeof(double) * (size_t)N));
   FBCHK(sync_stream(e));
+  // the batch launches queued behind a stopping iteration returned on its flag: that iteration's rows are the resident ones
+  e->nes_rec.iter = e->h_ctl->broke ? (long long)e->h_ctl->stop_iter : e->nes_rec.queued;
   return FB_OK;
 }
 
@@ -2688,7 +2717,7 @@ static int wb_enqueue(fb_engine *e, const fb_nes_params *q, int64_t N, uint32_t 
 // the start of every white-box entry point, before its arguments are looked at: the route counters of the call start at zero
 static void wb_call_begin(fb_engine *e) {
   if (!e) return;
-  e->bench_it = -1;
+  e->bench_it = e->nes_rec.iter = -1;
   memset(e->nes_route, 0, sizeof(e->nes_route));
   memset(e->wb_route, 0, sizeof(e->wb_route));
   e->wb_air_launches = 0;
@@ -2926,7 +2955,7 @@ extern "C" int fb_debug_iv_feat_grad(fb_engine *e, const float *feats, int Tv, c
   HIPCHK(hipSetDevice(e->device));
   FBCHK(sync_stream(e));
   const FbIvDev &iv = e->iv;
-  e->bench_it = -1;
+  e->bench_it = e->nes_rec.iter = -1;
   memset(e->wb_route, 0, sizeof(e->wb_route));
   FBCHK(wb_prepare(e, 1, Tv, true));
   FBCHK(e->feats.ensure(sizeof(float) * (size_t)Tv * iv.D));
@@ -3422,6 +3451,27 @@ extern "C" int fb_debug_nes_route(fb_engine *e, int *info) {
   return FB_OK;
 }
 
+extern "C" int fb_debug_nes_batch(fb_engine *e, int64_t N, int half, int16_t *q, float *z, long long *iter) {
+  if (!e) return fb_fail(FB_E_ARG, "null engine");
+  const auto &r = e->nes_rec;
+  if (r.iter < 0) return fb_fail(FB_E_STATE, "fb_debug_nes_batch: no NES batch is resident on the engine");
+  if (N != r.N || half != r.half)
+    return fb_fail(FB_E_ARG, "fb_debug_nes_batch: N %lld, half %d; the last call ran N %lld, half %d", (long long)N, half,
+                   (long long)r.N, r.half);
+  const int B = 2 * half + 1;
+  const size_t nq = sizeof(int16_t) * (size_t)N * B, nz = sizeof(float) * (size_t)N * half;
+  if (q && (!r.q || e->cached_B != B || e->cached_N != N || nq > e->wav.cap))
+    return fb_fail(FB_E_STATE, "fb_debug_nes_batch: the engine holds no int16 batch of the last call (a foreign model's is in its x)");
+  if (z && (!r.z || nz > e->zbuf.cap))
+    return fb_fail(FB_E_STATE, "fb_debug_nes_batch: the last call kept no normals (it ran on injected ones)");
+  HIPCHK(hipSetDevice(e->device));
+  if (q) FBCHK(d2h(e, q, e->wav.p, nq));
+  if (z) FBCHK(d2h(e, z, e->zbuf.p, nz));
+  FBCHK(sync_stream(e));
+  if (iter) *iter = r.iter;
+  return FB_OK;
+}
+
 extern "C" int fb_debug_foreign_path(fb_engine *e, fb_foreign_path_info *info) {
   if (!e || !info) return fb_fail(FB_E_ARG, "null argument");
   if (e->foreign.path == 0) return fb_fail(FB_E_STATE, "no foreign-model call has run yet");
@@ -3459,7 +3509,7 @@ static int ensure_pso_buffers(fb_engine *e, int64_t N, int P) {
 
 extern "C" int fb_attack_pso(fb_engine *e, const fb_nes_params *p, const fb_pso_params *q, const double *audio, int64_t N,
                              int16_t *adv_i16, double *adv_f64, int *success, int *n_iters, double *trace, double *losses) {
-  if (e) e->bench_it = -1;
+  if (e) e->bench_it = e->nes_rec.iter = -1;
   if (!e || !p || !q || !audio || !adv_i16 || !success || !n_iters || !trace || !losses) return fb_fail(FB_E_ARG, "null argument");
   if (!e->have_gmm) return fb_fail(FB_E_STATE, "no model loaded");
   if (e->eot > 1)
@@ -3652,7 +3702,7 @@ static void launch_kv_candidates(fb_engine *e, int64_t N, int W, int rows, const
 extern "C" int fb_attack_kenansville(fb_engine *e, const fb_nes_params *p, const fb_kv_params *k, const int32_t *tables,
                                      const double *audio, int64_t N, int16_t *adv_i16, int *success, int *factor,
                                      int *n_queries, int *n_rounds, int *qs, int *decisions, double *scores, int *trace) {
-  if (e) e->bench_it = -1;
+  if (e) e->bench_it = e->nes_rec.iter = -1;
   if (!e || !p || !k || !audio || !adv_i16 || !success || !factor || !n_queries || !n_rounds || !qs || !decisions || !scores || !trace)
     return fb_fail(FB_E_ARG, "null argument");
   if (!e->have_gmm) return fb_fail(FB_E_STATE, "no model loaded");
@@ -3920,7 +3970,7 @@ static void launch_hsj_dir(fb_engine *e, int B, int64_t N, uint64_t seed, uint32
 extern "C" int fb_attack_hsj(fb_engine *e, const fb_nes_params *p, const fb_hsj_params *k, const double *audio, const double *init,
                              int64_t N, int16_t *adv_i16, double *adv_f64, int *success, double *dist2, int *n_iters,
                              int *n_queries, double *trace, int *decisions, long long decisions_cap, double *x_trace) {
-  if (e) e->bench_it = -1;
+  if (e) e->bench_it = e->nes_rec.iter = -1;
   if (!e || !p || !k || !audio || !adv_i16 || !success || !dist2 || !n_iters || !n_queries || !trace || !decisions)
     return fb_fail(FB_E_ARG, "null argument");
   if (!init) return fb_fail(FB_E_ARG, "null init: HopSkipJump starts from an audio that is already decided as wanted");
@@ -4252,6 +4302,7 @@ extern "C" int fb_bench_hsj_kernels(fb_engine *e, const double *a, const double 
   HIPCHK(hipSetDevice(e->device));
   FBCHK(sync_stream(e));
   e->cached_B = -1;
+  e->nes_rec.iter = -1;  // (the k_perturb launches below overwrite zbuf)
   const int half = (B + 1) / 2, nes_rows = 2 * half + 1, rows = std::max(std::max(B, G), nes_rows);
   FBCHK(prepare_hsj(e, N, rows));
   FBCHK(ensure_nes_buffers(e, N, nes_rows));
@@ -4316,7 +4367,7 @@ extern "C" int fb_estimate_threshold(fb_engine *e, const fb_nes_params *p_in, do
                                      const double *audio, int64_t N, const double *noise_all, int max_total_iters,
                                      double *score_out, int *n_iters_out, int *n_outer_out, double *thr_final,
                                      double *adver_f64) {
-  if (e) e->bench_it = -1;
+  if (e) e->bench_it = e->nes_rec.iter = -1;
   if (!audio || !score_out) return fb_fail(FB_E_ARG, "null argument");
   if (!p_in) return fb_fail(FB_E_ARG, "null params");
   if (p_in->task == FB_TASK_CSI) return fb_fail(FB_E_ARG, "no threshold to estimate for CSI (FAKEBOB.py:41-43)");
@@ -4642,7 +4693,7 @@ extern "C" int fb_set_input_transform(fb_engine *e, const fb_tf_stage *stages, i
   }
   e->tf_taps = std::move(fresh);
   e->tf = ch;
-  e->bench_it = -1;  // an attack fb_bench_nes left resident was scored through the previous chain
+  e->bench_it = e->nes_rec.iter = -1;  // an attack fb_bench_nes left resident was scored through the previous chain
   return FB_OK;
 }
 
@@ -4659,7 +4710,7 @@ extern "C" int fb_debug_input_transform(fb_engine *e, const int16_t *wav, const 
   HIPCHK(hipSetDevice(e->device));
   FBCHK(sync_stream(e));
   e->cached_B = -1;  // the scoring batch layout no longer describes e->wav / e->wav_off
-  e->bench_it = -1;
+  e->bench_it = e->nes_rec.iter = -1;
   const size_t bytes = sizeof(int16_t) * (size_t)off[B];
   FBCHK(e->wav.ensure(bytes));
   FBCHK(e->wav_tf.ensure(bytes));
@@ -4692,7 +4743,7 @@ extern "C" int fb_set_air_channel(fb_engine *e, const fb_air_params *p) {
     set.rho_hi = p->rho_hi;
   }
   e->air = set;
-  e->bench_it = -1;  // an attack fb_bench_nes left resident was scored through the previous setting
+  e->bench_it = e->nes_rec.iter = -1;  // an attack fb_bench_nes left resident was scored through the previous setting
   return FB_OK;
 }
 
@@ -4752,7 +4803,7 @@ extern "C" int fb_set_codec(fb_engine *e, int kind) {
   if (kind != FB_CODEC_NONE && kind != FB_CODEC_ULAW && kind != FB_CODEC_ALAW && kind != FB_CODEC_ADPCM)
     return fb_fail(FB_E_ARG, "codec kind %d: 0 (none), 1 (mu-law), 2 (A-law) or 3 (IMA ADPCM)", kind);
   e->codec = kind;
-  e->bench_it = -1;  // an attack fb_bench_nes left resident was scored through the previous setting
+  e->bench_it = e->nes_rec.iter = -1;  // an attack fb_bench_nes left resident was scored through the previous setting
   return FB_OK;
 }
 
@@ -4790,7 +4841,7 @@ extern "C" int fb_set_eot(fb_engine *e, int r) {
   if ((e->comp_K1 + 1) * r > 32)
     return fb_fail(FB_E_ARG, "EOT size %d with %d utterances (fb_set_companions): utterances * eot is at most 32", r, e->comp_K1 + 1);
   e->eot = r;
-  e->bench_it = -1;  // an attack fb_bench_nes left resident was laid out for the previous size
+  e->bench_it = e->nes_rec.iter = -1;  // an attack fb_bench_nes left resident was laid out for the previous size
   return FB_OK;
 }
 
@@ -4813,7 +4864,7 @@ extern "C" int fb_set_companions(fb_engine *e, const int16_t *wav, int K1, int64
   }
   e->comp_K1 = K1;
   e->comp_N = K1 ? N : 0;
-  e->bench_it = -1;  // an attack fb_bench_nes left resident was laid out for the previous setting
+  e->bench_it = e->nes_rec.iter = -1;  // an attack fb_bench_nes left resident was laid out for the previous setting
   return FB_OK;
 }
 
@@ -4829,7 +4880,7 @@ extern "C" int fb_debug_compose(fb_engine *e, const int16_t *q, int B, int64_t N
   HIPCHK(hipSetDevice(e->device));
   FBCHK(sync_stream(e));
   e->cached_B = -1;  // the scoring batch layout no longer describes e->wav / e->wav_off
-  e->bench_it = -1;
+  e->bench_it = e->nes_rec.iter = -1;
   const size_t bytes = sizeof(int16_t) * (size_t)B * (size_t)N;
   DevBuf d_a0;
   FBCHK(e->wav.ensure(bytes));
@@ -4860,7 +4911,7 @@ extern "C" int fb_set_feature_compression(fb_engine *e, double ratio, int iters)
     return fb_fail(FB_E_ARG, "feature compression takes 0 < ratio <= 1 and 1 .. 64 iterations, or 0 and 0 for none (got %g, %d)", ratio, iters);
   e->feco_ratio = off ? 0.0 : ratio;
   e->feco_iters = iters;
-  e->bench_it = -1;  // an attack fb_bench_nes left resident ran under the previous setting
+  e->bench_it = e->nes_rec.iter = -1;  // an attack fb_bench_nes left resident ran under the previous setting
   return FB_OK;
 }
 
@@ -5009,7 +5060,7 @@ extern "C" int fb_debug_input_transform_eot(fb_engine *e, const int16_t *wav, co
   HIPCHK(hipSetDevice(e->device));
   FBCHK(sync_stream(e));
   e->cached_B = -1;  // the scoring batch layout no longer describes e->wav / e->wav_off
-  e->bench_it = -1;
+  e->bench_it = e->nes_rec.iter = -1;
   const size_t bytes = sizeof(int16_t) * (size_t)off[B];
   DevBuf d_out_off;
   FBCHK(e->wav.ensure(bytes));
@@ -5128,7 +5179,7 @@ extern "C" int fb_debug_defence_vjp(fb_engine *e, const int16_t *wav, int64_t n,
   if (e->comp_K1 > 0) return fb_fail(FB_E_STATE, "white-box gradients: companions are set (fb_set_companions: clear them)");
   if (num_frames(e->cfg, n) <= 0) return fb_fail(FB_E_ARG, "audio shorter than one frame");
   HIPCHK(hipSetDevice(e->device));
-  e->bench_it = -1;
+  e->bench_it = e->nes_rec.iter = -1;
   memset(e->wb_route, 0, sizeof(e->wb_route));
   e->wb_air_launches = 0;
   const int r = e->eot;
@@ -5273,6 +5324,7 @@ extern "C" int fb_bench_nes(fb_engine *e, const fb_nes_params *p, const double *
   double gmm_ms = 0.0;
   int64_t vrows = 0;
   const int it0 = (int)e->bench_it + warmup;
+  e->nes_rec.iter = -1;
   FBCHK(sync_stream(e));
   HIPCHK(hipEventRecord(e->ev0, e->stream));
   e->time_gmm = time_gmm;
@@ -5280,6 +5332,7 @@ extern "C" int fb_bench_nes(fb_engine *e, const fb_nes_params *p, const double *
   e->gmm_launches = 0;
   FBCHK(attack_loop(e, p, N, sc, kn, nullptr, it0, iters, nullptr));
   e->bench_it = it0 + iters;
+  e->nes_rec.iter = e->nes_rec.queued;
   e->bench_N = N;
   e->bench_B = B;
   e->nes_iters += warmup + iters;

@@ -1123,7 +1123,8 @@ class Engine(object):
         propagate it)."""
         def _cb(_ctx, aud, n, b, out):
             try:
-                a = np.ascontiguousarray(np.ctypeslib.as_array(aud, shape=(b, n)).T)   # (N, B) copy, columns = utterances
+                # (N, B) copy, columns = utterances (np.array: ascontiguousarray hands back a view of the buffer when n == 1)
+                a = np.array(np.ctypeslib.as_array(aud, shape=(b, n)).T, order="C")
                 sc = np.asarray(score_fn(a), np.float64).reshape(b, S)
                 np.ctypeslib.as_array(out, shape=(b, S))[...] = sc
                 return 0
@@ -1237,6 +1238,18 @@ class Engine(object):
         info = (C.c_int * len(self._NES_ROUTE))()
         N.check(self._L.fb_debug_nes_route(self._h, info))
         return dict(zip(self._NES_ROUTE, (int(v) for v in info)))
+
+    def debug_nes_batch(self, n, half, want_q=True, want_z=True):
+        """The NES batch the last get_grad* / attack* / bench_nes call left on the device (fb_debug_nes_batch; read only) ->
+        (q, z, iter): q (2 half + 1, n) int16, the batch of the engine's own systems (None without want_q: a foreign
+        model's batch is in its x), z (half, n) float32, the normals kept for the gradient (None without want_z: a call on
+        injected normals keeps none), iter the Philox iteration index the rows were drawn for."""
+        q = np.empty((2 * half + 1, n), np.int16) if want_q else None
+        z = np.empty((half, n), np.float32) if want_z else None
+        it = C.c_longlong()
+        N.check(self._L.fb_debug_nes_batch(self._h, C.c_int64(n), C.c_int(half), None if q is None else N.ptr(q),
+                                           None if z is None else N.ptr(z), C.byref(it)))
+        return q, z, it.value
 
     def estimate_threshold(self, params, model_threshold, audio, noise_all=None, max_total_iters=100000):
         audio = np.ascontiguousarray(audio, np.float64).reshape(-1)

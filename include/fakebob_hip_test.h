@@ -235,6 +235,19 @@ int fb_debug_foreign_path(fb_engine *e, fb_foreign_path_info *info);
 #define FB_NES_ROUTE_K_GRAD_UPDATE 5      /* k_grad_update on its own */
 #define FB_NES_ROUTE_N 6
 int fb_debug_nes_route(fb_engine *e, int *info);
+/* What the last fb_get_grad* / fb_attack* / fb_bench_nes call left on the device, read only (no launch; the attack can be
+ * continued afterwards): q[2 half + 1][N] the int16 batch of the engine's own systems (nullable; FB_E_STATE when q is asked for
+ * after a foreign-model call, whose batch lives in the caller's x, or under fb_set_eot / fb_set_companions), z[half][N] the
+ * float32 normals kept for the gradient (nullable; FB_E_STATE after a call on injected normals, which keeps none), *iter
+ * (nullable) the Philox iteration index those rows were drawn for.  FB_E_STATE before the first such call, after one that
+ * failed and after any call that reuses the buffers; FB_E_ARG when N or half is not the last call's.
+ * Which batch that is, recorded on the host as the launches are enqueued: fb_get_grad*: the call's own.  An attack that ran to
+ * max_iter on a route whose update launch writes the next batch (k_update_perturb(_x), k_gmm_finalize_loss_update): iteration
+ * max_iter's, built from the returned float64 audio and never scored; on the other routes (k_perturb*, k_grad_update):
+ * iteration max_iter - 1's, built from the iterate before the last step.  An attack that stopped early: the stopping
+ * iteration's.  fb_attack's epilogue quantises the returned audio into row 0 of q: where the update launch wrote the batch that
+ * is the value it wrote there. */
+int fb_debug_nes_batch(fb_engine *e, int64_t N, int half, int16_t *q, float *z, long long *iter);
 
 /* Which diagonal-GMM arithmetic the loaded model runs on: 2 = two-term f16 split (k_gmm_fx2w / k_gmm_fx2, default),
  * 1 = exact three-term bf16 split (k_gmm_bx3: chosen automatically when a parameter does not fit f16's exponent

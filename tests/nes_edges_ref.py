@@ -40,7 +40,12 @@ def adv_i16(z, i, audio):
     return adv.astype(np.int16)
 
 
-def replay_noise(engine, seed, stream, n, half, iters):
+def replay_noise(engine, seed, stream, n, half, iters, oracle=None):
     """The device's Philox normals of iterations 0 .. iters - 1 as the noise_all an attack takes: float32 widened to
-    float64, transposed to [N][half] (tests/test_gpu_plugin_api.py: test_philox_path_and_error_propagation)."""
-    return np.stack([engine.debug_noise(seed, it, stream, n, half).astype(np.float64).T.copy() for it in range(iters)])
+    float64, transposed to [N][half] (tests/test_gpu_plugin_api.py: test_philox_path_and_error_propagation).  With the
+    oracle fixture handed in, the tensor must be the oracle generator's bit for bit: the replay then stands on the oracle,
+    not on k_noise."""
+    z = np.stack([engine.debug_noise(seed, it, stream, n, half) for it in range(iters)])
+    if oracle is not None:
+        assert np.array_equal(z.view(np.uint32), np.stack([oracle.noise(seed, it, stream, n, half) for it in range(iters)]).view(np.uint32))
+    return np.ascontiguousarray(z.astype(np.float64).transpose(0, 2, 1))

@@ -361,7 +361,7 @@ def test_gmm_launch_chains_are_identical_and_equal_the_philox_replay(oracle, cle
             for k in env:
                 clean_env.delenv(k, raising=False)
         e.set_fused_chain(True)
-        noise = R.replay_noise(e, 5, 0, n, half, 6)
+        noise = R.replay_noise(e, 5, 0, n, half, 6, oracle=oracle)
         rep = e.attack(p_full, audio, noise_all=noise)
         assert _launches(e) == dict(fin_loss=6, k_grad_update=6)
         grad0 = e.get_grad(p_full, audio, it=0)

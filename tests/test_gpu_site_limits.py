@@ -298,7 +298,7 @@ def test_nes_step_behind_a_60_model_site(oracle, nes_site, clean_env, task, spd)
             for k in env:
                 clean_env.delenv(k, raising=False)
         e.set_fused_chain(True)
-        rep = e.attack(p, audio, noise_all=R.replay_noise(e, 5, 0, n, half, iters))
+        rep = e.attack(p, audio, noise_all=R.replay_noise(e, 5, 0, n, half, iters, oracle=oracle))
         assert _launches(e) == dict(fin_loss=iters, k_grad_update=iters)
         grad0 = e.get_grad(p, audio, it=0)
         assert _launches(e) == dict(k_loss=1, k_grad_update=1)
@@ -422,7 +422,7 @@ def test_ivector_tail_loss_with_60_speakers(oracle, iv60, iv60_ctx, clean_env, t
             for k in env:
                 clean_env.delenv(k, raising=False)
         e.set_fused_chain(True)
-        rep = e.attack(p, audio, noise_all=R.replay_noise(e, 7, 1, n, half, iters))
+        rep = e.attack(p, audio, noise_all=R.replay_noise(e, 7, 1, n, half, iters, oracle=oracle))
         assert _launches(e) == dict(iv_tail=iters, k_grad_update=iters)
         flg, gg, alg, scg = e.get_grad(p, audio, it=0)
     finally:
