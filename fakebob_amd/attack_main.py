@@ -151,6 +151,26 @@ def _pair(text):
         raise argparse.ArgumentTypeError("%r: two numbers joined by a colon" % (text,))
 
 
+def _quorum(text):
+    """--query-eot's value: "majority" or 1 .. 32"""
+    from .query_eot import quorum_code
+    q = text if text == "majority" else int(text)
+    if quorum_code(q) == 0:
+        raise ValueError(text)
+    return q
+
+
+def print_votes(attack, name, flag, res):
+    """--query-eot: the summary of an attack's logged votes (Kenansville's and HopSkipJump's results carry them)"""
+    votes = getattr(res, "votes", None)
+    if votes is None:
+        return
+    v = np.asarray(votes).reshape(-1)
+    v = v[v >= 0]
+    if v.size:
+        print("%s %s: success %d, votes of %d rows: min %d, mean %.2f, max %d" % (attack, name, flag, v.size, v.min(), v.mean(), v.max()))
+
+
 def main(argv=None, model_factory=None, bob_factory=None):
     """model_factory(architecture, task, model_list, pre_model_dir, threshold, group_id) / bob_factory(task,
     attack_type, model, **hyper_parameters): injection points for the driver-rule tests (a stub model / stub FakeBob
@@ -202,6 +222,10 @@ def main(argv=None, model_factory=None, bob_factory=None):
                     help="expectation over transformation against a randomised victim (a 'noise:' / 'at:' stage, --dither): "
                          "every NES sample is scored under this many independent draws and the losses are averaged "
                          "(1 .. 32); default: 1, or FB_EOT_SIZE")
+    ap.add_argument("--query-eot", dest="query_eot", nargs="?", const="majority", default=None, type=_quorum, metavar="Q",
+                    help="--attack pso | kenansville | hsj: take --eot-size and --companions -- every candidate is scored "
+                         "utterances * eot-size times and counts as adversarial from Q adversarial replicas on (its votes; "
+                         "no value: the majority; pso reads the mean loss).  Without this flag the three attacks refuse both")
     ap.add_argument("--companions", dest="companions", default=0, type=int, metavar="N",
                     help="universal perturbation: the next N utterances of the same speaker in the data directory ride along "
                          "with every attacked one (1 .. 31, times --eot-size at most 32); all are cropped to the shortest, "
@@ -278,20 +302,23 @@ def main(argv=None, model_factory=None, bob_factory=None):
     ap.add_argument("--out_dir", default=".")
     ap.add_argument("--dist-backend", default=None)
     args = ap.parse_args(argv)
-    if args.attack == "pso":      # refused here, before any model is built
+    query_attack = args.attack in ("pso", "kenansville", "hsj")
+    if args.query_eot is not None and not query_attack:
+        ap.error("--query-eot belongs to --attack pso, kenansville and hsj (--attack %s)" % args.attack)
+    if args.attack == "pso" and args.query_eot is None:      # refused here, before any model is built
         if args.eot_size is not None and args.eot_size > 1:
             ap.error("--attack pso does not run under expectation over transformation (--eot-size %d)" % args.eot_size)
         if args.companions > 0:
             ap.error("--attack pso does not take companion utterances (--companions %d)" % args.companions)
-    if args.attack == "kenansville":      # likewise
+    if args.attack == "kenansville" and args.query_eot is None:      # likewise
         if args.eot_size is not None and args.eot_size > 1:
             ap.error("--attack kenansville does not run under expectation over transformation (--eot-size %d)" % args.eot_size)
         if args.companions > 0:
             ap.error("--attack kenansville does not take companion utterances (--companions %d)" % args.companions)
     if args.attack == "hsj":      # likewise
-        if args.eot_size is not None and args.eot_size > 1:
+        if args.query_eot is None and args.eot_size is not None and args.eot_size > 1:
             ap.error("--attack hsj does not run under expectation over transformation (--eot-size %d)" % args.eot_size)
-        if args.companions > 0:
+        if args.query_eot is None and args.companions > 0:
             ap.error("--attack hsj does not take companion utterances (--companions %d)" % args.companions)
         if args.hsj_init is None and (args.attack_type == "targeted" or args.task == "SV"):
             ap.error("--attack hsj: a targeted attack needs --hsj-init, an audio the system already decides as the target")
@@ -376,7 +403,9 @@ def main(argv=None, model_factory=None, bob_factory=None):
     for m in models:  # (a stub model of the driver-rule tests has no engine)
         if hasattr(m, "engine") and hasattr(m.engine, "set_dither_seed"):
             m.engine.set_dither_seed(args.dither_seed)
-        if args.eot_size is not None and hasattr(m, "engine") and hasattr(m.engine, "set_eot"):
+        # (under --query-eot the three query attacks set the size themselves, for the length of an attack: the threshold sweep
+        #  runs without)
+        if args.eot_size is not None and not (query_attack and args.query_eot is not None) and hasattr(m, "engine") and hasattr(m.engine, "set_eot"):
             m.engine.set_eot(args.eot_size)
     if K >= 3:  # several engines share the GPU: the separate launches interleave better (fb_set_fused_chain)
         for m in models:
@@ -401,6 +430,8 @@ def main(argv=None, model_factory=None, bob_factory=None):
                   max_iter=args.max_iter)
         if args.hsj_init is not None:
             hsj_init = np.asarray(read(args.hsj_init)[1], np.float64).reshape(-1) / (2 ** (bits_per_sample - 1))
+    if query_attack and args.query_eot is not None:   # (absent otherwise: a bob_factory sees the keywords it always saw)
+        hp.update(eot_size=args.eot_size, quorum=args.query_eot)
     if args.attack == "pgd":
         hp = dict(adver_thresh=args.adver_thresh, epsilon=args.epsilon, max_iter=args.max_iter, max_lr=args.max_lr,
                   min_lr=args.min_lr, momentum=args.momentum, plateau_length=args.plateau_length, plateau_drop=args.plateau_drop)
@@ -492,22 +523,25 @@ def main(argv=None, model_factory=None, bob_factory=None):
             bob._stream = idx + 1         # Philox stream = global attack index: results do not depend on the sharding
             # the reference passes true= only for CSI untargeted (:346) and target= only for targeted attacks (:332,:367)
             true = it["true"] if (task == "CSI" and attack_type == "untargeted") else None
+            extra = dict(init=hsj_init) if args.attack == "hsj" else {}
             if args.companions > 0:
                 audio, comp = with_companions(items, idx, args.companions)
                 if hasattr(bob, "attack_universal"):   # (the PGD classes: PGD.attack keeps FakeBob.attack's plain signature)
                     adv, flag = bob.attack_universal(audio, it["cp_path"], comp, threshold=threshold, true=true, target=it["target"],
                                                      fs=fs, bits_per_sample=bits_per_sample)
                 else:
-                    adv, flag = bob.attack(audio, it["cp_path"], threshold=threshold, true=true, target=it["target"], fs=fs,
-                                           bits_per_sample=bits_per_sample, companions=comp)
+                    res = bob.attack(audio, it["cp_path"], threshold=threshold, true=true, target=it["target"], fs=fs,
+                                     bits_per_sample=bits_per_sample, companions=comp, **extra)
+                    adv, flag = res
+                    print_votes(args.attack, it["name"], flag, res)
                 write(it["wav_path"], fs, adv)
                 with lock:
                     results[idx] = flag
                 continue
-            extra = dict(init=hsj_init) if args.attack == "hsj" else {}
             res = bob.attack(it["audio"], it["cp_path"], threshold=threshold, true=true,
                              target=it["target"], fs=fs, bits_per_sample=bits_per_sample, **extra)
             adv, flag = res
+            print_votes(args.attack, it["name"], flag, res)
             if args.attack == "psy" and hasattr(res, "best_dist"):
                 print("psy %s: success %d, dist %.6g, over %d, l2 %.6g, snr %.2f dB, c %.3g" %
                       (it["name"], flag, res.best_dist, res.n_over, res.best_l2, res.snr_db, res.const))

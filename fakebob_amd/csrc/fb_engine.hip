@@ -122,6 +122,8 @@ struct fb_engine {
   DevBuf tf_power;              // k_tf_power's per-utterance sums of squares (chains with an SNR stage)
   int eot = 1;                  // fb_set_eot: replicas of every NES row (1: none)
   DevBuf eot_sc, eot_l;         // k_loss_eot's per-replica scores [B * r][S] and losses [B * r]
+  int query_quorum = FB_QUORUM_OFF;  // fb_set_query_eot: 0 off | -1 majority | 1 .. 32
+  DevBuf vote_look;             // k_vote's look block {votes[rows], nodec[rows], mean[rows][S]}
   // over-the-air channel (fb_set_air_channel; its contract is in fakebob_hip.h): air.L == 0 -- none
   FbAir air = {};               // the setting (the key fields are filled per launch: fb_air_key)
   DevBuf wav_air;               // the channel's output, in the replicated layout: what the chain -- or, without one, the MFCC -- reads
@@ -3491,6 +3493,50 @@ extern "C" int fb_attack_iter_seconds(fb_engine *e, double *seconds, int n) {
 // scores it, k_loss forms loss[P] and scores[P][S], the host reads them once per iteration, decides the personal and global
 // bests and the stop, and k_pso_step moves the swarm -- taking the best-copies and the next batch's int16 cast along.
 // The fused finalisation, the i-vector tail-loss shortcut and the device control block are not used.
+// Under fb_set_query_eot with R = K * eot > 1 replicas the batch of the three query attacks is the replicated one of fb_attack
+// (prepare_nes_replicas, call.eot, call.K): PSO then reads k_loss_eot's means, the two decision-only attacks k_vote's look block.
+// What fb_set_eot and fb_set_companions mean to the three query attacks (`who`: the public call).  Switch off
+// (fb_set_query_eot): both are refused.  On: *r = K * eot replicas of every candidate row and *quorum = the adversarial
+// replicas a row needs (majority: r / 2 + 1); an explicit quorum no row can reach is refused here, before anything runs.
+static int query_replicas(const fb_engine *e, const char *who, int *r, int *quorum) {
+  *r = 1;
+  *quorum = 1;
+  if (e->query_quorum == FB_QUORUM_OFF) {
+    if (e->eot > 1)
+      return fb_fail(FB_E_STATE, "%s does not run under expectation over transformation (fb_set_eot(%d)): set 1", who, e->eot);
+    if (e->comp_K1 > 0)
+      return fb_fail(FB_E_STATE, "%s does not run with companion utterances (fb_set_companions: %d set): clear them", who, e->comp_K1);
+    return FB_OK;
+  }
+  *r = nes_replicas(e);
+  *quorum = e->query_quorum == FB_QUORUM_MAJORITY ? *r / 2 + 1 : e->query_quorum;
+  if (*quorum > *r)
+    return fb_fail(FB_E_ARG, "quorum %d (fb_set_query_eot) with utterances * eot = %d replicas per row: no row can reach it", *quorum, *r);
+  return FB_OK;
+}
+// k_vote's look block for `rows` candidate rows of S scores on the device (e->vote_look) and on the host: votes[rows],
+// nodec[rows] (int32), mean[rows][S] (float64), contiguous
+struct FbVoteLook {
+  int *votes, *nodec;
+  double *mean;
+  size_t bytes;
+};
+static size_t vote_look_bytes(int rows, int S) { return sizeof(int) * 2 * (size_t)rows + sizeof(double) * (size_t)rows * S; }
+static FbVoteLook vote_look_at(void *base, int rows, int S) {
+  FbVoteLook v;
+  v.votes = static_cast<int *>(base);
+  v.nodec = v.votes + rows;
+  v.mean = reinterpret_cast<double *>(v.nodec + rows);
+  v.bytes = vote_look_bytes(rows, S);
+  return v;
+}
+// the launch behind the replicated scoring path of rows * r rows: e->raw, e->tv -> e->vote_look
+static void launch_vote(fb_engine *e, const fb_nes_params *p, int rows, int r, bool targeted, int label) {
+  const FbVoteLook v = vote_look_at(e->vote_look.p, rows, fb_num_speakers(e));
+  fb_launch_vote(e->stream, e->raw.as<double>(), e->tv.as<int>(), rows, r, e->n_out, p->task, e->kind, e->zmean.as<double>(),
+                 e->zstd.as<double>(), p->threshold, targeted ? 1 : 0, label, e->eot_sc.as<double>(), v.votes, v.nodec, v.mean);
+}
+
 static int check_pso_swarm(int P, double eps, double v_max, int bits) {
   if (P < 2 || P > FB_PSO_MAX_PARTICLES) return fb_fail(FB_E_ARG, "particles %d outside 2 .. %d", P, FB_PSO_MAX_PARTICLES);
   if (!isfinite(eps) || !(eps > 0.0)) return fb_fail(FB_E_ARG, "epsilon must be finite and > 0");
@@ -3512,10 +3558,8 @@ extern "C" int fb_attack_pso(fb_engine *e, const fb_nes_params *p, const fb_pso_
   if (e) e->bench_it = e->nes_rec.iter = -1;
   if (!e || !p || !q || !audio || !adv_i16 || !success || !n_iters || !trace || !losses) return fb_fail(FB_E_ARG, "null argument");
   if (!e->have_gmm) return fb_fail(FB_E_STATE, "no model loaded");
-  if (e->eot > 1)
-    return fb_fail(FB_E_STATE, "fb_attack_pso does not run under expectation over transformation (fb_set_eot(%d)): set 1", e->eot);
-  if (e->comp_K1 > 0)
-    return fb_fail(FB_E_STATE, "fb_attack_pso does not run with companion utterances (fb_set_companions: %d set): clear them", e->comp_K1);
+  int R = 1, quorum = 1;   // replicas of every particle (fb_set_query_eot; the quorum is the decision-only attacks')
+  FBCHK(query_replicas(e, "fb_attack_pso", &R, &quorum));
   const int P = q->particles, bits = nes_bits(p);
   FBCHK(check_pso_swarm(P, p->epsilon, q->v_max, bits));
   for (double c : {q->w_init, q->w_end, q->c1, q->c2})
@@ -3527,7 +3571,8 @@ extern "C" int fb_attack_pso(fb_engine *e, const fb_nes_params *p, const fb_pso_
   FBCHK(check_goal_params(p, S));
   if (num_frames(e->cfg, N) <= 0) return fb_fail(FB_E_ARG, "audio shorter than one frame");
   HIPCHK(hipSetDevice(e->device));
-  FBCHK(prepare_nes_batch(e, N, P));
+  if (R > 1) FBCHK(prepare_nes_replicas(e, N, P));
+  else FBCHK(prepare_nes_batch(e, N, P));
   FBCHK(ensure_pso_buffers(e, N, P));
   // what the host reads once per iteration, in one block: k_loss's result block (for its "no voiced frames" word), loss[P],
   // scores[P][S]
@@ -3541,6 +3586,7 @@ extern "C" int fb_attack_pso(fb_engine *e, const fb_nes_params *p, const fb_pso_
 
   double *x = e->pso_x.as<double>(), *gb = e->pso_gb.as<double>();
   FBCHK(h2d(e, e->audio.p, audio, sizeof(double) * (size_t)N));
+  if (R > 1) cast_a0(e, p, e->audio.as<double>(), N);
   fb_launch_pso_init(e->stream, e->audio.as<double>(), N, P, p->epsilon, q->v_max, p->seed, p->stream, bits, x,
                      e->pso_v.as<double>(), e->wav.as<int16_t>());
   std::vector<double> look(look_d), pl((size_t)P, 0.0);
@@ -3550,10 +3596,20 @@ extern "C" int fb_attack_pso(fb_engine *e, const fb_nes_params *p, const fb_pso_
   auto t_prev = std::chrono::steady_clock::now();
   for (;; ++k) {
     FbScoreCall call{FbRngPoint{p->seed, p->stream, (uint32_t)k, 0}};
-    FBCHK(run_scoring(e, call, P, e->h_frame_off[P]));
-    fb_launch_loss(e->stream, e->raw.as<double>(), e->tv.as<int>(), P, e->n_out, p->task, e->kind, p->attack_type,
-                   e->zmean.as<double>(), e->zstd.as<double>(), p->threshold, p->adver_thresh, p->target, p->true_label,
-                   nullptr, 0, scores_dev, loss_dev, out_dev);
+    if (R > 1) {   // every particle under R replicas: l_p and its score row are fb_set_eot's means (k_loss_eot)
+      call.eot = e->eot;
+      call.K = e->comp_K1 + 1;
+      FBCHK(run_scoring(e, call, P * R, e->h_frame_off[P * R]));
+      fb_launch_loss_eot(e->stream, e->raw.as<double>(), e->tv.as<int>(), P, R, e->n_out, p->task, e->kind, p->attack_type,
+                         e->zmean.as<double>(), e->zstd.as<double>(), p->threshold, p->adver_thresh, p->target, p->true_label,
+                         nullptr, 0, e->eot_sc.as<double>(), e->eot_l.as<double>(), scores_dev, loss_dev, out_dev, nullptr,
+                         nullptr, 0);
+    } else {
+      FBCHK(run_scoring(e, call, P, e->h_frame_off[P]));
+      fb_launch_loss(e->stream, e->raw.as<double>(), e->tv.as<int>(), P, e->n_out, p->task, e->kind, p->attack_type,
+                     e->zmean.as<double>(), e->zstd.as<double>(), p->threshold, p->adver_thresh, p->target, p->true_label,
+                     nullptr, 0, scores_dev, loss_dev, out_dev);
+    }
     // the one look of the iteration: one copy through pinned memory, one synchronisation
     FBCHK(d2h(e, look.data(), e->pso_look.p, sizeof(double) * look_d));
     FBCHK(sync_stream(e));
@@ -3706,10 +3762,8 @@ extern "C" int fb_attack_kenansville(fb_engine *e, const fb_nes_params *p, const
   if (!e || !p || !k || !audio || !adv_i16 || !success || !factor || !n_queries || !n_rounds || !qs || !decisions || !scores || !trace)
     return fb_fail(FB_E_ARG, "null argument");
   if (!e->have_gmm) return fb_fail(FB_E_STATE, "no model loaded");
-  if (e->eot > 1)
-    return fb_fail(FB_E_STATE, "fb_attack_kenansville does not run under expectation over transformation (fb_set_eot(%d)): set 1", e->eot);
-  if (e->comp_K1 > 0)
-    return fb_fail(FB_E_STATE, "fb_attack_kenansville does not run with companion utterances (fb_set_companions: %d set): clear them", e->comp_K1);
+  int R = 1, quorum = 1;   // replicas of every candidate row and the votes a row needs (fb_set_query_eot)
+  FBCHK(query_replicas(e, "fb_attack_kenansville", &R, &quorum));
   const int W = k->window, G = k->grid, bits = nes_bits(p);
   FBCHK(check_kv_tables(W, tables));
   if (G < 1 || G > FB_KV_MAX_ROWS) return fb_fail(FB_E_ARG, "grid %d outside 1 .. %d", G, FB_KV_MAX_ROWS);
@@ -3740,13 +3794,18 @@ extern "C" int fb_attack_kenansville(fb_engine *e, const fb_nes_params *p, const
   FbNesDev *out_dev = e->kv_look.as<FbNesDev>();
   double *loss_dev = e->kv_look.as<double>() + out_d, *scores_dev = e->kv_look.as<double>() + sc_d;
   int *tv_dev = reinterpret_cast<int *>(e->kv_look.as<double>() + tv_d);
+  if (R > 1) {   // the replicated batch of a full round and k_vote's look block in place of k_loss's
+    FBCHK(prepare_nes_replicas(e, N, G));
+    FBCHK(e->vote_look.ensure(vote_look_bytes(G, S)));
+  }
   FBCHK(launch_state_reset(e));
   e->iter_seconds.clear();
 
   FBCHK(h2d(e, e->audio.p, audio, sizeof(double) * (size_t)N));
   fb_launch_quantize(e->stream, e->audio.as<double>(), N, bits, e->kv_x.as<int16_t>());
+  if (R > 1) cast_a0(e, p, e->audio.as<double>(), N);   // (a_0 = x)
   launch_kv_analyse(e, N, W);
-  std::vector<double> look(look_d);
+  std::vector<double> look(std::max(look_d, vote_look_bytes(G, S) / sizeof(double)));
   const double *sc = look.data() + sc_d;
   std::vector<int> cand;
   cand.reserve(G);
@@ -3772,38 +3831,55 @@ extern "C" int fb_attack_kenansville(fb_engine *e, const fb_nes_params *p, const
       }
     }
     const int rows = (int)cand.size();
-    FBCHK(prepare_nes_batch(e, N, rows));
+    if (R > 1) FBCHK(prepare_nes_replicas(e, N, rows));
+    else FBCHK(prepare_nes_batch(e, N, rows));
     launch_kv_candidates(e, N, W, rows, cand.data(), e->wav.as<int16_t>());
     FbScoreCall call{FbRngPoint{p->seed, p->stream, (uint32_t)r, 0}};
-    FBCHK(run_scoring(e, call, rows, e->h_frame_off[rows]));
-    // (k_loss is here for the system scores of fb_loss_row alone: its loss and its labels are not this attack's)
-    fb_launch_loss(e->stream, e->raw.as<double>(), e->tv.as<int>(), rows, e->n_out, p->task, e->kind, FB_UNTARGETED,
-                   e->zmean.as<double>(), e->zstd.as<double>(), p->threshold, 0.0, 0, 0, nullptr, 0, scores_dev, loss_dev, out_dev);
-    HIPCHK(hipMemcpyAsync(tv_dev, e->tv.p, sizeof(int) * (size_t)rows, hipMemcpyDeviceToDevice, e->stream));
-    // the one look of the round: one copy through pinned memory, one synchronisation
-    FBCHK(d2h(e, look.data(), e->kv_look.p, sizeof(double) * look_d));
-    FBCHK(sync_stream(e));
-    const int *tv = reinterpret_cast<const int *>(look.data() + tv_d);
     int first = -1;   // the smallest succeeding candidate's row
     for (int j = 0; j < G; ++j) qs[(size_t)r * G + j] = j < rows ? cand[j] : -1;
-    for (int j = 0; j < rows; ++j) {
-      const double *s = sc + (size_t)j * S;
-      for (int m = 0; m < S; ++m) scores[((size_t)r * G + j) * S + m] = s[m];
-      int d;
-      if (tv[j] <= 0) {
-        d = -2;   // no voiced frames: no decision
-      } else if (p->task == FB_TASK_SV) {
-        d = s[0] >= p->threshold ? 1 : -1;
-      } else {
-        int am = 0;
-        for (int m = 1; m < S; ++m) if (s[m] > s[am]) am = m;   // the first maximum
-        d = (p->task == FB_TASK_OSI && s[am] < p->threshold) ? -1 : am;
+    if (R > 1) {
+      call.eot = e->eot;
+      call.K = e->comp_K1 + 1;
+      FBCHK(run_scoring(e, call, rows * R, e->h_frame_off[rows * R]));
+      launch_vote(e, p, rows, R, targeted, label);
+      // the one look of the round: the votes and the mean scores, nothing per replica
+      const FbVoteLook v = vote_look_at(look.data(), rows, S);
+      FBCHK(d2h(e, look.data(), e->vote_look.p, v.bytes));
+      FBCHK(sync_stream(e));
+      for (int j = 0; j < rows; ++j) {
+        for (int m = 0; m < S; ++m) scores[((size_t)r * G + j) * S + m] = v.mean[(size_t)j * S + m];
+        decisions[(size_t)r * G + j] = v.votes[j];   // the row's vote
+        if (v.votes[j] >= quorum && first < 0) first = j;
       }
-      decisions[(size_t)r * G + j] = d;
-      const bool ok = d != -2 && (targeted ? d == label : d != label);
-      if (ok && first < 0) first = j;
+    } else {
+      FBCHK(run_scoring(e, call, rows, e->h_frame_off[rows]));
+      // (k_loss is here for the system scores of fb_loss_row alone: its loss and its labels are not this attack's)
+      fb_launch_loss(e->stream, e->raw.as<double>(), e->tv.as<int>(), rows, e->n_out, p->task, e->kind, FB_UNTARGETED,
+                     e->zmean.as<double>(), e->zstd.as<double>(), p->threshold, 0.0, 0, 0, nullptr, 0, scores_dev, loss_dev, out_dev);
+      HIPCHK(hipMemcpyAsync(tv_dev, e->tv.p, sizeof(int) * (size_t)rows, hipMemcpyDeviceToDevice, e->stream));
+      // the one look of the round: one copy through pinned memory, one synchronisation
+      FBCHK(d2h(e, look.data(), e->kv_look.p, sizeof(double) * look_d));
+      FBCHK(sync_stream(e));
+      const int *tv = reinterpret_cast<const int *>(look.data() + tv_d);
+      for (int j = 0; j < rows; ++j) {
+        const double *s = sc + (size_t)j * S;
+        for (int m = 0; m < S; ++m) scores[((size_t)r * G + j) * S + m] = s[m];
+        int d;
+        if (tv[j] <= 0) {
+          d = -2;   // no voiced frames: no decision
+        } else if (p->task == FB_TASK_SV) {
+          d = s[0] >= p->threshold ? 1 : -1;
+        } else {
+          int am = 0;
+          for (int m = 1; m < S; ++m) if (s[m] > s[am]) am = m;   // the first maximum
+          d = (p->task == FB_TASK_OSI && s[am] < p->threshold) ? -1 : am;
+        }
+        decisions[(size_t)r * G + j] = d;
+        const bool ok = d != -2 && (targeted ? d == label : d != label);
+        if (ok && first < 0) first = j;
+      }
     }
-    queries += rows;
+    queries += rows * R;
     if (first >= 0) {
       hi = cand[first];
       // the candidate of hi is a row that was scored: kept before the next round's batch takes its place
@@ -3813,7 +3889,7 @@ extern "C" int fb_attack_kenansville(fb_engine *e, const fb_nes_params *p, const
     } else if (hi >= 0 && rows > 0) {
       lo = cand[rows - 1];
     }
-    trace[3 * r] = lo; trace[3 * r + 1] = hi; trace[3 * r + 2] = rows;
+    trace[3 * r] = lo; trace[3 * r + 1] = hi; trace[3 * r + 2] = rows * R;
     const auto t_now = std::chrono::steady_clock::now();
     e->iter_seconds.push_back(std::chrono::duration<double>(t_now - t_prev).count());
     t_prev = t_now;
@@ -3975,10 +4051,8 @@ extern "C" int fb_attack_hsj(fb_engine *e, const fb_nes_params *p, const fb_hsj_
     return fb_fail(FB_E_ARG, "null argument");
   if (!init) return fb_fail(FB_E_ARG, "null init: HopSkipJump starts from an audio that is already decided as wanted");
   if (!e->have_gmm) return fb_fail(FB_E_STATE, "no model loaded");
-  if (e->eot > 1)
-    return fb_fail(FB_E_STATE, "fb_attack_hsj does not run under expectation over transformation (fb_set_eot(%d)): set 1", e->eot);
-  if (e->comp_K1 > 0)
-    return fb_fail(FB_E_STATE, "fb_attack_hsj does not run with companion utterances (fb_set_companions: %d set): clear them", e->comp_K1);
+  int R = 1, quorum = 1;   // replicas of every candidate row and the votes a row needs (fb_set_query_eot)
+  FBCHK(query_replicas(e, "fb_attack_hsj", &R, &quorum));
   FBCHK(check_hsj_params(k));
   const int G = k->grid, bits = nes_bits(p);
   if (p->max_iter < 0) return fb_fail(FB_E_ARG, "max_iter %d < 0", p->max_iter);
@@ -4001,6 +4075,13 @@ extern "C" int fb_attack_hsj(fb_engine *e, const fb_nes_params *p, const fb_hsj_
     return fb_fail(FB_E_ARG, "the decision log holds %lld entries, this call may score %lld rows", decisions_cap, need);
   HIPCHK(hipSetDevice(e->device));
   const int max_rows = std::max(G, k->num_evals_max);
+  if (R > 1) {   // the largest replicated batch, checked before anything is scored; k_vote's look block
+    if ((int64_t)max_rows * R > 65535)
+      return fb_fail(FB_E_LIMIT, "max(grid, num_evals_max) * utterances * eot = %lld rows: a scoring batch takes up to 65535",
+                     (long long)max_rows * R);
+    FBCHK(prepare_nes_replicas(e, N, max_rows));
+    FBCHK(e->vote_look.ensure(vote_look_bytes(max_rows, S)));
+  }
   FBCHK(prepare_hsj(e, N, max_rows));
   // the probes launch keeps its normals as float32 [B][N] for the direction launch: at B = 1024, N = 48 000 the pair takes
   // 160 us so against 206 us with the direction launch drawing them again (tools/hsj_rate.py)
@@ -4019,16 +4100,35 @@ extern "C" int fb_attack_hsj(fb_engine *e, const fb_nes_params *p, const fb_hsj_
   const double *a_dev = e->audio.as<double>();
   FBCHK(h2d(e, e->audio.p, audio, sizeof(double) * (size_t)N));
   FBCHK(h2d(e, e->hsj_init.p, init, sizeof(double) * (size_t)N));
-  std::vector<double> look(look_d);
+  if (R > 1) cast_a0(e, p, a_dev, N);
+  std::vector<double> look(std::max(look_d, vote_look_bytes(max_rows, S) / sizeof(double)));
   std::vector<int> dec(max_rows), cand;
   cand.reserve(G);
-  int queries = 0;
+  int queries = 0, logged = 0;   // victim queries (candidate rows * R) and entries of the decision log (candidate rows)
   uint32_t epoch = 0;
   bool stopped = false;   // max_queries: nothing is scored any more
-  auto over = [&](int rows) { return k->max_queries > 0 && (long long)queries + rows > k->max_queries; };
+  auto over = [&](int rows) { return k->max_queries > 0 && (long long)queries + (long long)rows * R > k->max_queries; };
+  // the batch layout of `rows` candidate rows (under R replicas: of rows * R)
+  auto layout = [&](int rows) -> int { return R > 1 ? prepare_nes_replicas(e, N, rows) : prepare_nes_batch(e, N, rows); };
   // scores the `rows` rows that stand in e->wav: dec[0 .. rows) and the log; one look
   auto score = [&](int rows) -> int {
     FbScoreCall call{FbRngPoint{p->seed, p->stream, epoch++, 0}};
+    if (R > 1) {   // R replicas of every row: the log holds the votes, a row is adversarial from `quorum` votes on
+      call.eot = e->eot;
+      call.K = e->comp_K1 + 1;
+      FBCHK(run_scoring(e, call, rows * R, e->h_frame_off[rows * R]));
+      launch_vote(e, p, rows, R, targeted, label);
+      const FbVoteLook v = vote_look_at(look.data(), rows, S);
+      FBCHK(d2h(e, look.data(), e->vote_look.p, v.bytes));
+      FBCHK(sync_stream(e));
+      for (int j = 0; j < rows; ++j) {
+        decisions[logged + j] = v.votes[j];
+        dec[j] = v.votes[j] >= quorum ? 1 : 0;
+      }
+      logged += rows;
+      queries += rows * R;
+      return FB_OK;
+    }
     FBCHK(run_scoring(e, call, rows, e->h_frame_off[rows]));
     // (k_loss is here for the system scores of fb_loss_row alone: its loss and its labels are not this attack's)
     fb_launch_loss(e->stream, e->raw.as<double>(), e->tv.as<int>(), rows, e->n_out, p->task, e->kind, FB_UNTARGETED,
@@ -4050,9 +4150,10 @@ extern "C" int fb_attack_hsj(fb_engine *e, const fb_nes_params *p, const fb_hsj_
         for (int m = 1; m < S; ++m) if (s[m] > s[am]) am = m;   // the first maximum
         d = (p->task == FB_TASK_OSI && s[am] < p->threshold) ? -1 : am;
       }
-      decisions[queries + j] = d;
+      decisions[logged + j] = d;
       dec[j] = (d != -2 && (targeted ? d == label : d != label)) ? 1 : 0;
     }
+    logged += rows;
     queries += rows;
     return FB_OK;
   };
@@ -4075,7 +4176,7 @@ extern "C" int fb_attack_hsj(fb_engine *e, const fb_nes_params *p, const fb_hsj_
       }
       const int rows = (int)cand.size();
       if (!(r == 0 && first_exempt) && over(rows)) { stopped = true; break; }
-      FBCHK(prepare_nes_batch(e, N, rows));
+      FBCHK(layout(rows));
       fb_launch_hsj_line(e->stream, a_dev, y_dev, N, rows, cand.data(), bits, e->wav.as<int16_t>());
       FBCHK(score(rows));
       rounds = r + 1;
@@ -4146,7 +4247,7 @@ extern "C" int fb_attack_hsj(fb_engine *e, const fb_nes_params *p, const fb_hsj_
     const int B = hsj_evals(k, t);
     if (over(B)) break;
     const double s0 = (k->probe_scale * dist) / std::sqrt((double)N), sigma = s0 > k->sigma_min ? s0 : k->sigma_min;
-    FBCHK(prepare_nes_batch(e, N, B));
+    FBCHK(layout(B));
     fb_launch_hsj_probes(e->stream, e->hsj_x.as<double>(), N, B, sigma, p->seed, p->stream, (uint32_t)t, bits,
                          e->wav.as<int16_t>(), e->hsj_z.as<float>());
     FBCHK(score(B));
@@ -4163,7 +4264,7 @@ extern "C" int fb_attack_hsj(fb_engine *e, const fb_nes_params *p, const fb_hsj_
     // 3 step
     if (over(G)) break;
     const double xi = dist / std::sqrt((double)t);
-    FBCHK(prepare_nes_batch(e, N, G));
+    FBCHK(layout(G));
     fb_launch_hsj_step(e->stream, e->hsj_x.as<double>(), e->hsj_v.as<double>(), e->hsj_sc.as<double>() + 1, xi, 0, G, N, bits,
                        e->wav.as<int16_t>(), nullptr);
     FBCHK(score(G));
@@ -4345,6 +4446,69 @@ extern "C" int fb_bench_hsj_kernels(fb_engine *e, const double *a, const double 
     HIPCHK(hipEventElapsedTime(&t, e->ev0, e->ev1));
     ms[which] = (double)t / reps;
   }
+  FBCHK(sync_stream(e));
+  HIPCHK(hipGetLastError());
+  return FB_OK;
+}
+
+// ---- voted decisions: k_vote alone, on raw scores handed in (fakebob_hip_test.h)
+// the checks and uploads of both hooks: raw[rows * r][n_out] -> e->raw, tv[rows * r] -> e->tv; the label by the attacks' rule
+static int stage_vote(fb_engine *e, const double *raw, const int *tv, int rows, int r, int task, int attack_type, int label) {
+  if (!e || !raw || !tv) return fb_fail(FB_E_ARG, "null argument");
+  if (!e->have_gmm) return fb_fail(FB_E_STATE, "no model loaded");
+  if (task != e->task) return fb_fail(FB_E_ARG, "task %d != engine system task %d", task, e->task);
+  if (attack_type != FB_TARGETED && attack_type != FB_UNTARGETED) return fb_fail(FB_E_ARG, "bad attack_type %d", attack_type);
+  if (r < 1 || r > 32) return fb_fail(FB_E_ARG, "%d replicas per row: 1 .. 32", r);
+  if (rows < 1 || (int64_t)rows * r > 65535) return fb_fail(FB_E_LIMIT, "rows %d * replicas %d outside 1 .. 65535", rows, r);
+  const int S = fb_num_speakers(e);
+  const bool ok = task == FB_TASK_SV ? (label == 1 || label == -1) : task == FB_TASK_OSI ? (label >= -1 && label < S) : (label >= 0 && label < S);
+  if (!ok) return fb_fail(FB_E_ARG, "label %d is no decision of this system", label);
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  const size_t n = (size_t)rows * r;
+  FBCHK(e->raw.ensure(sizeof(double) * n * e->n_out));
+  FBCHK(e->tv.ensure(sizeof(int) * n));
+  FBCHK(e->eot_sc.ensure(sizeof(double) * n * (size_t)std::max(S, 1)));
+  FBCHK(e->vote_look.ensure(vote_look_bytes(rows, S)));
+  FBCHK(h2d(e, e->raw.p, raw, sizeof(double) * n * e->n_out));
+  FBCHK(h2d(e, e->tv.p, tv, sizeof(int) * n));
+  return FB_OK;
+}
+extern "C" int fb_debug_vote(fb_engine *e, const double *raw, const int *tv, int rows, int r, int task, double threshold,
+                             int attack_type, int label, int *votes, int *nodec, double *mean) {
+  if (!votes || !nodec || !mean) return fb_fail(FB_E_ARG, "null argument");
+  FBCHK(stage_vote(e, raw, tv, rows, r, task, attack_type, label));
+  fb_nes_params p = {};
+  p.task = task;
+  p.threshold = threshold;
+  launch_vote(e, &p, rows, r, attack_type == FB_TARGETED, label);
+  const int S = fb_num_speakers(e);
+  std::vector<double> look(vote_look_bytes(rows, S) / sizeof(double));
+  const FbVoteLook v = vote_look_at(look.data(), rows, S);
+  FBCHK(d2h(e, look.data(), e->vote_look.p, v.bytes));
+  FBCHK(sync_stream(e));
+  HIPCHK(hipGetLastError());
+  memcpy(votes, v.votes, sizeof(int) * (size_t)rows);
+  memcpy(nodec, v.nodec, sizeof(int) * (size_t)rows);
+  memcpy(mean, v.mean, sizeof(double) * (size_t)rows * S);
+  return FB_OK;
+}
+// tools/query_eot_rate.py: `reps` launches of k_vote between two events, after one to warm up -> *ms per launch
+extern "C" int fb_bench_vote(fb_engine *e, const double *raw, const int *tv, int rows, int r, int task, double threshold,
+                             int attack_type, int label, int reps, double *ms) {
+  if (!ms || reps < 1) return fb_fail(FB_E_ARG, "bad argument");
+  FBCHK(stage_vote(e, raw, tv, rows, r, task, attack_type, label));
+  fb_nes_params p = {};
+  p.task = task;
+  p.threshold = threshold;
+  launch_vote(e, &p, rows, r, attack_type == FB_TARGETED, label);
+  HIPCHK(hipEventRecord(e->ev0, e->stream));
+  for (int i = 0; i < reps; ++i) launch_vote(e, &p, rows, r, attack_type == FB_TARGETED, label);
+  HIPCHK(hipEventRecord(e->ev1, e->stream));
+  HIPCHK(hipEventSynchronize(e->ev1));
+  float t = 0.f;
+  HIPCHK(hipEventElapsedTime(&t, e->ev0, e->ev1));
+  *ms = (double)t / reps;
   FBCHK(sync_stream(e));
   HIPCHK(hipGetLastError());
   return FB_OK;
@@ -4842,6 +5006,15 @@ extern "C" int fb_set_eot(fb_engine *e, int r) {
     return fb_fail(FB_E_ARG, "EOT size %d with %d utterances (fb_set_companions): utterances * eot is at most 32", r, e->comp_K1 + 1);
   e->eot = r;
   e->bench_it = e->nes_rec.iter = -1;  // an attack fb_bench_nes left resident was laid out for the previous size
+  return FB_OK;
+}
+
+// ---- voted decisions: fb_attack_pso / _kenansville / _hsj under EOT and companions
+extern "C" int fb_set_query_eot(fb_engine *e, int quorum) {
+  if (!e) return fb_fail(FB_E_ARG, "null engine");
+  if (quorum != FB_QUORUM_OFF && quorum != FB_QUORUM_MAJORITY && (quorum < 1 || quorum > 32))
+    return fb_fail(FB_E_ARG, "quorum %d: 0 (off), -1 (majority) or 1 .. 32", quorum);
+  e->query_quorum = quorum;
   return FB_OK;
 }
 

@@ -297,6 +297,12 @@ void fb_launch_loss_eot(hipStream_t s, const double *raw, const int *tv, int B, 
                         double adver_thresh, int target, int true_label, const double *dist_part, int n_dist_part,
                         double *rep_sc, double *rep_l, double *scores, double *loss, FbNesDev *out, FbCtlDev *ctl,
                         double *trace, int it);
+// the voted decision of rows scored r times (fb_set_query_eot; k_vote): raw[rows * r][M] and tv[rows * r] of the replicated
+// batch -> per-replica scores rep_sc[rows * r][S] by the operations of k_loss, and the look block: votes[rows] (adversarial
+// replicas), nodec[rows] (replicas without voiced frames), mean[rows][S] (k_loss_eot's means).  label: a decision value
+void fb_launch_vote(hipStream_t s, const double *raw, const int *tv, int rows, int r, int M, int task, int znorm_all,
+                    const double *z_mean, const double *z_std, double threshold, int targeted, int label, double *rep_sc,
+                    int *votes, int *nodec, double *mean);
 // k_grad_update (iteration `next_iter - 1`) + k_perturb (iteration next_iter) in one launch; device-controlled attacks
 // with Philox noise and half <= FB_FUSE_MAX_HALF only.  Returns the number of distance partials written.
 // threads: 256 or 512 per workgroup of 256 samples (the same bits either way; nes_kernels.hip says which when)

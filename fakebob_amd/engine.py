@@ -96,6 +96,7 @@ class Engine(object):
         self.wb_frontend = False
         self.wb_universal = False
         self.companions = None
+        self.query_eot = None
         self.feature_compression = None
 
     def close(self):
@@ -250,6 +251,53 @@ class Engine(object):
             raise ValueError("%d utterances under eot %d: utterances * eot is at most %d" % (arr.shape[0] + 1, self.eot, MAX_REPLICAS))
         N.check(self._L.fb_set_companions(self._h, N.ptr(arr), C.c_int(arr.shape[0]), C.c_int64(arr.shape[1])))
         self.companions = arr
+
+    def set_query_eot(self, quorum):
+        """Voted decisions (fb_set_query_eot): with a quorum set attack_pso, attack_kenansville and attack_hsj accept
+        set_eot(r) and companions -- every candidate row is scored r' = K * eot times, PSO reads the mean loss, the two
+        decision-only attacks the number of adversarial replicas (the row's vote) against the quorum.  None (the default)
+        switches it off: the three attacks refuse EOT and companions.  "majority" (or -1): r' // 2 + 1 votes; 1 .. 32: that
+        many (larger than r' is refused at the attack call)."""
+        from .query_eot import quorum_code
+        q = quorum_code(quorum)
+        N.check(self._L.fb_set_query_eot(self._h, C.c_int(q)))
+        self.query_eot = None if q == 0 else ("majority" if q == -1 else q)
+
+    @property
+    def query_replicas(self):
+        """r' of the three query attacks: K * eot replicas of every candidate row under set_query_eot, else 1"""
+        if self.query_eot is None:
+            return 1
+        return (1 + (0 if self.companions is None else self.companions.shape[0])) * self.eot
+
+    def _vote_args(self, raw, tv, task, attack_type, label):
+        raw = np.ascontiguousarray(raw, np.float64)
+        if raw.ndim != 3:
+            raise ValueError("raw must be (rows, replicas, n_out)")
+        rows, r, _m = raw.shape
+        tv = np.ascontiguousarray(tv, np.int32).reshape(-1)
+        if tv.size != rows * r:
+            raise ValueError("tv must hold rows * replicas entries")
+        S = max(self.n_speakers, 1)
+        head = (self._h, N.ptr(raw), N.ptr(tv), C.c_int(rows), C.c_int(r), C.c_int(N.TASK[task]))
+        tail = (C.c_int(N.ATTACK[attack_type]), C.c_int(int(label)))
+        return raw, tv, rows, S, head, tail
+
+    def debug_vote(self, raw, tv, task, threshold, attack_type, label):
+        """k_vote alone (fb_debug_vote) on raw scores (rows, replicas, n_out) of the loaded system and tv (rows * replicas)
+        -> votes (rows,), nodec (rows,) int32 and mean (rows, S) float64."""
+        raw, tv, rows, S, head, tail = self._vote_args(raw, tv, task, attack_type, label)
+        votes, nodec = np.empty(rows, np.int32), np.empty(rows, np.int32)
+        mean = np.empty((rows, S), np.float64)
+        N.check(self._L.fb_debug_vote(*head, C.c_double(float(threshold)), *tail, N.ptr(votes), N.ptr(nodec), N.ptr(mean)))
+        return votes, nodec, mean
+
+    def bench_vote(self, raw, tv, task, threshold, attack_type, label, reps=50):
+        """Milliseconds per k_vote launch (fb_bench_vote: device events around `reps` launches)."""
+        raw, tv, rows, S, head, tail = self._vote_args(raw, tv, task, attack_type, label)
+        ms = C.c_double()
+        N.check(self._L.fb_bench_vote(*head, C.c_double(float(threshold)), *tail, C.c_int(int(reps)), C.byref(ms)))
+        return ms.value
 
     def debug_compose(self, q, a0, r, seed, stream, epoch):
         """The int16 rows the composing launch writes (fb_debug_compose) for the hand-made NES rows q (B, N) and the cast
@@ -1046,8 +1094,10 @@ class Engine(object):
                                       C.c_int64(n), N.ptr(adv), N.ptr(adv_f), C.byref(flag), C.byref(d2), C.byref(ni),
                                       C.byref(nq), N.ptr(trace), N.ptr(dec), C.c_longlong(dec.size if cap >= 0 else -1),
                                       N.ptr(xs) if keep_x else None))
+        # (one log entry per candidate row; n_queries counts victim queries: under voted decisions r' = K * eot per row)
+        n_log = nq.value // self.query_replicas
         res = dict(adv=adv, adv_f64=adv_f, success=flag.value, dist2=d2.value, n_iters=ni.value, n_queries=nq.value,
-                   trace=trace[:ni.value + 1], decisions=dec[:nq.value])
+                   trace=trace[:ni.value + 1], decisions=dec[:n_log])
         if keep_x:
             res["xs"] = xs[:ni.value + 1] if flag.value == 1 else xs[:0]
         return res

@@ -8,7 +8,9 @@ direction, a batch of step sizes along it, and a boundary search again.  Every b
 NES batch (fb_attack_hsj; the arithmetic is written out in include/fakebob_hip.h, "decision-only attack II").  The surface
 is FakeBob's: the same `attack` arguments and return pair, plus `init`.
 
-Not in this version: expectation over transformation, companion utterances, foreign models.
+Randomised victims and several utterances: with `quorum=` set, `eot_size=` and `attack(..., companions=[...])` score every row
+r' = K * eot_size times and a row counts as adversarial from `quorum` adversarial replicas on -- its votes
+(fakebob_amd.query_eot; "voted decisions" in the header).  Not in this version: foreign models.
 """
 import math
 import pickle
@@ -18,6 +20,7 @@ import numpy as np
 
 from .attack import _check_bits, _col
 from .companions import cast_i16
+from . import query_eot as QE
 from .engine import hsj_params, nes_params
 
 MAX_GRID, MAX_ROUNDS, MAX_EVALS = 64, 32, 1024
@@ -37,7 +40,10 @@ def fit_init(init, n):
 class HopSkipJump(object):
 
     def __init__(self, task, attack_type, model, grid=15, max_rounds=8, num_evals_init=32, num_evals_max=256, max_queries=0,
-                 sigma_min=2.0 ** -15, probe_scale=0.05, max_iter=20, seed=None, verbose=True):
+                 sigma_min=2.0 ** -15, probe_scale=0.05, max_iter=20, seed=None, verbose=True, eot_size=None, quorum=None):
+        """eot_size: every scored row under that many draws of a randomised victim; quorum ("majority" or 1 .. 32; None:
+        off) is the number of adversarial draws a row needs -- its votes -- to count as adversarial."""
+        self.eot_size, self.quorum = QE.check_options("HopSkipJump", eot_size, quorum)
         if task not in ("OSI", "CSI", "SV"):
             raise ValueError("task must be OSI, CSI or SV")
         if attack_type not in ("targeted", "untargeted"):
@@ -109,8 +115,12 @@ class HopSkipJump(object):
         return None
 
     def attack(self, audio, checkpoint_path, threshold=0., true=None, target=None, fs=16000, bits_per_sample=16, n_jobs=10,
-               debug=False, init=None):
-        """Returns (int16 adversarial audio (N, 1), success flag +-1), as FakeBob.attack does: a row that was scored and
+               debug=False, init=None, companions=None):
+        """companions (needs quorum=): utterances as long as `audio` that ride along, as in FakeBob.attack -- every scored
+        row's perturbation is scored on all of them, each (utterance, draw) one vote.  The returned pair is a
+        companions.AttackResult: perturbation_i16, apply_perturbation, per_utterance and votes -- the logged votes of every
+        scored row in scoring order (None when the rows were scored once).
+        Returns (int16 adversarial audio (N, 1), success flag +-1), as FakeBob.attack does: a row that was scored and
         decided as wanted, as close to `audio` as the walk came -- or the int16 cast of the audio with -1 when `init` (or, for
         an untargeted attack without one, every noise start) is not decided as wanted.  init: the starting audio, cropped or
         tiled to N samples; a targeted attack needs one.  checkpoint_path (or None) receives a pickle (protocol -1) with one
@@ -141,7 +151,7 @@ class HopSkipJump(object):
         if start is None:
             if self.verbose:
                 print("--- no noise start is decided as wanted ---")
-            return x0[:, np.newaxis], -1
+            return QE.result(self.model, self.task, self.attack_type, x0, -1, audio[:, 0], bits, None, None)
         p = nes_params(self.task, self.attack_type, max_iter=self.max_iter, threshold=threshold, target=target, true=true,
                        seed=self.seed, stream=self._stream, bits_per_sample=bits)
         k = hsj_params(self.grid, self.max_rounds, self.num_evals_init, self.num_evals_max, self.max_queries, self.sigma_min,
@@ -149,7 +159,9 @@ class HopSkipJump(object):
         self._stream += 1
         eng = self.model.engine
         t0 = time.time()
-        res = eng.attack_hsj(p, k, audio[:, 0], start)
+        with QE.Settings("HopSkipJump", eng, self.eot_size, self.quorum, companions, n, bits) as st:
+            res = eng.attack_hsj(p, k, audio[:, 0], start)
+        rp = st.replicas if st.quorum is not None else 1
         dt = time.time() - t0
         rows = res["trace"].shape[0]
         used_time = eng.attack_iter_seconds(rows)
@@ -168,4 +180,6 @@ class HopSkipJump(object):
         if self.verbose:
             print("--- %d iterations, %d queries, success %d, |x - a| %s, SNR %s dB, %.3f s ---" % (
                 res["n_iters"], self.n_queries, res["success"], self.dist, self.snr_db, dt))
-        return res["adv"][:, np.newaxis], res["success"]
+        return QE.result(self.model, self.task, self.attack_type, res["adv"], res["success"], audio[:, 0], bits, st.comp,
+                         res["decisions"] if rp > 1 else None, target=target, true=true, fs=fs, bits_per_sample=bits_per_sample,
+                         n_jobs=n_jobs, debug=debug)

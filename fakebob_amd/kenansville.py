@@ -10,7 +10,9 @@ per round (fb_attack_kenansville; the arithmetic is written out in include/fakeb
 `tables` builds the four integer tables the engine takes, `remove` is the contract's host twin in vectorised numpy, as
 codec.py is for the codecs.  The surface is FakeBob's: the same `attack` arguments and return pair.
 
-Not in this version: expectation over transformation, companion utterances, foreign models.
+Randomised victims and several utterances: with `quorum=` set, `eot_size=` and `attack(..., companions=[...])` score every row
+r' = K * eot_size times and a row counts as adversarial from `quorum` adversarial replicas on -- its votes
+(fakebob_amd.query_eot; "voted decisions" in the header).  Not in this version: foreign models.
 """
 import math
 import pickle
@@ -20,6 +22,7 @@ import numpy as np
 
 from .attack import _check_bits, _col
 from .engine import kv_params, nes_params
+from . import query_eot as QE
 
 MIN_WINDOW, MAX_WINDOW = 8, 128
 MAX_GRID, MAX_ROUNDS, Q_ONE = 64, 32, 65536
@@ -100,7 +103,11 @@ def q_of(max_factor):
 
 class Kenansville(object):
 
-    def __init__(self, task, attack_type, model, window=100, grid=15, max_factor=1.0, max_rounds=32, seed=None, verbose=True):
+    def __init__(self, task, attack_type, model, window=100, grid=15, max_factor=1.0, max_rounds=32, seed=None, verbose=True,
+                 eot_size=None, quorum=None):
+        """eot_size: every candidate scored under that many draws of a randomised victim; quorum ("majority" or 1 .. 32;
+        None: off) is the number of adversarial draws a candidate needs -- its votes -- to count as succeeding."""
+        self.eot_size, self.quorum = QE.check_options("Kenansville", eot_size, quorum)
         if task not in ("OSI", "CSI", "SV"):
             raise ValueError("task must be OSI, CSI or SV")
         if attack_type not in ("targeted", "untargeted"):
@@ -143,8 +150,12 @@ class Kenansville(object):
         return res
 
     def attack(self, audio, checkpoint_path, threshold=0., true=None, target=None, fs=16000, bits_per_sample=16, n_jobs=10,
-               debug=False):
-        """Returns (int16 adversarial audio (N, 1), success flag +-1), as FakeBob.attack does: the candidate with the smallest
+               debug=False, companions=None):
+        """companions (needs quorum=): utterances as long as `audio` that ride along, as in FakeBob.attack -- every candidate's
+        perturbation is scored on all of them, each (utterance, draw) one vote.  The returned pair is a
+        companions.AttackResult: perturbation_i16, apply_perturbation, per_utterance and votes (n_rounds, G) -- the logged
+        votes of every candidate (None when the rows were scored once: the checkpoint's decisions are decisions then).
+        Returns (int16 adversarial audio (N, 1), success flag +-1), as FakeBob.attack does: the candidate with the smallest
         factor that was seen to succeed -- a row that was scored -- or the int16 cast of the audio with -1.  For SV
         true=None means 1 (the enrolled speaker speaks).  checkpoint_path (or None) receives a pickle (protocol -1) with one
         row per round: [qs, decisions, scores (rows, S), lo, hi, used_time]."""
@@ -169,13 +180,15 @@ class Kenansville(object):
         self._stream += 1
         eng = self.model.engine
         t0 = time.time()
-        res = eng.attack_kenansville(p, k, audio[:, 0])
+        with QE.Settings("Kenansville", eng, self.eot_size, self.quorum, companions, audio.shape[0], bits) as st:
+            res = eng.attack_kenansville(p, k, audio[:, 0])
+        rp = st.replicas if st.quorum is not None else 1
         dt = time.time() - t0
         n = res["trace"].shape[0]
         used_time = eng.attack_iter_seconds(n)
         cp = []
         for r in range(n):
-            rows = int(res["trace"][r, 2])
+            rows = int(res["trace"][r, 2]) // rp     # (the column counts victim queries: rows * r')
             cp.append([res["qs"][r, :rows].copy(), res["decisions"][r, :rows].copy(), res["scores"][r, :rows].copy(),
                        int(res["trace"][r, 0]), int(res["trace"][r, 1]), float(used_time[r])])
         if checkpoint_path:
@@ -185,4 +198,6 @@ class Kenansville(object):
         self.n_queries = res["n_queries"]
         if self.verbose:
             print("--- %d rounds, %d queries, factor %s / 65536, %.3f s ---" % (n, self.n_queries, self.factor, dt))
-        return res["adv"][:, np.newaxis], res["success"]
+        return QE.result(self.model, self.task, self.attack_type, res["adv"], res["success"], audio[:, 0], bits, st.comp,
+                         res["decisions"] if rp > 1 else None, target=target, true=true, fs=fs, bits_per_sample=bits_per_sample,
+                         n_jobs=n_jobs, debug=debug)

@@ -6,7 +6,9 @@ scores every NES batch; one launch moves the swarm (fb_attack_pso; the arithmeti
 include/fakebob_hip.h, "particle-swarm attack").  The surface is FakeBob's: the same `attack` arguments and return pair,
 the same Philox stream handling (`seed`, one stream per attack() call), so a driver swaps one for the other.
 
-Not in this version: expectation over transformation, companion utterances, foreign models, swarm restarts.
+Randomised victims and several utterances: `eot_size=` and `attack(..., companions=[...])` score every particle r' = K *
+eot_size times and the swarm reads the mean loss, once `quorum=` switches that on (fakebob_amd.query_eot; "voted decisions"
+in the header).  Not in this version: foreign models, swarm restarts.
 """
 import math
 import pickle
@@ -16,6 +18,7 @@ import numpy as np
 
 from .attack import FakeBob, _check_bits, _col
 from .engine import nes_params, pso_params
+from . import query_eot as QE
 
 MAX_PARTICLES = 64
 
@@ -23,8 +26,11 @@ MAX_PARTICLES = 64
 class ParticleSwarm(object):
 
     def __init__(self, task, attack_type, model, adver_thresh=0., epsilon=0.002, max_iter=300, n_particles=25,
-                 w_init=0.9, w_end=0.1, c1=1.4961, c2=1.4961, v_max=None, seed=None, verbose=True):
-        """v_max=None: epsilon (a particle crosses the ball's radius in one step at most)."""
+                 w_init=0.9, w_end=0.1, c1=1.4961, c2=1.4961, v_max=None, seed=None, verbose=True, eot_size=None, quorum=None):
+        """v_max=None: epsilon (a particle crosses the ball's radius in one step at most).  eot_size: every particle scored
+        under that many draws of a randomised victim, the swarm reading the mean loss; it needs quorum= ("majority" or 1 ..
+        32; None: off), the switch the three query attacks share -- PSO itself reads no votes."""
+        self.eot_size, self.quorum = QE.check_options("ParticleSwarm", eot_size, quorum)
         if task not in ("OSI", "CSI", "SV"):
             raise ValueError("task must be OSI, CSI or SV")
         if attack_type not in ("targeted", "untargeted"):
@@ -76,8 +82,11 @@ class ParticleSwarm(object):
         return res
 
     def attack(self, audio, checkpoint_path, threshold=0., true=None, target=None, fs=16000, bits_per_sample=16, n_jobs=10,
-               debug=False):
-        """Returns (int16 adversarial audio (N, 1), success flag +-1), as FakeBob.attack does: the swarm's best position --
+               debug=False, companions=None):
+        """companions (needs quorum=): utterances as long as `audio` that ride along, as in FakeBob.attack -- one perturbation
+        over all of them, the losses means over utterances and draws; the returned pair is a companions.AttackResult
+        (perturbation_i16, apply_perturbation, per_utterance, votes = None).
+        Returns (int16 adversarial audio (N, 1), success flag +-1), as FakeBob.attack does: the swarm's best position --
         a position that was scored -- and whether its loss fell below zero.  checkpoint_path (or None) receives a pickle
         (protocol -1) with one row per iteration, [array([gbest_loss]), gbest_score (a scalar for SV), used_time]: the
         layout is this attack's own (no distance column: the ball bounds it)."""
@@ -93,7 +102,8 @@ class ParticleSwarm(object):
         self._stream += 1
         eng = self.model.engine
         t0 = time.time()
-        adv, flag, _advf, trace, _losses = eng.attack_pso(p, q, audio[:, 0])
+        with QE.Settings("ParticleSwarm", eng, self.eot_size, self.quorum, companions, audio.shape[0], bits) as st:
+            adv, flag, _advf, trace, _losses = eng.attack_pso(p, q, audio[:, 0])
         dt = time.time() - t0
         n = trace.shape[0]
         used_time = eng.attack_iter_seconds(n)
@@ -106,4 +116,5 @@ class ParticleSwarm(object):
                 pickle.dump(cp, writer, protocol=-1)
         if self.verbose:
             print("--- %d iters, %d particles, gbest loss:%f, %.1f iters/s ---" % (n, self.n_particles, trace[-1, 0], n / dt if dt > 0 else 0.0))
-        return adv[:, np.newaxis], flag
+        return QE.result(self.model, self.task, self.attack_type, adv, flag, audio[:, 0], bits, st.comp, None, target=target,
+                         true=true, fs=fs, bits_per_sample=bits_per_sample, n_jobs=n_jobs, debug=debug)

@@ -405,8 +405,8 @@ int fb_set_feature_compression(fb_engine *e, double ratio, int iters);
  * validated.
  * Refusals.  FB_E_ARG: particles outside 2 .. 64; w_init, w_end, c1 or c2 not finite or < 0; v_max not finite or <= 0;
  * max_iter < 1; epsilon not finite or <= 0; the task, target, true-label and bits_per_sample rules of fb_attack.  FB_E_STATE:
- * no system loaded, or fb_set_eot(r > 1) or companions (fb_set_companions) in force -- BOTH STAY OUT OF THIS VERSION: set 1 /
- * clear them.  FB_E_NO_VOICED: some particle of some iteration has no voiced frames.  The engine's own systems only (GMM and
+ * no system loaded, or fb_set_eot(r > 1) or companions (fb_set_companions) in force while fb_set_query_eot is off (the
+ * default; the "voted decisions" section below says what they mean with it on): set 1 / clear them.  FB_E_NO_VOICED: some particle of some iteration has no voiced frames.  The engine's own systems only (GMM and
  * i-vector): there are no _ext / _dev twins.  The input-transform chain, dither and feature compression act as in fb_attack,
  * keyed by the call's (seed, stream) with epoch = the PSO iteration k and utterance row = the particle index.
  * Arithmetic.  Everything below is float64, round to nearest, one rounding per written operation, no fused multiply-add;
@@ -500,8 +500,8 @@ int fb_attack_pso(fb_engine *e, const fb_nes_params *p, const fb_pso_params *q, 
  * keyed by the call's (seed, stream) with epoch = the round and utterance row = the candidate's index in the round.
  * Refusals.  FB_E_ARG: anything outside the ranges above, a task other than the engine's, a label that is no decision of
  * the system, wrong tables, bits_per_sample outside 2 .. 16, audio shorter than one frame.  FB_E_STATE: no system loaded, or
- * fb_set_eot(r > 1) or companions in force -- BOTH STAY OUT OF THIS VERSION: set 1 / clear them.  The engine's own systems
- * only: there are no _ext / _dev twins.
+ * fb_set_eot(r > 1) or companions in force while fb_set_query_eot is off (the default; "voted decisions" below): set 1 /
+ * clear them.  The engine's own systems only: there are no _ext / _dev twins.
  * Deviations from Kenansville / SpeakerGuard's version: theirs transforms with a floating-point FFT (or SSA) and bisects one
  * candidate per query; here the arithmetic is the integer contract above and a round scores G candidates. */
 typedef struct { int window; int grid; int q_max; int max_rounds; } fb_kv_params;
@@ -571,8 +571,8 @@ int fb_attack_kenansville(fb_engine *e, const fb_nes_params *p, const fb_kv_para
  * step), 0.05.
  * Refusals.  FB_E_ARG: anything outside those ranges, max_iter < 0, a null `init`, bits_per_sample outside 2 .. 16, audio
  * shorter than one frame, a task other than the engine's, a label that is no decision of the system, a decision log that is
- * too small.  FB_E_STATE: no system loaded, or fb_set_eot(r > 1) or companions in force -- BOTH STAY OUT OF THIS VERSION: set
- * 1 / clear them.  The engine's own systems only: there are no _ext / _dev twins.
+ * too small.  FB_E_STATE: no system loaded, or fb_set_eot(r > 1) or companions in force while fb_set_query_eot is off (the
+ * default; "voted decisions" below): set 1 / clear them.  The engine's own systems only: there are no _ext / _dev twins.
  * Deviations from the paper: the L2 variant only; grid rounds of G rows instead of one-query bisection and one-query step
  * halving; Gaussian probes that are not normalised to the sphere; a probe radius with a floor of sigma_min, because the
  * paper's delta = dist / d lies far below one int16 step for audio and the cast would erase it; keyed draws; a stall instead
@@ -584,6 +584,54 @@ int fb_attack_hsj(fb_engine *e, const fb_nes_params *p, const fb_hsj_params *k, 
                   int64_t N, int16_t *adv_i16, double *adv_f64 /*nullable*/, int *success, double *dist2, int *n_iters,
                   int *n_queries, double *trace /*[max_iter + 1][8]*/, int *decisions /*[decisions_cap]*/,
                   long long decisions_cap, double *x_trace /*nullable [max_iter + 1][N]*/);
+
+/* ---- voted decisions: the particle-swarm and the two decision-only attacks on a randomised victim, and on companions ---------
+ * Against a randomised victim (noise stages, dither, the air channel, feature compression) one query per candidate is a coin
+ * flip: fb_attack_kenansville's bracket and fb_attack_hsj's boundary search assume that a candidate HAS a decision.  With this
+ * switch on the three attacks of the sections above accept fb_set_eot(r), companions (fb_set_companions) and both together:
+ * every candidate row is scored r' = K * eot <= 32 times in ONE replicating launch chain -- fb_attack's under EOT --, and
+ * one launch (k_vote) turns the r' replica rows of a candidate into one vote.
+ * fb_set_query_eot(e, quorum): FB_QUORUM_OFF = 0 (the default) -- the three attacks refuse EOT and companions with FB_E_STATE
+ * exactly as their sections say; FB_QUORUM_MAJORITY = -1 -- a row needs r' / 2 + 1 (integer division) adversarial replicas;
+ * 1 .. 32 -- it needs that many.  Anything else is FB_E_ARG and keeps the previous value.  An explicit quorum larger than
+ * the r' in force is FB_E_ARG at the attack call, before anything runs (fb_attack_pso reads no quorum, and refuses it all
+ * the same).  Switched on with r' = 1 nothing changes: no launch is added, every output is bit-identical to the switch-off
+ * run, decisions[] keeps holding decisions.  fb_estimate_threshold keeps returning FB_E_STATE under EOT or companions, and
+ * foreign models stay out.  Everything below is for r' > 1.
+ * Replication.  Exactly fb_set_companions' rule.  The attack's `rows` candidate rows stand un-replicated in the batch buffer
+ * (q_b: particle b, candidate b of the round, row b of a search round / of the probes / of the step sizes).  a_0 is the int16
+ * cast of the call's `audio`, made once per call (for fb_attack_kenansville that is its x).  Utterance u of row b is q_b for
+ * u = 0 and clip(a_u + q_b - a_0, -32768, 32767) for a companion; replica rho = u * eot + j is row b * r' + rho of what the
+ * front end scores; the noise stages, dither, feature compression and the air channel draw with `replica` = rho, utterance
+ * row = b (the row's index in its un-replicated batch), and epoch = the attack's own: the PSO iteration, the Kenansville
+ * round, fb_attack_hsj's running count of scoring batches.  rows * r' > 65535 is FB_E_LIMIT before anything is scored: for
+ * fb_attack_hsj max(grid, num_evals_max) * r' is checked up front.  A call whose N differs from the companions' is FB_E_ARG.
+ * fb_attack_pso.  l_p and particle p's score row are fb_set_eot's means over its r' replicas: loss_fn and the system scores
+ * per replica row, then (v_0 + v_1 + ... + v_{r' - 1}) / r' in float64, rho ascending, one rounding per addition and one for
+ * the division (k_loss_eot, as in fb_attack).  FB_E_NO_VOICED if ANY replica of any particle has no voiced frames.  Everything
+ * behind step 1 is unchanged and sees the P averaged rows; the ball, the returned audio and adv_f64 are utterance 0's, and
+ * the perturbation to carry over to the companions is adv_i16 - a_0.  As in fb_attack THE STOP TEST READS A MEAN.
+ * fb_attack_kenansville and fb_attack_hsj.  Per replica row the system scores are formed exactly as without replicas (the
+ * device function of k_loss), then the decision d by the rule of the "decision-only attack" section (SV s >= threshold;
+ * OSI / CSI the first maximum; OSI maximum < threshold -> -1; no voiced frames -> -2), then the replica's flag: adversarial
+ * iff d == target (targeted), or d != true_label and d != -2 (untargeted).  A replica without voiced frames is a failed
+ * replica, never an error.
+ *   vote       of a candidate row: the number of its adversarial replicas, 0 .. r'.
+ *   adversarial a row is adversarial ("succeeds") iff vote >= quorum.  Wherever the two sections say that a row succeeds, is
+ *              adversarial or WAS scored and decided adversarial, read "voted adversarial": the bracket's update, n+ and the
+ *              weights w_j, the smallest adversarial step size m, the row of hi that is returned.
+ *   logs       decisions[] holds the VOTES, in the places the decisions had (one entry per candidate row; fb_hsj_max_rows is
+ *              unchanged).  fb_attack_kenansville's scores[r][G][S] holds the fb_set_eot mean of the replicas' score rows.
+ *   queries    *n_queries, max_queries, fb_attack_kenansville's trace[.][2] and fb_attack_hsj's trace[.][6] count VICTIM
+ *              queries: candidate rows * r'.  max_queries stops before a batch whose rows * r' would pass it.
+ *   the rest   of both searches is unchanged: candidates, bracket, probes, direction, step sizes, stalls, stops; the float64
+ *              state and the returned row are utterance 0's.
+ * The launch.  k_vote reads the finalised raw scores and tv of the rows * r' replica rows and writes ONE contiguous block
+ * {votes[rows] int32, nodec[rows] int32 (replicas with -2), mean[rows][S] float64}; the host copies that block and nothing
+ * per replica.  It stands where k_loss stood: the replicated chain gains no launch beyond fb_attack's under EOT.  One wave
+ * per candidate row counts with two ballots and adds in a fixed order: no atomics, bit-reproducible. */
+enum { FB_QUORUM_OFF = 0, FB_QUORUM_MAJORITY = -1 };
+int fb_set_query_eot(fb_engine *e, int quorum);   /* 0 off (default) | -1 majority | 1 .. 32 */
 
 /* ---- white-box gradients: backpropagation through the GMM-UBM victim ------------------------------------------------------
  * fb_get_grad estimates the gradient of the loss from scores (NES); the victim lives in the engine, so the gradient itself

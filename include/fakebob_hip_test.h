@@ -152,6 +152,18 @@ int fb_debug_hsj_step(fb_engine *e, const double *x, const double *v, int64_t N,
  * launch (k_perturb) of 2 ceil(B / 2) + 1 rows. */
 int fb_bench_hsj_kernels(fb_engine *e, const double *a, const double *y, int64_t N, int B, int G, int bits, int reps, double *ms);
 
+/* Voted decisions (fakebob_hip.h: fb_set_query_eot).  fb_debug_vote runs k_vote alone, exactly the launch the attacks run, on
+ * raw scores handed in: raw [rows][r][n_out] -- what fb_score_* returns for the loaded system, n_out columns per row -- and
+ * tv [rows * r] (<= 0: that replica has no voiced frames).  The loaded system gives n_out, S and the z-norm tables; `task`
+ * must be the engine's; label is the target (FB_TARGETED) or the true label (FB_UNTARGETED), a decision value.  rows * r <=
+ * 65535, r = 1 .. 32.  Outputs: votes [rows], nodec [rows], mean [rows][S].
+ * fb_bench_vote (tools/query_eot_rate.py): the same launch `reps` times between two events after one to warm up -> *ms per
+ * launch. */
+int fb_debug_vote(fb_engine *e, const double *raw, const int *tv, int rows, int r, int task, double threshold, int attack_type,
+                  int label, int *votes, int *nodec, double *mean);
+int fb_bench_vote(fb_engine *e, const double *raw, const int *tv, int rows, int r, int task, double threshold, int attack_type,
+                  int label, int reps, double *ms);
+
 /* What the front end of the last batch ran (fb_score_*, fb_get_grad, an NES iteration, fb_debug_mfcc / _feats, enrolment
  * statistics): info[5] = {the MFCC kernel, the chain after it, where the CompressedMatrix round trip ran, the longest
  * utterance of the batch in frames, the batch size}.  Recorded on the host when the kernels are enqueued; read only.
