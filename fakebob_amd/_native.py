@@ -145,7 +145,7 @@ class ForeignPathInfo(C.Structure):
 
 EXPORTS = [
     "fb_last_error", "fb_version", "fb_device_count", "fb_engine_create", "fb_engine_destroy",
-    "fb_default_frontend", "fb_set_frontend", "fb_set_dither_seed", "fb_set_input_transform", "fb_set_air_channel", "fb_set_codec", "fb_set_eot", "fb_set_companions", "fb_set_query_eot", "fb_set_feature_compression", "fb_load_gmm", "fb_load_ivector", "fb_set_system", "fb_num_speakers",
+    "fb_default_frontend", "fb_set_frontend", "fb_set_dither_seed", "fb_set_input_transform", "fb_set_air_channel", "fb_set_codec", "fb_set_eot", "fb_set_companions", "fb_set_play_offset", "fb_debug_play_offsets", "fb_debug_play_route", "fb_bench_play_compose", "fb_debug_wb_play_compose_t", "fb_debug_wb_play_route", "fb_set_query_eot", "fb_set_feature_compression", "fb_load_gmm", "fb_load_ivector", "fb_set_system", "fb_num_speakers",
     "fb_score_i16", "fb_score_f64", "fb_system_scores", "fb_get_grad", "fb_attack", "fb_get_grad_wb", "fb_get_grad_wb_iter", "fb_set_wb_bpda", "fb_set_wb_ivector", "fb_set_wb_air", "fb_set_wb_frontend", "fb_set_wb_universal", "fb_get_grad_wb_from", "fb_attack_wb", "fb_attack_cw2", "fb_debug_cw2_step", "fb_attack_psy", "fb_debug_psy_loss", "fb_debug_psy_step", "fb_attack_pso", "fb_attack_kenansville", "fb_attack_hsj", "fb_hsj_max_rows", "fb_attack_iter_seconds", "fb_get_grad_ext", "fb_attack_ext",
     "fb_get_grad_dev", "fb_attack_dev", "fb_debug_foreign_path", "fb_debug_nes_route", "fb_debug_nes_batch", "fb_debug_shared_chain_engines",
     "fb_estimate_threshold", "fb_debug_noise", "fb_debug_quantize", "fb_debug_mfcc", "fb_debug_feats", "fb_debug_dither_noise", "fb_debug_mfcc_dither", "fb_debug_feats_dither", "fb_debug_input_transform", "fb_debug_tf_noise", "fb_debug_input_transform_eot", "fb_debug_compose", "fb_debug_air_taps", "fb_debug_air_convolve", "fb_debug_codec", "fb_debug_feature_compress", "fb_debug_feco_keys", "fb_debug_pso_init", "fb_debug_pso_step", "fb_debug_kv_analyse", "fb_debug_kv_candidates", "fb_debug_hsj_line", "fb_debug_hsj_probes", "fb_debug_hsj_dir", "fb_debug_hsj_step", "fb_debug_vote", "fb_debug_gmm_frames", "fb_debug_gmm_acc_rows", "fb_debug_gmm_feat_grad", "fb_debug_frontend_vjp", "fb_debug_defence_vjp", "fb_debug_wb_route", "fb_debug_air_conv_t", "fb_debug_air_conv_t_chunk", "fb_debug_wb_air_route", "fb_debug_feature_compress_vjp", "fb_debug_wb_feco_route", "fb_debug_wb_feco_state", "fb_debug_wb_compose_t", "fb_debug_wb_universal_route", "fb_debug_iv_backend_grad", "fb_debug_iv_feat_grad", "fb_debug_iv_active", "fb_debug_iv_gselect", "fb_debug_frontend_route", "fb_debug_launch_shape", "fb_stats", "fb_gmm_acc_stats", "fb_last_ivectors", "fb_gmm_kernel_mode", "fb_gmm_kernel_variant", "fb_gmm_delta_tiles", "fb_gmm_delta_tiles_f6", "fb_set_fused_chain",

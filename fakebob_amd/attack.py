@@ -52,7 +52,7 @@ class FakeBob(object):
 
     def __init__(self, task, attack_type, model, adver_thresh=0., epsilon=0.002, max_iter=1000,
                  max_lr=0.001, min_lr=1e-6, samples_per_draw=50, sigma=0.001, momentum=0.9,
-                 plateau_length=5, plateau_drop=2., seed=None, verbose=True, eot_size=None):
+                 plateau_length=5, plateau_drop=2., seed=None, verbose=True, eot_size=None, play_offset=None):
         self.task = task
         self.attack_type = attack_type
         self.model = model
@@ -99,6 +99,12 @@ class FakeBob(object):
             self.eot_size = None
             if eot_size is not None and eot_option(eot_size) != 1:
                 raise ValueError("eot_size applies to the engine's own systems, not to a foreign model")
+        # play offset (fb_set_play_offset): the perturbation plays on a loop, every replica hears it at an offset of its own in
+        # 0 .. play_offset.  Set on the engine for the length of an attack() call; the engine's own systems only.
+        from .play_offset import check_offset
+        self.play_offset = check_offset(play_offset)
+        if self.play_offset and not self._native:
+            raise ValueError("play_offset applies to the engine's own systems, not to a foreign model")
 
     # ------------------------------------------------------------------ helpers
     def _params(self, attack_type=None, max_iter=None, stream=None, bits_per_sample=16):
@@ -279,7 +285,12 @@ class FakeBob(object):
         perturbation over all of them (fb_set_companions; the loop's losses are means over the utterances), for this
         call only.  The returned pair is a companions.AttackResult: it also carries perturbation_i16,
         apply_perturbation(wavs) and, with companions, per_utterance -- every composed utterance re-scored through
-        model.make_decisions, with its success."""
+        model.make_decisions, with its success.
+        With FakeBob(play_offset=S) the engine draws an offset in 0 .. S for every replica of every row for the length of this
+        call (fb_set_play_offset; S must stay below the length of `audio`), and the result carries per_offset: for each of the K
+        utterances the perturbation rotated by each offset of play_offset.offset_grid(S) is composed onto it and re-scored
+        through model.make_decisions -- a list of K dicts with utterance, offsets, decisions, successes (a list of booleans)
+        and n_success."""
         audio = _col(audio)
         bits = _check_bits(bits_per_sample)
         from . import companions as CP
@@ -297,14 +308,21 @@ class FakeBob(object):
         kw = dict(fs=fs, bits_per_sample=bits_per_sample, n_jobs=n_jobs, debug=debug)
         if self._native:
             eng = self.model.engine
-            if companions is None:
+            if self.play_offset >= audio.shape[0] > 0:
+                raise ValueError("play_offset %d: the audio has %d samples, the offset must stay below that" % (self.play_offset, audio.shape[0]))
+            # (an engine is asked for a setting only when this call changes it)
+            before = eng.companions if companions is not None else None
+            before_S = eng.play_offset if self.play_offset else 0
+            try:
+                if companions is not None:
+                    eng.set_companions(comp)
+                if self.play_offset:
+                    eng.set_play_offset(self.play_offset)
                 adv, flag, _advf, trace = eng.attack(p, audio[:, 0], noise_all=noise_all)
-            else:
-                before = eng.companions
-                eng.set_companions(comp)
-                try:
-                    adv, flag, _advf, trace = eng.attack(p, audio[:, 0], noise_all=noise_all)
-                finally:
+            finally:
+                if self.play_offset:
+                    eng.set_play_offset(before_S)
+                if companions is not None:
                     eng.set_companions(before)
         elif self._device:
             eng = self._engine()
@@ -341,7 +359,12 @@ class FakeBob(object):
                 dec, sc = self.model.make_decisions(w, **kw)
                 per.append(dict(utterance=u, audio_i16=w, decision=dec, score=sc,
                                 success=CP.succeeded(self.task, self.attack_type, dec, target=target, true=true)))
-        return CP.AttackResult(adv[:, np.newaxis], flag, delta, bits, per)
+        per_off = None
+        if self._native and self.play_offset:
+            from .play_offset import per_offset
+            per_off = per_offset(self.model, self.task, self.attack_type, [a0] + ([] if comp is None else list(comp)), delta,
+                                 self.play_offset, target=target, true=true, **kw)
+        return CP.AttackResult(adv[:, np.newaxis], flag, delta, bits, per, per_off)
 
     # ------------------------------------------------------------------ get_grad
     def get_grad(self, audio, fs=16000, bits_per_sample=16, n_jobs=10, debug=False, iteration=0, noise_pos=None):

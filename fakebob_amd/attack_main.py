@@ -171,6 +171,36 @@ def print_votes(attack, name, flag, res):
         print("%s %s: success %d, votes of %d rows: min %d, mean %.2f, max %d" % (attack, name, flag, v.size, v.min(), v.mean(), v.max()))
 
 
+def _play_offset(text):
+    """--play-offset's value: "max" or an integer 0 .. 2^31 - 2"""
+    from .play_offset import check_offset
+    t = str(text).strip().lower()
+    if t == "max":
+        return "max"
+    try:
+        return check_offset(int(t))
+    except ValueError as ex:
+        raise argparse.ArgumentTypeError("--play-offset: 'max' or an integer 0 .. 2^31 - 2 (%s)" % ex)
+
+
+def set_play_offset(bob, option, n_samples):
+    """--play-offset for the attack that comes next: through the attack object's own check where it has one (the PGD classes:
+    an offset needs universal=True), else the attribute FakeBob.attack reads"""
+    from .play_offset import parse_option
+    S = parse_option(option, n_samples)
+    if hasattr(bob, "_set_play_offset"):
+        bob._set_play_offset(S)
+    else:
+        bob.play_offset = S
+
+
+def print_offsets(name, res):
+    """--play-offset: how many of the grid's offsets succeeded on every utterance (AttackResult.per_offset)"""
+    per = getattr(res, "per_offset", None)
+    if per:
+        print("play offset %s: %s of %d offsets succeed (utterance 0 first)" % (name, [d["n_success"] for d in per], len(per[0]["offsets"])))
+
+
 def main(argv=None, model_factory=None, bob_factory=None):
     """model_factory(architecture, task, model_list, pre_model_dir, threshold, group_id) / bob_factory(task,
     attack_type, model, **hyper_parameters): injection points for the driver-rule tests (a stub model / stub FakeBob
@@ -230,6 +260,11 @@ def main(argv=None, model_factory=None, bob_factory=None):
                     help="universal perturbation: the next N utterances of the same speaker in the data directory ride along "
                          "with every attacked one (1 .. 31, times --eot-size at most 32); all are cropped to the shortest, "
                          "which is printed; default: 0")
+    ap.add_argument("--play-offset", dest="play_offset", default=None, type=_play_offset, metavar="S|max",
+                    help="--attack nes | pgd: the perturbation plays on a loop and cannot be timed to the victim's speech -- every "
+                         "replica of every row (--eot-size, --companions) carries it rotated by an offset of its own, uniform in "
+                         "0 .. S samples; 'max': the whole loop, N - 1 of the (cropped) utterance; --attack pgd needs --wb-universal; "
+                         "the result's per_offset counts are printed; default: none")
     ap.add_argument("--attack", default="nes", choices=["nes", "pso", "kenansville", "hsj", "pgd", "cw2", "psy"],
                     help="the search: FAKEBOB's NES gradient estimate (default), SirenAttack's particle swarm "
                          "(fakebob_amd/pso.py; -epsilon, -max_iter, -adver and --seed apply, the other NES options do not), "
@@ -323,6 +358,11 @@ def main(argv=None, model_factory=None, bob_factory=None):
         if args.hsj_init is None and (args.attack_type == "targeted" or args.task == "SV"):
             ap.error("--attack hsj: a targeted attack needs --hsj-init, an audio the system already decides as the target")
 
+    if args.play_offset is not None and args.play_offset != 0:      # likewise: what the library refuses by name is refused here
+        if args.attack in ("pso", "kenansville", "hsj", "cw2", "psy"):
+            ap.error("--attack %s does not run under a play offset in this version (--play-offset %s)" % (args.attack, args.play_offset))
+        if args.attack == "pgd" and not args.wb_universal:
+            ap.error("--attack pgd takes --play-offset %s only with --wb-universal (the offset rides on the universal path)" % args.play_offset)
     if args.bpda and args.attack not in ("pgd", "cw2", "psy"):
         ap.error("--bpda belongs to --attack pgd (--attack %s)" % args.attack)
     if args.wb_ivector and args.attack not in ("pgd", "cw2", "psy"):
@@ -407,6 +447,8 @@ def main(argv=None, model_factory=None, bob_factory=None):
         #  runs without)
         if args.eot_size is not None and not (query_attack and args.query_eot is not None) and hasattr(m, "engine") and hasattr(m.engine, "set_eot"):
             m.engine.set_eot(args.eot_size)
+    if args.play_offset and any(not hasattr(m, "engine") for m in models):   # (as FakeBob refuses eot_size there)
+        ap.error("--play-offset applies to the engine's own systems, not to a foreign model")
     if K >= 3:  # several engines share the GPU: the separate launches interleave better (fb_set_fused_chain)
         for m in models:
             if hasattr(m, "engine"):
@@ -521,19 +563,24 @@ def main(argv=None, model_factory=None, bob_factory=None):
                 return
             it = items[idx]
             bob._stream = idx + 1         # Philox stream = global attack index: results do not depend on the sharding
+            audio_c, comp = with_companions(items, idx, args.companions) if args.companions > 0 else (it["audio"], None)
+            if args.play_offset:          # ('max': N - 1 of THIS utterance, cropped as --companions crops; fixed otherwise)
+                set_play_offset(bob, args.play_offset, len(audio_c))
             # the reference passes true= only for CSI untargeted (:346) and target= only for targeted attacks (:332,:367)
             true = it["true"] if (task == "CSI" and attack_type == "untargeted") else None
             extra = dict(init=hsj_init) if args.attack == "hsj" else {}
             if args.companions > 0:
-                audio, comp = with_companions(items, idx, args.companions)
+                audio = audio_c
                 if hasattr(bob, "attack_universal"):   # (the PGD classes: PGD.attack keeps FakeBob.attack's plain signature)
-                    adv, flag = bob.attack_universal(audio, it["cp_path"], comp, threshold=threshold, true=true, target=it["target"],
-                                                     fs=fs, bits_per_sample=bits_per_sample)
+                    res = bob.attack_universal(audio, it["cp_path"], comp, threshold=threshold, true=true, target=it["target"],
+                                               fs=fs, bits_per_sample=bits_per_sample)
+                    adv, flag = res
                 else:
                     res = bob.attack(audio, it["cp_path"], threshold=threshold, true=true, target=it["target"], fs=fs,
                                      bits_per_sample=bits_per_sample, companions=comp, **extra)
                     adv, flag = res
                     print_votes(args.attack, it["name"], flag, res)
+                print_offsets(it["name"], res)
                 write(it["wav_path"], fs, adv)
                 with lock:
                     results[idx] = flag
@@ -542,6 +589,7 @@ def main(argv=None, model_factory=None, bob_factory=None):
                              target=it["target"], fs=fs, bits_per_sample=bits_per_sample, **extra)
             adv, flag = res
             print_votes(args.attack, it["name"], flag, res)
+            print_offsets(it["name"], res)
             if args.attack == "psy" and hasattr(res, "best_dist"):
                 print("psy %s: success %d, dist %.6g, over %d, l2 %.6g, snr %.2f dB, c %.3g" %
                       (it["name"], flag, res.best_dist, res.n_over, res.best_l2, res.snr_db, res.const))

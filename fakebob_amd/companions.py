@@ -106,14 +106,22 @@ class AttackResult(tuple):
       apply_perturbation(wavs)  the contract's clip-add of it onto other recordings -> a list of int16 arrays
       per_utterance     with companions: one dict per composed utterance (0 = the attacked one) -- audio_i16, score and
                         decision from the system's ordinary score / make_decisions, success; None without companions
+      per_offset        after an attack under a play offset (FakeBob(play_offset=S)) only -- the attribute is absent otherwise:
+                        one dict per utterance with the perturbation re-scored at each offset of play_offset.offset_grid(S)
+      apply_perturbation(wavs, offset=t)  the perturbation rotated circularly by t samples first (play_offset.compose)
     The flag is the loop's: it reads the MEAN loss over the utterances; per_utterance says which of them succeeded."""
 
-    def __new__(cls, adv, flag, perturbation, bits_per_sample=16, per_utterance=None):
+    def __new__(cls, adv, flag, perturbation, bits_per_sample=16, per_utterance=None, per_offset=None):
         self = tuple.__new__(cls, (adv, flag))
         self.perturbation_i16 = perturbation
         self.bits_per_sample = bits_per_sample
         self.per_utterance = per_utterance
+        if per_offset is not None:
+            self.per_offset = per_offset
         return self
 
-    def apply_perturbation(self, wavs):
-        return apply_perturbation(self.perturbation_i16, wavs, self.bits_per_sample)
+    def apply_perturbation(self, wavs, offset=0):
+        if offset == 0:
+            return apply_perturbation(self.perturbation_i16, wavs, self.bits_per_sample)
+        from .play_offset import apply_perturbation as rotated
+        return rotated(self.perturbation_i16, wavs, offset, self.bits_per_sample)

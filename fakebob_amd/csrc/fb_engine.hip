@@ -135,6 +135,11 @@ struct fb_engine {
   int comp_K1 = 0;              // companions set; with the call's own utterance K = comp_K1 + 1
   int64_t comp_N = 0;           // ... their length
   DevBuf comp_wav, comp_a0;     // the companions [K1][N] and the int16 cast of the call's original audio [N] (cast once per call)
+  // play offset (fb_set_play_offset; the "Play offset" section of fakebob_hip.h): play_S == 0 -- none
+  int64_t play_S = 0;           // every replica's perturbation is rotated by a tau of its own, uniform in 0 .. play_S
+  DevBuf wav_play, play_tau;    // k_play_compose's rows [B * r'][N] (padded to eight samples) and its offsets [B * r']
+  int play_launches = 0;        // k_play_compose launches since fb_set_play_offset (fb_debug_play_route)
+  int wb_play_launches = 0;     // k_wb_play_compose_t launches of the last white-box call (fb_debug_wb_play_route)
   // feature compression (fb_set_feature_compression; the stage contract of fakebob_hip.h): feco_iters == 0 -- off, the back
   // end reads `feats` / `row_off` as the front end wrote them
   double feco_ratio = 0.0;
@@ -857,6 +862,7 @@ struct FbScoreCall {
   int keep_iv_quad_rows = 1;     // ... rows 0 .. this - 1: every replica's under fb_set_wb_universal
   bool keep_air_sat = false;     // an air channel: k_air_conv also writes its saturation bytes to e->wb_air_sat (white box)
   bool keep_feco = false;        // feature compression: k_feature_compress also writes its final labels, counts and k's to e->wb_feco_* (white box)
+  int64_t play = 0;              // > 0 (fb_set_play_offset): k_play_compose writes the K * eot replicas, each under its own offset in 0 .. play
   int replicas() const { return K * eot; }
 };
 // The replicating / composing transform launch: rn.r replicas of every utterance of `in` (in_off[B_in + 1]; longest: n_max) --
@@ -883,12 +889,14 @@ static int launch_transform_replicas(fb_engine *e, const int16_t *in, const int6
 // FbScoreCall::keep_air_sat.
 static int launch_air_path(fb_engine *e, const int16_t *in, const int64_t *in_off, int B_in, int r, int eot, int64_t n_max,
                            size_t out_samples, const int64_t *out_off, const FbRngPoint &pt, const FbTfComp *cn, const int *stop,
-                           const int16_t **res, bool keep_sat = false) {
-  const int rows = B_in * r, L = e->air.L;
+                           const int16_t **res, bool keep_sat = false, int pre = 0) {
+  // pre > 0 (k_play_compose wrote `in`): the B_in rows are already the replicas -- row R is replica R % pre of utterance row
+  // R / pre and draws as such; the convolution takes one input row per output row (r = 1, cn null)
+  const int rows = B_in * r, L = e->air.L, draw_r = pre > 0 ? pre : r;
   FBCHK(e->wav_air.ensure(sizeof(int16_t) * out_samples));
   FBCHK(e->air_taps.ensure(sizeof(int16_t) * (size_t)rows * (size_t)L));
   if (keep_sat) FBCHK(e->wb_air_sat.ensure(out_samples));
-  fb_launch_air_taps(e->stream, fb_air_key(pt, e->air, r), 0, rows, e->air_taps.as<int16_t>(), nullptr, nullptr, stop);
+  fb_launch_air_taps(e->stream, fb_air_key(pt, e->air, draw_r), 0, rows, e->air_taps.as<int16_t>(), nullptr, nullptr, stop);
   fb_launch_air_conv(e->stream, in, in_off, rows, r, eot, n_max, e->air_taps.as<int16_t>(), L, e->wav_air.as<int16_t>(), out_off, cn, stop,
                      keep_sat ? e->wb_air_sat.as<unsigned char>() : nullptr);
   *res = e->wav_air.as<int16_t>();
@@ -899,7 +907,7 @@ static int launch_air_path(fb_engine *e, const int16_t *in, const int64_t *in_of
                               e->wav_tf.as<int16_t>(), stop);
   } else {  // the noise stages draw with (utterance row R / r, replica R % r); k_tf_power, the plain form, sums the channel's output rows
     FbTfRnd rn = fb_tf_rnd(pt, 1);
-    rn.pre = r;
+    rn.pre = draw_r;
     FBCHK(launch_transform_replicas(e, e->wav_air.as<int16_t>(), out_off, rows, n_max, e->wav_tf.as<int16_t>(), out_off, rn, nullptr, stop));
   }
   *res = e->wav_tf.as<int16_t>();
@@ -912,11 +920,39 @@ static int launch_air_path(fb_engine *e, const int16_t *in, const int64_t *in_of
 static int chained_wav(fb_engine *e, const FbScoreCall &call, const int64_t *off, int B, const int16_t **wav) {
   *wav = e->wav.as<int16_t>();
   const int r = call.replicas();
-  if (e->tf.n == 0 && r == 1 && e->air.L == 0) return FB_OK;
+  if (e->tf.n == 0 && r == 1 && e->air.L == 0 && call.play == 0) return FB_OK;
   if (B > 65535) return fb_fail(FB_E_LIMIT, "an input-transform chain takes batches of up to 65535 utterances");
   int64_t n_max = 0;
   for (int b = 0; b < B; ++b) n_max = std::max(n_max, off[b + 1] - off[b]);
   if (n_max > 0x7fffffffLL) return fb_fail(FB_E_LIMIT, "utterance longer than 2^31 samples");
+  if (call.play > 0) {
+    if (n_max <= call.play) return fb_fail(FB_E_ARG, "rows of %lld samples under a play offset of up to %lld", (long long)n_max, (long long)call.play);
+    // (fb_set_play_offset) one launch composes the B rows -- B / r NES rows of n_max samples each, r replicas of every one, each
+    // under its own offset -- into e->wav_play; what follows takes them as input that is already replicated
+    const FbTfComp cn{call.K, n_max, e->comp_a0.as<int16_t>(), e->comp_wav.as<int16_t>()};
+    FBCHK(e->wav_play.ensure(sizeof(int16_t) * ((size_t)off[B] + 8)));
+    FBCHK(e->play_tau.ensure(sizeof(uint32_t) * (size_t)B));
+    fb_launch_play_compose(e->stream, fb_play_key(call.pt, call.play), e->wav.as<int16_t>(), cn, call.eot, B / r, e->wav_play.as<int16_t>(),
+                           e->play_tau.as<uint32_t>(), call.stop);
+    e->play_launches += 1;
+    *wav = e->wav_play.as<int16_t>();
+    if (e->air.L > 0)
+      return launch_air_path(e, e->wav_play.as<int16_t>(), e->wav_off.as<int64_t>(), B, 1, call.eot, n_max, (size_t)off[B],
+                             e->wav_off.as<int64_t>(), call.pt, nullptr, call.stop, wav, call.keep_air_sat, r);
+    if (e->tf.n == 0) return FB_OK;  // the buffer is the batch the front end reads
+    FBCHK(e->wav_tf.ensure(sizeof(int16_t) * (size_t)off[B]));
+    if (tf_noise_stages(e->tf, false) == 0) {
+      fb_launch_input_transform(e->stream, e->tf, e->tf_taps.as<double>(), e->wav_play.as<int16_t>(), e->wav_off.as<int64_t>(), B, n_max,
+                                e->wav_tf.as<int16_t>(), call.stop);
+    } else {  // (row R: utterance row R / r, replica R % r; k_tf_power, the plain form, sums the composed, offset rows)
+      FbTfRnd rn = fb_tf_rnd(call.pt, 1);
+      rn.pre = r;
+      FBCHK(launch_transform_replicas(e, e->wav_play.as<int16_t>(), e->wav_off.as<int64_t>(), B, n_max, e->wav_tf.as<int16_t>(),
+                                      e->wav_off.as<int64_t>(), rn, nullptr, call.stop));
+    }
+    *wav = e->wav_tf.as<int16_t>();
+    return FB_OK;
+  }
   if (e->air.L > 0) {  // (fb_set_air_channel) the channel writes the replicas, the chain follows row by row
     const FbTfComp cn{call.K, e->comp_N, e->comp_a0.as<int16_t>(), e->comp_wav.as<int16_t>()};
     return launch_air_path(e, e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), B / r, r, call.eot, n_max, (size_t)off[B],
@@ -1251,7 +1287,7 @@ static int run_scoring(fb_engine *e, FbScoreCall &call, int B, int total_frames)
     FbIvTail tail = {};
     {
       const char *tv_env = getenv("FB_IV_TAIL");
-      const bool split = (tv_env && strcmp(tv_env, "split") == 0) || call.replicas() > 1;  // (fb_set_eot: k_loss_eot follows k_iv_backend)
+      const bool split = (tv_env && strcmp(tv_env, "split") == 0) || call.replicas() > 1 || call.play > 0;  // (fb_set_eot: k_loss_eot follows k_iv_backend)
       if (!e->iv_tail_counter.p) {
         FBCHK(e->iv_tail_counter.ensure(sizeof(int)));
         HIPCHK(hipMemsetAsync(e->iv_tail_counter.p, 0, sizeof(int), s));
@@ -1653,26 +1689,43 @@ static int check_params(fb_engine *e, const fb_nes_params *p, int64_t N) {
 static inline int nes_bits(const fb_nes_params *p) { return p->bits_per_sample ? p->bits_per_sample : 16; }
 // replicas of every NES row the front end scores in the native NES calls: K * eot (fb_set_companions, fb_set_eot)
 static inline int nes_replicas(const fb_engine *e) { return (e->comp_K1 + 1) * e->eot; }
+// fb_set_play_offset: the loop the offset rotates has the utterance's length, so every offset must lie inside it
+static int check_play_length(const fb_engine *e, int64_t N) {
+  if (e->play_S > 0 && N <= e->play_S)
+    return fb_fail(FB_E_ARG, "the audio has %lld samples, the play offset (fb_set_play_offset) goes up to %lld: it must stay below the length",
+                   (long long)N, (long long)e->play_S);
+  return FB_OK;
+}
+// the calls that do not model a play offset refuse it by name
+static int refuse_play(const fb_engine *e, const char *who) {
+  if (e && e->play_S > 0)
+    return fb_fail(FB_E_STATE, "%s does not run under a play offset (fb_set_play_offset(%lld)): not in this version, set 0", who,
+                   (long long)e->play_S);
+  return FB_OK;
+}
 // The checks and buffers of a native NES call that scale with the replicas.  B: the rows of the NES batch.
+// composes: the call composes its rows under the play offset when one is set (every native NES and white-box entry; false: a
+// hook that ignores the setting) -- the offsets must then stay below N, which k_play_compose's single wrap relies on.
 static int prepare_nes_batch(fb_engine *e, int64_t N, int B);
-static int prepare_nes_replicas(fb_engine *e, int64_t N, int B) {
+static int prepare_nes_replicas(fb_engine *e, int64_t N, int B, bool composes = true) {
   const int r = nes_replicas(e);
+  if (composes) FBCHK(check_play_length(e, N));
   if (e->comp_K1 > 0 && N != e->comp_N)
     return fb_fail(FB_E_ARG, "the audio has %lld samples, the companions (fb_set_companions) %lld", (long long)N, (long long)e->comp_N);
   if (r > 32) return fb_fail(FB_E_ARG, "utterances * eot = %d replicas per NES row: at most 32", r);
   if ((int64_t)B * r > 65535)
     return fb_fail(FB_E_LIMIT, "(samples_per_draw + 1) * utterances * eot = %lld rows: a scoring batch takes up to 65535", (long long)B * r);
   FBCHK(prepare_nes_batch(e, N, B * r));
-  if (r > 1) {
+  if (r > 1 || e->play_S > 0) {
     FBCHK(e->eot_sc.ensure(sizeof(double) * (size_t)B * r * (size_t)std::max(fb_num_speakers(e), 1)));
     FBCHK(e->eot_l.ensure(sizeof(double) * (size_t)B * r));
   }
-  if (e->comp_K1 > 0) FBCHK(e->comp_a0.ensure(sizeof(int16_t) * (size_t)N));
+  if (e->comp_K1 > 0 || e->play_S > 0) FBCHK(e->comp_a0.ensure(sizeof(int16_t) * (size_t)N));
   return FB_OK;
 }
 // a_0 of the composition: the int16 cast of the call's original audio (x: device float64 [N]), once per call
 static void cast_a0(fb_engine *e, const fb_nes_params *p, const double *x, int64_t N) {
-  if (e->comp_K1 > 0) fb_launch_quantize(e->stream, x, N, nes_bits(p), e->comp_a0.as<int16_t>());
+  if (e->comp_K1 > 0 || e->play_S > 0) fb_launch_quantize(e->stream, x, N, nes_bits(p), e->comp_a0.as<int16_t>());
 }
 
 // (re)builds the equal-length batch layout of B utterances of N samples
@@ -1772,7 +1825,7 @@ static FbLoopKnobs loop_knobs(const fb_engine *e, const FbScorer &sc) {
     k.fuse_upd = true;
   } else if (sc.kind == FB_SCORER_NATIVE) {
     k.look = attack_batch();
-    k.fuse_fin = fb_fuse_part(e, 1) && nes_replicas(e) == 1;  // (fb_set_eot, fb_set_companions: the finalisation, then k_loss_eot)
+    k.fuse_fin = fb_fuse_part(e, 1) && nes_replicas(e) == 1 && e->play_S == 0;  // (fb_set_eot, fb_set_companions, fb_set_play_offset: the finalisation, then k_loss_eot)
     k.fuse_upd = fb_fuse_part(e, 2);
     const char *fu = getenv("FB_FUSE_UPD");
     k.upd_in_fin = !(fu && fu[0] == '0');
@@ -1797,6 +1850,7 @@ static int enqueue_get_grad(fb_engine *e, const fb_nes_params *p, int64_t N, uin
                             const FbUpdArgs *upd = nullptr, bool *upd_done = nullptr) {
   const int half = p->samples_per_draw / 2, B = 2 * half + 1;
   const int r = nes_replicas(e), BR = B * r;  // fb_set_eot, fb_set_companions: the front end scores r replicas of every row
+  const bool rep = r > 1 || e->play_S > 0;    // ... and with a play offset the call takes that route at r = 1 too
   int ndp = 0;
   const int *stop = ctl ? &ctl->stop : nullptr;
   if (ctl && e->pre_iter == (long long)iter && !noise_dev) {
@@ -1805,7 +1859,7 @@ static int enqueue_get_grad(fb_engine *e, const fb_nes_params *p, int64_t N, uin
     fb_launch_perturb(e->stream, e->adver.as<double>(), with_dist ? e->audio.as<double>() : nullptr, N, half,
                       p->sigma, p->seed, iter, p->stream, noise_dev, e->wav.as<int16_t>(),
                       e->dist_part.as<double>(), &ndp, noise_dev ? nullptr : e->zbuf.as<float>(), stop, nes_bits(p));
-    record_nes_batch(e, iter, N, half, r == 1, !noise_dev);  // (r > 1: the composed rows are pinned elsewhere)
+    record_nes_batch(e, iter, N, half, !rep, !noise_dev);  // (replicated, or rotated by a play offset: the rows scored are pinned elsewhere)
   }
   e->pre_iter = -1;
   // GMM systems inside the device-controlled loop: finalisation and loss share one launch
@@ -1815,10 +1869,11 @@ static int enqueue_get_grad(fb_engine *e, const fb_nes_params *p, int64_t N, uin
   FbScoreCall call{FbRngPoint{p->seed, p->stream, iter, 0}};
   call.eot = e->eot;
   call.K = e->comp_K1 + 1;
+  call.play = e->play_S;
   call.stop = stop;
   call.defer_finalize = fuse_fin;
   FbIvTail t = {};
-  if (e->kind == 1 && r == 1) {  // i-vector systems: the loss body rides in the tail of the solve kernel when the batch allows it
+  if (e->kind == 1 && !rep) {  // i-vector systems: the loss body rides in the tail of the solve kernel when the batch allows it
     t.task = p->task; t.attack_type = p->attack_type;
     t.z_mean = e->zmean.as<double>(); t.z_std = e->zstd.as<double>();
     t.threshold = p->threshold; t.adver_thresh = p->adver_thresh;
@@ -1829,7 +1884,7 @@ static int enqueue_get_grad(fb_engine *e, const fb_nes_params *p, int64_t N, uin
     call.tail_loss = &t;
   }
   FBCHK(run_scoring(e, call, BR, e->h_frame_off[BR]));
-  if (r > 1) {
+  if (rep) {
     fb_launch_loss_eot(e->stream, e->raw.as<double>(), e->tv.as<int>(), B, r, e->n_out, p->task, e->kind, p->attack_type,
                        e->zmean.as<double>(), e->zstd.as<double>(), p->threshold, p->adver_thresh, p->target, p->true_label,
                        e->dist_part.as<double>(), with_dist ? ndp : 0, e->eot_sc.as<double>(), e->eot_l.as<double>(),
@@ -2416,6 +2471,11 @@ static int wb_check(fb_engine *e, const fb_nes_params *p, const double *audio, i
   if (e->eot > 1 && !e->wb_bpda) return fb_fail(FB_E_STATE, "white-box gradients: fb_set_eot(%d) is in force (set 1)", e->eot);
   // (the universal perturbation has the fifth switch, fb_set_wb_universal: refused with the other four on as well)
   if (e->comp_K1 > 0 && !e->wb_universal) return fb_fail(FB_E_STATE, "white-box gradients: companions are set (fb_set_companions: clear them)");
+  // (a play offset rides on the universal path: k_wb_play_compose_t in k_wb_compose_t's place)
+  if (e->play_S > 0 && !e->wb_universal)
+    return fb_fail(FB_E_STATE, "white-box gradients: a play offset is set (fb_set_play_offset(%lld)) without fb_set_wb_universal: not in this version",
+                   (long long)e->play_S);
+  FBCHK(check_play_length(e, N));
   if (e->tf.n > 0 && !e->wb_bpda)
     return fb_fail(FB_E_STATE, "white-box gradients: an input-transform chain is set (no BPDA through defences in this version)");
   // (the channel's transpose is a switch of its own, fb_set_wb_air: refused with the other two on as well)
@@ -2481,14 +2541,15 @@ static int wb_prepare(fb_engine *e, int64_t N, int T, bool need_gmm) {
   // (the replicas of the one row: the EOT draws, times the utterances of a universal perturbation -- wb_check: only under
   //  fb_set_wb_universal)
   const size_t R = (size_t)nes_replicas(e);
-  const bool uni = e->comp_K1 > 0;
+  // (a play offset takes the universal route at K = 1 too; its chain transpose reads the composed rows from e->wav_play)
+  const bool play = e->play_S > 0, uni = e->comp_K1 > 0 || play;
   if (e->wb_bpda || (uni && e->tf.n > 0)) FBCHK(e->wb_gj.ensure(sizeof(double) * (size_t)N));
   if (e->wb_air && e->air.L > 0) {  // the R replicas' cotangents are kept for the one k_air_conv_t launch behind the loop
     FBCHK(e->wb_air_cot.ensure(sizeof(double) * R * (size_t)N));
-    if (R > 1) FBCHK(e->wb_air_dx.ensure(sizeof(double) * R * (size_t)N));
-  } else if (uni) {                 // ... and without a channel for k_wb_compose_t
+    if (R > 1 || play) FBCHK(e->wb_air_dx.ensure(sizeof(double) * R * (size_t)N));
+  } else if (uni) {                 // ... and without a channel for k_wb_compose_t / k_wb_play_compose_t
     FBCHK(e->wb_uni_cot.ensure(sizeof(double) * R * (size_t)N));
-    if (e->tf.n > 0) FBCHK(e->wb_uni_rows.ensure(sizeof(int16_t) * (size_t)(e->comp_K1 + 1) * (size_t)N));
+    if (e->tf.n > 0 && !play) FBCHK(e->wb_uni_rows.ensure(sizeof(int16_t) * (size_t)(e->comp_K1 + 1) * (size_t)N));
   }
   if (e->wb_frontend && e->feco_iters > 0) {  // the R replicas' kept assignments, and one replica's cotangent on its voiced rows
     FBCHK(e->wb_feco_label.ensure(sizeof(int) * R * (size_t)T));
@@ -2567,14 +2628,18 @@ static void wb_launch_feco_t(fb_engine *e, int j, int T, const int *stop) {
 // With companions (fb_set_wb_universal) j is rho = u * eot + j': without a channel the chain read utterance u's COMPOSED row,
 // which wb_enqueue wrote to e->wb_uni_rows (the forward had it in LDS only), and its SNR power is tf_power[0 * K + u], as the
 // forward indexed it; the noise counters are (utterance row 0, replica rho) there as well.
+// play: the forward of THIS call composed under a play offset (FbScoreCall::play > 0; a hook whose forward ignores the setting
+// passes false whatever the engine holds).  Without a channel the chain then read replica j's row of e->wav_play, composed under
+// ITS offset, and k_tf_power, the plain form, summed those rows: tf_power[j], as under a channel.
 static int wb_launch_chain_t(fb_engine *e, const FbRngPoint &pt, int j, int64_t N, const double *cot, double *grad, bool accumulate,
-                             const int *stop) {
+                             const int *stop, bool play) {
   const bool air = e->air.L > 0;
   const int u = e->comp_K1 > 0 ? j / e->eot : 0;
   FbTfRnd rn = fb_tf_rnd(pt, e->eot);
-  rn.power = tf_noise_stages(e->tf, true) > 0 ? e->tf_power.as<unsigned long long>() + (air ? j : u) : nullptr;
+  rn.power = tf_noise_stages(e->tf, true) > 0 ? e->tf_power.as<unsigned long long>() + (air || play ? j : u) : nullptr;
   const int16_t *row = air ? e->wav_air.as<int16_t>() + (size_t)j * (size_t)N
-                           : e->comp_K1 > 0 ? e->wb_uni_rows.as<int16_t>() + (size_t)u * (size_t)N : e->wav.as<int16_t>();
+                       : play ? e->wav_play.as<int16_t>() + (size_t)j * (size_t)N
+                       : e->comp_K1 > 0 ? e->wb_uni_rows.as<int16_t>() + (size_t)u * (size_t)N : e->wav.as<int16_t>();
   if (!fb_launch_wb_chain_t(e->stream, e->tf, e->tf_taps.as<double>(), row, N, rn, j, cot, grad, accumulate ? 1 : 0, stop))
     return fb_fail(FB_E_HIP, "k_wb_chain_t: %zu bytes of LDS were refused", fb_wb_chain_t_lds_bytes(e->tf));
   e->wb_route[FB_WB_ROUTE_CHAIN_T] += 1;
@@ -2582,7 +2647,15 @@ static int wb_launch_chain_t(fb_engine *e, const FbRngPoint &pt, int j, int64_t 
 }
 // the composition transposed (fb_set_wb_universal), ONE launch: the R = K * eot cotangents cot [R][N] on the composed rows, the
 // un-replicated q still in e->wav, a_0 and the companions give out [N], rho ascending
-static void wb_launch_compose_t(fb_engine *e, const double *cot, int64_t N, double *out, const int *stop) {
+// play (the forward of this call composed under a play offset): k_wb_play_compose_t takes its place, at K = 1 too: the offsets
+// are the forward's, still in e->play_tau.
+static void wb_launch_compose_t(fb_engine *e, const double *cot, int64_t N, double *out, const int *stop, bool play) {
+  if (play) {
+    fb_launch_wb_play_compose_t(e->stream, cot, e->wav.as<int16_t>(), e->comp_a0.as<int16_t>(), e->comp_wav.as<int16_t>(),
+                                e->play_tau.as<uint32_t>(), e->comp_K1 + 1, e->eot, N, out, stop);
+    e->wb_play_launches += 1;
+    return;
+  }
   fb_launch_wb_compose_t(e->stream, cot, e->wav.as<int16_t>(), e->comp_a0.as<int16_t>(), e->comp_wav.as<int16_t>(), e->comp_K1 + 1, e->eot,
                          N, out, stop);
   e->wb_universal_launches += 1;
@@ -2590,12 +2663,13 @@ static void wb_launch_compose_t(fb_engine *e, const double *cot, int64_t N, doub
 // the channel's transpose for all r replicas of the one row (fb_set_wb_air), ONE launch: the cotangents e->wb_air_cot [r][N] on
 // the channel's output, the forward's saturation bytes and the forward's own responses in e->air_taps -- nothing is redrawn --
 // give dx[r][N]; out (device, [N]) = their sum, j ascending (r = 1: k_air_conv_t writes out itself)
-static void wb_launch_air_t(fb_engine *e, int r, int64_t N, double *out, const int *stop) {
-  double *dx = r > 1 ? e->wb_air_dx.as<double>() : out;
+// play: as in wb_launch_chain_t (k_wb_play_compose_t reads dx at rotated indices: never in place)
+static void wb_launch_air_t(fb_engine *e, int r, int64_t N, double *out, const int *stop, bool play) {
+  double *dx = r > 1 || play ? e->wb_air_dx.as<double>() : out;
   fb_launch_air_conv_t(e->stream, e->wb_air_cot.as<double>(), e->wb_air_sat.as<unsigned char>(), r, N, e->air_taps.as<int16_t>(), e->air.L,
                        dx, stop);
   e->wb_air_launches += 1;
-  if (e->comp_K1 > 0) wb_launch_compose_t(e, dx, N, out, stop);  // (r = K * eot: dx_rho is the cotangent on utterance u(rho)'s composed row)
+  if (e->comp_K1 > 0 || play) wb_launch_compose_t(e, dx, N, out, stop, play);  // (r = K * eot: dx_rho is the cotangent on utterance u(rho)'s composed row)
   else if (r > 1) fb_launch_air_sum_t(e->stream, dx, r, N, out, stop);
 }
 
@@ -2622,8 +2696,9 @@ static void wb_launch_air_t(fb_engine *e, int r, int64_t N, double *out, const i
 static int wb_enqueue(fb_engine *e, const fb_nes_params *q, int64_t N, uint32_t it, bool with_dist, FbCtlDev *ctl, double *trace_dev) {
   const int *stop = ctl ? &ctl->stop : nullptr;
   // the replicas of the one row: the EOT draws, and under fb_set_wb_universal rho = u * eot + j over the K composed utterances
+  // (with a play offset the call takes the universal, replicated route whatever K and r are)
   const int K = e->comp_K1 + 1, r = K * e->eot;
-  const bool uni = K > 1;
+  const bool play = e->play_S > 0, uni = K > 1 || play, rep = r > 1 || play;
   int ndp = 0;
   fb_launch_perturb(e->stream, e->adver.as<double>(), with_dist ? e->audio.as<double>() : nullptr, N, 0, q->sigma, q->seed, it,
                     q->stream, nullptr, e->wav.as<int16_t>(), e->dist_part.as<double>(), &ndp, nullptr, stop, nes_bits(q));
@@ -2632,6 +2707,7 @@ static int wb_enqueue(fb_engine *e, const fb_nes_params *q, int64_t N, uint32_t 
   FbScoreCall call{pt};
   call.eot = e->eot;
   call.K = K;
+  call.play = e->play_S;
   call.stop = stop;
   call.keep_iv_quad = e->kind == 1;
   call.keep_iv_quad_rows = e->wb_universal ? r : 1;  // (r > 1 on an i-vector system: wb_check, only under fb_set_wb_universal)
@@ -2642,7 +2718,7 @@ static int wb_enqueue(fb_engine *e, const fb_nes_params *q, int64_t N, uint32_t 
   const int T = e->h_frame_off[1];
   FBCHK(run_scoring(e, call, r, e->h_frame_off[r]));
   const double scale = ldexp(1.0, nes_bits(q) - 1);
-  if (r > 1) {
+  if (rep) {
     fb_launch_loss_eot(e->stream, e->raw.as<double>(), e->tv.as<int>(), 1, r, e->n_out, q->task, e->kind, q->attack_type,
                        e->zmean.as<double>(), e->zstd.as<double>(), q->threshold, q->adver_thresh, q->target, q->true_label,
                        e->dist_part.as<double>(), with_dist ? ndp : 0, e->eot_sc.as<double>(), e->eot_l.as<double>(),
@@ -2661,17 +2737,17 @@ static int wb_enqueue(fb_engine *e, const fb_nes_params *q, int64_t N, uint32_t 
   //  here either; a chain without a channel read utterance u's composed row, which existed in the forward's LDS only: the K
   //  rows are written once per iteration.  At K = 1 none of this is queued.)
   const bool through_chain = e->tf.n > 0 || (r > 1 && !air && !uni);
-  if (uni && e->tf.n > 0 && !air)
+  if (uni && e->tf.n > 0 && !air && !play)
     fb_launch_wb_compose_rows(e->stream, e->wav.as<int16_t>(), e->comp_a0.as<int16_t>(), e->comp_wav.as<int16_t>(), K, N,
                               e->wb_uni_rows.as<int16_t>(), stop);
   const int S = fb_num_speakers(e);
   for (int j = 0; j < r; ++j) {
-    if (r > 1 && e->kind == 1) {
+    if (rep && e->kind == 1) {
       fb_launch_wb_iv_ctl_rep(e->stream, e->eot_sc.as<double>() + (size_t)j * S, e->scores.as<double>(), e->nes_out.as<FbNesDev>(), S, r,
                               q->task, q->attack_type, e->zstd.as<double>(), q->threshold, q->target, q->true_label,
                               e->wb_w.as<double>(), ctl, j == 0 ? 1 : 0, trace_dev, (int)it);
       e->wb_route[FB_WB_ROUTE_CTL_REP] += 1;
-    } else if (r > 1) {
+    } else if (rep) {
       fb_launch_wb_ctl_rep(e->stream, e->eot_sc.as<double>() + (size_t)j * S, e->scores.as<double>(), e->nes_out.as<FbNesDev>(),
                            e->gmm.M, r, q->task, q->attack_type, e->zstd.as<double>(), q->threshold, q->target, q->true_label,
                            e->wb_w.as<double>(), ctl, j == 0 ? 1 : 0, trace_dev, (int)it);
@@ -2686,7 +2762,7 @@ static int wb_enqueue(fb_engine *e, const fb_nes_params *q, int64_t N, uint32_t 
       e->wb_route[FB_WB_ROUTE_CTL] += 1;
     }
     // (row_off[0] = 0 and tv[0] = row_off[1]: replica 0 of an unreplicated batch is what the launch always took)
-    if (e->kind == 1 && r > 1) {  // replica j's own i-vector, quad, rows (under feature compression its k_j centres)
+    if (e->kind == 1 && rep) {  // replica j's own i-vector, quad, rows (under feature compression its k_j centres)
       wb_launch_iv_backend_t(e, e->iv_ivec.as<double>() + (size_t)j * (size_t)e->iv.R, stop);
       wb_launch_iv_backward(e, feco ? e->wb_feco_k.as<int>() + j : e->tv.as<int>() + j, T, stop, j, e->row_off.as<int>() + j);
     } else if (e->kind == 1) {
@@ -2695,8 +2771,8 @@ static int wb_enqueue(fb_engine *e, const fb_nes_params *q, int64_t N, uint32_t 
     } else {
       // (under feature compression the rows scored are replica j's k_j centres -- the kept k, not the VAD's count e->tv[j],
       //  which the front-end backward still checks its mask against; e->feats / e->row_off are the compressed pair)
-      const int *n_rows = feco ? e->wb_feco_k.as<int>() + j : r > 1 ? e->tv.as<int>() + j : e->row_off.as<int>() + 1;
-      wb_launch_gmm_backward(e, n_rows, T, stop, r > 1 ? e->row_off.as<int>() + j : nullptr);
+      const int *n_rows = feco ? e->wb_feco_k.as<int>() + j : rep ? e->tv.as<int>() + j : e->row_off.as<int>() + 1;
+      wb_launch_gmm_backward(e, n_rows, T, stop, rep ? e->row_off.as<int>() + j : nullptr);
     }
     if (feco) wb_launch_feco_t(e, j, T, stop);
     // replica j's cotangent on the channel's output, or (a universal perturbation without a channel) on its composed row
@@ -2709,10 +2785,10 @@ static int wb_enqueue(fb_engine *e, const fb_nes_params *q, int64_t N, uint32_t 
     wb_launch_frontend_vjp(e, e->fe_wav, j, N, T, scale, fe_out, stop, feco ? e->wb_xbar.as<double>() : nullptr,
                            e->cfg.dither > 0.0 ? &dith : nullptr);
     e->wb_route[FB_WB_ROUTE_BACKWARD] += 1;
-    if (through_chain) FBCHK(wb_launch_chain_t(e, pt, j, N, e->wb_gj.as<double>(), slot ? slot : e->grad.as<double>(), !slot && j > 0, stop));
+    if (through_chain) FBCHK(wb_launch_chain_t(e, pt, j, N, e->wb_gj.as<double>(), slot ? slot : e->grad.as<double>(), !slot && j > 0, stop, play));
   }
-  if (air) wb_launch_air_t(e, r, N, e->grad.as<double>(), stop);
-  else if (uni) wb_launch_compose_t(e, e->wb_uni_cot.as<double>(), N, e->grad.as<double>(), stop);
+  if (air) wb_launch_air_t(e, r, N, e->grad.as<double>(), stop, play);
+  else if (uni) wb_launch_compose_t(e, e->wb_uni_cot.as<double>(), N, e->grad.as<double>(), stop, play);
   return FB_OK;
 }
 
@@ -2725,6 +2801,7 @@ static void wb_call_begin(fb_engine *e) {
   e->wb_air_launches = 0;
   e->wb_feco_launches = 0;
   e->wb_universal_launches = 0;
+  e->wb_play_launches = 0;
 }
 
 static int wb_status_check(fb_engine *e, int status) {
@@ -2764,7 +2841,7 @@ extern "C" int fb_get_grad_wb_from(fb_engine *e, const fb_nes_params *p, const d
   FBCHK(ensure_nes_buffers(e, N, 1));
   FBCHK(wb_prepare(e, N, e->h_frame_off[1], true));
   FBCHK(h2d(e, e->adver.p, audio, sizeof(double) * (size_t)N));
-  if (e->comp_K1 > 0) {  // a_0: cast once per call, by the batch's cast rule
+  if (e->comp_K1 > 0 || e->play_S > 0) {  // a_0: cast once per call, by the batch's cast rule
     if (original) FBCHK(h2d(e, e->audio.p, original, sizeof(double) * (size_t)N));
     cast_a0(e, &q, original ? e->audio.as<double>() : e->adver.as<double>(), N);
   }
@@ -3046,6 +3123,7 @@ extern "C" int fb_attack_wb(fb_engine *e, const fb_nes_params *p, const double *
 static int cw2_check(const fb_engine *e, const fb_nes_params *p, const fb_cw2_params *c) {
   // refused by name whatever the white-box switches say: none of them has a CW2 test of its own in this version
   if (e->comp_K1 > 0) return fb_fail(FB_E_STATE, "CW2: companions are set (fb_set_companions: clear them)");
+  FBCHK(refuse_play(e, "CW2 / the masking attack"));
   if (e->air.L > 0) return fb_fail(FB_E_STATE, "CW2: an air channel is set (fb_set_air_channel: clear it)");
   if (e->feco_iters > 0) return fb_fail(FB_E_STATE, "CW2: feature compression is on (fb_set_feature_compression: switch it off)");
   if (e->cfg.dither > 0.0) return fb_fail(FB_E_STATE, "CW2: dither %g > 0 (set 0)", e->cfg.dither);
@@ -3501,6 +3579,7 @@ extern "C" int fb_attack_iter_seconds(fb_engine *e, double *seconds, int n) {
 static int query_replicas(const fb_engine *e, const char *who, int *r, int *quorum) {
   *r = 1;
   *quorum = 1;
+  FBCHK(refuse_play(e, who));  // (with or without fb_set_query_eot)
   if (e->query_quorum == FB_QUORUM_OFF) {
     if (e->eot > 1)
       return fb_fail(FB_E_STATE, "%s does not run under expectation over transformation (fb_set_eot(%d)): set 1", who, e->eot);
@@ -4539,6 +4618,7 @@ extern "C" int fb_estimate_threshold(fb_engine *e, const fb_nes_params *p_in, do
     return fb_fail(FB_E_STATE, "fb_estimate_threshold does not run under expectation over transformation (fb_set_eot(%d)): set 1", e->eot);
   if (e && e->comp_K1 > 0)
     return fb_fail(FB_E_STATE, "fb_estimate_threshold does not run with companion utterances (fb_set_companions: %d set): clear them", e->comp_K1);
+  FBCHK(refuse_play(e, "fb_estimate_threshold"));
   fb_nes_params q = *p_in;
   q.attack_type = FB_UNTARGETED;  // :73-74
   FbScorer sc{FB_SCORER_NATIVE};
@@ -5065,7 +5145,17 @@ extern "C" int fb_debug_compose(fb_engine *e, const int16_t *q, int B, int64_t N
   FBCHK(h2d(e, d_a0.p, a0, sizeof(int16_t) * (size_t)N));
   const FbTfComp cn{K, N, d_a0.as<int16_t>(), e->comp_wav.as<int16_t>()};
   const int16_t *res = e->wav_tf.as<int16_t>();
-  if (e->air.L > 0)
+  if (e->play_S > 0) {  // (fb_set_play_offset) the NES calls' own path whole: k_play_compose, the air and chain launches on its rows,
+                        // and the codec where one is set -- in place on the composed buffer when nothing stands between
+    FBCHK(check_play_length(e, N));
+    FBCHK(e->comp_a0.ensure(sizeof(int16_t) * (size_t)N));
+    FBCHK(h2d(e, e->comp_a0.p, a0, sizeof(int16_t) * (size_t)N));
+    FbScoreCall call{FbRngPoint{seed, stream, epoch, 0}};
+    call.eot = r;
+    call.K = K;
+    call.play = e->play_S;
+    FBCHK(transformed_wav(e, call, off.data(), B * R, &res));
+  } else if (e->air.L > 0)
     FBCHK(launch_air_path(e, e->wav.as<int16_t>(), e->wav_off.as<int64_t>(), B, R, r, N, (size_t)B * (size_t)N * R, e->wav_off.as<int64_t>(),
                           FbRngPoint{seed, stream, epoch, 0}, K > 1 ? &cn : nullptr, nullptr, &res));
   else
@@ -5073,6 +5163,114 @@ extern "C" int fb_debug_compose(fb_engine *e, const int16_t *q, int B, int64_t N
                                     e->wav_off.as<int64_t>(), fb_tf_rnd(FbRngPoint{seed, stream, epoch, 0}, r), &cn, nullptr));
   HIPCHK(hipGetLastError());
   FBCHK(d2h(e, out, res, bytes * R));
+  FBCHK(sync_stream(e));
+  return FB_OK;
+}
+
+// ---- play offset: the perturbation plays on a loop, the victim speaks whenever they speak
+extern "C" int fb_set_play_offset(fb_engine *e, int64_t S) {
+  if (!e) return fb_fail(FB_E_ARG, "null engine");
+  if (S < 0 || S > 0x7ffffffeLL) return fb_fail(FB_E_ARG, "play offset %lld outside 0 .. 2^31 - 2", (long long)S);
+  e->play_S = S;
+  e->play_launches = 0;
+  e->bench_it = e->nes_rec.iter = -1;  // an attack fb_bench_nes left resident was laid out for the previous setting
+  return FB_OK;
+}
+
+extern "C" int fb_debug_play_offsets(fb_engine *e, uint64_t seed, uint32_t stream, uint32_t epoch, uint32_t utt0, int B, int r,
+                                     uint32_t *tau_out) {
+  if (!e || !tau_out || B <= 0 || r < 1 || r > 32 || (int64_t)B * r > 65535) return fb_fail(FB_E_ARG, "bad argument");
+  if (e->play_S <= 0) return fb_fail(FB_E_STATE, "no play offset is set: fb_set_play_offset first");
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  DevBuf d_tau;
+  FBCHK(d_tau.ensure(sizeof(uint32_t) * (size_t)B * r));
+  fb_launch_play_offsets(e->stream, fb_play_key(FbRngPoint{seed, stream, epoch, utt0}, e->play_S), r, B * r, d_tau.as<uint32_t>());
+  HIPCHK(hipGetLastError());
+  FBCHK(d2h(e, tau_out, d_tau.p, sizeof(uint32_t) * (size_t)B * r));
+  FBCHK(sync_stream(e));
+  return FB_OK;
+}
+
+extern "C" int fb_debug_play_route(fb_engine *e, int *n_launches) {
+  if (!e || !n_launches) return fb_fail(FB_E_ARG, "null argument");
+  *n_launches = e->play_launches;
+  return FB_OK;
+}
+
+// k_play_compose alone: milliseconds per launch (device events around `reps` launches) on B rows of n samples, K utterances
+// (K - 1 companions of a fixed pattern) and eot draws of each, offsets up to S = n - 1 at (seed, stream) = (1, 0)
+extern "C" int fb_bench_play_compose(fb_engine *e, int B, int64_t n, int K, int eot, int reps, double *ms) {
+  if (!e || !ms || B < 1 || K < 1 || eot < 1 || K * eot > 32 || (int64_t)B * K * eot > 65535 || n < 2 || n > 0x7fffffffLL || reps < 1)
+    return fb_fail(FB_E_ARG, "bad argument");
+  const int r = K * eot;
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  DevBuf d_q, d_a0, d_comp, d_out, d_tau;
+  FBCHK(d_q.ensure(sizeof(int16_t) * (size_t)B * (size_t)n));
+  if (K > 1) {
+    FBCHK(d_comp.ensure(sizeof(int16_t) * (size_t)(K - 1) * (size_t)n));
+    HIPCHK(hipMemsetAsync(d_comp.p, 0x05, sizeof(int16_t) * (size_t)(K - 1) * (size_t)n, e->stream));
+  }
+  FBCHK(d_a0.ensure(sizeof(int16_t) * (size_t)n));
+  FBCHK(d_out.ensure(sizeof(int16_t) * ((size_t)B * r * (size_t)n + 8)));
+  FBCHK(d_tau.ensure(sizeof(uint32_t) * (size_t)B * r));
+  HIPCHK(hipMemsetAsync(d_q.p, 0x11, sizeof(int16_t) * (size_t)B * (size_t)n, e->stream));
+  HIPCHK(hipMemsetAsync(d_a0.p, 0x07, sizeof(int16_t) * (size_t)n, e->stream));
+  const FbTfComp cn{K, n, d_a0.as<int16_t>(), K > 1 ? d_comp.as<int16_t>() : nullptr};
+  const FbPlay pk = fb_play_key(FbRngPoint{1, 0, 0, 0}, n - 1);
+  auto launch = [&]() { fb_launch_play_compose(e->stream, pk, d_q.as<int16_t>(), cn, eot, B, d_out.as<int16_t>(), d_tau.as<uint32_t>(), nullptr); };
+  launch();
+  HIPCHK(hipEventRecord(e->ev0, e->stream));
+  for (int i = 0; i < reps; ++i) launch();
+  HIPCHK(hipEventRecord(e->ev1, e->stream));
+  HIPCHK(hipEventSynchronize(e->ev1));
+  float t = 0.f;
+  HIPCHK(hipEventElapsedTime(&t, e->ev0, e->ev1));
+  *ms = (double)t / reps;
+  FBCHK(sync_stream(e));
+  HIPCHK(hipGetLastError());
+  return FB_OK;
+}
+
+extern "C" int fb_debug_wb_play_route(fb_engine *e, int *n_launches) {
+  if (!e || !n_launches) return fb_fail(FB_E_ARG, "null argument");
+  *n_launches = e->wb_play_launches;
+  return FB_OK;
+}
+
+// Test hook: k_wb_play_compose_t alone, ONE launch, on arrays handed in: cot [K * eot][n], q / a0 [n], comp [K - 1][n] (K = 1: not
+// read), tau [K * eot], every one below n
+extern "C" int fb_debug_wb_play_compose_t(fb_engine *e, const double *cot, const int16_t *q, const int16_t *a0, const int16_t *comp,
+                                          const uint32_t *tau, int K, int eot, int64_t n, double *grad) {
+  if (!e || !cot || !q || !a0 || !tau || !grad || K < 1 || eot < 1 || K * eot > 32 || n <= 0 || (K > 1 && !comp))
+    return fb_fail(FB_E_ARG, "bad argument");
+  if (n > 0x7fffffffLL) return fb_fail(FB_E_LIMIT, "row longer than 2^31 samples");
+  const size_t R = (size_t)K * (size_t)eot, ns = (size_t)n;
+  for (size_t rho = 0; rho < R; ++rho)
+    if ((int64_t)tau[rho] >= n) return fb_fail(FB_E_ARG, "tau[%zu] = %u is not below n = %lld", rho, tau[rho], (long long)n);
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  DevBuf d_cot, d_q, d_a0, d_comp, d_tau, d_grad;
+  FBCHK(d_cot.ensure(sizeof(double) * R * ns));
+  FBCHK(d_q.ensure(sizeof(int16_t) * ns));
+  FBCHK(d_a0.ensure(sizeof(int16_t) * ns));
+  FBCHK(d_tau.ensure(sizeof(uint32_t) * R));
+  FBCHK(d_grad.ensure(sizeof(double) * ns));
+  FBCHK(h2d(e, d_cot.p, cot, sizeof(double) * R * ns));
+  FBCHK(h2d(e, d_q.p, q, sizeof(int16_t) * ns));
+  FBCHK(h2d(e, d_a0.p, a0, sizeof(int16_t) * ns));
+  FBCHK(h2d(e, d_tau.p, tau, sizeof(uint32_t) * R));
+  if (K > 1) {
+    FBCHK(d_comp.ensure(sizeof(int16_t) * (size_t)(K - 1) * ns));
+    FBCHK(h2d(e, d_comp.p, comp, sizeof(int16_t) * (size_t)(K - 1) * ns));
+  }
+  e->wb_play_launches = 0;
+  fb_launch_wb_play_compose_t(e->stream, d_cot.as<double>(), d_q.as<int16_t>(), d_a0.as<int16_t>(), K > 1 ? d_comp.as<int16_t>() : nullptr,
+                              d_tau.as<uint32_t>(), K, eot, n, d_grad.as<double>(), nullptr);
+  e->wb_play_launches += 1;
+  HIPCHK(hipGetLastError());
+  FBCHK(d2h(e, grad, d_grad.p, sizeof(double) * ns));
   FBCHK(sync_stream(e));
   return FB_OK;
 }
@@ -5356,7 +5554,7 @@ extern "C" int fb_debug_defence_vjp(fb_engine *e, const int16_t *wav, int64_t n,
   memset(e->wb_route, 0, sizeof(e->wb_route));
   e->wb_air_launches = 0;
   const int r = e->eot;
-  FBCHK(prepare_nes_replicas(e, n, 1));
+  FBCHK(prepare_nes_replicas(e, n, 1, false));  // (no contract point of the play offset: the forward below leaves call.play at 0)
   FBCHK(e->wb_gj.ensure(sizeof(double) * (size_t)n));
   FBCHK(e->grad.ensure(sizeof(double) * (size_t)n));
   FBCHK(h2d(e, e->wav.p, wav, sizeof(int16_t) * (size_t)n));
@@ -5375,7 +5573,7 @@ extern "C" int fb_debug_defence_vjp(fb_engine *e, const int16_t *wav, int64_t n,
     if (e->tf.n == 0) FBCHK(h2d(e, e->wb_air_cot.p, cot, bytes));
     for (int j = 0; j < r && e->tf.n > 0; ++j) {
       FBCHK(h2d(e, e->wb_gj.p, cot + (size_t)j * n, sizeof(double) * (size_t)n));
-      FBCHK(wb_launch_chain_t(e, pt, j, n, e->wb_gj.as<double>(), e->wb_air_cot.as<double>() + (size_t)j * (size_t)n, false, nullptr));
+      FBCHK(wb_launch_chain_t(e, pt, j, n, e->wb_gj.as<double>(), e->wb_air_cot.as<double>() + (size_t)j * (size_t)n, false, nullptr, false));
       FBCHK(sync_stream(e));
     }
     fb_launch_air_conv_t(e->stream, e->wb_air_cot.as<double>(), e->wb_air_sat.as<unsigned char>(), r, n, e->air_taps.as<int16_t>(), e->air.L,
@@ -5388,7 +5586,7 @@ extern "C" int fb_debug_defence_vjp(fb_engine *e, const int16_t *wav, int64_t n,
   }
   for (int j = 0; j < r; ++j) {
     FBCHK(h2d(e, e->wb_gj.p, cot + (size_t)j * n, sizeof(double) * (size_t)n));
-    FBCHK(wb_launch_chain_t(e, pt, j, n, e->wb_gj.as<double>(), e->grad.as<double>(), false, nullptr));
+    FBCHK(wb_launch_chain_t(e, pt, j, n, e->wb_gj.as<double>(), e->grad.as<double>(), false, nullptr, false));
     FBCHK(d2h(e, dwav + (size_t)j * n, e->grad.p, sizeof(double) * (size_t)n));
     FBCHK(sync_stream(e));
   }

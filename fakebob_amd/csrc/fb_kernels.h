@@ -105,6 +105,27 @@ hipError_t fb_launch_tf_power_cmp(hipStream_t s, const int16_t *wav, const int64
 // z[n] = the normals a noise stage adds to samples i0 .. i0 + n - 1 of utterance rn.utt0 (fb_debug_tf_noise)
 void fb_launch_tf_noise(hipStream_t s, const FbTfRnd &rn, int replica, int stage, int64_t i0, int64_t n, float *z);
 
+// ---- play offset (fb_set_play_offset; play_offset_kernels.hip) ----------------------------------------------------
+// What a launch carries of the "Play offset" contract (include/fakebob_hip.h): the Philox key (seed_lo ^ "PLAY", seed_hi ^
+// stream), counter word 3, the row of the batch's first utterance within the call, and S (tau is uniform in 0 .. S)
+struct FbPlay {
+  uint32_t k0, k1, epoch, utt0, S;
+};
+static inline FbPlay fb_play_key(const FbRngPoint &pt, int64_t S) {
+  return FbPlay{(uint32_t)pt.seed ^ 0x504C4159u, (uint32_t)(pt.seed >> 32) ^ pt.stream, pt.epoch, pt.utt0, (uint32_t)S};
+}
+// out [B * cn.K * eot][cn.N] (flat, padded to a multiple of eight samples): row b * r' + rho = utterance rho / eot of NES row b
+// of q [B][cn.N] as composed under the offset tau[b * r' + rho], which the launch draws and writes too (cn.K == 1: cn.comp is
+// not read; cn.N > pk.S).  Honours `stop`.
+void fb_launch_play_compose(hipStream_t s, const FbPlay &pk, const int16_t *q, const FbTfComp &cn, int eot, int B, int16_t *out,
+                            uint32_t *tau, const int *stop);
+// tau[rows], row R = replica R % r of utterance row R / r: the draw alone (fb_debug_play_offsets)
+void fb_launch_play_offsets(hipStream_t s, const FbPlay &pk, int r, int rows, uint32_t *tau);
+// the composition under offsets transposed, ONE launch: cot [K * eot][n] on the composed rows of the one NES row q [n], the
+// offsets tau [K * eot] as the forward drew them -> grad [n], rho ascending (the header's "Transposed rule")
+void fb_launch_wb_play_compose_t(hipStream_t s, const double *cot, const int16_t *q, const int16_t *a0, const int16_t *comp,
+                                 const uint32_t *tau, int K, int eot, int64_t n, double *grad, const int *stop);
+
 // ---- over-the-air channel (fb_set_air_channel; air_channel_kernel.hip) -------------------------------------------
 // What a launch carries of the channel's contract (include/fakebob_hip.h): the setting (L == 0: no channel), the Philox key
 // (seed_lo ^ "AIRC", seed_hi ^ stream), counter word 3, the row of the batch's first utterance within the call and the output

@@ -96,6 +96,7 @@ class Engine(object):
         self.wb_frontend = False
         self.wb_universal = False
         self.companions = None
+        self.play_offset = 0
         self.query_eot = None
         self.feature_compression = None
 
@@ -701,6 +702,65 @@ class Engine(object):
                                               C.c_int(K), C.c_int(int(eot)), C.c_int64(n), N.ptr(grad)))
         return grad
 
+    def set_play_offset(self, S):
+        """Play offset (fb_set_play_offset): get_grad and attack -- and, under set_wb_universal(True), get_grad_wb and attack_wb
+        -- then score every replica of every row with the perturbation rotated circularly by an offset of its own, uniform in
+        0 .. S: the loudspeaker plays the perturbation on a loop and cannot time it to the victim's speech.  None or 0 (the
+        default) clears it and changes nothing; up to 2 ** 31 - 2, and below the length of the audio the calls attack.  The
+        stop test reads the MEAN loss over the offsets: see FakeBob.attack(...)'s per_offset for what each offset does."""
+        from .play_offset import MAX_OFFSET
+        S = 0 if S is None else int(S)
+        if not 0 <= S <= MAX_OFFSET:
+            raise ValueError("play offset %d outside 0 .. 2^31 - 2" % S)
+        N.check(self._L.fb_set_play_offset(self._h, C.c_int64(S)))
+        self.play_offset = S
+
+    def debug_play_offsets(self, seed, stream, epoch, B, r, utt0=0):
+        """The offsets k_play_compose draws (fb_debug_play_offsets) for B rows from utterance row utt0 on and r replicas of
+        each, at (seed, stream, epoch) under the S set: a uint32 array (B, r)."""
+        tau = np.empty((int(B), int(r)), np.uint32)
+        N.check(self._L.fb_debug_play_offsets(self._h, C.c_uint64(int(seed)), C.c_uint32(int(stream)), C.c_uint32(int(epoch)),
+                                              C.c_uint32(int(utt0)), C.c_int(int(B)), C.c_int(int(r)), N.ptr(tau)))
+        return tau
+
+    def debug_play_route(self):
+        """k_play_compose launches since the last set_play_offset call (fb_debug_play_route)."""
+        n = C.c_int(0)
+        N.check(self._L.fb_debug_play_route(self._h, C.byref(n)))
+        return int(n.value)
+
+    def bench_play_compose(self, B, n, eot, reps=50, K=1):
+        """Milliseconds per k_play_compose launch on B rows of n samples, K utterances per row and eot draws of each
+        (fb_bench_play_compose: device events around `reps` launches)."""
+        ms = C.c_double()
+        N.check(self._L.fb_bench_play_compose(self._h, C.c_int(int(B)), C.c_int64(int(n)), C.c_int(int(K)), C.c_int(int(eot)),
+                                              C.c_int(int(reps)), C.byref(ms)))
+        return ms.value
+
+    def debug_wb_play_route(self):
+        """k_wb_play_compose_t launches of the last get_grad_wb / attack_wb / debug_wb_play_compose_t call
+        (fb_debug_wb_play_route): one per iteration with a play offset set, none without."""
+        n = C.c_int(0)
+        N.check(self._L.fb_debug_wb_play_route(self._h, C.byref(n)))
+        return int(n.value)
+
+    def debug_wb_play_compose_t(self, cot, q, a0, comp, tau, eot=1):
+        """k_wb_play_compose_t alone (fb_debug_wb_play_compose_t): debug_wb_compose_t's arguments and the offsets tau (K * eot,),
+        every one below n -> grad (n,) float64 by the "Transposed rule" of the play offset."""
+        q = np.ascontiguousarray(q, np.int16).reshape(-1)
+        a0 = np.ascontiguousarray(a0, np.int16).reshape(-1)
+        n = q.size
+        comp = np.ascontiguousarray(comp, np.int16).reshape(-1, n) if comp is not None and np.size(comp) else None
+        K = 1 if comp is None else comp.shape[0] + 1
+        cot = np.ascontiguousarray(cot, np.float64).reshape(K * int(eot), n)
+        tau = np.ascontiguousarray(tau, np.uint32).reshape(K * int(eot))
+        if a0.size != n:
+            raise ValueError("a0 has %d samples, q %d" % (a0.size, n))
+        grad = np.empty(n, np.float64)
+        N.check(self._L.fb_debug_wb_play_compose_t(self._h, N.ptr(cot), N.ptr(q), N.ptr(a0), None if comp is None else N.ptr(comp),
+                                                   N.ptr(tau), C.c_int(K), C.c_int(int(eot)), C.c_int64(n), N.ptr(grad)))
+        return grad
+
     def debug_wb_feco_route(self):
         """k_wb_feco_t launches of the last get_grad_wb / attack_wb / debug_feature_compress_vjp call
         (fb_debug_wb_feco_route): r per iteration with feature compression on, none otherwise."""
@@ -765,7 +825,8 @@ class Engine(object):
     def get_grad_wb_from(self, params, audio, original=None, iter=0, want_grad=True):
         """fb_get_grad_wb_from: get_grad_wb_iter with a_0 of the composition given (set_wb_universal, set_companions): original
         (None: audio itself, the call is then fb_get_grad_wb_iter) is the audio whose int16 cast is a_0, as the attack's start
-        is in attack_wb -- audio - original is the perturbation the companions carry.  Without companions it is not read."""
+        is in attack_wb -- audio - original is the perturbation the companions carry -- and, under set_play_offset, the loop that is rotated on every
+        replica, utterance 0's included.  With neither companions nor a play offset it is not read."""
         audio = np.ascontiguousarray(audio, np.float64).reshape(-1)
         n = audio.size
         grad = np.empty(n, np.float64) if want_grad else None

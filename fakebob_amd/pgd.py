@@ -29,7 +29,7 @@ class PGD(object):
     KINDS = ("gmm",)   # engine kinds the class differentiates (IvectorPGD: the i-vector back end as well)
 
     def __init__(self, task, attack_type, model, adver_thresh=0., epsilon=0.002, max_iter=1000, max_lr=0.001, min_lr=1e-6,
-                 momentum=0.9, plateau_length=5, plateau_drop=2., seed=None, verbose=True):
+                 momentum=0.9, plateau_length=5, plateau_drop=2., seed=None, verbose=True, play_offset=None):
         if task not in ("OSI", "CSI", "SV"):
             raise ValueError("task must be OSI, CSI or SV")
         if not hasattr(model, "engine"):
@@ -42,6 +42,10 @@ class PGD(object):
         self.air = False    # (air=True of AdaptivePGD / IvectorPGD: Engine.set_wb_air is on; seed / stream key the rooms)
         self.frontend = False   # (frontend=True of the two: Engine.set_wb_frontend is on; seed / stream key the k-means and dither draws)
         self.universal = False  # (universal=True of AdaptivePGD: Engine.set_wb_universal is on; attack() takes companions)
+        self.play_offset = 0    # (play_offset=S of the two with universal=True: Engine.set_play_offset for the length of attack())
+        from .play_offset import check_offset
+        if check_offset(play_offset):   # (FakeBob's keyword; the subclasses take it themselves and do not hand it on)
+            raise ValueError("PGD: play_offset %d needs universal=True (AdaptivePGD / IvectorPGD: Engine.set_wb_universal)" % int(play_offset))
         self.eot_size = 1
         self.task = task
         self.attack_type = attack_type
@@ -89,8 +93,8 @@ class PGD(object):
         return nes_params(self.task, self.attack_type, adver_thresh=self.adver_thresh, epsilon=self.epsilon,
                           max_iter=self.max_iter, max_lr=self.max_lr, min_lr=self.min_lr, samples_per_draw=0, sigma=0.0,
                           momentum=self.momentum, plateau_length=self.plateau_length, plateau_drop=self.plateau_drop,
-                          threshold=self.threshold, target=self.target, true=self.true, seed=self.seed if (self.bpda or self.air or self.frontend) else 0,
-                          stream=self._stream if (self.bpda or self.air or self.frontend) else 0, bits_per_sample=bits_per_sample)
+                          threshold=self.threshold, target=self.target, true=self.true, seed=self.seed if (self.bpda or self.air or self.frontend or self.play_offset) else 0,
+                          stream=self._stream if (self.bpda or self.air or self.frontend or self.play_offset) else 0, bits_per_sample=bits_per_sample)
 
     def get_grad(self, audio, fs=16000, bits_per_sample=16, n_jobs=10, debug=False):
         """-> (grad (N,1) = d loss / d audio, adver_loss (1,), score), the analytic twin of FakeBob.get_grad's last three."""
@@ -129,15 +133,22 @@ class PGD(object):
         self.true = true
         self.target = target
         eng = self.model.engine
+        if self.play_offset >= audio.shape[0] > 0:
+            raise ValueError("play_offset %d: the audio has %d samples, the offset must stay below that" % (self.play_offset, audio.shape[0]))
         t0 = time.time()
-        if companions is None:
+        # (an engine is asked for a setting only when this call changes it)
+        before = eng.companions if companions is not None else None
+        before_S = eng.play_offset if self.play_offset else 0
+        try:
+            if companions is not None:
+                eng.set_companions(comp)
+            if self.play_offset:
+                eng.set_play_offset(self.play_offset)
             adv, flag, _advf, trace = eng.attack_wb(self._params(bits), audio[:, 0])
-        else:
-            before = eng.companions
-            eng.set_companions(comp)
-            try:
-                adv, flag, _advf, trace = eng.attack_wb(self._params(bits), audio[:, 0])
-            finally:
+        finally:
+            if self.play_offset:
+                eng.set_play_offset(before_S)
+            if companions is not None:
                 eng.set_companions(before)
         dt = time.time() - t0
         n = trace.shape[0]
@@ -156,14 +167,28 @@ class PGD(object):
         a0 = CP.cast_i16(audio[:, 0], bits)
         delta = adv.astype(np.int32) - a0.astype(np.int32)
         per = None
+        kw = dict(fs=fs, bits_per_sample=bits_per_sample, n_jobs=n_jobs, debug=debug)
         if comp is not None:
-            kw = dict(fs=fs, bits_per_sample=bits_per_sample, n_jobs=n_jobs, debug=debug)
             per = []
             for u, w in enumerate([adv] + CP.apply_perturbation(delta, list(comp))):
                 dec, sc = self.model.make_decisions(w, **kw)
                 per.append(dict(utterance=u, audio_i16=w, decision=dec, score=sc,
                                 success=CP.succeeded(self.task, self.attack_type, dec, target=target, true=true)))
-        return CP.AttackResult(adv[:, np.newaxis], flag, delta, bits, per)
+        per_off = None
+        if self.play_offset:   # every utterance under the perturbation at each offset of the grid, as in FakeBob.attack
+            from .play_offset import per_offset
+            per_off = per_offset(self.model, self.task, self.attack_type, [a0] + ([] if comp is None else list(comp)), delta,
+                                 self.play_offset, target=target, true=true, **kw)
+        return CP.AttackResult(adv[:, np.newaxis], flag, delta, bits, per, per_off)
+
+    def _set_play_offset(self, play_offset):
+        """play_offset=S of AdaptivePGD / IvectorPGD: kept here, set on the engine for the length of an attack (fb_set_play_offset
+        rides on the universal path: ValueError without universal=True)"""
+        from .play_offset import check_offset
+        S = check_offset(play_offset)
+        if S and not self.universal:
+            raise ValueError("%s: play_offset %d needs universal=True (Engine.set_wb_universal)" % (type(self).__name__, S))
+        self.play_offset = S
 
 
 class AdaptivePGD(PGD):
@@ -177,9 +202,12 @@ class AdaptivePGD(PGD):
     model's feature compression and dither (Engine.set_wb_frontend): the gradient at the k-means assignment and the dither
     draws of each of the eot_size forwards.  universal=True switches it to take companions (Engine.set_wb_universal):
     attack(..., companions=[...]) then descends the loss averaged over the utterances (times the eot_size draws of each); it needs
-    no other switch on an undefended victim (bpda=False)."""
+    no other switch on an undefended victim (bpda=False).  play_offset=S (with universal=True; Engine.set_play_offset for the length of
+    an attack) rotates the perturbation by an offset of its own in 0 .. S on every replica: the attack descends the loss
+    averaged over playback timings, and the result carries per_offset."""
 
-    def __init__(self, task, attack_type, model, bpda=True, eot_size=1, air=False, frontend=False, universal=False, **kw):
+    def __init__(self, task, attack_type, model, bpda=True, eot_size=1, air=False, frontend=False, universal=False, play_offset=None,
+                 **kw):
         eot_size = int(eot_size)
         if not 1 <= eot_size <= 32:
             raise ValueError("AdaptivePGD: eot_size %d outside 1 .. 32" % eot_size)
@@ -201,6 +229,7 @@ class AdaptivePGD(PGD):
         self.universal = bool(universal)
         if self.universal:
             model.engine.set_wb_universal(True)
+        self._set_play_offset(play_offset)
 
     def attack(self, audio, checkpoint_path, threshold=0., true=None, target=None, fs=16000, bits_per_sample=16, n_jobs=10,
                debug=False, companions=None):
@@ -221,7 +250,8 @@ class IvectorPGD(PGD):
     checkpoint layout are PGD's."""
     KINDS = ("gmm", "iv")
 
-    def __init__(self, task, attack_type, model, bpda=False, air=False, frontend=False, universal=False, eot_size=1, **kw):
+    def __init__(self, task, attack_type, model, bpda=False, air=False, frontend=False, universal=False, eot_size=1, play_offset=None,
+                 **kw):
         eot_size = int(eot_size)
         if not 1 <= eot_size <= 32:
             raise ValueError("IvectorPGD: eot_size %d outside 1 .. 32" % eot_size)
@@ -244,3 +274,4 @@ class IvectorPGD(PGD):
             self.eot_size = eot_size
             if self.bpda:
                 model.engine.set_eot(eot_size)
+        self._set_play_offset(play_offset)

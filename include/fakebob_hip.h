@@ -356,6 +356,49 @@ int fb_set_eot(fb_engine *e, int r);
  * fb_score_*, fb_gmm_acc_stats and the fb_debug_* hooks of the sections above ignore companions. */
 int fb_set_companions(fb_engine *e, const int16_t *wav, int K1, int64_t N);
 
+/* ---- play offset: the perturbation plays on a loop, the victim speaks whenever they speak ---------------------------------
+ * Over the air the attacker cannot time the perturbation to the victim's speech: a loudspeaker plays it on a loop and the
+ * recogniser hears speech plus the perturbation at an unknown offset.  With S > 0 every replica of every NES row carries the
+ * perturbation rotated by an offset tau of its own, uniform in 0 .. S.  The loop has the utterance's length N, so the rotation
+ * is circular.  It is the expectation of fb_set_eot and fb_set_companions, taken over the playback timing as well.
+ * Setting.  fb_set_play_offset(e, S): 0 <= S <= 2^31 - 2; anything else is FB_E_ARG and keeps the previous value.  S = 0
+ * clears the setting (the default: no launch is added, no code path differs).  An NES or white-box call whose N <= S returns
+ * FB_E_ARG.
+ * Draw.  Philox4x32-10 on a key of its own:
+ *   key     = (seed_lo ^ 0x504C4159 ("PLAY"), seed_hi ^ stream)
+ *   counter = (0, replica rho, utterance row b of the un-replicated batch, epoch)
+ * seed, stream, epoch, row and replica exactly by the rules of the "Noise RNG contract" and of fb_set_companions' "Row order";
+ * w = output word 0 and tau = (uint32_t)(((uint64_t)w * (uint64_t)(S + 1)) >> 32).  An attack's offsets depend on (seed,
+ * stream) only.
+ * Composition (the names of fb_set_companions).  d_b[i] = q_b[i] - a_0[i], int32.  Utterance u, draw j of NES row b is
+ *     w[b][rho][i] = clip(a_u[i] + d_b[(i - tau) mod N], -32768, 32767)        FOR EVERY u, u = 0 INCLUDED
+ * where a_0 is the int16 cast of the call's original audio (utterance 0) and tau = tau(b, rho).  At tau = 0, u = 0 this is
+ * q_b[i] exactly; row 0 of an NES batch (q_0 = a_0) composes to the unperturbed utterances whatever the offsets are.
+ * Row order.  rho = u * eot + j, r' = K * eot <= 32, order and averaging as in fb_set_companions.
+ * Order of stages.  Composition with the offset, then the air channel, the chain, the codec, the front end, dither and FeCo.
+ * Those stages' own contracts stay untouched -- they draw with (rho, b) as always --, and an SNR noise stage takes its power
+ * from the composed, offset row "as it is handed to the chain" (under a channel: from the channel's output, as before).
+ * Route.  With an offset set a call takes the route a call with eot > 1 takes, even at K * eot = 1: the unfused finalisation
+ * and no i-vector tail-loss shortcut.  One launch (k_play_compose) in front of the air and chain launches writes the B * r'
+ * composed rows and their offsets; fb_stats counts what the front end scored (K * eot rows per NES row).
+ * Unchanged.  Everything behind the averaging: the stop test, the plateau rule, the trace, the gradient estimate, the sign
+ * step, the epsilon ball, the returned adv_i16 and the distance column -- all utterance 0's at offset 0.  The loop to play is
+ * adv_i16 - a_0.  THE STOP TEST READS A MEAN OVER OFFSETS, as it reads a mean over utterances.
+ * Where it acts.  fb_get_grad and fb_attack; fb_get_grad_wb* and fb_attack_wb when fb_set_wb_universal is on (together with the
+ * switches the other stages need).  fb_score_*, fb_gmm_acc_stats, the fb_debug_* hooks without a contract point and foreign
+ * models (_ext, _dev) ignore it, as they ignore companions.
+ * Refused by name (FB_E_STATE, "not in this version") while S > 0: fb_estimate_threshold; fb_attack_pso, fb_attack_kenansville
+ * and fb_attack_hsj, with or without fb_set_query_eot; fb_attack_cw2 and fb_attack_psy; the white-box calls when
+ * fb_set_wb_universal is off.  Not modelled either: a loop shorter than the utterance, zero-filled instead of circular offsets.
+ * Transposed rule (white box; k_wb_play_compose_t in k_wb_compose_t's place, also at K = 1, one launch per iteration).  In
+ * float64, from +0.0, with one rounding per addition and a masked term adding +0.0:
+ *     grad[k] = sum over rho ascending of m_rho[i] * cot_rho[i]   at i = (k + tau_rho) mod N
+ * m_rho[i] = 1 where a_u[i] + d[(i - tau_rho) mod N], taken before the clip, lies inside [-32768, 32767], 0 elsewhere: a sample
+ * at a rail that was not clipped passes.  The offsets are the forward's; nothing is drawn again.  Under a channel cot_rho is
+ * k_air_conv_t's dx row rho; a chain's transpose reads replica rho's row from the composed buffer.  At S = 0 this is
+ * k_wb_compose_t's rule, including m_0 = 1. */
+int fb_set_play_offset(fb_engine *e, int64_t S);
+
 /* ---- feature compression: a feature-level defence (SpeakerGuard's FeCo) -------------------------------------------------
  * The victim clusters the T voiced feature vectors of an utterance with k-means and scores the k = ratio * T cluster centres
  * instead of the frames.  The stage is SpeakerGuard's "final" one: behind VAD, deltas, CMVN and voiced-frame selection, in

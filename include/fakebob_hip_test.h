@@ -78,7 +78,7 @@ int fb_debug_air_taps(fb_engine *e, uint64_t seed, uint32_t stream, uint32_t epo
 int fb_debug_air_convolve(fb_engine *e, const int16_t *wav, const int64_t *off, int B, const int16_t *taps, int L, int16_t *out);
 
 /* Telephone-line codec (fakebob_hip.h: fb_set_codec and its stage contract).  The hooks above that return int16 rows
- * (fb_debug_input_transform*, fb_debug_compose, fb_debug_air_*) ignore the codec; fb_debug_mfcc / _feats apply it.
+ * (fb_debug_input_transform*, fb_debug_compose -- unless a play offset is set, see below --, fb_debug_air_*) ignore the codec; fb_debug_mfcc / _feats apply it.
  * fb_debug_codec: k_codec on rows handed in as they are -- B rows of any length >= 1 (off[B + 1], off[0] = 0), B up to
  * 65535; out has wav's layout.  kind (FB_CODEC_ULAW, _ALAW or _ADPCM) comes from the argument: the engine's setting is
  * neither read nor changed.
@@ -453,6 +453,31 @@ int fb_debug_wb_feco_state(fb_engine *e, int j, int cap, int *labels, int *count
 int fb_debug_wb_compose_t(fb_engine *e, const double *cot /*[K*eot][n]*/, const int16_t *q, const int16_t *a0,
                           const int16_t *comp /*[K-1][n], nullable at K = 1*/, int K, int eot, int64_t n, double *grad /*[n]*/);
 int fb_debug_wb_universal_route(fb_engine *e, int *n_launches);
+
+/* Play offset (fakebob_hip.h: fb_set_play_offset, "Draw", "Composition" and "Transposed rule").
+ * fb_debug_compose above applies the offset when one is set -- k_play_compose in front of the air and chain launches, exactly
+ * the NES calls' path, at its (seed, stream, epoch) --; N must then exceed S.  With an offset set it returns the rows the front
+ * end reads, so a codec (fb_set_codec) IS applied -- behind a chain or a channel in place on their buffer, else in place on the
+ * composed buffer; without an offset the hook is unchanged and ignores the codec, as said above.
+ * fb_debug_play_offsets: tau_out[B * r], the offset of replica rho of utterance row utt0 + b at slot b * r + rho, under the
+ * engine's S (FB_E_STATE without one).
+ * fb_debug_play_route: *n_launches = the k_play_compose launches since the last fb_set_play_offset call.
+ * fb_debug_wb_play_compose_t: k_wb_play_compose_t alone, ONE launch, on arrays handed in as they are: fb_debug_wb_compose_t's
+ * arguments and tau[K * eot], every one below n.  The engine's settings are neither used nor changed.
+ * fb_debug_wb_play_route: *n_launches = the k_wb_play_compose_t launches the last fb_get_grad_wb* / fb_attack_wb /
+ * fb_debug_wb_play_compose_t call enqueued -- one per iteration with an offset set (fb_debug_wb_universal_route then says
+ * none), none without. */
+int fb_debug_play_offsets(fb_engine *e, uint64_t seed, uint32_t stream, uint32_t epoch, uint32_t utt0, int B, int r,
+                          uint32_t *tau_out /*[B*r]*/);
+int fb_debug_play_route(fb_engine *e, int *n_launches);
+/* fb_bench_play_compose: *ms = milliseconds per k_play_compose launch (device events around `reps` launches) on B rows of n
+ * samples, K utterances per row (K - 1 companions of a fixed pattern) and eot draws of each, offsets up to n - 1; it writes
+ * B * K * eot * n * 2 bytes per launch.  The engine's settings are neither used nor changed. */
+int fb_bench_play_compose(fb_engine *e, int B, int64_t n, int K, int eot, int reps, double *ms);
+int fb_debug_wb_play_compose_t(fb_engine *e, const double *cot /*[K*eot][n]*/, const int16_t *q, const int16_t *a0,
+                               const int16_t *comp /*[K-1][n], nullable at K = 1*/, const uint32_t *tau /*[K*eot]*/, int K, int eot,
+                               int64_t n, double *grad /*[n]*/);
+int fb_debug_wb_play_route(fb_engine *e, int *n_launches);
 
 /* White-box gradients through the i-vector-PLDA back end (fakebob_hip.h: fb_set_wb_ivector).  Both hooks need a loaded i-vector
  * system (FB_E_STATE otherwise) and run whatever the switch says, with exactly the launches an attack iteration runs for
