@@ -124,6 +124,17 @@ class DevModel(C.Structure):
                 ("look_every", C.c_int)]
 
 
+# fb_decide_cb: int (*)(void *ctx, const double *audios, int64_t N, int B, int *decisions, double *scores)
+DECIDE_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int64, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double))
+FB_VICTIM_HOST_SCORES, FB_VICTIM_HOST_DECISIONS, FB_VICTIM_DEVICE_SCORES = 1, 2, 3
+
+
+class Victim(C.Structure):
+    """fb_victim"""
+    _fields_ = [("mode", C.c_int), ("S", C.c_int), ("score", SCORE_CB), ("decide", DECIDE_CB), ("dev", C.POINTER(DevModel)),
+                ("score_dev", SCORE_DEV_CB), ("ctx", C.c_void_p)]
+
+
 class TfStage(C.Structure):
     """fb_tf_stage"""
     _fields_ = [("kind", C.c_int), ("k", C.c_int), ("taps", C.POINTER(C.c_double))]
@@ -146,11 +157,11 @@ class ForeignPathInfo(C.Structure):
 EXPORTS = [
     "fb_last_error", "fb_version", "fb_device_count", "fb_engine_create", "fb_engine_destroy",
     "fb_default_frontend", "fb_set_frontend", "fb_set_dither_seed", "fb_set_input_transform", "fb_set_air_channel", "fb_set_codec", "fb_set_eot", "fb_set_companions", "fb_set_play_offset", "fb_debug_play_offsets", "fb_debug_play_route", "fb_bench_play_compose", "fb_debug_wb_play_compose_t", "fb_debug_wb_play_route", "fb_set_query_eot", "fb_set_feature_compression", "fb_load_gmm", "fb_load_ivector", "fb_set_system", "fb_num_speakers",
-    "fb_score_i16", "fb_score_f64", "fb_system_scores", "fb_get_grad", "fb_attack", "fb_get_grad_wb", "fb_get_grad_wb_iter", "fb_set_wb_bpda", "fb_set_wb_ivector", "fb_set_wb_air", "fb_set_wb_frontend", "fb_set_wb_universal", "fb_get_grad_wb_from", "fb_attack_wb", "fb_attack_cw2", "fb_debug_cw2_step", "fb_attack_psy", "fb_debug_psy_loss", "fb_debug_psy_step", "fb_attack_pso", "fb_attack_kenansville", "fb_attack_hsj", "fb_hsj_max_rows", "fb_attack_iter_seconds", "fb_get_grad_ext", "fb_attack_ext",
+    "fb_score_i16", "fb_score_f64", "fb_system_scores", "fb_get_grad", "fb_attack", "fb_get_grad_wb", "fb_get_grad_wb_iter", "fb_set_wb_bpda", "fb_set_wb_ivector", "fb_set_wb_air", "fb_set_wb_frontend", "fb_set_wb_universal", "fb_get_grad_wb_from", "fb_attack_wb", "fb_attack_cw2", "fb_debug_cw2_step", "fb_attack_psy", "fb_debug_psy_loss", "fb_debug_psy_step", "fb_attack_pso", "fb_attack_kenansville", "fb_attack_hsj", "fb_hsj_max_rows", "fb_attack_pso_foreign", "fb_attack_kenansville_foreign", "fb_attack_hsj_foreign", "fb_debug_rows_to_model", "fb_debug_decide_foreign", "fb_attack_iter_seconds", "fb_get_grad_ext", "fb_attack_ext",
     "fb_get_grad_dev", "fb_attack_dev", "fb_debug_foreign_path", "fb_debug_nes_route", "fb_debug_nes_batch", "fb_debug_shared_chain_engines",
     "fb_estimate_threshold", "fb_debug_noise", "fb_debug_quantize", "fb_debug_mfcc", "fb_debug_feats", "fb_debug_dither_noise", "fb_debug_mfcc_dither", "fb_debug_feats_dither", "fb_debug_input_transform", "fb_debug_tf_noise", "fb_debug_input_transform_eot", "fb_debug_compose", "fb_debug_air_taps", "fb_debug_air_convolve", "fb_debug_codec", "fb_debug_feature_compress", "fb_debug_feco_keys", "fb_debug_pso_init", "fb_debug_pso_step", "fb_debug_kv_analyse", "fb_debug_kv_candidates", "fb_debug_hsj_line", "fb_debug_hsj_probes", "fb_debug_hsj_dir", "fb_debug_hsj_step", "fb_debug_vote", "fb_debug_gmm_frames", "fb_debug_gmm_acc_rows", "fb_debug_gmm_feat_grad", "fb_debug_frontend_vjp", "fb_debug_defence_vjp", "fb_debug_wb_route", "fb_debug_air_conv_t", "fb_debug_air_conv_t_chunk", "fb_debug_wb_air_route", "fb_debug_feature_compress_vjp", "fb_debug_wb_feco_route", "fb_debug_wb_feco_state", "fb_debug_wb_compose_t", "fb_debug_wb_universal_route", "fb_debug_iv_backend_grad", "fb_debug_iv_feat_grad", "fb_debug_iv_active", "fb_debug_iv_gselect", "fb_debug_frontend_route", "fb_debug_launch_shape", "fb_stats", "fb_gmm_acc_stats", "fb_last_ivectors", "fb_gmm_kernel_mode", "fb_gmm_kernel_variant", "fb_gmm_delta_tiles", "fb_gmm_delta_tiles_f6", "fb_set_fused_chain",
     "fb_debug_prepare_gmm", "fb_debug_prepare_ivector", "fb_debug_prepare_frontend",
-    "fb_bench_gmm_kernel", "fb_bench_kv_kernels", "fb_bench_hsj_kernels", "fb_bench_vote", "fb_bench_nes", "fb_bench_nes_state",
+    "fb_bench_gmm_kernel", "fb_bench_kv_kernels", "fb_bench_hsj_kernels", "fb_bench_vote", "fb_bench_foreign_rows", "fb_bench_nes", "fb_bench_nes_state",
 ]
 
 ABI_VERSION = 101  # fb_version() of the library these bindings were written for (101: fb_set_wb_bpda, fb_get_grad_wb_iter)

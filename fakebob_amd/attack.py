@@ -48,6 +48,18 @@ def _col(audio):
     return audio
 
 
+def model_speakers(model, task, probe_audio=None, probe=None):
+    """Number of score columns of a foreign model: 1 for SV, len(model.spk_ids) when the model has the attribute, else
+    probe(probe_audio) -- the width of ONE extra query (None: the model cannot be asked for scores)."""
+    if task == "SV":
+        return 1
+    if hasattr(model, "spk_ids"):
+        return len(model.spk_ids)
+    if probe_audio is not None and probe is not None:
+        return probe(probe_audio)
+    raise ValueError("cannot tell how many speakers the model scores: give it a spk_ids attribute")
+
+
 class FakeBob(object):
 
     def __init__(self, task, attack_type, model, adver_thresh=0., epsilon=0.002, max_iter=1000,
@@ -139,18 +151,15 @@ class FakeBob(object):
         attribute the reference's drivers read (attackMain.py:95), else the width of ONE extra score call made the
         way the reference calls score (same keywords); a model that counts its queries should carry spk_ids."""
         if self._n_spk is None:
-            if self.task == "SV":
-                self._n_spk = 1
-            elif hasattr(self.model, "spk_ids"):
-                self._n_spk = len(self.model.spk_ids)
-            elif probe_audio is not None and self._device:
-                torch = self._torch()
-                x = torch.as_tensor(np.ascontiguousarray(probe_audio[:, 0]), device=self._cuda()).to(self._x_dtype())
-                self._n_spk = int(self.model.score_device(x.reshape(1, -1)).numel())
-            elif probe_audio is not None:
-                self._n_spk = int(np.asarray(self.model.score(probe_audio, **score_kw)).size)
+            if self._device:
+                def probe(a):
+                    torch = self._torch()
+                    x = torch.as_tensor(np.ascontiguousarray(a[:, 0]), device=self._cuda()).to(self._x_dtype())
+                    return int(self.model.score_device(x.reshape(1, -1)).numel())
             else:
-                raise ValueError("cannot tell how many speakers the model scores: give it a spk_ids attribute")
+                def probe(a):
+                    return int(np.asarray(self.model.score(a, **score_kw)).size)
+            self._n_spk = model_speakers(self.model, self.task, probe_audio, probe)
         return self._n_spk
 
     def _score_fn(self, fs, bits_per_sample, n_jobs, debug):

@@ -234,6 +234,7 @@ struct fb_engine {
   DevBuf hsj_init, hsj_y, hsj_x, hsj_v; // fb_attack_hsj: the starting audio, the step's end point, the boundary point, the direction [N] float64
   DevBuf hsj_part, hsj_sc, hsj_w;       // ... ssq's chunk sums, the two sums {D2, S}, the probes' weights [B] int32
   DevBuf hsj_best, hsj_look, hsj_z;     // ... the row of hi [N] int16, the host's look {FbNesDev, loss, scores, tv}, the probes' normals [B][N] float32
+  DevBuf fg_look;                       // fb_attack_*_foreign: k_decide_foreign's look block {decisions[rows] int32, scores[rows][S] float64}
   // white-box gradients (fb_get_grad_wb / fb_attack_wb): fb_load_gmm's plain float32 parameters, kept on the host and uploaded
   // by the first white-box call after the load; the weights w[M], the GMM backward's per-model rows and the cotangent g on the
   // compacted rows, the front-end backward's float64 stages, a status word (1: the recomputed voiced mask is not the forward's)
@@ -2090,6 +2091,18 @@ static int enqueue_score_loss_dev(fb_engine *e, const fb_nes_params *p, const Fb
 
 static bool x_aligned(const fb_dev_model *m) { return (reinterpret_cast<uintptr_t>(m->x) & 15) == 0; }
 
+// a foreign model's scores are final: k_loss reads them under the z-norm of the identity, (s - 0) / 1 == s bit for bit
+static int ensure_identity_znorm(fb_engine *e) {
+  const size_t had = e->ext_z.cap;
+  FBCHK(e->ext_z.ensure(sizeof(double) * 2 * 64));
+  if (e->ext_z.cap != had) {
+    double z[128];
+    for (int i = 0; i < 64; ++i) { z[i] = 0.0; z[64 + i] = 1.0; }
+    FBCHK(h2d(e, e->ext_z.p, z, sizeof(z)));
+  }
+  return FB_OK;
+}
+
 // ------------------------------------------------- the NES driver of every scorer
 // Checks and buffers of a NES call.  attack: fb_attack*, which also need max_iter > 0.
 static int nes_setup(fb_engine *e, const fb_nes_params *p, int64_t N, FbScorer &sc, bool attack) {
@@ -2110,14 +2123,7 @@ static int nes_setup(fb_engine *e, const fb_nes_params *p, int64_t N, FbScorer &
     FBCHK(e->ext_x.ensure(sizeof(double) * (size_t)N * B));
     FBCHK(e->raw.ensure(sizeof(double) * (size_t)B * sc.S));
   }
-  const size_t had = e->ext_z.cap;
-  FBCHK(e->ext_z.ensure(sizeof(double) * 2 * 64));
-  if (e->ext_z.cap != had) {  // z-norm of the identity: (s - 0) / 1 == s bit for bit
-    double z[128];
-    for (int i = 0; i < 64; ++i) { z[i] = 0.0; z[64 + i] = 1.0; }
-    FBCHK(h2d(e, e->ext_z.p, z, sizeof(z)));
-  }
-  return FB_OK;
+  return ensure_identity_znorm(e);
 }
 
 // fb_get_grad*: one NES gradient estimate at `audio`
@@ -3616,6 +3622,176 @@ static void launch_vote(fb_engine *e, const fb_nes_params *p, int rows, int r, b
                  e->zstd.as<double>(), p->threshold, targeted ? 1 : 0, label, e->eot_sc.as<double>(), v.votes, v.nodec, v.mean);
 }
 
+// ------------------------------------------------- foreign victims of the three query attacks
+// fb_attack_pso_foreign / _kenansville_foreign / _hsj_foreign (the "foreign victims" section of fakebob_hip.h).  The three
+// drivers below write their int16 batch into e->wav exactly as for the engine's own systems; where those call run_scoring,
+// a foreign call converts the rows (k_rows_to_model), hands them to the model -- through the host's staging memory or in the
+// model's own device buffer -- and reads scores or decisions back.  None of the engine's front end, defences or batch
+// layout is touched, so no system need be loaded.
+struct FbForeignRun {
+  const fb_victim *v = nullptr;
+  int S = 0, rows_max = 0, bits = 16, task = 0;
+  int64_t N = 0;
+  double threshold = 0.0;
+  std::vector<double> sc_h, spill, look;   // the callback's scores, a batch too large for the staging arena, the look block
+  std::vector<int> dec_h;
+};
+// k_decide_foreign's look block for `rows` rows of S scores: decisions[rows] int32, padded to 8 bytes, scores[rows][S] float64
+static size_t foreign_look_doubles(int rows, int S) { return ((size_t)rows + 1) / 2 + (size_t)rows * S; }
+
+// the descriptor's checks and the settings a foreign victim refuses (`who`: the public call; decisions_ok: the call takes
+// FB_VICTIM_HOST_DECISIONS), then the buffers of batches of up to rows_max rows
+static int foreign_setup(fb_engine *e, const char *who, const fb_nes_params *p, const fb_victim *v, int64_t N, int rows_max,
+                         bool decisions_ok, FbForeignRun *fr) {
+  if (v->mode != FB_VICTIM_HOST_SCORES && v->mode != FB_VICTIM_HOST_DECISIONS && v->mode != FB_VICTIM_DEVICE_SCORES)
+    return fb_fail(FB_E_ARG, "%s: unknown victim mode %d", who, v->mode);
+  if (v->mode == FB_VICTIM_HOST_DECISIONS && !decisions_ok)
+    return fb_fail(FB_E_ARG, "%s reads scores: FB_VICTIM_HOST_DECISIONS is not for it", who);
+  if (v->mode == FB_VICTIM_HOST_SCORES && !v->score) return fb_fail(FB_E_ARG, "%s: FB_VICTIM_HOST_SCORES without a score callback", who);
+  if (v->mode == FB_VICTIM_HOST_DECISIONS && !v->decide) return fb_fail(FB_E_ARG, "%s: FB_VICTIM_HOST_DECISIONS without a decide callback", who);
+  if (v->mode == FB_VICTIM_DEVICE_SCORES && (!v->dev || !v->score_dev))
+    return fb_fail(FB_E_ARG, "%s: FB_VICTIM_DEVICE_SCORES without dev or score_dev", who);
+  if (p->task != FB_TASK_OSI && p->task != FB_TASK_CSI && p->task != FB_TASK_SV) return fb_fail(FB_E_ARG, "bad task %d", p->task);
+  if (v->S <= 0 || v->S > 62) return fb_fail(FB_E_ARG, "number of speakers must be in [1, 62] (got %d)", v->S);
+  if (p->task == FB_TASK_SV && v->S != 1) return fb_fail(FB_E_ARG, "SV scores one speaker (got S = %d)", v->S);
+  if (N <= 0) return fb_fail(FB_E_ARG, "empty audio");
+  // a foreign victim's randomness is its own
+  if (e->eot > 1)
+    return fb_fail(FB_E_STATE, "%s does not run under expectation over transformation (fb_set_eot(%d)): set 1", who, e->eot);
+  if (e->comp_K1 > 0)
+    return fb_fail(FB_E_STATE, "%s does not run with companion utterances (fb_set_companions: %d set): clear them", who, e->comp_K1);
+  FBCHK(refuse_play(e, who));
+  if (e->query_quorum != FB_QUORUM_OFF)
+    return fb_fail(FB_E_STATE, "%s does not vote (fb_set_query_eot(%d)): set 0", who, e->query_quorum);
+  fr->v = v;
+  fr->S = v->S;
+  fr->rows_max = rows_max;
+  fr->bits = nes_bits(p);
+  fr->task = p->task;
+  fr->N = N;
+  fr->threshold = p->threshold;
+  return FB_OK;
+}
+// ... once the call's own parameters have passed as well (fr->rows_max rows of N samples at the most)
+static int foreign_buffers(fb_engine *e, FbForeignRun *fr) {
+  const fb_victim *v = fr->v;
+  const size_t rows = (size_t)fr->rows_max, N = (size_t)fr->N, S = (size_t)fr->S;
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  if (v->mode == FB_VICTIM_DEVICE_SCORES) {   // fb_attack_dev's checks, without look_every
+    const fb_dev_model *m = v->dev;
+    if (m->x_dtype != FB_DT_F32 && m->x_dtype != FB_DT_F64)
+      return fb_fail(FB_E_ARG, "x_dtype %d: FB_DT_F32 (%d) or FB_DT_F64 (%d)", m->x_dtype, FB_DT_F32, FB_DT_F64);
+    if (m->score_dtype != FB_DT_F32 && m->score_dtype != FB_DT_F64)
+      return fb_fail(FB_E_ARG, "score_dtype %d: FB_DT_F32 (%d) or FB_DT_F64 (%d)", m->score_dtype, FB_DT_F32, FB_DT_F64);
+    FBCHK(check_dev_buffer(e, "x", m->x, (m->x_dtype == FB_DT_F32 ? sizeof(float) : sizeof(double)) * N * rows));
+    FBCHK(check_dev_buffer(e, "scores", m->scores, (m->score_dtype == FB_DT_F32 ? sizeof(float) : sizeof(double)) * rows * S));
+  } else {
+    FBCHK(e->ext_x.ensure(sizeof(double) * N * rows));
+    FBCHK(e->raw.ensure(sizeof(double) * rows * S));
+    fr->sc_h.resize(rows * S);
+    fr->dec_h.resize(rows);
+  }
+  e->cached_B = -1;   // (e->wav takes the batches, without a batch layout)
+  FBCHK(e->wav.ensure(sizeof(int16_t) * N * rows));
+  FBCHK(e->fg_look.ensure(sizeof(double) * foreign_look_doubles(fr->rows_max, fr->S)));
+  fr->look.resize(foreign_look_doubles(fr->rows_max, fr->S));
+  FBCHK(ensure_identity_znorm(e));
+  const bool dev = v->mode == FB_VICTIM_DEVICE_SCORES;
+  e->foreign = fb_foreign_path_info{};
+  e->foreign.path = dev ? FB_FOREIGN_DEV : FB_FOREIGN_HOST;
+  e->foreign.x_dtype = dev ? v->dev->x_dtype : FB_DT_F64;
+  e->foreign.score_dtype = dev ? v->dev->score_dtype : FB_DT_F64;
+  e->foreign.launches_per_iter = v->mode == FB_VICTIM_HOST_DECISIONS ? 1 : 2;   // per batch: the conversion; k_decide_foreign or k_loss
+  return FB_OK;
+}
+// The `rows` rows of e->wav as the victim's audio.  Device mode: in dev->x.  Host modes: *xh points at float64 [rows][N] in
+// the staging arena (or in fr->spill beyond its size), valid until the next copy through the arena; the stream is idle.
+static int foreign_hand_rows(fb_engine *e, FbForeignRun *fr, int rows, const double **xh) {
+  const fb_victim *v = fr->v;
+  if (v->mode == FB_VICTIM_DEVICE_SCORES) {
+    fb_launch_rows_to_model(e->stream, v->dev->x_dtype, e->wav.as<int16_t>(), rows, fr->N, fr->bits, v->dev->x);
+    return FB_OK;
+  }
+  fb_launch_rows_to_model(e->stream, FB_DT_F64, e->wav.as<int16_t>(), rows, fr->N, fr->bits, e->ext_x.p);
+  const size_t xb = sizeof(double) * (size_t)fr->N * (size_t)rows;
+  if (xb <= FB_PIN_MAX) {  // the callback reads the pinned staging area directly
+    char *st = nullptr;
+    FBCHK(pin_reserve(e, xb, &st));
+    HIPCHK(hipMemcpyAsync(st, e->ext_x.p, xb, hipMemcpyDeviceToHost, e->stream));
+    FBCHK(sync_stream(e));
+    *xh = reinterpret_cast<const double *>(st);
+  } else {
+    fr->spill.resize((size_t)fr->N * (size_t)rows);
+    FBCHK(sync_stream(e));
+    HIPCHK(hipMemcpy(fr->spill.data(), e->ext_x.p, xb, hipMemcpyDeviceToHost));
+    *xh = fr->spill.data();
+  }
+  e->foreign.batch_bytes_d2h += (int64_t)xb;
+  return FB_OK;
+}
+// The score modes: the model scores the `rows` rows of e->wav; *sc is device memory [rows][S] of *dtype, in stream order.
+static int foreign_scores(fb_engine *e, FbForeignRun *fr, int rows, const void **sc, int *dtype) {
+  const fb_victim *v = fr->v;
+  const double *xh = nullptr;
+  FBCHK(foreign_hand_rows(e, fr, rows, &xh));
+  e->foreign.model_calls += 1;
+  if (v->mode == FB_VICTIM_DEVICE_SCORES) {
+    const int rc = v->score_dev(v->ctx, (void *)e->stream, fr->N, rows, fr->S);
+    if (rc != 0) {
+      (void)sync_stream(e);  // (whatever the model did enqueue has finished when the caller sees the error)
+      return fb_fail(FB_E_CALLBACK, "score callback failed (rc %d)", rc);
+    }
+    *sc = v->dev->scores;
+    *dtype = v->dev->score_dtype;
+    return FB_OK;
+  }
+  const size_t n = (size_t)rows * fr->S;
+  const int rc = v->score(v->ctx, xh, fr->N, rows, fr->sc_h.data());
+  if (rc != 0) return fb_fail(FB_E_CALLBACK, "score callback failed (rc %d)", rc);
+  FBCHK(h2d(e, e->raw.p, fr->sc_h.data(), sizeof(double) * n));
+  e->foreign.score_bytes_h2d += (int64_t)(sizeof(double) * n);
+  *sc = e->raw.p;
+  *dtype = FB_DT_F64;
+  return FB_OK;
+}
+// The decisions of the `rows` rows of e->wav: dec[rows], and the model's scores[rows][S] (NaN where a decision callback wrote
+// none; nullable).  One look.
+static int foreign_decide(fb_engine *e, FbForeignRun *fr, int rows, int *dec, double *scores) {
+  const fb_victim *v = fr->v;
+  const int S = fr->S;
+  if (v->mode == FB_VICTIM_HOST_DECISIONS) {
+    const double *xh = nullptr;
+    FBCHK(foreign_hand_rows(e, fr, rows, &xh));
+    for (size_t i = 0; i < (size_t)rows * S; ++i) fr->sc_h[i] = std::numeric_limits<double>::quiet_NaN();
+    for (int j = 0; j < rows; ++j) fr->dec_h[j] = -2;
+    e->foreign.model_calls += 1;
+    const int rc = v->decide(v->ctx, xh, fr->N, rows, fr->dec_h.data(), fr->sc_h.data());
+    if (rc != 0) return fb_fail(FB_E_CALLBACK, "decide callback failed (rc %d)", rc);
+    for (int j = 0; j < rows; ++j) {
+      const int d = fr->dec_h[j];
+      const bool ok = d == -2 || (fr->task == FB_TASK_SV ? (d == 1 || d == -1)
+                                  : fr->task == FB_TASK_OSI ? (d >= -1 && d < S) : (d >= 0 && d < S));
+      if (!ok) return fb_fail(FB_E_CALLBACK, "the decide callback returned %d for row %d: no decision of this task and not -2", d, j);
+      dec[j] = d;
+    }
+    if (scores) memcpy(scores, fr->sc_h.data(), sizeof(double) * (size_t)rows * S);
+    return FB_OK;
+  }
+  const void *sc = nullptr;
+  int dtype = FB_DT_F64;
+  FBCHK(foreign_scores(e, fr, rows, &sc, &dtype));
+  int *dec_dev = e->fg_look.as<int>();
+  double *sc_dev = e->fg_look.as<double>() + ((size_t)rows + 1) / 2;
+  fb_launch_decide_foreign(e->stream, dtype, sc, rows, S, fr->task, fr->threshold, dec_dev, sc_dev);
+  const size_t nd = foreign_look_doubles(rows, S);
+  FBCHK(d2h(e, fr->look.data(), e->fg_look.p, sizeof(double) * nd));
+  FBCHK(sync_stream(e));
+  memcpy(dec, fr->look.data(), sizeof(int) * (size_t)rows);
+  if (scores) memcpy(scores, fr->look.data() + ((size_t)rows + 1) / 2, sizeof(double) * (size_t)rows * S);
+  return FB_OK;
+}
+
 static int check_pso_swarm(int P, double eps, double v_max, int bits) {
   if (P < 2 || P > FB_PSO_MAX_PARTICLES) return fb_fail(FB_E_ARG, "particles %d outside 2 .. %d", P, FB_PSO_MAX_PARTICLES);
   if (!isfinite(eps) || !(eps > 0.0)) return fb_fail(FB_E_ARG, "epsilon must be finite and > 0");
@@ -3632,25 +3808,29 @@ static int ensure_pso_buffers(fb_engine *e, int64_t N, int P) {
   return FB_OK;
 }
 
-extern "C" int fb_attack_pso(fb_engine *e, const fb_nes_params *p, const fb_pso_params *q, const double *audio, int64_t N,
-                             int16_t *adv_i16, double *adv_f64, int *success, int *n_iters, double *trace, double *losses) {
+// vic: null for the engine's own system (fb_attack_pso), else the foreign victim that scores the swarm (fb_attack_pso_foreign)
+static int pso_attack(fb_engine *e, const fb_nes_params *p, const fb_pso_params *q, const fb_victim *vic, const double *audio,
+                      int64_t N, int16_t *adv_i16, double *adv_f64, int *success, int *n_iters, double *trace, double *losses) {
   if (e) e->bench_it = e->nes_rec.iter = -1;
   if (!e || !p || !q || !audio || !adv_i16 || !success || !n_iters || !trace || !losses) return fb_fail(FB_E_ARG, "null argument");
-  if (!e->have_gmm) return fb_fail(FB_E_STATE, "no model loaded");
+  FbForeignRun fr;
+  if (vic) FBCHK(foreign_setup(e, "fb_attack_pso_foreign", p, vic, N, q->particles, false, &fr));
+  else if (!e->have_gmm) return fb_fail(FB_E_STATE, "no model loaded");
   int R = 1, quorum = 1;   // replicas of every particle (fb_set_query_eot; the quorum is the decision-only attacks')
-  FBCHK(query_replicas(e, "fb_attack_pso", &R, &quorum));
+  if (!vic) FBCHK(query_replicas(e, "fb_attack_pso", &R, &quorum));
   const int P = q->particles, bits = nes_bits(p);
   FBCHK(check_pso_swarm(P, p->epsilon, q->v_max, bits));
   for (double c : {q->w_init, q->w_end, q->c1, q->c2})
     if (!isfinite(c) || c < 0.0) return fb_fail(FB_E_ARG, "w_init, w_end, c1 and c2 must be finite and >= 0");
   if (p->max_iter < 1) return fb_fail(FB_E_ARG, "max_iter must be > 0");
   if (N <= 0) return fb_fail(FB_E_ARG, "empty audio");
-  if (p->task != e->task) return fb_fail(FB_E_ARG, "params.task %d != engine system task %d", p->task, e->task);
-  const int S = fb_num_speakers(e);
+  if (!vic && p->task != e->task) return fb_fail(FB_E_ARG, "params.task %d != engine system task %d", p->task, e->task);
+  const int S = vic ? vic->S : fb_num_speakers(e);
   FBCHK(check_goal_params(p, S));
-  if (num_frames(e->cfg, N) <= 0) return fb_fail(FB_E_ARG, "audio shorter than one frame");
+  if (!vic && num_frames(e->cfg, N) <= 0) return fb_fail(FB_E_ARG, "audio shorter than one frame");
   HIPCHK(hipSetDevice(e->device));
-  if (R > 1) FBCHK(prepare_nes_replicas(e, N, P));
+  if (vic) FBCHK(foreign_buffers(e, &fr));
+  else if (R > 1) FBCHK(prepare_nes_replicas(e, N, P));
   else FBCHK(prepare_nes_batch(e, N, P));
   FBCHK(ensure_pso_buffers(e, N, P));
   // what the host reads once per iteration, in one block: k_loss's result block (for its "no voiced frames" word), loss[P],
@@ -3675,7 +3855,19 @@ extern "C" int fb_attack_pso(fb_engine *e, const fb_nes_params *p, const fb_pso_
   auto t_prev = std::chrono::steady_clock::now();
   for (;; ++k) {
     FbScoreCall call{FbRngPoint{p->seed, p->stream, (uint32_t)k, 0}};
-    if (R > 1) {   // every particle under R replicas: l_p and its score row are fb_set_eot's means (k_loss_eot)
+    if (vic) {   // the model's scores are final: loss_fn on them as fb_attack_ext / fb_attack_dev form it
+      const void *fsc = nullptr;
+      int dtype = FB_DT_F64;
+      FBCHK(foreign_scores(e, &fr, P, &fsc, &dtype));
+      if (dtype == FB_DT_F32)
+        fb_launch_loss(e->stream, static_cast<const float *>(fsc), nullptr, P, S, p->task, 1, p->attack_type, e->ext_z.as<double>(),
+                       e->ext_z.as<double>() + 64, p->threshold, p->adver_thresh, p->target, p->true_label, nullptr, 0, scores_dev,
+                       loss_dev, out_dev);
+      else
+        fb_launch_loss(e->stream, static_cast<const double *>(fsc), nullptr, P, S, p->task, 1, p->attack_type, e->ext_z.as<double>(),
+                       e->ext_z.as<double>() + 64, p->threshold, p->adver_thresh, p->target, p->true_label, nullptr, 0, scores_dev,
+                       loss_dev, out_dev);
+    } else if (R > 1) {   // every particle under R replicas: l_p and its score row are fb_set_eot's means (k_loss_eot)
       call.eot = e->eot;
       call.K = e->comp_K1 + 1;
       FBCHK(run_scoring(e, call, P * R, e->h_frame_off[P * R]));
@@ -3740,6 +3932,17 @@ extern "C" int fb_attack_pso(fb_engine *e, const fb_nes_params *p, const fb_pso_
   FBCHK(sync_stream(e));
   HIPCHK(hipGetLastError());
   return FB_OK;
+}
+
+extern "C" int fb_attack_pso(fb_engine *e, const fb_nes_params *p, const fb_pso_params *q, const double *audio, int64_t N,
+                             int16_t *adv_i16, double *adv_f64, int *success, int *n_iters, double *trace, double *losses) {
+  return pso_attack(e, p, q, nullptr, audio, N, adv_i16, adv_f64, success, n_iters, trace, losses);
+}
+extern "C" int fb_attack_pso_foreign(fb_engine *e, const fb_nes_params *p, const fb_pso_params *q, const fb_victim *v,
+                                     const double *audio, int64_t N, int16_t *adv_i16, double *adv_f64, int *success, int *n_iters,
+                                     double *trace, double *losses) {
+  if (!e || !p || !q || !v) return fb_fail(FB_E_ARG, "null argument (the victim descriptor included)");
+  return pso_attack(e, p, q, v, audio, N, adv_i16, adv_f64, success, n_iters, trace, losses);
 }
 
 extern "C" int fb_debug_pso_init(fb_engine *e, const double *audio, int64_t N, double epsilon, int P, double v_max, uint64_t seed,
@@ -3834,15 +4037,18 @@ static void launch_kv_candidates(fb_engine *e, int64_t N, int W, int rows, const
                           e->kv_mb.as<int32_t>(), e->kv_cum.as<long long>(), e->kv_E.as<long long>(), out);
 }
 
-extern "C" int fb_attack_kenansville(fb_engine *e, const fb_nes_params *p, const fb_kv_params *k, const int32_t *tables,
-                                     const double *audio, int64_t N, int16_t *adv_i16, int *success, int *factor,
-                                     int *n_queries, int *n_rounds, int *qs, int *decisions, double *scores, int *trace) {
+// vic: null for the engine's own system, else the foreign victim that decides the candidates (fb_attack_kenansville_foreign)
+static int kv_attack(fb_engine *e, const fb_nes_params *p, const fb_kv_params *k, const fb_victim *vic, const int32_t *tables,
+                     const double *audio, int64_t N, int16_t *adv_i16, int *success, int *factor, int *n_queries, int *n_rounds,
+                     int *qs, int *decisions, double *scores, int *trace) {
   if (e) e->bench_it = e->nes_rec.iter = -1;
   if (!e || !p || !k || !audio || !adv_i16 || !success || !factor || !n_queries || !n_rounds || !qs || !decisions || !scores || !trace)
     return fb_fail(FB_E_ARG, "null argument");
-  if (!e->have_gmm) return fb_fail(FB_E_STATE, "no model loaded");
+  FbForeignRun fr;
+  if (vic) FBCHK(foreign_setup(e, "fb_attack_kenansville_foreign", p, vic, N, k->grid, true, &fr));
+  else if (!e->have_gmm) return fb_fail(FB_E_STATE, "no model loaded");
   int R = 1, quorum = 1;   // replicas of every candidate row and the votes a row needs (fb_set_query_eot)
-  FBCHK(query_replicas(e, "fb_attack_kenansville", &R, &quorum));
+  if (!vic) FBCHK(query_replicas(e, "fb_attack_kenansville", &R, &quorum));
   const int W = k->window, G = k->grid, bits = nes_bits(p);
   FBCHK(check_kv_tables(W, tables));
   if (G < 1 || G > FB_KV_MAX_ROWS) return fb_fail(FB_E_ARG, "grid %d outside 1 .. %d", G, FB_KV_MAX_ROWS);
@@ -3850,10 +4056,10 @@ extern "C" int fb_attack_kenansville(fb_engine *e, const fb_nes_params *p, const
   if (k->max_rounds < 1 || k->max_rounds > FB_KV_MAX_ROUNDS) return fb_fail(FB_E_ARG, "max_rounds %d outside 1 .. %d", k->max_rounds, FB_KV_MAX_ROUNDS);
   if (bits < 2 || bits > 16) return fb_fail(FB_E_ARG, "bits_per_sample %d unsupported (2 .. 16)", bits);
   if (N <= 0) return fb_fail(FB_E_ARG, "empty audio");
-  if (p->task != e->task) return fb_fail(FB_E_ARG, "params.task %d != engine system task %d", p->task, e->task);
+  if (!vic && p->task != e->task) return fb_fail(FB_E_ARG, "params.task %d != engine system task %d", p->task, e->task);
   if (p->task != FB_TASK_SV && p->task != FB_TASK_OSI && p->task != FB_TASK_CSI) return fb_fail(FB_E_ARG, "bad task %d", p->task);
   if (p->attack_type != FB_TARGETED && p->attack_type != FB_UNTARGETED) return fb_fail(FB_E_ARG, "bad attack_type %d", p->attack_type);
-  const int S = fb_num_speakers(e);
+  const int S = vic ? vic->S : fb_num_speakers(e);
   const bool targeted = p->attack_type == FB_TARGETED;
   const int label = targeted ? p->target : p->true_label;   // a decision value
   {
@@ -3861,8 +4067,9 @@ extern "C" int fb_attack_kenansville(fb_engine *e, const fb_nes_params *p, const
                   : p->task == FB_TASK_OSI ? (label >= -1 && label < S) : (label >= 0 && label < S);
     if (!ok) return fb_fail(FB_E_ARG, "%s %d is no decision of this system", targeted ? "target" : "true label", label);
   }
-  if (num_frames(e->cfg, N) <= 0) return fb_fail(FB_E_ARG, "audio shorter than one frame");
+  if (!vic && num_frames(e->cfg, N) <= 0) return fb_fail(FB_E_ARG, "audio shorter than one frame");
   HIPCHK(hipSetDevice(e->device));
+  if (vic) FBCHK(foreign_buffers(e, &fr));
   FBCHK(e->audio.ensure(sizeof(double) * (size_t)N));
   FBCHK(prepare_kv(e, N, W, tables));
   // what the host reads once per round, in one block: k_loss's result block (not read), loss[G] (not read), scores[G][S], tv[G]
@@ -3910,13 +4117,20 @@ extern "C" int fb_attack_kenansville(fb_engine *e, const fb_nes_params *p, const
       }
     }
     const int rows = (int)cand.size();
-    if (R > 1) FBCHK(prepare_nes_replicas(e, N, rows));
+    if (vic) {}   // (e->wav holds a full round's rows: foreign_buffers)
+    else if (R > 1) FBCHK(prepare_nes_replicas(e, N, rows));
     else FBCHK(prepare_nes_batch(e, N, rows));
     launch_kv_candidates(e, N, W, rows, cand.data(), e->wav.as<int16_t>());
     FbScoreCall call{FbRngPoint{p->seed, p->stream, (uint32_t)r, 0}};
     int first = -1;   // the smallest succeeding candidate's row
     for (int j = 0; j < G; ++j) qs[(size_t)r * G + j] = j < rows ? cand[j] : -1;
-    if (R > 1) {
+    if (vic) {   // the model's decisions, or the rule on its scores: one look
+      if (rows > 0) FBCHK(foreign_decide(e, &fr, rows, decisions + (size_t)r * G, scores + (size_t)r * G * S));
+      for (int j = 0; j < rows && first < 0; ++j) {
+        const int d = decisions[(size_t)r * G + j];
+        if (d != -2 && (targeted ? d == label : d != label)) first = j;
+      }
+    } else if (R > 1) {
       call.eot = e->eot;
       call.K = e->comp_K1 + 1;
       FBCHK(run_scoring(e, call, rows * R, e->h_frame_off[rows * R]));
@@ -3983,6 +4197,19 @@ extern "C" int fb_attack_kenansville(fb_engine *e, const fb_nes_params *p, const
   FBCHK(sync_stream(e));
   HIPCHK(hipGetLastError());
   return FB_OK;
+}
+
+extern "C" int fb_attack_kenansville(fb_engine *e, const fb_nes_params *p, const fb_kv_params *k, const int32_t *tables,
+                                     const double *audio, int64_t N, int16_t *adv_i16, int *success, int *factor,
+                                     int *n_queries, int *n_rounds, int *qs, int *decisions, double *scores, int *trace) {
+  return kv_attack(e, p, k, nullptr, tables, audio, N, adv_i16, success, factor, n_queries, n_rounds, qs, decisions, scores, trace);
+}
+extern "C" int fb_attack_kenansville_foreign(fb_engine *e, const fb_nes_params *p, const fb_kv_params *k, const fb_victim *v,
+                                             const int32_t *tables, const double *audio, int64_t N, int16_t *adv_i16, int *success,
+                                             int *factor, int *n_queries, int *n_rounds, int *qs, int *decisions, double *scores,
+                                             int *trace) {
+  if (!e || !p || !k || !v) return fb_fail(FB_E_ARG, "null argument (the victim descriptor included)");
+  return kv_attack(e, p, k, v, tables, audio, N, adv_i16, success, factor, n_queries, n_rounds, qs, decisions, scores, trace);
 }
 
 extern "C" int fb_debug_kv_analyse(fb_engine *e, const int16_t *x, int64_t N, int W, const int32_t *tables, int32_t *a,
@@ -4122,25 +4349,28 @@ static void launch_hsj_dir(fb_engine *e, int B, int64_t N, uint64_t seed, uint32
   fb_launch_hsj_sum(e->stream, e->hsj_part.as<double>(), fb_hsj_chunks(N), e->hsj_sc.as<double>() + 1);
 }
 
-extern "C" int fb_attack_hsj(fb_engine *e, const fb_nes_params *p, const fb_hsj_params *k, const double *audio, const double *init,
-                             int64_t N, int16_t *adv_i16, double *adv_f64, int *success, double *dist2, int *n_iters,
-                             int *n_queries, double *trace, int *decisions, long long decisions_cap, double *x_trace) {
+// vic: null for the engine's own system, else the foreign victim that decides every row (fb_attack_hsj_foreign)
+static int hsj_attack(fb_engine *e, const fb_nes_params *p, const fb_hsj_params *k, const fb_victim *vic, const double *audio,
+                      const double *init, int64_t N, int16_t *adv_i16, double *adv_f64, int *success, double *dist2, int *n_iters,
+                      int *n_queries, double *trace, int *decisions, long long decisions_cap, double *x_trace) {
   if (e) e->bench_it = e->nes_rec.iter = -1;
   if (!e || !p || !k || !audio || !adv_i16 || !success || !dist2 || !n_iters || !n_queries || !trace || !decisions)
     return fb_fail(FB_E_ARG, "null argument");
   if (!init) return fb_fail(FB_E_ARG, "null init: HopSkipJump starts from an audio that is already decided as wanted");
-  if (!e->have_gmm) return fb_fail(FB_E_STATE, "no model loaded");
+  FbForeignRun fr;
+  if (vic) FBCHK(foreign_setup(e, "fb_attack_hsj_foreign", p, vic, N, std::max(k->grid, k->num_evals_max), true, &fr));
+  else if (!e->have_gmm) return fb_fail(FB_E_STATE, "no model loaded");
   int R = 1, quorum = 1;   // replicas of every candidate row and the votes a row needs (fb_set_query_eot)
-  FBCHK(query_replicas(e, "fb_attack_hsj", &R, &quorum));
+  if (!vic) FBCHK(query_replicas(e, "fb_attack_hsj", &R, &quorum));
   FBCHK(check_hsj_params(k));
   const int G = k->grid, bits = nes_bits(p);
   if (p->max_iter < 0) return fb_fail(FB_E_ARG, "max_iter %d < 0", p->max_iter);
   if (bits < 2 || bits > 16) return fb_fail(FB_E_ARG, "bits_per_sample %d unsupported (2 .. 16)", bits);
   if (N <= 0) return fb_fail(FB_E_ARG, "empty audio");
-  if (p->task != e->task) return fb_fail(FB_E_ARG, "params.task %d != engine system task %d", p->task, e->task);
+  if (!vic && p->task != e->task) return fb_fail(FB_E_ARG, "params.task %d != engine system task %d", p->task, e->task);
   if (p->task != FB_TASK_SV && p->task != FB_TASK_OSI && p->task != FB_TASK_CSI) return fb_fail(FB_E_ARG, "bad task %d", p->task);
   if (p->attack_type != FB_TARGETED && p->attack_type != FB_UNTARGETED) return fb_fail(FB_E_ARG, "bad attack_type %d", p->attack_type);
-  const int S = fb_num_speakers(e);
+  const int S = vic ? vic->S : fb_num_speakers(e);
   const bool targeted = p->attack_type == FB_TARGETED;
   const int label = targeted ? p->target : p->true_label;   // a decision value
   {
@@ -4148,7 +4378,7 @@ extern "C" int fb_attack_hsj(fb_engine *e, const fb_nes_params *p, const fb_hsj_
                   : p->task == FB_TASK_OSI ? (label >= -1 && label < S) : (label >= 0 && label < S);
     if (!ok) return fb_fail(FB_E_ARG, "%s %d is no decision of this system", targeted ? "target" : "true label", label);
   }
-  if (num_frames(e->cfg, N) <= 0) return fb_fail(FB_E_ARG, "audio shorter than one frame");
+  if (!vic && num_frames(e->cfg, N) <= 0) return fb_fail(FB_E_ARG, "audio shorter than one frame");
   const long long need = fb_hsj_max_rows(p->max_iter, k);
   if (decisions_cap < need)
     return fb_fail(FB_E_ARG, "the decision log holds %lld entries, this call may score %lld rows", decisions_cap, need);
@@ -4161,6 +4391,7 @@ extern "C" int fb_attack_hsj(fb_engine *e, const fb_nes_params *p, const fb_hsj_
     FBCHK(prepare_nes_replicas(e, N, max_rows));
     FBCHK(e->vote_look.ensure(vote_look_bytes(max_rows, S)));
   }
+  if (vic) FBCHK(foreign_buffers(e, &fr));
   FBCHK(prepare_hsj(e, N, max_rows));
   // the probes launch keeps its normals as float32 [B][N] for the direction launch: at B = 1024, N = 48 000 the pair takes
   // 160 us so against 206 us with the direction launch drawing them again (tools/hsj_rate.py)
@@ -4188,9 +4419,20 @@ extern "C" int fb_attack_hsj(fb_engine *e, const fb_nes_params *p, const fb_hsj_
   bool stopped = false;   // max_queries: nothing is scored any more
   auto over = [&](int rows) { return k->max_queries > 0 && (long long)queries + (long long)rows * R > k->max_queries; };
   // the batch layout of `rows` candidate rows (under R replicas: of rows * R)
-  auto layout = [&](int rows) -> int { return R > 1 ? prepare_nes_replicas(e, N, rows) : prepare_nes_batch(e, N, rows); };
+  // (a foreign victim: e->wav holds the largest batch already, foreign_buffers)
+  auto layout = [&](int rows) -> int { return vic ? FB_OK : R > 1 ? prepare_nes_replicas(e, N, rows) : prepare_nes_batch(e, N, rows); };
   // scores the `rows` rows that stand in e->wav: dec[0 .. rows) and the log; one look
   auto score = [&](int rows) -> int {
+    if (vic) {   // the model's decisions, or the rule on its scores: one look
+      FBCHK(foreign_decide(e, &fr, rows, decisions + logged, nullptr));
+      for (int j = 0; j < rows; ++j) {
+        const int d = decisions[logged + j];
+        dec[j] = (d != -2 && (targeted ? d == label : d != label)) ? 1 : 0;
+      }
+      logged += rows;
+      queries += rows;
+      return FB_OK;
+    }
     FbScoreCall call{FbRngPoint{p->seed, p->stream, epoch++, 0}};
     if (R > 1) {   // R replicas of every row: the log holds the votes, a row is adversarial from `quorum` votes on
       call.eot = e->eot;
@@ -4371,6 +4613,21 @@ extern "C" int fb_attack_hsj(fb_engine *e, const fb_nes_params *p, const fb_hsj_
   FBCHK(sync_stream(e));
   HIPCHK(hipGetLastError());
   return FB_OK;
+}
+
+extern "C" int fb_attack_hsj(fb_engine *e, const fb_nes_params *p, const fb_hsj_params *k, const double *audio, const double *init,
+                             int64_t N, int16_t *adv_i16, double *adv_f64, int *success, double *dist2, int *n_iters,
+                             int *n_queries, double *trace, int *decisions, long long decisions_cap, double *x_trace) {
+  return hsj_attack(e, p, k, nullptr, audio, init, N, adv_i16, adv_f64, success, dist2, n_iters, n_queries, trace, decisions,
+                    decisions_cap, x_trace);
+}
+extern "C" int fb_attack_hsj_foreign(fb_engine *e, const fb_nes_params *p, const fb_hsj_params *k, const fb_victim *v,
+                                     const double *audio, const double *init, int64_t N, int16_t *adv_i16, double *adv_f64,
+                                     int *success, double *dist2, int *n_iters, int *n_queries, double *trace, int *decisions,
+                                     long long decisions_cap, double *x_trace) {
+  if (!e || !p || !k || !v) return fb_fail(FB_E_ARG, "null argument (the victim descriptor included)");
+  return hsj_attack(e, p, k, v, audio, init, N, adv_i16, adv_f64, success, dist2, n_iters, n_queries, trace, decisions,
+                    decisions_cap, x_trace);
 }
 
 // ---- the hooks: exactly the launches of the attack, on state handed in
@@ -4589,6 +4846,99 @@ extern "C" int fb_bench_vote(fb_engine *e, const double *raw, const int *tv, int
   HIPCHK(hipEventElapsedTime(&t, e->ev0, e->ev1));
   *ms = (double)t / reps;
   FBCHK(sync_stream(e));
+  HIPCHK(hipGetLastError());
+  return FB_OK;
+}
+
+// ---- foreign victims: the two launches alone, on arrays handed in (fakebob_hip_test.h)
+extern "C" int fb_debug_rows_to_model(fb_engine *e, const int16_t *rows_i16, int rows, int64_t N, int bits, int dtype, void *out) {
+  if (!e || !rows_i16 || !out) return fb_fail(FB_E_ARG, "null argument");
+  if (rows < 1 || N < 1 || (int64_t)rows * N > ((int64_t)1 << 31)) return fb_fail(FB_E_ARG, "rows %d x N %lld outside 1 .. 2^31 elements", rows, (long long)N);
+  if (bits < 2 || bits > 16) return fb_fail(FB_E_ARG, "bits_per_sample %d unsupported (2 .. 16)", bits);
+  if (dtype != FB_DT_F32 && dtype != FB_DT_F64) return fb_fail(FB_E_ARG, "dtype %d: FB_DT_F32 or FB_DT_F64", dtype);
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  e->cached_B = -1;  // (e->wav takes the rows, without a batch layout)
+  const size_t n = (size_t)rows * (size_t)N, xb = n * (dtype == FB_DT_F32 ? sizeof(float) : sizeof(double));
+  FBCHK(e->wav.ensure(sizeof(int16_t) * n));
+  FBCHK(e->ext_x.ensure(xb));
+  FBCHK(h2d(e, e->wav.p, rows_i16, sizeof(int16_t) * n));
+  fb_launch_rows_to_model(e->stream, dtype, e->wav.as<int16_t>(), rows, N, bits, e->ext_x.p);
+  FBCHK(d2h(e, out, e->ext_x.p, xb));
+  FBCHK(sync_stream(e));
+  HIPCHK(hipGetLastError());
+  return FB_OK;
+}
+extern "C" int fb_debug_decide_foreign(fb_engine *e, const void *scores, int dtype, int rows, int S, int task, double threshold,
+                                       int *decisions, double *scores_f64) {
+  if (!e || !scores || !decisions || !scores_f64) return fb_fail(FB_E_ARG, "null argument");
+  if (rows < 1 || rows > 65535) return fb_fail(FB_E_ARG, "rows %d outside 1 .. 65535", rows);
+  if (S < 1 || S > 62) return fb_fail(FB_E_ARG, "S %d outside 1 .. 62", S);
+  if (task != FB_TASK_SV && task != FB_TASK_OSI && task != FB_TASK_CSI) return fb_fail(FB_E_ARG, "bad task %d", task);
+  if (task == FB_TASK_SV && S != 1) return fb_fail(FB_E_ARG, "SV scores one speaker (got S = %d)", S);
+  if (dtype != FB_DT_F32 && dtype != FB_DT_F64) return fb_fail(FB_E_ARG, "dtype %d: FB_DT_F32 or FB_DT_F64", dtype);
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  const size_t n = (size_t)rows * S, sb = n * (dtype == FB_DT_F32 ? sizeof(float) : sizeof(double));
+  FBCHK(e->raw.ensure(sb));
+  FBCHK(e->fg_look.ensure(sizeof(double) * foreign_look_doubles(rows, S)));
+  FBCHK(h2d(e, e->raw.p, scores, sb));
+  double *sc_dev = e->fg_look.as<double>() + ((size_t)rows + 1) / 2;
+  fb_launch_decide_foreign(e->stream, dtype, e->raw.p, rows, S, task, threshold, e->fg_look.as<int>(), sc_dev);
+  FBCHK(d2h(e, decisions, e->fg_look.p, sizeof(int) * (size_t)rows));
+  FBCHK(d2h(e, scores_f64, sc_dev, sizeof(double) * n));
+  FBCHK(sync_stream(e));
+  HIPCHK(hipGetLastError());
+  return FB_OK;
+}
+// tools/foreign_rate.py: ms[5] = milliseconds of k_rows_to_model<float>, k_rows_to_model<double>, k_decide_foreign<double>
+// (`reps` launches of each between two events after one to warm up), and of the two ways a host victim can get its rows, on
+// the host's clock, once each after one to warm up: the float64 rows copied to the host; the int16 rows copied and widened there
+extern "C" int fb_bench_foreign_rows(fb_engine *e, int rows, int64_t N, int bits, int S, int reps, double *ms) {
+  if (!e || !ms || reps < 1) return fb_fail(FB_E_ARG, "bad argument");
+  if (rows < 1 || rows > 65535 || N < 1 || S < 1 || S > 62 || bits < 2 || bits > 16) return fb_fail(FB_E_ARG, "bad shape");
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  e->cached_B = -1;
+  const size_t n = (size_t)rows * (size_t)N;
+  FBCHK(e->wav.ensure(sizeof(int16_t) * n));
+  FBCHK(e->ext_x.ensure(sizeof(double) * n));
+  FBCHK(e->raw.ensure(sizeof(double) * (size_t)rows * S));
+  FBCHK(e->fg_look.ensure(sizeof(double) * foreign_look_doubles(rows, S)));
+  HIPCHK(hipMemsetAsync(e->wav.p, 0x11, sizeof(int16_t) * n, e->stream));
+  HIPCHK(hipMemsetAsync(e->raw.p, 0, sizeof(double) * (size_t)rows * S, e->stream));
+  auto run = [&](int which) {
+    if (which == 0) fb_launch_rows_to_model(e->stream, FB_DT_F32, e->wav.as<int16_t>(), rows, N, bits, e->ext_x.p);
+    else if (which == 1) fb_launch_rows_to_model(e->stream, FB_DT_F64, e->wav.as<int16_t>(), rows, N, bits, e->ext_x.p);
+    else fb_launch_decide_foreign(e->stream, FB_DT_F64, e->raw.p, rows, S, FB_TASK_CSI, 0.0, e->fg_look.as<int>(),
+                                  e->fg_look.as<double>() + ((size_t)rows + 1) / 2);
+  };
+  for (int which = 0; which < 3; ++which) {
+    run(which);
+    HIPCHK(hipEventRecord(e->ev0, e->stream));
+    for (int i = 0; i < reps; ++i) run(which);
+    HIPCHK(hipEventRecord(e->ev1, e->stream));
+    HIPCHK(hipEventSynchronize(e->ev1));
+    float t = 0.f;
+    HIPCHK(hipEventElapsedTime(&t, e->ev0, e->ev1));
+    ms[which] = (double)t / reps;
+  }
+  run(1);
+  std::vector<double> xh(n);
+  std::vector<int16_t> qh(n);
+  const double scale = ldexp(1.0, -(bits - 1));
+  for (int pass = 0; pass < 2; ++pass) {   // (the first pass touches the pages)
+    auto t0 = std::chrono::steady_clock::now();
+    FBCHK(d2h(e, xh.data(), e->ext_x.p, sizeof(double) * n));
+    FBCHK(sync_stream(e));
+    auto t1 = std::chrono::steady_clock::now();
+    FBCHK(d2h(e, qh.data(), e->wav.p, sizeof(int16_t) * n));
+    FBCHK(sync_stream(e));
+    for (size_t i = 0; i < n; ++i) xh[i] = (double)qh[i] * scale;
+    auto t2 = std::chrono::steady_clock::now();
+    ms[3] = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    ms[4] = std::chrono::duration<double, std::milli>(t2 - t1).count();
+  }
   HIPCHK(hipGetLastError());
   return FB_OK;
 }

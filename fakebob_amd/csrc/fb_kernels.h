@@ -324,6 +324,14 @@ void fb_launch_loss_eot(hipStream_t s, const double *raw, const int *tv, int B, 
 void fb_launch_vote(hipStream_t s, const double *raw, const int *tv, int rows, int r, int M, int task, int znorm_all,
                     const double *z_mean, const double *z_std, double threshold, int targeted, int label, double *rep_sc,
                     int *votes, int *nodec, double *mean);
+// ---- foreign victims of the swarm and the decision-only attacks (fb_attack_*_foreign; foreign_rows_kernel.hip) ----------
+// the int16 batch q[rows][N] as the audio a foreign model reads: x[rows][N] of x_dtype (FB_DT_*), x = q * 2^-(bits - 1),
+// exact.  16-byte loads and stores when q and x are 16-byte aligned, element by element otherwise
+void fb_launch_rows_to_model(hipStream_t s, int x_dtype, const int16_t *q, int rows, int64_t N, int bits, void *x);
+// a foreign model's scores[rows][S] of score_dtype -> decisions[rows] by the make_decisions rule and the scores widened to
+// float64 (k_decide_foreign)
+void fb_launch_decide_foreign(hipStream_t s, int score_dtype, const void *scores, int rows, int S, int task, double threshold,
+                              int *decisions, double *scores_out);
 // k_grad_update (iteration `next_iter - 1`) + k_perturb (iteration next_iter) in one launch; device-controlled attacks
 // with Philox noise and half <= FB_FUSE_MAX_HALF only.  Returns the number of distance partials written.
 // threads: 256 or 512 per workgroup of 256 samples (the same bits either way; nes_kernels.hip says which when)

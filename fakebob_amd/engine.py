@@ -300,6 +300,43 @@ class Engine(object):
         N.check(self._L.fb_bench_vote(*head, C.c_double(float(threshold)), *tail, C.c_int(int(reps)), C.byref(ms)))
         return ms.value
 
+    # ---- foreign victims of the swarm and the decision-only attacks: the two launches alone
+    def debug_rows_to_model(self, rows_i16, bits_per_sample=16, dtype=np.float64):
+        """k_rows_to_model alone (fb_debug_rows_to_model): int16 rows (rows, N) -> (rows, N) float32 / float64, the audio a
+        foreign model reads."""
+        q = np.ascontiguousarray(rows_i16, np.int16)
+        q = q.reshape(1, -1) if q.ndim == 1 else q
+        dt = np.dtype(dtype)
+        out = np.empty(q.shape, dt)
+        N.check(self._L.fb_debug_rows_to_model(self._h, N.ptr(q), C.c_int(q.shape[0]), C.c_int64(q.shape[1]),
+                                               C.c_int(int(bits_per_sample)), C.c_int(self._np_dt(dt)), N.ptr(out)))
+        return out
+
+    def debug_decide_foreign(self, scores, task, threshold):
+        """k_decide_foreign alone (fb_debug_decide_foreign): scores (rows, S) float32 / float64 -> (decisions (rows,) int32,
+        scores (rows, S) float64), the two parts of the look block."""
+        sc = np.ascontiguousarray(scores)
+        if sc.dtype not in (np.float32, np.float64):
+            sc = sc.astype(np.float64)
+        rows, S = sc.shape
+        dec, out = np.empty(rows, np.int32), np.empty((rows, S), np.float64)
+        N.check(self._L.fb_debug_decide_foreign(self._h, N.ptr(sc), C.c_int(self._np_dt(sc.dtype)), C.c_int(rows), C.c_int(S),
+                                                C.c_int(N.TASK[task]), C.c_double(float(threshold)), N.ptr(dec), N.ptr(out)))
+        return dec, out
+
+    @staticmethod
+    def _np_dt(dt):
+        return N.FB_DT_F32 if np.dtype(dt) == np.float32 else N.FB_DT_F64
+
+    def bench_foreign_rows(self, rows, n, S=1, bits_per_sample=16, reps=20):
+        """fb_bench_foreign_rows -> milliseconds: k_rows_to_model<float>, k_rows_to_model<double>, k_decide_foreign per
+        launch; the float64 rows copied to the host; the int16 rows copied and widened on the host."""
+        ms = np.zeros(5, np.float64)
+        N.check(self._L.fb_bench_foreign_rows(self._h, C.c_int(int(rows)), C.c_int64(int(n)), C.c_int(int(bits_per_sample)),
+                                              C.c_int(int(S)), C.c_int(int(reps)), N.ptr(ms)))
+        return dict(rows_f32=float(ms[0]), rows_f64=float(ms[1]), decide=float(ms[2]), d2h_f64=float(ms[3]),
+                    d2h_i16_widen=float(ms[4]))
+
     def debug_compose(self, q, a0, r, seed, stream, epoch):
         """The int16 rows the composing launch writes (fb_debug_compose) for the hand-made NES rows q (B, N) and the cast
         original a0 (N,), r draws per utterance at (seed, stream, epoch): an array (B, K, r, N), K - 1 the companions set."""
@@ -1017,16 +1054,29 @@ class Engine(object):
     def attack_pso(self, params, pso, audio):
         """fb_attack_pso: the particle-swarm attack on this engine's system -> (int16 adv, flag, float64 adv, trace
         (n_iters, 3 + S): gbest loss, gbest particle, particles improved, gbest scores; losses (n_iters, P))."""
+        return self._attack_pso(params, pso, audio, None)
+
+    def attack_pso_foreign(self, params, pso, victim, audio):
+        """fb_attack_pso_foreign: the same swarm, scored by a foreign model.  victim: a dict of mode ("host_scores" /
+        "device_scores"), S, fn -- fn((N, B) float64) -> (B, S) scores, or fn(x [B, N] tensor) -> [B, S] on the GPU -- and,
+        device mode, the torch tensors x [P, N] and scores [P, S] on this engine's device.  Returns what attack_pso does."""
+        return self._attack_pso(params, pso, audio, victim)
+
+    def _attack_pso(self, params, pso, audio, victim):
         audio = np.ascontiguousarray(audio, np.float64).reshape(-1)
-        n, S, P = audio.size, self.n_speakers, max(int(pso.particles), 1)
+        n, P = audio.size, max(int(pso.particles), 1)
+        S = self.n_speakers if victim is None else max(int(victim["S"]), 1)
         adv = np.empty(n, np.int16)
         adv_f = np.empty(n, np.float64)
         rows = max(params.max_iter, 1)
         trace = np.zeros((rows, 3 + S), np.float64)
         losses = np.zeros((rows, P), np.float64)
         flag, ni = C.c_int(), C.c_int()
-        N.check(self._L.fb_attack_pso(self._h, C.byref(params), C.byref(pso), N.ptr(audio), C.c_int64(n), N.ptr(adv),
-                                      N.ptr(adv_f), C.byref(flag), C.byref(ni), N.ptr(trace), N.ptr(losses)))
+        tail = (N.ptr(audio), C.c_int64(n), N.ptr(adv), N.ptr(adv_f), C.byref(flag), C.byref(ni), N.ptr(trace), N.ptr(losses))
+        if victim is None:
+            N.check(self._L.fb_attack_pso(self._h, C.byref(params), C.byref(pso), *tail))
+        else:
+            self._foreign_call(self._L.fb_attack_pso_foreign, victim, P, n, (C.byref(params), C.byref(pso)), tail)
         return adv, flag.value, adv_f, trace[:ni.value], losses[:ni.value]
 
     def debug_pso_init(self, audio, epsilon, particles, v_max, seed, stream, bits_per_sample=16):
@@ -1068,9 +1118,19 @@ class Engine(object):
         factor (-1: none), n_queries, and per round qs (n_rounds, G) (-1 in unused places), decisions (n_rounds, G) (-2: no
         voiced frames; unused places -3), scores (n_rounds, G, S) (unused places NaN), trace (n_rounds, 3) = lo, hi, rows.
         tables=None: fakebob_amd.kenansville.tables(kv.window)."""
+        return self._attack_kenansville(params, kv, audio, tables, None)
+
+    def attack_kenansville_foreign(self, params, kv, victim, audio, tables=None):
+        """fb_attack_kenansville_foreign: the same search, the candidates decided by a foreign model.  victim: as for
+        attack_pso_foreign, with mode "host_decisions" as well -- fn((N, B) float64) -> (decisions (B,), scores (B, S) or
+        None); -2 is "no decision" -- and x [grid, N], scores [grid, S] in device mode.  Returns what attack_kenansville
+        does; scores are the model's (NaN where a decision model gave none)."""
+        return self._attack_kenansville(params, kv, audio, tables, victim)
+
+    def _attack_kenansville(self, params, kv, audio, tables, victim):
         from . import kenansville as KV
         audio = np.ascontiguousarray(audio, np.float64).reshape(-1)
-        n, S = audio.size, max(self.n_speakers, 1)
+        n, S = audio.size, max(self.n_speakers if victim is None else int(victim["S"]), 1)
         G, R = min(max(int(kv.grid), 1), 64), min(max(int(kv.max_rounds), 1), 32)
         tab = self._kv_tables(KV, kv.window, tables)
         adv = np.empty(n, np.int16)
@@ -1079,9 +1139,12 @@ class Engine(object):
         sc = np.full((R, G, S), np.nan, np.float64)
         trace = np.zeros((R, 3), np.int32)
         flag, factor, nq, nr = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-        N.check(self._L.fb_attack_kenansville(self._h, C.byref(params), C.byref(kv), N.ptr(tab), N.ptr(audio), C.c_int64(n),
-                                              N.ptr(adv), C.byref(flag), C.byref(factor), C.byref(nq), C.byref(nr), N.ptr(qs),
-                                              N.ptr(dec), N.ptr(sc), N.ptr(trace)))
+        tail = (N.ptr(tab), N.ptr(audio), C.c_int64(n), N.ptr(adv), C.byref(flag), C.byref(factor), C.byref(nq), C.byref(nr),
+                N.ptr(qs), N.ptr(dec), N.ptr(sc), N.ptr(trace))
+        if victim is None:
+            N.check(self._L.fb_attack_kenansville(self._h, C.byref(params), C.byref(kv), *tail))
+        else:
+            self._foreign_call(self._L.fb_attack_kenansville_foreign, victim, G, n, (C.byref(params), C.byref(kv)), tail)
         r = nr.value
         return dict(adv=adv, success=flag.value, factor=factor.value, n_queries=nq.value, qs=qs[:r], decisions=dec[:r],
                     scores=sc[:r], trace=trace[:r])
@@ -1138,6 +1201,15 @@ class Engine(object):
         (n_iters + 1, 8) = D2, B, n+, m, hi, rounds, queries so far, sigma (row 0: the start search), decisions (n_queries,)
         in scoring order (-2: no voiced frames) and, keep_x=True, xs (n_iters + 1, N): x after the start and every iteration.
         log_capacity=None: the decision log holds fb_hsj_max_rows entries."""
+        return self._attack_hsj(params, hsj, audio, init, keep_x, log_capacity, None)
+
+    def attack_hsj_foreign(self, params, hsj, victim, audio, init, keep_x=False, log_capacity=None):
+        """fb_attack_hsj_foreign: the same walk, every row decided by a foreign model.  victim: as for
+        attack_kenansville_foreign, with x [max(grid, num_evals_max), N] and scores [.., S] in device mode.  Returns what
+        attack_hsj does (-2 in decisions: the model gave no decision)."""
+        return self._attack_hsj(params, hsj, audio, init, keep_x, log_capacity, victim)
+
+    def _attack_hsj(self, params, hsj, audio, init, keep_x, log_capacity, victim):
         audio = np.ascontiguousarray(audio, np.float64).reshape(-1)
         n = audio.size
         if init is not None:
@@ -1151,12 +1223,16 @@ class Engine(object):
         trace = np.zeros((T + 1, 8), np.float64)
         xs = np.zeros((T + 1, n), np.float64) if keep_x else None
         flag, ni, nq, d2 = C.c_int(), C.c_int(), C.c_int(), C.c_double()
-        N.check(self._L.fb_attack_hsj(self._h, C.byref(params), C.byref(hsj), N.ptr(audio), N.ptr(init) if init is not None else None,
-                                      C.c_int64(n), N.ptr(adv), N.ptr(adv_f), C.byref(flag), C.byref(d2), C.byref(ni),
-                                      C.byref(nq), N.ptr(trace), N.ptr(dec), C.c_longlong(dec.size if cap >= 0 else -1),
-                                      N.ptr(xs) if keep_x else None))
+        tail = (N.ptr(audio), N.ptr(init) if init is not None else None, C.c_int64(n), N.ptr(adv), N.ptr(adv_f), C.byref(flag),
+                C.byref(d2), C.byref(ni), C.byref(nq), N.ptr(trace), N.ptr(dec), C.c_longlong(dec.size if cap >= 0 else -1),
+                N.ptr(xs) if keep_x else None)
+        if victim is None:
+            N.check(self._L.fb_attack_hsj(self._h, C.byref(params), C.byref(hsj), *tail))
+        else:
+            rows_max = max(int(hsj.grid), int(hsj.num_evals_max), 1)
+            self._foreign_call(self._L.fb_attack_hsj_foreign, victim, rows_max, n, (C.byref(params), C.byref(hsj)), tail)
         # (one log entry per candidate row; n_queries counts victim queries: under voted decisions r' = K * eot per row)
-        n_log = nq.value // self.query_replicas
+        n_log = nq.value // (self.query_replicas if victim is None else 1)
         res = dict(adv=adv, adv_f64=adv_f, success=flag.value, dist2=d2.value, n_iters=ni.value, n_queries=nq.value,
                    trace=trace[:ni.value + 1], decisions=dec[:n_log])
         if keep_x:
@@ -1250,6 +1326,50 @@ class Engine(object):
             raise err[0]
         raise ex
 
+    @staticmethod
+    def _decide_cb(decide_fn, S, err):
+        """decide_fn(audios (N, B) float64) -> (decisions (B,), scores (B, S) or None), wrapped as an fb_decide_cb.  The model
+        gets its OWN C-contiguous (N, B) array, as _score_cb hands it one; scores it does not give stay NaN."""
+        def _cb(_ctx, aud, n, b, dec, out):
+            try:
+                a = np.array(np.ctypeslib.as_array(aud, shape=(b, n)).T, order="C")
+                d, sc = decide_fn(a)
+                np.ctypeslib.as_array(dec, shape=(b,))[...] = np.asarray(d).reshape(b)
+                if sc is not None:
+                    np.ctypeslib.as_array(out, shape=(b, S))[...] = np.asarray(sc, np.float64).reshape(b, S)
+                return 0
+            except BaseException as ex:  # noqa: BLE001
+                err[0] = ex
+                return 1
+        return N.DECIDE_CB(_cb)
+
+    _VICTIM_MODES = {"host_scores": N.FB_VICTIM_HOST_SCORES, "host_decisions": N.FB_VICTIM_HOST_DECISIONS,
+                     "device_scores": N.FB_VICTIM_DEVICE_SCORES}
+
+    def _foreign_call(self, fn, victim, rows_max, n, head, tail):
+        """fn(engine, *head, fb_victim, *tail) for the victim dict of attack_*_foreign; a mode the library does not know
+        (an int) is handed through for it to refuse.  An exception raised by the model is re-raised here.  check_extent=False
+        in a device victim leaves the size of x and scores to the library's own check of the allocations."""
+        mode = victim["mode"]
+        S, err = int(victim["S"]), [None]
+        v = N.Victim()
+        v.mode, v.S = self._VICTIM_MODES.get(mode, mode if isinstance(mode, int) else 0), S
+        keep = []
+        if mode == "host_scores" and victim.get("fn") is not None:
+            v.score = self._score_cb(victim["fn"], S, err)
+        elif mode == "host_decisions" and victim.get("fn") is not None:
+            v.decide = self._decide_cb(victim["fn"], S, err)
+        elif mode == "device_scores" and victim.get("fn") is not None:
+            x, scores = victim["x"], victim["scores"]
+            m = self._dev_buffers(rows_max, S, n, x, scores, 0, exact=victim.get("check_extent", True))
+            keep.append(m)
+            v.dev = C.pointer(m)
+            v.score_dev = self._score_dev_cb(victim["fn"], x, scores, S, err)
+        try:
+            N.check(fn(self._h, *(tuple(head) + (C.byref(v),) + tuple(tail))))
+        except N.NativeError as ex:
+            self._raise_cb(err, ex)
+
     def _host_model(self, S, score_fn):
         def model(_n):
             err = [None]
@@ -1267,8 +1387,11 @@ class Engine(object):
     # ---- NES with a foreign model on the same GPU: the batch and the scores stay in device memory
     def _dev_model(self, params, S, n, x, scores, look_every):
         """fb_dev_model over the torch tensors x [B, N] and scores [B, S] (float32 / float64, on this engine's device)."""
+        return self._dev_buffers(2 * (params.samples_per_draw // 2) + 1, S, n, x, scores, look_every)
+
+    def _dev_buffers(self, B, S, n, x, scores, look_every, exact=True):
+        """... for batches of up to B rows (exact=False: the element counts are left to the library's own extent check)"""
         torch = N.torch_first()
-        B = 2 * (params.samples_per_draw // 2) + 1
         dts = {torch.float32: N.FB_DT_F32, torch.float64: N.FB_DT_F64}
         for name, t, want in (("x", x, B * n), ("scores", scores, B * S)):
             if not isinstance(t, torch.Tensor):
@@ -1277,7 +1400,7 @@ class Engine(object):
                 raise ValueError("%s is on %s: the device path needs a tensor on cuda:%d" % (name, t.device, self.device))
             if t.dtype not in dts:
                 raise ValueError("%s has dtype %s: float32 or float64" % (name, t.dtype))
-            if not t.is_contiguous() or t.numel() != want:
+            if not t.is_contiguous() or (exact and t.numel() != want):
                 raise ValueError("%s must be contiguous with %d elements (got %s)" % (name, want, tuple(t.shape)))
         m = N.DevModel()
         m.x_dtype, m.x = dts[x.dtype], x.data_ptr()
@@ -1298,10 +1421,11 @@ class Engine(object):
                 if not ext:
                     ext.append(torch.cuda.ExternalStream(stream, device=torch.device("cuda", self.device)))
                 with torch.cuda.stream(ext[0]):
-                    out = score_fn(x.view(b, n))
+                    # (the first b rows: a batch of the swarm and decision attacks may be smaller than the buffers)
+                    out = score_fn(x.view(-1)[:b * n].view(b, n))
                     if not isinstance(out, torch.Tensor):
                         out = torch.as_tensor(out, device=scores.device)
-                    scores.view(b, s).copy_(out.reshape(b, s))
+                    scores.view(-1)[:b * s].view(b, s).copy_(out.reshape(b, s))
                 return 0
             except BaseException as ex:  # noqa: BLE001
                 err[0] = ex

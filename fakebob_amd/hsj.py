@@ -10,7 +10,9 @@ is FakeBob's: the same `attack` arguments and return pair, plus `init`.
 
 Randomised victims and several utterances: with `quorum=` set, `eot_size=` and `attack(..., companions=[...])` score every row
 r' = K * eot_size times and a row counts as adversarial from `quorum` adversarial replicas on -- its votes
-(fakebob_amd.query_eot; "voted decisions" in the header).  Not in this version: foreign models.
+(fakebob_amd.query_eot; "voted decisions" in the header).  A foreign model -- any object with `make_decisions`, `score`, or
+`score_device` for a model on the same GPU -- is attacked by the same walk once the constructor is told `foreign=True` (fb_attack_hsj_foreign; fakebob_amd.foreign): it
+decides every row, the engine does the rest; eot_size, quorum, companions and play_offset are refused for it by name.
 """
 import math
 import pickle
@@ -21,6 +23,7 @@ import numpy as np
 from .attack import _check_bits, _col
 from .companions import cast_i16
 from . import query_eot as QE
+from . import foreign as FG
 from .engine import hsj_params, nes_params
 
 MAX_GRID, MAX_ROUNDS, MAX_EVALS = 64, 32, 1024
@@ -40,16 +43,23 @@ def fit_init(init, n):
 class HopSkipJump(object):
 
     def __init__(self, task, attack_type, model, grid=15, max_rounds=8, num_evals_init=32, num_evals_max=256, max_queries=0,
-                 sigma_min=2.0 ** -15, probe_scale=0.05, max_iter=20, seed=None, verbose=True, eot_size=None, quorum=None):
+                 sigma_min=2.0 ** -15, probe_scale=0.05, max_iter=20, seed=None, verbose=True, eot_size=None, quorum=None,
+                 play_offset=None, foreign=False):
         """eot_size: every scored row under that many draws of a randomised victim; quorum ("majority" or 1 .. 32; None:
         off) is the number of adversarial draws a row needs -- its votes -- to count as adversarial."""
+        if FG.is_foreign(model):    # (before the options' own rules: a foreign model takes none of them)
+            FG.require_opt_in("HopSkipJump", foreign)
+            FG.refuse_options("HopSkipJump", eot_size, quorum, None, play_offset)
         self.eot_size, self.quorum = QE.check_options("HopSkipJump", eot_size, quorum)
         if task not in ("OSI", "CSI", "SV"):
             raise ValueError("task must be OSI, CSI or SV")
         if attack_type not in ("targeted", "untargeted"):
             raise ValueError("attack_type must be targeted or untargeted")
-        if not hasattr(model, "engine"):
-            raise ValueError("HopSkipJump attacks the engine's own systems (fakebob_amd.systems), not a foreign model")
+        self._victim = None
+        if FG.is_foreign(model):    # the reference's plugin API: the model decides every row
+            self._victim = FG.Victim("HopSkipJump", task, model, decisions=True)
+        elif play_offset:
+            raise ValueError("HopSkipJump does not run under a play offset: not in this version")
         if getattr(model, "task", task) != task:
             raise ValueError("model implements task %s, attack asked for %s" % (model.task, task))
         grid, max_rounds, max_iter, max_queries = int(grid), int(max_rounds), int(max_iter), int(max_queries)
@@ -104,12 +114,15 @@ class HopSkipJump(object):
         d = int(d)
         return d == target if self.attack_type == "targeted" else (d != true and d != -2)
 
-    def _noise_start(self, n, true, target):
+    def _noise_start(self, n, true, target, threshold=0., **score_kw):
         """the first of up to NOISE_STARTS rows of uniform noise in [-1, 1) that the system decides as wanted, or None"""
         rs = np.random.RandomState(self.seed & 0xFFFFFFFF)
         for _ in range(NOISE_STARTS):
             row = rs.uniform(-1.0, 1.0, n)
-            d = self.model.make_decisions(row[:, np.newaxis])[0]        # (decisions, scores), as the system classes return
+            if self._victim is not None:   # a foreign model: its make_decisions, or the score rule on score / score_device
+                d = self._victim.decide_one(row, threshold, **score_kw)
+            else:
+                d = self.model.make_decisions(row[:, np.newaxis])[0]    # (decisions, scores), as the system classes return
             if self._wanted(np.asarray(d).reshape(-1)[0], true, target):
                 return row
         return None
@@ -147,7 +160,12 @@ class HopSkipJump(object):
         self.dist = self.snr_db = self.linf_lsb = None
         self.n_queries = 0
         x0 = cast_i16(audio[:, 0], bits)
-        start = fit_init(init, n) if init is not None else self._noise_start(n, true, target)
+        if self._victim is not None:
+            FG.refuse_options("HopSkipJump", companions=companions)
+            start = fit_init(init, n) if init is not None else self._noise_start(
+                n, true, target, threshold, fs=fs, bits_per_sample=bits_per_sample, n_jobs=n_jobs, debug=debug)
+        else:
+            start = fit_init(init, n) if init is not None else self._noise_start(n, true, target)
         if start is None:
             if self.verbose:
                 print("--- no noise start is decided as wanted ---")
@@ -157,11 +175,18 @@ class HopSkipJump(object):
         k = hsj_params(self.grid, self.max_rounds, self.num_evals_init, self.num_evals_max, self.max_queries, self.sigma_min,
                        self.probe_scale)
         self._stream += 1
-        eng = self.model.engine
-        t0 = time.time()
-        with QE.Settings("HopSkipJump", eng, self.eot_size, self.quorum, companions, n, bits) as st:
-            res = eng.attack_hsj(p, k, audio[:, 0], start)
-        rp = st.replicas if st.quorum is not None else 1
+        if self._victim is not None:
+            eng = self._victim.engine()
+            spec = self._victim.spec(max(self.grid, self.num_evals_max), n, audio, fs, bits_per_sample, n_jobs, debug)
+            t0 = time.time()
+            res = eng.attack_hsj_foreign(p, k, spec, audio[:, 0], start)
+            st, rp = QE.Settings("HopSkipJump", eng, None, None, None, n, bits), 1
+        else:
+            eng = self.model.engine
+            t0 = time.time()
+            with QE.Settings("HopSkipJump", eng, self.eot_size, self.quorum, companions, n, bits) as st:
+                res = eng.attack_hsj(p, k, audio[:, 0], start)
+            rp = st.replicas if st.quorum is not None else 1
         dt = time.time() - t0
         rows = res["trace"].shape[0]
         used_time = eng.attack_iter_seconds(rows)

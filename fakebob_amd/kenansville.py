@@ -12,7 +12,10 @@ codec.py is for the codecs.  The surface is FakeBob's: the same `attack` argumen
 
 Randomised victims and several utterances: with `quorum=` set, `eot_size=` and `attack(..., companions=[...])` score every row
 r' = K * eot_size times and a row counts as adversarial from `quorum` adversarial replicas on -- its votes
-(fakebob_amd.query_eot; "voted decisions" in the header).  Not in this version: foreign models.
+(fakebob_amd.query_eot; "voted decisions" in the header).  A foreign model -- any object with `make_decisions`, `score`, or
+`score_device` for a model on the same GPU -- is attacked by the same search once the constructor is told `foreign=True` (fb_attack_kenansville_foreign;
+fakebob_amd.foreign): it decides the candidates, the engine does the rest; eot_size, quorum, companions and play_offset are
+refused for it by name.
 """
 import math
 import pickle
@@ -23,6 +26,7 @@ import numpy as np
 from .attack import _check_bits, _col
 from .engine import kv_params, nes_params
 from . import query_eot as QE
+from . import foreign as FG
 
 MIN_WINDOW, MAX_WINDOW = 8, 128
 MAX_GRID, MAX_ROUNDS, Q_ONE = 64, 32, 65536
@@ -104,16 +108,22 @@ def q_of(max_factor):
 class Kenansville(object):
 
     def __init__(self, task, attack_type, model, window=100, grid=15, max_factor=1.0, max_rounds=32, seed=None, verbose=True,
-                 eot_size=None, quorum=None):
+                 eot_size=None, quorum=None, play_offset=None, foreign=False):
         """eot_size: every candidate scored under that many draws of a randomised victim; quorum ("majority" or 1 .. 32;
         None: off) is the number of adversarial draws a candidate needs -- its votes -- to count as succeeding."""
+        if FG.is_foreign(model):    # (before the options' own rules: a foreign model takes none of them)
+            FG.require_opt_in("Kenansville", foreign)
+            FG.refuse_options("Kenansville", eot_size, quorum, None, play_offset)
         self.eot_size, self.quorum = QE.check_options("Kenansville", eot_size, quorum)
         if task not in ("OSI", "CSI", "SV"):
             raise ValueError("task must be OSI, CSI or SV")
         if attack_type not in ("targeted", "untargeted"):
             raise ValueError("attack_type must be targeted or untargeted")
-        if not hasattr(model, "engine"):
-            raise ValueError("Kenansville attacks the engine's own systems (fakebob_amd.systems), not a foreign model")
+        self._victim = None
+        if FG.is_foreign(model):    # the reference's plugin API: the model decides the candidates
+            self._victim = FG.Victim("Kenansville", task, model, decisions=True)
+        elif play_offset:
+            raise ValueError("Kenansville does not run under a play offset: not in this version")
         if getattr(model, "task", task) != task:
             raise ValueError("model implements task %s, attack asked for %s" % (model.task, task))
         self.window = _check_window(window)
@@ -178,11 +188,19 @@ class Kenansville(object):
                        stream=self._stream, bits_per_sample=bits)
         k = kv_params(self.window, self.grid, self.q_max, self.max_rounds)
         self._stream += 1
-        eng = self.model.engine
-        t0 = time.time()
-        with QE.Settings("Kenansville", eng, self.eot_size, self.quorum, companions, audio.shape[0], bits) as st:
-            res = eng.attack_kenansville(p, k, audio[:, 0])
-        rp = st.replicas if st.quorum is not None else 1
+        if self._victim is not None:
+            FG.refuse_options("Kenansville", companions=companions)
+            eng = self._victim.engine()
+            spec = self._victim.spec(self.grid, audio.shape[0], audio, fs, bits_per_sample, n_jobs, debug)
+            t0 = time.time()
+            res = eng.attack_kenansville_foreign(p, k, spec, audio[:, 0])
+            st, rp = QE.Settings("Kenansville", eng, None, None, None, audio.shape[0], bits), 1
+        else:
+            eng = self.model.engine
+            t0 = time.time()
+            with QE.Settings("Kenansville", eng, self.eot_size, self.quorum, companions, audio.shape[0], bits) as st:
+                res = eng.attack_kenansville(p, k, audio[:, 0])
+            rp = st.replicas if st.quorum is not None else 1
         dt = time.time() - t0
         n = res["trace"].shape[0]
         used_time = eng.attack_iter_seconds(n)

@@ -8,7 +8,9 @@ the same Philox stream handling (`seed`, one stream per attack() call), so a dri
 
 Randomised victims and several utterances: `eot_size=` and `attack(..., companions=[...])` score every particle r' = K *
 eot_size times and the swarm reads the mean loss, once `quorum=` switches that on (fakebob_amd.query_eot; "voted decisions"
-in the header).  Not in this version: foreign models, swarm restarts.
+in the header).  A foreign model -- any object with `score`, or `score_device` for a model on the same GPU -- is attacked by
+the same swarm once the constructor is told `foreign=True` (fb_attack_pso_foreign; fakebob_amd.foreign): it scores the particles, the engine does the rest; eot_size,
+quorum, companions and play_offset are refused for it by name.  Not in this version: swarm restarts.
 """
 import math
 import pickle
@@ -19,6 +21,7 @@ import numpy as np
 from .attack import FakeBob, _check_bits, _col
 from .engine import nes_params, pso_params
 from . import query_eot as QE
+from . import foreign as FG
 
 MAX_PARTICLES = 64
 
@@ -26,17 +29,24 @@ MAX_PARTICLES = 64
 class ParticleSwarm(object):
 
     def __init__(self, task, attack_type, model, adver_thresh=0., epsilon=0.002, max_iter=300, n_particles=25,
-                 w_init=0.9, w_end=0.1, c1=1.4961, c2=1.4961, v_max=None, seed=None, verbose=True, eot_size=None, quorum=None):
+                 w_init=0.9, w_end=0.1, c1=1.4961, c2=1.4961, v_max=None, seed=None, verbose=True, eot_size=None, quorum=None,
+                 play_offset=None, foreign=False):
         """v_max=None: epsilon (a particle crosses the ball's radius in one step at most).  eot_size: every particle scored
         under that many draws of a randomised victim, the swarm reading the mean loss; it needs quorum= ("majority" or 1 ..
         32; None: off), the switch the three query attacks share -- PSO itself reads no votes."""
+        if FG.is_foreign(model):    # (before the options' own rules: a foreign model takes none of them)
+            FG.require_opt_in("ParticleSwarm", foreign)
+            FG.refuse_options("ParticleSwarm", eot_size, quorum, None, play_offset)
         self.eot_size, self.quorum = QE.check_options("ParticleSwarm", eot_size, quorum)
         if task not in ("OSI", "CSI", "SV"):
             raise ValueError("task must be OSI, CSI or SV")
         if attack_type not in ("targeted", "untargeted"):
             raise ValueError("attack_type must be targeted or untargeted")
-        if not hasattr(model, "engine"):
-            raise ValueError("ParticleSwarm attacks the engine's own systems (fakebob_amd.systems), not a foreign model")
+        self._victim = None
+        if FG.is_foreign(model):    # the reference's plugin API: the model scores the swarm
+            self._victim = FG.Victim("ParticleSwarm", task, model, decisions=False)
+        elif play_offset:
+            raise ValueError("ParticleSwarm does not run under a play offset: not in this version")
         if getattr(model, "task", task) != task:
             raise ValueError("model implements task %s, attack asked for %s" % (model.task, task))
         n_particles, max_iter = int(n_particles), int(max_iter)
@@ -100,11 +110,29 @@ class ParticleSwarm(object):
                        stream=self._stream, bits_per_sample=bits)
         q = pso_params(self.n_particles, self.w_init, self.w_end, self.c1, self.c2, self.v_max)
         self._stream += 1
+        if self._victim is not None:
+            FG.refuse_options("ParticleSwarm", companions=companions)
+            return self._attack_foreign(p, q, audio, checkpoint_path, bits, fs, bits_per_sample, n_jobs, debug)
         eng = self.model.engine
         t0 = time.time()
         with QE.Settings("ParticleSwarm", eng, self.eot_size, self.quorum, companions, audio.shape[0], bits) as st:
             adv, flag, _advf, trace, _losses = eng.attack_pso(p, q, audio[:, 0])
         dt = time.time() - t0
+        return self._finish(eng, adv, flag, trace, dt, audio, checkpoint_path, bits, st.comp, target, true, fs, bits_per_sample,
+                            n_jobs, debug)
+
+    def _attack_foreign(self, p, q, audio, checkpoint_path, bits, fs, bits_per_sample, n_jobs, debug):
+        vic = self._victim
+        eng = vic.engine()
+        spec = vic.spec(self.n_particles, audio.shape[0], audio, fs, bits_per_sample, n_jobs, debug)
+        t0 = time.time()
+        adv, flag, _advf, trace, _losses = eng.attack_pso_foreign(p, q, spec, audio[:, 0])
+        dt = time.time() - t0
+        return self._finish(eng, adv, flag, trace, dt, audio, checkpoint_path, bits, None, self.target, self.true, fs,
+                            bits_per_sample, n_jobs, debug)
+
+    def _finish(self, eng, adv, flag, trace, dt, audio, checkpoint_path, bits, comp, target, true, fs, bits_per_sample, n_jobs,
+                debug):
         n = trace.shape[0]
         used_time = eng.attack_iter_seconds(n)
         cp = []
@@ -116,5 +144,5 @@ class ParticleSwarm(object):
                 pickle.dump(cp, writer, protocol=-1)
         if self.verbose:
             print("--- %d iters, %d particles, gbest loss:%f, %.1f iters/s ---" % (n, self.n_particles, trace[-1, 0], n / dt if dt > 0 else 0.0))
-        return QE.result(self.model, self.task, self.attack_type, adv, flag, audio[:, 0], bits, st.comp, None, target=target,
+        return QE.result(self.model, self.task, self.attack_type, adv, flag, audio[:, 0], bits, comp, None, target=target,
                          true=true, fs=fs, bits_per_sample=bits_per_sample, n_jobs=n_jobs, debug=debug)

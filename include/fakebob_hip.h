@@ -449,8 +449,8 @@ int fb_set_feature_compression(fb_engine *e, double ratio, int iters);
  * Refusals.  FB_E_ARG: particles outside 2 .. 64; w_init, w_end, c1 or c2 not finite or < 0; v_max not finite or <= 0;
  * max_iter < 1; epsilon not finite or <= 0; the task, target, true-label and bits_per_sample rules of fb_attack.  FB_E_STATE:
  * no system loaded, or fb_set_eot(r > 1) or companions (fb_set_companions) in force while fb_set_query_eot is off (the
- * default; the "voted decisions" section below says what they mean with it on): set 1 / clear them.  FB_E_NO_VOICED: some particle of some iteration has no voiced frames.  The engine's own systems only (GMM and
- * i-vector): there are no _ext / _dev twins.  The input-transform chain, dither and feature compression act as in fb_attack,
+ * default; the "voted decisions" section below says what they mean with it on): set 1 / clear them.  FB_E_NO_VOICED: some particle of some iteration has no voiced frames.  The engine's own systems (GMM and
+ * i-vector); fb_attack_pso_foreign (the "foreign victims" section) runs the same swarm on a foreign model.  The input-transform chain, dither and feature compression act as in fb_attack,
  * keyed by the call's (seed, stream) with epoch = the PSO iteration k and utterance row = the particle index.
  * Arithmetic.  Everything below is float64, round to nearest, one rounding per written operation, no fused multiply-add;
  * clip(s, l, h) = min(max(s, l), h); a = `audio` as given, i the sample index, p the particle.
@@ -544,7 +544,8 @@ int fb_attack_pso(fb_engine *e, const fb_nes_params *p, const fb_pso_params *q, 
  * Refusals.  FB_E_ARG: anything outside the ranges above, a task other than the engine's, a label that is no decision of
  * the system, wrong tables, bits_per_sample outside 2 .. 16, audio shorter than one frame.  FB_E_STATE: no system loaded, or
  * fb_set_eot(r > 1) or companions in force while fb_set_query_eot is off (the default; "voted decisions" below): set 1 /
- * clear them.  The engine's own systems only: there are no _ext / _dev twins.
+ * clear them.  The engine's own systems; the _foreign twin (the "foreign victims"
+ * section) runs the same search on a foreign model.
  * Deviations from Kenansville / SpeakerGuard's version: theirs transforms with a floating-point FFT (or SSA) and bisects one
  * candidate per query; here the arithmetic is the integer contract above and a round scores G candidates. */
 typedef struct { int window; int grid; int q_max; int max_rounds; } fb_kv_params;
@@ -615,7 +616,8 @@ int fb_attack_kenansville(fb_engine *e, const fb_nes_params *p, const fb_kv_para
  * Refusals.  FB_E_ARG: anything outside those ranges, max_iter < 0, a null `init`, bits_per_sample outside 2 .. 16, audio
  * shorter than one frame, a task other than the engine's, a label that is no decision of the system, a decision log that is
  * too small.  FB_E_STATE: no system loaded, or fb_set_eot(r > 1) or companions in force while fb_set_query_eot is off (the
- * default; "voted decisions" below): set 1 / clear them.  The engine's own systems only: there are no _ext / _dev twins.
+ * default; "voted decisions" below): set 1 / clear them.  The engine's own systems; the _foreign twin (the "foreign victims"
+ * section) runs the same search on a foreign model.
  * Deviations from the paper: the L2 variant only; grid rounds of G rows instead of one-query bisection and one-query step
  * halving; Gaussian probes that are not normalised to the sphere; a probe radius with a floor of sigma_min, because the
  * paper's delta = dist / d lies far below one int16 step for audio and the cast would erase it; keyed draws; a stall instead
@@ -1141,6 +1143,79 @@ int fb_get_grad_dev(fb_engine *e, const fb_nes_params *p, int S, const fb_dev_mo
 int fb_attack_dev(fb_engine *e, const fb_nes_params *p, int S, const fb_dev_model *m, fb_score_dev_cb cb, void *ctx,
                   const double *audio, int64_t N, const double *noise_all, int16_t *adv_i16,
                   double *adver_f64, double *trace, int *n_trace, int *success_flag);
+
+/* ---- foreign victims for the swarm and the decision-only attacks ----------------------------------------------------------
+ * fb_attack_pso, fb_attack_kenansville and fb_attack_hsj against a model that is not one of this library's systems: the
+ * victim a decision-only attack exists for -- a commercial API behind a host callback, a neural recogniser in PyTorch on
+ * the same GPU.  Each call takes the arguments of its native call plus one descriptor, fb_victim, between the attack's
+ * parameters and the native call's tail.
+ * The search is the native one.  The candidates, particles, line rows, probes and step sizes, the bracket, the direction,
+ *   ssq, the stops, the traces and the logs are those of the three sections "particle-swarm attack", "decision-only attack"
+ *   and "decision-only attack II", made by the same launches: the int16 batch a _foreign call produces for a given history
+ *   of decisions (losses, for PSO) equals, bit for bit, the batch the native call produces for that history.  Only who
+ *   scores the batch differs.
+ * What the victim sees.  Row b of a batch is x[b][i] = (double)q[b][i] * 2^-(bits_per_sample - 1), q the int16 row: exact,
+ *   and the audio an attacker would submit as a wav file (k_rows_to_model, the one added pass over the batch).
+ *   - FB_VICTIM_HOST_SCORES, FB_VICTIM_HOST_DECISIONS: the callback gets the rows as float64 [B][N], utterance-major, in the
+ *     engine's staging memory; lifetime as for fb_score_cb (valid only DURING the call).
+ *   - FB_VICTIM_DEVICE_SCORES: the rows go into dev->x as dev->x_dtype; the float32 value is exact too.  score_dev then
+ *     enqueues the model on the engine's stream as for fb_attack_dev and writes dev->scores [B][S] as dev->score_dtype.
+ *     dev->x must hold rows_max * N elements and dev->scores rows_max * S: rows_max = particles (PSO), grid (Kenansville),
+ *     max(grid, num_evals_max) (HopSkipJump).  The device, dtype and extent checks are fb_attack_dev's (FB_E_ARG).
+ *     dev->look_every is not read: these attacks look once per batch.
+ *   - The callback runs exactly once per scored batch, with that batch's row count as B.
+ * Decisions (fb_attack_kenansville_foreign, fb_attack_hsj_foreign).
+ *   - FB_VICTIM_HOST_DECISIONS: decisions[B] are the callback's values, checked: a decision value of the task (SV +-1, OSI
+ *     -1 .. S - 1, CSI 0 .. S - 1) or -2 = no decision (never adversarial, never a success, never an error, as a row without
+ *     voiced frames in the native calls).  Anything else is FB_E_CALLBACK, the value named in fb_last_error.  scores[B * S]
+ *     is prefilled with NaN by the engine; the model MAY write its scores there.
+ *   - FB_VICTIM_HOST_SCORES, FB_VICTIM_DEVICE_SCORES: the model's scores are the system scores as they stand -- no UBM
+ *     subtraction and no z-norm: the model's output is final, as for fb_attack_ext -- and the decision is the rule of the
+ *     "decision-only attack" section: SV  s >= threshold ? 1 : -1;  OSI, CSI  the first maximum by strict > in ascending m, so
+ *     that a NaN never displaces the running maximum (a NaN in column 0 stays it);  OSI  a maximum < threshold gives -1.
+ *     float32 scores are widened exactly before any comparison.  -2 never arises.  One launch (k_decide_foreign) writes the
+ *     look block {decisions [rows] int32, padding to 8 bytes, scores [rows][S] float64}, which the host copies once per batch.
+ *   - fb_attack_kenansville_foreign's scores[r][G][S] log holds the model's scores, or NaN where a decision callback wrote
+ *     none.
+ * fb_attack_pso_foreign takes the two score modes; FB_VICTIM_HOST_DECISIONS is FB_E_ARG.  loss_fn is formed on the device
+ *   from the model's scores exactly as fb_attack_ext / fb_attack_dev form it.  There is no FB_E_NO_VOICED.
+ * No system need be loaded.  The engine's defences -- the input-transform chain, the codec, the air channel, feature
+ *   compression and dither -- are NOT applied to a foreign batch, as documented for fb_attack_ext.
+ * FB_E_STATE before anything runs, the setting named in the message, while fb_set_eot(r > 1), companions
+ *   (fb_set_companions), a play offset (fb_set_play_offset) or fb_set_query_eot is in force: a foreign victim's randomness is
+ *   its own.
+ * FB_E_ARG: a null descriptor; an unknown mode; the callback of the mode missing (score for HOST_SCORES, decide for
+ *   HOST_DECISIONS, dev and score_dev for DEVICE_SCORES); S outside 1 .. 62; FB_TASK_SV with S != 1; the native calls' own
+ *   parameter and label rules (labels against the descriptor's S).  N >= 1 suffices: there is no front end, hence no
+ *   "shorter than one frame" rule.
+ * A non-zero callback return is FB_E_CALLBACK.  The engine stays usable after every refusal and every callback failure.
+ * *n_queries, max_queries and the traces' query columns count rows handed to the model.  fb_attack_iter_seconds behaves as
+ *   in the native calls; fb_stats does not count foreign rows.  fb_debug_foreign_path (fakebob_hip_test.h) reports host or
+ *   device and the dtypes for these calls too. */
+typedef int (*fb_decide_cb)(void *ctx, const double *audios /*[B][N]*/, int64_t N, int B, int *decisions /*[B] out*/,
+                            double *scores /*[B*S], NaN on entry, optional out*/);
+enum { FB_VICTIM_HOST_SCORES = 1, FB_VICTIM_HOST_DECISIONS = 2, FB_VICTIM_DEVICE_SCORES = 3 };
+typedef struct {
+  int mode;                    /* FB_VICTIM_* */
+  int S;                       /* enrolled speakers (1 for SV) */
+  fb_score_cb score;           /* FB_VICTIM_HOST_SCORES */
+  fb_decide_cb decide;         /* FB_VICTIM_HOST_DECISIONS */
+  const fb_dev_model *dev;     /* FB_VICTIM_DEVICE_SCORES: the caller's buffers ... */
+  fb_score_dev_cb score_dev;   /* ... and the model */
+  void *ctx;                   /* handed to the callback of the mode */
+} fb_victim;
+int fb_attack_pso_foreign(fb_engine *e, const fb_nes_params *p, const fb_pso_params *q, const fb_victim *v, const double *audio,
+                          int64_t N, int16_t *adv_i16, double *adv_f64 /*nullable*/, int *success, int *n_iters,
+                          double *trace /*[max_iter][3 + S]*/, double *losses /*[max_iter][P]*/);
+int fb_attack_kenansville_foreign(fb_engine *e, const fb_nes_params *p, const fb_kv_params *k, const fb_victim *v,
+                                  const int32_t *tables /*[4][W]*/, const double *audio, int64_t N, int16_t *adv_i16, int *success,
+                                  int *factor, int *n_queries, int *n_rounds, int *qs /*[max_rounds][G]*/,
+                                  int *decisions /*[max_rounds][G]*/, double *scores /*[max_rounds][G][S]*/,
+                                  int *trace /*[max_rounds][3]*/);
+int fb_attack_hsj_foreign(fb_engine *e, const fb_nes_params *p, const fb_hsj_params *k, const fb_victim *v, const double *audio,
+                          const double *init, int64_t N, int16_t *adv_i16, double *adv_f64 /*nullable*/, int *success,
+                          double *dist2, int *n_iters, int *n_queries, double *trace /*[max_iter + 1][8]*/,
+                          int *decisions /*[decisions_cap]*/, long long decisions_cap, double *x_trace /*nullable*/);
 
 /* Launch chain of the device-controlled attack loop.  on = 1: 4 launches per NES iteration of a GMM system (MFCC; VAD +
  * deltas + CMVN; GMM log-likelihoods; finalisation + loss + loop control + update of iteration i + perturbation of

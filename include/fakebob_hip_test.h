@@ -164,6 +164,19 @@ int fb_debug_vote(fb_engine *e, const double *raw, const int *tv, int rows, int 
 int fb_bench_vote(fb_engine *e, const double *raw, const int *tv, int rows, int r, int task, double threshold, int attack_type,
                   int label, int reps, double *ms);
 
+/* Foreign victims of the swarm and the decision-only attacks (fakebob_hip.h: fb_attack_*_foreign).  No system need be loaded.
+ * fb_debug_rows_to_model runs k_rows_to_model alone, exactly the launch the attacks run: rows_i16 [rows][N] -> out_host
+ * [rows][N] of dtype (FB_DT_*), out = q * 2^-(bits - 1).
+ * fb_debug_decide_foreign runs k_decide_foreign alone: scores_host [rows][S] of dtype -> decisions [rows] and the scores
+ * widened to float64 [rows][S], the two parts of the look block.
+ * fb_bench_foreign_rows (tools/foreign_rate.py): ms[5] = milliseconds per launch of k_rows_to_model<float>,
+ * k_rows_to_model<double> (rows x N) and k_decide_foreign<double> (rows x S), `reps` of each between two events after one to
+ * warm up; then, on the host's clock, the float64 rows copied to host memory, and the int16 rows copied and widened there. */
+int fb_debug_rows_to_model(fb_engine *e, const int16_t *rows_i16, int rows, int64_t N, int bits, int dtype, void *out_host);
+int fb_debug_decide_foreign(fb_engine *e, const void *scores_host, int dtype, int rows, int S, int task, double threshold,
+                            int *decisions, double *scores_f64);
+int fb_bench_foreign_rows(fb_engine *e, int rows, int64_t N, int bits, int S, int reps, double *ms);
+
 /* What the front end of the last batch ran (fb_score_*, fb_get_grad, an NES iteration, fb_debug_mfcc / _feats, enrolment
  * statistics): info[5] = {the MFCC kernel, the chain after it, where the CompressedMatrix round trip ran, the longest
  * utterance of the batch in frames, the batch size}.  Recorded on the host when the kernels are enqueued; read only.
@@ -222,7 +235,10 @@ int fb_debug_shared_chain_engines(fb_engine *e, int *count);
  * the batch and score dtypes (FB_DT_*; the host path hands its callback float64 and reads float64 back), the engine
  * launches of one NES iteration, the model calls, and the bytes of the batch copied device -> host and of the scores
  * copied host -> device during the loop (final outputs and control-block reads not counted).  Recorded on the host as
- * the work is enqueued.  FB_E_STATE before the first foreign call. */
+ * the work is enqueued.  FB_E_STATE before the first foreign call.
+ * fb_attack_pso_foreign, fb_attack_kenansville_foreign and fb_attack_hsj_foreign are recorded too: FB_FOREIGN_DEV for
+ * FB_VICTIM_DEVICE_SCORES, FB_FOREIGN_HOST for the two host modes; launches_per_iter then counts the engine launches of one
+ * scored BATCH (the conversion; k_loss or k_decide_foreign in the score modes), model_calls the scored batches. */
 #define FB_FOREIGN_HOST 1   /* fb_get_grad_ext / fb_attack_ext */
 #define FB_FOREIGN_DEV 2    /* fb_get_grad_dev / fb_attack_dev */
 typedef struct {
