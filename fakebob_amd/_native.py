@@ -102,6 +102,52 @@ def ivector_struct(system):
     return sy, keep
 
 
+FB_XV_MAX_LAYERS, FB_XV_MAX_CTX = 8, 5
+
+
+class XvectorLayer(C.Structure):
+    """fb_xvector_layer"""
+    _fields_ = [("dout", C.c_int), ("n_ctx", C.c_int), ("ctx", C.c_int * FB_XV_MAX_CTX), ("W", C.c_void_p),
+                ("bias", C.c_void_p), ("bn_scale", C.c_void_p), ("bn_offset", C.c_void_p)]
+
+
+class XvectorSystem(C.Structure):
+    """fb_xvector_system"""
+    _fields_ = [
+        ("D", C.c_int), ("n_layers", C.c_int), ("layers", XvectorLayer * FB_XV_MAX_LAYERS),
+        ("seg_W", C.c_void_p), ("seg_bias", C.c_void_p), ("R", C.c_int), ("L", C.c_int), ("S", C.c_int),
+        ("lda_cols", C.c_int), ("mean_vec", C.c_void_p), ("lda", C.c_void_p), ("plda_mean", C.c_void_p),
+        ("plda_transform", C.c_void_p), ("plda_psi", C.c_void_p), ("enrolled", C.c_void_p),
+        ("z_mean", C.c_void_p), ("z_std", C.c_void_p),
+    ]
+
+
+def xvector_struct(system):
+    """models.XvectorSystem -> (fb_xvector_system, the arrays it points into: keep them alive for the call).  More layers
+    or context offsets than the struct holds are a ValueError here; every other limit is the library's to refuse."""
+    if len(system.layers) > FB_XV_MAX_LAYERS:
+        raise ValueError("an x-vector system has at most %d frame layers (got %d)" % (FB_XV_MAX_LAYERS, len(system.layers)))
+    sy = XvectorSystem()
+    sy.D, sy.n_layers = system.D, len(system.layers)
+    keep = []
+    for l, ly in enumerate(system.layers):
+        d = sy.layers[l]
+        d.dout, d.n_ctx = ly["W"].shape[0], len(ly["ctx"])
+        if d.n_ctx <= FB_XV_MAX_CTX:     # (more: the library refuses n_ctx by name, it reads no offset then)
+            for j, c in enumerate(ly["ctx"]):
+                d.ctx[j] = c
+        for name in ("W", "bias", "bn_scale", "bn_offset"):
+            keep.append(ly[name])
+            setattr(d, name, ly[name].ctypes.data)
+    sy.R, sy.L, sy.S = system.R, system.L, system.S
+    sy.lda_cols = system.lda.shape[1]
+    for name in ("seg_W", "seg_bias", "mean_vec", "lda", "plda_mean", "plda_transform", "plda_psi", "enrolled", "z_mean", "z_std"):
+        a = getattr(system, name)
+        keep.append(a)
+        setattr(sy, name, a.ctypes.data)
+    return sy, keep
+
+
 class GmmPlan(C.Structure):
     """fb_gmm_plan (include/fakebob_hip_test.h)"""
     _fields_ = [("mode", C.c_int), ("NK", C.c_int), ("NKF", C.c_int), ("kx", C.c_int), ("kx2", C.c_int), ("kacc", C.c_int),
@@ -161,6 +207,7 @@ EXPORTS = [
     "fb_get_grad_dev", "fb_attack_dev", "fb_debug_foreign_path", "fb_debug_nes_route", "fb_debug_nes_batch", "fb_debug_shared_chain_engines",
     "fb_estimate_threshold", "fb_debug_noise", "fb_debug_quantize", "fb_debug_mfcc", "fb_debug_feats", "fb_debug_dither_noise", "fb_debug_mfcc_dither", "fb_debug_feats_dither", "fb_debug_input_transform", "fb_debug_tf_noise", "fb_debug_input_transform_eot", "fb_debug_compose", "fb_debug_air_taps", "fb_debug_air_convolve", "fb_debug_codec", "fb_debug_feature_compress", "fb_debug_feco_keys", "fb_debug_pso_init", "fb_debug_pso_step", "fb_debug_kv_analyse", "fb_debug_kv_candidates", "fb_debug_hsj_line", "fb_debug_hsj_probes", "fb_debug_hsj_dir", "fb_debug_hsj_step", "fb_debug_vote", "fb_debug_gmm_frames", "fb_debug_gmm_acc_rows", "fb_debug_gmm_feat_grad", "fb_debug_frontend_vjp", "fb_debug_defence_vjp", "fb_debug_wb_route", "fb_debug_air_conv_t", "fb_debug_air_conv_t_chunk", "fb_debug_wb_air_route", "fb_debug_feature_compress_vjp", "fb_debug_wb_feco_route", "fb_debug_wb_feco_state", "fb_debug_wb_compose_t", "fb_debug_wb_universal_route", "fb_debug_iv_backend_grad", "fb_debug_iv_feat_grad", "fb_debug_iv_active", "fb_debug_iv_gselect", "fb_debug_frontend_route", "fb_debug_launch_shape", "fb_stats", "fb_gmm_acc_stats", "fb_last_ivectors", "fb_gmm_kernel_mode", "fb_gmm_kernel_variant", "fb_gmm_delta_tiles", "fb_gmm_delta_tiles_f6", "fb_set_fused_chain",
     "fb_debug_prepare_gmm", "fb_debug_prepare_ivector", "fb_debug_prepare_frontend",
+    "fb_load_xvector", "fb_debug_prepare_xvector", "fb_debug_xv_embed", "fb_bench_xvector",
     "fb_bench_gmm_kernel", "fb_bench_kv_kernels", "fb_bench_hsj_kernels", "fb_bench_vote", "fb_bench_foreign_rows", "fb_bench_nes", "fb_bench_nes_state",
 ]
 

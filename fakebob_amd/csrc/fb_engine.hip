@@ -153,8 +153,13 @@ struct fb_engine {
   double gmm_delta_rms = 0.0;  // fb_load_gmm's shift statistic behind gmm.delta_p
   int n_groups = 0;
   // i-vector system (kind == 1): the diagonalised UBM lives in `gmm` (M = 1)
-  int kind = 0;   // 0 = GMM-UBM, 1 = i-vector/PLDA
-  int n_out = 0;  // columns of `raw`: models (GMM) or enrolled speakers (i-vector)
+  int kind = 0;   // 0 = GMM-UBM, 1 = i-vector/PLDA, 2 = x-vector/PLDA
+  int n_out = 0;  // columns of `raw`: models (GMM) or enrolled speakers (i-vector, x-vector)
+  // x-vector system (kind == 2): the layers in `xv`, the back end in the back-end fields of `iv` (the others stay unset), the
+  // embeddings in iv_ivec; `gmm` holds a one-component placeholder so that what sizes the batch by it keeps working
+  FbXvDev xv;
+  DevBuf xv_w[FB_XV_MAX_LAYERS], xv_par, xv_seg;   // weight images; bias / scale / offset of every layer; segT + seg_bias
+  DevBuf xv_rowinfo, xv_amax, xv_act[2], xv_stats;
   FbIvDev iv;
   DevBuf iv_fg, iv_fg64, iv_fgL, iv_tri, iv_sim, iv_u, iv_backend;
   DevBuf iv_ll, iv_sel, iv_post, iv_gamma, iv_X, iv_linp, iv_quad, iv_A, iv_linv, iv_ivec, iv_fail, iv_active, iv_bws, iv_pairs, iv_llf;
@@ -633,6 +638,7 @@ extern "C" int fb_set_system(fb_engine *e, int task, const double *z_mean, const
   if (!e->have_gmm) return fb_fail(FB_E_STATE, "load a model first");
   if (task != FB_TASK_OSI && task != FB_TASK_CSI && task != FB_TASK_SV) return fb_fail(FB_E_ARG, "bad task");
   if (e->kind == 1) return fb_fail(FB_E_STATE, "i-vector systems take their task and z-norm from fb_load_ivector");
+  if (e->kind == 2) return fb_fail(FB_E_STATE, "x-vector systems take their task and z-norm from fb_load_xvector");
   const int M = e->n_out;
   if (task != FB_TASK_CSI && M < 2) return fb_fail(FB_E_ARG, "OSI/SV need the UBM + >=1 speaker model");
   if (task == FB_TASK_SV && M != 2) return fb_fail(FB_E_ARG, "SV takes exactly [ubm, speaker]");
@@ -650,7 +656,7 @@ extern "C" int fb_set_system(fb_engine *e, int task, const double *z_mean, const
 
 extern "C" int fb_num_speakers(fb_engine *e) {
   if (!e || !e->have_gmm) return 0;
-  if (e->kind == 1) return e->n_out;
+  if (e->kind != 0) return e->n_out;
   return e->task == FB_TASK_CSI ? e->n_out : e->n_out - 1;
 }
 
@@ -1120,6 +1126,33 @@ static int feature_compress(fb_engine *e, const FbScoreCall &call, int B, int to
   return FB_OK;
 }
 
+// The x-vector chain (xvector_kernels.hip) on e->feats / e->row_off: frame layers 0 .. min(upto, n_layers - 1), then -- with
+// upto >= n_layers -- pooling into xv_stats and, with upto > n_layers, the segment affine into iv_ivec.  *last (nullable): the
+// buffer that holds the last frame layer run.  Purely asynchronous.
+static int run_xvector(fb_engine *e, int B, int total_frames, int upto, const float **last) {
+  const FbXvDev &xv = e->xv;
+  hipStream_t s = e->stream;
+  const size_t rows = (size_t)(total_frames > 0 ? total_frames : 1);
+  FBCHK(e->xv_rowinfo.ensure(sizeof(int2) * rows));
+  FBCHK(e->xv_amax.ensure(sizeof(float) * rows));
+  for (int i = 0; i < 2; ++i) FBCHK(e->xv_act[i].ensure(sizeof(float) * rows * (size_t)xv.max_width));
+  FBCHK(e->xv_stats.ensure(sizeof(double) * (size_t)B * 2 * xv.P));
+  FBCHK(e->iv_ivec.ensure(sizeof(double) * (size_t)B * xv.R));
+  const int *n_rows = e->row_off.as<int>() + B;
+  fb_launch_xv_rowinfo(s, e->row_off.as<int>(), B, e->xv_rowinfo.as<int2>());
+  const float *in = e->feats.as<float>();
+  for (int l = 0; l < xv.n_layers && l <= upto; ++l) {
+    float *out = e->xv_act[l & 1].as<float>();
+    fb_launch_xv_rowmax(s, in, xv.layer[l].din, n_rows, total_frames, e->xv_amax.as<float>());
+    fb_launch_xv_affine(s, xv.layer[l], in, e->xv_amax.as<float>(), e->xv_rowinfo.as<int2>(), n_rows, total_frames, out);
+    in = out;
+  }
+  if (last) *last = in;
+  if (upto >= xv.n_layers) fb_launch_xv_pool(s, in, xv.P, e->row_off.as<int>(), B, e->xv_stats.as<double>());
+  if (upto > xv.n_layers) fb_launch_xv_segment(s, xv, e->xv_stats.as<double>(), B, e->iv_ivec.as<double>());
+  return FB_OK;
+}
+
 // wav (device) + offsets (device) -> raw[B][M] (device).  Purely asynchronous.
 static int run_scoring(fb_engine *e, FbScoreCall &call, int B, int total_frames) {
   FBCHK(e->mfcc.ensure(sizeof(float) * (size_t)total_frames * e->fe.nc));
@@ -1159,6 +1192,15 @@ static int run_scoring(fb_engine *e, FbScoreCall &call, int B, int total_frames)
     if (!call.defer_finalize)
       fb_launch_gmm_finalize(s, g, e->part_m.as<float>(), e->part_s.as<float>(), total_frames, n_chunks,
                              e->row_off.as<int>(), B, e->raw.as<double>());
+  } else if (e->kind == 2) {
+    // x-vector systems: the layers, pooling and the segment affine, then the back end as its own launch; the caller's
+    // k_loss / k_loss_eot / k_vote follows (the i-vector branch's "split" tail)
+    FB_DBG_SYNC(e, "front-end");
+    FBCHK(time_begin(e));
+    FBCHK(run_xvector(e, B, total_frames, e->xv.n_layers + 1, nullptr));
+    FBCHK(time_end(e));
+    fb_launch_iv_backend(s, e->iv, e->iv_ivec.as<double>(), B, e->raw.as<double>());
+    FB_DBG_SYNC(e, "backend");
   } else {
     const FbIvDev &iv = e->iv;
     const int64_t Q = (int64_t)iv.C * iv.D;
@@ -1406,7 +1448,7 @@ extern "C" int fb_system_scores(fb_engine *e, const double *raw, int B, double *
   if (!e || !raw || !scores || B <= 0) return fb_fail(FB_E_ARG, "bad argument");
   if (!e->have_gmm) return fb_fail(FB_E_STATE, "no model loaded");
   const int M = e->n_out;
-  if (e->task == FB_TASK_CSI || e->kind == 1) {
+  if (e->task == FB_TASK_CSI || e->kind != 0) {
     for (int b = 0; b < B; ++b)
       for (int m = 0; m < M; ++m)
         scores[(size_t)b * M + m] = (raw[(size_t)b * M + m] - e->h_zmean[m]) / e->h_zstd[m];
@@ -1515,6 +1557,91 @@ extern "C" int fb_load_ivector(fb_engine *e, const fb_ivector_system *sy, int ta
   return FB_OK;
 }
 
+// ----------------------------------------------------------------- x-vector
+static int prepare_xvector(const fb_xvector_system *sy, FbXvPrepared *out) {
+  std::string err;
+  const int rc = fb_prepare_xvector(sy, out, &err);
+  return rc == FB_OK ? FB_OK : fb_fail(rc, "%s", err.c_str());
+}
+
+extern "C" int fb_load_xvector(fb_engine *e, const fb_xvector_system *sy, int task) {
+  if (!e || !sy) return fb_fail(FB_E_ARG, "null argument");
+  if (task != FB_TASK_OSI && task != FB_TASK_CSI && task != FB_TASK_SV) return fb_fail(FB_E_ARG, "bad task");
+  {
+    std::string err;
+    const int rc = fb_xvector_check(sy, &err);
+    if (rc != FB_OK) return fb_fail(rc, "%s", err.c_str());
+  }
+  if (!e->have_fe || e->fe.dim != sy->D)
+    return fb_fail(FB_E_ARG, "x-vector feature dim D=%d != front-end feature dim %d", sy->D, e->have_fe ? e->fe.dim : -1);
+  if (task == FB_TASK_SV && sy->S != 1) return fb_fail(FB_E_ARG, "SV takes exactly one enrolled speaker");
+  if (e->feco_iters > 0)
+    return fb_fail(FB_E_STATE, "fb_load_xvector: feature compression is on (k-means discards the frame order a TDNN reads: switch it off)");
+  // everything on the host first: a refused call leaves the engine and the device as they were
+  FbXvPrepared p;
+  FBCHK(prepare_xvector(sy, &p));
+  const int D = sy->D, R = sy->R, L = sy->L, S = sy->S;
+  // the placeholder in `gmm`: one component, zero mean, unit variance (never scored)
+  const std::vector<float> ph_gc(1, 0.0f), ph_miv(D, 0.0f), ph_iv(D, 1.0f);
+  FbGmmPrepared pg;
+  FBCHK(prepare_gmm(e, 1, 1, D, ph_gc.data(), ph_miv.data(), ph_iv.data(), &pg));
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  // ---- ensure
+  size_t n_par = 0;
+  for (int l = 0; l < p.n_layers; ++l) {
+    FBCHK(e->xv_w[l].ensure(sizeof(uint16_t) * p.layer[l].w.size()));
+    n_par += 3 * (size_t)p.layer[l].dout;
+  }
+  FBCHK(e->xv_par.ensure(sizeof(float) * n_par));
+  FBCHK(e->xv_seg.ensure(sizeof(double) * (p.segT.size() + p.seg_bias.size())));
+  FBCHK(e->iv_backend.ensure(sizeof(double) * p.be.backend.size()));
+  FBCHK(commit_gmm(e, pg, ph_gc.data(), ph_miv.data(), ph_iv.data()));
+  FBCHK(e->zmean.ensure(sizeof(double) * S));
+  FBCHK(e->zstd.ensure(sizeof(double) * S));
+  // ---- upload and assign
+  FbXvDev &xv = e->xv;
+  xv = FbXvDev{};
+  xv.D = D; xv.n_layers = p.n_layers; xv.P = p.P; xv.R = R; xv.max_width = p.max_width;
+  float *par = e->xv_par.as<float>();
+  for (int l = 0; l < p.n_layers; ++l) {
+    const FbXvLayerPrepared &q = p.layer[l];
+    FbXvLayerDev &d = xv.layer[l];
+    HIPCHK(hipMemcpy(e->xv_w[l].p, q.w.data(), sizeof(uint16_t) * q.w.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(par, q.bias.data(), sizeof(float) * q.dout, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(par + q.dout, q.scale.data(), sizeof(float) * q.dout, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(par + 2 * q.dout, q.offset.data(), sizeof(float) * q.dout, hipMemcpyHostToDevice));
+    d.din = q.din; d.dout = q.dout; d.n_ctx = q.n_ctx;
+    for (int j = 0; j < FB_XV_MAX_CTX; ++j) d.ctx[j] = q.ctx[j];
+    d.K = q.K; d.n_steps = q.n_steps; d.kw = q.kw;
+    d.w = e->xv_w[l].as<unsigned short>();
+    d.bias = par; d.scale = par + q.dout; d.offset = par + 2 * q.dout;
+    par += 3 * (size_t)q.dout;
+  }
+  double *seg = e->xv_seg.as<double>();
+  HIPCHK(hipMemcpy(seg, p.segT.data(), sizeof(double) * p.segT.size(), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(seg + p.segT.size(), p.seg_bias.data(), sizeof(double) * p.seg_bias.size(), hipMemcpyHostToDevice));
+  xv.segT = seg;
+  xv.seg_bias = seg + p.segT.size();
+  HIPCHK(hipMemcpy(e->iv_backend.p, p.be.backend.data(), sizeof(double) * p.be.backend.size(), hipMemcpyHostToDevice));
+  e->h_zmean.assign(sy->z_mean, sy->z_mean + S);
+  e->h_zstd.assign(sy->z_std, sy->z_std + S);
+  HIPCHK(hipMemcpy(e->zmean.p, e->h_zmean.data(), sizeof(double) * S, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(e->zstd.p, e->h_zstd.data(), sizeof(double) * S, hipMemcpyHostToDevice));
+  // the back-end fields of `iv`, and nothing else of it
+  FbIvDev &iv = e->iv;
+  iv = FbIvDev{};
+  const double *b = e->iv_backend.as<double>();
+  iv.mean_vec = b + p.be.o_mean; iv.ldaT = b + p.be.o_lda; iv.plda_mean = b + p.be.o_pm; iv.pldaT = b + p.be.o_pt;
+  iv.plda_psi = b + p.be.o_psi; iv.train = b + p.be.o_tr;
+  iv.text_scores = e->cfg.text_scores;
+  iv.D = D; iv.R = R; iv.L = L; iv.S = S; iv.lda_cols = sy->lda_cols;
+  e->kind = 2;
+  e->n_out = S;
+  e->task = task;
+  return FB_OK;
+}
+
 // ------------------------------------------------- the loaders' host preparation without an engine (fakebob_hip_test.h)
 // size-then-fill: *size = the named buffer's bytes; with out != NULL it is copied there (cap bytes must hold it)
 static int give_bytes(const char *name, const void *src, size_t n, void *out, int64_t cap, int64_t *size) {
@@ -1569,6 +1696,109 @@ extern "C" int fb_debug_prepare_ivector(const fb_ivector_system *sy, const char 
     return give_vector(buffer, o, out, cap, size);
   }
   return fb_fail(FB_E_ARG, "no i-vector buffer '%s' (dg_gc, dg_miv, dg_iv, fg_gc, tri, fg64, fgL, backend, backend_offsets)", buffer);
+}
+
+extern "C" int fb_debug_prepare_xvector(const fb_xvector_system *sy, const char *buffer, void *out, int64_t cap, int64_t *size) {
+  if (!sy || !buffer) return fb_fail(FB_E_ARG, "null argument");
+  FbXvPrepared p;
+  FBCHK(prepare_xvector(sy, &p));
+  if (buffer[0] == 'w' && buffer[1] >= '0' && buffer[1] < '0' + p.n_layers && buffer[2] == 0)
+    return give_vector(buffer, p.layer[buffer[1] - '0'].w, out, cap, size);
+  if (strcmp(buffer, "kw") == 0) {
+    std::vector<int32_t> kw;
+    for (int l = 0; l < p.n_layers; ++l) kw.push_back(p.layer[l].kw);
+    return give_vector(buffer, kw, out, cap, size);
+  }
+  if (strcmp(buffer, "segT") == 0) return give_vector(buffer, p.segT, out, cap, size);
+  if (strcmp(buffer, "backend") == 0) return give_vector(buffer, p.be.backend, out, cap, size);
+  if (strcmp(buffer, "backend_offsets") == 0) {
+    const std::vector<int64_t> o = {(int64_t)p.be.o_mean, (int64_t)p.be.o_lda, (int64_t)p.be.o_pm, (int64_t)p.be.o_pt,
+                                    (int64_t)p.be.o_psi, (int64_t)p.be.o_tr};
+    return give_vector(buffer, o, out, cap, size);
+  }
+  return fb_fail(FB_E_ARG, "no x-vector buffer '%s' (w0 .. w%d, kw, segT, backend, backend_offsets)", buffer, p.n_layers - 1);
+}
+
+// Test hook: the x-vector chain on rows handed in (fakebob_hip_test.h)
+extern "C" int fb_debug_xv_embed(fb_engine *e, const float *feats, const int *row_off, int B, int layer, void *out) {
+  if (!e || !feats || !row_off || !out || B <= 0) return fb_fail(FB_E_ARG, "bad argument");
+  if (!e->have_gmm || e->kind != 2) return fb_fail(FB_E_STATE, "load an x-vector system first");
+  const FbXvDev &xv = e->xv;
+  if (layer < 0 || layer > xv.n_layers + 1) return fb_fail(FB_E_ARG, "layer %d outside 0 .. %d", layer, xv.n_layers + 1);
+  if (row_off[0] != 0) return fb_fail(FB_E_ARG, "row_off[0] must be 0");
+  for (int b = 0; b < B; ++b)
+    if (row_off[b + 1] < row_off[b]) return fb_fail(FB_E_ARG, "row_off must not descend");
+  const int rows = row_off[B];
+  if (rows <= 0) return fb_fail(FB_E_ARG, "no rows");
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  e->cached_B = -1;
+  e->bench_it = e->nes_rec.iter = -1;
+  FBCHK(e->feats.ensure(sizeof(float) * (size_t)rows * xv.D));
+  FBCHK(e->row_off.ensure(sizeof(int) * (size_t)(B + 1)));
+  FBCHK(h2d(e, e->feats.p, feats, sizeof(float) * (size_t)rows * xv.D));
+  FBCHK(h2d(e, e->row_off.p, row_off, sizeof(int) * (size_t)(B + 1)));
+  const float *last = nullptr;
+  FBCHK(run_xvector(e, B, rows, layer, &last));
+  HIPCHK(hipGetLastError());
+  if (layer < xv.n_layers) FBCHK(d2h(e, out, last, sizeof(float) * (size_t)rows * xv.layer[layer].dout));
+  else if (layer == xv.n_layers) FBCHK(d2h(e, out, e->xv_stats.p, sizeof(double) * (size_t)B * 2 * xv.P));
+  else FBCHK(d2h(e, out, e->iv_ivec.p, sizeof(double) * (size_t)B * xv.R));
+  return sync_stream(e);
+}
+
+// Benchmark hook (tools/xvector_rate.py): every launch of the x-vector chain on rows handed in, `reps` times between device
+// events after one launch to warm up
+extern "C" int fb_bench_xvector(fb_engine *e, const float *feats, const int *row_off, int B, int reps, double *ms_rowmax,
+                                double *ms_affine, double *ms_tail) {
+  if (!e || !feats || !row_off || !ms_rowmax || !ms_affine || !ms_tail || B <= 0 || reps <= 0) return fb_fail(FB_E_ARG, "bad argument");
+  if (!e->have_gmm || e->kind != 2) return fb_fail(FB_E_STATE, "load an x-vector system first");
+  const FbXvDev &xv = e->xv;
+  const int rows = row_off[B];
+  if (row_off[0] != 0 || rows <= 0) return fb_fail(FB_E_ARG, "bad row_off");
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  e->cached_B = -1;
+  e->bench_it = e->nes_rec.iter = -1;
+  FBCHK(e->feats.ensure(sizeof(float) * (size_t)rows * xv.D));
+  FBCHK(e->row_off.ensure(sizeof(int) * (size_t)(B + 1)));
+  FBCHK(e->raw.ensure(sizeof(double) * (size_t)B * e->n_out));
+  FBCHK(h2d(e, e->feats.p, feats, sizeof(float) * (size_t)rows * xv.D));
+  FBCHK(h2d(e, e->row_off.p, row_off, sizeof(int) * (size_t)(B + 1)));
+  FBCHK(run_xvector(e, B, rows, xv.n_layers + 1, nullptr));   // every buffer sized, every stage's input in place
+  FBCHK(sync_stream(e));
+  hipStream_t s = e->stream;
+  hipEvent_t ev0, ev1;
+  HIPCHK(hipEventCreate(&ev0));
+  HIPCHK(hipEventCreate(&ev1));
+  auto timed = [&](auto &&launch, double *ms) -> int {
+    launch();
+    HIPCHK(hipEventRecord(ev0, s));
+    for (int i = 0; i < reps; ++i) launch();
+    HIPCHK(hipEventRecord(ev1, s));
+    HIPCHK(hipEventSynchronize(ev1));
+    float t = 0.0f;
+    HIPCHK(hipEventElapsedTime(&t, ev0, ev1));
+    *ms = (double)t / reps;
+    return FB_OK;
+  };
+  const int *n_rows = e->row_off.as<int>() + B;
+  int rc = FB_OK;
+  const float *in = e->feats.as<float>();
+  for (int l = 0; l < xv.n_layers && rc == FB_OK; ++l) {
+    float *out = e->xv_act[l & 1].as<float>();
+    rc = timed([&] { fb_launch_xv_rowmax(s, in, xv.layer[l].din, n_rows, rows, e->xv_amax.as<float>()); }, ms_rowmax + l);
+    if (rc == FB_OK)
+      rc = timed([&] { fb_launch_xv_affine(s, xv.layer[l], in, e->xv_amax.as<float>(), e->xv_rowinfo.as<int2>(), n_rows, rows, out); },
+                 ms_affine + l);
+    in = out;
+  }
+  if (rc == FB_OK) rc = timed([&] { fb_launch_xv_pool(s, in, xv.P, e->row_off.as<int>(), B, e->xv_stats.as<double>()); }, ms_tail + 0);
+  if (rc == FB_OK) rc = timed([&] { fb_launch_xv_segment(s, xv, e->xv_stats.as<double>(), B, e->iv_ivec.as<double>()); }, ms_tail + 1);
+  if (rc == FB_OK) rc = timed([&] { fb_launch_iv_backend(s, e->iv, e->iv_ivec.as<double>(), B, e->raw.as<double>()); }, ms_tail + 2);
+  (void)hipEventDestroy(ev0);
+  (void)hipEventDestroy(ev1);
+  return rc;
 }
 
 extern "C" int fb_debug_prepare_frontend(const fb_frontend_cfg *c, const char *buffer, void *out, int64_t cap, int64_t *size) {
@@ -1652,7 +1882,7 @@ extern "C" int fb_debug_iv_gselect(fb_engine *e, int *sel, int64_t sel_cap, int6
 // i-vector as the speaker identity)
 extern "C" int fb_last_ivectors(fb_engine *e, int B, double *ivecs) {
   if (!e || !ivecs || B <= 0) return fb_fail(FB_E_ARG, "bad argument");
-  if (e->kind != 1 || e->last_B < B) return fb_fail(FB_E_STATE, "score a batch with an i-vector system first");
+  if (e->kind == 0 || e->last_B < B) return fb_fail(FB_E_STATE, "score a batch with an i-vector or x-vector system first");
   HIPCHK(hipSetDevice(e->device));
   FBCHK(sync_stream(e));
   HIPCHK(hipMemcpy(ivecs, e->iv_ivec.p, sizeof(double) * (size_t)B * e->iv.R, hipMemcpyDeviceToHost));
@@ -2468,6 +2698,8 @@ extern "C" int fb_attack_dev(fb_engine *e, const fb_nes_params *p, int S, const 
 static int wb_check(fb_engine *e, const fb_nes_params *p, const double *audio, int64_t N, fb_nes_params *q) {
   if (!e || !p || !audio) return fb_fail(FB_E_ARG, "null argument");
   if (!e->have_gmm) return fb_fail(FB_E_STATE, "no model loaded");
+  if (e->kind == 2)
+    return fb_fail(FB_E_STATE, "white-box gradients: an x-vector system is loaded (no gradient through the TDNN: not in this version)");
   if (e->kind != 0 && !e->wb_ivector)
     return fb_fail(FB_E_STATE, "white-box gradients: an i-vector system is loaded (GMM-UBM systems only in this version)");
   // (the forward keeps the selection, posteriors and statistics of ONE row for the backward, not those of r replicas)
@@ -5113,6 +5345,8 @@ static int gmm_stats_launch(fb_engine *e, const int *n_rows_ptr, int T, double *
 // of the loaded GMM (the UBM, loaded alone) on the voiced frames of one utterance.
 extern "C" int fb_gmm_acc_stats(fb_engine *e, const int16_t *wav, int64_t n, double *occ, double *F, int *tv_out) {
   if (!e || !wav || !occ || !F || n <= 0) return fb_fail(FB_E_ARG, "bad argument");
+  if (e->have_gmm && e->kind == 2)
+    return fb_fail(FB_E_STATE, "fb_gmm_acc_stats: an x-vector system is loaded (GMM statistics of a TDNN victim: not in this version)");
   if (!e->have_gmm || e->kind != 0 || e->gmm.M != 1)
     return fb_fail(FB_E_STATE, "load exactly one diagonal GMM (the UBM) before accumulating statistics");
   FBCHK(debug_frontend(e, wav, n));  // MFCC, VAD, deltas, CMVN, voiced rows of this utterance
@@ -5630,6 +5864,8 @@ extern "C" int fb_set_feature_compression(fb_engine *e, double ratio, int iters)
   const bool off = ratio == 0.0 && iters == 0;
   if (!off && (!(ratio > 0.0 && ratio <= 1.0) || iters < 1 || iters > 64))
     return fb_fail(FB_E_ARG, "feature compression takes 0 < ratio <= 1 and 1 .. 64 iterations, or 0 and 0 for none (got %g, %d)", ratio, iters);
+  if (!off && e->have_gmm && e->kind == 2)
+    return fb_fail(FB_E_STATE, "feature compression: an x-vector system is loaded (k-means discards the frame order a TDNN reads: not in this version)");
   e->feco_ratio = off ? 0.0 : ratio;
   e->feco_iters = iters;
   e->bench_it = e->nes_rec.iter = -1;  // an attack fb_bench_nes left resident ran under the previous setting

@@ -757,3 +757,29 @@ bool fb_launch_iv_solve_rw(hipStream_t s, const FbIvDev &iv, const double *quad,
                            double *Aall, double *LinvAll, double *ivec, int *fail, unsigned *prog, int *ticket, unsigned epoch,
                            const FbIvTail &tail);
 void fb_launch_iv_backend(hipStream_t s, const FbIvDev &iv, const double *ivec, int B, double *llr);
+
+// ---- x-vector (TDNN) system (xvector_kernels.hip; the "x-vector" section of fakebob_hip.h) ------------------------
+struct FbXvLayerDev {
+  int din, dout, n_ctx, ctx[FB_XV_MAX_CTX];
+  int K, n_steps;            // n_ctx * din, ceil(K / 16)
+  int kw;                    // the image holds W * 2^-kw
+  const unsigned short *w;   // fb_xv_frag_index images, one per column tile of 32 channels (fb_prepare.h)
+  const float *bias, *scale, *offset;
+};
+struct FbXvDev {
+  int D, n_layers, P, R, max_width;
+  FbXvLayerDev layer[FB_XV_MAX_LAYERS];
+  const double *segT;        // [2 P][R]
+  const double *seg_bias;    // [R]
+};
+// rowinfo[row] = {first row, rows} of the utterance the row belongs to, for the rows below row_off[B] (rows_cap bounds them)
+void fb_launch_xv_rowinfo(hipStream_t s, const int *row_off, int B, int2 *rowinfo);
+// amax[row] = max |x[row][0 .. din)|
+void fb_launch_xv_rowmax(hipStream_t s, const float *x, int din, const int *n_rows_ptr, int rows_cap, float *amax);
+// one frame layer: y[row][dout] from x[row][din] (k_xv_affine)
+void fb_launch_xv_affine(hipStream_t s, const FbXvLayerDev &ly, const float *x, const float *amax, const int2 *rowinfo,
+                         const int *n_rows_ptr, int rows_cap, float *y);
+// stats[b][2 P] = {mean, std} over the utterance's rows of h[row][P]
+void fb_launch_xv_pool(hipStream_t s, const float *h, int P, const int *row_off, int B, double *stats);
+// emb[b][R] = segT' stats[b] + seg_bias
+void fb_launch_xv_segment(hipStream_t s, const FbXvDev &xv, const double *stats, int B, double *emb);

@@ -138,6 +138,32 @@ bool fb_iv_chol_image(const fb_ivector_system *sy, const std::vector<float> &fg_
 void fb_iv_backend_table(const fb_ivector_system *sy, FbIvPrepared *out);
 int fb_prepare_ivector(const fb_ivector_system *sy, FbIvPrepared *out, std::string *err);
 
+// ------------------------------------------------------------------------------------------------ x-vector
+// Where K position k of output channel place cc (0 .. 31) of term `term` (0: f16(v), 1: f16(v - term 0)) stands in a
+// column tile's image [n_steps][2 terms][64 lanes] x 8 values -- fb_gmm_frag_index's lane rule, the terms of a K step side
+// by side (k_xv_affine fetches both with one address)
+static inline size_t fb_xv_frag_index(int term, int k, int cc) {
+  const int st = k / 16, hh = (k % 16) / 8, i = k % 8, lane = hh * 32 + cc;
+  return (((size_t)st * 2 + term) * 64 + lane) * 8 + i;
+}
+struct FbXvLayerPrepared {
+  int din = 0, dout = 0, n_ctx = 0, ctx[FB_XV_MAX_CTX] = {0, 0, 0, 0, 0};
+  int K = 0, n_steps = 0;          // n_ctx * din, ceil(K / 16)
+  int kw = 0;                      // the image holds W * 2^-kw: max |W| 2^-kw in [2^14, 2^15) (0 for an all-zero layer)
+  std::vector<uint16_t> w;         // [ceil(dout / 32)] tiles of fb_xv_frag_index, zeros past dout
+  std::vector<float> bias, scale, offset;
+};
+struct FbXvPrepared {
+  int D = 0, n_layers = 0, P = 0, R = 0, max_width = 0;
+  FbXvLayerPrepared layer[FB_XV_MAX_LAYERS];
+  std::vector<double> segT;        // [2 P][R]: seg_W transposed, float64
+  std::vector<double> seg_bias;    // [R]
+  FbIvPrepared be;                 // the back end's table (backend, o_*): fb_iv_backend_table's
+};
+// FB_E_ARG with the limit's name in *err for a system outside the contract's limits (fakebob_hip.h, "x-vector")
+int fb_xvector_check(const fb_xvector_system *sy, std::string *err);
+int fb_prepare_xvector(const fb_xvector_system *sy, FbXvPrepared *out, std::string *err);
+
 // ------------------------------------------------------------------------------------------------ front-end
 struct FbFrontendTables {
   std::vector<double> window, tw_half, tw_full, mel_w, dct, lifter, dscale;

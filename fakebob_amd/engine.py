@@ -471,6 +471,45 @@ class Engine(object):
         self.task = task
         self.kind = "iv"
 
+    def load_xvector(self, system, task="OSI"):
+        """system: models.XvectorSystem"""
+        sy, keep = N.xvector_struct(system)
+        N.check(self._L.fb_load_xvector(self._h, C.byref(sy), C.c_int(N.TASK[task])))
+        self._xv_shape = ([ly["W"].shape[0] for ly in system.layers], system.P, system.R)
+        self.n_models = system.S
+        self.task = task
+        self.kind = "xv"
+
+    def debug_xv_embed(self, mats, layer):
+        """The loaded x-vector system's chain on feature rows handed in (fb_debug_xv_embed): `mats`, a list of (T_b,
+        feat_dim) float32 arrays -> that frame layer's outputs, a list of (T_b, dout) float32 arrays (layer < n_layers);
+        the pooled statistics, (B, 2 P) float64 (layer == n_layers); the embeddings, (B, R) float64 (n_layers + 1)."""
+        douts, P, R = self._xv_shape
+        lst = [np.ascontiguousarray(m, np.float32).reshape(-1, self.feat_dim) for m in mats]
+        off = np.zeros(len(lst) + 1, np.int32)
+        off[1:] = np.cumsum([m.shape[0] for m in lst])
+        cat = np.ascontiguousarray(np.concatenate(lst, axis=0))
+        layer = int(layer)
+        if layer < len(douts):
+            out = np.empty((cat.shape[0], douts[max(layer, 0)]), np.float32)
+        else:
+            out = np.empty((len(lst), 2 * P if layer == len(douts) else R), np.float64)
+        N.check(self._L.fb_debug_xv_embed(self._h, N.ptr(cat), N.ptr(off), C.c_int(len(lst)), C.c_int(layer), N.ptr(out)))
+        if layer < len(douts):
+            return [out[off[b]:off[b + 1]].copy() for b in range(len(lst))]
+        return out
+
+    def bench_xvector(self, B, T, reps=10, seed=0):
+        """fb_bench_xvector on B utterances of T seeded feature rows each -> a dict of milliseconds per launch: rowmax and
+        affine (one entry per frame layer), pool, segment, backend."""
+        douts, _P, _R = self._xv_shape
+        rng = np.random.default_rng(seed)
+        cat = (3.0 * rng.standard_normal((B * T, self.feat_dim), dtype=np.float32))
+        off = (np.arange(B + 1, dtype=np.int64) * T).astype(np.int32)
+        rm, af, tail = np.zeros(len(douts)), np.zeros(len(douts)), np.zeros(3)
+        N.check(self._L.fb_bench_xvector(self._h, N.ptr(cat), N.ptr(off), C.c_int(B), C.c_int(int(reps)), N.ptr(rm), N.ptr(af), N.ptr(tail)))
+        return dict(rowmax=rm.tolist(), affine=af.tolist(), pool=float(tail[0]), segment=float(tail[1]), backend=float(tail[2]))
+
     def gmm_acc_stats(self, wav):
         """UBM (loaded alone) posterior statistics of one utterance: occ[C], F[C,D] (float64), voiced frames."""
         wav = np.ascontiguousarray(wav).reshape(-1)

@@ -92,6 +92,35 @@ def enroll_ivector(pre, enroll_audios, znorm_audios, device=0, num_gselect=20, m
     return ivs, np.mean(llr, axis=0).flatten(), np.std(llr, axis=0).flatten()
 
 
+def enroll_xvector(system, enroll_audios, znorm_audios, device=0, frontend=None):
+    """system: a models.XvectorSystem (its enrolled speakers are ignored); enroll_audios: per speaker one utterance or a
+    list of utterances -- the speaker's enrolment embedding is the mean of its utterances' embeddings (Kaldi's
+    ivector-mean over a speaker's x-vectors), each read back through Engine.last_ivectors; frontend: front-end overrides
+    (Engine.set_frontend keywords; the feature dimension must be system.D).  -> (embeddings [S, R] float32, z_mean[S],
+    z_std[S])."""
+    from .engine import Engine
+    per_spk = [[_i16(u) for u in a] if isinstance(a, (list, tuple)) else [_i16(a)] for a in enroll_audios]
+    S = len(per_spk)
+    flat = [u for utts in per_spk for u in utts]
+    base = system.with_enrolled(np.zeros((1, system.R), np.float32), np.zeros(1), np.ones(1))
+    e = Engine(device)
+    try:
+        if frontend:
+            e.set_frontend(**frontend)
+        e.load_xvector(base, "CSI")
+        e.score_raw(flat)
+        emb = e.last_ivectors(len(flat), system.R)
+        out, o = np.empty((S, system.R), np.float32), 0
+        for s, utts in enumerate(per_spk):
+            out[s] = emb[o:o + len(utts)].mean(axis=0)       # stored as float32, like Kaldi's vectors
+            o += len(utts)
+        e.load_xvector(base.with_enrolled(out, np.zeros(S), np.ones(S)), "CSI")
+        llr, _ = e.score_raw([_i16(a) for a in znorm_audios])     # (n_znorm, S) PLDA log-likelihood ratios
+    finally:
+        e.close()
+    return out, np.mean(llr, axis=0).flatten(), np.std(llr, axis=0).flatten()
+
+
 def _list_wavs(d):
     out = []
     for name in sorted(os.listdir(d)):

@@ -220,3 +220,101 @@ def synthetic_ivector_system(C=2048, D=72, R=400, L=200, n_speakers=1, seed=3001
     f32 = inv_covars.astype(np.float32)
     return IvectorSystem(w, mic, f32, M, f32.astype(np.float64), prior_offset, np.zeros(R), lda, np.zeros(L),
                          np.eye(L), psi, enrolled)
+
+
+XV_BACKEND = ("mean_vec", "lda", "plda_mean", "plda_transform", "plda_psi", "enrolled", "z_mean", "z_std")
+STOCK_XV_CONTEXTS = ((-2, -1, 0, 1, 2), (-2, 0, 2), (-3, 0, 3), (0,), (0,))
+
+
+class XvectorSystem(object):
+    """A Kaldi x-vector recogniser as fb_load_xvector takes it (include/fakebob_hip.h, "x-vector"):
+      layers       a list of dicts {ctx: ascending frame offsets, W [dout, n_ctx * din], bias, bn_scale, bn_offset [dout]}
+                   (float32): h_out[t] = bn_scale * max(W . splice(h_in, t) + bias, 0) + bn_offset
+      segment      seg_W [R, 2 P], seg_bias [R] (float32) on [mean; std] of the last layer's P channels
+      back-end     as IvectorSystem's: mean_vec [R], lda [L, R or R+1] (float32); plda mean [L], transform [L,L], psi [L]
+      enrolled     embeddings [S,R] (float32), z-norm mean/std [S]
+    """
+
+    def __init__(self, D, layers, seg_W, seg_bias, mean_vec, lda, plda_mean, plda_transform, plda_psi, enrolled,
+                 z_mean=None, z_std=None):
+        f32, f64 = np.float32, np.float64
+        self.D = int(D)
+        self.layers = []
+        din = self.D
+        for ly in layers:
+            ctx = tuple(int(c) for c in ly["ctx"])
+            W = np.ascontiguousarray(ly["W"], f32)
+            assert W.ndim == 2 and W.shape[1] == len(ctx) * din, (W.shape, ctx, din)
+            d = {"ctx": ctx, "W": W}
+            for k in ("bias", "bn_scale", "bn_offset"):
+                d[k] = np.ascontiguousarray(ly[k], f32).reshape(-1)
+                assert d[k].shape == (W.shape[0],)
+            self.layers.append(d)
+            din = W.shape[0]
+        self.P = din
+        self.seg_W = np.ascontiguousarray(seg_W, f32)
+        self.seg_bias = np.ascontiguousarray(seg_bias, f32)
+        self.mean_vec = np.ascontiguousarray(mean_vec, f32)
+        self.lda = np.ascontiguousarray(lda, f32)
+        self.plda_mean = np.ascontiguousarray(plda_mean, f64)
+        self.plda_transform = np.ascontiguousarray(plda_transform, f64)
+        self.plda_psi = np.ascontiguousarray(plda_psi, f64)
+        self.enrolled = np.ascontiguousarray(np.atleast_2d(enrolled), f32)
+        S = self.enrolled.shape[0]
+        self.z_mean = np.ascontiguousarray(np.zeros(S) if z_mean is None else z_mean, f64)
+        self.z_std = np.ascontiguousarray(np.ones(S) if z_std is None else z_std, f64)
+        self.R, self.L, self.S = self.seg_W.shape[0], self.lda.shape[0], S
+        assert self.seg_W.shape == (self.R, 2 * self.P) and self.seg_bias.shape == (self.R,)
+        assert self.lda.shape[1] in (self.R, self.R + 1) and self.enrolled.shape[1] == self.R
+
+    def with_enrolled(self, enrolled, z_mean=None, z_std=None):
+        return XvectorSystem(self.D, self.layers, self.seg_W, self.seg_bias, self.mean_vec, self.lda, self.plda_mean,
+                             self.plda_transform, self.plda_psi, enrolled, z_mean, z_std)
+
+    def to_arrays(self):
+        """The named arrays of xvector.npz (from_arrays reads them back)."""
+        out = {"D": np.int64(self.D), "n_layers": np.int64(len(self.layers)), "seg_W": self.seg_W, "seg_bias": self.seg_bias}
+        for l, ly in enumerate(self.layers):
+            out["ctx%d" % l] = np.asarray(ly["ctx"], np.int64)
+            for k in ("W", "bias", "bn_scale", "bn_offset"):
+                out["%s%d" % (k, l)] = ly[k]
+        for k in XV_BACKEND:
+            out[k] = getattr(self, k)
+        return out
+
+    @staticmethod
+    def from_arrays(a):
+        layers = [{"ctx": a["ctx%d" % l], "W": a["W%d" % l], "bias": a["bias%d" % l], "bn_scale": a["bn_scale%d" % l],
+                   "bn_offset": a["bn_offset%d" % l]} for l in range(int(a["n_layers"]))]
+        return XvectorSystem(int(a["D"]), layers, a["seg_W"], a["seg_bias"], *[a[k] for k in XV_BACKEND])
+
+    def save(self, path):
+        np.savez(path, **self.to_arrays())
+
+    @staticmethod
+    def load(path):
+        with np.load(path) as a:
+            return XvectorSystem.from_arrays(a)
+
+
+def synthetic_xvector_system(D, hidden=512, pool=1500, R=512, L=150, n_speakers=1, seed=4001, contexts=STOCK_XV_CONTEXTS):
+    """The stock five-layer TDNN of Kaldi's x-vector recipes -- contexts {-2..2}, {-2,0,2}, {-3,0,3}, {0}, {0}, widths
+    hidden x 4 then pool -- with He-scaled weights (std sqrt(2 / fan_in)), small biases and batchnorm scales near one, so
+    that activations neither die nor blow up; the segment affine Xavier-scaled; the back end as synthetic_ivector_system's
+    (mean.vec 0, LDA the first L rows of a random orthogonal R x R, PLDA psi_i = 8 * 0.97^i).  Enrolled embeddings ~ N(0, I)
+    (replace them with engine-extracted ones via with_enrolled())."""
+    rng = np.random.default_rng(seed)
+    layers, din = [], D
+    for l, ctx in enumerate(contexts):
+        dout = pool if l == len(contexts) - 1 else hidden
+        K = len(ctx) * din
+        layers.append({"ctx": ctx, "W": rng.normal(0.0, np.sqrt(2.0 / K), size=(dout, K)),
+                       "bias": rng.normal(0.0, 0.1, size=dout), "bn_scale": rng.uniform(0.8, 1.25, size=dout),
+                       "bn_offset": rng.normal(0.0, 0.1, size=dout)})
+        din = dout
+    seg_W = rng.normal(0.0, np.sqrt(1.0 / (2 * din)), size=(R, 2 * din))
+    seg_bias = rng.normal(0.0, 0.1, size=R)
+    Q, _ = np.linalg.qr(rng.normal(size=(R, R)))
+    psi = 8.0 * 0.97 ** np.arange(L)
+    return XvectorSystem(D, layers, seg_W, seg_bias, np.zeros(R), Q[:L], np.zeros(L), np.eye(L), psi,
+                         rng.normal(size=(n_speakers, R)))

@@ -514,3 +514,76 @@ class iv_SV(_IvSystem):
 
     def make_decisions_value(self, score):
         return -1 if score < self.threshold else 1
+
+
+# ------------------------------------------------------------------ x-vector / PLDA
+class _XvSetup(object):
+    """The x-vector classes: the i-vector classes' surface (score, make_decisions, engine, spk_ids, threshold) and decision
+    rules over a TDNN embedding extractor (models.XvectorSystem; include/fakebob_hip.h, "x-vector").  The model comes as
+    `system=` or from pre_model_dir/xvector.npz (XvectorSystem.save's named arrays; a Kaldi nnet3 reader is not part of this
+    package).  A model_list entry is (spk_id, utt_id, enrolment embedding -- an array of R numbers or a Kaldi vector
+    location --, z-norm mean, z-norm std).  Every defence keyword of the other classes except feature_compression: k-means
+    over the frames discards the order a TDNN reads, and the engine refuses the pair by name."""
+
+    def _setup(self, group_id, model_list, pre_model_dir, engine, system, text_scores=None, compress_feats=None, mfcc_f32=None,
+               dither=None, input_transform=None, eot_size=None, companions=None, air_channel=None, codec=None):
+        from .models import XvectorSystem
+        from .kaldi_io import read_ivector_location
+        self.pre_model_dir = os.path.abspath(pre_model_dir)
+        self.group_id = os.path.abspath(group_id)
+        self.n_speakers = len(model_list)
+        order = list(range(len(model_list)))
+        if len(model_list) > 1:   # sorted by spk_id string, as the i-vector wrappers do
+            order = sorted(order, key=lambda i: model_list[i][0])
+        ml = [model_list[i] for i in order]
+        self.spk_ids, self.utt_ids = [m[0] for m in ml], [m[1] for m in ml]
+        self.identity_locations = [m[2] for m in ml]
+        self.z_norm_means = np.array([m[3] for m in ml], np.float64)
+        self.z_norm_stds = np.array([m[4] for m in ml], np.float64)
+        self._engine = engine if engine is not None else Engine(default_device())
+        enrolled = np.stack([np.asarray(x, np.float32).reshape(-1) if not isinstance(x, str) else read_ivector_location(x)
+                             for x in self.identity_locations])
+        if system is None:
+            over = _conf_overrides(self.pre_model_dir, dither)
+            system = XvectorSystem.load(os.path.join(self.pre_model_dir, "xvector.npz"))
+        else:
+            over = _conf_overrides(None, dither)
+        _apply_frontend(self._engine, over, text_scores, compress_feats, mfcc_f32, self.PIPELINE)
+        system = system.with_enrolled(enrolled, self.z_norm_means, self.z_norm_stds)
+        _apply_input_transform(self._engine, input_transform)
+        _apply_air_channel(self._engine, air_channel)
+        _apply_codec(self._engine, codec)
+        apply_eot(self._engine, eot_size)
+        apply_companions(self._engine, companions)
+        self._engine.load_xvector(system, self.task)
+        self.system = system
+
+
+class xv_OSI(_XvSetup, iv_OSI):
+    def __init__(self, group_id, model_list, pre_model_dir="pre-models", threshold=0.0, engine=None, system=None,
+                 text_scores=None, compress_feats=None, mfcc_f32=None, dither=None,
+                 input_transform=None, eot_size=None, companions=None, air_channel=None, codec=None):
+        self.threshold = threshold
+        self._setup(group_id, model_list, pre_model_dir, engine, system, text_scores, compress_feats, mfcc_f32, dither,
+                    input_transform, eot_size, companions, air_channel, codec)
+
+
+class xv_CSI(_XvSetup, iv_CSI):
+    def __init__(self, group_id, model_list, pre_model_dir="pre-models", engine=None, system=None, text_scores=None,
+                 compress_feats=None, mfcc_f32=None, dither=None,
+                 input_transform=None, eot_size=None, companions=None, air_channel=None, codec=None):
+        self._setup(group_id, model_list, pre_model_dir, engine, system, text_scores, compress_feats, mfcc_f32, dither,
+                    input_transform, eot_size, companions, air_channel, codec)
+
+
+class xv_SV(_XvSetup, iv_SV):
+    def __init__(self, spk_id, model, pre_model_dir="pre-models", threshold=0.0, engine=None, system=None,
+                 text_scores=None, compress_feats=None, mfcc_f32=None, dither=None,
+                 input_transform=None, eot_size=None, companions=None, air_channel=None, codec=None):
+        self.threshold = threshold
+        self._setup(spk_id, [model], pre_model_dir, engine, system, text_scores, compress_feats, mfcc_f32, dither,
+                    input_transform, eot_size, companions, air_channel, codec)
+        self.spk_id = self.group_id
+        self.utt_id = model[1]
+        self.identity_location = model[2]
+        self.z_norm_mean, self.z_norm_std = model[3], model[4]

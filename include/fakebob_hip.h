@@ -1036,6 +1036,74 @@ typedef struct {
  * enrolled speakers per engine", refused before anything is touched: the system loaded before stays loaded. */
 int fb_load_ivector(fb_engine *e, const fb_ivector_system *sys, int task);
 
+/* ---- x-vector (TDNN) system ----------------------------------------------------------------------------
+ * The Kaldi x-vector recogniser (egs/sre16/v2, egs/voxceleb/v2): frame-level TDNN layers over the voiced, normalised
+ * feature rows the front end writes, statistics pooling, one segment-level affine whose output is the embedding, then
+ * the back end of the i-vector system (mean subtraction, LDA, length normalisation, PLDA, z-norm).  The engine's system
+ * kind 2; scored by fb_score_*, attacked by fb_get_grad, fb_attack, fb_estimate_threshold, fb_attack_pso,
+ * fb_attack_kenansville and fb_attack_hsj; every defence in front of the front end, dither, fb_set_eot,
+ * fb_set_companions and fb_set_play_offset apply as they do to the other two kinds.
+ *
+ * Function, for an utterance with T >= 1 voiced rows x[0 .. T):
+ *   frame layer   h_out[t] = bn_scale * max(W . splice(h_in, t) + bias, 0) + bn_offset   (Kaldi's relu-batchnorm-layer,
+ *                 the batchnorm folded into a scale and an offset per channel).  splice(h_in, t) concatenates
+ *                 h_in[clamp(t + ctx[j], 0, T - 1)] for ascending j: the utterance's own edge rows are replicated, never
+ *                 a neighbour's of the batch, so every layer keeps T rows and a one-frame utterance has an embedding.
+ *                 (Kaldi's nnet3-xvector-compute drops the edge frames that lack their full context instead; a model is
+ *                 scored here on T rows where Kaldi pools T - (left + right context) of them.)
+ *   pooling       per channel of the last layer: mean and sqrt(max(E[h^2] - mean^2, 1e-10)) over the T rows, float64,
+ *                 in an order that depends on T alone.
+ *   embedding     seg_W . [mean; std] + seg_bias, float64, fixed order.  No ReLU behind it: Kaldi extracts at the affine.
+ *   back end      the i-vector system's, unchanged, on the embedding rounded to float32 (Kaldi stores x-vectors, like
+ *                 i-vectors, as float vectors) minus mean_vec.
+ * An utterance without a voiced frame is FB_E_NO_VOICED.
+ *
+ * Arithmetic of the frame layers: values are float32; every product is formed to at least 22 bits (each operand as two
+ * f16 terms under a power of two of its own -- one per layer for the weights, chosen at load time, one per row for the
+ * spliced input, so operands of any finite magnitude keep their bits --, three of the four partial products on the matrix
+ * cores) and accumulated in float32 in an order that depends on the layer's shape alone.  bias, ReLU, scale and offset
+ * are float32 operations, each rounded.  Hence
+ *   (a) a run repeats bit for bit, and
+ *   (b) the embedding of a row does not depend on the batch it is scored in: not on B, its position, or its neighbours'
+ *       lengths.
+ *
+ * Limits: D == the front end's feature dimension; 1 <= n_layers <= 8; 1 <= n_ctx <= 5 with ascending offsets,
+ * |offset| <= 8; every dout in 1 .. 2048 (a multiple of 32 wastes no lane; Kaldi's stock pooling width, 1500, is none) and
+ * n_ctx * din whatever it is; R a multiple of 32 in 32 .. 2048; L <= 512; S <= 60
+ * (SV: S == 1); lda_cols R or R + 1.  Anything else is FB_E_ARG by name and the system loaded before stays loaded.
+ * Refused by name ("not in this version") while an x-vector system is loaded: every white-box entry (fb_get_grad_wb*,
+ * fb_attack_wb, fb_attack_cw2, fb_attack_psy) whatever the fb_set_wb_* switches say, fb_set_feature_compression with
+ * iters > 0 (k-means discards the frame order a TDNN reads; fb_load_xvector is refused likewise while it is on) and
+ * fb_gmm_acc_stats.  fb_last_ivectors returns the embeddings (B x R, float64) of the batch scored last. */
+#define FB_XV_MAX_LAYERS 8
+#define FB_XV_MAX_CTX 5
+typedef struct {
+  int dout;                         /* output channels */
+  int n_ctx;                        /* 1 .. 5 */
+  int ctx[FB_XV_MAX_CTX];           /* ascending frame offsets */
+  const float *W;                   /* [dout][n_ctx * din]: Kaldi's affine layout, offsets-major along the columns;
+                                       din = D for layer 0, else the previous layer's dout */
+  const float *bias;                /* [dout] */
+  const float *bn_scale, *bn_offset; /* [dout] */
+} fb_xvector_layer;
+typedef struct {
+  int D;                            /* feature dim */
+  int n_layers;                     /* frame-level layers */
+  fb_xvector_layer layers[FB_XV_MAX_LAYERS];
+  const float *seg_W;               /* [R][2 * P], P = the last frame-level dout: columns [mean; std] */
+  const float *seg_bias;            /* [R] */
+  int R, L, S;                      /* embedding dim, LDA dim, speakers */
+  int lda_cols;                     /* R, or R+1 when transform.mat carries an offset column */
+  const float *mean_vec;            /* [R] */
+  const float *lda;                 /* [L][lda_cols] */
+  const double *plda_mean;          /* [L] */
+  const double *plda_transform;     /* [L][L] */
+  const double *plda_psi;           /* [L] */
+  const float *enrolled;            /* [S][R] enrolment embeddings */
+  const double *z_mean, *z_std;     /* [S] */
+} fb_xvector_system;
+int fb_load_xvector(fb_engine *e, const fb_xvector_system *sys, int task);
+
 /* How raw per-model log-likelihoods become system scores:
  *  OSI / SV: model 0 is the UBM, S = M-1, score = raw[1+s] - raw[0]
  *  CSI     : S = M, score = (raw - z_mean) / z_std                          */
@@ -1242,7 +1310,8 @@ int fb_stats(fb_engine *e, int64_t *scored_utts, int64_t *scored_frames,
  * MAP mean update itself (gmm-global-est-map.cc:62-92, `MapDiagGmmUpdate`, means only) is a C*D
  * element-wise formula done by the host mirror (fakebob_amd/enroll.py).
  * fb_last_ivectors returns the i-vectors (B x R, float64, before mean subtraction / LDA) of the batch scored
- * last with an i-vector system: the enrolment identity of ivector_PLDA (build_spk_models.py:104-150). */
+ * last with an i-vector system: the enrolment identity of ivector_PLDA (build_spk_models.py:104-150); with an x-vector
+ * system the embeddings (B x R, float64). */
 int fb_gmm_acc_stats(fb_engine *e, const int16_t *wav, int64_t n, double *occ, double *F, int *tv_out);
 int fb_last_ivectors(fb_engine *e, int B, double *ivecs);
 

@@ -323,6 +323,23 @@ int fb_debug_prepare_gmm(int M, int C, int D, const float *gconsts, const float 
                          fb_gmm_plan *plan, int *perm, const char *buffer, int pass, void *out, int64_t cap, int64_t *size);
 int fb_debug_prepare_ivector(const fb_ivector_system *sy, const char *buffer, void *out, int64_t cap, int64_t *size);
 int fb_debug_prepare_frontend(const fb_frontend_cfg *c, const char *buffer, void *out, int64_t cap, int64_t *size);
+/* fb_debug_prepare_xvector (fb_load_xvector's checks and images): "w<l>" -- layer l's weights as k_xv_affine reads them:
+ * uint16 f16 bits [ceil(dout / 32)][ceil(n_ctx * din / 16)][2 terms][64 lanes][8], lane 32 h + c of K step s holding
+ * W[32 tile + c][16 s + 8 h .. + 7] * 2^-kw (zero past n_ctx * din and past dout), term 0 = f16(v), term 1 = f16(v - term 0) --,
+ * "kw" (int32[n_layers], the layers' powers of two), "segT" (float64 [2 P][R], seg_W transposed), "backend" and
+ * "backend_offsets" as for an i-vector system. */
+int fb_debug_prepare_xvector(const fb_xvector_system *sy, const char *buffer, void *out, int64_t cap, int64_t *size);
+
+/* The x-vector chain of the loaded system on feature rows handed in as they are (no front end): feats[row_off[B]][D]
+ * float32, row_off[B + 1] the utterances' first rows.  layer < n_layers: that frame layer's output, float32
+ * [rows][dout]; layer == n_layers: the pooled statistics, float64 [B][2 P]; layer == n_layers + 1: the embeddings,
+ * float64 [B][R]. */
+int fb_debug_xv_embed(fb_engine *e, const float *feats, const int *row_off, int B, int layer, void *out);
+/* Benchmark hook: the launches of that chain one by one, each `reps` times between device events after one launch to warm
+ * up, milliseconds per launch: ms_rowmax[l] and ms_affine[l] (k_xv_rowmax, k_xv_affine of frame layer l), ms_tail[3]
+ * (k_xv_pool, k_xv_segment, k_iv_backend). */
+int fb_bench_xvector(fb_engine *e, const float *feats, const int *row_off, int B, int reps, double *ms_rowmax, double *ms_affine,
+                     double *ms_tail);
 
 /* the GMM kernel the engine scores with, on T rows of D features handed in as they are (no front-end): per-frame
  * log-likelihoods out[m * T + t] of every model (gmm-global-get-frame-likes without --average).  Lets the tests reach
