@@ -208,6 +208,7 @@ EXPORTS = [
     "fb_estimate_threshold", "fb_debug_noise", "fb_debug_quantize", "fb_debug_mfcc", "fb_debug_feats", "fb_debug_dither_noise", "fb_debug_mfcc_dither", "fb_debug_feats_dither", "fb_debug_input_transform", "fb_debug_tf_noise", "fb_debug_input_transform_eot", "fb_debug_compose", "fb_debug_air_taps", "fb_debug_air_convolve", "fb_debug_codec", "fb_debug_feature_compress", "fb_debug_feco_keys", "fb_debug_pso_init", "fb_debug_pso_step", "fb_debug_kv_analyse", "fb_debug_kv_candidates", "fb_debug_hsj_line", "fb_debug_hsj_probes", "fb_debug_hsj_dir", "fb_debug_hsj_step", "fb_debug_vote", "fb_debug_gmm_frames", "fb_debug_gmm_acc_rows", "fb_debug_gmm_feat_grad", "fb_debug_frontend_vjp", "fb_debug_defence_vjp", "fb_debug_wb_route", "fb_debug_air_conv_t", "fb_debug_air_conv_t_chunk", "fb_debug_wb_air_route", "fb_debug_feature_compress_vjp", "fb_debug_wb_feco_route", "fb_debug_wb_feco_state", "fb_debug_wb_compose_t", "fb_debug_wb_universal_route", "fb_debug_iv_backend_grad", "fb_debug_iv_feat_grad", "fb_debug_iv_active", "fb_debug_iv_gselect", "fb_debug_frontend_route", "fb_debug_launch_shape", "fb_stats", "fb_gmm_acc_stats", "fb_last_ivectors", "fb_gmm_kernel_mode", "fb_gmm_kernel_variant", "fb_gmm_delta_tiles", "fb_gmm_delta_tiles_f6", "fb_set_fused_chain",
     "fb_debug_prepare_gmm", "fb_debug_prepare_ivector", "fb_debug_prepare_frontend",
     "fb_load_xvector", "fb_debug_prepare_xvector", "fb_debug_xv_embed", "fb_bench_xvector",
+    "fb_set_wb_xvector", "fb_debug_xv_backward", "fb_debug_xv_masks", "fb_debug_wb_xv_route", "fb_bench_xv_backward",
     "fb_bench_gmm_kernel", "fb_bench_kv_kernels", "fb_bench_hsj_kernels", "fb_bench_vote", "fb_bench_foreign_rows", "fb_bench_nes", "fb_bench_nes_state",
 ]
 

@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 OBJDIR = os.path.join(HERE, "build")
 LIB = os.path.join(LIBDIR, "libfakebob_hip.so")
-SOURCES = ["nes_kernels.hip", "whitebox_kernels.hip", "whitebox_bpda_kernels.hip", "whitebox_iv_kernels.hip", "whitebox_air_kernels.hip", "whitebox_universal_kernels.hip", "play_offset_kernels.hip", "cw2_kernels.hip", "psy_kernels.hip", "pso_kernels.hip", "kenansville_kernels.hip", "hsj_kernels.hip", "vote_kernel.hip", "foreign_rows_kernel.hip", "input_transform_kernel.hip", "air_channel_kernel.hip", "codec_kernel.hip", "feature_compress_kernel.hip", "frontend_kernels.hip", "frontend_f32_kernels.hip", "gmm_kernels.hip", "gmm_wide_kernel.hip", "ivector_kernels.hip", "ivector_solve.hip", "xvector_kernels.hip",
+SOURCES = ["nes_kernels.hip", "whitebox_kernels.hip", "whitebox_bpda_kernels.hip", "whitebox_iv_kernels.hip", "whitebox_xv_kernels.hip", "whitebox_air_kernels.hip", "whitebox_universal_kernels.hip", "play_offset_kernels.hip", "cw2_kernels.hip", "psy_kernels.hip", "pso_kernels.hip", "kenansville_kernels.hip", "hsj_kernels.hip", "vote_kernel.hip", "foreign_rows_kernel.hip", "input_transform_kernel.hip", "air_channel_kernel.hip", "codec_kernel.hip", "feature_compress_kernel.hip", "frontend_kernels.hip", "frontend_f32_kernels.hip", "gmm_kernels.hip", "gmm_wide_kernel.hip", "ivector_kernels.hip", "ivector_solve.hip", "xvector_kernels.hip",
            "fb_engine.hip",
            # host-only C++ (no HIP header, no HIP call): the tables the loaders upload (csrc/fb_prepare.h)
            "fb_prepare_gmm.cpp", "fb_prepare_ivector.cpp", "fb_prepare_xvector.cpp", "fb_prepare_frontend.cpp"]

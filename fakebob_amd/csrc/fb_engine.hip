@@ -160,6 +160,15 @@ struct fb_engine {
   FbXvDev xv;
   DevBuf xv_w[FB_XV_MAX_LAYERS], xv_par, xv_seg;   // weight images; bias / scale / offset of every layer; segT + seg_bias
   DevBuf xv_rowinfo, xv_amax, xv_act[2], xv_stats;
+  // white-box gradients through the TDNN (fb_set_wb_xvector)
+  int wb_xvector = 0;                  // the switch: 0 (as created) refuses an x-vector system, as before it existed
+  DevBuf xv_mask[FB_XV_MAX_LAYERS];    // the ReLU decisions of the batch scored last with FbScoreCall::keep_xv_mask: [row][dout] bytes
+  int xv_mask_B = 0;                   // ... its utterances (0: none kept); its rows are row_off[B] of that call
+  DevBuf xv_mask_rows;                 // ... that count, copied on the device behind the forward (row_off is reused)
+  DevBuf wb_xv_ebar, wb_xv_sbar;       // cotangents on the embeddings [r][R] and on the statistics [r][2 P], float64
+  DevBuf wb_xv_y[2], wb_xv_z, wb_xv_G, wb_xv_amax;   // float32: cotangents between layers (ping-pong), zbar, G [rows][K], max |zbar| per row
+  DevBuf wb_xv_g;                      // float64 cotangent on the feature rows: utterance b's row t at (b * T + t) * D
+  int wb_xv_route[FB_WB_XV_ROUTE_N] = {};   // launches of the TDNN backward the last call enqueued (fb_debug_wb_xv_route)
   FbIvDev iv;
   DevBuf iv_fg, iv_fg64, iv_fgL, iv_tri, iv_sim, iv_u, iv_backend;
   DevBuf iv_ll, iv_sel, iv_post, iv_gamma, iv_X, iv_linp, iv_quad, iv_A, iv_linv, iv_ivec, iv_fail, iv_active, iv_bws, iv_pairs, iv_llf;
@@ -868,6 +877,7 @@ struct FbScoreCall {
   bool keep_iv_quad = false;     // i-vector systems: row 0 of quad as the contraction left it is copied to e->wb_iv_quad (white box)
   int keep_iv_quad_rows = 1;     // ... rows 0 .. this - 1: every replica's under fb_set_wb_universal
   bool keep_air_sat = false;     // an air channel: k_air_conv also writes its saturation bytes to e->wb_air_sat (white box)
+  bool keep_xv_mask = false;     // x-vector systems: k_xv_affine also writes every layer's ReLU decisions to e->xv_mask (white box)
   bool keep_feco = false;        // feature compression: k_feature_compress also writes its final labels, counts and k's to e->wb_feco_* (white box)
   int64_t play = 0;              // > 0 (fb_set_play_offset): k_play_compose writes the K * eot replicas, each under its own offset in 0 .. play
   int replicas() const { return K * eot; }
@@ -1129,7 +1139,8 @@ static int feature_compress(fb_engine *e, const FbScoreCall &call, int B, int to
 // The x-vector chain (xvector_kernels.hip) on e->feats / e->row_off: frame layers 0 .. min(upto, n_layers - 1), then -- with
 // upto >= n_layers -- pooling into xv_stats and, with upto > n_layers, the segment affine into iv_ivec.  *last (nullable): the
 // buffer that holds the last frame layer run.  Purely asynchronous.
-static int run_xvector(fb_engine *e, int B, int total_frames, int upto, const float **last) {
+// keep_mask: every layer run also leaves its ReLU decisions in e->xv_mask[l] (the white-box backward's)
+static int run_xvector(fb_engine *e, int B, int total_frames, int upto, const float **last, bool keep_mask = false) {
   const FbXvDev &xv = e->xv;
   hipStream_t s = e->stream;
   const size_t rows = (size_t)(total_frames > 0 ? total_frames : 1);
@@ -1138,13 +1149,22 @@ static int run_xvector(fb_engine *e, int B, int total_frames, int upto, const fl
   for (int i = 0; i < 2; ++i) FBCHK(e->xv_act[i].ensure(sizeof(float) * rows * (size_t)xv.max_width));
   FBCHK(e->xv_stats.ensure(sizeof(double) * (size_t)B * 2 * xv.P));
   FBCHK(e->iv_ivec.ensure(sizeof(double) * (size_t)B * xv.R));
+  if (keep_mask) {
+    for (int l = 0; l < xv.n_layers; ++l) FBCHK(e->xv_mask[l].ensure(rows * (size_t)xv.layer[l].dout));
+    FBCHK(e->xv_mask_rows.ensure(sizeof(int)));
+  }
   const int *n_rows = e->row_off.as<int>() + B;
+  if (keep_mask) {
+    HIPCHK(hipMemcpyAsync(e->xv_mask_rows.p, n_rows, sizeof(int), hipMemcpyDeviceToDevice, s));
+    e->xv_mask_B = B;
+  }
   fb_launch_xv_rowinfo(s, e->row_off.as<int>(), B, e->xv_rowinfo.as<int2>());
   const float *in = e->feats.as<float>();
   for (int l = 0; l < xv.n_layers && l <= upto; ++l) {
     float *out = e->xv_act[l & 1].as<float>();
     fb_launch_xv_rowmax(s, in, xv.layer[l].din, n_rows, total_frames, e->xv_amax.as<float>());
-    fb_launch_xv_affine(s, xv.layer[l], in, e->xv_amax.as<float>(), e->xv_rowinfo.as<int2>(), n_rows, total_frames, out);
+    fb_launch_xv_affine(s, xv.layer[l], in, e->xv_amax.as<float>(), e->xv_rowinfo.as<int2>(), n_rows, total_frames, out,
+                        keep_mask ? e->xv_mask[l].as<unsigned char>() : nullptr);
     in = out;
   }
   if (last) *last = in;
@@ -1197,7 +1217,7 @@ static int run_scoring(fb_engine *e, FbScoreCall &call, int B, int total_frames)
     // k_loss / k_loss_eot / k_vote follows (the i-vector branch's "split" tail)
     FB_DBG_SYNC(e, "front-end");
     FBCHK(time_begin(e));
-    FBCHK(run_xvector(e, B, total_frames, e->xv.n_layers + 1, nullptr));
+    FBCHK(run_xvector(e, B, total_frames, e->xv.n_layers + 1, nullptr, call.keep_xv_mask));
     FBCHK(time_end(e));
     fb_launch_iv_backend(s, e->iv, e->iv_ivec.as<double>(), B, e->raw.as<double>());
     FB_DBG_SYNC(e, "backend");
@@ -1590,7 +1610,7 @@ extern "C" int fb_load_xvector(fb_engine *e, const fb_xvector_system *sy, int ta
   // ---- ensure
   size_t n_par = 0;
   for (int l = 0; l < p.n_layers; ++l) {
-    FBCHK(e->xv_w[l].ensure(sizeof(uint16_t) * p.layer[l].w.size()));
+    FBCHK(e->xv_w[l].ensure(sizeof(uint16_t) * (p.layer[l].w.size() + p.layer[l].wt.size())));   // the image, then the transposed one
     n_par += 3 * (size_t)p.layer[l].dout;
   }
   FBCHK(e->xv_par.ensure(sizeof(float) * n_par));
@@ -1615,6 +1635,9 @@ extern "C" int fb_load_xvector(fb_engine *e, const fb_xvector_system *sy, int ta
     for (int j = 0; j < FB_XV_MAX_CTX; ++j) d.ctx[j] = q.ctx[j];
     d.K = q.K; d.n_steps = q.n_steps; d.kw = q.kw;
     d.w = e->xv_w[l].as<unsigned short>();
+    HIPCHK(hipMemcpy(e->xv_w[l].as<unsigned short>() + q.w.size(), q.wt.data(), sizeof(uint16_t) * q.wt.size(), hipMemcpyHostToDevice));
+    d.nt_steps = q.nt_steps; d.kwt = q.kwt;
+    d.wt = e->xv_w[l].as<unsigned short>() + q.w.size();
     d.bias = par; d.scale = par + q.dout; d.offset = par + 2 * q.dout;
     par += 3 * (size_t)q.dout;
   }
@@ -1639,6 +1662,7 @@ extern "C" int fb_load_xvector(fb_engine *e, const fb_xvector_system *sy, int ta
   e->kind = 2;
   e->n_out = S;
   e->task = task;
+  e->xv_mask_B = 0;
   return FB_OK;
 }
 
@@ -1709,6 +1733,13 @@ extern "C" int fb_debug_prepare_xvector(const fb_xvector_system *sy, const char 
     for (int l = 0; l < p.n_layers; ++l) kw.push_back(p.layer[l].kw);
     return give_vector(buffer, kw, out, cap, size);
   }
+  if (buffer[0] == 'w' && buffer[1] == 't' && buffer[2] >= '0' && buffer[2] < '0' + p.n_layers && buffer[3] == 0)
+    return give_vector(buffer, p.layer[buffer[2] - '0'].wt, out, cap, size);
+  if (strcmp(buffer, "kwt") == 0) {
+    std::vector<int32_t> kwt;
+    for (int l = 0; l < p.n_layers; ++l) kwt.push_back(p.layer[l].kwt);
+    return give_vector(buffer, kwt, out, cap, size);
+  }
   if (strcmp(buffer, "segT") == 0) return give_vector(buffer, p.segT, out, cap, size);
   if (strcmp(buffer, "backend") == 0) return give_vector(buffer, p.be.backend, out, cap, size);
   if (strcmp(buffer, "backend_offsets") == 0) {
@@ -1716,7 +1747,8 @@ extern "C" int fb_debug_prepare_xvector(const fb_xvector_system *sy, const char 
                                     (int64_t)p.be.o_psi, (int64_t)p.be.o_tr};
     return give_vector(buffer, o, out, cap, size);
   }
-  return fb_fail(FB_E_ARG, "no x-vector buffer '%s' (w0 .. w%d, kw, segT, backend, backend_offsets)", buffer, p.n_layers - 1);
+  return fb_fail(FB_E_ARG, "no x-vector buffer '%s' (w0 .. w%d, kw, wt0 .. wt%d, kwt, segT, backend, backend_offsets)", buffer, p.n_layers - 1,
+                 p.n_layers - 1);
 }
 
 // Test hook: the x-vector chain on rows handed in (fakebob_hip_test.h)
@@ -2692,19 +2724,33 @@ extern "C" int fb_attack_dev(fb_engine *e, const fb_nes_params *p, int S, const 
 // ------------------------------------------------- white-box gradients: fb_get_grad_wb / fb_attack_wb
 // The analytic gradient of the loss with respect to the samples ("white-box gradients" in fakebob_hip.h): GMM-UBM systems on
 // an undefended victim; with fb_set_wb_bpda(e, 1) through an input-transform chain, a codec and EOT replicas as well
-// (BPDA / EOT, the same contract); with fb_set_wb_ivector(e, 1) i-vector-PLDA systems too; with fb_set_wb_air(e, 1) through an
+// (BPDA / EOT, the same contract); with fb_set_wb_ivector(e, 1) i-vector-PLDA systems too; with fb_set_wb_xvector(e, 1) x-vector
+// systems (undefended or under fb_set_wb_bpda; never with a channel, dither, companions or a play offset); with fb_set_wb_air(e, 1) through an
 // over-the-air channel; with fb_set_wb_frontend(e, 1) through feature compression and dither; with fb_set_wb_universal(e, 1) over
 // the companions of a universal perturbation.  Everything else is refused by name.
 static int wb_check(fb_engine *e, const fb_nes_params *p, const double *audio, int64_t N, fb_nes_params *q) {
   if (!e || !p || !audio) return fb_fail(FB_E_ARG, "null argument");
   if (!e->have_gmm) return fb_fail(FB_E_STATE, "no model loaded");
-  if (e->kind == 2)
+  if (e->kind == 2 && !e->wb_xvector)
     return fb_fail(FB_E_STATE, "white-box gradients: an x-vector system is loaded (no gradient through the TDNN: not in this version)");
-  if (e->kind != 0 && !e->wb_ivector)
+  if (e->kind == 2) {
+    // fb_set_wb_xvector: undefended, or with fb_set_wb_bpda through a chain, a codec and EOT replicas (the generic checks below);
+    // these four stay refused whatever their own switches say
+    if (e->air.L > 0)
+      return fb_fail(FB_E_STATE, "white-box gradients: an air channel is set (fb_set_air_channel: not through an x-vector system in this version: clear it)");
+    if (e->cfg.dither > 0.0)
+      return fb_fail(FB_E_STATE, "white-box gradients: dither %g > 0 (not through an x-vector system in this version)", e->cfg.dither);
+    if (e->comp_K1 > 0)
+      return fb_fail(FB_E_STATE, "white-box gradients: companions are set (fb_set_companions: not through an x-vector system in this version: clear them)");
+    if (e->play_S > 0)
+      return fb_fail(FB_E_STATE, "white-box gradients: a play offset is set (fb_set_play_offset(%lld): not through an x-vector system in this version)",
+                     (long long)e->play_S);
+  }
+  if (e->kind == 1 && !e->wb_ivector)
     return fb_fail(FB_E_STATE, "white-box gradients: an i-vector system is loaded (GMM-UBM systems only in this version)");
   // (the forward keeps the selection, posteriors and statistics of ONE row for the backward, not those of r replicas)
   // (... unless fb_set_wb_universal: the forward then keeps quad of every replica, and sel / post / the i-vectors are per row anyway)
-  if (e->kind != 0 && e->eot > 1 && !e->wb_universal)
+  if (e->kind == 1 && e->eot > 1 && !e->wb_universal)
     return fb_fail(FB_E_STATE, "white-box gradients: fb_set_eot(%d) is in force on an i-vector system (per-replica i-vector state is not kept: set 1)", e->eot);
   if (e->eot > 1 && !e->wb_bpda) return fb_fail(FB_E_STATE, "white-box gradients: fb_set_eot(%d) is in force (set 1)", e->eot);
   // (the universal perturbation has the fifth switch, fb_set_wb_universal: refused with the other four on as well)
@@ -2728,6 +2774,53 @@ static int wb_check(fb_engine *e, const fb_nes_params *p, const double *audio, i
   q->samples_per_draw = 0;
   q->sigma = 1.0;
   return check_params(e, q, N);
+}
+
+// the TDNN backward's workspace for B utterances of `rows` rows in all; cap64: rows per utterance in e->wb_xv_g
+static int wb_xv_ensure(fb_engine *e, int B, size_t rows, int cap64) {
+  const FbXvDev &xv = e->xv;
+  if (rows < 1) rows = 1;
+  size_t maxK = 1;
+  for (int l = 0; l < xv.n_layers; ++l) maxK = std::max(maxK, (size_t)xv.layer[l].K);
+  FBCHK(e->wb_xv_ebar.ensure(sizeof(double) * (size_t)B * xv.R));
+  FBCHK(e->wb_xv_sbar.ensure(sizeof(double) * (size_t)B * 2 * xv.P));
+  for (int i = 0; i < 2; ++i) FBCHK(e->wb_xv_y[i].ensure(sizeof(float) * rows * (size_t)xv.max_width));
+  FBCHK(e->wb_xv_z.ensure(sizeof(float) * rows * (size_t)xv.max_width));
+  FBCHK(e->wb_xv_G.ensure(sizeof(float) * rows * maxK));
+  FBCHK(e->wb_xv_amax.ensure(sizeof(float) * rows));
+  FBCHK(e->wb_xv_g.ensure(sizeof(double) * (size_t)B * (size_t)(cap64 > 0 ? cap64 : 1) * xv.D));
+  return FB_OK;
+}
+// The TDNN's backward over the whole batch the forward just scored with its masks kept (B utterances, at most rows_cap rows;
+// e->row_off / e->xv_rowinfo / e->xv_stats / the last layer's output as the forward left them): from the cotangents
+// e->wb_xv_ebar [B][R] on the embeddings down to stage `down_to` (fb_debug_xv_backward's numbering; 0: the feature rows, float64
+// in e->wb_xv_g with cap64 rows per utterance).  *last32 (nullable): where a stage in 1 .. n_layers left its float32 cotangent.
+// wb_xv_ensure has sized the buffers.
+static void wb_xv_backward(fb_engine *e, int B, int rows_cap, int down_to, int cap64, const int *stop, const float **last32) {
+  const FbXvDev &xv = e->xv;
+  hipStream_t s = e->stream;
+  const int *row_off = e->row_off.as<int>(), *n_rows = row_off + B;
+  const int2 *rowinfo = e->xv_rowinfo.as<int2>();
+  fb_launch_wb_xv_segment_t(s, xv, e->wb_xv_ebar.as<double>(), B, e->wb_xv_sbar.as<double>(), stop);
+  e->wb_xv_route[FB_WB_XV_ROUTE_SEGMENT_T] += 1;
+  if (down_to > xv.n_layers) return;
+  int cur = 0;
+  fb_launch_wb_xv_pool_t(s, e->xv_act[(xv.n_layers - 1) & 1].as<float>(), xv.P, row_off, B, e->xv_stats.as<double>(),
+                         e->wb_xv_sbar.as<double>(), e->wb_xv_y[cur].as<float>(), stop);
+  e->wb_xv_route[FB_WB_XV_ROUTE_POOL_T] += 1;
+  for (int l = xv.n_layers - 1; l >= down_to; --l) {
+    const FbXvLayerDev &ly = xv.layer[l];
+    fb_launch_wb_xv_act_t(s, ly, e->wb_xv_y[cur].as<float>(), e->xv_mask[l].as<unsigned char>(), n_rows, rows_cap, e->wb_xv_z.as<float>(),
+                          e->wb_xv_amax.as<float>(), stop);
+    e->wb_xv_route[FB_WB_XV_ROUTE_ACT_T] += 1;
+    fb_launch_wb_xv_affine_t(s, ly, e->wb_xv_z.as<float>(), e->wb_xv_amax.as<float>(), n_rows, rows_cap, e->wb_xv_G.as<float>(), stop);
+    e->wb_xv_route[FB_WB_XV_ROUTE_AFFINE_T] += 1;
+    fb_launch_wb_xv_unsplice(s, ly, e->wb_xv_G.as<float>(), rowinfo, row_off, B, n_rows, rows_cap, l > 0 ? e->wb_xv_y[cur ^ 1].as<float>() : nullptr,
+                             l > 0 ? nullptr : e->wb_xv_g.as<double>(), cap64, stop);
+    e->wb_xv_route[FB_WB_XV_ROUTE_UNSPLICE] += 1;
+    cur ^= 1;
+  }
+  if (last32) *last32 = e->wb_xv_y[cur].as<float>();
 }
 
 // the plain parameters on the device (once per fb_load_gmm) and the workspace of one utterance of N samples / T frames
@@ -2754,6 +2847,9 @@ static int wb_prepare(fb_engine *e, int64_t N, int T, bool need_gmm) {
       HIPCHK(hipMemsetAsync(e->wb_iv_A.p, 0, e->wb_iv_A.cap, e->stream));
       e->wb_iv_A_R = iv.R;
     }
+  } else if (need_gmm && e->kind == 2) {
+    FBCHK(e->wb_w.ensure(sizeof(double) * (size_t)e->iv.S));
+    FBCHK(wb_xv_ensure(e, nes_replicas(e), (size_t)nes_replicas(e) * (size_t)T, T));
   } else if (need_gmm) {
     const FbGmmDev &g = e->gmm;
     if (!e->wb_uploaded) {
@@ -2931,6 +3027,10 @@ static void wb_launch_air_t(fb_engine *e, int r, int64_t N, double *out, const i
 // samples and sums the slots, rho ascending, into e->grad.  On an i-vector system the forward then keeps quad of all R rows and
 // replica rho takes its own copy, i-vector and rows (k_wb_iv_ctl_rep for its weights) -- which is also what lets fb_set_eot(r > 1)
 // run there without companions.
+// With fb_set_wb_xvector on and an x-vector system loaded: the forward also keeps every layer's ReLU decisions (e->xv_mask); the
+// loop becomes two -- per replica the weights and k_wb_iv_backend_t at ITS embedding, into slot j of e->wb_xv_ebar; then ONE TDNN
+// backward over all rows of the batch (wb_xv_backward); then per replica, as for the other kinds, the front-end backward on ITS
+// slice of e->wb_xv_g, the chain's transpose and the ascending sum.
 static int wb_enqueue(fb_engine *e, const fb_nes_params *q, int64_t N, uint32_t it, bool with_dist, FbCtlDev *ctl, double *trace_dev) {
   const int *stop = ctl ? &ctl->stop : nullptr;
   // the replicas of the one row: the EOT draws, and under fb_set_wb_universal rho = u * eot + j over the K composed utterances
@@ -2949,6 +3049,8 @@ static int wb_enqueue(fb_engine *e, const fb_nes_params *q, int64_t N, uint32_t 
   call.stop = stop;
   call.keep_iv_quad = e->kind == 1;
   call.keep_iv_quad_rows = e->wb_universal ? r : 1;  // (r > 1 on an i-vector system: wb_check, only under fb_set_wb_universal)
+  const bool xvk = e->kind == 2;  // (wb_check: only under fb_set_wb_xvector; no channel, dither, companions or play offset then)
+  call.keep_xv_mask = xvk;
   const bool air = e->air.L > 0;  // (wb_check: only under fb_set_wb_air)
   call.keep_air_sat = air;
   const bool feco = e->feco_iters > 0;  // (wb_check: only under fb_set_wb_frontend, like a dither > 0)
@@ -2979,8 +3081,31 @@ static int wb_enqueue(fb_engine *e, const fb_nes_params *q, int64_t N, uint32_t 
     fb_launch_wb_compose_rows(e->stream, e->wav.as<int16_t>(), e->comp_a0.as<int16_t>(), e->comp_wav.as<int16_t>(), K, N,
                               e->wb_uni_rows.as<int16_t>(), stop);
   const int S = fb_num_speakers(e);
+  // An x-vector system: first every replica's weights and the back end's transpose at ITS embedding, into slot j of e->wb_xv_ebar;
+  // then ONE TDNN backward over all rows of the batch, as the forward ran; the loop below then takes replica j's slice of the
+  // cotangent on the feature rows through the front end and the chain.
+  if (xvk) {
+    for (int j = 0; j < r; ++j) {
+      if (rep) {
+        fb_launch_wb_iv_ctl_rep(e->stream, e->eot_sc.as<double>() + (size_t)j * S, e->scores.as<double>(), e->nes_out.as<FbNesDev>(), S, r,
+                                q->task, q->attack_type, e->zstd.as<double>(), q->threshold, q->target, q->true_label,
+                                e->wb_w.as<double>(), ctl, j == 0 ? 1 : 0, trace_dev, (int)it);
+        e->wb_route[FB_WB_ROUTE_CTL_REP] += 1;
+      } else {
+        fb_launch_wb_iv_ctl(e->stream, e->scores.as<double>(), e->nes_out.as<FbNesDev>(), S, q->task, q->attack_type,
+                            e->zstd.as<double>(), q->threshold, q->target, q->true_label, e->wb_w.as<double>(), ctl, trace_dev, (int)it);
+        e->wb_route[FB_WB_ROUTE_IV_CTL] += 1;
+      }
+      fb_launch_wb_iv_backend_t(e->stream, e->iv, e->iv_ivec.as<double>() + (size_t)j * (size_t)e->iv.R, e->wb_w.as<double>(),
+                                e->wb_xv_ebar.as<double>() + (size_t)j * (size_t)e->iv.R, stop);
+      e->wb_xv_route[FB_WB_XV_ROUTE_BACKEND_T] += 1;
+    }
+    wb_xv_backward(e, r, e->h_frame_off[r], 0, T, stop, nullptr);
+  }
   for (int j = 0; j < r; ++j) {
-    if (rep && e->kind == 1) {
+    if (xvk) {
+      // (an x-vector system's weights were formed above, replica by replica)
+    } else if (rep && e->kind == 1) {
       fb_launch_wb_iv_ctl_rep(e->stream, e->eot_sc.as<double>() + (size_t)j * S, e->scores.as<double>(), e->nes_out.as<FbNesDev>(), S, r,
                               q->task, q->attack_type, e->zstd.as<double>(), q->threshold, q->target, q->true_label,
                               e->wb_w.as<double>(), ctl, j == 0 ? 1 : 0, trace_dev, (int)it);
@@ -3000,7 +3125,9 @@ static int wb_enqueue(fb_engine *e, const fb_nes_params *q, int64_t N, uint32_t 
       e->wb_route[FB_WB_ROUTE_CTL] += 1;
     }
     // (row_off[0] = 0 and tv[0] = row_off[1]: replica 0 of an unreplicated batch is what the launch always took)
-    if (e->kind == 1 && rep) {  // replica j's own i-vector, quad, rows (under feature compression its k_j centres)
+    if (xvk) {
+      // (the one TDNN backward above left replica j's cotangent in its slice of e->wb_xv_g)
+    } else if (e->kind == 1 && rep) {  // replica j's own i-vector, quad, rows (under feature compression its k_j centres)
       wb_launch_iv_backend_t(e, e->iv_ivec.as<double>() + (size_t)j * (size_t)e->iv.R, stop);
       wb_launch_iv_backward(e, feco ? e->wb_feco_k.as<int>() + j : e->tv.as<int>() + j, T, stop, j, e->row_off.as<int>() + j);
     } else if (e->kind == 1) {
@@ -3020,7 +3147,8 @@ static int wb_enqueue(fb_engine *e, const fb_nes_params *q, int64_t N, uint32_t 
     FbRngPoint ptj = pt;
     ptj.utt0 = pt.utt0 + (uint32_t)j;   // the forward's dither draws of replicated row j
     const FbDitherKey dith = fb_dither_key(ptj, e->cfg.dither);
-    wb_launch_frontend_vjp(e, e->fe_wav, j, N, T, scale, fe_out, stop, feco ? e->wb_xbar.as<double>() : nullptr,
+    wb_launch_frontend_vjp(e, e->fe_wav, j, N, T, scale, fe_out, stop,
+                           xvk ? e->wb_xv_g.as<double>() + (size_t)j * (size_t)T * (size_t)e->fe.dim : feco ? e->wb_xbar.as<double>() : nullptr,
                            e->cfg.dither > 0.0 ? &dith : nullptr);
     e->wb_route[FB_WB_ROUTE_BACKWARD] += 1;
     if (through_chain) FBCHK(wb_launch_chain_t(e, pt, j, N, e->wb_gj.as<double>(), slot ? slot : e->grad.as<double>(), !slot && j > 0, stop, play));
@@ -3036,6 +3164,7 @@ static void wb_call_begin(fb_engine *e) {
   e->bench_it = e->nes_rec.iter = -1;
   memset(e->nes_route, 0, sizeof(e->nes_route));
   memset(e->wb_route, 0, sizeof(e->wb_route));
+  memset(e->wb_xv_route, 0, sizeof(e->wb_xv_route));
   e->wb_air_launches = 0;
   e->wb_feco_launches = 0;
   e->wb_universal_launches = 0;
@@ -3105,6 +3234,159 @@ extern "C" int fb_get_grad_wb_iter(fb_engine *e, const fb_nes_params *p, const d
 extern "C" int fb_get_grad_wb(fb_engine *e, const fb_nes_params *p, const double *audio, int64_t N, double *adver_loss,
                               double *grad, double *score0) {
   return fb_get_grad_wb_iter(e, p, audio, N, 0, adver_loss, grad, score0);
+}
+
+extern "C" int fb_set_wb_xvector(fb_engine *e, int on) {
+  if (!e) return fb_fail(FB_E_ARG, "null engine");
+  if (on != 0 && on != 1) return fb_fail(FB_E_ARG, "fb_set_wb_xvector takes 0 or 1, not %d", on);
+  e->wb_xvector = on;
+  return FB_OK;
+}
+
+extern "C" int fb_debug_wb_xv_route(fb_engine *e, int *info) {
+  if (!e || !info) return fb_fail(FB_E_ARG, "null argument");
+  for (int i = 0; i < FB_WB_XV_ROUTE_N; ++i) info[i] = e->wb_xv_route[i];
+  return FB_OK;
+}
+
+// Test hook: the x-vector chain on rows handed in with every layer's masks kept, as fb_debug_xv_embed runs it, then the TDNN
+// backward from the cotangents ebar [B][R] on the embeddings down to `stage` (fakebob_hip_test.h)
+extern "C" int fb_debug_xv_backward(fb_engine *e, const float *feats, const int *row_off, int B, const double *ebar, int stage, void *out,
+                                    int64_t cap) {
+  if (!e || !feats || !row_off || !ebar || !out || B <= 0) return fb_fail(FB_E_ARG, "bad argument");
+  if (!e->have_gmm || e->kind != 2) return fb_fail(FB_E_STATE, "load an x-vector system first");
+  const FbXvDev &xv = e->xv;
+  if (stage < 0 || stage > xv.n_layers + 1) return fb_fail(FB_E_ARG, "stage %d outside 0 .. %d", stage, xv.n_layers + 1);
+  if (row_off[0] != 0) return fb_fail(FB_E_ARG, "row_off[0] must be 0");
+  int cap64 = 1;
+  for (int b = 0; b < B; ++b) {
+    if (row_off[b + 1] < row_off[b]) return fb_fail(FB_E_ARG, "row_off must not descend");
+    cap64 = std::max(cap64, row_off[b + 1] - row_off[b]);
+  }
+  const int rows = row_off[B];
+  if (rows <= 0) return fb_fail(FB_E_ARG, "no rows");
+  // (stage n_layers: the last layer's OUTPUT, P wide; below it the INPUT of layer `stage`)
+  const size_t want = stage > xv.n_layers    ? sizeof(double) * (size_t)B * 2 * xv.P
+                      : stage == xv.n_layers ? sizeof(float) * (size_t)rows * (size_t)xv.P
+                      : stage == 0           ? sizeof(double) * (size_t)rows * xv.D
+                                             : sizeof(float) * (size_t)rows * (size_t)xv.layer[stage].din;
+  if (cap < (int64_t)want) return fb_fail(FB_E_ARG, "out holds %lld bytes, stage %d needs %lld", (long long)cap, stage, (long long)want);
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  e->cached_B = -1;
+  e->bench_it = e->nes_rec.iter = -1;
+  memset(e->wb_xv_route, 0, sizeof(e->wb_xv_route));
+  FBCHK(e->feats.ensure(sizeof(float) * (size_t)rows * xv.D));
+  FBCHK(e->row_off.ensure(sizeof(int) * (size_t)(B + 1)));
+  FBCHK(wb_xv_ensure(e, B, (size_t)rows, cap64));
+  FBCHK(h2d(e, e->feats.p, feats, sizeof(float) * (size_t)rows * xv.D));
+  FBCHK(h2d(e, e->row_off.p, row_off, sizeof(int) * (size_t)(B + 1)));
+  FBCHK(h2d(e, e->wb_xv_ebar.p, ebar, sizeof(double) * (size_t)B * xv.R));
+  FBCHK(run_xvector(e, B, rows, xv.n_layers + 1, nullptr, true));
+  const float *last32 = nullptr;
+  wb_xv_backward(e, B, rows, stage, cap64, nullptr, &last32);
+  HIPCHK(hipGetLastError());
+  if (stage > xv.n_layers) {
+    FBCHK(d2h(e, out, e->wb_xv_sbar.p, want));
+  } else if (stage > 0) {
+    FBCHK(d2h(e, out, last32, want));
+  } else {
+    for (int b = 0; b < B; ++b) {   // utterance b's rows from its slot of cap64 rows
+      const size_t n = sizeof(double) * (size_t)(row_off[b + 1] - row_off[b]) * xv.D;
+      FBCHK(d2h(e, (char *)out + sizeof(double) * (size_t)row_off[b] * xv.D, e->wb_xv_g.as<double>() + (size_t)b * cap64 * xv.D, n));
+    }
+  }
+  return sync_stream(e);
+}
+
+// Benchmark hook (tools/xvector_wb_rate.py): every launch of the TDNN backward on rows handed in, `reps` times between device
+// events after one launch to warm up, each on the inputs the whole backward left it
+extern "C" int fb_bench_xv_backward(fb_engine *e, const float *feats, const int *row_off, int B, int reps, double *ms_act, double *ms_affine,
+                                    double *ms_unsplice, double *ms_tail) {
+  if (!e || !feats || !row_off || !ms_act || !ms_affine || !ms_unsplice || !ms_tail || B <= 0 || reps <= 0) return fb_fail(FB_E_ARG, "bad argument");
+  if (!e->have_gmm || e->kind != 2) return fb_fail(FB_E_STATE, "load an x-vector system first");
+  const FbXvDev &xv = e->xv;
+  const int rows = row_off[B];
+  if (row_off[0] != 0 || rows <= 0) return fb_fail(FB_E_ARG, "bad row_off");
+  int cap64 = 1;
+  for (int b = 0; b < B; ++b) {
+    if (row_off[b + 1] < row_off[b]) return fb_fail(FB_E_ARG, "row_off must not descend");
+    cap64 = std::max(cap64, row_off[b + 1] - row_off[b]);
+  }
+  HIPCHK(hipSetDevice(e->device));
+  FBCHK(sync_stream(e));
+  e->cached_B = -1;
+  e->bench_it = e->nes_rec.iter = -1;
+  FBCHK(e->feats.ensure(sizeof(float) * (size_t)rows * xv.D));
+  FBCHK(e->row_off.ensure(sizeof(int) * (size_t)(B + 1)));
+  FBCHK(wb_xv_ensure(e, B, (size_t)rows, cap64));
+  FBCHK(h2d(e, e->feats.p, feats, sizeof(float) * (size_t)rows * xv.D));
+  FBCHK(h2d(e, e->row_off.p, row_off, sizeof(int) * (size_t)(B + 1)));
+  {  // cotangents on the embeddings: a fixed pattern of unit scale
+    std::vector<double> eb((size_t)B * xv.R);
+    for (size_t i = 0; i < eb.size(); ++i) eb[i] = (double)((int)((i * 2654435761u) >> 20 & 2047) - 1024) / 1024.0;
+    FBCHK(h2d(e, e->wb_xv_ebar.p, eb.data(), sizeof(double) * eb.size()));
+  }
+  FBCHK(run_xvector(e, B, rows, xv.n_layers + 1, nullptr, true));
+  wb_xv_backward(e, B, rows, 0, cap64, nullptr, nullptr);   // every buffer sized; every layer's G and amax have been written once
+  FBCHK(sync_stream(e));
+  hipStream_t s = e->stream;
+  hipEvent_t ev0, ev1;
+  HIPCHK(hipEventCreate(&ev0));
+  HIPCHK(hipEventCreate(&ev1));
+  auto timed = [&](auto &&launch, double *ms) -> int {
+    launch();
+    HIPCHK(hipEventRecord(ev0, s));
+    for (int i = 0; i < reps; ++i) launch();
+    HIPCHK(hipEventRecord(ev1, s));
+    HIPCHK(hipEventSynchronize(ev1));
+    float t = 0.0f;
+    HIPCHK(hipEventElapsedTime(&t, ev0, ev1));
+    *ms = (double)t / reps;
+    return FB_OK;
+  };
+  const int *ro = e->row_off.as<int>(), *n_rows = ro + B;
+  const int2 *rowinfo = e->xv_rowinfo.as<int2>();
+  int rc = timed([&] { fb_launch_wb_xv_segment_t(s, xv, e->wb_xv_ebar.as<double>(), B, e->wb_xv_sbar.as<double>(), nullptr); }, ms_tail + 0);
+  int cur = 0;
+  if (rc == FB_OK)
+    rc = timed([&] { fb_launch_wb_xv_pool_t(s, e->xv_act[(xv.n_layers - 1) & 1].as<float>(), xv.P, ro, B, e->xv_stats.as<double>(),
+                                            e->wb_xv_sbar.as<double>(), e->wb_xv_y[cur].as<float>(), nullptr); }, ms_tail + 1);
+  for (int l = xv.n_layers - 1; l >= 0 && rc == FB_OK; --l) {
+    const FbXvLayerDev &ly = xv.layer[l];
+    rc = timed([&] { fb_launch_wb_xv_act_t(s, ly, e->wb_xv_y[cur].as<float>(), e->xv_mask[l].as<unsigned char>(), n_rows, rows,
+                                           e->wb_xv_z.as<float>(), e->wb_xv_amax.as<float>(), nullptr); }, ms_act + l);
+    if (rc == FB_OK)
+      rc = timed([&] { fb_launch_wb_xv_affine_t(s, ly, e->wb_xv_z.as<float>(), e->wb_xv_amax.as<float>(), n_rows, rows, e->wb_xv_G.as<float>(), nullptr); },
+                 ms_affine + l);
+    if (rc == FB_OK)
+      rc = timed([&] { fb_launch_wb_xv_unsplice(s, ly, e->wb_xv_G.as<float>(), rowinfo, ro, B, n_rows, rows, l > 0 ? e->wb_xv_y[cur ^ 1].as<float>() : nullptr,
+                                                l > 0 ? nullptr : e->wb_xv_g.as<double>(), cap64, nullptr); }, ms_unsplice + l);
+    cur ^= 1;
+  }
+  (void)hipEventDestroy(ev0);
+  (void)hipEventDestroy(ev1);
+  return rc;
+}
+
+// Test hook: the ReLU decisions of layer `layer` for the batch scored last with its masks kept (a white-box call on an x-vector
+// system, fb_debug_xv_backward): [rows][dout] bytes, size-then-fill
+extern "C" int fb_debug_xv_masks(fb_engine *e, int layer, unsigned char *out, int64_t cap, int64_t *size) {
+  if (!e) return fb_fail(FB_E_ARG, "null engine");
+  if (!e->have_gmm || e->kind != 2) return fb_fail(FB_E_STATE, "load an x-vector system first");
+  if (layer < 0 || layer >= e->xv.n_layers) return fb_fail(FB_E_ARG, "layer %d outside 0 .. %d", layer, e->xv.n_layers - 1);
+  if (e->xv_mask_B <= 0) return fb_fail(FB_E_STATE, "no batch has been scored with its masks kept");
+  HIPCHK(hipSetDevice(e->device));
+  int rows = 0;
+  FBCHK(d2h(e, &rows, e->xv_mask_rows.p, sizeof(int)));
+  FBCHK(sync_stream(e));
+  const size_t n = (size_t)rows * (size_t)e->xv.layer[layer].dout;
+  if (n > e->xv_mask[layer].cap) return fb_fail(FB_E_STATE, "the kept masks are smaller than the batch's rows");
+  if (size) *size = (int64_t)n;
+  if (!out) return FB_OK;
+  if (cap < (int64_t)n) return fb_fail(FB_E_ARG, "out holds %lld bytes, the masks need %lld", (long long)cap, (long long)n);
+  FBCHK(d2h(e, out, e->xv_mask[layer].p, n));
+  return sync_stream(e);
 }
 
 extern "C" int fb_set_wb_universal(fb_engine *e, int on) {

@@ -765,6 +765,8 @@ struct FbXvLayerDev {
   int kw;                    // the image holds W * 2^-kw
   const unsigned short *w;   // fb_xv_frag_index images, one per column tile of 32 channels (fb_prepare.h)
   const float *bias, *scale, *offset;
+  int nt_steps, kwt;         // the transposed image (white-box backward): ceil(dout / 16) K steps, W' * 2^-kwt
+  const unsigned short *wt;  // ... one image per tile of 32 of the K columns
 };
 struct FbXvDev {
   int D, n_layers, P, R, max_width;
@@ -776,10 +778,30 @@ struct FbXvDev {
 void fb_launch_xv_rowinfo(hipStream_t s, const int *row_off, int B, int2 *rowinfo);
 // amax[row] = max |x[row][0 .. din)|
 void fb_launch_xv_rowmax(hipStream_t s, const float *x, int din, const int *n_rows_ptr, int rows_cap, float *amax);
-// one frame layer: y[row][dout] from x[row][din] (k_xv_affine)
+// one frame layer: y[row][dout] from x[row][din] (k_xv_affine); mask (nullable): mask[row][dout] = 1 where the layer's own
+// float32 z = W . splice + bias was > 0, else 0 (what the white-box backward differentiates the ReLU by)
 void fb_launch_xv_affine(hipStream_t s, const FbXvLayerDev &ly, const float *x, const float *amax, const int2 *rowinfo,
-                         const int *n_rows_ptr, int rows_cap, float *y);
+                         const int *n_rows_ptr, int rows_cap, float *y, unsigned char *mask = nullptr);
 // stats[b][2 P] = {mean, std} over the utterance's rows of h[row][P]
 void fb_launch_xv_pool(hipStream_t s, const float *h, int P, const int *row_off, int B, double *stats);
 // emb[b][R] = segT' stats[b] + seg_bias
 void fb_launch_xv_segment(hipStream_t s, const FbXvDev &xv, const double *stats, int B, double *emb);
+// ---- the TDNN's backward (whitebox_xv_kernels.hip; fb_set_wb_xvector in fakebob_hip.h).  stop (nullable): a set flag skips
+// the launch's work.  Rows are the batch's voiced rows, row_off / rowinfo the forward's.
+// sbar[b][2 P] = seg_W' ebar[b]: the cotangent on the statistics from the one on the embedding (float64)
+void fb_launch_wb_xv_segment_t(hipStream_t s, const FbXvDev &xv, const double *ebar, int B, double *sbar, const int *stop);
+// ybar[row][P] (float32) = mbar / T + sbar (h - mean) / (T std) where the variance floor is not active: the cotangent on the
+// last frame layer's output h from the one on its statistics
+void fb_launch_wb_xv_pool_t(hipStream_t s, const float *h, int P, const int *row_off, int B, const double *stats, const double *sbar,
+                            float *ybar, const int *stop);
+// zbar[row][dout] = ybar * bn_scale * mask, and amax[row] = max |zbar[row]|
+void fb_launch_wb_xv_act_t(hipStream_t s, const FbXvLayerDev &ly, const float *ybar, const unsigned char *mask, const int *n_rows_ptr,
+                           int rows_cap, float *zbar, float *amax, const int *stop);
+// G[row][K] = sum_c zbar[row][c] W[c][.] on the matrix cores (k_wb_xv_affine_t)
+void fb_launch_wb_xv_affine_t(hipStream_t s, const FbXvLayerDev &ly, const float *zbar, const float *amax, const int *n_rows_ptr,
+                              int rows_cap, float *G, const int *stop);
+// the splice transposed: xbar[t'][din] = sum_j sum_{t : clamp(t + ctx[j]) = t'} G[t][j din + .], j then t ascending, float64
+// sums rounded once.  out32 (layers above 0): [row][din] float32.  out64 (layer 0): utterance b's row t' at
+// out64[(b * cap64 + t') * din], float64 -- b found from row_off[0 .. B]
+void fb_launch_wb_xv_unsplice(hipStream_t s, const FbXvLayerDev &ly, const float *G, const int2 *rowinfo, const int *row_off, int B,
+                              const int *n_rows_ptr, int rows_cap, float *out32, double *out64, int cap64, const int *stop);

@@ -152,6 +152,11 @@ struct FbXvLayerPrepared {
   int kw = 0;                      // the image holds W * 2^-kw: max |W| 2^-kw in [2^14, 2^15) (0 for an all-zero layer)
   std::vector<uint16_t> w;         // [ceil(dout / 32)] tiles of fb_xv_frag_index, zeros past dout
   std::vector<float> bias, scale, offset;
+  // the transposed image, for the white-box backward (k_wb_xv_affine_t): W' as a [K][dout] matrix in the same layout -- the K
+  // columns of the forward are its "channels" ([ceil(K / 32)] tiles), dout its contraction (nt_steps = ceil(dout / 16))
+  int nt_steps = 0;
+  int kwt = 0;                     // the image holds W' * 2^-kwt, by kw's rule
+  std::vector<uint16_t> wt;
 };
 struct FbXvPrepared {
   int D = 0, n_layers = 0, P = 0, R = 0, max_width = 0;

@@ -1,5 +1,5 @@
 // fb_prepare_xvector.cpp -- what fb_load_xvector uploads, prepared on the host (fb_prepare.h): the argument checks of the
-// "x-vector" section of fakebob_hip.h, the frame layers' weights as k_xv_affine's f16 fragment images, the segment affine
+// "x-vector" section of fakebob_hip.h, the frame layers' weights as k_xv_affine's f16 fragment images (and, transposed, k_wb_xv_affine_t's), the segment affine
 // transposed in float64, and the back end's table (fb_iv_backend_table, shared with the i-vector loader).  No HIP.
 #include <math.h>
 #include <stdarg.h>
@@ -87,6 +87,24 @@ int fb_prepare_xvector(const fb_xvector_system *sy, FbXvPrepared *out, std::stri
         __builtin_memcpy(&ub, &b, 2);
         tile[fb_xv_frag_index(0, k, o % 32)] = ua;
         tile[fb_xv_frag_index(1, k, o % 32)] = ub;
+      }
+    }
+    // W transposed, the same two terms under the same power of two: channel place = a K column, K position = an output channel
+    q.nt_steps = (y.dout + 15) / 16;
+    q.kwt = q.kw;
+    const size_t per_tile_t = (size_t)q.nt_steps * 2 * 64 * 8;
+    q.wt.assign((size_t)((q.K + 31) / 32) * per_tile_t, 0);   // (zeros past K and past dout)
+    for (int k = 0; k < q.K; ++k) {
+      uint16_t *tile = q.wt.data() + (size_t)(k / 32) * per_tile_t;
+      for (int o = 0; o < y.dout; ++o) {
+        const float v = ldexpf(y.W[(size_t)o * q.K + k], -q.kwt);
+        const _Float16 a = (_Float16)v;
+        const _Float16 b = (_Float16)(v - (float)a);
+        uint16_t ua, ub;
+        __builtin_memcpy(&ua, &a, 2);
+        __builtin_memcpy(&ub, &b, 2);
+        tile[fb_xv_frag_index(0, o, k % 32)] = ua;
+        tile[fb_xv_frag_index(1, o, k % 32)] = ub;
       }
     }
     q.bias.assign(y.bias, y.bias + y.dout);

@@ -3,7 +3,7 @@
 //   k_xv_rowinfo   {first row, rows} of its utterance for every voiced row of the batch
 //   k_xv_rowmax    max |x| of every input row of a layer: what the per-row power of two of k_xv_affine is taken from
 //   k_xv_affine    one frame layer: splice, affine on the matrix cores (three f16 products per K step), bias / ReLU /
-//                  scale-offset epilogue
+//                  scale-offset epilogue; on request the ReLU's decisions, a byte per (row, channel)
 //   k_xv_pool      mean and standard deviation per (utterance, channel), float64
 //   k_xv_segment   the segment affine, float64
 // Every result is a function of the utterance's own rows and the layer's shape: no atomics, no order that depends on the
@@ -54,7 +54,7 @@ void fb_launch_xv_rowmax(hipStream_t s, const float *x, int din, const int *n_ro
 // global_load_dwordx4 per term.  The K order of an output element is ascending K step, the three products in that order.
 __global__ __launch_bounds__(256) void k_xv_affine(FbXvLayerDev ly, const float *__restrict__ x, const float *__restrict__ amax,
                                                    const int2 *__restrict__ rowinfo, const int *__restrict__ n_rows_ptr,
-                                                   float *__restrict__ y) {
+                                                   float *__restrict__ y, unsigned char *__restrict__ mask) {
   __shared__ u32x4 sA[XV_KS][XV_RT][2][64];      // 32 KB
   __shared__ int sSrc[XV_ROWS][FB_XV_MAX_CTX];   // source row of (row, context place); -1: the row does not exist
   __shared__ int sSh[XV_ROWS];                   // the row's values are multiplied by 2^-sSh
@@ -150,16 +150,18 @@ __global__ __launch_bounds__(256) void k_xv_affine(FbXvLayerDev ly, const float 
       const int m = rt * 32 + 8 * (i >> 2) + 4 * (lane >> 5) + (i & 3), g = row0 + m;
       if (g < n_rows) {
         float t = ldexpf(acc[rt][i], sSh[m] + ly.kw);
-        t = fmaxf(__fadd_rn(t, bias), 0.0f);
+        t = __fadd_rn(t, bias);
+        if (mask) mask[(size_t)g * ly.dout + ch] = t > 0.0f ? 1 : 0;   // the ReLU's decision, kept for the white-box backward
+        t = fmaxf(t, 0.0f);
         y[(size_t)g * ly.dout + ch] = __fadd_rn(__fmul_rn(sc, t), of);
       }
     }
 }
 void fb_launch_xv_affine(hipStream_t s, const FbXvLayerDev &ly, const float *x, const float *amax, const int2 *rowinfo,
-                         const int *n_rows_ptr, int rows_cap, float *y) {
+                         const int *n_rows_ptr, int rows_cap, float *y, unsigned char *mask) {
   if (rows_cap <= 0) return;
   const dim3 grid((rows_cap + XV_ROWS - 1) / XV_ROWS, (ly.dout + 32 * XV_CT - 1) / (32 * XV_CT));
-  hipLaunchKernelGGL(k_xv_affine, grid, dim3(256), 0, s, ly, x, amax, rowinfo, n_rows_ptr, y);
+  hipLaunchKernelGGL(k_xv_affine, grid, dim3(256), 0, s, ly, x, amax, rowinfo, n_rows_ptr, y, mask);
 }
 
 // One workgroup per (utterance, 64 channels): thread (q, c) sums quarter q of the utterance's rows, [T q / 4, T (q + 1) / 4),

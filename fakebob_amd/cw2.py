@@ -7,11 +7,13 @@ pseudo-code are in include/fakebob_hip.h), does not stop at the first success bu
 bisects the trade-off constant c over binary_search_steps runs of max_iter iterations each.  `confidence` is CW's kappa: it
 is FakeBob's adver_thresh, inside loss_fn.  Success is FakeBob's own test, adver_loss < 0 on the int16 row that was scored.
 
-Victims: an undefended GMM-UBM system; with ivector=True an i-vector-PLDA system (Engine.set_wb_ivector); with bpda=True a
+Victims: an undefended GMM-UBM system; with ivector=True an i-vector-PLDA system (Engine.set_wb_ivector); with xvector=True an
+x-vector (TDNN) system (Engine.set_wb_xvector; eot_size > 1 with bpda=True as on a GMM-UBM system); with bpda=True a
 victim behind an input-transform chain or a codec, and with eot_size = r > 1 the expectation over r draws of its random
 stages (Engine.set_wb_bpda, Engine.set_eot).  Companions, an air channel, feature compression and dither are refused by the
 engine in this version, whatever the other white-box switches say.
 """
+import functools
 import math
 import pickle
 import time
@@ -51,7 +53,18 @@ def snr_db(a0_i16, perturbation_i16):
     return 10.0 * math.log10(s / d) if s > 0.0 else float("-inf")
 
 
+def _takes_xvector(init):
+    """CW2.__init__ with one more keyword, xvector=False.  The constructor's own parameter list is what callers and the host
+    tests read with inspect.signature (functools.wraps keeps it so): the x-vector switch is a keyword-only extension to it."""
+    @functools.wraps(init)
+    def wrapper(self, *args, xvector=False, **kw):
+        self.xvector = bool(xvector)
+        return init(self, *args, **kw)
+    return wrapper
+
+
 class CW2(object):
+    @_takes_xvector
     def __init__(self, task, attack_type, model, confidence=0., initial_const=1e-3, binary_search_steps=9, max_iter=10000, lr=1e-2,
                  stop_early=True, stop_early_iter=1000, bpda=False, eot_size=1, ivector=False, seed=None, verbose=True):
         if task not in ("OSI", "CSI", "SV"):
@@ -60,10 +73,14 @@ class CW2(object):
             raise TypeError("CW2 differentiates this library's own systems: the model has no engine")
         if getattr(model, "task", task) != task:
             raise ValueError("model implements task %s, attack asked for %s" % (model.task, task))
-        if getattr(model.engine, "kind", "gmm") != "gmm" and not ivector:
+        kind = getattr(model.engine, "kind", "gmm")
+        xvector = getattr(self, "xvector", False)    # (_takes_xvector: the keyword-only xvector=True)
+        if kind == "xv" and not xvector:
+            raise ValueError("CW2: an x-vector system needs xvector=True (Engine.set_wb_xvector)")
+        if kind not in ("gmm", "xv") and not ivector:
             raise ValueError("CW2: an i-vector system needs ivector=True (Engine.set_wb_ivector)")
         check_cw2_params(initial_const, binary_search_steps, max_iter, lr, stop_early_iter, eot_size, bpda)
-        if getattr(model.engine, "kind", "gmm") != "gmm" and int(eot_size) > 1:
+        if kind not in ("gmm", "xv") and int(eot_size) > 1:
             raise ValueError("CW2: no expectation over transformation on an i-vector system (eot_size %d)" % int(eot_size))
         self.task = task
         self.attack_type = attack_type
@@ -87,6 +104,8 @@ class CW2(object):
         self._stream = 0
         if self.ivector:
             model.engine.set_wb_ivector(True)
+        if self.xvector:
+            model.engine.set_wb_xvector(True)
         if self.bpda:  # (left alone otherwise: the engine's own refusals then name what is set)
             model.engine.set_eot(self.eot_size)
             model.engine.set_wb_bpda(True)

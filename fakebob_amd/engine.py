@@ -92,6 +92,7 @@ class Engine(object):
         self.eot = 1
         self.wb_bpda = False
         self.wb_ivector = False
+        self.wb_xvector = False
         self.wb_air = False
         self.wb_frontend = False
         self.wb_universal = False
@@ -499,6 +500,47 @@ class Engine(object):
             return [out[off[b]:off[b + 1]].copy() for b in range(len(lst))]
         return out
 
+    def debug_xv_backward(self, mats, ebar, stage):
+        """The loaded x-vector system's chain on feature rows handed in, then the TDNN's backward from the embedding cotangents
+        ebar (B, R) down to `stage` (fb_debug_xv_backward): n_layers + 1 -> the cotangent on the statistics, (B, 2 P) float64;
+        n_layers -> on the last frame layer's output, a list of (T_b, P) float32; 1 .. n_layers - 1 -> on the input of that
+        layer, a list of (T_b, din) float32; 0 -> on the feature rows, a list of (T_b, feat_dim) float64."""
+        douts, P, R = self._xv_shape
+        lst = [np.ascontiguousarray(m, np.float32).reshape(-1, self.feat_dim) for m in mats]
+        off = np.zeros(len(lst) + 1, np.int32)
+        off[1:] = np.cumsum([m.shape[0] for m in lst])
+        cat = np.ascontiguousarray(np.concatenate(lst, axis=0))
+        ebar = np.ascontiguousarray(ebar, np.float64).reshape(len(lst), R)
+        stage, nl = int(stage), len(douts)
+        if stage > nl:
+            out = np.empty((len(lst), 2 * P), np.float64)
+        elif stage <= 0:
+            out = np.empty((cat.shape[0], self.feat_dim), np.float64)
+        else:
+            out = np.empty((cat.shape[0], douts[stage - 1]), np.float32)
+        N.check(self._L.fb_debug_xv_backward(self._h, N.ptr(cat), N.ptr(off), C.c_int(len(lst)), N.ptr(ebar), C.c_int(stage), N.ptr(out),
+                                             C.c_int64(out.nbytes)))
+        if stage > nl:
+            return out
+        return [out[off[b]:off[b + 1]].copy() for b in range(len(lst))]
+
+    def debug_xv_masks(self, layer):
+        """The ReLU decisions of frame layer `layer` for the batch scored last with them kept -- a white-box call on an x-vector
+        system, or debug_xv_backward (fb_debug_xv_masks) -> (rows, dout) uint8, 1 where the layer's float32 z was > 0."""
+        douts, _P, _R = self._xv_shape
+        size = C.c_int64()
+        N.check(self._L.fb_debug_xv_masks(self._h, C.c_int(int(layer)), None, C.c_int64(0), C.byref(size)))
+        out = np.empty(size.value, np.uint8)
+        N.check(self._L.fb_debug_xv_masks(self._h, C.c_int(int(layer)), N.ptr(out), C.c_int64(out.nbytes), C.byref(size)))
+        return out.reshape(-1, douts[int(layer)])
+
+    def debug_wb_xv_route(self):
+        """Launches of the TDNN backward the last white-box call (or debug_xv_backward) enqueued (fb_debug_wb_xv_route): a dict
+        backend_t, segment_t, pool_t, act_t, affine_t, unsplice -- the last three once per frame layer."""
+        info = (C.c_int * 6)()
+        N.check(self._L.fb_debug_wb_xv_route(self._h, info))
+        return dict(zip(("backend_t", "segment_t", "pool_t", "act_t", "affine_t", "unsplice"), [int(v) for v in info]))
+
     def bench_xvector(self, B, T, reps=10, seed=0):
         """fb_bench_xvector on B utterances of T seeded feature rows each -> a dict of milliseconds per launch: rowmax and
         affine (one entry per frame layer), pool, segment, backend."""
@@ -509,6 +551,18 @@ class Engine(object):
         rm, af, tail = np.zeros(len(douts)), np.zeros(len(douts)), np.zeros(3)
         N.check(self._L.fb_bench_xvector(self._h, N.ptr(cat), N.ptr(off), C.c_int(B), C.c_int(int(reps)), N.ptr(rm), N.ptr(af), N.ptr(tail)))
         return dict(rowmax=rm.tolist(), affine=af.tolist(), pool=float(tail[0]), segment=float(tail[1]), backend=float(tail[2]))
+
+    def bench_xv_backward(self, B, T, reps=10, seed=0):
+        """fb_bench_xv_backward on B utterances of T seeded feature rows each -> a dict of milliseconds per launch of the TDNN
+        backward: act_t, affine_t and unsplice (one entry per frame layer), segment_t, pool_t."""
+        douts, _P, _R = self._xv_shape
+        rng = np.random.default_rng(seed)
+        cat = (3.0 * rng.standard_normal((B * T, self.feat_dim), dtype=np.float32))
+        off = (np.arange(B + 1, dtype=np.int64) * T).astype(np.int32)
+        ac, af, us, tail = np.zeros(len(douts)), np.zeros(len(douts)), np.zeros(len(douts)), np.zeros(2)
+        N.check(self._L.fb_bench_xv_backward(self._h, N.ptr(cat), N.ptr(off), C.c_int(B), C.c_int(int(reps)), N.ptr(ac), N.ptr(af), N.ptr(us),
+                                             N.ptr(tail)))
+        return dict(act_t=ac.tolist(), affine_t=af.tolist(), unsplice=us.tolist(), segment_t=float(tail[0]), pool_t=float(tail[1]))
 
     def gmm_acc_stats(self, wav):
         """UBM (loaded alone) posterior statistics of one utterance: occ[C], F[C,D] (float64), voiced frames."""
@@ -726,6 +780,15 @@ class Engine(object):
         N.check(self._L.fb_set_wb_ivector(self._h, C.c_int(1 if on is True else 0 if on is False else int(on))))
         self.wb_ivector = bool(on)
 
+    def set_wb_xvector(self, on):
+        """fb_set_wb_xvector: with True, get_grad_wb, attack_wb, attack_cw2 and attack_psy differentiate through a loaded
+        x-vector (TDNN) system -- the forward's ReLU and pooling-floor decisions held constant: the rules are in
+        include/fakebob_hip.h --, undefended, or with set_wb_bpda(True) through a chain, a codec and set_eot(r).  An air channel,
+        dither, companions and a play offset stay refused.  False (as created): an x-vector system is refused and nothing else
+        changes; the other kinds run the same launches either way."""
+        N.check(self._L.fb_set_wb_xvector(self._h, C.c_int(1 if on is True else 0 if on is False else int(on))))
+        self.wb_xvector = bool(on)
+
     def set_wb_air(self, on):
         """fb_set_wb_air: with True, get_grad_wb and attack_wb differentiate through the over-the-air channel of
         set_air_channel -- the forward's own drawn responses transposed, a saturated output passing zero; with set_eot(r) the
@@ -892,6 +955,7 @@ class Engine(object):
         random stages of a defended victim.  Refused (NativeError, FB_E_STATE) for i-vector systems and while an air channel,
         feature compression, dither or companions are set; an input transform, a codec and EOT only after set_wb_bpda(True).
         After set_wb_ivector(True) an i-vector system is differentiated as well (never with set_eot > 1); after
+        set_wb_xvector(True) an x-vector system is (undefended, or with set_wb_bpda(True) through a chain, a codec and EOT); after
         set_wb_air(True) an air channel is too (the forward's drawn responses transposed); after set_wb_frontend(True) feature
         compression and dither are (the forward's final assignment and its dither draws held constant); after
         set_wb_universal(True) companions are: the gradient of the mean loss over the K utterances, a_0 of the composition being
@@ -922,7 +986,8 @@ class Engine(object):
     def attack_wb(self, params, audio):
         """fb_attack_wb: FakeBob.attack's loop with the analytic gradient in place of the NES estimate (momentum = 0: PGD
         with the margin loss; max_iter = 1: the single-step attack) -> (int16 adv, flag, float64 adv, trace), as attack.
-        GMM-UBM systems; i-vector systems after set_wb_ivector(True), with the same loop, trace layout and stop test."""
+        GMM-UBM systems; i-vector systems after set_wb_ivector(True) and x-vector systems after set_wb_xvector(True), with the
+        same loop, trace layout and stop test."""
         audio = np.ascontiguousarray(audio, np.float64).reshape(-1)
         n, S = audio.size, max(self.n_speakers, 1)
         adv = np.empty(n, np.int16)

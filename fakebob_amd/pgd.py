@@ -14,7 +14,9 @@ unless universal=True (Engine.set_wb_universal: attack(..., companions=[...]) th
 the utterances -- the white-box twin of FakeBob.attack(..., companions=)); refused as well are i-vector
 systems and foreign models -- the gradient is that of this library's own forward.  IvectorPGD is the same attack on an i-vector-PLDA system (Engine.set_wb_ivector): the
 gradient through the PLDA back end, both length normalisations, the posterior solve and the full-covariance posteriors, with
-the frames' component selection and pruned sets held constant; PGD and AdaptivePGD keep refusing such a system.
+the frames' component selection and pruned sets held constant; PGD and AdaptivePGD keep refusing such a system.  XvectorPGD
+is the same attack on an x-vector (TDNN) system (Engine.set_wb_xvector): the gradient through the PLDA back end, the segment
+affine, statistics pooling and every frame layer, with the forward's ReLU and variance-floor decisions held constant.
 """
 import pickle
 import time
@@ -37,6 +39,8 @@ class PGD(object):
         if getattr(model, "task", task) != task:
             raise ValueError("model implements task %s, attack asked for %s" % (model.task, task))
         if getattr(model.engine, "kind", "gmm") not in self.KINDS:
+            if getattr(model.engine, "kind", "gmm") == "xv":
+                raise ValueError("%s: an x-vector system needs XvectorPGD (Engine.set_wb_xvector)" % type(self).__name__)
             raise ValueError("PGD: i-vector systems are out of this version (GMM-UBM systems only)")
         self.bpda = False   # (AdaptivePGD: True -- the engine's switch is on and seed / stream key the victim's draws)
         self.air = False    # (air=True of AdaptivePGD / IvectorPGD: Engine.set_wb_air is on; seed / stream key the rooms)
@@ -275,3 +279,28 @@ class IvectorPGD(PGD):
             if self.bpda:
                 model.engine.set_eot(eot_size)
         self._set_play_offset(play_offset)
+
+
+class XvectorPGD(PGD):
+    """PGD on an x-vector (TDNN) victim (and, unchanged, on a GMM-UBM one).  The constructor switches the model's engine to
+    differentiate through the TDNN (Engine.set_wb_xvector; the rules are in include/fakebob_hip.h) and, with bpda=True, through
+    an input-transform chain and a codec as well (Engine.set_wb_bpda), eot_size = r then taking the mean loss and gradient over
+    r draws of the random stages per iteration (Engine.set_eot); all stay set.  An air channel, dither, companions and a play
+    offset are refused by the engine on this victim.  Knobs, attack(), get_grad(), estimate_threshold(), the return pair and the
+    checkpoint layout are PGD's."""
+    KINDS = ("gmm", "xv")
+
+    def __init__(self, task, attack_type, model, bpda=False, eot_size=1, **kw):
+        eot_size = int(eot_size)
+        if not 1 <= eot_size <= 32:
+            raise ValueError("XvectorPGD: eot_size %d outside 1 .. 32" % eot_size)
+        if eot_size > 1 and not bpda:
+            raise ValueError("XvectorPGD: eot_size %d needs bpda=True (expectation over transformation is part of the "
+                             "adaptive attack)" % eot_size)
+        PGD.__init__(self, task, attack_type, model, **kw)
+        self.bpda = bool(bpda)
+        model.engine.set_wb_xvector(True)
+        if self.bpda:
+            self.eot_size = eot_size
+            model.engine.set_eot(eot_size)
+            model.engine.set_wb_bpda(True)

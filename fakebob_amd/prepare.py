@@ -55,10 +55,10 @@ def ivector_buffer(system, name):
 
 def xvector_buffer(system, name):
     """of a models.XvectorSystem: "w<l>" (uint16: layer l's f16 fragment image), "kw" (int32), "segT", "backend" (float64),
-    "backend_offsets" (int64)"""
+    "backend_offsets" (int64); "wt<l>" (uint16: layer l's transposed image, the white-box backward's) and "kwt" (int32)"""
     sy, keep = N.xvector_struct(system)
     L = N.lib()
-    dtype = np.uint16 if name.startswith("w") else {"kw": np.int32, "backend_offsets": np.int64}.get(name, np.float64)
+    dtype = np.uint16 if name.startswith("w") else {"kw": np.int32, "kwt": np.int32, "backend_offsets": np.int64}.get(name, np.float64)
     return _fetch(lambda out, cap, size: L.fb_debug_prepare_xvector(C.byref(sy), name.encode(), out, cap, size), dtype)
 
 

@@ -42,6 +42,7 @@
  *   fb_attack_psy             (none in FAKEBOB: that attack with Qin et al.'s psychoacoustic masking loss as the distortion)
  *   fb_set_wb_bpda / fb_get_grad_wb_iter   (none in FAKEBOB: the adaptive form of those attacks on a DEFENDED victim -- BPDA
  *                             through the input-transform chain and the codec, EOT over the random stages)
+ *   fb_set_wb_xvector         (none in FAKEBOB: the same white-box calls on an x-vector system, the ReLU and pooling-floor decisions held constant)
  *   fb_set_wb_ivector         (none in FAKEBOB: the same white-box calls on an i-vector-PLDA system, the frames' component
  *                             selection and pruned sets held constant)
  *   fb_get_grad_ext / fb_attack_ext   the same around a foreign `model` (README.md:136)
@@ -878,9 +879,46 @@ int fb_set_query_eot(fb_engine *e, int quorum);   /* 0 off (default) | -1 majori
  * Refused for an i-vector system with the switch on, FB_E_STATE, the cause named: companions (unless fb_set_wb_universal), an air channel (unless fb_set_wb_air), feature
  * compression and dither > 0 (unless fb_set_wb_frontend), and fb_set_eot(r > 1) -- the last with fb_set_wb_bpda on as well ("i-vector", "fb_set_eot": the
  * forward keeps one row's i-vector state, not r replicas' -- unless fb_set_wb_universal, "Universal perturbations" above).  An input-transform chain and a codec need fb_set_wb_bpda(e, 1), as
- * for a GMM-UBM system, and are then taken at r = 1.  FB_E_NO_VOICED and the "not positive definite" error are scoring's. */
+ * for a GMM-UBM system, and are then taken at r = 1.  FB_E_NO_VOICED and the "not positive definite" error are scoring's.
+ *
+ * The x-vector (TDNN) victim (fb_set_wb_xvector).  A sixth switch, for the same reason as the others: fb_set_wb_xvector(e, on),
+ * on = 0 or 1 (anything else: FB_E_ARG, the setting stays), 0 at engine creation, kept across fb_load_*.  With 0 every call,
+ * launch, value and message is what it was before the switch existed: an x-vector system is refused ("not in this version").
+ * With 1 the other two kinds still take the very same launches, and fb_get_grad_wb, fb_get_grad_wb_iter, fb_get_grad_wb_from,
+ * fb_attack_wb, fb_attack_cw2 and fb_attack_psy accept a loaded x-vector system, all three tasks and both attack types.  The
+ * function that is differentiated is the engine's own forward ("x-vector (TDNN) system" below); its hard decisions are
+ * constants:
+ *  - the front end as above: straight-through cast, the voiced mask held constant, an active floor contributes zero;
+ *  - frame layer: the derivative of max(z, 0) is 1 where the forward's own float32 z = W . splice + bias was > 0, else 0.  The
+ *    decision is the one the forward took -- k_xv_affine writes a byte per (row, channel) when the scoring call asks for it --,
+ *    not one re-derived from the output: y == bn_offset does not imply z <= 0 once bn_scale * t is absorbed by the offset.  A
+ *    replicated edge row (clamp(t + ctx[j], 0, T - 1)) receives the cotangents of every place that read it;
+ *  - pooling: the mean passes mbar / T; the standard deviation passes sbar (h - mean) / (T std) where E[h^2] - mean^2 > 1e-10
+ *    and nothing where the floor is active -- every channel of a one-row utterance;
+ *  - embedding to back end: the rounding to float32 is straight-through (k_wb_iv_backend_t treats it so); the back end, the
+ *    z-norm and loss_fn as for the i-vector victim.
+ * Backward: the weights (k_wb_iv_ctl; k_wb_iv_ctl_rep per replica) and ebar = d (sum_s w_s LLR_s) / d embedding
+ * (k_wb_iv_backend_t) per replica, float64; then ONE pass over all voiced rows of the batch, as the forward runs:
+ * sbar = seg_W' ebar (k_wb_xv_segment_t, float64); the pooling rule (k_wb_xv_pool_t, float64, rounded once to the float32
+ * cotangent on the last layer's output); per frame layer, last to first, zbar = ybar * bn_scale * mask (k_wb_xv_act_t, one
+ * rounding per multiplication, and max |zbar| of every row), G[t][n] = sum_c zbar[t][c] W[c][n] over the layer's n_ctx * din
+ * columns (k_wb_xv_affine_t) and xbar[t'][d] = sum_j sum_{t : clamp(t + ctx[j], 0, T - 1) = t'} G[t][j din + d], j ascending
+ * and then t ascending, summed in float64 and rounded once (k_wb_xv_unsplice; layer 0 hands its float64 sums to the front-end
+ * backward unrounded).  Arithmetic of the transposed affine: the forward's -- the cotangent row as two f16 terms under a power
+ * of two of its own row, W' as two f16 terms under one power of two per layer chosen at load time, three products per K step on
+ * the matrix cores, float32 accumulation in an order that depends on the layer's shape alone.  Cotangents between frame
+ * layers are float32; there are no floating-point atomics.  Hence (a) a run repeats bit for bit, and (b) the cotangent on an
+ * utterance's feature rows does not depend on the batch the utterance sits in.  adver_loss and score0 are bit for bit
+ * fb_get_grad's at samples_per_draw = 0: the same scoring call.
+ * With fb_set_wb_bpda(e, 1) as well an x-vector system is differentiated through an input-transform chain, through a codec
+ * and under fb_set_eot(r): the r replicas' embeddings each get their cotangent, the one TDNN backward runs over all r * T rows,
+ * and the front-end backward and the chain's transpose follow per replica, summed ascending.  Refused for an x-vector system,
+ * FB_E_STATE, the cause named, whatever their own switches say: an air channel, dither > 0, companions and a play offset;
+ * fb_set_eot(r > 1), a chain and a codec without fb_set_wb_bpda as for a GMM-UBM system.  Feature compression cannot be on with
+ * this system at all. */
 int fb_set_wb_bpda(fb_engine *e, int on);
 int fb_set_wb_ivector(fb_engine *e, int on);
+int fb_set_wb_xvector(fb_engine *e, int on);
 int fb_set_wb_air(fb_engine *e, int on);
 int fb_set_wb_frontend(fb_engine *e, int on);
 int fb_set_wb_universal(fb_engine *e, int on);
@@ -1072,7 +1110,8 @@ int fb_load_ivector(fb_engine *e, const fb_ivector_system *sys, int task);
  * n_ctx * din whatever it is; R a multiple of 32 in 32 .. 2048; L <= 512; S <= 60
  * (SV: S == 1); lda_cols R or R + 1.  Anything else is FB_E_ARG by name and the system loaded before stays loaded.
  * Refused by name ("not in this version") while an x-vector system is loaded: every white-box entry (fb_get_grad_wb*,
- * fb_attack_wb, fb_attack_cw2, fb_attack_psy) whatever the fb_set_wb_* switches say, fb_set_feature_compression with
+ * fb_attack_wb, fb_attack_cw2, fb_attack_psy) unless fb_set_wb_xvector(e, 1) ("white-box gradients" above: the analytic
+ * gradient through the TDNN) -- the other fb_set_wb_* switches do not admit it --, fb_set_feature_compression with
  * iters > 0 (k-means discards the frame order a TDNN reads; fb_load_xvector is refused likewise while it is on) and
  * fb_gmm_acc_stats.  fb_last_ivectors returns the embeddings (B x R, float64) of the batch scored last. */
 #define FB_XV_MAX_LAYERS 8

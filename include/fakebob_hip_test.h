@@ -327,7 +327,9 @@ int fb_debug_prepare_frontend(const fb_frontend_cfg *c, const char *buffer, void
  * uint16 f16 bits [ceil(dout / 32)][ceil(n_ctx * din / 16)][2 terms][64 lanes][8], lane 32 h + c of K step s holding
  * W[32 tile + c][16 s + 8 h .. + 7] * 2^-kw (zero past n_ctx * din and past dout), term 0 = f16(v), term 1 = f16(v - term 0) --,
  * "kw" (int32[n_layers], the layers' powers of two), "segT" (float64 [2 P][R], seg_W transposed), "backend" and
- * "backend_offsets" as for an i-vector system. */
+ * "backend_offsets" as for an i-vector system; "wt<l>" -- layer l's weights transposed, as k_wb_xv_affine_t reads them: the
+ * same layout for the [n_ctx * din][dout] matrix W', [ceil(n_ctx * din / 32)][ceil(dout / 16)][2 terms][64 lanes][8], lane
+ * 32 h + c of K step s holding W[16 s + 8 h .. + 7][32 tile + c] * 2^-kwt --, "kwt" (int32[n_layers]). */
 int fb_debug_prepare_xvector(const fb_xvector_system *sy, const char *buffer, void *out, int64_t cap, int64_t *size);
 
 /* The x-vector chain of the loaded system on feature rows handed in as they are (no front end): feats[row_off[B]][D]
@@ -335,6 +337,33 @@ int fb_debug_prepare_xvector(const fb_xvector_system *sy, const char *buffer, vo
  * [rows][dout]; layer == n_layers: the pooled statistics, float64 [B][2 P]; layer == n_layers + 1: the embeddings,
  * float64 [B][R]. */
 int fb_debug_xv_embed(fb_engine *e, const float *feats, const int *row_off, int B, int layer, void *out);
+/* White-box gradients through the TDNN (fakebob_hip.h: fb_set_wb_xvector; the switch need not be on for the hooks).
+ * fb_debug_xv_backward: the chain on handed-in rows as fb_debug_xv_embed runs it, every layer's ReLU decisions kept, then the
+ * backward from the cotangents ebar[B][R] on the embeddings down to `stage`: n_layers + 1 -- the cotangent on the statistics,
+ * float64 [B][2 P]; n_layers -- on the last frame layer's output, float32 [rows][P]; l in 1 .. n_layers - 1 -- on the input of
+ * layer l, float32 [rows][din_l]; 0 -- on the feature rows, float64 [rows][D].  cap: bytes out holds.
+ * fb_debug_xv_masks: the ReLU decisions of frame layer `layer` for the batch scored last with them kept (any white-box call on
+ * an x-vector system, fb_debug_xv_backward), bytes [rows][dout], 1 where z > 0; size-then-fill (out NULL: *size only).
+ * fb_debug_wb_xv_route: info[FB_WB_XV_ROUTE_N] counts the launches of the TDNN backward the last white-box call (or
+ * fb_debug_xv_backward) enqueued; fb_debug_wb_route's keys are as they were (an x-vector system counts its weights under
+ * FB_WB_ROUTE_IV_CTL / FB_WB_ROUTE_CTL_REP, the front-end backward and the chain under theirs). */
+#define FB_WB_XV_ROUTE_BACKEND_T 0  /* k_wb_iv_backend_t at a replica's embedding */
+#define FB_WB_XV_ROUTE_SEGMENT_T 1  /* k_wb_xv_segment_t: once per call, all replicas */
+#define FB_WB_XV_ROUTE_POOL_T 2     /* k_wb_xv_pool_t: once per call */
+#define FB_WB_XV_ROUTE_ACT_T 3      /* k_wb_xv_act_t: once per frame layer */
+#define FB_WB_XV_ROUTE_AFFINE_T 4   /* k_wb_xv_affine_t: once per frame layer */
+#define FB_WB_XV_ROUTE_UNSPLICE 5   /* k_wb_xv_unsplice: once per frame layer */
+#define FB_WB_XV_ROUTE_N 6
+int fb_debug_xv_backward(fb_engine *e, const float *feats, const int *row_off, int B, const double *ebar /*[B][R]*/, int stage,
+                         void *out, int64_t cap);
+int fb_debug_xv_masks(fb_engine *e, int layer, unsigned char *out, int64_t cap, int64_t *size);
+int fb_debug_wb_xv_route(fb_engine *e, int *info);
+/* Benchmark hook: the launches of the TDNN backward one by one on rows handed in (the forward with its masks kept and one whole
+ * backward first), each `reps` times between device events after one launch to warm up, milliseconds per launch: ms_act[l],
+ * ms_affine[l] and ms_unsplice[l] (k_wb_xv_act_t, k_wb_xv_affine_t, k_wb_xv_unsplice of frame layer l), ms_tail[2]
+ * (k_wb_xv_segment_t, k_wb_xv_pool_t). */
+int fb_bench_xv_backward(fb_engine *e, const float *feats, const int *row_off, int B, int reps, double *ms_act, double *ms_affine,
+                         double *ms_unsplice, double *ms_tail);
 /* Benchmark hook: the launches of that chain one by one, each `reps` times between device events after one launch to warm
  * up, milliseconds per launch: ms_rowmax[l] and ms_affine[l] (k_xv_rowmax, k_xv_affine of frame layer l), ms_tail[3]
  * (k_xv_pool, k_xv_segment, k_iv_backend). */
